@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the fpng encode hot path (and of the GPU decoder on the encoder's output) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|4k|1080p] [--batch B] [--flags F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|4k|1080p] [--batch B] [--flags F] [--dump-outputs DIR]
 
 A "step" is one submission of the hot path (fpng_encode_image_to_memory semantics, 1-pass) over a
 batch of B synthetic device-resident images; inputs and outputs live in HBM for the whole timed
@@ -12,6 +12,11 @@ region (no PCIe).  Default workload: the configuration BASELINE.json's metric is
 With --gpus N > 1 (launched by torch.distributed.run, one rank per GPU) every rank encodes its own
 batch (images are independent objects: no data-path collective), time is max over ranks,
 value = all ranks' pixels / that time, scaling = weak.
+
+--steps K times exactly K steps (one timed region; --regions R times R regions of K steps each), and
+`ms_per_step` is the time of one of them.  --dump-outputs DIR writes what the last timed step
+computed (the PNG files a caller receives: sizes, modes, statuses, CRC-32s and a fixed sample of
+their bytes) as DIR/<name>.npy, so that two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line, including
   roofline     : dominant kernel's algorithmic bytes / its HIP-event-measured duration vs 8 TB/s
@@ -58,9 +63,11 @@ def parse():
     ap.add_argument("--pipelines", type=int, default=0, help="--mode nodeimage: devices of the node (default: every visible GPU; on a one-GPU box "
                     "device 0 listed this many times)")
     ap.add_argument("--decode-steps", type=int, default=20, help="timed decode steps per region (the `decode` object / --mode decode)")
-    ap.add_argument("--regions", type=int, default=3,
-                    help="timed regions per run, each EXACTLY --steps steps between two barriers; value = the median region, "
-                         "`runs` / `spread` report all of them (a single 10 ms region cannot show a 5 %% change)")
+    ap.add_argument("--regions", type=int, default=1,
+                    help="timed regions per run, each EXACTLY --steps steps between two barriers (regions x steps timed steps in all); "
+                         "value = the median region, `runs` / `spread` report all of them (a single 10 ms region cannot show a 5 %% change)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="--mode batch: write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--end-to-end-only", default=None, choices=["cabi", "dropin"], help="(internal) print that part of the end_to_end object for --workload WxHxC and exit")
     ap.add_argument("--device", type=int, default=0)
@@ -231,6 +238,43 @@ def verify_outputs(args, rank, w, h, c, outs, sizes):
             raise SystemExit(f"bench.py: PARITY FAILURE, the {len(outs)} files' digests do not hash to the reference's {want_all[1]}")
         n = len(outs)
     return n or None
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy files in all, headers included (64 MB is the cap)
+NPY_HEADER = 128  # bytes of the header np.save writes in front of each of these arrays
+
+
+def dump_per_file(n):
+    """--dump-outputs: bytes of each of n files that fit the budget (each one costs a float32 value + a float64 index)."""
+    return max(0, (DUMP_BUDGET - (2 * n + 1) * NPY_HEADER - 32 * n) // max(1, n) // 12)
+
+
+def dump_outputs(dirname, outs, res, rank, world):
+    """--dump-outputs: the B files of the last timed step, as a caller of the encoder receives them.
+      png_info.npy         float64 [B, 4]: size in bytes, mode, status, zlib CRC-32 of the whole file
+      png_<i>.npy          float32 [n]: bytes of file i at the positions in png_<i>_index.npy -- the whole file when every
+      png_<i>_index.npy    float64 [n]  file fits the budget, else its first and last `edge` bytes plus a fixed, seeded sample
+                                        (edge = a quarter of the file's share of the budget, at most 4096), n <= dump_per_file(B)
+    With --gpus N > 1 every rank writes its own files, names prefixed rank<r>_."""
+    import zlib
+    os.makedirs(dirname, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    sizes = [int(r[0]) for r in res]
+    per_file = dump_per_file(len(outs))
+    info = np.zeros((len(outs), 4), dtype=np.float64)
+    for i, (out, r) in enumerate(zip(outs, res)):
+        data = out[: sizes[i]].cpu().numpy()
+        info[i] = (sizes[i], r[1], r[2], zlib.crc32(data))
+        if sizes[i] <= per_file:
+            idx = np.arange(sizes[i], dtype=np.int64)
+        else:
+            rng = np.random.default_rng(1000 + i)
+            e = min(4096, per_file // 4)  # (sizes[i] > per_file >= 2 e: the two ends do not overlap)
+            edge = np.r_[np.arange(e), np.arange(sizes[i] - e, sizes[i])]
+            idx = np.unique(np.r_[edge, rng.integers(0, sizes[i], per_file - edge.size)]).astype(np.int64)
+        np.save(os.path.join(dirname, f"{pre}png_{i}.npy"), data[idx].astype(np.float32))
+        np.save(os.path.join(dirname, f"{pre}png_{i}_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, f"{pre}png_info.npy"), info)
 
 
 def _cpu_worker(task):
@@ -624,6 +668,10 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s): n_gpus would not be what the command says")
     if args.dry_launch:
         return dry_launch(args, rank, world)
+    if args.dump_outputs and args.mode != "batch":
+        raise SystemExit("--dump-outputs: --mode batch only")
+    if args.dump_outputs and dump_per_file(args.batch) < 1:
+        raise SystemExit(f"--dump-outputs: {args.batch} files do not fit {DUMP_BUDGET} bytes")
     import fpng_amd  # (before the first HIP call of the process: loading the library sets the runtime's hardware queues, csrc/api.cpp runtime_defaults())
     torch.cuda.set_device(local_rank)
     if distributed:
@@ -714,6 +762,8 @@ def main():
     # self-check: EVERY image of the last timed submission's output set against the reference's bytes
     # (tests/golden/batches.json / kat.json: sha256 of the unmodified reference encoder's file for this input)
     parity_checked = verify_outputs(args, rank, w, h, c, out_sets[(args.steps - 1) % n_sets], [r[0] for r in res])
+    if args.dump_outputs:  # (before the profiling steps below, which write into out_sets[0])
+        dump_outputs(args.dump_outputs, out_sets[(args.steps - 1) % n_sets], res, rank, world)
     pixels_per_step = B * w * h
     value = world * pixels_per_step * args.steps / elapsed / 1e6
     run_values = [round(world * pixels_per_step * args.steps / r / 1e6, 1) for r in runs]
@@ -757,13 +807,14 @@ def main():
         "parity_images": parity_checked, "runs": run_values,
         "spread": round((max(run_values) - min(run_values)) / value, 4) if len(run_values) > 1 else None,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4), "per_rank_ms_per_step": per_rank_ms, "higher_is_better": True, "scaling": "weak",
+        "regions": max(1, args.regions), "timed_steps": max(1, args.regions) * args.steps,
         "vs_baseline": None, "dtype": "u8", "data": "synthetic",
         "config": {"workload": f"{B} x {w}x{h} {'RGBA' if c == 4 else 'RGB'} '{args.kind}' frames per GPU per step, "
                                f"flags={args.flags}, bit-exact fpng PNG output", "batch_per_gpu": B,
                    "width": w, "height": h, "channels": c, "png_bytes_per_step_per_gpu": png_bytes,
                    "parallelism": f"images sharded over {world} GPU(s), no data-path collective",
-                   # how the submissions' chains share the GPU (fpng_amd_runtime_info(): the library asks the HIP runtime for eight hardware
-                   # queues when it is loaded before the process's first HIP call; a process that comes too late runs two lanes over four)
+                   # how the submissions' chains share the GPU (fpng_amd_runtime_info(): the library asks the HIP runtime for two hardware
+                   # queues when it is loaded before the process's first HIP call, unless the variable is set already)
                    "lanes": enc.lanes, "hw_queues": rt["hw_queues"], "hw_queue_source": rt["hw_queue_source"]},
         "roofline": roofline,
     }

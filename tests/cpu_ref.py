@@ -2,8 +2,8 @@
 
 `oracle`  : oracle/libfpng_oracle.so  -- the row-local C restatement (always available; built by
             __graft_entry__.build() / `make -C oracle`).
-`ref`     : oracle/_ref/libfpng_ref.so -- the UNMODIFIED reference compiled from /root/reference
-            (present in the dev container and, as a prebuilt file, on the GPU box).
+`ref`     : oracle/_ref/libfpng_ref.so -- the UNMODIFIED reference, compiled by oracle/Makefile where its sources are
+            at hand; elsewhere its recorded encode / decode answers (tests/golden/ref_answers.npz).
 """
 import ctypes as C
 import os
@@ -175,6 +175,13 @@ class _Ref:
         ok = self.L.ref_encode(img.ctypes.data, w, h, c, flags, out.ctypes.data, cap, C.byref(n))
         return out[: n.value].tobytes() if ok else None
 
+    def get_info(self, png):
+        """fpng_get_info -> (status, w, h, c)"""
+        b = np.frombuffer(bytes(png), dtype=np.uint8)
+        w, h, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        st = self.L.ref_get_info(b.ctypes.data, b.size, C.byref(w), C.byref(h), C.byref(c))
+        return st, w.value, h.value, c.value
+
     def decode(self, png, desired):
         b = np.frombuffer(png, dtype=np.uint8)
         w, h, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
@@ -211,15 +218,134 @@ def oracle():
 
 
 def have_ref():
-    return os.path.exists(os.path.join(ORACLE_DIR, "_ref", "libfpng_ref.so")) or os.path.exists(
-        "/root/reference/src/fpng.cpp")
+    """The reference build itself (oracle/_ref, made by build() where the reference's sources are at hand)."""
+    return os.path.exists(os.path.join(ORACLE_DIR, "_ref", "libfpng_ref.so"))
+
+
+ANSWERS = os.path.join(ROOT, "tests", "golden", "ref_answers.npz")
+
+
+def have_ref_answers():
+    """ref().encode / ref().decode can be answered: by the reference build, or else by its recorded answers."""
+    return have_ref() or os.path.exists(ANSWERS)
 
 
 def ref():
     global _ref
     if _ref is None:
-        _ref = _Ref()
+        if os.environ.get("FPNG_RECORD_REF_ANSWERS"):
+            _ref = _RecordingRef(_Ref())
+        elif have_ref():
+            _ref = _Ref()
+        else:
+            _ref = _RecordedRef()
     return _ref
+
+
+# ---------------------------------------------------------------------------------------------
+# The reference's answers, recorded (tests/golden/ref_answers.npz, oracle/make_golden_ref_answers.py)
+# ---------------------------------------------------------------------------------------------
+def _digest(*parts):
+    import hashlib
+    h = hashlib.blake2b(digest_size=16)
+    for p in parts:
+        h.update(p if isinstance(p, (bytes, bytearray, memoryview)) else np.ascontiguousarray(p).tobytes())
+    return h.digest()
+
+
+def _encode_key(img, w, h, c, flags):
+    return _digest(b"E", np.array([w, h, c, flags], dtype=np.int64), np.ascontiguousarray(img, dtype=np.uint8))
+
+
+def _decode_key(png, desired):
+    return _digest(b"D", np.array([desired], dtype=np.int64), bytes(png))
+
+
+def _info_key(png):
+    return _digest(b"I", bytes(png))
+
+
+class _RecordingRef:
+    """FPNG_RECORD_REF_ANSWERS=1: the reference answers, and every encode / decode call's answer is kept (size or status and
+    dimensions, a digest of the bytes) and merged into tests/golden/ref_answers.npz when the process ends."""
+
+    def __init__(self, real):
+        import atexit
+        self.real, self.L, self.rows = real, real.L, {}
+        atexit.register(self.save)
+
+    def encode(self, img, w, h, c, flags=0):
+        png = self.real.encode(img, w, h, c, flags)
+        self.rows[_encode_key(img, w, h, c, flags)] = ((-1, 0, 0, 0), b"\0" * 16) if png is None else ((len(png), 0, 0, 0), _digest(png))
+        return png
+
+    def get_info(self, png):
+        info = self.real.get_info(png)
+        self.rows[_info_key(png)] = (info, b"\0" * 16)
+        return info
+
+    def decode(self, png, desired):
+        st, out, w, h, c = self.real.decode(png, desired)
+        self.rows[_decode_key(png, desired)] = ((st, w, h, c), _digest(out) if st == 0 else b"\0" * 16)
+        return st, out, w, h, c
+
+    def __getattr__(self, name):
+        return getattr(self.real, name)
+
+    def save(self):
+        rows = dict(_load_answers()) if os.path.exists(ANSWERS) else {}
+        rows.update(self.rows)
+        keys = sorted(rows)
+        np.savez_compressed(ANSWERS, keys=np.frombuffer(b"".join(keys), np.uint8).reshape(-1, 16),
+                            ints=np.array([rows[k][0] for k in keys], dtype=np.int64).reshape(-1, 4),
+                            digests=np.frombuffer(b"".join(rows[k][1] for k in keys), np.uint8).reshape(-1, 16))
+
+
+def _load_answers():
+    z = np.load(ANSWERS)
+    return {bytes(k): (tuple(int(v) for v in i), bytes(d)) for k, i, d in zip(z["keys"], z["ints"], z["digests"])}
+
+
+class _RecordedRef:
+    """The reference's recorded answers, for a checkout without the reference build.  The bytes handed back are computed here
+    -- the file by the C restatement (oracle/), the pixels by the drop-in's CPU decoder -- and must have the digest the
+    reference's own bytes had: a call whose answer was never recorded, or bytes that differ from the reference's, fail."""
+
+    def __init__(self):
+        self.rows = _load_answers()
+
+    def _row(self, key, what):
+        if key not in self.rows:
+            raise AssertionError(f"no recorded reference answer for this {what} call (oracle/make_golden_ref_answers.py records them)")
+        return self.rows[key]
+
+    def encode(self, img, w, h, c, flags=0):
+        (size, *_), dig = self._row(_encode_key(img, w, h, c, flags), "encode")
+        if size < 0:
+            return None
+        png = oracle().encode(img, w, h, c, flags)
+        assert png is not None and len(png) == size and _digest(png) == dig, "the C restatement's file differs from the reference's"
+        return png
+
+    def get_info(self, png):
+        return self._row(_info_key(png), "get_info")[0]
+
+    def decode(self, png, desired):
+        (st, w, h, c), dig = self._row(_decode_key(png, desired), "decode")
+        if st != 0:
+            return st, None, w, h, c
+        import dropin
+        old = os.environ.get("FPNG_AMD_DECODE_CPU")
+        os.environ["FPNG_AMD_DECODE_CPU"] = "1"
+        try:
+            st2, out, *_ = dropin.decode(png, desired)
+        finally:
+            if old is None:
+                del os.environ["FPNG_AMD_DECODE_CPU"]
+            else:
+                os.environ["FPNG_AMD_DECODE_CPU"] = old
+        assert st2 == 0 and _digest(np.asarray(out)) == dig, "the drop-in's pixels differ from the reference's"
+        return st, np.asarray(out), w, h, c
 
 
 # ---------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import dropin
-from cpu_ref import fuzz_image, have_ref, oracle, ref
+from cpu_ref import fuzz_image, have_ref, have_ref_answers, oracle, ref
 
 
 def test_roundtrip_all_channel_conversions():
@@ -29,7 +29,7 @@ def test_roundtrip_all_channel_conversions():
                 assert (out == exp2.reshape(-1)).all(), (w, h, c, fl, desired)
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_status_codes_match_reference_on_damaged_files():
     rng = np.random.default_rng(32)
     checked = differing = 0
@@ -106,7 +106,7 @@ def edited_containers(rng, n_images, per_image=10):
     return out
 
 
-@pytest.mark.skipif(not have_ref(), reason="the reference's decoder is the judge")
+@pytest.mark.skipif(not have_ref_answers(), reason="the reference's decoder (or its recorded answers) is the judge")
 def test_container_and_block_edits_get_the_references_answer():
     """A flipped bit in a PNG container ends at the chunk's CRC.  These files carry good CRCs and odd STRUCTURE: chunks inserted,
     missing, doubled or out of order, IHDR fields and dimensions changed, several IDATs, junk behind IEND, other zlib headers and
@@ -114,17 +114,14 @@ def test_container_and_block_edits_get_the_references_answer():
     reference lets pass: src/fpng.cpp:2158-2166), dynamic headers with other counts.  fpng_get_info and fpng_decode_memory of the
     reference judge; the drop-in's functions and the GPU decoder's host side (fpng_amd_decode_plan + the kernels' logic on the
     CPU; UNDECIDED = the drop-in's CPU decoder answers) must agree in status, geometry and pixels."""
-    import ctypes as C
     import test_decode_model as M
     rng = np.random.default_rng(606)
     R = ref()
     seen, accepted, left = set(), 0, 0
     for name, f in edited_containers(rng, 260):
-        b = np.frombuffer(f, dtype=np.uint8)
-        w, h, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        gst = R.L.ref_get_info(b.ctypes.data, b.size, C.byref(w), C.byref(h), C.byref(c))
+        gst, *whc = R.get_info(f)
         mine = dropin.get_info(f)
-        assert mine[0] == gst and (gst != 0 or mine[1:] == (w.value, h.value, c.value)), (name, gst, mine)
+        assert mine[0] == gst and (gst != 0 or mine[1:] == tuple(whc)), (name, gst, mine)
         desired = int(rng.choice([3, 4]))
         st_r, out_r, *dr = R.decode(f, desired)
         st_c, out_c, *dc = dropin.decode(f, desired)
@@ -181,7 +178,7 @@ def other_tables(rng, n_images, per_image=8):
     return out
 
 
-@pytest.mark.skipif(not have_ref(), reason="the reference's decoder is the judge")
+@pytest.mark.skipif(not have_ref_answers(), reason="the reference's decoder (or its recorded answers) is the judge")
 def test_other_huffman_tables_and_the_reserved_length_symbols():
     """The block header's reader and the table builders under tables no fpng encoder writes: random complete codes up to 12 bits
     (and longer: turned away), single-code tables, HLIT / HDIST / HCLEN larger than needed, the code lengths spelled with the repeat
@@ -255,7 +252,7 @@ def test_cpu_decoder_under_the_sanitizers(tmp_path):
     assert n == 2 * len(files) and 0.2 * n < ok < 0.9 * n, q.stdout
 
 
-@pytest.mark.skipif(not have_ref(), reason="the reference's decoder is the judge")
+@pytest.mark.skipif(not have_ref_answers(), reason="the reference's decoder (or its recorded answers) is the judge")
 def test_flat_rows_with_a_run_at_the_first_pixel():
     """The CPU decoder copies the row above where a row is its first pixel of zero literals + runs of zero deltas.  Hand-made rows
     that LOOK like that by their byte counts: a run of zeros that starts at the first pixel (the reference takes it: the pixel in

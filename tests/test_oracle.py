@@ -8,7 +8,7 @@ import zlib
 import numpy as np
 import pytest
 
-from cpu_ref import ROOT, fuzz_image, have_ref, oracle, ref
+from cpu_ref import ROOT, fuzz_image, have_ref, have_ref_answers, oracle, ref
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -96,7 +96,7 @@ def test_oracle_bad_arguments():
     assert oracle().encode(img, (1 << 24) + 1, 1, 3) is None
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_oracle_vs_reference_fuzz():
     """The pin: byte-for-byte against the unmodified reference on the edge-case recipe."""
     rng = np.random.default_rng(11)
@@ -110,7 +110,7 @@ def test_oracle_vs_reference_fuzz():
     assert raw > 100  # the recipe must actually reach the stored-block fallback
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_oracle_vs_reference_adjust_freq_quirk():
     """Large skewed histograms: vertical deltas in {0,+1,-1} plus singleton outliers."""
     rng = np.random.default_rng(12)
@@ -124,7 +124,7 @@ def test_oracle_vs_reference_adjust_freq_quirk():
         assert oracle().encode(img, w, h, c, fl) == ref().encode(img, w, h, c, fl)
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_reference_decodes_oracle_output():
     rng = np.random.default_rng(13)
     for _ in range(30):
@@ -167,7 +167,7 @@ def test_oracle_on_the_natural_image():
             assert hashlib.sha256(png).hexdigest() == g[k]["flags"][str(fl)]["sha256"], (k, fl)
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_oracle_vs_reference_wide_rows():
     """The checker itself on the wide-row generator the -m gpu suite uses (tools/gpu_wide_fuzz.py): rows of 257..4100 pixels,
     runs crossing every 256-pixel border -- identical to the unmodified reference for all three flag values."""
@@ -187,7 +187,7 @@ def _is_stored(png):
     return (png[58 + 2] & 6) == 0  # (58 = signature + IHDR + fdEC + the IDAT's prefix; the block's type bits sit behind the zlib header)
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_oracle_vs_reference_at_the_stored_or_compressed_boundary():
     """The reference keeps the compressed stream unless its coder "ran out of buffer" -- a rule with a closed form in the final bit
     position and 8 bytes of slack (reference src/fpng.cpp:567-588 / :1728-1758).  Images whose first K pixels are noise and
@@ -249,7 +249,7 @@ def skewed_images(rng, max_bytes=400_000):
     return out
 
 
-@pytest.mark.skipif(not have_ref(), reason="reference build not available")
+@pytest.mark.skipif(not have_ref_answers(), reason="neither the reference build nor its recorded answers")
 def test_oracle_vs_reference_on_skewed_histograms():
     rng = np.random.default_rng(1618)
     imgs = skewed_images(rng)

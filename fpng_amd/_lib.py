@@ -21,6 +21,11 @@ class Image(C.Structure):
                 ("d_out", C.c_void_p), ("out_cap", C.c_size_t)]
 
 
+class ImageEx(C.Structure):
+    _fields_ = [("d_pixels", C.c_void_p), ("row_pitch", C.c_int64), ("w", C.c_uint32), ("h", C.c_uint32), ("format", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_cap", C.c_size_t)]
+
+
 class Result(C.Structure):
     _fields_ = [("png_size", C.c_uint64), ("mode", C.c_uint32), ("status", C.c_uint32)]
 
@@ -96,6 +101,7 @@ SIGNATURES = {
     "fpng_amd_encode_batch_async": (_int, [_vp, C.POINTER(Image), _u32, _u32]),
     "fpng_amd_encode_finish": (_int, [_vp, C.POINTER(Result), _u32]),
     "fpng_amd_encode_submit": (_int, [_vp, C.POINTER(Image), _u32, _u32, C.POINTER(_u64)]),
+    "fpng_amd_encode_submit_ex": (_int, [_vp, C.POINTER(ImageEx), _u32, _u32, C.POINTER(_u64)]),
     "fpng_amd_encode_wait": (_int, [_vp, _u64, C.POINTER(Result), _u32]),
     "fpng_amd_encode_query": (_int, [_vp, _u64]),
     "fpng_amd_encode_host": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(_sz)]),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Band, BandStats, FpngAmdError, HostImage, Image, Result, check
+from ._lib import Band, BandStats, FpngAmdError, HostImage, Image, ImageEx, Result, check
 
 FPNG_ENCODE_SLOWER = 1        # reference src/fpng.h:38
 FPNG_FORCE_UNCOMPRESSED = 2   # reference src/fpng.h:41
@@ -26,6 +26,58 @@ FPNG_CRC32_INIT = 0           # reference src/fpng.h:26
 FPNG_ADLER32_INIT = 1         # reference src/fpng.h:30
 
 MODE_COMPRESSED, MODE_STORED = 0, 1
+
+# source formats of Encoder.submit_ex (FPNG_AMD_SRC_* in include/fpng_amd.h): name -> (value, source bytes per pixel, PNG channels)
+SRC_FORMATS = {"RGB": (0, 3, 3), "BGR": (1, 3, 3), "RGBA": (2, 4, 4), "BGRA": (3, 4, 4), "ARGB": (4, 4, 4), "ABGR": (5, 4, 4),
+               "RGBX": (6, 4, 3), "BGRX": (7, 4, 3), "XRGB": (8, 4, 3), "XBGR": (9, 4, 3)}
+SRC_RGB, SRC_BGR, SRC_RGBA, SRC_BGRA, SRC_ARGB, SRC_ABGR, SRC_RGBX, SRC_BGRX, SRC_XRGB, SRC_XBGR = range(10)
+
+
+def format_channels(fmt):
+    """Channel count of the PNG a FPNG_AMD_SRC_* format is encoded to."""
+    return [v[2] for v in SRC_FORMATS.values() if v[0] == fmt][0]
+
+
+def source_layout(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, format) of a uint8 (h, w, c) tensor VIEW for Encoder.submit_ex, from its strides and data_ptr() alone
+    (the device is not touched, so CPU tensors work too).
+
+    order: the channel order of the view's c channels -- "rgb" / "bgr" for c = 3, "rgba" / "bgra" / "argb" / "abgr" for c = 4
+    ("rgb" / "bgr" there mean alpha last).  stride(2) must be 1 and stride(1), the source pixel, 3 or 4 bytes.  A 3-channel view
+    with 4-byte pixels ([..., :3] of RGBA) is an *X format; one whose first byte is the pixel's second byte ([..., 1:] of ARGB) an
+    X*** format, its base moved back one byte.  bottom_up: the tensor's row 0 is the image's BOTTOM row (a GL readback): the file
+    starts with the tensor's last row and the pitch is negative.  Rows that overlap, stride 0 and other dtypes are refused."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+        raise ValueError("source_layout: a uint8 tensor shaped (h, w, c)")
+    h, w, c = t.shape
+    if c not in (3, 4) or h < 1 or w < 1:
+        raise ValueError(f"source_layout: {c} channels (3 or 4), {w} x {h}")
+    order = order.lower()
+    if c == 4 and order in ("rgb", "bgr"):
+        order += "a"
+    if sorted(order) != sorted("rgba"[:c]):
+        raise ValueError(f"source_layout: order {order!r} does not name the {c} channels")
+    if c > 1 and t.stride(2) != 1:
+        raise ValueError("source_layout: the channels of a pixel must be adjacent bytes (stride(2) == 1)")
+    px = t.stride(1) if w > 1 else (4 if (t.stride(1) == 4 or c == 4) else 3)
+    if px not in (3, 4) or px < c:
+        raise ValueError(f"source_layout: pixel stride {t.stride(1)} (3 or 4 bytes, at least the channels)")
+    ptr = t.data_ptr()
+    name = order.upper()
+    if c == 3 and px == 4:
+        # the ignored byte is the one the view leaves out: behind the channels on a dword boundary, else in front of them
+        if ptr % 4 == 1:
+            name, ptr = "X" + name, ptr - 1
+        else:
+            name += "X"
+    rp = t.stride(0)
+    if h > 1 and (rp == 0 or rp < w * px):
+        raise ValueError(f"source_layout: row stride {rp} < w * {px} (rows overlap, or stride 0)")
+    if h == 1:
+        rp = 0  # (one row: no pitch)
+    if bottom_up and h > 1:
+        ptr, rp = ptr + (h - 1) * rp, -rp
+    return ptr, rp, SRC_FORMATS[name][0]
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
 
 
@@ -299,6 +351,39 @@ class Encoder:
         check(self.lib.fpng_amd_encode_submit(self.h, batch[2], n, flags, C.byref(t)))
         self.last_ticket = t.value
         # buffers of submissions in flight stay alive; a submission 8 tickets back has finished (its slot was reused)
+        self._keep[t.value] = batch
+        for old in [k for k in self._keep if k + 8 <= t.value]:
+            del self._keep[old]
+        return n
+
+    @staticmethod
+    def make_batch_ex(images, outs, order="rgb", bottom_up=False):
+        """Descriptor array (fpng_amd_image_ex[n]) for submit_ex(): uint8 CUDA tensor VIEWS (h, w, c) in place -- crops, BGR(A),
+        [..., :3] of RGBA, bottom-up buffers -- described by source_layout(view, order, bottom_up) (order / bottom_up: one value, or
+        one per image).  outs: uint8 CUDA tensors of >= max_encoded_size(w, h, c) bytes."""
+        n = len(images)
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        arr = (ImageEx * n)()
+        for i, (im, out) in enumerate(zip(images, outs)):
+            assert im.is_cuda and out.is_cuda
+            ptr, rp, fmt = source_layout(im, orders[i], ups[i])
+            arr[i].d_pixels, arr[i].row_pitch, arr[i].format = ptr, rp, fmt
+            arr[i].w, arr[i].h = im.shape[1], im.shape[0]
+            arr[i].d_out = out.data_ptr()
+            arr[i].out_cap = out.numel()
+        return (images, outs, arr)
+
+    def submit_ex(self, images, outs=None, flags=0, order="rgb", bottom_up=False):
+        """submit() for images in other layouts (fpng_amd_encode_submit_ex): images = tensor views as for make_batch_ex() with outs,
+        or a make_batch_ex() descriptor and outs = None.  The files are the ones submit() writes for the same pixels repacked as
+        R,G,B[,A].  Asynchronous; wait(last_ticket, n) / finish() for the sizes."""
+        batch = images if outs is None else self.make_batch_ex(images, outs, order, bottom_up)
+        n = len(batch[2])
+        self._sync_stream()
+        t = C.c_uint64(0)
+        check(self.lib.fpng_amd_encode_submit_ex(self.h, batch[2], n, flags, C.byref(t)))
+        self.last_ticket = t.value
         self._keep[t.value] = batch
         for old in [k for k in self._keep if k + 8 <= t.value]:
             del self._keep[old]

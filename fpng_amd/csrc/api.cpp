@@ -447,6 +447,8 @@ struct Submission {
     uint64_t total_rows = 0;
     uint64_t local_dwords = kLocalFrontPad; // scratch for the rows' local streams (assemble_kernel may read up to four dwords in front of a stream)
     uint32_t chan_mask = 0;    // bit 0: 3-channel jobs present, bit 1: 4-channel jobs
+    bool ex = false;           // fpng_amd_encode_submit_ex: the jobs carry a source layout, the *_ex kernels read their pixels
+    uint32_t layout_mask = 0;  // (ex) bit 0: 3-byte sources, bit 1: 4-byte sources with 4 channels, bit 2: 4-byte sources with 3
     uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
 };
 
@@ -474,12 +476,23 @@ int fpng_amd::drain(fpng_amd_encoder *e)
 
 namespace {
 
+// FPNG_AMD_SRC_*: source bytes per pixel, PNG channels, and the v_perm_b32 selector that turns a source pixel's dword into the
+// PNG pixel (byte k of the selector = source byte of PNG channel k; 0x0c = a zero byte)
+struct SrcFormat {
+    uint32_t bytes, chans, sel;
+};
+constexpr SrcFormat kSrcFormats[FPNG_AMD_SRC_COUNT] = {
+    {3, 3, 0x0c020100u}, {3, 3, 0x0c000102u},                                              // RGB BGR
+    {4, 4, 0x03020100u}, {4, 4, 0x03000102u}, {4, 4, 0x00030201u}, {4, 4, 0x00010203u},    // RGBA BGRA ARGB ABGR
+    {4, 3, 0x0c020100u}, {4, 3, 0x0c000102u}, {4, 3, 0x0c030201u}, {4, 3, 0x0c010203u}};   // RGBX BGRX XRGB XBGR
+
 // Fills slot.jobs[0..n) for whole-image jobs and sizes the scratch buffers.  Only `slot` (which is free) and
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
+// ex_images (fpng_amd_encode_submit_ex) replaces `images` when it is given.
 int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const fpng_amd_image *images,
-                 uint32_t n, uint32_t flags, Submission &sub)
+                 const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, Submission &sub)
 {
-    if (!e || !images || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    if (!e || !(images || ex_images) || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "batch larger than 65535 images");
     int rc;
     if ((rc = slot.jobs.ensure(n)) || (rc = slot.results.ensure(n))) return rc;
@@ -488,8 +501,27 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     const bool two_pass = (flags & FPNG_AMD_ENCODE_SLOWER) && !force_stored;
     sub = Submission();
     sub.n = n;
+    sub.ex = ex_images != nullptr;
     for (uint32_t i = 0; i < n; i++) {
-        const fpng_amd_image &im = images[i];
+        fpng_amd_image im_of_ex;
+        const SrcFormat *fmt = nullptr;
+        int64_t pitch = 0;
+        if (ex_images) {
+            const fpng_amd_image_ex &x = ex_images[i];
+            if (x.format >= FPNG_AMD_SRC_COUNT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown source format");
+            fmt = &kSrcFormats[x.format];
+            if ((rc = check_dims(x.w, x.h, fmt->chans))) return rc;
+            const int64_t packed = (int64_t)x.w * fmt->bytes;
+            pitch = x.row_pitch ? x.row_pitch : packed;
+            if ((pitch < 0 ? -pitch : pitch) < packed) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w * source bytes per pixel");
+            if (fmt->bytes == 4 && (((uintptr_t)x.d_pixels & 3) || (pitch & 3)))
+                return fail(FPNG_AMD_ERR_INVALID_ARG, "4-byte source pixels need d_pixels and row_pitch to be multiples of 4");
+            im_of_ex.d_pixels = x.d_pixels;
+            im_of_ex.w = x.w, im_of_ex.h = x.h, im_of_ex.num_chans = fmt->chans;
+            im_of_ex.d_out = x.d_out;
+            im_of_ex.out_cap = x.out_cap;
+        }
+        const fpng_amd_image &im = ex_images ? im_of_ex : images[i];
         if ((rc = check_dims(im.w, im.h, im.num_chans))) return rc;
         if (!im.d_pixels || !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
         if (((uintptr_t)im.d_out & 15) || (im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)))
@@ -523,6 +555,12 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
         j.local_stride = (uint32_t)(((((uint64_t)j.bpl + 1) * bits_per_byte + 64 + 31) / 32 + 4 + 31) & ~31ull); // whole 128-byte lines
         j.local_base = sub.local_dwords;
         sub.chan_mask |= (im.num_chans == 3) ? 1u : 2u;
+        if (fmt) {
+            j.pitch = pitch;
+            j.src_bytes = fmt->bytes;
+            j.sel = fmt->sel;
+            sub.layout_mask |= fmt->bytes == 3 ? 1u : (fmt->chans == 4 ? 2u : 4u);
+        }
         if (im.num_chans == 4) sub.px4 += (uint64_t)im.w * im.h, sub.px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
         const uint64_t units = im.h; // records of the job: one per row
         sub.local_dwords += (uint64_t)j.local_stride * units;
@@ -544,7 +582,7 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     return FPNG_AMD_OK;
 }
 
-int submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags, uint64_t *ticket_out)
+int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out)
 {
     if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
     HIP_TRY(hipSetDevice(e->device));
@@ -569,7 +607,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32
     hipStream_t s = e->lane_stream[lane];
     fpng_amd_encoder::Scratch &sc = e->sc[lane];
     Submission sub;
-    int rc = prepare_jobs(e, slot, sc, images, n, flags, sub);
+    int rc = prepare_jobs(e, slot, sc, images, ex_images, n, flags, sub);
     if (rc) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
@@ -617,7 +655,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32
     // 7 us MORE per chain: every kernel's first touch of the record goes over PCIe.)
     // One image: its record travels in the arguments of the chain's first kernel, which leaves it in d_jobs for the others
     // (encode_rows_first_kernel): no blit kernel + dispatch gap in front of the chain.
-    const bool job_in_args = n == 1 && !force_stored;
+    const bool job_in_args = n == 1 && !force_stored && !sub.ex; // (the *_first kernels have no layout forms)
     const Job *d_jobs = sc.d_jobs.p;
     if (!job_in_args) HIP_TRY(hipMemcpyAsync(sc.d_jobs.p, slot.jobs.p, n * sizeof(Job), hipMemcpyHostToDevice, s));
     if ((rc = mark(e, s, 0))) return rc;
@@ -636,6 +674,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32
         sc.hist_zero = 0;
         if (job_in_args)
             launch_hist_first(s, slot.jobs.p[0], sc.d_jobs.p, sc.d_hist.p);
+        else if (sub.ex)
+            launch_hist_ex(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
         else
             launch_hist(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
         if ((rc = mark(e, s, ++ph))) return rc;
@@ -661,6 +701,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32
     // (both kernels get slower by more than the two small launches cost) and 5-19 % MORE single-frame latency.
     if (job_in_args)
         launch_encode_rows_first(s, two_pass ? slot.jobs2.p[0] : slot.jobs.p[0], sc.d_jobs.p, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
+    else if (!force_stored && sub.ex)
+        launch_encode_rows_ex(s, d_jobs, n, sub.max_rows, sub.layout_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
     else if (!force_stored)
         launch_encode_rows(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
     if ((rc = mark(e, s, ++ph))) return rc;
@@ -680,7 +722,10 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32
     launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
     if ((rc = mark(e, s, ++ph))) return rc;
     uint32_t *adler_parts = sc.d_partials.p + (size_t)n * sub.max_crc_blocks;
-    launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
+    if (sub.ex)
+        launch_assemble_ex(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
+    else
+        launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
     if ((rc = mark(e, s, ++ph))) return rc;
     launch_finalize(s, d_jobs, n, sub.max_crc_blocks, sc.d_rows.p, sc.d_states.p, dt.crc, sc.d_partials.p, adler_parts, slot.results.p);
     if ((rc = mark(e, s, ++ph))) return rc;
@@ -710,12 +755,18 @@ extern "C" {
 
 int fpng_amd_encode_submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags, uint64_t *ticket)
 {
-    return submit(e, images, n, flags, ticket);
+    return submit(e, images, nullptr, n, flags, ticket);
+}
+
+int fpng_amd_encode_submit_ex(fpng_amd_encoder *e, const fpng_amd_image_ex *images, uint32_t n, uint32_t flags, uint64_t *ticket)
+{
+    if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    return submit(e, nullptr, images, n, flags, ticket);
 }
 
 int fpng_amd_encode_batch_async(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags)
 {
-    return submit(e, images, n, flags, nullptr);
+    return submit(e, images, nullptr, n, flags, nullptr);
 }
 
 int fpng_amd_encode_query(fpng_amd_encoder *e, uint64_t ticket)
@@ -958,7 +1009,7 @@ static int host_batch_ring(fpng_amd_encoder *e, const fpng_amd_host_image *imgs,
         uint64_t t = 0;
         {
             std::lock_guard<std::mutex> lk(emu);
-            if ((rc = submit(e, &im, 1, flags, &t))) failed = rc;
+            if ((rc = submit(e, &im, nullptr, 1, flags, &t))) failed = rc;
         }
         {
             std::lock_guard<std::mutex> lk(mu);

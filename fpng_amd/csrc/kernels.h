@@ -30,10 +30,17 @@ struct Job {
     uint64_t local_base;      // dwords
     uint32_t local_stride;    // dwords per row (worst-case token bits of a row + slack)
     uint32_t local_pad;
-    uint32_t reserved[6];     // (keeps the record at 224 bytes and png_header where it was: the row walk's and the histogram pass's code is, instruction for
-                              //  instruction, the build round 5's profiles were measured on -- tools/isa_diff.py)
+    // source layout of fpng_amd_encode_submit_ex jobs (zero elsewhere; read only by the *_ex kernels): row r of the job starts at
+    // rows + r * pitch, a pixel is src_bytes bytes, and v_perm_b32 with selector `sel` turns a source pixel's dword into the PNG's
+    // R,G,B[,A] bytes (0x0c = a zero byte).  These words were reserved before: the record stays 224 bytes and png_header where it
+    // was, so the other kernels' code is, instruction for instruction, the same (tools/isa_diff.py)
+    int64_t pitch;            // signed bytes from one row to the next
+    uint32_t src_bytes;       // 3 or 4
+    uint32_t sel;
+    uint32_t reserved[2];
     uint8_t png_header[60];   // 58 bytes used (reference fpng.cpp:1767-1791), IDAT length patched on device
 };
+static_assert(sizeof(Job) == 224 && offsetof(Job, pitch) == 136 && offsetof(Job, png_header) == 160, "Job layout");
 
 struct RowInfo {
     uint32_t bits; // token bits of the row
@@ -92,6 +99,13 @@ void launch_crc(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_cr
                 const CrcDeviceTables *tabs, uint32_t *partials);
 void launch_finalize(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, const RowInfo *rows,
                      JobState *states, const CrcDeviceTables *tabs, const uint32_t *partials, const uint32_t *adler_parts, Result *results);
+// fpng_amd_encode_submit_ex: the same chain for jobs with a source layout (Job::pitch / src_bytes / sel).  Only the kernels that read
+// pixels have layout forms.  layout_mask: bit 0 = 3-byte sources, bit 1 = 4-byte sources with 4 channels, bit 2 = 4-byte sources with 3
+void launch_hist_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist);
+void launch_encode_rows_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t layout_mask, RowInfo *rows,
+                           JobState *states, uint32_t *local, bool wide4);
+void launch_assemble_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
+                        const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
 // table training: sums[0..288) += the 16-bit adjusted histogram of every image (hist_all: 288 counters per image)
 void launch_train_accumulate(hipStream_t s, const uint32_t *hist_all, uint32_t n_images, uint64_t *sums);
 // dst[0..16) |= src[0..16): the 16-byte piece two neighbouring band windows share (each holds zeros where the other's bits are)

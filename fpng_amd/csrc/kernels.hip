@@ -22,6 +22,9 @@
 // scan_kernel + assemble_kernel into a window of the file (bits of other bands stay zero); crc_kernel is the CRC pass of
 // fpng_amd_wrap_png() for callers that do not hand over the bands' CRC partials.
 //
+// fpng_amd_encode_submit_ex jobs (strided / bottom-up / BGR(A) / padded-alpha sources) take the same chain; the kernels that read
+// pixels have layout forms for them (hist_ex_kernel, encode_rows_ex_kernel, stored_ex_kernel), the others are shared as they are.
+//
 // Integer / byte work throughout, bounded by VALU issue and HBM traffic: no MFMA.
 #include "kernels.h"
 
@@ -50,6 +53,7 @@ constexpr int kScanBlock = kWave * kScanWaves;
 constexpr int kHistWaves = 8;              // hist_kernel: one LDS histogram (36 KiB) and one round of global atomics per block
 constexpr int kHistBlock = kWave * kHistWaves;
 constexpr int kRowBlock = kWave * kRowWaves;
+constexpr uint32_t kStoredExBlocks = 64; // stored_ex_kernel: workgroups per image
 #ifndef FPNG_STAGE_DWORDS
 #define FPNG_STAGE_DWORDS 1024
 #endif
@@ -298,14 +302,21 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, ui
     return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)p, 0, (int)uniform(bytes), 0x00020000);
 }
 
-template <int C> struct RowWindows {
+// L: source layout.  0 = packed R,G,B[,A] (fpng_amd_encode_submit), else the bytes per source pixel of an _ex job (3 or 4): the loads
+// follow the source pixel, and one v_perm_b32 with the job's wave-uniform selector turns the FILTERED pixel into the PNG's byte order
+// (the filter is bytewise, so permuting before or after it is the same; a selector byte 0x0c zeroes an ignored X byte).  Everything
+// downstream -- literal tokens, the RLE compare, the histogram, the Adler sums -- sees only permuted values.
+template <int C, int L = 0> struct RowWindows {
+    static constexpr int SB = L ? L : C; // source bytes per pixel
     __amdgpu_buffer_rsrc_t cur, up;
     uint32_t voff; // per-lane byte offset of its pixel inside window 0 of the row (RGB: aligned down)
     uint32_t sh;   // RGB: byte phase of the pixel inside its aligned dword
+    uint32_t sel = 0; // L != 0: v_perm_b32 selector, source pixel -> PNG pixel
 
+    // bpl: bytes of a source row (w * SB)
     __device__ __forceinline__ void init(const uint8_t *row, const uint8_t *up_row, uint32_t bpl, uint32_t lane)
     {
-        if (C == 4) {
+        if (SB == 4) {
             cur = make_rsrc(row, bpl);
             up = make_rsrc(up_row ? up_row : row, up_row ? bpl : 0);
             voff = lane * 4;
@@ -340,7 +351,7 @@ template <int C> struct RowWindows {
     __device__ __forceinline__ Raw load_raw(uint32_t x0) const
     {
         Raw q;
-        if (C == 4) {
+        if (SB == 4) {
             q.c_lo = __builtin_amdgcn_raw_buffer_load_b32(cur, voff, x0 * 4, 0);
             q.u_lo = __builtin_amdgcn_raw_buffer_load_b32(up, voff, x0 * 4, 0);
             q.c_hi = q.u_hi = 0;
@@ -356,9 +367,11 @@ template <int C> struct RowWindows {
     // filtered pixel: bytes of (cur - up) mod 256 (reference fpng.cpp:1605-1655)
     __device__ __forceinline__ uint32_t filter(const Raw &q) const
     {
+        if (L == 4) return __builtin_amdgcn_perm(0u, sub_bytes(q.c_lo, q.u_lo), sel);
         if (C == 4) return sub_bytes(q.c_lo, q.u_lo);
         const uint32_t c = __builtin_amdgcn_alignbyte(q.c_hi, q.c_lo, sh);
         const uint32_t u = __builtin_amdgcn_alignbyte(q.u_hi, q.u_lo, up_sh);
+        if (L == 3) return __builtin_amdgcn_perm(0u, sub_bytes(c, u), sel);
         return sub_bytes(c, u) & 0xFFFFFFu;
     }
     __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
@@ -514,18 +527,20 @@ struct RowResult {
     uint32_t s1, s2;         // Adler raw sums of the filtered row, mod 65521
 };
 
-// Walks row r of the job.
-template <int C, Pass PASS>
+// Walks row r of the job.  L: source layout (RowWindows); rows of an L != 0 job lie job.pitch bytes apart.
+template <int C, Pass PASS, int L = 0>
 __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables &T, uint32_t *hist, uint32_t r, uint32_t lane, EmitSink *sink)
 {
-    using Raw = typename RowWindows<C>::Raw;
+    using Raw = typename RowWindows<C, L>::Raw;
+    constexpr int SB = RowWindows<C, L>::SB;
     constexpr int PF = 4; // windows in flight ahead of the one being processed
     constexpr bool kEmit = PASS == Pass::Encode; // builds and stages the token bits
     constexpr bool kSums = PASS == Pass::Encode; // Adler sums, final flush unit
     const uint32_t w = uniform(job.w), bpl = uniform(job.bpl);
-    const uint8_t *row = job.rows + (size_t)r * bpl;
+    const int64_t pitch = L ? (int64_t)uniform64((uint64_t)job.pitch) : 0; // (L == 0: packed rows, bpl apart)
+    const uint8_t *row = L ? job.rows + (int64_t)r * pitch : job.rows + (size_t)r * bpl;
     const bool filter_up = (uniform(job.y0) + r) != 0;
-    const uint8_t *up_row = filter_up ? (r ? row - bpl : job.row_above) : nullptr;
+    const uint8_t *up_row = filter_up ? (r ? (L ? row - pitch : row - bpl) : job.row_above) : nullptr;
     const uint32_t filter_byte = filter_up ? 2u : 0u;
     const bool one_pass = uniform(job.one_pass) != 0;
     const bool lit_test = (C == 4) && one_pass; // reference fpng.cpp:1520-1528
@@ -533,8 +548,9 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
     const uint32_t nwin = (w + 63) >> 6;
     const uint32_t n_interior = (w >= 128) ? (w >> 6) - 1 : 0; // windows k with (k+2)*64 <= w
 
-    RowWindows<C> px;
-    px.init(row, up_row, bpl, lane);
+    RowWindows<C, L> px;
+    if (L) px.sel = uniform(job.sel);
+    px.init(row, up_row, L ? w * (uint32_t)SB : bpl, lane);
 
     Rle<C> rle;
     uint32_t row_bits = 0, last_unit = 0;
@@ -706,7 +722,8 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
     uint32_t carry_f = 0; // filtered value of the pixel just before window k0
     {
         constexpr int ND = C;                         // filtered dwords per lane: 4 pixels x C bytes
-        constexpr uint32_t kLaneBytes = 4u * C, kSuperBytes = 256u * C;
+        constexpr uint32_t kLaneBytes = 4u * C, kSuperBytes = 256u * C;  // filtered (PNG) bytes
+        constexpr uint32_t kSrcLaneBytes = 4u * SB, kSrcSuperBytes = 256u * SB; // source bytes
         // NS super-windows are followed by at least one more pixel of the row.  A row that ENDS with a complete
         // super-window (w a multiple of 256: 512, 3840, 7680 ...) takes that one here too when it is of a cheap tier: no
         // look-ahead pixel, and the token of the row's last pixel is the final flush unit.  (Taking an INCOMPLETE last
@@ -716,16 +733,16 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
         const uint32_t NSX = NS + (((w & 255u) == 0) ? 1u : 0u);
         constexpr uint32_t S0 = 0; // the walk's first super-window
         if (NSX > S0) {
-            const uint32_t voff4 = lane * kLaneBytes;
+            const uint32_t voff4 = lane * kSrcLaneBytes;
             auto load4 = [&](uint32_t S, u32x4 &c4, u32x4 &u4) {
                 // RGB: 16 aligned bytes that contain the lane's 12 (the resources start on a dword, the row begins
                 // px.phase / px.up_phase bytes into them)
-                c4 = __builtin_amdgcn_raw_buffer_load_b128(px.cur, voff4, S * kSuperBytes, 0);
-                u4 = __builtin_amdgcn_raw_buffer_load_b128(px.up, voff4, S * kSuperBytes, 0); // (an nt hint on this last use of the row: 0.557 vs 0.500 ms)
+                c4 = __builtin_amdgcn_raw_buffer_load_b128(px.cur, voff4, S * kSrcSuperBytes, 0);
+                u4 = __builtin_amdgcn_raw_buffer_load_b128(px.up, voff4, S * kSrcSuperBytes, 0); // (an nt hint on this last use of the row: 0.557 vs 0.500 ms)
             };
-            // filtered bytes of the lane's four pixels, packed: fd[0..ND)
+            // filtered bytes of the lane's four pixels, packed: fd[0..ND) (L != 0: in source order, four dwords for 4-byte sources)
             auto filt = [&](const u32x4 &c4, const u32x4 &u4, uint32_t (&fd)[4]) {
-                if constexpr (C == 4) {
+                if constexpr (SB == 4) {
                     sub_bytes_x4(c4, u4, fd);
                 } else {
                     u32x4 ca, ua;
@@ -741,7 +758,16 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             };
             // pixel values (what the per-pixel walk calls f_cur): RGBA = the dwords, RGB = 24-bit fields
             auto pixels = [&](const uint32_t (&fd)[4], uint32_t (&pv)[4]) {
-                if constexpr (C == 4) {
+                if constexpr (L == 4) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) pv[j] = __builtin_amdgcn_perm(0u, fd[j], px.sel);
+                } else if constexpr (L == 3) {
+                    // pixel j = stream bytes 3j..3j+2: selector bytes (0..2) moved to where they sit in a pair of dwords
+                    pv[0] = __builtin_amdgcn_perm(0u, fd[0], px.sel);
+                    pv[1] = __builtin_amdgcn_perm(fd[1], fd[0], px.sel + 0x030303u);
+                    pv[2] = __builtin_amdgcn_perm(fd[2], fd[1], px.sel + 0x020202u);
+                    pv[3] = __builtin_amdgcn_perm(0u, fd[2], px.sel + 0x010101u);
+                } else if constexpr (C == 4) {
                     pv[0] = fd[0], pv[1] = fd[1], pv[2] = fd[2], pv[3] = fd[3];
                 } else {
                     pv[0] = fd[0] & 0xFFFFFFu;
@@ -758,7 +784,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             uint32_t fd[4];
             filt(c_first, u_first, fd);
             // pixel just before the super-window; in front of pixel 0: a value pixel 0 cannot equal (it has no left neighbour)
-            uint32_t last_f = ~uniform(fd[0]);
+            uint32_t last_f = L ? ~uniform(__builtin_amdgcn_perm(0u, fd[0], px.sel)) : ~uniform(fd[0]);
             uint32_t wgt = bpl - kLaneBytes * lane - S0 * kSuperBytes; // bytes from this lane's first byte to the row end
             const uint32_t c1_bits = chunk1 & 0xFF;
             // gather the per-pixel view of 64-pixel window jw of the current super-window (lane i <- pixel 64*jw+i)
@@ -783,7 +809,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
                     if (S + 1 + PF4 <= NS) load4(S + 1 + PF4, rc[js], ru[js]);
                     uint32_t f[4]; // the four pixels of this lane
                     pixels(fd, f);
-                    const uint32_t next_first = (C == 4) ? fn[0] : (fn[0] & 0xFFFFFFu);
+                    const uint32_t next_first = L ? __builtin_amdgcn_perm(0u, fn[0], px.sel) : (C == 4) ? fn[0] : (fn[0] & 0xFFFFFFu);
                     // per-lane "equals its left neighbour" predicates (their SGPR form is the wave ballot)
                     const bool s0 = f[0] == lane_prev(f[3], last_f); // (pixel 0 of the row: last_f was chosen to differ)
                     const bool s1 = f[1] == f[0], s2 = f[2] == f[1], s3 = f[3] == f[2];
@@ -815,10 +841,19 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
                             // Adler: 4*C consecutive bytes per lane
                             constexpr uint32_t kOffs[4] = {0x03020100u, 0x07060504u, 0x0B0A0908u, 0x0F0E0D0Cu};
                             uint32_t a = 0;
+                            if constexpr (L != 0) {
+                                // (fd is in source order here: the sums take the four PNG pixels, C bytes apart)
 #pragma unroll
-                            for (int j = 0; j < ND; j++) {
-                                a = __builtin_amdgcn_sad_u8(fd[j], 0u, a);
-                                acc_j = __builtin_amdgcn_udot4(fd[j], kOffs[j], acc_j, false);
+                                for (int j = 0; j < 4; j++) {
+                                    a = __builtin_amdgcn_sad_u8(f[j], 0u, a);
+                                    acc_j = __builtin_amdgcn_udot4(f[j], 0x03020100u + 0x01010101u * (uint32_t)(C * j), acc_j, false);
+                                }
+                            } else {
+#pragma unroll
+                                for (int j = 0; j < ND; j++) {
+                                    a = __builtin_amdgcn_sad_u8(fd[j], 0u, a);
+                                    acc_j = __builtin_amdgcn_udot4(fd[j], kOffs[j], acc_j, false);
+                                }
                             }
                             acc_a += a;
                             acc_w += (uint64_t)wgt * a;
@@ -947,6 +982,8 @@ __device__ __forceinline__ const Job &job_of_block(const Job *jobs) { return job
 // hist_kernel (2-pass, pass 1): literal / length-symbol histogram of the whole image
 // (reference fpng.cpp:1021-1084 / :1299-1363).  job.table here is the "symbol" table whose
 // chunk[q] holds (length symbol - 256).
+// EX: the jobs of fpng_amd_encode_submit_ex (hist_ex_kernel), walked with their source layout
+template <bool EX = false>
 __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
 {
     __shared__ PackedTables T;
@@ -957,7 +994,14 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, r = blockIdx.x * kHistWaves + uniform(threadIdx.x >> 6);
     if (r < job.nrows) {
-        if (job.c == 4)
+        if (EX) {
+            if (job.c == 4)
+                walk_row<4, Pass::Hist, 4>(job, T, hist, r, lane, nullptr);
+            else if (job.src_bytes == 4)
+                walk_row<3, Pass::Hist, 4>(job, T, hist, r, lane, nullptr);
+            else
+                walk_row<3, Pass::Hist, 3>(job, T, hist, r, lane, nullptr);
+        } else if (job.c == 4)
             walk_row<4, Pass::Hist>(job, T, hist, r, lane, nullptr);
         else
             walk_row<3, Pass::Hist>(job, T, hist, r, lane, nullptr);
@@ -973,6 +1017,10 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
 __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_kernel(const Job *jobs, uint32_t *hist_out)
 {
     hist_block(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
+}
+__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_ex_kernel(const Job *jobs, uint32_t *hist_out)
+{
+    hist_block<true>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
 }
 // (JobArg / the *_first_kernel forms: one image per submission, its job record in the kernel arguments -- see encode_rows_first_kernel)
 struct JobArg {
@@ -1164,12 +1212,13 @@ __global__ __launch_bounds__(kScanBlock) void scan_kernel(const Job *jobs, const
 // ---------------------------------------------------------------------------------------------
 // One instantiation per channel count (jobs of the other kind leave at once): the 3-channel walk needs far
 // fewer registers than the 4-pixels-per-lane RGBA one and keeps 8 waves per SIMD.
-template <int C>
+// L: source layout (RowWindows); an L != 0 instantiation takes the _ex jobs of its channel count and source pixel size.
+template <int C, int L = 0>
 __device__ __forceinline__ void encode_rows_block(const Job &job, uint32_t by, uint32_t bx, RowInfo *rows_out, JobState *states, uint32_t *local)
 {
     __shared__ PackedTables T;
     __shared__ __attribute__((aligned(16))) uint32_t stage[kRowWaves][kStageDwords + 2 * kWave + 4]; // + dump slots, see sink_put
-    if (job.c != C || bx * kRowWaves >= job.nrows) return;
+    if (job.c != C || (L && job.src_bytes != (uint32_t)L) || bx * kRowWaves >= job.nrows) return;
     stage_packed_tables<kRowBlock>(T, job.table);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, wv = uniform(threadIdx.x >> 6), r = bx * kRowWaves + wv;
@@ -1190,7 +1239,7 @@ __device__ __forceinline__ void encode_rows_block(const Job &job, uint32_t by, u
         sink_zero(sink, lane, kStageDwords);
     wave_lds_fence();
 
-    const RowResult res = walk_row<C, Pass::Encode>(job, T, nullptr, r, lane, &sink);
+    const RowResult res = walk_row<C, Pass::Encode, L>(job, T, nullptr, r, lane, &sink);
     if (r == job.nrows - 1 && job.is_last) {
         // end of block symbol behind the last row's tokens (reference fpng.cpp:1564-1567); not part of ri.bits
         const uint32_t eob = T.lit[256];
@@ -1228,6 +1277,15 @@ __global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdg
     uint32_t bx, by;
     xcd_block_order(bx, by);
     encode_rows_block<C>(jobs[by], by, bx, rows_out, states, local);
+}
+// the _ex jobs: source pixels of L bytes (3-byte sources give 3 channels; 4-byte ones 4, or 3 with an ignored X byte)
+template <int C, int WPE, int L>
+__global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_ex_kernel(const Job *jobs, RowInfo *rows_out,
+                                                                                                         JobState *states, uint32_t *local)
+{
+    uint32_t bx, by;
+    xcd_block_order(bx, by);
+    encode_rows_block<C, L>(jobs[by], by, bx, rows_out, states, local);
 }
 
 // One image per submission, first kernel of its chain: the job record comes IN THE KERNEL ARGUMENTS instead of through an
@@ -1486,12 +1544,22 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(const Job *jobs, const
 // -- together with its CRC partial and its share of the Adler-32 (byte sum, position-weighted sum: finalize_kernel adds the
 // ranges up).  A piece of 16 file bytes that lies inside one stored block and one row is 16 consecutive pixel bytes (5 aligned
 // loads + v_alignbyte); pieces with a block header, a filter byte or the ends of the stream are built byte by byte.
+// EX: jobs of fpng_amd_encode_submit_ex -- PNG byte b of a row is channel b % c of pixel b / c, found in the source through the
+// job's pitch, pixel size and selector; those images take the byte-by-byte path for every piece (stored blocks are their fallback
+// and FPNG_FORCE_UNCOMPRESSED's form, not a hot path)
+template <bool EX = false>
 __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 px, uint32_t s)
 {
     const uint32_t stride = job.bpl + 1, row = s / stride, col = s - row * stride;
+    if (EX) {
+        if (!col) return 0u;
+        const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
+        return (uint32_t)px[(int64_t)row * job.pitch + (int64_t)p * job.src_bytes + ((job.sel >> (8 * ch)) & 3u)];
+    }
     return col ? (uint32_t)px[(size_t)row * job.bpl + col - 1] : 0u;
 }
 
+template <bool EX = false>
 __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &st, int64_t range_begin, uint32_t range_bytes, int32_t db, int32_t de,
                                                 uint32_t (*tab)[256], uint32_t *red, const CrcDeviceTables *tabs, uint32_t *crc_out, uint32_t *adler_out)
 {
@@ -1512,7 +1580,7 @@ __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &
         if (o + 16 > db && o < de) {
             const int64_t fo = range_begin + o;
             bool fast = false;
-            if (z >= 7 && w >= 5 && w <= 65540u - 16u) {
+            if (!EX && z >= 7 && w >= 5 && w <= 65540u - 16u) {
                 const uint64_t s0 = k * 65535u + (w - 5);
                 if (s0 + 16 <= n_filtered) {
                     const uint32_t s32 = (uint32_t)s0, r = s32 / stride, col = s32 - r * stride;
@@ -1554,7 +1622,7 @@ __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &
                         } else {
                             const uint64_t sj = kk * 65535u + (ww - 5);
                             if (sj < n_filtered) {
-                                b = stored_stream_byte(job, px, (uint32_t)sj);
+                                b = stored_stream_byte<EX>(job, px, (uint32_t)sj);
                                 a_sum += b;
                                 w_sum += (uint64_t)(n_filtered - (uint32_t)sj) * b;
                             }
@@ -1810,6 +1878,37 @@ __global__ __launch_bounds__(kBlock) void assemble_kernel(const Job *jobs, JobSt
     if ((tid & 63) == 0) red[tid >> 6] = c;
     __syncthreads();
     if (tid == 0) partials[(size_t)blockIdx.y * max_crc_blocks + blockIdx.x] = red[0] ^ red[1] ^ red[2] ^ red[3];
+}
+
+// stored_ex_kernel: the stored blocks of the _ex images that fell back (or were asked for with FPNG_FORCE_UNCOMPRESSED), straight
+// from their source layout, with their ranges' Adler shares.  grid (<= max_crc_blocks, n_jobs), each workgroup takes every
+// gridDim.x-th range; compressed images leave at once.  assemble_kernel runs behind it with adler_parts = NULL: for a stored image it
+// then takes the CRC of the bytes in place, as for a stored row band, and writes nothing.  (A layout form of assemble_kernel itself
+// does not leave the packed form's code as it is: the compiler allocates registers differently once both exist.)
+__global__ __launch_bounds__(kBlock) void stored_ex_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
+                                                          uint32_t *adler_parts, uint32_t max_crc_blocks)
+{
+    __shared__ uint32_t tab[16][256];
+    __shared__ uint32_t red[3 * kWavesPerBlock];
+    const Job &job = job_of_block(jobs);
+    const JobState &st = states[blockIdx.y];
+    if (uniform(st.mode) == 0u) return;
+    const int64_t data_begin = kPngHeaderBytes, data_end = (int64_t)(kPngHeaderBytes + st.zlib_size - 4);
+    const int64_t end_aligned = (data_end + 15) & ~15ll;
+    const uint32_t range_bytes = 1u << uniform(crc_range_log2(st));
+    auto sat = [](int64_t v) { return (int32_t)(v > 0x7FFFFFFFll ? 0x7FFFFFFFll : (v < -0x7FFFFFFFll ? -0x7FFFFFFFll : v)); };
+    if (end_aligned - (int64_t)blockIdx.x * range_bytes <= (data_begin & ~15ll)) return;
+    for (int i = threadIdx.x; i < 16 * 256; i += kBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
+    __syncthreads();
+    for (uint32_t b = blockIdx.x; b < max_crc_blocks; b += gridDim.x) {
+        const int64_t range_end = end_aligned - (int64_t)b * range_bytes;
+        if (range_end <= (data_begin & ~15ll)) break; // nothing of the data in this range or the ones behind it
+        const int64_t range_begin = range_end - range_bytes;
+        const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
+        const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
+        assemble_stored<true>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
+        __syncthreads(); // (`red` is read by thread 0 at the end of the range)
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2318,6 +2417,22 @@ void launch_encode_rows(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_
     else if (chan_mask & 2u)
         hipLaunchKernelGGL((encode_rows_kernel<4, FPNG_ROWS_WPE>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
 }
+void launch_hist_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist)
+{
+    hipLaunchKernelGGL(hist_ex_kernel, dim3((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1), dim3(kHistBlock), 0, s, jobs, hist);
+}
+void launch_encode_rows_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t layout_mask, RowInfo *rows,
+                           JobState *states, uint32_t *local, bool wide4)
+{
+    if (layout_mask & 1u)
+        hipLaunchKernelGGL((encode_rows_ex_kernel<3, FPNG_ROWS_WPE, 3>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+    if (layout_mask & 4u)
+        hipLaunchKernelGGL((encode_rows_ex_kernel<3, FPNG_ROWS_WPE, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+    if ((layout_mask & 2u) && wide4)
+        hipLaunchKernelGGL((encode_rows_ex_kernel<4, FPNG_ROWS_WPE4, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+    else if (layout_mask & 2u)
+        hipLaunchKernelGGL((encode_rows_ex_kernel<4, FPNG_ROWS_WPE, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+}
 void launch_encode_rows_first(hipStream_t s, const Job &job, Job *d_job, RowInfo *rows, JobState *states, uint32_t *local)
 {
     JobArg arg;
@@ -2334,6 +2449,15 @@ void launch_assemble(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t m
 {
     hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
                        partials, adler_parts, max_crc_blocks);
+}
+void launch_assemble_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
+                        const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts)
+{
+    // (a small grid: for compressed images -- the usual case -- its workgroups only look at the mode)
+    const uint32_t gx = std::min(max_crc_blocks, kStoredExBlocks);
+    hipLaunchKernelGGL(stored_ex_kernel, dim3(gx, n_jobs), dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
+    hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
+                       partials, (uint32_t *)nullptr, max_crc_blocks);
 }
 void launch_crc(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, const JobState *states,
                 const CrcDeviceTables *tabs, uint32_t *partials)

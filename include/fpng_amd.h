@@ -140,7 +140,7 @@ void fpng_amd_encoder_destroy(fpng_amd_encoder *enc);
 void *fpng_amd_encoder_stream(fpng_amd_encoder *enc);
 
 typedef struct fpng_amd_image {
-    const void *d_pixels; /* DEVICE pointer, R first, pitch = w*num_chans (reference src/fpng.h:44-47) */
+    const void *d_pixels; /* DEVICE pointer, R first, pitch = w*num_chans (reference src/fpng.h:44-47; other layouts: fpng_amd_image_ex) */
     uint32_t w, h, num_chans;
     uint8_t *d_out;  /* DEVICE pointer, receives the whole .png file */
     size_t out_cap;  /* >= fpng_amd_max_encoded_size(w,h,num_chans) */
@@ -173,6 +173,43 @@ int fpng_amd_encode_batch_async(fpng_amd_encoder *enc, const fpng_amd_image *ima
 int fpng_amd_encode_submit(fpng_amd_encoder *enc, const fpng_amd_image *images, uint32_t n, uint32_t flags, uint64_t *ticket);
 int fpng_amd_encode_wait(fpng_amd_encoder *enc, uint64_t ticket, fpng_amd_result *results, uint32_t n);
 int fpng_amd_encode_query(fpng_amd_encoder *enc, uint64_t ticket);
+
+/* ---- device images in other pixel layouts: strided, bottom-up, BGR(A), padded alpha -- encoded where they lie, without a
+ *      repacking copy.  The file is byte for byte the one fpng_encode_image_to_memory() writes for the same pixels repacked as
+ *      R,G,B[,A] rows.  A format fixes the source bytes per pixel, the PNG's channel count and where R, G, B (and A) sit in the
+ *      source pixel (X = a byte that is ignored):
+ *        RGB  BGR                     3 source bytes, 3-channel PNG
+ *        RGBA BGRA ARGB ABGR          4 source bytes, 4-channel PNG
+ *        RGBX BGRX XRGB XBGR          4 source bytes, 3-channel PNG
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encode_submit_ex with dlsym. ---- */
+#define FPNG_AMD_SRC_RGB 0u
+#define FPNG_AMD_SRC_BGR 1u
+#define FPNG_AMD_SRC_RGBA 2u
+#define FPNG_AMD_SRC_BGRA 3u
+#define FPNG_AMD_SRC_ARGB 4u
+#define FPNG_AMD_SRC_ABGR 5u
+#define FPNG_AMD_SRC_RGBX 6u
+#define FPNG_AMD_SRC_BGRX 7u
+#define FPNG_AMD_SRC_XRGB 8u
+#define FPNG_AMD_SRC_XBGR 9u
+#define FPNG_AMD_SRC_COUNT 10u
+
+typedef struct fpng_amd_image_ex {
+    const void *d_pixels; /* DEVICE pointer to the first byte of the TOP row's first source pixel */
+    int64_t row_pitch;    /* signed bytes from one row to the next; 0 = packed (w * source bytes).  Negative: a bottom-up buffer
+                           * (d_pixels = its last row) is encoded top-down */
+    uint32_t w, h, format; /* format: FPNG_AMD_SRC_* */
+    uint8_t *d_out;       /* DEVICE pointer, 16-byte aligned, receives the whole .png file */
+    size_t out_cap;       /* >= fpng_amd_max_encoded_size(w, h, the format's channel count) */
+} fpng_amd_image_ex;
+
+/* fpng_amd_encode_submit() for images described by fpng_amd_image_ex.  One submission may mix formats, pitches and channel
+ * counts; its ticket works with fpng_amd_encode_wait / _query / _finish / _join like any other.  Rules, all checked before
+ * anything is launched (a failed call enqueues nothing and hands out no ticket): a known format; |row_pitch| >= w * source
+ * bytes; 4-byte sources need d_pixels and row_pitch to be multiples of 4 (3-byte sources may start and be pitched at any byte);
+ * w, h and out_cap as for fpng_amd_encode_submit with the format's channel count.  Rows are not read past w pixels: pitch
+ * padding and X bytes never reach the file. */
+int fpng_amd_encode_submit_ex(fpng_amd_encoder *enc, const fpng_amd_image_ex *images, uint32_t n, uint32_t flags, uint64_t *ticket);
 
 /* Device-side join: the encoder's stream waits (no host wait) for every submission made so far. */
 int fpng_amd_encoder_join(fpng_amd_encoder *enc);

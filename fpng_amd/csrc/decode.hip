@@ -194,14 +194,10 @@ template <int WAVES> __device__ __forceinline__ uint32_t block_sum(uint32_t v, u
     return r;
 }
 
-#ifndef FPNG_DEC_PERSISTENT // 1: a few workgroups per compute unit loop over the blocks; 0: one workgroup per block
-#define FPNG_DEC_PERSISTENT 0
-#endif
-
 // ---- token records (decode_core.h): where a subsequence's settling decode leaves what it decoded, an 8-byte entry per step of the
-//      walk.  The 64 lanes of a wave write side by side -- entry k of lane l at 8-byte word k * 64 + l of the wave's chunk -- and
-//      walk in step, so their stores fill whole lines.  A step that decoded nothing plain leaves its (empty) entry where the next
-//      step's will go. ----
+//      walk.  Entry k of lane l lies at 8-byte word (k / 4) * 256 + (l / 8) * 32 + (k % 4) * 8 + l % 8 of the wave's chunk (rec_index):
+//      eight lanes' entries of one step side by side, their next three steps' behind them, so the lanes, walking in step, fill whole
+//      lines.  A step that decoded nothing plain leaves its (empty) entry where the next step's will go. ----
 typedef __attribute__((address_space(1))) uint64_t gu64e;
 struct TokOut {
     gu64e *col; // the subsequence's entry 0 (decode_core.h: rec_index)
@@ -268,9 +264,6 @@ __device__ __forceinline__ PhaseMap rec_map(const DecBlockRec &r)
 // ---- synchronisation ----
 constexpr uint32_t kGatherMin = 4; // threads of a workgroup to correct from which on they are gathered into one wave (dec_sync_kernel<true>)
 enum : uint32_t { kLeftMany = 1, kLeftCrawling = 2 }; // DecBlockRec::left: why round 0 left the workgroup unsettled
-#ifndef FPNG_DEC_PREFILTER // 0: the border rounds walk over their blocks one check after the other (A/B builds)
-#define FPNG_DEC_PREFILTER 1
-#endif
 #ifndef FPNG_DEC_PAD_LDS
 #define FPNG_DEC_PAD_LDS 0
 #endif
@@ -306,7 +299,7 @@ __global__ __launch_bounds__(kSubBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
     // (round 2 is launched blind behind round 1: when round 1 rewrote no record there is nothing for it to find)
     if (CAND && round == 2 && !*changed) return;
     __shared__ uint32_t open_bits[CAND ? kSubBlock / 32 : 1];
-    if (CAND && round && FPNG_DEC_PREFILTER) {
+    if (CAND && round) {
         const uint32_t bi = blockIdx.x + t * gridDim.x;
         bool open = false;
         if (bi < n_blocks && (first_block + bi) * kSubBlock < total_subs) {
@@ -322,7 +315,7 @@ __global__ __launch_bounds__(kSubBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
         __syncthreads();
     }
     for (uint32_t bi = blockIdx.x; bi < n_blocks; bi += gridDim.x) {
-        if (CAND && round && FPNG_DEC_PREFILTER) {
+        if (CAND && round) {
             const uint32_t k = (bi - blockIdx.x) / gridDim.x;
             if (k < (uint32_t)kSubBlock && !((open_bits[k >> 5] >> (k & 31u)) & 1u)) continue; // (blocks behind the kSubBlock-th are looked at the old way)
         }
@@ -1429,7 +1422,7 @@ void launch_dec_fetch(hipStream_t s, const DecFileRef *files, uint32_t n, uint32
     hipLaunchKernelGGL(dec_fetch_kernel, dim3(n), dim3(kDecBlock), 0, s, files, head, tail, out);
 }
 
-// (the synchronisation and the emit run as persistent workgroups, `resident` of them: a few per compute unit)
+// (round 0 runs one workgroup per block; the border rounds run as persistent workgroups, `resident` of them: a few per compute unit)
 void launch_dec_sync(hipStream_t s, uint32_t resident, const DecJob *jobs, uint32_t n_jobs, uint32_t first_block, uint32_t n_blocks, uint32_t total_subs, uint32_t round,
                      DecSubArrays a, DecBlockRec *recs, uint32_t *changed, uint32_t *multi)
 {
@@ -1441,8 +1434,7 @@ void launch_dec_sync(hipStream_t s, uint32_t resident, const DecJob *jobs, uint3
     if (round)
         hipLaunchKernelGGL(dec_sync_kernel<true>, dim3(std::min(n_blocks, resident)), block, 0, s, jobs, n_jobs, first_block, n_blocks, total_subs, round, a, recs, changed, multi);
     else
-        hipLaunchKernelGGL(dec_sync_kernel<false>, dim3(FPNG_DEC_PERSISTENT ? std::min(n_blocks, resident) : n_blocks), block, 0, s, jobs, n_jobs, first_block, n_blocks, total_subs, round, a,
-                           recs, changed, multi);
+        hipLaunchKernelGGL(dec_sync_kernel<false>, dim3(n_blocks), block, 0, s, jobs, n_jobs, first_block, n_blocks, total_subs, round, a, recs, changed, multi);
 }
 void launch_dec_offsets(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t first_block, uint32_t n_blocks, uint32_t total_subs, const DecJob *group_jobs,
                         uint32_t n_group_jobs, DecSubArrays a, const DecBlockRec *recs, uint64_t *block_off, uint32_t *status, uint32_t *eob_index)

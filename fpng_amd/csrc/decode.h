@@ -16,6 +16,14 @@ constexpr uint32_t kDecLeadIn = FPNG_DEC_LEADIN; // bits a subsequence's first d
 #endif
 constexpr uint32_t kDecUnfRows = FPNG_DEC_UNF_ROWS; // rows per segment of the Up filter's undoing (held in registers)
 enum : uint32_t { kDecNotConverged = 1u, kDecBadStream = 2u, kDecBadFilter = 8u, kDecStalled = 16u, kDecStoredOdd = 32u, kDecSawEob = 0x100u };
+// dec_unfilter_kernel's own findings, bits of their own: a tile's walk met a bad match (kEmitBadStream of decode_core.h) or a match at
+// a row's first pixel (kEmitLeaveToCpu), or its look-back gave up waiting for a lower segment.  The host reads them as kDecBadStream,
+// kDecStalled, kDecStalled (decode_api.cpp: dec_result).
+enum : uint32_t { kDecTileBadStream = 4u, kDecTileLeaveToCpu = 64u, kDecTileStalled = 128u };
+// the bits for which dec_unfilter_kernel skips a file's tiles in the batch path: set only by kernels in FRONT of its launch, never
+// by the kernel itself, so that every thread of every workgroup reads the same answer (a tile that skips publishes no look-back granule)
+constexpr uint32_t kDecUnfSkipMask = kDecNotConverged | kDecBadStream | kDecStalled;
+static_assert(!(kDecUnfSkipMask & (kDecTileBadStream | kDecTileLeaveToCpu | kDecTileStalled | kDecBadFilter)), "dec_unfilter_kernel must not set the bits it skips on");
 
 struct DecJob {
     const uint8_t *z;         // device: the zlib stream (IDAT payload) from the dword its first byte (0x78) lies in; readable up to z_bytes + 16 rounded down to a dword

@@ -1132,10 +1132,12 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
         job.sub_base = uni32(job.sub_base);
         job.w = uni32(job.w), job.h = uni32(job.h), job.bpl = uni32(job.bpl), job.src_c = uni32(job.src_c), job.dst_c = uni32(job.dst_c), job.nseg = uni32(job.nseg), job.mode = uni32(job.mode);
         // (only bits that the kernels in FRONT of this one set decide: every workgroup must come to the same conclusion about a
-        //  file, or a later segment would wait for an earlier one that was skipped -- the checks below have bits of their own.
-        //  skip_mask = those bits; 0 where kernels that set them run NEXT to this launch -- the streamed form undoes a piece's rows
-        //  on a stream of its own while the next piece is decoded: there every workgroup runs and publishes, whatever the status
-        //  word says by then; a damaged file's rows are garbage either way and its status says so)
+        //  file, or a later segment would wait for an earlier one that was skipped.  This kernel's own findings -- the tile's walk,
+        //  the filter bytes, the look-back -- set other bits (decode.h: kDecTile*, kDecBadFilter; the static_assert there keeps them
+        //  out of kDecUnfSkipMask), so the word's skip bits are the same for every thread of the launch.  skip_mask = kDecUnfSkipMask;
+        //  0 where kernels that set those bits run NEXT to this launch -- the streamed form undoes a piece's rows on a stream of its
+        //  own while the next piece is decoded: there every workgroup runs and publishes, whatever the status word says by then; a
+        //  damaged file's rows are garbage either way and its status says so)
         if (job.mode != 0 || (status[ji] & skip_mask)) return;
         const uint32_t ncol = (job.bpl + 3) / 4;
         const uint32_t sc = job.src_c, dc = job.dst_c, lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
@@ -1155,7 +1157,7 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
             lds_u32 *bm = (lds_u32 *)mask_mem, *epx = (lds_u32 *)epx_mem;
             const uint32_t err = sc == 4 ? fill_tile<4>(job, placed, last_sub, y0, nrows, cb, ncb, cbw, tile, bm, epx, s_first, s_i0, s_res, item0)
                                          : fill_tile<3>(job, placed, last_sub, y0, nrows, cb, ncb, cbw, tile, bm, epx, s_first, s_i0, s_res, item0);
-            if (err) atomicOr(&status[ji], err);
+            if (err) atomicOr(&status[ji], (err & kEmitBadStream ? kDecTileBadStream : 0u) | (err & kEmitLeaveToCpu ? kDecTileLeaveToCpu : 0u));
             __syncthreads();
             if (sc == 4) propagate_matches<4>(tile, bm, epx, nrows, s_i0); else propagate_matches<3>(tile, bm, epx, nrows, s_i0);
         }
@@ -1209,7 +1211,7 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
                     carry = add_bytes(carry, (uint32_t)x);
                     if (((uint32_t)(x >> 32) & 3u) == 2u) break;
                 }
-                if (stalled) atomicOr(&status[ji], kDecStalled);
+                if (stalled) atomicOr(&status[ji], kDecTileStalled);
                 if (sg + 1 < job.nseg)
                     __hip_atomic_store(mine, ((unsigned long long)(epoch << 2 | 2u) << 32) | add_bytes(carry, p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -1455,7 +1457,7 @@ void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, Dec
 {
     if (n_items)
         hipLaunchKernelGGL(dec_unfilter_kernel, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch,
-                           concurrent_status ? 0u : (kDecNotConverged | kDecBadStream | kDecStalled));
+                           concurrent_status ? 0u : kDecUnfSkipMask);
 }
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks)

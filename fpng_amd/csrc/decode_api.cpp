@@ -199,8 +199,9 @@ int file_status(const Parsed &p, int st, uint64_t need) { return !p.status && ne
 // A dynamic file's result from its device status word (stored files: kDecStoredOdd, collect_results())
 int dec_result(uint32_t st)
 {
-    if (st & (kDecNotConverged | kDecStalled)) return FPNG_AMD_DECODE_UNDECIDED; // (nothing else is known then: "invalid" may be a speculative decode's)
-    return ((st & (kDecBadStream | kDecBadFilter)) || !(st & kDecSawEob)) ? fpng::FPNG_DECODE_NOT_FPNG : 0; // (no kDecSawEob: the stream never ended)
+    // (nothing else is known then: "invalid" may be a speculative decode's; a match at a row's first pixel is the CPU decoder's)
+    if (st & (kDecNotConverged | kDecStalled | kDecTileLeaveToCpu | kDecTileStalled)) return FPNG_AMD_DECODE_UNDECIDED;
+    return ((st & (kDecBadStream | kDecTileBadStream | kDecBadFilter)) || !(st & kDecSawEob)) ? fpng::FPNG_DECODE_NOT_FPNG : 0; // (no kDecSawEob: the stream never ended)
 }
 
 // The job record of a parsed file; its pointers are the caller's to set

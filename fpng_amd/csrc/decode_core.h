@@ -406,7 +406,7 @@ FPNG_DEC_HD uint32_t info_nrec(uint32_t v) { return (v >> 13) & 1023u; }
 // of 48 rows x one block of columns, and fills each tile's rows from the records of the subsequences that cover them.  A WINDOW =
 // the bytes of one row that one tile holds: column block cb of row y covers the row's bytes [xw, xe), xw = cb ? 1 + cb * cbw : 0 (the
 // first block also holds the row's filter byte), xe = min(1 + (cb + 1) * cbw, stride); a window never crosses a row end.
-enum : uint32_t { kEmitBadStream = 2u, kEmitLeaveToCpu = 16u }; // (= kDecBadStream, kDecStalled of decode.h)
+enum : uint32_t { kEmitBadStream = 2u, kEmitLeaveToCpu = 16u }; // (the host reads them as kDecBadStream, kDecStalled of decode.h; dec_unfilter_kernel records them as kDecTile*)
 struct Window {
     uint64_t ws;   // stream offset of its first byte
     uint32_t wlen; // its bytes

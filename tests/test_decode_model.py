@@ -436,3 +436,66 @@ def test_periodic_streams_with_many_phases():
 
 
 kRefixRounds = 3
+
+
+def _first_changed_token(s, f):
+    """index of the LargeStream token in whose bits `f`'s stream first differs from the original's (None: the same stream)"""
+    import struct
+    ln = struct.unpack(">I", f[s.ofs: s.ofs + 4])[0]
+    z = int.from_bytes(f[s.ofs + 8: s.ofs + 8 + ln - 4], "little")  # (without the Adler-32)
+    x = z ^ s.zint
+    if not x:
+        return None
+    return int(np.searchsorted(s.bitpos, (x & -x).bit_length() - 1, side="right")) - 1
+
+
+def test_mutate_large_puts_its_edit_in_the_rows_asked_for():
+    """token_mutator.mutate_large(rows=, kind=): the first bit that differs from the original stream lies in a token whose output row
+    is one of the rows asked for, for every kind of edit, at the top, in the middle and at the bottom of 1- and 2-pass files."""
+    import fpng_amd
+    import token_mutator as TM
+    rng = np.random.default_rng(31)
+    made = {}
+    import ui_images
+    for kind, w, h, c, flags in (("grad", 600, 160, 4, 0), ("glyphs", 640, 200, 3, 1), ("blocks", 600, 200, 4, 0)):
+        img = ui_images.glyphs(w, h, c, seed=5) if kind == "glyphs" else fpng_amd.synth_image(kind, w, h, c)
+        png = oracle().encode(np.ascontiguousarray(img).reshape(-1), w, h, c, flags)
+        s = TM.LargeStream(png, plan, emul())
+        for name in TM.LARGE_KINDS:
+            for rows in ((0, 5), (70, 71), (h - 3, h - 1)):
+                for _ in range(30):
+                    got, f = TM.mutate_large(s, rng, rows=rows, kind=name)
+                    assert got in (name, "none"), (got, name)
+                    if f is None:
+                        continue
+                    i = _first_changed_token(s, f)
+                    if i is None:
+                        assert name in ("literal", "filter_byte")  # (a value drawn equal to the one it replaces)
+                        continue
+                    assert rows[0] <= s.out_pos[i] // s.stride <= rows[1], (name, rows, i, int(s.out_pos[i]))
+                    made[name] = made.get(name, 0) + 1
+                    break
+    # (merge wants two neighbouring matches of 258 bytes at most together, which fpng's encoders hardly ever write)
+    assert set(made) >= set(TM.LARGE_KINDS) - {"merge"}, repr(made)
+
+
+def test_mutate_large_draws_as_before_by_default():
+    """Without rows= and kind=, mutate_large makes the same edits from the same seeds as its first version did (tests chose their
+    seeds by the outcomes): names, the files' digests and the generator's state afterwards, recorded from that version."""
+    import hashlib
+    import fpng_amd
+    import token_mutator as TM
+    recorded = {
+        "grad": ("e7d4e0ffaea2", 382722, 3110073619114516771, "c323eb32432b13f7"),
+        "blocks": ("8e9667eec645", 1370, 3539212668077324189, "939bf3490fa4bc78"),
+    }
+    for kind, w, h, c, fl, seed in (("grad", 600, 160, 4, 0, 5), ("blocks", 500, 130, 3, 1, 6)):
+        png = oracle().encode(np.asarray(fpng_amd.synth_image(kind, w, h, c)).reshape(-1), w, h, c, fl)
+        s = TM.LargeStream(png, plan, emul())
+        rng = np.random.default_rng(seed)
+        got = []
+        for _ in range(40):
+            name, f = TM.mutate_large(s, rng)
+            got.append((name, hashlib.blake2b(f, digest_size=6).hexdigest() if f is not None else None))
+        digest = hashlib.blake2b(repr(got).encode(), digest_size=8).hexdigest()
+        assert (hashlib.blake2b(png, digest_size=6).hexdigest(), s.n, int(rng.integers(0, 1 << 62)), digest) == recorded[kind], (kind, got, digest)

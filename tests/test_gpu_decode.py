@@ -540,9 +540,9 @@ def test_a_match_at_a_rows_first_pixel_is_left_to_the_cpu_decoder(enc):
 def test_edited_token_streams_get_the_references_answer(enc, device):
     """tests/token_mutator.py through the kernels: valid code streams whose tokens bend or break the decoder's semantic rules (matches
     lengthened, split, off a pixel boundary, at a row's first pixel, over the row's end, filter literals changed, the end-of-block
-    symbol moved ...).  Status and pixels of the reference's decoder; where the kernels say UNDECIDED (a match at a row's first
-    pixel), the drop-in's CPU decoder must give them."""
-    from test_decode_model import edited_files
+    symbol moved ...).  Status and pixels of the reference's decoder; the kernels may say UNDECIDED only where their logic does (the
+    emulator at their constants: a match at a row's first pixel ...), and the drop-in's CPU decoder must then give them."""
+    from test_decode_model import CONFIGS, edited_files, emul_decode
     rng = np.random.default_rng(77)
     files = edited_files(rng, 60)
     pngs = [f for _, f in files]
@@ -557,6 +557,7 @@ def test_edited_token_streams_get_the_references_answer(enc, device):
         for (name, png), (st, px, cf) in zip(files, got):
             cst, cpx, w, h, c = judge(png, desired)
             if st == UNDECIDED:
+                assert emul_decode(png, desired, CONFIGS[0], border_rounds=63)[0] == UNDECIDED, name  # (63: the GPU's border rounds)
                 left += 1
                 os.environ["FPNG_AMD_DECODE_CPU"] = "1"
                 try:
@@ -655,7 +656,8 @@ def test_token_edited_megapixel_files(enc, case):
     spans hundreds of workgroups -- a match lengthened over a row's end, off a pixel boundary, an end-of-block symbol moved, a
     filter literal changed ...), through fpng_amd_decode_batch, fpng_amd_decode_batch_device and fpng::fpng_decode_memory (which
     STREAMS the 4K file: more than 8 MiB of IDAT; semantics src/fpng.cpp:2587-2901).  Status and pixels of the reference's decoder
-    at both channel counts; UNDECIDED only where the drop-in's CPU decoder then gives the reference's answer."""
+    at both channel counts; UNDECIDED only for a match at a row's first pixel (lit2match_firstpx), and the drop-in's CPU decoder
+    must then give the reference's answer."""
     import struct
     import fpng_amd
     import test_decode_model as M
@@ -680,6 +682,7 @@ def test_token_edited_megapixel_files(enc, case):
         for got in (enc.decode_batch([f for _, f in files], desired), enc.decode_device(_device_files([f for _, f in files], shift=2), desired, dims)):
             for (name, f), (cst, cpx, *_), (st, px, _) in zip(files, judged, got):
                 if st == UNDECIDED:
+                    assert name == "lit2match_firstpx", (name, st, cst)
                     os.environ["FPNG_AMD_DECODE_CPU"] = "1"
                     try:
                         st, dpx, *_ = dropin.decode(f, desired)

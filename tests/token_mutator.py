@@ -297,13 +297,26 @@ class LargeStream:
         return head + struct.pack(">I", len(z)) + b"IDAT" + z + struct.pack(">I", zlib.crc32(b"IDAT" + z)) + struct.pack(">I", 0) + b"IEND" + struct.pack(">I", zlib.crc32(b"IEND"))
 
 
-def mutate_large(s, rng):
+LARGE_KINDS = {"lit2match": 0, "lit2match_firstpx": 1, "split": 2, "merge": 3, "match_takes_next_pixel": 4, "match_gives_last_pixel": 5,
+               "literal": 6, "filter_byte": 7, "match_over_row_end": 8, "match_plus_a_byte": 9, "match_minus_a_byte": 9}
+
+
+def mutate_large(s, rng, rows=None, kind=None):
     """-> (name, file) or (name, None): ONE local edit of a LargeStream, most of them keeping the byte count (the edit itself is
-    what the decoders judge), at a random place of the stream"""
+    what the decoders judge), at a random place of the stream.  rows=(y0, y1): the edited token's output row (out_pos // stride)
+    lies in y0 .. y1; kind: a name of LARGE_KINDS, the edit to make (None: drawn).  With both None the draws are those of the
+    first version of this function (tests chose their seeds by the outcomes)."""
     C, stride, n = s.c, s.stride, s.n
-    kind = int(rng.integers(0, 10))
-    i = int(rng.integers(0, n - 1))
-    lo, hi = i, min(n - 1, i + 4000)
+    want = kind
+    kind = int(rng.integers(0, 10)) if want is None else LARGE_KINDS[want]
+    if rows is None:
+        i = int(rng.integers(0, n - 1))
+        lo, hi = i, min(n - 1, i + 4000)
+    else:  # (every token of those rows is a candidate; the end-of-block symbol never is)
+        lo, hi = (int(np.searchsorted(s.out_pos, y * stride)) for y in (rows[0], rows[1] + 1))
+        hi = min(hi, n - 1)
+        if hi <= lo:
+            return "none", None
     k, v, col = s.kind[lo:hi], s.value[lo:hi].astype(np.int64), (s.out_pos[lo:hi] % stride)
     px_start = (col >= 1) & ((col - 1) % C == 0)
     lits = k == 0
@@ -369,8 +382,8 @@ def mutate_large(s, rng):
     if j is None or j + 2 >= n or s.kind[j + 1] != 0:
         return "none", None
     L = int(s.value[j])
-    if L + 1 <= 258 and rng.random() < 0.5:
+    if L + 1 <= 258 and (rng.random() < 0.5 if want is None else want == "match_plus_a_byte"):
         return "match_plus_a_byte", s.splice(j, j + 2, [("match", L + 1, 0)])
-    if L - 1 >= 3:
+    if L - 1 >= 3 and want != "match_plus_a_byte":
         return "match_minus_a_byte", s.splice(j, j + 1, [("match", L - 1, 0), ("lit", int(rng.integers(0, 256)))])
     return "none", None

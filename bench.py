@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the fpng encode hot path (and of the GPU decoder on the encoder's output) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|4k|1080p] [--batch B] [--flags F] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8k|4k|1080p] [--batch B] [--flags F] [--dump-outputs DIR] [--full]
 
 A "step" is one submission of the hot path (fpng_encode_image_to_memory semantics, 1-pass) over a
 batch of B synthetic device-resident images; inputs and outputs live in HBM for the whole timed
@@ -18,8 +18,12 @@ value = all ranks' pixels / that time, scaling = weak.
 computed (the PNG files a caller receives: sizes, modes, statuses, CRC-32s and a fixed sample of
 their bytes) as DIR/<name>.npy, so that two builds can be compared output for output.
 
-Rank 0 prints ONE JSON line, including
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and
+prints the line: value, ms_per_step, runs, config.  --full adds what takes work of its own beyond that:
+  parity       : every file of the last timed step against the reference's golden vectors (tests/golden/)
   roofline     : dominant kernel's algorithmic bytes / its HIP-event-measured duration vs 8 TB/s
+  decode       : the GPU decoder on the files of the last timed step (--mode decode makes it the line)
+  end_to_end   : host pixels -> host PNG, in fresh processes, PCIe inclusive
   cpu_baseline : the reference's own SSE4.1 encoder (oracle/_ref) timed on one host core on a
                  bounded sample of the same workload (falls back to the C port in oracle/)
 """
@@ -68,6 +72,9 @@ def parse():
                          "value = the median region, `runs` / `spread` report all of them (a single 10 ms region cannot show a 5 %% change)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="--mode batch: write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode batch / decode: also the golden-vector parity check, the per-kernel roofline, the `decode` object, "
+                         "end_to_end and the CPU baselines (a plain run times the steps and prints the headline alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--end-to-end-only", default=None, choices=["cabi", "dropin"], help="(internal) print that part of the end_to_end object for --workload WxHxC and exit")
     ap.add_argument("--device", type=int, default=0)
@@ -759,52 +766,17 @@ def main():
 
     png_bytes = sum(r[0] for r in res)
     assert all(r[2] == 0 for r in res)
-    # self-check: EVERY image of the last timed submission's output set against the reference's bytes
-    # (tests/golden/batches.json / kat.json: sha256 of the unmodified reference encoder's file for this input)
-    parity_checked = verify_outputs(args, rank, w, h, c, out_sets[(args.steps - 1) % n_sets], [r[0] for r in res])
-    if args.dump_outputs:  # (before the profiling steps below, which write into out_sets[0])
+    if args.dump_outputs:  # (before the profiling steps of --full, which write into out_sets[0])
         dump_outputs(args.dump_outputs, out_sets[(args.steps - 1) % n_sets], res, rank, world)
     pixels_per_step = B * w * h
     value = world * pixels_per_step * args.steps / elapsed / 1e6
     run_values = [round(world * pixels_per_step * args.steps / r / 1e6, 1) for r in runs]
 
-    # ---- per-kernel durations with HIP events on the encoder's own stream (untimed extra steps) ----
-    enc.set_profiling(True)
-    phases = np.zeros(8)
-    reps = 5
-    for _ in range(reps):
-        step()
-        phases += np.array(enc.last_phase_ms())
-    phases /= reps
-    enc.set_profiling(False)
-    names = enc.phase_names()
-    phase_ms = {n: round(float(phases[i]), 4) for i, n in enumerate(names)}
-    alg_bytes = B * w * h * c + png_bytes  # input read once + PNG written once
-    dom = max((k for k in names if k in ("encode_rows", "assemble", "hist")), key=lambda k: phase_ms[k])
-    dom_s = phase_ms[dom] / 1e3
-    achieved = alg_bytes / dom_s / 1e9
-    kernels_s = sum(phase_ms[k] for k in names) / 1e3
-    traffic, traffic_src = committed_traffic(f"{dom}_kernel", workload_tag(args))  # PMC passes of THIS command, if committed
-    roofline = {"bound": "hbm", "kernel": f"{dom}_kernel", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "frac_of_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": phase_ms[dom],
-                "all_kernels_ms": round(kernels_s * 1e3, 4),
-                "pipeline_frac": round(alg_bytes / kernels_s / 1e9 / HBM_PEAK_GBS, 4),
-                "step_frac": round(alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),  # the timed, pipelined step against the same peak
-                "phase_ms": phase_ms}
-    # what the whole chain moves per step (all kernels, PMC) and the rate it moves it at in the timed, pipelined regions: the
-    # number to hold against what plain streaming kernels reach on the same read/write mix (profiles/r03_mix_probe.txt: 5.1 TB/s)
-    chain = committed_chain_traffic(workload_tag(args))
-    if chain:
-        roofline["chain_traffic"] = chain
-        roofline["chain_traffic_rate_GBs"] = round(chain / (elapsed / args.steps) / 1e9, 1)
-
     line = {
         "metric": f"encode megapixels/sec ({scope_name(world)}), {PASS_NAME.get(args.flags, 'flags=%d' % args.flags)}, device-resident",
         "value": round(value, 1), "unit": "MP/s", "value_MiPs": round(value * 1e6 / 2 ** 20, 1), "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "prewarm": args.prewarm, "prewarm_bursts": 1 if (args.prewarm + args.warmup) else 0,  # (+ one untimed burst of `steps` submissions shaped like a timed region)
-        "parity_checked": bool(parity_checked) if parity_checked is not None else None,
-        "parity_images": parity_checked, "runs": run_values,
+        "runs": run_values,
         "spread": round((max(run_values) - min(run_values)) / value, 4) if len(run_values) > 1 else None,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4), "per_rank_ms_per_step": per_rank_ms, "higher_is_better": True, "scaling": "weak",
         "regions": max(1, args.regions), "timed_steps": max(1, args.regions) * args.steps,
@@ -816,8 +788,46 @@ def main():
                    # how the submissions' chains share the GPU (fpng_amd_runtime_info(): the library asks the HIP runtime for two hardware
                    # queues when it is loaded before the process's first HIP call, unless the variable is set already)
                    "lanes": enc.lanes, "hw_queues": rt["hw_queues"], "hw_queue_source": rt["hw_queue_source"]},
-        "roofline": roofline,
     }
+    if args.full:
+        # self-check: EVERY image of the last timed submission's output set against the reference's bytes
+        # (tests/golden/batches.json / kat.json: sha256 of the unmodified reference encoder's file for this input)
+        parity_checked = verify_outputs(args, rank, w, h, c, out_sets[(args.steps - 1) % n_sets], [r[0] for r in res])
+        line["parity_checked"] = bool(parity_checked) if parity_checked is not None else None
+        line["parity_images"] = parity_checked
+
+        # ---- per-kernel durations with HIP events on the encoder's own stream (untimed extra steps) ----
+        enc.set_profiling(True)
+        phases = np.zeros(8)
+        reps = 5
+        for _ in range(reps):
+            step()
+            phases += np.array(enc.last_phase_ms())
+        phases /= reps
+        enc.set_profiling(False)
+        names = enc.phase_names()
+        phase_ms = {n: round(float(phases[i]), 4) for i, n in enumerate(names)}
+        alg_bytes = B * w * h * c + png_bytes  # input read once + PNG written once
+        dom = max((k for k in names if k in ("encode_rows", "assemble", "hist")), key=lambda k: phase_ms[k])
+        dom_s = phase_ms[dom] / 1e3
+        achieved = alg_bytes / dom_s / 1e9
+        kernels_s = sum(phase_ms[k] for k in names) / 1e3
+        traffic, traffic_src = committed_traffic(f"{dom}_kernel", workload_tag(args))  # PMC passes of THIS command, if committed
+        roofline = {"bound": "hbm", "kernel": f"{dom}_kernel", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "frac_of_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": phase_ms[dom],
+                    "all_kernels_ms": round(kernels_s * 1e3, 4),
+                    "pipeline_frac": round(alg_bytes / kernels_s / 1e9 / HBM_PEAK_GBS, 4),
+                    "step_frac": round(alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),  # the timed, pipelined step against the same peak
+                    "phase_ms": phase_ms}
+        # what the whole chain moves per step (all kernels, PMC) and the rate it moves it at in the timed, pipelined regions: the
+        # number to hold against what plain streaming kernels reach on the same read/write mix (profiles/r03_mix_probe.txt: 5.1 TB/s)
+        chain = committed_chain_traffic(workload_tag(args))
+        if chain:
+            roofline["chain_traffic"] = chain
+            roofline["chain_traffic_rate_GBs"] = round(chain / (elapsed / args.steps) / 1e9, 1)
+        line["roofline"] = roofline
+
     # ---- the way back: the files of the last submission, still in device memory, decoded to pixels in device memory ----
     def all_max(el):
         if distributed:
@@ -826,12 +836,12 @@ def main():
             el = float(t.item())
         return el
 
-    last_set = out_sets[(args.steps - 1) % n_sets]
-    pngs = [o[: r[0]] for o, r in zip(last_set, res)]
-    dec = decode_bench(args, enc, imgs, pngs, w, h, c, rank, world, barrier, all_max, rank == 0 and world == 1 and not args.no_cpu_baseline)
-    if True:
+    if args.full or args.mode == "decode":
+        last_set = out_sets[(args.steps - 1) % n_sets]
+        pngs = [o[: r[0]] for o, r in zip(last_set, res)]
+        dec = decode_bench(args, enc, imgs, pngs, w, h, c, rank, world, barrier, all_max, args.full and rank == 0 and world == 1 and not args.no_cpu_baseline)
         if args.mode == "decode":  # the line is the decoder's; what the encoder did in this run goes along
-            enc_part = {k: line[k] for k in ("metric", "value", "unit", "ms_per_step", "parity_checked", "parity_images", "roofline")}
+            enc_part = {k: line[k] for k in ("metric", "value", "unit", "ms_per_step", "parity_checked", "parity_images", "roofline") if k in line}
             line = dict(line, **{k: dec[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "runs", "parity_checked", "parity_images", "roofline")})
             line["spread"] = round((max(dec["runs"]) - min(dec["runs"])) / dec["value"], 4) if len(dec["runs"]) > 1 else None
             line["warmup"], line["prewarm"] = 3, 0
@@ -843,7 +853,7 @@ def main():
             line["encode"] = enc_part
         else:
             line["decode"] = dec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode != "decode":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode != "decode":
         line["end_to_end"] = end_to_end(local_rank, w, h, c, args.kind, args.flags)
         line["cpu_baseline"] = cpu_baseline(w, h, c, args.kind, args.flags, args.cpu_reps)
         line["speedup_vs_cpu_1core"] = round(value / line["cpu_baseline"]["value"], 1)

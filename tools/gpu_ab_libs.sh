@@ -9,6 +9,6 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['value'],
 for i in 1 2 3; do
   [ -d r1tree ] && (cd r1tree && python bench.py --no-cpu-baseline --steps 30 --warmup 5 $ARGS 2>/dev/null | p r1)
   for lib in "$@"; do
-    FPNG_AMD_LIB=$R/fpng_amd/lib/$lib python bench.py --no-cpu-baseline --steps 30 --warmup 5 $ARGS 2>/dev/null | p $lib
+    FPNG_AMD_LIB=$R/fpng_amd/lib/$lib python bench.py --full --no-cpu-baseline --steps 30 --warmup 5 $ARGS 2>/dev/null | p $lib
   done
 done

@@ -4,7 +4,7 @@
 RND=$1
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; O=$R/gpurun_out
 run() { tag=$1; shift
-  timeout 300 python bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>$O/bench_${RND}_$tag.err | grep "^{" > $O/bench_${RND}_$tag.json
+  timeout 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>$O/bench_${RND}_$tag.err | grep "^{" > $O/bench_${RND}_$tag.json
   python -c "import json; d=json.load(open('$O/bench_${RND}_$tag.json')); print('$tag', d['value'], d['ms_per_step'], d['runs'], d['parity_checked'], d['roofline']['phase_ms'])"
   bash tools/gpu_profile_round.sh ${RND}_$tag "$@" > /dev/null 2>&1
 }

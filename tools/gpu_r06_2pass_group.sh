@@ -17,7 +17,7 @@ for W in "--workload 8k --batch 8" "--workload 4k --batch 16" "--workload 4k --b
   for L in 4 2; do
     for G in 0 1 2 4; do
       echo "rep $rep: $W flags=1 lanes=$L group=$G" >> $OUT
-      FPNG_AMD_LANES=$L FPNG_AMD_2PASS_GROUP=$G timeout 300 python bench.py $W --flags 1 --steps 20 --warmup 4 --no-cpu-baseline --decode-steps 1 --regions 3 > $O/tmp_2pg.json 2> $O/tmp_2pg.err
+      FPNG_AMD_LANES=$L FPNG_AMD_2PASS_GROUP=$G timeout 300 python bench.py $W --flags 1 --steps 20 --warmup 4 --full --no-cpu-baseline --decode-steps 1 --regions 3 > $O/tmp_2pg.json 2> $O/tmp_2pg.err
       line $O/tmp_2pg.json >> $OUT
     done
   done

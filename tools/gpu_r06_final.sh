@@ -7,6 +7,6 @@ bash tools/gpu_session.sh $TAG
 bash tools/gpu_profile_round.sh ${TAG}_8k > /dev/null 2>&1
 SKIP_CAL=1 bash tools/gpu_profile_round.sh ${TAG}_decode_8k --mode decode --decode-steps 3 > /dev/null 2>&1
 cd $R
-timeout 600 python bench.py --mode decode > $O/${TAG}_bench_decode_8k.json 2> $O/${TAG}_bench_decode_8k.err
+timeout 600 python bench.py --mode decode --full > $O/${TAG}_bench_decode_8k.json 2> $O/${TAG}_bench_decode_8k.err
 bash tools/gpu_r06_decode_ab3.sh ${TAG} "_r05dec ." "8K RGBA grad" "4K RGBA grad" "1080p RGB grad" "512x512" "photo" "8K RGBA solid" "8K RGBA blocks" "8K RGBA stripes" "8K RGBA noise" "4K UI" > /dev/null 2>&1
 ls $O | grep $TAG

@@ -44,7 +44,7 @@ fscale = GiB / [v for k, v in cal_f.items() if "calib_read_kernel<unsigned int>"
 wscale = GiB / [v for k, v in cal_w.items() if "calib_write_kernel<unsigned int>" in k][0]
 args = " ".join(sys.argv[4:])
 only = os.environ.get("PROFILE_KERNELS", "")  # e.g. dec_ : the decoder's kernels of a bench.py --mode decode run
-# (the default bench.py run also decodes -- its `decode` object -- and checks pixels with torch: without PROFILE_KERNELS the summary
+# (a bench.py --full run also decodes -- its `decode` object -- and checks pixels with torch: without PROFILE_KERNELS the summary
 #  is the ENCODE chain's, the decoder's kernels have their own file)
 skip = () if only else ("dec_", "at::")
 lines = [f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate runs, --kernel-trace only) -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline {args}".rstrip()

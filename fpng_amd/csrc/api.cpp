@@ -161,6 +161,15 @@ int fpng_amd::check_dims(uint32_t w, uint32_t h, uint32_t c)
     return FPNG_AMD_OK;
 }
 
+static_assert(kStatusStoredTooLarge == FPNG_AMD_STATUS_STORED_TOO_LARGE, "device status code");
+
+int fpng_amd::fail_status(uint32_t status)
+{
+    if (status == FPNG_AMD_STATUS_STORED_TOO_LARGE)
+        return fail(FPNG_AMD_ERR_UNSUPPORTED, "stored blocks past 4 GiB (the reference returns false: src/fpng.cpp:1747-1755)");
+    return fail(FPNG_AMD_ERR_HIP, "device reported an encode failure");
+}
+
 void fpng_amd::make_png_header(uint8_t *hdr, uint32_t w, uint32_t h, uint32_t c)
 {
     // reference src/fpng.cpp:1767-1791.  Only the low 16 bits of each dimension are stored there
@@ -955,7 +964,7 @@ static int host_batch_ring(fpng_amd_encoder *e, const fpng_amd_host_image *imgs,
                 sl->in_flight = false;
             }
             if (res.status) {
-                failed = FPNG_AMD_ERR_HIP;
+                failed = res.status == FPNG_AMD_STATUS_STORED_TOO_LARGE ? FPNG_AMD_ERR_UNSUPPORTED : FPNG_AMD_ERR_HIP;
             } else {
                 uint8_t *dst = imgs[i].out;
                 if (!dst) {

@@ -86,6 +86,8 @@ template <typename T> struct PinnedBuf {
 
 // reference src/fpng.cpp:1670-1680 plus the 32-bit arithmetic limit of :1682-1705
 int check_dims(uint32_t w, uint32_t h, uint32_t c);
+// the error a host path returns for a nonzero fpng_amd_result.status (FPNG_AMD_ERR_UNSUPPORTED for a stored file over 4 GiB)
+int fail_status(uint32_t status);
 // the 58 bytes in front of the zlib stream (reference src/fpng.cpp:1767-1791); the IDAT length (bytes 50..53) is left zero
 void make_png_header(uint8_t *hdr60, uint32_t w, uint32_t h, uint32_t c);
 // first token bit / end-of-block length of the 1-pass table (host copy of the format tables)

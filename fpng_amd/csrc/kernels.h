@@ -56,10 +56,14 @@ struct JobState {
     uint32_t last_unit_bits;
     uint32_t s1, s2;        // Adler raw sums of the job's filtered bytes
     uint32_t adler, crc;
-    uint32_t status;        // nonzero = device-side failure, reported in fpng_amd_result.status
+    uint32_t status;        // nonzero = device-side failure, reported in fpng_amd_result.status (kStatus*)
     uint32_t range_log2;    // log2 of the bytes one assemble/crc block covers (12..16; 0 = 16), chosen by scan_kernel
     uint64_t reserved[2];
 };
+
+// JobState::status: a stored outcome whose 58 + zlib_size exceeds UINT32_MAX (FPNG_AMD_STATUS_STORED_TOO_LARGE): scan_kernel decides
+// it, and assemble / stored_ex / finalize then write nothing of that file
+constexpr uint32_t kStatusStoredTooLarge = 1;
 
 struct Result {
     uint64_t png_size;

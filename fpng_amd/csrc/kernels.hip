@@ -1157,11 +1157,14 @@ __device__ __forceinline__ void scan_job(const Job &job, JobState &st, const Row
     const uint64_t zlib_bytes_no_adler = stored ? (2 + n_filtered + 5 * ((n_filtered + kStoredBlockMax - 1) / kStoredBlockMax))
                                                 : ((s_last + eob_len + 7) >> 3);
     const uint64_t zlib_size = (!job.whole_png && job.band_zlib_size) ? job.band_zlib_size : zlib_bytes_no_adler + 4;
+    // the reference sizes the stored buffer as a uint32_t 58 + zlib size (fpng.cpp:1747): past UINT32_MAX it wraps, write_raw_block
+    // finds no room and the call returns false (:1749-1755).  Refused here; the kernels behind this one write nothing of the file.
+    const bool too_large = stored && job.whole_png && kPngHeaderBytes + zlib_size > 0xFFFFFFFFull;
 
     if (t == 0) {
         st.token_end_bit = s_last;
         st.mode = stored ? 1u : 0u;
-        st.status = 0;
+        st.status = too_large ? kStatusStoredTooLarge : 0u;
         st.zlib_size = zlib_size;
         st.s1 = (uint32_t)S1;
         st.s2 = (uint32_t)S2;
@@ -1181,6 +1184,7 @@ __device__ __forceinline__ void scan_job(const Job &job, JobState &st, const Row
     }
     // a band's counting phase stops here; whole images and band placements prepare the head of the output
     if (!job.whole_png && !(job.flags & 0x100u)) return;
+    if (too_large) return;
 
     // --- PNG header + Deflate block header; assemble_kernel, which places the rows, wants the head followed by zeros
     //     up to the next 16-byte boundary ---
@@ -1422,11 +1426,11 @@ __device__ __forceinline__ void finalize_job(const Job &job, const RowInfo *rows
                                              const uint32_t *pj, const uint32_t *aj, Result &result, uint32_t *red, uint64_t *red64)
 {
     const uint32_t t = threadIdx.x;
-    if (!job.whole_png) {
+    if (!job.whole_png || st.status) { // (a refused file: nothing of it was written)
         if (t == 0) {
             result.png_size = 0;
             result.mode = st.mode;
-            result.status = 0;
+            result.status = job.whole_png ? st.status : 0u;
         }
         return;
     }
@@ -1721,6 +1725,7 @@ __global__ __launch_bounds__(kBlock) void assemble_kernel(const Job *jobs, JobSt
     const bool compressed = uniform(st.mode) == 0u;
     const bool gather = compressed; // (a band that is to be stored gathers nothing: its bytes are in place, only the CRC is taken)
     if (!compressed && job.whole_png && adler_parts) { // the image fell back to stored blocks: this workgroup writes its range of them
+        if (uniform(st.status)) return;                // (stored past 4 GiB: refused by scan_kernel, nothing is written)
         const size_t slot = (size_t)blockIdx.y * max_crc_blocks + blockIdx.x;
         assemble_stored(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
         return;
@@ -1892,7 +1897,7 @@ __global__ __launch_bounds__(kBlock) void stored_ex_kernel(const Job *jobs, cons
     __shared__ uint32_t red[3 * kWavesPerBlock];
     const Job &job = job_of_block(jobs);
     const JobState &st = states[blockIdx.y];
-    if (uniform(st.mode) == 0u) return;
+    if (uniform(st.mode) == 0u || uniform(st.status)) return;
     const int64_t data_begin = kPngHeaderBytes, data_end = (int64_t)(kPngHeaderBytes + st.zlib_size - 4);
     const int64_t end_aligned = (data_end + 15) & ~15ll;
     const uint32_t range_bytes = 1u << uniform(crc_range_log2(st));

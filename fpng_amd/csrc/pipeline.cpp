@@ -258,7 +258,7 @@ int encode_host_serial(fpng_amd_encoder *e, const void *pixels, bool uploaded, u
     if ((rc = fpng_amd_encode_batch_async(e, &im, 1, flags))) return rc;
     fpng_amd_result res;
     if ((rc = fpng_amd_encode_finish(e, &res, 1))) return rc;
-    if (res.status) return fail(FPNG_AMD_ERR_HIP, "device reported an encode failure");
+    if (res.status) return fail_status(res.status);
     *out_size = (size_t)res.png_size;
     uint8_t *out = reserve(user, (size_t)res.png_size); // the size is known before a single output byte moves
     if (!out) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "output buffer too small");

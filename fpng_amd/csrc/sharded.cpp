@@ -157,7 +157,7 @@ extern "C" int fpng_amd_encode_image_sharded(fpng_amd_encoder *e, const fpng_amd
             im.d_pixels = e->d_stage_in.p, im.w = w, im.h = h, im.num_chans = c, im.d_out = d_png, im.out_cap = png_cap;
             fpng_amd_result res;
             if ((rc = fpng_amd_encode_batch_async(e, &im, 1, FPNG_AMD_FORCE_UNCOMPRESSED)) || (rc = fpng_amd_encode_finish(e, &res, 1))) return rc;
-            if (res.status) return fail(FPNG_AMD_ERR_HIP, "device reported an encode failure");
+            if (res.status) return fail_status(res.status);
             *png_size = (size_t)res.png_size;
         } else {
             T_TRY(t->group_begin(t->ctx));

@@ -35,7 +35,9 @@ extern "C" {
 #define FPNG_AMD_ERR_HIP (-3)
 #define FPNG_AMD_ERR_BUFFER_TOO_SMALL (-4)
 #define FPNG_AMD_ERR_OUT_OF_MEMORY (-5)
-#define FPNG_AMD_ERR_UNSUPPORTED (-6)      /* > 4 GiB of filtered bytes: undefined in the reference (src/fpng.cpp:1682-1705) */
+#define FPNG_AMD_ERR_UNSUPPORTED (-6)      /* > 4 GiB of filtered bytes: undefined in the reference (src/fpng.cpp:1682-1705); or an image
+                                            * whose outcome is stored blocks of more than 4 GiB (fpng_amd_result.status
+                                            * FPNG_AMD_STATUS_STORED_TOO_LARGE): the reference returns false there (src/fpng.cpp:1747-1755) */
 #define FPNG_AMD_ERR_IO (-7)               /* a file could not be written (reference src/fpng.cpp:1818-1827 returns false) */
 
 /* ---- encode flags: same bit values as reference src/fpng.h:34-42 ---- */
@@ -149,8 +151,13 @@ typedef struct fpng_amd_image {
 typedef struct fpng_amd_result {
     uint64_t png_size; /* bytes written to d_out */
     uint32_t mode;     /* FPNG_AMD_MODE_* */
-    uint32_t status;   /* 0 = ok */
+    uint32_t status;   /* 0 = ok, else FPNG_AMD_STATUS_* (png_size is then 0 and nothing was written to d_out) */
 } fpng_amd_result;
+
+/* fpng_amd_result.status: the image's outcome is stored blocks (FPNG_FORCE_UNCOMPRESSED, or an incompressible image) and
+ * 58 + zlib size would exceed UINT32_MAX.  The reference sizes that buffer in 32 bits (src/fpng.cpp:1747), finds it too small and
+ * returns false; such a file would also carry a wrapped IDAT length.  The host paths report it as FPNG_AMD_ERR_UNSUPPORTED. */
+#define FPNG_AMD_STATUS_STORED_TOO_LARGE 1u
 
 /*
  * THE HOT PATH.  fpng_encode_image_to_memory() (reference src/fpng.h:48, src/fpng.cpp:1662-1803)

@@ -718,6 +718,10 @@ int fpo_encode(const void *image, uint32_t w, uint32_t h, uint32_t num_chans, ui
     const uint64_t n = ((uint64_t)w * num_chans + 1) * h;
     if (n > 0xFFFFFF00ull) return 0; /* reference arithmetic is 32-bit here (src/fpng.cpp:1682-1705): undefined there */
     if (out_cap < fpo_max_encoded_size(w, h, num_chans)) return 0;
+    /* the stored outcome's buffer, 58 + zlib size, is a uint32_t sum in the reference (src/fpng.cpp:1747): past UINT32_MAX it
+     * wraps, write_raw_block finds no room and the call returns false (:1749-1755) */
+    const int stored_fits = 58 + 6 + n + 5 * ((n + 65534) / 65535) <= 0xFFFFFFFFull;
+    if ((flags & FPO_FORCE_UNCOMPRESSED) && !stored_fits) return 0;
 
     /* byte budget handed to the coder: src/fpng.cpp:1705, :1713-1722 */
     const uint64_t D = ((58 + n + 7) & ~7ull) - 58;
@@ -785,7 +789,10 @@ int fpo_encode(const void *image, uint32_t w, uint32_t h, uint32_t num_chans, ui
         }
         free(scratch);
     }
-    if (!zlen) zlen = write_stored((const uint8_t *)image, w, h, num_chans, z);
+    if (!zlen) {
+        if (!stored_fits) return 0;
+        zlen = write_stored((const uint8_t *)image, w, h, num_chans, z);
+    }
 
     /* container: src/fpng.cpp:1764-1800 */
     static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A};

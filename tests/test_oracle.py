@@ -257,3 +257,56 @@ def test_oracle_vs_reference_on_skewed_histograms():
     for img, w, h, c in imgs:
         for flags in (0, 1):
             assert oracle().encode(img, w, h, c, flags) == ref().encode(img, w, h, c, flags), (w, h, c, flags)
+
+
+def _large():
+    with open(os.path.join(GOLD, "large.json")) as f:
+        return json.load(f)
+
+
+def _stored_fits(n):
+    """the reference's stored-outcome buffer, a uint32_t sum (src/fpng.cpp:1747): 58 + 6 + n + 5 per 65535-byte block"""
+    return 58 + 6 + n + 5 * ((n + 65534) // 65535) <= 0xFFFFFFFF
+
+
+def test_stored_size_limit_arithmetic_against_the_golden_verdicts():
+    """n* = the largest filtered size whose stored file the reference writes; every stored outcome of tests/golden/large.json lies
+    on the side of n* its verdict says (a file at or below it, null above it), and the file's size is 58 + zlib size + 16"""
+    lo, hi = 0, 2**32
+    while lo < hi:
+        m = (lo + hi + 1) // 2
+        lo, hi = (m, hi) if _stored_fits(m) else (lo, m - 1)
+    n_star = lo
+    assert n_star == 4294639571
+    assert _stored_fits(n_star) and not _stored_fits(n_star + 1)
+    gold = _large()
+    seen = {True: 0, False: 0}
+    for name, g in gold.items():
+        if name == "seed":
+            continue
+        n = (g["w"] * g["c"] + 1) * g["h"]
+        assert n <= 0xFFFFFF00  # accepted by check_dims
+        assert not n_star < n <= n_star + 64  # (there the reference's wrapped size is below its header: no valid judge)
+        for fl, exp in g["flags"].items():
+            stored = int(fl) == 2 or g["kind"] == "noise"
+            if exp is not None:
+                assert exp["size"] == 58 + exp["idat_len"] + 16
+                if stored:
+                    assert exp["idat_len"] == 6 + n + 5 * ((n + 65534) // 65535)
+            if stored:
+                assert (exp is not None) == (n <= n_star), f"{name} flags {fl}"
+                seen[n <= n_star] += 1
+            else:
+                assert exp is not None
+    assert seen[True] >= 2 and seen[False] >= 2
+
+
+def test_oracle_refuses_stored_past_4gib(built_lib):
+    """B2's shape (63970 x 16784 RGBA) with FPNG_FORCE_UNCOMPRESSED: the reference returns false (golden null), so does the oracle --
+    before it writes anything (np.zeros: untouched pages cost nothing)"""
+    g = _large()["B2"]
+    assert g["flags"]["2"] is None
+    w, h, c = g["w"], g["h"], g["c"]
+    assert not _stored_fits((w * c + 1) * h)
+    img = np.zeros((h, w, c), dtype=np.uint8)
+    assert oracle().encode(img, w, h, c, 2) is None

@@ -50,6 +50,11 @@ class PngIn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("reserved", C.c_uint32), ("d_pixels", C.c_void_p), ("pixels_cap", C.c_size_t)]
 
 
+class PngExIn(C.Structure):  # fpng_amd_png_ex: 40 bytes, no padding
+    _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("format", C.c_uint32), ("d_pixels", C.c_void_p), ("row_pitch", C.c_int64),
+                ("pixels_cap", C.c_size_t)]
+
+
 class DecodeResult(C.Structure):
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels_in_file", C.c_uint32), ("status", C.c_int32)]
 
@@ -135,6 +140,8 @@ SIGNATURES = {
     "fpng_amd_node_encode_host_image": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, RESERVE_FN, _vp, C.POINTER(_sz)]),
     "fpng_amd_decode_batch": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_last_phase_ms": (_int, [_vp, C.POINTER(C.c_float * 4)]),
     "fpng_amd_decode_host": (_int, [_vp, _vp, _u32, _u32, RESERVE_FN, _vp, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_plan": (_int, [_vp, _u32, C.POINTER(DecodeResult), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_uint64),

@@ -38,6 +38,34 @@ def format_channels(fmt):
     return [v[2] for v in SRC_FORMATS.values() if v[0] == fmt][0]
 
 
+def _view_rows(t, who):
+    """(h, w, c, pixel bytes) of a uint8 (h, w, c) tensor view whose channels are adjacent bytes, 3 or 4 of them in pixels of 3 or 4
+    bytes, checked (source_layout / dest_layout)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+        raise ValueError(f"{who}: a uint8 tensor shaped (h, w, c)")
+    h, w, c = t.shape
+    if c not in (3, 4) or h < 1 or w < 1:
+        raise ValueError(f"{who}: {c} channels (3 or 4), {w} x {h}")
+    if c > 1 and t.stride(2) != 1:
+        raise ValueError(f"{who}: the channels of a pixel must be adjacent bytes (stride(2) == 1)")
+    px = t.stride(1) if w > 1 else (4 if (t.stride(1) == 4 or c == 4) else 3)
+    if px not in (3, 4) or px < c:
+        raise ValueError(f"{who}: pixel stride {t.stride(1)} (3 or 4 bytes, at least the channels)")
+    return h, w, c, px
+
+
+def _row_pitch(t, ptr, h, w, px, bottom_up, who):
+    """(base, signed row pitch) of the view's rows: 0 for a single row; bottom_up: the tensor's row 0 is the image's bottom row"""
+    rp = t.stride(0)
+    if h > 1 and (rp == 0 or rp < w * px):
+        raise ValueError(f"{who}: row stride {rp} < w * {px} (rows overlap, or stride 0)")
+    if h == 1:
+        rp = 0  # (one row: no pitch)
+    if bottom_up and h > 1:
+        ptr, rp = ptr + (h - 1) * rp, -rp
+    return ptr, rp
+
+
 def source_layout(t, order="rgb", bottom_up=False):
     """(d_pixels, row_pitch, format) of a uint8 (h, w, c) tensor VIEW for Encoder.submit_ex, from its strides and data_ptr() alone
     (the device is not touched, so CPU tensors work too).
@@ -47,21 +75,12 @@ def source_layout(t, order="rgb", bottom_up=False):
     with 4-byte pixels ([..., :3] of RGBA) is an *X format; one whose first byte is the pixel's second byte ([..., 1:] of ARGB) an
     X*** format, its base moved back one byte.  bottom_up: the tensor's row 0 is the image's BOTTOM row (a GL readback): the file
     starts with the tensor's last row and the pitch is negative.  Rows that overlap, stride 0 and other dtypes are refused."""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
-        raise ValueError("source_layout: a uint8 tensor shaped (h, w, c)")
-    h, w, c = t.shape
-    if c not in (3, 4) or h < 1 or w < 1:
-        raise ValueError(f"source_layout: {c} channels (3 or 4), {w} x {h}")
+    h, w, c, px = _view_rows(t, "source_layout")
     order = order.lower()
     if c == 4 and order in ("rgb", "bgr"):
         order += "a"
     if sorted(order) != sorted("rgba"[:c]):
         raise ValueError(f"source_layout: order {order!r} does not name the {c} channels")
-    if c > 1 and t.stride(2) != 1:
-        raise ValueError("source_layout: the channels of a pixel must be adjacent bytes (stride(2) == 1)")
-    px = t.stride(1) if w > 1 else (4 if (t.stride(1) == 4 or c == 4) else 3)
-    if px not in (3, 4) or px < c:
-        raise ValueError(f"source_layout: pixel stride {t.stride(1)} (3 or 4 bytes, at least the channels)")
     ptr = t.data_ptr()
     name = order.upper()
     if c == 3 and px == 4:
@@ -70,14 +89,34 @@ def source_layout(t, order="rgb", bottom_up=False):
             name, ptr = "X" + name, ptr - 1
         else:
             name += "X"
-    rp = t.stride(0)
-    if h > 1 and (rp == 0 or rp < w * px):
-        raise ValueError(f"source_layout: row stride {rp} < w * {px} (rows overlap, or stride 0)")
-    if h == 1:
-        rp = 0  # (one row: no pitch)
-    if bottom_up and h > 1:
-        ptr, rp = ptr + (h - 1) * rp, -rp
+    ptr, rp = _row_pitch(t, ptr, h, w, px, bottom_up, "source_layout")
     return ptr, rp, SRC_FORMATS[name][0]
+
+
+# destination bytes per pixel of an FPNG_AMD_SRC_* value when it names the pixel a decode writes (fpng_amd_decode_batch_ex)
+def dest_bytes(fmt):
+    return [v[1] for v in SRC_FORMATS.values() if v[0] == fmt][0]
+
+
+def dest_layout(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, format) of a uint8 (h, w, c) tensor VIEW that a decode fills in place (Encoder.decode_device_ex /
+    decode_batch_ex, fpng_amd_png_ex): the destination twin of source_layout(), from strides and data_ptr() alone.
+
+    order: the view's channel order -- "rgb" / "bgr" for c = 3; for c = 4 "rgba" / "bgra" / "argb" / "abgr" ("rgb" / "bgr": alpha
+    last) or, with an X byte the decoder sets to 0xFF, "rgbx" / "bgrx" / "xrgb" / "xbgr".  A 3-channel view of 4-byte pixels
+    ([..., :3] of RGBA) is refused: the decoder writes whole pixels and would write the byte the view leaves out.  bottom_up: the
+    tensor's row 0 is the image's BOTTOM row (the file's first row lands in the tensor's last).  Rows that overlap, stride 0 and
+    other dtypes are refused."""
+    h, w, c, px = _view_rows(t, "dest_layout")
+    if px != c:
+        raise ValueError(f"dest_layout: a {c}-channel view of {px}-byte pixels (the decoder would write the byte it leaves out)")
+    order = order.lower()
+    if c == 4 and order in ("rgb", "bgr"):
+        order += "a"
+    if sorted(order) not in ([sorted("rgb")] if c == 3 else [sorted("rgba"), sorted("rgbx")]):
+        raise ValueError(f"dest_layout: order {order!r} does not name the {c} channels")
+    ptr, rp = _row_pitch(t, t.data_ptr(), h, w, px, bottom_up, "dest_layout")
+    return ptr, rp, SRC_FORMATS[order.upper()][0]
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
 
 
@@ -277,6 +316,22 @@ class DecodeBatch:
         for r, t in zip(self.res, self.outs):
             out.append((r.status, t.view(-1)[: r.w * r.h * d].view(r.h, r.w, d) if r.status == 0 else None, r.channels_in_file))
         return out
+
+
+class DecodeBatchEx:
+    """What Encoder.make_decode_batch_ex() returns: the files, the caller's destination views and the C arrays of one
+    fpng_amd_decode_batch(_device)_ex() call."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep):
+        self.pngs, self.outs, self.arr, self.res, self.device_data, self._keep = pngs, outs, arr, res, device_data, keep
+
+    def statuses(self):
+        """status of every file after the last call"""
+        return np.frombuffer(self.res, dtype=np.int32).reshape(-1, 4)[:, 3]
+
+    def results(self):
+        """list of (status, the caller's own destination view (filled in place) or None, channels_in_file)"""
+        return [(r.status, t if r.status == 0 else None, r.channels_in_file) for r, t in zip(self.res, self.outs)]
 
 
 class Encoder:
@@ -499,6 +554,60 @@ class Encoder:
         batch = pngs if isinstance(pngs, DecodeBatch) else self.make_decode_batch(pngs, desired_chans, dims, outs)
         self._sync_stream()
         check(self.lib.fpng_amd_decode_batch_device(self.h, batch.arr, len(batch.arr), batch.desired_chans, batch.res))
+        return batch.results() if results else batch
+
+    @staticmethod
+    def make_decode_batch_ex(pngs, outs, order="rgb", bottom_up=False):
+        """Descriptor (fpng_amd_png_ex[n] + the result records) for decode_device_ex() / decode_batch_ex(): the files -- uint8 CUDA
+        tensors holding whole files, or bytes-like objects in host memory, one kind per batch -- and uint8 (h, w, c) tensor VIEWS on
+        the device that the pixels are decoded into where they lie: crops, BGR(A), *X, bottom-up buffers, described by
+        dest_layout(view, order, bottom_up) (order / bottom_up: one value, or one per file).  Size every view to its file: the
+        call's room check (pixels_cap) is the span from the view's first byte to its last, so a file with more rows or more bytes
+        than that is refused (FPNG_AMD_ERR_BUFFER_TOO_SMALL), but a shorter, wider one would write between the view's rows.
+        Build it once when the same buffers are decoded repeatedly."""
+        n = len(pngs)
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        arr = (_lib.PngExIn * n)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        for i, (p, t) in enumerate(zip(pngs, outs)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise ValueError("make_decode_batch_ex: the destinations are CUDA tensors")
+            ptr, rp, fmt = dest_layout(t, orders[i], ups[i])
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError("make_decode_batch_ex: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            h, w, _ = t.shape
+            arr[i].format, arr[i].d_pixels, arr[i].row_pitch = fmt, ptr, rp
+            arr[i].pixels_cap = (h - 1) * abs(rp) + w * dest_bytes(fmt)  # (the view's own rows: nothing around them)
+        return DecodeBatchEx(list(pngs), list(outs), arr, res, device_data, keep)
+
+    def decode_device_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
+        """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
+        `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
+        pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
+        batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
+        if not batch.device_data:
+            raise ValueError("decode_device_ex: the files are in host memory (decode_batch_ex)")
+        self._sync_stream()
+        check(self.lib.fpng_amd_decode_batch_device_ex(self.h, batch.arr, len(batch.arr), batch.res))
+        return batch.results() if results else batch
+
+    def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
+        """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
+        for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
+        batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
+        if batch.device_data:
+            raise ValueError("decode_batch_ex: the files are in device memory (decode_device_ex)")
+        self._sync_stream()
+        check(self.lib.fpng_amd_decode_batch_ex(self.h, batch.arr, len(batch.arr), batch.res))
         return batch.results() if results else batch
 
     def last_decode_phase_ms(self):

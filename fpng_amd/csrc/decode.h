@@ -1,6 +1,7 @@
 // decode.h -- host/device shared structures of the GPU batch decoder (decode.hip, decode_api.cpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace fpng_amd {
@@ -34,16 +35,24 @@ struct DecJob {
     uint32_t *win;            // device scratch: h x dec_col_blocks() x dec::kWinWords words: for each window of dec_unfilter_kernel's tiles (decode_core.h:
                               // Window) the file's subsequence (counted from its first one) in whose output it begins, 0xFFFFFFFF: none; and where
                               // that subsequence's walk may begin (decode_core.h: Resume)
-    uint8_t *out;             // device: w * h * dst_c pixels
+    uint8_t *out;             // device: w * h * dst_c pixels (layout jobs: the top row's first destination pixel)
     uint32_t *segsum;         // device scratch: nseg x ceil(bpl / 4) 8-byte granules {tag, column sum} of dec_unfilter_kernel's look-back
     uint32_t w, h, src_c, dst_c, bpl;
     uint32_t n_sub;           // subsequences of the file
     uint32_t sub_base;        // index of its first subsequence (a multiple of kDecSubBlock: one file per workgroup)
     uint32_t mode;            // 0 one dynamic block, 1 stored blocks
     uint32_t nseg;            // segments of kDecUnfRows rows (dec_unfilter_*_kernel)
-    uint32_t pad_[2];
+    // destination layout of fpng_amd_decode_batch_ex jobs (zero elsewhere; read only by the *_ex kernels): row y starts at
+    // out + y * pitch, a pixel is dst_c bytes, and v_perm_b32 with selector `sel` turns an R,G,B,A pixel dword into the destination's
+    // byte order (0x0d = a 0xFF byte).  These words were padding before: the record stays 112 bytes with z_shift where it was, so
+    // the other kernels' code is, instruction for instruction, the same (tools/isa_diff.py)
+    uint32_t sel;
+    int32_t pitch;            // signed bytes from one row to the next
     uint32_t z_shift;         // bytes between z (rounded down to a dword) and the stream's first byte; the bit positions above count from z
 };
+static_assert(sizeof(DecJob) == 112 && offsetof(DecJob, sel) == 100 && offsetof(DecJob, z_shift) == 108, "DecJob layout");
+// DecJob::sel of the R,G,B order: rows of 3-channel files go out as they are
+constexpr uint32_t kDecSelRGB = 0x0d020100u;
 
 // Column blocks of dec_unfilter_kernel for one file: 256 PIXELS of the file's rows each -- 256 dword columns of 4-byte pixels, or
 // 4 waves x 48 dword columns of 3-byte ones (see the kernel) -- so that a match, which repeats whole pixels, is whole pixels in
@@ -139,8 +148,10 @@ struct DecPlaced {
     uint32_t sub_limit;
 };
 // concurrent_status: kernels that may set the file's status bits run next to this launch (no workgroup may then skip its file: dec_unfilter_kernel)
-void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status);
-void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored);
+// layout: the jobs are fpng_amd_decode_batch_ex's (DecJob::sel / pitch: the *_ex kernels write them; a launch is all one or the other)
+void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
+                         bool layout = false);
+void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

@@ -1065,6 +1065,9 @@ __device__ __forceinline__ uint32_t gload_u32(const gu8 *base, uint32_t off) { r
 __device__ __forceinline__ void gstore_u32(gu8 *base, uint32_t off, uint32_t v) { *(gu32_any *)(scalar_base(base) + off) = v; }
 __device__ __forceinline__ void gstore_u8(gu8 *base, uint32_t off, uint32_t v) { scalar_base(base)[off] = (uint8_t)v; }
 // (three workgroups of eight waves per compute unit: the tiles' LDS)
+// kLayout: the jobs of fpng_amd_decode_batch_ex -- rows DecJob::pitch bytes apart, pixels that leave through v_perm_b32 with
+// DecJob::sel; else packed R,G,B[,A] rows (the same instructions as the kernel before it had the parameter: tools/isa_diff.py)
+template <bool kLayout>
 __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tile_mem[kUnfRows * kTilePitch];
@@ -1131,6 +1134,7 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
         job.segsum = (uint32_t *)uni64((uint64_t)(uintptr_t)job.segsum);
         job.sub_base = uni32(job.sub_base);
         job.w = uni32(job.w), job.h = uni32(job.h), job.bpl = uni32(job.bpl), job.src_c = uni32(job.src_c), job.dst_c = uni32(job.dst_c), job.nseg = uni32(job.nseg), job.mode = uni32(job.mode);
+        if constexpr (kLayout) job.sel = uni32(job.sel), job.pitch = (int32_t)uni32((uint32_t)job.pitch);
         // (only bits that the kernels in FRONT of this one set decide: every workgroup must come to the same conclusion about a
         //  file, or a later segment would wait for an earlier one that was skipped.  This kernel's own findings -- the tile's walk,
         //  the filter bytes, the look-back -- set other bits (decode.h: kDecTile*, kDecBadFilter; the static_assert there keeps them
@@ -1220,16 +1224,44 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
         //      unaligned dwords, as it does for the loads above); bytes only where a row ends inside a dword ----
         FPNG_TILE_STAMP(3);
         const size_t os = (size_t)job.w * dc;
-        gu8 *orow = (gu8 *)(uintptr_t)(job.out + (size_t)y0 * os);
+        gu8 *orow = (gu8 *)(uintptr_t)(job.out + (kLayout ? (int64_t)y0 * job.pitch : (int64_t)((size_t)y0 * os)));
+        auto row = [&](uint32_t k) -> gu8 * { // (layout jobs: a signed pitch, negative for bottom-up rows)
+            if constexpr (kLayout) return orow + (int64_t)k * job.pitch;
+            else return orow + (size_t)k * os;
+        };
         auto row_sum = [&](uint32_t k) { return active ? add_bytes(carry, T[k * P]) : 0u; }; // the pixels' bytes of row k, this thread's four
-        if (sc == dc) {
+        // (layout jobs: a pixel dword in R,G,B,A order -> the destination's byte order, X bytes 0xFF)
+        auto reorder = [&](uint32_t v) {
+            if constexpr (kLayout) return __builtin_amdgcn_perm(0u, v, job.sel);
+            else return v;
+        };
+        if (kLayout && sc == 3 && dc == 3 && job.sel != kDecSelRGB) {
+            // 3 -> 3 bytes, B and R swapped: lane L holds bytes 4L .. 4L + 3 of the wave's 192 (64 whole pixels), and output byte i
+            // is input byte i + 2, i or i - 2 as i is the first, second or third byte of its pixel -- for L % 3 = m the offsets
+            // are (2, 1, 0, 5), (0, -1, 4, 3), (-2, 3, 2, 1) from 4L: two neighbours' dwords (the wave's first and last lanes need
+            // none past the wave's ends), an 8-byte window out of the three, one v_perm_b32.  All lanes of the row come along:
+            // they are each other's sources, the last one's bytes only where the row ends inside its dword.
+            const uint32_t nb = min(4u, job.bpl - j4 * 4), m = lane % 3u;
+            const uint32_t sh = m == 1 ? 24u : 0u, selm = m == 0 ? 0x05000102u : (m == 1 ? 0x04050001u : 0x05060702u);
+            const int prev_l = (int)(((lane - 1u) & 63u) << 2), next_l = (int)(((lane + 1u) & 63u) << 2);
+            const bool ragged = __builtin_amdgcn_ballot_w64(nb != 4) != 0;
+            for (uint32_t k = 0; k < nrows; k++) {
+                const uint32_t v = row_sum(k);
+                const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute(prev_l, (int)v), next = (uint32_t)__builtin_amdgcn_ds_bpermute(next_l, (int)v);
+                const uint32_t a = m ? prev : v, b = m ? v : next; // the window: bytes 0 .. 7 of b:a from byte sh / 8
+                const uint32_t d = __builtin_amdgcn_perm(funnel(next, b, sh), funnel(b, a, sh), selm);
+                if (nb == 4) gstore_u32(row(k), j4 * 4, d);
+                if (ragged && nb != 4)
+                    for (uint32_t q = 0; q < nb; q++) gstore_u8(row(k), j4 * 4 + q, d >> (8 * q));
+            }
+        } else if (sc == dc) {
             const uint32_t nb = min(4u, job.bpl - j4 * 4);
             if (nb == 4) {
-                for (uint32_t k = 0; k < nrows; k++) gstore_u32(orow + (size_t)k * os, j4 * 4, row_sum(k));
+                for (uint32_t k = 0; k < nrows; k++) gstore_u32(row(k), j4 * 4, kLayout && sc == 4 ? reorder(row_sum(k)) : row_sum(k));
             } else {
                 for (uint32_t k = 0; k < nrows; k++) {
                     const uint32_t v = row_sum(k);
-                    for (uint32_t b = 0; b < nb; b++) gstore_u8(orow + (size_t)k * os, j4 * 4 + b, v >> (8 * b));
+                    for (uint32_t b = 0; b < nb; b++) gstore_u8(row(k), j4 * 4 + b, v >> (8 * b));
                 }
             }
         } else if (widen) {
@@ -1239,7 +1271,7 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
             for (uint32_t k = 0; k < nrows; k++) {
                 const uint32_t v = row_sum(k);
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v), hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((src + 1) << 2), (int)v);
-                if (st) gstore_u32(orow + (size_t)k * os, (wave_px + lane) * 4, funnel(hi, lo, 8 * sh) | 0xFF000000u);
+                if (st) gstore_u32(row(k), (wave_px + lane) * 4, reorder(funnel(hi, lo, 8 * sh) | 0xFF000000u));
             }
         } else {
             // 4 -> 3 channels: the wave's 64 pixels are 48 dwords; lane L < 48 builds dword L = bytes 4L .. 4L + 3 of the 192
@@ -1254,10 +1286,10 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
             };
             const bool ragged = __builtin_amdgcn_ballot_w64(nb - 1u < 3u) != 0; // the row ends inside some lane's dword (all lanes come along: they are the gather's sources)
             for (uint32_t k = 0; k < nrows; k++) {
-                const uint32_t d = dword(row_sum(k));
-                if (nb == 4) gstore_u32(orow + (size_t)k * os, off, d);
+                const uint32_t d = dword(reorder(row_sum(k)));
+                if (nb == 4) gstore_u32(row(k), off, d);
                 if (ragged && nb - 1u < 3u)
-                    for (uint32_t q = 0; q < nb; q++) gstore_u8(orow + (size_t)k * os, off + q, d >> (8 * q));
+                    for (uint32_t q = 0; q < nb; q++) gstore_u8(row(k), off + q, d >> (8 * q));
             }
         }
         FPNG_TILE_STAMP(4);
@@ -1276,6 +1308,10 @@ __device__ __forceinline__ uint64_t stored_pos(uint64_t s) // byte s of the stre
     while (r >= 65535) r -= 65535, q++;
     return 2 + 5 * (q + 1) + s;
 }
+// kLayout: as dec_unfilter_kernel's -- rows DecJob::pitch bytes apart; the dword copy where file and destination pixels are the
+// same size and either are 4 bytes (a dword is a pixel: v_perm_b32 with DecJob::sel reorders it) or the format is RGB, else a pixel
+// at a time through v_perm_b32
+template <bool kLayout>
 __global__ __launch_bounds__(kDecBlock) void dec_stored_kernel(const DecJob *jobs, uint32_t *status)
 {
     const DecJob &job = jobs[blockIdx.y];
@@ -1292,7 +1328,8 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_kernel(const DecJob *job
         odd |= hd[0] != (i + 1 == nblk ? 1 : 0) || (hd[1] | hd[2] << 8) != len || (hd[3] | hd[4] << 8) != (~len & 0xFFFFu);
     }
     // rows: `lanes` threads per row (a power of two), kDecBlock / lanes rows per workgroup and turn
-    const uint32_t units = sc == dc ? (bpl + 3) / 4 : w; // dwords of a row, or pixels
+    const bool copy = sc == dc && (!kLayout || sc == 4 || job.sel == kDecSelRGB); // (else a pixel at a time)
+    const uint32_t units = copy ? (bpl + 3) / 4 : w; // dwords of a row, or pixels
     uint32_t lanes = 1;
     while (lanes < units && lanes < (uint32_t)kDecBlock) lanes <<= 1;
     const uint32_t rows_per = kDecBlock / lanes, t_row = threadIdx.x / lanes, t_x = threadIdx.x & (lanes - 1);
@@ -1300,12 +1337,19 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_kernel(const DecJob *job
     for (uint32_t y = blockIdx.x * rows_per + t_row; y < h; y += gridDim.x * rows_per) {
         const uint64_t s0 = (uint64_t)y * ((uint64_t)bpl + 1); // the row's filter byte
         if (t_x == 0) odd |= z[stored_pos(s0)] != 0;
-        uint8_t *o = job.out + (size_t)y * os;
-        if (sc == dc) {
+        uint8_t *o = job.out + (kLayout ? (int64_t)y * job.pitch : (int64_t)((size_t)y * os));
+        if (copy) {
             for (uint32_t x = 4 * t_x; x < bpl; x += 4 * lanes) {
                 const uint64_t s = s0 + 1 + x, p = stored_pos(s);
                 const uint32_t nb = min(4u, bpl - x);
-                if (nb == 4 && stored_pos(s + 3) == p + 3)
+                if (kLayout && sc == 4) { // (one whole pixel: rows of 4-byte pixels are whole dwords)
+                    uint32_t v = 0;
+                    if (stored_pos(s + 3) == p + 3)
+                        v = load_u32_unaligned(z + p);
+                    else
+                        for (uint32_t b = 0; b < 4; b++) v |= (uint32_t)z[stored_pos(s + b)] << (8 * b);
+                    store_u32_unaligned(o + x, __builtin_amdgcn_perm(0u, v, job.sel));
+                } else if (nb == 4 && stored_pos(s + 3) == p + 3)
                     store_u32_unaligned(o + x, load_u32_unaligned(z + p));
                 else
                     for (uint32_t b = 0; b < nb; b++) o[x + b] = z[stored_pos(s + b)];
@@ -1315,6 +1359,10 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_kernel(const DecJob *job
                 const uint64_t s = s0 + 1 + (uint64_t)x * sc;
                 uint32_t px = 0xFF000000u;
                 for (uint32_t b = 0; b < 3; b++) px |= (uint32_t)z[stored_pos(s + b)] << (8 * b);
+                if constexpr (kLayout) {
+                    if (sc == 4 && dc == 4) px = (px & 0xFFFFFFu) | (uint32_t)z[stored_pos(s + 3)] << 24; // (alpha: where the format keeps it)
+                    px = __builtin_amdgcn_perm(0u, px, job.sel);
+                }
                 if (dc == 4)
                     store_u32_unaligned(o + (size_t)x * 4, px);
                 else
@@ -1453,10 +1501,11 @@ void launch_dec_offsets_range(hipStream_t s, const DecJob *jobs, uint32_t sub_ba
 }
 // jobs / status: of the group's first file; plan: device arrays (decode_api.cpp); epoch: this launch's (a new one every time; the
 // granules are never cleared)
-void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status)
+void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
+                         bool layout)
 {
     if (n_items)
-        hipLaunchKernelGGL(dec_unfilter_kernel, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch,
+        hipLaunchKernelGGL(layout ? dec_unfilter_kernel<true> : dec_unfilter_kernel<false>, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch,
                            concurrent_status ? 0u : kDecUnfSkipMask);
 }
 #ifdef FPNG_DEC_SYNC_TIMING
@@ -1483,12 +1532,12 @@ void dec_dump_tile_times(const char *path, uint32_t n_items)
     }
 }
 #endif
-void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored)
+void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout)
 {
-    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false);
+    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout);
     if (!any_stored) return; // (a workgroup that finds its file is not a stored one leaves at once, but n_jobs x 512 of them is not free)
     for (uint32_t j0 = 0; j0 < n_jobs; j0 += 32768) // (the y dimension of a grid holds at most 65535 workgroups)
-        hipLaunchKernelGGL(dec_stored_kernel, dim3(512, std::min(32768u, n_jobs - j0)), dim3(kDecBlock), 0, s, jobs + j0, status + j0);
+        hipLaunchKernelGGL(layout ? dec_stored_kernel<true> : dec_stored_kernel<false>, dim3(512, std::min(32768u, n_jobs - j0)), dim3(kDecBlock), 0, s, jobs + j0, status + j0);
 }
 
 } // namespace fpng_amd

@@ -193,6 +193,18 @@ int resident_workgroups(fpng_amd_encoder *e, uint32_t &resident)
     return FPNG_AMD_OK;
 }
 
+// FPNG_AMD_SRC_* as a DESTINATION (fpng_amd_decode_batch_ex): bytes per pixel, and the v_perm_b32 selector that turns a pixel dword
+// in R,G,B,A order (A = 0xFF for 3-channel files) into the format's bytes (byte k of the selector = the R,G,B,A byte of destination
+// byte k; 0x0d = a 0xFF byte: the X of the *X formats, and what a 3-byte format's fourth selector byte is never used for)
+struct DstFormat {
+    uint32_t bytes, sel;
+};
+constexpr DstFormat kDstFormats[FPNG_AMD_SRC_COUNT] = {
+    {3, kDecSelRGB}, {3, 0x0d000102u},                                               // RGB BGR
+    {4, 0x03020100u}, {4, 0x03000102u}, {4, 0x02010003u}, {4, 0x00010203u},          // RGBA BGRA ARGB ABGR
+    {4, 0x0d020100u}, {4, 0x0d000102u}, {4, 0x0201000du}, {4, 0x0001020du}};         // RGBX BGRX XRGB XBGR
+static_assert(sizeof(fpng_amd_png_ex) == 40 && offsetof(fpng_amd_png_ex, d_pixels) == 16 && offsetof(fpng_amd_png_ex, pixels_cap) == 32, "fpng_amd_png_ex layout");
+
 // A parsed file's status: the container's (geometry may be half known), the pixels' size, then the parser's st (reference :3131-3136)
 int file_status(const Parsed &p, int st, uint64_t need) { return !p.status && need > UINT32_MAX ? (int)fpng::FPNG_DECODE_FAILED_DIMENSIONS_TOO_LARGE : st; }
 
@@ -297,6 +309,7 @@ struct Group { // files whose upload and decode overlap with the other groups'
 struct Batch {
     fpng_amd_encoder *e;
     const fpng_amd_png *files;
+    const fpng_amd_png_ex *ex; // fpng_amd_decode_batch(_device)_ex: the files' layouts (files[] then holds their data and size), else NULL
     uint32_t n, desired;
     fpng_amd_decode_result *results;
     bool device_data;
@@ -374,16 +387,27 @@ int parse_files(Batch &b)
             }
         }
         r.w = p.w, r.h = p.h, r.channels_in_file = p.c;
-        const uint64_t need = (uint64_t)p.w * p.h * b.desired;
+        const uint32_t desired = b.ex ? kDstFormats[b.ex[i].format].bytes : b.desired;
+        const uint64_t need = (uint64_t)p.w * p.h * desired;
         if ((r.status = file_status(p, st, need))) continue;
-        if (!f.d_pixels || f.pixels_cap < need) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < w * h * desired_chans"); // (only files that will be written need room)
+        // (only files that will be written need room)
+        int64_t pitch = 0;
+        if (b.ex) {
+            const uint64_t row = (uint64_t)p.w * desired;
+            pitch = b.ex[i].row_pitch ? b.ex[i].row_pitch : (int64_t)row;
+            const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
+            if (step < row) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w * format bytes");
+            if (!f.d_pixels || f.pixels_cap < (uint64_t)(p.h - 1) * step + row) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (h - 1) * |row_pitch| + w * format bytes");
+        } else if (!f.d_pixels || f.pixels_cap < need)
+            return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < w * h * desired_chans");
         if (!p.mode && !b.max_rounds) {
             r.status = FPNG_AMD_DECODE_UNDECIDED;
             continue;
         }
         if (!p.mode) p.lut = b.luts.find_or_add(sizes);
-        DecJob j = make_job(p, b.desired);
+        DecJob j = make_job(p, desired);
         j.out = f.d_pixels, j.sub_base = b.sub_total;
+        if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
         if (!p.mode) {
             b.sub_total += (j.n_sub + kDecSubBlock - 1) / kDecSubBlock * kDecSubBlock; // whole workgroups per file
             // offsets into the shared scratch (pointers are patched once the buffers exist)
@@ -546,7 +570,7 @@ int finish_group(Batch &b, uint32_t gi)
     // (all groups run on one stream: two un-filter kernels never run at once -- each one's workgroups wait for lower-numbered ones
     //  of their own launch, and two sets of waiting workgroups could keep each other's predecessors off the compute units)
     const DecPlaced placed = {b.d.sub, b.d.block_off, b.d_eob + g.j0, 0xFFFFFFFFu};
-    launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored);
+    launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr);
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -678,15 +702,17 @@ int collect_results(Batch &b)
     return FPNG_AMD_OK;
 }
 
-int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data)
+// ex: fpng_amd_decode_batch(_device)_ex's files (files = their data and size; desired is not used)
+int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
+                 const fpng_amd_png_ex *ex = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    if (desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
+    if (!ex && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
     std::memset(results, 0, (size_t)n * sizeof *results); // (every entry is defined on every way out)
     HIP_TRY(hipSetDevice(e->device));
     int rc = drain(e);
     if (rc) return rc;
-    Batch b{e, files, n, desired, results, device_data, e->stream};
+    Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
     if ((rc = parse_files(b)) || !b.nj()) return rc;
@@ -897,6 +923,35 @@ extern "C" int fpng_amd_decode_batch(fpng_amd_encoder *e, const fpng_amd_png *fi
 extern "C" int fpng_amd_decode_batch_device(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results)
 {
     return decode_files(e, files, n, desired, results, true);
+}
+
+namespace {
+// fpng_amd_decode_batch(_device)_ex: the rules that need no file are checked here, for every file, before anything is done; the
+// pitch's and the room's once a file's header is known (parse_files)
+int decode_files_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results, bool device_data)
+{
+    if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    std::vector<fpng_amd_png> plain(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const fpng_amd_png_ex &x = files[i];
+        if (x.format >= FPNG_AMD_SRC_COUNT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown destination format");
+        if (kDstFormats[x.format].bytes == 4 && (((uintptr_t)x.d_pixels & 3) || (x.row_pitch & 3)))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "4-byte destination pixels need d_pixels and row_pitch to be multiples of 4");
+        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
+        plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
+    }
+    return decode_files(e, plain.data(), n, 0, results, device_data, files);
+}
+} // namespace
+
+extern "C" int fpng_amd_decode_batch_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results)
+{
+    return decode_files_ex(e, files, n, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results)
+{
+    return decode_files_ex(e, files, n, results, true);
 }
 
 // One host-resident file to host pixels: what fpng::fpng_decode_memory() does for large images (fpng_decode.cpp).  The pixels land in

@@ -454,6 +454,32 @@ int fpng_amd_decode_batch(fpng_amd_encoder *enc, const fpng_amd_png *files, uint
                           fpng_amd_decode_result *results);
 int fpng_amd_decode_batch_device(fpng_amd_encoder *enc, const fpng_amd_png *files, uint32_t n, uint32_t desired_chans,
                                  fpng_amd_decode_result *results);
+/* ---- decoding into other pixel layouts: strided, bottom-up, BGR(A), padded alpha -- the twin of fpng_amd_encode_submit_ex.  A
+ *      FPNG_AMD_SRC_* format names the DESTINATION pixel here and fixes its bytes; the values are those fpng_decode_memory() gives
+ *      for desired_channels = 3 (RGB, BGR) or 4 (the others), reordered into the format:
+ *        RGB  BGR                     3 bytes: a 4-channel file's alpha is dropped
+ *        RGBA BGRA ARGB ABGR          4 bytes: a 3-channel file gets alpha 0xFF
+ *        RGBX BGRX XRGB XBGR          4 bytes: the colour bytes, and X = 0xFF for 3- and 4-channel files alike
+ *      Only the h spans of w * (format bytes) at d_pixels + y * row_pitch are written, whatever a file's status: pitch padding
+ *      and whatever lies in front of or behind the image are never touched.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_ex with dlsym. ---- */
+typedef struct fpng_amd_png_ex {
+    const void *data;  /* the file: HOST memory (fpng_amd_decode_batch_ex) or DEVICE memory (fpng_amd_decode_batch_device_ex) */
+    uint32_t size;
+    uint32_t format;   /* FPNG_AMD_SRC_*: the destination pixel */
+    uint8_t *d_pixels; /* DEVICE: the first byte of the TOP row's first destination pixel */
+    int64_t row_pitch; /* signed bytes from one row to the next; 0 = packed (w * format bytes); negative = bottom-up rows */
+    size_t pixels_cap; /* bytes writable in the span the h rows cover, from the LOWEST-addressed row's first byte */
+} fpng_amd_png_ex;     /* 40 bytes, no padding */
+/* fpng_amd_decode_batch(_device) for destinations described by fpng_amd_png_ex.  status, w, h and channels_in_file of every file
+ * are what the packed call returns with desired_chans = the format's bytes (FPNG_AMD_DECODE_UNDECIDED included;
+ * FPNG_AMD_DECODE_MAX_ROUNDS in the environment works the same).  One batch may mix formats, pitches and 3- / 4-channel files.  Rules (a failed call
+ * writes no pixel and launches nothing that could): FPNG_AMD_ERR_INVALID_ARG for an unknown format, 4-byte formats whose d_pixels
+ * or row_pitch is not a multiple of 4 (3-byte formats may start and be pitched at any byte), |row_pitch| >= 2^31, and -- for files
+ * whose header is accepted -- a row_pitch other than 0 with |row_pitch| < w * format bytes; FPNG_AMD_ERR_BUFFER_TOO_SMALL when
+ * d_pixels is NULL or pixels_cap < (h - 1) * |row_pitch| + w * format bytes (a file the container walk rejects needs no room). */
+int fpng_amd_decode_batch_ex(fpng_amd_encoder *enc, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_ex(fpng_amd_encoder *enc, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

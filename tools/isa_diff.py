@@ -5,7 +5,8 @@
     python tools/isa_diff.py compare /tmp/before.json /tmp/after.json
 
 `dump` compiles the file device-only for gfx950 and stores, per kernel, the sha256 of its listing with the function numbers in
-block labels (.LBB<n>_<k>) and debug notes taken out; `compare` names every kernel that is new, gone or different.  Used when code
+block labels (.LBB<n>_<k>), debug notes and the kernel's own name taken out; `compare` names every kernel that is new, gone or
+different, and pairs a gone kernel with a new one of the same code as "renamed" (a kernel that became a template's instantiation).  Used when code
 is REMOVED from a frozen hot file: the kernels that stay must not move (no GPU needed)."""
 import hashlib
 import json
@@ -28,7 +29,7 @@ def kernels(txt):
             ln = ln.split(";")[0].rstrip()
             if not ln.strip() or ln.strip().startswith((".loc", ".file", ".cfi", ".p2align")):
                 continue
-            body.append(re.sub(r"\.LBB\d+_", ".LBB_", ln))
+            body.append(re.sub(r"\.LBB\d+_", ".LBB_", ln).replace(name, "<kernel>"))
         out[name] = {"sha256": hashlib.sha256("\n".join(body).encode()).hexdigest(), "lines": len(body)}
     return out
 
@@ -41,11 +42,21 @@ if __name__ == "__main__":
     else:
         a, b = json.load(open(sys.argv[2])), json.load(open(sys.argv[3]))
         same = [n for n in a if n in b and a[n] == b[n]]
+        gone, new = [n for n in sorted(a) if n not in b], [n for n in sorted(b) if n not in a]
+        renamed = {}
+        for n in gone:
+            m = next((m for m in new if b[m] == a[n] and m not in renamed.values()), None)
+            if m:
+                renamed[n] = m
         for n in sorted(set(a) | set(b)):
-            if n not in b:
+            if n in renamed:
+                print("renamed   ", n, "->", renamed[n], "(same code)")
+            elif n in renamed.values():
+                continue
+            elif n not in b:
                 print("gone      ", n)
             elif n not in a:
                 print("new       ", n)
             elif a[n] != b[n]:
                 print("DIFFERENT ", n, a[n]["lines"], "->", b[n]["lines"])
-        print(f"{len(same)} kernels identical")
+        print(f"{len(same)} kernels identical" + (f", {len(renamed)} renamed with the same code" if renamed else ""))

@@ -26,6 +26,11 @@ class ImageEx(C.Structure):
                 ("d_out", C.c_void_p), ("out_cap", C.c_size_t)]
 
 
+class ImagePlanar(C.Structure):  # fpng_amd_image_planar: 56 bytes, no padding
+    _fields_ = [("d_pixels", C.c_void_p), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("num_chans", C.c_uint32), ("reserved", C.c_uint32), ("d_out", C.c_void_p), ("out_cap", C.c_size_t)]
+
+
 class Result(C.Structure):
     _fields_ = [("png_size", C.c_uint64), ("mode", C.c_uint32), ("status", C.c_uint32)]
 
@@ -53,6 +58,11 @@ class PngIn(C.Structure):
 class PngExIn(C.Structure):  # fpng_amd_png_ex: 40 bytes, no padding
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("format", C.c_uint32), ("d_pixels", C.c_void_p), ("row_pitch", C.c_int64),
                 ("pixels_cap", C.c_size_t)]
+
+
+class PngPlanarIn(C.Structure):  # fpng_amd_png_planar: 48 bytes, no padding
+    _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("num_chans", C.c_uint32), ("d_pixels", C.c_void_p), ("row_pitch", C.c_int64),
+                ("plane_pitch", C.c_int64), ("pixels_cap", C.c_size_t)]
 
 
 class DecodeResult(C.Structure):
@@ -107,6 +117,7 @@ SIGNATURES = {
     "fpng_amd_encode_finish": (_int, [_vp, C.POINTER(Result), _u32]),
     "fpng_amd_encode_submit": (_int, [_vp, C.POINTER(Image), _u32, _u32, C.POINTER(_u64)]),
     "fpng_amd_encode_submit_ex": (_int, [_vp, C.POINTER(ImageEx), _u32, _u32, C.POINTER(_u64)]),
+    "fpng_amd_encode_submit_planar": (_int, [_vp, C.POINTER(ImagePlanar), _u32, _u32, C.POINTER(_u64)]),
     "fpng_amd_encode_wait": (_int, [_vp, _u64, C.POINTER(Result), _u32]),
     "fpng_amd_encode_query": (_int, [_vp, _u64]),
     "fpng_amd_encode_host": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(_sz)]),
@@ -142,6 +153,8 @@ SIGNATURES = {
     "fpng_amd_decode_batch_device": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_planar": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_last_phase_ms": (_int, [_vp, C.POINTER(C.c_float * 4)]),
     "fpng_amd_decode_host": (_int, [_vp, _vp, _u32, _u32, RESERVE_FN, _vp, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_plan": (_int, [_vp, _u32, C.POINTER(DecodeResult), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_uint64),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Band, BandStats, FpngAmdError, HostImage, Image, ImageEx, Result, check
+from ._lib import Band, BandStats, FpngAmdError, HostImage, Image, ImageEx, ImagePlanar, Result, check
 
 FPNG_ENCODE_SLOWER = 1        # reference src/fpng.h:38
 FPNG_FORCE_UNCOMPRESSED = 2   # reference src/fpng.h:41
@@ -117,6 +117,59 @@ def dest_layout(t, order="rgb", bottom_up=False):
         raise ValueError(f"dest_layout: order {order!r} does not name the {c} channels")
     ptr, rp = _row_pitch(t, t.data_ptr(), h, w, px, bottom_up, "dest_layout")
     return ptr, rp, SRC_FORMATS[order.upper()][0]
+
+
+def _planar_layout(t, order, bottom_up, who):
+    """(d_pixels, row_pitch, plane_pitch) of a uint8 (c, h, w) tensor view: one plane of w-byte rows per channel"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+        raise ValueError(f"{who}: a uint8 tensor shaped (c, h, w)")
+    c, h, w = t.shape
+    if c not in (3, 4) or h < 1 or w < 1:
+        raise ValueError(f"{who}: {c} planes (3 or 4), {w} x {h}")
+    if w > 1 and t.stride(2) != 1:
+        raise ValueError(f"{who}: the pixels of a row must be adjacent bytes (stride(2) == 1); stride(2) == {t.stride(2)} is an "
+                         "interleaved view -- describe it as (h, w, c) with source_layout / dest_layout and use submit_ex / decode_device_ex")
+    rp, pp = t.stride(1), t.stride(0)
+    if h > 1 and rp < w:
+        raise ValueError(f"{who}: row stride {rp} < w (rows overlap, or stride 0)")
+    if h == 1:
+        rp = 0  # (one row: no pitch)
+    span = (h - 1) * rp + w  # bytes of a plane, from its first row's first byte
+    if pp < span:
+        raise ValueError(f"{who}: plane stride {pp} < (h - 1) * row stride + w = {span} (planes overlap, or stride 0)")
+    order = order.lower()
+    if c == 4 and order == "rgb":
+        order = "rgba"
+    if order not in (("rgb", "bgr") if c == 3 else ("rgba", "abgr")):
+        raise ValueError(f"{who}: order {order!r} for {c} planes -- one base and one plane pitch can say "
+                         + ("'rgb' or 'bgr'" if c == 3 else "'rgba' or 'abgr'") + " only")
+    ptr = t.data_ptr()
+    if order[0] != "r":  # the planes lie in reverse: start at the last one and walk back
+        ptr, pp = ptr + (c - 1) * pp, -pp
+    if bottom_up and h > 1:
+        ptr, rp = ptr + (h - 1) * rp, -rp
+    return ptr, rp, pp
+
+
+def source_layout_planar(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, plane_pitch) of a uint8 (c, h, w) tensor VIEW for Encoder.submit_planar (fpng_amd_image_planar), from
+    its strides and data_ptr() alone (the device is not touched, so CPU tensors work too): c = 3 or 4 planes, stride(2) == 1,
+    stride(1) the row pitch, stride(0) the plane pitch -- a contiguous CHW tensor, nchw[i], rgba_chw[:3], a crop chw[:, y0:y1, x0:x1].
+
+    order: how the planes are stored -- "rgb" or, planes stored B, G, R, "bgr" (the base is then the last plane and the plane pitch
+    negative); for c = 4 "rgba" or "abgr" (one pitch cannot say another order).  bottom_up: the tensor's row 0 is the image's BOTTOM
+    row.  Refused: other dtypes and ranks, stride(2) != 1 (an interleaved view: that is submit_ex's), rows or planes that overlap,
+    stride 0."""
+    return _planar_layout(t, order, bottom_up, "source_layout_planar")
+
+
+def dest_layout_planar(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, plane_pitch) of a uint8 (c, h, w) tensor VIEW that a decode fills in place (Encoder.decode_device_planar /
+    decode_batch_planar, fpng_amd_png_planar): the destination twin of source_layout_planar(), same rules.  c = 4 planes of a
+    3-channel file: the A plane is filled with 0xFF; c = 3 of a 4-channel file: alpha is dropped."""
+    return _planar_layout(t, order, bottom_up, "dest_layout_planar")
+
+
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
 
 
@@ -318,9 +371,8 @@ class DecodeBatch:
         return out
 
 
-class DecodeBatchEx:
-    """What Encoder.make_decode_batch_ex() returns: the files, the caller's destination views and the C arrays of one
-    fpng_amd_decode_batch(_device)_ex() call."""
+class _DecodeBatchViews:
+    """The files, the caller's destination views and the C arrays of one decode call into views (DecodeBatchEx, DecodeBatchPlanar)"""
 
     def __init__(self, pngs, outs, arr, res, device_data, keep):
         self.pngs, self.outs, self.arr, self.res, self.device_data, self._keep = pngs, outs, arr, res, device_data, keep
@@ -332,6 +384,16 @@ class DecodeBatchEx:
     def results(self):
         """list of (status, the caller's own destination view (filled in place) or None, channels_in_file)"""
         return [(r.status, t if r.status == 0 else None, r.channels_in_file) for r, t in zip(self.res, self.outs)]
+
+
+class DecodeBatchEx(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_ex() returns: the files, the caller's destination views and the C arrays of one
+    fpng_amd_decode_batch(_device)_ex() call."""
+
+
+class DecodeBatchPlanar(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_planar() returns: the same for one fpng_amd_decode_batch(_device)_planar() call (outs: the
+    caller's (c, h, w) views).  Not a DecodeBatchEx: neither call takes the other's descriptor."""
 
 
 class Encoder:
@@ -438,6 +500,42 @@ class Encoder:
         self._sync_stream()
         t = C.c_uint64(0)
         check(self.lib.fpng_amd_encode_submit_ex(self.h, batch[2], n, flags, C.byref(t)))
+        self.last_ticket = t.value
+        self._keep[t.value] = batch
+        for old in [k for k in self._keep if k + 8 <= t.value]:
+            del self._keep[old]
+        return n
+
+    @staticmethod
+    def make_batch_planar(images, outs, order="rgb", bottom_up=False):
+        """Descriptor array (fpng_amd_image_planar[n]) for submit_planar(): uint8 tensor VIEWS shaped (c, h, w) -- channels first, as
+        torch holds images -- encoded where they lie, described by source_layout_planar(view, order, bottom_up) (order / bottom_up: one
+        value, or one per image).  list(nchw_batch) is a valid `images`.  outs: uint8 tensors of >= max_encoded_size(w, h, c) bytes."""
+        n = len(images)
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        arr = (ImagePlanar * n)()
+        for i, (im, out) in enumerate(zip(images, outs)):
+            ptr, rp, pp = source_layout_planar(im, orders[i], ups[i])
+            arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = ptr, rp, pp
+            arr[i].num_chans, arr[i].h, arr[i].w = im.shape
+            arr[i].reserved = 0
+            arr[i].d_out = out.data_ptr()
+            arr[i].out_cap = out.numel()
+        return (images, outs, arr)
+
+    def submit_planar(self, images, outs=None, flags=0, order="rgb", bottom_up=False):
+        """submit() for planar (c, h, w) images (fpng_amd_encode_submit_planar): images = CUDA tensor views as for make_batch_planar()
+        with outs, or a make_batch_planar() descriptor and outs = None.  The files are the ones submit() writes for the same pixels
+        interleaved as R,G,B[,A] -- without the permute(1, 2, 0).contiguous() copy.  Asynchronous; wait(last_ticket, n) / finish()
+        for the sizes."""
+        batch = images if outs is None else self.make_batch_planar(images, outs, order, bottom_up)
+        if not all(im.is_cuda and out.is_cuda for im, out in zip(batch[0], batch[1])):
+            raise ValueError("submit_planar: images and outs are CUDA tensors")
+        n = len(batch[2])
+        self._sync_stream()
+        t = C.c_uint64(0)
+        check(self.lib.fpng_amd_encode_submit_planar(self.h, batch[2], n, flags, C.byref(t)))
         self.last_ticket = t.value
         self._keep[t.value] = batch
         for old in [k for k in self._keep if k + 8 <= t.value]:
@@ -593,6 +691,8 @@ class Encoder:
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
+        if isinstance(pngs, DecodeBatchPlanar):
+            raise ValueError("decode_device_ex: a planar descriptor (decode_device_planar)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if not batch.device_data:
             raise ValueError("decode_device_ex: the files are in host memory (decode_batch_ex)")
@@ -603,12 +703,67 @@ class Encoder:
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
+        if isinstance(pngs, DecodeBatchPlanar):
+            raise ValueError("decode_batch_ex: a planar descriptor (decode_batch_planar)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if batch.device_data:
             raise ValueError("decode_batch_ex: the files are in device memory (decode_device_ex)")
         self._sync_stream()
         check(self.lib.fpng_amd_decode_batch_ex(self.h, batch.arr, len(batch.arr), batch.res))
         return batch.results() if results else batch
+
+    @staticmethod
+    def make_decode_batch_planar(pngs, outs, order="rgb", bottom_up=False):
+        """Descriptor (fpng_amd_png_planar[n] + the result records) for decode_device_planar() / decode_batch_planar(): the files --
+        uint8 CUDA tensors holding whole files, or bytes-like objects in host memory, one kind per batch -- and uint8 (c, h, w)
+        tensor VIEWS that the pixels are decoded into where they lie, a plane per channel, described by
+        dest_layout_planar(view, order, bottom_up) (order / bottom_up: one value, or one per file).  c = the planes written, 3 or 4.
+        Size every view to its file, as for make_decode_batch_ex(): pixels_cap is the view's own span.  Build it once when the same
+        buffers are decoded repeatedly."""
+        n = len(pngs)
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        arr = (_lib.PngPlanarIn * n)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        for i, (p, t) in enumerate(zip(pngs, outs)):
+            ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError("make_decode_batch_planar: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            c, h, w = t.shape
+            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
+            arr[i].pixels_cap = (c - 1) * abs(pp) + (h - 1) * abs(rp) + w  # (the view's own spans: nothing around them)
+        return DecodeBatchPlanar(list(pngs), list(outs), arr, res, device_data, keep)
+
+    def _decode_planar(self, who, fn, device_data, pngs, outs, order, bottom_up, results):
+        if isinstance(pngs, DecodeBatchEx):
+            raise ValueError(f"{who}: a make_decode_batch_ex() descriptor (decode_device_ex / decode_batch_ex)")
+        batch = pngs if isinstance(pngs, DecodeBatchPlanar) else self.make_decode_batch_planar(pngs, outs, order, bottom_up)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_planar)" if device_data else "device memory (decode_device_planar)"))
+        if not all(t.is_cuda for t in batch.outs):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, len(batch.arr), batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_planar(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
+        """fpng_amd_decode_batch_device_planar: uint8 CUDA tensors holding whole files, decoded into the caller's (c, h, w) device
+        tensor views `outs` in place (make_decode_batch_planar() has the rules) -> list of (status, the caller's view or None,
+        channels_in_file) -- without the permute(2, 0, 1).contiguous() copy behind a packed decode.  pngs may be a
+        make_decode_batch_planar() descriptor of device files (outs = None); results=False returns the descriptor."""
+        return self._decode_planar("decode_device_planar", self.lib.fpng_amd_decode_batch_device_planar, True, pngs, outs, order, bottom_up, results)
+
+    def decode_batch_planar(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
+        """fpng_amd_decode_batch_planar: decode_device_planar() for files in host memory (bytes)."""
+        return self._decode_planar("decode_batch_planar", self.lib.fpng_amd_decode_batch_planar, False, pngs, outs, order, bottom_up, results)
 
     def last_decode_phase_ms(self):
         """{"sync", "offsets", "emit", "unfilter"} -> ms of the last decode call's kernels (first group of files), measured with HIP

@@ -457,6 +457,7 @@ struct Submission {
     uint64_t local_dwords = kLocalFrontPad; // scratch for the rows' local streams (assemble_kernel may read up to four dwords in front of a stream)
     uint32_t chan_mask = 0;    // bit 0: 3-channel jobs present, bit 1: 4-channel jobs
     bool ex = false;           // fpng_amd_encode_submit_ex: the jobs carry a source layout, the *_ex kernels read their pixels
+    bool planar = false;       // fpng_amd_encode_submit_planar: planar jobs, the *_planar kernels read their pixels (chan_mask says which)
     uint32_t layout_mask = 0;  // (ex) bit 0: 3-byte sources, bit 1: 4-byte sources with 4 channels, bit 2: 4-byte sources with 3
     uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
 };
@@ -495,13 +496,15 @@ constexpr SrcFormat kSrcFormats[FPNG_AMD_SRC_COUNT] = {
     {4, 4, 0x03020100u}, {4, 4, 0x03000102u}, {4, 4, 0x00030201u}, {4, 4, 0x00010203u},    // RGBA BGRA ARGB ABGR
     {4, 3, 0x0c020100u}, {4, 3, 0x0c000102u}, {4, 3, 0x0c030201u}, {4, 3, 0x0c010203u}};   // RGBX BGRX XRGB XBGR
 
+static_assert(sizeof(fpng_amd_image_planar) == 56 && offsetof(fpng_amd_image_planar, w) == 24 && offsetof(fpng_amd_image_planar, d_out) == 40, "fpng_amd_image_planar layout");
+
 // Fills slot.jobs[0..n) for whole-image jobs and sizes the scratch buffers.  Only `slot` (which is free) and
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
-// ex_images (fpng_amd_encode_submit_ex) replaces `images` when it is given.
+// ex_images (fpng_amd_encode_submit_ex) or pl_images (fpng_amd_encode_submit_planar) replaces `images` when it is given.
 int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const fpng_amd_image *images,
-                 const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, Submission &sub)
+                 const fpng_amd_image_ex *ex_images, const fpng_amd_image_planar *pl_images, uint32_t n, uint32_t flags, Submission &sub)
 {
-    if (!e || !(images || ex_images) || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    if (!e || !(images || ex_images || pl_images) || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "batch larger than 65535 images");
     int rc;
     if ((rc = slot.jobs.ensure(n)) || (rc = slot.results.ensure(n))) return rc;
@@ -511,10 +514,30 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     sub = Submission();
     sub.n = n;
     sub.ex = ex_images != nullptr;
+    sub.planar = pl_images != nullptr;
     for (uint32_t i = 0; i < n; i++) {
         fpng_amd_image im_of_ex;
         const SrcFormat *fmt = nullptr;
-        int64_t pitch = 0;
+        int64_t pitch = 0, plane_pitch = 0;
+        if (pl_images) {
+            const fpng_amd_image_planar &x = pl_images[i];
+            if (x.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "reserved must be 0");
+            if ((rc = check_dims(x.w, x.h, x.num_chans))) return rc;
+            pitch = x.row_pitch ? x.row_pitch : (int64_t)x.w;
+            const int64_t apitch = pitch < 0 ? -pitch : pitch;
+            if (apitch < (int64_t)x.w) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w");
+            // (h, w < 2^24 and |row_pitch| < 2^63 / 2^24 keep the span in 64 bits)
+            if (apitch > (INT64_MAX >> 26)) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| too large");
+            const int64_t span = (int64_t)(x.h - 1) * apitch + x.w; // bytes from a plane's lowest row to the end of its highest
+            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)x.h * apitch;
+            if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
+            if ((plane_pitch < 0 ? -plane_pitch : plane_pitch) < span)
+                return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w: the planes overlap");
+            im_of_ex.d_pixels = x.d_pixels;
+            im_of_ex.w = x.w, im_of_ex.h = x.h, im_of_ex.num_chans = x.num_chans;
+            im_of_ex.d_out = x.d_out;
+            im_of_ex.out_cap = x.out_cap;
+        }
         if (ex_images) {
             const fpng_amd_image_ex &x = ex_images[i];
             if (x.format >= FPNG_AMD_SRC_COUNT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown source format");
@@ -530,10 +553,10 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
             im_of_ex.d_out = x.d_out;
             im_of_ex.out_cap = x.out_cap;
         }
-        const fpng_amd_image &im = ex_images ? im_of_ex : images[i];
+        const fpng_amd_image &im = (ex_images || pl_images) ? im_of_ex : images[i];
         if ((rc = check_dims(im.w, im.h, im.num_chans))) return rc;
         if (!im.d_pixels || !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
-        if (((uintptr_t)im.d_out & 15) || (im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)))
+        if (((uintptr_t)im.d_out & 15) || (!pl_images && im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)))
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
         if (im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.num_chans))
             return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
@@ -570,6 +593,11 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
             j.sel = fmt->sel;
             sub.layout_mask |= fmt->bytes == 3 ? 1u : (fmt->chans == 4 ? 2u : 4u);
         }
+        if (pl_images) {
+            j.pitch = pitch;
+            j.plane_pitch = plane_pitch;
+            j.src_bytes = 1;
+        }
         if (im.num_chans == 4) sub.px4 += (uint64_t)im.w * im.h, sub.px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
         const uint64_t units = im.h; // records of the job: one per row
         sub.local_dwords += (uint64_t)j.local_stride * units;
@@ -591,7 +619,8 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     return FPNG_AMD_OK;
 }
 
-int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out)
+int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out,
+           const fpng_amd_image_planar *pl_images = nullptr)
 {
     if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
     HIP_TRY(hipSetDevice(e->device));
@@ -616,7 +645,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     hipStream_t s = e->lane_stream[lane];
     fpng_amd_encoder::Scratch &sc = e->sc[lane];
     Submission sub;
-    int rc = prepare_jobs(e, slot, sc, images, ex_images, n, flags, sub);
+    int rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub);
     if (rc) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
@@ -664,7 +693,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     // 7 us MORE per chain: every kernel's first touch of the record goes over PCIe.)
     // One image: its record travels in the arguments of the chain's first kernel, which leaves it in d_jobs for the others
     // (encode_rows_first_kernel): no blit kernel + dispatch gap in front of the chain.
-    const bool job_in_args = n == 1 && !force_stored && !sub.ex; // (the *_first kernels have no layout forms)
+    const bool job_in_args = n == 1 && !force_stored && !sub.ex && !sub.planar; // (the *_first kernels have no layout forms)
     const Job *d_jobs = sc.d_jobs.p;
     if (!job_in_args) HIP_TRY(hipMemcpyAsync(sc.d_jobs.p, slot.jobs.p, n * sizeof(Job), hipMemcpyHostToDevice, s));
     if ((rc = mark(e, s, 0))) return rc;
@@ -683,6 +712,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
         sc.hist_zero = 0;
         if (job_in_args)
             launch_hist_first(s, slot.jobs.p[0], sc.d_jobs.p, sc.d_hist.p);
+        else if (sub.planar)
+            launch_hist_planar(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
         else if (sub.ex)
             launch_hist_ex(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
         else
@@ -710,6 +741,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     // (both kernels get slower by more than the two small launches cost) and 5-19 % MORE single-frame latency.
     if (job_in_args)
         launch_encode_rows_first(s, two_pass ? slot.jobs2.p[0] : slot.jobs.p[0], sc.d_jobs.p, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
+    else if (!force_stored && sub.planar)
+        launch_encode_rows_planar(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
     else if (!force_stored && sub.ex)
         launch_encode_rows_ex(s, d_jobs, n, sub.max_rows, sub.layout_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
     else if (!force_stored)
@@ -731,7 +764,9 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
     if ((rc = mark(e, s, ++ph))) return rc;
     uint32_t *adler_parts = sc.d_partials.p + (size_t)n * sub.max_crc_blocks;
-    if (sub.ex)
+    if (sub.planar)
+        launch_assemble_planar(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
+    else if (sub.ex)
         launch_assemble_ex(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
     else
         launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
@@ -771,6 +806,12 @@ int fpng_amd_encode_submit_ex(fpng_amd_encoder *e, const fpng_amd_image_ex *imag
 {
     if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     return submit(e, nullptr, images, n, flags, ticket);
+}
+
+int fpng_amd_encode_submit_planar(fpng_amd_encoder *e, const fpng_amd_image_planar *images, uint32_t n, uint32_t flags, uint64_t *ticket)
+{
+    if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    return submit(e, nullptr, nullptr, n, flags, ticket, images);
 }
 
 int fpng_amd_encode_batch_async(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags)

@@ -149,9 +149,12 @@ struct DecPlaced {
 };
 // concurrent_status: kernels that may set the file's status bits run next to this launch (no workgroup may then skip its file: dec_unfilter_kernel)
 // layout: the jobs are fpng_amd_decode_batch_ex's (DecJob::sel / pitch: the *_ex kernels write them; a launch is all one or the other)
+// plane_pitch (device, a word per file of `jobs`, or NULL): the jobs are fpng_amd_decode_batch_planar's -- dst_c planes, DecJob::pitch
+// between a plane's rows; the *_planar kernels write them
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout = false);
-void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false);
+                         bool layout = false, const int64_t *plane_pitch = nullptr);
+void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false,
+                       const int64_t *plane_pitch = nullptr);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

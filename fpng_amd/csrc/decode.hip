@@ -1064,236 +1064,27 @@ __device__ __forceinline__ gu8 *scalar_base(const gu8 *p)
 __device__ __forceinline__ uint32_t gload_u32(const gu8 *base, uint32_t off) { return *(const gu32_any *)(scalar_base(base) + off); }
 __device__ __forceinline__ void gstore_u32(gu8 *base, uint32_t off, uint32_t v) { *(gu32_any *)(scalar_base(base) + off) = v; }
 __device__ __forceinline__ void gstore_u8(gu8 *base, uint32_t off, uint32_t v) { scalar_base(base)[off] = (uint8_t)v; }
+// the dword of lane I of every quad of lanes, in all four (DPP quad_perm:[I,I,I,I])
+template <int I> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, I * 0x55, 0xF, 0xF, true);
+}
 // (three workgroups of eight waves per compute unit: the tiles' LDS)
 // kLayout: the jobs of fpng_amd_decode_batch_ex -- rows DecJob::pitch bytes apart, pixels that leave through v_perm_b32 with
 // DecJob::sel; else packed R,G,B[,A] rows (the same instructions as the kernel before it had the parameter: tools/isa_diff.py)
 template <bool kLayout>
 __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t tile_mem[kUnfRows * kTilePitch];
-    __shared__ uint32_t mask_mem[kUnfRows * kRowMaskWords], epx_mem[kUnfRows]; // the rows' marked pixels (long matches), their entry pixels
-    __shared__ uint32_t s_first[kWave + 1], s_i0[kWave], s_res[3 * kWave];      // the tile's walks (fill_tile)
-    FPNG_TILE_STAMP(0);
-    // Items are numbered SEGMENT by segment across all files of the group: the files, sorted by their segment counts (most
-    // first), form `pieces` of segments over which the set of files that still have rows is constant -- its first `alive` ones,
-    // cbpre[] = their column blocks' prefix sums.  One workgroup per item, item = workgroup number: an item waits for items with
-    // LOWER numbers only, and the hardware starts the workgroups of a grid in rising order (per XCD, each XCD taking a fixed share
-    // of the numbers: the lowest unfinished item is then always running or next in line for a free slot).  Measured alternatives,
-    // 8 x 8K: tickets drawn from one atomic counter 1.72 ms, from one counter per column block 0.78 ms, persistent workgroups
-    // taking their items in rising order 0.89 ms, this 0.54 ms, the former two kernels (sums, then a second read) 0.88 ms.  A spin
-    // that does not end -- it cannot, unless workgroups do not start in that order after all -- gives up after kSpinLimit polls
-    // and leaves the file to the CPU decoder (FPNG_AMD_DECODE_UNDECIDED).
-    constexpr uint32_t kSpinLimit = 1u << 20;
-    {
-        // Which item?  The hardware deals a grid's workgroups to the eight XCDs in turn, and neighbouring items -- the column blocks of
-        // one band of rows -- read the same blocks of token records where their windows meet: inside every run of 64 workgroups the
-        // numbers are dealt so that eight neighbours share an XCD, i.e. an L2.  (Items still wait for lower numbers only; the order of
-        // the runs is the grid's.)
-        const uint32_t b = blockIdx.x, b_run = b & ~63u;
-        const uint32_t item = item0 + (b_run + 64u <= gridDim.x ? b_run + ((b & 7u) << 3) + ((b >> 3) & 7u) : b); // (item0: a later launch for the same files, fpng_amd_decode_host's streamed form)
-        if (item >= plan.total_items) return;
-        // (which piece, which file: the lists are short -- eight files, one piece -- and a binary search over them in memory is a chain of
-        //  round trips in front of everything else the tile does: the lanes of a wave look at an element each, all at once)
-        const uint32_t l64 = threadIdx.x & (kWave - 1);
-        DecUnfPiece pc;
-        uint32_t per_seg, fidx, cb0, ji_w = 0xFFFFFFFFu;
-        if (plan.n_pieces <= (uint32_t)kWave && plan.n_files < (uint32_t)kWave) {
-            const bool hasp = l64 < plan.n_pieces, hasf = l64 <= plan.n_files;
-            const DecUnfPiece mine = plan.pieces[hasp ? l64 : 0u];
-            const uint32_t cbl = plan.cbpre[hasf ? l64 : 0u], ordl = plan.order[l64 < plan.n_files ? l64 : 0u];
-            const uint32_t pi = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(hasp && mine.item0 <= item)) - 1u; // (pieces rise; the first one begins at item 0)
-            pc.item0 = (uint32_t)__builtin_amdgcn_readlane((int)mine.item0, (int)pi), pc.seg0 = (uint32_t)__builtin_amdgcn_readlane((int)mine.seg0, (int)pi);
-            pc.alive = (uint32_t)__builtin_amdgcn_readlane((int)mine.alive, (int)pi), pc.pad_ = 0;
-            per_seg = (uint32_t)__builtin_amdgcn_readlane((int)cbl, (int)pc.alive);
-            const uint32_t within0 = (item - pc.item0) % per_seg;
-            fidx = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(l64 < pc.alive && cbl <= within0)) - 1u;
-            cb0 = (uint32_t)__builtin_amdgcn_readlane((int)cbl, (int)fidx);
-            ji_w = (uint32_t)__builtin_amdgcn_readlane((int)ordl, (int)fidx);
-        } else {
-            uint32_t lo = 0, hi = plan.n_pieces;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (plan.pieces[mid].item0 <= item) lo = mid; else hi = mid;
-            }
-            pc = plan.pieces[lo];
-            per_seg = plan.cbpre[pc.alive];
-            const uint32_t within0 = (item - pc.item0) % per_seg;
-            lo = 0, hi = pc.alive;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (plan.cbpre[mid] <= within0) lo = mid; else hi = mid;
-            }
-            fidx = lo, cb0 = plan.cbpre[lo];
-        }
-        const uint32_t rel = item - pc.item0, sg = uni32(pc.seg0 + rel / per_seg), within = rel % per_seg;
-        const uint32_t ji = ji_w != 0xFFFFFFFFu ? ji_w : uni32(plan.order[fidx]), cb = uni32(within - cb0);
-        // (the file's record, read by every lane, into scalar registers: the compiler keeps what it loads from writable global
-        //  memory in vector registers, and every address derived from it would cost a register pair per row)
-        DecJob job = jobs[ji];
-        job.win = (uint32_t *)uni64((uint64_t)(uintptr_t)job.win), job.out = (uint8_t *)uni64((uint64_t)(uintptr_t)job.out);
-        job.segsum = (uint32_t *)uni64((uint64_t)(uintptr_t)job.segsum);
-        job.sub_base = uni32(job.sub_base);
-        job.w = uni32(job.w), job.h = uni32(job.h), job.bpl = uni32(job.bpl), job.src_c = uni32(job.src_c), job.dst_c = uni32(job.dst_c), job.nseg = uni32(job.nseg), job.mode = uni32(job.mode);
-        if constexpr (kLayout) job.sel = uni32(job.sel), job.pitch = (int32_t)uni32((uint32_t)job.pitch);
-        // (only bits that the kernels in FRONT of this one set decide: every workgroup must come to the same conclusion about a
-        //  file, or a later segment would wait for an earlier one that was skipped.  This kernel's own findings -- the tile's walk,
-        //  the filter bytes, the look-back -- set other bits (decode.h: kDecTile*, kDecBadFilter; the static_assert there keeps them
-        //  out of kDecUnfSkipMask), so the word's skip bits are the same for every thread of the launch.  skip_mask = kDecUnfSkipMask;
-        //  0 where kernels that set those bits run NEXT to this launch -- the streamed form undoes a piece's rows on a stream of its
-        //  own while the next piece is decoded: there every workgroup runs and publishes, whatever the status word says by then; a
-        //  damaged file's rows are garbage either way and its status says so)
-        if (job.mode != 0 || (status[ji] & skip_mask)) return;
-        const uint32_t ncol = (job.bpl + 3) / 4;
-        const uint32_t sc = job.src_c, dc = job.dst_c, lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-        // Which dword column is this thread's?  Rows of 4-byte pixels: workgroup-thread t has column cb * 256 + t.  Rows of 3-byte
-        // pixels: a wave takes 48 dword columns = 192 bytes = 64 WHOLE pixels (its lanes 48..63 hold no column), a column block is
-        // 256 pixels either way; where such rows become 4-channel pixels every lane writes one pixel, gathered from two lanes'
-        // dwords -- dword stores instead of a byte at a time.
-        const bool three = sc == 3, widen = three && dc == 4;
-        const uint32_t wave_px = (cb * (kDecBlock / kWave) + wv) * kWave; // (the wave's first pixel)
-        const uint32_t j4 = three ? (wave_px / 4) * 3 + lane : cb * kDecBlock + threadIdx.x;
-        const bool active = j4 < ncol && (!three || lane < 48) && threadIdx.x < (uint32_t)kDecBlock;
-        const uint32_t y0 = sg * kUnfRows, nrows = min(kUnfRows, job.h - y0);
-        // ---- the tile's rows, from the token records (all threads; the barriers stand in front of every way out) ----
-        lds_u8 *tile = (lds_u8 *)tile_mem;
-        {
-            const uint32_t ncb = dec_col_blocks(job.w, sc, dc), cbw = dec_col_block_bytes(sc, dc), last_sub = placed.eob_index[ji];
-            lds_u32 *bm = (lds_u32 *)mask_mem, *epx = (lds_u32 *)epx_mem;
-            const uint32_t err = sc == 4 ? fill_tile<4>(job, placed, last_sub, y0, nrows, cb, ncb, cbw, tile, bm, epx, s_first, s_i0, s_res, item0)
-                                         : fill_tile<3>(job, placed, last_sub, y0, nrows, cb, ncb, cbw, tile, bm, epx, s_first, s_i0, s_res, item0);
-            if (err) atomicOr(&status[ji], (err & kEmitBadStream ? kDecTileBadStream : 0u) | (err & kEmitLeaveToCpu ? kDecTileLeaveToCpu : 0u));
-            __syncthreads();
-            if (sc == 4) propagate_matches<4>(tile, bm, epx, nrows, s_i0); else propagate_matches<3>(tile, bm, epx, nrows, s_i0);
-        }
-        __syncthreads();
-        FPNG_TILE_STAMP(1);
-        if (threadIdx.x >= (uint32_t)kDecBlock) return; // (the tile is filled: from here on a thread per dword column)
-        if (cb == 0 && threadIdx.x == 0) {
-            bool bad = false;
-            for (uint32_t k = 0; k < nrows; k++) bad |= tile[k * kTilePitch + kTileData - 1] != (y0 + k ? 2 : 0);
-            if (bad) atomicOr(&status[ji], kDecBadFilter);
-        }
-        if (!widen && !active) return; // (the lanes of a widening wave all stay: they write pixels)
-        if (widen && wave_px >= job.w) return;
-        // ---- the columns' running sums, in place: row k of the tile becomes the sum of its rows 0 .. k (every thread its own dword
-        //      column; eight rows in flight).  The rows stay in LDS -- until round 6 a thread held its 48 of them in registers, which
-        //      is what kept the kernel at four waves per SIMD. ----
-        lds_u32 *T = (lds_u32 *)(tile + kTileData) + (three ? wv * 48 + lane : threadIdx.x); // this thread's dword column of the tile
-        constexpr uint32_t P = kTilePitch / 4;
-        uint32_t p = 0;
-        if (active) {
-            for (uint32_t k = 0; k < nrows; k += 8) {
-                uint32_t t8[8];
-#pragma unroll
-                for (uint32_t q = 0; q < 8; q++) t8[q] = T[min(k + q, nrows - 1) * P];
-#pragma unroll
-                for (uint32_t q = 0; q < 8; q++)
-                    if (k + q < nrows) p = add_bytes(p, t8[q]), T[(k + q) * P] = p;
-            }
-        }
-        FPNG_TILE_STAMP(2);
-        gu64 *gran = (gu64 *)(uintptr_t)job.segsum + j4;
-        uint32_t carry = 0;
-        if (active && (sg + 1 < job.nseg || sg)) { // (a file of one segment publishes nothing)
-            gu64 *mine = gran + (size_t)sg * ncol;
-            if (sg == 0)
-                __hip_atomic_store(mine, ((unsigned long long)(epoch << 2 | 2u) << 32) | p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else {
-                if (sg + 1 < job.nseg) __hip_atomic_store(mine, ((unsigned long long)(epoch << 2 | 1u) << 32) | p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                bool stalled = false;
-                for (uint32_t q = sg; q-- > 0 && !stalled;) {
-                    gu64 *g = gran + (size_t)q * ncol;
-                    unsigned long long x = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    for (uint32_t spins = 0; (uint32_t)(x >> 34) != epoch; spins++) {
-                        if (spins == kSpinLimit) {
-                            stalled = true;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(2);
-                        x = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    carry = add_bytes(carry, (uint32_t)x);
-                    if (((uint32_t)(x >> 32) & 3u) == 2u) break;
-                }
-                if (stalled) atomicOr(&status[ji], kDecTileStalled);
-                if (sg + 1 < job.nseg)
-                    __hip_atomic_store(mine, ((unsigned long long)(epoch << 2 | 2u) << 32) | add_bytes(carry, p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        // ---- the pixels.  Dword stores at any byte address (rows of 3-channel pixels start anywhere; the hardware takes
-        //      unaligned dwords, as it does for the loads above); bytes only where a row ends inside a dword ----
-        FPNG_TILE_STAMP(3);
-        const size_t os = (size_t)job.w * dc;
-        gu8 *orow = (gu8 *)(uintptr_t)(job.out + (kLayout ? (int64_t)y0 * job.pitch : (int64_t)((size_t)y0 * os)));
-        auto row = [&](uint32_t k) -> gu8 * { // (layout jobs: a signed pitch, negative for bottom-up rows)
-            if constexpr (kLayout) return orow + (int64_t)k * job.pitch;
-            else return orow + (size_t)k * os;
-        };
-        auto row_sum = [&](uint32_t k) { return active ? add_bytes(carry, T[k * P]) : 0u; }; // the pixels' bytes of row k, this thread's four
-        // (layout jobs: a pixel dword in R,G,B,A order -> the destination's byte order, X bytes 0xFF)
-        auto reorder = [&](uint32_t v) {
-            if constexpr (kLayout) return __builtin_amdgcn_perm(0u, v, job.sel);
-            else return v;
-        };
-        if (kLayout && sc == 3 && dc == 3 && job.sel != kDecSelRGB) {
-            // 3 -> 3 bytes, B and R swapped: lane L holds bytes 4L .. 4L + 3 of the wave's 192 (64 whole pixels), and output byte i
-            // is input byte i + 2, i or i - 2 as i is the first, second or third byte of its pixel -- for L % 3 = m the offsets
-            // are (2, 1, 0, 5), (0, -1, 4, 3), (-2, 3, 2, 1) from 4L: two neighbours' dwords (the wave's first and last lanes need
-            // none past the wave's ends), an 8-byte window out of the three, one v_perm_b32.  All lanes of the row come along:
-            // they are each other's sources, the last one's bytes only where the row ends inside its dword.
-            const uint32_t nb = min(4u, job.bpl - j4 * 4), m = lane % 3u;
-            const uint32_t sh = m == 1 ? 24u : 0u, selm = m == 0 ? 0x05000102u : (m == 1 ? 0x04050001u : 0x05060702u);
-            const int prev_l = (int)(((lane - 1u) & 63u) << 2), next_l = (int)(((lane + 1u) & 63u) << 2);
-            const bool ragged = __builtin_amdgcn_ballot_w64(nb != 4) != 0;
-            for (uint32_t k = 0; k < nrows; k++) {
-                const uint32_t v = row_sum(k);
-                const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute(prev_l, (int)v), next = (uint32_t)__builtin_amdgcn_ds_bpermute(next_l, (int)v);
-                const uint32_t a = m ? prev : v, b = m ? v : next; // the window: bytes 0 .. 7 of b:a from byte sh / 8
-                const uint32_t d = __builtin_amdgcn_perm(funnel(next, b, sh), funnel(b, a, sh), selm);
-                if (nb == 4) gstore_u32(row(k), j4 * 4, d);
-                if (ragged && nb != 4)
-                    for (uint32_t q = 0; q < nb; q++) gstore_u8(row(k), j4 * 4 + q, d >> (8 * q));
-            }
-        } else if (sc == dc) {
-            const uint32_t nb = min(4u, job.bpl - j4 * 4);
-            if (nb == 4) {
-                for (uint32_t k = 0; k < nrows; k++) gstore_u32(row(k), j4 * 4, kLayout && sc == 4 ? reorder(row_sum(k)) : row_sum(k));
-            } else {
-                for (uint32_t k = 0; k < nrows; k++) {
-                    const uint32_t v = row_sum(k);
-                    for (uint32_t b = 0; b < nb; b++) gstore_u8(row(k), j4 * 4 + b, v >> (8 * b));
-                }
-            }
-        } else if (widen) {
-            // lane L's pixel = bytes 3L .. 3L + 2 of the wave's 192: in the dwords of lanes 3L / 4 and the next one
-            const uint32_t src = (3u * lane) >> 2, sh = (3u * lane) & 3u;
-            const bool st = wave_px + lane < job.w;
-            for (uint32_t k = 0; k < nrows; k++) {
-                const uint32_t v = row_sum(k);
-                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v), hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((src + 1) << 2), (int)v);
-                if (st) gstore_u32(row(k), (wave_px + lane) * 4, reorder(funnel(hi, lo, 8 * sh) | 0xFF000000u));
-            }
-        } else {
-            // 4 -> 3 channels: the wave's 64 pixels are 48 dwords; lane L < 48 builds dword L = bytes 4L .. 4L + 3 of the 192
-            // from the pixels 4L / 3 and the next one
-            const uint32_t wpx = (cb * (kDecBlock / kWave) + wv) * kWave, nv = min((uint32_t)kWave, job.w - wpx); // (this wave's pixels: j4 = wpx + lane < w)
-            const uint32_t p0 = (4u * lane) / 3u, r = 4u * lane - 3u * p0, have = 3u * nv; // bytes of the wave
-            const uint32_t nb = lane < 48 ? (4u * lane + 4 <= have ? 4u : (4u * lane < have ? have - 4u * lane : 0u)) : 0u;
-            const uint32_t off = wpx * 3 + 4u * lane;
-            auto dword = [&](uint32_t acc) {
-                const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(p0 << 2), (int)acc), b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((p0 + 1) & 63u) << 2), (int)acc);
-                return funnel((b & 0xFFFFFFu) >> 8, (a & 0xFFFFFFu) | (b << 24), 8 * r); // (b's 24 bits : a's 24 bits) >> 8 r
-            };
-            const bool ragged = __builtin_amdgcn_ballot_w64(nb - 1u < 3u) != 0; // the row ends inside some lane's dword (all lanes come along: they are the gather's sources)
-            for (uint32_t k = 0; k < nrows; k++) {
-                const uint32_t d = dword(reorder(row_sum(k)));
-                if (nb == 4) gstore_u32(row(k), off, d);
-                if (ragged && nb - 1u < 3u)
-                    for (uint32_t q = 0; q < nb; q++) gstore_u8(row(k), off + q, d >> (8 * q));
-            }
-        }
-        FPNG_TILE_STAMP(4);
-    }
+    constexpr bool kPlanar = false;
+    constexpr const int64_t *plane_pitch = nullptr;
+#include "dec_unfilter_body.inc"
+}
+// the planar jobs of fpng_amd_decode_batch_planar; plane_pitch: a word per file of `jobs` (DecJob has no room for it)
+__global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_planar_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask,
+                                                                                                                const int64_t *plane_pitch)
+{
+    constexpr bool kLayout = false, kPlanar = true;
+#include "dec_unfilter_body.inc"
 }
 
 // ---- stored files (reference src/fpng.cpp:2107-2207): the filter-0 stream sits in stored blocks, in fpng's files all of 65535
@@ -1368,6 +1159,37 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_kernel(const DecJob *job
                 else
                     for (uint32_t b = 0; b < 3; b++) o[(size_t)x * 3 + b] = (uint8_t)(px >> (8 * b));
             }
+        }
+    }
+    if (odd) atomicOr(&status[blockIdx.y], kDecStoredOdd);
+}
+
+// the stored files of fpng_amd_decode_batch_planar: the same checks, the rows a pixel at a time, a byte into each of the dst_c planes
+__global__ __launch_bounds__(kDecBlock) void dec_stored_planar_kernel(const DecJob *jobs, uint32_t *status, const int64_t *plane_pitch)
+{
+    const DecJob &job = jobs[blockIdx.y];
+    if (job.mode != 1) return;
+    const uint8_t *z = job.z + job.z_shift;
+    const uint32_t sc = job.src_c, dc = job.dst_c, bpl = job.bpl, w = job.w, h = job.h;
+    const int64_t pp = plane_pitch[blockIdx.y];
+    const uint64_t total = ((uint64_t)bpl + 1) * h;
+    const uint32_t nblk = (uint32_t)((total + 65534) / 65535);
+    bool odd = false;
+    for (uint32_t i = blockIdx.x * kDecBlock + threadIdx.x; i < nblk; i += gridDim.x * kDecBlock) {
+        const uint8_t *hd = z + 2 + (uint64_t)i * 65540;
+        const uint32_t len = i + 1 < nblk ? 65535u : (uint32_t)(total - (uint64_t)i * 65535);
+        odd |= hd[0] != (i + 1 == nblk ? 1 : 0) || (hd[1] | hd[2] << 8) != len || (hd[3] | hd[4] << 8) != (~len & 0xFFFFu);
+    }
+    uint32_t lanes = 1;
+    while (lanes < w && lanes < (uint32_t)kDecBlock) lanes <<= 1;
+    const uint32_t rows_per = kDecBlock / lanes, t_row = threadIdx.x / lanes, t_x = threadIdx.x & (lanes - 1);
+    for (uint32_t y = blockIdx.x * rows_per + t_row; y < h; y += gridDim.x * rows_per) {
+        const uint64_t s0 = (uint64_t)y * ((uint64_t)bpl + 1); // the row's filter byte
+        if (t_x == 0) odd |= z[stored_pos(s0)] != 0;
+        uint8_t *o = job.out + (int64_t)y * job.pitch;
+        for (uint32_t x = t_x; x < w; x += lanes) {
+            const uint64_t s = s0 + 1 + (uint64_t)x * sc;
+            for (uint32_t b = 0; b < dc; b++) o[(int64_t)b * pp + x] = b < sc ? z[stored_pos(s + b)] : (uint8_t)0xFF;
         }
     }
     if (odd) atomicOr(&status[blockIdx.y], kDecStoredOdd);
@@ -1502,9 +1324,11 @@ void launch_dec_offsets_range(hipStream_t s, const DecJob *jobs, uint32_t sub_ba
 // jobs / status: of the group's first file; plan: device arrays (decode_api.cpp); epoch: this launch's (a new one every time; the
 // granules are never cleared)
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout)
+                         bool layout, const int64_t *plane_pitch)
 {
-    if (n_items)
+    if (n_items && plane_pitch)
+        hipLaunchKernelGGL(dec_unfilter_planar_kernel, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch, concurrent_status ? 0u : kDecUnfSkipMask, plane_pitch);
+    else if (n_items)
         hipLaunchKernelGGL(layout ? dec_unfilter_kernel<true> : dec_unfilter_kernel<false>, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch,
                            concurrent_status ? 0u : kDecUnfSkipMask);
 }
@@ -1532,12 +1356,18 @@ void dec_dump_tile_times(const char *path, uint32_t n_items)
     }
 }
 #endif
-void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout)
+void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout,
+                       const int64_t *plane_pitch)
 {
-    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout);
+    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch);
     if (!any_stored) return; // (a workgroup that finds its file is not a stored one leaves at once, but n_jobs x 512 of them is not free)
-    for (uint32_t j0 = 0; j0 < n_jobs; j0 += 32768) // (the y dimension of a grid holds at most 65535 workgroups)
-        hipLaunchKernelGGL(layout ? dec_stored_kernel<true> : dec_stored_kernel<false>, dim3(512, std::min(32768u, n_jobs - j0)), dim3(kDecBlock), 0, s, jobs + j0, status + j0);
+    for (uint32_t j0 = 0; j0 < n_jobs; j0 += 32768) { // (the y dimension of a grid holds at most 65535 workgroups)
+        const dim3 grid(512, std::min(32768u, n_jobs - j0));
+        if (plane_pitch)
+            hipLaunchKernelGGL(dec_stored_planar_kernel, grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0, plane_pitch + j0);
+        else
+            hipLaunchKernelGGL(layout ? dec_stored_kernel<true> : dec_stored_kernel<false>, grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0);
+    }
 }
 
 } // namespace fpng_amd

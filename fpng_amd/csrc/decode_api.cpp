@@ -315,6 +315,9 @@ struct Batch {
     bool device_data;
     hipStream_t s;
     uint32_t resident = 0, max_rounds = kMaxRounds;
+    const fpng_amd_png_planar *planar = nullptr; // fpng_amd_decode_batch(_device)_planar: the same for planar destinations
+    std::vector<int64_t> plane_pitch;            // (planar) a word per job, uploaded with the job records
+    int64_t *d_plane_pitch = nullptr;
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     std::vector<Parsed> ps;
     std::vector<DecJob> jobs;                // (their pointers into the scratch are offsets until place_files())
@@ -387,12 +390,25 @@ int parse_files(Batch &b)
             }
         }
         r.w = p.w, r.h = p.h, r.channels_in_file = p.c;
-        const uint32_t desired = b.ex ? kDstFormats[b.ex[i].format].bytes : b.desired;
+        const uint32_t desired = b.planar ? b.planar[i].num_chans : b.ex ? kDstFormats[b.ex[i].format].bytes : b.desired;
         const uint64_t need = (uint64_t)p.w * p.h * desired;
         if ((r.status = file_status(p, st, need))) continue;
         // (only files that will be written need room)
-        int64_t pitch = 0;
-        if (b.ex) {
+        int64_t pitch = 0, plane_pitch = 0;
+        if (b.planar) {
+            const fpng_amd_png_planar &x = b.planar[i];
+            pitch = x.row_pitch ? x.row_pitch : (int64_t)p.w;
+            const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
+            if (step < p.w) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w");
+            const uint64_t span = (uint64_t)(p.h - 1) * step + p.w; // a plane, from its lowest row's first byte
+            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)p.h * step);
+            if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
+            const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
+            if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w: the planes overlap");
+            if (pstep > (UINT64_MAX >> 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
+            if (!f.d_pixels || f.pixels_cap < (uint64_t)(desired - 1) * pstep + span)
+                return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w");
+        } else if (b.ex) {
             const uint64_t row = (uint64_t)p.w * desired;
             pitch = b.ex[i].row_pitch ? b.ex[i].row_pitch : (int64_t)row;
             const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
@@ -408,6 +424,7 @@ int parse_files(Batch &b)
         DecJob j = make_job(p, desired);
         j.out = f.d_pixels, j.sub_base = b.sub_total;
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
+        if (b.planar) j.pitch = (int32_t)pitch, b.plane_pitch.push_back(plane_pitch); // (|pitch| < 2^31: decode_files_planar)
         if (!p.mode) {
             b.sub_total += (j.n_sub + kDecSubBlock - 1) / kDecSubBlock * kDecSubBlock; // whole workgroups per file
             // offsets into the shared scratch (pointers are patched once the buffers exist)
@@ -439,11 +456,12 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     int rc;
     if ((rc = sc.place(e, b.d))) return rc;
     uint8_t *base = e->d_decode.p;
     b.d_luts = (uint32_t *)(base + o_luts), b.d_keys = base + o_keys, b.d_jobs = (DecJob *)(base + o_jobs), b.d_plan = base + o_plan, b.d_status = (uint32_t *)(base + o_status);
+    b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -541,6 +559,7 @@ int plan_groups(Batch &b)
     if (!pieces.empty()) std::memcpy(h_setup + b.setup_plan, pieces.data(), pieces.size() * sizeof(DecUnfPiece));
     if (!words.empty()) std::memcpy(h_setup + b.setup_plan + ((size_t)nj + kMaxGroups) * sizeof(DecUnfPiece), words.data(), words.size() * 4);
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
+    if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     return FPNG_AMD_OK;
 }
 
@@ -570,7 +589,8 @@ int finish_group(Batch &b, uint32_t gi)
     // (all groups run on one stream: two un-filter kernels never run at once -- each one's workgroups wait for lower-numbered ones
     //  of their own launch, and two sets of waiting workgroups could keep each other's predecessors off the compute units)
     const DecPlaced placed = {b.d.sub, b.d.block_off, b.d_eob + g.j0, 0xFFFFFFFFu};
-    launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr);
+    launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr,
+                      b.planar ? b.d_plane_pitch + g.j0 : nullptr);
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -702,17 +722,18 @@ int collect_results(Batch &b)
     return FPNG_AMD_OK;
 }
 
-// ex: fpng_amd_decode_batch(_device)_ex's files (files = their data and size; desired is not used)
+// ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used)
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
-                 const fpng_amd_png_ex *ex = nullptr)
+                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    if (!ex && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
+    if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
     std::memset(results, 0, (size_t)n * sizeof *results); // (every entry is defined on every way out)
     HIP_TRY(hipSetDevice(e->device));
     int rc = drain(e);
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
+    b.planar = planar;
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
     if ((rc = parse_files(b)) || !b.nj()) return rc;
@@ -943,6 +964,33 @@ int decode_files_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t 
     return decode_files(e, plain.data(), n, 0, results, device_data, files);
 }
 } // namespace
+
+namespace {
+static_assert(sizeof(fpng_amd_png_planar) == 48 && offsetof(fpng_amd_png_planar, d_pixels) == 16 && offsetof(fpng_amd_png_planar, pixels_cap) == 40, "fpng_amd_png_planar layout");
+// fpng_amd_decode_batch(_device)_planar: as decode_files_ex -- the rules that need no file here, the pitches' and the room's in parse_files
+int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data)
+{
+    if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    std::vector<fpng_amd_png> plain(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const fpng_amd_png_planar &x = files[i];
+        if (x.num_chans != 3 && x.num_chans != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "num_chans must be 3 or 4");
+        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
+        plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
+    }
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files);
+}
+} // namespace
+
+extern "C" int fpng_amd_decode_batch_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results)
+{
+    return decode_files_planar(e, files, n, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results)
+{
+    return decode_files_planar(e, files, n, results, true);
+}
 
 extern "C" int fpng_amd_decode_batch_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results)
 {

@@ -35,12 +35,12 @@ struct Job {
     // R,G,B[,A] bytes (0x0c = a zero byte).  These words were reserved before: the record stays 224 bytes and png_header where it
     // was, so the other kernels' code is, instruction for instruction, the same (tools/isa_diff.py)
     int64_t pitch;            // signed bytes from one row to the next
-    uint32_t src_bytes;       // 3 or 4
+    uint32_t src_bytes;       // 3 or 4; 1 = a planar job (fpng_amd_encode_submit_planar): a byte per pixel and plane
     uint32_t sel;
-    uint32_t reserved[2];
+    int64_t plane_pitch;      // planar jobs: signed bytes from one channel's plane to the next (R -> G -> B [-> A]); `rows` is the R plane's top row
     uint8_t png_header[60];   // 58 bytes used (reference fpng.cpp:1767-1791), IDAT length patched on device
 };
-static_assert(sizeof(Job) == 224 && offsetof(Job, pitch) == 136 && offsetof(Job, png_header) == 160, "Job layout");
+static_assert(sizeof(Job) == 224 && offsetof(Job, pitch) == 136 && offsetof(Job, plane_pitch) == 152 && offsetof(Job, png_header) == 160, "Job layout");
 
 struct RowInfo {
     uint32_t bits; // token bits of the row
@@ -110,6 +110,13 @@ void launch_encode_rows_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint
                            JobState *states, uint32_t *local, bool wide4);
 void launch_assemble_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
                         const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
+// fpng_amd_encode_submit_planar: the same chain again for planar jobs (Job::plane_pitch, src_bytes = 1), kernels of their own.
+// chan_mask as launch_encode_rows
+void launch_hist_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist);
+void launch_encode_rows_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
+                               JobState *states, uint32_t *local);
+void launch_assemble_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
+                            const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
 // table training: sums[0..288) += the 16-bit adjusted histogram of every image (hist_all: 288 counters per image)
 void launch_train_accumulate(hipStream_t s, const uint32_t *hist_all, uint32_t n_images, uint64_t *sums);
 // dst[0..16) |= src[0..16): the 16-byte piece two neighbouring band windows share (each holds zeros where the other's bits are)

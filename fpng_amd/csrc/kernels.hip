@@ -69,6 +69,16 @@ constexpr uint32_t kStoredExBlocks = 64; // stored_ex_kernel: workgroups per ima
 #ifndef FPNG_ROWS_WPE4
 #define FPNG_ROWS_WPE4 7
 #endif
+// the planar walks (encode_rows_planar_kernel): a super-window's source dwords are two per plane and row instead of the packed
+// walk's four per row: 65 / 77 vector registers (3 / 4 channels) and no scratch at six / five waves per SIMD, the setting the timings
+// of profiles/planar_timing.txt were taken with.  Seven / six compile to the same register counts, also without scratch, and have
+// not been timed; eight / seven spill in the super-window loop (profiles/planar_kernel_resources.txt)
+#ifndef FPNG_ROWS_WPE_PLANAR3
+#define FPNG_ROWS_WPE_PLANAR3 6
+#endif
+#ifndef FPNG_ROWS_WPE_PLANAR4
+#define FPNG_ROWS_WPE_PLANAR4 5
+#endif
 constexpr int kStageDwords = FPNG_STAGE_DWORDS; // per-wave LDS staging window of the output bit stream
 // Local-stream stores carry the non-temporal hint (build with -DFPNG_LOCAL_NT=0 to A/B it: the hint decides whether the
 // streams are kept in L2 / Infinity Cache for assemble_kernel)
@@ -145,6 +155,7 @@ __device__ __forceinline__ void wave_lds_fence()
 typedef const FPNG_GLOBAL uint8_t *gptr_cu8;
 typedef const FPNG_GLOBAL uint32_t *gptr_cu32;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef const FPNG_GLOBAL u32x4 *gptr_cu128;
 typedef FPNG_GLOBAL u32x4 *gptr_u128;
 typedef FPNG_GLOBAL uint8_t *gptr_u8;
@@ -377,6 +388,69 @@ template <int C, int L = 0> struct RowWindows {
     __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
 };
 
+// L = 1: a PLANAR source (fpng_amd_encode_submit_planar) -- one plane of w-byte rows per channel, Job::plane_pitch bytes apart, a
+// byte per pixel and plane.  One buffer resource per plane and row (all wave-uniform), each with its base aligned down to a dword
+// and its own byte phase, as the 3-byte path does: rows and planes start at any byte.  64-pixel windows load a byte per plane and
+// lane and pack the pixel; the super-windows load the dwords that hold the lane's four bytes of every plane (walk_row).  The
+// resources end with the dword the row's last byte lies in, so lanes past the row end may see up to three bytes that are not the
+// row's: the walk masks them, as it does for packed 3-byte pixels.
+template <int C> struct RowWindows<C, 1> {
+    static constexpr int SB = 1;
+    __amdgpu_buffer_rsrc_t cur[C], up[C];
+    uint32_t phase[C], up_phase[C];
+    uint32_t sel = 0;
+    uint32_t lane_ = 0;
+
+    // row / up_row: the R plane's rows; w: bytes of a plane's row
+    __device__ __forceinline__ void init_planes(const uint8_t *row, const uint8_t *up_row, int64_t plane_pitch, uint32_t w, uint32_t lane)
+    {
+        lane_ = lane;
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            const uint8_t *rp = row + (int64_t)ch * plane_pitch;
+            const uint32_t a = uniform((uint32_t)((uintptr_t)rp & 3));
+            phase[ch] = a;
+            cur[ch] = make_rsrc(rp - a, (a + w + 3) & ~3u);
+            // (branch-free, as in the primary template: no Up row -> a zero-sized resource, reads return 0)
+            const uint8_t *ub = (up_row ? up_row : row) + (int64_t)ch * plane_pitch;
+            const uint32_t b = uniform((uint32_t)((uintptr_t)ub & 3));
+            up_phase[ch] = b;
+            up[ch] = make_rsrc(ub - b, up_row ? ((b + w + 3) & ~3u) : 0u);
+        }
+    }
+    struct Raw {
+        uint32_t c[C], u[C];
+    };
+    __device__ __forceinline__ Raw load_raw(uint32_t x0) const
+    {
+        Raw q;
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            q.c[ch] = __builtin_amdgcn_raw_buffer_load_b8(cur[ch], lane_, x0 + phase[ch], 0);
+            q.u[ch] = __builtin_amdgcn_raw_buffer_load_b8(up[ch], lane_, x0 + up_phase[ch], 0);
+        }
+        return q;
+    }
+    static __device__ __forceinline__ uint32_t pack(const uint32_t (&b)[C])
+    {
+        const uint32_t lo = b[0] | (b[1] << 8);
+        return lo | ((C == 4 ? (b[2] | (b[3] << 8)) : b[2]) << 16);
+    }
+    __device__ __forceinline__ uint32_t filter(const Raw &q) const { return sub_bytes(pack(q.c), pack(q.u)); } // (C == 3: the top byte is 0 - 0)
+    __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
+};
+// the dwords of one super-window of a planar row: per plane the two that hold the lane's four bytes
+template <int C> struct PlaneDwords {
+    uint32_t lo[C], hi[C];
+};
+// pixel 0 of the four that a lane's plane dwords hold (byte 0 of each plane's dword)
+template <int C> __device__ __forceinline__ uint32_t planar_first_pixel(const uint32_t (&fd)[4])
+{
+    const uint32_t rg = __builtin_amdgcn_perm(fd[1], fd[0], 0x0c0c0400u);
+    if (C == 4) return __builtin_amdgcn_perm(__builtin_amdgcn_perm(fd[3], fd[2], 0x0c0c0400u), rg, 0x05040100u);
+    return __builtin_amdgcn_perm(fd[2], rg, 0x0c040100u);
+}
+
 // 64-bit mask of lanes whose pixel index x0+lane is below `limit`
 __device__ __forceinline__ uint64_t valid_mask(uint32_t x0, uint32_t limit)
 {
@@ -550,7 +624,10 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
 
     RowWindows<C, L> px;
     if (L) px.sel = uniform(job.sel);
-    px.init(row, up_row, L ? w * (uint32_t)SB : bpl, lane);
+    if constexpr (L == 1)
+        px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane);
+    else
+        px.init(row, up_row, L ? w * (uint32_t)SB : bpl, lane);
 
     Rle<C> rle;
     uint32_t row_bits = 0, last_unit = 0;
@@ -689,7 +766,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
         if (kSums) {
             // Adler-32 partial sums (reference fpng.cpp:407-487 computes the same quantity serially).  Lanes
             // past the row end read 0 (RGBA) or are masked (RGB shares an aligned dword with real bytes).
-            const uint32_t fa = (!TAIL || C == 4 || valid) ? f_cur : 0u;
+            const uint32_t fa = (!TAIL || (C == 4 && L != 1) || valid) ? f_cur : 0u;
             const uint32_t a = __builtin_amdgcn_sad_u8(fa, 0u, 0u);
             acc_a += a;
             acc_w += (uint64_t)(bpl - (uint32_t)C * (x0 + lane)) * a; // invalid lanes: a == 0
@@ -734,15 +811,33 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
         constexpr uint32_t S0 = 0; // the walk's first super-window
         if (NSX > S0) {
             const uint32_t voff4 = lane * kSrcLaneBytes;
-            auto load4 = [&](uint32_t S, u32x4 &c4, u32x4 &u4) {
+            // (planar sources: per plane, the two aligned dwords that hold the lane's four bytes of the row and of the row above)
+            using W4 = std::conditional_t<L == 1, PlaneDwords<C>, u32x4>;
+            auto load4 = [&](uint32_t S, W4 &c4, W4 &u4) {
+                if constexpr (L == 1) {
+#pragma unroll
+                    for (int ch = 0; ch < C; ch++) {
+                        const u32x2 c2 = __builtin_amdgcn_raw_buffer_load_b64(px.cur[ch], voff4, S * kSrcSuperBytes, 0);
+                        const u32x2 u2 = __builtin_amdgcn_raw_buffer_load_b64(px.up[ch], voff4, S * kSrcSuperBytes, 0);
+                        c4.lo[ch] = c2.x, c4.hi[ch] = c2.y, u4.lo[ch] = u2.x, u4.hi[ch] = u2.y;
+                    }
+                } else {
                 // RGB: 16 aligned bytes that contain the lane's 12 (the resources start on a dword, the row begins
                 // px.phase / px.up_phase bytes into them)
                 c4 = __builtin_amdgcn_raw_buffer_load_b128(px.cur, voff4, S * kSrcSuperBytes, 0);
                 u4 = __builtin_amdgcn_raw_buffer_load_b128(px.up, voff4, S * kSrcSuperBytes, 0); // (an nt hint on this last use of the row: 0.557 vs 0.500 ms)
+                }
             };
             // filtered bytes of the lane's four pixels, packed: fd[0..ND) (L != 0: in source order, four dwords for 4-byte sources)
-            auto filt = [&](const u32x4 &c4, const u32x4 &u4, uint32_t (&fd)[4]) {
-                if constexpr (SB == 4) {
+            // (planar: fd[ch] = the lane's four filtered bytes of plane ch)
+            auto filt = [&](const W4 &c4, const W4 &u4, uint32_t (&fd)[4]) {
+                if constexpr (L == 1) {
+#pragma unroll
+                    for (int ch = 0; ch < C; ch++)
+                        fd[ch] = sub_bytes(__builtin_amdgcn_alignbyte(c4.hi[ch], c4.lo[ch], px.phase[ch]),
+                                           __builtin_amdgcn_alignbyte(u4.hi[ch], u4.lo[ch], px.up_phase[ch]));
+                    if (C == 3) fd[3] = 0;
+                } else if constexpr (SB == 4) {
                     sub_bytes_x4(c4, u4, fd);
                 } else {
                     u32x4 ca, ua;
@@ -758,7 +853,18 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             };
             // pixel values (what the per-pixel walk calls f_cur): RGBA = the dwords, RGB = 24-bit fields
             auto pixels = [&](const uint32_t (&fd)[4], uint32_t (&pv)[4]) {
-                if constexpr (L == 4) {
+                if constexpr (L == 1) {
+                    // byte transpose, planes -> pixels: R and G interleaved first, then joined with B (and A)
+                    const uint32_t rg01 = __builtin_amdgcn_perm(fd[1], fd[0], 0x05010400u), rg23 = __builtin_amdgcn_perm(fd[1], fd[0], 0x07030602u);
+                    if constexpr (C == 4) {
+                        const uint32_t ba01 = __builtin_amdgcn_perm(fd[3], fd[2], 0x05010400u), ba23 = __builtin_amdgcn_perm(fd[3], fd[2], 0x07030602u);
+                        pv[0] = __builtin_amdgcn_perm(ba01, rg01, 0x05040100u), pv[1] = __builtin_amdgcn_perm(ba01, rg01, 0x07060302u);
+                        pv[2] = __builtin_amdgcn_perm(ba23, rg23, 0x05040100u), pv[3] = __builtin_amdgcn_perm(ba23, rg23, 0x07060302u);
+                    } else {
+                        pv[0] = __builtin_amdgcn_perm(fd[2], rg01, 0x0c040100u), pv[1] = __builtin_amdgcn_perm(fd[2], rg01, 0x0c050302u);
+                        pv[2] = __builtin_amdgcn_perm(fd[2], rg23, 0x0c060100u), pv[3] = __builtin_amdgcn_perm(fd[2], rg23, 0x0c070302u);
+                    }
+                } else if constexpr (L == 4) {
 #pragma unroll
                     for (int j = 0; j < 4; j++) pv[j] = __builtin_amdgcn_perm(0u, fd[j], px.sel);
                 } else if constexpr (L == 3) {
@@ -777,14 +883,14 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
                 }
             };
             constexpr int PF4 = 1; // super-windows in flight ahead of the look-ahead one
-            u32x4 c_first, u_first, rc[PF4], ru[PF4];
+            W4 c_first, u_first, rc[PF4], ru[PF4];
             load4(S0, c_first, u_first);
 #pragma unroll
             for (int j = 0; j < PF4; j++) load4(S0 + (uint32_t)j + 1, rc[j], ru[j]);
             uint32_t fd[4];
             filt(c_first, u_first, fd);
             // pixel just before the super-window; in front of pixel 0: a value pixel 0 cannot equal (it has no left neighbour)
-            uint32_t last_f = L ? ~uniform(__builtin_amdgcn_perm(0u, fd[0], px.sel)) : ~uniform(fd[0]);
+            uint32_t last_f = L == 1 ? ~uniform(planar_first_pixel<C>(fd)) : L ? ~uniform(__builtin_amdgcn_perm(0u, fd[0], px.sel)) : ~uniform(fd[0]);
             uint32_t wgt = bpl - kLaneBytes * lane - S0 * kSuperBytes; // bytes from this lane's first byte to the row end
             const uint32_t c1_bits = chunk1 & 0xFF;
             // gather the per-pixel view of 64-pixel window jw of the current super-window (lane i <- pixel 64*jw+i)
@@ -809,7 +915,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
                     if (S + 1 + PF4 <= NS) load4(S + 1 + PF4, rc[js], ru[js]);
                     uint32_t f[4]; // the four pixels of this lane
                     pixels(fd, f);
-                    const uint32_t next_first = L ? __builtin_amdgcn_perm(0u, fn[0], px.sel) : (C == 4) ? fn[0] : (fn[0] & 0xFFFFFFu);
+                    const uint32_t next_first = L == 1 ? planar_first_pixel<C>(fn) : L ? __builtin_amdgcn_perm(0u, fn[0], px.sel) : (C == 4) ? fn[0] : (fn[0] & 0xFFFFFFu);
                     // per-lane "equals its left neighbour" predicates (their SGPR form is the wave ballot)
                     const bool s0 = f[0] == lane_prev(f[3], last_f); // (pixel 0 of the row: last_f was chosen to differ)
                     const bool s1 = f[1] == f[0], s2 = f[2] == f[1], s3 = f[3] == f[2];
@@ -982,8 +1088,8 @@ __device__ __forceinline__ const Job &job_of_block(const Job *jobs) { return job
 // hist_kernel (2-pass, pass 1): literal / length-symbol histogram of the whole image
 // (reference fpng.cpp:1021-1084 / :1299-1363).  job.table here is the "symbol" table whose
 // chunk[q] holds (length symbol - 256).
-// EX: the jobs of fpng_amd_encode_submit_ex (hist_ex_kernel), walked with their source layout
-template <bool EX = false>
+// EX: 1 = the jobs of fpng_amd_encode_submit_ex (hist_ex_kernel), walked with their source layout; 2 = planar jobs (hist_planar_kernel)
+template <int EX = 0>
 __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
 {
     __shared__ PackedTables T;
@@ -994,7 +1100,12 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, r = blockIdx.x * kHistWaves + uniform(threadIdx.x >> 6);
     if (r < job.nrows) {
-        if (EX) {
+        if (EX == 2) {
+            if (job.c == 4)
+                walk_row<4, Pass::Hist, 1>(job, T, hist, r, lane, nullptr);
+            else
+                walk_row<3, Pass::Hist, 1>(job, T, hist, r, lane, nullptr);
+        } else if (EX) {
             if (job.c == 4)
                 walk_row<4, Pass::Hist, 4>(job, T, hist, r, lane, nullptr);
             else if (job.src_bytes == 4)
@@ -1021,6 +1132,11 @@ __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) vo
 __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_ex_kernel(const Job *jobs, uint32_t *hist_out)
 {
     hist_block<true>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
+}
+// the jobs of fpng_amd_encode_submit_planar
+__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_planar_kernel(const Job *jobs, uint32_t *hist_out)
+{
+    hist_block<2>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
 }
 // (JobArg / the *_first_kernel forms: one image per submission, its job record in the kernel arguments -- see encode_rows_first_kernel)
 struct JobArg {
@@ -1292,6 +1408,16 @@ __global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdg
     encode_rows_block<C, L>(jobs[by], by, bx, rows_out, states, local);
 }
 
+// the planar jobs (fpng_amd_encode_submit_planar) of C channels: RowWindows<C, 1>
+template <int C, int WPE>
+__global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_planar_kernel(const Job *jobs, RowInfo *rows_out,
+                                                                                                             JobState *states, uint32_t *local)
+{
+    uint32_t bx, by;
+    xcd_block_order(bx, by);
+    encode_rows_block<C, 1>(jobs[by], by, bx, rows_out, states, local);
+}
+
 // One image per submission, first kernel of its chain: the job record comes IN THE KERNEL ARGUMENTS instead of through an
 // upload in front of the chain (a blit kernel + a dispatch gap: ~7 us of a single frame's ~90); workgroup 0 leaves it in
 // device memory for scan / assemble / finalize, which start after this kernel has ended.
@@ -1551,10 +1677,16 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(const Job *jobs, const
 // EX: jobs of fpng_amd_encode_submit_ex -- PNG byte b of a row is channel b % c of pixel b / c, found in the source through the
 // job's pitch, pixel size and selector; those images take the byte-by-byte path for every piece (stored blocks are their fallback
 // and FPNG_FORCE_UNCOMPRESSED's form, not a hot path)
-template <bool EX = false>
+// EX == 2: planar jobs (stored_planar_kernel) -- channel ch of pixel p of a row lies at ch * plane_pitch + row * pitch + p
+template <int EX = 0>
 __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 px, uint32_t s)
 {
     const uint32_t stride = job.bpl + 1, row = s / stride, col = s - row * stride;
+    if (EX == 2) {
+        if (!col) return 0u;
+        const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
+        return (uint32_t)px[(int64_t)ch * job.plane_pitch + (int64_t)row * job.pitch + (int64_t)p];
+    }
     if (EX) {
         if (!col) return 0u;
         const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
@@ -1563,7 +1695,7 @@ __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 
     return col ? (uint32_t)px[(size_t)row * job.bpl + col - 1] : 0u;
 }
 
-template <bool EX = false>
+template <int EX = 0>
 __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &st, int64_t range_begin, uint32_t range_bytes, int32_t db, int32_t de,
                                                 uint32_t (*tab)[256], uint32_t *red, const CrcDeviceTables *tabs, uint32_t *crc_out, uint32_t *adler_out)
 {
@@ -1912,6 +2044,33 @@ __global__ __launch_bounds__(kBlock) void stored_ex_kernel(const Job *jobs, cons
         const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
         const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
         assemble_stored<true>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
+        __syncthreads(); // (`red` is read by thread 0 at the end of the range)
+    }
+}
+
+// stored_planar_kernel: the same for the planar jobs of fpng_amd_encode_submit_planar
+__global__ __launch_bounds__(kBlock) void stored_planar_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
+                                                          uint32_t *adler_parts, uint32_t max_crc_blocks)
+{
+    __shared__ uint32_t tab[16][256];
+    __shared__ uint32_t red[3 * kWavesPerBlock];
+    const Job &job = job_of_block(jobs);
+    const JobState &st = states[blockIdx.y];
+    if (uniform(st.mode) == 0u || uniform(st.status)) return;
+    const int64_t data_begin = kPngHeaderBytes, data_end = (int64_t)(kPngHeaderBytes + st.zlib_size - 4);
+    const int64_t end_aligned = (data_end + 15) & ~15ll;
+    const uint32_t range_bytes = 1u << uniform(crc_range_log2(st));
+    auto sat = [](int64_t v) { return (int32_t)(v > 0x7FFFFFFFll ? 0x7FFFFFFFll : (v < -0x7FFFFFFFll ? -0x7FFFFFFFll : v)); };
+    if (end_aligned - (int64_t)blockIdx.x * range_bytes <= (data_begin & ~15ll)) return;
+    for (int i = threadIdx.x; i < 16 * 256; i += kBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
+    __syncthreads();
+    for (uint32_t b = blockIdx.x; b < max_crc_blocks; b += gridDim.x) {
+        const int64_t range_end = end_aligned - (int64_t)b * range_bytes;
+        if (range_end <= (data_begin & ~15ll)) break; // nothing of the data in this range or the ones behind it
+        const int64_t range_begin = range_end - range_bytes;
+        const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
+        const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
+        assemble_stored<2>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
         __syncthreads(); // (`red` is read by thread 0 at the end of the range)
     }
 }
@@ -2438,6 +2597,18 @@ void launch_encode_rows_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint
     else if (layout_mask & 2u)
         hipLaunchKernelGGL((encode_rows_ex_kernel<4, FPNG_ROWS_WPE, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
 }
+void launch_hist_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist)
+{
+    hipLaunchKernelGGL(hist_planar_kernel, dim3((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1), dim3(kHistBlock), 0, s, jobs, hist);
+}
+void launch_encode_rows_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
+                               JobState *states, uint32_t *local)
+{
+    if (chan_mask & 1u)
+        hipLaunchKernelGGL((encode_rows_planar_kernel<3, FPNG_ROWS_WPE_PLANAR3>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+    if (chan_mask & 2u)
+        hipLaunchKernelGGL((encode_rows_planar_kernel<4, FPNG_ROWS_WPE_PLANAR4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+}
 void launch_encode_rows_first(hipStream_t s, const Job &job, Job *d_job, RowInfo *rows, JobState *states, uint32_t *local)
 {
     JobArg arg;
@@ -2461,6 +2632,14 @@ void launch_assemble_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_
     // (a small grid: for compressed images -- the usual case -- its workgroups only look at the mode)
     const uint32_t gx = std::min(max_crc_blocks, kStoredExBlocks);
     hipLaunchKernelGGL(stored_ex_kernel, dim3(gx, n_jobs), dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
+    hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
+                       partials, (uint32_t *)nullptr, max_crc_blocks);
+}
+void launch_assemble_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
+                            const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts)
+{
+    const uint32_t gx = std::min(max_crc_blocks, kStoredExBlocks);
+    hipLaunchKernelGGL(stored_planar_kernel, dim3(gx, n_jobs), dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
     hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
                        partials, (uint32_t *)nullptr, max_crc_blocks);
 }

@@ -218,6 +218,30 @@ typedef struct fpng_amd_image_ex {
  * padding and X bytes never reach the file. */
 int fpng_amd_encode_submit_ex(fpng_amd_encoder *enc, const fpng_amd_image_ex *images, uint32_t n, uint32_t flags, uint64_t *ticket);
 
+/* ---- planar (channels-first, CHW) device images: one plane of w-byte rows per channel, in R, G, B[, A] order, described by ONE
+ *      base pointer and two signed pitches -- a torch (c, h, w) uint8 tensor or view as it lies, encoded without a permute copy.
+ *      The file is byte for byte the one fpng_encode_image_to_memory() writes for the same pixels interleaved as R,G,B[,A].
+ *      Planar is no FPNG_AMD_SRC_* format; it has records and entry points of its own.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encode_submit_planar with dlsym. ---- */
+typedef struct fpng_amd_image_planar {
+    const void *d_pixels; /* DEVICE: first byte of the TOP row of the R plane */
+    int64_t row_pitch;    /* signed bytes between rows inside a plane; 0 = w; negative = bottom-up rows */
+    int64_t plane_pitch;  /* signed bytes from one channel's plane to the next (R -> G -> B [-> A]); 0 = h * |row_pitch|;
+                           * negative: the planes lie in [A,]B,G,R order in memory and d_pixels points into the last one */
+    uint32_t w, h, num_chans, reserved; /* num_chans 3 or 4 = the PNG's channels; reserved = 0 */
+    uint8_t *d_out;       /* DEVICE pointer, 16-byte aligned, receives the whole .png file */
+    size_t out_cap;       /* >= fpng_amd_max_encoded_size(w, h, num_chans) */
+} fpng_amd_image_planar; /* 56 bytes, no padding */
+
+/* fpng_amd_encode_submit() for planar images.  One submission may mix channel counts and pitches; its ticket works with
+ * fpng_amd_encode_wait / _query / _finish / _join like any other.  Planes and rows may start at ANY byte and be pitched by any
+ * amount.  Rules, all checked before anything is launched (a failed call enqueues nothing and hands out no ticket):
+ * |row_pitch| >= w; |plane_pitch| >= (h - 1) * |row_pitch| + w (the planes do not overlap); num_chans 3 or 4; reserved 0; w, h,
+ * d_out and out_cap as for fpng_amd_encode_submit (FPNG_AMD_ERR_BUFFER_TOO_SMALL for out_cap, else FPNG_AMD_ERR_INVALID_ARG).
+ * The source is only read: of the w bytes of each of the num_chans * h rows every byte reaches the file, and nothing beyond the
+ * aligned dwords those bytes lie in is touched -- num_chans = 3 over a tensor that has a fourth plane never reads that plane. */
+int fpng_amd_encode_submit_planar(fpng_amd_encoder *enc, const fpng_amd_image_planar *images, uint32_t n, uint32_t flags, uint64_t *ticket);
+
 /* Device-side join: the encoder's stream waits (no host wait) for every submission made so far. */
 int fpng_amd_encoder_join(fpng_amd_encoder *enc);
 
@@ -480,6 +504,29 @@ typedef struct fpng_amd_png_ex {
  * d_pixels is NULL or pixels_cap < (h - 1) * |row_pitch| + w * format bytes (a file the container walk rejects needs no room). */
 int fpng_amd_decode_batch_ex(fpng_amd_encoder *enc, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results);
 int fpng_amd_decode_batch_device_ex(fpng_amd_encoder *enc, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results);
+/* ---- decoding into planar (channels-first, CHW) device images -- the twin of fpng_amd_encode_submit_planar: num_chans planes of
+ *      w-byte rows in R, G, B[, A] order.  The values are those fpng_decode_memory() gives for desired_channels = num_chans: a
+ *      3-channel file into four planes fills the A plane with 0xFF, a 4-channel file into three planes drops alpha.  Only the
+ *      num_chans * h spans of w bytes are written, whatever a file's status: not a byte of pitch padding, of the space between
+ *      the planes, or in front of or behind them.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar with dlsym. ---- */
+typedef struct fpng_amd_png_planar {
+    const void *data;   /* the file: HOST memory (fpng_amd_decode_batch_planar) or DEVICE memory (fpng_amd_decode_batch_device_planar) */
+    uint32_t size;
+    uint32_t num_chans; /* planes written, 3 or 4 */
+    uint8_t *d_pixels;  /* DEVICE: first byte of the TOP row of the R plane */
+    int64_t row_pitch;  /* signed bytes between rows inside a plane; 0 = w; negative = bottom-up rows */
+    int64_t plane_pitch; /* signed bytes from one channel's plane to the next; 0 = h * |row_pitch|; negative: planes in [A,]B,G,R order */
+    size_t pixels_cap;  /* bytes writable from the LOWEST-addressed row's first byte: (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w */
+} fpng_amd_png_planar;  /* 48 bytes, no padding */
+/* status, w, h and channels_in_file of every file are what fpng_amd_decode_batch(_device) returns with desired_chans = num_chans
+ * (FPNG_AMD_DECODE_UNDECIDED included; FPNG_AMD_DECODE_MAX_ROUNDS works the same).  One batch may mix channel counts, pitches and
+ * 3- / 4-channel files.  Rules (a failed call writes no pixel and launches nothing that could): FPNG_AMD_ERR_INVALID_ARG for
+ * num_chans other than 3 or 4, |row_pitch| >= 2^31, and -- for files whose header is accepted -- 0 < |row_pitch| < w or planes that
+ * overlap (0 < |plane_pitch| < (h - 1) * |row_pitch| + w); FPNG_AMD_ERR_BUFFER_TOO_SMALL when d_pixels is NULL or pixels_cap is
+ * below the span above (a file the container walk rejects needs no room). */
+int fpng_amd_decode_batch_planar(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_planar(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

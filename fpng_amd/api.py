@@ -27,6 +27,10 @@ FPNG_ADLER32_INIT = 1         # reference src/fpng.h:30
 
 MODE_COMPRESSED, MODE_STORED = 0, 1
 
+# Encoder.set_decode_verify (FPNG_AMD_VERIFY_* in include/fpng_amd.h) and the two statuses only a checked decode returns
+VERIFY_CRC32, VERIFY_ADLER32 = 1, 2
+DECODE_BAD_CRC32, DECODE_BAD_ADLER32 = 65, 66
+
 # source formats of Encoder.submit_ex (FPNG_AMD_SRC_* in include/fpng_amd.h): name -> (value, source bytes per pixel, PNG channels)
 SRC_FORMATS = {"RGB": (0, 3, 3), "BGR": (1, 3, 3), "RGBA": (2, 4, 4), "BGRA": (3, 4, 4), "ARGB": (4, 4, 4), "ABGR": (5, 4, 4),
                "RGBX": (6, 4, 3), "BGRX": (7, 4, 3), "XRGB": (8, 4, 3), "XBGR": (9, 4, 3)}
@@ -764,6 +768,17 @@ class Encoder:
     def decode_batch_planar(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_planar: decode_device_planar() for files in host memory (bytes)."""
         return self._decode_planar("decode_batch_planar", self.lib.fpng_amd_decode_batch_planar, False, pngs, outs, order, bottom_up, results)
+
+    def set_decode_verify(self, flags):
+        """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32
+        (VERIFY_CRC32) and / or the zlib stream's Adler-32 (VERIFY_ADLER32); 0 = neither (the default, and the reference's
+        behaviour).  A file that would have decoded with status 0 then returns DECODE_BAD_CRC32 (65) or DECODE_BAD_ADLER32 (66)
+        when the checksum in the file is not the one of its bytes; every other status stays what it is."""
+        check(self.lib.fpng_amd_encoder_set_decode_verify(self.h, int(flags)))
+
+    @property
+    def decode_verify(self):
+        return int(self.lib.fpng_amd_encoder_decode_verify(self.h))
 
     def last_decode_phase_ms(self):
         """{"sync", "offsets", "emit", "unfilter"} -> ms of the last decode call's kernels (first group of files), measured with HIP

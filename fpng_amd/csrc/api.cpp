@@ -150,6 +150,12 @@ int ensure_device_tables(int dev)
 
 } // namespace
 
+const CrcDeviceTables *fpng_amd::device_crc_tables(int device)
+{
+    std::lock_guard<std::mutex> lock(g_mu);
+    return device >= 0 && device < kMaxDevices ? g_dev[device].crc : nullptr;
+}
+
 // reference src/fpng.cpp:1670-1680 plus the 32-bit arithmetic limit of :1682-1705
 int fpng_amd::check_dims(uint32_t w, uint32_t h, uint32_t c)
 {
@@ -404,6 +410,8 @@ void fpng_amd_encoder_destroy(fpng_amd_encoder *e)
     for (hipEvent_t ev : e->dec_ev2)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->dec_ev3)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->dec_crc_ev)
         if (ev) (void)hipEventDestroy(ev);
     e->h_dec_fetch.release();
     if (e->dec_up) (void)hipStreamDestroy(e->dec_up);

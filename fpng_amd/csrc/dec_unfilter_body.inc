@@ -4,6 +4,9 @@
 //   kLayout, kPlanar   constexpr bool: DecJob::sel / pitch destinations; planes (dst_c planes of w-byte rows, DecJob::pitch between a
 //                      plane's rows, plane_pitch[file] between the planes).  Only the last stage ("the pixels") differs.
 //   plane_pitch        const int64_t *, a word per file of `jobs` (kPlanar; else a null constant that is never read)
+//   kVerify            constexpr bool: the tile also sums its filtered bytes for the file's Adler-32 (fpng_amd_encoder_set_decode_verify);
+//                      false in the three kernels that were there before, whose instructions it leaves alone
+//   adler_acc          unsigned long long *, two words per file of `jobs` (kVerify; else a null constant that is never read)
 // and the kernel's arguments jobs, plan, placed, item0, status, epoch, skip_mask.
     __shared__ __attribute__((aligned(16))) uint8_t tile_mem[kUnfRows * kTilePitch];
     __shared__ uint32_t mask_mem[kUnfRows * kRowMaskWords], epx_mem[kUnfRows]; // the rows' marked pixels (long matches), their entry pixels
@@ -117,6 +120,22 @@
         lds_u32 *T = (lds_u32 *)(tile + kTileData) + (three ? wv * 48 + lane : threadIdx.x); // this thread's dword column of the tile
         constexpr uint32_t P = kTilePitch / 4;
         uint32_t p = 0;
+        // (kVerify) The Adler-32 of the filtered stream, from the dwords this loop holds anyway: s1 = the bytes' sum, s2 = their sum
+        // weighted with N - i, the bytes from byte i of the stream to its end (N = (bpl + 1) * h; the byte at row y, offset j of
+        // the row's data is i = y * (bpl + 1) + 1 + j).  A dword's four weights are vw3 + 3, + 2, + 1, + 0 with vw3 the weight of
+        // its last byte mod 65521 (bytes past the row's end are masked to zero: theirs does not matter): vw3 * (sum of the bytes)
+        // + (3, 2, 1, 0) . bytes, at most 65520 * 1020 + 1530 a dword -- 48 rows of them fit 32 bits.  The filter bytes
+        // (checked above: kDecBadFilter) are added in closed form by dec_verify_kernel.
+        uint32_t vs1 = 0, vs2 = 0, vw3 = 0, vstep = 0, vmask = 0;
+        if constexpr (kVerify) {
+            static_assert(kUnfRows <= 64, "a thread's weighted sum must fit 32 bits");
+            const uint64_t stride = (uint64_t)job.bpl + 1;
+            const uint32_t row_m = (uint32_t)((stride * (job.h - y0) - 1) % kAdlerMod); // N - (y0 * stride + 1): the weight of row y0's first data byte
+            vw3 = (row_m + kAdlerMod - (4u * j4 + 3u) % kAdlerMod) % kAdlerMod;
+            vstep = (uint32_t)(stride % kAdlerMod);
+            const uint32_t nbv = active ? min(4u, job.bpl - 4u * j4) : 0u;
+            vmask = nbv == 4 ? 0xFFFFFFFFu : (1u << (8 * nbv)) - 1u;
+        }
         if (active) {
             for (uint32_t k = 0; k < nrows; k += 8) {
                 uint32_t t8[8];
@@ -124,7 +143,31 @@
                 for (uint32_t q = 0; q < 8; q++) t8[q] = T[min(k + q, nrows - 1) * P];
 #pragma unroll
                 for (uint32_t q = 0; q < 8; q++)
-                    if (k + q < nrows) p = add_bytes(p, t8[q]), T[(k + q) * P] = p;
+                    if (k + q < nrows) {
+                        if constexpr (kVerify) {
+                            const uint32_t v = t8[q] & vmask, bs = __builtin_amdgcn_sad_u8(v, 0u, 0u);
+                            vs1 += bs;
+                            vs2 += vw3 * bs + 3u * (v & 0xFFu) + 2u * ((v >> 8) & 0xFFu) + ((v >> 16) & 0xFFu);
+                            vw3 = vw3 >= vstep ? vw3 - vstep : vw3 + kAdlerMod - vstep;
+                        }
+                        p = add_bytes(p, t8[q]), T[(k + q) * P] = p;
+                    }
+            }
+        }
+        if constexpr (kVerify) {
+            // The lanes that are still here form a prefix of the wave (lanes without a column have left, or -- where pixels are
+            // widened or planes written -- all 64 have stayed): a reduction towards lane 0 through lanes that exist, then one
+            // atomic add per sum and wave.  Integer adds commute: the file's sums do not depend on the order of the tiles.
+            const uint32_t alive = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(true));
+            vs2 %= kAdlerMod;
+#pragma unroll
+            for (uint32_t o = 32; o; o >>= 1) {
+                const uint32_t a1 = (uint32_t)__shfl_down((int)vs1, o, kWave), a2 = (uint32_t)__shfl_down((int)vs2, o, kWave);
+                if (lane + o < alive) vs1 += a1, vs2 += a2;
+            }
+            if (lane == 0 && (vs1 | vs2)) {
+                atomicAdd(&adler_acc[2 * (size_t)ji], (unsigned long long)vs1);
+                atomicAdd(&adler_acc[2 * (size_t)ji + 1], (unsigned long long)vs2);
             }
         }
         FPNG_TILE_STAMP(2);

@@ -24,7 +24,11 @@ enum : uint32_t { kDecTileBadStream = 4u, kDecTileLeaveToCpu = 64u, kDecTileStal
 // the bits for which dec_unfilter_kernel skips a file's tiles in the batch path: set only by kernels in FRONT of its launch, never
 // by the kernel itself, so that every thread of every workgroup reads the same answer (a tile that skips publishes no look-back granule)
 constexpr uint32_t kDecUnfSkipMask = kDecNotConverged | kDecBadStream | kDecStalled;
-static_assert(!(kDecUnfSkipMask & (kDecTileBadStream | kDecTileLeaveToCpu | kDecTileStalled | kDecBadFilter)), "dec_unfilter_kernel must not set the bits it skips on");
+// what the optional check of a file's checksums found (fpng_amd_encoder_set_decode_verify; set by dec_verify_kernel, the last kernel
+// of the chain, and read by the host only for files whose other bits say "decoded": decode_api.cpp, verify_result): the IDAT
+// chunk's CRC-32 / the zlib stream's Adler-32 is not what the file says
+enum : uint32_t { kDecBadCrc = 0x200u, kDecBadAdler = 0x400u };
+static_assert(!(kDecUnfSkipMask & (kDecTileBadStream | kDecTileLeaveToCpu | kDecTileStalled | kDecBadFilter | kDecBadCrc | kDecBadAdler)), "dec_unfilter_kernel must not set the bits it skips on");
 
 struct DecJob {
     const uint8_t *z;         // device: the zlib stream (IDAT payload) from the dword its first byte (0x78) lies in; readable up to z_bytes + 16 rounded down to a dword
@@ -151,10 +155,43 @@ struct DecPlaced {
 // layout: the jobs are fpng_amd_decode_batch_ex's (DecJob::sel / pitch: the *_ex kernels write them; a launch is all one or the other)
 // plane_pitch (device, a word per file of `jobs`, or NULL): the jobs are fpng_amd_decode_batch_planar's -- dst_c planes, DecJob::pitch
 // between a plane's rows; the *_planar kernels write them
+// adler_acc (device, two 64-bit words per file of `jobs`, or NULL): the verify forms of the kernels run instead -- every tile adds its
+// filtered bytes' sum and position-weighted sum (mod 65521) to its file's two words (DecVerify)
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout = false, const int64_t *plane_pitch = nullptr);
+                         bool layout = false, const int64_t *plane_pitch = nullptr, unsigned long long *adler_acc = nullptr);
+// The optional check of the files' checksums (fpng_amd_encoder_set_decode_verify), per launch of launch_dec_finish: flags =
+// FPNG_AMD_VERIFY_*; adler_acc as above, zero when the launch begins; crc_partials: max_ranges words per file that launch_dec_crc
+// filled (FPNG_AMD_VERIFY_CRC32).  All pointers are the entries of the launch's first file.
+struct CrcDeviceTables;
+struct DecVerify {
+    uint32_t flags, max_ranges;
+    uint32_t stored_blocks, pad_; // the most stored blocks (of 65535 bytes) a stored file of the launch has
+    unsigned long long *adler_acc;
+    const uint32_t *crc_partials;
+    const CrcDeviceTables *tabs;
+};
+// ranges of kDecCrcRange bytes that launch_dec_crc cuts a payload of idat_len bytes at address z into (they hang off the payload's
+// end, rounded up to 16 bytes).  The one place this is computed: the host sizes the partials with it, dec_crc_kernel's grid covers
+// it and dec_verify_kernel folds that many.  A file has a 32-bit size and at least 57 bytes that are not IDAT payload (signature,
+// IHDR, the IDAT's own 12 bytes, IEND), so payload + 2 * 15 bytes of alignment < 2^32: at most 2^32 / range of them.
+// crc_fold_partials (crc_device.h) gives each of its kCrcBlock = 256 threads 2^g partials, g <= 8 (its table of in-group powers
+// has 256 entries), and reads CrcDeviceTables::fold[range log2 + g - 12] of 13 rows: both hold while a file has at most 2^16 ranges
+// of at most 2^16 bytes.
+constexpr uint32_t kDecCrcRangeLog2 = 16;
+static_assert(kDecCrcRangeLog2 >= 12 && 32 - kDecCrcRangeLog2 <= 8 + 8 && kDecCrcRangeLog2 + 8 - 12 <= 12,
+              "a file's CRC ranges: at most 256 threads x 256 partials, and CrcDeviceTables::fold has rows e = 12 .. 24 (crc_fold_partials)");
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline uint32_t dec_crc_ranges(uintptr_t z, uint64_t idat_len)
+{
+    const uint64_t a = z & ~(uintptr_t)15, e = (z + idat_len + 15) & ~(uint64_t)15;
+    return (uint32_t)((e - a + (1ull << kDecCrcRangeLog2) - 1) >> kDecCrcRangeLog2);
+}
+// raw CRC-32 partials of every file's IDAT payload, max_ranges words per file (depends on nothing but the files' bytes and the job records)
+void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t max_ranges, const CrcDeviceTables *tabs, uint32_t *partials);
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false,
-                       const int64_t *plane_pitch = nullptr);
+                       const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

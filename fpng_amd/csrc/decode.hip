@@ -33,6 +33,7 @@
 //                       the segments above through a decoupled look-back; channel count conversion
 //   dec_stored_kernel   files that are stored blocks (reference fpng.cpp:2107-2207): a strided copy
 #include "decode.h"
+#include "crc_device.h"
 #include "decode_core.h"
 
 #include <hip/hip_runtime.h>
@@ -1075,15 +1076,34 @@ template <int I> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v)
 template <bool kLayout>
 __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask)
 {
-    constexpr bool kPlanar = false;
+    constexpr bool kPlanar = false, kVerify = false;
     constexpr const int64_t *plane_pitch = nullptr;
+    constexpr unsigned long long *adler_acc = nullptr;
 #include "dec_unfilter_body.inc"
 }
 // the planar jobs of fpng_amd_decode_batch_planar; plane_pitch: a word per file of `jobs` (DecJob has no room for it)
 __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_planar_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask,
                                                                                                                 const int64_t *plane_pitch)
 {
-    constexpr bool kLayout = false, kPlanar = true;
+    constexpr bool kLayout = false, kPlanar = true, kVerify = false;
+    constexpr unsigned long long *adler_acc = nullptr;
+#include "dec_unfilter_body.inc"
+}
+// The verify forms (fpng_amd_encoder_set_decode_verify with FPNG_AMD_VERIFY_ADLER32): the same body, which then also adds every tile's
+// share of the filtered stream's Adler sums to adler_acc (two words per file of `jobs`).  Kernels of their own, so that the three
+// above keep their instructions.
+template <bool kLayout>
+__global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_verify_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask,
+                                                                                                                unsigned long long *adler_acc)
+{
+    constexpr bool kPlanar = false, kVerify = true;
+    constexpr const int64_t *plane_pitch = nullptr;
+#include "dec_unfilter_body.inc"
+}
+__global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_planar_verify_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch,
+                                                                                                                       uint32_t skip_mask, const int64_t *plane_pitch, unsigned long long *adler_acc)
+{
+    constexpr bool kLayout = false, kPlanar = true, kVerify = true;
 #include "dec_unfilter_body.inc"
 }
 
@@ -1193,6 +1213,100 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_planar_kernel(const DecJ
         }
     }
     if (odd) atomicOr(&status[blockIdx.y], kDecStoredOdd);
+}
+
+// ---- the optional check of a file's checksums (fpng_amd_encoder_set_decode_verify) ----
+// The Adler sums of a STORED file: the stream is the stored blocks' payloads in order, and a block's payload is contiguous -- a
+// workgroup per block of 65535 bytes (grid: blocks x files), a thread a dword at a time, the sums as in dec_unfilter_verify_kernel
+// (here the filter bytes are part of what is read).  The layout is the usual one or the file's status says otherwise
+// (kDecStoredOdd, or the host's check_stored()): every byte read lies inside the IDAT payload.
+__global__ __launch_bounds__(kDecBlock) void dec_stored_adler_kernel(const DecJob *jobs, unsigned long long *adler_acc)
+{
+    __shared__ uint32_t red[kDecBlock / kWave];
+    const DecJob &job = jobs[blockIdx.y];
+    if (job.mode != 1) return;
+    const uint64_t total = ((uint64_t)job.bpl + 1) * job.h, first = (uint64_t)blockIdx.x * 65535u;
+    if (first >= total) return;
+    const uint32_t len = (uint32_t)min((uint64_t)65535u, total - first);
+    const uint8_t *src = job.z + job.z_shift + 2 + 5 * ((uint64_t)blockIdx.x + 1) + first;
+    // weight of the last byte of this thread's first dword, mod 65521; a step of the loop is kDecBlock dwords further
+    uint32_t w3 = (uint32_t)((total - first - 4u * threadIdx.x + kAdlerMod - 3u) % kAdlerMod);
+    constexpr uint32_t step = (4u * kDecBlock) % kAdlerMod;
+    uint64_t s1 = 0, s2 = 0;
+    for (uint32_t o = 4u * threadIdx.x; o < len; o += 4u * kDecBlock) {
+        const uint32_t nb = min(4u, len - o); // (a dword that ends behind the block reads the next block's header or the Adler-32: inside the payload)
+        const uint32_t v = load_u32_unaligned(src + o) & (nb == 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1u), bs = __builtin_amdgcn_sad_u8(v, 0u, 0u);
+        s1 += bs;
+        s2 += w3 * bs + 3u * (v & 0xFFu) + 2u * ((v >> 8) & 0xFFu) + ((v >> 16) & 0xFFu);
+        w3 = w3 >= step ? w3 - step : w3 + kAdlerMod - step;
+    }
+    const uint32_t b1 = block_sum<kDecBlock / kWave>((uint32_t)s1, red), b2 = block_sum<kDecBlock / kWave>((uint32_t)(s2 % kAdlerMod), red);
+    if (threadIdx.x == 0) {
+        atomicAdd(&adler_acc[2 * (size_t)blockIdx.y], (unsigned long long)b1);
+        atomicAdd(&adler_acc[2 * (size_t)blockIdx.y + 1], (unsigned long long)b2);
+    }
+}
+
+// Raw CRC-32 partials of the files' IDAT payloads, grid (range, file): the encoder's crc_kernel over bytes that lie at any address.
+// The ranges hang off the payload's end rounded up to 16 bytes -- in ADDRESS space, so that every lane's load is an aligned 16
+// bytes (one that shares its 16 bytes with the payload cannot leave the allocation the payload lies in).
+__global__ __launch_bounds__(kDecBlock) void dec_crc_kernel(const DecJob *jobs, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t max_ranges)
+{
+    __shared__ uint32_t tab[16][256];
+    __shared__ uint32_t red[kDecBlock / kWave];
+    const DecJob &job = jobs[blockIdx.y];
+    const uintptr_t z = (uintptr_t)job.z + job.z_shift, base = z & ~(uintptr_t)15;
+    const int64_t data_begin = (int64_t)(z - base), data_end = data_begin + (int64_t)(job.z_bytes - job.z_shift);
+    const int64_t range_end = ((data_end + 15) & ~15ll) - ((int64_t)blockIdx.x << kDecCrcRangeLog2);
+    if (range_end <= 0) return; // nothing of the payload in this range
+    for (int i = threadIdx.x; i < 16 * 256; i += kDecBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
+    __syncthreads();
+    const uint32_t c = crc_range_partial((crc_gptr_cu8)base, data_begin, data_end, range_end, 1u << kDecCrcRangeLog2, tab, tabs, red);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * max_ranges + blockIdx.x] = c;
+}
+
+__device__ __forceinline__ uint32_t load_be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+// One workgroup per file, behind everything else of the chain: the CRC partials folded (the encoder's fold) and held against the
+// four bytes behind the payload; the Adler sums reduced, the filter bytes' share added, and held against the four bytes behind
+// the byte that holds the last bit of the end-of-block symbol (stored files: behind the last block).  A file whose status says
+// anything but "decoded" is left alone: its sums may be incomplete, and its status stands whatever the checksums say.
+__global__ __launch_bounds__(kDecBlock) void dec_verify_kernel(const DecJob *jobs, DecPlaced placed, uint32_t *status, DecVerify v)
+{
+    __shared__ uint32_t red[kDecBlock / kWave + 1];
+    const DecJob &job = jobs[blockIdx.x];
+    const uint32_t st = status[blockIdx.x];
+    if (job.mode == 0 ? st != kDecSawEob : st != 0u) return;
+    const uint8_t *z = job.z + job.z_shift;
+    const uint64_t len = job.z_bytes - job.z_shift;
+    uint32_t bad = 0;
+    if (v.flags & 1u) {
+        const uintptr_t za = (uintptr_t)z;
+        const uint32_t pad = (uint32_t)((16u - ((za + len) & 15u)) & 15u);
+        const uint32_t n_ranges = dec_crc_ranges(za, len);
+        uint32_t len_pow = 0;
+        const uint32_t raw = crc_fold_partials(v.tabs, v.crc_partials + (size_t)blockIdx.x * v.max_ranges, n_ranges, kDecCrcRangeLog2, len, pad, red, &len_pow);
+        if (threadIdx.x == 0) {
+            uint32_t s = 0xFFFFFFFFu; // the running state (init ~0) behind the chunk's type, advanced over the payload
+            s = dev_crc_byte(s, 'I'), s = dev_crc_byte(s, 'D'), s = dev_crc_byte(s, 'A'), s = dev_crc_byte(s, 'T');
+            s = dev_mulmod(s, len_pow) ^ raw;
+            if (~s != load_be32(z + len)) bad |= kDecBadCrc;
+        }
+    }
+    if ((v.flags & 2u) && threadIdx.x == 0) {
+        const uint64_t stride = (uint64_t)job.bpl + 1, total = stride * job.h;
+        uint64_t s1 = v.adler_acc[2 * (size_t)blockIdx.x] % kAdlerMod, s2 = v.adler_acc[2 * (size_t)blockIdx.x + 1] % kAdlerMod, pos;
+        if (job.mode == 0) {
+            // the filter bytes: 0 for row 0, 2 for every other row y, at weight total - y * stride: together stride * h * (h - 1)
+            s1 += 2ull * (job.h - 1);
+            s2 += (stride % kAdlerMod) * ((uint64_t)job.h * (job.h - 1) % kAdlerMod);
+            const uint32_t sub = placed.eob_index[blockIdx.x];
+            pos = (job.first_bit + (uint64_t)sub * kSubBits + placed.a.eob[job.sub_base + sub] + 7) >> 3; // (bits count from job.z)
+        } else
+            pos = job.z_shift + 2 + 5 * ((total + 65534) / 65535) + total;
+        const uint32_t adler = (uint32_t)((total % kAdlerMod + s2) % kAdlerMod) << 16 | (uint32_t)((1 + s1) % kAdlerMod);
+        if (pos + 4 > job.z_bytes || adler != load_be32(job.z + pos)) bad |= kDecBadAdler;
+    }
+    if (bad) atomicOr(&status[blockIdx.x], bad);
 }
 
 // ---- the kernels' lookup table (decode_core.h) from a file's 288 literal / length code lengths, one workgroup per table: what
@@ -1324,8 +1438,17 @@ void launch_dec_offsets_range(hipStream_t s, const DecJob *jobs, uint32_t sub_ba
 // jobs / status: of the group's first file; plan: device arrays (decode_api.cpp); epoch: this launch's (a new one every time; the
 // granules are never cleared)
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout, const int64_t *plane_pitch)
+                         bool layout, const int64_t *plane_pitch, unsigned long long *adler_acc)
 {
+    if (n_items && adler_acc) { // the verify forms
+        if (plane_pitch)
+            hipLaunchKernelGGL(dec_unfilter_planar_verify_kernel, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch, concurrent_status ? 0u : kDecUnfSkipMask, plane_pitch,
+                               adler_acc);
+        else
+            hipLaunchKernelGGL(layout ? dec_unfilter_verify_kernel<true> : dec_unfilter_verify_kernel<false>, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch,
+                               concurrent_status ? 0u : kDecUnfSkipMask, adler_acc);
+        return;
+    }
     if (n_items && plane_pitch)
         hipLaunchKernelGGL(dec_unfilter_planar_kernel, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch, concurrent_status ? 0u : kDecUnfSkipMask, plane_pitch);
     else if (n_items)
@@ -1356,17 +1479,37 @@ void dec_dump_tile_times(const char *path, uint32_t n_items)
     }
 }
 #endif
-void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout,
-                       const int64_t *plane_pitch)
+// (the grid is max_ranges x files, max_ranges being the batch's largest file's: a smaller file's surplus workgroups read its job record
+//  and leave, and so do all of a file whose status already says it failed -- nothing for batches of like files, some 0.04 ms for one 8K
+//  file among 255 small ones (2026 x 256 workgroups: profiles/decode_verify_timing.txt); dec_stored_adler_kernel's grid is cut the same way)
+void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t max_ranges, const CrcDeviceTables *tabs, uint32_t *partials)
 {
-    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch);
-    if (!any_stored) return; // (a workgroup that finds its file is not a stored one leaves at once, but n_jobs x 512 of them is not free)
-    for (uint32_t j0 = 0; j0 < n_jobs; j0 += 32768) { // (the y dimension of a grid holds at most 65535 workgroups)
+    for (uint32_t j0 = 0; j0 < n_jobs; j0 += 32768) // (the y dimension of a grid holds at most 65535 workgroups)
+        hipLaunchKernelGGL(dec_crc_kernel, dim3(max_ranges, std::min(32768u, n_jobs - j0)), dim3(kDecBlock), 0, s, jobs + j0, tabs, partials + (size_t)j0 * max_ranges, max_ranges);
+}
+void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout,
+                       const int64_t *plane_pitch, const DecVerify *verify)
+{
+    unsigned long long *const acc = verify && (verify->flags & 2u) ? verify->adler_acc : nullptr;
+    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch, acc);
+    // (a workgroup that finds its file is not a stored one leaves at once, but n_jobs x 512 of them is not free)
+    for (uint32_t j0 = 0; any_stored && j0 < n_jobs; j0 += 32768) { // (the y dimension of a grid holds at most 65535 workgroups)
         const dim3 grid(512, std::min(32768u, n_jobs - j0));
         if (plane_pitch)
             hipLaunchKernelGGL(dec_stored_planar_kernel, grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0, plane_pitch + j0);
         else
             hipLaunchKernelGGL(layout ? dec_stored_kernel<true> : dec_stored_kernel<false>, grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0);
+    }
+    if (!verify) return;
+    for (uint32_t j0 = 0; j0 < n_jobs; j0 += 32768) {
+        const uint32_t nj = std::min(32768u, n_jobs - j0);
+        // (stored files: at most 65536 blocks of 65535 bytes -- a file has less than 4 GiB of filtered bytes)
+        if (any_stored && acc) hipLaunchKernelGGL(dec_stored_adler_kernel, dim3(verify->stored_blocks, nj), dim3(kDecBlock), 0, s, jobs + j0, acc + 2 * (size_t)j0);
+        DecVerify v = *verify;
+        v.adler_acc = acc ? acc + 2 * (size_t)j0 : nullptr, v.crc_partials = v.crc_partials ? v.crc_partials + (size_t)j0 * v.max_ranges : nullptr;
+        DecPlaced pl = placed;
+        pl.eob_index += j0;
+        hipLaunchKernelGGL(dec_verify_kernel, dim3(nj), dim3(kDecBlock), 0, s, jobs + j0, pl, status + j0, v);
     }
 }
 

@@ -216,6 +216,15 @@ int dec_result(uint32_t st)
     return ((st & (kDecBadStream | kDecTileBadStream | kDecBadFilter)) || !(st & kDecSawEob)) ? fpng::FPNG_DECODE_NOT_FPNG : 0; // (no kDecSawEob: the stream never ended)
 }
 
+// ... and what the optional check of the checksums adds (fpng_amd_encoder_set_decode_verify): only a file that would have returned
+// 0 can return FPNG_AMD_DECODE_BAD_CRC32 or _BAD_ADLER32, the CRC first
+int verify_result(int st, uint32_t device_status)
+{
+    if (st) return st;
+    return device_status & kDecBadCrc ? FPNG_AMD_DECODE_BAD_CRC32 : (device_status & kDecBadAdler ? FPNG_AMD_DECODE_BAD_ADLER32 : 0);
+}
+static_assert(sizeof(unsigned long long) == 8, "the Adler accumulators");
+
 // The job record of a parsed file; its pointers are the caller's to set
 DecJob make_job(const Parsed &p, uint32_t desired)
 {
@@ -325,6 +334,11 @@ struct Batch {
     LutKeys luts;
     size_t z_total = 0, win_total = 0, seg_total = 0;
     uint32_t sub_total = 0;
+    // the optional check of the checksums: FPNG_AMD_VERIFY_*, the most CRC ranges a file has and the most stored blocks, the files'
+    // Adler accumulators (two words each) and CRC partials (max_ranges words each) in the scratch
+    uint32_t verify = 0, max_ranges = 1, stored_blocks = 1;
+    unsigned long long *d_adler_acc = nullptr;
+    uint32_t *d_crc_part = nullptr;
     std::vector<uint8_t> whole; // a device-resident file the head and tail were not enough for
     DecArrays d;
     uint32_t *d_luts, *d_status, *d_changed, *d_eob, *d_multi;
@@ -433,6 +447,11 @@ int parse_files(Batch &b)
             j.segsum = (uint32_t *)(uintptr_t)b.seg_total;
             b.seg_total += (size_t)j.nseg * ((j.bpl + 3) / 4);
         }
+        if (b.verify) {
+            // (the streams of host-resident files start on 16-byte boundaries of the scratch)
+            b.max_ranges = std::max(b.max_ranges, dec_crc_ranges(b.device_data ? (uintptr_t)f.data + p.idat_ofs + 8 : 0, p.idat_len));
+            if (p.mode) b.stored_blocks = std::max(b.stored_blocks, (uint32_t)((((uint64_t)j.bpl + 1) * j.h + 65534) / 65535));
+        }
         if (b.device_data) {
             const uintptr_t zr = (uintptr_t)f.data + p.idat_ofs + 8;
             j.z = (const uint8_t *)(zr & ~(uintptr_t)3), j.z_shift = (uint32_t)(zr & 3);
@@ -457,9 +476,13 @@ int place_files(Batch &b)
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
                  o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+    // (nothing more than without the check unless it is asked for)
+    const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
     int rc;
     if ((rc = sc.place(e, b.d))) return rc;
     uint8_t *base = e->d_decode.p;
+    if (b.verify & FPNG_AMD_VERIFY_ADLER32) b.d_adler_acc = (unsigned long long *)(base + o_acc);
+    if (b.verify & FPNG_AMD_VERIFY_CRC32) b.d_crc_part = (uint32_t *)(base + o_part);
     b.d_luts = (uint32_t *)(base + o_luts), b.d_keys = base + o_keys, b.d_jobs = (DecJob *)(base + o_jobs), b.d_plan = base + o_plan, b.d_status = (uint32_t *)(base + o_status);
     b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
@@ -490,6 +513,9 @@ int place_files(Batch &b)
         DecJob &j = b.jobs[k];
         const Parsed &p = b.ps[b.job_file[k]];
         if (!b.device_data) j.z = b.d.z + (size_t)(uintptr_t)j.z;
+        // (parse_files sized the CRC partials of a host-resident file for a stream that starts on a 16-byte boundary; dec_verify_kernel
+        //  counts the ranges from the real address, and one more range than sized would be the next file's slot)
+        if (!b.device_data && (b.verify & FPNG_AMD_VERIFY_CRC32) && ((uintptr_t)j.z & 15)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "decode scratch: a file's stream is not 16-byte aligned");
         if (!j.mode) {
             j.win = b.d.win + (size_t)(uintptr_t)j.win;
             j.segsum = (uint32_t *)(b.d.seg + (size_t)(uintptr_t)j.segsum);
@@ -568,7 +594,9 @@ hipError_t upload_group(const Batch &b, const Group &g, hipStream_t st)
 {
     for (uint32_t k = g.j0; k < g.j1; k++) {
         const Parsed &p = b.ps[b.job_file[k]];
-        if (hipError_t err = hipMemcpyAsync((void *)b.jobs[k].z, (const uint8_t *)b.files[b.job_file[k]].data + p.idat_ofs + 8, p.idat_len, hipMemcpyHostToDevice, st)) return err;
+        // (with the CRC check the chunk's CRC word, the four bytes behind the payload, comes along: the container walk has seen that they are there)
+        const size_t len = (size_t)p.idat_len + (b.verify & FPNG_AMD_VERIFY_CRC32 ? 4 : 0);
+        if (hipError_t err = hipMemcpyAsync((void *)b.jobs[k].z, (const uint8_t *)b.files[b.job_file[k]].data + p.idat_ofs + 8, len, hipMemcpyHostToDevice, st)) return err;
     }
     return hipSuccess;
 }
@@ -589,8 +617,14 @@ int finish_group(Batch &b, uint32_t gi)
     // (all groups run on one stream: two un-filter kernels never run at once -- each one's workgroups wait for lower-numbered ones
     //  of their own launch, and two sets of waiting workgroups could keep each other's predecessors off the compute units)
     const DecPlaced placed = {b.d.sub, b.d.block_off, b.d_eob + g.j0, 0xFFFFFFFFu};
+    DecVerify verify = {b.verify, b.max_ranges, b.stored_blocks, 0, nullptr, nullptr, device_crc_tables(b.e->device)};
+    if (b.verify & FPNG_AMD_VERIFY_ADLER32) { // (zero every time: a group that needed more rounds comes here again)
+        verify.adler_acc = b.d_adler_acc + 2 * (size_t)g.j0;
+        HIP_TRY(hipMemsetAsync(verify.adler_acc, 0, (size_t)(g.j1 - g.j0) * 16, b.s));
+    }
+    if (b.verify & FPNG_AMD_VERIFY_CRC32) verify.crc_partials = b.d_crc_part + (size_t)g.j0 * b.max_ranges;
     launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr,
-                      b.planar ? b.d_plane_pitch + g.j0 : nullptr);
+                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr);
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -643,11 +677,33 @@ int enqueue_groups(Batch &b)
             HIP_TRY(hipStreamWaitEvent(b.s, e->dec_ev[gi], 0));
         }
         if (tracing()) fprintf(stderr, "[decode] +%.0f us: group %u (files %u..%u, %u workgroups) starts\n", b.since(), gi, g.j0, g.j1, g.blk1 - g.blk0);
+        // The CRC pass needs the group's bytes and job records and nothing else: on a lane's stream (the lanes are drained), so that it
+        // can run next to the synchronisation, which is bound by issue and latency while this streams through the files once.
+        hipStream_t s_crc = e->lane_stream[0] ? e->lane_stream[0] : b.s;
+        // (a failure between the launch and the main stream's wait for it must not return while the kernel may still read the
+        //  scratch, which the next call reuses)
+        struct CrcInFlight {
+            hipStream_t s = nullptr;
+            ~CrcInFlight() { if (s) (void)hipStreamSynchronize(s); }
+        } crc_in_flight;
+        if (b.verify & FPNG_AMD_VERIFY_CRC32) {
+            for (hipEvent_t *ev : {&e->dec_crc_ev[2 * gi], &e->dec_crc_ev[2 * gi + 1]})
+                if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+            if (s_crc != b.s) {
+                HIP_TRY(hipEventRecord(e->dec_crc_ev[2 * gi], b.s));
+                HIP_TRY(hipStreamWaitEvent(s_crc, e->dec_crc_ev[2 * gi], 0));
+            }
+            launch_dec_crc(s_crc, b.d_jobs + g.j0, g.j1 - g.j0, b.max_ranges, device_crc_tables(e->device), b.d_crc_part + (size_t)g.j0 * b.max_ranges);
+            if (s_crc != b.s) crc_in_flight.s = s_crc;
+            if (s_crc != b.s) HIP_TRY(hipEventRecord(e->dec_crc_ev[2 * gi + 1], s_crc));
+        }
         HIP_TRY(stamp(b, gi, 0));
         // round 0 settles every workgroup in itself; the borders between workgroups get kBorderRounds rounds launched blind (a
         // workgroup whose border holds leaves at once), and the chain check of dec_offsets_kernel says whether that was enough
         for (uint32_t r = 0; g.blk1 > g.blk0 && r <= std::min(kBorderRounds, b.max_rounds - 1); r++)
             launch_dec_sync(b.s, b.resident, b.d_jobs, b.nj(), g.blk0, g.blk1 - g.blk0, b.sub_total, r, b.d.sub, b.d.recs, b.d_changed + gi, b.d_multi + gi);
+        if ((b.verify & FPNG_AMD_VERIFY_CRC32) && s_crc != b.s) HIP_TRY(hipStreamWaitEvent(b.s, e->dec_crc_ev[2 * gi + 1], 0));
+        crc_in_flight.s = nullptr; // (from here on the main stream is behind it)
         if (int rc = finish_group(b, gi)) return rc;
         if (tracing()) fprintf(stderr, "[decode] +%.0f us: group %u enqueued\n", b.since(), gi);
     }
@@ -708,8 +764,9 @@ int collect_results(Batch &b)
         if (tracing())
             fprintf(stderr, "[decode] file %u: %ux%ux%u mode %u, %u subsequences, first bit %llu, device status 0x%x\n", b.job_file[k], j.w, j.h, j.src_c, j.mode, j.n_sub, (unsigned long long)j.first_bit, status);
         int32_t &st = b.results[b.job_file[k]].status;
-        if (!j.mode) st = dec_result(status);
-        else if (status & kDecStoredOdd) { // not the usual stored layout after all: the whole file, on the host (check_stored() is the rule)
+        if (!j.mode) st = verify_result(dec_result(status), status);
+        else if (!(status & kDecStoredOdd)) st = verify_result(0, status);
+        else { // not the usual stored layout after all: the whole file, on the host (check_stored() is the rule)
             st = FPNG_AMD_DECODE_UNDECIDED;
             if (b.device_data) {
                 const Parsed &p = b.ps[b.job_file[k]];
@@ -733,7 +790,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     int rc = drain(e);
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
-    b.planar = planar;
+    b.planar = planar, b.verify = e->dec_verify;
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
     if ((rc = parse_files(b)) || !b.nj()) return rc;
@@ -926,6 +983,16 @@ int decode_host_streamed(fpng_amd_encoder *e, const uint8_t *png, const Parsed &
 
 } // namespace
 
+extern "C" int fpng_amd_encoder_set_decode_verify(fpng_amd_encoder *e, uint32_t flags)
+{
+    if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
+    if (flags & ~(uint32_t)(FPNG_AMD_VERIFY_CRC32 | FPNG_AMD_VERIFY_ADLER32)) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown FPNG_AMD_VERIFY_* bits");
+    e->dec_verify = flags;
+    return FPNG_AMD_OK;
+}
+
+extern "C" uint32_t fpng_amd_encoder_decode_verify(const fpng_amd_encoder *e) { return e ? e->dec_verify : 0u; }
+
 extern "C" int fpng_amd_decode_last_phase_ms(fpng_amd_encoder *e, float ms[FPNG_AMD_NUM_DECODE_PHASES])
 {
     if (!e || !ms) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
@@ -1031,7 +1098,8 @@ extern "C" int fpng_amd_decode_host(fpng_amd_encoder *e, const void *png, uint32
         const char *v = getenv("FPNG_AMD_DECODE_STREAM");
         return !(v && v[0] == '0');
     }();
-    if (stream_ok && sp.mode == 0 && sp.idat_len >= (8u << 20) && getenv("FPNG_AMD_DECODE_MAX_ROUNDS") == nullptr) {
+    // (with the checksums' check on, the serial form below: fpng_amd_encoder_set_decode_verify in fpng_amd.h)
+    if (stream_ok && !e->dec_verify && sp.mode == 0 && sp.idat_len >= (8u << 20) && getenv("FPNG_AMD_DECODE_MAX_ROUNDS") == nullptr) {
         uint8_t *out = reserve(user, (size_t)need);
         if (!out) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "no room for the pixels");
         bool redo = false;

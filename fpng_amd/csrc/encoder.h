@@ -184,6 +184,8 @@ struct fpng_amd_encoder {
     DeviceBuf<uint8_t> d_decode;  // fpng_amd_decode_batch(): all of its device scratch
     DeviceBuf<unsigned long long> d_dec_gran; // ... the look-back granules of dec_unfilter_kernel: zeroed when allocated, then told apart by epochs
     uint32_t dec_epoch = 0;
+    uint32_t dec_verify = 0; // fpng_amd_encoder_set_decode_verify: FPNG_AMD_VERIFY_* of every later decode call
+    hipEvent_t dec_crc_ev[8] = {}; // ... a group's bytes are there / its CRC partials are (dec_crc_kernel is launched on a lane's stream so that it can run next to the synchronisation)
     // the decoder's lookup tables of the last batch that had at most kDecLutCache distinct ones (1-pass files: always the same two):
     // a batch whose tables are all here neither uploads code lengths nor builds tables (dec_build_lut_kernel: 34 us in front of everything)
     static constexpr uint32_t kDecLutCache = 4;
@@ -207,6 +209,8 @@ struct fpng_amd_encoder {
 namespace fpng_amd {
 // Host-side wait for every submission in flight on the lanes.
 int drain(fpng_amd_encoder *e);
+// api.cpp: the device's CRC constants (there once an encoder was made on it, else NULL)
+const CrcDeviceTables *device_crc_tables(int device);
 // stops and joins the encoder's copy threads (no-op when there are none)
 void destroy_host_workers(fpng_amd_encoder *e);
 // has this host range been copied one direction at a time before (or page-locked through fpng_amd_pin_host_memory)?

@@ -79,8 +79,9 @@ struct StoredBlocks {
     }
 };
 
+// adler (here and in inflate_rows; may be null): the running Adler-32 of the filtered bytes, row by row (FPNG_AMD_DECODE_VERIFY)
 bool inflate_stored(const uint8_t *z, uint32_t avail, uint32_t zlib_len, uint8_t *dst, uint32_t w, uint32_t h, uint32_t src_chans,
-                    uint32_t dst_chans)
+                    uint32_t dst_chans, uint32_t *adler, size_t *adler_pos)
 {
     const size_t src_bpl = (size_t)w * src_chans, dst_bpl = (size_t)w * dst_chans;
     StoredBlocks in = {z, 2, avail};
@@ -91,8 +92,10 @@ bool inflate_stored(const uint8_t *z, uint32_t avail, uint32_t zlib_len, uint8_t
         uint8_t *o = dst + (size_t)y * dst_bpl;
         if (src_chans == dst_chans) {
             if (in.read(o, src_bpl) != src_bpl) return false;
+            if (adler) *adler = fpng_amd_adler32(o, src_bpl, fpng_amd_adler32(&f, 1, *adler));
         } else {
             if (in.read(tmp.data(), src_bpl) != src_bpl) return false;
+            if (adler) *adler = fpng_amd_adler32(tmp.data(), src_bpl, fpng_amd_adler32(&f, 1, *adler));
             const uint8_t *t = tmp.data();
             if (dst_chans == 4)
                 for (uint32_t x = 0; x < w; x++, t += 3, o += 4) { // (one 32-bit load -- the row buffer has the slack --, one store)
@@ -109,6 +112,8 @@ bool inflate_stored(const uint8_t *z, uint32_t avail, uint32_t zlib_len, uint8_t
     const size_t more = in.read(extra, 2); // (walks through whatever blocks follow, empty ones included, up to the final one)
     if (in.bad || !in.final_seen || in.left) return false;
     if (more > 1 || (more == 1 && extra[0] != 0)) return false;
+    if (adler && more) *adler = fpng_amd_adler32(extra, 1, *adler); // (the one zero byte the reference lets pass is part of the stream)
+    *adler_pos = (size_t)in.src;
     return in.src + 4 == zlib_len;
 }
 
@@ -226,7 +231,7 @@ template <int SC, int DC> void unfilter_row(const uint8_t *f, const uint8_t *up,
 }
 
 // SC channels in the file, DC channels out
-template <int SC, int DC> bool inflate_rows(const FastBits &in_, const uint32_t *rt, uint8_t *dst, uint32_t w, uint32_t h, size_t *end_bit)
+template <int SC, int DC> bool inflate_rows(const FastBits &in_, const uint32_t *rt, uint8_t *dst, uint32_t w, uint32_t h, size_t *end_bit, uint32_t *adler)
 {
     FastBits in = in_; // (a local copy: its fields live in registers, byte stores into the row buffer cannot alias them)
     const size_t bpl = (size_t)w * SC, stride = bpl + 1, dst_bpl = (size_t)w * DC;
@@ -312,6 +317,7 @@ template <int SC, int DC> bool inflate_rows(const FastBits &in_, const uint32_t 
         const size_t over = fill - stride;        // literals of the next row (at most two)
         if (over && y + 1 == h) return false;
         nb[0] = rb[stride], nb[1] = rb[stride + 1];
+        if (adler) *adler = fpng_amd_adler32(rb, stride, *adler); // (the row as Deflate sees it: filter byte, filtered bytes)
         // ---- Up filter undone (row 0: filter 0 = the bytes themselves; `up` is a row of zeros there), channels converted ----
         // (a flat row as fpng's encoders write it: the first pixel as literals -- no match stands there --, the rest runs of zero deltas)
         uint32_t first_px;
@@ -334,12 +340,23 @@ template <int SC, int DC> bool inflate_rows(const FastBits &in_, const uint32_t 
     return true;
 }
 
+// adler_ok (may be null: no check): is the big-endian word in the four bytes behind the byte that holds the stream's last bit -- stored
+// files: behind the last block -- the Adler-32 of the filtered bytes?  (Only meaningful when the function returns true.)
 bool inflate_pixels(const uint8_t *z, uint32_t avail, uint32_t zlib_len, uint8_t *dst, uint32_t w, uint32_t h, uint32_t src_chans,
-                    uint32_t dst_chans)
+                    uint32_t dst_chans, bool *adler_ok)
 {
     if (zlib_len < 7) return false;
     if (z[0] != 0x78 || z[1] != 0x01) return false;
-    if ((z[2] & 6) == 0) return inflate_stored(z, avail, zlib_len, dst, w, h, src_chans, dst_chans);
+    uint32_t adler_sum = 1, *const adler = adler_ok ? &adler_sum : nullptr;
+    auto check_adler = [&](size_t pos) {
+        if (adler_ok) *adler_ok = pos + 4 <= zlib_len && pos + 4 <= avail && be32(z + pos) == adler_sum;
+    };
+    if ((z[2] & 6) == 0) {
+        size_t pos = 0;
+        if (!inflate_stored(z, avail, zlib_len, dst, w, h, src_chans, dst_chans, adler, &pos)) return false;
+        check_adler(pos);
+        return true;
+    }
     Bits in = {z, avail, 2, 0, 0, false};
     if (in.get(1) != 1 || in.get(2) != 2) return false; // one final dynamic block
     // (one heap block for both tables: thread-local arrays cost a __tls_get_addr call at every use in a shared library, and the
@@ -352,11 +369,13 @@ bool inflate_pixels(const uint8_t *z, uint32_t avail, uint32_t zlib_len, uint8_t
     size_t end_bit = 0;
     bool ok;
     if (src_chans == 3)
-        ok = dst_chans == 3 ? inflate_rows<3, 3>(fb, row_table, dst, w, h, &end_bit) : inflate_rows<3, 4>(fb, row_table, dst, w, h, &end_bit);
+        ok = dst_chans == 3 ? inflate_rows<3, 3>(fb, row_table, dst, w, h, &end_bit, adler) : inflate_rows<3, 4>(fb, row_table, dst, w, h, &end_bit, adler);
     else
-        ok = dst_chans == 3 ? inflate_rows<4, 3>(fb, row_table, dst, w, h, &end_bit) : inflate_rows<4, 4>(fb, row_table, dst, w, h, &end_bit);
+        ok = dst_chans == 3 ? inflate_rows<4, 3>(fb, row_table, dst, w, h, &end_bit, adler) : inflate_rows<4, 4>(fb, row_table, dst, w, h, &end_bit, adler);
     if (!ok) return false;
-    return ((end_bit + 7) >> 3) + 4 == zlib_len;
+    if (((end_bit + 7) >> 3) + 4 != zlib_len) return false;
+    check_adler((end_bit + 7) >> 3);
+    return true;
 }
 
 } // namespace
@@ -403,8 +422,16 @@ int fpng_decode_memory(const void *pImage, uint32_t image_size, std::vector<uint
         const char *v = getenv("FPNG_AMD_DECODE_CPU");
         return v && v[0] == '1';
     }();
+    // FPNG_AMD_DECODE_VERIFY=1|2|3 (FPNG_AMD_VERIFY_* of fpng_amd.h; read once): both tiers also check the IDAT chunk's CRC-32 and / or the
+    // zlib stream's Adler-32 and return FPNG_DECODE_BAD_CRC32 / FPNG_DECODE_BAD_ADLER32 for a file that would have decoded otherwise
+    static const uint32_t verify = [] {
+        const char *v = getenv("FPNG_AMD_DECODE_VERIFY");
+        return v ? (uint32_t)atoi(v) & (FPNG_AMD_VERIFY_CRC32 | FPNG_AMD_VERIFY_ADLER32) : 0u;
+    }();
     if (!cpu_only && (uint64_t)width * height >= kGpuDecodeMinPixels) {
-        if (fpng_amd_encoder *enc = dropin_thread_encoder()) {
+        fpng_amd_encoder *enc = dropin_thread_encoder();
+        if (enc && fpng_amd_encoder_decode_verify(enc) != verify && fpng_amd_encoder_set_decode_verify(enc, verify) != FPNG_AMD_OK) enc = nullptr;
+        if (enc) {
             fpng_amd_decode_result r;
             const int rc = fpng_amd_decode_host(enc, pImage, image_size, desired_channels,
                                                 [](void *user, size_t bytes) -> uint8_t * {
@@ -424,9 +451,13 @@ int fpng_decode_memory(const void *pImage, uint32_t image_size, std::vector<uint
     const uint8_t *z = png + idat_ofs + 8;
     const uint32_t avail = image_size - (idat_ofs + 8);
     // a 4-channel file whose alpha deltas are dropped still needs them for the run logic: handled inside
-    if (!inflate_pixels(z, avail, idat_len, out.data(), width, height, channels_in_file, desired_channels)) {
+    bool adler_ok = true;
+    if (!inflate_pixels(z, avail, idat_len, out.data(), width, height, channels_in_file, desired_channels, verify & FPNG_AMD_VERIFY_ADLER32 ? &adler_ok : nullptr)) {
         return FPNG_DECODE_NOT_FPNG; // (`out` keeps the image's size, its contents are whatever was decoded so far: src/fpng.cpp:3131-3136)
     }
+    // (only a file that decodes can fail a checksum, the chunk's CRC first; the container walk has seen that its four bytes are there)
+    if ((verify & FPNG_AMD_VERIFY_CRC32) && fpng_amd_crc32(png + idat_ofs + 4, 4 + (size_t)idat_len, 0) != be32(png + idat_ofs + 8 + idat_len)) return FPNG_DECODE_BAD_CRC32;
+    if (!adler_ok) return FPNG_DECODE_BAD_ADLER32;
     return FPNG_DECODE_SUCCESS;
 }
 

@@ -27,6 +27,7 @@
 //
 // Integer / byte work throughout, bounded by VALU issue and HBM traffic: no MFMA.
 #include "kernels.h"
+#include "crc_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -40,6 +41,7 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = kWave * kWavesPerBlock;
+static_assert(kBlock == kCrcBlock, "crc_device.h: the CRC workgroups' size");
 // Rows (waves) per block of encode_rows_kernel.  Every block re-reads the row above its first row (another block's row,
 // rarely still in L2), so bigger blocks mean less traffic -- but coarser scheduling costs more: measured on one box,
 // 8 x 8K RGBA / 256 x 1080p RGB / 1024 x 512^2: 16 rows 480 / 465 / - GP/s, 8 rows 517 / 482 / 314, 4 rows 537 / 522 / 323,
@@ -125,13 +127,6 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v)
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_sum(v), 63);
-}
-
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v ^= __shfl_xor(v, o, 64);
-    return v;
 }
 
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -1445,17 +1440,6 @@ __global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdg
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t crc_range_log2(const JobState &st) { return st.range_log2 ? st.range_log2 : 16u; }
 
-__device__ __forceinline__ uint32_t dev_mulmod(uint32_t a, uint32_t b)
-{
-    uint32_t r = 0;
-#pragma unroll 8
-    for (int i = 31; i >= 0; i--) {
-        r ^= b & (0u - ((a >> i) & 1u));
-        b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1u)));
-    }
-    return r;
-}
-
 __global__ __launch_bounds__(kBlock) void crc_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs,
                                                     uint32_t *partials, uint32_t max_crc_blocks)
 {
@@ -1472,66 +1456,13 @@ __global__ __launch_bounds__(kBlock) void crc_kernel(const Job *jobs, const JobS
     for (int i = threadIdx.x; i < 16 * 256; i += kBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
     __syncthreads();
     gptr_cu8 base = to_global<gptr_cu8>(job.out);
-    const uint32_t tid = threadIdx.x;
-    uint32_t c = 0;
-    for (uint32_t row = 0; row < range_bytes / kCrcRowBytes; row++) {
-        const int64_t o = range_end - range_bytes + (int64_t)row * kCrcRowBytes + tid * 16;
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (o + 16 > data_begin && o < data_end) {
-            const u32x4 d = *(gptr_cu128)(base + o);
-            w[0] = d.x, w[1] = d.y, w[2] = d.z, w[3] = d.w;
-            if (o < data_begin || o + 16 > data_end) { // zero the bytes outside [data_begin, data_end)
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    uint32_t m = 0;
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const int64_t pos = o + 4 * k + b;
-                        if (pos >= data_begin && pos < data_end) m |= 0xFFu << (8 * b);
-                    }
-                    w[k] &= m;
-                }
-            }
-        }
-        w[0] ^= c;
-        uint32_t n = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            n ^= tab[4 * k + 0][w[k] & 0xFF] ^ tab[4 * k + 1][(w[k] >> 8) & 0xFF] ^ tab[4 * k + 2][(w[k] >> 16) & 0xFF] ^
-                 tab[4 * k + 3][w[k] >> 24];
-        c = n;
-    }
-    // lane stripes now sit at range_end + 16*tid: move them all to range_end + one block row, fold
-    c = wave_xor(dev_mulmod(c, tabs->lane_fix[tid]));
-    if ((tid & 63) == 0) red[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) partials[(size_t)blockIdx.y * max_crc_blocks + blockIdx.x] = red[0] ^ red[1] ^ red[2] ^ red[3];
+    const uint32_t c = crc_range_partial(base, data_begin, data_end, range_end, range_bytes, tab, tabs, red);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * max_crc_blocks + blockIdx.x] = c;
 }
 
 // ---------------------------------------------------------------------------------------------
 // finalize_kernel: one block per job
 // ---------------------------------------------------------------------------------------------
-// four independent products, interleaved (the single product is a chain of 32 dependent steps)
-__device__ __forceinline__ void dev_mulmod4(const uint32_t (&a)[4], const uint32_t (&b_in)[4], uint32_t (&r)[4])
-{
-    uint32_t b[4] = {b_in[0], b_in[1], b_in[2], b_in[3]};
-    r[0] = r[1] = r[2] = r[3] = 0;
-#pragma unroll 4
-    for (int i = 31; i >= 0; i--) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            r[k] ^= b[k] & (0u - ((a[k] >> i) & 1u));
-            b[k] = (b[k] >> 1) ^ (0xEDB88320u & (0u - (b[k] & 1u)));
-        }
-    }
-}
-__device__ __forceinline__ uint32_t dev_crc_byte(uint32_t c, uint32_t byte)
-{
-    c ^= byte;
-    for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-    return c;
-}
-
 __device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t *red64)
 {
     const uint32_t t = threadIdx.x;
@@ -1579,58 +1510,17 @@ __device__ __forceinline__ void finalize_job(const Job &job, const RowInfo *rows
 
     // ---- fold the CRC partials.  Partial j sits (j ranges + one block row) before the common end
     //      point, so  T = XOR_j p_j * X^j  with X = x^(8*64Ki); all needed constants are x^(8*2^i). ----
-    uint32_t g = 0; // each thread folds G = 2^g consecutive partials
-    while (((uint64_t)kBlock << g) < n_ranges) g++;
-    const uint32_t G = 1u << g;
-    // (the constants of the later steps are asked for now: their loads travel together with those of the partials instead of
-    // one round trip each behind the fold)
-    const uint32_t group_pow = tabs->fold[rl + g - 12][t];
-    const uint32_t len_pow = (t < 6) ? tabs->pow_byte[t][((zlib_size - 4) >> (8 * t)) & 0xFF] : 0x80000000u; // 0x80000000 = 1
-    const uint32_t unpad = tabs->inv_row_pad[(uint32_t)(end_aligned - data_end)];
-    uint32_t v = 0;
-    {
-        // partial i of the group times x^(8*range*i): independent multiplications, four at a time (a Horner chain would
-        // be G dependent ones: G = 32 for a 16384^2 image)
-        const uint32_t *xp = tabs->fold[rl - 12];
-        for (uint32_t i = 0; i < G; i += 4) {
-            uint32_t a[4], b[4], r[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) {
-                const uint32_t j = t * G + i + k;
-                a[k] = (i + k < G && j < n_ranges) ? pj[j] : 0u;
-                b[k] = xp[(i + k) & 255u];
-            }
-            dev_mulmod4(a, b, r);
-            v ^= r[0] ^ r[1] ^ r[2] ^ r[3];
-        }
-    }
-    // the thread's group starts t * G ranges before the common end point: one multiplication by a tabulated power, then
-    // the groups simply XOR together (no multiplications inside the reduction)
-    if (v && t) v = dev_mulmod(v, group_pow);
-    v = wave_xor(v);
-    // x^(8*(zlib_size-4)): six tabulated factors (one per byte of the length), multiplied as a tree by lanes 0..7 of wave 0
-    uint32_t f = len_pow;
-    if (t < 64) {
-#pragma unroll
-        for (int o = 4; o > 0; o >>= 1) {
-            const uint32_t other = (uint32_t)__shfl_down((int)f, o, 8);
-            f = dev_mulmod(f, other);
-        }
-    }
-    if ((t & 63) == 0) red[t >> 6] = v;
-    if (t == 0) red[kWavesPerBlock] = f;
-    __syncthreads();
-    const uint32_t folded = red[0] ^ red[1] ^ red[2] ^ red[3];
+    uint32_t len_pow = 0;
+    const uint32_t raw_data = crc_fold_partials(tabs, pj, n_ranges, rl, zlib_size - 4, (uint32_t)(end_aligned - data_end), red, &len_pow);
     if (t == 0) {
         gptr_u8 out = to_global<gptr_u8>(job.out);
-        const uint32_t raw_data = dev_mulmod(folded, unpad);
         // running CRC state (init ~0) after "IDAT", advanced over the data, then the 4 Adler bytes
         uint32_t s = 0xFFFFFFFFu;
         s = dev_crc_byte(s, 'I');
         s = dev_crc_byte(s, 'D');
         s = dev_crc_byte(s, 'A');
         s = dev_crc_byte(s, 'T');
-        s = dev_mulmod(s, red[kWavesPerBlock]) ^ raw_data;
+        s = dev_mulmod(s, len_pow) ^ raw_data;
         gptr_u8 tail = out + kPngHeaderBytes + zlib_size - 4;
         store_be32(tail, adler); // reference fpng.cpp:1569-1577 / :851-863
         s = dev_crc_byte(s, adler >> 24);

@@ -14,6 +14,8 @@
 //   * fpng_decode_memory() leaves `out` with the reference's size() on every exit (empty after a container-level failure, width *
 //     height * desired_channels after success or a failure inside the stream: src/fpng.cpp:3087-3136), but a vector reused from call
 //     to call is not zero-filled again (the reference resizes it to 0 and back on every call);
+//   * with FPNG_AMD_DECODE_VERIFY=1|2|3 in the environment (off by default) the decode functions also check the IDAT chunk's CRC-32 and / or
+//     the zlib stream's Adler-32 and can return FPNG_DECODE_BAD_CRC32 / FPNG_DECODE_BAD_ADLER32 (below);
 //   * FPNG_DISABLE_DECODE_CRC32_CHECKS (src/fpng.cpp:50-53) is honoured when the libraries are built with it
 //     (python -m fpng_amd.build --variant nocrc -> libfpng_nocrc.so + libfpng_amd_nocrc.so).
 #pragma once
@@ -66,7 +68,13 @@ enum {
     FPNG_DECODE_FILE_OPEN_FAILED,
     FPNG_DECODE_FILE_TOO_LARGE,
     FPNG_DECODE_FILE_READ_FAILED,
-    FPNG_DECODE_FILE_SEEK_FAILED
+    FPNG_DECODE_FILE_SEEK_FAILED,
+    // Extensions beyond the reference's enum, returned only with FPNG_AMD_DECODE_VERIFY=1|2|3 in the environment (bit 0: the IDAT chunk's
+    // CRC-32, bit 1: the zlib stream's Adler-32; read once per process; unset or 0: neither is checked, as in the reference).  A file
+    // that would have decoded with FPNG_DECODE_SUCCESS returns one of these when the checksum it carries is not the one of its bytes
+    // (both wrong: the CRC's); `out` then has the image's size and undefined contents.  Every other status is what it is without the check.
+    FPNG_DECODE_BAD_CRC32 = 65,  // = FPNG_AMD_DECODE_BAD_CRC32
+    FPNG_DECODE_BAD_ADLER32 = 66 // = FPNG_AMD_DECODE_BAD_ADLER32
 };
 
 int fpng_get_info(const void *pImage, uint32_t image_size, uint32_t &width, uint32_t &height, uint32_t &channels_in_file);

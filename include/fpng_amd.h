@@ -536,6 +536,44 @@ int fpng_amd_decode_batch_device_planar(fpng_amd_encoder *enc, const fpng_amd_pn
  * result->status as in fpng_amd_decode_batch(): FPNG_AMD_DECODE_UNDECIDED = decode it on the CPU. */
 int fpng_amd_decode_host(fpng_amd_encoder *enc, const void *png, uint32_t size, uint32_t desired_chans, fpng_amd_reserve_fn reserve,
                          void *user, fpng_amd_decode_result *result);
+/* ---- checking a file's checksums while it is decoded (opt-in; the reference's decoder checks neither, and by default neither is
+ *      checked here: a changed literal of a compressed file, or any changed pixel byte of a stored one, decodes with status 0).
+ *      The setting is sticky per encoder, like fpng_amd_encoder_set_profiling, and applies to every later call of
+ *      fpng_amd_decode_batch, fpng_amd_decode_batch_device, their _ex and _planar forms and fpng_amd_decode_host on that encoder.
+ *      flags: 0 (the default: every status, pixel and kernel as without this section) or FPNG_AMD_VERIFY_* bits; any other bit:
+ *      FPNG_AMD_ERR_INVALID_ARG, and nothing changes.  Rules:
+ *      - Status order: a file whose status without the check is anything but 0 keeps that status -- every FPNG_DECODE_* failure
+ *        code and FPNG_AMD_DECODE_UNDECIDED included.  Only a file that would have returned 0 can return
+ *        FPNG_AMD_DECODE_BAD_CRC32 or FPNG_AMD_DECODE_BAD_ADLER32; when both checks are on and both fail: BAD_CRC32.
+ *      - Expected CRC-32: the four bytes behind the IDAT payload, held against the CRC-32 of the chunk's four type bytes and
+ *        the payload.
+ *      - Expected Adler-32 (zlib's definition): the big-endian word in the four bytes behind the byte that holds the last bit of
+ *        the end-of-block symbol -- stored files: behind the last stored block --, held against the Adler-32 of the
+ *        (w * channels_in_file + 1) * h filtered bytes the stream decodes to.  Fewer than four payload bytes there:
+ *        BAD_ADLER32.  Payload bytes behind those four are ignored, as they are without the check.
+ *      - Pixel memory: undefined when the status is BAD_CRC32 or BAD_ADLER32, as for any status but 0; the promises about bytes
+ *        that are never touched (pitch padding, the space between planes) hold.
+ *      - Device-resident files: nothing more of a file visits the host than without the check (its first 1024 and last 64
+ *        bytes); the expected words are read and compared on the device.
+ *      - Cost: the CRC-32 is one more read of the files' bytes by a kernel that runs on a second stream next to the
+ *        synchronisation; the Adler-32 is summed inside the pass that writes the pixels, from the filtered bytes it
+ *        holds anyway (stored files: one more read).  fpng_amd_decode_host decodes large files in its serial form while a
+ *        check is on (upload, decode and download one after the other instead of overlapped).
+ *        Measured on an MI355X (profiles/decode_verify_timing.txt), added to a call without the check: 8 x 8K RGBA compressed
+ *        (1.54 ms) CRC-32 +0.16 ms, Adler-32 +0.57 ms, both +0.73 ms; 8 x 8K stored (0.62 ms) +0.26 / +0.47 / +0.73 ms;
+ *        64 x 1080p RGB (0.79 ms) +0.07 / +0.04 / +0.10 ms; 256 x 512 x 512 (0.56 ms) +0.04 / +0.02 / +0.06 ms.  The CRC kernel does
+ *        overlap the synchronisation, which runs that much longer next to it; the Adler-32 alone costs about what one re-read of
+ *        the pixels would, both together more.  The host's own CRC-32 over one 8K file takes 2.9 ms.
+ *        fpng_amd_decode_host on one 8K RGBA file (Python caller, medians): serial form with both checks 14.7 ms, serial form
+ *        without a check 14.9 ms, streamed form without a check 17.8 ms -- the serial form cost nothing there, and the check's
+ *        own cost (under 0.1 ms of kernels for one file) is below that call's spread of +-0.5 ms.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encoder_set_decode_verify with dlsym. ---- */
+#define FPNG_AMD_VERIFY_CRC32 1u   /* the IDAT chunk's CRC-32 (over "IDAT" + payload) */
+#define FPNG_AMD_VERIFY_ADLER32 2u /* the zlib stream's Adler-32 (over the filtered bytes the stream stands for) */
+int fpng_amd_encoder_set_decode_verify(fpng_amd_encoder *enc, uint32_t flags);
+uint32_t fpng_amd_encoder_decode_verify(const fpng_amd_encoder *enc);
+#define FPNG_AMD_DECODE_BAD_CRC32 65
+#define FPNG_AMD_DECODE_BAD_ADLER32 66
 /* What fpng_amd_decode_batch() settles on the HOST about one file before the GPU sees it (no GPU needed; tests/ run the decode
  * kernels' per-thread code on the CPU against it): result (container status, geometry; status 0 = the stream's shape is acceptable so
  * far), mode (0 = one dynamic block, 1 = stored blocks), the IDAT chunk's offset and payload length, the first row token's bit and

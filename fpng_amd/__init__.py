@@ -25,4 +25,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   png_head, png_tail, pin_host_memory, unpin_host_memory, release_cached_memory, runtime_info,
                   SRC_FORMATS, format_channels, source_layout, dest_layout, dest_bytes, DecodeBatchEx,
                   source_layout_planar, dest_layout_planar, DecodeBatchPlanar,
+                  FLOAT_DTYPES, normalize_constants, dest_layout_float, DecodeBatchFloat,
                   VERIFY_CRC32, VERIFY_ADLER32, DECODE_BAD_CRC32, DECODE_BAD_ADLER32)

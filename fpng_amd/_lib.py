@@ -65,6 +65,13 @@ class PngPlanarIn(C.Structure):  # fpng_amd_png_planar: 48 bytes, no padding
                 ("plane_pitch", C.c_int64), ("pixels_cap", C.c_size_t)]
 
 
+class FloatFormat(C.Structure):  # fpng_amd_float_format: 40 bytes
+    _fields_ = [("dtype", C.c_uint32), ("reserved", C.c_uint32), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+F32, F16, BF16 = 0, 1, 2  # FPNG_AMD_F32 / _F16 / _BF16
+
+
 class DecodeResult(C.Structure):
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels_in_file", C.c_uint32), ("status", C.c_int32)]
 
@@ -155,6 +162,8 @@ SIGNATURES = {
     "fpng_amd_decode_batch_device_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_planar": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_planar": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_planar_float": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_float": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),
     "fpng_amd_encoder_decode_verify": (_u32, [_vp]),
     "fpng_amd_decode_last_phase_ms": (_int, [_vp, C.POINTER(C.c_float * 4)]),

@@ -123,10 +123,12 @@ def dest_layout(t, order="rgb", bottom_up=False):
     return ptr, rp, SRC_FORMATS[order.upper()][0]
 
 
-def _planar_layout(t, order, bottom_up, who):
-    """(d_pixels, row_pitch, plane_pitch) of a uint8 (c, h, w) tensor view: one plane of w-byte rows per channel"""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
-        raise ValueError(f"{who}: a uint8 tensor shaped (c, h, w)")
+def _planar_layout(t, order, bottom_up, who, elem=None):
+    """(d_pixels, row_pitch, plane_pitch) of a uint8 (c, h, w) tensor view: one plane of w-byte rows per channel.  elem: the view
+    holds elements of that many bytes instead (dest_layout_float, which has checked the dtype): the same rules on its strides,
+    which count elements, and the pitches returned in bytes"""
+    if not isinstance(t, torch.Tensor) or (elem is None and t.dtype != torch.uint8) or t.dim() != 3:
+        raise ValueError(f"{who}: a " + ("uint8" if elem is None else "float") + " tensor shaped (c, h, w)")
     c, h, w = t.shape
     if c not in (3, 4) or h < 1 or w < 1:
         raise ValueError(f"{who}: {c} planes (3 or 4), {w} x {h}")
@@ -147,6 +149,8 @@ def _planar_layout(t, order, bottom_up, who):
     if order not in (("rgb", "bgr") if c == 3 else ("rgba", "abgr")):
         raise ValueError(f"{who}: order {order!r} for {c} planes -- one base and one plane pitch can say "
                          + ("'rgb' or 'bgr'" if c == 3 else "'rgba' or 'abgr'") + " only")
+    if elem is not None:
+        rp, pp = rp * elem, pp * elem
     ptr = t.data_ptr()
     if order[0] != "r":  # the planes lie in reverse: start at the last one and walk back
         ptr, pp = ptr + (c - 1) * pp, -pp
@@ -172,6 +176,36 @@ def dest_layout_planar(t, order="rgb", bottom_up=False):
     decode_batch_planar, fpng_amd_png_planar): the destination twin of source_layout_planar(), same rules.  c = 4 planes of a
     3-channel file: the A plane is filled with 0xFF; c = 3 of a 4-channel file: alpha is dropped."""
     return _planar_layout(t, order, bottom_up, "dest_layout_planar")
+
+
+# torch dtype of a float destination -> FPNG_AMD_F32 / _F16 / _BF16 (fpng_amd_float_format::dtype)
+FLOAT_DTYPES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+
+
+def normalize_constants(mean, std, max_value=255.0):
+    """(scale[4], bias[4]) as float32 arrays for the float decode calls: an element is fmaf(byte, scale[c], bias[c]), and with
+    scale[c] = 1 / (max_value * std[c]), bias[c] = -mean[c] / std[c] that is (byte / max_value - mean[c]) / std[c] -- torchvision's
+    ToTensor() + Normalize(mean, std).  Computed in float64, rounded once; channels that mean / std do not name (alpha, usually)
+    get 1 / max_value and 0: plain [0, 1] values."""
+    mean, std = np.atleast_1d(np.asarray(mean, dtype=np.float64)), np.atleast_1d(np.asarray(std, dtype=np.float64))
+    if mean.ndim != 1 or mean.shape != std.shape or mean.size > 4:
+        raise ValueError("normalize_constants: mean and std are sequences of the same length, at most 4")
+    if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std)) and np.all(std != 0) and np.isfinite(max_value) and max_value != 0):
+        raise ValueError("normalize_constants: finite mean, finite non-zero std and max_value")
+    scale, bias = np.full(4, 1.0 / float(max_value)), np.zeros(4)
+    scale[: mean.size], bias[: mean.size] = 1.0 / (float(max_value) * std), -mean / std
+    return scale.astype(np.float32), bias.astype(np.float32)
+
+
+def dest_layout_float(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, plane_pitch, dtype code) of a float32 / float16 / bfloat16 (c, h, w) tensor VIEW that a float decode
+    fills in place (Encoder.decode_device_float / decode_batch_float): dest_layout_planar()'s rules on strides counted in
+    ELEMENTS -- contiguous CHW, nchw[i], chw4[:3], crops, padded rows, order "bgr" / "abgr", bottom_up -- and its refusals, plus
+    any other dtype; the pitches come back in BYTES, as fpng_amd_png_planar takes them."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in FLOAT_DTYPES:
+        raise ValueError("dest_layout_float: a float32, float16 or bfloat16 tensor shaped (c, h, w)")
+    ptr, rp, pp = _planar_layout(t, order, bottom_up, "dest_layout_float", elem=t.element_size())
+    return ptr, rp, pp, FLOAT_DTYPES[t.dtype]
 
 
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
@@ -398,6 +432,16 @@ class DecodeBatchEx(_DecodeBatchViews):
 class DecodeBatchPlanar(_DecodeBatchViews):
     """What Encoder.make_decode_batch_planar() returns: the same for one fpng_amd_decode_batch(_device)_planar() call (outs: the
     caller's (c, h, w) views).  Not a DecodeBatchEx: neither call takes the other's descriptor."""
+
+
+class DecodeBatchFloat(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_float() returns: the same for one fpng_amd_decode_batch(_device)_planar_float() call (outs: the
+    caller's float (c, h, w) views, all of one dtype; fmt: the call's fpng_amd_float_format).  Neither a DecodeBatchPlanar nor a
+    DecodeBatchEx: no call takes another's descriptor."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.fmt = fmt
 
 
 class Encoder:
@@ -695,8 +739,8 @@ class Encoder:
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
-        if isinstance(pngs, DecodeBatchPlanar):
-            raise ValueError("decode_device_ex: a planar descriptor (decode_device_planar)")
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat)):
+            raise ValueError("decode_device_ex: a planar or float descriptor (decode_device_planar, decode_device_float)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if not batch.device_data:
             raise ValueError("decode_device_ex: the files are in host memory (decode_batch_ex)")
@@ -707,8 +751,8 @@ class Encoder:
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
-        if isinstance(pngs, DecodeBatchPlanar):
-            raise ValueError("decode_batch_ex: a planar descriptor (decode_batch_planar)")
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat)):
+            raise ValueError("decode_batch_ex: a planar or float descriptor (decode_batch_planar, decode_batch_float)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if batch.device_data:
             raise ValueError("decode_batch_ex: the files are in device memory (decode_device_ex)")
@@ -749,6 +793,8 @@ class Encoder:
     def _decode_planar(self, who, fn, device_data, pngs, outs, order, bottom_up, results):
         if isinstance(pngs, DecodeBatchEx):
             raise ValueError(f"{who}: a make_decode_batch_ex() descriptor (decode_device_ex / decode_batch_ex)")
+        if isinstance(pngs, DecodeBatchFloat):
+            raise ValueError(f"{who}: a make_decode_batch_float() descriptor (decode_device_float / decode_batch_float)")
         batch = pngs if isinstance(pngs, DecodeBatchPlanar) else self.make_decode_batch_planar(pngs, outs, order, bottom_up)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_planar)" if device_data else "device memory (decode_device_planar)"))
@@ -768,6 +814,79 @@ class Encoder:
     def decode_batch_planar(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_planar: decode_device_planar() for files in host memory (bytes)."""
         return self._decode_planar("decode_batch_planar", self.lib.fpng_amd_decode_batch_planar, False, pngs, outs, order, bottom_up, results)
+
+    @staticmethod
+    def make_decode_batch_float(pngs, outs, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+        """Descriptor (fpng_amd_png_planar[n], the fpng_amd_float_format and the result records) for decode_device_float() /
+        decode_batch_float(): the files as for make_decode_batch_planar(), and float32 / float16 / bfloat16 (c, h, w) tensor VIEWS --
+        all of ONE dtype -- described by dest_layout_float(view, order, bottom_up).  An element of plane c is
+        fmaf(byte, scale[c], bias[c]) of the FILE's channel c (R, G, B, A, whatever the planes' order in memory), rounded to the
+        dtype: give mean and std (normalize_constants(): (byte / 255 - mean) / std), or scale and bias (up to four values each,
+        padded with 1 / 255 and 0), or neither for plain [0, 1] values.  pixels_cap is the view's own span in bytes."""
+        if (mean is None) != (std is None) or (mean is not None and (scale is not None or bias is not None)):
+            raise ValueError("make_decode_batch_float: mean and std together, or scale and / or bias, or neither")
+        if mean is not None:
+            sc, bi = normalize_constants(mean, std)
+        else:
+            sc, bi = normalize_constants([], [])
+            for dst, src, what in ((sc, scale, "scale"), (bi, bias, "bias")):
+                if src is not None:
+                    v = np.atleast_1d(np.asarray(src, dtype=np.float32))
+                    if v.ndim != 1 or not 1 <= v.size <= 4:
+                        raise ValueError(f"make_decode_batch_float: {what} has 1 to 4 values")
+                    dst[: v.size] = v
+        if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(bi))):
+            raise ValueError("make_decode_batch_float: scale and bias must be finite")
+        n = len(pngs)
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"make_decode_batch_float: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        arr = (_lib.PngPlanarIn * n)()
+        res = (_lib.DecodeResult * n)()
+        fmt = _lib.FloatFormat()
+        keep = []
+        for i, (p, t) in enumerate(zip(pngs, outs)):
+            ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError("make_decode_batch_float: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            c, h, w = t.shape
+            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
+            arr[i].pixels_cap = (c - 1) * abs(pp) + (h - 1) * abs(rp) + w * t.element_size()  # (the view's own spans, in bytes)
+        for k in range(4):
+            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt)
+
+    def _decode_float(self, who, fn, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar)):
+            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_float() makes this one's)")
+        batch = pngs if isinstance(pngs, DecodeBatchFloat) else self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_float)" if device_data else "device memory (decode_device_float)"))
+        if not all(t.is_cuda for t in batch.outs):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, len(batch.arr), C.byref(batch.fmt), batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_float(self, pngs, outs=None, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_device_planar_float: uint8 CUDA tensors holding whole files, decoded into the caller's float (c, h, w)
+        device tensor views `outs` in place as normalised values (make_decode_batch_float() has the rules) -> list of (status, the
+        caller's view or None, channels_in_file) -- without the x.to(dtype).sub(mean).div(std) pass behind decode_device_planar().
+        pngs may be a make_decode_batch_float() descriptor of device files (outs = None); results=False returns the descriptor."""
+        return self._decode_float("decode_device_float", self.lib.fpng_amd_decode_batch_device_planar_float, True, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
+
+    def decode_batch_float(self, pngs, outs=None, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_planar_float: decode_device_float() for files in host memory (bytes)."""
+        return self._decode_float("decode_batch_float", self.lib.fpng_amd_decode_batch_planar_float, False, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

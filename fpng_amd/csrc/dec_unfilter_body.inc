@@ -7,6 +7,10 @@
 //   kVerify            constexpr bool: the tile also sums its filtered bytes for the file's Adler-32 (fpng_amd_encoder_set_decode_verify);
 //                      false in the three kernels that were there before, whose instructions it leaves alone
 //   adler_acc          unsigned long long *, two words per file of `jobs` (kVerify; else a null constant that is never read)
+//   kFloat             constexpr int: -1, or (kPlanar) the FPNG_AMD_F32 / F16 / BF16 of fpng_amd_decode_batch_planar_float -- the planes
+//                      hold elements of that type, fmaf(value, flt.scale[c], flt.bias[c]) of the file's channel c; -1 in the kernels
+//                      that were there before, whose instructions it leaves alone
+//   flt                DecFloat, a kernel argument: wave-uniform (kFloat >= 0; else an empty constant that is never read)
 // and the kernel's arguments jobs, plan, placed, item0, status, epoch, skip_mask.
     __shared__ __attribute__((aligned(16))) uint8_t tile_mem[kUnfRows * kTilePitch];
     __shared__ uint32_t mask_mem[kUnfRows * kRowMaskWords], epx_mem[kUnfRows]; // the rows' marked pixels (long matches), their entry pixels
@@ -222,10 +226,35 @@
             if (three) ch = lane >> 4, x = wave_px + 4u * (lane & 15u);
             else ch = lane & 3u, x = wave_px + (lane & ~3u);
             const uint32_t nb = (ch < dc && x < job.w) ? min(4u, job.w - x) : 0u;
-            gu8 *pb = (gu8 *)(uintptr_t)(job.out + (int64_t)ch * pp + (int64_t)y0 * job.pitch + (int64_t)x);
+            constexpr uint32_t kElem = kFloat < 0 ? 1u : dec_float_bytes((uint32_t)kFloat); // bytes of a plane's element (the pitches are bytes)
+            gu8 *pb = (gu8 *)(uintptr_t)(job.out + (int64_t)ch * pp + (int64_t)y0 * job.pitch + (int64_t)x * kElem);
+            // (kFloat: the lane's channel's two constants, picked once from the four pairs in scalar registers)
+            const float fs = kFloat < 0 ? 0.f : (ch == 0 ? flt.scale[0] : (ch == 1 ? flt.scale[1] : (ch == 2 ? flt.scale[2] : flt.scale[3])));
+            const float fb = kFloat < 0 ? 0.f : (ch == 0 ? flt.bias[0] : (ch == 1 ? flt.bias[1] : (ch == 2 ? flt.bias[2] : flt.bias[3])));
             auto put = [&](uint32_t k, uint32_t d) {
                 gu8 *q = pb + (int64_t)k * job.pitch;
-                if (nb == 4) *(gu32_any *)q = d;
+                if constexpr (kFloat >= 0) {
+                    // the dword's four bytes -> floats (v_cvt_f32_ubyte0 .. 3), ONE fused multiply-add each, then 16 (f32) or 8 bytes
+                    // per lane (f16, bf16: packed conversions, round to nearest even); elements only where the row ends inside them
+                    const float f0 = __builtin_fmaf((float)(d & 0xFFu), fs, fb), f1 = __builtin_fmaf((float)((d >> 8) & 0xFFu), fs, fb);
+                    const float f2 = __builtin_fmaf((float)((d >> 16) & 0xFFu), fs, fb), f3 = __builtin_fmaf((float)(d >> 24), fs, fb);
+                    if constexpr (kFloat == 0) {
+                        if (nb == 4) *(gf32x4_any *)q = f32x4{f0, f1, f2, f3};
+                        else if (nb) {
+                            *(gf32_any *)q = f0;
+                            if (nb > 1) *(gf32_any *)(q + 4) = f1;
+                            if (nb > 2) *(gf32_any *)(q + 8) = f2;
+                        }
+                    } else {
+                        const uint32_t lo = pack_half2<kFloat>(f0, f1), hi = pack_half2<kFloat>(f2, f3);
+                        if (nb == 4) *(gu32x2_any *)q = u32x2{lo, hi};
+                        else if (nb) {
+                            *(gu16_any *)q = (uint16_t)lo;
+                            if (nb > 1) *(gu16_any *)(q + 2) = (uint16_t)(lo >> 16);
+                            if (nb > 2) *(gu16_any *)(q + 4) = (uint16_t)hi;
+                        }
+                    }
+                } else if (nb == 4) *(gu32_any *)q = d;
                 else
                     for (uint32_t b = 0; b < nb; b++) q[b] = (uint8_t)(d >> (8 * b));
             };

@@ -157,8 +157,19 @@ struct DecPlaced {
 // between a plane's rows; the *_planar kernels write them
 // adler_acc (device, two 64-bit words per file of `jobs`, or NULL): the verify forms of the kernels run instead -- every tile adds its
 // filtered bytes' sum and position-weighted sum (mod 65521) to its file's two words (DecVerify)
+// flt (host, or NULL; needs plane_pitch): the jobs are fpng_amd_decode_batch_planar_float's -- the planes hold flt->dtype elements,
+// fmaf(value, scale[c], bias[c]) of the file's channel c; DecJob::pitch and plane_pitch stay bytes; the *_float kernels write them
+struct DecFloat { // (the words of fpng_amd_float_format)
+    uint32_t dtype, pad_; // FPNG_AMD_F32 / F16 / BF16
+    float scale[4], bias[4];
+};
+constexpr uint32_t kDecFloatTypes = 3;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr uint32_t dec_float_bytes(uint32_t dtype) { return dtype == 0 ? 4u : 2u; }
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout = false, const int64_t *plane_pitch = nullptr, unsigned long long *adler_acc = nullptr);
+                         bool layout = false, const int64_t *plane_pitch = nullptr, unsigned long long *adler_acc = nullptr, const DecFloat *flt = nullptr);
 // The optional check of the files' checksums (fpng_amd_encoder_set_decode_verify), per launch of launch_dec_finish: flags =
 // FPNG_AMD_VERIFY_*; adler_acc as above, zero when the launch begins; crc_partials: max_ranges words per file that launch_dec_crc
 // filled (FPNG_AMD_VERIFY_CRC32).  All pointers are the entries of the launch's first file.
@@ -191,7 +202,7 @@ inline uint32_t dec_crc_ranges(uintptr_t z, uint64_t idat_len)
 // raw CRC-32 partials of every file's IDAT payload, max_ranges words per file (depends on nothing but the files' bytes and the job records)
 void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t max_ranges, const CrcDeviceTables *tabs, uint32_t *partials);
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false,
-                       const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr);
+                       const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr, const DecFloat *flt = nullptr);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

@@ -1065,6 +1065,36 @@ __device__ __forceinline__ gu8 *scalar_base(const gu8 *p)
 __device__ __forceinline__ uint32_t gload_u32(const gu8 *base, uint32_t off) { return *(const gu32_any *)(scalar_base(base) + off); }
 __device__ __forceinline__ void gstore_u32(gu8 *base, uint32_t off, uint32_t v) { *(gu32_any *)(scalar_base(base) + off) = v; }
 __device__ __forceinline__ void gstore_u8(gu8 *base, uint32_t off, uint32_t v) { scalar_base(base)[off] = (uint8_t)v; }
+// (the float planes of fpng_amd_decode_batch_planar_float: 16- and 8-byte stores at any multiple of the element size, elements at a row's end)
+typedef float __attribute__((ext_vector_type(4))) f32x4;
+typedef uint32_t __attribute__((ext_vector_type(2))) u32x2;
+typedef float __attribute__((aligned(4))) f32_a;
+typedef f32x4 __attribute__((aligned(4))) f32x4_a;
+typedef u32x2 __attribute__((aligned(2))) u32x2_a;
+typedef uint16_t __attribute__((aligned(2))) u16_a;
+typedef __attribute__((address_space(1))) f32_a gf32_any;
+typedef __attribute__((address_space(1))) f32x4_a gf32x4_any;
+typedef __attribute__((address_space(1))) u32x2_a gu32x2_any;
+typedef __attribute__((address_space(1))) u16_a gu16_any;
+// float -> the bits of a 2-byte element, round to nearest even (kDtype: FPNG_AMD_F16 = 1, FPNG_AMD_BF16 = 2); a pair in a dword, the
+// first one low (v_cvt_pk_f16_f32, v_cvt_pk_bf16_f32)
+template <int kDtype> __device__ __forceinline__ uint16_t half_bits(float f)
+{
+    asm("" : "+v"(f)); // (the fp32 result as it is: no fused multiply-add that rounds straight to the narrow type)
+    if constexpr (kDtype == 1) return __builtin_bit_cast(uint16_t, (_Float16)f);
+    else return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+template <int kDtype> __device__ __forceinline__ uint32_t pack_half2(float a, float b)
+{
+    typedef float __attribute__((ext_vector_type(2))) f32x2;
+    if constexpr (kDtype == 1) {
+        typedef _Float16 __attribute__((ext_vector_type(2))) h2;
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, h2));
+    } else {
+        typedef __bf16 __attribute__((ext_vector_type(2))) b2;
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, b2));
+    }
+}
 // the dword of lane I of every quad of lanes, in all four (DPP quad_perm:[I,I,I,I])
 template <int I> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v)
 {
@@ -1079,6 +1109,8 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
     constexpr bool kPlanar = false, kVerify = false;
     constexpr const int64_t *plane_pitch = nullptr;
     constexpr unsigned long long *adler_acc = nullptr;
+    constexpr int kFloat = -1;
+    constexpr DecFloat flt = {};
 #include "dec_unfilter_body.inc"
 }
 // the planar jobs of fpng_amd_decode_batch_planar; plane_pitch: a word per file of `jobs` (DecJob has no room for it)
@@ -1087,6 +1119,8 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
 {
     constexpr bool kLayout = false, kPlanar = true, kVerify = false;
     constexpr unsigned long long *adler_acc = nullptr;
+    constexpr int kFloat = -1;
+    constexpr DecFloat flt = {};
 #include "dec_unfilter_body.inc"
 }
 // The verify forms (fpng_amd_encoder_set_decode_verify with FPNG_AMD_VERIFY_ADLER32): the same body, which then also adds every tile's
@@ -1098,12 +1132,27 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
 {
     constexpr bool kPlanar = false, kVerify = true;
     constexpr const int64_t *plane_pitch = nullptr;
+    constexpr int kFloat = -1;
+    constexpr DecFloat flt = {};
 #include "dec_unfilter_body.inc"
 }
 __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_planar_verify_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch,
                                                                                                                        uint32_t skip_mask, const int64_t *plane_pitch, unsigned long long *adler_acc)
 {
     constexpr bool kLayout = false, kPlanar = true, kVerify = true;
+    constexpr int kFloat = -1;
+    constexpr DecFloat flt = {};
+#include "dec_unfilter_body.inc"
+}
+// The float planes of fpng_amd_decode_batch_planar_float: the planar body once more, whose last stage converts the lane's four bytes
+// of one channel and stores elements of type kDtype (FPNG_AMD_F32 / F16 / BF16, a compile-time constant: the store loop has no
+// branch on it).  flt is a kernel argument, so the four scale / bias pairs sit in scalar registers.  adler_acc: kVerify only.
+template <int kDtype, bool kVerifyT>
+__global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_float_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask,
+                                                                                                               const int64_t *plane_pitch, unsigned long long *adler_acc, DecFloat flt)
+{
+    constexpr bool kLayout = false, kPlanar = true, kVerify = kVerifyT;
+    constexpr int kFloat = kDtype;
 #include "dec_unfilter_body.inc"
 }
 
@@ -1210,6 +1259,42 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_planar_kernel(const DecJ
         for (uint32_t x = t_x; x < w; x += lanes) {
             const uint64_t s = s0 + 1 + (uint64_t)x * sc;
             for (uint32_t b = 0; b < dc; b++) o[(int64_t)b * pp + x] = b < sc ? z[stored_pos(s + b)] : (uint8_t)0xFF;
+        }
+    }
+    if (odd) atomicOr(&status[blockIdx.y], kDecStoredOdd);
+}
+// ... and of fpng_amd_decode_batch_planar_float: the same, an element of type kDtype = fmaf(byte, scale, bias) into each plane
+template <int kDtype>
+__global__ __launch_bounds__(kDecBlock) void dec_stored_float_kernel(const DecJob *jobs, uint32_t *status, const int64_t *plane_pitch, DecFloat flt)
+{
+    const DecJob &job = jobs[blockIdx.y];
+    if (job.mode != 1) return;
+    const uint8_t *z = job.z + job.z_shift;
+    const uint32_t sc = job.src_c, dc = job.dst_c, bpl = job.bpl, w = job.w, h = job.h;
+    const int64_t pp = plane_pitch[blockIdx.y];
+    const uint64_t total = ((uint64_t)bpl + 1) * h;
+    const uint32_t nblk = (uint32_t)((total + 65534) / 65535);
+    bool odd = false;
+    for (uint32_t i = blockIdx.x * kDecBlock + threadIdx.x; i < nblk; i += gridDim.x * kDecBlock) {
+        const uint8_t *hd = z + 2 + (uint64_t)i * 65540;
+        const uint32_t len = i + 1 < nblk ? 65535u : (uint32_t)(total - (uint64_t)i * 65535);
+        odd |= hd[0] != (i + 1 == nblk ? 1 : 0) || (hd[1] | hd[2] << 8) != len || (hd[3] | hd[4] << 8) != (~len & 0xFFFFu);
+    }
+    uint32_t lanes = 1;
+    while (lanes < w && lanes < (uint32_t)kDecBlock) lanes <<= 1;
+    const uint32_t rows_per = kDecBlock / lanes, t_row = threadIdx.x / lanes, t_x = threadIdx.x & (lanes - 1);
+    for (uint32_t y = blockIdx.x * rows_per + t_row; y < h; y += gridDim.x * rows_per) {
+        const uint64_t s0 = (uint64_t)y * ((uint64_t)bpl + 1); // the row's filter byte
+        if (t_x == 0) odd |= z[stored_pos(s0)] != 0;
+        uint8_t *o = job.out + (int64_t)y * job.pitch;
+        for (uint32_t x = t_x; x < w; x += lanes) {
+            const uint64_t s = s0 + 1 + (uint64_t)x * sc;
+            for (uint32_t b = 0; b < dc; b++) {
+                const float f = __builtin_fmaf((float)(b < sc ? z[stored_pos(s + b)] : (uint8_t)0xFF), flt.scale[b], flt.bias[b]);
+                uint8_t *q = o + (int64_t)b * pp + (int64_t)x * dec_float_bytes((uint32_t)kDtype);
+                if constexpr (kDtype == 0) *(f32_a *)q = f;
+                else *(u16_a *)q = half_bits<kDtype>(f);
+            }
         }
     }
     if (odd) atomicOr(&status[blockIdx.y], kDecStoredOdd);
@@ -1438,8 +1523,18 @@ void launch_dec_offsets_range(hipStream_t s, const DecJob *jobs, uint32_t sub_ba
 // jobs / status: of the group's first file; plan: device arrays (decode_api.cpp); epoch: this launch's (a new one every time; the
 // granules are never cleared)
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout, const int64_t *plane_pitch, unsigned long long *adler_acc)
+                         bool layout, const int64_t *plane_pitch, unsigned long long *adler_acc, const DecFloat *flt)
 {
+    if (flt) { // the float planes: a kernel per element type, with and without the Adler sums
+        using Kernel = void (*)(const DecJob *, DecUnfPlan, DecPlaced, uint32_t, uint32_t *, uint32_t, uint32_t, const int64_t *, unsigned long long *, DecFloat);
+        static const Kernel kernels[kDecFloatTypes][2] = {{dec_unfilter_float_kernel<0, false>, dec_unfilter_float_kernel<0, true>},
+                                                          {dec_unfilter_float_kernel<1, false>, dec_unfilter_float_kernel<1, true>},
+                                                          {dec_unfilter_float_kernel<2, false>, dec_unfilter_float_kernel<2, true>}};
+        if (n_items)
+            hipLaunchKernelGGL(kernels[flt->dtype][adler_acc ? 1 : 0], dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch, concurrent_status ? 0u : kDecUnfSkipMask,
+                               plane_pitch, adler_acc, *flt);
+        return;
+    }
     if (n_items && adler_acc) { // the verify forms
         if (plane_pitch)
             hipLaunchKernelGGL(dec_unfilter_planar_verify_kernel, dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch, concurrent_status ? 0u : kDecUnfSkipMask, plane_pitch,
@@ -1488,14 +1583,18 @@ void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t
         hipLaunchKernelGGL(dec_crc_kernel, dim3(max_ranges, std::min(32768u, n_jobs - j0)), dim3(kDecBlock), 0, s, jobs + j0, tabs, partials + (size_t)j0 * max_ranges, max_ranges);
 }
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout,
-                       const int64_t *plane_pitch, const DecVerify *verify)
+                       const int64_t *plane_pitch, const DecVerify *verify, const DecFloat *flt)
 {
     unsigned long long *const acc = verify && (verify->flags & 2u) ? verify->adler_acc : nullptr;
-    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch, acc);
+    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch, acc, flt);
     // (a workgroup that finds its file is not a stored one leaves at once, but n_jobs x 512 of them is not free)
     for (uint32_t j0 = 0; any_stored && j0 < n_jobs; j0 += 32768) { // (the y dimension of a grid holds at most 65535 workgroups)
         const dim3 grid(512, std::min(32768u, n_jobs - j0));
-        if (plane_pitch)
+        if (flt) {
+            using Kernel = void (*)(const DecJob *, uint32_t *, const int64_t *, DecFloat);
+            static const Kernel kernels[kDecFloatTypes] = {dec_stored_float_kernel<0>, dec_stored_float_kernel<1>, dec_stored_float_kernel<2>};
+            hipLaunchKernelGGL(kernels[flt->dtype], grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0, plane_pitch + j0, *flt);
+        } else if (plane_pitch)
             hipLaunchKernelGGL(dec_stored_planar_kernel, grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0, plane_pitch + j0);
         else
             hipLaunchKernelGGL(layout ? dec_stored_kernel<true> : dec_stored_kernel<false>, grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0);

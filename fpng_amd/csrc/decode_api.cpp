@@ -12,6 +12,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <chrono>
 #include <condition_variable>
@@ -327,6 +328,8 @@ struct Batch {
     const fpng_amd_png_planar *planar = nullptr; // fpng_amd_decode_batch(_device)_planar: the same for planar destinations
     std::vector<int64_t> plane_pitch;            // (planar) a word per job, uploaded with the job records
     int64_t *d_plane_pitch = nullptr;
+    const DecFloat *flt = nullptr; // fpng_amd_decode_batch(_device)_planar_float: the planes' element type and constants (else NULL) ...
+    uint32_t elem = 1;             // ... and an element's bytes: a row of a plane is w * elem bytes
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     std::vector<Parsed> ps;
     std::vector<DecJob> jobs;                // (their pointers into the scratch are offsets until place_files())
@@ -411,17 +414,19 @@ int parse_files(Batch &b)
         int64_t pitch = 0, plane_pitch = 0;
         if (b.planar) {
             const fpng_amd_png_planar &x = b.planar[i];
-            pitch = x.row_pitch ? x.row_pitch : (int64_t)p.w;
+            const uint64_t roww = (uint64_t)p.w * b.elem; // bytes of a plane's row (float planes: w elements)
+            if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
+            pitch = x.row_pitch ? x.row_pitch : (int64_t)roww;
             const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
-            if (step < p.w) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w");
-            const uint64_t span = (uint64_t)(p.h - 1) * step + p.w; // a plane, from its lowest row's first byte
+            if (step < roww) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
+            const uint64_t span = (uint64_t)(p.h - 1) * step + roww; // a plane, from its lowest row's first byte
             plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)p.h * step);
             if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
             const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
-            if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w: the planes overlap");
+            if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
             if (pstep > (UINT64_MAX >> 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
             if (!f.d_pixels || f.pixels_cap < (uint64_t)(desired - 1) * pstep + span)
-                return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w");
+                return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w (* element bytes)");
         } else if (b.ex) {
             const uint64_t row = (uint64_t)p.w * desired;
             pitch = b.ex[i].row_pitch ? b.ex[i].row_pitch : (int64_t)row;
@@ -624,7 +629,7 @@ int finish_group(Batch &b, uint32_t gi)
     }
     if (b.verify & FPNG_AMD_VERIFY_CRC32) verify.crc_partials = b.d_crc_part + (size_t)g.j0 * b.max_ranges;
     launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr,
-                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr);
+                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.flt);
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -779,9 +784,10 @@ int collect_results(Batch &b)
     return FPNG_AMD_OK;
 }
 
-// ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used)
+// ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
+// planar files are fpng_amd_decode_batch(_device)_planar_float's
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
-                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr)
+                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -791,6 +797,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.verify = e->dec_verify;
+    if (flt) b.flt = flt, b.elem = dec_float_bytes(flt->dtype);
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
     if ((rc = parse_files(b)) || !b.nj()) return rc;
@@ -1035,19 +1042,47 @@ int decode_files_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t 
 namespace {
 static_assert(sizeof(fpng_amd_png_planar) == 48 && offsetof(fpng_amd_png_planar, d_pixels) == 16 && offsetof(fpng_amd_png_planar, pixels_cap) == 40, "fpng_amd_png_planar layout");
 // fpng_amd_decode_batch(_device)_planar: as decode_files_ex -- the rules that need no file here, the pitches' and the room's in parse_files
-int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data)
+// fmt: fpng_amd_decode_batch(_device)_planar_float's format (its planes hold elements of fmt->dtype, the pitches stay bytes), else NULL
+static_assert(sizeof(fpng_amd_float_format) == 40 && sizeof(DecFloat) == 40 && offsetof(DecFloat, scale) == offsetof(fpng_amd_float_format, scale) &&
+                  offsetof(DecFloat, bias) == offsetof(fpng_amd_float_format, bias), "fpng_amd_float_format layout");
+static_assert(FPNG_AMD_F32 == 0 && FPNG_AMD_F16 == 1 && FPNG_AMD_BF16 == 2 && kDecFloatTypes == 3, "the kernels' element types");
+int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    DecFloat flt = {};
+    uint32_t elem = 1;
+    if (fmt) {
+        if (fmt->dtype >= kDecFloatTypes) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown element type (FPNG_AMD_F32, _F16, _BF16)");
+        if (fmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_float_format::reserved must be 0");
+        for (int c = 0; c < 4; c++)
+            if (!std::isfinite(fmt->scale[c]) || !std::isfinite(fmt->bias[c])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
+        flt.dtype = fmt->dtype, elem = dec_float_bytes(fmt->dtype);
+        std::memcpy(flt.scale, fmt->scale, sizeof flt.scale), std::memcpy(flt.bias, fmt->bias, sizeof flt.bias);
+    }
     std::vector<fpng_amd_png> plain(n);
     for (uint32_t i = 0; i < n; i++) {
         const fpng_amd_png_planar &x = files[i];
         if (x.num_chans != 3 && x.num_chans != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "num_chans must be 3 or 4");
+        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (elem - 1))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
         plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr);
 }
 } // namespace
+
+extern "C" int fpng_amd_decode_batch_planar_float(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null format");
+    return decode_files_planar(e, files, n, results, false, fmt);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_float(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null format");
+    return decode_files_planar(e, files, n, results, true, fmt);
+}
 
 extern "C" int fpng_amd_decode_batch_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results)
 {

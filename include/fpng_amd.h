@@ -527,6 +527,31 @@ typedef struct fpng_amd_png_planar {
  * below the span above (a file the container walk rejects needs no room). */
 int fpng_amd_decode_batch_planar(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results);
 int fpng_amd_decode_batch_device_planar(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results);
+/* ---- decoding into planar images of NORMALISED FLOATS (f32, f16 or bf16): what a loader otherwise does with a second kernel,
+ *      x.to(dtype).sub(mean).div(std), inside the pass that writes the pixels.  For a file that decodes with status 0, plane c
+ *      holds the file's channel c (R, G, B[, A] = 0 .. 3, wherever the planes lie in memory); with v the byte that
+ *      fpng_decode_memory() gives at desired_channels = num_chans (255 for the A plane of a 3-channel file), an element is
+ *          round_to_dtype(fmaf((float)v, scale[c], bias[c]))
+ *      -- ONE fp32 fused multiply-add, round to nearest even; round_to_dtype: the identity for f32, round to nearest even for f16
+ *      and bf16 (f16 overflow and fp32 denormal results: the hardware's IEEE behaviour).  mean / std normalisation of v / 255 is
+ *      scale[c] = 1 / (255 * std[c]), bias[c] = -mean[c] / std[c].
+ *      The fpng_amd_png_planar records are used as they are: row_pitch, plane_pitch and pixels_cap stay BYTES, of the float
+ *      destination -- a row is w * (element bytes), 0 still means tight, negative pitches bottom-up rows and reversed planes.  Every
+ *      rule of fpng_amd_decode_batch_planar holds with w * (element bytes) in the place of w (|row_pitch| >= that, the planes' overlap,
+ *      the room, what is never written, the statuses, FPNG_AMD_DECODE_UNDECIDED, FPNG_AMD_DECODE_MAX_ROUNDS, the checksums' check);
+ *      in addition FPNG_AMD_ERR_INVALID_ARG, with nothing launched, for a dtype other than the three, reserved != 0, a scale or
+ *      bias that is not finite, and d_pixels, row_pitch or plane_pitch that is not a multiple of the element size.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_float with dlsym. ---- */
+enum { FPNG_AMD_F32 = 0, FPNG_AMD_F16 = 1, FPNG_AMD_BF16 = 2 };
+typedef struct fpng_amd_float_format {
+    uint32_t dtype;    /* FPNG_AMD_F32, _F16 or _BF16: the planes' element type, one per call */
+    uint32_t reserved; /* 0 */
+    float scale[4], bias[4]; /* per FILE channel R, G, B, A */
+} fpng_amd_float_format; /* 40 bytes */
+int fpng_amd_decode_batch_planar_float(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt,
+                                       fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_planar_float(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt,
+                                              fpng_amd_decode_result *results);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

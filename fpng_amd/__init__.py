@@ -26,4 +26,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   SRC_FORMATS, format_channels, source_layout, dest_layout, dest_bytes, DecodeBatchEx,
                   source_layout_planar, dest_layout_planar, DecodeBatchPlanar,
                   FLOAT_DTYPES, normalize_constants, dest_layout_float, DecodeBatchFloat,
+                  denormalize_constants, source_layout_float,
                   VERIFY_CRC32, VERIFY_ADLER32, DECODE_BAD_CRC32, DECODE_BAD_ADLER32)

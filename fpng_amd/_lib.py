@@ -125,6 +125,8 @@ SIGNATURES = {
     "fpng_amd_encode_submit": (_int, [_vp, C.POINTER(Image), _u32, _u32, C.POINTER(_u64)]),
     "fpng_amd_encode_submit_ex": (_int, [_vp, C.POINTER(ImageEx), _u32, _u32, C.POINTER(_u64)]),
     "fpng_amd_encode_submit_planar": (_int, [_vp, C.POINTER(ImagePlanar), _u32, _u32, C.POINTER(_u64)]),
+    "fpng_amd_encode_submit_planar_float": (_int, [_vp, C.POINTER(ImagePlanar), _u32, C.POINTER(FloatFormat), _u32, C.POINTER(_u64)]),
+    "fpng_amd_quantize_float": (_int, [_vp, _u32, C.c_float, C.c_float, _vp, _sz]),
     "fpng_amd_encode_wait": (_int, [_vp, _u64, C.POINTER(Result), _u32]),
     "fpng_amd_encode_query": (_int, [_vp, _u64]),
     "fpng_amd_encode_host": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(_sz)]),

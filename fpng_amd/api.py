@@ -208,6 +208,52 @@ def dest_layout_float(t, order="rgb", bottom_up=False):
     return ptr, rp, pp, FLOAT_DTYPES[t.dtype]
 
 
+def denormalize_constants(mean, std, max_value=255.0):
+    """(scale[4], bias[4]) as float32 arrays for the float encode calls, the inverse of normalize_constants(): a byte is
+    rint(fmaf(x, scale[c], bias[c])) clamped to [0, 255], and with scale[c] = max_value * std[c], bias[c] = max_value * mean[c] that
+    is (x * std[c] + mean[c]) * max_value -- what undoes torchvision's Normalize(mean, std) and ToTensor().  Computed in float64,
+    rounded once; channels that mean / std do not name (alpha, usually) get max_value and 0: plain [0, 1] values."""
+    mean, std = np.atleast_1d(np.asarray(mean, dtype=np.float64)), np.atleast_1d(np.asarray(std, dtype=np.float64))
+    if mean.ndim != 1 or mean.shape != std.shape or mean.size > 4:
+        raise ValueError("denormalize_constants: mean and std are sequences of the same length, at most 4")
+    if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std)) and np.all(std != 0) and np.isfinite(max_value) and max_value != 0):
+        raise ValueError("denormalize_constants: finite mean, finite non-zero std and max_value")
+    scale, bias = np.full(4, float(max_value)), np.zeros(4)
+    scale[: mean.size], bias[: mean.size] = float(max_value) * std, float(max_value) * mean
+    return scale.astype(np.float32), bias.astype(np.float32)
+
+
+def source_layout_float(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, plane_pitch, dtype code) of a float32 / float16 / bfloat16 (c, h, w) tensor VIEW for
+    Encoder.submit_float (fpng_amd_encode_submit_planar_float): source_layout_planar()'s rules on strides counted in ELEMENTS --
+    contiguous CHW, nchw[i], chw4[:3], crops, padded rows, order "bgr" / "abgr", bottom_up -- and its refusals, plus any other
+    dtype; the pitches come back in BYTES, as fpng_amd_image_planar takes them.  The device is not touched: CPU tensors work too."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in FLOAT_DTYPES:
+        raise ValueError("source_layout_float: a float32, float16 or bfloat16 tensor shaped (c, h, w)")
+    ptr, rp, pp = _planar_layout(t, order, bottom_up, "source_layout_float", elem=t.element_size())
+    return ptr, rp, pp, FLOAT_DTYPES[t.dtype]
+
+
+def _float_constants(who, make, mean, std, scale, bias):
+    """scale[4], bias[4] of a float call from its mean / std or scale / bias arguments; make: normalize_constants or
+    denormalize_constants, whose values for no channels named are the defaults"""
+    if (mean is None) != (std is None) or (mean is not None and (scale is not None or bias is not None)):
+        raise ValueError(f"{who}: mean and std together, or scale and / or bias, or neither")
+    if mean is not None:
+        sc, bi = make(mean, std)
+    else:
+        sc, bi = make([], [])
+        for dst, src, what in ((sc, scale, "scale"), (bi, bias, "bias")):
+            if src is not None:
+                v = np.atleast_1d(np.asarray(src, dtype=np.float32))
+                if v.ndim != 1 or not 1 <= v.size <= 4:
+                    raise ValueError(f"{who}: {what} has 1 to 4 values")
+                dst[: v.size] = v
+    if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(bi))):
+        raise ValueError(f"{who}: scale and bias must be finite")
+    return sc, bi
+
+
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
 
 
@@ -590,6 +636,52 @@ class Encoder:
             del self._keep[old]
         return n
 
+    @staticmethod
+    def make_batch_float(images, outs, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+        """Descriptor (images, outs, fpng_amd_image_planar[n], fpng_amd_float_format) for submit_float(): float32 / float16 /
+        bfloat16 tensor VIEWS shaped (c, h, w) -- all of ONE dtype -- encoded where they lie, described by
+        source_layout_float(view, order, bottom_up) (order / bottom_up: one value, or one per image).  A byte of the file's channel c
+        (R, G, B, A, whatever the planes' order in memory) is rint(fmaf(x, scale[c], bias[c])) clamped to [0, 255], NaN giving 0: give
+        mean and std (denormalize_constants(): (x * std + mean) * 255), or scale and bias (up to four values each, padded with 255
+        and 0), or neither for plain [0, 1] values.  list(nchw_batch) is a valid `images`."""
+        sc, bi = _float_constants("make_batch_float", denormalize_constants, mean, std, scale, bias)
+        n = len(images)
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        dtypes = {t.dtype for t in images if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"make_batch_float: the images of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        arr = (ImagePlanar * n)()
+        fmt = _lib.FloatFormat()
+        for i, (im, out) in enumerate(zip(images, outs)):
+            ptr, rp, pp, fmt.dtype = source_layout_float(im, orders[i], ups[i])
+            arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = ptr, rp, pp
+            arr[i].num_chans, arr[i].h, arr[i].w = im.shape
+            arr[i].reserved = 0
+            arr[i].d_out = out.data_ptr()
+            arr[i].out_cap = out.numel()
+        for k in range(4):
+            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        return (images, outs, arr, fmt)
+
+    def submit_float(self, images, outs=None, flags=0, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+        """submit_planar() for float (c, h, w) images (fpng_amd_encode_submit_planar_float): images = CUDA tensor views as for
+        make_batch_float() with outs, or a make_batch_float() descriptor and outs = None.  The files are the ones submit_planar()
+        writes for x.mul(scale).add(bias).round().clamp(0, 255).to(torch.uint8) -- without those passes and the uint8 image between
+        them.  Asynchronous; wait(last_ticket, n) / finish() for the sizes."""
+        batch = images if outs is None else self.make_batch_float(images, outs, order, bottom_up, mean, std, scale, bias)
+        if not all(im.is_cuda and out.is_cuda for im, out in zip(batch[0], batch[1])):
+            raise ValueError("submit_float: images and outs are CUDA tensors")
+        n = len(batch[2])
+        self._sync_stream()
+        t = C.c_uint64(0)
+        check(self.lib.fpng_amd_encode_submit_planar_float(self.h, batch[2], n, C.byref(batch[3]), flags, C.byref(t)))
+        self.last_ticket = t.value
+        self._keep[t.value] = batch
+        for old in [k for k in self._keep if k + 8 <= t.value]:
+            del self._keep[old]
+        return n
+
     def wait(self, ticket, n):
         """Waits for the submission `ticket` (see last_ticket) only; returns its (png_size, mode, status) records."""
         res = (Result * n)()
@@ -823,20 +915,7 @@ class Encoder:
         fmaf(byte, scale[c], bias[c]) of the FILE's channel c (R, G, B, A, whatever the planes' order in memory), rounded to the
         dtype: give mean and std (normalize_constants(): (byte / 255 - mean) / std), or scale and bias (up to four values each,
         padded with 1 / 255 and 0), or neither for plain [0, 1] values.  pixels_cap is the view's own span in bytes."""
-        if (mean is None) != (std is None) or (mean is not None and (scale is not None or bias is not None)):
-            raise ValueError("make_decode_batch_float: mean and std together, or scale and / or bias, or neither")
-        if mean is not None:
-            sc, bi = normalize_constants(mean, std)
-        else:
-            sc, bi = normalize_constants([], [])
-            for dst, src, what in ((sc, scale, "scale"), (bi, bias, "bias")):
-                if src is not None:
-                    v = np.atleast_1d(np.asarray(src, dtype=np.float32))
-                    if v.ndim != 1 or not 1 <= v.size <= 4:
-                        raise ValueError(f"make_decode_batch_float: {what} has 1 to 4 values")
-                    dst[: v.size] = v
-        if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(bi))):
-            raise ValueError("make_decode_batch_float: scale and bias must be finite")
+        sc, bi = _float_constants("make_decode_batch_float", normalize_constants, mean, std, scale, bias)
         n = len(pngs)
         orders = [order] * n if isinstance(order, str) else list(order)
         ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)

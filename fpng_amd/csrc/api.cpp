@@ -5,8 +5,10 @@
 // stream.  There is no CPU implementation of the encode path in this library.
 #include "encoder.h"
 #include "lanes.h"
+#include "quantize.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -466,6 +468,9 @@ struct Submission {
     uint32_t chan_mask = 0;    // bit 0: 3-channel jobs present, bit 1: 4-channel jobs
     bool ex = false;           // fpng_amd_encode_submit_ex: the jobs carry a source layout, the *_ex kernels read their pixels
     bool planar = false;       // fpng_amd_encode_submit_planar: planar jobs, the *_planar kernels read their pixels (chan_mask says which)
+    bool planar_float = false; // fpng_amd_encode_submit_planar_float: planar jobs of floats (`planar` is set too), the *_planar_float kernels of float_dtype
+    uint32_t float_dtype = 0;
+    FloatQuant fq = {};
     uint32_t layout_mask = 0;  // (ex) bit 0: 3-byte sources, bit 1: 4-byte sources with 4 channels, bit 2: 4-byte sources with 3
     uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
 };
@@ -509,8 +514,10 @@ static_assert(sizeof(fpng_amd_image_planar) == 56 && offsetof(fpng_amd_image_pla
 // Fills slot.jobs[0..n) for whole-image jobs and sizes the scratch buffers.  Only `slot` (which is free) and
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
 // ex_images (fpng_amd_encode_submit_ex) or pl_images (fpng_amd_encode_submit_planar) replaces `images` when it is given.
+// ffmt (fpng_amd_encode_submit_planar_float, with pl_images): the planes hold floats of that type; pitches stay bytes.
 int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const fpng_amd_image *images,
-                 const fpng_amd_image_ex *ex_images, const fpng_amd_image_planar *pl_images, uint32_t n, uint32_t flags, Submission &sub)
+                 const fpng_amd_image_ex *ex_images, const fpng_amd_image_planar *pl_images, uint32_t n, uint32_t flags, Submission &sub,
+                 const fpng_amd_float_format *ffmt = nullptr)
 {
     if (!e || !(images || ex_images || pl_images) || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "batch larger than 65535 images");
@@ -523,6 +530,18 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     sub.n = n;
     sub.ex = ex_images != nullptr;
     sub.planar = pl_images != nullptr;
+    int64_t elem = 1; // bytes of a planar source's element
+    if (ffmt) {
+        if (ffmt->dtype > FPNG_AMD_BF16) return fail(FPNG_AMD_ERR_INVALID_ARG, "dtype is FPNG_AMD_F32, _F16 or _BF16");
+        if (ffmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt->reserved must be 0");
+        for (int k = 0; k < 4; k++) {
+            if (!std::isfinite(ffmt->scale[k]) || !std::isfinite(ffmt->bias[k])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
+            sub.fq.scale[k] = ffmt->scale[k], sub.fq.bias[k] = ffmt->bias[k];
+        }
+        sub.planar_float = true;
+        sub.float_dtype = ffmt->dtype;
+        elem = ffmt->dtype == FPNG_AMD_F32 ? 4 : 2;
+    }
     for (uint32_t i = 0; i < n; i++) {
         fpng_amd_image im_of_ex;
         const SrcFormat *fmt = nullptr;
@@ -531,16 +550,19 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
             const fpng_amd_image_planar &x = pl_images[i];
             if (x.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "reserved must be 0");
             if ((rc = check_dims(x.w, x.h, x.num_chans))) return rc;
-            pitch = x.row_pitch ? x.row_pitch : (int64_t)x.w;
+            const int64_t row_bytes = (int64_t)x.w * elem;
+            if (elem > 1 && (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (uint64_t)(elem - 1)))
+                return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
+            pitch = x.row_pitch ? x.row_pitch : row_bytes;
             const int64_t apitch = pitch < 0 ? -pitch : pitch;
-            if (apitch < (int64_t)x.w) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w");
+            if (apitch < row_bytes) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
             // (h, w < 2^24 and |row_pitch| < 2^63 / 2^24 keep the span in 64 bits)
             if (apitch > (INT64_MAX >> 26)) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| too large");
-            const int64_t span = (int64_t)(x.h - 1) * apitch + x.w; // bytes from a plane's lowest row to the end of its highest
+            const int64_t span = (int64_t)(x.h - 1) * apitch + row_bytes; // bytes from a plane's lowest row to the end of its highest
             plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)x.h * apitch;
             if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
             if ((plane_pitch < 0 ? -plane_pitch : plane_pitch) < span)
-                return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w: the planes overlap");
+                return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
             im_of_ex.d_pixels = x.d_pixels;
             im_of_ex.w = x.w, im_of_ex.h = x.h, im_of_ex.num_chans = x.num_chans;
             im_of_ex.d_out = x.d_out;
@@ -604,7 +626,7 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
         if (pl_images) {
             j.pitch = pitch;
             j.plane_pitch = plane_pitch;
-            j.src_bytes = 1;
+            j.src_bytes = ffmt ? kFloatLayout + ffmt->dtype : 1;
         }
         if (im.num_chans == 4) sub.px4 += (uint64_t)im.w * im.h, sub.px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
         const uint64_t units = im.h; // records of the job: one per row
@@ -628,7 +650,7 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
 }
 
 int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out,
-           const fpng_amd_image_planar *pl_images = nullptr)
+           const fpng_amd_image_planar *pl_images = nullptr, const fpng_amd_float_format *ffmt = nullptr)
 {
     if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
     HIP_TRY(hipSetDevice(e->device));
@@ -653,7 +675,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     hipStream_t s = e->lane_stream[lane];
     fpng_amd_encoder::Scratch &sc = e->sc[lane];
     Submission sub;
-    int rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub);
+    int rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub, ffmt);
     if (rc) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
@@ -720,6 +742,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
         sc.hist_zero = 0;
         if (job_in_args)
             launch_hist_first(s, slot.jobs.p[0], sc.d_jobs.p, sc.d_hist.p);
+        else if (sub.planar_float)
+            launch_hist_planar_float(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p, sub.float_dtype, sub.fq);
         else if (sub.planar)
             launch_hist_planar(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
         else if (sub.ex)
@@ -749,6 +773,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     // (both kernels get slower by more than the two small launches cost) and 5-19 % MORE single-frame latency.
     if (job_in_args)
         launch_encode_rows_first(s, two_pass ? slot.jobs2.p[0] : slot.jobs.p[0], sc.d_jobs.p, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
+    else if (!force_stored && sub.planar_float)
+        launch_encode_rows_planar_float(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, sub.float_dtype, sub.fq);
     else if (!force_stored && sub.planar)
         launch_encode_rows_planar(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
     else if (!force_stored && sub.ex)
@@ -772,7 +798,10 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
     if ((rc = mark(e, s, ++ph))) return rc;
     uint32_t *adler_parts = sc.d_partials.p + (size_t)n * sub.max_crc_blocks;
-    if (sub.planar)
+    if (sub.planar_float)
+        launch_assemble_planar_float(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts,
+                                     sub.float_dtype, sub.fq);
+    else if (sub.planar)
         launch_assemble_planar(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
     else if (sub.ex)
         launch_assemble_ex(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
@@ -820,6 +849,27 @@ int fpng_amd_encode_submit_planar(fpng_amd_encoder *e, const fpng_amd_image_plan
 {
     if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     return submit(e, nullptr, nullptr, n, flags, ticket, images);
+}
+
+int fpng_amd_encode_submit_planar_float(fpng_amd_encoder *e, const fpng_amd_image_planar *images, uint32_t n, const fpng_amd_float_format *fmt, uint32_t flags,
+                                        uint64_t *ticket)
+{
+    if (!images || !fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch or format");
+    return submit(e, nullptr, nullptr, n, flags, ticket, images, fmt);
+}
+
+int fpng_amd_quantize_float(const void *src, uint32_t dtype, float scale, float bias, uint8_t *dst, size_t n)
+{
+    if ((!src || !dst) && n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (dtype == FPNG_AMD_F32) {
+        for (size_t i = 0; i < n; i++) dst[i] = (uint8_t)quantize(widen<kF32>(((const uint32_t *)src)[i]), scale, bias);
+    } else if (dtype == FPNG_AMD_F16) {
+        for (size_t i = 0; i < n; i++) dst[i] = (uint8_t)quantize(widen<kF16>(((const uint16_t *)src)[i]), scale, bias);
+    } else if (dtype == FPNG_AMD_BF16) {
+        for (size_t i = 0; i < n; i++) dst[i] = (uint8_t)quantize(widen<kBF16>(((const uint16_t *)src)[i]), scale, bias);
+    } else
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "dtype is FPNG_AMD_F32, _F16 or _BF16");
+    return FPNG_AMD_OK;
 }
 
 int fpng_amd_encode_batch_async(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags)

@@ -35,7 +35,8 @@ struct Job {
     // R,G,B[,A] bytes (0x0c = a zero byte).  These words were reserved before: the record stays 224 bytes and png_header where it
     // was, so the other kernels' code is, instruction for instruction, the same (tools/isa_diff.py)
     int64_t pitch;            // signed bytes from one row to the next
-    uint32_t src_bytes;       // 3 or 4; 1 = a planar job (fpng_amd_encode_submit_planar): a byte per pixel and plane
+    uint32_t src_bytes;       // 3 or 4; 1 = a planar job (fpng_amd_encode_submit_planar): a byte per pixel and plane;
+                              // kFloatLayout + dtype = a planar job of floats (fpng_amd_encode_submit_planar_float): pitches in bytes of the float source
     uint32_t sel;
     int64_t plane_pitch;      // planar jobs: signed bytes from one channel's plane to the next (R -> G -> B [-> A]); `rows` is the R plane's top row
     uint8_t png_header[60];   // 58 bytes used (reference fpng.cpp:1767-1791), IDAT length patched on device
@@ -117,6 +118,19 @@ void launch_encode_rows_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, 
                                JobState *states, uint32_t *local);
 void launch_assemble_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
                             const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
+// fpng_amd_encode_submit_planar_float: planar jobs whose planes hold f32 / f16 / bf16 elements (dtype: FPNG_AMD_F32 / _F16 / _BF16).
+// The kernels that read pixels turn every element into its byte as they load it (quantize.h); the constants are the submission's
+// and travel in the kernel arguments -- the Job record is full.  Job::src_bytes = kFloatLayout + dtype.
+constexpr uint32_t kFloatLayout = 16;
+struct FloatQuant {
+    float scale[4], bias[4]; // per file channel R, G, B, A
+};
+void launch_hist_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, uint32_t dtype, const FloatQuant &fq);
+void launch_encode_rows_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
+                                     JobState *states, uint32_t *local, uint32_t dtype, const FloatQuant &fq);
+void launch_assemble_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
+                                  const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts,
+                                  uint32_t dtype, const FloatQuant &fq);
 // table training: sums[0..288) += the 16-bit adjusted histogram of every image (hist_all: 288 counters per image)
 void launch_train_accumulate(hipStream_t s, const uint32_t *hist_all, uint32_t n_images, uint64_t *sums);
 // dst[0..16) |= src[0..16): the 16-byte piece two neighbouring band windows share (each holds zeros where the other's bits are)

@@ -28,6 +28,7 @@
 // Integer / byte work throughout, bounded by VALU issue and HBM traffic: no MFMA.
 #include "kernels.h"
 #include "crc_device.h"
+#include "quantize.h"
 
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,20 @@ constexpr uint32_t kStoredExBlocks = 64; // stored_ex_kernel: workgroups per ima
 #endif
 #ifndef FPNG_ROWS_WPE_PLANAR4
 #define FPNG_ROWS_WPE_PLANAR4 5
+#endif
+// the float walks (encode_rows_planar_float_kernel): the planar walk with twice (f32) or one and a half times (f16 / bf16) the source
+// dwords of a super-window in flight, converted to the planar walk's bytes as they arrive.  Per instantiation the most waves per
+// SIMD without scratch (profiles/float_encode_kernel_resources.txt): 3 channels 79 (f32) / 73 (f16, bf16) vector registers at six,
+// 4 channels 89 (f16, bf16) at five and 98 (f32) at four -- f32 at five spills one register in the super-window loop.  Not timed
+// against each other.
+#ifndef FPNG_ROWS_WPE_FLOAT3
+#define FPNG_ROWS_WPE_FLOAT3 6
+#endif
+#ifndef FPNG_ROWS_WPE_FLOAT4
+#define FPNG_ROWS_WPE_FLOAT4 5
+#endif
+#ifndef FPNG_ROWS_WPE_FLOAT4_F32
+#define FPNG_ROWS_WPE_FLOAT4_F32 4
 #endif
 constexpr int kStageDwords = FPNG_STAGE_DWORDS; // per-wave LDS staging window of the output bit stream
 // Local-stream stores carry the non-temporal hint (build with -DFPNG_LOCAL_NT=0 to A/B it: the hint decides whether the
@@ -151,6 +166,7 @@ typedef const FPNG_GLOBAL uint8_t *gptr_cu8;
 typedef const FPNG_GLOBAL uint32_t *gptr_cu32;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef const FPNG_GLOBAL u32x4 *gptr_cu128;
 typedef FPNG_GLOBAL u32x4 *gptr_u128;
 typedef FPNG_GLOBAL uint8_t *gptr_u8;
@@ -438,6 +454,106 @@ template <int C> struct RowWindows<C, 1> {
 template <int C> struct PlaneDwords {
     uint32_t lo[C], hi[C];
 };
+// L = kFloatLayout + dtype: a planar source of FLOATS (fpng_amd_encode_submit_planar_float) -- RowWindows<C, 1> with elements of four
+// (f32) or two (f16 / bf16) bytes in the place of its bytes.  Every element is turned into its byte (quantize.h) as soon as it is
+// loaded, the row above too (Up subtracts the QUANTISED row), so that filter() and the super-windows' filt hand the walk what the
+// planar layout does.  Elements are aligned to their size only: the resources' bases are aligned down to a dword and a 16-bit row
+// may start two bytes into it (phase 0 or 2; always 0 for f32).  A missing Up row is a zero-sized resource whose loads return 0.0,
+// which does not quantise to 0 with a bias: up_mask clears those bytes.
+constexpr bool is_float_layout(int L) { return L >= (int)kFloatLayout; }
+constexpr bool is_planar_layout(int L) { return L == 1 || is_float_layout(L); }
+template <int C, uint32_t DT> struct FloatRowWindows {
+    static constexpr int SB = DT == kF32 ? 4 : 2; // bytes per element
+    __amdgpu_buffer_rsrc_t cur[C], up[C];
+    uint32_t phase[C], up_phase[C];
+    uint32_t up_mask = 0;
+    float scale[C], bias[C];
+    uint32_t sel = 0;
+    uint32_t lane_ = 0;
+
+    // row / up_row: the R plane's rows; w: elements of a plane's row
+    __device__ __forceinline__ void init_planes(const uint8_t *row, const uint8_t *up_row, int64_t plane_pitch, uint32_t w, uint32_t lane, const FloatQuant &fq)
+    {
+        lane_ = lane;
+        up_mask = up_row ? ~0u : 0u;
+        const uint32_t bytes = w * (uint32_t)SB;
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            scale[ch] = fq.scale[ch], bias[ch] = fq.bias[ch];
+            const uint8_t *rp = row + (int64_t)ch * plane_pitch;
+            const uint32_t a = uniform((uint32_t)((uintptr_t)rp & 3));
+            phase[ch] = a;
+            cur[ch] = make_rsrc(rp - a, (a + bytes + 3) & ~3u);
+            const uint8_t *ub = (up_row ? up_row : row) + (int64_t)ch * plane_pitch;
+            const uint32_t b = uniform((uint32_t)((uintptr_t)ub & 3));
+            up_phase[ch] = b;
+            up[ch] = make_rsrc(ub - b, up_row ? ((b + bytes + 3) & ~3u) : 0u);
+        }
+    }
+    __device__ __forceinline__ uint32_t byte_of(uint32_t bits, int ch) const { return quantize(widen<DT>(bits), scale[ch], bias[ch]); }
+    struct Raw {
+        uint32_t c[C], u[C]; // one element per plane (16-bit types: in the low half)
+    };
+    __device__ __forceinline__ Raw load_raw(uint32_t x0) const
+    {
+        Raw q;
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            if (DT == kF32) {
+                q.c[ch] = __builtin_amdgcn_raw_buffer_load_b32(cur[ch], lane_ * 4, x0 * 4, 0);
+                q.u[ch] = __builtin_amdgcn_raw_buffer_load_b32(up[ch], lane_ * 4, x0 * 4, 0);
+            } else {
+                q.c[ch] = __builtin_amdgcn_raw_buffer_load_b16(cur[ch], lane_ * 2, x0 * 2 + phase[ch], 0);
+                q.u[ch] = __builtin_amdgcn_raw_buffer_load_b16(up[ch], lane_ * 2, x0 * 2 + up_phase[ch], 0);
+            }
+        }
+        return q;
+    }
+    __device__ __forceinline__ uint32_t filter(const Raw &q) const
+    {
+        uint32_t cb[C], ub[C];
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) cb[ch] = byte_of(q.c[ch], ch), ub[ch] = byte_of(q.u[ch], ch);
+        return sub_bytes(RowWindows<C, 1>::pack(cb), RowWindows<C, 1>::pack(ub) & up_mask);
+    }
+    __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
+
+    // a super-window: the dwords that hold the lane's four elements of every plane -- four for f32, three for the 16-bit types
+    // (two when the row starts on a dword, and the next one when it starts two bytes into it)
+    static constexpr int ND = DT == kF32 ? 4 : 3;
+    struct Dwords {
+        uint32_t d[C][ND];
+    };
+    __device__ __forceinline__ void load_dwords(const __amdgpu_buffer_rsrc_t (&res)[C], uint32_t voff, uint32_t soff, Dwords &o) const
+    {
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            if constexpr (DT == kF32) {
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(res[ch], voff, soff, 0);
+                o.d[ch][0] = v.x, o.d[ch][1] = v.y, o.d[ch][2] = v.z, o.d[ch][3] = v.w;
+            } else {
+                const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(res[ch], voff, soff, 0);
+                o.d[ch][0] = v.x, o.d[ch][1] = v.y, o.d[ch][2] = v.z;
+            }
+        }
+    }
+    // the lane's four bytes of plane ch, packed
+    __device__ __forceinline__ uint32_t bytes_of(const Dwords &q, int ch, uint32_t ph) const
+    {
+        uint32_t e[4];
+        if constexpr (DT == kF32) {
+            e[0] = q.d[ch][0], e[1] = q.d[ch][1], e[2] = q.d[ch][2], e[3] = q.d[ch][3];
+        } else {
+            const uint32_t lo = __builtin_amdgcn_alignbyte(q.d[ch][1], q.d[ch][0], ph), hi = __builtin_amdgcn_alignbyte(q.d[ch][2], q.d[ch][1], ph);
+            e[0] = lo & 0xFFFFu, e[1] = lo >> 16, e[2] = hi & 0xFFFFu, e[3] = hi >> 16;
+        }
+        return byte_of(e[0], ch) | (byte_of(e[1], ch) << 8) | (byte_of(e[2], ch) << 16) | (byte_of(e[3], ch) << 24);
+    }
+};
+template <int C> struct RowWindows<C, (int)(kFloatLayout + kF32)> : FloatRowWindows<C, kF32> {};
+template <int C> struct RowWindows<C, (int)(kFloatLayout + kF16)> : FloatRowWindows<C, kF16> {};
+template <int C> struct RowWindows<C, (int)(kFloatLayout + kBF16)> : FloatRowWindows<C, kBF16> {};
+
 // pixel 0 of the four that a lane's plane dwords hold (byte 0 of each plane's dword)
 template <int C> __device__ __forceinline__ uint32_t planar_first_pixel(const uint32_t (&fd)[4])
 {
@@ -445,6 +561,14 @@ template <int C> __device__ __forceinline__ uint32_t planar_first_pixel(const ui
     if (C == 4) return __builtin_amdgcn_perm(__builtin_amdgcn_perm(fd[3], fd[2], 0x0c0c0400u), rg, 0x05040100u);
     return __builtin_amdgcn_perm(fd[2], rg, 0x0c040100u);
 }
+
+// what a lane holds of one super-window of a row before it is filtered (walk_row, phase A)
+template <int C, int L, bool = is_float_layout(L)> struct SuperWindowSource {
+    using type = std::conditional_t<L == 1, PlaneDwords<C>, u32x4>;
+};
+template <int C, int L> struct SuperWindowSource<C, L, true> {
+    using type = typename RowWindows<C, L>::Dwords;
+};
 
 // 64-bit mask of lanes whose pixel index x0+lane is below `limit`
 __device__ __forceinline__ uint64_t valid_mask(uint32_t x0, uint32_t limit)
@@ -597,9 +721,11 @@ struct RowResult {
 };
 
 // Walks row r of the job.  L: source layout (RowWindows); rows of an L != 0 job lie job.pitch bytes apart.
-template <int C, Pass PASS, int L = 0>
-__device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables &T, uint32_t *hist, uint32_t r, uint32_t lane, EmitSink *sink)
+// FQ: nothing, or (float layouts) the submission's FloatQuant
+template <int C, Pass PASS, int L = 0, typename... FQ>
+__device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables &T, uint32_t *hist, uint32_t r, uint32_t lane, EmitSink *sink, const FQ &...fq)
 {
+    constexpr bool kFloat = is_float_layout(L), kPlanar = is_planar_layout(L); // (float sources are planar ones: fq has their constants)
     using Raw = typename RowWindows<C, L>::Raw;
     constexpr int SB = RowWindows<C, L>::SB;
     constexpr int PF = 4; // windows in flight ahead of the one being processed
@@ -619,7 +745,9 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
 
     RowWindows<C, L> px;
     if (L) px.sel = uniform(job.sel);
-    if constexpr (L == 1)
+    if constexpr (kFloat)
+        px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane, fq...);
+    else if constexpr (L == 1)
         px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane);
     else
         px.init(row, up_row, L ? w * (uint32_t)SB : bpl, lane);
@@ -761,7 +889,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
         if (kSums) {
             // Adler-32 partial sums (reference fpng.cpp:407-487 computes the same quantity serially).  Lanes
             // past the row end read 0 (RGBA) or are masked (RGB shares an aligned dword with real bytes).
-            const uint32_t fa = (!TAIL || (C == 4 && L != 1) || valid) ? f_cur : 0u;
+            const uint32_t fa = (!TAIL || (C == 4 && !is_planar_layout(L)) || valid) ? f_cur : 0u;
             const uint32_t a = __builtin_amdgcn_sad_u8(fa, 0u, 0u);
             acc_a += a;
             acc_w += (uint64_t)(bpl - (uint32_t)C * (x0 + lane)) * a; // invalid lanes: a == 0
@@ -807,9 +935,13 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
         if (NSX > S0) {
             const uint32_t voff4 = lane * kSrcLaneBytes;
             // (planar sources: per plane, the two aligned dwords that hold the lane's four bytes of the row and of the row above)
-            using W4 = std::conditional_t<L == 1, PlaneDwords<C>, u32x4>;
+            // (float sources: per plane, the dwords that hold the lane's four elements)
+            using W4 = typename SuperWindowSource<C, L>::type;
             auto load4 = [&](uint32_t S, W4 &c4, W4 &u4) {
-                if constexpr (L == 1) {
+                if constexpr (kFloat) {
+                    px.load_dwords(px.cur, voff4, S * kSrcSuperBytes, c4);
+                    px.load_dwords(px.up, voff4, S * kSrcSuperBytes, u4);
+                } else if constexpr (L == 1) {
 #pragma unroll
                     for (int ch = 0; ch < C; ch++) {
                         const u32x2 c2 = __builtin_amdgcn_raw_buffer_load_b64(px.cur[ch], voff4, S * kSrcSuperBytes, 0);
@@ -826,7 +958,11 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             // filtered bytes of the lane's four pixels, packed: fd[0..ND) (L != 0: in source order, four dwords for 4-byte sources)
             // (planar: fd[ch] = the lane's four filtered bytes of plane ch)
             auto filt = [&](const W4 &c4, const W4 &u4, uint32_t (&fd)[4]) {
-                if constexpr (L == 1) {
+                if constexpr (kFloat) {
+#pragma unroll
+                    for (int ch = 0; ch < C; ch++) fd[ch] = sub_bytes(px.bytes_of(c4, ch, px.phase[ch]), px.bytes_of(u4, ch, px.up_phase[ch]) & px.up_mask);
+                    if (C == 3) fd[3] = 0;
+                } else if constexpr (L == 1) {
 #pragma unroll
                     for (int ch = 0; ch < C; ch++)
                         fd[ch] = sub_bytes(__builtin_amdgcn_alignbyte(c4.hi[ch], c4.lo[ch], px.phase[ch]),
@@ -848,7 +984,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             };
             // pixel values (what the per-pixel walk calls f_cur): RGBA = the dwords, RGB = 24-bit fields
             auto pixels = [&](const uint32_t (&fd)[4], uint32_t (&pv)[4]) {
-                if constexpr (L == 1) {
+                if constexpr (kPlanar) {
                     // byte transpose, planes -> pixels: R and G interleaved first, then joined with B (and A)
                     const uint32_t rg01 = __builtin_amdgcn_perm(fd[1], fd[0], 0x05010400u), rg23 = __builtin_amdgcn_perm(fd[1], fd[0], 0x07030602u);
                     if constexpr (C == 4) {
@@ -885,7 +1021,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             uint32_t fd[4];
             filt(c_first, u_first, fd);
             // pixel just before the super-window; in front of pixel 0: a value pixel 0 cannot equal (it has no left neighbour)
-            uint32_t last_f = L == 1 ? ~uniform(planar_first_pixel<C>(fd)) : L ? ~uniform(__builtin_amdgcn_perm(0u, fd[0], px.sel)) : ~uniform(fd[0]);
+            uint32_t last_f = kPlanar ? ~uniform(planar_first_pixel<C>(fd)) : L ? ~uniform(__builtin_amdgcn_perm(0u, fd[0], px.sel)) : ~uniform(fd[0]);
             uint32_t wgt = bpl - kLaneBytes * lane - S0 * kSuperBytes; // bytes from this lane's first byte to the row end
             const uint32_t c1_bits = chunk1 & 0xFF;
             // gather the per-pixel view of 64-pixel window jw of the current super-window (lane i <- pixel 64*jw+i)
@@ -910,7 +1046,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
                     if (S + 1 + PF4 <= NS) load4(S + 1 + PF4, rc[js], ru[js]);
                     uint32_t f[4]; // the four pixels of this lane
                     pixels(fd, f);
-                    const uint32_t next_first = L == 1 ? planar_first_pixel<C>(fn) : L ? __builtin_amdgcn_perm(0u, fn[0], px.sel) : (C == 4) ? fn[0] : (fn[0] & 0xFFFFFFu);
+                    const uint32_t next_first = kPlanar ? planar_first_pixel<C>(fn) : L ? __builtin_amdgcn_perm(0u, fn[0], px.sel) : (C == 4) ? fn[0] : (fn[0] & 0xFFFFFFu);
                     // per-lane "equals its left neighbour" predicates (their SGPR form is the wave ballot)
                     const bool s0 = f[0] == lane_prev(f[3], last_f); // (pixel 0 of the row: last_f was chosen to differ)
                     const bool s1 = f[1] == f[0], s2 = f[2] == f[1], s3 = f[3] == f[2];
@@ -1083,9 +1219,10 @@ __device__ __forceinline__ const Job &job_of_block(const Job *jobs) { return job
 // hist_kernel (2-pass, pass 1): literal / length-symbol histogram of the whole image
 // (reference fpng.cpp:1021-1084 / :1299-1363).  job.table here is the "symbol" table whose
 // chunk[q] holds (length symbol - 256).
-// EX: 1 = the jobs of fpng_amd_encode_submit_ex (hist_ex_kernel), walked with their source layout; 2 = planar jobs (hist_planar_kernel)
-template <int EX = 0>
-__device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
+// EX: 1 = the jobs of fpng_amd_encode_submit_ex (hist_ex_kernel), walked with their source layout; 2 = planar jobs (hist_planar_kernel);
+// kFloatLayout + dtype = planar jobs of floats (hist_planar_float_kernel), fq their constants
+template <int EX = 0, typename... FQ>
+__device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const FQ &...fq)
 {
     __shared__ PackedTables T;
     __shared__ uint32_t hist[288 * kHistReplicas];
@@ -1095,7 +1232,12 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst)
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, r = blockIdx.x * kHistWaves + uniform(threadIdx.x >> 6);
     if (r < job.nrows) {
-        if (EX == 2) {
+        if constexpr (is_float_layout(EX)) {
+            if (job.c == 4)
+                walk_row<4, Pass::Hist, EX>(job, T, hist, r, lane, nullptr, fq...);
+            else
+                walk_row<3, Pass::Hist, EX>(job, T, hist, r, lane, nullptr, fq...);
+        } else if (EX == 2) {
             if (job.c == 4)
                 walk_row<4, Pass::Hist, 1>(job, T, hist, r, lane, nullptr);
             else
@@ -1132,6 +1274,12 @@ __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) vo
 __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_planar_kernel(const Job *jobs, uint32_t *hist_out)
 {
     hist_block<2>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
+}
+// the jobs of fpng_amd_encode_submit_planar_float with elements of type DT
+template <uint32_t DT>
+__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_planar_float_kernel(const Job *jobs, uint32_t *hist_out, const FloatQuant fq)
+{
+    hist_block<(int)(kFloatLayout + DT)>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288, fq);
 }
 // (JobArg / the *_first_kernel forms: one image per submission, its job record in the kernel arguments -- see encode_rows_first_kernel)
 struct JobArg {
@@ -1328,8 +1476,8 @@ __global__ __launch_bounds__(kScanBlock) void scan_kernel(const Job *jobs, const
 // One instantiation per channel count (jobs of the other kind leave at once): the 3-channel walk needs far
 // fewer registers than the 4-pixels-per-lane RGBA one and keeps 8 waves per SIMD.
 // L: source layout (RowWindows); an L != 0 instantiation takes the _ex jobs of its channel count and source pixel size.
-template <int C, int L = 0>
-__device__ __forceinline__ void encode_rows_block(const Job &job, uint32_t by, uint32_t bx, RowInfo *rows_out, JobState *states, uint32_t *local)
+template <int C, int L = 0, typename... FQ>
+__device__ __forceinline__ void encode_rows_block(const Job &job, uint32_t by, uint32_t bx, RowInfo *rows_out, JobState *states, uint32_t *local, const FQ &...fq)
 {
     __shared__ PackedTables T;
     __shared__ __attribute__((aligned(16))) uint32_t stage[kRowWaves][kStageDwords + 2 * kWave + 4]; // + dump slots, see sink_put
@@ -1354,7 +1502,7 @@ __device__ __forceinline__ void encode_rows_block(const Job &job, uint32_t by, u
         sink_zero(sink, lane, kStageDwords);
     wave_lds_fence();
 
-    const RowResult res = walk_row<C, Pass::Encode, L>(job, T, nullptr, r, lane, &sink);
+    const RowResult res = walk_row<C, Pass::Encode, L>(job, T, nullptr, r, lane, &sink, fq...);
     if (r == job.nrows - 1 && job.is_last) {
         // end of block symbol behind the last row's tokens (reference fpng.cpp:1564-1567); not part of ri.bits
         const uint32_t eob = T.lit[256];
@@ -1411,6 +1559,17 @@ __global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdg
     uint32_t bx, by;
     xcd_block_order(bx, by);
     encode_rows_block<C, 1>(jobs[by], by, bx, rows_out, states, local);
+}
+
+// the planar jobs of floats (fpng_amd_encode_submit_planar_float) of C channels and element type DT: the constants in the arguments
+template <int C, int WPE, uint32_t DT>
+__global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_planar_float_kernel(const Job *jobs, RowInfo *rows_out,
+                                                                                                                   JobState *states, uint32_t *local,
+                                                                                                                   const FloatQuant fq)
+{
+    uint32_t bx, by;
+    xcd_block_order(bx, by);
+    encode_rows_block<C, (int)(kFloatLayout + DT)>(jobs[by], by, bx, rows_out, states, local, fq);
 }
 
 // One image per submission, first kernel of its chain: the job record comes IN THE KERNEL ARGUMENTS instead of through an
@@ -1568,10 +1727,21 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(const Job *jobs, const
 // job's pitch, pixel size and selector; those images take the byte-by-byte path for every piece (stored blocks are their fallback
 // and FPNG_FORCE_UNCOMPRESSED's form, not a hot path)
 // EX == 2: planar jobs (stored_planar_kernel) -- channel ch of pixel p of a row lies at ch * plane_pitch + row * pitch + p
-template <int EX = 0>
-__device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 px, uint32_t s)
+__device__ __forceinline__ float channel_of(const float (&v)[4], uint32_t ch) { return ch == 0 ? v[0] : ch == 1 ? v[1] : ch == 2 ? v[2] : v[3]; }
+// EX == kFloatLayout + dtype: planar jobs of floats (stored_planar_float_kernel) -- the element there, quantised with fq's constants
+template <int EX = 0, typename... FQ>
+__device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 px, uint32_t s, const FQ &...fq)
 {
     const uint32_t stride = job.bpl + 1, row = s / stride, col = s - row * stride;
+    if constexpr (is_float_layout(EX)) {
+        if (!col) return 0u;
+        constexpr uint32_t DT = (uint32_t)EX - kFloatLayout;
+        const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
+        gptr_cu8 e = px + ((int64_t)ch * job.plane_pitch + (int64_t)row * job.pitch + (int64_t)p * (DT == kF32 ? 4 : 2));
+        const uint32_t bits = DT == kF32 ? *(gptr_cu32)(uintptr_t)e : (uint32_t) * (const FPNG_GLOBAL uint16_t *)(uintptr_t)e;
+        // (selected, not indexed: indexing the kernel argument by a lane's value would put a copy of it into scratch)
+        return quantize(widen<DT>(bits), channel_of(fq.scale, ch)..., channel_of(fq.bias, ch)...);
+    }
     if (EX == 2) {
         if (!col) return 0u;
         const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
@@ -1585,9 +1755,10 @@ __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 
     return col ? (uint32_t)px[(size_t)row * job.bpl + col - 1] : 0u;
 }
 
-template <int EX = 0>
+template <int EX = 0, typename... FQ>
 __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &st, int64_t range_begin, uint32_t range_bytes, int32_t db, int32_t de,
-                                                uint32_t (*tab)[256], uint32_t *red, const CrcDeviceTables *tabs, uint32_t *crc_out, uint32_t *adler_out)
+                                                uint32_t (*tab)[256], uint32_t *red, const CrcDeviceTables *tabs, uint32_t *crc_out, uint32_t *adler_out,
+                                                const FQ &...fq)
 {
     const uint32_t tid = threadIdx.x, stride = job.bpl + 1;
     const uint32_t n_filtered = stride * job.nrows; // (< 2^32: check_dims)
@@ -1648,7 +1819,7 @@ __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &
                         } else {
                             const uint64_t sj = kk * 65535u + (ww - 5);
                             if (sj < n_filtered) {
-                                b = stored_stream_byte<EX>(job, px, (uint32_t)sj);
+                                b = stored_stream_byte<EX>(job, px, (uint32_t)sj, fq...);
                                 a_sum += b;
                                 w_sum += (uint64_t)(n_filtered - (uint32_t)sj) * b;
                             }
@@ -1961,6 +2132,34 @@ __global__ __launch_bounds__(kBlock) void stored_planar_kernel(const Job *jobs, 
         const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
         const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
         assemble_stored<2>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
+        __syncthreads(); // (`red` is read by thread 0 at the end of the range)
+    }
+}
+
+// stored_planar_float_kernel: the same for the planar jobs of floats of fpng_amd_encode_submit_planar_float, element type DT
+template <uint32_t DT>
+__global__ __launch_bounds__(kBlock) void stored_planar_float_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
+                                                                uint32_t *adler_parts, uint32_t max_crc_blocks, const FloatQuant fq)
+{
+    __shared__ uint32_t tab[16][256];
+    __shared__ uint32_t red[3 * kWavesPerBlock];
+    const Job &job = job_of_block(jobs);
+    const JobState &st = states[blockIdx.y];
+    if (uniform(st.mode) == 0u || uniform(st.status)) return;
+    const int64_t data_begin = kPngHeaderBytes, data_end = (int64_t)(kPngHeaderBytes + st.zlib_size - 4);
+    const int64_t end_aligned = (data_end + 15) & ~15ll;
+    const uint32_t range_bytes = 1u << uniform(crc_range_log2(st));
+    auto sat = [](int64_t v) { return (int32_t)(v > 0x7FFFFFFFll ? 0x7FFFFFFFll : (v < -0x7FFFFFFFll ? -0x7FFFFFFFll : v)); };
+    if (end_aligned - (int64_t)blockIdx.x * range_bytes <= (data_begin & ~15ll)) return;
+    for (int i = threadIdx.x; i < 16 * 256; i += kBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
+    __syncthreads();
+    for (uint32_t b = blockIdx.x; b < max_crc_blocks; b += gridDim.x) {
+        const int64_t range_end = end_aligned - (int64_t)b * range_bytes;
+        if (range_end <= (data_begin & ~15ll)) break; // nothing of the data in this range or the ones behind it
+        const int64_t range_begin = range_end - range_bytes;
+        const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
+        const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
+        assemble_stored<(int)(kFloatLayout + DT)>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot], fq);
         __syncthreads(); // (`red` is read by thread 0 at the end of the range)
     }
 }
@@ -2499,6 +2698,35 @@ void launch_encode_rows_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, 
     if (chan_mask & 2u)
         hipLaunchKernelGGL((encode_rows_planar_kernel<4, FPNG_ROWS_WPE_PLANAR4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
 }
+void launch_hist_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, uint32_t dtype, const FloatQuant &fq)
+{
+    const dim3 grid((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1);
+    if (dtype == kF32)
+        hipLaunchKernelGGL(hist_planar_float_kernel<kF32>, grid, dim3(kHistBlock), 0, s, jobs, hist, fq);
+    else if (dtype == kF16)
+        hipLaunchKernelGGL(hist_planar_float_kernel<kF16>, grid, dim3(kHistBlock), 0, s, jobs, hist, fq);
+    else
+        hipLaunchKernelGGL(hist_planar_float_kernel<kBF16>, grid, dim3(kHistBlock), 0, s, jobs, hist, fq);
+}
+template <uint32_t DT>
+static void launch_encode_rows_planar_float_of(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
+                                               JobState *states, uint32_t *local, const FloatQuant &fq)
+{
+    if (chan_mask & 1u)
+        hipLaunchKernelGGL((encode_rows_planar_float_kernel<3, FPNG_ROWS_WPE_FLOAT3, DT>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local, fq);
+    if (chan_mask & 2u)
+        hipLaunchKernelGGL((encode_rows_planar_float_kernel<4, DT == kF32 ? FPNG_ROWS_WPE_FLOAT4_F32 : FPNG_ROWS_WPE_FLOAT4, DT>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local, fq);
+}
+void launch_encode_rows_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
+                                     JobState *states, uint32_t *local, uint32_t dtype, const FloatQuant &fq)
+{
+    if (dtype == kF32)
+        launch_encode_rows_planar_float_of<kF32>(s, jobs, n_jobs, max_rows, chan_mask, rows, states, local, fq);
+    else if (dtype == kF16)
+        launch_encode_rows_planar_float_of<kF16>(s, jobs, n_jobs, max_rows, chan_mask, rows, states, local, fq);
+    else
+        launch_encode_rows_planar_float_of<kBF16>(s, jobs, n_jobs, max_rows, chan_mask, rows, states, local, fq);
+}
 void launch_encode_rows_first(hipStream_t s, const Job &job, Job *d_job, RowInfo *rows, JobState *states, uint32_t *local)
 {
     JobArg arg;
@@ -2530,6 +2758,20 @@ void launch_assemble_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uin
 {
     const uint32_t gx = std::min(max_crc_blocks, kStoredExBlocks);
     hipLaunchKernelGGL(stored_planar_kernel, dim3(gx, n_jobs), dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
+    hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
+                       partials, (uint32_t *)nullptr, max_crc_blocks);
+}
+void launch_assemble_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
+                                  const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts,
+                                  uint32_t dtype, const FloatQuant &fq)
+{
+    const dim3 grid(std::min(max_crc_blocks, kStoredExBlocks), n_jobs);
+    if (dtype == kF32)
+        hipLaunchKernelGGL(stored_planar_float_kernel<kF32>, grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, fq);
+    else if (dtype == kF16)
+        hipLaunchKernelGGL(stored_planar_float_kernel<kF16>, grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, fq);
+    else
+        hipLaunchKernelGGL(stored_planar_float_kernel<kBF16>, grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, fq);
     hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
                        partials, (uint32_t *)nullptr, max_crc_blocks);
 }

@@ -552,6 +552,31 @@ int fpng_amd_decode_batch_planar_float(fpng_amd_encoder *enc, const fpng_amd_png
                                        fpng_amd_decode_result *results);
 int fpng_amd_decode_batch_device_planar_float(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt,
                                               fpng_amd_decode_result *results);
+/* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
+ *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
+ *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever
+ *      the planes lie in memory) and a source element x:
+ *          y    = fmaf((float)x, scale[c], bias[c])        ONE fp32 fused multiply-add; f16 / bf16 widen exactly
+ *          byte = y is NaN ? 0 : (uint8) min(max(rint(y), 0), 255)          rint: round to nearest, ties to even
+ *      so -inf, negatives and -0.0 give 0; +inf and anything >= 255.5 give 255; 0.5 -> 0, 1.5 -> 2, 254.5 -> 254.  The file is byte
+ *      for byte the one fpng_encode_image_to_memory() writes for those bytes interleaved as R,G,B[,A], in compressed, 2-pass and
+ *      stored modes alike.  Plain [0, 1] values: scale = 255, bias = 0; the inverse of Normalize(mean, std):
+ *      scale[c] = 255 * std[c], bias[c] = 255 * mean[c].
+ *      The fpng_amd_image_planar records are used as they are: row_pitch and plane_pitch stay BYTES, of the float source -- a row
+ *      is w * (element bytes), 0 still means tight (w * elem, h * |row_pitch|), negative pitches bottom-up rows and reversed planes.
+ *      fmt is one per call.  Every rule of fpng_amd_encode_submit_planar holds with w * (element bytes) in the place of w
+ *      (|row_pitch| >= that, the planes' overlap; w, h, d_out, out_cap); in addition FPNG_AMD_ERR_INVALID_ARG, with nothing
+ *      launched and no ticket handed out, for a dtype other than the three, fmt->reserved != 0, a scale or bias that is not finite,
+ *      d_pixels, row_pitch or plane_pitch that is not a multiple of the element size, and a null fmt.  Elements need no more than
+ *      their own alignment.  The ticket works with fpng_amd_encode_wait / _query / _finish / _join like any other; float, planar and
+ *      packed submissions may be in flight on one encoder at once.  The source is only read: of a row only its w elements reach the
+ *      file, and num_chans = 3 over a tensor that has a fourth plane never lets that plane influence anything.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encode_submit_planar_float with dlsym. ---- */
+int fpng_amd_encode_submit_planar_float(fpng_amd_encoder *enc, const fpng_amd_image_planar *images, uint32_t n,
+                                        const fpng_amd_float_format *fmt, uint32_t flags, uint64_t *ticket);
+/* The rule above on the HOST, over the text the kernels compile (csrc/quantize.h): dst[i] = byte of element i of src (n elements of
+ * FPNG_AMD_F32 / _F16 / _BF16) with one scale and bias.  For tests and for callers that want to predict a file's bytes. */
+int fpng_amd_quantize_float(const void *src, uint32_t dtype, float scale, float bias, uint8_t *dst, size_t n);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

@@ -72,6 +72,18 @@ class FloatFormat(C.Structure):  # fpng_amd_float_format: 40 bytes
 F32, F16, BF16 = 0, 1, 2  # FPNG_AMD_F32 / _F16 / _BF16
 
 
+class Pack(C.Structure):  # fpng_amd_pack: 40 bytes
+    _fields_ = [("d_arena", C.c_void_p), ("arena_cap", C.c_uint64), ("align", C.c_uint32), ("lead", C.c_uint32), ("d_table", C.c_void_p),
+                ("reserved", C.c_uint64)]
+
+
+class PackedResult(C.Structure):  # fpng_amd_packed_result: 24 bytes
+    _fields_ = [("offset", C.c_uint64), ("png_size", C.c_uint64), ("mode", C.c_uint32), ("status", C.c_uint32)]
+
+
+DESC_IMAGE, DESC_EX, DESC_PLANAR, DESC_PLANAR_FLOAT = 0, 1, 2, 3  # FPNG_AMD_DESC_*
+
+
 class DecodeResult(C.Structure):
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels_in_file", C.c_uint32), ("status", C.c_int32)]
 
@@ -127,6 +139,10 @@ SIGNATURES = {
     "fpng_amd_encode_submit_planar": (_int, [_vp, C.POINTER(ImagePlanar), _u32, _u32, C.POINTER(_u64)]),
     "fpng_amd_encode_submit_planar_float": (_int, [_vp, C.POINTER(ImagePlanar), _u32, C.POINTER(FloatFormat), _u32, C.POINTER(_u64)]),
     "fpng_amd_quantize_float": (_int, [_vp, _u32, C.c_float, C.c_float, _vp, _sz]),
+    "fpng_amd_encode_submit_packed": (_int, [_vp, _u32, _vp, _u32, C.POINTER(FloatFormat), _u32, C.POINTER(Pack), C.POINTER(_u64)]),
+    "fpng_amd_encode_wait_packed": (_int, [_vp, _u64, C.POINTER(PackedResult), _u32, C.POINTER(_u64)]),
+    "fpng_amd_pack_place": (_int, [C.POINTER(_u64), C.POINTER(_u32), _u32, _u32, _u32, _u64, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u64)]),
+    "fpng_amd_pack_capacity": (_sz, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _u32, _u32, _u32]),
     "fpng_amd_encode_wait": (_int, [_vp, _u64, C.POINTER(Result), _u32]),
     "fpng_amd_encode_query": (_int, [_vp, _u64]),
     "fpng_amd_encode_host": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(_sz)]),

@@ -26,6 +26,8 @@ FPNG_CRC32_INIT = 0           # reference src/fpng.h:26
 FPNG_ADLER32_INIT = 1         # reference src/fpng.h:30
 
 MODE_COMPRESSED, MODE_STORED = 0, 1
+# fpng_amd_result.status / fpng_amd_packed_result.status
+STATUS_STORED_TOO_LARGE, STATUS_ARENA_FULL = 1, 2
 
 # Encoder.set_decode_verify (FPNG_AMD_VERIFY_* in include/fpng_amd.h) and the two statuses only a checked decode returns
 VERIFY_CRC32, VERIFY_ADLER32 = 1, 2
@@ -292,6 +294,41 @@ def adler32_combine(adler_x, adler_y, len_y):
 
 def max_encoded_size(w, h, num_chans):
     return _lib.load().fpng_amd_max_encoded_size(w, h, num_chans)
+
+
+def pack_capacity(dims, align=16, lead=0):
+    """fpng_amd_pack_capacity: the arena size with which Encoder.submit_packed() can refuse none of the images `dims` = [(w, h, c)]:
+    the placement rule applied to max_encoded_size() of each."""
+    n = len(dims)
+    w, h, c = ((C.c_uint32 * n)(*[int(d[k]) for d in dims]) for k in range(3))
+    cap = int(_lib.load().fpng_amd_pack_capacity(w, h, c, n, align, lead))
+    if n and not cap:
+        raise ValueError("pack_capacity: align is 0 or a power of two in 16 .. 65536, lead a multiple of 16 up to 65536")
+    return cap
+
+
+def pack_place(sizes, align, lead, cap, statuses=None):
+    """fpng_amd_pack_place, the placement rule of packed submissions on the host: file sizes (and their statuses before placement,
+    default all 0) -> ([(offset, status)], total) as the GPU decides them for an arena of `cap` bytes."""
+    n = len(sizes)
+    sz = (C.c_uint64 * n)(*[int(v) for v in sizes])
+    st = (C.c_uint32 * n)(*[int(v) for v in statuses]) if statuses is not None else None
+    off, st_out, total = (C.c_uint64 * n)(), (C.c_uint32 * n)(), C.c_uint64(0)
+    check(_lib.load().fpng_amd_pack_place(sz, st, n, align, lead, cap, off, st_out, C.byref(total)))
+    return list(zip(off, st_out)), total.value
+
+
+class _NoOut:
+    """stands where a make_batch_*() call expects an output tensor: a packed submission's descriptors carry none"""
+    is_cuda = True
+
+    @staticmethod
+    def data_ptr():
+        return None
+
+    @staticmethod
+    def numel():
+        return 0
 
 
 def layout_1pass(num_chans):
@@ -681,6 +718,83 @@ class Encoder:
         for old in [k for k in self._keep if k + 8 <= t.value]:
             del self._keep[old]
         return n
+
+    _PACK_KINDS = {"image": _lib.DESC_IMAGE, "ex": _lib.DESC_EX, "planar": _lib.DESC_PLANAR, "float": _lib.DESC_PLANAR_FLOAT}
+
+    @staticmethod
+    def make_batch_packed(images, kind="image", **layout):
+        """Descriptor for submit_packed(): the make_batch*() descriptor of `kind` ("image" | "ex" | "planar" | "float", with that
+        kind's layout arguments: order, bottom_up, and for "float" mean / std / scale / bias) without outputs."""
+        if kind not in Encoder._PACK_KINDS:
+            raise ValueError(f"make_batch_packed: kind is one of {sorted(Encoder._PACK_KINDS)}, not {kind!r}")
+        outs = [_NoOut] * len(images)
+        if kind == "image":
+            if layout:
+                raise ValueError(f"make_batch_packed: kind 'image' takes no layout arguments, got {sorted(layout)}")
+            arr = (Image * len(images))()
+            for a, im in zip(arr, images):
+                if im.dtype != torch.uint8 or im.dim() != 3 or not im.is_contiguous():
+                    raise ValueError("make_batch_packed: kind 'image' takes contiguous uint8 tensors shaped (h, w, c)")
+                a.d_pixels, (a.h, a.w, a.num_chans) = im.data_ptr(), im.shape
+            batch = (images, outs, arr)
+        else:
+            make = {"ex": Encoder.make_batch_ex, "planar": Encoder.make_batch_planar, "float": Encoder.make_batch_float}[kind]
+            batch = make(images, outs, **layout)
+        return ("packed", kind) + tuple(batch)
+
+    def submit_packed(self, images, arena, kind="image", align=16, lead=0, table=None, flags=0, **layout):
+        """fpng_amd_encode_submit_packed: the files of ONE submission back to back in `arena` (a uint8 CUDA tensor whose address is a
+        multiple of align), placed on the GPU from their actual sizes: every file at round_up(cursor, align) + lead, `lead` bytes
+        in front of it left untouched; a file that finds no room gets status STATUS_ARENA_FULL and not a byte of it is written
+        (pack_place() is the rule, pack_capacity() the size that refuses nothing).  images: tensors as for submit / submit_ex /
+        submit_planar / submit_float (kind, **layout: that call's order / bottom_up / mean / std / scale / bias), or a
+        make_batch_packed() descriptor.  table: optional int64 CUDA tensor of 2 * (n + 1) elements, filled with {offset, png_size} per
+        file and {total, files placed}.  Asynchronous; wait_packed(last_ticket, n) for the records."""
+        batch = images if isinstance(images, tuple) and images[:1] == ("packed",) else self.make_batch_packed(images, kind, **layout)
+        kind, arr = batch[1], batch[4]
+        n = len(arr)
+        if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()):
+            raise ValueError("submit_packed: arena is a contiguous uint8 CUDA tensor")
+        if not all(im.is_cuda for im in batch[2]):
+            raise ValueError("submit_packed: images are CUDA tensors")
+        pack = _lib.Pack(arena.data_ptr(), arena.numel(), align, lead, None, 0)
+        if table is not None:
+            if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= 2 * (n + 1)):
+                raise ValueError("submit_packed: table is a contiguous int64 CUDA tensor of 2 * (n + 1) elements")
+            pack.d_table = table.data_ptr()
+        self._sync_stream()
+        t = C.c_uint64(0)
+        check(self.lib.fpng_amd_encode_submit_packed(self.h, self._PACK_KINDS[kind], C.cast(arr, C.c_void_p), n,
+                                                     C.byref(batch[5]) if kind == "float" else None, flags, C.byref(pack), C.byref(t)))
+        self.last_ticket = t.value
+        self._keep[t.value] = (batch, arena, table)  # the arena and the table stay alive with the sources
+        for old in [k for k in self._keep if k + 8 <= t.value]:
+            del self._keep[old]
+        return n
+
+    def wait_packed(self, ticket, n):
+        """Waits for the packed submission `ticket`; returns ([(offset, png_size, mode, status)], total): file i is
+        arena[offset:offset + png_size], total the end of the last file placed."""
+        res = (_lib.PackedResult * n)()
+        total = C.c_uint64(0)
+        check(self.lib.fpng_amd_encode_wait_packed(self.h, ticket, res, n, C.byref(total)))
+        self._keep.pop(ticket, None)
+        return [(r.offset, r.png_size, r.mode, r.status) for r in res], total.value
+
+    def encode_packed(self, images, kind="image", align=16, lead=0, flags=0, **layout):
+        """Convenience: an arena of pack_capacity() bytes, one packed submission, the wait: returns (arena[:total], records) --
+        records as wait_packed() gives them; one .cpu() of the first and one write() make a shard body."""
+        batch = self.make_batch_packed(images, kind, **layout)
+        arr = batch[4]
+        dims = [(a.w, a.h, format_channels(a.format) if kind == "ex" else a.num_chans) for a in arr]
+        cap = pack_capacity(dims, align, lead)
+        a = max(int(align), 16)
+        raw = torch.empty(cap + a, dtype=torch.uint8, device=batch[2][0].device)
+        skip = (-raw.data_ptr()) % a
+        arena = raw[skip:skip + cap]
+        n = self.submit_packed(batch, arena, align=align, lead=lead, flags=flags)
+        records, total = self.wait_packed(self.last_ticket, n)
+        return arena[:total], records
 
     def wait(self, ticket, n):
         """Waits for the submission `ticket` (see last_ticket) only; returns its (png_size, mode, status) records."""

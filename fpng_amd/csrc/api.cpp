@@ -169,7 +169,7 @@ int fpng_amd::check_dims(uint32_t w, uint32_t h, uint32_t c)
     return FPNG_AMD_OK;
 }
 
-static_assert(kStatusStoredTooLarge == FPNG_AMD_STATUS_STORED_TOO_LARGE, "device status code");
+static_assert(kStatusStoredTooLarge == FPNG_AMD_STATUS_STORED_TOO_LARGE && kStatusArenaFull == FPNG_AMD_STATUS_ARENA_FULL, "device status codes");
 
 int fpng_amd::fail_status(uint32_t status)
 {
@@ -392,6 +392,7 @@ void fpng_amd_encoder_destroy(fpng_amd_encoder *e)
         sl.jobs.release();
         sl.jobs2.release();
         sl.results.release();
+        sl.offsets.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.in) (void)hipEventDestroy(sl.in);
         if (sl.walked) (void)hipEventDestroy(sl.walked);
@@ -515,14 +516,16 @@ static_assert(sizeof(fpng_amd_image_planar) == 56 && offsetof(fpng_amd_image_pla
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
 // ex_images (fpng_amd_encode_submit_ex) or pl_images (fpng_amd_encode_submit_planar) replaces `images` when it is given.
 // ffmt (fpng_amd_encode_submit_planar_float, with pl_images): the planes hold floats of that type; pitches stay bytes.
+// packed (fpng_amd_encode_submit_packed): the records carry no outputs -- pack_place_kernel fills Job::out / out_cap on the device.
 int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const fpng_amd_image *images,
                  const fpng_amd_image_ex *ex_images, const fpng_amd_image_planar *pl_images, uint32_t n, uint32_t flags, Submission &sub,
-                 const fpng_amd_float_format *ffmt = nullptr)
+                 const fpng_amd_float_format *ffmt = nullptr, bool packed = false)
 {
     if (!e || !(images || ex_images || pl_images) || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "batch larger than 65535 images");
     int rc;
     if ((rc = slot.jobs.ensure(n)) || (rc = slot.results.ensure(n))) return rc;
+    if (packed && (rc = slot.offsets.ensure((size_t)n + 2))) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
     const bool two_pass = (flags & FPNG_AMD_ENCODE_SLOWER) && !force_stored;
@@ -585,10 +588,11 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
         }
         const fpng_amd_image &im = (ex_images || pl_images) ? im_of_ex : images[i];
         if ((rc = check_dims(im.w, im.h, im.num_chans))) return rc;
-        if (!im.d_pixels || !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
+        if (packed && (im.d_out || im.out_cap)) return fail(FPNG_AMD_ERR_INVALID_ARG, "packed submission: d_out must be NULL and out_cap 0");
+        if (!im.d_pixels || (!packed && !im.d_out)) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
         if (((uintptr_t)im.d_out & 15) || (!pl_images && im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)))
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
-        if (im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.num_chans))
+        if (!packed && im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.num_chans))
             return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
         Job &j = slot.jobs.p[i];
         std::memset(&j, 0, sizeof j);
@@ -650,7 +654,7 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
 }
 
 int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out,
-           const fpng_amd_image_planar *pl_images = nullptr, const fpng_amd_float_format *ffmt = nullptr)
+           const fpng_amd_image_planar *pl_images = nullptr, const fpng_amd_float_format *ffmt = nullptr, const fpng_amd_pack *pack = nullptr)
 {
     if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
     HIP_TRY(hipSetDevice(e->device));
@@ -675,7 +679,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     hipStream_t s = e->lane_stream[lane];
     fpng_amd_encoder::Scratch &sc = e->sc[lane];
     Submission sub;
-    int rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub, ffmt);
+    int rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub, ffmt, pack != nullptr);
     if (rc) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
@@ -795,7 +799,16 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
             e->prev_walked = slot.walked;
         }
     }
-    launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
+    // a packed submission: scan (sizes only) -> place (offsets from the sizes, Job::out patched on the device) -> heads; the phase
+    // "scan" covers the three
+    if (pack) {
+        PackArgs pa;
+        pa.arena = pack->d_arena, pa.cap = pack->arena_cap;
+        pa.align = pack_align_of(pack->align), pa.lead = pack->lead;
+        pa.d_table = pack->d_table, pa.h_offsets = slot.offsets.p;
+        launch_scan_packed(s, sc.d_jobs.p, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p, pa);
+    } else
+        launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
     if ((rc = mark(e, s, ++ph))) return rc;
     uint32_t *adler_parts = sc.d_partials.p + (size_t)n * sub.max_crc_blocks;
     if (sub.planar_float)
@@ -818,6 +831,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     e->submitted++;
     slot.ticket = e->submitted;
     slot.n = n;
+    slot.packed = pack != nullptr;
     slot.in_flight = true;
     if (ticket_out) *ticket_out = slot.ticket;
     return FPNG_AMD_OK;
@@ -856,6 +870,83 @@ int fpng_amd_encode_submit_planar_float(fpng_amd_encoder *e, const fpng_amd_imag
 {
     if (!images || !fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch or format");
     return submit(e, nullptr, nullptr, n, flags, ticket, images, fmt);
+}
+
+int fpng_amd_encode_submit_packed(fpng_amd_encoder *e, uint32_t desc_kind, const void *images, uint32_t n, const fpng_amd_float_format *fmt,
+                                  uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket)
+{
+    // everything about the arena is checked here, before the encoder is looked at: nothing is launched, no ticket handed out
+    if (desc_kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
+    if (!pack || !pack->d_arena) return fail(FPNG_AMD_ERR_INVALID_ARG, "null pack or d_arena");
+    const uint32_t align = pack_align_of(pack->align);
+    if (!align) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->align must be 0 or a power of two in 16 .. 65536");
+    if (!pack_lead_ok(pack->lead)) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->lead must be a multiple of 16, at most 65536");
+    if ((uintptr_t)pack->d_arena & (align - 1)) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->d_arena must be a multiple of pack->align");
+    if ((uintptr_t)pack->d_table & 7) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->d_table must be 8-byte aligned");
+    if (pack->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->reserved must be 0");
+    if ((desc_kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (fmt != nullptr))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
+    if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    if (desc_kind == FPNG_AMD_DESC_IMAGE) return submit(e, (const fpng_amd_image *)images, nullptr, n, flags, ticket, nullptr, nullptr, pack);
+    if (desc_kind == FPNG_AMD_DESC_EX) return submit(e, nullptr, (const fpng_amd_image_ex *)images, n, flags, ticket, nullptr, nullptr, pack);
+    return submit(e, nullptr, nullptr, n, flags, ticket, (const fpng_amd_image_planar *)images, fmt, pack);
+}
+
+int fpng_amd_encode_wait_packed(fpng_amd_encoder *e, uint64_t ticket, fpng_amd_packed_result *results, uint32_t n, uint64_t *total)
+{
+    if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
+    HIP_TRY(hipSetDevice(e->device));
+    fpng_amd_encoder::Slot *sl = slot_of(e, ticket);
+    if (!sl) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown or expired ticket (records are kept for the last 8 submissions)");
+    if (!sl->packed) return fail(FPNG_AMD_ERR_INVALID_ARG, "not the ticket of a packed submission");
+    if (results && n > sl->n) return fail(FPNG_AMD_ERR_INVALID_ARG, "more results requested than images submitted");
+    if (sl->in_flight) {
+        HIP_TRY(hipEventSynchronize(sl->done));
+        sl->in_flight = false;
+    }
+    if (results)
+        for (uint32_t i = 0; i < n; i++) {
+            results[i].offset = sl->offsets.p[i];
+            results[i].png_size = sl->results.p[i].png_size;
+            results[i].mode = sl->results.p[i].mode;
+            results[i].status = sl->results.p[i].status;
+        }
+    if (total) *total = sl->offsets.p[sl->n];
+    return FPNG_AMD_OK;
+}
+
+int fpng_amd_pack_place(const uint64_t *png_sizes, const uint32_t *statuses, uint32_t n, uint32_t align, uint32_t lead, uint64_t arena_cap,
+                        uint64_t *offsets, uint32_t *statuses_out, uint64_t *total)
+{
+    if (!png_sizes && n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    align = pack_align_of(align);
+    if (!align || !pack_lead_ok(lead)) return fail(FPNG_AMD_ERR_INVALID_ARG, "align: 0 or a power of two in 16 .. 65536; lead: a multiple of 16, at most 65536");
+    uint64_t before = 0, end = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t st_in = statuses ? statuses[i] : 0u;
+        uint64_t off;
+        const uint32_t st = pack_place_one(before, png_sizes[i], st_in, lead, arena_cap, &off);
+        before += pack_stride(png_sizes[i], st_in, align, lead);
+        if (offsets) offsets[i] = off;
+        if (statuses_out) statuses_out[i] = st;
+        if (!st) end = off + png_sizes[i];
+    }
+    if (total) *total = end;
+    return FPNG_AMD_OK;
+}
+
+size_t fpng_amd_pack_capacity(const uint32_t *w, const uint32_t *h, const uint32_t *num_chans, uint32_t n, uint32_t align, uint32_t lead)
+{
+    align = pack_align_of(align);
+    if (!align || !pack_lead_ok(lead) || ((!w || !h || !num_chans) && n)) return 0;
+    // the cursor behind the last file: the strides in front of it, its lead and its extent
+    uint64_t before = 0, cursor = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t size = fpng_amd_max_encoded_size(w[i], h[i], num_chans[i]);
+        cursor = before + lead + pack_extent(size);
+        before += pack_stride(size, 0, align, lead);
+    }
+    return (size_t)cursor;
 }
 
 int fpng_amd_quantize_float(const void *src, uint32_t dtype, float scale, float bias, uint8_t *dst, size_t n)

@@ -164,6 +164,8 @@ struct fpng_amd_encoder {
     struct Slot {
         PinnedBuf<Job> jobs, jobs2; // jobs2: the second upload of 2-pass (tables patched)
         PinnedBuf<Result> results;
+        PinnedBuf<uint64_t> offsets; // packed submissions: n offsets, total, files placed -- written by pack_place_kernel
+        bool packed = false;
         hipEvent_t in = nullptr;     // recorded on the caller's stream: the inputs are ready
         hipEvent_t walked = nullptr; // recorded after the row walk
         hipEvent_t done = nullptr;   // recorded on the lane: PNGs and result records are complete

@@ -1,6 +1,7 @@
 // kernels.h -- host/device shared structures and kernel launchers (internal).
 #pragma once
 #include "format.h"
+#include "pack.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -63,8 +64,13 @@ struct JobState {
 };
 
 // JobState::status: a stored outcome whose 58 + zlib_size exceeds UINT32_MAX (FPNG_AMD_STATUS_STORED_TOO_LARGE): scan_kernel decides
-// it, and assemble / stored_ex / finalize then write nothing of that file
+// it, and assemble / stored_ex / finalize then write nothing of that file.  (kStatusArenaFull = 2, packed submissions: pack.h)
 constexpr uint32_t kStatusStoredTooLarge = 1;
+// JobState::zlib_size of a file of a packed submission that is refused (by pack_place_kernel, or by the scan before it).  assemble_kernel has no look at the status on its way to a compressed file's
+// rows (before packed submissions only stored files could be refused), but it leaves -- as the stored forms and crc_kernel do -- when
+// its range holds nothing of the data [58, 58 + zlib_size - 4): with this value that interval is [58, 0), empty for every range, so
+// no workgroup gets as far as Job::out, which such a file does not have.  (Modulo 2^64: 58 + kZlibSizeNoFile - 4 == 0.)
+constexpr uint64_t kZlibSizeNoFile = (uint64_t)4 - kPngHeaderBytes;
 
 struct Result {
     uint64_t png_size;
@@ -88,6 +94,18 @@ void build_crc_device_tables(CrcDeviceTables *t);
 
 void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist);
 void launch_scan(hipStream_t s, const Job *jobs, uint32_t n_jobs, const RowInfo *rows, uint64_t *row_off, JobState *states);
+// fpng_amd_encode_submit_packed: the scan without the heads (the jobs have no `out` yet), then pack_place_kernel -- one workgroup:
+// the rule of pack.h over the sizes the scan decided; it patches jobs[i].out / out_cap and refuses (JobState::status =
+// kStatusArenaFull, JobState::zlib_size = kZlibSizeNoFile) what finds no room -- and pack_heads_kernel, which writes the heads of
+// the placed files.  Three launches.  assemble / stored_* / finalize behind them are the ones every submission runs.
+struct PackArgs {
+    uint8_t *arena;
+    uint64_t cap;
+    uint32_t align, lead; // align: the effective one (pack_align_of)
+    uint64_t *d_table;    // device, 2 * (n + 1) words, or NULL
+    uint64_t *h_offsets;  // pinned host memory (device-visible), n + 2 words: the files' offsets, total, files placed
+};
+void launch_scan_packed(hipStream_t s, Job *jobs, uint32_t n_jobs, const RowInfo *rows, uint64_t *row_off, JobState *states, const PackArgs &pa);
 // chan_mask: bit 0 = the batch has 3-channel jobs, bit 1 = 4-channel jobs (one kernel instantiation each)
 // wide4: the 4-channel jobs' pixels lie mostly in rows of kWideRowPixels and more (their walk then runs with seven waves per SIMD instead of eight: kernels.hip)
 constexpr uint32_t kWideRowPixels = 3584; // (same-box A/B: 3840-pixel rows gain with six waves, 3072-pixel rows lose 1 % in 1-pass)

@@ -1328,6 +1328,28 @@ template <typename P> __device__ __forceinline__ void store_be32(P p, uint32_t v
     p[3] = (uint8_t)v;
 }
 
+// The head of a file or of a first band's window: PNG header, Deflate prefix, zeros up to the next 16-byte boundary (assemble_kernel,
+// which places the rows, wants them there) and the IDAT length.  All NT threads of the block call it (thread t of them).
+template <uint32_t NT>
+__device__ __forceinline__ void write_head(const Job &job, const TokenTable *tab, bool stored, uint64_t zlib_size, uint32_t t)
+{
+    gptr_u8 out = to_global<gptr_u8>(job.out);
+    if (job.whole_png)
+        for (uint32_t i = t; i < kPngHeaderBytes; i += NT)
+            if (i < 50 || i >= 54) out[i] = job.png_header[i];
+    gptr_u8 zl = out + (job.bit_bias >> 3); // zlib byte 0 (only meaningful for the first band / whole image)
+    if (!stored && job.is_first) {
+        const uint32_t head_bytes = (tab->header_bits + 7) >> 3; // (the last one holds the pending bits in front of the first token)
+        for (uint32_t i = t; i < head_bytes; i += NT) zl[i] = tab->header[i];
+        const uint32_t head_end = kPngHeaderBytes + head_bytes;
+        for (uint32_t i = head_end + t; i < ((head_end + 15u) & ~15u); i += NT) out[i] = 0;
+    }
+    if (t == 0 && job.whole_png) store_be32(out + 50, (uint32_t)zlib_size); // IDAT length (reference fpng.cpp:1782)
+}
+
+// PACKED: a job of a packed submission (fpng_amd_encode_submit_packed) has no `out` yet -- pack_place_kernel decides it from the sizes
+// this kernel leaves -- so it stops in front of the head, like a band's counting phase; pack_heads_kernel writes the head later
+template <bool PACKED = false>
 __device__ __forceinline__ void scan_job(const Job &job, JobState &st, const RowInfo *rows, uint64_t *row_off, uint32_t n_jobs,
                                          uint64_t (*wsum)[kScanWaves] /* LDS [3][kScanWaves] */)
 {
@@ -1443,22 +1465,10 @@ __device__ __forceinline__ void scan_job(const Job &job, JobState &st, const Row
     }
     // a band's counting phase stops here; whole images and band placements prepare the head of the output
     if (!job.whole_png && !(job.flags & 0x100u)) return;
-    if (too_large) return;
+    if (PACKED || too_large) return;
 
-    // --- PNG header + Deflate block header; assemble_kernel, which places the rows, wants the head followed by zeros
-    //     up to the next 16-byte boundary ---
-    gptr_u8 out = to_global<gptr_u8>(job.out);
-    if (job.whole_png)
-        for (uint32_t i = t; i < kPngHeaderBytes; i += kScanBlock)
-            if (i < 50 || i >= 54) out[i] = job.png_header[i];
-    gptr_u8 zl = out + (job.bit_bias >> 3); // zlib byte 0 (only meaningful for the first band / whole image)
-    if (!stored && job.is_first) {
-        const uint32_t head_bytes = (tab->header_bits + 7) >> 3; // (the last one holds the pending bits in front of the first token)
-        for (uint32_t i = t; i < head_bytes; i += kScanBlock) zl[i] = tab->header[i];
-        const uint32_t head_end = kPngHeaderBytes + head_bytes;
-        for (uint32_t i = head_end + t; i < ((head_end + 15u) & ~15u); i += kScanBlock) out[i] = 0;
-    }
-    if (t == 0 && job.whole_png) store_be32(out + 50, (uint32_t)zlib_size); // IDAT length (reference fpng.cpp:1782)
+    // --- PNG header + Deflate block header ---
+    write_head<kScanBlock>(job, tab, stored, zlib_size, t);
 }
 
 // scan_kernel: one block per job (whole images; row bands: counting phase and placement phase)
@@ -1466,6 +1476,102 @@ __global__ __launch_bounds__(kScanBlock) void scan_kernel(const Job *jobs, const
 {
     __shared__ uint64_t wsum[3][kScanWaves];
     scan_job(jobs[blockIdx.x], states[blockIdx.x], rows, row_off, gridDim.x, wsum);
+}
+// ... of a packed submission: everything but the head (there is no `out` yet)
+__global__ __launch_bounds__(kScanBlock) void scan_packed_kernel(const Job *jobs, const RowInfo *rows, uint64_t *row_off, JobState *states)
+{
+    __shared__ uint64_t wsum[3][kScanWaves];
+    scan_job<true>(jobs[blockIdx.x], states[blockIdx.x], rows, row_off, gridDim.x, wsum);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Packed submissions: the chain is rows -> scan -> PLACE -> HEADS -> assemble -> finalize.
+//
+// pack_place_kernel: ONE workgroup per submission.  It reads the sizes and statuses scan_packed_kernel left in states[], applies the
+// placement rule of pack.h -- an exclusive prefix sum of the files' strides: wave scan, LDS across the waves, a carry from one
+// round of kPlaceBlock files to the next, so n has no upper bound -- and
+//   - patches jobs[i].out / out_cap IN DEVICE MEMORY: assemble_kernel, the stored forms and finalize_kernel read them from there;
+//   - sets states[i].status = kStatusArenaFull for a file that found no room, and the zlib_size of every refused file to
+//     kZlibSizeNoFile: the stored forms and finalize_kernel leave at the status, assemble_kernel because no range of such a file
+//     holds data -- nothing of it is written, and nothing is read through the `out` it does not have;
+//   - leaves {offset, png_size} per file and {total, files placed} behind them in d_table (optional) and the offsets, total and
+//     count in the slot's pinned host memory (h_offsets: n + 2 words).
+// pack_heads_kernel (grid n, one wave each) then writes the heads.  Two small kernels, not one: a single launch with grid n would
+// have every workgroup either redo the prefix in front of its file (n^2 / 2 loads: seconds at n = 65535) or wait for workgroup 0's
+// result, and a wait on another workgroup of the same launch only ends if that one gets to run.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kPlaceBlock = 256, kPlaceWaves = kPlaceBlock / kWave;
+
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o)
+{
+    return ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, kWave) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o, kWave);
+}
+
+__global__ __launch_bounds__(kPlaceBlock) void pack_place_kernel(Job *jobs, JobState *states, uint32_t n, const PackArgs pa)
+{
+    __shared__ uint64_t wsum[kPlaceWaves];
+    __shared__ uint64_t wend[kPlaceWaves];
+    __shared__ uint32_t wcnt[kPlaceWaves];
+    const uint32_t t = threadIdx.x, lane = t & 63, wv = uniform(t >> 6);
+    uint64_t carry = 0;  // strides of the rounds so far (the same in every thread)
+    uint64_t my_end = 0; // end of the last file this thread placed
+    uint32_t my_cnt = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += kPlaceBlock) {
+        const uint32_t i = i0 + t;
+        const bool valid = i < n;
+        const uint32_t status_in = valid ? states[i].status : 1u;
+        const uint64_t png_size = kPngHeaderBytes + (valid ? states[i].zlib_size : 0u) + kPngTrailerBytes;
+        const uint64_t stride = pack_stride(png_size, status_in, pa.align, pa.lead);
+        uint64_t wave_total;
+        const uint64_t excl = wave_exclusive_sum_u64(stride, lane, wave_total);
+        if (lane == 0) wsum[wv] = wave_total;
+        __syncthreads();
+        uint64_t before = 0, round = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kPlaceWaves; k++) {
+            const uint64_t v = wsum[k];
+            if (k < wv) before += v;
+            round += v;
+        }
+        __syncthreads(); // (wsum is written again in the next round)
+        if (valid) {
+            uint64_t off;
+            const uint32_t status = pack_place_one(carry + before + excl, png_size, status_in, pa.lead, pa.cap, &off);
+            const uint64_t size = status ? 0u : png_size;
+            if (status != status_in) states[i].status = status;
+            if (status) states[i].zlib_size = kZlibSizeNoFile; // (kernels.h: no range of it holds data; a file refused by the scan has no `out` here either)
+            jobs[i].out = status ? nullptr : pa.arena + off;
+            jobs[i].out_cap = status ? 0u : pack_extent(png_size);
+            pa.h_offsets[i] = off;
+            if (pa.d_table) pa.d_table[2 * (size_t)i] = off, pa.d_table[2 * (size_t)i + 1] = size;
+            if (!status) my_end = off + size, my_cnt++; // (offsets grow with i)
+        }
+        carry += round;
+    }
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const uint64_t v = shfl_xor_u64(my_end, o);
+        my_end = v > my_end ? v : my_end;
+    }
+    my_cnt = wave_sum(my_cnt);
+    if (lane == 0) wend[wv] = my_end, wcnt[wv] = my_cnt;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t total = 0;
+        uint32_t cnt = 0;
+        for (uint32_t k = 0; k < kPlaceWaves; k++) total = wend[k] > total ? wend[k] : total, cnt += wcnt[k];
+        pa.h_offsets[n] = total, pa.h_offsets[(size_t)n + 1] = cnt;
+        if (pa.d_table) pa.d_table[2 * (size_t)n] = total, pa.d_table[2 * (size_t)n + 1] = cnt;
+    }
+}
+
+// the heads of the files pack_place_kernel found room for: one wave per file
+__global__ __launch_bounds__(kWave) void pack_heads_kernel(const Job *jobs, const JobState *states)
+{
+    const Job &job = jobs[blockIdx.x];
+    const JobState &st = states[blockIdx.x];
+    if (uniform(st.status)) return;
+    write_head<kWave>(job, job.table, uniform(st.mode) != 0u, st.zlib_size, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2655,6 +2761,12 @@ void launch_hist_first(hipStream_t s, const Job &job, Job *d_job, uint32_t *hist
 void launch_scan(hipStream_t s, const Job *jobs, uint32_t n_jobs, const RowInfo *rows, uint64_t *row_off, JobState *states)
 {
     hipLaunchKernelGGL(scan_kernel, dim3(n_jobs), dim3(kScanBlock), 0, s, jobs, rows, row_off, states);
+}
+void launch_scan_packed(hipStream_t s, Job *jobs, uint32_t n_jobs, const RowInfo *rows, uint64_t *row_off, JobState *states, const PackArgs &pa)
+{
+    hipLaunchKernelGGL(scan_packed_kernel, dim3(n_jobs), dim3(kScanBlock), 0, s, (const Job *)jobs, rows, row_off, states);
+    hipLaunchKernelGGL(pack_place_kernel, dim3(1), dim3(kPlaceBlock), 0, s, jobs, states, n_jobs, pa);
+    hipLaunchKernelGGL(pack_heads_kernel, dim3(n_jobs), dim3(kWave), 0, s, (const Job *)jobs, (const JobState *)states);
 }
 void launch_build_dynamic(hipStream_t s, const Job *jobs, uint32_t n_jobs, const uint32_t *hist, TokenTable *tables, uint32_t rezero)
 {

@@ -577,6 +577,63 @@ int fpng_amd_encode_submit_planar_float(fpng_amd_encoder *enc, const fpng_amd_im
 /* The rule above on the HOST, over the text the kernels compile (csrc/quantize.h): dst[i] = byte of element i of src (n elements of
  * FPNG_AMD_F32 / _F16 / _BF16) with one scale and bias.  For tests and for callers that want to predict a file's bytes. */
 int fpng_amd_quantize_float(const void *src, uint32_t dtype, float scale, float bias, uint8_t *dst, size_t n);
+/* ---- a submission's files back to back in ONE caller-supplied device arena, placed on the GPU from their actual sizes -- what a
+ *      shard or record writer wants: one device-to-host copy of `total` bytes and one write() instead of n worst-case buffers, n
+ *      copies and a host round trip for the sizes; and a consumer on the same stream (fpng_amd_encoder_join) finds every file's
+ *      offset and size in device memory (d_table) without the host in between.
+ *      One entry point for the four descriptor kinds: `images` is an array of n records of the type desc_kind names; their d_out must
+ *      be NULL and their out_cap 0 (the per-image out_cap >= fpng_amd_max_encoded_size() rule does not apply: the arena's room is
+ *      checked per file on the device).  fmt: for FPNG_AMD_DESC_PLANAR_FLOAT, else NULL.  Every other rule of the kind's own submit
+ *      call holds unchanged, and the files are byte for byte the ones it writes.
+ *      PLACEMENT RULE (csrc/pack.h: the text the kernel and fpng_amd_pack_place both compile), files in descriptor order:
+ *          cursor = 0
+ *          a file whose status is not 0 before placement (FPNG_AMD_STATUS_STORED_TOO_LARGE): offset 0, size 0, the cursor stays
+ *          offset_i = round_up(cursor, align) + lead          the lead region starts at a multiple of align, the file behind it
+ *          extent_i = round_up(png_size_i + E, 16)             E = 0: the chain touches no byte behind png_size (see csrc/pack.h)
+ *          cursor   = offset_i + extent_i                      whether or not the file fits
+ *          offset_i + extent_i <= arena_cap: the file lies at d_arena + offset_i; else status FPNG_AMD_STATUS_ARENA_FULL, offset 0,
+ *          size 0, and -- the cursor never goes back -- every later file is refused as well
+ *          total = offset + png_size of the last file placed; 0 when none was
+ *      GUARANTEE: arena bytes outside the placed files' [offset_i, offset_i + extent_i) are never written: not the lead regions, not
+ *      the alignment gaps, nothing from the first refused file's would-be place on.  Inside an extent the bytes behind png_size are
+ *      not written either (E = 0), but only the extent is promised.
+ *      d_table (optional, DEVICE): 2 * (n + 1) 64-bit words -- {offset, png_size} per file, then {total, files placed} -- complete
+ *      when the submission is (written in front of the files' bytes, by the placement kernel).
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched, no ticket handed out and the encoder as it was: an unknown desc_kind; a null
+ *      pack or d_arena; align that is not 0 or a power of two in 16 .. 65536; lead that is not a multiple of 16 or exceeds 65536;
+ *      d_arena not a multiple of align; d_table not a multiple of 8; reserved != 0; a descriptor with d_out != NULL or out_cap != 0;
+ *      fmt given for another kind than PLANAR_FLOAT, or missing for it.
+ *      The ticket works with fpng_amd_encode_wait (sizes without offsets) / _query / _finish / _join like any other;
+ *      fpng_amd_encode_wait_packed on a ticket that was not packed: FPNG_AMD_ERR_INVALID_ARG.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encode_submit_packed with dlsym. ---- */
+#define FPNG_AMD_DESC_IMAGE 0u        /* fpng_amd_image */
+#define FPNG_AMD_DESC_EX 1u           /* fpng_amd_image_ex */
+#define FPNG_AMD_DESC_PLANAR 2u       /* fpng_amd_image_planar */
+#define FPNG_AMD_DESC_PLANAR_FLOAT 3u /* fpng_amd_image_planar + fpng_amd_float_format */
+typedef struct fpng_amd_pack {
+    uint8_t *d_arena;   /* DEVICE, a multiple of `align` */
+    uint64_t arena_cap; /* bytes */
+    uint32_t align;     /* power of two, 16 .. 65536; 0 = 16 */
+    uint32_t lead;      /* bytes left untouched in front of every file (a container header's room): multiple of 16, <= 65536 */
+    uint64_t *d_table;  /* optional DEVICE, 8-byte aligned, 2 * (n + 1) words */
+    uint64_t reserved;  /* 0 */
+} fpng_amd_pack; /* 40 bytes */
+typedef struct fpng_amd_packed_result {
+    uint64_t offset, png_size;
+    uint32_t mode, status;
+} fpng_amd_packed_result; /* 24 bytes */
+#define FPNG_AMD_STATUS_ARENA_FULL 2u
+int fpng_amd_encode_submit_packed(fpng_amd_encoder *enc, uint32_t desc_kind, const void *images, uint32_t n,
+                                  const fpng_amd_float_format *fmt, uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket);
+/* results (n <= the submission's images) and total may be NULL */
+int fpng_amd_encode_wait_packed(fpng_amd_encoder *enc, uint64_t ticket, fpng_amd_packed_result *results, uint32_t n, uint64_t *total);
+/* The placement rule on the HOST: what the GPU does for these sizes.  statuses (may be NULL = all 0): the files' statuses before
+ * placement.  offsets, statuses_out and total may be NULL.  FPNG_AMD_ERR_INVALID_ARG for an align or lead the submit call refuses. */
+int fpng_amd_pack_place(const uint64_t *png_sizes, const uint32_t *statuses, uint32_t n, uint32_t align, uint32_t lead,
+                        uint64_t arena_cap, uint64_t *offsets, uint32_t *statuses_out, uint64_t *total);
+/* The arena size with which nothing can be refused: the cursor after placing n files of fpng_amd_max_encoded_size() each
+ * (0 for an invalid align or lead). */
+size_t fpng_amd_pack_capacity(const uint32_t *w, const uint32_t *h, const uint32_t *num_chans, uint32_t n, uint32_t align, uint32_t lead);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

@@ -72,6 +72,13 @@ class FloatFormat(C.Structure):  # fpng_amd_float_format: 40 bytes
 F32, F16, BF16 = 0, 1, 2  # FPNG_AMD_F32 / _F16 / _BF16
 
 
+class Crop(C.Structure):  # fpng_amd_crop: 16 bytes, in pixels of the file, top-down
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
+
+
+DECODE_CROP_OUTSIDE = 67  # FPNG_AMD_DECODE_CROP_OUTSIDE: a file's status when its crop leaves the image
+
+
 class Pack(C.Structure):  # fpng_amd_pack: 40 bytes
     _fields_ = [("d_arena", C.c_void_p), ("arena_cap", C.c_uint64), ("align", C.c_uint32), ("lead", C.c_uint32), ("d_table", C.c_void_p),
                 ("reserved", C.c_uint64)]
@@ -182,6 +189,9 @@ SIGNATURES = {
     "fpng_amd_decode_batch_device_planar": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_planar_float": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_planar_float": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_planar_crop": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_crop": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),
     "fpng_amd_encoder_decode_verify": (_u32, [_vp]),
     "fpng_amd_decode_last_phase_ms": (_int, [_vp, C.POINTER(C.c_float * 4)]),

@@ -32,6 +32,8 @@ STATUS_STORED_TOO_LARGE, STATUS_ARENA_FULL = 1, 2
 # Encoder.set_decode_verify (FPNG_AMD_VERIFY_* in include/fpng_amd.h) and the two statuses only a checked decode returns
 VERIFY_CRC32, VERIFY_ADLER32 = 1, 2
 DECODE_BAD_CRC32, DECODE_BAD_ADLER32 = 65, 66
+# a file's status when its crop leaves the image (Encoder.decode_device_crop; FPNG_AMD_DECODE_CROP_OUTSIDE)
+DECODE_CROP_OUTSIDE = _lib.DECODE_CROP_OUTSIDE
 
 # source formats of Encoder.submit_ex (FPNG_AMD_SRC_* in include/fpng_amd.h): name -> (value, source bytes per pixel, PNG channels)
 SRC_FORMATS = {"RGB": (0, 3, 3), "BGR": (1, 3, 3), "RGBA": (2, 4, 4), "BGRA": (3, 4, 4), "ARGB": (4, 4, 4), "ABGR": (5, 4, 4),
@@ -254,6 +256,18 @@ def _float_constants(who, make, mean, std, scale, bias):
     if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(bi))):
         raise ValueError(f"{who}: scale and bias must be finite")
     return sc, bi
+
+
+def crop_tiles(file_w, file_h, crop):
+    """fpng_amd_decode_crop_tiles: (n_segments, first_col_block, n_col_blocks) -- the tiles of the decoder's pixel pass (segments of
+    48 rows x column blocks of 256 pixels) that a crop (x, y, w, h) of a file_w x file_h file needs: segments 0 .. n_segments - 1
+    of the column blocks first_col_block .. first_col_block + n_col_blocks - 1.  No GPU needed.  An empty crop or one that
+    leaves the image raises FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
+    x, y, w, h = (int(v) for v in crop)
+    c = _lib.Crop(x, y, w, h)
+    nseg, first, ncb = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(_lib.load().fpng_amd_decode_crop_tiles(int(file_w), int(file_h), C.byref(c), C.byref(nseg), C.byref(first), C.byref(ncb)))
+    return nseg.value, first.value, ncb.value
 
 
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
@@ -525,6 +539,16 @@ class DecodeBatchFloat(_DecodeBatchViews):
     def __init__(self, pngs, outs, arr, res, device_data, keep, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
         self.fmt = fmt
+
+
+class DecodeBatchCrop(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_crop() returns: the same for one fpng_amd_decode_batch(_device)_planar_crop() call (crops: the
+    fpng_amd_crop[n]; outs: the caller's (c, crop h, crop w) views, uint8 or all of one float dtype; fmt: the call's
+    fpng_amd_float_format, None for uint8 planes).  No other call takes this descriptor."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, crops, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.crops, self.fmt = crops, fmt
 
 
 class Encoder:
@@ -945,8 +969,8 @@ class Encoder:
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat)):
-            raise ValueError("decode_device_ex: a planar or float descriptor (decode_device_planar, decode_device_float)")
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop)):
+            raise ValueError("decode_device_ex: a planar, float or crop descriptor (decode_device_planar, decode_device_float, decode_device_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if not batch.device_data:
             raise ValueError("decode_device_ex: the files are in host memory (decode_batch_ex)")
@@ -957,8 +981,8 @@ class Encoder:
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat)):
-            raise ValueError("decode_batch_ex: a planar or float descriptor (decode_batch_planar, decode_batch_float)")
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop)):
+            raise ValueError("decode_batch_ex: a planar, float or crop descriptor (decode_batch_planar, decode_batch_float, decode_batch_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if batch.device_data:
             raise ValueError("decode_batch_ex: the files are in device memory (decode_device_ex)")
@@ -1001,6 +1025,8 @@ class Encoder:
             raise ValueError(f"{who}: a make_decode_batch_ex() descriptor (decode_device_ex / decode_batch_ex)")
         if isinstance(pngs, DecodeBatchFloat):
             raise ValueError(f"{who}: a make_decode_batch_float() descriptor (decode_device_float / decode_batch_float)")
+        if isinstance(pngs, DecodeBatchCrop):
+            raise ValueError(f"{who}: a make_decode_batch_crop() descriptor (decode_device_crop / decode_batch_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchPlanar) else self.make_decode_batch_planar(pngs, outs, order, bottom_up)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_planar)" if device_data else "device memory (decode_device_planar)"))
@@ -1059,7 +1085,7 @@ class Encoder:
         return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt)
 
     def _decode_float(self, who, fn, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_float() makes this one's)")
         batch = pngs if isinstance(pngs, DecodeBatchFloat) else self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias)
         if batch.device_data != device_data:
@@ -1080,6 +1106,97 @@ class Encoder:
     def decode_batch_float(self, pngs, outs=None, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
         """fpng_amd_decode_batch_planar_float: decode_device_float() for files in host memory (bytes)."""
         return self._decode_float("decode_batch_float", self.lib.fpng_amd_decode_batch_planar_float, False, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
+
+    @staticmethod
+    def make_decode_batch_crop(pngs, crops, outs, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+        """Descriptor (fpng_amd_png_planar[n], fpng_amd_crop[n], the fpng_amd_float_format if any and the result records) for
+        decode_device_crop() / decode_batch_crop(): the files as for make_decode_batch_planar(); crops: a sequence of (x, y, w, h)
+        in pixels of each file, top-down; outs: (c, h, w) tensor VIEWS whose (h, w) is the crop's (ValueError otherwise) -- uint8
+        views, described by dest_layout_planar() (mean / std / scale / bias must then be absent), or float32 / float16 / bfloat16
+        views of ONE dtype, described by dest_layout_float() with the constants of make_decode_batch_float().  Element (c, j, i) is
+        what the full call writes at (c, y + j, x + i).  A crop that leaves its file's image is that file's status
+        (DECODE_CROP_OUTSIDE), found by the call; pixels_cap is the view's own span in bytes."""
+        n = len(pngs)
+        if len(crops) != n or len(outs) != n:
+            raise ValueError(f"make_decode_batch_crop: {n} files, {len(crops)} crops, {len(outs)} destinations")
+        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"make_decode_batch_crop: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        is_u8 = dtypes == {torch.uint8}
+        fmt = None
+        if is_u8:
+            if any(v is not None for v in (mean, std, scale, bias)):
+                raise ValueError("make_decode_batch_crop: mean / std / scale / bias go with float destinations, not uint8 ones")
+        else:
+            sc, bi = _float_constants("make_decode_batch_crop", normalize_constants, mean, std, scale, bias)
+            fmt = _lib.FloatFormat()
+            for k in range(4):
+                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        arr = (_lib.PngPlanarIn * n)()
+        carr = (_lib.Crop * n)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        for i, (p, t) in enumerate(zip(pngs, outs)):
+            if is_u8:
+                ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
+            else:
+                ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
+            x, y, w, h = (int(v) for v in crops[i])
+            if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
+                raise ValueError(f"make_decode_batch_crop: crop {tuple(crops[i])} of file {i} (four values of 32 bits, not negative)")
+            c, th, tw = t.shape
+            if (th, tw) != (h, w):
+                raise ValueError(f"make_decode_batch_crop: destination {i} is {tw} x {th}, its crop {w} x {h}")
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError("make_decode_batch_crop: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            carr[i].x, carr[i].y, carr[i].w, carr[i].h = x, y, w, h
+            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
+            arr[i].pixels_cap = (c - 1) * abs(pp) + (h - 1) * abs(rp) + w * t.element_size()  # (the view's own spans, in bytes)
+        return DecodeBatchCrop(list(pngs), list(outs), arr, res, device_data, keep, carr, fmt)
+
+    def _decode_crop(self, who, fn, device_data, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat)):
+            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_crop() makes this one's)")
+        if isinstance(pngs, DecodeBatchCrop):
+            batch = pngs
+        else:
+            if outs is None:  # (c = 3 planes of the crop's size each; files with alpha lose it)
+                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
+                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+                outs = [torch.empty((3, int(c[3]), int(c[2])), dtype=dtype, device=f"cuda:{self.device}") for c in crops]
+            batch = self.make_decode_batch_crop(pngs, crops, outs, order, bottom_up, mean, std, scale, bias)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_crop)" if device_data else "device memory (decode_device_crop)"))
+        if not all(t.is_cuda for t in batch.outs):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, batch.crops, len(batch.arr), C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_crop(self, pngs, crops=None, outs=None, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None,
+                           results=True):
+        """fpng_amd_decode_batch_device_planar_crop: uint8 CUDA tensors holding whole files, of each of which the crop (x, y, w, h)
+        is decoded into the caller's (c, h, w) device tensor view in place (make_decode_batch_crop() has the rules) -> list of
+        (status, the caller's view or None, channels_in_file) -- without the full decode and the t[:, y:y+h, x:x+w].contiguous()
+        copy behind it.  outs=None allocates (3, h, w) tensors of `dtype` (default torch.uint8).  pngs may be a
+        make_decode_batch_crop() descriptor of device files (crops = outs = None); results=False returns the descriptor."""
+        return self._decode_crop("decode_device_crop", self.lib.fpng_amd_decode_batch_device_planar_crop, True, pngs, crops, outs, dtype, order, bottom_up,
+                                 mean, std, scale, bias, results)
+
+    def decode_batch_crop(self, pngs, crops=None, outs=None, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None,
+                          results=True):
+        """fpng_amd_decode_batch_planar_crop: decode_device_crop() for files in host memory (bytes)."""
+        return self._decode_crop("decode_batch_crop", self.lib.fpng_amd_decode_batch_planar_crop, False, pngs, crops, outs, dtype, order, bottom_up,
+                                 mean, std, scale, bias, results)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

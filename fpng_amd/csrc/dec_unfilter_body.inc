@@ -11,6 +11,11 @@
 //                      hold elements of that type, fmaf(value, flt.scale[c], flt.bias[c]) of the file's channel c; -1 in the kernels
 //                      that were there before, whose instructions it leaves alone
 //   flt                DecFloat, a kernel argument: wave-uniform (kFloat >= 0; else an empty constant that is never read)
+//   kCrop              constexpr bool (kPlanar): the planes hold a crop of the file (fpng_amd_decode_batch_planar_crop) -- the plan numbers only
+//                      the tiles the crop needs (dec_crop_tiles; all of them where kVerify), tiles and waves that hold none of its
+//                      pixels leave once their look-back granules are published, and the last stage clips to the crop; false in the
+//                      kernels that were there before, whose instructions it leaves alone
+//   crops              const DecCrop *, a record per file of `jobs` (kCrop; else a null constant that is never read)
 // and the kernel's arguments jobs, plan, placed, item0, status, epoch, skip_mask.
     __shared__ __attribute__((aligned(16))) uint8_t tile_mem[kUnfRows * kTilePitch];
     __shared__ uint32_t mask_mem[kUnfRows * kRowMaskWords], epx_mem[kUnfRows]; // the rows' marked pixels (long matches), their entry pixels
@@ -68,7 +73,16 @@
             fidx = lo, cb0 = plan.cbpre[lo];
         }
         const uint32_t rel = item - pc.item0, sg = uni32(pc.seg0 + rel / per_seg), within = rel % per_seg;
-        const uint32_t ji = ji_w != 0xFFFFFFFFu ? ji_w : uni32(plan.order[fidx]), cb = uni32(within - cb0);
+        const uint32_t ji = ji_w != 0xFFFFFFFFu ? ji_w : uni32(plan.order[fidx]);
+        // (kCrop: the crop's four words, wave-uniform like the job's; the plan counts column blocks from the crop's first one --
+        //  from the file's where every tile runs for the Adler-32)
+        static_assert(!kCrop || kPlanar, "crops are planar destinations");
+        DecCrop crop = {};
+        if constexpr (kCrop) {
+            crop = crops[ji];
+            crop.x = uni32(crop.x), crop.y = uni32(crop.y), crop.w = uni32(crop.w), crop.h = uni32(crop.h);
+        }
+        const uint32_t cb = uni32(within - cb0) + (kCrop && !kVerify ? dec_crop_first_block(crop.x) : 0u);
         // (the file's record, read by every lane, into scalar registers: the compiler keeps what it loads from writable global
         //  memory in vector registers, and every address derived from it would cost a register pair per row)
         DecJob job = jobs[ji];
@@ -203,6 +217,12 @@
                     __hip_atomic_store(mine, ((unsigned long long)(epoch << 2 | 2u) << 32) | add_bytes(carry, p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
+        if constexpr (kCrop) {
+            // (published: nothing below waits for this tile any more.  A tile above or below the crop's rows has no pixels to write,
+            //  nor has a wave whose 64 pixels lie beside its columns -- the whole wave leaves, its lanes are each other's sources)
+            if (y0 + nrows <= crop.y || y0 >= crop.y + crop.h) return;
+            if (wave_px >= crop.x + crop.w || wave_px + (uint32_t)kWave <= crop.x) return;
+        }
         // ---- the pixels.  Dword stores at any byte address (rows of 3-channel pixels start anywhere; the hardware takes
         //      unaligned dwords, as it does for the loads above); bytes only where a row ends inside a dword ----
         FPNG_TILE_STAMP(3);
@@ -227,13 +247,52 @@
             else ch = lane & 3u, x = wave_px + (lane & ~3u);
             const uint32_t nb = (ch < dc && x < job.w) ? min(4u, job.w - x) : 0u;
             constexpr uint32_t kElem = kFloat < 0 ? 1u : dec_float_bytes((uint32_t)kFloat); // bytes of a plane's element (the pitches are bytes)
-            gu8 *pb = (gu8 *)(uintptr_t)(job.out + (int64_t)ch * pp + (int64_t)y0 * job.pitch + (int64_t)x * kElem);
+            // (kCrop: the destination's row 0 is the file's row crop.y, its column 0 the file's column crop.x -- both differences may
+            //  be negative here, the clipping below keeps every store inside; keep: bit e = the lane's pixel x + e lies in the crop's
+            //  columns, cut at BOTH ends; k_lo .. k_hi: the tile's rows that lie in the crop's)
+            gu8 *pb = (gu8 *)(uintptr_t)(job.out + (int64_t)ch * pp + ((int64_t)y0 - (int64_t)crop.y) * job.pitch + ((int64_t)x - (int64_t)crop.x) * kElem);
+            uint32_t keep = 0;
+            if constexpr (kCrop) {
+                const uint32_t c_lo = max(x, crop.x) - x, c_hi = min(x + 4u, crop.x + crop.w) - x; // (the wave meets the crop; a lane beside it: c_lo >= c_hi, mod 2^32)
+                if (ch < dc && x < crop.x + crop.w && x + 4u > crop.x) keep = (0xFu << c_lo) & (0xFu >> (4u - c_hi));
+            }
+            const uint32_t k_lo = kCrop ? max(crop.y, y0) - y0 : 0u, k_hi = kCrop ? min(crop.y + crop.h, y0 + nrows) - y0 : nrows;
             // (kFloat: the lane's channel's two constants, picked once from the four pairs in scalar registers)
             const float fs = kFloat < 0 ? 0.f : (ch == 0 ? flt.scale[0] : (ch == 1 ? flt.scale[1] : (ch == 2 ? flt.scale[2] : flt.scale[3])));
             const float fb = kFloat < 0 ? 0.f : (ch == 0 ? flt.bias[0] : (ch == 1 ? flt.bias[1] : (ch == 2 ? flt.bias[2] : flt.bias[3])));
             auto put = [&](uint32_t k, uint32_t d) {
                 gu8 *q = pb + (int64_t)k * job.pitch;
-                if constexpr (kFloat >= 0) {
+                if constexpr (kCrop) {
+                    // a whole quad as one store, as below; a quad cut at the front or the back as single elements
+                    if constexpr (kFloat >= 0) {
+                        const float f0 = __builtin_fmaf((float)(d & 0xFFu), fs, fb), f1 = __builtin_fmaf((float)((d >> 8) & 0xFFu), fs, fb);
+                        const float f2 = __builtin_fmaf((float)((d >> 16) & 0xFFu), fs, fb), f3 = __builtin_fmaf((float)(d >> 24), fs, fb);
+                        if constexpr (kFloat == 0) {
+                            if (keep == 0xFu) *(gf32x4_any *)q = f32x4{f0, f1, f2, f3};
+                            else if (keep) {
+                                if (keep & 1u) *(gf32_any *)q = f0;
+                                if (keep & 2u) *(gf32_any *)(q + 4) = f1;
+                                if (keep & 4u) *(gf32_any *)(q + 8) = f2;
+                                if (keep & 8u) *(gf32_any *)(q + 12) = f3;
+                            }
+                        } else {
+                            const uint32_t lo = pack_half2<kFloat>(f0, f1), hi = pack_half2<kFloat>(f2, f3);
+                            if (keep == 0xFu) *(gu32x2_any *)q = u32x2{lo, hi};
+                            else if (keep) {
+                                if (keep & 1u) *(gu16_any *)q = (uint16_t)lo;
+                                if (keep & 2u) *(gu16_any *)(q + 2) = (uint16_t)(lo >> 16);
+                                if (keep & 4u) *(gu16_any *)(q + 4) = (uint16_t)hi;
+                                if (keep & 8u) *(gu16_any *)(q + 6) = (uint16_t)(hi >> 16);
+                            }
+                        }
+                    } else if (keep == 0xFu) *(gu32_any *)q = d;
+                    else if (keep) {
+                        if (keep & 1u) q[0] = (uint8_t)d;
+                        if (keep & 2u) q[1] = (uint8_t)(d >> 8);
+                        if (keep & 4u) q[2] = (uint8_t)(d >> 16);
+                        if (keep & 8u) q[3] = (uint8_t)(d >> 24);
+                    }
+                } else if constexpr (kFloat >= 0) {
                     // the dword's four bytes -> floats (v_cvt_f32_ubyte0 .. 3), ONE fused multiply-add each, then 16 (f32) or 8 bytes
                     // per lane (f16, bf16: packed conversions, round to nearest even); elements only where the row ends inside them
                     const float f0 = __builtin_fmaf((float)(d & 0xFFu), fs, fb), f1 = __builtin_fmaf((float)((d >> 8) & 0xFFu), fs, fb);
@@ -264,7 +323,7 @@
                 const uint32_t d3 = 3u * (lane & 15u);
                 const int la = (int)(d3 << 2), lb = (int)((d3 + 1) << 2), lc = (int)((d3 + 2) << 2);
                 const uint32_t s1 = ch == 0 ? 0x0c060300u : (ch == 1 ? 0x0c070401u : 0x0c0c0502u), s2 = ch == 0 ? 0x05020100u : (ch == 1 ? 0x06020100u : 0x07040100u);
-                for (uint32_t k = 0; k < nrows; k++) {
+                for (uint32_t k = k_lo; k < k_hi; k++) {
                     const uint32_t v = row_sum(k);
                     const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(la, (int)v), b = (uint32_t)__builtin_amdgcn_ds_bpermute(lb, (int)v), c = (uint32_t)__builtin_amdgcn_ds_bpermute(lc, (int)v);
                     const uint32_t d = ch == 3 ? 0xFFFFFFFFu : __builtin_amdgcn_perm(c, __builtin_amdgcn_perm(b, a, s1), s2);
@@ -274,7 +333,7 @@
                 // a thread holds one pixel: 4 x 4 bytes transposed inside every quad of lanes (DPP broadcasts of the quad's four
                 // dwords stay in the VALU), lane 4 q + ch then holds channel ch of pixels 4 q .. 4 q + 3
                 const uint32_t sq = ch | (4u + ch) << 8 | 0x0c0c0000u;
-                for (uint32_t k = 0; k < nrows; k++) {
+                for (uint32_t k = k_lo; k < k_hi; k++) {
                     const uint32_t v = row_sum(k);
                     const uint32_t v0 = quad_bcast<0>(v), v1 = quad_bcast<1>(v), v2 = quad_bcast<2>(v), v3 = quad_bcast<3>(v);
                     put(k, __builtin_amdgcn_perm(__builtin_amdgcn_perm(v3, v2, sq), __builtin_amdgcn_perm(v1, v0, sq), 0x05040100u));

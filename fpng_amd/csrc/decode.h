@@ -168,8 +168,31 @@ constexpr uint32_t kDecFloatTypes = 3;
 __host__ __device__
 #endif
 constexpr uint32_t dec_float_bytes(uint32_t dtype) { return dtype == 0 ? 4u : 2u; }
+// crops (device, a record per file of `jobs`, or NULL; needs plane_pitch): the jobs are fpng_amd_decode_batch_planar_crop's -- the
+// planes hold the crop's w x h elements (bytes, or flt's), DecJob::out / pitch and plane_pitch describe THAT destination, and
+// DecJob::nseg and the plan's column blocks count only the tiles dec_crop_tiles() names (all of them where adler_acc is given: the
+// Adler-32 needs every filtered byte); the *_crop kernels write them
+struct DecCrop { // (the words of fpng_amd_crop)
+    uint32_t x, y, w, h;
+};
+// The tiles of dec_unfilter_kernel that a crop needs: segments 0 .. n_segments - 1 (a pixel depends on its column in the rows above
+// it) of the column blocks first_col_block .. first_col_block + n_col_blocks - 1.  The ONE text: the host's plan, the kernels
+// (dec_crop_first_block) and fpng_amd_decode_crop_tiles use it.  false: the crop is empty or leaves the image.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t dec_crop_first_block(uint32_t crop_x) { return crop_x / 256u; }
+inline bool dec_crop_tiles(uint32_t file_w, uint32_t file_h, const DecCrop &c, uint32_t *n_segments, uint32_t *first_col_block, uint32_t *n_col_blocks)
+{
+    if (!c.w || !c.h || (uint64_t)c.x + c.w > file_w || (uint64_t)c.y + c.h > file_h) return false;
+    *n_segments = (c.y + c.h + kDecUnfRows - 1) / kDecUnfRows;
+    *first_col_block = dec_crop_first_block(c.x);
+    *n_col_blocks = (c.x + c.w - 1) / 256u - *first_col_block + 1;
+    return true;
+}
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout = false, const int64_t *plane_pitch = nullptr, unsigned long long *adler_acc = nullptr, const DecFloat *flt = nullptr);
+                         bool layout = false, const int64_t *plane_pitch = nullptr, unsigned long long *adler_acc = nullptr, const DecFloat *flt = nullptr,
+                         const DecCrop *crops = nullptr);
 // The optional check of the files' checksums (fpng_amd_encoder_set_decode_verify), per launch of launch_dec_finish: flags =
 // FPNG_AMD_VERIFY_*; adler_acc as above, zero when the launch begins; crc_partials: max_ranges words per file that launch_dec_crc
 // filled (FPNG_AMD_VERIFY_CRC32).  All pointers are the entries of the launch's first file.
@@ -202,7 +225,7 @@ inline uint32_t dec_crc_ranges(uintptr_t z, uint64_t idat_len)
 // raw CRC-32 partials of every file's IDAT payload, max_ranges words per file (depends on nothing but the files' bytes and the job records)
 void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t max_ranges, const CrcDeviceTables *tabs, uint32_t *partials);
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false,
-                       const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr, const DecFloat *flt = nullptr);
+                       const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr, const DecFloat *flt = nullptr, const DecCrop *crops = nullptr);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

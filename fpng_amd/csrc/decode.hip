@@ -1111,6 +1111,8 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
     constexpr unsigned long long *adler_acc = nullptr;
     constexpr int kFloat = -1;
     constexpr DecFloat flt = {};
+    constexpr bool kCrop = false;
+    constexpr const DecCrop *crops = nullptr;
 #include "dec_unfilter_body.inc"
 }
 // the planar jobs of fpng_amd_decode_batch_planar; plane_pitch: a word per file of `jobs` (DecJob has no room for it)
@@ -1121,6 +1123,8 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
     constexpr unsigned long long *adler_acc = nullptr;
     constexpr int kFloat = -1;
     constexpr DecFloat flt = {};
+    constexpr bool kCrop = false;
+    constexpr const DecCrop *crops = nullptr;
 #include "dec_unfilter_body.inc"
 }
 // The verify forms (fpng_amd_encoder_set_decode_verify with FPNG_AMD_VERIFY_ADLER32): the same body, which then also adds every tile's
@@ -1134,6 +1138,8 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
     constexpr const int64_t *plane_pitch = nullptr;
     constexpr int kFloat = -1;
     constexpr DecFloat flt = {};
+    constexpr bool kCrop = false;
+    constexpr const DecCrop *crops = nullptr;
 #include "dec_unfilter_body.inc"
 }
 __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_planar_verify_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch,
@@ -1142,6 +1148,8 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
     constexpr bool kLayout = false, kPlanar = true, kVerify = true;
     constexpr int kFloat = -1;
     constexpr DecFloat flt = {};
+    constexpr bool kCrop = false;
+    constexpr const DecCrop *crops = nullptr;
 #include "dec_unfilter_body.inc"
 }
 // The float planes of fpng_amd_decode_batch_planar_float: the planar body once more, whose last stage converts the lane's four bytes
@@ -1152,6 +1160,18 @@ __global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6)
                                                                                                                const int64_t *plane_pitch, unsigned long long *adler_acc, DecFloat flt)
 {
     constexpr bool kLayout = false, kPlanar = true, kVerify = kVerifyT;
+    constexpr int kFloat = kDtype;
+    constexpr bool kCrop = false;
+    constexpr const DecCrop *crops = nullptr;
+#include "dec_unfilter_body.inc"
+}
+// The crops of fpng_amd_decode_batch_planar_crop: the planar body with kCrop -- kDtype = -1: uint8 planes, else the float kernel's
+// element type; flt is read only then.  adler_acc: kVerify only (every tile of the file then runs, and the plan says so).
+template <int kDtype, bool kVerifyT>
+__global__ __launch_bounds__(kUnfBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void dec_unfilter_crop_kernel(const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t *status, uint32_t epoch, uint32_t skip_mask,
+                                                                                                              const int64_t *plane_pitch, unsigned long long *adler_acc, DecFloat flt, const DecCrop *crops)
+{
+    constexpr bool kLayout = false, kPlanar = true, kVerify = kVerifyT, kCrop = true;
     constexpr int kFloat = kDtype;
 #include "dec_unfilter_body.inc"
 }
@@ -1294,6 +1314,51 @@ __global__ __launch_bounds__(kDecBlock) void dec_stored_float_kernel(const DecJo
                 uint8_t *q = o + (int64_t)b * pp + (int64_t)x * dec_float_bytes((uint32_t)kDtype);
                 if constexpr (kDtype == 0) *(f32_a *)q = f;
                 else *(u16_a *)q = half_bits<kDtype>(f);
+            }
+        }
+    }
+    if (odd) atomicOr(&status[blockIdx.y], kDecStoredOdd);
+}
+// ... and of fpng_amd_decode_batch_planar_crop: the layout is checked over the WHOLE file as above, the copy takes the crop's window
+// only -- rows crop.y .. crop.y + crop.h - 1, pixels crop.x .. crop.x + crop.w - 1, into a destination of the crop's size (kDtype:
+// -1 bytes, else dec_stored_float_kernel's elements)
+template <int kDtype>
+__global__ __launch_bounds__(kDecBlock) void dec_stored_crop_kernel(const DecJob *jobs, uint32_t *status, const int64_t *plane_pitch, DecFloat flt, const DecCrop *crops)
+{
+    const DecJob &job = jobs[blockIdx.y];
+    if (job.mode != 1) return;
+    const uint8_t *z = job.z + job.z_shift;
+    const uint32_t sc = job.src_c, dc = job.dst_c, bpl = job.bpl, h = job.h;
+    const int64_t pp = plane_pitch[blockIdx.y];
+    const DecCrop crop = crops[blockIdx.y];
+    const uint64_t total = ((uint64_t)bpl + 1) * h;
+    const uint32_t nblk = (uint32_t)((total + 65534) / 65535);
+    bool odd = false;
+    for (uint32_t i = blockIdx.x * kDecBlock + threadIdx.x; i < nblk; i += gridDim.x * kDecBlock) {
+        const uint8_t *hd = z + 2 + (uint64_t)i * 65540;
+        const uint32_t len = i + 1 < nblk ? 65535u : (uint32_t)(total - (uint64_t)i * 65535);
+        odd |= hd[0] != (i + 1 == nblk ? 1 : 0) || (hd[1] | hd[2] << 8) != len || (hd[3] | hd[4] << 8) != (~len & 0xFFFFu);
+    }
+    // (every row's filter byte, a thread each)
+    for (uint32_t y = blockIdx.x * kDecBlock + threadIdx.x; y < h; y += gridDim.x * kDecBlock) odd |= z[stored_pos((uint64_t)y * ((uint64_t)bpl + 1))] != 0;
+    uint32_t lanes = 1;
+    while (lanes < crop.w && lanes < (uint32_t)kDecBlock) lanes <<= 1;
+    const uint32_t rows_per = kDecBlock / lanes, t_row = threadIdx.x / lanes, t_x = threadIdx.x & (lanes - 1);
+    constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
+    for (uint32_t j = blockIdx.x * rows_per + t_row; j < crop.h; j += gridDim.x * rows_per) {
+        const uint64_t s0 = (uint64_t)(crop.y + j) * ((uint64_t)bpl + 1); // the row's filter byte
+        uint8_t *o = job.out + (int64_t)j * job.pitch;
+        for (uint32_t i = t_x; i < crop.w; i += lanes) {
+            const uint64_t s = s0 + 1 + (uint64_t)(crop.x + i) * sc;
+            for (uint32_t b = 0; b < dc; b++) {
+                const uint8_t v = b < sc ? z[stored_pos(s + b)] : (uint8_t)0xFF;
+                uint8_t *q = o + (int64_t)b * pp + (int64_t)i * kElem;
+                if constexpr (kDtype < 0) *q = v;
+                else {
+                    const float f = __builtin_fmaf((float)v, flt.scale[b], flt.bias[b]);
+                    if constexpr (kDtype == 0) *(f32_a *)q = f;
+                    else *(u16_a *)q = half_bits<kDtype>(f);
+                }
             }
         }
     }
@@ -1523,8 +1588,19 @@ void launch_dec_offsets_range(hipStream_t s, const DecJob *jobs, uint32_t sub_ba
 // jobs / status: of the group's first file; plan: device arrays (decode_api.cpp); epoch: this launch's (a new one every time; the
 // granules are never cleared)
 void launch_dec_unfilter(hipStream_t s, const DecJob *jobs, DecUnfPlan plan, DecPlaced placed, uint32_t item0, uint32_t n_items, uint32_t *status, uint32_t epoch, bool concurrent_status,
-                         bool layout, const int64_t *plane_pitch, unsigned long long *adler_acc, const DecFloat *flt)
+                         bool layout, const int64_t *plane_pitch, unsigned long long *adler_acc, const DecFloat *flt, const DecCrop *crops)
 {
+    if (crops) { // the crops: uint8 planes (no flt) or an element type's, with and without the Adler sums
+        using Kernel = void (*)(const DecJob *, DecUnfPlan, DecPlaced, uint32_t, uint32_t *, uint32_t, uint32_t, const int64_t *, unsigned long long *, DecFloat, const DecCrop *);
+        static const Kernel kernels[kDecFloatTypes + 1][2] = {{dec_unfilter_crop_kernel<-1, false>, dec_unfilter_crop_kernel<-1, true>},
+                                                              {dec_unfilter_crop_kernel<0, false>, dec_unfilter_crop_kernel<0, true>},
+                                                              {dec_unfilter_crop_kernel<1, false>, dec_unfilter_crop_kernel<1, true>},
+                                                              {dec_unfilter_crop_kernel<2, false>, dec_unfilter_crop_kernel<2, true>}};
+        if (n_items)
+            hipLaunchKernelGGL(kernels[flt ? flt->dtype + 1 : 0][adler_acc ? 1 : 0], dim3(n_items), dim3(kUnfBlock), 0, s, jobs, plan, placed, item0, status, epoch,
+                               concurrent_status ? 0u : kDecUnfSkipMask, plane_pitch, adler_acc, flt ? *flt : DecFloat{}, crops);
+        return;
+    }
     if (flt) { // the float planes: a kernel per element type, with and without the Adler sums
         using Kernel = void (*)(const DecJob *, DecUnfPlan, DecPlaced, uint32_t, uint32_t *, uint32_t, uint32_t, const int64_t *, unsigned long long *, DecFloat);
         static const Kernel kernels[kDecFloatTypes][2] = {{dec_unfilter_float_kernel<0, false>, dec_unfilter_float_kernel<0, true>},
@@ -1583,14 +1659,18 @@ void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t
         hipLaunchKernelGGL(dec_crc_kernel, dim3(max_ranges, std::min(32768u, n_jobs - j0)), dim3(kDecBlock), 0, s, jobs + j0, tabs, partials + (size_t)j0 * max_ranges, max_ranges);
 }
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout,
-                       const int64_t *plane_pitch, const DecVerify *verify, const DecFloat *flt)
+                       const int64_t *plane_pitch, const DecVerify *verify, const DecFloat *flt, const DecCrop *crops)
 {
     unsigned long long *const acc = verify && (verify->flags & 2u) ? verify->adler_acc : nullptr;
-    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch, acc, flt);
+    if (plan.total_items) launch_dec_unfilter(s, jobs, plan, placed, 0, plan.total_items, status, epoch, false, layout, plane_pitch, acc, flt, crops);
     // (a workgroup that finds its file is not a stored one leaves at once, but n_jobs x 512 of them is not free)
     for (uint32_t j0 = 0; any_stored && j0 < n_jobs; j0 += 32768) { // (the y dimension of a grid holds at most 65535 workgroups)
         const dim3 grid(512, std::min(32768u, n_jobs - j0));
-        if (flt) {
+        if (crops) {
+            using Kernel = void (*)(const DecJob *, uint32_t *, const int64_t *, DecFloat, const DecCrop *);
+            static const Kernel kernels[kDecFloatTypes + 1] = {dec_stored_crop_kernel<-1>, dec_stored_crop_kernel<0>, dec_stored_crop_kernel<1>, dec_stored_crop_kernel<2>};
+            hipLaunchKernelGGL(kernels[flt ? flt->dtype + 1 : 0], grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0, plane_pitch + j0, flt ? *flt : DecFloat{}, crops + j0);
+        } else if (flt) {
             using Kernel = void (*)(const DecJob *, uint32_t *, const int64_t *, DecFloat);
             static const Kernel kernels[kDecFloatTypes] = {dec_stored_float_kernel<0>, dec_stored_float_kernel<1>, dec_stored_float_kernel<2>};
             hipLaunchKernelGGL(kernels[flt->dtype], grid, dim3(kDecBlock), 0, s, jobs + j0, status + j0, plane_pitch + j0, *flt);

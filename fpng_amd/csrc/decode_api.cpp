@@ -330,6 +330,10 @@ struct Batch {
     int64_t *d_plane_pitch = nullptr;
     const DecFloat *flt = nullptr; // fpng_amd_decode_batch(_device)_planar_float: the planes' element type and constants (else NULL) ...
     uint32_t elem = 1;             // ... and an element's bytes: a row of a plane is w * elem bytes
+    const fpng_amd_crop *crops = nullptr; // fpng_amd_decode_batch(_device)_planar_crop: the planar files' crops (else NULL) ...
+    std::vector<DecCrop> crop;            // ... a record per job, uploaded with the job records
+    DecCrop *d_crops = nullptr;
+    std::vector<uint32_t> col_blocks;     // per job: the column blocks its tiles are numbered over (a crop's: dec_crop_tiles)
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     std::vector<Parsed> ps;
     std::vector<DecJob> jobs;                // (their pointers into the scratch are offsets until place_files())
@@ -410,17 +414,27 @@ int parse_files(Batch &b)
         const uint32_t desired = b.planar ? b.planar[i].num_chans : b.ex ? kDstFormats[b.ex[i].format].bytes : b.desired;
         const uint64_t need = (uint64_t)p.w * p.h * desired;
         if ((r.status = file_status(p, st, need))) continue;
+        // (a crop that leaves the image: the file's own outcome -- it is not decoded and needs no room)
+        DecCrop crop = {0, 0, p.w, p.h};
+        uint32_t crop_nseg = 0, crop_cb0 = 0, crop_ncb = 0;
+        if (b.crops) {
+            crop = {b.crops[i].x, b.crops[i].y, b.crops[i].w, b.crops[i].h};
+            if (!dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb)) {
+                r.status = FPNG_AMD_DECODE_CROP_OUTSIDE;
+                continue;
+            }
+        }
         // (only files that will be written need room)
         int64_t pitch = 0, plane_pitch = 0;
         if (b.planar) {
             const fpng_amd_png_planar &x = b.planar[i];
-            const uint64_t roww = (uint64_t)p.w * b.elem; // bytes of a plane's row (float planes: w elements)
+            const uint64_t roww = (uint64_t)crop.w * b.elem; // bytes of a plane's row (float planes: w elements; a crop: its own w and h)
             if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
             pitch = x.row_pitch ? x.row_pitch : (int64_t)roww;
             const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
             if (step < roww) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
-            const uint64_t span = (uint64_t)(p.h - 1) * step + roww; // a plane, from its lowest row's first byte
-            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)p.h * step);
+            const uint64_t span = (uint64_t)(crop.h - 1) * step + roww; // a plane, from its lowest row's first byte
+            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)crop.h * step);
             if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
             const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
             if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
@@ -444,6 +458,14 @@ int parse_files(Batch &b)
         j.out = f.d_pixels, j.sub_base = b.sub_total;
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
         if (b.planar) j.pitch = (int32_t)pitch, b.plane_pitch.push_back(plane_pitch); // (|pitch| < 2^31: decode_files_planar)
+        // (the tiles a crop needs: DecJob::nseg is read by the un-filter kernels, by the plan and by the granules' sizing only, so
+        //  a crop's job carries the segments it needs and the plan its column blocks; with the Adler-32 check every tile runs)
+        uint32_t ncb = dec_col_blocks(j.w, j.src_c, j.dst_c);
+        if (b.crops) {
+            if (!p.mode && !(b.verify & FPNG_AMD_VERIFY_ADLER32)) j.nseg = crop_nseg, ncb = crop_ncb;
+            b.crop.push_back(crop);
+        }
+        b.col_blocks.push_back(ncb);
         if (!p.mode) {
             b.sub_total += (j.n_sub + kDecSubBlock - 1) / kDecSubBlock * kDecSubBlock; // whole workgroups per file
             // offsets into the shared scratch (pointers are patched once the buffers exist)
@@ -480,7 +502,7 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
     int rc;
@@ -490,6 +512,7 @@ int place_files(Batch &b)
     if (b.verify & FPNG_AMD_VERIFY_CRC32) b.d_crc_part = (uint32_t *)(base + o_part);
     b.d_luts = (uint32_t *)(base + o_luts), b.d_keys = base + o_keys, b.d_jobs = (DecJob *)(base + o_jobs), b.d_plan = base + o_plan, b.d_status = (uint32_t *)(base + o_status);
     b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
+    b.d_crops = b.crops ? (DecCrop *)(base + o_crop) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -573,7 +596,7 @@ int plan_groups(Batch &b)
         const uint32_t m = (uint32_t)order.size();
         const size_t w0 = words.size(), p0 = pieces.size();
         words.push_back(0);
-        for (uint32_t k = 0; k < m; k++) words.push_back(words.back() + dec_col_blocks(jobs[g.j0 + order[k]].w, jobs[g.j0 + order[k]].src_c, jobs[g.j0 + order[k]].dst_c));
+        for (uint32_t k = 0; k < m; k++) words.push_back(words.back() + b.col_blocks[g.j0 + order[k]]);
         words.insert(words.end(), order.begin(), order.end());
         uint32_t seg = 0, item = 0;
         for (uint32_t alive = m; alive >= 1; alive--) { // the alive-th file of the order is the next one to run out of rows
@@ -591,6 +614,7 @@ int plan_groups(Batch &b)
     if (!words.empty()) std::memcpy(h_setup + b.setup_plan + ((size_t)nj + kMaxGroups) * sizeof(DecUnfPiece), words.data(), words.size() * 4);
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
+    if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
     return FPNG_AMD_OK;
 }
 
@@ -629,7 +653,7 @@ int finish_group(Batch &b, uint32_t gi)
     }
     if (b.verify & FPNG_AMD_VERIFY_CRC32) verify.crc_partials = b.d_crc_part + (size_t)g.j0 * b.max_ranges;
     launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr,
-                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.flt);
+                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.flt, b.crops ? b.d_crops + g.j0 : nullptr);
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -785,9 +809,9 @@ int collect_results(Batch &b)
 }
 
 // ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
-// planar files are fpng_amd_decode_batch(_device)_planar_float's
+// planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
-                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr)
+                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -796,7 +820,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     int rc = drain(e);
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
-    b.planar = planar, b.verify = e->dec_verify;
+    b.planar = planar, b.crops = crops, b.verify = e->dec_verify;
     if (flt) b.flt = flt, b.elem = dec_float_bytes(flt->dtype);
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
@@ -1046,9 +1070,14 @@ static_assert(sizeof(fpng_amd_png_planar) == 48 && offsetof(fpng_amd_png_planar,
 static_assert(sizeof(fpng_amd_float_format) == 40 && sizeof(DecFloat) == 40 && offsetof(DecFloat, scale) == offsetof(fpng_amd_float_format, scale) &&
                   offsetof(DecFloat, bias) == offsetof(fpng_amd_float_format, bias), "fpng_amd_float_format layout");
 static_assert(FPNG_AMD_F32 == 0 && FPNG_AMD_F16 == 1 && FPNG_AMD_BF16 == 2 && kDecFloatTypes == 3, "the kernels' element types");
-int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr)
+// crops: fpng_amd_decode_batch(_device)_planar_crop's, a crop per file (the destinations are then the crops' sizes), else NULL
+static_assert(sizeof(fpng_amd_crop) == 16 && sizeof(DecCrop) == 16 && offsetof(fpng_amd_crop, w) == offsetof(DecCrop, w), "fpng_amd_crop layout");
+int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
+                        const fpng_amd_crop *crops = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    for (uint32_t i = 0; crops && i < n; i++)
+        if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
     DecFloat flt = {};
     uint32_t elem = 1;
     if (fmt) {
@@ -1068,7 +1097,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
         plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops);
 }
 } // namespace
 
@@ -1092,6 +1121,28 @@ extern "C" int fpng_amd_decode_batch_planar(fpng_amd_encoder *e, const fpng_amd_
 extern "C" int fpng_amd_decode_batch_device_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results)
 {
     return decode_files_planar(e, files, n, results, true);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_crop(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, uint32_t n, const fpng_amd_float_format *fmt,
+                                                 fpng_amd_decode_result *results)
+{
+    if (!crops) return fail(FPNG_AMD_ERR_INVALID_ARG, "null crops");
+    return decode_files_planar(e, files, n, results, false, fmt, crops);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_crop(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, uint32_t n, const fpng_amd_float_format *fmt,
+                                                        fpng_amd_decode_result *results)
+{
+    if (!crops) return fail(FPNG_AMD_ERR_INVALID_ARG, "null crops");
+    return decode_files_planar(e, files, n, results, true, fmt, crops);
+}
+
+extern "C" int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_crop *crop, uint32_t *n_segments, uint32_t *first_col_block, uint32_t *n_col_blocks)
+{
+    if (!crop || !n_segments || !first_col_block || !n_col_blocks) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (!dec_crop_tiles(file_w, file_h, {crop->x, crop->y, crop->w, crop->h}, n_segments, first_col_block, n_col_blocks))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "the crop is empty or leaves the image");
+    return FPNG_AMD_OK;
 }
 
 extern "C" int fpng_amd_decode_batch_ex(fpng_amd_encoder *e, const fpng_amd_png_ex *files, uint32_t n, fpng_amd_decode_result *results)

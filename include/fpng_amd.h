@@ -552,6 +552,46 @@ int fpng_amd_decode_batch_planar_float(fpng_amd_encoder *enc, const fpng_amd_png
                                        fpng_amd_decode_result *results);
 int fpng_amd_decode_batch_device_planar_float(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt,
                                               fpng_amd_decode_result *results);
+/* ---- decoding a CROP of each file into planar images, uint8 (fmt == NULL) or normalised floats (fmt): what a loader otherwise does
+ *      with a full decode and t[:, y:y+h, x:x+w].contiguous().  fpng's files use filter 0 on the first row and Up on every other
+ *      one, so a pixel depends only on its own column in the rows above it: of the 48-row x 256-pixel tiles the pixel pass works
+ *      in, only those fpng_amd_decode_crop_tiles names run, and only the crop's pixels are written.
+ *      Destination: the fpng_amd_png_planar record describes planes of crop.w x crop.h elements.  Every rule of
+ *      fpng_amd_decode_batch_planar (fmt == NULL) or fpng_amd_decode_batch_planar_float (fmt) holds with crop.w in the place of w and
+ *      crop.h in the place of h: 0 = tight pitches, negative pitches, the planes' overlap, pixels_cap, the element-size multiples,
+ *      the checks of fmt.  Element (c, j, i) of the destination is exactly what the full call writes at (c, crop.y + j, crop.x + i):
+ *      the same byte, or the same round_to_dtype(fmaf(v, scale[c], bias[c])) -- 0xFF / fmaf(255, ..) in the A plane of a 3-channel
+ *      file and a dropped alpha included.  Only the num_chans * crop.h spans of crop.w elements are written, whatever a file's status.
+ *      Call-level errors, with nothing launched: FPNG_AMD_ERR_INVALID_ARG for a null crops and for a crop.w or crop.h of 0.
+ *      A crop that leaves the image -- x + w > the file's w or y + h > its h, in 64 bits -- is, for a file whose header is accepted,
+ *      that FILE's outcome: status FPNG_AMD_DECODE_CROP_OUTSIDE with the file's w, h and channels_in_file; the file is not
+ *      decoded and needs no room, the batch's other files are unaffected.  results[i].w / h are always the file's, not the crop's.
+ *      Statuses: the container walk, the block header, the synchronisation, the placement of the subsequences and a stored file's
+ *      block-layout check cover the WHOLE file, and what they decide is the full call's (FPNG_AMD_DECODE_UNDECIDED and
+ *      FPNG_AMD_DECODE_MAX_ROUNDS included).  The pixel pass finds three things -- a filter byte that is not 0 (first row) or 2, a
+ *      bad match met by a tile's walk, a match at a row's first pixel -- and finds them only in the tiles that run: segments
+ *      0 .. n_segments - 1 of the column blocks first_col_block .. first_col_block + n_col_blocks - 1.  So: a file the full call
+ *      decodes with 0 decodes with 0; a file whose only damage is of those three kinds and lies outside the needed tiles decodes
+ *      with 0 too, and its crop holds the pixels the tokens say; otherwise the status is the full call's less what the tiles that
+ *      did not run would have found.
+ *      Checksums (fpng_amd_encoder_set_decode_verify): the CRC-32 check is the full call's (it reads the file's bytes alone).  With
+ *      FPNG_AMD_VERIFY_ADLER32 on EVERY tile of the file runs -- the Adler-32 covers all filtered bytes -- while the writes stay
+ *      clipped; the file's status is then exactly the full call's under the same flags.
+ *      One batch may mix crops, channel counts, pitches, 3- and 4-channel files and stored files.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_crop with dlsym. ---- */
+typedef struct fpng_amd_crop {
+    uint32_t x, y, w, h; /* in pixels of the file, top-down */
+} fpng_amd_crop;         /* 16 bytes */
+#define FPNG_AMD_DECODE_CROP_OUTSIDE 67 /* per-file status: the crop leaves the image */
+int fpng_amd_decode_batch_planar_crop(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, uint32_t n,
+                                      const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_planar_crop(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, uint32_t n,
+                                             const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results);
+/* The tiles a crop of a file_w x file_h file needs (no GPU needed; the text the decoder's own plan uses): segments of 48 rows
+ * 0 .. *n_segments - 1, column blocks of 256 pixels *first_col_block .. *first_col_block + *n_col_blocks - 1.
+ * FPNG_AMD_ERR_INVALID_ARG for a null argument, an empty crop and one that leaves the image. */
+int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_crop *crop, uint32_t *n_segments, uint32_t *first_col_block,
+                               uint32_t *n_col_blocks);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

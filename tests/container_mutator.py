@@ -178,3 +178,12 @@ def mutate(png, rng):
         b = ch[idat_i][1]
         ch[idat_i] = (b"IDAT", b[:-4] if rng.random() < 0.5 else b + bytes(int(rng.integers(1, 9)))); name = "IDAT_tail"
     return name, build(ch, tail)
+
+
+def with_dimensions(png, w, h):
+    """the file with IHDR's width and height set to (w, h) and IHDR's CRC made good: every fpng encoder writes only the low 16 bits
+    of each dimension (as the reference does), so a file with a dimension above 65535 needs its header corrected before any
+    decoder sees what was encoded"""
+    assert png[:8] == SIG and png[12:16] == b"IHDR"
+    body = struct.pack(">II", w, h) + bytes(png[24:29])
+    return bytes(png[:16]) + body + struct.pack(">I", zlib.crc32(b"IHDR" + body) & 0xFFFFFFFF) + bytes(png[33:])

@@ -165,3 +165,95 @@ def test_descriptors_of_the_other_kinds_are_refused(built_lib):
         Encoder.decode_device_float(e, flt)  # (host files: decode_batch_float)
     with pytest.raises(ValueError, match="CUDA"):
         Encoder.decode_batch_float(e, flt)  # (CPU destinations)
+
+
+# ---- the constant sets of the GPU tests: what they hold, and which wrong epilogues they tell from the rule ----
+def _f16_of(f32, mode):
+    """float32 values -> float16 bits by integer arithmetic: mode "even" (the rule), "away" (ties away from zero) or "trunc"
+    (toward zero).  -> (bits, a mask of the finite values that lie exactly half way between two float16 values)"""
+    x = np.abs(f32.astype(np.float64))
+    finite = np.isfinite(x)
+    _, e = np.frexp(np.where(finite & (x > 0), x, 1.0))  # x = m * 2^e, 0.5 <= m < 1
+    q = np.ldexp(1.0, np.maximum(e - 1, -14) - 10)  # the float16 step at x (subnormals: 2^-24)
+    n = np.where(finite, x, 0.0) / q  # exact: a power of two
+    lo = np.floor(n)
+    tie = finite & (n - lo == 0.5)
+    up = {"even": (n - lo > 0.5) | (tie & (lo % 2 == 1)), "away": n - lo >= 0.5, "trunc": np.zeros(n.shape, dtype=bool)}[mode]
+    r = (lo + up) * q
+    big = r > 65504.0
+    r = np.where(big, 65504.0 if mode == "trunc" else np.inf, r)
+    r = np.where(finite, r, np.inf)
+    bits = r.astype(np.float16).view(np.uint16)  # (exact: r is a float16 value)
+    return bits | (f32.view(np.uint32) >> 16 & 0x8000).astype(np.uint16), tie & ~big | (tie & (x == 65520.0))
+
+
+def _bf16_of(f32, mode):
+    b = f32.view(np.uint32).astype(np.uint64)
+    tie = np.isfinite(f32) & (b & 0xFFFF == 0x8000)
+    add = 0x8000 if mode == "away" else 0x7FFF + (b >> 16 & 1)
+    return ((b + add) >> 16).astype(np.uint16), tie
+
+
+def _flush(bits, mant, exp):
+    """subnormals of a bit pattern (mantissa mask, exponent mask) to a zero of their sign"""
+    sub = (bits & exp == 0) & (bits & mant != 0)
+    return np.where(sub, bits & ~np.array(mant | exp, dtype=bits.dtype), bits), sub
+
+
+def _census(consts):
+    """the reference tables of one constant set, what they hold, and which of the five wrong epilogues they show"""
+    from test_gpu_decode_float import _tables
+    scale, bias = consts
+    assert scale.dtype == bias.dtype == np.float32 and scale.shape == bias.shape == (4,)
+    t32 = _tables(consts, "float32")  # (asserts with fractions.Fraction that every float64 product and sum is exact)
+    f32 = t32.view(np.float32)
+    assert not np.isnan(f32).any()
+    t16, tb = _tables(consts, "float16"), _tables(consts, "bfloat16")
+    even16, tie16 = _f16_of(f32, "even")
+    evenb, tieb = _bf16_of(f32, "even")
+    # torch's conversions, numpy's and the integer models here are the same round-to-nearest-even
+    with np.errstate(over="ignore"):
+        assert np.array_equal(t16, f32.astype(np.float16).view(np.uint16)) and np.array_equal(t16, even16) and np.array_equal(tb, evenb)
+    flushed32, sub32 = _flush(t32, 0x007FFFFF, 0x7F800000)
+    flushed16, sub16 = _flush(t16, 0x03FF, 0x7C00)
+    holds = {"bf16_ties": int(tieb.sum()), "f16_ties": int(tie16.sum()), "f16_inf": int((t16 & 0x7FFF == 0x7C00).sum()),
+             "f16_subnormals": int(sub16.sum()), "f32_subnormals": int(sub32.sum()), "f32_inf": int(np.isinf(f32).sum()),
+             "minus_zero": int((t32 == 0x80000000).sum())}
+    wrong = {"bf16_half_away": int((_bf16_of(f32, "away")[0] != tb).sum()), "f16_half_away": int((_f16_of(f32, "away")[0] != t16).sum()),
+             "f32_flushed": int((flushed32 != t32).sum()), "f16_flushed": int((flushed16 != t16).sum()),
+             "f16_truncated": int((_f16_of(f32, "trunc")[0] != t16).sum())}
+    return holds, wrong
+
+
+# per set: what its tables must hold (counts of the 4 x 256 entries), and the wrong epilogues it is there to show
+HARD_HOLDS = {
+    "A": ({"bf16_ties": 512}, ["bf16_half_away"]),
+    "B": ({"f16_ties": 190, "bf16_ties": 165, "f16_inf": 38}, ["f16_half_away", "bf16_half_away", "f16_truncated"]),
+    "C": ({"f16_subnormals": 1018, "f16_ties": 224, "minus_zero": 1}, ["f16_flushed", "f16_half_away", "f16_truncated"]),
+    "D": ({"f32_subnormals": 510}, ["f32_flushed"]),
+    "E": ({"f32_inf": 699}, []),
+}
+
+
+def test_the_hard_constant_sets_tell_wrong_epilogues_from_the_rule():
+    """test_gpu_decode_float.HARD, sets A-E, against five wrong models of the float epilogue: bf16 and f16 conversions that round
+    half away from zero, fp32 and f16 results with subnormals flushed to zero, and an f16 conversion that truncates.  The three
+    older sets (CONSTS: ImageNet's mean / std, 1 / 255, 2 / 255 - 1) show NONE of the first four -- asserted below -- because their
+    tables hold no tie, no subnormal, no infinity and no -0.0; each of A-E must hold what it was written for (the counts, exactly)
+    and show the models named with it, so a set that is edited, or replaced by one of the old three, fails here.  Also asserted, for
+    every set: exact float32 constants, no NaN, and float64 arithmetic that is exact (so that _tables IS one fused multiply-add)."""
+    from test_gpu_decode_float import CONSTS, HARD
+    for k, consts in enumerate(CONSTS):
+        holds, wrong = _census(consts)
+        assert not any(holds.values()), (k, holds)
+        assert [wrong[m] for m in ("bf16_half_away", "f16_half_away", "f32_flushed", "f16_flushed")] == [0] * 4 and wrong["f16_truncated"] > 400, (k, wrong)
+    assert sorted(HARD) == sorted(HARD_HOLDS)
+    seen = set()
+    for name, consts in HARD.items():
+        holds, wrong = _census(consts)
+        want, shows = HARD_HOLDS[name]
+        assert {key: holds[key] for key in want} == want, (name, holds)
+        for m in shows:
+            assert wrong[m] > 0, (name, m, wrong)
+        seen |= {m for m, n in wrong.items() if n}
+    assert seen == {"bf16_half_away", "f16_half_away", "f32_flushed", "f16_flushed", "f16_truncated"}

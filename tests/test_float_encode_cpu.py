@@ -350,3 +350,55 @@ def test_float_image_generator(code):
         assert (diff == 0).mean() > 0.9 and (diff <= 1).mean() > 0.99  # + f16's rounding, up to 0.06 of a byte
     else:
         assert (diff <= 1).mean() > 0.99  # bf16's step near 1.0 is a whole byte
+
+
+# ---- subnormal source elements: widen_f16's host branch for them, the hardware conversion on the device ----
+def subnormal_image(code, w, h, c):
+    """-> (elements (h, w, c), scale[4], bias[4], the bytes by the rule).  Every element is a SUBNORMAL of its type, so every place
+    of the image -- a row's first and last pixel, window interiors -- holds one, with a scale that brings them into the byte range:
+    f16 (code 1): all 2046 non-zero subnormal bit patterns +-k * 2^-24, k = 1 ... 1023, scale 2^22 -- values +-k / 4, ties at
+    k = 2 mod 4; f32 (code 0): +-k * 2^-149 for k on a stride through 1 ... 2^23 - 1 and next to 2^21 and 3 * 2^21, scale 2^127 --
+    values +-k * 2^-22, exact ties at 0.5 and 1.5.  Products are exact in fp32 and in float64, so the rule's bytes are exact.  (bf16
+    shares fp32's exponent range and widens by a shift: no case of its own.)  A flush of the source to zero gives all-zero bytes."""
+    n = w * h * c
+    i = np.arange(n, dtype=np.int64)
+    if code == 1:
+        pat = np.concatenate([np.arange(1, 1024), 0x8000 + np.arange(1, 1024)]).astype(np.uint16)
+        assert pat.size == 2046 and n >= 2046
+        el = pat[(i * 5 + i // (w * c)) % 2046].view(np.float16)  # (5 and 2046 are coprime: every pattern occurs; rows start apart)
+        scale = 2.0 ** 22
+    else:
+        assert code == 0
+        ks = np.concatenate([np.arange(1, 1 << 23, 4099), [(1 << 23) - 1], [m * (1 << 21) + d for m in (1, 3) for d in (-1, 0, 1)]]).astype(np.uint32)
+        pat = np.concatenate([ks, ks[::3] | np.uint32(0x80000000)])
+        assert n >= pat.size
+        el = pat[(i * 7 + i // (w * c)) % pat.size].view(np.float32)
+        scale = 2.0 ** 127
+    el = el.reshape(h, w, c)
+    x = element_values(el, code)
+    assert bool(((x != 0) & (np.abs(x) < (2.0 ** -14 if code == 1 else 2.0 ** -126))).all())
+    sc, bi = np.full(4, scale, dtype=np.float32), np.zeros(4, dtype=np.float32)
+    by = oracle_quantize(x, sc[0], bi[0])
+    return el, sc, bi, by
+
+
+@pytest.mark.parametrize("code", [0, 1])
+def test_subnormal_sources(built_lib, code):
+    """fpng_amd_quantize_float on subnormal elements (f16: widen_f16's branch for a zero exponent; f32: no flush): the rule's
+    bytes, ties to even among them, and the patterns the generator promises"""
+    el, sc, bi, by = subnormal_image(code, 300, 9, 3)
+    bits = np.ascontiguousarray(el).view(np.uint16 if code == 1 else np.uint32)
+    if code == 1:
+        assert np.unique(bits).size == 2046
+        assert sorted(np.unique(by).tolist()) == list(range(256))
+        k = np.arange(1, 1024)
+        want = np.clip(np.rint(k / 4.0), 0, 255).astype(np.uint8)
+        assert np.array_equal(lib_quantize(k.astype(np.uint16).view(np.float16), 1, sc[0], 0.0), want)
+        assert want[1] == 0 and want[5] == 2 and want[9] == 2 and want[13] == 4  # k = 2, 6, 10, 14: 0.5, 1.5, 2.5, 3.5 to even
+    else:
+        assert sorted(np.unique(by).tolist()) == [0, 1, 2]
+        ties = np.array([(1 << 21) - 1, 1 << 21, (1 << 21) + 1, 3 * (1 << 21) - 1, 3 * (1 << 21), 3 * (1 << 21) + 1], dtype=np.uint32).view(np.float32)
+        assert lib_quantize(ties, 0, sc[0], 0.0).tolist() == [0, 0, 1, 1, 2, 2]
+        assert set(ties.view(np.uint32).tolist()) <= set(bits.reshape(-1).tolist())
+    assert np.array_equal(lib_quantize(el, code, sc[0], bi[0]), by)
+    assert np.array_equal(lib_quantize(el[::-1, ::-1], code, sc[0], bi[0]), by[::-1, ::-1])

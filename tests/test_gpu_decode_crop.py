@@ -5,7 +5,9 @@ dtypes, three and four planes, every pitch kind, host and device files.
 Expected values are the FULL calls' (decode_device_planar, decode_device_float: other tests pin those to the reference's decoder and
 to a single fused multiply-add), sliced -- and, for uint8, the reference's decoder's (judge()) directly.  Everything is compared
 bit for bit: an element of a crop is the same byte, or the same fmaf and rounding, as the full call's.  Buffers are sentinel-filled
-and compared WHOLE, so not one element outside the num_chans x crop.h spans of crop.w elements may change."""
+and compared WHOLE, so not one element outside the num_chans x crop.h spans of crop.w elements may change.
+(test_hard_constants_at_cut_quads is the exception: its float values come from the table of test_gpu_decode_float, not from the
+full call, at constants where the results tie, go subnormal or overflow.)"""
 import ctypes as C
 import os
 
@@ -13,7 +15,7 @@ import numpy as np
 import pytest
 
 from test_gpu_decode import UNDECIDED, _device_files, judge
-from test_gpu_decode_float import CONSTS
+from test_gpu_decode_float import CONSTS, HARD, _bits as _table_bits, _tables, hard_files
 from test_gpu_decode_layouts import SENTINEL, _damaged_files, _encode_gpu, _header_dims
 from test_gpu_decode_planar import KINDS, _Region
 import verify_files as vf
@@ -157,6 +159,34 @@ def test_crop_matrix(enc, files, c, dtype, device):
         assert st == 0 and cf == chans[i] and view is views[k], (k, i, st, cf)
     exp = _expect(total, dtype, regs, crops, [full[(c, dtype)][i] for i, _ in batch])
     assert _first_difference(host, exp, regs) is None, (c, dtype, device, _first_difference(host, exp, regs))
+
+
+@pytest.mark.parametrize("dtype", DTYPES[1:])
+@pytest.mark.parametrize("name", sorted(HARD))
+def test_hard_constants_at_cut_quads(enc, name, dtype):
+    """test_gpu_decode_float's hard constant sets and files (w = 257 ... 260, every byte value at every quad position) through the
+    crop kernels: crops that cut the first quad by 1, 2 and 3 elements and the last quad as well, and the whole image, into three
+    and four planes.  The expected bits are the TABLE's (one fma in exact float64 arithmetic, round to nearest even) at the
+    reference's pixels -- not the full call's, so that a mistake the two kernels share cannot cancel."""
+    pngs, judged = hard_files()
+    tab = _tables(HARD[name], dtype)
+    k = sorted(HARD).index(name) + DTYPES.index(dtype)
+    for c in (3, 4):
+        batch, sources = [], []
+        for i, p in enumerate(pngs):
+            st, px, w, h, _ = judged[c][i]
+            src = _table_bits(np.asarray(px)[: w * h * c].reshape(h, w, c), tab).transpose(2, 0, 1)
+            for crop in ((1, 0, w - 1, 256), (2, 1, w - 3, 255), (3, 0, w - 3, 256), (0, 0, w, 256)):
+                batch.append((i, crop))
+                sources.append(src)
+        crops = [crop for _, crop in batch]
+        kinds = [KINDS[(j + k + c) % len(KINDS)] for j in range(len(batch))]
+        regs, total = _regions(crops, c, kinds)
+        device = bool((k + c) & 1)
+        got, host, views = _decode_crop(enc, [pngs[i] for i, _ in batch], crops, regs, total, dtype, device, consts=HARD[name])
+        assert [st for st, _, _ in got] == [0] * len(batch)
+        exp = _expect(total, dtype, regs, crops, sources)
+        assert _first_difference(host, exp, regs) is None, (name, c, dtype, device, _first_difference(host, exp, regs))
 
 
 def test_results_report_the_files_dimensions(enc, files):

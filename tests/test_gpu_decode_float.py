@@ -5,7 +5,9 @@ f16 and bf16, every pitch kind, host and device files.
 Expected values never come from the code under test: the pixels are the REFERENCE's decoder's (judge()), and an element is looked up
 in a 256-entry table per channel, np.float32(np.float64(v) * np.float64(scale32) + np.float64(bias32)) -- the table builder checks
 with fractions.Fraction that the float64 product and sum are EXACT, so their one rounding to float32 is what a single fp32 fused
-multiply-add gives -- then torch's CPU conversion to f16 / bf16 (round to nearest even).  Buffers are compared whole and bitwise."""
+multiply-add gives -- then torch's CPU conversion to f16 / bf16 (round to nearest even).  Buffers are compared whole and bitwise.
+CONSTS are the constants a loader uses (results in [-2.2, 2.7]: no tie, subnormal or infinity); HARD are the ones at which the
+rule's rounding, subnormals, overflow and zero sign show (test_float_cpu.py: which wrong epilogue each set tells from the rule)."""
 import os
 import struct
 from fractions import Fraction
@@ -13,6 +15,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from cpu_ref import oracle
 from test_gpu_decode import UNDECIDED, _device_files, judge
 from test_gpu_decode_layouts import SENTINEL, _damaged_files, _encode_gpu, _header_dims, _matrix_files
 from test_gpu_decode_planar import KINDS, _Region, _regions
@@ -33,6 +36,16 @@ _MEAN, _STD = (0.485, 0.456, 0.406, 0.5), (0.229, 0.224, 0.225, 0.25)
 CONSTS = [(_f32([1.0 / (255.0 * s) for s in _STD]), _f32([-m / s for m, s in zip(_MEAN, _STD)])),
           (_f32([1.0 / 255.0] * 4), _f32([0.0] * 4)),
           (_f32([2.0 / 255.0] * 4), _f32([-1.0] * 4))]
+# Constants at which the results ROUND HARD or leave a type's normal range -- CONSTS' 3 x 4 x 256 results lie in [-2.2, 2.7] and hold
+# no f16 or bf16 tie, no subnormal of any type, no infinity and no -0.0.  Every value is an exact float32, the float64 product and
+# sum are exact for all of them (test_float_cpu.py asserts both, and what each set holds), and no result is NaN.
+HARD = {
+    "A": (_f32([1.0, 1.0, 0.5, 2.0]), _f32([256.0, -511.0, 128.0, 512.0])),                           # bf16 ties
+    "B": (_f32([1.0, 8.0, -257.0, 300.0]), _f32([2048.0, -4096.0, 0.0, -100.0])),                     # f16 ties, f16 overflow
+    "C": (_f32([2.0 ** -24, 2.0 ** -25, -(2.0 ** -26), 3 * 2.0 ** -27]), _f32([0.0, 0.0, -0.0, 2.0 ** -24])),  # f16 subnormals, -0.0
+    "D": (_f32([2.0 ** -149, -(2.0 ** -140), 0.0, -0.0]), _f32([0.0, 2.0 ** -133, -0.0, 0.0])),       # fp32 subnormals
+    "E": (_f32([2.0 ** 127, -(2.0 ** 127), 2.0 ** 120, 2.0 ** 104]), _f32([0.0, 2.0 ** 127, 1.5 * 2.0 ** 127, -(2.0 ** 127)])),  # fp32 overflow
+}
 
 
 def _tables(consts, dtype):
@@ -45,7 +58,8 @@ def _tables(consts, dtype):
         for v in range(256):
             x = np.float64(v) * s64 + b64
             assert Fraction(float(x)) == Fraction(v) * Fraction(float(s64)) + Fraction(float(b64)), (c, v)  # the float64 value is exact
-            f32[c, v] = np.float32(x)
+            with np.errstate(over="ignore"):  # (past float32's range: the infinity an fp32 fma gives)
+                f32[c, v] = np.float32(x)
     if dtype == "float32":
         return f32.view(np.uint32)
     t = torch.from_numpy(f32).to(getattr(torch, dtype))
@@ -129,6 +143,88 @@ def test_every_dtype_pitch_and_width(enc, matrix, c, dtype, device):
     bad = np.nonzero(host != exp)[0]
     assert bad.size == 0, (c, dtype, device, bad.size, int(bad[0]), hex(int(host[bad[0]])), hex(int(exp[bad[0]])),
                            [(i, r.w, r.h, r.kind, int(bad[0]) - r.lo) for i, r in enumerate(regs) if r.off <= bad[0] < r.off + r.size])
+
+
+_HARD_FILES = None
+
+
+def hard_files():
+    """(pngs, judged[desired][i]) -- made once, shared with test_gpu_decode_crop -- of the files the hard constant sets are decoded
+    from: 3 and 4 channels x widths 257 ... 260 (a ragged row end of 1, 2, 3 and 0 elements behind the last whole quad) x 256 rows,
+    pixel (x + 5 y + 64 ch) & 255, written 1-pass, 2-pass and stored by the oracle; the pixels are the reference's decoder's.
+    Asserted on those pixels, not assumed: in every file every plane of the file's meets every byte value at every x mod 4 (a
+    lane's quad) AND at every element of the last quad, so every table entry passes through every conversion site."""
+    global _HARD_FILES
+    if _HARD_FILES is None:
+        pngs, chans = [], []
+        for c in (3, 4):
+            for w in (257, 258, 259, 260):
+                y, x, ch = np.meshgrid(np.arange(256), np.arange(w), np.arange(c), indexing="ij")
+                img = np.ascontiguousarray(((x + 5 * y + 64 * ch) & 255).astype(np.uint8))
+                for fl in (0, 1, 2):
+                    pngs.append(oracle().encode(img, w, 256, c, fl))
+                    chans.append(c)
+        assert [(p[60] & 6) != 0 for p in pngs] == [fl != 2 for _ in range(8) for fl in (0, 1, 2)]  # Deflate blocks, but for the stored ones
+        judged = {d: [judge(p, d) for p in pngs] for d in (3, 4)}
+        for d in (3, 4):
+            for (st, px, w, h, fc), c in zip(judged[d], chans):
+                assert st == 0 and h == 256 and fc == c
+                px = np.asarray(px)[: w * h * d].reshape(h, w, d)
+                last = (w - 1) & ~3
+                for ch in range(d):
+                    if ch >= c:
+                        assert bool((px[:, :, ch] == 255).all())  # (the alpha a 3-channel file gets: scale[3] and bias[3] at 255)
+                        continue
+                    for k in range(4):
+                        assert np.unique(px[:, k::4, ch]).size == 256, (w, c, ch, k)
+                    for x in range(last, w):
+                        assert np.unique(px[:, x, ch]).size == 256, (w, c, ch, x)
+        _HARD_FILES = (pngs, judged)
+    return _HARD_FILES
+
+
+def _hard_case(enc, name, dtype, c, device, shift):
+    """the hard files into c planes of `dtype` under HARD[name], pitch kinds dealt round-robin from `shift`: the whole buffer
+    against the table look-up of the reference's pixels and the sentinel"""
+    pngs, judged = hard_files()
+    consts = HARD[name]
+    tab = _tables(consts, dtype)
+    dims = [struct.unpack(">II", bytes(p[16:24])) for p in pngs]
+    kinds = [KINDS[(i + shift) % len(KINDS)] for i in range(len(pngs))]
+    regs, total = _regions(dims, c, kinds)
+    got, host, views = _decode_float(enc, pngs, regs, total, dtype, consts, device)
+    exp = np.full(total, _sentinel(dtype), dtype=host.dtype)
+    for i, (r, (st, view, cf)) in enumerate(zip(regs, got)):
+        cst, cpx, w, h, fc = judged[c][i]
+        assert st == cst == 0 and cf == fc and view is views[i], (i, st, cst)
+        r.put(exp, _bits(np.asarray(cpx)[: w * h * c].reshape(h, w, c), tab))
+    bad = np.nonzero(host != exp)[0]
+    assert bad.size == 0, (name, c, dtype, device, bad.size, int(bad[0]), hex(int(host[bad[0]])), hex(int(exp[bad[0]])),
+                           [(i, r.w, r.h, r.kind, int(bad[0]) - r.lo) for i, r in enumerate(regs) if r.off <= bad[0] < r.off + r.size])
+
+
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", sorted(HARD))
+def test_hard_constants(enc, name, dtype, device):
+    """Every set of HARD (bf16 ties; f16 ties and overflow; f16 subnormals and -0.0; fp32 subnormals; fp32 overflow) x every dtype
+    x both entry points, into three and into four planes (a 3-channel file into four pins fmaf(255, scale[3], bias[3])): one fp32
+    fused multiply-add, then round to nearest even -- ties to even, subnormal results kept, infinities past the type's range, the
+    zero's sign -- bit for bit, at whole-quad stores, single-element stores at ragged row ends and the stored files' scalar path."""
+    for c in (3, 4):
+        _hard_case(enc, name, dtype, c, device, shift=sorted(HARD).index(name) + DTYPES.index(dtype) + c)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_hard_constants_with_checksums_verified(enc, dtype):
+    """the subnormal sets (C: f16, D: fp32) through the kernels' verify instantiations (set_decode_verify(CRC | ADLER))"""
+    enc.set_decode_verify(3)
+    try:
+        for k, name in enumerate(("C", "D")):
+            for c in (3, 4):
+                _hard_case(enc, name, dtype, c, device=bool((k + c) & 1), shift=k + c)
+    finally:
+        enc.set_decode_verify(0)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -29,4 +29,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   denormalize_constants, source_layout_float,
                   pack_capacity, pack_place, STATUS_STORED_TOO_LARGE, STATUS_ARENA_FULL,
                   VERIFY_CRC32, VERIFY_ADLER32, DECODE_BAD_CRC32, DECODE_BAD_ADLER32,
-                  DECODE_CROP_OUTSIDE, DecodeBatchCrop, crop_tiles)
+                  DECODE_CROP_OUTSIDE, DecodeBatchCrop, crop_tiles,
+                  RESIZE_MIRROR, DecodeBatchResize, resize_weights)

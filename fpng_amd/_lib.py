@@ -79,6 +79,14 @@ class Crop(C.Structure):  # fpng_amd_crop: 16 bytes, in pixels of the file, top-
 DECODE_CROP_OUTSIDE = 67  # FPNG_AMD_DECODE_CROP_OUTSIDE: a file's status when its crop leaves the image
 
 
+class Resize(C.Structure):  # fpng_amd_resize: 16 bytes, the output size of a file's crop
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RESIZE_MIRROR = 1  # FPNG_AMD_RESIZE_MIRROR
+RESIZE_MAX_TAPS = 65  # weights per output sample of fpng_amd_resize_weights
+
+
 class Pack(C.Structure):  # fpng_amd_pack: 40 bytes
     _fields_ = [("d_arena", C.c_void_p), ("arena_cap", C.c_uint64), ("align", C.c_uint32), ("lead", C.c_uint32), ("d_table", C.c_void_p),
                 ("reserved", C.c_uint64)]
@@ -191,6 +199,9 @@ SIGNATURES = {
     "fpng_amd_decode_batch_device_planar_float": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_planar_crop": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_planar_crop": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_planar_resize": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(Resize), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_resize": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(Resize), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_resize_weights": (_int, [_u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_int32)]),
     "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),
     "fpng_amd_encoder_decode_verify": (_u32, [_vp]),

@@ -34,6 +34,8 @@ VERIFY_CRC32, VERIFY_ADLER32 = 1, 2
 DECODE_BAD_CRC32, DECODE_BAD_ADLER32 = 65, 66
 # a file's status when its crop leaves the image (Encoder.decode_device_crop; FPNG_AMD_DECODE_CROP_OUTSIDE)
 DECODE_CROP_OUTSIDE = _lib.DECODE_CROP_OUTSIDE
+# fpng_amd_resize.flags (Encoder.decode_device_resize: mirror=True sets it): the output's columns in reverse order
+RESIZE_MIRROR = _lib.RESIZE_MIRROR
 
 # source formats of Encoder.submit_ex (FPNG_AMD_SRC_* in include/fpng_amd.h): name -> (value, source bytes per pixel, PNG channels)
 SRC_FORMATS = {"RGB": (0, 3, 3), "BGR": (1, 3, 3), "RGBA": (2, 4, 4), "BGRA": (3, 4, 4), "ARGB": (4, 4, 4), "ABGR": (5, 4, 4),
@@ -268,6 +270,21 @@ def crop_tiles(file_w, file_h, crop):
     nseg, first, ncb = C.c_uint32(), C.c_uint32(), C.c_uint32()
     check(_lib.load().fpng_amd_decode_crop_tiles(int(file_w), int(file_h), C.byref(c), C.byref(nseg), C.byref(first), C.byref(ncb)))
     return nseg.value, first.value, ncb.value
+
+
+def resize_weights(in_size, out_size):
+    """fpng_amd_resize_weights: (first, count, weights) of one axis of decode_device_resize() -- numpy arrays first[out_size],
+    count[out_size] (uint32) and weights[out_size, 65] (int32, 22-bit fixed point, 0 behind a row's count): output sample o is
+    clamp((2^21 + sum_t in[first[o] + t] * weights[o, t]) >> 22, 0, 255).  The text the kernel runs; no GPU needed.  A size of 0
+    or in_size > 32 * out_size raises FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
+    in_size, out_size = int(in_size), int(out_size)
+    if not (0 <= in_size <= 0xFFFFFFFF and 0 <= out_size <= 0xFFFFFFFF):
+        raise ValueError(f"resize_weights: sizes {in_size} -> {out_size} (32 bits, not negative)")
+    first, count = np.zeros(max(out_size, 1), dtype=np.uint32), np.zeros(max(out_size, 1), dtype=np.uint32)
+    weights = np.zeros((max(out_size, 1), _lib.RESIZE_MAX_TAPS), dtype=np.int32)
+    check(_lib.load().fpng_amd_resize_weights(in_size, out_size, first.ctypes.data_as(C.POINTER(C.c_uint32)), count.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              weights.ctypes.data_as(C.POINTER(C.c_int32))))
+    return first, count, weights
 
 
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
@@ -549,6 +566,16 @@ class DecodeBatchCrop(_DecodeBatchViews):
     def __init__(self, pngs, outs, arr, res, device_data, keep, crops, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
         self.crops, self.fmt = crops, fmt
+
+
+class DecodeBatchResize(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_resize() returns: the same for one fpng_amd_decode_batch(_device)_planar_resize() call (crops:
+    the fpng_amd_crop[n]; sizes: the fpng_amd_resize[n]; outs: the caller's (c, out_h, out_w) views, uint8 or all of one float
+    dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No other call takes this descriptor."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, crops, sizes, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.crops, self.sizes, self.fmt = crops, sizes, fmt
 
 
 class Encoder:
@@ -969,7 +996,7 @@ class Encoder:
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop)):
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize)):
             raise ValueError("decode_device_ex: a planar, float or crop descriptor (decode_device_planar, decode_device_float, decode_device_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if not batch.device_data:
@@ -981,7 +1008,7 @@ class Encoder:
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop)):
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize)):
             raise ValueError("decode_batch_ex: a planar, float or crop descriptor (decode_batch_planar, decode_batch_float, decode_batch_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if batch.device_data:
@@ -1027,6 +1054,8 @@ class Encoder:
             raise ValueError(f"{who}: a make_decode_batch_float() descriptor (decode_device_float / decode_batch_float)")
         if isinstance(pngs, DecodeBatchCrop):
             raise ValueError(f"{who}: a make_decode_batch_crop() descriptor (decode_device_crop / decode_batch_crop)")
+        if isinstance(pngs, DecodeBatchResize):
+            raise ValueError(f"{who}: a make_decode_batch_resize() descriptor (decode_device_resize / decode_batch_resize)")
         batch = pngs if isinstance(pngs, DecodeBatchPlanar) else self.make_decode_batch_planar(pngs, outs, order, bottom_up)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_planar)" if device_data else "device memory (decode_device_planar)"))
@@ -1085,7 +1114,7 @@ class Encoder:
         return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt)
 
     def _decode_float(self, who, fn, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop, DecodeBatchResize)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_float() makes this one's)")
         batch = pngs if isinstance(pngs, DecodeBatchFloat) else self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias)
         if batch.device_data != device_data:
@@ -1164,7 +1193,7 @@ class Encoder:
         return DecodeBatchCrop(list(pngs), list(outs), arr, res, device_data, keep, carr, fmt)
 
     def _decode_crop(self, who, fn, device_data, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchResize)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_crop() makes this one's)")
         if isinstance(pngs, DecodeBatchCrop):
             batch = pngs
@@ -1197,6 +1226,107 @@ class Encoder:
         """fpng_amd_decode_batch_planar_crop: decode_device_crop() for files in host memory (bytes)."""
         return self._decode_crop("decode_batch_crop", self.lib.fpng_amd_decode_batch_planar_crop, False, pngs, crops, outs, dtype, order, bottom_up,
                                  mean, std, scale, bias, results)
+
+    @staticmethod
+    def make_decode_batch_resize(pngs, crops, outs, mirror=False, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+        """Descriptor (fpng_amd_png_planar[n], fpng_amd_crop[n], fpng_amd_resize[n], the fpng_amd_float_format if any and the result
+        records) for decode_device_resize() / decode_batch_resize(): the files and crops as for make_decode_batch_crop(); outs:
+        (c, out_h, out_w) tensor VIEWS of any size from 1 x 1 up -- list(batch) of an (n, 3, 224, 224) tensor -- uint8, or float32 /
+        float16 / bfloat16 of ONE dtype with the constants of make_decode_batch_float(); mirror: one bool, or one per file.  Each
+        crop is resized to its view's size by Pillow's 8-bit antialiased bilinear rule, mirrored where
+        asked, and written once.  The call refuses (FpngAmdError) an empty crop and one of more than 32 x its output size in w or h."""
+        n = len(pngs)
+        if len(crops) != n or len(outs) != n:
+            raise ValueError(f"make_decode_batch_resize: {n} files, {len(crops)} crops, {len(outs)} destinations")
+        mirrors = [bool(mirror)] * n if isinstance(mirror, (bool, int, np.bool_)) else [bool(m) for m in mirror]
+        if len(mirrors) != n:
+            raise ValueError(f"make_decode_batch_resize: {n} files, {len(mirrors)} mirror flags")
+        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"make_decode_batch_resize: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        is_u8 = dtypes == {torch.uint8}
+        fmt = None
+        if is_u8:
+            if any(v is not None for v in (mean, std, scale, bias)):
+                raise ValueError("make_decode_batch_resize: mean / std / scale / bias go with float destinations, not uint8 ones")
+        else:
+            sc, bi = _float_constants("make_decode_batch_resize", normalize_constants, mean, std, scale, bias)
+            fmt = _lib.FloatFormat()
+            for k in range(4):
+                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        arr = (_lib.PngPlanarIn * n)()
+        carr = (_lib.Crop * n)()
+        sarr = (_lib.Resize * n)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        for i, (p, t) in enumerate(zip(pngs, outs)):
+            if is_u8:
+                ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
+            else:
+                ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
+            x, y, w, h = (int(v) for v in crops[i])
+            if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
+                raise ValueError(f"make_decode_batch_resize: crop {tuple(crops[i])} of file {i} (four values of 32 bits, not negative)")
+            c, oh, ow = t.shape
+            if oh < 1 or ow < 1:
+                raise ValueError(f"make_decode_batch_resize: destination {i} is {ow} x {oh}")
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError("make_decode_batch_resize: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            carr[i].x, carr[i].y, carr[i].w, carr[i].h = x, y, w, h
+            sarr[i].out_w, sarr[i].out_h, sarr[i].flags, sarr[i].reserved = ow, oh, (RESIZE_MIRROR if mirrors[i] else 0), 0
+            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
+            arr[i].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
+        return DecodeBatchResize(list(pngs), list(outs), arr, res, device_data, keep, carr, sarr, fmt)
+
+    def _decode_resize(self, who, fn, device_data, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop)):
+            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize() makes this one's)")
+        if isinstance(pngs, DecodeBatchResize):
+            batch = pngs
+        else:
+            if crops is None:
+                raise ValueError(f"{who}: crops, an (x, y, w, h) per file")
+            if outs is None:  # (c = 3 planes of the output size each; files with alpha lose it)
+                if size is None:
+                    raise ValueError(f"{who}: outs, or size=(out_h, out_w) to allocate them")
+                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
+                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+                oh, ow = (int(v) for v in size)
+                outs = list(torch.empty((len(pngs), 3, oh, ow), dtype=dtype, device=f"cuda:{self.device}"))
+            batch = self.make_decode_batch_resize(pngs, crops, outs, mirror, order, bottom_up, mean, std, scale, bias)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_resize)" if device_data else "device memory (decode_device_resize)"))
+        if not all(t.is_cuda for t in batch.outs):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, batch.crops, batch.sizes, len(batch.arr), C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_resize(self, pngs, crops=None, outs=None, size=None, mirror=False, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None,
+                             scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_device_planar_resize: uint8 CUDA tensors holding whole files, of each of which the crop (x, y, w, h)
+        is decoded, resized to its (c, out_h, out_w) device tensor view's size, mirrored where asked and written in place, as bytes
+        or as normalised floats (make_decode_batch_resize() has the rules) -> list of (status, the caller's view or None,
+        channels_in_file) -- RandomResizedCrop + RandomHorizontalFlip + Normalize without the F.interpolate, flip and normalise
+        passes behind decode_device_crop().  outs=None with size=(out_h, out_w) allocates one (n, 3, out_h, out_w) tensor of `dtype`
+        and returns its slices.  pngs may be a make_decode_batch_resize() descriptor of device files; results=False returns it."""
+        return self._decode_resize("decode_device_resize", self.lib.fpng_amd_decode_batch_device_planar_resize, True, pngs, crops, outs, size, mirror, dtype, order,
+                                   bottom_up, mean, std, scale, bias, results)
+
+    def decode_batch_resize(self, pngs, crops=None, outs=None, size=None, mirror=False, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None,
+                            scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_planar_resize: decode_device_resize() for files in host memory (bytes)."""
+        return self._decode_resize("decode_batch_resize", self.lib.fpng_amd_decode_batch_planar_resize, False, pngs, crops, outs, size, mirror, dtype, order,
+                                   bottom_up, mean, std, scale, bias, results)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

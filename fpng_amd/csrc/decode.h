@@ -226,6 +226,12 @@ inline uint32_t dec_crc_ranges(uintptr_t z, uint64_t idat_len)
 void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t max_ranges, const CrcDeviceTables *tabs, uint32_t *partials);
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false,
                        const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr, const DecFloat *flt = nullptr, const DecCrop *crops = nullptr);
+// The second stage of fpng_amd_decode_batch_planar_resize (resize.h, resize.hip): recs (device) -- a record per file of the launch,
+// whose crops' uint8 planes the crop kernels in front of it on the stream wrote; max_tiles / lds_bytes: the most tiles per plane a
+// file of the launch has and the most LDS one of its tiles needs (resize_tile_lds); flt (host, or NULL: bytes): the elements.
+// false: max_tiles or lds_bytes is out of range, nothing was launched.
+struct DecResize;
+bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

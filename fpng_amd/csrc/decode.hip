@@ -35,6 +35,7 @@
 #include "decode.h"
 #include "crc_device.h"
 #include "decode_core.h"
+#include "float_store.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1068,22 +1069,14 @@ __device__ __forceinline__ void gstore_u8(gu8 *base, uint32_t off, uint32_t v) {
 // (the float planes of fpng_amd_decode_batch_planar_float: 16- and 8-byte stores at any multiple of the element size, elements at a row's end)
 typedef float __attribute__((ext_vector_type(4))) f32x4;
 typedef uint32_t __attribute__((ext_vector_type(2))) u32x2;
-typedef float __attribute__((aligned(4))) f32_a;
 typedef f32x4 __attribute__((aligned(4))) f32x4_a;
 typedef u32x2 __attribute__((aligned(2))) u32x2_a;
-typedef uint16_t __attribute__((aligned(2))) u16_a;
 typedef __attribute__((address_space(1))) f32_a gf32_any;
 typedef __attribute__((address_space(1))) f32x4_a gf32x4_any;
 typedef __attribute__((address_space(1))) u32x2_a gu32x2_any;
 typedef __attribute__((address_space(1))) u16_a gu16_any;
-// float -> the bits of a 2-byte element, round to nearest even (kDtype: FPNG_AMD_F16 = 1, FPNG_AMD_BF16 = 2); a pair in a dword, the
-// first one low (v_cvt_pk_f16_f32, v_cvt_pk_bf16_f32)
-template <int kDtype> __device__ __forceinline__ uint16_t half_bits(float f)
-{
-    asm("" : "+v"(f)); // (the fp32 result as it is: no fused multiply-add that rounds straight to the narrow type)
-    if constexpr (kDtype == 1) return __builtin_bit_cast(uint16_t, (_Float16)f);
-    else return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
+// (f32_a, u16_a and half_bits -- float -> the bits of a 2-byte element -- live in float_store.h: dec_resize_kernel rounds with the same text)
+// a pair of 2-byte elements in a dword, the first one low (v_cvt_pk_f16_f32, v_cvt_pk_bf16_f32)
 template <int kDtype> __device__ __forceinline__ uint32_t pack_half2(float a, float b)
 {
     typedef float __attribute__((ext_vector_type(2))) f32x2;

@@ -7,6 +7,7 @@
 #include "encoder.h"
 #include "host_workers.h"
 #include "png_parse.h"
+#include "resize.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -334,6 +335,14 @@ struct Batch {
     std::vector<DecCrop> crop;            // ... a record per job, uploaded with the job records
     DecCrop *d_crops = nullptr;
     std::vector<uint32_t> col_blocks;     // per job: the column blocks its tiles are numbered over (a crop's: dec_crop_tiles)
+    // fpng_amd_decode_batch(_device)_planar_resize: the files' output sizes (else NULL; needs crops).  The jobs' out / pitch /
+    // plane_pitch then describe the crop's uint8 planes in the scratch (mid_total bytes, 16-byte aligned per file), which the crop
+    // kernels fill as for uint8 destinations; the caller's destination travels in a record per job to dec_resize_kernel
+    const fpng_amd_resize *sizes = nullptr;
+    std::vector<DecResize> resize; // (src: an offset into the intermediate planes until place_files())
+    std::vector<uint32_t> resize_tiles, resize_lds; // per job: its tiles per plane, the LDS bytes of one
+    DecResize *d_resize = nullptr;
+    size_t mid_total = 0;
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     std::vector<Parsed> ps;
     std::vector<DecJob> jobs;                // (their pointers into the scratch are offsets until place_files())
@@ -428,13 +437,15 @@ int parse_files(Batch &b)
         int64_t pitch = 0, plane_pitch = 0;
         if (b.planar) {
             const fpng_amd_png_planar &x = b.planar[i];
-            const uint64_t roww = (uint64_t)crop.w * b.elem; // bytes of a plane's row (float planes: w elements; a crop: its own w and h)
+            // (a crop: its own w and h; a resize: the output size's)
+            const uint32_t dest_w = b.sizes ? b.sizes[i].out_w : crop.w, dest_h = b.sizes ? b.sizes[i].out_h : crop.h;
+            const uint64_t roww = (uint64_t)dest_w * b.elem; // bytes of a plane's row (float planes: w elements)
             if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
             pitch = x.row_pitch ? x.row_pitch : (int64_t)roww;
             const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
             if (step < roww) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
-            const uint64_t span = (uint64_t)(crop.h - 1) * step + roww; // a plane, from its lowest row's first byte
-            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)crop.h * step);
+            const uint64_t span = (uint64_t)(dest_h - 1) * step + roww; // a plane, from its lowest row's first byte
+            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)dest_h * step);
             if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
             const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
             if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
@@ -457,6 +468,22 @@ int parse_files(Batch &b)
         DecJob j = make_job(p, desired);
         j.out = f.d_pixels, j.sub_base = b.sub_total;
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
+        if (b.sizes) {
+            // the crop kernels write tight uint8 planes of the crop's size into the scratch; the resize reads them and writes the caller's
+            const fpng_amd_resize &z = b.sizes[i];
+            if (crop.w >= 0x80000000u) return fail(FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31");
+            const uint64_t tiles = (uint64_t)((z.out_w + kResizeTileW - 1) / kResizeTileW) * ((z.out_h + kResizeTileH - 1) / kResizeTileH);
+            if (tiles * 4 * kResizeBlock >= (1ull << 32)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16");
+            DecResize rs = {};
+            rs.src = (const uint8_t *)(uintptr_t)b.mid_total, rs.dst = (uint8_t *)f.d_pixels, rs.plane_pitch = plane_pitch, rs.pitch = (int32_t)pitch;
+            rs.in_w = crop.w, rs.in_h = crop.h, rs.out_w = z.out_w, rs.out_h = z.out_h, rs.flags = z.flags, rs.planes = desired;
+            rs.taps_x = resize_max_taps(crop.w, z.out_w), rs.taps_y = resize_max_taps(crop.h, z.out_h), rs.rows = resize_tile_rows(crop.h, z.out_h);
+            b.resize.push_back(rs);
+            b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
+            j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
+            pitch = (int64_t)crop.w, plane_pitch = (int64_t)((uint64_t)crop.w * crop.h);
+            b.mid_total += ((size_t)plane_pitch * desired + 15) & ~(size_t)15;
+        }
         if (b.planar) j.pitch = (int32_t)pitch, b.plane_pitch.push_back(plane_pitch); // (|pitch| < 2^31: decode_files_planar)
         // (the tiles a crop needs: DecJob::nseg is read by the un-filter kernels, by the plan and by the granules' sizing only, so
         //  a crop's job carries the segments it needs and the plan its column blocks; with the Adler-32 check every tile runs)
@@ -502,8 +529,9 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.sizes ? nj * sizeof(DecResize) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
+    const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
     int rc;
     if ((rc = sc.place(e, b.d))) return rc;
@@ -513,6 +541,7 @@ int place_files(Batch &b)
     b.d_luts = (uint32_t *)(base + o_luts), b.d_keys = base + o_keys, b.d_jobs = (DecJob *)(base + o_jobs), b.d_plan = base + o_plan, b.d_status = (uint32_t *)(base + o_status);
     b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
     b.d_crops = b.crops ? (DecCrop *)(base + o_crop) : nullptr;
+    b.d_resize = b.sizes ? (DecResize *)(base + o_resize) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -541,6 +570,7 @@ int place_files(Batch &b)
         DecJob &j = b.jobs[k];
         const Parsed &p = b.ps[b.job_file[k]];
         if (!b.device_data) j.z = b.d.z + (size_t)(uintptr_t)j.z;
+        if (b.sizes) j.out = base + o_mid + (size_t)(uintptr_t)j.out, b.resize[k].src = j.out;
         // (parse_files sized the CRC partials of a host-resident file for a stream that starts on a 16-byte boundary; dec_verify_kernel
         //  counts the ranges from the real address, and one more range than sized would be the next file's slot)
         if (!b.device_data && (b.verify & FPNG_AMD_VERIFY_CRC32) && ((uintptr_t)j.z & 15)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "decode scratch: a file's stream is not 16-byte aligned");
@@ -615,6 +645,7 @@ int plan_groups(Batch &b)
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
+    if (b.sizes) std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), nj * sizeof(DecResize));
     return FPNG_AMD_OK;
 }
 
@@ -653,7 +684,13 @@ int finish_group(Batch &b, uint32_t gi)
     }
     if (b.verify & FPNG_AMD_VERIFY_CRC32) verify.crc_partials = b.d_crc_part + (size_t)g.j0 * b.max_ranges;
     launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr,
-                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.flt, b.crops ? b.d_crops + g.j0 : nullptr);
+                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.sizes ? nullptr : b.flt, b.crops ? b.d_crops + g.j0 : nullptr);
+    // (the resize: behind the group's pixel pass and stored copy on the same stream, on whatever the scratch then holds -- it writes
+    //  the spans of the destination and nothing else, whatever a file's status turns out to be)
+    if (b.sizes) {
+        const uint32_t tiles = *std::max_element(b.resize_tiles.begin() + g.j0, b.resize_tiles.begin() + g.j1), lds = *std::max_element(b.resize_lds.begin() + g.j0, b.resize_lds.begin() + g.j1);
+        if (!launch_dec_resize(b.s, b.d_resize + g.j0, g.j1 - g.j0, tiles, lds, b.flt)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
+    }
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -809,9 +846,11 @@ int collect_results(Batch &b)
 }
 
 // ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
-// planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's
+// planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's; sizes (with
+// crops): ... fpng_amd_decode_batch(_device)_planar_resize's
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
-                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr)
+                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
+                 const fpng_amd_resize *sizes = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -820,7 +859,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     int rc = drain(e);
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
-    b.planar = planar, b.crops = crops, b.verify = e->dec_verify;
+    b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (flt) b.flt = flt, b.elem = dec_float_bytes(flt->dtype);
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
@@ -1072,12 +1111,29 @@ static_assert(sizeof(fpng_amd_float_format) == 40 && sizeof(DecFloat) == 40 && o
 static_assert(FPNG_AMD_F32 == 0 && FPNG_AMD_F16 == 1 && FPNG_AMD_BF16 == 2 && kDecFloatTypes == 3, "the kernels' element types");
 // crops: fpng_amd_decode_batch(_device)_planar_crop's, a crop per file (the destinations are then the crops' sizes), else NULL
 static_assert(sizeof(fpng_amd_crop) == 16 && sizeof(DecCrop) == 16 && offsetof(fpng_amd_crop, w) == offsetof(DecCrop, w), "fpng_amd_crop layout");
+static_assert(sizeof(fpng_amd_resize) == 16 && offsetof(fpng_amd_resize, flags) == 8 && FPNG_AMD_RESIZE_MIRROR == kResizeMirror, "fpng_amd_resize layout");
+// sizes: fpng_amd_decode_batch(_device)_planar_resize's, an output size per file (with crops; the destinations are then those sizes).
+// The records' own rules, which need no file, no encoder and no device
+int check_resize_records(const fpng_amd_crop *crops, const fpng_amd_resize *sizes, uint32_t n)
+{
+    for (uint32_t i = 0; crops && sizes && i < n; i++) {
+        const fpng_amd_resize &z = sizes[i];
+        if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
+        if (!z.out_w || !z.out_h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty output size (out_w or out_h is 0)");
+        if (z.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_resize::reserved must be 0");
+        if (z.flags & ~(uint32_t)FPNG_AMD_RESIZE_MIRROR) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_resize::flags bits");
+        if (!resize_scale_ok(crops[i].w, z.out_w) || !resize_scale_ok(crops[i].h, z.out_h))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "a crop of more than 32 x its output size (w <= 32 * out_w and h <= 32 * out_h)");
+    }
+    return FPNG_AMD_OK;
+}
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
-                        const fpng_amd_crop *crops = nullptr)
+                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize *sizes = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && i < n; i++)
         if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
+    if (int rc = check_resize_records(crops, sizes, n)) return rc;
     DecFloat flt = {};
     uint32_t elem = 1;
     if (fmt) {
@@ -1097,7 +1153,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
         plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, sizes);
 }
 } // namespace
 
@@ -1135,6 +1191,37 @@ extern "C" int fpng_amd_decode_batch_device_planar_crop(fpng_amd_encoder *e, con
 {
     if (!crops) return fail(FPNG_AMD_ERR_INVALID_ARG, "null crops");
     return decode_files_planar(e, files, n, results, true, fmt, crops);
+}
+
+// (the records are judged first: their refusals need neither an encoder nor a device)
+extern "C" int fpng_amd_decode_batch_planar_resize(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize *sizes, uint32_t n,
+                                                   const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!crops || !sizes) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null sizes" : "null crops");
+    if (int rc = check_resize_records(crops, sizes, n)) return rc;
+    return decode_files_planar(e, files, n, results, false, fmt, crops, sizes);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize *sizes, uint32_t n,
+                                                          const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!crops || !sizes) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null sizes" : "null crops");
+    if (int rc = check_resize_records(crops, sizes, n)) return rc;
+    return decode_files_planar(e, files, n, results, true, fmt, crops, sizes);
+}
+
+// out_size rows of kResizeMaxTaps weights (those behind a row's count: 0), first and count per output sample: resize_weights_of,
+// the text dec_resize_kernel runs
+extern "C" int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint32_t *first, uint32_t *count, int32_t *weights)
+{
+    if (!first || !count || !weights) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (!resize_scale_ok(in_size, out_size)) return fail(FPNG_AMD_ERR_INVALID_ARG, "in_size and out_size are at least 1, and in_size <= 32 * out_size");
+    for (uint32_t o = 0; o < out_size; o++) {
+        int32_t *K = weights + (size_t)o * kResizeMaxTaps;
+        std::fill(K, K + kResizeMaxTaps, 0);
+        count[o] = resize_weights_of(in_size, out_size, o, &first[o], K, 1);
+    }
+    return FPNG_AMD_OK;
 }
 
 extern "C" int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_crop *crop, uint32_t *n_segments, uint32_t *first_col_block, uint32_t *n_col_blocks)

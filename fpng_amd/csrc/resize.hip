@@ -1,0 +1,109 @@
+// resize.hip -- the second stage of fpng_amd_decode_batch(_device)_planar_resize: the crop's uint8 planes, which the crop kernels of
+// decode.hip (dec_unfilter_crop_kernel<-1, *>, dec_stored_crop_kernel<-1>) left in the decode scratch, are resized to the caller's
+// out_w x out_h planes by the rule of resize.h, mirrored where asked, and written once -- bytes, or the float call's elements.
+//
+// One workgroup per (file, plane, tile of kResizeTileW x kResizeTileH output samples):
+//   1. a thread per output column / row of the tile computes that sample's first tap, tap count and weights (resize_weights_of,
+//      the text the host's fpng_amd_resize_weights runs) into LDS: Kx[t][column], Ky[t][row];
+//   2. the horizontal pass over the source rows the tile's Ky reach -- a wave per row, a lane per column, the row's bytes from
+//      global memory (neighbouring lanes read neighbouring bytes: the same cache lines), the weights from LDS without bank
+//      conflicts (consecutive lanes, consecutive dwords) -- into LDS bytes T[row][column];
+//   3. the vertical pass out of T (a wave reads 64 consecutive bytes of a row, Ky[t][row] is one address for the wave: a
+//      broadcast), then the mirror as an index of the store, the fmaf and the conversion of the float call, and stores that are
+//      contiguous along a row for the wave in either direction.
+// The sums are integers, so their order is free; no atomics, nothing between workgroups.  LDS is sized by the launch for the
+// largest tile of its files (resize_tile_lds): ~8 KB for a 1080p crop -> 224 x 224, 55 KB at the 32 x limit.
+#include "decode.h"
+#include "float_store.h"
+#include "resize.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+namespace fpng_amd {
+
+namespace {
+
+template <int kDtype>
+__global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResize *recs, DecFloat flt)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
+    const DecResize r = recs[blockIdx.z];
+    const uint32_t plane = blockIdx.y;
+    const uint32_t tiles_x = (r.out_w + kResizeTileW - 1) / kResizeTileW, tiles_y = (r.out_h + kResizeTileH - 1) / kResizeTileH;
+    if (plane >= r.planes || (uint64_t)blockIdx.x >= (uint64_t)tiles_x * tiles_y) return; // (the grid is the launch's largest file)
+    const uint32_t ox0 = blockIdx.x % tiles_x * kResizeTileW, oq0 = blockIdx.x / tiles_x * kResizeTileH;
+    const uint32_t nq = std::min(kResizeTileH, r.out_h - oq0);
+    int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
+    uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
+    uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
+    const uint32_t tid = threadIdx.x;
+    // ---- 1. the tile's weights ----
+    if (tid < kResizeTileW) {
+        uint32_t first = 0, count = 0;
+        if (ox0 + tid < r.out_w) count = resize_weights_of(r.in_w, r.out_w, ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        fx[tid] = first, cx[tid] = count;
+    } else if (tid < kResizeTileW + kResizeTileH) {
+        const uint32_t q = tid - kResizeTileW;
+        uint32_t first = 0, count = 0;
+        if (q < nq) count = resize_weights_of(r.in_h, r.out_h, oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        fy[q] = first, cy[q] = count;
+    }
+    __syncthreads();
+    // ---- 2. the horizontal pass: source rows row0 .. row0 + nrows - 1 (first and first + count do not decrease with the sample) ----
+    const uint32_t row0 = fy[0];
+    const uint32_t nrows = std::min(fy[nq - 1] + cy[nq - 1] - row0, r.rows); // (the host's bound holds: T has r.rows rows)
+    const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
+    const uint8_t *const P = r.src + (uint64_t)plane * r.in_w * r.in_h;
+    {
+        const uint32_t first = fx[o], count = cx[o];
+        for (uint32_t j = wave; j < nrows; j += kResizeBlock / kResizeTileW) {
+            const uint8_t *s = P + (uint64_t)(row0 + j) * r.in_w + first;
+            int32_t sum = 1 << (kResizeBits - 1);
+            for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
+            T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
+        }
+    }
+    __syncthreads();
+    // ---- 3. the vertical pass, the mirror, the element ----
+    if (ox0 + o >= r.out_w) return;
+    const uint32_t col = r.flags & kResizeMirror ? r.out_w - 1 - (ox0 + o) : ox0 + o;
+    constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
+    // (c is the FILE's channel: plane b of the record is channel b, whatever the planes' order in memory -- a select, not an index
+    //  into the argument, which would put it into private memory)
+    const float sc = plane == 0 ? flt.scale[0] : plane == 1 ? flt.scale[1] : plane == 2 ? flt.scale[2] : flt.scale[3];
+    const float bi = plane == 0 ? flt.bias[0] : plane == 1 ? flt.bias[1] : plane == 2 ? flt.bias[2] : flt.bias[3];
+    uint8_t *const D = r.dst + (int64_t)plane * r.plane_pitch + (int64_t)col * kElem;
+    for (uint32_t q = wave; q < nq; q += kResizeBlock / kResizeTileW) {
+        const uint32_t first = fy[q] - row0;
+        const uint32_t count = first < nrows ? std::min(cy[q], nrows - first) : 0u;
+        int32_t sum = 1 << (kResizeBits - 1);
+        for (uint32_t t = 0; t < count; t++) sum += (int32_t)T[(first + t) * kResizeTileW + o] * Ky[t * kResizeTileH + q];
+        const uint32_t v = resize_clip8(sum);
+        uint8_t *p = D + (int64_t)(oq0 + q) * r.pitch;
+        if constexpr (kDtype < 0) *p = (uint8_t)v;
+        else {
+            const float f = __builtin_fmaf((float)v, sc, bi);
+            if constexpr (kDtype == 0) *(f32_a *)p = f;
+            else *(u16_a *)p = half_bits<kDtype>(f);
+        }
+    }
+}
+
+} // namespace
+
+bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt)
+{
+    using Kernel = void (*)(const DecResize *, DecFloat);
+    static const Kernel kernels[kDecFloatTypes + 1] = {dec_resize_kernel<-1>, dec_resize_kernel<0>, dec_resize_kernel<1>, dec_resize_kernel<2>};
+    // (a launch holds fewer than 2^32 threads, its z dimension at most 65535 workgroups)
+    const uint64_t per_file = (uint64_t)max_tiles * 4 * kResizeBlock;
+    if (!max_tiles || per_file >= (1ull << 32) || lds_bytes > 65536u) return false;
+    const uint32_t step = (uint32_t)std::min<uint64_t>(32768u, ((1ull << 32) - 1) / per_file);
+    for (uint32_t j0 = 0; j0 < n; j0 += step)
+        hipLaunchKernelGGL(kernels[flt ? flt->dtype + 1 : 0], dim3(max_tiles, 4, std::min(step, n - j0)), dim3(kResizeBlock), lds_bytes, s, recs + j0, flt ? *flt : DecFloat{});
+    return true;
+}
+
+} // namespace fpng_amd

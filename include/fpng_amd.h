@@ -592,6 +592,49 @@ int fpng_amd_decode_batch_device_planar_crop(fpng_amd_encoder *enc, const fpng_a
  * FPNG_AMD_ERR_INVALID_ARG for a null argument, an empty crop and one that leaves the image. */
 int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_crop *crop, uint32_t *n_segments, uint32_t *first_col_block,
                                uint32_t *n_col_blocks);
+/* ---- decoding a crop of each file RESIZED to a fixed size, optionally mirrored, into planar images, uint8 (fmt == NULL) or
+ *      normalised floats (fmt): a loader's RandomResizedCrop(size) + RandomHorizontalFlip() + Normalize, written once.  Per file a
+ *      crop as for fpng_amd_decode_batch_planar_crop and an fpng_amd_resize record.  P, one channel of the crop (crop.h x crop.w
+ *      bytes), is exactly what that call writes for uint8 planes (A = 255 for a 3-channel file, a dropped alpha).  The resize is
+ *      Pillow's 8-bit resampler with the triangle filter, antialiased when shrinking -- what torchvision's PIL backend computes for
+ *      resized_crop(..., interpolation=BILINEAR) -- defined in integers so that every output is exact.  Weights of one axis
+ *      (in -> out), in IEEE double, no fused multiply-add, operations in the order written:
+ *          scale = in / out;  fs = max(scale, 1.0);  support = fs;  ss = 1.0 / fs
+ *          for o in 0 .. out-1:
+ *              center = (o + 0.5) * scale
+ *              first  = max((int)(center - support + 0.5), 0)              (int): truncation toward zero
+ *              count  = min((int)(center + support + 0.5), in) - first
+ *              k[t]   = tri(((t + first) - center + 0.5) * ss),  t = 0 .. count-1;   tri(a) = |a| < 1 ? 1 - |a| : 0
+ *              ww     = k[0] + k[1] + ... (in this order);   k[t] = k[t] / ww   (if ww != 0)
+ *              K[o][t] = (int)(0.5 + k[t] * 4194304.0)                      2^22
+ *          pass(row, K)[o] = clamp((2^21 + sum_t row[first_o + t] * K[o][t]) >> 22, 0, 255)
+ *      T[j][o] = pass(P[j], Kx)[o] for every crop row j (BYTES), then R[q][o] = pass(T[:, o], Ky)[q]: out_h x out_w bytes.
+ *      Element (c, q, i) of the destination comes from R_c[q][out_w - 1 - i] with FPNG_AMD_RESIZE_MIRROR, else from R_c[q][i], and
+ *      is that byte (uint8 planes) or round_to_dtype(fmaf((float)byte, scale[c], bias[c])) as in the float call; c is the FILE's
+ *      channel.  Taps never leave the crop; in == out is the identity on that axis.
+ *      Destination: the fpng_amd_png_planar record describes planes of out_w x out_h elements; every rule of the crop call holds
+ *      with those in the place of crop.w / crop.h.  Only the num_chans * out_h spans of out_w elements are written, whatever a file's
+ *      status.  results[i].w / h stay the FILE's.
+ *      Call-level errors, with nothing launched: FPNG_AMD_ERR_INVALID_ARG for null crops or sizes, an empty crop, out_w or out_h
+ *      of 0, reserved != 0, unknown flag bits, and a crop past the scale limit (crop.w <= 32 * out_w and crop.h <= 32 * out_h; at
+ *      most 65 taps; upscaling is unbounded).  A crop that leaves the image stays that file's own status 67; statuses,
+ *      FPNG_AMD_DECODE_UNDECIDED, FPNG_AMD_DECODE_MAX_ROUNDS and the checksum flags behave as in the crop call.
+ *      Not offered: other filters and antialias off; premultiplied alpha (every plane is resized on its own, as an "L" image);
+ *      a resize without a crop record (give the whole image as the crop); the interleaved destinations, fpng_amd_decode_host and
+ *      the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize with dlsym. ---- */
+typedef struct fpng_amd_resize {
+    uint32_t out_w, out_h, flags, reserved;
+} fpng_amd_resize; /* 16 bytes */
+#define FPNG_AMD_RESIZE_MIRROR 1u
+int fpng_amd_decode_batch_planar_resize(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize *sizes,
+                                        uint32_t n, const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, const fpng_amd_crop *crops,
+                                               const fpng_amd_resize *sizes, uint32_t n, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                               fpng_amd_decode_result *results);
+/* The weights of one axis (no GPU needed; the text the kernel runs): first[o], count[o] and weights[o * 65 + t], t < count[o] (0
+ * behind them), for o < out_size.  FPNG_AMD_ERR_INVALID_ARG for a null argument, a size of 0 and in_size > 32 * out_size. */
+int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint32_t *first, uint32_t *count, int32_t *weights /* out_size x 65 */);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

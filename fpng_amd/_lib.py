@@ -83,6 +83,12 @@ class Resize(C.Structure):  # fpng_amd_resize: 16 bytes, the output size of a fi
     _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ResizeView(C.Structure):  # fpng_amd_resize_view: 32 bytes, a window of a file's crop resized to full_w x full_h
+    _fields_ = [("full_w", C.c_uint32), ("full_h", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("flags", C.c_uint32), ("filter", C.c_uint32)]
+
+
+FILTER_BILINEAR, FILTER_BICUBIC = 0, 1  # FPNG_AMD_FILTER_*
 RESIZE_MIRROR = 1  # FPNG_AMD_RESIZE_MIRROR
 RESIZE_MAX_TAPS = 65  # weights per output sample of fpng_amd_resize_weights
 
@@ -202,6 +208,10 @@ SIGNATURES = {
     "fpng_amd_decode_batch_planar_resize": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(Resize), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_planar_resize": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(Resize), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_resize_weights": (_int, [_u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_int32)]),
+    "fpng_amd_decode_batch_planar_resize_view": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_resize_view": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_resize_weights_filter": (_int, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_int32)]),
+    "fpng_amd_resize_view_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(Crop)]),
     "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),
     "fpng_amd_encoder_decode_verify": (_u32, [_vp]),

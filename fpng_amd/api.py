@@ -36,6 +36,8 @@ DECODE_BAD_CRC32, DECODE_BAD_ADLER32 = 65, 66
 DECODE_CROP_OUTSIDE = _lib.DECODE_CROP_OUTSIDE
 # fpng_amd_resize.flags (Encoder.decode_device_resize: mirror=True sets it): the output's columns in reverse order
 RESIZE_MIRROR = _lib.RESIZE_MIRROR
+# fpng_amd_resize_view.filter (Encoder.decode_device_resize_view: filter="bilinear" / "bicubic")
+FILTER_BILINEAR, FILTER_BICUBIC = _lib.FILTER_BILINEAR, _lib.FILTER_BICUBIC
 
 # source formats of Encoder.submit_ex (FPNG_AMD_SRC_* in include/fpng_amd.h): name -> (value, source bytes per pixel, PNG channels)
 SRC_FORMATS = {"RGB": (0, 3, 3), "BGR": (1, 3, 3), "RGBA": (2, 4, 4), "BGRA": (3, 4, 4), "ARGB": (4, 4, 4), "ABGR": (5, 4, 4),
@@ -272,19 +274,85 @@ def crop_tiles(file_w, file_h, crop):
     return nseg.value, first.value, ncb.value
 
 
-def resize_weights(in_size, out_size):
-    """fpng_amd_resize_weights: (first, count, weights) of one axis of decode_device_resize() -- numpy arrays first[out_size],
-    count[out_size] (uint32) and weights[out_size, 65] (int32, 22-bit fixed point, 0 behind a row's count): output sample o is
-    clamp((2^21 + sum_t in[first[o] + t] * weights[o, t]) >> 22, 0, 255).  The text the kernel runs; no GPU needed.  A size of 0
-    or in_size > 32 * out_size raises FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
+FILTERS = {"bilinear": FILTER_BILINEAR, "bicubic": FILTER_BICUBIC}
+
+
+def _filter_id(who, f):
+    """a filter's name ("bilinear", "bicubic") or FILTER_* value -> the value"""
+    if isinstance(f, str):
+        if f not in FILTERS:
+            raise ValueError(f"{who}: filter {f!r} ({', '.join(sorted(FILTERS))})")
+        return FILTERS[f]
+    f = int(f)
+    if not 0 <= f <= 0xFFFFFFFF:
+        raise ValueError(f"{who}: filter {f}")
+    return f  # (an unknown value: the library's refusal)
+
+
+def resize_weights(in_size, out_size, filter="bilinear"):
+    """fpng_amd_resize_weights(_filter): (first, count, weights) of one axis of decode_device_resize() / decode_device_resize_view()
+    -- numpy arrays first[out_size], count[out_size] (uint32) and weights[out_size, 65] (int32, 22-bit fixed point, 0 behind a row's
+    count): output sample o is clamp((2^21 + sum_t in[first[o] + t] * weights[o, t]) >> 22, 0, 255).  filter: "bilinear" (the
+    default) or "bicubic", whose weights may be negative.  The text the kernel runs; no GPU needed.  A size of 0 or in_size >
+    32 * out_size (bicubic: 16 * out_size) raises FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
     in_size, out_size = int(in_size), int(out_size)
     if not (0 <= in_size <= 0xFFFFFFFF and 0 <= out_size <= 0xFFFFFFFF):
         raise ValueError(f"resize_weights: sizes {in_size} -> {out_size} (32 bits, not negative)")
+    fid = _filter_id("resize_weights", filter)
     first, count = np.zeros(max(out_size, 1), dtype=np.uint32), np.zeros(max(out_size, 1), dtype=np.uint32)
     weights = np.zeros((max(out_size, 1), _lib.RESIZE_MAX_TAPS), dtype=np.int32)
-    check(_lib.load().fpng_amd_resize_weights(in_size, out_size, first.ctypes.data_as(C.POINTER(C.c_uint32)), count.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                              weights.ctypes.data_as(C.POINTER(C.c_int32))))
+    ptrs = (first.ctypes.data_as(C.POINTER(C.c_uint32)), count.ctypes.data_as(C.POINTER(C.c_uint32)), weights.ctypes.data_as(C.POINTER(C.c_int32)))
+    if fid == FILTER_BILINEAR:
+        check(_lib.load().fpng_amd_resize_weights(in_size, out_size, *ptrs))
+    else:
+        check(_lib.load().fpng_amd_resize_weights_filter(in_size, out_size, fid, *ptrs))
     return first, count, weights
+
+
+def _view_record(who, full, window, filter, mirror, rec=None):
+    """(full_w, full_h), (x, y, w, h) or None for the whole, a filter, a mirror flag -> an fpng_amd_resize_view"""
+    fw, fh = (int(v) for v in full)
+    x, y, w, h = (0, 0, fw, fh) if window is None else (int(v) for v in window)
+    if min(fw, fh, x, y, w, h) < 0 or max(fw, fh, x, y, w, h) > 0xFFFFFFFF:
+        raise ValueError(f"{who}: full {tuple(full)}, window {window} (values of 32 bits, not negative)")
+    rec = _lib.ResizeView() if rec is None else rec
+    rec.full_w, rec.full_h, rec.x, rec.y, rec.w, rec.h = fw, fh, x, y, w, h
+    rec.flags, rec.filter = (RESIZE_MIRROR if mirror else 0), _filter_id(who, filter)
+    return rec
+
+
+def resize_view_source(crop, full, window=None, filter="bilinear"):
+    """fpng_amd_resize_view_source: the box (x, y, w, h) of the file's pixels that the taps of a view reach -- the window (x, y, w,
+    h) (None: the whole) of the crop (x, y, w, h) resized to full = (full_w, full_h) by `filter` -- which is what the crop stage of
+    decode_device_resize_view() decodes: crop_tiles(file_w, file_h, box) names the tiles that run.  No GPU needed.  Whatever the
+    call refuses in a record raises FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
+    x, y, w, h = (int(v) for v in crop)
+    if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
+        raise ValueError(f"resize_view_source: crop {tuple(crop)} (four values of 32 bits, not negative)")
+    c, box = _lib.Crop(x, y, w, h), _lib.Crop()
+    v = _view_record("resize_view_source", full, window, filter, False)
+    check(_lib.load().fpng_amd_resize_view_source(C.byref(c), C.byref(v), C.byref(box)))
+    return box.x, box.y, box.w, box.h
+
+
+def center_crop_view(file_w, file_h, resize, crop):
+    """torchvision's Resize(resize) + CenterCrop(crop) of a file_w x file_h file as (crop_box, full, window) for
+    decode_device_resize_view(): crop_box = the whole file, full = (full_w, full_h) with the shorter side at `resize` and the
+    longer at int(resize * long / short), window = the (x, y, cw, ch) centre of it (crop: an int, or (h, w)) with
+    left = int(round((full_w - cw) / 2.0)), top = int(round((full_h - ch) / 2.0)).  ValueError if the window does not fit
+    (torchvision would pad)."""
+    file_w, file_h, resize = int(file_w), int(file_h), int(resize)
+    ch, cw = (int(crop), int(crop)) if isinstance(crop, (int, np.integer)) else (int(v) for v in crop)
+    if min(file_w, file_h, resize, ch, cw) < 1:
+        raise ValueError(f"center_crop_view: file {file_w} x {file_h}, resize {resize}, crop {ch} x {cw} (all at least 1)")
+    if file_w <= file_h:
+        full_w, full_h = resize, int(resize * file_h / file_w)
+    else:
+        full_w, full_h = int(resize * file_w / file_h), resize
+    if cw > full_w or ch > full_h:
+        raise ValueError(f"center_crop_view: a {cw} x {ch} window does not fit the resized {full_w} x {full_h} image (no padding)")
+    left, top = int(round((full_w - cw) / 2.0)), int(round((full_h - ch) / 2.0))
+    return (0, 0, file_w, file_h), (full_w, full_h), (left, top, cw, ch)
 
 
 SYNTH_KINDS = {"noise": 0, "solid": 1, "grad": 2, "blocks": 3}
@@ -576,6 +644,16 @@ class DecodeBatchResize(_DecodeBatchViews):
     def __init__(self, pngs, outs, arr, res, device_data, keep, crops, sizes, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
         self.crops, self.sizes, self.fmt = crops, sizes, fmt
+
+
+class DecodeBatchResizeView(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_resize_view() returns: the same for one fpng_amd_decode_batch(_device)_planar_resize_view() call
+    (crops: the fpng_amd_crop[n]; views: the fpng_amd_resize_view[n]; outs: the caller's (c, window h, window w) views, uint8 or all
+    of one float dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No other call takes this descriptor."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, crops, views, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.crops, self.views, self.fmt = crops, views, fmt
 
 
 class Encoder:
@@ -996,7 +1074,7 @@ class Encoder:
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize)):
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView)):
             raise ValueError("decode_device_ex: a planar, float or crop descriptor (decode_device_planar, decode_device_float, decode_device_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if not batch.device_data:
@@ -1008,7 +1086,7 @@ class Encoder:
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize)):
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView)):
             raise ValueError("decode_batch_ex: a planar, float or crop descriptor (decode_batch_planar, decode_batch_float, decode_batch_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if batch.device_data:
@@ -1114,7 +1192,7 @@ class Encoder:
         return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt)
 
     def _decode_float(self, who, fn, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop, DecodeBatchResize)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_float() makes this one's)")
         batch = pngs if isinstance(pngs, DecodeBatchFloat) else self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias)
         if batch.device_data != device_data:
@@ -1193,7 +1271,7 @@ class Encoder:
         return DecodeBatchCrop(list(pngs), list(outs), arr, res, device_data, keep, carr, fmt)
 
     def _decode_crop(self, who, fn, device_data, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchResize)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchResize, DecodeBatchResizeView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_crop() makes this one's)")
         if isinstance(pngs, DecodeBatchCrop):
             batch = pngs
@@ -1288,7 +1366,7 @@ class Encoder:
         return DecodeBatchResize(list(pngs), list(outs), arr, res, device_data, keep, carr, sarr, fmt)
 
     def _decode_resize(self, who, fn, device_data, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResizeView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize() makes this one's)")
         if isinstance(pngs, DecodeBatchResize):
             batch = pngs
@@ -1327,6 +1405,130 @@ class Encoder:
         """fpng_amd_decode_batch_planar_resize: decode_device_resize() for files in host memory (bytes)."""
         return self._decode_resize("decode_batch_resize", self.lib.fpng_amd_decode_batch_planar_resize, False, pngs, crops, outs, size, mirror, dtype, order,
                                    bottom_up, mean, std, scale, bias, results)
+
+    @staticmethod
+    def make_decode_batch_resize_view(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
+                                      scale=None, bias=None):
+        """Descriptor (fpng_amd_png_planar[n], fpng_amd_crop[n], fpng_amd_resize_view[n], the fpng_amd_float_format if any and the
+        result records) for decode_device_resize_view() / decode_batch_resize_view(): files, crops, destinations and constants as
+        for make_decode_batch_resize().  full: (full_w, full_h), the size each crop is resized to, or one per file; window: the
+        (x, y, w, h) of that resized image that is written, or one per file -- None: the whole of it; filter: "bilinear" or
+        "bicubic" (FILTER_*), or one per file; mirror: one bool, or one per file.  A destination's (h, w) is its window's, else
+        ValueError.  Resize(256) + CenterCrop(224): crop, full, window = center_crop_view(file_w, file_h, 256, 224).  The call
+        refuses (FpngAmdError) an empty crop or window, a window that leaves the full size and a crop of more than 32 x (bicubic:
+        16 x) the full size in w or h."""
+        who = "make_decode_batch_resize_view"
+        n = len(pngs)
+        if len(crops) != n or len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(crops)} crops, {len(outs)} destinations")
+
+        def per_file(v, one, what):
+            vs = [v] * n if one(v) else list(v)
+            if len(vs) != n:
+                raise ValueError(f"{who}: {n} files, {len(vs)} {what}")
+            return vs
+
+        def is_ints(v):
+            return all(isinstance(a, (int, np.integer)) for a in v)
+
+        fulls = per_file(full, lambda v: len(v) == 2 and is_ints(v), "full sizes")
+        windows = per_file(window, lambda v: v is None or (len(v) == 4 and is_ints(v)), "windows")
+        filters = per_file(filter, lambda v: isinstance(v, (str, int, np.integer)), "filters")
+        mirrors = [bool(m) for m in per_file(mirror, lambda v: isinstance(v, (bool, int, np.bool_)), "mirror flags")]
+        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        is_u8 = dtypes == {torch.uint8}
+        fmt = None
+        if is_u8:
+            if any(v is not None for v in (mean, std, scale, bias)):
+                raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
+        else:
+            sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
+            fmt = _lib.FloatFormat()
+            for k in range(4):
+                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        orders = [order] * n if isinstance(order, str) else list(order)
+        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        arr = (_lib.PngPlanarIn * n)()
+        carr = (_lib.Crop * n)()
+        varr = (_lib.ResizeView * n)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        for i, (p, t) in enumerate(zip(pngs, outs)):
+            if is_u8:
+                ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
+            else:
+                ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
+            x, y, w, h = (int(v) for v in crops[i])
+            if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
+                raise ValueError(f"{who}: crop {tuple(crops[i])} of file {i} (four values of 32 bits, not negative)")
+            v = _view_record(who, fulls[i], windows[i], filters[i], mirrors[i], varr[i])
+            c, oh, ow = t.shape
+            if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
+                raise ValueError(f"{who}: destination {i} is {ow} x {oh}, its window {v.w} x {v.h}")
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            carr[i].x, carr[i].y, carr[i].w, carr[i].h = x, y, w, h
+            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
+            arr[i].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
+        return DecodeBatchResizeView(list(pngs), list(outs), arr, res, device_data, keep, carr, varr, fmt)
+
+    def _decode_resize_view(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize)):
+            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize_view() makes this one's)")
+        if isinstance(pngs, DecodeBatchResizeView):
+            batch = pngs
+        else:
+            if crops is None or full is None:
+                raise ValueError(f"{who}: crops, an (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
+            if outs is None:  # (c = 3 planes of the window's size each; files with alpha lose it)
+                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
+                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+                one_full = len(full) == 2 and all(isinstance(a, (int, np.integer)) for a in full)
+                one_win = window is None or (len(window) == 4 and all(isinstance(a, (int, np.integer)) for a in window))
+                if one_full and one_win:  # one size: one (n, 3, h, w) tensor and its slices
+                    ow, oh = (int(window[2]), int(window[3])) if window is not None else (int(full[0]), int(full[1]))
+                    outs = list(torch.empty((len(pngs), 3, oh, ow), dtype=dtype, device=f"cuda:{self.device}"))
+                else:
+                    fulls = [full] * len(pngs) if one_full else list(full)
+                    wins = [window] * len(pngs) if one_win else list(window)
+                    sizes = [(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fulls, wins)]
+                    outs = [torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes]
+            batch = self.make_decode_batch_resize_view(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_resize_view)" if device_data else "device memory (decode_device_resize_view)"))
+        if not all(t.is_cuda for t in batch.outs):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, batch.crops, batch.views, len(batch.arr), C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_resize_view(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                                  bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_device_planar_resize_view: uint8 CUDA tensors holding whole files; of each the crop (x, y, w, h) is
+        resized to full = (full_w, full_h) by `filter` ("bilinear" or "bicubic": Pillow's 8-bit rules) --
+        never materialised -- and the window (x, y, w, h) of that image is written to its (c, h, w) device tensor view, mirrored
+        where asked, as bytes or normalised floats (make_decode_batch_resize_view() has the rules) -> list of (status, the caller's
+        view or None, channels_in_file).  Resize(256) + CenterCrop(224) + Normalize in one call: crops, full and window from
+        center_crop_view().  Only the source pixels the window's taps reach are decoded (resize_view_source()).  outs=None
+        allocates (3, h, w) tensors of `dtype`, one (n, 3, h, w) tensor's slices where all files share one size.  pngs may be a
+        make_decode_batch_resize_view() descriptor of device files; results=False returns it."""
+        return self._decode_resize_view("decode_device_resize_view", self.lib.fpng_amd_decode_batch_device_planar_resize_view, True, pngs, crops, outs, full, window,
+                                        filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
+
+    def decode_batch_resize_view(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                                 bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_planar_resize_view: decode_device_resize_view() for files in host memory (bytes)."""
+        return self._decode_resize_view("decode_batch_resize_view", self.lib.fpng_amd_decode_batch_planar_resize_view, False, pngs, crops, outs, full, window,
+                                        filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

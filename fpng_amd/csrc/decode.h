@@ -231,7 +231,7 @@ void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUn
 // file of the launch has and the most LDS one of its tiles needs (resize_tile_lds); flt (host, or NULL: bytes): the elements.
 // false: max_tiles or lds_bytes is out of range, nothing was launched.
 struct DecResize;
-bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt);
+bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt, bool any_filter);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

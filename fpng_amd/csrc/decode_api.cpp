@@ -335,10 +335,11 @@ struct Batch {
     std::vector<DecCrop> crop;            // ... a record per job, uploaded with the job records
     DecCrop *d_crops = nullptr;
     std::vector<uint32_t> col_blocks;     // per job: the column blocks its tiles are numbered over (a crop's: dec_crop_tiles)
-    // fpng_amd_decode_batch(_device)_planar_resize: the files' output sizes (else NULL; needs crops).  The jobs' out / pitch /
-    // plane_pitch then describe the crop's uint8 planes in the scratch (mid_total bytes, 16-byte aligned per file), which the crop
-    // kernels fill as for uint8 destinations; the caller's destination travels in a record per job to dec_resize_kernel
-    const fpng_amd_resize *sizes = nullptr;
+    // fpng_amd_decode_batch(_device)_planar_resize(_view): the files' views (else NULL; needs crops; the plain resize call's sizes
+    // arrive as whole-window bilinear views).  The jobs' out / pitch / plane_pitch then describe uint8 planes in the scratch
+    // (mid_total bytes, 16-byte aligned per file) of the BOX of the crop that the view's taps reach, which the crop kernels fill as
+    // for uint8 destinations of that box; the caller's destination travels in a record per job to dec_resize_kernel
+    const fpng_amd_resize_view *sizes = nullptr;
     std::vector<DecResize> resize; // (src: an offset into the intermediate planes until place_files())
     std::vector<uint32_t> resize_tiles, resize_lds; // per job: its tiles per plane, the LDS bytes of one
     DecResize *d_resize = nullptr;
@@ -372,6 +373,16 @@ struct Batch {
     uint32_t nj() const { return (uint32_t)jobs.size(); }
     double since() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
+
+// the pixels of the file that the taps of view z of `crop` reach (fpng_amd_resize_view_source): per axis first(x) ..
+// first(x + w - 1) + count(x + w - 1) of the crop's samples.  z has passed check_view_records()
+DecCrop view_box(const DecCrop &crop, const fpng_amd_resize_view &z)
+{
+    uint32_t x0, x1, y0, y1;
+    resize_source_span(z.filter, crop.w, z.full_w, z.x, z.w, &x0, &x1);
+    resize_source_span(z.filter, crop.h, z.full_h, z.y, z.h, &y0, &y1);
+    return {crop.x + x0, crop.y + y0, x1 - x0, y1 - y0};
+}
 
 // ---- parse: every file's container and stream header (device-resident ones: from their heads and tails), job record, table key ----
 int parse_files(Batch &b)
@@ -433,12 +444,18 @@ int parse_files(Batch &b)
                 continue;
             }
         }
+        // (a view: judged on the caller's crop above; what the crop stage decodes, and the tiles that run, are its box's)
+        const DecCrop whole_crop = crop;
+        if (b.sizes) {
+            crop = view_box(crop, b.sizes[i]);
+            dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb); // (inside the caller's crop: never outside)
+        }
         // (only files that will be written need room)
         int64_t pitch = 0, plane_pitch = 0;
         if (b.planar) {
             const fpng_amd_png_planar &x = b.planar[i];
             // (a crop: its own w and h; a resize: the output size's)
-            const uint32_t dest_w = b.sizes ? b.sizes[i].out_w : crop.w, dest_h = b.sizes ? b.sizes[i].out_h : crop.h;
+            const uint32_t dest_w = b.sizes ? b.sizes[i].w : crop.w, dest_h = b.sizes ? b.sizes[i].h : crop.h;
             const uint64_t roww = (uint64_t)dest_w * b.elem; // bytes of a plane's row (float planes: w elements)
             if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
             pitch = x.row_pitch ? x.row_pitch : (int64_t)roww;
@@ -469,15 +486,17 @@ int parse_files(Batch &b)
         j.out = f.d_pixels, j.sub_base = b.sub_total;
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
         if (b.sizes) {
-            // the crop kernels write tight uint8 planes of the crop's size into the scratch; the resize reads them and writes the caller's
-            const fpng_amd_resize &z = b.sizes[i];
+            // the crop kernels write tight uint8 planes of the box's size into the scratch; the resize reads them and writes the caller's
+            const fpng_amd_resize_view &z = b.sizes[i];
             if (crop.w >= 0x80000000u) return fail(FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31");
-            const uint64_t tiles = (uint64_t)((z.out_w + kResizeTileW - 1) / kResizeTileW) * ((z.out_h + kResizeTileH - 1) / kResizeTileH);
+            const uint64_t tiles = (uint64_t)((z.w + kResizeTileW - 1) / kResizeTileW) * ((z.h + kResizeTileH - 1) / kResizeTileH);
             if (tiles * 4 * kResizeBlock >= (1ull << 32)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16");
             DecResize rs = {};
             rs.src = (const uint8_t *)(uintptr_t)b.mid_total, rs.dst = (uint8_t *)f.d_pixels, rs.plane_pitch = plane_pitch, rs.pitch = (int32_t)pitch;
-            rs.in_w = crop.w, rs.in_h = crop.h, rs.out_w = z.out_w, rs.out_h = z.out_h, rs.flags = z.flags, rs.planes = desired;
-            rs.taps_x = resize_max_taps(crop.w, z.out_w), rs.taps_y = resize_max_taps(crop.h, z.out_h), rs.rows = resize_tile_rows(crop.h, z.out_h);
+            rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags, rs.planes = desired, rs.filter = z.filter;
+            rs.x = z.x, rs.y = z.y, rs.w = z.w, rs.h = z.h;
+            rs.box_x = crop.x - whole_crop.x, rs.box_y = crop.y - whole_crop.y, rs.box_w = crop.w, rs.box_h = crop.h;
+            rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
             b.resize.push_back(rs);
             b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
             j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
@@ -689,7 +708,9 @@ int finish_group(Batch &b, uint32_t gi)
     //  the spans of the destination and nothing else, whatever a file's status turns out to be)
     if (b.sizes) {
         const uint32_t tiles = *std::max_element(b.resize_tiles.begin() + g.j0, b.resize_tiles.begin() + g.j1), lds = *std::max_element(b.resize_lds.begin() + g.j0, b.resize_lds.begin() + g.j1);
-        if (!launch_dec_resize(b.s, b.d_resize + g.j0, g.j1 - g.j0, tiles, lds, b.flt)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
+        // (a group of bilinear files -- the plain resize call's always are -- runs the instantiation without the second filter)
+        const bool any_filter = std::any_of(b.resize.begin() + g.j0, b.resize.begin() + g.j1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
+        if (!launch_dec_resize(b.s, b.d_resize + g.j0, g.j1 - g.j0, tiles, lds, b.flt, any_filter)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
     }
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
@@ -847,10 +868,10 @@ int collect_results(Batch &b)
 
 // ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
 // planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's; sizes (with
-// crops): ... fpng_amd_decode_batch(_device)_planar_resize's
+// crops): ... fpng_amd_decode_batch(_device)_planar_resize_view's (the plain resize call's: as whole-window bilinear views)
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
-                 const fpng_amd_resize *sizes = nullptr)
+                 const fpng_amd_resize_view *sizes = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -1127,14 +1148,34 @@ int check_resize_records(const fpng_amd_crop *crops, const fpng_amd_resize *size
     }
     return FPNG_AMD_OK;
 }
+static_assert(sizeof(fpng_amd_resize_view) == 32 && offsetof(fpng_amd_resize_view, x) == 8 && offsetof(fpng_amd_resize_view, flags) == 24 && offsetof(fpng_amd_resize_view, filter) == 28,
+              "fpng_amd_resize_view layout");
+static_assert(FPNG_AMD_FILTER_BILINEAR == kResizeBilinear && FPNG_AMD_FILTER_BICUBIC == kResizeBicubic, "the kernel's filters");
+// views: fpng_amd_decode_batch(_device)_planar_resize_view's, a view per file (with crops; the destinations are then the views'
+// windows).  As check_resize_records: no file, no encoder, no device
+int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t n)
+{
+    for (uint32_t i = 0; crops && views && i < n; i++) {
+        const fpng_amd_resize_view &z = views[i];
+        if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
+        if (!z.full_w || !z.full_h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty full size (full_w or full_h is 0)");
+        if (!z.w || !z.h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty window (w or h is 0)");
+        if ((uint64_t)z.x + z.w > z.full_w || (uint64_t)z.y + z.h > z.full_h) return fail(FPNG_AMD_ERR_INVALID_ARG, "a window that leaves the full size (x + w <= full_w and y + h <= full_h)");
+        if (z.flags & ~(uint32_t)FPNG_AMD_RESIZE_MIRROR) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_resize_view::flags bits");
+        if (z.filter >= kResizeFilters) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown filter (FPNG_AMD_FILTER_BILINEAR, _BICUBIC)");
+        if (!resize_scale_ok(crops[i].w, z.full_w, z.filter) || !resize_scale_ok(crops[i].h, z.full_h, z.filter))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, z.filter == kResizeBicubic ? "a crop of more than 16 x its full size (bicubic: w <= 16 * full_w and h <= 16 * full_h)"
+                                                                              : "a crop of more than 32 x its full size (bilinear: w <= 32 * full_w and h <= 32 * full_h)");
+    }
+    return FPNG_AMD_OK;
+}
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
-                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize *sizes = nullptr)
+                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && i < n; i++)
         if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
-    if (int rc = check_resize_records(crops, sizes, n)) return rc;
-    DecFloat flt = {};
+    DecFloat flt = {}; // (views: their entry points have judged them -- check_resize_records / check_view_records)
     uint32_t elem = 1;
     if (fmt) {
         if (fmt->dtype >= kDecFloatTypes) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown element type (FPNG_AMD_F32, _F16, _BF16)");
@@ -1153,7 +1194,14 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
         plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, sizes);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views);
+}
+// the plain resize call's records as views: the whole of the resized crop, bilinear
+std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
+{
+    std::vector<fpng_amd_resize_view> v(n);
+    for (uint32_t i = 0; i < n; i++) v[i] = {sizes[i].out_w, sizes[i].out_h, 0, 0, sizes[i].out_w, sizes[i].out_h, sizes[i].flags, FPNG_AMD_FILTER_BILINEAR};
+    return v;
 }
 } // namespace
 
@@ -1199,7 +1247,7 @@ extern "C" int fpng_amd_decode_batch_planar_resize(fpng_amd_encoder *e, const fp
 {
     if (!crops || !sizes) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null sizes" : "null crops");
     if (int rc = check_resize_records(crops, sizes, n)) return rc;
-    return decode_files_planar(e, files, n, results, false, fmt, crops, sizes);
+    return decode_files_planar(e, files, n, results, false, fmt, crops, whole_views(sizes, n).data());
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize *sizes, uint32_t n,
@@ -1207,7 +1255,33 @@ extern "C" int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *e, c
 {
     if (!crops || !sizes) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null sizes" : "null crops");
     if (int rc = check_resize_records(crops, sizes, n)) return rc;
-    return decode_files_planar(e, files, n, results, true, fmt, crops, sizes);
+    return decode_files_planar(e, files, n, results, true, fmt, crops, whole_views(sizes, n).data());
+}
+
+extern "C" int fpng_amd_decode_batch_planar_resize_view(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t n,
+                                                        const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!crops || !views) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null views" : "null crops");
+    if (int rc = check_view_records(crops, views, n)) return rc;
+    return decode_files_planar(e, files, n, results, false, fmt, crops, views);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_resize_view(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
+                                                               uint32_t n, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!crops || !views) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null views" : "null crops");
+    if (int rc = check_view_records(crops, views, n)) return rc;
+    return decode_files_planar(e, files, n, results, true, fmt, crops, views);
+}
+
+// the source pixels, in the file's coordinates, that the taps of a view of a crop reach: what the crop stage decodes
+extern "C" int fpng_amd_resize_view_source(const fpng_amd_crop *crop, const fpng_amd_resize_view *view, fpng_amd_crop *box)
+{
+    if (!crop || !view || !box) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (int rc = check_view_records(crop, view, 1)) return rc;
+    const DecCrop b = view_box({crop->x, crop->y, crop->w, crop->h}, *view);
+    box->x = b.x, box->y = b.y, box->w = b.w, box->h = b.h;
+    return FPNG_AMD_OK;
 }
 
 // out_size rows of kResizeMaxTaps weights (those behind a row's count: 0), first and count per output sample: resize_weights_of,
@@ -1219,7 +1293,22 @@ extern "C" int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint
     for (uint32_t o = 0; o < out_size; o++) {
         int32_t *K = weights + (size_t)o * kResizeMaxTaps;
         std::fill(K, K + kResizeMaxTaps, 0);
-        count[o] = resize_weights_of(in_size, out_size, o, &first[o], K, 1);
+        count[o] = resize_weights_of<kResizeBilinear>(in_size, out_size, o, &first[o], K, 1);
+    }
+    return FPNG_AMD_OK;
+}
+
+extern "C" int fpng_amd_resize_weights_filter(uint32_t in_size, uint32_t out_size, uint32_t filter, uint32_t *first, uint32_t *count, int32_t *weights)
+{
+    if (!first || !count || !weights) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (filter >= kResizeFilters) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown filter (FPNG_AMD_FILTER_BILINEAR, _BICUBIC)");
+    if (!resize_scale_ok(in_size, out_size, filter))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, filter == kResizeBicubic ? "in_size and out_size are at least 1, and in_size <= 16 * out_size (bicubic)"
+                                                                       : "in_size and out_size are at least 1, and in_size <= 32 * out_size (bilinear)");
+    for (uint32_t o = 0; o < out_size; o++) {
+        int32_t *K = weights + (size_t)o * kResizeMaxTaps;
+        std::fill(K, K + kResizeMaxTaps, 0);
+        count[o] = resize_weights_of(filter, in_size, out_size, o, &first[o], K, 1);
     }
     return FPNG_AMD_OK;
 }

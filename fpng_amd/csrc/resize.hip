@@ -1,10 +1,13 @@
-// resize.hip -- the second stage of fpng_amd_decode_batch(_device)_planar_resize: the crop's uint8 planes, which the crop kernels of
-// decode.hip (dec_unfilter_crop_kernel<-1, *>, dec_stored_crop_kernel<-1>) left in the decode scratch, are resized to the caller's
-// out_w x out_h planes by the rule of resize.h, mirrored where asked, and written once -- bytes, or the float call's elements.
+// resize.hip -- the second stage of fpng_amd_decode_batch(_device)_planar_resize and _planar_resize_view: uint8 planes of the crop,
+// which the crop kernels of decode.hip (dec_unfilter_crop_kernel<-1, *>, dec_stored_crop_kernel<-1>) left in the decode scratch,
+// are resized by the rule of resize.h (bilinear or bicubic), mirrored where asked, and written once -- bytes, or the float
+// call's elements.  What is written is a WINDOW (x, y, w, h) of the crop resized to full_w x full_h (the plain resize call: the
+// whole of it); the scratch holds the box of the crop that the window's taps reach, so a tap at crop column f is byte f - box_x of
+// its row.
 //
-// One workgroup per (file, plane, tile of kResizeTileW x kResizeTileH output samples):
-//   1. a thread per output column / row of the tile computes that sample's first tap, tap count and weights (resize_weights_of,
-//      the text the host's fpng_amd_resize_weights runs) into LDS: Kx[t][column], Ky[t][row];
+// One workgroup per (file, plane, tile of kResizeTileW x kResizeTileH samples of the window):
+//   1. a thread per column / row of the tile computes the first tap, tap count and weights of sample x + column / y + row of the
+//      full image (resize_weights_of, the text the host's fpng_amd_resize_weights_filter runs) into LDS: Kx[t][column], Ky[t][row];
 //   2. the horizontal pass over the source rows the tile's Ky reach -- a wave per row, a lane per column, the row's bytes from
 //      global memory (neighbouring lanes read neighbouring bytes: the same cache lines), the weights from LDS without bank
 //      conflicts (consecutive lanes, consecutive dwords) -- into LDS bytes T[row][column];
@@ -12,7 +15,8 @@
 //      broadcast), then the mirror as an index of the store, the fmaf and the conversion of the float call, and stores that are
 //      contiguous along a row for the wave in either direction.
 // The sums are integers, so their order is free; no atomics, nothing between workgroups.  LDS is sized by the launch for the
-// largest tile of its files (resize_tile_lds): ~8 KB for a 1080p crop -> 224 x 224, 55 KB at the 32 x limit.
+// largest tile of its files (resize_tile_lds): ~8 KB for a 1080p crop -> 224 x 224, 55 KB at the bilinear 32 x limit, 41 KB at the
+// bicubic 16 x limit.
 #include "decode.h"
 #include "float_store.h"
 #include "resize.h"
@@ -25,41 +29,44 @@ namespace fpng_amd {
 
 namespace {
 
-template <int kDtype>
+// kAnyFilter: the launch's records may ask for the bicubic filter; false: all of them are bilinear (the plain resize call's launches,
+// and a view call's whose files are), and the kernel holds the triangle's weight code alone
+template <int kDtype, bool kAnyFilter>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResize *recs, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
     const DecResize r = recs[blockIdx.z];
     const uint32_t plane = blockIdx.y;
-    const uint32_t tiles_x = (r.out_w + kResizeTileW - 1) / kResizeTileW, tiles_y = (r.out_h + kResizeTileH - 1) / kResizeTileH;
+    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW, tiles_y = (r.h + kResizeTileH - 1) / kResizeTileH;
     if (plane >= r.planes || (uint64_t)blockIdx.x >= (uint64_t)tiles_x * tiles_y) return; // (the grid is the launch's largest file)
     const uint32_t ox0 = blockIdx.x % tiles_x * kResizeTileW, oq0 = blockIdx.x / tiles_x * kResizeTileH;
-    const uint32_t nq = std::min(kResizeTileH, r.out_h - oq0);
+    const uint32_t nq = std::min(kResizeTileH, r.h - oq0);
     int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
     uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
     uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
     const uint32_t tid = threadIdx.x;
-    // ---- 1. the tile's weights ----
+    const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
+    // ---- 1. the tile's weights (first: relative to the box, which the host made of these samples' own first and count -- resize_taps) ----
     if (tid < kResizeTileW) {
-        uint32_t first = 0, count = 0;
-        if (ox0 + tid < r.out_w) count = resize_weights_of(r.in_w, r.out_w, ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
-        fx[tid] = first, cx[tid] = count;
+        uint32_t first = r.box_x, count = 0;
+        if (ox0 + tid < r.w) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        fx[tid] = first - r.box_x, cx[tid] = count;
     } else if (tid < kResizeTileW + kResizeTileH) {
         const uint32_t q = tid - kResizeTileW;
-        uint32_t first = 0, count = 0;
-        if (q < nq) count = resize_weights_of(r.in_h, r.out_h, oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
-        fy[q] = first, cy[q] = count;
+        uint32_t first = r.box_y, count = 0;
+        if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        fy[q] = first - r.box_y, cy[q] = count;
     }
     __syncthreads();
     // ---- 2. the horizontal pass: source rows row0 .. row0 + nrows - 1 (first and first + count do not decrease with the sample) ----
     const uint32_t row0 = fy[0];
     const uint32_t nrows = std::min(fy[nq - 1] + cy[nq - 1] - row0, r.rows); // (the host's bound holds: T has r.rows rows)
     const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
-    const uint8_t *const P = r.src + (uint64_t)plane * r.in_w * r.in_h;
+    const uint8_t *const P = r.src + (uint64_t)plane * r.box_w * r.box_h;
     {
         const uint32_t first = fx[o], count = cx[o];
         for (uint32_t j = wave; j < nrows; j += kResizeBlock / kResizeTileW) {
-            const uint8_t *s = P + (uint64_t)(row0 + j) * r.in_w + first;
+            const uint8_t *s = P + (uint64_t)(row0 + j) * r.box_w + first;
             int32_t sum = 1 << (kResizeBits - 1);
             for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
             T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
@@ -67,8 +74,8 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
     }
     __syncthreads();
     // ---- 3. the vertical pass, the mirror, the element ----
-    if (ox0 + o >= r.out_w) return;
-    const uint32_t col = r.flags & kResizeMirror ? r.out_w - 1 - (ox0 + o) : ox0 + o;
+    if (ox0 + o >= r.w) return;
+    const uint32_t col = r.flags & kResizeMirror ? r.w - 1 - (ox0 + o) : ox0 + o;
     constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
     // (c is the FILE's channel: plane b of the record is channel b, whatever the planes' order in memory -- a select, not an index
     //  into the argument, which would put it into private memory)
@@ -93,16 +100,17 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
 
 } // namespace
 
-bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt)
+bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
 {
     using Kernel = void (*)(const DecResize *, DecFloat);
-    static const Kernel kernels[kDecFloatTypes + 1] = {dec_resize_kernel<-1>, dec_resize_kernel<0>, dec_resize_kernel<1>, dec_resize_kernel<2>};
+    static const Kernel kernels[2][kDecFloatTypes + 1] = {{dec_resize_kernel<-1, false>, dec_resize_kernel<0, false>, dec_resize_kernel<1, false>, dec_resize_kernel<2, false>},
+                                                          {dec_resize_kernel<-1, true>, dec_resize_kernel<0, true>, dec_resize_kernel<1, true>, dec_resize_kernel<2, true>}};
     // (a launch holds fewer than 2^32 threads, its z dimension at most 65535 workgroups)
     const uint64_t per_file = (uint64_t)max_tiles * 4 * kResizeBlock;
     if (!max_tiles || per_file >= (1ull << 32) || lds_bytes > 65536u) return false;
     const uint32_t step = (uint32_t)std::min<uint64_t>(32768u, ((1ull << 32) - 1) / per_file);
     for (uint32_t j0 = 0; j0 < n; j0 += step)
-        hipLaunchKernelGGL(kernels[flt ? flt->dtype + 1 : 0], dim3(max_tiles, 4, std::min(step, n - j0)), dim3(kResizeBlock), lds_bytes, s, recs + j0, flt ? *flt : DecFloat{});
+        hipLaunchKernelGGL(kernels[any_filter][flt ? flt->dtype + 1 : 0], dim3(max_tiles, 4, std::min(step, n - j0)), dim3(kResizeBlock), lds_bytes, s, recs + j0, flt ? *flt : DecFloat{});
     return true;
 }
 

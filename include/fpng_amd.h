@@ -619,9 +619,10 @@ int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_
  *      of 0, reserved != 0, unknown flag bits, and a crop past the scale limit (crop.w <= 32 * out_w and crop.h <= 32 * out_h; at
  *      most 65 taps; upscaling is unbounded).  A crop that leaves the image stays that file's own status 67; statuses,
  *      FPNG_AMD_DECODE_UNDECIDED, FPNG_AMD_DECODE_MAX_ROUNDS and the checksum flags behave as in the crop call.
- *      Not offered: other filters and antialias off; premultiplied alpha (every plane is resized on its own, as an "L" image);
- *      a resize without a crop record (give the whole image as the crop); the interleaved destinations, fpng_amd_decode_host and
- *      the fpng:: drop-in.
+ *      Not offered by THIS call: a window of the resized image and the bicubic filter (fpng_amd_decode_batch_planar_resize_view,
+ *      below, has both).  Not offered at all: antialias off, nearest and Lanczos; premultiplied alpha (every plane is resized on
+ *      its own, as an "L" image); a resize without a crop record (give the whole image as the crop); the interleaved destinations,
+ *      fpng_amd_decode_host and the fpng:: drop-in.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize with dlsym. ---- */
 typedef struct fpng_amd_resize {
     uint32_t out_w, out_h, flags, reserved;
@@ -635,6 +636,58 @@ int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *enc, const fpng
 /* The weights of one axis (no GPU needed; the text the kernel runs): first[o], count[o] and weights[o * 65 + t], t < count[o] (0
  * behind them), for o < out_size.  FPNG_AMD_ERR_INVALID_ARG for a null argument, a size of 0 and in_size > 32 * out_size. */
 int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint32_t *first, uint32_t *count, int32_t *weights /* out_size x 65 */);
+/* ---- decoding a WINDOW of each file's crop resized to a fixed size, with a choice of filter: the resize call above generalised
+ *      twice.  Per file a crop and an fpng_amd_resize_view record: R is the crop resized to full_w x full_h -- never
+ *      materialised -- and the destination is the w x h window of R at (x, y).  RandomResizedCrop(size) is the view
+ *      {out_w, out_h, 0, 0, out_w, out_h} of a random crop (with FPNG_AMD_FILTER_BILINEAR: byte for byte the call above); the
+ *      evaluation transform Resize(256) + CenterCrop(224) is the crop (0, 0, file w, file h) with full = the resized size and the
+ *      centre window.  Resize-then-crop is NOT crop-then-resize: a sample at the window's edge takes taps from pixels outside the
+ *      window's pre-image.  Taps never leave the CROP.
+ *      The filter is a kernel function k_f and a base support s_f in the rule above, which is otherwise unchanged:
+ *          support = s_f * fs;   k[t] = k_f(((t + first) - center + 0.5) * ss)
+ *          K[o][t] = k[t] < 0 ? (int)(-0.5 + k[t] * 4194304.0) : (int)(0.5 + k[t] * 4194304.0)
+ *      FPNG_AMD_FILTER_BILINEAR: s_f = 1, k_f = tri -- the weights of the call above, bit for bit.
+ *      FPNG_AMD_FILTER_BICUBIC:  s_f = 2, k_f = the Keys cubic with a = -0.5 (Pillow's Image.BICUBIC), with x = |a|:
+ *          x < 1: ((1.5 * x - 2.5) * x) * x + 1;    x < 2: (((x - 5) * x + 8) * x - 4) * -0.5;    else 0
+ *      in double, operations in the order written, no fused multiply-add.  Its weights may be negative, so the clamp of a pass is
+ *      live at 0 and at 255, after the horizontal pass (bytes) and after the vertical one; >> 22 is an arithmetic shift.  The sum of
+ *      a sample's |K| is 1.167 * 2^22 at the scale limit and below 1.27 * 2^22 anywhere, so a pass's sum stays inside 32 bits.
+ *      Element (c, q, i) of the destination is R_c[y + q][x + i], with FPNG_AMD_RESIZE_MIRROR R_c[y + q][x + w - 1 - i], as a byte
+ *      or through the float call's fmaf and conversion.  The fpng_amd_png_planar record describes planes of w x h elements (the
+ *      window's), with every rule of the resize call.
+ *      The crop stage decodes only the BOX of source pixels that the window's taps reach -- per axis first(x) .. first(x + w - 1) +
+ *      count(x + w - 1) of the crop's samples, fpng_amd_resize_view_source -- so fpng_amd_decode_crop_tiles(box) names the tiles of
+ *      the pixel pass that run, and the statuses are those of fpng_amd_decode_batch_planar_crop for that box; under
+ *      FPNG_AMD_VERIFY_ADLER32 every tile runs.  FPNG_AMD_DECODE_CROP_OUTSIDE (67) is judged on the caller's crop.
+ *      Call-level errors, with nothing launched and before the encoder is looked at: FPNG_AMD_ERR_INVALID_ARG for null crops or
+ *      views, an empty crop, full_w, full_h, w or h of 0, x + w > full_w or y + h > full_h (in 64 bits), unknown flag bits, an
+ *      unknown filter, and a crop past the filter's scale limit against the FULL size: bilinear crop.w <= 32 * full_w, bicubic
+ *      crop.w <= 16 * full_w (the same for h; at most 65 taps either way).  The bound of 2^22 tiles of 64 x 16 applies to the window.
+ *      Not offered: antialias off, nearest, Lanczos; premultiplied alpha; the interleaved destinations, fpng_amd_decode_host and
+ *      the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize_view with dlsym. ---- */
+typedef struct fpng_amd_resize_view {
+    uint32_t full_w, full_h; /* the size the CROP is resized to (never materialised) */
+    uint32_t x, y, w, h;     /* the window of that full_w x full_h image that is written: the destination is w x h */
+    uint32_t flags;          /* FPNG_AMD_RESIZE_MIRROR */
+    uint32_t filter;         /* FPNG_AMD_FILTER_BILINEAR, FPNG_AMD_FILTER_BICUBIC */
+} fpng_amd_resize_view;      /* 32 bytes */
+#define FPNG_AMD_FILTER_BILINEAR 0u
+#define FPNG_AMD_FILTER_BICUBIC 1u
+int fpng_amd_decode_batch_planar_resize_view(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, const fpng_amd_crop *crops,
+                                             const fpng_amd_resize_view *views, uint32_t n, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                             fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_planar_resize_view(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, const fpng_amd_crop *crops,
+                                                    const fpng_amd_resize_view *views, uint32_t n,
+                                                    const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results);
+/* fpng_amd_resize_weights for either filter (FPNG_AMD_FILTER_BILINEAR: the same answer).  FPNG_AMD_ERR_INVALID_ARG also for an
+ * unknown filter and for in_size past the filter's limit (32 * out_size, bicubic 16 * out_size). */
+int fpng_amd_resize_weights_filter(uint32_t in_size, uint32_t out_size, uint32_t filter, uint32_t *first, uint32_t *count,
+                                   int32_t *weights /* out_size x 65 */);
+/* The source pixels that a view's taps reach, in the FILE's coordinates (no GPU needed; the text the decoder's own plan uses; the
+ * twin of fpng_amd_decode_crop_tiles): box.x = crop.x + first_x(x), box.w = first_x(x + w - 1) + count_x(x + w - 1) - first_x(x), the
+ * y axis alike.  FPNG_AMD_ERR_INVALID_ARG for a null argument and for everything the view call refuses in a record. */
+int fpng_amd_resize_view_source(const fpng_amd_crop *crop, const fpng_amd_resize_view *view, fpng_amd_crop *box);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

@@ -31,4 +31,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   VERIFY_CRC32, VERIFY_ADLER32, DECODE_BAD_CRC32, DECODE_BAD_ADLER32,
                   DECODE_CROP_OUTSIDE, DecodeBatchCrop, crop_tiles,
                   RESIZE_MIRROR, DecodeBatchResize, resize_weights,
-                  FILTER_BILINEAR, FILTER_BICUBIC, DecodeBatchResizeView, resize_view_source, center_crop_view)
+                  FILTER_BILINEAR, FILTER_BICUBIC, DecodeBatchResizeView, resize_view_source, center_crop_view,
+                  DecodeBatchMultiView, views_source)

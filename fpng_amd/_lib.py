@@ -88,6 +88,10 @@ class ResizeView(C.Structure):  # fpng_amd_resize_view: 32 bytes, a window of a 
                 ("flags", C.c_uint32), ("filter", C.c_uint32)]
 
 
+class ViewDest(C.Structure):  # fpng_amd_view_dest: 32 bytes, the destination of ONE view of fpng_amd_decode_batch(_device)_planar_views
+    _fields_ = [("d_pixels", C.c_void_p), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("pixels_cap", C.c_size_t)]
+
+
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1  # FPNG_AMD_FILTER_*
 RESIZE_MIRROR = 1  # FPNG_AMD_RESIZE_MIRROR
 RESIZE_MAX_TAPS = 65  # weights per output sample of fpng_amd_resize_weights
@@ -212,6 +216,11 @@ SIGNATURES = {
     "fpng_amd_decode_batch_device_planar_resize_view": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_resize_weights_filter": (_int, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_int32)]),
     "fpng_amd_resize_view_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(Crop)]),
+    "fpng_amd_decode_batch_planar_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                                  C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                                         C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_views_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(Crop)]),
     "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),
     "fpng_amd_encoder_decode_verify": (_u32, [_vp]),

@@ -335,6 +335,60 @@ def resize_view_source(crop, full, window=None, filter="bilinear"):
     return box.x, box.y, box.w, box.h
 
 
+def _is_ints(v, k):
+    return not isinstance(v, (str, bytes)) and hasattr(v, "__len__") and len(v) == k and all(isinstance(a, (int, np.integer)) for a in v)
+
+
+# what one value of a view's argument looks like (make_decode_batch_views: once for all, per file or per view)
+_VIEW_ARG = {"full sizes": lambda v: _is_ints(v, 2), "windows": lambda v: v is None or _is_ints(v, 4),
+             "filters": lambda v: isinstance(v, (str, int, np.integer)), "mirror flags": lambda v: isinstance(v, (bool, int, np.bool_)),
+             "plane orders": lambda v: isinstance(v, str), "bottom_up flags": lambda v: isinstance(v, (bool, np.bool_))}
+
+
+def _per_view(who, counts, v, what):
+    """an argument of the views call -> a list per file of a value per view.  v: one value (for all views of all files), a
+    sequence with an entry per file, each entry one value (for the file's views) or a sequence with a value per view"""
+    one = _VIEW_ARG[what]
+    if one(v):
+        return [[v] * c for c in counts]
+    vs = list(v)
+    if len(vs) != len(counts):
+        raise ValueError(f"{who}: {len(counts)} files, {len(vs)} {what}")
+    out = []
+    for i, (c, f) in enumerate(zip(counts, vs)):
+        fs = [f] * c if one(f) else list(f)
+        if len(fs) != c or not all(one(a) for a in fs):
+            raise ValueError(f"{who}: file {i} has {c} views, its {what}: {f!r}")
+        out.append(fs)
+    return out
+
+
+def _crop_record(who, crop, rec=None):
+    x, y, w, h = (int(v) for v in crop)
+    if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
+        raise ValueError(f"{who}: crop {tuple(crop)} (four values of 32 bits, not negative)")
+    rec = _lib.Crop() if rec is None else rec
+    rec.x, rec.y, rec.w, rec.h = x, y, w, h
+    return rec
+
+
+def views_source(crops, fulls, windows=None, filters="bilinear"):
+    """fpng_amd_views_source: the ONE box (x, y, w, h) of a file's pixels that decode_device_views() decodes for a file with these
+    views -- the bounding rectangle of resize_view_source(crops[k], fulls[k], windows[k], filters[k]).  crops: an (x, y, w, h) per
+    view; fulls, windows, filters: one per view, or one for all.  crop_tiles(file_w, file_h, box) names the tiles that run.  No GPU
+    needed.  Whatever the call refuses in a record, and no view at all, raise FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
+    who = "views_source"
+    count = len(crops)
+    fulls, windows, filters = (_per_view(who, [count], [v] if _VIEW_ARG[what](v) else [list(v)], what)[0]
+                               for v, what in ((fulls, "full sizes"), (windows, "windows"), (filters, "filters")))
+    carr, varr, box = (_lib.Crop * max(count, 1))(), (_lib.ResizeView * max(count, 1))(), _lib.Crop()
+    for k in range(count):
+        _crop_record(who, crops[k], carr[k])
+        _view_record(who, fulls[k], windows[k], filters[k], False, varr[k])
+    check(_lib.load().fpng_amd_views_source(carr, varr, count, C.byref(box)))
+    return box.x, box.y, box.w, box.h
+
+
 def center_crop_view(file_w, file_h, resize, crop):
     """torchvision's Resize(resize) + CenterCrop(crop) of a file_w x file_h file as (crop_box, full, window) for
     decode_device_resize_view(): crop_box = the whole file, full = (full_w, full_h) with the shorter side at `resize` and the
@@ -654,6 +708,22 @@ class DecodeBatchResizeView(_DecodeBatchViews):
     def __init__(self, pngs, outs, arr, res, device_data, keep, crops, views, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
         self.crops, self.views, self.fmt = crops, views, fmt
+
+
+class DecodeBatchMultiView(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_views() returns: the same for one fpng_amd_decode_batch(_device)_planar_views() call, which
+    writes SEVERAL views of each file (counts: the uint32[n] views per file; crops, views, dests: the fpng_amd_crop,
+    fpng_amd_resize_view and fpng_amd_view_dest records, one per view, file 0's first; outs: per file the list of the caller's (c,
+    window h, window w) views, uint8 or all of one float dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No
+    other call takes this descriptor."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.counts, self.crops, self.views, self.dests, self.fmt = counts, crops, views, dests, fmt
+
+    def results(self):
+        """list, per file, of (status, the list of the caller's own destination views (filled in place) or None, channels_in_file)"""
+        return [(r.status, list(ts) if r.status == 0 else None, r.channels_in_file) for r, ts in zip(self.res, self.outs)]
 
 
 class Encoder:
@@ -1074,7 +1144,7 @@ class Encoder:
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView)):
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
             raise ValueError("decode_device_ex: a planar, float or crop descriptor (decode_device_planar, decode_device_float, decode_device_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if not batch.device_data:
@@ -1086,7 +1156,7 @@ class Encoder:
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView)):
+        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
             raise ValueError("decode_batch_ex: a planar, float or crop descriptor (decode_batch_planar, decode_batch_float, decode_batch_crop)")
         batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
         if batch.device_data:
@@ -1192,7 +1262,7 @@ class Encoder:
         return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt)
 
     def _decode_float(self, who, fn, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_float() makes this one's)")
         batch = pngs if isinstance(pngs, DecodeBatchFloat) else self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias)
         if batch.device_data != device_data:
@@ -1271,7 +1341,7 @@ class Encoder:
         return DecodeBatchCrop(list(pngs), list(outs), arr, res, device_data, keep, carr, fmt)
 
     def _decode_crop(self, who, fn, device_data, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchResize, DecodeBatchResizeView)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_crop() makes this one's)")
         if isinstance(pngs, DecodeBatchCrop):
             batch = pngs
@@ -1366,7 +1436,7 @@ class Encoder:
         return DecodeBatchResize(list(pngs), list(outs), arr, res, device_data, keep, carr, sarr, fmt)
 
     def _decode_resize(self, who, fn, device_data, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResizeView)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResizeView, DecodeBatchMultiView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize() makes this one's)")
         if isinstance(pngs, DecodeBatchResize):
             batch = pngs
@@ -1482,7 +1552,7 @@ class Encoder:
         return DecodeBatchResizeView(list(pngs), list(outs), arr, res, device_data, keep, carr, varr, fmt)
 
     def _decode_resize_view(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize)):
+        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchMultiView)):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize_view() makes this one's)")
         if isinstance(pngs, DecodeBatchResizeView):
             batch = pngs
@@ -1529,6 +1599,122 @@ class Encoder:
         """fpng_amd_decode_batch_planar_resize_view: decode_device_resize_view() for files in host memory (bytes)."""
         return self._decode_resize_view("decode_batch_resize_view", self.lib.fpng_amd_decode_batch_planar_resize_view, False, pngs, crops, outs, full, window,
                                         filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
+
+    @staticmethod
+    def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
+                                scale=None, bias=None):
+        """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
+        per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
+        decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
+        one (x, y, w, h) per view, at least one; outs[i]: the list of its destinations, a (c, window h, window w) view each, all of
+        one c per file and one dtype per call.  full, window, filter, mirror, order and bottom_up: one value for all views, or a list
+        with an entry per file, each entry one value for the file's views or a list with a value per view.  Constants as for
+        make_decode_batch_resize()."""
+        who = "make_decode_batch_views"
+        n = len(pngs)
+        if len(crops) != n or len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(crops)} lists of crops, {len(outs)} lists of destinations")
+        crops, outs = [list(c) for c in crops], [list(o) for o in outs]
+        counts = [len(c) for c in crops]
+        for i in range(n):
+            if counts[i] < 1 or len(outs[i]) != counts[i]:
+                raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
+        fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
+        filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
+        dtypes = {t.dtype for ts in outs for t in ts if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        is_u8 = dtypes == {torch.uint8}
+        fmt = None
+        if is_u8:
+            if any(v is not None for v in (mean, std, scale, bias)):
+                raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
+        else:
+            sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
+            fmt = _lib.FloatFormat()
+            for k in range(4):
+                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        total = sum(counts)
+        arr = (_lib.PngPlanarIn * n)()
+        narr = (C.c_uint32 * n)(*counts)
+        carr, varr, darr = (_lib.Crop * total)(), (_lib.ResizeView * total)(), (_lib.ViewDest * total)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        at = 0
+        for i, p in enumerate(pngs):
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            chans = {t.shape[0] for t in outs[i]}
+            if len(chans) != 1:
+                raise ValueError(f"{who}: the destinations of file {i} share one channel count, not {sorted(chans)}")
+            arr[i].num_chans = chans.pop()  # (d_pixels, the pitches and pixels_cap stay NULL / 0: the destinations are the views')
+            for k, t in enumerate(outs[i]):
+                if is_u8:
+                    ptr, rp, pp = dest_layout_planar(t, orders[i][k], bool(ups[i][k]))
+                else:
+                    ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i][k], bool(ups[i][k]))
+                _crop_record(f"{who}: file {i}", crops[i][k], carr[at])
+                v = _view_record(who, fulls[i][k], windows[i][k], filters[i][k], bool(mirrors[i][k]), varr[at])
+                c, oh, ow = t.shape
+                if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
+                    raise ValueError(f"{who}: destination {k} of file {i} is {ow} x {oh}, its window {v.w} x {v.h}")
+                darr[at].d_pixels, darr[at].row_pitch, darr[at].plane_pitch = ptr, rp, pp
+                darr[at].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
+                at += 1
+        return DecodeBatchMultiView(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+
+    def _decode_views(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+        if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
+            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
+        if isinstance(pngs, DecodeBatchMultiView):
+            batch = pngs
+        else:
+            if crops is None or full is None:
+                raise ValueError(f"{who}: crops, a list of (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
+            if outs is None or any(o is None for o in outs):  # (c = 3 planes of each window's size; files with alpha lose it)
+                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
+                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+                counts = [len(c) for c in crops]
+                fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
+                sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
+                outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
+                        for i in range(len(crops))]
+            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
+        if not all(t.is_cuda for ts in batch.outs for t in ts):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
+        decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
+        multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
+        (c, h, w) device tensor view, mirrored where asked, as bytes or normalised floats: exactly what decode_device_resize_view()
+        writes for that view alone (make_decode_batch_views() has the nesting rules) -> list, per file, of (status, the list of
+        the caller's views or None, channels_in_file).  A file is decoded ONCE, the bounding rectangle of its views' source boxes
+        (views_source()); two small views far apart decode everything between them, and listing the file twice in
+        decode_device_resize_view() may then be cheaper.  outs=None (or None for a file) allocates (3, h, w) tensors of `dtype`.
+        pngs may be a make_decode_batch_views() descriptor of device files; results=False returns it."""
+        return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, True, pngs, crops, outs, full, window, filter, mirror,
+                                  dtype, order, bottom_up, mean, std, scale, bias, results)
+
+    def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
+        return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, False, pngs, crops, outs, full, window, filter, mirror,
+                                  dtype, order, bottom_up, mean, std, scale, bias, results)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

@@ -227,11 +227,16 @@ void launch_dec_crc(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, uint32_t
 void launch_dec_finish(hipStream_t s, const DecJob *jobs, uint32_t n_jobs, DecUnfPlan plan, DecPlaced placed, uint32_t *status, uint32_t epoch, bool any_stored, bool layout = false,
                        const int64_t *plane_pitch = nullptr, const DecVerify *verify = nullptr, const DecFloat *flt = nullptr, const DecCrop *crops = nullptr);
 // The second stage of fpng_amd_decode_batch_planar_resize (resize.h, resize.hip): recs (device) -- a record per file of the launch,
-// whose crops' uint8 planes the crop kernels in front of it on the stream wrote; max_tiles / lds_bytes: the most tiles per plane a
+// whose boxes' uint8 planes the crop kernels in front of it on the stream wrote; max_tiles / lds_bytes: the most tiles per plane a
 // file of the launch has and the most LDS one of its tiles needs (resize_tile_lds); flt (host, or NULL: bytes): the elements.
 // false: max_tiles or lds_bytes is out of range, nothing was launched.
 struct DecResize;
 bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt, bool any_filter);
+// The same for fpng_amd_decode_batch(_device)_planar_views, whose records -- several per file -- mix sizes and plane counts: a grid
+// of exactly the records' workgroups.  pre (device) and h_pre (host, the same words): n + 1 entries, the workgroups (planes x tiles)
+// of the batch's records in front of each of recs[0 .. n]; split into launches of fewer than 2^24 workgroups.  false: a record
+// without or with too many workgroups, or lds_bytes out of range; nothing more is launched.
+bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter);
 #ifdef FPNG_DEC_SYNC_TIMING
 void dec_dump_sync_times(const char *path, uint32_t n_blocks); // (diagnostic build: dec_sync_kernel<false>'s per-workgroup time stamps of the last launch)
 #endif

@@ -338,11 +338,19 @@ struct Batch {
     // fpng_amd_decode_batch(_device)_planar_resize(_view): the files' views (else NULL; needs crops; the plain resize call's sizes
     // arrive as whole-window bilinear views).  The jobs' out / pitch / plane_pitch then describe uint8 planes in the scratch
     // (mid_total bytes, 16-byte aligned per file) of the BOX of the crop that the view's taps reach, which the crop kernels fill as
-    // for uint8 destinations of that box; the caller's destination travels in a record per job to dec_resize_kernel
+    // for uint8 destinations of that box; the caller's destination travels in a record per VIEW to dec_resize_kernel.
+    // fpng_amd_decode_batch(_device)_planar_views: file i has view_count[i] views, whose crops / sizes / dests records start at
+    // view_ofs[i] (else NULL / empty: one view per file, record i, its destination the planar file's); a job's box is then the
+    // bounding rectangle of its views' boxes, and job k's records are job_rec[k] .. job_rec[k + 1] - 1
     const fpng_amd_resize_view *sizes = nullptr;
-    std::vector<DecResize> resize; // (src: an offset into the intermediate planes until place_files())
-    std::vector<uint32_t> resize_tiles, resize_lds; // per job: its tiles per plane, the LDS bytes of one
+    const uint32_t *view_count = nullptr;
+    const fpng_amd_view_dest *dests = nullptr;
+    std::vector<uint32_t> view_ofs, job_rec;
+    std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
+    std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
+    std::vector<uint64_t> resize_pre; // (views call) per view and one more: the workgroups -- planes x tiles -- of the views in front
     DecResize *d_resize = nullptr;
+    uint64_t *d_resize_pre = nullptr;
     size_t mid_total = 0;
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     std::vector<Parsed> ps;
@@ -371,6 +379,8 @@ struct Batch {
     Worker *uploader = nullptr;
     ~Batch() { if (uploader) uploader->wait(); } // (every way out waits for the uploader first: it works on this struct)
     uint32_t nj() const { return (uint32_t)jobs.size(); }
+    uint32_t first_view(uint32_t file) const { return view_count ? view_ofs[file] : file; }
+    uint32_t views_of(uint32_t file) const { return view_count ? view_count[file] : 1u; }
     double since() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
 
@@ -382,6 +392,22 @@ DecCrop view_box(const DecCrop &crop, const fpng_amd_resize_view &z)
     resize_source_span(z.filter, crop.w, z.full_w, z.x, z.w, &x0, &x1);
     resize_source_span(z.filter, crop.h, z.full_h, z.y, z.h, &y0, &y1);
     return {crop.x + x0, crop.y + y0, x1 - x0, y1 - y0};
+}
+
+// the ONE box a file with these count >= 1 views decodes (fpng_amd_views_source): the bounding rectangle of their boxes.  The
+// records have passed check_view_records(); the crops may leave the image, so the far edges are taken in 64 bits and the answer's
+// w / h saturate (such a file is refused before its box is used).  each (or NULL): the views' own boxes, view_box() of each
+DecCrop views_box(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, DecCrop *each = nullptr)
+{
+    uint64_t x0 = UINT64_MAX, y0 = UINT64_MAX, x1 = 0, y1 = 0;
+    for (uint32_t k = 0; k < count; k++) {
+        const DecCrop c = {crops[k].x, crops[k].y, crops[k].w, crops[k].h};
+        const DecCrop v = view_box({0, 0, c.w, c.h}, views[k]); // (within the crop: no sum wraps)
+        if (each) each[k] = {c.x + v.x, c.y + v.y, v.w, v.h};
+        x0 = std::min<uint64_t>(x0, (uint64_t)c.x + v.x), x1 = std::max<uint64_t>(x1, (uint64_t)c.x + v.x + v.w);
+        y0 = std::min<uint64_t>(y0, (uint64_t)c.y + v.y), y1 = std::max<uint64_t>(y1, (uint64_t)c.y + v.y + v.h);
+    }
+    return {(uint32_t)x0, (uint32_t)y0, (uint32_t)std::min<uint64_t>(x1 - x0, UINT32_MAX), (uint32_t)std::min<uint64_t>(y1 - y0, UINT32_MAX)};
 }
 
 // ---- parse: every file's container and stream header (device-resident ones: from their heads and tails), job record, table key ----
@@ -404,6 +430,9 @@ int parse_files(Batch &b)
     }
     uint32_t *const table = nullptr; // (no host-side lookup table: the header reader only checks the code)
     HeaderMemo memo;
+    std::vector<DecResize> file_recs; // (the records of the file at hand's views, and their source boxes)
+    std::vector<DecCrop> file_boxes;
+    b.resize_pre.assign(1, 0);
     b.ps.resize(b.n);
     for (uint32_t i = 0; i < b.n; i++) {
         const fpng_amd_png &f = b.files[i];
@@ -437,38 +466,70 @@ int parse_files(Batch &b)
         // (a crop that leaves the image: the file's own outcome -- it is not decoded and needs no room)
         DecCrop crop = {0, 0, p.w, p.h};
         uint32_t crop_nseg = 0, crop_cb0 = 0, crop_ncb = 0;
+        const uint32_t v0 = b.first_view(i), nv = b.views_of(i); // (the file's records of crops / sizes / dests)
         if (b.crops) {
-            crop = {b.crops[i].x, b.crops[i].y, b.crops[i].w, b.crops[i].h};
-            if (!dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb)) {
+            bool inside = true; // (every one of the file's crops)
+            for (uint32_t v = v0; v < v0 + nv && inside; v++) {
+                crop = {b.crops[v].x, b.crops[v].y, b.crops[v].w, b.crops[v].h};
+                inside = dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb);
+            }
+            if (!inside) {
                 r.status = FPNG_AMD_DECODE_CROP_OUTSIDE;
                 continue;
             }
         }
-        // (a view: judged on the caller's crop above; what the crop stage decodes, and the tiles that run, are its box's)
-        const DecCrop whole_crop = crop;
+        // (views: judged on the caller's crops above; what the crop stage decodes, and the tiles that run, are those of the ONE box
+        //  that holds the boxes of all of the file's views)
         if (b.sizes) {
-            crop = view_box(crop, b.sizes[i]);
-            dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb); // (inside the caller's crop: never outside)
+            file_boxes.resize(nv);
+            crop = views_box(b.crops + v0, b.sizes + v0, nv, file_boxes.data());
+            dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb); // (inside the caller's crops: never outside)
         }
         // (only files that will be written need room)
         int64_t pitch = 0, plane_pitch = 0;
         if (b.planar) {
+            // a destination of dest_w x dest_h elements per plane (a crop: its own w and h; a view: its window's): its pitches, its room
+            auto judge = [&](uint8_t *d_pixels, int64_t row_pitch, int64_t plane_pitch_in, size_t pixels_cap, uint32_t dest_w, uint32_t dest_h) -> int {
+                const uint64_t roww = (uint64_t)dest_w * b.elem; // bytes of a plane's row (float planes: w elements)
+                if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
+                pitch = row_pitch ? row_pitch : (int64_t)roww;
+                const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
+                if (step < roww) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
+                const uint64_t span = (uint64_t)(dest_h - 1) * step + roww; // a plane, from its lowest row's first byte
+                plane_pitch = plane_pitch_in ? plane_pitch_in : (int64_t)((uint64_t)dest_h * step);
+                if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
+                const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
+                if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
+                if (pstep > (UINT64_MAX >> 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
+                if (!d_pixels || pixels_cap < (uint64_t)(desired - 1) * pstep + span)
+                    return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w (* element bytes)");
+                return FPNG_AMD_OK;
+            };
             const fpng_amd_png_planar &x = b.planar[i];
-            // (a crop: its own w and h; a resize: the output size's)
-            const uint32_t dest_w = b.sizes ? b.sizes[i].w : crop.w, dest_h = b.sizes ? b.sizes[i].h : crop.h;
-            const uint64_t roww = (uint64_t)dest_w * b.elem; // bytes of a plane's row (float planes: w elements)
-            if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
-            pitch = x.row_pitch ? x.row_pitch : (int64_t)roww;
-            const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
-            if (step < roww) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
-            const uint64_t span = (uint64_t)(dest_h - 1) * step + roww; // a plane, from its lowest row's first byte
-            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)((uint64_t)dest_h * step);
-            if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
-            const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
-            if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
-            if (pstep > (UINT64_MAX >> 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
-            if (!f.d_pixels || f.pixels_cap < (uint64_t)(desired - 1) * pstep + span)
-                return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w (* element bytes)");
+            if (!b.sizes) {
+                if (int rc = judge((uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap, crop.w, crop.h)) return rc;
+            } else {
+                // a record per view for dec_resize_kernel, which reads the view's own box inside the planes of the job's box (src: an
+                // offset from those planes' first byte until the file is known to become a job)
+                if (crop.w >= 0x80000000u) return fail(FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31");
+                file_recs.clear();
+                for (uint32_t v = v0; v < v0 + nv; v++) {
+                    const fpng_amd_resize_view &z = b.sizes[v];
+                    const fpng_amd_view_dest dest = b.dests ? b.dests[v] : fpng_amd_view_dest{(uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap};
+                    if (int rc = judge(dest.d_pixels, dest.row_pitch, dest.plane_pitch, dest.pixels_cap, z.w, z.h)) return rc;
+                    if (resize_tiles(z.w, z.h) * 4 * kResizeBlock >= (1ull << 32)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16");
+                    const DecCrop whole_crop = {b.crops[v].x, b.crops[v].y, b.crops[v].w, b.crops[v].h}, box = file_boxes[v - v0];
+                    DecResize rs = {};
+                    rs.src = (const uint8_t *)(uintptr_t)((size_t)(box.y - crop.y) * crop.w + (box.x - crop.x));
+                    rs.src_pitch = crop.w, rs.src_plane_pitch = (uint64_t)crop.w * crop.h;
+                    rs.dst = dest.d_pixels, rs.plane_pitch = plane_pitch, rs.pitch = (int32_t)pitch;
+                    rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags, rs.planes = desired, rs.filter = z.filter;
+                    rs.x = z.x, rs.y = z.y, rs.w = z.w, rs.h = z.h;
+                    rs.box_x = box.x - whole_crop.x, rs.box_y = box.y - whole_crop.y;
+                    rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
+                    file_recs.push_back(rs);
+                }
+            }
         } else if (b.ex) {
             const uint64_t row = (uint64_t)p.w * desired;
             pitch = b.ex[i].row_pitch ? b.ex[i].row_pitch : (int64_t)row;
@@ -487,18 +548,14 @@ int parse_files(Batch &b)
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
         if (b.sizes) {
             // the crop kernels write tight uint8 planes of the box's size into the scratch; the resize reads them and writes the caller's
-            const fpng_amd_resize_view &z = b.sizes[i];
-            if (crop.w >= 0x80000000u) return fail(FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31");
-            const uint64_t tiles = (uint64_t)((z.w + kResizeTileW - 1) / kResizeTileW) * ((z.h + kResizeTileH - 1) / kResizeTileH);
-            if (tiles * 4 * kResizeBlock >= (1ull << 32)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16");
-            DecResize rs = {};
-            rs.src = (const uint8_t *)(uintptr_t)b.mid_total, rs.dst = (uint8_t *)f.d_pixels, rs.plane_pitch = plane_pitch, rs.pitch = (int32_t)pitch;
-            rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags, rs.planes = desired, rs.filter = z.filter;
-            rs.x = z.x, rs.y = z.y, rs.w = z.w, rs.h = z.h;
-            rs.box_x = crop.x - whole_crop.x, rs.box_y = crop.y - whole_crop.y, rs.box_w = crop.w, rs.box_h = crop.h;
-            rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
-            b.resize.push_back(rs);
-            b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
+            b.job_rec.push_back((uint32_t)b.resize.size());
+            for (DecResize &rs : file_recs) {
+                rs.src += b.mid_total; // (an offset until place_files())
+                const uint64_t tiles = resize_tiles(rs.w, rs.h);
+                b.resize.push_back(rs);
+                b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
+                b.resize_pre.push_back(b.resize_pre.back() + rs.planes * tiles);
+            }
             j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
             pitch = (int64_t)crop.w, plane_pitch = (int64_t)((uint64_t)crop.w * crop.h);
             b.mid_total += ((size_t)plane_pitch * desired + 15) & ~(size_t)15;
@@ -536,6 +593,7 @@ int parse_files(Batch &b)
         b.jobs.push_back(j);
         b.job_file.push_back(i);
     }
+    b.job_rec.push_back((uint32_t)b.resize.size());
     if (tracing()) fprintf(stderr, "[decode] +%.0f us: %u files parsed, %u lookup tables wanted\n", b.since(), b.n, b.luts.count());
     return FPNG_AMD_OK;
 }
@@ -548,7 +606,7 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.sizes ? nj * sizeof(DecResize) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * sizeof(DecResize)), o_pre = sc.carve(b.view_count ? b.resize_pre.size() * sizeof(uint64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
     const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
@@ -561,6 +619,7 @@ int place_files(Batch &b)
     b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
     b.d_crops = b.crops ? (DecCrop *)(base + o_crop) : nullptr;
     b.d_resize = b.sizes ? (DecResize *)(base + o_resize) : nullptr;
+    b.d_resize_pre = b.view_count ? (uint64_t *)(base + o_pre) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -589,7 +648,10 @@ int place_files(Batch &b)
         DecJob &j = b.jobs[k];
         const Parsed &p = b.ps[b.job_file[k]];
         if (!b.device_data) j.z = b.d.z + (size_t)(uintptr_t)j.z;
-        if (b.sizes) j.out = base + o_mid + (size_t)(uintptr_t)j.out, b.resize[k].src = j.out;
+        if (b.sizes) {
+            j.out = base + o_mid + (size_t)(uintptr_t)j.out;
+            for (uint32_t q = b.job_rec[k]; q < b.job_rec[k + 1]; q++) b.resize[q].src = base + o_mid + (size_t)(uintptr_t)b.resize[q].src;
+        }
         // (parse_files sized the CRC partials of a host-resident file for a stream that starts on a 16-byte boundary; dec_verify_kernel
         //  counts the ranges from the real address, and one more range than sized would be the next file's slot)
         if (!b.device_data && (b.verify & FPNG_AMD_VERIFY_CRC32) && ((uintptr_t)j.z & 15)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "decode scratch: a file's stream is not 16-byte aligned");
@@ -664,7 +726,8 @@ int plan_groups(Batch &b)
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
-    if (b.sizes) std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), nj * sizeof(DecResize));
+    if (b.sizes) std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), b.resize.size() * sizeof(DecResize));
+    if (b.view_count) std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), b.resize_pre.data(), b.resize_pre.size() * sizeof(uint64_t));
     return FPNG_AMD_OK;
 }
 
@@ -707,10 +770,15 @@ int finish_group(Batch &b, uint32_t gi)
     // (the resize: behind the group's pixel pass and stored copy on the same stream, on whatever the scratch then holds -- it writes
     //  the spans of the destination and nothing else, whatever a file's status turns out to be)
     if (b.sizes) {
-        const uint32_t tiles = *std::max_element(b.resize_tiles.begin() + g.j0, b.resize_tiles.begin() + g.j1), lds = *std::max_element(b.resize_lds.begin() + g.j0, b.resize_lds.begin() + g.j1);
-        // (a group of bilinear files -- the plain resize call's always are -- runs the instantiation without the second filter)
-        const bool any_filter = std::any_of(b.resize.begin() + g.j0, b.resize.begin() + g.j1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
-        if (!launch_dec_resize(b.s, b.d_resize + g.j0, g.j1 - g.j0, tiles, lds, b.flt, any_filter)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
+        const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1]; // (the records of the group's jobs)
+        const uint32_t tiles = *std::max_element(b.resize_tiles.begin() + r0, b.resize_tiles.begin() + r1), lds = *std::max_element(b.resize_lds.begin() + r0, b.resize_lds.begin() + r1);
+        // (a group of bilinear views -- the plain resize call's always are -- runs the instantiation without the second filter)
+        const bool any_filter = std::any_of(b.resize.begin() + r0, b.resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
+        // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
+        //  output per file keep the grid of the largest record)
+        const bool ok = b.view_count ? launch_dec_resize_exact(b.s, b.d_resize + r0, b.d_resize_pre + r0, b.resize_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
+                                     : launch_dec_resize(b.s, b.d_resize + r0, r1 - r0, tiles, lds, b.flt, any_filter);
+        if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
     }
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
@@ -868,10 +936,11 @@ int collect_results(Batch &b)
 
 // ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
 // planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's; sizes (with
-// crops): ... fpng_amd_decode_batch(_device)_planar_resize_view's (the plain resize call's: as whole-window bilinear views)
+// crops): ... fpng_amd_decode_batch(_device)_planar_resize_view's (the plain resize call's: as whole-window bilinear views); view_count
+// and dests (with sizes): ... fpng_amd_decode_batch(_device)_planar_views's, whose crops, sizes and dests hold a record per view
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
-                 const fpng_amd_resize_view *sizes = nullptr)
+                 const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -881,6 +950,11 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
+    if (view_count) { // (their sum fits 32 bits: decode_files_views)
+        b.view_count = view_count, b.dests = dests;
+        b.view_ofs.resize(n);
+        for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
+    }
     if (flt) b.flt = flt, b.elem = dec_float_bytes(flt->dtype);
     if ((rc = resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
@@ -1169,11 +1243,13 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
     }
     return FPNG_AMD_OK;
 }
+// view_count, dests: fpng_amd_decode_batch(_device)_planar_views's (decode_files_views has judged the counts and the records; crops and
+// views then hold a record per view, and the destinations, which `files` leave empty, are dests')
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
-                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr)
+                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    for (uint32_t i = 0; crops && i < n; i++)
+    for (uint32_t i = 0; crops && !view_count && i < n; i++)
         if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
     DecFloat flt = {}; // (views: their entry points have judged them -- check_resize_records / check_view_records)
     uint32_t elem = 1;
@@ -1194,7 +1270,32 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
         plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views);
+    uint64_t n_views = 0;
+    for (uint32_t i = 0; view_count && i < n; i++) n_views += view_count[i];
+    for (uint64_t v = 0; v < n_views; v++) { // (the same two rules for every view's destination)
+        const fpng_amd_view_dest &x = dests[v];
+        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (elem - 1))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
+        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
+    }
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests);
+}
+// fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
+static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
+int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
+                       const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data)
+{
+    if (!files || !view_count || !crops || !views || !dests || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!view_count[i]) return fail(FPNG_AMD_ERR_INVALID_ARG, "a view_count of 0 (every file has at least one view)");
+        if ((total += view_count[i]) > UINT32_MAX) return fail(FPNG_AMD_ERR_INVALID_ARG, "the sum of view_count does not fit 32 bits");
+    }
+    if (int rc = check_view_records(crops, views, (uint32_t)total)) return rc;
+    for (uint32_t i = 0; i < n; i++)
+        if (files[i].d_pixels || files[i].row_pitch || files[i].plane_pitch || files[i].pixels_cap)
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_png_planar::d_pixels, row_pitch, plane_pitch and pixels_cap must be NULL / 0: the destinations are the fpng_amd_view_dest records");
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1272,6 +1373,30 @@ extern "C" int fpng_amd_decode_batch_device_planar_resize_view(fpng_amd_encoder 
     if (!crops || !views) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null views" : "null crops");
     if (int rc = check_view_records(crops, views, n)) return rc;
     return decode_files_planar(e, files, n, results, true, fmt, crops, views);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                  const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                         const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt,
+                                                         fpng_amd_decode_result *results)
+{
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, true);
+}
+
+// the ONE box that a file with these views decodes: the bounding rectangle of the boxes below
+extern "C" int fpng_amd_views_source(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, fpng_amd_crop *box)
+{
+    if (!crops || !views || !box) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (!count) return fail(FPNG_AMD_ERR_INVALID_ARG, "a count of 0");
+    if (int rc = check_view_records(crops, views, count)) return rc;
+    const DecCrop b = views_box(crops, views, count);
+    box->x = b.x, box->y = b.y, box->w = b.w, box->h = b.h;
+    return FPNG_AMD_OK;
 }
 
 // the source pixels, in the file's coordinates, that the taps of a view of a crop reach: what the crop stage decodes

@@ -33,6 +33,7 @@
 // Double add, multiply, divide, compare and conversion are correctly rounded on the host and on gfx950; what could differ is a
 // multiply and an add contracted into one fused operation, which hipcc does in device code by default: contraction is off in here.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -186,21 +187,30 @@ FPNG_RESIZE_FN uint32_t resize_tile_lds(uint32_t taps_x, uint32_t taps_y, uint32
     return (taps_x * kResizeTileW + taps_y * kResizeTileH + 2u * (kResizeTileW + kResizeTileH)) * 4u + rows * kResizeTileW;
 }
 
-// a file's work for dec_resize_kernel: the window (x, y, w, h) of its crop (in_w x in_h) resized to full_w x full_h becomes the
-// caller's planes (dst: DecJob's rules -- row 0 of plane 0, signed byte pitches).  src holds the BOX of the crop that the window's
-// taps reach, as uint8 planes (tight: rows of box_w bytes, planes of box_w * box_h); box_x / box_y: its origin within the crop
+// a view's work for dec_resize_kernel: the window (x, y, w, h) of its crop (in_w x in_h) resized to full_w x full_h becomes the
+// caller's planes (dst: DecJob's rules -- row 0 of plane 0, signed byte pitches).  src is the first byte of the BOX of the crop
+// that the window's taps reach, inside the uint8 planes that the file's job decoded (rows src_pitch bytes apart, planes
+// src_plane_pitch: those of the job's own box, which holds the boxes of all of the file's views -- with one view they are the
+// view's box, tight); box_x / box_y: the view's box's origin within its crop, so a tap at crop column f is byte f - box_x of its row
 struct DecResize {
     const uint8_t *src;
     uint8_t *dst;
     int64_t plane_pitch;
+    uint64_t src_plane_pitch;
     int32_t pitch;
     uint32_t in_w, in_h, full_w, full_h, flags, planes;
     uint32_t taps_x, taps_y, rows; // what the tile's LDS is laid out with (resize_max_taps, resize_tile_rows)
     uint32_t filter;
     uint32_t x, y, w, h;
-    uint32_t box_x, box_y, box_w, box_h;
-    uint32_t pad_;
+    uint32_t box_x, box_y;
+    uint32_t src_pitch;
 };
-static_assert(sizeof(DecResize) == 104, "DecResize layout");
+static_assert(sizeof(DecResize) == 104 && offsetof(DecResize, src_plane_pitch) == 24 && offsetof(DecResize, pitch) == 32 && offsetof(DecResize, src_pitch) == 100, "DecResize layout");
+
+// tiles of kResizeTileW x kResizeTileH samples that a w x h window has per plane
+FPNG_RESIZE_FN uint64_t resize_tiles(uint32_t w, uint32_t h)
+{
+    return (uint64_t)((w + kResizeTileW - 1) / kResizeTileW) * ((h + kResizeTileH - 1) / kResizeTileH);
+}
 
 } // namespace fpng_amd

@@ -1,9 +1,10 @@
-// resize.hip -- the second stage of fpng_amd_decode_batch(_device)_planar_resize and _planar_resize_view: uint8 planes of the crop,
-// which the crop kernels of decode.hip (dec_unfilter_crop_kernel<-1, *>, dec_stored_crop_kernel<-1>) left in the decode scratch,
-// are resized by the rule of resize.h (bilinear or bicubic), mirrored where asked, and written once -- bytes, or the float
-// call's elements.  What is written is a WINDOW (x, y, w, h) of the crop resized to full_w x full_h (the plain resize call: the
-// whole of it); the scratch holds the box of the crop that the window's taps reach, so a tap at crop column f is byte f - box_x of
-// its row.
+// resize.hip -- the second stage of fpng_amd_decode_batch(_device)_planar_resize, _planar_resize_view and _planar_views: uint8
+// planes of the file, which the crop kernels of decode.hip (dec_unfilter_crop_kernel<-1, *>, dec_stored_crop_kernel<-1>) left in the
+// decode scratch, are resized by the rule of resize.h (bilinear or bicubic), mirrored where asked, and written once -- bytes, or
+// the float call's elements.  What is written is a WINDOW (x, y, w, h) of the crop resized to full_w x full_h (the plain resize
+// call: the whole of it); the scratch holds the box of the crop that the window's taps reach, so a tap at crop column f is byte
+// f - box_x of its row -- as a sub-rectangle of the planes of ONE box per file that holds the boxes of all of the file's views (the
+// views call; the other calls have one view per file, whose box those planes are).
 //
 // One workgroup per (file, plane, tile of kResizeTileW x kResizeTileH samples of the window):
 //   1. a thread per column / row of the tile computes the first tap, tap count and weights of sample x + column / y + row of the
@@ -29,24 +30,23 @@ namespace fpng_amd {
 
 namespace {
 
+// One tile of one plane of one record: the kernels below find the three and hand them over.
 // kAnyFilter: the launch's records may ask for the bicubic filter; false: all of them are bilinear (the plain resize call's launches,
 // and a view call's whose files are), and the kernel holds the triangle's weight code alone
 template <int kDtype, bool kAnyFilter>
-__global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResize *recs, DecFloat flt)
+__device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t plane, uint32_t tile, const DecFloat &flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
-    const DecResize r = recs[blockIdx.z];
-    const uint32_t plane = blockIdx.y;
-    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW, tiles_y = (r.h + kResizeTileH - 1) / kResizeTileH;
-    if (plane >= r.planes || (uint64_t)blockIdx.x >= (uint64_t)tiles_x * tiles_y) return; // (the grid is the launch's largest file)
-    const uint32_t ox0 = blockIdx.x % tiles_x * kResizeTileW, oq0 = blockIdx.x / tiles_x * kResizeTileH;
+    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW;
+    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
     const uint32_t nq = std::min(kResizeTileH, r.h - oq0);
     int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
     uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
     uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
     const uint32_t tid = threadIdx.x;
     const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
-    // ---- 1. the tile's weights (first: relative to the box, which the host made of these samples' own first and count -- resize_taps) ----
+    // ---- 1. the tile's weights (first: relative to the view's box, which the host made of these samples' own first and count --
+    //      resize_taps -- so first >= box_x and first >= box_y, whatever the file's other views are) ----
     if (tid < kResizeTileW) {
         uint32_t first = r.box_x, count = 0;
         if (ox0 + tid < r.w) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
@@ -62,11 +62,11 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
     const uint32_t row0 = fy[0];
     const uint32_t nrows = std::min(fy[nq - 1] + cy[nq - 1] - row0, r.rows); // (the host's bound holds: T has r.rows rows)
     const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
-    const uint8_t *const P = r.src + (uint64_t)plane * r.box_w * r.box_h;
+    const uint8_t *const P = r.src + (uint64_t)plane * r.src_plane_pitch;
     {
         const uint32_t first = fx[o], count = cx[o];
         for (uint32_t j = wave; j < nrows; j += kResizeBlock / kResizeTileW) {
-            const uint8_t *s = P + (uint64_t)(row0 + j) * r.box_w + first;
+            const uint8_t *s = P + (uint64_t)(row0 + j) * r.src_pitch + first;
             int32_t sum = 1 << (kResizeBits - 1);
             for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
             T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
@@ -98,7 +98,58 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
     }
 }
 
+// The rectangular grid of the calls with one output per file: (the launch's largest record's tiles, 4 planes, records); the surplus
+// workgroups of smaller records leave at once.
+template <int kDtype, bool kAnyFilter>
+__global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResize *recs, DecFloat flt)
+{
+    const DecResize r = recs[blockIdx.z];
+    if (blockIdx.y >= r.planes || (uint64_t)blockIdx.x >= resize_tiles(r.w, r.h)) return; // (the grid is the launch's largest file)
+    dec_resize_tile<kDtype, kAnyFilter>(r, blockIdx.y, blockIdx.x, flt);
+}
+
+// The exact grid of the views call, whose records mix sizes and plane counts by design: one dimension, a workgroup per (record,
+// plane, tile) and none in surplus.  pre[k] (k = 0 .. n): the workgroups of the batch's records in front of this launch's record k
+// (planes x tiles each, never 0), so workgroup b of the launch is number pre[0] + b of the batch and belongs to the last record
+// whose pre is not above that; the launch has pre[n] - pre[0] workgroups.  The search is the same for all of a workgroup's threads.
+template <int kDtype, bool kAnyFilter>
+__global__ __launch_bounds__(kResizeBlock) void dec_resize_exact_kernel(const DecResize *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
+{
+    const uint64_t g = pre[0] + blockIdx.x;
+    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const DecResize r = recs[lo];
+    const uint32_t rel = (uint32_t)(g - pre[lo]), tiles = (uint32_t)resize_tiles(r.w, r.h); // (planes x tiles < 2^24: the host's rule)
+    const uint32_t plane = rel / tiles;
+    if (plane >= r.planes) return; // (never, with the host's pre)
+    dec_resize_tile<kDtype, kAnyFilter>(r, plane, rel - plane * tiles, flt);
+}
+
 } // namespace
+
+bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
+{
+    using Kernel = void (*)(const DecResize *, const uint64_t *, uint32_t, DecFloat);
+    static const Kernel kernels[2][kDecFloatTypes + 1] = {
+        {dec_resize_exact_kernel<-1, false>, dec_resize_exact_kernel<0, false>, dec_resize_exact_kernel<1, false>, dec_resize_exact_kernel<2, false>},
+        {dec_resize_exact_kernel<-1, true>, dec_resize_exact_kernel<0, true>, dec_resize_exact_kernel<1, true>, dec_resize_exact_kernel<2, true>}};
+    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups, far below the 2^31 a grid's dimension allows)
+    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
+    if (lds_bytes > 65536u) return false;
+    for (uint32_t r0 = 0; r0 < n;) {
+        uint32_t r1 = r0 + 1;
+        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
+        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
+        hipLaunchKernelGGL(kernels[any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
+                           flt ? *flt : DecFloat{});
+        r0 = r1;
+    }
+    return true;
+}
 
 bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
 {

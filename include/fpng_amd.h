@@ -688,6 +688,50 @@ int fpng_amd_resize_weights_filter(uint32_t in_size, uint32_t out_size, uint32_t
  * twin of fpng_amd_decode_crop_tiles): box.x = crop.x + first_x(x), box.w = first_x(x + w - 1) + count_x(x + w - 1) - first_x(x), the
  * y axis alike.  FPNG_AMD_ERR_INVALID_ARG for a null argument and for everything the view call refuses in a record. */
 int fpng_amd_resize_view_source(const fpng_amd_crop *crop, const fpng_amd_resize_view *view, fpng_amd_crop *box);
+/* ---- decoding SEVERAL views of each file from one decode of it: what contrastive and multi-crop training ask for (two 224 x 224
+ *      views; two global views and six local 96 x 96 ones).  File i has view_count[i] >= 1 views; crops, views and dests hold a
+ *      record per view, file 0's first, sum(view_count) of each.  Listing a file once per view in the call above gives the same
+ *      elements and repeats everything that does not depend on the view: the upload of a host file, the container walk, the
+ *      tables, the whole-file synchronisation pass and its token-record scratch (16 x the compressed bytes, V times).
+ *      files[i].data / size / num_chans are used as in the call above; num_chans holds for all of the file's views.  Its
+ *      destination fields are not used: d_pixels must be NULL, row_pitch, plane_pitch and pixels_cap 0.  The destinations are the
+ *      dests records, one per view, with every rule the call above applies to a file's destination: planes of the view's w x h
+ *      elements, 0 = tight, negative pitches, |row_pitch| >= w (* element bytes), planes that do not overlap, room, multiples of
+ *      the element size under fmt.  Destinations of one call must not overlap each other.
+ *      GUARANTEE: for a file that decodes with status 0, each view's destination holds exactly the elements that
+ *      fpng_amd_decode_batch(_device)_planar_resize_view writes for that (file, crop, view, fmt) alone, whatever the file's other
+ *      views are.  Only the spans of the views' windows are written, whatever the status.
+ *      A file's job decodes ONE box: the bounding rectangle of its views' source boxes (fpng_amd_resize_view_source of each), which
+ *      fpng_amd_views_source returns without a GPU, from the text the plan uses.  fpng_amd_decode_crop_tiles(box) names the tiles
+ *      of the pixel pass that run, the file's status is fpng_amd_decode_batch_planar_crop's for that box (under
+ *      FPNG_AMD_VERIFY_ADLER32 every tile runs), and the scratch holds the box's planes once.  The box of two small views that lie
+ *      far apart holds everything between them: where that is much more than the two boxes, list the file twice.
+ *      If the crop of ANY view leaves the image the FILE gets FPNG_AMD_DECODE_CROP_OUTSIDE: none of its views is written, it needs
+ *      no room, the other files are not affected, results[i].w / h stay the file's.  results has n records, one per FILE.
+ *      Call-level errors, with nothing launched and before the encoder is looked at: FPNG_AMD_ERR_INVALID_ARG for a null array, a
+ *      view_count of 0, a sum of the counts that does not fit 32 bits, every record the call above refuses, and destination
+ *      fields of `files` that are not NULL / 0.
+ *      Everything else is the call above's: fmt, the mirror flag, the filters, the scale limits, FPNG_AMD_DECODE_UNDECIDED and
+ *      FPNG_AMD_DECODE_MAX_ROUNDS.  One batch may mix counts, filters, mirrors, sizes, 3- and 4-channel, compressed and stored files.
+ *      Not offered: unions of boxes that are not rectangles, views without a resize, interleaved destinations.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views with dlsym. ---- */
+typedef struct fpng_amd_view_dest { /* the destination fields of fpng_amd_png_planar, for ONE view */
+    uint8_t *d_pixels;   /* plane 0, row 0 */
+    int64_t row_pitch;   /* bytes; 0 = tight; negative: bottom-up */
+    int64_t plane_pitch; /* bytes; 0 = tight; negative: planes in reverse */
+    size_t pixels_cap;   /* >= (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w (* element bytes) */
+} fpng_amd_view_dest;    /* 32 bytes */
+int fpng_amd_decode_batch_planar_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                       const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                       const fpng_amd_view_dest *dests /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                       fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                              const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                              const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results);
+/* The box that a file with these `count` >= 1 views decodes, in the FILE's coordinates (no GPU needed; the text the plan uses): the
+ * bounding rectangle of fpng_amd_resize_view_source(crops[k], views[k]); count == 1: that box.  FPNG_AMD_ERR_INVALID_ARG for a
+ * null argument, a count of 0 and for everything the view call refuses in a record. */
+int fpng_amd_views_source(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, fpng_amd_crop *box);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

@@ -92,6 +92,11 @@ class ViewDest(C.Structure):  # fpng_amd_view_dest: 32 bytes, the destination of
     _fields_ = [("d_pixels", C.c_void_p), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("pixels_cap", C.c_size_t)]
 
 
+class ViewDestHwc(C.Structure):  # fpng_amd_view_dest_hwc: 32 bytes, the channels-last destination of ONE view of fpng_amd_decode_batch(_device)_hwc_views
+    _fields_ = [("d_pixels", C.c_void_p), ("row_pitch", C.c_int64), ("pixel_elems", C.c_uint32), ("flags", C.c_uint32), ("pixels_cap", C.c_size_t)]
+
+
+HWC_REVERSED = 1  # FPNG_AMD_HWC_REVERSED
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1  # FPNG_AMD_FILTER_*
 RESIZE_MIRROR = 1  # FPNG_AMD_RESIZE_MIRROR
 RESIZE_MAX_TAPS = 65  # weights per output sample of fpng_amd_resize_weights
@@ -220,6 +225,10 @@ SIGNATURES = {
                                                   C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_planar_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
                                                          C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_hwc_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                               C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_hwc_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                                      C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_views_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(Crop)]),
     "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),

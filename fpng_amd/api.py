@@ -142,7 +142,8 @@ def _planar_layout(t, order, bottom_up, who, elem=None):
         raise ValueError(f"{who}: {c} planes (3 or 4), {w} x {h}")
     if w > 1 and t.stride(2) != 1:
         raise ValueError(f"{who}: the pixels of a row must be adjacent bytes (stride(2) == 1); stride(2) == {t.stride(2)} is an "
-                         "interleaved view -- describe it as (h, w, c) with source_layout / dest_layout and use submit_ex / decode_device_ex")
+                         "interleaved view -- describe it as (h, w, c) with source_layout / dest_layout and use submit_ex / decode_device_ex, "
+                         "or decode into it with decode_device_views_hwc")
     rp, pp = t.stride(1), t.stride(0)
     if h > 1 and rp < w:
         raise ValueError(f"{who}: row stride {rp} < w (rows overlap, or stride 0)")
@@ -214,6 +215,49 @@ def dest_layout_float(t, order="rgb", bottom_up=False):
         raise ValueError("dest_layout_float: a float32, float16 or bfloat16 tensor shaped (c, h, w)")
     ptr, rp, pp = _planar_layout(t, order, bottom_up, "dest_layout_float", elem=t.element_size())
     return ptr, rp, pp, FLOAT_DTYPES[t.dtype]
+
+
+def dest_layout_hwc(t, order="rgb", bottom_up=False):
+    """(d_pixels, row_pitch, pixel_elems, flags, dtype code or None) of an (h, w, c) tensor VIEW -- uint8 (dtype code None) or
+    float32 / float16 / bfloat16 -- that Encoder.decode_device_views_hwc / decode_batch_views_hwc fill in place
+    (fpng_amd_view_dest_hwc), from its strides and data_ptr() alone (the device is not touched, so CPU tensors work too).
+
+    c is 3 or 4 and stride(2) == 1; stride(1), the pixel, is c elements, or 4 with c = 3 ([..., :3] of an RGBA tensor: the fourth
+    element of every pixel is never written, and the view starts on a multiple of 4 elements: [..., 1:] is refused; with w == 1 any
+    stride(1) is accepted); stride(0) at least the row's span, rows that
+    overlap and stride 0 refused.  A contiguous HWC tensor, a crop hwc[y0:y1, x0:x1], and -- what the call exists for -- the
+    permute(1, 2, 0) of x[i] of a torch.channels_last batch x.  order: "rgb" / "bgr" for c = 3, "rgba" / "abgr" for c = 4 ("rgb"
+    with 4 means "rgba"); bottom_up: the tensor's row 0 is the image's BOTTOM row.  Strides count elements; the pitch comes back
+    in BYTES."""
+    who = "dest_layout_hwc"
+    if not isinstance(t, torch.Tensor) or (t.dtype != torch.uint8 and t.dtype not in FLOAT_DTYPES) or t.dim() != 3:
+        raise ValueError(f"{who}: a uint8, float32, float16 or bfloat16 tensor shaped (h, w, c)")
+    h, w, c = t.shape
+    if c not in (3, 4) or h < 1 or w < 1:
+        raise ValueError(f"{who}: {c} channels (3 or 4), {w} x {h}")
+    if t.stride(2) != 1:
+        raise ValueError(f"{who}: the channels of a pixel must be adjacent elements (stride(2) == 1); stride(2) == {t.stride(2)} is a planar "
+                         "view -- describe it as (c, h, w) and use decode_device_views")
+    px = t.stride(1) if w > 1 else c
+    if px != c and not (px == 4 and c == 3):
+        raise ValueError(f"{who}: pixel stride {t.stride(1)} ({c} elements" + (" or 4" if c == 3 else "") + ")")
+    order = order.lower()
+    if c == 4 and order == "rgb":
+        order = "rgba"
+    if order not in (("rgb", "bgr") if c == 3 else ("rgba", "abgr")):
+        raise ValueError(f"{who}: order {order!r} for {c} channels -- " + ("'rgb' or 'bgr'" if c == 3 else "'rgba' or 'abgr'"))
+    rp, span = t.stride(0), (w - 1) * px + c
+    if h > 1 and rp < span:
+        raise ValueError(f"{who}: row stride {rp} < (w - 1) * pixel stride + c = {span} (rows overlap, or stride 0)")
+    if h == 1:
+        rp = 0  # (one row: no pitch)
+    e = t.element_size()
+    ptr, rp = t.data_ptr(), rp * e
+    if px != c and ptr % (4 * e):
+        raise ValueError(f"{who}: a 3-channel view of 4-element pixels starts at the pixel's first element ([..., :3], not [..., 1:])")
+    if bottom_up and h > 1:
+        ptr, rp = ptr + (h - 1) * rp, -rp
+    return ptr, rp, px, (0 if order[0] == "r" else _lib.HWC_REVERSED), FLOAT_DTYPES.get(t.dtype)
 
 
 def denormalize_constants(mean, std, max_value=255.0):
@@ -716,6 +760,20 @@ class DecodeBatchMultiView(_DecodeBatchViews):
     fpng_amd_resize_view and fpng_amd_view_dest records, one per view, file 0's first; outs: per file the list of the caller's (c,
     window h, window w) views, uint8 or all of one float dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No
     other call takes this descriptor."""
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.counts, self.crops, self.views, self.dests, self.fmt = counts, crops, views, dests, fmt
+
+    def results(self):
+        """list, per file, of (status, the list of the caller's own destination views (filled in place) or None, channels_in_file)"""
+        return [(r.status, list(ts) if r.status == 0 else None, r.channels_in_file) for r, ts in zip(self.res, self.outs)]
+
+
+class DecodeBatchMultiViewHwc(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_views_hwc() returns: DecodeBatchMultiView's twin for one
+    fpng_amd_decode_batch(_device)_hwc_views() call (dests: the fpng_amd_view_dest_hwc records; outs: per file the list of the
+    caller's (window h, window w, c) views).  No other call takes this descriptor."""
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1715,6 +1773,123 @@ class Encoder:
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, False, pngs, crops, outs, full, window, filter, mirror,
                                   dtype, order, bottom_up, mean, std, scale, bias, results)
+
+    @staticmethod
+    def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
+                                    scale=None, bias=None):
+        """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
+        destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
+        file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
+        value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants -- is
+        make_decode_batch_views()'s."""
+        who = "make_decode_batch_views_hwc"
+        n = len(pngs)
+        if len(crops) != n or len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(crops)} lists of crops, {len(outs)} lists of destinations")
+        crops, outs = [list(c) for c in crops], [list(o) for o in outs]
+        counts = [len(c) for c in crops]
+        for i in range(n):
+            if counts[i] < 1 or len(outs[i]) != counts[i]:
+                raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
+        fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
+        filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
+        dtypes = {t.dtype for ts in outs for t in ts if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+        is_u8 = dtypes == {torch.uint8}
+        fmt = None
+        if is_u8:
+            if any(v is not None for v in (mean, std, scale, bias)):
+                raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
+        else:
+            sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
+            fmt = _lib.FloatFormat()
+            for k in range(4):
+                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+        orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
+        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        total = sum(counts)
+        arr = (_lib.PngPlanarIn * n)()
+        narr = (C.c_uint32 * n)(*counts)
+        carr, varr, darr = (_lib.Crop * total)(), (_lib.ResizeView * total)(), (_lib.ViewDestHwc * total)()
+        res = (_lib.DecodeResult * n)()
+        keep = []
+        at = 0
+        for i, p in enumerate(pngs):
+            if device_data:
+                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                    raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
+                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+            else:
+                b = np.frombuffer(bytes(p), dtype=np.uint8)
+                keep.append(b)
+                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+            layouts = [dest_layout_hwc(t, orders[i][k], bool(ups[i][k])) for k, t in enumerate(outs[i])]
+            chans = {t.shape[2] for t in outs[i]}
+            if len(chans) != 1:
+                raise ValueError(f"{who}: the destinations of file {i} share one channel count, not {sorted(chans)}")
+            arr[i].num_chans = chans.pop()  # (d_pixels, the pitches and pixels_cap stay NULL / 0: the destinations are the views')
+            for k, t in enumerate(outs[i]):
+                ptr, rp, px, flags, code = layouts[k]
+                if code is not None:
+                    fmt.dtype = code
+                _crop_record(f"{who}: file {i}", crops[i][k], carr[at])
+                v = _view_record(who, fulls[i][k], windows[i][k], filters[i][k], bool(mirrors[i][k]), varr[at])
+                oh, ow, c = t.shape
+                if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
+                    raise ValueError(f"{who}: destination {k} of file {i} is {ow} x {oh}, its window {v.w} x {v.h}")
+                darr[at].d_pixels, darr[at].row_pitch, darr[at].pixel_elems, darr[at].flags = ptr, rp, px, flags
+                darr[at].pixels_cap = (oh - 1) * abs(rp) + ((ow - 1) * px + c) * t.element_size()  # (the view's own spans, in bytes)
+                at += 1
+        return DecodeBatchMultiViewHwc(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+
+    def _decode_views_hwc(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+        if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
+            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
+        if isinstance(pngs, DecodeBatchMultiViewHwc):
+            batch = pngs
+        else:
+            if crops is None or full is None:
+                raise ValueError(f"{who}: crops, a list of (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
+            if outs is None or any(o is None for o in outs):  # (each window's size with c = 3 channels; files with alpha lose it)
+                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
+                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+                counts = [len(c) for c in crops]
+                fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
+                sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
+                outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
+                        for i in range(len(crops))]
+            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
+        if not all(t.is_cuda for ts in batch.outs for t in ts):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        return batch.results() if results else batch
+
+    def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
+        written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
+        without a permute copy.  For a batch that trains in torch.channels_last,
+
+            x = torch.empty((n, 3, 224, 224), dtype=torch.float16, device="cuda", memory_format=torch.channels_last)
+
+        file i's destination is x[i].permute(1, 2, 0); x stays contiguous in channels_last.  Also: a contiguous HWC tensor, a crop
+        of one, rgba[..., :3] (the fourth element of every pixel is left alone), order "bgr" / "abgr", bottom_up
+        (dest_layout_hwc() has the rules).  full equal to a crop's size with the whole window is the identity: a plain HWC crop,
+        uint8 or float.  -> list, per file, of (status, the list of the caller's views or None, channels_in_file).  outs=None (or
+        None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
+        of device files; results=False returns it."""
+        return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, True, pngs, crops, outs, full, window, filter,
+                                      mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
+
+    def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+        """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
+        return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, False, pngs, crops, outs, full, window, filter, mirror,
+                                      dtype, order, bottom_up, mean, std, scale, bias, results)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

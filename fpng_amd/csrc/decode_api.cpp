@@ -8,6 +8,7 @@
 #include "host_workers.h"
 #include "png_parse.h"
 #include "resize.h"
+#include "resize_hwc.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -345,6 +346,13 @@ struct Batch {
     const fpng_amd_resize_view *sizes = nullptr;
     const uint32_t *view_count = nullptr;
     const fpng_amd_view_dest *dests = nullptr;
+    // fpng_amd_decode_batch(_device)_hwc_views: the views call with channels-last destinations (then dests is NULL).  The records of
+    // `resize` keep everything but the destination's layout -- dst: pixel (0, 0) of the top row, pitch: the rows' -- and go up as
+    // DecResizeHwc records with hwc_px (per view: pixel_elems, flags); the launch's prefix sums count tiles: hwc_pre
+    const fpng_amd_view_dest_hwc *hwc = nullptr;
+    std::vector<std::pair<uint32_t, uint32_t>> hwc_px;
+    std::vector<uint64_t> hwc_pre;
+    DecResizeHwc *d_resize_hwc = nullptr;
     std::vector<uint32_t> view_ofs, job_rec;
     std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
     std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
@@ -432,7 +440,8 @@ int parse_files(Batch &b)
     HeaderMemo memo;
     std::vector<DecResize> file_recs; // (the records of the file at hand's views, and their source boxes)
     std::vector<DecCrop> file_boxes;
-    b.resize_pre.assign(1, 0);
+    std::vector<std::pair<uint32_t, uint32_t>> file_px; // (channels-last destinations: the same views' pixel_elems and flags)
+    b.resize_pre.assign(1, 0), b.hwc_pre.assign(1, 0);
     b.ps.resize(b.n);
     for (uint32_t i = 0; i < b.n; i++) {
         const fpng_amd_png &f = b.files[i];
@@ -505,6 +514,21 @@ int parse_files(Batch &b)
                     return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w (* element bytes)");
                 return FPNG_AMD_OK;
             };
+            // the sibling for a channels-last destination of dest_w x dest_h pixels of pixel_elems elements, `desired` of them written:
+            // the rows' pitch and the room (fpng_amd_view_dest_hwc's rule; the record's own rules: decode_files_planar)
+            auto judge_hwc = [&](const fpng_amd_view_dest_hwc &d, uint32_t dest_w, uint32_t dest_h) -> int {
+                const uint32_t px = d.pixel_elems ? d.pixel_elems : desired;
+                const uint64_t span = ((uint64_t)(dest_w - 1) * px + desired) * b.elem; // a row, from its first byte to its last written one
+                if (span >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "((w - 1) * pixel_elems + num_chans) * element bytes >= 2^31");
+                pitch = d.row_pitch ? d.row_pitch : (int64_t)((uint64_t)dest_w * px * b.elem);
+                const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
+                if (step >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * pixel_elems * element bytes >= 2^31");
+                if (step < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < ((w - 1) * pixel_elems + num_chans) * element bytes");
+                if (!d.d_pixels || d.pixels_cap < (uint64_t)(dest_h - 1) * step + span)
+                    return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (h - 1) * |row_pitch| + ((w - 1) * pixel_elems + num_chans) * element bytes");
+                plane_pitch = 0;
+                return FPNG_AMD_OK;
+            };
             const fpng_amd_png_planar &x = b.planar[i];
             if (!b.sizes) {
                 if (int rc = judge((uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap, crop.w, crop.h)) return rc;
@@ -512,11 +536,13 @@ int parse_files(Batch &b)
                 // a record per view for dec_resize_kernel, which reads the view's own box inside the planes of the job's box (src: an
                 // offset from those planes' first byte until the file is known to become a job)
                 if (crop.w >= 0x80000000u) return fail(FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31");
-                file_recs.clear();
+                file_recs.clear(), file_px.clear();
                 for (uint32_t v = v0; v < v0 + nv; v++) {
                     const fpng_amd_resize_view &z = b.sizes[v];
-                    const fpng_amd_view_dest dest = b.dests ? b.dests[v] : fpng_amd_view_dest{(uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap};
-                    if (int rc = judge(dest.d_pixels, dest.row_pitch, dest.plane_pitch, dest.pixels_cap, z.w, z.h)) return rc;
+                    const fpng_amd_view_dest dest = b.hwc     ? fpng_amd_view_dest{b.hwc[v].d_pixels, 0, 0, 0}
+                                                    : b.dests ? b.dests[v]
+                                                              : fpng_amd_view_dest{(uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap};
+                    if (int rc = b.hwc ? judge_hwc(b.hwc[v], z.w, z.h) : judge(dest.d_pixels, dest.row_pitch, dest.plane_pitch, dest.pixels_cap, z.w, z.h)) return rc;
                     if (resize_tiles(z.w, z.h) * 4 * kResizeBlock >= (1ull << 32)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16");
                     const DecCrop whole_crop = {b.crops[v].x, b.crops[v].y, b.crops[v].w, b.crops[v].h}, box = file_boxes[v - v0];
                     DecResize rs = {};
@@ -528,6 +554,7 @@ int parse_files(Batch &b)
                     rs.box_x = box.x - whole_crop.x, rs.box_y = box.y - whole_crop.y;
                     rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
                     file_recs.push_back(rs);
+                    if (b.hwc) file_px.push_back({b.hwc[v].pixel_elems ? b.hwc[v].pixel_elems : desired, b.hwc[v].flags});
                 }
             }
         } else if (b.ex) {
@@ -555,6 +582,11 @@ int parse_files(Batch &b)
                 b.resize.push_back(rs);
                 b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
                 b.resize_pre.push_back(b.resize_pre.back() + rs.planes * tiles);
+                if (b.hwc) { // (a workgroup per tile, all planes, and the tile's result bytes in its LDS)
+                    b.resize_lds.back() = resize_hwc_tile_lds(rs.taps_x, rs.taps_y, rs.rows, rs.planes);
+                    b.hwc_pre.push_back(b.hwc_pre.back() + tiles);
+                    b.hwc_px.push_back(file_px[&rs - file_recs.data()]);
+                }
             }
             j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
             pitch = (int64_t)crop.w, plane_pitch = (int64_t)((uint64_t)crop.w * crop.h);
@@ -606,7 +638,7 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * sizeof(DecResize)), o_pre = sc.carve(b.view_count ? b.resize_pre.size() * sizeof(uint64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * (b.hwc ? sizeof(DecResizeHwc) : sizeof(DecResize))), o_pre = sc.carve(b.view_count ? b.resize_pre.size() * sizeof(uint64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
     const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
@@ -619,6 +651,7 @@ int place_files(Batch &b)
     b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
     b.d_crops = b.crops ? (DecCrop *)(base + o_crop) : nullptr;
     b.d_resize = b.sizes ? (DecResize *)(base + o_resize) : nullptr;
+    b.d_resize_hwc = b.hwc ? (DecResizeHwc *)(base + o_resize) : nullptr;
     b.d_resize_pre = b.view_count ? (uint64_t *)(base + o_pre) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
@@ -726,8 +759,17 @@ int plan_groups(Batch &b)
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
-    if (b.sizes) std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), b.resize.size() * sizeof(DecResize));
-    if (b.view_count) std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), b.resize_pre.data(), b.resize_pre.size() * sizeof(uint64_t));
+    if (b.hwc) {
+        for (size_t q = 0; q < b.resize.size(); q++) {
+            const DecResizeHwc rec = {b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second};
+            std::memcpy(h_setup + ((uint8_t *)(b.d_resize_hwc + q) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
+        }
+    } else if (b.sizes)
+        std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), b.resize.size() * sizeof(DecResize));
+    if (b.view_count) { // (the launch's prefix sums: planes x tiles, the channels-last call's: tiles)
+        const std::vector<uint64_t> &pre = b.hwc ? b.hwc_pre : b.resize_pre;
+        std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), pre.data(), pre.size() * sizeof(uint64_t));
+    }
     return FPNG_AMD_OK;
 }
 
@@ -776,8 +818,9 @@ int finish_group(Batch &b, uint32_t gi)
         const bool any_filter = std::any_of(b.resize.begin() + r0, b.resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
         // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
         //  output per file keep the grid of the largest record)
-        const bool ok = b.view_count ? launch_dec_resize_exact(b.s, b.d_resize + r0, b.d_resize_pre + r0, b.resize_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
-                                     : launch_dec_resize(b.s, b.d_resize + r0, r1 - r0, tiles, lds, b.flt, any_filter);
+        const bool ok = b.hwc        ? launch_dec_resize_hwc(b.s, b.d_resize_hwc + r0, b.d_resize_pre + r0, b.hwc_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
+                        : b.view_count ? launch_dec_resize_exact(b.s, b.d_resize + r0, b.d_resize_pre + r0, b.resize_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
+                                       : launch_dec_resize(b.s, b.d_resize + r0, r1 - r0, tiles, lds, b.flt, any_filter);
         if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
     }
     HIP_TRY(stamp(b, gi, 4));
@@ -937,10 +980,12 @@ int collect_results(Batch &b)
 // ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
 // planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's; sizes (with
 // crops): ... fpng_amd_decode_batch(_device)_planar_resize_view's (the plain resize call's: as whole-window bilinear views); view_count
-// and dests (with sizes): ... fpng_amd_decode_batch(_device)_planar_views's, whose crops, sizes and dests hold a record per view
+// and dests (with sizes): ... fpng_amd_decode_batch(_device)_planar_views's, whose crops, sizes and dests hold a record per view; hwc
+// in the place of dests: fpng_amd_decode_batch(_device)_hwc_views's
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
-                 const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr)
+                 const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
+                 const fpng_amd_view_dest_hwc *hwc = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -951,7 +996,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests;
+        b.view_count = view_count, b.dests = dests, b.hwc = hwc;
         b.view_ofs.resize(n);
         for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
     }
@@ -1246,7 +1291,8 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
 // view_count, dests: fpng_amd_decode_batch(_device)_planar_views's (decode_files_views has judged the counts and the records; crops and
 // views then hold a record per view, and the destinations, which `files` leave empty, are dests')
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
-                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr)
+                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
+                        const fpng_amd_view_dest_hwc *hwc = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && !view_count && i < n; i++)
@@ -1272,20 +1318,29 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
     }
     uint64_t n_views = 0;
     for (uint32_t i = 0; view_count && i < n; i++) n_views += view_count[i];
-    for (uint64_t v = 0; v < n_views; v++) { // (the same two rules for every view's destination)
+    for (uint64_t v = 0; hwc && v < n_views; v++) { // (a channels-last destination's twins of the two rules below)
+        const fpng_amd_view_dest_hwc &x = hwc[v];
+        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch) & (elem - 1)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels and row_pitch must be multiples of the element size");
+        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
+    }
+    for (uint64_t v = 0; dests && v < n_views; v++) { // (the same two rules for every view's destination)
         const fpng_amd_view_dest &x = dests[v];
         if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (elem - 1))
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
+// hwc in the place of dests: fpng_amd_decode_batch(_device)_hwc_views's destinations, whose own rules -- pixel_elems, flags -- are judged here too
+static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_dest_hwc, row_pitch) == 8 && offsetof(fpng_amd_view_dest_hwc, pixel_elems) == 16 &&
+                  offsetof(fpng_amd_view_dest_hwc, flags) == 20 && offsetof(fpng_amd_view_dest_hwc, pixels_cap) == 24 && FPNG_AMD_HWC_REVERSED == kHwcReversed,
+              "fpng_amd_view_dest_hwc layout");
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
-                       const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data)
+                       const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr)
 {
-    if (!files || !view_count || !crops || !views || !dests || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (!view_count[i]) return fail(FPNG_AMD_ERR_INVALID_ARG, "a view_count of 0 (every file has at least one view)");
@@ -1295,7 +1350,13 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
     for (uint32_t i = 0; i < n; i++)
         if (files[i].d_pixels || files[i].row_pitch || files[i].plane_pitch || files[i].pixels_cap)
             return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_png_planar::d_pixels, row_pitch, plane_pitch and pixels_cap must be NULL / 0: the destinations are the fpng_amd_view_dest records");
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests);
+    for (uint32_t i = 0, v = 0; hwc && i < n; i++)
+        for (const uint32_t end = v + view_count[i]; v < end; v++) {
+            const uint32_t px = hwc[v].pixel_elems, c = files[i].num_chans;
+            if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
+            if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
+        }
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1386,6 +1447,21 @@ extern "C" int fpng_amd_decode_batch_device_planar_views(fpng_amd_encoder *e, co
                                                          fpng_amd_decode_result *results)
 {
     return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, true);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                               const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    if (!dests) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    return decode_files_views(e, files, n, view_count, crops, views, nullptr, fmt, results, false, dests);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                      const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_float_format *fmt,
+                                                      fpng_amd_decode_result *results)
+{
+    if (!dests) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    return decode_files_views(e, files, n, view_count, crops, views, nullptr, fmt, results, true, dests);
 }
 
 // the ONE box that a file with these views decodes: the bounding rectangle of the boxes below

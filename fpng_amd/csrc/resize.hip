@@ -21,6 +21,7 @@
 #include "decode.h"
 #include "float_store.h"
 #include "resize.h"
+#include "resize_hwc.h"
 
 #include <hip/hip_runtime.h>
 
@@ -162,6 +163,176 @@ bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_
     const uint32_t step = (uint32_t)std::min<uint64_t>(32768u, ((1ull << 32) - 1) / per_file);
     for (uint32_t j0 = 0; j0 < n; j0 += step)
         hipLaunchKernelGGL(kernels[any_filter][flt ? flt->dtype + 1 : 0], dim3(max_tiles, 4, std::min(step, n - j0)), dim3(kResizeBlock), lds_bytes, s, recs + j0, flt ? *flt : DecFloat{});
+    return true;
+}
+
+// ---- the channels-last destinations of fpng_amd_decode_batch(_device)_hwc_views (resize_hwc.h) ----
+namespace {
+
+// One workgroup per (record, tile of kResizeTileW x kResizeTileH samples of the window), ALL planes: the exact grid of
+// dec_resize_exact_kernel with pre counting tiles.
+//   1. the tile's weights, first taps and tap counts as in dec_resize_tile -- once, not once per plane;
+//   2. per plane the two passes of dec_resize_tile (the same integer sums, resize_clip8 after each, the same guards) through the
+//      same T bytes, a thread's result BYTES of its four rows kept in four registers, a byte per plane; behind the last plane they
+//      go to LDS as O[row][column * planes + plane], in the place of the weights and T, which are done with -- so a tile needs no
+//      more LDS than the planar kernel's, and as many workgroups fit a compute unit (with 3 or 4 KB on top of the 20 KB of a 10 x
+//      reduction one fewer did, and the kernel ran 8 % longer: profiles/views_hwc_timing.txt);
+//   3. a wave per row of the tile walks the row's run of the destination in memory order: element e is position e % pixel_elems of
+//      pixel e / pixel_elems (positions >= planes belong to the caller: skipped), neighbouring lanes write neighbouring elements.
+//      The mirror is an index into O -- the tile's columns ox0 .. ox0 + nw - 1 of the window are pixels w - ox0 - nw .. w - ox0 - 1
+//      of the destination, back to front -- the reversed order an index into the pixel; the fmaf and the conversion are
+//      dec_resize_tile's.  Where every element of the run is written (pixel_elems == planes) and the elements are narrower than a
+//      dword, the run goes out as single elements up to the first 4-byte boundary, dwords, and single elements behind the last one.
+template <int kDtype, bool kAnyFilter>
+__global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecResizeHwc *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
+    const uint64_t g = pre[0] + blockIdx.x;
+    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const DecResize r = recs[lo].r;
+    const uint32_t P = recs[lo].pixel_elems, reversed = recs[lo].hwc_flags & kHwcReversed, C = r.planes;
+    const uint32_t tile = (uint32_t)(g - pre[lo]);
+    if ((uint64_t)tile >= resize_tiles(r.w, r.h)) return; // (never, with the host's pre)
+    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW;
+    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
+    const uint32_t nq = std::min(kResizeTileH, r.h - oq0), nw = std::min(kResizeTileW, r.w - ox0);
+    int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
+    uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
+    uint8_t *const T = (uint8_t *)(cy + kResizeTileH), *const O = resize_lds; // (O: once the passes are done, in the place of everything else)
+    const uint32_t tid = threadIdx.x;
+    const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
+    // ---- 1. the tile's weights ----
+    if (tid < kResizeTileW) {
+        uint32_t first = r.box_x, count = 0;
+        if (tid < nw) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        fx[tid] = first - r.box_x, cx[tid] = count;
+    } else if (tid < kResizeTileW + kResizeTileH) {
+        const uint32_t q = tid - kResizeTileW;
+        uint32_t first = r.box_y, count = 0;
+        if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        fy[q] = first - r.box_y, cy[q] = count;
+    }
+    __syncthreads();
+    // ---- 2. per plane: the horizontal pass into T, the vertical pass out of it into a byte of res[k] -- row wave + 4 k of the
+    //      tile, column o, plane b in byte b ----
+    const uint32_t row0 = fy[0];
+    const uint32_t nrows = std::min(fy[nq - 1] + cy[nq - 1] - row0, r.rows); // (the host's bound holds: T has r.rows rows)
+    const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
+    const uint32_t o_stride = kResizeTileW * C; // bytes of a row of O
+    constexpr uint32_t kWaves = kResizeBlock / kResizeTileW, kRowsPerWave = kResizeTileH / kWaves;
+    uint32_t res[kRowsPerWave] = {};
+    for (uint32_t plane = 0; plane < C; plane++) {
+        if (plane) __syncthreads(); // (the plane before has been read out of T)
+        const uint8_t *const S = r.src + (uint64_t)plane * r.src_plane_pitch;
+        {
+            const uint32_t first = fx[o], count = cx[o];
+            for (uint32_t j = wave; j < nrows; j += kResizeBlock / kResizeTileW) {
+                const uint8_t *s = S + (uint64_t)(row0 + j) * r.src_pitch + first;
+                int32_t sum = 1 << (kResizeBits - 1);
+                for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
+                T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
+            }
+        }
+        __syncthreads();
+        if (o < nw) {
+#pragma unroll
+            for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                const uint32_t q = wave + k * kWaves;
+                if (q >= nq) break;
+                const uint32_t first = fy[q] - row0;
+                const uint32_t count = first < nrows ? std::min(cy[q], nrows - first) : 0u;
+                int32_t sum = 1 << (kResizeBits - 1);
+                for (uint32_t t = 0; t < count; t++) sum += (int32_t)T[(first + t) * kResizeTileW + o] * Ky[t * kResizeTileH + q];
+                res[k] |= resize_clip8(sum) << (8 * plane);
+            }
+        }
+    }
+    __syncthreads(); // (weights, taps and T have been read for the last time: O takes their place)
+    if (o < nw) {
+#pragma unroll
+        for (uint32_t k = 0; k < kRowsPerWave; k++) {
+            const uint32_t q = wave + k * kWaves;
+            if (q >= nq) break;
+            uint8_t *const p = O + q * o_stride + o * C;
+            if (C == 4) *(uint32_t *)p = res[k];
+            else p[0] = (uint8_t)res[k], p[1] = (uint8_t)(res[k] >> 8), p[2] = (uint8_t)(res[k] >> 16);
+        }
+    }
+    __syncthreads();
+    // ---- 3. the store: a wave per row, the row's run in memory order ----
+    constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
+    const bool mirror = r.flags & kResizeMirror;
+    const uint32_t d0 = mirror ? r.w - ox0 - nw : ox0; // the run's first pixel of the destination's row
+    const uint32_t n_el = (nw - 1) * P + C;            // the run's elements, up to the last one that is written
+    for (uint32_t q = wave; q < nq; q += kResizeBlock / kResizeTileW) {
+        const uint8_t *const Oq = O + q * o_stride;
+        uint8_t *const D = r.dst + (int64_t)(oq0 + q) * r.pitch + (int64_t)((uint64_t)d0 * P * kElem);
+        // element e of the run as the bits of its kElem bytes (e's position within its pixel is below C)
+        auto bits = [&](uint32_t e) -> uint32_t {
+            const uint32_t i = P == 4 ? e >> 2 : e / 3u, k = e - i * P; // (P is 3 or 4)
+            const uint32_t c = reversed ? C - 1 - k : k;              // the FILE's channel
+            const uint32_t v = Oq[(mirror ? nw - 1 - i : i) * C + c];
+            if constexpr (kDtype < 0) return v;
+            else {
+                // (a select, not an index into the argument, which would put it into private memory)
+                const float sc = c == 0 ? flt.scale[0] : c == 1 ? flt.scale[1] : c == 2 ? flt.scale[2] : flt.scale[3];
+                const float bi = c == 0 ? flt.bias[0] : c == 1 ? flt.bias[1] : c == 2 ? flt.bias[2] : flt.bias[3];
+                const float f = __builtin_fmaf((float)v, sc, bi);
+                if constexpr (kDtype == 0) return __builtin_bit_cast(uint32_t, f);
+                else return half_bits<kDtype>(f);
+            }
+        };
+        auto store1 = [&](uint32_t e) {
+            uint8_t *p = D + (size_t)e * kElem;
+            const uint32_t b = bits(e);
+            if constexpr (kDtype < 0) *p = (uint8_t)b;
+            else if constexpr (kDtype == 0) *(f32_a *)p = __builtin_bit_cast(float, b);
+            else *(u16_a *)p = (uint16_t)b;
+        };
+        if (kElem == 4 || P != C) {
+            for (uint32_t e = o; e < n_el; e += kResizeTileW)
+                if (P == C || (e & 3u) < C) store1(e); // (P == 4: position e % 4; 3 is the caller's)
+        } else {
+            constexpr uint32_t kPer = 4u / kElem; // elements per dword
+            const uint32_t head = std::min(n_el, (uint32_t)((0u - (uint32_t)(uintptr_t)D) & 3u) / kElem); // (D is a multiple of kElem)
+            const uint32_t nd = (n_el - head) / kPer, tail0 = head + nd * kPer;
+            if (o < head) store1(o);
+            for (uint32_t d = o; d < nd; d += kResizeTileW) {
+                const uint32_t e = head + d * kPer;
+                uint32_t word;
+                if constexpr (kPer == 4) word = bits(e) | bits(e + 1) << 8 | bits(e + 2) << 16 | bits(e + 3) << 24;
+                else word = bits(e) | bits(e + 1) << 16;
+                *(uint32_t *)(D + (size_t)e * kElem) = word;
+            }
+            if (tail0 + o < n_el) store1(tail0 + o);
+        }
+    }
+}
+
+} // namespace
+
+bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
+{
+    using Kernel = void (*)(const DecResizeHwc *, const uint64_t *, uint32_t, DecFloat);
+    static const Kernel kernels[2][kDecFloatTypes + 1] = {
+        {dec_resize_hwc_kernel<-1, false>, dec_resize_hwc_kernel<0, false>, dec_resize_hwc_kernel<1, false>, dec_resize_hwc_kernel<2, false>},
+        {dec_resize_hwc_kernel<-1, true>, dec_resize_hwc_kernel<0, true>, dec_resize_hwc_kernel<1, true>, dec_resize_hwc_kernel<2, true>}};
+    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
+    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
+    if (lds_bytes > 65536u) return false;
+    for (uint32_t r0 = 0; r0 < n;) {
+        uint32_t r1 = r0 + 1;
+        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
+        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
+        hipLaunchKernelGGL(kernels[any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
+                           flt ? *flt : DecFloat{});
+        r0 = r1;
+    }
     return true;
 }
 

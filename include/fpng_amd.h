@@ -621,8 +621,8 @@ int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_
  *      FPNG_AMD_DECODE_UNDECIDED, FPNG_AMD_DECODE_MAX_ROUNDS and the checksum flags behave as in the crop call.
  *      Not offered by THIS call: a window of the resized image and the bicubic filter (fpng_amd_decode_batch_planar_resize_view,
  *      below, has both).  Not offered at all: antialias off, nearest and Lanczos; premultiplied alpha (every plane is resized on
- *      its own, as an "L" image); a resize without a crop record (give the whole image as the crop); the interleaved destinations,
- *      fpng_amd_decode_host and the fpng:: drop-in.
+ *      its own, as an "L" image); a resize without a crop record (give the whole image as the crop); fpng_amd_decode_host and the
+ *      fpng:: drop-in.  Interleaved (channels-last) destinations: fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize with dlsym. ---- */
 typedef struct fpng_amd_resize {
     uint32_t out_w, out_h, flags, reserved;
@@ -663,8 +663,8 @@ int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint32_t *first
  *      views, an empty crop, full_w, full_h, w or h of 0, x + w > full_w or y + h > full_h (in 64 bits), unknown flag bits, an
  *      unknown filter, and a crop past the filter's scale limit against the FULL size: bilinear crop.w <= 32 * full_w, bicubic
  *      crop.w <= 16 * full_w (the same for h; at most 65 taps either way).  The bound of 2^22 tiles of 64 x 16 applies to the window.
- *      Not offered: antialias off, nearest, Lanczos; premultiplied alpha; the interleaved destinations, fpng_amd_decode_host and
- *      the fpng:: drop-in.
+ *      Not offered: antialias off, nearest, Lanczos; premultiplied alpha; fpng_amd_decode_host and the fpng:: drop-in.
+ *      Interleaved (channels-last) destinations: fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize_view with dlsym. ---- */
 typedef struct fpng_amd_resize_view {
     uint32_t full_w, full_h; /* the size the CROP is resized to (never materialised) */
@@ -713,7 +713,8 @@ int fpng_amd_resize_view_source(const fpng_amd_crop *crop, const fpng_amd_resize
  *      fields of `files` that are not NULL / 0.
  *      Everything else is the call above's: fmt, the mirror flag, the filters, the scale limits, FPNG_AMD_DECODE_UNDECIDED and
  *      FPNG_AMD_DECODE_MAX_ROUNDS.  One batch may mix counts, filters, mirrors, sizes, 3- and 4-channel, compressed and stored files.
- *      Not offered: unions of boxes that are not rectangles, views without a resize, interleaved destinations.
+ *      Not offered: unions of boxes that are not rectangles, views without a resize.  Interleaved (channels-last) destinations:
+ *      fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views with dlsym. ---- */
 typedef struct fpng_amd_view_dest { /* the destination fields of fpng_amd_png_planar, for ONE view */
     uint8_t *d_pixels;   /* plane 0, row 0 */
@@ -732,6 +733,47 @@ int fpng_amd_decode_batch_device_planar_views(fpng_amd_encoder *enc, const fpng_
  * bounding rectangle of fpng_amd_resize_view_source(crops[k], views[k]); count == 1: that box.  FPNG_AMD_ERR_INVALID_ARG for a
  * null argument, a count of 0 and for everything the view call refuses in a record. */
 int fpng_amd_views_source(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, fpng_amd_crop *box);
+/* ---- the views call with CHANNELS-LAST (interleaved, HWC) destinations: what training in torch.channels_last asks for -- a
+ *      channels-last batch is an NHWC buffer, and decoding into planes first costs a permute copy of the batch.  The argument list
+ *      is fpng_amd_decode_batch(_device)_planar_views's with fpng_amd_view_dest_hwc in the place of fpng_amd_view_dest, and
+ *      everything but the destination comes from that call unchanged: files (destination fields NULL / 0, num_chans 3 or 4 for all
+ *      of a file's views), view_count, crops, views, fmt, every status and FPNG_AMD_DECODE_CROP_OUTSIDE per file,
+ *      FPNG_AMD_DECODE_UNDECIDED and FPNG_AMD_DECODE_MAX_ROUNDS, the checksum flags, the filters, the scale limits, the mirror flag,
+ *      the ONE bounding box per file (fpng_amd_views_source and fpng_amd_decode_crop_tiles describe what runs) and the bound of
+ *      2^22 tiles per window.  ONE call is enough, because the views call contains the others: one view per file is the
+ *      resize_view call, a whole-window bilinear view the resize call, and full equal to the crop's size is the identity -- the
+ *      crop call and the whole-file float call, in HWC.
+ *      The destination.  E: the element bytes (1 for uint8, else those of fmt's dtype); P: pixel_elems (0 means num_chans); C:
+ *      num_chans.  Element (q, i, c) of a w x h view -- row q, pixel i, the FILE's channel c -- lies at
+ *          d_pixels + q * row_pitch + (i * P + k) * E,      k = c, with FPNG_AMD_HWC_REVERSED k = C - 1 - c (BGR, ABGR)
+ *      GUARANTEE: for a file with status 0 that element is exactly what fpng_amd_decode_batch(_device)_planar_views writes at
+ *      (c, q, i) for the same file, crop, view and fmt: the same byte, or the same round_to_dtype(fmaf(v, scale[c], bias[c])).
+ *      A = 255 in the fourth element of a 3-channel file with C = 4; alpha is dropped for a 4-channel file with C = 3.
+ *      A row's span is S = ((w - 1) * P + C) * E bytes.  Only the h spans of each view are written, whatever the status; inside a
+ *      span with P = 4 and C = 3 the fourth element of every pixel is NEVER written -- it is the caller's, as with a [..., :3] view
+ *      of an RGBA tensor; pitch padding is not written, nor anything in front of or behind the view.  Destinations of one call
+ *      must not overlap.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched: P other than 0, C, or 4 with C = 3, and unknown flag bits (both before the
+ *      encoder is looked at, with the call-level errors of the views call); |row_pitch| >= 2^31; 0 < |row_pitch| < S; a tight
+ *      pitch (w * P * E) of 2^31 or more; with fmt, a d_pixels or row_pitch that is not a multiple of E.
+ *      FPNG_AMD_ERR_BUFFER_TOO_SMALL: a NULL d_pixels, or pixels_cap < (h - 1) * |row_pitch| + S.  A failed call writes nothing.
+ *      Not offered: channel orders beyond forward and reversed, fpng_amd_decode_host and the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_hwc_views with dlsym. ---- */
+typedef struct fpng_amd_view_dest_hwc {
+    uint8_t *d_pixels;    /* DEVICE: first element of pixel (0, 0) of the view's TOP row */
+    int64_t row_pitch;    /* signed bytes between rows; 0 = tight (w * pixel_elems * element bytes); negative = bottom-up */
+    uint32_t pixel_elems; /* elements from one pixel to the next: 0 = num_chans; else num_chans, or 4 with num_chans = 3 */
+    uint32_t flags;       /* FPNG_AMD_HWC_REVERSED */
+    size_t pixels_cap;    /* bytes writable from the LOWEST-addressed row's first byte: >= (h - 1) * |row_pitch| + S */
+} fpng_amd_view_dest_hwc; /* 32 bytes */
+#define FPNG_AMD_HWC_REVERSED 1u /* file channel c is element num_chans - 1 - c of its pixel */
+int fpng_amd_decode_batch_hwc_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                    const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                    const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 */,
+                                    fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                           const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                           const fpng_amd_float_format *fmt /* NULL: uint8 */, fpng_amd_decode_result *results);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

@@ -32,4 +32,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   DECODE_CROP_OUTSIDE, DecodeBatchCrop, crop_tiles,
                   RESIZE_MIRROR, DecodeBatchResize, resize_weights,
                   FILTER_BILINEAR, FILTER_BICUBIC, DecodeBatchResizeView, resize_view_source, center_crop_view,
-                  DecodeBatchMultiView, views_source, dest_layout_hwc, DecodeBatchMultiViewHwc)
+                  DecodeBatchMultiView, views_source, dest_layout_hwc, DecodeBatchMultiViewHwc,
+                  color_matrix, color_apply)

@@ -96,6 +96,10 @@ class ViewDestHwc(C.Structure):  # fpng_amd_view_dest_hwc: 32 bytes, the channel
     _fields_ = [("d_pixels", C.c_void_p), ("row_pitch", C.c_int64), ("pixel_elems", C.c_uint32), ("flags", C.c_uint32), ("pixels_cap", C.c_size_t)]
 
 
+class ViewColor(C.Structure):  # fpng_amd_view_color: 64 bytes, the colour matrix of ONE view of the _views_color calls
+    _fields_ = [("m", (C.c_float * 4) * 3), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 HWC_REVERSED = 1  # FPNG_AMD_HWC_REVERSED
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1  # FPNG_AMD_FILTER_*
 RESIZE_MIRROR = 1  # FPNG_AMD_RESIZE_MIRROR
@@ -229,6 +233,15 @@ SIGNATURES = {
                                                C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_hwc_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
                                                       C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_planar_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                                        C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                                               C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_hwc_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                                     C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_hwc_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                                            C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_color_apply": (None, [C.POINTER(ViewColor), C.POINTER(C.c_uint8 * 3), C.POINTER(C.c_float * 3)]),
     "fpng_amd_views_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(Crop)]),
     "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "fpng_amd_encoder_set_decode_verify": (_int, [_vp, _u32]),

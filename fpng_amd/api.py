@@ -433,6 +433,94 @@ def views_source(crops, fulls, windows=None, filters="bilinear"):
     return box.x, box.y, box.w, box.h
 
 
+_LUMA = (0.2989, 0.587, 0.114)  # torchvision's rgb_to_grayscale
+_RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.595716, -0.274453, -0.321263), (0.211456, -0.522591, 0.311135))  # (rows I and Q sum to 0: gray has none of either)
+
+
+def color_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, contrast_center=128.0):
+    """The (3, 4) float32 matrix of fpng_amd_view_color (row c: coefficients of R, G, B and a constant, in byte units) of
+    ColorJitter-style factors, composed in float64 -- brightness first, then contrast, saturation, hue -- and rounded once:
+        brightness  x -> b * x
+        contrast    x -> k * (x - contrast_center) + contrast_center     (about a FIXED centre, not the image's own mean)
+        saturation  x -> s * x + (1 - s) * L(x),  L = 0.2989 R + 0.587 G + 0.114 B (torchvision's luma); 0: RandomGrayscale's output
+        hue         a rotation by `hue` turns (torchvision's range -0.5 .. 0.5) of the I, Q plane of YIQ, positive from red towards
+                    yellow and green as torchvision's; 0 is exactly no step
+    The defaults give exactly the identity.  No clamp between the steps: the decoder clamps once, after the matrix.  The matrix is
+    the contract, this helper a convenience: for another order or another transform, multiply your own."""
+    m = np.eye(4, dtype=np.float64)
+
+    def step(a, const=(0.0, 0.0, 0.0)):
+        nonlocal m
+        t = np.eye(4, dtype=np.float64)
+        t[:3, :3], t[:3, 3] = a, const
+        m = t @ m
+
+    b, k, sat, turn, center = float(brightness), float(contrast), float(saturation), float(hue), float(contrast_center)
+    step(np.eye(3) * b)
+    step(np.eye(3) * k, [(1.0 - k) * center] * 3)
+    step(np.eye(3) * sat + (1.0 - sat) * np.array([_LUMA] * 3, dtype=np.float64))
+    if turn != 0.0:
+        yiq = np.array(_RGB_TO_YIQ, dtype=np.float64)
+        co, si = np.cos(2.0 * np.pi * turn), np.sin(2.0 * np.pi * turn)
+        step(np.linalg.inv(yiq) @ np.array([[1.0, 0.0, 0.0], [0.0, co, si], [0.0, -si, co]]) @ yiq)
+    return np.ascontiguousarray(m[:3] + 0.0, dtype=np.float32)  # (+ 0.0: no negative zero)
+
+
+def _color_record(who, m, rec=None):
+    a = np.asarray(m, dtype=np.float32)
+    if a.shape != (3, 4):
+        raise ValueError(f"{who}: a colour matrix is (3, 4) -- per row the coefficients of R, G, B and a constant -- not {a.shape}")
+    rec = _lib.ViewColor() if rec is None else rec
+    for c in range(3):
+        for k in range(4):
+            rec.m[c][k] = float(a[c, k])
+    return rec
+
+
+def _color_records(who, counts, color):
+    """the color= argument of the views calls -> fpng_amd_view_color[sum(counts)]: one (3, 4) array-like for all views, or a list per
+    file of a list per view"""
+    arr = (_lib.ViewColor * max(sum(counts), 1))()
+    try:
+        one = np.asarray(color, dtype=np.float32)
+    except (ValueError, TypeError):
+        one = None
+    if one is not None and one.shape == (3, 4):
+        for at in range(sum(counts)):
+            _color_record(who, one, arr[at])
+        return arr
+    if isinstance(color, np.ndarray) or not hasattr(color, "__len__"):
+        raise ValueError(f"{who}: color is one (3, 4) matrix for all views, or a list per file of a (3, 4) matrix per view")
+    if len(color) != len(counts):
+        raise ValueError(f"{who}: {len(counts)} files, {len(color)} lists of colour matrices")
+    at = 0
+    for i, (c, ms) in enumerate(zip(counts, color)):
+        if isinstance(ms, np.ndarray) and ms.ndim != 3 or not hasattr(ms, "__len__") or len(ms) != c:
+            raise ValueError(f"{who}: file {i} has {c} views, its colour matrices: {np.shape(ms)}")
+        for m in ms:
+            _color_record(f"{who}: file {i}", m, arr[at])
+            at += 1
+    return arr
+
+
+def color_apply(matrix, rgb_bytes):
+    """fpng_amd_color_apply, the host twin of the colour step (no GPU): rgb_bytes (..., 3) uint8 -> (..., 3) float32, the u_c of the
+    rule -- fminf(fmaxf(fmaf(m[c][2], b, fmaf(m[c][1], g, fmaf(m[c][0], r, m[c][3]))), 0), 255) -- that the kernel computes for
+    those bytes under `matrix` (3, 4)."""
+    rec = _color_record("color_apply", matrix)
+    px = np.ascontiguousarray(rgb_bytes, dtype=np.uint8)
+    if px.ndim < 1 or px.shape[-1] != 3:
+        raise ValueError(f"color_apply: rgb_bytes is (..., 3) uint8, not {px.shape}")
+    out = np.empty(px.shape, dtype=np.float32)
+    fn, flat, oflat = _lib.load().fpng_amd_color_apply, px.reshape(-1, 3), out.reshape(-1, 3)
+    rgb, u = (C.c_uint8 * 3)(), (C.c_float * 3)()
+    for k in range(flat.shape[0]):
+        rgb[0], rgb[1], rgb[2] = flat[k]
+        fn(C.byref(rec), C.byref(rgb), C.byref(u))
+        oflat[k] = u[0], u[1], u[2]
+    return out
+
+
 def center_crop_view(file_w, file_h, resize, crop):
     """torchvision's Resize(resize) + CenterCrop(crop) of a file_w x file_h file as (crop_box, full, window) for
     decode_device_resize_view(): crop_box = the whole file, full = (full_w, full_h) with the shorter side at `resize` and the
@@ -759,7 +847,10 @@ class DecodeBatchMultiView(_DecodeBatchViews):
     writes SEVERAL views of each file (counts: the uint32[n] views per file; crops, views, dests: the fpng_amd_crop,
     fpng_amd_resize_view and fpng_amd_view_dest records, one per view, file 0's first; outs: per file the list of the caller's (c,
     window h, window w) views, uint8 or all of one float dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No
-    other call takes this descriptor."""
+    other call takes this descriptor.  colors: the fpng_amd_view_color records of a descriptor made with color=, one per view (the
+    call is then fpng_amd_decode_batch(_device)_planar_views_color), else None."""
+
+    colors = None
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -773,7 +864,10 @@ class DecodeBatchMultiView(_DecodeBatchViews):
 class DecodeBatchMultiViewHwc(_DecodeBatchViews):
     """What Encoder.make_decode_batch_views_hwc() returns: DecodeBatchMultiView's twin for one
     fpng_amd_decode_batch(_device)_hwc_views() call (dests: the fpng_amd_view_dest_hwc records; outs: per file the list of the
-    caller's (window h, window w, c) views).  No other call takes this descriptor."""
+    caller's (window h, window w, c) views; colors: as DecodeBatchMultiView's, for fpng_amd_decode_batch(_device)_hwc_views_color).
+    No other call takes this descriptor."""
+
+    colors = None
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1660,14 +1754,16 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None):
+                                scale=None, bias=None, color=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
         one (x, y, w, h) per view, at least one; outs[i]: the list of its destinations, a (c, window h, window w) view each, all of
         one c per file and one dtype per call.  full, window, filter, mirror, order and bottom_up: one value for all views, or a list
         with an entry per file, each entry one value for the file's views or a list with a value per view.  Constants as for
-        make_decode_batch_resize()."""
+        make_decode_batch_resize().  color: None, or the views' colour matrices (color_matrix() makes them) -- one (3, 4)
+        array-like for all views, or a list per file of one per view; the descriptor then goes through
+        fpng_amd_decode_batch(_device)_planar_views_color."""
         who = "make_decode_batch_views"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -1727,12 +1823,18 @@ class Encoder:
                 darr[at].d_pixels, darr[at].row_pitch, darr[at].plane_pitch = ptr, rp, pp
                 darr[at].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
                 at += 1
-        return DecodeBatchMultiView(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+        batch = DecodeBatchMultiView(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+        if color is not None:
+            batch.colors = _color_records(who, counts, color)
+        return batch
 
-    def _decode_views(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+    def _decode_views(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                      color):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiView):
+            if color is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices (make_decode_batch_views(..., color=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -1745,17 +1847,21 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
+            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
-        check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        fmt = C.byref(batch.fmt) if batch.fmt is not None else None
+        if batch.colors is None:
+            check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
+        else:
+            check(fn_color(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, fmt, batch.res))
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -1764,24 +1870,28 @@ class Encoder:
         the caller's views or None, channels_in_file).  A file is decoded ONCE, the bounding rectangle of its views' source boxes
         (views_source()); two small views far apart decode everything between them, and listing the file twice in
         decode_device_resize_view() may then be cheaper.  outs=None (or None for a file) allocates (3, h, w) tensors of `dtype`.
-        pngs may be a make_decode_batch_views() descriptor of device files; results=False returns it."""
-        return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, True, pngs, crops, outs, full, window, filter, mirror,
-                                  dtype, order, bottom_up, mean, std, scale, bias, results)
+        pngs may be a make_decode_batch_views() descriptor of device files; results=False returns it.
+        color: None, or a colour matrix per view (one (3, 4) array-like for all, or a list per file of one per view; color_matrix()
+        makes them from ColorJitter-style factors), applied between the resize's bytes and the normalisation --
+        fpng_amd_decode_batch_device_planar_views_color: u_c = clamp(m[c] . (r, g, b, 1), 0, 255) in fp32 fused multiply-adds, then
+        rint for uint8 or the fmaf of scale / bias; a fourth plane skips the matrix.  The identity gives exactly the call without."""
+        return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, self.lib.fpng_amd_decode_batch_device_planar_views_color, True, pngs,
+                                  crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
-        return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, False, pngs, crops, outs, full, window, filter, mirror,
-                                  dtype, order, bottom_up, mean, std, scale, bias, results)
+        return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, self.lib.fpng_amd_decode_batch_planar_views_color, False, pngs, crops,
+                                  outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None):
+                                    scale=None, bias=None, color=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
-        value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants -- is
-        make_decode_batch_views()'s."""
+        value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
+        fpng_amd_decode_batch(_device)_hwc_views_color) -- is make_decode_batch_views()'s."""
         who = "make_decode_batch_views_hwc"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -1841,12 +1951,18 @@ class Encoder:
                 darr[at].d_pixels, darr[at].row_pitch, darr[at].pixel_elems, darr[at].flags = ptr, rp, px, flags
                 darr[at].pixels_cap = (oh - 1) * abs(rp) + ((ow - 1) * px + c) * t.element_size()  # (the view's own spans, in bytes)
                 at += 1
-        return DecodeBatchMultiViewHwc(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+        batch = DecodeBatchMultiViewHwc(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+        if color is not None:
+            batch.colors = _color_records(who, counts, color)
+        return batch
 
-    def _decode_views_hwc(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+    def _decode_views_hwc(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                          color):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiViewHwc):
+            if color is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices (make_decode_batch_views_hwc(..., color=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -1859,17 +1975,21 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
+            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
-        check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
+        fmt = C.byref(batch.fmt) if batch.fmt is not None else None
+        if batch.colors is None:
+            check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
+        else:
+            check(fn_color(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, fmt, batch.res))
         return batch.results() if results else batch
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -1881,15 +2001,15 @@ class Encoder:
         (dest_layout_hwc() has the rules).  full equal to a crop's size with the whole window is the identity: a plain HWC crop,
         uint8 or float.  -> list, per file, of (status, the list of the caller's views or None, channels_in_file).  outs=None (or
         None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
-        of device files; results=False returns it."""
-        return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, True, pngs, crops, outs, full, window, filter,
-                                      mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
+        of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
+        return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, self.lib.fpng_amd_decode_batch_device_hwc_views_color, True, pngs,
+                                      crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
-        return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, False, pngs, crops, outs, full, window, filter, mirror,
-                                      dtype, order, bottom_up, mean, std, scale, bias, results)
+        return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, self.lib.fpng_amd_decode_batch_hwc_views_color, False, pngs, crops,
+                                      outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

@@ -8,6 +8,7 @@
 #include "host_workers.h"
 #include "png_parse.h"
 #include "resize.h"
+#include "resize_color.h"
 #include "resize_hwc.h"
 
 #include <algorithm>
@@ -353,6 +354,14 @@ struct Batch {
     std::vector<std::pair<uint32_t, uint32_t>> hwc_px;
     std::vector<uint64_t> hwc_pre;
     DecResizeHwc *d_resize_hwc = nullptr;
+    // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: either views call with a colour matrix per view (else
+    // NULL).  The records go up as DecResizeColor -- the record above (planar destinations: pixel_elems and flags 0) and the matrix
+    // of color_view (per record: its view's index in `color`) -- and the launch's prefix sums count tiles, as hwc_pre does
+    const fpng_amd_view_color *color = nullptr;
+    std::vector<uint32_t> color_view;
+    DecResizeColor *d_resize_color = nullptr;
+    bool per_tile() const { return hwc || color; } // a workgroup per (record, tile), all planes: dec_resize_hwc_kernel, dec_resize_color_kernel
+    size_t resize_rec_bytes() const { return color ? sizeof(DecResizeColor) : hwc ? sizeof(DecResizeHwc) : sizeof(DecResize); }
     std::vector<uint32_t> view_ofs, job_rec;
     std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
     std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
@@ -582,10 +591,11 @@ int parse_files(Batch &b)
                 b.resize.push_back(rs);
                 b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
                 b.resize_pre.push_back(b.resize_pre.back() + rs.planes * tiles);
-                if (b.hwc) { // (a workgroup per tile, all planes, and the tile's result bytes in its LDS)
-                    b.resize_lds.back() = resize_hwc_tile_lds(rs.taps_x, rs.taps_y, rs.rows, rs.planes);
+                if (b.per_tile()) { // (a workgroup per tile, all planes; channels-last: the tile's result bytes in its LDS)
+                    if (b.hwc) b.resize_lds.back() = resize_hwc_tile_lds(rs.taps_x, rs.taps_y, rs.rows, rs.planes);
                     b.hwc_pre.push_back(b.hwc_pre.back() + tiles);
-                    b.hwc_px.push_back(file_px[&rs - file_recs.data()]);
+                    b.hwc_px.push_back(b.hwc ? file_px[&rs - file_recs.data()] : std::pair<uint32_t, uint32_t>{0, 0});
+                    if (b.color) b.color_view.push_back(v0 + (uint32_t)(&rs - file_recs.data()));
                 }
             }
             j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
@@ -638,7 +648,7 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * (b.hwc ? sizeof(DecResizeHwc) : sizeof(DecResize))), o_pre = sc.carve(b.view_count ? b.resize_pre.size() * sizeof(uint64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * b.resize_rec_bytes()), o_pre = sc.carve(b.view_count ? b.resize_pre.size() * sizeof(uint64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
     const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
@@ -652,6 +662,7 @@ int place_files(Batch &b)
     b.d_crops = b.crops ? (DecCrop *)(base + o_crop) : nullptr;
     b.d_resize = b.sizes ? (DecResize *)(base + o_resize) : nullptr;
     b.d_resize_hwc = b.hwc ? (DecResizeHwc *)(base + o_resize) : nullptr;
+    b.d_resize_color = b.color ? (DecResizeColor *)(base + o_resize) : nullptr;
     b.d_resize_pre = b.view_count ? (uint64_t *)(base + o_pre) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
@@ -759,15 +770,21 @@ int plan_groups(Batch &b)
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
-    if (b.hwc) {
+    if (b.color) {
+        for (size_t q = 0; q < b.resize.size(); q++) {
+            DecResizeColor rec = {{b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second}, {}};
+            std::memcpy(rec.m, b.color[b.color_view[q]].m, sizeof rec.m);
+            std::memcpy(h_setup + ((uint8_t *)(b.d_resize_color + q) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
+        }
+    } else if (b.hwc) {
         for (size_t q = 0; q < b.resize.size(); q++) {
             const DecResizeHwc rec = {b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second};
             std::memcpy(h_setup + ((uint8_t *)(b.d_resize_hwc + q) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
         }
     } else if (b.sizes)
         std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), b.resize.size() * sizeof(DecResize));
-    if (b.view_count) { // (the launch's prefix sums: planes x tiles, the channels-last call's: tiles)
-        const std::vector<uint64_t> &pre = b.hwc ? b.hwc_pre : b.resize_pre;
+    if (b.view_count) { // (the launch's prefix sums: planes x tiles, the channels-last and colour calls': tiles)
+        const std::vector<uint64_t> &pre = b.per_tile() ? b.hwc_pre : b.resize_pre;
         std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), pre.data(), pre.size() * sizeof(uint64_t));
     }
     return FPNG_AMD_OK;
@@ -818,7 +835,8 @@ int finish_group(Batch &b, uint32_t gi)
         const bool any_filter = std::any_of(b.resize.begin() + r0, b.resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
         // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
         //  output per file keep the grid of the largest record)
-        const bool ok = b.hwc        ? launch_dec_resize_hwc(b.s, b.d_resize_hwc + r0, b.d_resize_pre + r0, b.hwc_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
+        const bool ok = b.color      ? launch_dec_resize_color(b.s, b.d_resize_color + r0, b.d_resize_pre + r0, b.hwc_pre.data() + r0, r1 - r0, lds, b.flt, any_filter, b.hwc != nullptr)
+                        : b.hwc      ? launch_dec_resize_hwc(b.s, b.d_resize_hwc + r0, b.d_resize_pre + r0, b.hwc_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
                         : b.view_count ? launch_dec_resize_exact(b.s, b.d_resize + r0, b.d_resize_pre + r0, b.resize_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
                                        : launch_dec_resize(b.s, b.d_resize + r0, r1 - r0, tiles, lds, b.flt, any_filter);
         if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
@@ -981,11 +999,11 @@ int collect_results(Batch &b)
 // planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's; sizes (with
 // crops): ... fpng_amd_decode_batch(_device)_planar_resize_view's (the plain resize call's: as whole-window bilinear views); view_count
 // and dests (with sizes): ... fpng_amd_decode_batch(_device)_planar_views's, whose crops, sizes and dests hold a record per view; hwc
-// in the place of dests: fpng_amd_decode_batch(_device)_hwc_views's
+// in the place of dests: fpng_amd_decode_batch(_device)_hwc_views's; color (with either): the _views_color calls' matrices, one per view
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
                  const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                 const fpng_amd_view_dest_hwc *hwc = nullptr)
+                 const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -996,7 +1014,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests, b.hwc = hwc;
+        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color;
         b.view_ofs.resize(n);
         for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
     }
@@ -1292,7 +1310,7 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
 // views then hold a record per view, and the destinations, which `files` leave empty, are dests')
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
                         const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                        const fpng_amd_view_dest_hwc *hwc = nullptr)
+                        const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && !view_count && i < n; i++)
@@ -1329,7 +1347,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
@@ -1338,7 +1356,8 @@ static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_des
                   offsetof(fpng_amd_view_dest_hwc, flags) == 20 && offsetof(fpng_amd_view_dest_hwc, pixels_cap) == 24 && FPNG_AMD_HWC_REVERSED == kHwcReversed,
               "fpng_amd_view_dest_hwc layout");
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
-                       const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr)
+                       const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr,
+                       const fpng_amd_view_color *color = nullptr)
 {
     if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
@@ -1356,7 +1375,29 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
             if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
             if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
         }
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc);
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color);
+}
+// fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: the matrices are judged first -- a record per view, the sum of
+// the counts (those the views call refuses: its own message, below) -- then everything the views call judges
+static_assert(sizeof(fpng_amd_view_color) == 64 && offsetof(fpng_amd_view_color, flags) == 48 && offsetof(fpng_amd_view_color, reserved) == 52, "fpng_amd_view_color layout");
+int decode_files_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
+                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_float_format *fmt,
+                             fpng_amd_decode_result *results, bool device_data)
+{
+    if (!colors) return fail(FPNG_AMD_ERR_INVALID_ARG, "null colors");
+    if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    uint64_t total = 0;
+    bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
+    for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
+    for (uint64_t v = 0; counts_ok && v < total; v++) {
+        const fpng_amd_view_color &c = colors[v];
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(c.m[k / 4][k % 4]) || std::fabs(c.m[k / 4][k % 4]) > kColorMaxEntry)
+                return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_color::m: every entry must be finite and at most 65536 in magnitude");
+        if (c.flags) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_color::flags bits (must be 0)");
+        if (c.reserved[0] | c.reserved[1] | c.reserved[2]) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_color::reserved must be 0");
+    }
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1462,6 +1503,40 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views(fpng_amd_encoder *e, const
 {
     if (!dests) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     return decode_files_views(e, files, n, view_count, crops, views, nullptr, fmt, results, true, dests);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                        const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                        const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_color(e, files, n, view_count, crops, views, dests, nullptr, colors, fmt, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                               const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                               const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_color(e, files, n, view_count, crops, views, dests, nullptr, colors, fmt, results, true);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                     const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                     const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_color(e, files, n, view_count, crops, views, nullptr, dests, colors, fmt, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                            const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_color(e, files, n, view_count, crops, views, nullptr, dests, colors, fmt, results, true);
+}
+
+// u_c of the colour rule for one pixel, on the host: color_apply (resize_color.h), the text dec_resize_color_kernel runs
+extern "C" void fpng_amd_color_apply(const fpng_amd_view_color *color, const uint8_t rgb[3], float u[3])
+{
+    for (int c = 0; c < 3; c++) u[c] = color_apply(color->m[c][0], color->m[c][1], color->m[c][2], color->m[c][3], (float)rgb[0], (float)rgb[1], (float)rgb[2]);
 }
 
 // the ONE box that a file with these views decodes: the bounding rectangle of the boxes below

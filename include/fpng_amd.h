@@ -774,6 +774,59 @@ int fpng_amd_decode_batch_hwc_views(fpng_amd_encoder *enc, const fpng_amd_png_pl
 int fpng_amd_decode_batch_device_hwc_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
                                            const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
                                            const fpng_amd_float_format *fmt /* NULL: uint8 */, fpng_amd_decode_result *results);
+/* ---- either views call with a per-view COLOUR MATRIX between the resize and the normalisation: what contrastive and multi-crop
+ *      recipes (SimCLR, BYOL, MoCo, DINO, SwAV) put there -- ColorJitter and RandomGrayscale, drawn per view.  Brightness, contrast
+ *      about a fixed centre, saturation, hue as a rotation in YIQ, grayscale and channel mixing are all affine maps of (R, G, B),
+ *      so one 3 x 4 matrix per view covers them; fmt's scale and bias, per call and per channel, cannot.  The argument lists are
+ *      those of the two views calls with `colors`, a record per view (sum(view_count), file 0's first), in front of fmt.
+ *      THE RULE.  r, g, b are the three bytes that the views call would write for a sample of the view -- after both integer
+ *      passes of the resize and their clamps, before any float step -- converted to float exactly.  All arithmetic is IEEE
+ *      binary32, one fused multiply-add where written, in this order:
+ *          t_c = fmaf(m[c][2], b, fmaf(m[c][1], g, fmaf(m[c][0], r, m[c][3])))          c = 0, 1, 2
+ *          u_c = fminf(fmaxf(t_c, 0.0f), 255.0f)            always applied; a t_c of -0.0f gives +0.0f
+ *          uint8 destination:  (uint8_t)rintf(u_c), ties to even
+ *          float destination:  round_to_dtype(fmaf(u_c, scale[c], bias[c])): fmt's constants and conversion (fp32 first, then the
+ *                              narrow type), c the FILE's channel as everywhere else
+ *      A fourth channel skips the matrix -- the alpha of a 4-channel file, the A = 255 of a 3-channel file decoded into four: the
+ *      byte, or fmaf((float)a, scale[3], bias[3]), exactly as the plain views call writes it.  Mirror, window, filter, channel
+ *      order (reversed, the planes' order), pixel_elems = 4 with three channels, pitches and bottom-up rows choose only WHERE an
+ *      element goes, never which file channel c is.
+ *      GUARANTEE 1: with the identity (m[c][c] = 1, every other entry +0.0f) a call's destinations are bit for bit those of the
+ *      plain views call, for every dtype and layout (t_c is then exactly the byte).
+ *      GUARANTEE 2: for a file with status 0 a view's elements depend only on (file, crop, view, colour, fmt), never on the
+ *      file's other views.  Only the spans the plain call writes are written.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null colors; an entry of m that is
+ *      not finite or whose magnitude exceeds 65536 (so no t_c is infinite or NaN); flags != 0; a non-zero reserved word; and
+ *      everything the underlying views call refuses.  Everything not named here is that call's, unchanged: statuses,
+ *      FPNG_AMD_DECODE_CROP_OUTSIDE per file, the one bounding box per file, FPNG_AMD_DECODE_UNDECIDED and
+ *      FPNG_AMD_DECODE_MAX_ROUNDS, the checksum flags, the limits, the destination rules of each layout.
+ *      The helper below is the rule's u_c on the host, without a GPU: the one text that the kernel runs too.
+ *      Not offered: contrast about the image's own mean (a reduction: pass a centre), clamps between jitter steps, HSV hue, blur,
+ *      solarize, posterize, fpng_amd_decode_host and the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_color with dlsym. ---- */
+typedef struct fpng_amd_view_color {
+    float m[3][4];        /* row c: coefficients of the FILE's R, G, B and a constant, in byte units (0 .. 255) */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved[3]; /* 0 */
+} fpng_amd_view_color;    /* 64 bytes */
+int fpng_amd_decode_batch_planar_views_color(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                             const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                             const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same */,
+                                             const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_color(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                    const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                    const fpng_amd_view_color *colors, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                                    fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_color(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                          const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                          const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same */,
+                                          const fpng_amd_float_format *fmt /* NULL: uint8 */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_color(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                 const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                 const fpng_amd_view_color *colors, const fpng_amd_float_format *fmt /* NULL: uint8 */,
+                                                 fpng_amd_decode_result *results);
+/* u[c] = u_c of the rule above for the pixel rgb (no GPU, no checks: the arguments are not NULL) */
+void fpng_amd_color_apply(const fpng_amd_view_color *color, const uint8_t rgb[3], float u[3]);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

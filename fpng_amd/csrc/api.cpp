@@ -1241,9 +1241,7 @@ static int host_batch_ring(fpng_amd_encoder *e, const fpng_amd_host_image *imgs,
 // data; the same arithmetic as finalize_kernel)
 static uint32_t crc_ranges_of(uint64_t zlib_size)
 {
-    const int64_t data_end = (int64_t)(kPngHeaderBytes + zlib_size - 4);
-    const int64_t end_aligned = (data_end + 15) & ~15ll;
-    return (uint32_t)((end_aligned - 48 + (1ll << 16) - 1) >> 16);
+    return crc_n_ranges(crc_end_aligned(crc_data_end(zlib_size)), kCrcRangeLog2Max);
 }
 
 static int band_check(fpng_amd_encoder *e, const fpng_amd_band *b)

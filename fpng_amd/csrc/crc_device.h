@@ -9,6 +9,7 @@
 namespace fpng_amd {
 
 constexpr int kCrcBlock = 256; // threads of a workgroup that computes a range's partial or folds a file's partials
+static_assert(kCrcBlock == (int)kCrcFoldThreads, "crc_fold_depth counts with the fold's workgroup");
 
 typedef uint32_t crc_u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) crc_u32x4 *crc_gptr_cu128;
@@ -105,19 +106,18 @@ __device__ __forceinline__ uint32_t crc_fold_partials(const CrcDeviceTables *tab
                                                       uint32_t *red, uint32_t *len_pow_out)
 {
     const uint32_t t = threadIdx.x;
-    uint32_t g = 0; // each thread folds G = 2^g consecutive partials
-    while (((uint64_t)kCrcBlock << g) < n_ranges) g++;
+    const uint32_t g = crc_fold_depth(n_ranges); // each thread folds G = 2^g consecutive partials (crc_geometry.h)
     const uint32_t G = 1u << g;
     // (the constants of the later steps are asked for now: their loads travel together with those of the partials instead of
     // one round trip each behind the fold)
-    const uint32_t group_pow = tabs->fold[rl + g - 12][t];
+    const uint32_t group_pow = tabs->fold[crc_fold_group_row(rl, g)][t];
     const uint32_t len_pow = (t < 6) ? tabs->pow_byte[t][(len >> (8 * t)) & 0xFF] : 0x80000000u; // 0x80000000 = 1
     const uint32_t unpad = tabs->inv_row_pad[pad];
     uint32_t v = 0;
     {
         // partial i of the group times x^(8*range*i): independent multiplications, four at a time (a Horner chain would
         // be G dependent ones: G = 32 for a 16384^2 image)
-        const uint32_t *xp = tabs->fold[rl - 12];
+        const uint32_t *xp = tabs->fold[crc_fold_step_row(rl)];
         for (uint32_t i = 0; i < G; i += 4) {
             uint32_t a[4], b[4], r[4];
 #pragma unroll

@@ -2,6 +2,7 @@
 #pragma once
 #include "format.h"
 #include "pack.h"
+#include "crc_geometry.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -11,6 +12,7 @@ namespace fpng_amd {
 // 256 lanes x 16 B = one 4 KiB block row per step.
 constexpr uint32_t kCrcRangeBytes = 1u << 16;
 constexpr uint32_t kCrcRowBytes = 4096;
+static_assert(kCrcRangeBytes == 1u << kCrcRangeLog2Max && kCrcRowBytes == 1u << kCrcRangeLog2Min, "crc_geometry.h: range sizes from one block row to kCrcRangeBytes");
 
 // One unit of work: a whole image, or a band of rows of one image (multi-GPU).
 struct Job {
@@ -87,7 +89,7 @@ struct CrcDeviceTables {
     uint32_t inv_row;          // x^(-8*kCrcRowBytes)
     uint32_t pad[15];
     uint32_t inv_row_pad[16];  // x^(-8*(kCrcRowBytes + p)): inv_row * inv_pad[p]
-    uint32_t fold[13][256];    // fold[e-12][t] = x^(8 * 2^e * t), e = 12..24: thread t's group of partials -> the common end point
+    uint32_t fold[kCrcFoldRows][kCrcFoldCols]; // fold[e-12][t] = x^(8 * 2^e * t), e = 12..24: thread t's group of partials -> the common end point
     uint32_t pow_byte[6][256]; // pow_byte[k][b] = x^(8 * b * 256^k): x^(8n) is the product of six entries
 };
 void build_crc_device_tables(CrcDeviceTables *t);

@@ -1456,12 +1456,7 @@ __device__ __forceinline__ void scan_job(const Job &job, JobState &st, const Row
         // the 16 KiB CRC table), down to one 4 KiB block row for small files so that the submission still spreads
         // over ~2048 blocks
         const uint64_t span = kPngHeaderBytes + zlib_size; // >= aligned data end - 48
-        uint32_t want = 2048u / n_jobs;                    // blocks this job should get (512 / 256 / 128 measured: no better for single frames)
-        want = want < 4u ? 4u : want;
-        uint32_t rl = 12;
-        while (rl < 16 && (((span >> rl) + 1 > want) || ((span >> rl) + 1 > job.crc_blocks))) rl++;
-        if (!job.whole_png) rl = 16; // row bands: every rank must cut the file into the same ranges (their CRC partials are XOR-ed)
-        st.range_log2 = rl;
+        st.range_log2 = crc_range_log2_for(span, n_jobs, job.crc_blocks, job.whole_png != 0u); // (the rule: crc_geometry.h)
     }
     // a band's counting phase stops here; whole images and band placements prepare the head of the output
     if (!job.whole_png && !(job.flags & 0x100u)) return;
@@ -1757,10 +1752,10 @@ __device__ __forceinline__ void finalize_job(const Job &job, const RowInfo *rows
         return;
     }
     const uint64_t zlib_size = st.zlib_size;
-    const int64_t data_end = (int64_t)(kPngHeaderBytes + zlib_size - 4);
-    const int64_t end_aligned = (data_end + 15) & ~15ll;
+    const int64_t data_end = crc_data_end(zlib_size);
+    const int64_t end_aligned = crc_end_aligned(data_end);
     const uint32_t rl = crc_range_log2(st);
-    const uint32_t n_ranges = (uint32_t)((end_aligned - 48 + (1ll << rl) - 1) >> rl);
+    const uint32_t n_ranges = crc_n_ranges(end_aligned, rl);
     uint32_t adler = st.adler;
     if (st.mode == 1u && aj) {
         // stored mode: Adler-32 of the filter-0 stream from the ranges' sums (assemble_stored): byte sums, and sums weighted with
@@ -1776,7 +1771,7 @@ __device__ __forceinline__ void finalize_job(const Job &job, const RowInfo *rows
     // ---- fold the CRC partials.  Partial j sits (j ranges + one block row) before the common end
     //      point, so  T = XOR_j p_j * X^j  with X = x^(8*64Ki); all needed constants are x^(8*2^i). ----
     uint32_t len_pow = 0;
-    const uint32_t raw_data = crc_fold_partials(tabs, pj, n_ranges, rl, zlib_size - 4, (uint32_t)(end_aligned - data_end), red, &len_pow);
+    const uint32_t raw_data = crc_fold_partials(tabs, pj, n_ranges, rl, zlib_size - 4, crc_pad(data_end), red, &len_pow);
     if (t == 0) {
         gptr_u8 out = to_global<gptr_u8>(job.out);
         // running CRC state (init ~0) after "IDAT", advanced over the data, then the 4 Adler bytes

@@ -137,7 +137,7 @@ uint32_t fold_partials(const uint32_t *p, uint32_t n)
     return gf2_mulmod(acc, gf2_xpow((ord - (8ull * kCrcRowBytes) % ord) % ord));
 }
 
-uint32_t crc_ranges_for_end(uint64_t end_aligned) { return (uint32_t)((end_aligned - 48 + kCrcRangeBytes - 1) / kCrcRangeBytes); }
+uint32_t crc_ranges_for_end(uint64_t end_aligned) { return crc_n_ranges((int64_t)end_aligned, kCrcRangeLog2Max); }
 
 } // namespace
 

@@ -100,6 +100,13 @@ class ViewColor(C.Structure):  # fpng_amd_view_color: 64 bytes, the colour matri
     _fields_ = [("m", (C.c_float * 4) * 3), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class ViewPost(C.Structure):  # fpng_amd_view_post: 32 bytes, the post-processing record of ONE view of the _views_post calls
+    _fields_ = [("flags", C.c_uint32), ("blur_radius", C.c_uint32), ("blur_sigma", C.c_double), ("solarize_threshold", C.c_uint32), ("posterize_bits", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+POST_BLUR, POST_SOLARIZE, POST_POSTERIZE = 1, 2, 4  # FPNG_AMD_POST_*
+BLUR_MAX_RADIUS = 16  # FPNG_AMD_BLUR_MAX_RADIUS
 HWC_REVERSED = 1  # FPNG_AMD_HWC_REVERSED
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1  # FPNG_AMD_FILTER_*
 RESIZE_MIRROR = 1  # FPNG_AMD_RESIZE_MIRROR
@@ -241,6 +248,16 @@ SIGNATURES = {
                                                      C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_hwc_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
                                                             C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_planar_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                                       C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                                              C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_hwc_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                                    C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_hwc_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                                           C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
+    "fpng_amd_blur_weights": (_int, [_u32, C.c_double, C.POINTER(C.c_int32 * 17)]),
+    "fpng_amd_view_post_apply": (_int, [C.POINTER(ViewPost), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_color_apply": (None, [C.POINTER(ViewColor), C.POINTER(C.c_uint8 * 3), C.POINTER(C.c_float * 3)]),
     "fpng_amd_views_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(Crop)]),
     "fpng_amd_decode_crop_tiles": (_int, [_u32, _u32, C.POINTER(Crop), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),

@@ -521,6 +521,85 @@ def color_apply(matrix, rgb_bytes):
     return out
 
 
+def view_post(blur=None, solarize=None, posterize=None):
+    """The fpng_amd_view_post record of one view of the views calls' post= argument: what torchvision's GaussianBlur, RandomSolarize
+    and RandomPosterize do to a uint8 image, behind the colour matrix and in front of the normalisation.  blur: None, or (kernel_size,
+    sigma) with an odd kernel_size of 3 .. 33 (radius (kernel_size - 1) / 2) and sigma > 0; solarize: None, or the threshold 0 .. 255
+    (bytes >= it are inverted); posterize: None, or the bits 0 .. 8 that are kept.  All None: the view is the colour call's,
+    untouched.  The caller draws the probabilities and the sigma; the record is the contract."""
+    rec = _lib.ViewPost()
+    if blur is not None:
+        try:
+            ks, sigma = blur
+        except (TypeError, ValueError):
+            raise ValueError("view_post: blur is (kernel_size, sigma)") from None
+        if int(ks) != ks or int(ks) % 2 != 1 or not 3 <= int(ks) <= 2 * _lib.BLUR_MAX_RADIUS + 1:
+            raise ValueError(f"view_post: a blur's kernel_size is odd, 3 .. {2 * _lib.BLUR_MAX_RADIUS + 1}, not {ks}")
+        rec.flags |= _lib.POST_BLUR
+        rec.blur_radius, rec.blur_sigma = (int(ks) - 1) // 2, float(sigma)
+    if solarize is not None:
+        if int(solarize) != solarize or not 0 <= int(solarize) <= 255:
+            raise ValueError(f"view_post: a solarize threshold is an integer 0 .. 255, not {solarize}")
+        rec.flags |= _lib.POST_SOLARIZE
+        rec.solarize_threshold = int(solarize)
+    if posterize is not None:
+        if int(posterize) != posterize or not 0 <= int(posterize) <= 8:
+            raise ValueError(f"view_post: posterize keeps 0 .. 8 bits, not {posterize}")
+        rec.flags |= _lib.POST_POSTERIZE
+        rec.posterize_bits = int(posterize)
+    return rec
+
+
+def _post_records(who, counts, post):
+    """the post= argument of the views calls -> fpng_amd_view_post[sum(counts)]: one record (view_post() makes them) for all views, a
+    list with one per file, or a list per file of a list per view"""
+    total = sum(counts)
+    arr = (_lib.ViewPost * max(total, 1))()
+
+    def put(at, rec):
+        if not isinstance(rec, _lib.ViewPost):
+            raise ValueError(f"{who}: a post record is what view_post() returns, not {type(rec).__name__}")
+        C.memmove(C.byref(arr, at * C.sizeof(_lib.ViewPost)), C.byref(rec), C.sizeof(_lib.ViewPost))
+
+    if isinstance(post, _lib.ViewPost):
+        for at in range(total):
+            put(at, post)
+        return arr
+    if not hasattr(post, "__len__") or len(post) != len(counts):
+        raise ValueError(f"{who}: post is one view_post() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
+    at = 0
+    for i, (c, recs) in enumerate(zip(counts, post)):
+        if isinstance(recs, _lib.ViewPost):
+            recs = [recs] * c
+        if not hasattr(recs, "__len__") or len(recs) != c:
+            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} post records")
+        for rec in recs:
+            put(at, rec)
+            at += 1
+    return arr
+
+
+def blur_weights(radius, sigma):
+    """fpng_amd_blur_weights (no GPU): the int32 weights k[0 .. radius] (2^22 fixed point) of the post calls' blur of this radius (1 ..
+    16) and sigma; tap t = -radius .. radius has weight k[|t|]."""
+    k = (C.c_int32 * 17)()
+    check(_lib.load().fpng_amd_blur_weights(int(radius), float(sigma), C.byref(k)))
+    return np.array(k[:int(radius) + 1], dtype=np.int32)
+
+
+def view_post_apply(post, plane):
+    """fpng_amd_view_post_apply, the host twin of the post stage (no GPU): plane (h, w) uint8 -- one colour plane of a view's window as
+    the colour call writes it -- -> (h, w) uint8, blurred, solarized and posterized as `post` (a view_post() record) says."""
+    if not isinstance(post, _lib.ViewPost):
+        raise ValueError("view_post_apply: post is what view_post() returns")
+    px = np.ascontiguousarray(plane, dtype=np.uint8)
+    if px.ndim != 2 or px.size == 0:
+        raise ValueError(f"view_post_apply: plane is (h, w) uint8, not {px.shape}")
+    out = np.empty_like(px)
+    check(_lib.load().fpng_amd_view_post_apply(C.byref(post), px.shape[1], px.shape[0], px.ctypes.data, out.ctypes.data))
+    return out
+
+
 def center_crop_view(file_w, file_h, resize, crop):
     """torchvision's Resize(resize) + CenterCrop(crop) of a file_w x file_h file as (crop_box, full, window) for
     decode_device_resize_view(): crop_box = the whole file, full = (full_w, full_h) with the shorter side at `resize` and the
@@ -851,6 +930,7 @@ class DecodeBatchMultiView(_DecodeBatchViews):
     call is then fpng_amd_decode_batch(_device)_planar_views_color), else None."""
 
     colors = None
+    posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -868,6 +948,7 @@ class DecodeBatchMultiViewHwc(_DecodeBatchViews):
     No other call takes this descriptor."""
 
     colors = None
+    posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1754,7 +1835,7 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None, color=None):
+                                scale=None, bias=None, color=None, post=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
@@ -1763,7 +1844,9 @@ class Encoder:
         with an entry per file, each entry one value for the file's views or a list with a value per view.  Constants as for
         make_decode_batch_resize().  color: None, or the views' colour matrices (color_matrix() makes them) -- one (3, 4)
         array-like for all views, or a list per file of one per view; the descriptor then goes through
-        fpng_amd_decode_batch(_device)_planar_views_color."""
+        fpng_amd_decode_batch(_device)_planar_views_color.  post: None, or the views' post-processing records (view_post() makes
+        them) -- one for all views, a list with one per file, or a list per file of one per view; the descriptor then goes through
+        fpng_amd_decode_batch(_device)_planar_views_post, with color's matrices or without."""
         who = "make_decode_batch_views"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -1826,15 +1909,17 @@ class Encoder:
         batch = DecodeBatchMultiView(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
         if color is not None:
             batch.colors = _color_records(who, counts, color)
+        if post is not None:
+            batch.posts = _post_records(who, counts, post)
         return batch
 
     def _decode_views(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                      color):
+                      color, post=None, fn_post=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiView):
-            if color is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices (make_decode_batch_views(..., color=))")
+            if color is not None or post is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices and post records (make_decode_batch_views(..., color=, post=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -1847,21 +1932,23 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color)
+            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.colors is None:
+        if batch.posts is not None:
+            check(getattr(self.lib, fn_post)(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, batch.posts, fmt, batch.res))
+        elif batch.colors is None:
             check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
         else:
             check(fn_color(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, fmt, batch.res))
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -1874,24 +1961,30 @@ class Encoder:
         color: None, or a colour matrix per view (one (3, 4) array-like for all, or a list per file of one per view; color_matrix()
         makes them from ColorJitter-style factors), applied between the resize's bytes and the normalisation --
         fpng_amd_decode_batch_device_planar_views_color: u_c = clamp(m[c] . (r, g, b, 1), 0, 255) in fp32 fused multiply-adds, then
-        rint for uint8 or the fmaf of scale / bias; a fourth plane skips the matrix.  The identity gives exactly the call without."""
+        rint for uint8 or the fmaf of scale / bias; a fourth plane skips the matrix.  The identity gives exactly the call without.
+        post: None, or a post-processing record per view (view_post() makes them: Gaussian blur, solarize, posterize; one for all
+        views, one per file, or a list per file of one per view), applied to the colour step's bytes before the normalisation --
+        fpng_amd_decode_batch_device_planar_views_post; a record without flags leaves its view exactly the call's without."""
         return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, self.lib.fpng_amd_decode_batch_device_planar_views_color, True, pngs,
-                                  crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
+                                  crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
+                                  "fpng_amd_decode_batch_device_planar_views_post")
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, self.lib.fpng_amd_decode_batch_planar_views_color, False, pngs, crops,
-                                  outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
+                                  outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
+                                  "fpng_amd_decode_batch_planar_views_post")
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None, color=None):
+                                    scale=None, bias=None, color=None, post=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
         value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
-        fpng_amd_decode_batch(_device)_hwc_views_color) -- is make_decode_batch_views()'s."""
+        fpng_amd_decode_batch(_device)_hwc_views_color) and post (then: fpng_amd_decode_batch(_device)_hwc_views_post) -- is
+        make_decode_batch_views()'s."""
         who = "make_decode_batch_views_hwc"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -1954,15 +2047,17 @@ class Encoder:
         batch = DecodeBatchMultiViewHwc(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
         if color is not None:
             batch.colors = _color_records(who, counts, color)
+        if post is not None:
+            batch.posts = _post_records(who, counts, post)
         return batch
 
     def _decode_views_hwc(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                          color):
+                          color, post=None, fn_post=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiViewHwc):
-            if color is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices (make_decode_batch_views_hwc(..., color=))")
+            if color is not None or post is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices and post records (make_decode_batch_views_hwc(..., color=, post=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -1975,21 +2070,23 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color)
+            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.colors is None:
+        if batch.posts is not None:
+            check(getattr(self.lib, fn_post)(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, batch.posts, fmt, batch.res))
+        elif batch.colors is None:
             check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
         else:
             check(fn_color(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, fmt, batch.res))
         return batch.results() if results else batch
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -2003,13 +2100,15 @@ class Encoder:
         None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
         return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, self.lib.fpng_amd_decode_batch_device_hwc_views_color, True, pngs,
-                                      crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
+                                      crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
+                                      "fpng_amd_decode_batch_device_hwc_views_post")
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, self.lib.fpng_amd_decode_batch_hwc_views_color, False, pngs, crops,
-                                      outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color)
+                                      outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
+                                      "fpng_amd_decode_batch_hwc_views_post")
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

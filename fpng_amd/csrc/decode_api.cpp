@@ -9,6 +9,7 @@
 #include "png_parse.h"
 #include "resize.h"
 #include "resize_color.h"
+#include "view_post.h"
 #include "resize_hwc.h"
 
 #include <algorithm>
@@ -362,6 +363,19 @@ struct Batch {
     DecResizeColor *d_resize_color = nullptr;
     bool per_tile() const { return hwc || color; } // a workgroup per (record, tile), all planes: dec_resize_hwc_kernel, dec_resize_color_kernel
     size_t resize_rec_bytes() const { return color ? sizeof(DecResizeColor) : hwc ? sizeof(DecResizeHwc) : sizeof(DecResize); }
+    // fpng_amd_decode_batch(_device)_planar_views_post / _hwc_views_post: the colour call with a post-processing record per view
+    // (else NULL; only when at least one view has a flag, and then with `color`: the identity for a call without matrices).  A view
+    // with flags is a POST view: its record of `resize` writes the un-mirrored uint8 window into the scratch (dst: an offset until
+    // place_files(), as src) and its destination travels in post_recs[post_of[q]] to dec_view_post_kernel; a view without (post_of
+    // -1) is a DIRECT view, the colour call's.  The two kinds go up as two arrays, the direct records in front, and are launched
+    // one after the other with prefix sums of their own (dir_pre, post_pre: tiles); job k's post records are job_post[k] ..
+    // job_post[k + 1] - 1, its direct ones the rest of job_rec's
+    const fpng_amd_view_post *post = nullptr;
+    std::vector<int32_t> post_of;
+    std::vector<DecViewPost> post_recs;
+    std::vector<uint32_t> job_post;
+    std::vector<uint64_t> dir_pre, post_pre;
+    DecViewPost *d_post = nullptr;
     std::vector<uint32_t> view_ofs, job_rec;
     std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
     std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
@@ -588,19 +602,38 @@ int parse_files(Batch &b)
             for (DecResize &rs : file_recs) {
                 rs.src += b.mid_total; // (an offset until place_files())
                 const uint64_t tiles = resize_tiles(rs.w, rs.h);
+                const uint32_t view = v0 + (uint32_t)(&rs - file_recs.data());
+                const bool is_post = b.post && b.post[view].flags;
+                if (is_post) { // (the destination goes to the post stage; the resize writes tight un-mirrored uint8 planes)
+                    const fpng_amd_view_post &vp = b.post[view];
+                    DecViewPost pr = {};
+                    pr.dst = rs.dst, pr.plane_pitch = rs.plane_pitch, pr.pitch = rs.pitch, pr.w = rs.w, pr.h = rs.h, pr.planes = rs.planes, pr.mirror = rs.flags & kResizeMirror;
+                    if (b.hwc) pr.pixel_elems = file_px[view - v0].first, pr.hwc_flags = file_px[view - v0].second;
+                    pr.flags = vp.flags, pr.radius = vp.blur_radius, pr.threshold = vp.solarize_threshold, pr.bits = vp.posterize_bits;
+                    if (vp.flags & kPostBlur) post_blur_weights(vp.blur_radius, vp.blur_sigma, pr.k);
+                    b.post_recs.push_back(pr);
+                    rs.dst = nullptr, rs.pitch = (int32_t)rs.w, rs.plane_pitch = (int64_t)((uint64_t)rs.w * rs.h), rs.flags &= ~kResizeMirror;
+                }
+                if (b.post) b.post_of.push_back(is_post ? (int32_t)b.post_recs.size() - 1 : -1);
                 b.resize.push_back(rs);
                 b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
                 b.resize_pre.push_back(b.resize_pre.back() + rs.planes * tiles);
                 if (b.per_tile()) { // (a workgroup per tile, all planes; channels-last: the tile's result bytes in its LDS)
-                    if (b.hwc) b.resize_lds.back() = resize_hwc_tile_lds(rs.taps_x, rs.taps_y, rs.rows, rs.planes);
+                    if (b.hwc && !is_post) b.resize_lds.back() = resize_hwc_tile_lds(rs.taps_x, rs.taps_y, rs.rows, rs.planes);
                     b.hwc_pre.push_back(b.hwc_pre.back() + tiles);
-                    b.hwc_px.push_back(b.hwc ? file_px[&rs - file_recs.data()] : std::pair<uint32_t, uint32_t>{0, 0});
+                    b.hwc_px.push_back(b.hwc && !is_post ? file_px[&rs - file_recs.data()] : std::pair<uint32_t, uint32_t>{0, 0});
                     if (b.color) b.color_view.push_back(v0 + (uint32_t)(&rs - file_recs.data()));
                 }
             }
             j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
             pitch = (int64_t)crop.w, plane_pitch = (int64_t)((uint64_t)crop.w * crop.h);
             b.mid_total += ((size_t)plane_pitch * desired + 15) & ~(size_t)15;
+            // (the post views' windows: next to the box's planes)
+            for (size_t q = b.job_rec.back(); b.post && q < b.resize.size(); q++)
+                if (b.post_of[q] >= 0) {
+                    b.resize[q].dst = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
+                    b.mid_total += ((size_t)b.resize[q].w * b.resize[q].h * desired + 15) & ~(size_t)15;
+                }
         }
         if (b.planar) j.pitch = (int32_t)pitch, b.plane_pitch.push_back(plane_pitch); // (|pitch| < 2^31: decode_files_planar)
         // (the tiles a crop needs: DecJob::nseg is read by the un-filter kernels, by the plan and by the granules' sizing only, so
@@ -648,7 +681,7 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * b.resize_rec_bytes()), o_pre = sc.carve(b.view_count ? b.resize_pre.size() * sizeof(uint64_t) : 0), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * b.resize_rec_bytes()), o_pre = sc.carve(b.view_count ? (b.resize_pre.size() + (b.post ? 1 : 0)) * sizeof(uint64_t) : 0), o_post = sc.carve(b.post_recs.size() * sizeof(DecViewPost)), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
     const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
@@ -664,6 +697,7 @@ int place_files(Batch &b)
     b.d_resize_hwc = b.hwc ? (DecResizeHwc *)(base + o_resize) : nullptr;
     b.d_resize_color = b.color ? (DecResizeColor *)(base + o_resize) : nullptr;
     b.d_resize_pre = b.view_count ? (uint64_t *)(base + o_pre) : nullptr;
+    b.d_post = b.post ? (DecViewPost *)(base + o_post) : nullptr;
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -694,7 +728,10 @@ int place_files(Batch &b)
         if (!b.device_data) j.z = b.d.z + (size_t)(uintptr_t)j.z;
         if (b.sizes) {
             j.out = base + o_mid + (size_t)(uintptr_t)j.out;
-            for (uint32_t q = b.job_rec[k]; q < b.job_rec[k + 1]; q++) b.resize[q].src = base + o_mid + (size_t)(uintptr_t)b.resize[q].src;
+            for (uint32_t q = b.job_rec[k]; q < b.job_rec[k + 1]; q++) {
+                b.resize[q].src = base + o_mid + (size_t)(uintptr_t)b.resize[q].src;
+                if (b.post && b.post_of[q] >= 0) b.post_recs[b.post_of[q]].src = b.resize[q].dst = base + o_mid + (size_t)(uintptr_t)b.resize[q].dst;
+            }
         }
         // (parse_files sized the CRC partials of a host-resident file for a stream that starts on a 16-byte boundary; dec_verify_kernel
         //  counts the ranges from the real address, and one more range than sized would be the next file's slot)
@@ -770,7 +807,26 @@ int plan_groups(Batch &b)
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
-    if (b.color) {
+    if (b.post) {
+        // (the direct views' records, then the post views', each kind in the views' order and with the tiles in front of it)
+        const size_t nd = b.resize.size() - b.post_recs.size();
+        size_t di = 0, pi = 0;
+        b.dir_pre.assign(1, 0), b.post_pre.assign(1, 0), b.job_post.clear();
+        for (uint32_t k = 0, q = 0; k <= nj; k++) {
+            for (; q < b.job_rec[k]; q++) {
+                DecResizeColor rec = {{b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second}, {}};
+                std::memcpy(rec.m, b.color[b.color_view[q]].m, sizeof rec.m);
+                const bool is_post = b.post_of[q] >= 0;
+                std::vector<uint64_t> &pre = is_post ? b.post_pre : b.dir_pre;
+                pre.push_back(pre.back() + b.resize_tiles[q]);
+                std::memcpy(h_setup + ((uint8_t *)(b.d_resize_color + (is_post ? nd + pi++ : di++)) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
+            }
+            b.job_post.push_back((uint32_t)pi);
+        }
+        std::memcpy(h_setup + ((uint8_t *)b.d_post - (uint8_t *)b.d_jobs), b.post_recs.data(), b.post_recs.size() * sizeof(DecViewPost));
+        std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), b.dir_pre.data(), b.dir_pre.size() * sizeof(uint64_t));
+        std::memcpy(h_setup + ((uint8_t *)(b.d_resize_pre + nd + 1) - (uint8_t *)b.d_jobs), b.post_pre.data(), b.post_pre.size() * sizeof(uint64_t));
+    } else if (b.color) {
         for (size_t q = 0; q < b.resize.size(); q++) {
             DecResizeColor rec = {{b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second}, {}};
             std::memcpy(rec.m, b.color[b.color_view[q]].m, sizeof rec.m);
@@ -783,7 +839,7 @@ int plan_groups(Batch &b)
         }
     } else if (b.sizes)
         std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), b.resize.size() * sizeof(DecResize));
-    if (b.view_count) { // (the launch's prefix sums: planes x tiles, the channels-last and colour calls': tiles)
+    if (b.view_count && !b.post) { // (the launch's prefix sums: planes x tiles, the channels-last and colour calls': tiles)
         const std::vector<uint64_t> &pre = b.per_tile() ? b.hwc_pre : b.resize_pre;
         std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), pre.data(), pre.size() * sizeof(uint64_t));
     }
@@ -828,7 +884,22 @@ int finish_group(Batch &b, uint32_t gi)
                       b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.sizes ? nullptr : b.flt, b.crops ? b.d_crops + g.j0 : nullptr);
     // (the resize: behind the group's pixel pass and stored copy on the same stream, on whatever the scratch then holds -- it writes
     //  the spans of the destination and nothing else, whatever a file's status turns out to be)
-    if (b.sizes) {
+    if (b.post) {
+        // the group's direct views as the colour call launches them; its post views' windows into the scratch -- uint8, planar,
+        // un-mirrored -- and the post stage out of those into the destinations
+        const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1], p0 = b.job_post[g.j0], p1 = b.job_post[g.j1], d0 = r0 - p0, d1 = r1 - p1;
+        const uint32_t nd = (uint32_t)(b.resize.size() - b.post_recs.size());
+        uint32_t lds[2] = {0, 0};
+        bool any_filter[2] = {false, false};
+        for (uint32_t q = r0; q < r1; q++) {
+            const int kind = b.post_of[q] >= 0;
+            lds[kind] = std::max(lds[kind], b.resize_lds[q]), any_filter[kind] |= b.resize[q].filter != kResizeBilinear;
+        }
+        const bool ok = launch_dec_resize_color(b.s, b.d_resize_color + d0, b.d_resize_pre + d0, b.dir_pre.data() + d0, d1 - d0, lds[0], b.flt, any_filter[0], b.hwc != nullptr) &&
+                        launch_dec_resize_color(b.s, b.d_resize_color + nd + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, lds[1], nullptr, any_filter[1], false) &&
+                        launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr);
+        if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
+    } else if (b.sizes) {
         const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1]; // (the records of the group's jobs)
         const uint32_t tiles = *std::max_element(b.resize_tiles.begin() + r0, b.resize_tiles.begin() + r1), lds = *std::max_element(b.resize_lds.begin() + r0, b.resize_lds.begin() + r1);
         // (a group of bilinear views -- the plain resize call's always are -- runs the instantiation without the second filter)
@@ -1003,7 +1074,7 @@ int collect_results(Batch &b)
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
                  const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                 const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr)
+                 const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -1014,7 +1085,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color;
+        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr;
         b.view_ofs.resize(n);
         for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
     }
@@ -1310,7 +1381,7 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
 // views then hold a record per view, and the destinations, which `files` leave empty, are dests')
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
                         const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                        const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr)
+                        const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && !view_count && i < n; i++)
@@ -1347,7 +1418,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
@@ -1357,7 +1428,7 @@ static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_des
               "fpng_amd_view_dest_hwc layout");
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                        const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr,
-                       const fpng_amd_view_color *color = nullptr)
+                       const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr)
 {
     if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
@@ -1375,17 +1446,13 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
             if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
             if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
         }
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color);
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post);
 }
 // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: the matrices are judged first -- a record per view, the sum of
 // the counts (those the views call refuses: its own message, below) -- then everything the views call judges
 static_assert(sizeof(fpng_amd_view_color) == 64 && offsetof(fpng_amd_view_color, flags) == 48 && offsetof(fpng_amd_view_color, reserved) == 52, "fpng_amd_view_color layout");
-int decode_files_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
-                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_float_format *fmt,
-                             fpng_amd_decode_result *results, bool device_data)
+int check_color_records(const fpng_amd_view_color *colors, const uint32_t *view_count, uint32_t n)
 {
-    if (!colors) return fail(FPNG_AMD_ERR_INVALID_ARG, "null colors");
-    if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
     bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
@@ -1397,7 +1464,65 @@ int decode_files_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *fil
         if (c.flags) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_color::flags bits (must be 0)");
         if (c.reserved[0] | c.reserved[1] | c.reserved[2]) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_color::reserved must be 0");
     }
+    return FPNG_AMD_OK;
+}
+int decode_files_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
+                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_float_format *fmt,
+                             fpng_amd_decode_result *results, bool device_data)
+{
+    if (!colors) return fail(FPNG_AMD_ERR_INVALID_ARG, "null colors");
+    if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    if (int rc = check_color_records(colors, view_count, n)) return rc;
     return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
+}
+// fpng_amd_decode_batch(_device)_planar_views_post / _hwc_views_post: the post records are judged first, then the matrices (NULL: the
+// identity for every view), then everything the views call judges.  w, h: the view's window, where it is known (else 0: not judged)
+const char *check_post_record(const fpng_amd_view_post &p, uint32_t w, uint32_t h)
+{
+    if (p.flags & ~(uint32_t)(kPostBlur | kPostSolarize | kPostPosterize)) return "unknown fpng_amd_view_post::flags bits (FPNG_AMD_POST_BLUR, _SOLARIZE, _POSTERIZE)";
+    if (p.reserved[0] | p.reserved[1]) return "fpng_amd_view_post::reserved must be 0";
+    if (p.flags & kPostBlur) {
+        if (!p.blur_radius || p.blur_radius > kPostMaxRadius) return "fpng_amd_view_post::blur_radius must be 1 .. 16 with FPNG_AMD_POST_BLUR";
+        if (!std::isfinite(p.blur_sigma) || !(p.blur_sigma > 0.0)) return "fpng_amd_view_post::blur_sigma must be finite and > 0 with FPNG_AMD_POST_BLUR";
+        if (w && h && p.blur_radius >= std::min(w, h)) return "fpng_amd_view_post::blur_radius must be below the window's w and h (one reflection at the border)";
+    } else if (p.blur_radius || p.blur_sigma != 0.0) // (a NaN is not 0)
+        return "fpng_amd_view_post::blur_radius and blur_sigma must be 0 without FPNG_AMD_POST_BLUR";
+    if (p.solarize_threshold > 255u) return "fpng_amd_view_post::solarize_threshold must be 0 .. 255";
+    if (p.posterize_bits > 8u) return "fpng_amd_view_post::posterize_bits must be 0 .. 8";
+    if (p.solarize_threshold && !(p.flags & kPostSolarize)) return "fpng_amd_view_post::solarize_threshold must be 0 without FPNG_AMD_POST_SOLARIZE";
+    if (p.posterize_bits && !(p.flags & kPostPosterize)) return "fpng_amd_view_post::posterize_bits must be 0 without FPNG_AMD_POST_POSTERIZE";
+    return nullptr;
+}
+static_assert(sizeof(fpng_amd_view_post) == 32 && offsetof(fpng_amd_view_post, blur_sigma) == 8 && offsetof(fpng_amd_view_post, solarize_threshold) == 16 &&
+                  offsetof(fpng_amd_view_post, reserved) == 24 && FPNG_AMD_POST_BLUR == kPostBlur && FPNG_AMD_POST_SOLARIZE == kPostSolarize &&
+                  FPNG_AMD_POST_POSTERIZE == kPostPosterize && FPNG_AMD_BLUR_MAX_RADIUS == kPostMaxRadius,
+              "fpng_amd_view_post layout");
+int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
+                            const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_view_post *posts,
+                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data)
+{
+    if (!posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts");
+    if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    uint64_t total = 0;
+    bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
+    for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
+    bool any = false;
+    for (uint64_t v = 0; counts_ok && v < total; v++) {
+        if (const char *why = check_post_record(posts[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        any |= posts[v].flags != 0;
+    }
+    if (colors)
+        if (int rc = check_color_records(colors, view_count, n)) return rc;
+    // (no view with a flag: the colour call, or the plain one, enqueues what it always does)
+    if (!any) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
+    std::vector<fpng_amd_view_color> identity;
+    if (!colors) {
+        fpng_amd_view_color one = {};
+        one.m[0][0] = one.m[1][1] = one.m[2][2] = 1.0f;
+        identity.assign((size_t)total, one);
+        colors = identity.data();
+    }
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1531,6 +1656,73 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_color(fpng_amd_encoder *e,
                                                             const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
     return decode_files_views_color(e, files, n, view_count, crops, views, nullptr, dests, colors, fmt, results, true);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                       const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                       const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                              const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                              const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                    const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                    const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                           const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                           const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true);
+}
+
+// the blur's weights on the host: post_blur_weights (view_post.h), what the post calls hand to dec_view_post_kernel
+extern "C" int fpng_amd_blur_weights(uint32_t radius, double sigma, int32_t k[17])
+{
+    if (!k) return fail(FPNG_AMD_ERR_INVALID_ARG, "null k");
+    if (!radius || radius > kPostMaxRadius) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_post::blur_radius must be 1 .. 16 with FPNG_AMD_POST_BLUR");
+    if (!std::isfinite(sigma) || !(sigma > 0.0)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_post::blur_sigma must be finite and > 0 with FPNG_AMD_POST_BLUR");
+    post_blur_weights(radius, sigma, k);
+    return FPNG_AMD_OK;
+}
+
+// steps 2 to 4 of the post rule for one w x h plane of bytes, on the host: the texts of view_post.h, which dec_view_post_kernel runs
+extern "C" int fpng_amd_view_post_apply(const fpng_amd_view_post *post, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out)
+{
+    if (!post || !in || !out || !w || !h) return fail(FPNG_AMD_ERR_INVALID_ARG, "null post, in or out, or an empty plane");
+    if (const char *why = check_post_record(*post, w, h)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+    const size_t count = (size_t)w * h;
+    std::vector<uint8_t> g(in, in + count);
+    if (post->flags & kPostBlur) {
+        const int32_t R = (int32_t)post->blur_radius;
+        int32_t k[kPostMaxRadius + 1];
+        post_blur_weights(post->blur_radius, post->blur_sigma, k);
+        std::vector<uint8_t> hp(count);
+        for (uint32_t q = 0; q < h; q++)
+            for (uint32_t i = 0; i < w; i++) {
+                int32_t sum = 1 << (kResizeBits - 1);
+                for (int32_t t = -R; t <= R; t++) sum += (int32_t)in[(size_t)q * w + post_refl((int32_t)i + t, w)] * k[t < 0 ? -t : t];
+                hp[(size_t)q * w + i] = (uint8_t)resize_clip8(sum);
+            }
+        for (uint32_t q = 0; q < h; q++)
+            for (uint32_t i = 0; i < w; i++) {
+                int32_t sum = 1 << (kResizeBits - 1);
+                for (int32_t t = -R; t <= R; t++) sum += (int32_t)hp[(size_t)post_refl((int32_t)q + t, h) * w + i] * k[t < 0 ? -t : t];
+                g[(size_t)q * w + i] = (uint8_t)resize_clip8(sum);
+            }
+    }
+    for (size_t q = 0; q < count; q++) out[q] = (uint8_t)post_point(g[q], post->flags, post->solarize_threshold, post->posterize_bits);
+    return FPNG_AMD_OK;
 }
 
 // u_c of the colour rule for one pixel, on the host: color_apply (resize_color.h), the text dec_resize_color_kernel runs

@@ -1,0 +1,174 @@
+// view_post.hip -- the third stage of fpng_amd_decode_batch(_device)_planar_views_post and _hwc_views_post: a view's blur, solarize
+// and posterize (view_post.h: the rule, and the text the host's fpng_amd_view_post_apply runs) on the un-mirrored uint8 window that
+// dec_resize_color_kernel<-1, *, false> has written into the decode scratch, and the store into the caller's destination.  One
+// workgroup per (record, tile of kResizeTileW x kResizeTileH samples of the window), ALL planes, the exact grid with pre counting
+// tiles, as dec_resize_color_kernel runs.  Per colour plane, with R the view's radius:
+//   1. the tile and a halo of R samples on every side into LDS, the window's border reflected (post_refl): (16 + 2R) rows of
+//      (64 + 2R) bytes -- at R = 16 48 x 96;
+//   2. the horizontal pass out of those into LDS bytes, the tile's rows and the halo above and below (the horizontal pass of a
+//      reflected row IS that row of H);
+//   3. the vertical pass out of those, then solarize and posterize: a thread's bytes of its four rows go into four registers, a
+//      byte per plane, as in dec_resize_color_kernel.
+// R = 0 (point operations only) reads the scratch straight into the registers: no LDS, no barrier.  A fourth plane (alpha, or the
+// 255 of a 3-channel file) is copied.
+//   4. the store: a thread has all channels of its pixels; every element is stored on its own -- planar destinations as
+//      dec_resize_color_kernel's, lanes along a row of a plane; channels-last ones by element, position c or planes - 1 - c of the
+//      pixel, positions >= planes never written.
+// LDS reads of the passes are bytes at consecutive addresses along a wave's lanes: four lanes a bank, one address each -- no conflict.
+// The kernel is symmetric, so taps -d and d share one product: sum = 2^21 + s[0] k[0] + sum_d (s[-d] + s[d]) k[d] -- the same integer.
+#include "decode.h"
+#include "float_store.h"
+#include "resize.h"
+#include "resize_hwc.h"
+#include "view_post.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+namespace fpng_amd {
+
+namespace {
+
+constexpr uint32_t kPostHaloW = kResizeTileW + 2 * kPostMaxRadius, kPostHaloH = kResizeTileH + 2 * kPostMaxRadius; // 96 x 48
+
+// byte z of FILE channel c -> the destination's element, stored
+template <int kDtype> __device__ __forceinline__ void post_store(uint8_t *p, uint32_t z, float sc, float bi)
+{
+    if constexpr (kDtype < 0) *p = (uint8_t)z;
+    else {
+        const float f = __builtin_fmaf((float)z, sc, bi);
+        if constexpr (kDtype == 0) *(f32_a *)p = f;
+        else *(u16_a *)p = half_bits<kDtype>(f);
+    }
+}
+
+template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void dec_view_post_kernel(const DecViewPost *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t S[kPostHaloH * kPostHaloW]; // the tile and its halo, rows of sw bytes
+    __shared__ __attribute__((aligned(16))) uint8_t Hb[kPostHaloH * kResizeTileW]; // the horizontal pass: rows of kResizeTileW bytes
+    __shared__ int32_t K[kPostMaxRadius + 1];                                   // k[d]: taps -d and d share it
+    const uint64_t g = pre[0] + blockIdx.x;
+    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const DecViewPost &r = recs[lo];
+    const uint32_t w = r.w, h = r.h, C = r.planes, flags = r.flags;
+    const uint32_t tile = (uint32_t)(g - pre[lo]);
+    if ((uint64_t)tile >= resize_tiles(w, h)) return; // (never, with the host's pre)
+    const uint32_t tiles_x = (w + kResizeTileW - 1) / kResizeTileW;
+    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
+    const uint32_t nq = std::min(kResizeTileH, h - oq0), nw = std::min(kResizeTileW, w - ox0);
+    // (the host's records: 1 .. 16 with blur, and below w and h -- the bounds of S and of one reflection, held here too)
+    const uint32_t R = (flags & kPostBlur) ? std::min(std::min(r.radius, kPostMaxRadius), std::min(w, h) - 1u) : 0u;
+    const uint32_t tid = threadIdx.x, o = tid % kResizeTileW, wave = tid / kResizeTileW;
+    constexpr uint32_t kWaves = kResizeBlock / kResizeTileW, kRowsPerWave = kResizeTileH / kWaves;
+    const uint64_t plane_bytes = (uint64_t)w * h;
+    const uint32_t threshold = r.threshold, bits = r.bits;
+    uint32_t res[kRowsPerWave] = {};
+    if (R) {
+        if (tid <= R) K[tid] = r.k[tid];
+        const uint32_t sw = nw + 2 * R, sh = nq + 2 * R; // (<= kPostHaloW, kPostHaloH)
+        for (uint32_t plane = 0; plane < C && plane < 3; plane++) {
+            const uint8_t *const src = r.src + plane * plane_bytes;
+            if (plane) __syncthreads(); // (the plane before has been read out of S and Hb)
+            // ---- 1. the tile and its halo ----
+            for (uint32_t j = wave; j < sh; j += kWaves) {
+                const uint8_t *const row = src + (uint64_t)post_refl((int32_t)(oq0 + j) - (int32_t)R, h) * w;
+                for (uint32_t i = o; i < sw; i += kResizeTileW) S[j * kPostHaloW + i] = row[post_refl((int32_t)(ox0 + i) - (int32_t)R, w)];
+            }
+            __syncthreads();
+            // ---- 2. the horizontal pass ----
+            if (o < nw)
+                for (uint32_t j = wave; j < sh; j += kWaves) {
+                    const uint8_t *const s = S + j * kPostHaloW + o + R; // (the sample itself; taps -d and d: one product)
+                    int32_t sum = (1 << (kResizeBits - 1)) + (int32_t)s[0] * K[0];
+#pragma unroll 4
+                    for (uint32_t d = 1; d <= R; d++) sum += ((int32_t)s[-(int32_t)d] + (int32_t)s[d]) * K[d];
+                    Hb[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
+                }
+            __syncthreads();
+            // ---- 3. the vertical pass, the point operations ----
+            if (o < nw) {
+#pragma unroll
+                for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                    const uint32_t q = wave + k * kWaves;
+                    if (q >= nq) break;
+                    const uint8_t *const s = Hb + (q + R) * kResizeTileW + o;
+                    int32_t sum = (1 << (kResizeBits - 1)) + (int32_t)s[0] * K[0];
+#pragma unroll 4
+                    for (uint32_t d = 1; d <= R; d++) sum += ((int32_t)s[-(int32_t)(d * kResizeTileW)] + (int32_t)s[d * kResizeTileW]) * K[d];
+                    res[k] |= post_point(resize_clip8(sum), flags, threshold, bits) << (8 * plane);
+                }
+            }
+        }
+    } else if (o < nw) {
+        for (uint32_t plane = 0; plane < C && plane < 3; plane++) {
+#pragma unroll
+            for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                const uint32_t q = wave + k * kWaves;
+                if (q >= nq) break;
+                res[k] |= post_point(r.src[plane * plane_bytes + (uint64_t)(oq0 + q) * w + ox0 + o], flags, threshold, bits) << (8 * plane);
+            }
+        }
+    }
+    if (o >= nw) return; // (no barrier behind this line)
+    if (C == 4) {
+#pragma unroll
+        for (uint32_t k = 0; k < kRowsPerWave; k++) {
+            const uint32_t q = wave + k * kWaves;
+            if (q >= nq) break;
+            res[k] |= (uint32_t)r.src[3 * plane_bytes + (uint64_t)(oq0 + q) * w + ox0 + o] << 24;
+        }
+    }
+    // ---- 4. the store ----
+    constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
+    const uint32_t col = r.mirror ? w - 1 - (ox0 + o) : ox0 + o;
+    // (file channel c: plane c, or element c -- reversed: planes - 1 - c -- of its pixel)
+    int64_t at[4], first;
+    if constexpr (!kHwc) {
+        first = (int64_t)col * kElem;
+#pragma unroll
+        for (uint32_t c = 0; c < 4; c++) at[c] = (int64_t)c * r.plane_pitch;
+    } else {
+        const bool reversed = r.hwc_flags & kHwcReversed;
+        first = (int64_t)((uint64_t)col * r.pixel_elems * kElem);
+#pragma unroll
+        for (uint32_t c = 0; c < 4; c++) at[c] = (int64_t)((reversed ? C - 1 - c : c) * kElem);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kRowsPerWave; k++) {
+        const uint32_t q = wave + k * kWaves;
+        if (q >= nq) break;
+        uint8_t *const p = r.dst + (int64_t)(oq0 + q) * r.pitch + first;
+        post_store<kDtype>(p + at[0], res[k] & 255u, flt.scale[0], flt.bias[0]);
+        post_store<kDtype>(p + at[1], res[k] >> 8 & 255u, flt.scale[1], flt.bias[1]);
+        post_store<kDtype>(p + at[2], res[k] >> 16 & 255u, flt.scale[2], flt.bias[2]);
+        if (C == 4) post_store<kDtype>(p + at[3], res[k] >> 24, flt.scale[3], flt.bias[3]);
+    }
+}
+
+} // namespace
+
+bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc)
+{
+    using Kernel = void (*)(const DecViewPost *, const uint64_t *, uint32_t, DecFloat);
+    static const Kernel kernels[2][kDecFloatTypes + 1] = {
+        {dec_view_post_kernel<-1, false>, dec_view_post_kernel<0, false>, dec_view_post_kernel<1, false>, dec_view_post_kernel<2, false>},
+        {dec_view_post_kernel<-1, true>, dec_view_post_kernel<0, true>, dec_view_post_kernel<1, true>, dec_view_post_kernel<2, true>}};
+    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
+    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
+    for (uint32_t r0 = 0; r0 < n;) {
+        uint32_t r1 = r0 + 1;
+        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
+        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
+        hipLaunchKernelGGL(kernels[hwc][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+        r0 = r1;
+    }
+    return true;
+}
+
+} // namespace fpng_amd

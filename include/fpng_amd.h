@@ -801,8 +801,8 @@ int fpng_amd_decode_batch_device_hwc_views(fpng_amd_encoder *enc, const fpng_amd
  *      FPNG_AMD_DECODE_CROP_OUTSIDE per file, the one bounding box per file, FPNG_AMD_DECODE_UNDECIDED and
  *      FPNG_AMD_DECODE_MAX_ROUNDS, the checksum flags, the limits, the destination rules of each layout.
  *      The helper below is the rule's u_c on the host, without a GPU: the one text that the kernel runs too.
- *      Not offered: contrast about the image's own mean (a reduction: pass a centre), clamps between jitter steps, HSV hue, blur,
- *      solarize, posterize, fpng_amd_decode_host and the fpng:: drop-in.
+ *      Not offered: contrast about the image's own mean (a reduction: pass a centre), clamps between jitter steps, HSV hue,
+ *      fpng_amd_decode_host and the fpng:: drop-in.  Blur, solarize and posterize: the _views_post calls below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_color with dlsym. ---- */
 typedef struct fpng_amd_view_color {
     float m[3][4];        /* row c: coefficients of the FILE's R, G, B and a constant, in byte units (0 .. 255) */
@@ -827,6 +827,80 @@ int fpng_amd_decode_batch_device_hwc_views_color(fpng_amd_encoder *enc, const fp
                                                  fpng_amd_decode_result *results);
 /* u[c] = u_c of the rule above for the pixel rgb (no GPU, no checks: the arguments are not NULL) */
 void fpng_amd_color_apply(const fpng_amd_view_color *color, const uint8_t rgb[3], float u[3]);
+/* ---- either colour call with a POST-PROCESSING record per view behind the matrix: GaussianBlur (SimCLR, BYOL, MoCo v2/v3, DINO,
+ *      SwAV), RandomSolarize (BYOL, DINO) and posterize, drawn per view by the caller -- the library draws no probabilities.  The
+ *      argument lists are those of the _views_color calls with `posts`, a record per view (sum(view_count), file 0's first),
+ *      behind `colors`; colors may be NULL: the identity for every view.
+ *      THE RULE (every element is exact).  A view whose flags is 0 is written bit for bit as the _views_color call writes it (with
+ *      NULL colors: as the plain views call), in every dtype and layout.  For a view with any flag, file channels 0, 1, 2 only -- a
+ *      fourth channel (alpha, or the A = 255 of a 3-channel file) skips everything, as it skips the matrix:
+ *        1. bytes:  B_c[q][i] = (uint8_t)rintf(u_c), u_c the colour rule's value for sample (q, i) of the UN-MIRRORED window: what
+ *           the colour call writes into a uint8 planar destination without the mirror flag.  The steps behind the matrix work on
+ *           bytes, as torchvision's do on a PIL image.
+ *        2. blur (FPNG_AMD_POST_BLUR), radius R, kernel size 2R + 1.  The weights are computed on the host only, in IEEE double, in
+ *           this order (fpng_amd_blur_weights returns them; the kernel never evaluates exp):
+ *               p[d] = exp(-0.5 * (d / sigma) * (d / sigma))     d = 0 .. R    (torchvision's _get_gaussian_kernel1d)
+ *               ww = p[0];  for d = 1 .. R: ww = ww + 2.0 * p[d]
+ *               k[d] = (int)(0.5 + p[d] / ww * 4194304.0)        2^22, as the resize's weights
+ *           Tap t = -R .. R has weight k[|t|]; borders reflect without repeating the edge (torch's `reflect`, scipy's `mirror`):
+ *               refl(j, n) = j < 0 ? -j : j >= n ? 2 (n - 1) - j : j
+ *           Two passes, both to bytes, each the resize rule's pass, clamp((2^21 + sum) >> 22, 0, 255):
+ *               H[q][i] = pass(sum_t B[q][refl(i + t, w)] * k[|t|]),   G[q][i] = pass(sum_t H[refl(q + t, h)][i] * k[|t|])
+ *           The sums are integers below 2^31: their order is free.  Without the flag G = B.  The blur sees the WINDOW only: what
+ *           lies outside it in the resized image is not read, the border reflects.
+ *        3. solarize (FPNG_AMD_POST_SOLARIZE):  S = G >= threshold ? 255 - G : G          (Pillow's ImageOps.solarize)
+ *        4. posterize (FPNG_AMD_POST_POSTERIZE): Z = S & (0xFF00 >> bits) & 0xFF          (Pillow's ImageOps.posterize: the top
+ *           `bits` bits; 8 is the identity, 0 gives 0)
+ *        5. the element: Z for a uint8 destination, round_to_dtype(fmaf((float)Z, scale[c], bias[c])) for a float one, c the FILE's
+ *           channel; element (q, i) comes from Z[q][i], or Z[q][w - 1 - i] with FPNG_AMD_RESIZE_MIRROR.
+ *      Mirror, window, channel order, pixel_elems, pitches and bottom-up rows only place elements.
+ *      GUARANTEES: a record with flags == 0 leaves its view bit for bit the colour call's; for a file with status 0 a view depends
+ *      only on (file, crop, view, colour, post, fmt), never on the file's other views; only the spans the views call writes are
+ *      written (pitch padding, the fourth element of pixel_elems = 4, files of any status).
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null posts; unknown flag bits; a
+ *      non-zero reserved word; with BLUR a radius of 0 or above 16, a sigma that is not finite or not > 0, or R >= min(window w,
+ *      window h) (one reflection must be enough); without BLUR a non-zero radius or sigma; a threshold above 255; bits above 8; a
+ *      threshold or bits given without its flag; and everything the colour call refuses.  Statuses are the views call's.
+ *      A post view runs in two stages: its un-mirrored uint8 window goes into the encoder's decode scratch (C * w * h bytes per
+ *      post view), and a tiled separable filter with its halo in LDS writes the destination from there.  A call in which no view
+ *      has a flag enqueues exactly what the colour (or plain) call enqueues.
+ *      Not offered: blurring alpha, Pillow's box-approximated ImageFilter.GaussianBlur, kernel sizes above 33, a sigma per axis,
+ *      drawing the random parameters, fpng_amd_decode_host and the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_post with dlsym. ---- */
+#define FPNG_AMD_POST_BLUR 1u
+#define FPNG_AMD_POST_SOLARIZE 2u
+#define FPNG_AMD_POST_POSTERIZE 4u
+#define FPNG_AMD_BLUR_MAX_RADIUS 16u
+typedef struct fpng_amd_view_post {
+    uint32_t flags;              /* FPNG_AMD_POST_*; 0 = this view is the colour call's, untouched */
+    uint32_t blur_radius;        /* R: 1 .. 16 with BLUR (kernel size 2R + 1), else 0 */
+    double blur_sigma;           /* finite and > 0 with BLUR, else 0 */
+    uint32_t solarize_threshold; /* 0 .. 255 with SOLARIZE, else 0 */
+    uint32_t posterize_bits;     /* 0 .. 8 with POSTERIZE, else 0 */
+    uint32_t reserved[2];        /* 0 */
+} fpng_amd_view_post;            /* 32 bytes */
+int fpng_amd_decode_batch_planar_views_post(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                            const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                            const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                            const fpng_amd_view_post *posts /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                            fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_post(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                   const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                   const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt,
+                                                   fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_post(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                         const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                         const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                         const fpng_amd_view_post *posts /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 */,
+                                         fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_post(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt,
+                                                fpng_amd_decode_result *results);
+/* the blur's weights (no GPU): k[d], d = 0 .. radius; the rest 0.  FPNG_AMD_ERR_INVALID_ARG for a radius or sigma the calls refuse */
+int fpng_amd_blur_weights(uint32_t radius, double sigma, int32_t k[17]);
+/* steps 2 to 4 of the rule for ONE w x h plane of bytes (no GPU): the text that the kernel runs.  The record is judged as the calls judge it */
+int fpng_amd_view_post_apply(const fpng_amd_view_post *post, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

@@ -13,6 +13,7 @@ torch is only plumbing here (device memory + streams).  There is no CPU fallback
 or a GPU is missing, encode calls raise.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -579,6 +580,109 @@ def _post_records(who, counts, post):
     return arr
 
 
+_WARP_FILTERS = {"nearest": _lib.WARP_AFFINE, "bilinear": _lib.WARP_AFFINE | _lib.WARP_BILINEAR}
+
+
+def view_warp(matrix=None, filter="nearest", fill=0):
+    """The fpng_amd_view_warp record of one view of the views calls' warp= argument: matrix, the six coefficients of Pillow's
+    Image.transform(size, Image.AFFINE, matrix) -- output pixel centre -> source position, xs = a0 (x + .5) + a1 (y + .5) + a2,
+    ys = a3 (x + .5) + a4 (y + .5) + a5; affine_matrix() makes them -- sampled "nearest" or "bilinear" as Pillow samples, with `fill`
+    (one byte for all four channels, or a list of up to four, per FILE channel; a list's missing fourth is 255) outside the window.  matrix None: the view
+    is the post call's, untouched.  The caller draws the angles; the record is the contract."""
+    rec = _lib.ViewWarp()
+    if matrix is None:
+        return rec
+    try:
+        a = [float(v) for v in matrix]
+    except (TypeError, ValueError):
+        a = []
+    if len(a) != 6:
+        raise ValueError("view_warp: matrix is the six coefficients (a0 .. a5) of Pillow's AFFINE transform")
+    if filter not in _WARP_FILTERS:
+        raise ValueError(f"view_warp: filter is 'nearest' or 'bilinear', not {filter!r}")
+    fills = list(fill) if hasattr(fill, "__len__") else [fill] * 4
+    if not 1 <= len(fills) <= 4 or any(int(f) != f or not 0 <= int(f) <= 255 for f in fills):
+        raise ValueError(f"view_warp: fill is one byte 0 .. 255 or up to four of them, not {fill}")
+    if len(fills) < 3:
+        fills += [fills[-1]] * (3 - len(fills))
+    if len(fills) < 4:
+        fills.append(255)
+    rec.flags = _WARP_FILTERS[filter]
+    for k in range(6):
+        rec.a[k] = a[k]
+    for k in range(4):
+        rec.fill[k] = int(fills[k])
+    return rec
+
+
+def _warp_records(who, counts, warp):
+    """the warp= argument of the views calls -> fpng_amd_view_warp[sum(counts)]: nested as _post_records' argument"""
+    total = sum(counts)
+    arr = (_lib.ViewWarp * max(total, 1))()
+
+    def put(at, rec):
+        if not isinstance(rec, _lib.ViewWarp):
+            raise ValueError(f"{who}: a warp record is what view_warp() returns, not {type(rec).__name__}")
+        C.memmove(C.byref(arr, at * C.sizeof(_lib.ViewWarp)), C.byref(rec), C.sizeof(_lib.ViewWarp))
+
+    if isinstance(warp, _lib.ViewWarp):
+        for at in range(total):
+            put(at, warp)
+        return arr
+    if not hasattr(warp, "__len__") or len(warp) != len(counts):
+        raise ValueError(f"{who}: warp is one view_warp() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
+    at = 0
+    for i, (c, recs) in enumerate(zip(counts, warp)):
+        if isinstance(recs, _lib.ViewWarp):
+            recs = [recs] * c
+        if not hasattr(recs, "__len__") or len(recs) != c:
+            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} warp records")
+        for rec in recs:
+            put(at, rec)
+            at += 1
+    return arr
+
+
+def view_warp_apply(warp, plane, mirror=False, fill=None):
+    """fpng_amd_view_warp_apply, the host twin of the warp (no GPU): plane (h, w) uint8 -- one plane of a view's UN-MIRRORED window as
+    the colour call writes it -- -> (h, w) uint8, mirrored where asked and then warped as `warp` (a view_warp() record) says.  fill:
+    the byte outside (None: the record's fill[0])."""
+    if not isinstance(warp, _lib.ViewWarp):
+        raise ValueError("view_warp_apply: warp is what view_warp() returns")
+    px = np.ascontiguousarray(plane, dtype=np.uint8)
+    if px.ndim != 2 or px.size == 0:
+        raise ValueError(f"view_warp_apply: plane is (h, w) uint8, not {px.shape}")
+    out = np.empty_like(px)
+    check(_lib.load().fpng_amd_view_warp_apply(C.byref(warp), px.shape[1], px.shape[0], 1 if mirror else 0, px.ctypes.data, out.ctypes.data,
+                                               int(warp.fill[0] if fill is None else fill)))
+    return out
+
+
+def affine_matrix(w, h, angle=0.0, translate=(0, 0), scale=1.0, shear=(0.0, 0.0), center=None):
+    """The six coefficients for view_warp() of torchvision's affine(img, angle, translate, scale, shear) on a w x h PIL image: its
+    _get_inverse_affine_matrix restated in Python doubles, with the arguments that function takes -- angle and shear in degrees
+    (shear: one angle for x, or (x, y)), translate in pixels, center None (the image's, (w * 0.5, h * 0.5)) or (cx, cy) in pixels.
+    torchvision's rotate(img, a) hands that function -a: affine_matrix(w, h, angle=-a)."""
+    shear = tuple(shear) if hasattr(shear, "__len__") else (float(shear), 0.0)
+    if len(shear) != 2 or len(tuple(translate)) != 2:
+        raise ValueError("affine_matrix: translate is (tx, ty), shear one angle or (sx, sy)")
+    if not float(scale) > 0.0:
+        raise ValueError(f"affine_matrix: scale is > 0, not {scale}")
+    cx, cy = (float(w) * 0.5, float(h) * 0.5) if center is None else (float(center[0]), float(center[1]))
+    tx, ty = float(translate[0]), float(translate[1])
+    rot, sx, sy = math.radians(float(angle)), math.radians(float(shear[0])), math.radians(float(shear[1]))
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [v / float(scale) for v in (d, -b, 0.0, -c, a, 0.0)]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
 def blur_weights(radius, sigma):
     """fpng_amd_blur_weights (no GPU): the int32 weights k[0 .. radius] (2^22 fixed point) of the post calls' blur of this radius (1 ..
     16) and sigma; tap t = -radius .. radius has weight k[|t|]."""
@@ -931,6 +1035,7 @@ class DecodeBatchMultiView(_DecodeBatchViews):
 
     colors = None
     posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
+    warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -949,6 +1054,7 @@ class DecodeBatchMultiViewHwc(_DecodeBatchViews):
 
     colors = None
     posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
+    warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1835,7 +1941,7 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None, color=None, post=None):
+                                scale=None, bias=None, color=None, post=None, warp=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
@@ -1846,7 +1952,9 @@ class Encoder:
         array-like for all views, or a list per file of one per view; the descriptor then goes through
         fpng_amd_decode_batch(_device)_planar_views_color.  post: None, or the views' post-processing records (view_post() makes
         them) -- one for all views, a list with one per file, or a list per file of one per view; the descriptor then goes through
-        fpng_amd_decode_batch(_device)_planar_views_post, with color's matrices or without."""
+        fpng_amd_decode_batch(_device)_planar_views_post, with color's matrices or without.  warp: None, or the views' affine warp
+        records (view_warp() makes them), nested as post's; the descriptor then goes through
+        fpng_amd_decode_batch(_device)_planar_views_warp, with color's matrices and post's records or without."""
         who = "make_decode_batch_views"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -1911,15 +2019,17 @@ class Encoder:
             batch.colors = _color_records(who, counts, color)
         if post is not None:
             batch.posts = _post_records(who, counts, post)
+        if warp is not None:
+            batch.warps = _warp_records(who, counts, warp)
         return batch
 
     def _decode_views(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                      color, post=None, fn_post=None):
+                      color, post=None, fn_post=None, warp=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiView):
-            if color is not None or post is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices and post records (make_decode_batch_views(..., color=, post=))")
+            if color is not None or post is not None or warp is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post and warp records (make_decode_batch_views(..., color=, post=, warp=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -1932,14 +2042,17 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post)
+            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.posts is not None:
+        if batch.warps is not None:
+            check(getattr(self.lib, fn_post.replace("_views_post", "_views_warp"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
+                                                                                   batch.posts, batch.warps, fmt, batch.res))
+        elif batch.posts is not None:
             check(getattr(self.lib, fn_post)(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, batch.posts, fmt, batch.res))
         elif batch.colors is None:
             check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
@@ -1948,7 +2061,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -1964,27 +2077,32 @@ class Encoder:
         rint for uint8 or the fmaf of scale / bias; a fourth plane skips the matrix.  The identity gives exactly the call without.
         post: None, or a post-processing record per view (view_post() makes them: Gaussian blur, solarize, posterize; one for all
         views, one per file, or a list per file of one per view), applied to the colour step's bytes before the normalisation --
-        fpng_amd_decode_batch_device_planar_views_post; a record without flags leaves its view exactly the call's without."""
+        fpng_amd_decode_batch_device_planar_views_post; a record without flags leaves its view exactly the call's without.
+        warp: None, or an affine warp record per view (view_warp() makes them from Pillow's six AFFINE coefficients, affine_matrix()
+        those from torchvision's angle / translate / scale / shear; nested as post's), applied to the mirrored window's bytes
+        between the colour step and the blur -- fpng_amd_decode_batch_device_planar_views_warp: RandomRotation, RandomAffine and
+        RandAugment's geometric operations as Image.transform(size, AFFINE, ...) does them, nearest or bilinear, with a fill colour;
+        a record without flags leaves its view exactly the call's without."""
         return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, self.lib.fpng_amd_decode_batch_device_planar_views_color, True, pngs,
                                   crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_device_planar_views_post")
+                                  "fpng_amd_decode_batch_device_planar_views_post", warp)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, self.lib.fpng_amd_decode_batch_planar_views_color, False, pngs, crops,
                                   outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_planar_views_post")
+                                  "fpng_amd_decode_batch_planar_views_post", warp)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None, color=None, post=None):
+                                    scale=None, bias=None, color=None, post=None, warp=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
         value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
-        fpng_amd_decode_batch(_device)_hwc_views_color) and post (then: fpng_amd_decode_batch(_device)_hwc_views_post) -- is
-        make_decode_batch_views()'s."""
+        fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post) and warp (then:
+        fpng_amd_decode_batch(_device)_hwc_views_warp) -- is make_decode_batch_views()'s."""
         who = "make_decode_batch_views_hwc"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -2049,15 +2167,17 @@ class Encoder:
             batch.colors = _color_records(who, counts, color)
         if post is not None:
             batch.posts = _post_records(who, counts, post)
+        if warp is not None:
+            batch.warps = _warp_records(who, counts, warp)
         return batch
 
     def _decode_views_hwc(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                          color, post=None, fn_post=None):
+                          color, post=None, fn_post=None, warp=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiViewHwc):
-            if color is not None or post is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices and post records (make_decode_batch_views_hwc(..., color=, post=))")
+            if color is not None or post is not None or warp is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post and warp records (make_decode_batch_views_hwc(..., color=, post=, warp=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2070,14 +2190,17 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post)
+            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.posts is not None:
+        if batch.warps is not None:
+            check(getattr(self.lib, fn_post.replace("_views_post", "_views_warp"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
+                                                                                   batch.posts, batch.warps, fmt, batch.res))
+        elif batch.posts is not None:
             check(getattr(self.lib, fn_post)(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, batch.posts, fmt, batch.res))
         elif batch.colors is None:
             check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
@@ -2086,7 +2209,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -2101,14 +2224,14 @@ class Encoder:
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
         return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, self.lib.fpng_amd_decode_batch_device_hwc_views_color, True, pngs,
                                       crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_device_hwc_views_post")
+                                      "fpng_amd_decode_batch_device_hwc_views_post", warp)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, self.lib.fpng_amd_decode_batch_hwc_views_color, False, pngs, crops,
                                       outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_hwc_views_post")
+                                      "fpng_amd_decode_batch_hwc_views_post", warp)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

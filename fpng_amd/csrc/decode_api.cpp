@@ -376,6 +376,10 @@ struct Batch {
     std::vector<uint32_t> job_post;
     std::vector<uint64_t> dir_pre, post_pre;
     DecViewPost *d_post = nullptr;
+    // fpng_amd_decode_batch(_device)_planar_views_warp / _hwc_views_warp: the post call with a warp record per view (else NULL; only
+    // when at least one view has a warp flag and another matrix than the identity, and then with `post`: records without flags for a call without).  A view with a warp
+    // flag (and not the identity: warp_moves) is a post view whatever its post flags, and its record of post_recs carries the warp (DecViewPost::warp)
+    const fpng_amd_view_warp *warp = nullptr;
     std::vector<uint32_t> view_ofs, job_rec;
     std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
     std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
@@ -603,7 +607,7 @@ int parse_files(Batch &b)
                 rs.src += b.mid_total; // (an offset until place_files())
                 const uint64_t tiles = resize_tiles(rs.w, rs.h);
                 const uint32_t view = v0 + (uint32_t)(&rs - file_recs.data());
-                const bool is_post = b.post && b.post[view].flags;
+                const bool is_post = b.post && (b.post[view].flags || (b.warp && warp_moves(b.warp[view])));
                 if (is_post) { // (the destination goes to the post stage; the resize writes tight un-mirrored uint8 planes)
                     const fpng_amd_view_post &vp = b.post[view];
                     DecViewPost pr = {};
@@ -611,6 +615,7 @@ int parse_files(Batch &b)
                     if (b.hwc) pr.pixel_elems = file_px[view - v0].first, pr.hwc_flags = file_px[view - v0].second;
                     pr.flags = vp.flags, pr.radius = vp.blur_radius, pr.threshold = vp.solarize_threshold, pr.bits = vp.posterize_bits;
                     if (vp.flags & kPostBlur) post_blur_weights(vp.blur_radius, vp.blur_sigma, pr.k);
+                    if (b.warp) pr.warp = warp_record(b.warp[view]);
                     b.post_recs.push_back(pr);
                     rs.dst = nullptr, rs.pitch = (int32_t)rs.w, rs.plane_pitch = (int64_t)((uint64_t)rs.w * rs.h), rs.flags &= ~kResizeMirror;
                 }
@@ -897,7 +902,7 @@ int finish_group(Batch &b, uint32_t gi)
         }
         const bool ok = launch_dec_resize_color(b.s, b.d_resize_color + d0, b.d_resize_pre + d0, b.dir_pre.data() + d0, d1 - d0, lds[0], b.flt, any_filter[0], b.hwc != nullptr) &&
                         launch_dec_resize_color(b.s, b.d_resize_color + nd + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, lds[1], nullptr, any_filter[1], false) &&
-                        launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr);
+                        launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr, b.warp != nullptr);
         if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
     } else if (b.sizes) {
         const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1]; // (the records of the group's jobs)
@@ -1074,7 +1079,8 @@ int collect_results(Batch &b)
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
                  const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                 const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr)
+                 const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
+                 const fpng_amd_view_warp *warp = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -1085,7 +1091,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr;
+        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr, b.warp = b.post ? warp : nullptr;
         b.view_ofs.resize(n);
         for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
     }
@@ -1381,7 +1387,8 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
 // views then hold a record per view, and the destinations, which `files` leave empty, are dests')
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
                         const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                        const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr)
+                        const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
+                        const fpng_amd_view_warp *warp = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && !view_count && i < n; i++)
@@ -1418,7 +1425,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post, warp);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
@@ -1428,7 +1435,7 @@ static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_des
               "fpng_amd_view_dest_hwc layout");
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                        const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr,
-                       const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr)
+                       const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr, const fpng_amd_view_warp *warp = nullptr)
 {
     if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
@@ -1446,7 +1453,7 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
             if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
             if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
         }
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post);
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post, warp);
 }
 // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: the matrices are judged first -- a record per view, the sum of
 // the counts (those the views call refuses: its own message, below) -- then everything the views call judges
@@ -1499,22 +1506,32 @@ static_assert(sizeof(fpng_amd_view_post) == 32 && offsetof(fpng_amd_view_post, b
               "fpng_amd_view_post layout");
 int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_view_post *posts,
-                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data)
+                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_warp *warps = nullptr,
+                            bool with_warps = false)
 {
-    if (!posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts");
+    // with_warps: the _views_warp calls' -- the warp records are judged first, and posts may be NULL (no post flags)
+    if (with_warps && !warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps");
+    if (!with_warps && !posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts");
     if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
     bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
-    bool any = false;
-    for (uint64_t v = 0; counts_ok && v < total; v++) {
+    bool any = false, any_warp = false;
+    for (uint64_t v = 0; warps && counts_ok && v < total; v++) {
+        if (const char *why = check_warp_record(warps[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        any_warp |= warp_moves(warps[v]);
+    }
+    for (uint64_t v = 0; posts && counts_ok && v < total; v++) {
         if (const char *why = check_post_record(posts[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
         any |= posts[v].flags != 0;
     }
     if (colors)
         if (int rc = check_color_records(colors, view_count, n)) return rc;
-    // (no view with a flag: the colour call, or the plain one, enqueues what it always does)
-    if (!any) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
+    // (no view with a flag: the colour call, or the plain one, enqueues what it always does; no warp flag: the post call does)
+    if (!any && !any_warp) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
+    std::vector<fpng_amd_view_post> no_posts;
+    if (!posts) no_posts.assign((size_t)total, fpng_amd_view_post{}), posts = no_posts.data();
+    if (!any_warp) warps = nullptr;
     std::vector<fpng_amd_view_color> identity;
     if (!colors) {
         fpng_amd_view_color one = {};
@@ -1522,7 +1539,7 @@ int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *file
         identity.assign((size_t)total, one);
         colors = identity.data();
     }
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts);
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts, warps);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1684,6 +1701,46 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_post(fpng_amd_encoder *e, 
                                                            const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
     return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                       const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                       const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
+                                                       fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false, warps, true);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                              const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                              const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
+                                                              fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true, warps, true);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                    const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                    const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
+                                                    fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false, warps, true);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                           const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                           const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
+                                                           fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true);
+}
+
+// step 1a of the warp rule for one w x h plane of bytes, on the host: the texts of view_warp.h, which dec_view_post_kernel runs
+extern "C" int fpng_amd_view_warp_apply(const fpng_amd_view_warp *warp, uint32_t w, uint32_t h, uint32_t mirror, const uint8_t *in, uint8_t *out, uint8_t fill_value)
+{
+    const char *why = nullptr;
+    const int rc = warp_apply_checked(warp, w, h, mirror, in, out, fill_value, &why);
+    return rc ? fail(rc, why) : FPNG_AMD_OK;
 }
 
 // the blur's weights on the host: post_blur_weights (view_post.h), what the post calls hand to dec_view_post_kernel

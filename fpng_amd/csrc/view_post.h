@@ -17,6 +17,7 @@
 #pragma once
 #include "decode.h"
 #include "resize.h"
+#include "view_warp.h"
 
 #include <cmath>
 
@@ -59,11 +60,13 @@ struct DecViewPost {
     uint32_t pixel_elems, hwc_flags; // DecResizeHwc's
     uint32_t flags, radius, threshold, bits;
     int32_t k[kPostMaxRadius + 1];
+    DecWarp warp; // the _views_warp calls' (view_warp.h); flags 0: none.  With a warp the gather mirrors and the store does not
 };
-static_assert(sizeof(DecViewPost) == 136 && offsetof(DecViewPost, pitch) == 24 && offsetof(DecViewPost, k) == 68, "DecViewPost layout");
+static_assert(sizeof(DecViewPost) == 240 && offsetof(DecViewPost, pitch) == 24 && offsetof(DecViewPost, k) == 68 && offsetof(DecViewPost, warp) == 136, "DecViewPost layout");
 
 // An exact grid as launch_dec_resize_color's, a workgroup per (record, tile of kResizeTileW x kResizeTileH): pre / h_pre count TILES.
-// hwc: channels-last destinations.  false: a record without or with too many tiles; nothing more is launched.
-bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc);
+// hwc: channels-last destinations.  warp: some record of the call has a warp (the instantiations that gather; without, the post
+// call's own).  false: a record without or with too many tiles; nothing more is launched.
+bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, bool warp = false);
 
 } // namespace fpng_amd

@@ -11,6 +11,12 @@
 //      byte per plane, as in dec_resize_color_kernel.
 // R = 0 (point operations only) reads the scratch straight into the registers: no LDS, no barrier.  A fourth plane (alpha, or the
 // 255 of a 3-channel file) is copied.
+// A view with a WARP (the _views_warp calls; view_warp.h: the rule) reads W in the place of B: sample (q, i) of W is gathered from the
+// window -- one byte, or four and a blend in doubles -- wherever the text above loads B[q][i], the halo's reflected samples
+// included, and the mirror moves from the store into the gather's read index.  The kWarp instantiations run those calls: a
+// sample's position is found once (warp_locate) and serves its planes, so stage 1 fills the halos of all three colour planes in one
+// sweep (S holds three); the fourth plane is gathered too.  Whether a record has a warp is uniform across its workgroup.  The
+// window is at most a few hundred KB and has just been written: the gather reads it out of L2.
 //   4. the store: a thread has all channels of its pixels; every element is stored on its own -- planar destinations as
 //      dec_resize_color_kernel's, lanes along a row of a plane; channels-last ones by element, position c or planes - 1 - c of the
 //      pixel, positions >= planes never written.
@@ -43,9 +49,10 @@ template <int kDtype> __device__ __forceinline__ void post_store(uint8_t *p, uin
     }
 }
 
-template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void dec_view_post_kernel(const DecViewPost *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
+template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResizeBlock) void dec_view_post_kernel(const DecViewPost *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t S[kPostHaloH * kPostHaloW]; // the tile and its halo, rows of sw bytes
+    constexpr uint32_t kHalo = kPostHaloH * kPostHaloW;
+    __shared__ __attribute__((aligned(16))) uint8_t S[(kWarp ? 3 : 1) * kHalo]; // the tile and its halo, rows of sw bytes (kWarp: per colour plane)
     __shared__ __attribute__((aligned(16))) uint8_t Hb[kPostHaloH * kResizeTileW]; // the horizontal pass: rows of kResizeTileW bytes
     __shared__ int32_t K[kPostMaxRadius + 1];                                   // k[d]: taps -d and d share it
     const uint64_t g = pre[0] + blockIdx.x;
@@ -68,23 +75,37 @@ template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void
     constexpr uint32_t kWaves = kResizeBlock / kResizeTileW, kRowsPerWave = kResizeTileH / kWaves;
     const uint64_t plane_bytes = (uint64_t)w * h;
     const uint32_t threshold = r.threshold, bits = r.bits;
+    const uint32_t wflags = kWarp ? r.warp.flags : 0u, mirror = r.mirror;
     uint32_t res[kRowsPerWave] = {};
     if (R) {
         if (tid <= R) K[tid] = r.k[tid];
         const uint32_t sw = nw + 2 * R, sh = nq + 2 * R; // (<= kPostHaloW, kPostHaloH)
         for (uint32_t plane = 0; plane < C && plane < 3; plane++) {
             const uint8_t *const src = r.src + plane * plane_bytes;
+            uint8_t *const Sp = S + (kWarp ? plane * kHalo : 0u);
             if (plane) __syncthreads(); // (the plane before has been read out of S and Hb)
             // ---- 1. the tile and its halo ----
-            for (uint32_t j = wave; j < sh; j += kWaves) {
-                const uint8_t *const row = src + (uint64_t)post_refl((int32_t)(oq0 + j) - (int32_t)R, h) * w;
-                for (uint32_t i = o; i < sw; i += kResizeTileW) S[j * kPostHaloW + i] = row[post_refl((int32_t)(ox0 + i) - (int32_t)R, w)];
-            }
+            if (kWarp && wflags) {
+                if (!plane) { // (all colour planes of a sample from one position)
+                    const uint32_t np = std::min(C, 3u);
+                    for (uint32_t j = wave; j < sh; j += kWaves) {
+                        const uint32_t y = post_refl((int32_t)(oq0 + j) - (int32_t)R, h);
+                        for (uint32_t i = o; i < sw; i += kResizeTileW) {
+                            const WarpAt at = warp_locate(r.warp, post_refl((int32_t)(ox0 + i) - (int32_t)R, w), y, w, h, mirror);
+                            for (uint32_t p = 0; p < np; p++) S[p * kHalo + j * kPostHaloW + i] = (uint8_t)warp_sample(at, wflags, r.src + p * plane_bytes, w, r.warp.fill[p]);
+                        }
+                    }
+                }
+            } else
+                for (uint32_t j = wave; j < sh; j += kWaves) {
+                    const uint8_t *const row = src + (uint64_t)post_refl((int32_t)(oq0 + j) - (int32_t)R, h) * w;
+                    for (uint32_t i = o; i < sw; i += kResizeTileW) Sp[j * kPostHaloW + i] = row[post_refl((int32_t)(ox0 + i) - (int32_t)R, w)];
+                }
             __syncthreads();
             // ---- 2. the horizontal pass ----
             if (o < nw)
                 for (uint32_t j = wave; j < sh; j += kWaves) {
-                    const uint8_t *const s = S + j * kPostHaloW + o + R; // (the sample itself; taps -d and d: one product)
+                    const uint8_t *const s = Sp + j * kPostHaloW + o + R; // (the sample itself; taps -d and d: one product)
                     int32_t sum = (1 << (kResizeBits - 1)) + (int32_t)s[0] * K[0];
 #pragma unroll 4
                     for (uint32_t d = 1; d <= R; d++) sum += ((int32_t)s[-(int32_t)d] + (int32_t)s[d]) * K[d];
@@ -105,6 +126,16 @@ template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void
                 }
             }
         }
+    } else if (o < nw && kWarp && wflags) {
+#pragma unroll
+        for (uint32_t k = 0; k < kRowsPerWave; k++) {
+            const uint32_t q = wave + k * kWaves;
+            if (q >= nq) break;
+            const WarpAt at = warp_locate(r.warp, ox0 + o, oq0 + q, w, h, mirror);
+            for (uint32_t plane = 0; plane < C && plane < 3; plane++)
+                res[k] |= post_point(warp_sample(at, wflags, r.src + plane * plane_bytes, w, r.warp.fill[plane]), flags, threshold, bits) << (8 * plane);
+            if (C == 4) res[k] |= warp_sample(at, wflags, r.src + 3 * plane_bytes, w, r.warp.fill[3]) << 24;
+        }
     } else if (o < nw) {
         for (uint32_t plane = 0; plane < C && plane < 3; plane++) {
 #pragma unroll
@@ -116,7 +147,16 @@ template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void
         }
     }
     if (o >= nw) return; // (no barrier behind this line)
-    if (C == 4) {
+    if (C == 4 && kWarp && wflags) {
+        if (R) { // (without blur: gathered above)
+#pragma unroll
+            for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                const uint32_t q = wave + k * kWaves;
+                if (q >= nq) break;
+                res[k] |= warp_sample(warp_locate(r.warp, ox0 + o, oq0 + q, w, h, mirror), wflags, r.src + 3 * plane_bytes, w, r.warp.fill[3]) << 24;
+            }
+        }
+    } else if (C == 4) {
 #pragma unroll
         for (uint32_t k = 0; k < kRowsPerWave; k++) {
             const uint32_t q = wave + k * kWaves;
@@ -126,7 +166,7 @@ template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void
     }
     // ---- 4. the store ----
     constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
-    const uint32_t col = r.mirror ? w - 1 - (ox0 + o) : ox0 + o;
+    const uint32_t col = mirror && !wflags ? w - 1 - (ox0 + o) : ox0 + o; // (a warp has mirrored its reads)
     // (file channel c: plane c, or element c -- reversed: planes - 1 - c -- of its pixel)
     int64_t at[4], first;
     if constexpr (!kHwc) {
@@ -153,19 +193,21 @@ template <int kDtype, bool kHwc> __global__ __launch_bounds__(kResizeBlock) void
 
 } // namespace
 
-bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc)
+bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, bool warp)
 {
     using Kernel = void (*)(const DecViewPost *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][kDecFloatTypes + 1] = {
-        {dec_view_post_kernel<-1, false>, dec_view_post_kernel<0, false>, dec_view_post_kernel<1, false>, dec_view_post_kernel<2, false>},
-        {dec_view_post_kernel<-1, true>, dec_view_post_kernel<0, true>, dec_view_post_kernel<1, true>, dec_view_post_kernel<2, true>}};
+    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
+        {{dec_view_post_kernel<-1, false, false>, dec_view_post_kernel<0, false, false>, dec_view_post_kernel<1, false, false>, dec_view_post_kernel<2, false, false>},
+         {dec_view_post_kernel<-1, true, false>, dec_view_post_kernel<0, true, false>, dec_view_post_kernel<1, true, false>, dec_view_post_kernel<2, true, false>}},
+        {{dec_view_post_kernel<-1, false, true>, dec_view_post_kernel<0, false, true>, dec_view_post_kernel<1, false, true>, dec_view_post_kernel<2, false, true>},
+         {dec_view_post_kernel<-1, true, true>, dec_view_post_kernel<0, true, true>, dec_view_post_kernel<1, true, true>, dec_view_post_kernel<2, true, true>}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     for (uint32_t r0 = 0; r0 < n;) {
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[hwc][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+        hipLaunchKernelGGL(kernels[warp][hwc][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
         r0 = r1;
     }
     return true;

@@ -901,6 +901,83 @@ int fpng_amd_decode_batch_device_hwc_views_post(fpng_amd_encoder *enc, const fpn
 int fpng_amd_blur_weights(uint32_t radius, double sigma, int32_t k[17]);
 /* steps 2 to 4 of the rule for ONE w x h plane of bytes (no GPU): the text that the kernel runs.  The record is judged as the calls judge it */
 int fpng_amd_view_post_apply(const fpng_amd_view_post *post, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out);
+/* ---- either post call with an AFFINE WARP record per view behind the post record: RandomRotation, RandomAffine and the ShearX/Y,
+ *      TranslateX/Y and Rotate operations of RandAugment / TrivialAugment / AutoAugment -- on a PIL image torchvision's
+ *      Image.transform(size, AFFINE, a, resample, fillcolor) -- drawn per view by the caller.  The argument lists are those of the
+ *      _views_post calls with `warps`, a record per view, behind `posts`; colors and posts may be NULL: the identity, and no post
+ *      flags.
+ *      THE RULE (every element is exact).  A view whose warp flags is 0 is written bit for bit as the _views_post call writes it.
+ *      A view with FPNG_AMD_WARP_AFFINE is a post view even when its post flags are 0, and the warp sits between step 1 and step 2
+ *      of the post rule, on the MIRRORED window (torchvision's order: flip, then affine):
+ *        1a. M[q][i] = B[q][mirror ? w - 1 - i : i],  W = warp(M).  Steps 2 to 4 then run on W in the place of B, and a warp view's
+ *            element (q, i) comes from Z[q][i]: there is no second mirror.  ALL planes are warped, the fourth one (alpha, or the 255
+ *            of a 3-channel file) with fill[3]: geometry is not a colour operation.  Steps 2 to 4 still skip the fourth plane.
+ *            The output pixel centre (x + .5, y + .5) reads the source position
+ *                xs = a0 (x + .5) + a1 (y + .5) + a2,   ys = a3 (x + .5) + a4 (y + .5) + a5        (Pillow's AFFINE data)
+ *        nearest (without FPNG_AMD_WARP_BILINEAR) is Pillow's affine_fixed, in 16.16 integers made on the host:
+ *                FIX(v) = (int)floor(v * 65536.0 + 0.5)
+ *                A0, A1, A3, A4 = FIX(a0), FIX(a1), FIX(a3), FIX(a4)
+ *                A2 = FIX(a2 + a0 * 0.5 + a1 * 0.5),  A5 = FIX(a5 + a3 * 0.5 + a4 * 0.5)
+ *                sx = (A2 + x * A0 + y * A1) >> 16,   sy = (A5 + x * A3 + y * A4) >> 16           (arithmetic shifts)
+ *                W[y][x] = 0 <= sx < w && 0 <= sy < h ? M[sy][sx] : fill
+ *            (the integers are held 64 bits wide; where Pillow's int holds them they are Pillow's.)
+ *        bilinear (FPNG_AMD_WARP_BILINEAR) is Pillow's generic transform with bilinear_filter, in IEEE double WITHOUT contraction
+ *            (no fused multiply-add), in this order:
+ *                xs = (a0 * (x + 0.5) + a1 * (y + 0.5)) + a2,  ys likewise
+ *                fill if xs < 0 || xs >= w || ys < 0 || ys >= h; otherwise
+ *                xs -= 0.5; ys -= 0.5; xi = floor(xs); yi = floor(ys); dx = xs - xi; dy = ys - yi
+ *                x0 = clamp(xi, 0, w - 1), x1 = clamp(xi + 1, 0, w - 1), p = row clamp(yi, 0, h - 1) of M
+ *                v1 = p[x0] + (p[x1] - p[x0]) * dx
+ *                v2 = the same on row yi + 1 if 0 <= yi + 1 < h, else v1
+ *                v = v1 + (v2 - v1) * dy,  W[y][x] = (uint8_t)v                                    (TRUNCATED, not rounded)
+ *      SCOPE.  The nearest rule is Pillow's for every matrix with a1 != 0 || a3 != 0 and for pure translations by integers and
+ *      half-integers: everything torchvision's RandAugment and RandomAffine produce from integer translations.  For other pure
+ *      scale / translate matrices (a1 == 0 && a3 == 0) Pillow's nearest path uses running double sums and can differ in rare ties;
+ *      this library keeps the fixed-point rule.  The bilinear rule is Pillow's for every matrix.
+ *      GUARANTEES: a record with flags == 0 leaves its view bit for bit the post call's; the identity a = {1, 0, 0, 0, 1, 0} under
+ *      either filter gives bit for bit the elements of no warp, in every dtype: W = M there, and the library treats the record as
+ *      one without flags (so a float view without post flags keeps the colour rule's unrounded u_c); for a file with status 0 a view depends only on (file, crop, view,
+ *      colour, post, warp, fmt); only the spans the views call writes are written.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null warps; unknown flag bits;
+ *      BILINEAR without AFFINE; a non-zero reserved word; an a that is not finite; any of the four output corners (0, 0), (w, 0),
+ *      (0, h), (w, h) failing Pillow's check_fixed, fabs(x a0 + y a1 + a2) < 32768 && fabs(x a3 + y a4 + a5) < 32768 (for both
+ *      filters); a non-zero a or fill with flags == 0; and everything the post call refuses (the blur's R < min(w, h) unchanged).
+ *      A warp view runs as a post view does: its un-mirrored uint8 window goes into the decode scratch and the post stage gathers
+ *      through the warp where it would load -- with blur, the halo's reflected samples too.  A call in which no view has a warp
+ *      flag with another matrix than the identity enqueues exactly what the post, colour or plain call enqueues.
+ *      Not offered: perspective, bicubic sampling, an output size other than the window's (expand=True), a warp in
+ *      fpng_amd_decode_host or the fpng:: drop-in, drawing the random parameters.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_warp with dlsym. ---- */
+#define FPNG_AMD_WARP_AFFINE 1u
+#define FPNG_AMD_WARP_BILINEAR 2u /* only with AFFINE; without it: nearest */
+typedef struct fpng_amd_view_warp {
+    uint32_t flags;     /* FPNG_AMD_WARP_*; 0 = this view is the post call's, untouched */
+    uint32_t reserved0; /* 0 */
+    double a[6];        /* output pixel centre -> source position, Pillow's AFFINE data */
+    uint8_t fill[4];    /* per FILE channel, in the bytes of step 1 */
+    uint32_t reserved1; /* 0 */
+} fpng_amd_view_warp;   /* 64 bytes */
+int fpng_amd_decode_batch_planar_views_warp(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                            const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                            const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                            const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same */,
+                                            const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_warp(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                   const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                   const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                   const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_warp(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                         const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                         const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                         const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same */,
+                                         const fpng_amd_float_format *fmt /* NULL: uint8 */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_warp(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+/* step 1a of the rule for ONE w x h plane of bytes (no GPU): in is B, the un-mirrored window; out is W; fill_value is the plane's
+ * fill (the record's own fill is not read).  The text that the kernel runs.  The record is judged as the calls judge it */
+int fpng_amd_view_warp_apply(const fpng_amd_view_warp *warp, uint32_t w, uint32_t h, uint32_t mirror, const uint8_t *in, uint8_t *out, uint8_t fill_value);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

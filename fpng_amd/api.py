@@ -683,6 +683,87 @@ def affine_matrix(w, h, angle=0.0, translate=(0, 0), scale=1.0, shear=(0.0, 0.0)
     return m
 
 
+def view_tone(autocontrast=False, equalize=False, contrast=None):
+    """The fpng_amd_view_tone record of one view of the views calls' tone= argument: at most ONE of autocontrast
+    (ImageOps.autocontrast(img), cutoff 0), equalize (ImageOps.equalize(img)) and contrast=factor
+    (ImageEnhance.Contrast(img).enhance(factor): factor finite and >= 0, rounded to fp32 once) -- each a statistic of the whole view,
+    a table per channel and a point operation, behind the colour matrix and the warp and in front of the blur, solarize and
+    posterize.  None of them: the view is the warp call's, untouched.  The caller draws the operation; the record is the contract."""
+    if bool(autocontrast) + bool(equalize) + (contrast is not None) > 1:
+        raise ValueError("view_tone: at most one of autocontrast, equalize and contrast (two tone operations on one view are not offered)")
+    rec = _lib.ViewTone()
+    if autocontrast:
+        rec.op = _lib.TONE_AUTOCONTRAST
+    elif equalize:
+        rec.op = _lib.TONE_EQUALIZE
+    elif contrast is not None:
+        try:
+            with np.errstate(over="ignore"):
+                factor = float(np.float32(contrast))
+        except (TypeError, ValueError):
+            raise ValueError(f"view_tone: contrast is a number, not {contrast!r}") from None
+        if not math.isfinite(factor) or factor < 0.0:
+            raise ValueError(f"view_tone: contrast is finite and >= 0, not {contrast}")
+        rec.op, rec.factor = _lib.TONE_CONTRAST, factor
+    return rec
+
+
+def _tone_records(who, counts, tone):
+    """the tone= argument of the views calls -> fpng_amd_view_tone[sum(counts)]: nested as _post_records' argument"""
+    total = sum(counts)
+    arr = (_lib.ViewTone * max(total, 1))()
+
+    def put(at, rec):
+        if not isinstance(rec, _lib.ViewTone):
+            raise ValueError(f"{who}: a tone record is what view_tone() returns, not {type(rec).__name__}")
+        C.memmove(C.byref(arr, at * C.sizeof(_lib.ViewTone)), C.byref(rec), C.sizeof(_lib.ViewTone))
+
+    if isinstance(tone, _lib.ViewTone):
+        for at in range(total):
+            put(at, tone)
+        return arr
+    if not hasattr(tone, "__len__") or len(tone) != len(counts):
+        raise ValueError(f"{who}: tone is one view_tone() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
+    at = 0
+    for i, (c, recs) in enumerate(zip(counts, tone)):
+        if isinstance(recs, _lib.ViewTone):
+            recs = [recs] * c
+        if not hasattr(recs, "__len__") or len(recs) != c:
+            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} tone records")
+        for rec in recs:
+            put(at, rec)
+            at += 1
+    return arr
+
+
+def view_tone_lut(tone, hist):
+    """fpng_amd_view_tone_lut, the host twin of the tone tables (no GPU): hist (4, 256) counts -- of R, G, B and of Pillow's L -- ->
+    the (3, 256) uint8 tables of `tone` (a view_tone() record)."""
+    if not isinstance(tone, _lib.ViewTone):
+        raise ValueError("view_tone_lut: tone is what view_tone() returns")
+    h = np.asarray(hist)
+    if h.shape != (4, 256) or h.dtype.kind not in "iu" or (h.size and (h.min() < 0 or h.max() > 0xFFFFFFFF)):
+        raise ValueError("view_tone_lut: hist is (4, 256) counts that fit uint32")
+    h = np.ascontiguousarray(h, dtype=np.uint32)
+    lut = np.empty((3, 256), dtype=np.uint8)
+    check(_lib.load().fpng_amd_view_tone_lut(C.byref(tone), h.ctypes.data, lut.ctypes.data))
+    return lut
+
+
+def view_tone_apply(tone, planes):
+    """fpng_amd_view_tone_apply, the host twin of the tone stage (no GPU): planes (3, h, w) uint8 -- a view's window as the post stage
+    loads it -- -> (3, h, w) uint8 through the histograms and tables of `tone` (a view_tone() record)."""
+    if not isinstance(tone, _lib.ViewTone):
+        raise ValueError("view_tone_apply: tone is what view_tone() returns")
+    px = np.asarray(planes)
+    if px.dtype != np.uint8 or px.ndim != 3 or px.shape[0] != 3 or px.size == 0:
+        raise ValueError(f"view_tone_apply: planes is (3, h, w) uint8, not {px.shape} {px.dtype}")
+    px = np.ascontiguousarray(px)
+    out = np.empty_like(px)
+    check(_lib.load().fpng_amd_view_tone_apply(C.byref(tone), px.shape[2], px.shape[1], px.ctypes.data, out.ctypes.data))
+    return out
+
+
 def blur_weights(radius, sigma):
     """fpng_amd_blur_weights (no GPU): the int32 weights k[0 .. radius] (2^22 fixed point) of the post calls' blur of this radius (1 ..
     16) and sigma; tap t = -radius .. radius has weight k[|t|]."""
@@ -1036,6 +1117,7 @@ class DecodeBatchMultiView(_DecodeBatchViews):
     colors = None
     posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
     warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
+    tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1055,6 +1137,7 @@ class DecodeBatchMultiViewHwc(_DecodeBatchViews):
     colors = None
     posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
     warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
+    tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1941,7 +2024,7 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None, color=None, post=None, warp=None):
+                                scale=None, bias=None, color=None, post=None, warp=None, tone=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
@@ -1954,7 +2037,9 @@ class Encoder:
         them) -- one for all views, a list with one per file, or a list per file of one per view; the descriptor then goes through
         fpng_amd_decode_batch(_device)_planar_views_post, with color's matrices or without.  warp: None, or the views' affine warp
         records (view_warp() makes them), nested as post's; the descriptor then goes through
-        fpng_amd_decode_batch(_device)_planar_views_warp, with color's matrices and post's records or without."""
+        fpng_amd_decode_batch(_device)_planar_views_warp, with color's matrices and post's records or without.  tone: None, or the
+        views' tone records (view_tone() makes them), nested as post's; the descriptor then goes through
+        fpng_amd_decode_batch(_device)_planar_views_tone, with the others' records or without."""
         who = "make_decode_batch_views"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -2021,15 +2106,17 @@ class Encoder:
             batch.posts = _post_records(who, counts, post)
         if warp is not None:
             batch.warps = _warp_records(who, counts, warp)
+        if tone is not None:
+            batch.tones = _tone_records(who, counts, tone)
         return batch
 
     def _decode_views(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                      color, post=None, fn_post=None, warp=None):
+                      color, post=None, fn_post=None, warp=None, tone=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiView):
-            if color is not None or post is not None or warp is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post and warp records (make_decode_batch_views(..., color=, post=, warp=))")
+            if color is not None or post is not None or warp is not None or tone is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp and tone records (make_decode_batch_views(..., color=, post=, warp=, tone=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2042,14 +2129,17 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp)
+            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.warps is not None:
+        if batch.tones is not None:
+            check(getattr(self.lib, fn_post.replace("_views_post", "_views_tone"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
+                                                                                   batch.posts, batch.warps, batch.tones, fmt, batch.res))
+        elif batch.warps is not None:
             check(getattr(self.lib, fn_post.replace("_views_post", "_views_warp"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
                                                                                    batch.posts, batch.warps, fmt, batch.res))
         elif batch.posts is not None:
@@ -2061,7 +2151,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -2082,27 +2172,32 @@ class Encoder:
         those from torchvision's angle / translate / scale / shear; nested as post's), applied to the mirrored window's bytes
         between the colour step and the blur -- fpng_amd_decode_batch_device_planar_views_warp: RandomRotation, RandomAffine and
         RandAugment's geometric operations as Image.transform(size, AFFINE, ...) does them, nearest or bilinear, with a fill colour;
-        a record without flags leaves its view exactly the call's without."""
+        a record without flags leaves its view exactly the call's without.
+        tone: None, or a tone record per view (view_tone() makes them: autocontrast, equalize or contrast about the view's own mean,
+        as Pillow's ImageOps / ImageEnhance do them; nested as post's), applied to the bytes behind the colour step and the warp and
+        in front of the blur -- fpng_amd_decode_batch_device_planar_views_tone; a record without an op leaves its view exactly the
+        call's without."""
         return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, self.lib.fpng_amd_decode_batch_device_planar_views_color, True, pngs,
                                   crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_device_planar_views_post", warp)
+                                  "fpng_amd_decode_batch_device_planar_views_post", warp, tone)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, self.lib.fpng_amd_decode_batch_planar_views_color, False, pngs, crops,
                                   outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_planar_views_post", warp)
+                                  "fpng_amd_decode_batch_planar_views_post", warp, tone)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None, color=None, post=None, warp=None):
+                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
         value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
-        fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post) and warp (then:
-        fpng_amd_decode_batch(_device)_hwc_views_warp) -- is make_decode_batch_views()'s."""
+        fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post), warp (then:
+        fpng_amd_decode_batch(_device)_hwc_views_warp) and tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone) -- is
+        make_decode_batch_views()'s."""
         who = "make_decode_batch_views_hwc"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -2169,15 +2264,17 @@ class Encoder:
             batch.posts = _post_records(who, counts, post)
         if warp is not None:
             batch.warps = _warp_records(who, counts, warp)
+        if tone is not None:
+            batch.tones = _tone_records(who, counts, tone)
         return batch
 
     def _decode_views_hwc(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                          color, post=None, fn_post=None, warp=None):
+                          color, post=None, fn_post=None, warp=None, tone=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiViewHwc):
-            if color is not None or post is not None or warp is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post and warp records (make_decode_batch_views_hwc(..., color=, post=, warp=))")
+            if color is not None or post is not None or warp is not None or tone is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp and tone records (make_decode_batch_views_hwc(..., color=, post=, warp=, tone=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2190,14 +2287,17 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp)
+            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.warps is not None:
+        if batch.tones is not None:
+            check(getattr(self.lib, fn_post.replace("_views_post", "_views_tone"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
+                                                                                   batch.posts, batch.warps, batch.tones, fmt, batch.res))
+        elif batch.warps is not None:
             check(getattr(self.lib, fn_post.replace("_views_post", "_views_warp"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
                                                                                    batch.posts, batch.warps, fmt, batch.res))
         elif batch.posts is not None:
@@ -2209,7 +2309,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -2224,14 +2324,14 @@ class Encoder:
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
         return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, self.lib.fpng_amd_decode_batch_device_hwc_views_color, True, pngs,
                                       crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_device_hwc_views_post", warp)
+                                      "fpng_amd_decode_batch_device_hwc_views_post", warp, tone)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, self.lib.fpng_amd_decode_batch_hwc_views_color, False, pngs, crops,
                                       outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_hwc_views_post", warp)
+                                      "fpng_amd_decode_batch_hwc_views_post", warp, tone)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

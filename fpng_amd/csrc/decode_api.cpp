@@ -380,6 +380,15 @@ struct Batch {
     // when at least one view has a warp flag and another matrix than the identity, and then with `post`: records without flags for a call without).  A view with a warp
     // flag (and not the identity: warp_moves) is a post view whatever its post flags, and its record of post_recs carries the warp (DecViewPost::warp)
     const fpng_amd_view_warp *warp = nullptr;
+    // fpng_amd_decode_batch(_device)_planar_views_tone / _hwc_views_tone: the warp call with a tone record per view (else NULL; only
+    // when at least one view has an op, and then with `post`).  A view with an op is a post view whatever its other flags; tone view t
+    // (tone_refs[t]: its post record and the chunks of dec_view_tone_hist_kernel in front of it) has kToneBytes of the scratch at
+    // d_tone + t * kToneBytes; job k's tone views are job_tone[k] .. job_tone[k + 1] - 1
+    const fpng_amd_view_tone *tone = nullptr;
+    std::vector<DecToneRef> tone_refs;
+    std::vector<uint32_t> job_tone;
+    DecToneRef *d_tone_refs = nullptr;
+    uint8_t *d_tone = nullptr;
     std::vector<uint32_t> view_ofs, job_rec;
     std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
     std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
@@ -603,11 +612,12 @@ int parse_files(Batch &b)
         if (b.sizes) {
             // the crop kernels write tight uint8 planes of the box's size into the scratch; the resize reads them and writes the caller's
             b.job_rec.push_back((uint32_t)b.resize.size());
+            b.job_tone.push_back((uint32_t)b.tone_refs.size());
             for (DecResize &rs : file_recs) {
                 rs.src += b.mid_total; // (an offset until place_files())
                 const uint64_t tiles = resize_tiles(rs.w, rs.h);
                 const uint32_t view = v0 + (uint32_t)(&rs - file_recs.data());
-                const bool is_post = b.post && (b.post[view].flags || (b.warp && warp_moves(b.warp[view])));
+                const bool is_post = b.post && (b.post[view].flags || (b.warp && warp_moves(b.warp[view])) || (b.tone && b.tone[view].op));
                 if (is_post) { // (the destination goes to the post stage; the resize writes tight un-mirrored uint8 planes)
                     const fpng_amd_view_post &vp = b.post[view];
                     DecViewPost pr = {};
@@ -616,6 +626,11 @@ int parse_files(Batch &b)
                     pr.flags = vp.flags, pr.radius = vp.blur_radius, pr.threshold = vp.solarize_threshold, pr.bits = vp.posterize_bits;
                     if (vp.flags & kPostBlur) post_blur_weights(vp.blur_radius, vp.blur_sigma, pr.k);
                     if (b.warp) pr.warp = warp_record(b.warp[view]);
+                    if (b.tone && b.tone[view].op) { // (tone: an offset until place_files())
+                        pr.tone_op = b.tone[view].op, pr.tone_factor = b.tone[view].factor;
+                        const uint64_t before = b.tone_refs.empty() ? 0 : b.tone_refs.back().pre + tone_chunks(b.post_recs[b.tone_refs.back().rec].w, b.post_recs[b.tone_refs.back().rec].h);
+                        b.tone_refs.push_back({before, (uint32_t)b.post_recs.size(), 0});
+                    }
                     b.post_recs.push_back(pr);
                     rs.dst = nullptr, rs.pitch = (int32_t)rs.w, rs.plane_pitch = (int64_t)((uint64_t)rs.w * rs.h), rs.flags &= ~kResizeMirror;
                 }
@@ -674,6 +689,11 @@ int parse_files(Batch &b)
         b.job_file.push_back(i);
     }
     b.job_rec.push_back((uint32_t)b.resize.size());
+    b.job_tone.push_back((uint32_t)b.tone_refs.size());
+    if (!b.tone_refs.empty()) { // (the entry that closes the sums)
+        const DecViewPost &last = b.post_recs[b.tone_refs.back().rec];
+        b.tone_refs.push_back({b.tone_refs.back().pre + tone_chunks(last.w, last.h), 0, 0});
+    }
     if (tracing()) fprintf(stderr, "[decode] +%.0f us: %u files parsed, %u lookup tables wanted\n", b.since(), b.n, b.luts.count());
     return FPNG_AMD_OK;
 }
@@ -686,9 +706,11 @@ int place_files(Batch &b)
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
     const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * b.resize_rec_bytes()), o_pre = sc.carve(b.view_count ? (b.resize_pre.size() + (b.post ? 1 : 0)) * sizeof(uint64_t) : 0), o_post = sc.carve(b.post_recs.size() * sizeof(DecViewPost)), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * b.resize_rec_bytes()), o_pre = sc.carve(b.view_count ? (b.resize_pre.size() + (b.post ? 1 : 0)) * sizeof(uint64_t) : 0), o_post = sc.carve(b.post_recs.size() * sizeof(DecViewPost)), o_tone_refs = sc.carve(b.tone_refs.size() * sizeof(DecToneRef)), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
     // (nothing more than without the check unless it is asked for)
     const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
+    // (the tone views' histograms and tables: behind the set-up block, which is uploaded; these are zeroed and written on the device)
+    const size_t n_tone = b.tone_refs.empty() ? 0 : b.tone_refs.size() - 1, o_tone = sc.carve(n_tone * kToneBytes);
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
     int rc;
     if ((rc = sc.place(e, b.d))) return rc;
@@ -703,6 +725,8 @@ int place_files(Batch &b)
     b.d_resize_color = b.color ? (DecResizeColor *)(base + o_resize) : nullptr;
     b.d_resize_pre = b.view_count ? (uint64_t *)(base + o_pre) : nullptr;
     b.d_post = b.post ? (DecViewPost *)(base + o_post) : nullptr;
+    b.d_tone_refs = n_tone ? (DecToneRef *)(base + o_tone_refs) : nullptr, b.d_tone = n_tone ? base + o_tone : nullptr;
+    for (size_t t = 0; t < n_tone; t++) b.post_recs[b.tone_refs[t].rec].tone = (uint32_t *)(b.d_tone + t * kToneBytes);
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -829,6 +853,7 @@ int plan_groups(Batch &b)
             b.job_post.push_back((uint32_t)pi);
         }
         std::memcpy(h_setup + ((uint8_t *)b.d_post - (uint8_t *)b.d_jobs), b.post_recs.data(), b.post_recs.size() * sizeof(DecViewPost));
+        if (b.d_tone_refs) std::memcpy(h_setup + ((uint8_t *)b.d_tone_refs - (uint8_t *)b.d_jobs), b.tone_refs.data(), b.tone_refs.size() * sizeof(DecToneRef));
         std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), b.dir_pre.data(), b.dir_pre.size() * sizeof(uint64_t));
         std::memcpy(h_setup + ((uint8_t *)(b.d_resize_pre + nd + 1) - (uint8_t *)b.d_jobs), b.post_pre.data(), b.post_pre.size() * sizeof(uint64_t));
     } else if (b.color) {
@@ -900,9 +925,16 @@ int finish_group(Batch &b, uint32_t gi)
             const int kind = b.post_of[q] >= 0;
             lds[kind] = std::max(lds[kind], b.resize_lds[q]), any_filter[kind] |= b.resize[q].filter != kResizeBilinear;
         }
-        const bool ok = launch_dec_resize_color(b.s, b.d_resize_color + d0, b.d_resize_pre + d0, b.dir_pre.data() + d0, d1 - d0, lds[0], b.flt, any_filter[0], b.hwc != nullptr) &&
-                        launch_dec_resize_color(b.s, b.d_resize_color + nd + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, lds[1], nullptr, any_filter[1], false) &&
-                        launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr, b.warp != nullptr);
+        bool ok = launch_dec_resize_color(b.s, b.d_resize_color + d0, b.d_resize_pre + d0, b.dir_pre.data() + d0, d1 - d0, lds[0], b.flt, any_filter[0], b.hwc != nullptr) &&
+                  launch_dec_resize_color(b.s, b.d_resize_color + nd + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, lds[1], nullptr, any_filter[1], false);
+        // (the group's tone views: their histograms zeroed every time -- a group that needed more rounds comes here again -- and
+        //  counted out of the windows just written, then their tables; the post stage looks them up)
+        const uint32_t t0 = b.d_tone ? b.job_tone[g.j0] : 0, t1 = b.d_tone ? b.job_tone[g.j1] : 0;
+        if (ok && t1 > t0) {
+            HIP_TRY(hipMemsetAsync(b.d_tone + (size_t)t0 * kToneBytes, 0, (size_t)(t1 - t0) * kToneBytes, b.s));
+            ok = launch_dec_view_tone(b.s, b.d_post, b.d_tone_refs + t0, b.tone_refs.data() + t0, t1 - t0);
+        }
+        ok = ok && launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr, b.tone ? 2 : b.warp ? 1 : 0);
         if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
     } else if (b.sizes) {
         const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1]; // (the records of the group's jobs)
@@ -1080,7 +1112,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
                  const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
                  const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
-                 const fpng_amd_view_warp *warp = nullptr)
+                 const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -1091,7 +1123,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr, b.warp = b.post ? warp : nullptr;
+        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr, b.warp = b.post ? warp : nullptr, b.tone = b.post ? tone : nullptr;
         b.view_ofs.resize(n);
         for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
     }
@@ -1388,7 +1420,7 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
                         const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
                         const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
-                        const fpng_amd_view_warp *warp = nullptr)
+                        const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && !view_count && i < n; i++)
@@ -1425,7 +1457,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post, warp);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post, warp, tone);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
@@ -1435,7 +1467,8 @@ static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_des
               "fpng_amd_view_dest_hwc layout");
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                        const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr,
-                       const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr, const fpng_amd_view_warp *warp = nullptr)
+                       const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr, const fpng_amd_view_warp *warp = nullptr,
+                       const fpng_amd_view_tone *tone = nullptr)
 {
     if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
@@ -1453,7 +1486,7 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
             if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
             if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
         }
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post, warp);
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post, warp, tone);
 }
 // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: the matrices are judged first -- a record per view, the sum of
 // the counts (those the views call refuses: its own message, below) -- then everything the views call judges
@@ -1507,16 +1540,22 @@ static_assert(sizeof(fpng_amd_view_post) == 32 && offsetof(fpng_amd_view_post, b
 int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_view_post *posts,
                             const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_warp *warps = nullptr,
-                            bool with_warps = false)
+                            bool with_warps = false, const fpng_amd_view_tone *tones = nullptr, bool with_tones = false)
 {
-    // with_warps: the _views_warp calls' -- the warp records are judged first, and posts may be NULL (no post flags)
-    if (with_warps && !warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps");
+    // with_warps: the _views_warp calls' -- the warp records are judged first, and posts may be NULL (no post flags).  with_tones: the
+    // _views_tone calls' -- the tone records are judged first, and posts and warps may each be NULL
+    if (with_tones && !tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones");
+    if (with_warps && !with_tones && !warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps");
     if (!with_warps && !posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts");
     if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
     bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
-    bool any = false, any_warp = false;
+    bool any = false, any_warp = false, any_tone = false;
+    for (uint64_t v = 0; tones && counts_ok && v < total; v++) {
+        if (const char *why = check_tone_record(tones[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        any_tone |= tones[v].op != 0;
+    }
     for (uint64_t v = 0; warps && counts_ok && v < total; v++) {
         if (const char *why = check_warp_record(warps[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
         any_warp |= warp_moves(warps[v]);
@@ -1528,10 +1567,11 @@ int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *file
     if (colors)
         if (int rc = check_color_records(colors, view_count, n)) return rc;
     // (no view with a flag: the colour call, or the plain one, enqueues what it always does; no warp flag: the post call does)
-    if (!any && !any_warp) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
+    if (!any && !any_warp && !any_tone) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
     std::vector<fpng_amd_view_post> no_posts;
     if (!posts) no_posts.assign((size_t)total, fpng_amd_view_post{}), posts = no_posts.data();
     if (!any_warp) warps = nullptr;
+    if (!any_tone) tones = nullptr; // (no view with an op: what the warp call enqueues)
     std::vector<fpng_amd_view_color> identity;
     if (!colors) {
         fpng_amd_view_color one = {};
@@ -1539,7 +1579,7 @@ int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *file
         identity.assign((size_t)total, one);
         colors = identity.data();
     }
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts, warps);
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts, warps, tones);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1733,6 +1773,53 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_warp(fpng_amd_encoder *e, 
                                                            fpng_amd_decode_result *results)
 {
     return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                       const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                       const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                       const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false, warps, true, tones, true);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                              const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                              const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                              const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true, warps, true, tones, true);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                    const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                    const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                    const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false, warps, true, tones, true);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                           const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                           const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                           const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true, tones, true);
+}
+
+// the tone rule on the host: the texts of view_tone.h, which dec_view_tone_lut_kernel runs
+extern "C" int fpng_amd_view_tone_lut(const fpng_amd_view_tone *tone, const uint32_t *hist, uint8_t *lut)
+{
+    const char *why = nullptr;
+    const int rc = tone_lut_checked(tone, hist, lut, &why);
+    return rc ? fail(rc, why) : FPNG_AMD_OK;
+}
+
+extern "C" int fpng_amd_view_tone_apply(const fpng_amd_view_tone *tone, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out)
+{
+    const char *why = nullptr;
+    const int rc = tone_apply_checked(tone, w, h, in, out, &why);
+    return rc ? fail(rc, why) : FPNG_AMD_OK;
 }
 
 // step 1a of the warp rule for one w x h plane of bytes, on the host: the texts of view_warp.h, which dec_view_post_kernel runs

@@ -17,6 +17,7 @@
 #pragma once
 #include "decode.h"
 #include "resize.h"
+#include "view_tone.h"
 #include "view_warp.h"
 
 #include <cmath>
@@ -61,12 +62,35 @@ struct DecViewPost {
     uint32_t flags, radius, threshold, bits;
     int32_t k[kPostMaxRadius + 1];
     DecWarp warp; // the _views_warp calls' (view_warp.h); flags 0: none.  With a warp the gather mirrors and the store does not
+    // the _views_tone calls' (view_tone.h); tone_op 0: none.  tone: the view's kToneBytes of the decode scratch -- uint32 h[4][256],
+    // which dec_view_tone_hist_kernel counts, then the uint8 lut[3][256] that dec_view_tone_lut_kernel makes of them
+    uint32_t *tone;
+    uint32_t tone_op;
+    float tone_factor;
 };
-static_assert(sizeof(DecViewPost) == 240 && offsetof(DecViewPost, pitch) == 24 && offsetof(DecViewPost, k) == 68 && offsetof(DecViewPost, warp) == 136, "DecViewPost layout");
+static_assert(sizeof(DecViewPost) == 256 && offsetof(DecViewPost, pitch) == 24 && offsetof(DecViewPost, k) == 68 && offsetof(DecViewPost, warp) == 136 &&
+                  offsetof(DecViewPost, tone) == 240 && offsetof(DecViewPost, tone_factor) == 252,
+              "DecViewPost layout");
 
 // An exact grid as launch_dec_resize_color's, a workgroup per (record, tile of kResizeTileW x kResizeTileH): pre / h_pre count TILES.
-// hwc: channels-last destinations.  warp: some record of the call has a warp (the instantiations that gather; without, the post
-// call's own).  false: a record without or with too many tiles; nothing more is launched.
-bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, bool warp = false);
+// hwc: channels-last destinations.  mode 1: some record of the call has a warp (the instantiations that gather; 0: the post call's
+// own); mode 2: some record has a tone op (the instantiations that gather and apply a table).  false: a record without or with too
+// many tiles; nothing more is launched.
+bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, int mode = 0);
+
+// The tone views of a call, in the order of their post records: refs[t].rec is tone view t's record of `recs`, refs[t].pre the chunks
+// of kToneChunk samples of the tone views in front of it; refs[n].pre closes the sums.
+struct DecToneRef {
+    uint64_t pre;
+    uint32_t rec, pad_;
+};
+static_assert(sizeof(DecToneRef) == 16, "DecToneRef layout");
+// what one workgroup of dec_view_tone_hist_kernel counts: eight 64 x 16 tiles' worth of samples in all three planes -- 24576 (contrast:
+// 8192) LDS atomics against the at most 768 (256) global ones of its flush; a 224 x 224 view is seven workgroups
+constexpr uint32_t kToneChunk = 8 * kResizeTileW * kResizeTileH;
+inline uint64_t tone_chunks(uint32_t w, uint32_t h) { return ((uint64_t)w * h + kToneChunk - 1) / kToneChunk; }
+// refs .. refs + n (device; h_refs: the host's copy, n + 1 entries): the histograms -- zeroed on the stream by the caller -- and then
+// the tables of those tone views.  false: a view without or with too many chunks; nothing more is launched.
+bool launch_dec_view_tone(hipStream_t s, const DecViewPost *recs, const DecToneRef *refs, const DecToneRef *h_refs, uint32_t n);
 
 } // namespace fpng_amd

@@ -17,6 +17,10 @@
 // sample's position is found once (warp_locate) and serves its planes, so stage 1 fills the halos of all three colour planes in one
 // sweep (S holds three); the fourth plane is gathered too.  Whether a record has a warp is uniform across its workgroup.  The
 // window is at most a few hundred KB and has just been written: the gather reads it out of L2.
+// A view with a TONE op (the _views_tone calls; view_tone.h: the rule) reads W' = lut[W]: the kMode == 2 instantiations run those
+// calls.  They copy the view's three 256-byte tables, which dec_view_tone_lut_kernel has written into the scratch, into LDS (the
+// identity for a view of the call without an op) and look every sample up where the text above loads B or gathers W -- the halo
+// fill, the warp's halo fill and both R = 0 paths.  The fourth plane is not looked up.
 //   4. the store: a thread has all channels of its pixels; every element is stored on its own -- planar destinations as
 //      dec_resize_color_kernel's, lanes along a row of a plane; channels-last ones by element, position c or planes - 1 - c of the
 //      pixel, positions >= planes never written.
@@ -49,10 +53,13 @@ template <int kDtype> __device__ __forceinline__ void post_store(uint8_t *p, uin
     }
 }
 
-template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResizeBlock) void dec_view_post_kernel(const DecViewPost *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
+// kMode: 0 the post calls', 1 the warp calls' (gathers), 2 the tone calls' (gathers and applies a table)
+template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResizeBlock) void dec_view_post_kernel(const DecViewPost *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
+    constexpr bool kWarp = kMode >= 1, kTone = kMode == 2;
     constexpr uint32_t kHalo = kPostHaloH * kPostHaloW;
-    __shared__ __attribute__((aligned(16))) uint8_t S[(kWarp ? 3 : 1) * kHalo]; // the tile and its halo, rows of sw bytes (kWarp: per colour plane)
+    // the tile and its halo, rows of sw bytes (kWarp: per colour plane); kTone: behind them the view's tables, lut[c][v]
+    __shared__ __attribute__((aligned(16))) uint8_t S[(kWarp ? 3 : 1) * kHalo + (kTone ? kToneLutBytes : 0)];
     __shared__ __attribute__((aligned(16))) uint8_t Hb[kPostHaloH * kResizeTileW]; // the horizontal pass: rows of kResizeTileW bytes
     __shared__ int32_t K[kPostMaxRadius + 1];                                   // k[d]: taps -d and d share it
     const uint64_t g = pre[0] + blockIdx.x;
@@ -77,6 +84,17 @@ template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResiz
     const uint32_t threshold = r.threshold, bits = r.bits;
     const uint32_t wflags = kWarp ? r.warp.flags : 0u, mirror = r.mirror;
     uint32_t res[kRowsPerWave] = {};
+    uint8_t *const T = S + (kTone ? 3 * kHalo : 0u); // (kTone only)
+    if constexpr (kTone) {
+        const uint8_t *const lut = r.tone_op ? (const uint8_t *)(r.tone + kToneHistWords) : nullptr;
+        for (uint32_t k = tid; k < kToneLutBytes; k += kResizeBlock) T[k] = lut ? lut[k] : (uint8_t)k;
+        __syncthreads();
+    }
+    // (the byte of W' for the byte b of plane p of W)
+    const auto tone = [&](uint32_t p, uint32_t b) -> uint32_t {
+        if constexpr (kTone) return T[p * 256 + b];
+        else return b;
+    };
     if (R) {
         if (tid <= R) K[tid] = r.k[tid];
         const uint32_t sw = nw + 2 * R, sh = nq + 2 * R; // (<= kPostHaloW, kPostHaloH)
@@ -92,14 +110,14 @@ template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResiz
                         const uint32_t y = post_refl((int32_t)(oq0 + j) - (int32_t)R, h);
                         for (uint32_t i = o; i < sw; i += kResizeTileW) {
                             const WarpAt at = warp_locate(r.warp, post_refl((int32_t)(ox0 + i) - (int32_t)R, w), y, w, h, mirror);
-                            for (uint32_t p = 0; p < np; p++) S[p * kHalo + j * kPostHaloW + i] = (uint8_t)warp_sample(at, wflags, r.src + p * plane_bytes, w, r.warp.fill[p]);
+                            for (uint32_t p = 0; p < np; p++) S[p * kHalo + j * kPostHaloW + i] = (uint8_t)tone(p, warp_sample(at, wflags, r.src + p * plane_bytes, w, r.warp.fill[p]));
                         }
                     }
                 }
             } else
                 for (uint32_t j = wave; j < sh; j += kWaves) {
                     const uint8_t *const row = src + (uint64_t)post_refl((int32_t)(oq0 + j) - (int32_t)R, h) * w;
-                    for (uint32_t i = o; i < sw; i += kResizeTileW) Sp[j * kPostHaloW + i] = row[post_refl((int32_t)(ox0 + i) - (int32_t)R, w)];
+                    for (uint32_t i = o; i < sw; i += kResizeTileW) Sp[j * kPostHaloW + i] = (uint8_t)tone(plane, row[post_refl((int32_t)(ox0 + i) - (int32_t)R, w)]);
                 }
             __syncthreads();
             // ---- 2. the horizontal pass ----
@@ -133,7 +151,7 @@ template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResiz
             if (q >= nq) break;
             const WarpAt at = warp_locate(r.warp, ox0 + o, oq0 + q, w, h, mirror);
             for (uint32_t plane = 0; plane < C && plane < 3; plane++)
-                res[k] |= post_point(warp_sample(at, wflags, r.src + plane * plane_bytes, w, r.warp.fill[plane]), flags, threshold, bits) << (8 * plane);
+                res[k] |= post_point(tone(plane, warp_sample(at, wflags, r.src + plane * plane_bytes, w, r.warp.fill[plane])), flags, threshold, bits) << (8 * plane);
             if (C == 4) res[k] |= warp_sample(at, wflags, r.src + 3 * plane_bytes, w, r.warp.fill[3]) << 24;
         }
     } else if (o < nw) {
@@ -142,7 +160,7 @@ template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResiz
             for (uint32_t k = 0; k < kRowsPerWave; k++) {
                 const uint32_t q = wave + k * kWaves;
                 if (q >= nq) break;
-                res[k] |= post_point(r.src[plane * plane_bytes + (uint64_t)(oq0 + q) * w + ox0 + o], flags, threshold, bits) << (8 * plane);
+                res[k] |= post_point(tone(plane, r.src[plane * plane_bytes + (uint64_t)(oq0 + q) * w + ox0 + o]), flags, threshold, bits) << (8 * plane);
             }
         }
     }
@@ -193,21 +211,24 @@ template <int kDtype, bool kHwc, bool kWarp> __global__ __launch_bounds__(kResiz
 
 } // namespace
 
-bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, bool warp)
+bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, int mode)
 {
     using Kernel = void (*)(const DecViewPost *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
-        {{dec_view_post_kernel<-1, false, false>, dec_view_post_kernel<0, false, false>, dec_view_post_kernel<1, false, false>, dec_view_post_kernel<2, false, false>},
-         {dec_view_post_kernel<-1, true, false>, dec_view_post_kernel<0, true, false>, dec_view_post_kernel<1, true, false>, dec_view_post_kernel<2, true, false>}},
-        {{dec_view_post_kernel<-1, false, true>, dec_view_post_kernel<0, false, true>, dec_view_post_kernel<1, false, true>, dec_view_post_kernel<2, false, true>},
-         {dec_view_post_kernel<-1, true, true>, dec_view_post_kernel<0, true, true>, dec_view_post_kernel<1, true, true>, dec_view_post_kernel<2, true, true>}}};
+    static const Kernel kernels[3][2][kDecFloatTypes + 1] = {
+        {{dec_view_post_kernel<-1, false, 0>, dec_view_post_kernel<0, false, 0>, dec_view_post_kernel<1, false, 0>, dec_view_post_kernel<2, false, 0>},
+         {dec_view_post_kernel<-1, true, 0>, dec_view_post_kernel<0, true, 0>, dec_view_post_kernel<1, true, 0>, dec_view_post_kernel<2, true, 0>}},
+        {{dec_view_post_kernel<-1, false, 1>, dec_view_post_kernel<0, false, 1>, dec_view_post_kernel<1, false, 1>, dec_view_post_kernel<2, false, 1>},
+         {dec_view_post_kernel<-1, true, 1>, dec_view_post_kernel<0, true, 1>, dec_view_post_kernel<1, true, 1>, dec_view_post_kernel<2, true, 1>}},
+        {{dec_view_post_kernel<-1, false, 2>, dec_view_post_kernel<0, false, 2>, dec_view_post_kernel<1, false, 2>, dec_view_post_kernel<2, false, 2>},
+         {dec_view_post_kernel<-1, true, 2>, dec_view_post_kernel<0, true, 2>, dec_view_post_kernel<1, true, 2>, dec_view_post_kernel<2, true, 2>}}};
+    if (mode < 0 || mode > 2) return false;
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     for (uint32_t r0 = 0; r0 < n;) {
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[warp][hwc][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+        hipLaunchKernelGGL(kernels[mode][hwc][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
         r0 = r1;
     }
     return true;

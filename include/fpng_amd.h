@@ -978,6 +978,78 @@ int fpng_amd_decode_batch_device_hwc_views_warp(fpng_amd_encoder *enc, const fpn
 /* step 1a of the rule for ONE w x h plane of bytes (no GPU): in is B, the un-mirrored window; out is W; fill_value is the plane's
  * fill (the record's own fill is not read).  The text that the kernel runs.  The record is judged as the calls judge it */
 int fpng_amd_view_warp_apply(const fpng_amd_view_warp *warp, uint32_t w, uint32_t h, uint32_t mirror, const uint8_t *in, uint8_t *out, uint8_t fill_value);
+/* ---- the warp call with a TONE record per view behind the warp record: AutoContrast, Equalize and Contrast of RandAugment /
+ *      TrivialAugment / AutoAugment -- on a PIL image ImageOps.autocontrast(img), ImageOps.equalize(img) and
+ *      ImageEnhance.Contrast(img).enhance(factor), which is also ColorJitter's contrast -- drawn per view by the caller.  Each is a
+ *      statistic of the WHOLE view (its 256-bin histograms), a 256-entry table per channel and a point operation.  The argument
+ *      lists are those of the _views_warp calls with `tones`, a record per view, behind `warps`; colors, posts and warps may each be
+ *      NULL; tones may not.
+ *      THE RULE (every element is exact).  A view whose op is 0 is written bit for bit as the _views_warp call writes it.  A view
+ *      with an op is a post view whatever its other flags, and the tone stage sits behind the colour matrix and the warp and in
+ *      front of the blur, solarize and posterize:
+ *        W is the view's un-mirrored uint8 window as the post stage loads it: B of the post rule without a warp, the warp's W
+ *          (fill samples included, as Pillow sees them after transform) with one.  Only planes 0, 1, 2 take part: a fourth plane
+ *          skips the stage, as it skips the matrix and the blur.
+ *        h_c[v], c = 0, 1, 2: the count of byte v in plane c of W.  h_L[v]: the count of L = (19595 R + 38470 G + 7471 B + 0x8000)
+ *          >> 16, Pillow's convert("L") (CONTRAST only).  Counts are uint32.
+ *        AUTOCONTRAST (cutoff 0), per channel: lo and hi are the first and last v with h_c[v] > 0.  hi <= lo: the identity.
+ *          Otherwise in IEEE double WITHOUT contraction: scale = 255.0 / (hi - lo); offset = -lo * scale;
+ *          lut[v] = clamp((int)(v * scale + offset), 0, 255), the cast truncating toward zero.
+ *        EQUALIZE, per channel, in 64-bit integers: fewer than two non-zero bins: the identity.  Otherwise
+ *          step = (sum h_c - h_c[last non-zero]) / 255, floored; step == 0: the identity.  Otherwise n = step / 2 and for
+ *          v = 0 .. 255: lut[v] = min(255, n / step); n += h_c[v].  (The min is real: Pillow clips the list it hands to point().)
+ *        CONTRAST with `factor` (fp32, finite, >= 0): mean = (2 sum v h_L[v] + N) / (2 N), floored, N = w h: Pillow's
+ *          int(sum / count + 0.5).  All three channels use one table, in fp32 with every operation rounded on its own:
+ *              t = (float)mean + factor * (float)((int)v - (int)mean)
+ *              0 <= factor <= 1: lut[v] = (uint8_t)t, truncating;  else: 0 if t <= 0, 255 if t >= 255, (uint8_t)t in between
+ *          -- Pillow's ImagingBlend as an x86-64 build computes it (an aarch64 build may fuse the multiply and the add).
+ *        W'_c = lut_c[W_c]; steps 2 to 4 of the post rule, the conversion, the mirror and the store then run on W'.
+ *      GUARANTEES: a record with op == 0 leaves its view bit for bit the warp call's; a call in which no record has an op enqueues
+ *      exactly what the _views_warp call enqueues; for a file with status 0 a view depends only on (file, crop, view, colour, warp,
+ *      tone, post, fmt); only the spans the views call writes are written; statuses are the views call's.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null tones; an unknown op; a
+ *      non-zero reserved word; a factor that is not finite or is negative with CONTRAST; a non-zero factor (a NaN is not 0) without
+ *      it; w * h beyond 32 bits for a view with an op; and everything the warp call refuses.
+ *      A tone view runs as a post view does, with two small kernels in front of the post stage: dec_view_tone_hist_kernel counts
+ *      the window's bytes (through the warp's gather where there is one) into uint32[4][256] of the decode scratch, zeroed on the
+ *      stream in front of it, and dec_view_tone_lut_kernel writes the view's uint8[3][256] tables; the post stage applies them
+ *      wherever it loads a sample, the blur's reflected halo included.
+ *      Not offered: Sharpness (a 3 x 3 filter, not a statistic); two tone operations on one view; autocontrast's cutoff, ignore
+ *      and preserve_tone; aarch64 Pillow's fused blend; a tone record in fpng_amd_decode_host or the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_tone with dlsym. ---- */
+#define FPNG_AMD_TONE_AUTOCONTRAST 1
+#define FPNG_AMD_TONE_EQUALIZE 2
+#define FPNG_AMD_TONE_CONTRAST 3
+typedef struct fpng_amd_view_tone {
+    uint32_t op;          /* FPNG_AMD_TONE_*; 0 = none: this view is the warp call's, untouched */
+    float factor;         /* CONTRAST only, else 0 */
+    uint32_t reserved[2]; /* 0 */
+} fpng_amd_view_tone;     /* 16 bytes */
+int fpng_amd_decode_batch_planar_views_tone(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                            const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                            const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                            const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                            const fpng_amd_view_tone *tones /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                            fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_tone(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                   const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                   const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                   const fpng_amd_view_tone *tones, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_tone(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                         const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                         const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                         const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                         const fpng_amd_view_tone *tones /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 */,
+                                         fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_tone(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                const fpng_amd_view_tone *tones, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+/* the tables of the rule (no GPU): hist is h_R, h_G, h_B, h_L, 256 counts each; lut the three channels' tables.  The text that the
+ * kernel runs.  The record is judged as the calls judge it (op 0: the identity) */
+int fpng_amd_view_tone_lut(const fpng_amd_view_tone *tone, const uint32_t hist[4 * 256], uint8_t lut[3 * 256]);
+/* the whole stage for ONE view (no GPU): in is W, three planes of w x h bytes one behind the other; out is W' */
+int fpng_amd_view_tone_apply(const fpng_amd_view_tone *tone, uint32_t w, uint32_t h, const uint8_t *in /* 3 planes */, uint8_t *out /* 3 planes */);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

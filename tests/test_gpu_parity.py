@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from cpu_ref import ROOT, fuzz_image, have_ref, oracle, ref
+from walk_cases import direct_cases, row_end_cases, super_window_tier_cases, wide_fuzz, window_chunk_cases
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -105,71 +106,17 @@ def test_fuzz_vs_oracle_batched(enc, flags):
 @pytest.mark.parametrize("c", [3, 4])
 def test_widths_around_window_and_chunk_limits(enc, c):
     """Window (64 px) and chunk-cap (63 / 85 px) boundaries, runs crossing windows."""
-    rng = np.random.default_rng(7 + c)
-    imgs, dims = [], []
-    for w in [1, 2, 3, 62, 63, 64, 65, 66, 84, 85, 86, 87, 126, 127, 128, 129, 130, 170, 171, 172, 191, 192, 193, 255, 256,
-              257, 500, 1000, 4099]:
-        for h in (1, 2, 5):
-            for kind in range(4):
-                if kind == 0:      # solid
-                    img = np.full((h, w, c), 77, dtype=np.uint8)
-                elif kind == 1:    # long runs with random breaks
-                    img = np.repeat(rng.integers(0, 256, (h, (w + 39) // 40, c), dtype=np.uint8), 40, axis=1)[:, :w]
-                elif kind == 2:    # runs of random length 1..200 on the FILTERED rows: make rows identical so Up gives zeros after row 0
-                    row = np.repeat(rng.integers(0, 256, (1, w, c), dtype=np.uint8), h, axis=0)
-                    brk = rng.random((1, w)) < 0.03
-                    row[:, ~brk[0]] = 0
-                    row = np.maximum.accumulate(row, axis=1)
-                    img = row
-                else:              # two-pixel alternation (1-pixel matches -> literal-vs-match rule)
-                    a = rng.integers(0, 256, (h, 1, c), dtype=np.uint8)
-                    img = np.repeat(a, w, axis=1).copy()
-                    img[:, 2::3] = rng.integers(0, 256, (h, len(range(2, w, 3)), c), dtype=np.uint8)
-                imgs.append(np.ascontiguousarray(img))
-                dims.append((w, h, c))
+    imgs, dims = window_chunk_cases(c)
     for fl in (0, 1):
         pngs, _ = _gpu_encode(enc, imgs, fl)
         for img, (w, h, c_), p in zip(imgs, dims, pngs):
             _assert_same(p, oracle().encode(img, w, h, c_, fl), f"{w}x{h}x{c_} flags={fl}")
 
 
-def _tier_pattern(rng, kind, w, c):
-    """One FILTERED row exercising a particular mix of the row walker's super-window (256 px) tiers."""
-    row = rng.integers(0, 256, (w, c), dtype=np.uint8)
-    x = np.arange(w)
-    if kind == "sparse":           # isolated repeats, some of them straddling 4-pixel lane groups and super-window seams
-        rep = rng.random(w) < 0.01
-        rep[[i for i in (1, 3, 4, 255, 256, 257, 511, 512) if i < w]] = True
-        rep[0] = False
-        for i in np.flatnonzero(rep):
-            row[i] = row[i - 1]
-    elif kind == "lit_then_runs":  # literal super-windows, then run-heavy ones (walker hands the row over mid-way)
-        row[x >= (w // 2)] = row[w // 2]
-    elif kind == "runs_then_lit":
-        row[x < (w // 2)] = 9
-    elif kind == "alternate":      # general and literal super-windows alternate: the hand-over streak must reset
-        for s in range(0, w, 512):
-            row[s:s + 200] = row[s]
-    elif kind == "pairs":          # every second pixel repeats: 1-pixel matches everywhere (literal-vs-match rule)
-        row[1::2] = row[0:w - (w % 2):2][: len(row[1::2])]
-    elif kind == "long_run_mid":   # a run longer than the chunk cap crossing several super-windows
-        a, b = w // 5, w - w // 7
-        row[a:b] = row[a]
-    return row
-
-
 @pytest.mark.parametrize("c", [3, 4])
 def test_super_window_tiers(enc, c):
     """Widths around the 256-pixel super-window and its 4-pixel lane groups, with content that steers each tier."""
-    rng = np.random.default_rng(40 + c)
-    imgs, dims = [], []
-    for w in [252, 256, 257, 259, 260, 511, 512, 513, 516, 768, 1023, 1024, 1025, 1300, 2065]:
-        for kind in ("sparse", "lit_then_runs", "runs_then_lit", "alternate", "pairs", "long_run_mid"):
-            r0 = _tier_pattern(rng, kind, w, c)
-            r1 = (r0.astype(np.uint16) + _tier_pattern(rng, kind, w, c)).astype(np.uint8)   # Up-filtered row 1 = second pattern
-            r2 = (r1.astype(np.uint16) + _tier_pattern(rng, "sparse", w, c)).astype(np.uint8)
-            imgs.append(np.ascontiguousarray(np.stack([r0, r1, r2])))
-            dims.append((w, 3, c))
+    imgs, dims = super_window_tier_cases(c)
     for fl in (0, 1):
         pngs, _ = _gpu_encode(enc, imgs, fl)
         for img, (w, h, c_), p in zip(imgs, dims, pngs):
@@ -184,32 +131,16 @@ def test_rows_ending_on_a_super_window(enc, c):
     import torch
     from fpng_amd import sharded
     from band_backend import OracleBandBackend
-    rng = np.random.default_rng(90 + c)
     be = sharded.GpuBandBackend(enc)
-    for w in (256, 257, 259, 300, 511, 512, 700, 768, 1000, 1024, 1920, 3840, 4099):   # the last super-window complete or partial
-        for end in ("literal", "repeat1", "repeat2", "run_cap", "solid_tail", "sparse"):
-            rows = rng.integers(0, 256, (3, w, c), dtype=np.uint8)
-            for r in rows:  # the FILTERED rows get the pattern: build them, then integrate over y
-                if end == "repeat1":
-                    r[w - 1] = r[w - 2]
-                elif end == "repeat2":
-                    r[w - 2:] = r[w - 3]
-                elif end == "run_cap":
-                    r[w - 64:] = r[w - 65]
-                elif end == "solid_tail":
-                    r[w - 256:] = 5
-                elif end == "sparse":
-                    for i in (3, 64, 200, w - 5, w - 1):
-                        r[i] = r[i - 1]
-            img = np.ascontiguousarray(np.cumsum(rows.astype(np.uint16), axis=0).astype(np.uint8))
-            for fl in (0, 1):
-                pngs, _ = _gpu_encode(enc, [img], fl)
-                _assert_same(pngs[0], oracle().encode(img, w, 3, c, fl), f"row end {end} {w}x3x{c} flags={fl}")
-            # one band = the whole image: its counts straight from the kernels
-            t = torch.from_numpy(img).cuda()
-            got = be.encode(t, None, w, c, 0, 3, 3, 0, None)
-            want = OracleBandBackend(img).encode(None, None, w, c, 0, 3, 3, 0, None)
-            assert (got.token_bits, got.last_unit_bits, got.s1, got.s2) == (want.token_bits, want.last_unit_bits, want.s1, want.s2), (end, w, c, got, want)
+    for end, w, img in row_end_cases(c):
+        for fl in (0, 1):
+            pngs, _ = _gpu_encode(enc, [img], fl)
+            _assert_same(pngs[0], oracle().encode(img, w, 3, c, fl), f"row end {end} {w}x3x{c} flags={fl}")
+        # one band = the whole image: its counts straight from the kernels
+        t = torch.from_numpy(img).cuda()
+        got = be.encode(t, None, w, c, 0, 3, 3, 0, None)
+        want = OracleBandBackend(img).encode(None, None, w, c, 0, 3, 3, 0, None)
+        assert (got.token_bits, got.last_unit_bits, got.s1, got.s2) == (want.token_bits, want.last_unit_bits, want.s1, want.s2), (end, w, c, got, want)
 
 
 @pytest.mark.parametrize("c", [3, 4])
@@ -638,10 +569,7 @@ def test_wide_rows_fuzz(enc, flags):
     """Rows of 257..4100 pixels built in filtered space from runs of every interesting length, isolated pairs and literal
     stretches at random alignment to the 256-pixel super-windows (tools/gpu_wide_fuzz.py; a 27 000-image run of the same
     generator is in profiles/r03_fuzz_campaign.txt): batches of 200 through one submission each."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("gpu_wide_fuzz", os.path.join(ROOT, "tools", "gpu_wide_fuzz.py"))
-    wf = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(wf)
+    wf = wide_fuzz()
     rng = np.random.default_rng(4000 + flags)
     for _ in range(3):
         cases = [wf.wide_image(rng) for _ in range(200)]
@@ -731,49 +659,13 @@ def test_length_limited_tables_from_the_device_builder(enc):
     assert deep >= 10, deep  # (files whose literal codes reach the 12-bit limit)
 
 
-def _direct_cases(rng):
-    """Images that put seams where they hurt a walk in 256-pixel steps: widths just over / under / on multiples of 256, runs that cross seams or end
-    on them, flat rows (one run over the whole row: the look back over the pixels in front of a piece walks to the row's start),
-    64-pixel tiles, noise (chunks that overflow the wave's window and spill), gradients."""
-    import fpng_amd
-    cases = []
-    for w in (257, 300, 511, 512, 513, 768, 1025, 1280, 1537, 2049, 2304):
-        for c in (3, 4):
-            h = int(rng.integers(3, 12))
-            for kind in ("grad", "blocks", "solid"):
-                cases.append((fpng_amd.synth_image(kind, w, h, c, seed=int(rng.integers(1, 1 << 30))), w, h, c))
-            # runs of random lengths (1..700 pixels) of random colours, rows repeated now and then (Up-filtered: all-zero rows)
-            img = np.zeros((h, w, c), dtype=np.uint8)
-            for y in range(h):
-                if y and rng.random() < 0.3:
-                    img[y] = img[y - 1]
-                    continue
-                x = 0
-                while x < w:
-                    n = int(rng.integers(1, 700)) if rng.random() < 0.5 else int(rng.integers(1, 6))
-                    img[y, x:x + n] = rng.integers(0, 256, c, dtype=np.uint8)
-                    x += n
-            cases.append((img, w, h, c))
-            # a run that ends exactly on / one pixel after / one before every multiple of 256
-            img = rng.integers(0, 256, (h, w, c), dtype=np.uint8)
-            for y in range(h):
-                for s0 in range(256, w, 256):
-                    e = s0 + int(rng.integers(-1, 2))
-                    b = max(0, e - int(rng.integers(2, 200)))
-                    img[y, b:e] = img[y, b]
-            cases.append((img, w, h, c))
-    cases.append((fpng_amd.synth_image("noise", 2048, 5, 4), 2048, 5, 4))
-    cases.append((fpng_amd.synth_image("noise", 3000, 4, 3), 3000, 4, 3))
-    return cases
-
-
 def test_runs_across_super_window_borders(enc):
     """The row walk takes 256 pixels per step: widths just over / under / on multiples of 256, runs that cross such a border or end
     on it, flat rows, tiles, noise.  (The case list was written for round 5's direct-placement kernel, whose row pieces had their
     seams there; that kernel lost 2.3 x and left the product in round 6 -- profiles/r05_encode_onchip_ab.txt keeps its record --
     the cases stay, through the product's chain.)  Byte-identical to the checker, both passes."""
     rng = np.random.default_rng(5150)
-    cases = _direct_cases(rng)
+    cases = direct_cases(rng)
     judge = ref() if have_ref() else oracle()
     for flags in (0, 1):
         for k in range(0, len(cases), 24):

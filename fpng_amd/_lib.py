@@ -113,8 +113,13 @@ class ViewTone(C.Structure):  # fpng_amd_view_tone: 16 bytes, the tone record of
     _fields_ = [("op", C.c_uint32), ("factor", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class ViewEnhance(C.Structure):  # fpng_amd_view_enhance: 16 bytes, the enhance record of ONE view of the _views_enhance calls
+    _fields_ = [("op", C.c_uint32), ("factor", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 POST_BLUR, POST_SOLARIZE, POST_POSTERIZE = 1, 2, 4  # FPNG_AMD_POST_*
 TONE_AUTOCONTRAST, TONE_EQUALIZE, TONE_CONTRAST = 1, 2, 3  # FPNG_AMD_TONE_*
+ENHANCE_BRIGHTNESS, ENHANCE_COLOR, ENHANCE_SHARPNESS = 1, 2, 3  # FPNG_AMD_ENHANCE_*
 WARP_AFFINE, WARP_BILINEAR = 1, 2  # FPNG_AMD_WARP_*
 BLUR_MAX_RADIUS = 16  # FPNG_AMD_BLUR_MAX_RADIUS
 HWC_REVERSED = 1  # FPNG_AMD_HWC_REVERSED
@@ -285,6 +290,19 @@ SIGNATURES = {
                                             C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_view_tone_lut": (_int, [C.POINTER(ViewTone), C.c_void_p, C.c_void_p]),
     "fpng_amd_view_tone_apply": (_int, [C.POINTER(ViewTone), _u32, _u32, C.c_void_p, C.c_void_p]),
+    "fpng_amd_decode_batch_planar_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
+                                            C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_planar_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
+                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
+                                            C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_hwc_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
+                                            C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_hwc_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
+                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
+                                            C.POINTER(DecodeResult)]),
+    "fpng_amd_view_enhance_apply": (_int, [C.POINTER(ViewEnhance), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_blur_weights": (_int, [_u32, C.c_double, C.POINTER(C.c_int32 * 17)]),
     "fpng_amd_view_post_apply": (_int, [C.POINTER(ViewPost), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_color_apply": (None, [C.POINTER(ViewColor), C.POINTER(C.c_uint8 * 3), C.POINTER(C.c_float * 3)]),

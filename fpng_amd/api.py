@@ -708,32 +708,38 @@ def view_tone(autocontrast=False, equalize=False, contrast=None):
     return rec
 
 
-def _tone_records(who, counts, tone):
-    """the tone= argument of the views calls -> fpng_amd_view_tone[sum(counts)]: nested as _post_records' argument"""
+def _view_records(who, counts, arg, cls, noun):
+    """the `noun`= argument of the views calls -> cls[sum(counts)]: one record (view_<noun>() makes them) for all views, a list with
+    one per file, or a list per file of one per view"""
     total = sum(counts)
-    arr = (_lib.ViewTone * max(total, 1))()
+    arr = (cls * max(total, 1))()
 
     def put(at, rec):
-        if not isinstance(rec, _lib.ViewTone):
-            raise ValueError(f"{who}: a tone record is what view_tone() returns, not {type(rec).__name__}")
-        C.memmove(C.byref(arr, at * C.sizeof(_lib.ViewTone)), C.byref(rec), C.sizeof(_lib.ViewTone))
+        if not isinstance(rec, cls):
+            raise ValueError(f"{who}: {noun} takes what view_{noun}() returns, not {type(rec).__name__}")
+        C.memmove(C.byref(arr, at * C.sizeof(cls)), C.byref(rec), C.sizeof(cls))
 
-    if isinstance(tone, _lib.ViewTone):
+    if isinstance(arg, cls):
         for at in range(total):
-            put(at, tone)
+            put(at, arg)
         return arr
-    if not hasattr(tone, "__len__") or len(tone) != len(counts):
-        raise ValueError(f"{who}: tone is one view_tone() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
+    if not hasattr(arg, "__len__") or len(arg) != len(counts):
+        raise ValueError(f"{who}: {noun} is one view_{noun}() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
     at = 0
-    for i, (c, recs) in enumerate(zip(counts, tone)):
-        if isinstance(recs, _lib.ViewTone):
+    for i, (c, recs) in enumerate(zip(counts, arg)):
+        if isinstance(recs, cls):
             recs = [recs] * c
         if not hasattr(recs, "__len__") or len(recs) != c:
-            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} tone records")
+            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} {noun} records")
         for rec in recs:
             put(at, rec)
             at += 1
     return arr
+
+
+def _tone_records(who, counts, tone):
+    """the tone= argument of the views calls -> fpng_amd_view_tone[sum(counts)]: nested as _post_records' argument"""
+    return _view_records(who, counts, tone, _lib.ViewTone, "tone")
 
 
 def view_tone_lut(tone, hist):
@@ -762,6 +768,104 @@ def view_tone_apply(tone, planes):
     out = np.empty_like(px)
     check(_lib.load().fpng_amd_view_tone_apply(C.byref(tone), px.shape[2], px.shape[1], px.ctypes.data, out.ctypes.data))
     return out
+
+
+def view_enhance(brightness=None, color=None, sharpness=None):
+    """The fpng_amd_view_enhance record of one view of the views calls' enhance= argument: at most ONE of brightness=factor
+    (ImageEnhance.Brightness(img).enhance(factor)), color=factor (ImageEnhance.Color) and sharpness=factor (ImageEnhance.Sharpness)
+    -- factor finite and >= 0, rounded to fp32 once; 1 is the identity -- each Pillow's blend of a degenerate image (black, the
+    view's grey image, its SMOOTH-filtered image) and the view, behind the tone operation and in front of the blur, solarize and
+    posterize.  None of them: the view is the tone call's, untouched.  The caller draws the operation; the record is the contract."""
+    given = [(op, name, f) for op, name, f in ((_lib.ENHANCE_BRIGHTNESS, "brightness", brightness), (_lib.ENHANCE_COLOR, "color", color),
+                                               (_lib.ENHANCE_SHARPNESS, "sharpness", sharpness)) if f is not None]
+    if len(given) > 1:
+        raise ValueError("view_enhance: at most one of brightness, color and sharpness (two enhance operations on one view are not offered)")
+    rec = _lib.ViewEnhance()
+    for op, name, f in given:
+        try:
+            with np.errstate(over="ignore"):
+                factor = float(np.float32(f))
+        except (TypeError, ValueError):
+            raise ValueError(f"view_enhance: {name} is a number, not {f!r}") from None
+        if not math.isfinite(factor) or factor < 0.0:
+            raise ValueError(f"view_enhance: {name} is finite and >= 0, not {f}")
+        rec.op, rec.factor = op, factor
+    return rec
+
+
+def _enhance_records(who, counts, enhance):
+    """the enhance= argument of the views calls -> fpng_amd_view_enhance[sum(counts)]: nested as _post_records' argument"""
+    return _view_records(who, counts, enhance, _lib.ViewEnhance, "enhance")
+
+
+def view_enhance_apply(enhance, planes):
+    """fpng_amd_view_enhance_apply, the host twin of the enhance stage (no GPU): planes (3, h, w) uint8 -- what the tone stage hands
+    on -- -> (3, h, w) uint8 blended against the degenerate image of `enhance` (a view_enhance() record)."""
+    if not isinstance(enhance, _lib.ViewEnhance):
+        raise ValueError("view_enhance_apply: enhance is what view_enhance() returns")
+    px = np.asarray(planes)
+    if px.dtype != np.uint8 or px.ndim != 3 or px.shape[0] != 3 or px.size == 0:
+        raise ValueError(f"view_enhance_apply: planes is (3, h, w) uint8, not {px.shape} {px.dtype}")
+    px = np.ascontiguousarray(px)
+    out = np.empty_like(px)
+    check(_lib.load().fpng_amd_view_enhance_apply(C.byref(enhance), px.shape[2], px.shape[1], px.ctypes.data, out.ctypes.data))
+    return out
+
+
+def rotate_matrix(w, h, angle):
+    """The six coefficients for view_warp() that Pillow's Image.rotate(angle) (no expand, the default centre, no translate) hands to
+    transform() for a w x h image, computed as Pillow computes them: the cosine and sine of -radians(angle % 360) rounded to 15
+    digits, about the centre (w / 2, h / 2).  torchvision's rotate() of a PIL image calls Image.rotate; affine_matrix(w, h,
+    angle=-a) is torchvision's tensor path and differs from this in the last bits."""
+    cx, cy = w / 2, h / 2
+    a = -math.radians(float(angle) % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    m[2] = m[0] * -cx + m[1] * -cy + m[2]
+    m[5] = m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+AUGMENT_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness", "Posterize", "Solarize",
+               "AutoContrast", "Equalize")
+
+
+def augment_op(name, magnitude, w, h, filter="nearest", fill=0):
+    """The records of ONE operation of RandAugment / TrivialAugmentWide / AutoAugment on a w x h view, as a dict of keyword arguments
+    for the views calls (color= / warp= / tone= / enhance= / post=; only the keys the operation needs): `name` is one of the 14 that
+    torchvision's _apply_op knows (AUGMENT_OPS) and `magnitude` what _apply_op receives, already signed.  filter and fill are the
+    geometric operations' interpolation and fill."""
+    m = float(magnitude)
+    if name == "Identity":
+        return {}
+    if name == "ShearX":
+        return {"warp": view_warp(affine_matrix(w, h, shear=(math.degrees(math.atan(m)), 0.0), center=(0, 0)), filter, fill)}
+    if name == "ShearY":
+        return {"warp": view_warp(affine_matrix(w, h, shear=(0.0, math.degrees(math.atan(m))), center=(0, 0)), filter, fill)}
+    if name == "TranslateX":
+        return {"warp": view_warp(affine_matrix(w, h, translate=(int(m), 0)), filter, fill)}
+    if name == "TranslateY":
+        return {"warp": view_warp(affine_matrix(w, h, translate=(0, int(m))), filter, fill)}
+    if name == "Rotate":
+        return {"warp": view_warp(rotate_matrix(w, h, m), filter, fill)}
+    if name == "Brightness":
+        return {"enhance": view_enhance(brightness=1.0 + m)}
+    if name == "Color":
+        return {"enhance": view_enhance(color=1.0 + m)}
+    if name == "Sharpness":
+        return {"enhance": view_enhance(sharpness=1.0 + m)}
+    if name == "Contrast":
+        return {"tone": view_tone(contrast=1.0 + m)}
+    if name == "Posterize":
+        return {"post": view_post(posterize=int(m))}
+    if name == "Solarize":  # (ImageOps.solarize inverts the bytes that are not below m: those from ceil(m) on; none above 255)
+        return {"post": view_post(solarize=max(math.ceil(m), 0))} if m <= 255.0 else {}
+    if name == "AutoContrast":
+        return {"tone": view_tone(autocontrast=True)}
+    if name == "Equalize":
+        return {"tone": view_tone(equalize=True)}
+    raise ValueError(f"augment_op: name is one of {', '.join(AUGMENT_OPS)}, not {name!r}")
 
 
 def blur_weights(radius, sigma):
@@ -1118,6 +1222,7 @@ class DecodeBatchMultiView(_DecodeBatchViews):
     posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
     warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
     tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
+    enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1138,6 +1243,7 @@ class DecodeBatchMultiViewHwc(_DecodeBatchViews):
     posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
     warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
     tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
+    enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -2024,7 +2130,7 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None, color=None, post=None, warp=None, tone=None):
+                                scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
@@ -2039,7 +2145,9 @@ class Encoder:
         records (view_warp() makes them), nested as post's; the descriptor then goes through
         fpng_amd_decode_batch(_device)_planar_views_warp, with color's matrices and post's records or without.  tone: None, or the
         views' tone records (view_tone() makes them), nested as post's; the descriptor then goes through
-        fpng_amd_decode_batch(_device)_planar_views_tone, with the others' records or without."""
+        fpng_amd_decode_batch(_device)_planar_views_tone, with the others' records or without.  enhance: None, or the views' enhance
+        records (view_enhance() makes them), nested as post's; the descriptor then goes through
+        fpng_amd_decode_batch(_device)_planar_views_enhance, with the others' records or without."""
         who = "make_decode_batch_views"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -2108,15 +2216,17 @@ class Encoder:
             batch.warps = _warp_records(who, counts, warp)
         if tone is not None:
             batch.tones = _tone_records(who, counts, tone)
+        if enhance is not None:
+            batch.enhances = _enhance_records(who, counts, enhance)
         return batch
 
     def _decode_views(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                      color, post=None, fn_post=None, warp=None, tone=None):
+                      color, post=None, fn_post=None, warp=None, tone=None, enhance=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiView):
-            if color is not None or post is not None or warp is not None or tone is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp and tone records (make_decode_batch_views(..., color=, post=, warp=, tone=))")
+            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone and enhance records (make_decode_batch_views(..., color=, post=, warp=, tone=, enhance=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2129,14 +2239,17 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone)
+            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.tones is not None:
+        if batch.enhances is not None:
+            check(getattr(self.lib, fn_post.replace("_views_post", "_views_enhance"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
+                                                                                      batch.posts, batch.warps, batch.tones, batch.enhances, fmt, batch.res))
+        elif batch.tones is not None:
             check(getattr(self.lib, fn_post.replace("_views_post", "_views_tone"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
                                                                                    batch.posts, batch.warps, batch.tones, fmt, batch.res))
         elif batch.warps is not None:
@@ -2151,7 +2264,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -2176,28 +2289,31 @@ class Encoder:
         tone: None, or a tone record per view (view_tone() makes them: autocontrast, equalize or contrast about the view's own mean,
         as Pillow's ImageOps / ImageEnhance do them; nested as post's), applied to the bytes behind the colour step and the warp and
         in front of the blur -- fpng_amd_decode_batch_device_planar_views_tone; a record without an op leaves its view exactly the
-        call's without."""
+        call's without.
+        enhance: None, or an enhance record per view (view_enhance() makes them: brightness, color or sharpness as Pillow's
+        ImageEnhance does them; nested as post's), applied to the bytes behind the tone operation and in front of the blur --
+        fpng_amd_decode_batch_device_planar_views_enhance; a record without an op leaves its view exactly the call's without."""
         return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, self.lib.fpng_amd_decode_batch_device_planar_views_color, True, pngs,
                                   crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_device_planar_views_post", warp, tone)
+                                  "fpng_amd_decode_batch_device_planar_views_post", warp, tone, enhance)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, self.lib.fpng_amd_decode_batch_planar_views_color, False, pngs, crops,
                                   outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_planar_views_post", warp, tone)
+                                  "fpng_amd_decode_batch_planar_views_post", warp, tone, enhance)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None):
+                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
         value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
         fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post), warp (then:
-        fpng_amd_decode_batch(_device)_hwc_views_warp) and tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone) -- is
-        make_decode_batch_views()'s."""
+        fpng_amd_decode_batch(_device)_hwc_views_warp), tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone) and enhance (then:
+        fpng_amd_decode_batch(_device)_hwc_views_enhance) -- is make_decode_batch_views()'s."""
         who = "make_decode_batch_views_hwc"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
@@ -2266,15 +2382,17 @@ class Encoder:
             batch.warps = _warp_records(who, counts, warp)
         if tone is not None:
             batch.tones = _tone_records(who, counts, tone)
+        if enhance is not None:
+            batch.enhances = _enhance_records(who, counts, enhance)
         return batch
 
     def _decode_views_hwc(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                          color, post=None, fn_post=None, warp=None, tone=None):
+                          color, post=None, fn_post=None, warp=None, tone=None, enhance=None):
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
             raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
         if isinstance(pngs, DecodeBatchMultiViewHwc):
-            if color is not None or post is not None or warp is not None or tone is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp and tone records (make_decode_batch_views_hwc(..., color=, post=, warp=, tone=))")
+            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone and enhance records (make_decode_batch_views_hwc(..., color=, post=, warp=, tone=, enhance=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2287,14 +2405,17 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone)
+            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
         fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.tones is not None:
+        if batch.enhances is not None:
+            check(getattr(self.lib, fn_post.replace("_views_post", "_views_enhance"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
+                                                                                      batch.posts, batch.warps, batch.tones, batch.enhances, fmt, batch.res))
+        elif batch.tones is not None:
             check(getattr(self.lib, fn_post.replace("_views_post", "_views_tone"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
                                                                                    batch.posts, batch.warps, batch.tones, fmt, batch.res))
         elif batch.warps is not None:
@@ -2309,7 +2430,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -2324,14 +2445,14 @@ class Encoder:
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
         return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, self.lib.fpng_amd_decode_batch_device_hwc_views_color, True, pngs,
                                       crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_device_hwc_views_post", warp, tone)
+                                      "fpng_amd_decode_batch_device_hwc_views_post", warp, tone, enhance)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, self.lib.fpng_amd_decode_batch_hwc_views_color, False, pngs, crops,
                                       outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_hwc_views_post", warp, tone)
+                                      "fpng_amd_decode_batch_hwc_views_post", warp, tone, enhance)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

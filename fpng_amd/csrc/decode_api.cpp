@@ -385,6 +385,10 @@ struct Batch {
     // (tone_refs[t]: its post record and the chunks of dec_view_tone_hist_kernel in front of it) has kToneBytes of the scratch at
     // d_tone + t * kToneBytes; job k's tone views are job_tone[k] .. job_tone[k + 1] - 1
     const fpng_amd_view_tone *tone = nullptr;
+    // fpng_amd_decode_batch(_device)_planar_views_enhance / _hwc_views_enhance: the tone call with an enhance record per view (else NULL;
+    // only when at least one view has an op, and then with `post`).  A view with an op is a post view whatever its other flags, and
+    // the call's post stage is the kMode == 3 one
+    const fpng_amd_view_enhance *enhance = nullptr;
     std::vector<DecToneRef> tone_refs;
     std::vector<uint32_t> job_tone;
     DecToneRef *d_tone_refs = nullptr;
@@ -617,7 +621,7 @@ int parse_files(Batch &b)
                 rs.src += b.mid_total; // (an offset until place_files())
                 const uint64_t tiles = resize_tiles(rs.w, rs.h);
                 const uint32_t view = v0 + (uint32_t)(&rs - file_recs.data());
-                const bool is_post = b.post && (b.post[view].flags || (b.warp && warp_moves(b.warp[view])) || (b.tone && b.tone[view].op));
+                const bool is_post = b.post && (b.post[view].flags || (b.warp && warp_moves(b.warp[view])) || (b.tone && b.tone[view].op) || (b.enhance && b.enhance[view].op));
                 if (is_post) { // (the destination goes to the post stage; the resize writes tight un-mirrored uint8 planes)
                     const fpng_amd_view_post &vp = b.post[view];
                     DecViewPost pr = {};
@@ -626,6 +630,7 @@ int parse_files(Batch &b)
                     pr.flags = vp.flags, pr.radius = vp.blur_radius, pr.threshold = vp.solarize_threshold, pr.bits = vp.posterize_bits;
                     if (vp.flags & kPostBlur) post_blur_weights(vp.blur_radius, vp.blur_sigma, pr.k);
                     if (b.warp) pr.warp = warp_record(b.warp[view]);
+                    if (b.enhance) pr.enhance_op = b.enhance[view].op, pr.enhance_factor = b.enhance[view].factor;
                     if (b.tone && b.tone[view].op) { // (tone: an offset until place_files())
                         pr.tone_op = b.tone[view].op, pr.tone_factor = b.tone[view].factor;
                         const uint64_t before = b.tone_refs.empty() ? 0 : b.tone_refs.back().pre + tone_chunks(b.post_recs[b.tone_refs.back().rec].w, b.post_recs[b.tone_refs.back().rec].h);
@@ -934,7 +939,7 @@ int finish_group(Batch &b, uint32_t gi)
             HIP_TRY(hipMemsetAsync(b.d_tone + (size_t)t0 * kToneBytes, 0, (size_t)(t1 - t0) * kToneBytes, b.s));
             ok = launch_dec_view_tone(b.s, b.d_post, b.d_tone_refs + t0, b.tone_refs.data() + t0, t1 - t0);
         }
-        ok = ok && launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr, b.tone ? 2 : b.warp ? 1 : 0);
+        ok = ok && launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr, b.enhance ? 3 : b.tone ? 2 : b.warp ? 1 : 0);
         if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
     } else if (b.sizes) {
         const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1]; // (the records of the group's jobs)
@@ -1112,7 +1117,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
                  const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
                  const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
                  const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
-                 const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr)
+                 const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr, const fpng_amd_view_enhance *enhance = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -1123,7 +1128,7 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
     b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
     if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr, b.warp = b.post ? warp : nullptr, b.tone = b.post ? tone : nullptr;
+        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr, b.warp = b.post ? warp : nullptr, b.tone = b.post ? tone : nullptr, b.enhance = b.post ? enhance : nullptr;
         b.view_ofs.resize(n);
         for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
     }
@@ -1420,7 +1425,7 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
 int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
                         const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
                         const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
-                        const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr)
+                        const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr, const fpng_amd_view_enhance *enhance = nullptr)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; crops && !view_count && i < n; i++)
@@ -1457,7 +1462,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post, warp, tone);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post, warp, tone, enhance);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
@@ -1468,7 +1473,7 @@ static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_des
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                        const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr,
                        const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr, const fpng_amd_view_warp *warp = nullptr,
-                       const fpng_amd_view_tone *tone = nullptr)
+                       const fpng_amd_view_tone *tone = nullptr, const fpng_amd_view_enhance *enhance = nullptr)
 {
     if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
@@ -1486,7 +1491,7 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
             if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
             if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
         }
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post, warp, tone);
+    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post, warp, tone, enhance);
 }
 // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: the matrices are judged first -- a record per view, the sum of
 // the counts (those the views call refuses: its own message, below) -- then everything the views call judges
@@ -1540,18 +1545,26 @@ static_assert(sizeof(fpng_amd_view_post) == 32 && offsetof(fpng_amd_view_post, b
 int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_view_post *posts,
                             const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_warp *warps = nullptr,
-                            bool with_warps = false, const fpng_amd_view_tone *tones = nullptr, bool with_tones = false)
+                            bool with_warps = false, const fpng_amd_view_tone *tones = nullptr, bool with_tones = false, const fpng_amd_view_enhance *enhances = nullptr,
+                            bool with_enhances = false)
 {
     // with_warps: the _views_warp calls' -- the warp records are judged first, and posts may be NULL (no post flags).  with_tones: the
-    // _views_tone calls' -- the tone records are judged first, and posts and warps may each be NULL
-    if (with_tones && !tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones");
+    // _views_tone calls' -- the tone records are judged first, and posts and warps may each be NULL.  with_enhances: the _views_enhance
+    // calls' -- the enhance records are judged first, and tones may be NULL too
+    if (with_enhances && !enhances) return fail(FPNG_AMD_ERR_INVALID_ARG, "null enhances");
+    if (with_tones && !with_enhances && !tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones");
     if (with_warps && !with_tones && !warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps");
     if (!with_warps && !posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts");
     if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
     uint64_t total = 0;
     bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
-    bool any = false, any_warp = false, any_tone = false;
+    bool any = false, any_warp = false, any_tone = false, any_enhance = false;
+    for (uint32_t i = 0, v = 0; enhances && counts_ok && i < n; i++) // (the planes of a view's destination: its file's num_chans)
+        for (const uint32_t end = v + view_count[i]; v < end; v++) {
+            if (const char *why = check_enhance_record(enhances[v], files ? files[i].num_chans : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+            any_enhance |= enhances[v].op != 0;
+        }
     for (uint64_t v = 0; tones && counts_ok && v < total; v++) {
         if (const char *why = check_tone_record(tones[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
         any_tone |= tones[v].op != 0;
@@ -1567,11 +1580,12 @@ int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *file
     if (colors)
         if (int rc = check_color_records(colors, view_count, n)) return rc;
     // (no view with a flag: the colour call, or the plain one, enqueues what it always does; no warp flag: the post call does)
-    if (!any && !any_warp && !any_tone) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
+    if (!any && !any_warp && !any_tone && !any_enhance) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
     std::vector<fpng_amd_view_post> no_posts;
     if (!posts) no_posts.assign((size_t)total, fpng_amd_view_post{}), posts = no_posts.data();
     if (!any_warp) warps = nullptr;
-    if (!any_tone) tones = nullptr; // (no view with an op: what the warp call enqueues)
+    if (!any_tone) tones = nullptr;       // (no view with an op: what the warp call enqueues)
+    if (!any_enhance) enhances = nullptr; // (no view with an op: what the tone call enqueues)
     std::vector<fpng_amd_view_color> identity;
     if (!colors) {
         fpng_amd_view_color one = {};
@@ -1579,7 +1593,7 @@ int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *file
         identity.assign((size_t)total, one);
         colors = identity.data();
     }
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts, warps, tones);
+    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts, warps, tones, enhances);
 }
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
@@ -1805,6 +1819,48 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_tone(fpng_amd_encoder *e, 
                                                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
     return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true, tones, true);
+}
+
+extern "C" int fpng_amd_decode_batch_planar_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                          const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                          const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                          const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false, warps, true, tones, true, enhances, true);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                                 const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                                 const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                                 const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt,
+                                                                 fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true, warps, true, tones, true, enhances, true);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                       const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                       const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                       const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false, warps, true, tones, true, enhances, true);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                              const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                              const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                              const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt,
+                                                              fpng_amd_decode_result *results)
+{
+    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true, tones, true, enhances, true);
+}
+
+// the enhance rule on the host: the texts of view_enhance.h, which dec_view_post_kernel runs
+extern "C" int fpng_amd_view_enhance_apply(const fpng_amd_view_enhance *enhance, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out)
+{
+    const char *why = nullptr;
+    const int rc = enhance_apply_checked(enhance, w, h, in, out, &why);
+    return rc ? fail(rc, why) : FPNG_AMD_OK;
 }
 
 // the tone rule on the host: the texts of view_tone.h, which dec_view_tone_lut_kernel runs

@@ -17,6 +17,7 @@
 #pragma once
 #include "decode.h"
 #include "resize.h"
+#include "view_enhance.h"
 #include "view_tone.h"
 #include "view_warp.h"
 
@@ -67,15 +68,18 @@ struct DecViewPost {
     uint32_t *tone;
     uint32_t tone_op;
     float tone_factor;
+    // the _views_enhance calls' (view_enhance.h); enhance_op 0: none
+    uint32_t enhance_op;
+    float enhance_factor;
 };
-static_assert(sizeof(DecViewPost) == 256 && offsetof(DecViewPost, pitch) == 24 && offsetof(DecViewPost, k) == 68 && offsetof(DecViewPost, warp) == 136 &&
+static_assert(sizeof(DecViewPost) == 264 && offsetof(DecViewPost, enhance_op) == 256 && offsetof(DecViewPost, enhance_factor) == 260 && offsetof(DecViewPost, pitch) == 24 && offsetof(DecViewPost, k) == 68 && offsetof(DecViewPost, warp) == 136 &&
                   offsetof(DecViewPost, tone) == 240 && offsetof(DecViewPost, tone_factor) == 252,
               "DecViewPost layout");
 
 // An exact grid as launch_dec_resize_color's, a workgroup per (record, tile of kResizeTileW x kResizeTileH): pre / h_pre count TILES.
 // hwc: channels-last destinations.  mode 1: some record of the call has a warp (the instantiations that gather; 0: the post call's
-// own); mode 2: some record has a tone op (the instantiations that gather and apply a table).  false: a record without or with too
-// many tiles; nothing more is launched.
+// own); mode 2: some record has a tone op (the instantiations that gather and apply a table); mode 3: some record has an enhance op
+// (those that also blend against a degenerate image).  false: a record without or with too many tiles; nothing more is launched.
 bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, int mode = 0);
 
 // The tone views of a call, in the order of their post records: refs[t].rec is tone view t's record of `recs`, refs[t].pre the chunks

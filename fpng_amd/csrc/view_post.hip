@@ -21,6 +21,15 @@
 // calls.  They copy the view's three 256-byte tables, which dec_view_tone_lut_kernel has written into the scratch, into LDS (the
 // identity for a view of the call without an op) and look every sample up where the text above loads B or gathers W -- the halo
 // fill, the warp's halo fill and both R = 0 paths.  The fourth plane is not looked up.
+// A view with an ENHANCE op (the _views_enhance calls; view_enhance.h: the rule) reads E = blend(D, W'): the kMode == 3
+// instantiations run those calls, and do everything the kMode == 2 ones do.  BRIGHTNESS (D = 0) is composed into the tables as they
+// are copied into LDS.  COLOR (D = the sample's luma) needs the three planes of a sample together: stage 1 fills all three planes of
+// S in one sweep without a warp too, and both R = 0 paths are one that fetches a sample's three bytes.  SHARPNESS (D = SMOOTH, a
+// 3 x 3 filter) loads the tile with a halo of R + 1 -- S has rows of 98 bytes, 50 of them, here -- and one more pass per plane writes
+// E for the tile and a halo of R into a one-plane buffer behind the tables, rows of 96 bytes, out of which the horizontal pass
+// reads; with R = 0 E goes straight into the registers.  A sample of the halo is a frame sample by its reflected, TRUE coordinate.
+// With R = min(w, h) - 1 the outermost ring reflects to one past the window: its index is held inside (enhance_refl), for those
+// samples are neighbours of frame samples only, whose D does not read them.
 //   4. the store: a thread has all channels of its pixels; every element is stored on its own -- planar destinations as
 //      dec_resize_color_kernel's, lanes along a row of a plane; channels-last ones by element, position c or planes - 1 - c of the
 //      pixel, positions >= planes never written.
@@ -53,13 +62,16 @@ template <int kDtype> __device__ __forceinline__ void post_store(uint8_t *p, uin
     }
 }
 
-// kMode: 0 the post calls', 1 the warp calls' (gathers), 2 the tone calls' (gathers and applies a table)
+// kMode: 0 the post calls', 1 the warp calls' (gathers), 2 the tone calls' (gathers and applies a table), 3 the enhance calls' (gathers,
+// applies a table and blends against a degenerate image)
 template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResizeBlock) void dec_view_post_kernel(const DecViewPost *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
-    constexpr bool kWarp = kMode >= 1, kTone = kMode == 2;
-    constexpr uint32_t kHalo = kPostHaloH * kPostHaloW;
-    // the tile and its halo, rows of sw bytes (kWarp: per colour plane); kTone: behind them the view's tables, lut[c][v]
-    __shared__ __attribute__((aligned(16))) uint8_t S[(kWarp ? 3 : 1) * kHalo + (kTone ? kToneLutBytes : 0)];
+    constexpr bool kWarp = kMode >= 1, kTone = kMode >= 2, kEnh = kMode == 3;
+    constexpr uint32_t kSW = kPostHaloW + (kEnh ? 2 : 0), kSH = kPostHaloH + (kEnh ? 2 : 0); // (kEnh: sharpness reads one sample further)
+    constexpr uint32_t kHalo = kSH * kSW, kEHalo = kPostHaloH * kPostHaloW;
+    // the tile and its halo, rows of kSW bytes (kWarp: per colour plane); kTone: behind them the view's tables, lut[c][v]; kEnh: behind
+    // those E of one plane, the tile and the blur's halo, rows of kPostHaloW bytes
+    __shared__ __attribute__((aligned(16))) uint8_t S[(kWarp ? 3 : 1) * kHalo + (kTone ? kToneLutBytes : 0) + (kEnh ? kEHalo : 0)];
     __shared__ __attribute__((aligned(16))) uint8_t Hb[kPostHaloH * kResizeTileW]; // the horizontal pass: rows of kResizeTileW bytes
     __shared__ int32_t K[kPostMaxRadius + 1];                                   // k[d]: taps -d and d share it
     const uint64_t g = pre[0] + blockIdx.x;
@@ -87,7 +99,15 @@ template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResize
     uint8_t *const T = S + (kTone ? 3 * kHalo : 0u); // (kTone only)
     if constexpr (kTone) {
         const uint8_t *const lut = r.tone_op ? (const uint8_t *)(r.tone + kToneHistWords) : nullptr;
-        for (uint32_t k = tid; k < kToneLutBytes; k += kResizeBlock) T[k] = lut ? lut[k] : (uint8_t)k;
+        if constexpr (kEnh) { // (BRIGHTNESS: a point operation behind the table's)
+            const bool bright = r.enhance_op == kEnhanceBrightness;
+            const float f = r.enhance_factor;
+            for (uint32_t k = tid; k < kToneLutBytes; k += kResizeBlock) {
+                const uint32_t t = lut ? lut[k] : k & 255u;
+                T[k] = (uint8_t)(bright ? enhance_blend(0u, t, f) : t);
+            }
+        } else
+            for (uint32_t k = tid; k < kToneLutBytes; k += kResizeBlock) T[k] = lut ? lut[k] : (uint8_t)k;
         __syncthreads();
     }
     // (the byte of W' for the byte b of plane p of W)
@@ -95,7 +115,106 @@ template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResize
         if constexpr (kTone) return T[p * 256 + b];
         else return b;
     };
-    if (R) {
+    if constexpr (kEnh) {
+        const uint32_t eop = r.enhance_op, np = std::min(C, 3u);
+        const float ef = r.enhance_factor;
+        const uint32_t X = eop == kEnhanceSharpness && enhance_sharpens(w, h) ? 1u : 0u, Rh = R + X; // (the halo that stage 1 loads)
+        uint8_t *const Eb = T + kToneLutBytes;
+        // the bytes of E -- but for SHARPNESS: of W' -- of the sample (x, y) of the window, true coordinates, in planes 0 .. np - 1
+        const auto sample3 = [&](uint32_t x, uint32_t y, uint32_t v[3]) {
+            if (wflags) {
+                const WarpAt at = warp_locate(r.warp, x, y, w, h, mirror);
+#pragma unroll
+                for (uint32_t p = 0; p < 3; p++) v[p] = p < np ? T[p * 256 + warp_sample(at, wflags, r.src + p * plane_bytes, w, r.warp.fill[p])] : 0u;
+            } else {
+#pragma unroll
+                for (uint32_t p = 0; p < 3; p++) v[p] = p < np ? T[p * 256 + r.src[p * plane_bytes + (uint64_t)y * w + x]] : 0u;
+            }
+            if (eop == kEnhanceColor && np == 3) {
+                const uint32_t luma = tone_luma(v[0], v[1], v[2]);
+#pragma unroll
+                for (uint32_t p = 0; p < 3; p++) v[p] = enhance_blend(luma, v[p], ef);
+            }
+        };
+        // E of the sample at c of a plane of S whose true coordinates are (tx, ty) (X only)
+        const auto sharp = [&](const uint8_t *c, uint32_t tx, uint32_t ty) -> uint32_t { return enhance_on_frame(tx, ty, w, h) ? c[0] : enhance_sharp_at(c, (int32_t)kSW, ef); };
+        if (Rh) {
+            if (R && tid <= R) K[tid] = r.k[tid];
+            const uint32_t sw = nw + 2 * Rh, sh = nq + 2 * Rh; // (<= kSW, kSH)
+            // ---- 1. the tile and its halo, all colour planes of a sample at once ----
+            for (uint32_t j = wave; j < sh; j += kWaves) {
+                const uint32_t y = enhance_refl((int32_t)(oq0 + j) - (int32_t)Rh, h);
+                for (uint32_t i = o; i < sw; i += kResizeTileW) {
+                    uint32_t v[3];
+                    sample3(enhance_refl((int32_t)(ox0 + i) - (int32_t)Rh, w), y, v);
+#pragma unroll
+                    for (uint32_t p = 0; p < 3; p++)
+                        if (p < np) S[p * kHalo + j * kSW + i] = (uint8_t)v[p];
+                }
+            }
+            __syncthreads();
+            for (uint32_t plane = 0; plane < np; plane++) {
+                const uint8_t *const Sp = S + plane * kHalo;
+                const uint8_t *from = Sp; // (what the horizontal pass reads: rows of `stride` bytes, the tile and a halo of R)
+                uint32_t stride = kSW;
+                if (X && !R) { // ---- 1b. E into the registers, the point operations ----
+                    if (o < nw) {
+#pragma unroll
+                        for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                            const uint32_t q = wave + k * kWaves;
+                            if (q >= nq) break;
+                            res[k] |= post_point(sharp(Sp + (q + 1) * kSW + o + 1, ox0 + o, oq0 + q), flags, threshold, bits) << (8 * plane);
+                        }
+                    }
+                    continue;
+                }
+                if (X) { // ---- 1b. E of the tile and a halo of R (the plane before has been read out of Eb: a barrier since) ----
+                    for (uint32_t j = wave; j < nq + 2 * R; j += kWaves) {
+                        const uint32_t ty = post_refl((int32_t)(oq0 + j) - (int32_t)R, h);
+                        for (uint32_t i = o; i < nw + 2 * R; i += kResizeTileW)
+                            Eb[j * kPostHaloW + i] = (uint8_t)sharp(Sp + (j + 1) * kSW + i + 1, post_refl((int32_t)(ox0 + i) - (int32_t)R, w), ty);
+                    }
+                    from = Eb, stride = kPostHaloW;
+                    __syncthreads(); // (and the plane before has been read out of Hb)
+                } else if (plane)
+                    __syncthreads(); // (the plane before has been read out of Hb)
+                // ---- 2. the horizontal pass ----
+                if (o < nw)
+                    for (uint32_t j = wave; j < nq + 2 * R; j += kWaves) {
+                        const uint8_t *const s = from + j * stride + o + R;
+                        int32_t sum = (1 << (kResizeBits - 1)) + (int32_t)s[0] * K[0];
+#pragma unroll 4
+                        for (uint32_t d = 1; d <= R; d++) sum += ((int32_t)s[-(int32_t)d] + (int32_t)s[d]) * K[d];
+                        Hb[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
+                    }
+                __syncthreads();
+                // ---- 3. the vertical pass, the point operations ----
+                if (o < nw) {
+#pragma unroll
+                    for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                        const uint32_t q = wave + k * kWaves;
+                        if (q >= nq) break;
+                        const uint8_t *const s = Hb + (q + R) * kResizeTileW + o;
+                        int32_t sum = (1 << (kResizeBits - 1)) + (int32_t)s[0] * K[0];
+#pragma unroll 4
+                        for (uint32_t d = 1; d <= R; d++) sum += ((int32_t)s[-(int32_t)(d * kResizeTileW)] + (int32_t)s[d * kResizeTileW]) * K[d];
+                        res[k] |= post_point(resize_clip8(sum), flags, threshold, bits) << (8 * plane);
+                    }
+                }
+            }
+        } else if (o < nw) {
+#pragma unroll
+            for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                const uint32_t q = wave + k * kWaves;
+                if (q >= nq) break;
+                uint32_t v[3];
+                sample3(ox0 + o, oq0 + q, v);
+#pragma unroll
+                for (uint32_t p = 0; p < 3; p++)
+                    if (p < np) res[k] |= post_point(v[p], flags, threshold, bits) << (8 * p);
+            }
+        }
+    } else if (R) {
         if (tid <= R) K[tid] = r.k[tid];
         const uint32_t sw = nw + 2 * R, sh = nq + 2 * R; // (<= kPostHaloW, kPostHaloH)
         for (uint32_t plane = 0; plane < C && plane < 3; plane++) {
@@ -166,7 +285,7 @@ template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResize
     }
     if (o >= nw) return; // (no barrier behind this line)
     if (C == 4 && kWarp && wflags) {
-        if (R) { // (without blur: gathered above)
+        if (R || kEnh) { // (without blur: gathered above -- but for the enhance calls')
 #pragma unroll
             for (uint32_t k = 0; k < kRowsPerWave; k++) {
                 const uint32_t q = wave + k * kWaves;
@@ -214,14 +333,16 @@ template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResize
 bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, int mode)
 {
     using Kernel = void (*)(const DecViewPost *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[3][2][kDecFloatTypes + 1] = {
+    static const Kernel kernels[4][2][kDecFloatTypes + 1] = {
         {{dec_view_post_kernel<-1, false, 0>, dec_view_post_kernel<0, false, 0>, dec_view_post_kernel<1, false, 0>, dec_view_post_kernel<2, false, 0>},
          {dec_view_post_kernel<-1, true, 0>, dec_view_post_kernel<0, true, 0>, dec_view_post_kernel<1, true, 0>, dec_view_post_kernel<2, true, 0>}},
         {{dec_view_post_kernel<-1, false, 1>, dec_view_post_kernel<0, false, 1>, dec_view_post_kernel<1, false, 1>, dec_view_post_kernel<2, false, 1>},
          {dec_view_post_kernel<-1, true, 1>, dec_view_post_kernel<0, true, 1>, dec_view_post_kernel<1, true, 1>, dec_view_post_kernel<2, true, 1>}},
         {{dec_view_post_kernel<-1, false, 2>, dec_view_post_kernel<0, false, 2>, dec_view_post_kernel<1, false, 2>, dec_view_post_kernel<2, false, 2>},
-         {dec_view_post_kernel<-1, true, 2>, dec_view_post_kernel<0, true, 2>, dec_view_post_kernel<1, true, 2>, dec_view_post_kernel<2, true, 2>}}};
-    if (mode < 0 || mode > 2) return false;
+         {dec_view_post_kernel<-1, true, 2>, dec_view_post_kernel<0, true, 2>, dec_view_post_kernel<1, true, 2>, dec_view_post_kernel<2, true, 2>}},
+        {{dec_view_post_kernel<-1, false, 3>, dec_view_post_kernel<0, false, 3>, dec_view_post_kernel<1, false, 3>, dec_view_post_kernel<2, false, 3>},
+         {dec_view_post_kernel<-1, true, 3>, dec_view_post_kernel<0, true, 3>, dec_view_post_kernel<1, true, 3>, dec_view_post_kernel<2, true, 3>}}};
+    if (mode < 0 || mode > 3) return false;
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     for (uint32_t r0 = 0; r0 < n;) {

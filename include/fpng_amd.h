@@ -1014,7 +1014,7 @@ int fpng_amd_view_warp_apply(const fpng_amd_view_warp *warp, uint32_t w, uint32_
  *      the window's bytes (through the warp's gather where there is one) into uint32[4][256] of the decode scratch, zeroed on the
  *      stream in front of it, and dec_view_tone_lut_kernel writes the view's uint8[3][256] tables; the post stage applies them
  *      wherever it loads a sample, the blur's reflected halo included.
- *      Not offered: Sharpness (a 3 x 3 filter, not a statistic); two tone operations on one view; autocontrast's cutoff, ignore
+ *      Not offered: two tone operations on one view (Sharpness is the enhance record's, below); autocontrast's cutoff, ignore
  *      and preserve_tone; aarch64 Pillow's fused blend; a tone record in fpng_amd_decode_host or the fpng:: drop-in.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_tone with dlsym. ---- */
 #define FPNG_AMD_TONE_AUTOCONTRAST 1
@@ -1050,6 +1050,82 @@ int fpng_amd_decode_batch_device_hwc_views_tone(fpng_amd_encoder *enc, const fpn
 int fpng_amd_view_tone_lut(const fpng_amd_view_tone *tone, const uint32_t hist[4 * 256], uint8_t lut[3 * 256]);
 /* the whole stage for ONE view (no GPU): in is W, three planes of w x h bytes one behind the other; out is W' */
 int fpng_amd_view_tone_apply(const fpng_amd_view_tone *tone, uint32_t w, uint32_t h, const uint8_t *in /* 3 planes */, uint8_t *out /* 3 planes */);
+/* ---- the tone call with an ENHANCE record per view behind the tone record: Brightness, Color and Sharpness of RandAugment /
+ *      TrivialAugment / AutoAugment -- on a PIL image ImageEnhance.Brightness(img), ImageEnhance.Color(img) and
+ *      ImageEnhance.Sharpness(img).enhance(factor), the first two also ColorJitter's -- drawn per view by the caller.  Each is
+ *      Pillow's ImagingBlend of a DEGENERATE image and the view.  (The colour matrix offers brightness and saturation too, but
+ *      rounds where Pillow truncates and blends against no byte-rounded grey image: it is not bit-exact to these.)  The argument
+ *      lists are those of the _views_tone calls with `enhances`, a record per view, behind `tones`; colors, posts, warps and tones
+ *      may each be NULL; enhances may not.
+ *      THE RULE (every element is exact).  A view whose op is 0 is written bit for bit as the _views_tone call writes it.  A view
+ *      with an op is a post view whatever its other flags, and the enhance stage sits behind the tone stage and in front of the
+ *      blur, solarize and posterize:
+ *        W' is what the tone stage hands on: W itself for a view without a tone op.  Only planes 0, 1, 2 take part: a fourth plane
+ *          skips the stage, as it skips every other one.
+ *        E_c = blend(D_c, W'_c, factor) with `factor` fp32, finite and >= 0, and blend(d, v, f) the CONTRAST entry of the tone rule
+ *          with d in the place of the mean, in fp32 with every operation rounded on its own, no contraction:
+ *              t = (float)d + f * (float)((int)v - (int)d)
+ *              0 <= f <= 1: (uint8_t)t, truncating;  else: 0 if t <= 0, 255 if t >= 255, (uint8_t)t in between
+ *          -- Pillow's ImagingBlend as an x86-64 build computes it.  f == 1 gives v.
+ *        BRIGHTNESS: D_c = 0 (a point operation per channel: a 256-entry table).
+ *        COLOR: D_c = L = (19595 W'_0 + 38470 W'_1 + 7471 W'_2 + 0x8000) >> 16, Pillow's convert("L"), for all three channels.
+ *        SHARPNESS: D_c is ImageFilter.SMOOTH of plane c of W' over the un-mirrored w x h window.  w < 3 or h < 3: the stage is the
+ *          identity.  A sample on the window's outer frame (x = 0, x = w - 1, y = 0 or y = h - 1): D = W', so the blend returns W'
+ *          for every factor.  An interior sample: S = the sum of its 3 x 3 neighbourhood + 4 x the centre (kernel 1 1 1 / 1 5 1 /
+ *          1 1 1) and D = (2 S + 13) / 26, floored, in integers.  Pillow sums the nine products in fp32 with weights (float)(k / 13),
+ *          adds 0.5 and truncates; S / 13 + 0.5 is an odd multiple of 1 / 26, never within 0.038 of an integer, and the fp32 sum
+ *          is off by less than 0.001 in any order, so the integer form is exact.  The kernel is symmetric: sharpening the
+ *          un-mirrored window and mirroring at the store equals sharpening the mirrored image, and the blur's reflected halo
+ *          carries on from E, because E[refl(y)][refl(x)] is what sharpening the reflected neighbourhood gives ("a frame sample"
+ *          judged on the reflected, true coordinate).
+ *        Steps 2 to 4 of the post rule, the conversion, the mirror and the store then run on E.  The tone histograms are counted
+ *          in front of this stage: they are W's.
+ *      GUARANTEES: a record with op == 0 leaves its view bit for bit the _views_tone call's; a call in which no record has an op
+ *      enqueues exactly what the _views_tone call enqueues; factor == 1 gives W' bit for bit, for all three ops; for a file with
+ *      status 0 a view depends only on (file, crop, view, colour, warp, tone, enhance, post, fmt); only the spans the views call
+ *      writes are written; statuses are the views call's.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null enhances; an unknown op; a
+ *      non-zero reserved word; a factor that is not finite or is negative with an op; a non-zero factor (a NaN is not 0) without
+ *      one; COLOR on a destination of fewer than 3 planes; and everything the tone call refuses.
+ *      A call with an op runs the post stage's fourth set of instantiations (the first three are untouched): BRIGHTNESS is composed
+ *      into the tone tables in LDS, COLOR blends the three planes of a sample behind the look-up, SHARPNESS loads the tile with a
+ *      halo one wider than the blur's and filters it in LDS.
+ *      Not offered: two enhance operations on one view; an enhance operation in front of the tone operation; aarch64 Pillow's
+ *      fused blend; an enhance record in fpng_amd_decode_host or the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_enhance with dlsym. ---- */
+#define FPNG_AMD_ENHANCE_BRIGHTNESS 1
+#define FPNG_AMD_ENHANCE_COLOR 2
+#define FPNG_AMD_ENHANCE_SHARPNESS 3
+typedef struct fpng_amd_view_enhance {
+    uint32_t op;           /* FPNG_AMD_ENHANCE_*; 0 = none: this view is the tone call's, untouched */
+    float factor;          /* with an op: finite, >= 0 (1 = the identity); else 0 */
+    uint32_t reserved[2];  /* 0 */
+} fpng_amd_view_enhance;   /* 16 bytes */
+int fpng_amd_decode_batch_planar_views_enhance(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                               const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                               const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                               const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                               const fpng_amd_view_tone *tones /* the same, or NULL */, const fpng_amd_view_enhance *enhances /* the same */,
+                                               const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_enhance(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                      const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                      const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                      const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt,
+                                                      fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_enhance(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                            const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                            const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                            const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                            const fpng_amd_view_tone *tones /* the same, or NULL */, const fpng_amd_view_enhance *enhances /* the same */,
+                                            const fpng_amd_float_format *fmt /* NULL: uint8 */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_enhance(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                   const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                   const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                   const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt,
+                                                   fpng_amd_decode_result *results);
+/* the whole stage for ONE view (no GPU): in is W', three planes of w x h bytes one behind the other; out is E.  The text that the
+ * kernel runs.  The record is judged as the calls judge it (op 0: a copy) */
+int fpng_amd_view_enhance_apply(const fpng_amd_view_enhance *enhance, uint32_t w, uint32_t h, const uint8_t *in /* 3 planes */, uint8_t *out /* 3 planes */);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

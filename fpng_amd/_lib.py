@@ -247,61 +247,9 @@ SIGNATURES = {
     "fpng_amd_decode_batch_device_planar_resize_view": (_int, [_vp, C.POINTER(PngPlanarIn), C.POINTER(Crop), C.POINTER(ResizeView), _u32, C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_resize_weights_filter": (_int, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_int32)]),
     "fpng_amd_resize_view_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(Crop)]),
-    "fpng_amd_decode_batch_planar_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                  C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_planar_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                         C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_hwc_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                               C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_hwc_views": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                      C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_planar_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                        C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_planar_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                               C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_hwc_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                     C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_hwc_views_color": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                            C.POINTER(ViewColor), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_planar_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                       C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_planar_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                              C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_hwc_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                    C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_hwc_views_post": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                           C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_planar_views_warp": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                       C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_planar_views_warp": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                                              C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_hwc_views_warp": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                    C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_hwc_views_warp": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                                           C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_view_warp_apply": (_int, [C.POINTER(ViewWarp), _u32, _u32, _u32, C.c_void_p, C.c_void_p, C.c_uint8]),
-    "fpng_amd_decode_batch_planar_views_tone": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_planar_views_tone": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_hwc_views_tone": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_hwc_views_tone": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(FloatFormat), C.POINTER(DecodeResult)]),
     "fpng_amd_view_tone_lut": (_int, [C.POINTER(ViewTone), C.c_void_p, C.c_void_p]),
     "fpng_amd_view_tone_apply": (_int, [C.POINTER(ViewTone), _u32, _u32, C.c_void_p, C.c_void_p]),
-    "fpng_amd_decode_batch_planar_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
-                                            C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_planar_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDest),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
-                                            C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_hwc_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
-                                            C.POINTER(DecodeResult)]),
-    "fpng_amd_decode_batch_device_hwc_views_enhance": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewDestHwc),
-                                            C.POINTER(ViewColor), C.POINTER(ViewPost), C.POINTER(ViewWarp), C.POINTER(ViewTone), C.POINTER(ViewEnhance), C.POINTER(FloatFormat),
-                                            C.POINTER(DecodeResult)]),
     "fpng_amd_view_enhance_apply": (_int, [C.POINTER(ViewEnhance), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_blur_weights": (_int, [_u32, C.c_double, C.POINTER(C.c_int32 * 17)]),
     "fpng_amd_view_post_apply": (_int, [C.POINTER(ViewPost), _u32, _u32, C.c_void_p, C.c_void_p]),
@@ -323,6 +271,24 @@ SIGNATURES = {
     "fpng_amd_encoder_lanes": (_u32, [_vp]),
     "fpng_amd_release_cached_memory": (_int, []),
 }
+
+# The views calls: fpng_amd_decode_batch(_device)_{planar,hwc}_views<suffix>.  A stage's call takes the record arrays of every stage up
+# to and including its own, in this order, between the destinations and the float format.
+VIEW_STAGES = (("_color", ViewColor), ("_post", ViewPost), ("_warp", ViewWarp), ("_tone", ViewTone), ("_enhance", ViewEnhance))
+VIEW_LAYOUTS = (("planar", ViewDest), ("hwc", ViewDestHwc))
+
+
+def views_symbol(layout, device_data, stages):
+    """the name of the views call of `layout` ("planar" / "hwc") for files in device or host memory that takes the first `stages`
+    record arrays of VIEW_STAGES"""
+    return f"fpng_amd_decode_batch{'_device' if device_data else ''}_{layout}_views{VIEW_STAGES[stages - 1][0] if stages else ''}"
+
+
+for _layout, _dest in VIEW_LAYOUTS:
+    for _stages in range(len(VIEW_STAGES) + 1):
+        for _device in (False, True):
+            SIGNATURES[views_symbol(_layout, _device, _stages)] = (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(_dest)] +
+                                                                  [C.POINTER(rec) for _, rec in VIEW_STAGES[:_stages]] + [C.POINTER(FloatFormat), C.POINTER(DecodeResult)])
 
 _lib = None
 

@@ -551,35 +551,6 @@ def view_post(blur=None, solarize=None, posterize=None):
     return rec
 
 
-def _post_records(who, counts, post):
-    """the post= argument of the views calls -> fpng_amd_view_post[sum(counts)]: one record (view_post() makes them) for all views, a
-    list with one per file, or a list per file of a list per view"""
-    total = sum(counts)
-    arr = (_lib.ViewPost * max(total, 1))()
-
-    def put(at, rec):
-        if not isinstance(rec, _lib.ViewPost):
-            raise ValueError(f"{who}: a post record is what view_post() returns, not {type(rec).__name__}")
-        C.memmove(C.byref(arr, at * C.sizeof(_lib.ViewPost)), C.byref(rec), C.sizeof(_lib.ViewPost))
-
-    if isinstance(post, _lib.ViewPost):
-        for at in range(total):
-            put(at, post)
-        return arr
-    if not hasattr(post, "__len__") or len(post) != len(counts):
-        raise ValueError(f"{who}: post is one view_post() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
-    at = 0
-    for i, (c, recs) in enumerate(zip(counts, post)):
-        if isinstance(recs, _lib.ViewPost):
-            recs = [recs] * c
-        if not hasattr(recs, "__len__") or len(recs) != c:
-            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} post records")
-        for rec in recs:
-            put(at, rec)
-            at += 1
-    return arr
-
-
 _WARP_FILTERS = {"nearest": _lib.WARP_AFFINE, "bilinear": _lib.WARP_AFFINE | _lib.WARP_BILINEAR}
 
 
@@ -613,34 +584,6 @@ def view_warp(matrix=None, filter="nearest", fill=0):
     for k in range(4):
         rec.fill[k] = int(fills[k])
     return rec
-
-
-def _warp_records(who, counts, warp):
-    """the warp= argument of the views calls -> fpng_amd_view_warp[sum(counts)]: nested as _post_records' argument"""
-    total = sum(counts)
-    arr = (_lib.ViewWarp * max(total, 1))()
-
-    def put(at, rec):
-        if not isinstance(rec, _lib.ViewWarp):
-            raise ValueError(f"{who}: a warp record is what view_warp() returns, not {type(rec).__name__}")
-        C.memmove(C.byref(arr, at * C.sizeof(_lib.ViewWarp)), C.byref(rec), C.sizeof(_lib.ViewWarp))
-
-    if isinstance(warp, _lib.ViewWarp):
-        for at in range(total):
-            put(at, warp)
-        return arr
-    if not hasattr(warp, "__len__") or len(warp) != len(counts):
-        raise ValueError(f"{who}: warp is one view_warp() record for all views, or a list with an entry per file ({len(counts)}), each one record or a list of one per view")
-    at = 0
-    for i, (c, recs) in enumerate(zip(counts, warp)):
-        if isinstance(recs, _lib.ViewWarp):
-            recs = [recs] * c
-        if not hasattr(recs, "__len__") or len(recs) != c:
-            raise ValueError(f"{who}: file {i} has {c} views, not {len(recs) if hasattr(recs, '__len__') else 1} warp records")
-        for rec in recs:
-            put(at, rec)
-            at += 1
-    return arr
 
 
 def view_warp_apply(warp, plane, mirror=False, fill=None):
@@ -708,15 +651,16 @@ def view_tone(autocontrast=False, equalize=False, contrast=None):
     return rec
 
 
-def _view_records(who, counts, arg, cls, noun):
-    """the `noun`= argument of the views calls -> cls[sum(counts)]: one record (view_<noun>() makes them) for all views, a list with
-    one per file, or a list per file of one per view"""
+def _view_records(who, counts, arg, cls, noun, wrong=None):
+    """the `noun`= argument of the views calls (post, warp, tone, enhance) -> cls[sum(counts)]: one record (view_<noun>() makes them)
+    for all views, a list with one per file, or a list per file of one per view.  wrong: what to say of an entry that is no such
+    record, where the argument has a wording of its own"""
     total = sum(counts)
     arr = (cls * max(total, 1))()
 
     def put(at, rec):
         if not isinstance(rec, cls):
-            raise ValueError(f"{who}: {noun} takes what view_{noun}() returns, not {type(rec).__name__}")
+            raise ValueError(f"{who}: {wrong or f'{noun} takes what view_{noun}() returns'}, not {type(rec).__name__}")
         C.memmove(C.byref(arr, at * C.sizeof(cls)), C.byref(rec), C.sizeof(cls))
 
     if isinstance(arg, cls):
@@ -735,11 +679,6 @@ def _view_records(who, counts, arg, cls, noun):
             put(at, rec)
             at += 1
     return arr
-
-
-def _tone_records(who, counts, tone):
-    """the tone= argument of the views calls -> fpng_amd_view_tone[sum(counts)]: nested as _post_records' argument"""
-    return _view_records(who, counts, tone, _lib.ViewTone, "tone")
 
 
 def view_tone_lut(tone, hist):
@@ -791,11 +730,6 @@ def view_enhance(brightness=None, color=None, sharpness=None):
             raise ValueError(f"view_enhance: {name} is finite and >= 0, not {f}")
         rec.op, rec.factor = op, factor
     return rec
-
-
-def _enhance_records(who, counts, enhance):
-    """the enhance= argument of the views calls -> fpng_amd_view_enhance[sum(counts)]: nested as _post_records' argument"""
-    return _view_records(who, counts, enhance, _lib.ViewEnhance, "enhance")
 
 
 def view_enhance_apply(enhance, planes):
@@ -1210,7 +1144,25 @@ class DecodeBatchResizeView(_DecodeBatchViews):
         self.crops, self.views, self.fmt = crops, views, fmt
 
 
-class DecodeBatchMultiView(_DecodeBatchViews):
+class _DecodeBatchMultiViews(_DecodeBatchViews):
+    """what the descriptors of the views calls share, whatever the destinations' layout"""
+
+    colors = None
+    posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
+    warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
+    tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
+    enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
+        super().__init__(pngs, outs, arr, res, device_data, keep)
+        self.counts, self.crops, self.views, self.dests, self.fmt = counts, crops, views, dests, fmt
+
+    def results(self):
+        """list, per file, of (status, the list of the caller's own destination views (filled in place) or None, channels_in_file)"""
+        return [(r.status, list(ts) if r.status == 0 else None, r.channels_in_file) for r, ts in zip(self.res, self.outs)]
+
+
+class DecodeBatchMultiView(_DecodeBatchMultiViews):
     """What Encoder.make_decode_batch_views() returns: the same for one fpng_amd_decode_batch(_device)_planar_views() call, which
     writes SEVERAL views of each file (counts: the uint32[n] views per file; crops, views, dests: the fpng_amd_crop,
     fpng_amd_resize_view and fpng_amd_view_dest records, one per view, file 0's first; outs: per file the list of the caller's (c,
@@ -1218,40 +1170,130 @@ class DecodeBatchMultiView(_DecodeBatchViews):
     other call takes this descriptor.  colors: the fpng_amd_view_color records of a descriptor made with color=, one per view (the
     call is then fpng_amd_decode_batch(_device)_planar_views_color), else None."""
 
-    colors = None
-    posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
-    warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
-    tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
-    enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
-
-    def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.counts, self.crops, self.views, self.dests, self.fmt = counts, crops, views, dests, fmt
-
-    def results(self):
-        """list, per file, of (status, the list of the caller's own destination views (filled in place) or None, channels_in_file)"""
-        return [(r.status, list(ts) if r.status == 0 else None, r.channels_in_file) for r, ts in zip(self.res, self.outs)]
 
 
-class DecodeBatchMultiViewHwc(_DecodeBatchViews):
+class DecodeBatchMultiViewHwc(_DecodeBatchMultiViews):
     """What Encoder.make_decode_batch_views_hwc() returns: DecodeBatchMultiView's twin for one
     fpng_amd_decode_batch(_device)_hwc_views() call (dests: the fpng_amd_view_dest_hwc records; outs: per file the list of the
     caller's (window h, window w, c) views; colors: as DecodeBatchMultiView's, for fpng_amd_decode_batch(_device)_hwc_views_color).
     No other call takes this descriptor."""
 
-    colors = None
-    posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
-    warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
-    tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
-    enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
 
-    def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.counts, self.crops, self.views, self.dests, self.fmt = counts, crops, views, dests, fmt
+def _planar_view_dest(rec, t, order, bottom_up, is_u8):
+    """the fpng_amd_view_dest of a (c, h, w) view; -> the float format's dtype code, or None"""
+    if is_u8:
+        (ptr, rp, pp), code = dest_layout_planar(t, order, bottom_up), None
+    else:
+        ptr, rp, pp, code = dest_layout_float(t, order, bottom_up)
+    c, oh, ow = t.shape
+    rec.d_pixels, rec.row_pitch, rec.plane_pitch = ptr, rp, pp
+    rec.pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
+    return code
 
-    def results(self):
-        """list, per file, of (status, the list of the caller's own destination views (filled in place) or None, channels_in_file)"""
-        return [(r.status, list(ts) if r.status == 0 else None, r.channels_in_file) for r, ts in zip(self.res, self.outs)]
+
+def _hwc_view_dest(rec, t, order, bottom_up, is_u8):
+    """the fpng_amd_view_dest_hwc of an (h, w, c) view; -> the float format's dtype code, or None"""
+    ptr, rp, px, flags, code = dest_layout_hwc(t, order, bottom_up)
+    oh, ow, c = t.shape
+    rec.d_pixels, rec.row_pitch, rec.pixel_elems, rec.flags = ptr, rp, px, flags
+    rec.pixels_cap = (oh - 1) * abs(rp) + ((ow - 1) * px + c) * t.element_size()  # (the view's own spans, in bytes)
+    return code
+
+
+class _ViewsLayout:
+    """What the views calls' two destination layouts differ in.  name: the layout's part of the C symbols; suffix: of the Python
+    methods; dest_cls, batch_cls: the destination record and the descriptor; put_dest: writes a tensor view's destination record
+    (its layout function and pixels_cap formula); chw: a view's shape as (c, h, w); empty_shape: of an allocated (oh, ow) output."""
+
+    def __init__(self, name, suffix, dest_cls, batch_cls, put_dest, chw, empty_shape):
+        self.name, self.suffix, self.dest_cls, self.batch_cls, self.put_dest, self.chw, self.empty_shape = name, suffix, dest_cls, batch_cls, put_dest, chw, empty_shape
+        self.maker, self.host, self.device = f"make_decode_batch_views{suffix}", f"decode_batch_views{suffix}", f"decode_device_views{suffix}"
+
+
+_PLANAR_VIEWS = _ViewsLayout("planar", "", _lib.ViewDest, DecodeBatchMultiView, _planar_view_dest, lambda s: (s[0], s[1], s[2]), lambda oh, ow: (3, oh, ow))
+_HWC_VIEWS = _ViewsLayout("hwc", "_hwc", _lib.ViewDestHwc, DecodeBatchMultiViewHwc, _hwc_view_dest, lambda s: (s[2], s[0], s[1]), lambda oh, ow: (oh, ow, 3))
+
+
+def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance):
+    """the descriptor of a views call for either layout (Encoder.make_decode_batch_views / _hwc have the rules)"""
+    who = layout.maker
+    n = len(pngs)
+    if len(crops) != n or len(outs) != n:
+        raise ValueError(f"{who}: {n} files, {len(crops)} lists of crops, {len(outs)} lists of destinations")
+    crops, outs = [list(c) for c in crops], [list(o) for o in outs]
+    counts = [len(c) for c in crops]
+    for i in range(n):
+        if counts[i] < 1 or len(outs[i]) != counts[i]:
+            raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
+    fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
+    filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
+    dtypes = {t.dtype for ts in outs for t in ts if isinstance(t, torch.Tensor)}
+    if len(dtypes) > 1:
+        raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+    is_u8 = dtypes == {torch.uint8}
+    fmt = None
+    if is_u8:
+        if any(v is not None for v in (mean, std, scale, bias)):
+            raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
+    else:
+        sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
+        fmt = _lib.FloatFormat()
+        for k in range(4):
+            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+    orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
+    device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+    total = sum(counts)
+    arr = (_lib.PngPlanarIn * n)()
+    narr = (C.c_uint32 * n)(*counts)
+    carr, varr, darr = (_lib.Crop * total)(), (_lib.ResizeView * total)(), (layout.dest_cls * total)()
+    res = (_lib.DecodeResult * n)()
+    keep = []
+    at = 0
+    for i, p in enumerate(pngs):
+        if device_data:
+            if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
+            arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+        else:
+            b = np.frombuffer(bytes(p), dtype=np.uint8)
+            keep.append(b)
+            arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+        codes = [layout.put_dest(darr[at + k], t, orders[i][k], bool(ups[i][k]), is_u8) for k, t in enumerate(outs[i])]
+        chans = {layout.chw(t.shape)[0] for t in outs[i]}
+        if len(chans) != 1:
+            raise ValueError(f"{who}: the destinations of file {i} share one channel count, not {sorted(chans)}")
+        arr[i].num_chans = chans.pop()  # (d_pixels, the pitches and pixels_cap stay NULL / 0: the destinations are the views')
+        for k, t in enumerate(outs[i]):
+            if codes[k] is not None:
+                fmt.dtype = codes[k]
+            _crop_record(f"{who}: file {i}", crops[i][k], carr[at])
+            v = _view_record(who, fulls[i][k], windows[i][k], filters[i][k], bool(mirrors[i][k]), varr[at])
+            _, oh, ow = layout.chw(t.shape)
+            if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
+                raise ValueError(f"{who}: destination {k} of file {i} is {ow} x {oh}, its window {v.w} x {v.h}")
+            at += 1
+    batch = layout.batch_cls(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
+    if color is not None:
+        batch.colors = _color_records(who, counts, color)
+    if post is not None:
+        batch.posts = _view_records(who, counts, post, _lib.ViewPost, "post", "a post record is what view_post() returns")
+    if warp is not None:
+        batch.warps = _view_records(who, counts, warp, _lib.ViewWarp, "warp", "a warp record is what view_warp() returns")
+    if tone is not None:
+        batch.tones = _view_records(who, counts, tone, _lib.ViewTone, "tone")
+    if enhance is not None:
+        batch.enhances = _view_records(who, counts, enhance, _lib.ViewEnhance, "enhance")
+    return batch
+
+
+def views_entry(layout, device_data, batch):
+    """The C entry point of a views call and its arguments behind the encoder, as a pure function of the layout ("planar" / "hwc"),
+    where the files are and the descriptor: the last stage in the order colour < post < warp < tone < enhance whose records the
+    descriptor carries names the call, and the call takes the record arrays of all stages up to it (None for those not given)."""
+    arrays = [batch.colors, batch.posts, batch.warps, batch.tones, batch.enhances]
+    stages = max((k + 1 for k, a in enumerate(arrays) if a is not None), default=0)
+    fmt = C.byref(batch.fmt) if batch.fmt is not None else None
+    return _lib.views_symbol(layout, device_data, stages), [batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, *arrays[:stages], fmt, batch.res]
 
 
 class Encoder:
@@ -2148,119 +2190,37 @@ class Encoder:
         fpng_amd_decode_batch(_device)_planar_views_tone, with the others' records or without.  enhance: None, or the views' enhance
         records (view_enhance() makes them), nested as post's; the descriptor then goes through
         fpng_amd_decode_batch(_device)_planar_views_enhance, with the others' records or without."""
-        who = "make_decode_batch_views"
-        n = len(pngs)
-        if len(crops) != n or len(outs) != n:
-            raise ValueError(f"{who}: {n} files, {len(crops)} lists of crops, {len(outs)} lists of destinations")
-        crops, outs = [list(c) for c in crops], [list(o) for o in outs]
-        counts = [len(c) for c in crops]
-        for i in range(n):
-            if counts[i] < 1 or len(outs[i]) != counts[i]:
-                raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
-        fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
-        filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
-        dtypes = {t.dtype for ts in outs for t in ts if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        is_u8 = dtypes == {torch.uint8}
-        fmt = None
-        if is_u8:
-            if any(v is not None for v in (mean, std, scale, bias)):
-                raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
-        else:
-            sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
-            fmt = _lib.FloatFormat()
-            for k in range(4):
-                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
-        total = sum(counts)
-        arr = (_lib.PngPlanarIn * n)()
-        narr = (C.c_uint32 * n)(*counts)
-        carr, varr, darr = (_lib.Crop * total)(), (_lib.ResizeView * total)(), (_lib.ViewDest * total)()
-        res = (_lib.DecodeResult * n)()
-        keep = []
-        at = 0
-        for i, p in enumerate(pngs):
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            chans = {t.shape[0] for t in outs[i]}
-            if len(chans) != 1:
-                raise ValueError(f"{who}: the destinations of file {i} share one channel count, not {sorted(chans)}")
-            arr[i].num_chans = chans.pop()  # (d_pixels, the pitches and pixels_cap stay NULL / 0: the destinations are the views')
-            for k, t in enumerate(outs[i]):
-                if is_u8:
-                    ptr, rp, pp = dest_layout_planar(t, orders[i][k], bool(ups[i][k]))
-                else:
-                    ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i][k], bool(ups[i][k]))
-                _crop_record(f"{who}: file {i}", crops[i][k], carr[at])
-                v = _view_record(who, fulls[i][k], windows[i][k], filters[i][k], bool(mirrors[i][k]), varr[at])
-                c, oh, ow = t.shape
-                if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
-                    raise ValueError(f"{who}: destination {k} of file {i} is {ow} x {oh}, its window {v.w} x {v.h}")
-                darr[at].d_pixels, darr[at].row_pitch, darr[at].plane_pitch = ptr, rp, pp
-                darr[at].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
-                at += 1
-        batch = DecodeBatchMultiView(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
-        if color is not None:
-            batch.colors = _color_records(who, counts, color)
-        if post is not None:
-            batch.posts = _post_records(who, counts, post)
-        if warp is not None:
-            batch.warps = _warp_records(who, counts, warp)
-        if tone is not None:
-            batch.tones = _tone_records(who, counts, tone)
-        if enhance is not None:
-            batch.enhances = _enhance_records(who, counts, enhance)
-        return batch
+        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
 
-    def _decode_views(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                      color, post=None, fn_post=None, warp=None, tone=None, enhance=None):
-        if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiView):
-            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views() makes this one's)")
-        if isinstance(pngs, DecodeBatchMultiView):
+    def _decode_views(self, layout, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
+                      tone, enhance):
+        """a views call of either layout (_ViewsLayout), for files in device or host memory"""
+        who = layout.device if device_data else layout.host
+        if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, layout.batch_cls):
+            raise ValueError(f"{who}: a descriptor of another call ({layout.maker}() makes this one's)")
+        if isinstance(pngs, layout.batch_cls):
             if color is not None or post is not None or warp is not None or tone is not None or enhance is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone and enhance records (make_decode_batch_views(..., color=, post=, warp=, tone=, enhance=))")
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone and enhance records ({layout.maker}(..., color=, post=, warp=, tone=, enhance=))")
             batch = pngs
         else:
             if crops is None or full is None:
                 raise ValueError(f"{who}: crops, a list of (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
-            if outs is None or any(o is None for o in outs):  # (c = 3 planes of each window's size; files with alpha lose it)
+            if outs is None or any(o is None for o in outs):  # (each window's size with c = 3; files with alpha lose it)
                 if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
                     raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
                 counts = [len(c) for c in crops]
                 fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
-                outs = [[torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
+                outs = [[torch.empty(layout.empty_shape(oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = self.make_decode_batch_views(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
+            batch = _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
         if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views)" if device_data else "device memory (decode_device_views)"))
+            raise ValueError(f"{who}: the files are in " + (f"host memory ({layout.host})" if device_data else f"device memory ({layout.device})"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
             raise ValueError(f"{who}: the destinations are CUDA tensors")
         self._sync_stream()
-        fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.enhances is not None:
-            check(getattr(self.lib, fn_post.replace("_views_post", "_views_enhance"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
-                                                                                      batch.posts, batch.warps, batch.tones, batch.enhances, fmt, batch.res))
-        elif batch.tones is not None:
-            check(getattr(self.lib, fn_post.replace("_views_post", "_views_tone"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
-                                                                                   batch.posts, batch.warps, batch.tones, fmt, batch.res))
-        elif batch.warps is not None:
-            check(getattr(self.lib, fn_post.replace("_views_post", "_views_warp"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
-                                                                                   batch.posts, batch.warps, fmt, batch.res))
-        elif batch.posts is not None:
-            check(getattr(self.lib, fn_post)(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, batch.posts, fmt, batch.res))
-        elif batch.colors is None:
-            check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
-        else:
-            check(fn_color(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, fmt, batch.res))
+        symbol, args = views_entry(layout.name, device_data, batch)
+        check(getattr(self.lib, symbol)(self.h, *args))
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
@@ -2293,16 +2253,14 @@ class Encoder:
         enhance: None, or an enhance record per view (view_enhance() makes them: brightness, color or sharpness as Pillow's
         ImageEnhance does them; nested as post's), applied to the bytes behind the tone operation and in front of the blur --
         fpng_amd_decode_batch_device_planar_views_enhance; a record without an op leaves its view exactly the call's without."""
-        return self._decode_views("decode_device_views", self.lib.fpng_amd_decode_batch_device_planar_views, self.lib.fpng_amd_decode_batch_device_planar_views_color, True, pngs,
-                                  crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_device_planar_views_post", warp, tone, enhance)
+        return self._decode_views(_PLANAR_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
+                                  tone, enhance)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
-        return self._decode_views("decode_batch_views", self.lib.fpng_amd_decode_batch_planar_views, self.lib.fpng_amd_decode_batch_planar_views_color, False, pngs, crops,
-                                  outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                  "fpng_amd_decode_batch_planar_views_post", warp, tone, enhance)
+        return self._decode_views(_PLANAR_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
+                                  tone, enhance)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
@@ -2314,120 +2272,7 @@ class Encoder:
         fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post), warp (then:
         fpng_amd_decode_batch(_device)_hwc_views_warp), tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone) and enhance (then:
         fpng_amd_decode_batch(_device)_hwc_views_enhance) -- is make_decode_batch_views()'s."""
-        who = "make_decode_batch_views_hwc"
-        n = len(pngs)
-        if len(crops) != n or len(outs) != n:
-            raise ValueError(f"{who}: {n} files, {len(crops)} lists of crops, {len(outs)} lists of destinations")
-        crops, outs = [list(c) for c in crops], [list(o) for o in outs]
-        counts = [len(c) for c in crops]
-        for i in range(n):
-            if counts[i] < 1 or len(outs[i]) != counts[i]:
-                raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
-        fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
-        filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
-        dtypes = {t.dtype for ts in outs for t in ts if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        is_u8 = dtypes == {torch.uint8}
-        fmt = None
-        if is_u8:
-            if any(v is not None for v in (mean, std, scale, bias)):
-                raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
-        else:
-            sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
-            fmt = _lib.FloatFormat()
-            for k in range(4):
-                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
-        total = sum(counts)
-        arr = (_lib.PngPlanarIn * n)()
-        narr = (C.c_uint32 * n)(*counts)
-        carr, varr, darr = (_lib.Crop * total)(), (_lib.ResizeView * total)(), (_lib.ViewDestHwc * total)()
-        res = (_lib.DecodeResult * n)()
-        keep = []
-        at = 0
-        for i, p in enumerate(pngs):
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            layouts = [dest_layout_hwc(t, orders[i][k], bool(ups[i][k])) for k, t in enumerate(outs[i])]
-            chans = {t.shape[2] for t in outs[i]}
-            if len(chans) != 1:
-                raise ValueError(f"{who}: the destinations of file {i} share one channel count, not {sorted(chans)}")
-            arr[i].num_chans = chans.pop()  # (d_pixels, the pitches and pixels_cap stay NULL / 0: the destinations are the views')
-            for k, t in enumerate(outs[i]):
-                ptr, rp, px, flags, code = layouts[k]
-                if code is not None:
-                    fmt.dtype = code
-                _crop_record(f"{who}: file {i}", crops[i][k], carr[at])
-                v = _view_record(who, fulls[i][k], windows[i][k], filters[i][k], bool(mirrors[i][k]), varr[at])
-                oh, ow, c = t.shape
-                if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
-                    raise ValueError(f"{who}: destination {k} of file {i} is {ow} x {oh}, its window {v.w} x {v.h}")
-                darr[at].d_pixels, darr[at].row_pitch, darr[at].pixel_elems, darr[at].flags = ptr, rp, px, flags
-                darr[at].pixels_cap = (oh - 1) * abs(rp) + ((ow - 1) * px + c) * t.element_size()  # (the view's own spans, in bytes)
-                at += 1
-        batch = DecodeBatchMultiViewHwc(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
-        if color is not None:
-            batch.colors = _color_records(who, counts, color)
-        if post is not None:
-            batch.posts = _post_records(who, counts, post)
-        if warp is not None:
-            batch.warps = _warp_records(who, counts, warp)
-        if tone is not None:
-            batch.tones = _tone_records(who, counts, tone)
-        if enhance is not None:
-            batch.enhances = _enhance_records(who, counts, enhance)
-        return batch
-
-    def _decode_views_hwc(self, who, fn, fn_color, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
-                          color, post=None, fn_post=None, warp=None, tone=None, enhance=None):
-        if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, DecodeBatchMultiViewHwc):
-            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_views_hwc() makes this one's)")
-        if isinstance(pngs, DecodeBatchMultiViewHwc):
-            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone and enhance records (make_decode_batch_views_hwc(..., color=, post=, warp=, tone=, enhance=))")
-            batch = pngs
-        else:
-            if crops is None or full is None:
-                raise ValueError(f"{who}: crops, a list of (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
-            if outs is None or any(o is None for o in outs):  # (each window's size with c = 3 channels; files with alpha lose it)
-                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
-                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
-                counts = [len(c) for c in crops]
-                fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
-                sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
-                outs = [[torch.empty((oh, ow, 3), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
-                        for i in range(len(crops))]
-            batch = self.make_decode_batch_views_hwc(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_views_hwc)" if device_data else "device memory (decode_device_views_hwc)"))
-        if not all(t.is_cuda for ts in batch.outs for t in ts):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-        if batch.enhances is not None:
-            check(getattr(self.lib, fn_post.replace("_views_post", "_views_enhance"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
-                                                                                      batch.posts, batch.warps, batch.tones, batch.enhances, fmt, batch.res))
-        elif batch.tones is not None:
-            check(getattr(self.lib, fn_post.replace("_views_post", "_views_tone"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
-                                                                                   batch.posts, batch.warps, batch.tones, fmt, batch.res))
-        elif batch.warps is not None:
-            check(getattr(self.lib, fn_post.replace("_views_post", "_views_warp"))(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors,
-                                                                                   batch.posts, batch.warps, fmt, batch.res))
-        elif batch.posts is not None:
-            check(getattr(self.lib, fn_post)(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, batch.posts, fmt, batch.res))
-        elif batch.colors is None:
-            check(fn(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, fmt, batch.res))
-        else:
-            check(fn_color(self.h, batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, batch.colors, fmt, batch.res))
-        return batch.results() if results else batch
+        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                                 bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
@@ -2443,16 +2288,14 @@ class Encoder:
         uint8 or float.  -> list, per file, of (status, the list of the caller's views or None, channels_in_file).  outs=None (or
         None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
-        return self._decode_views_hwc("decode_device_views_hwc", self.lib.fpng_amd_decode_batch_device_hwc_views, self.lib.fpng_amd_decode_batch_device_hwc_views_color, True, pngs,
-                                      crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_device_hwc_views_post", warp, tone, enhance)
+        return self._decode_views(_HWC_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
+                                  tone, enhance)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
-        return self._decode_views_hwc("decode_batch_views_hwc", self.lib.fpng_amd_decode_batch_hwc_views, self.lib.fpng_amd_decode_batch_hwc_views_color, False, pngs, crops,
-                                      outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post,
-                                      "fpng_amd_decode_batch_hwc_views_post", warp, tone, enhance)
+        return self._decode_views(_HWC_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
+                                  tone, enhance)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

@@ -9,8 +9,9 @@
 #include "png_parse.h"
 #include "resize.h"
 #include "resize_color.h"
-#include "view_post.h"
 #include "resize_hwc.h"
+#include "view_plan.h"
+#include "view_post.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -338,68 +339,7 @@ struct Batch {
     std::vector<DecCrop> crop;            // ... a record per job, uploaded with the job records
     DecCrop *d_crops = nullptr;
     std::vector<uint32_t> col_blocks;     // per job: the column blocks its tiles are numbered over (a crop's: dec_crop_tiles)
-    // fpng_amd_decode_batch(_device)_planar_resize(_view): the files' views (else NULL; needs crops; the plain resize call's sizes
-    // arrive as whole-window bilinear views).  The jobs' out / pitch / plane_pitch then describe uint8 planes in the scratch
-    // (mid_total bytes, 16-byte aligned per file) of the BOX of the crop that the view's taps reach, which the crop kernels fill as
-    // for uint8 destinations of that box; the caller's destination travels in a record per VIEW to dec_resize_kernel.
-    // fpng_amd_decode_batch(_device)_planar_views: file i has view_count[i] views, whose crops / sizes / dests records start at
-    // view_ofs[i] (else NULL / empty: one view per file, record i, its destination the planar file's); a job's box is then the
-    // bounding rectangle of its views' boxes, and job k's records are job_rec[k] .. job_rec[k + 1] - 1
-    const fpng_amd_resize_view *sizes = nullptr;
-    const uint32_t *view_count = nullptr;
-    const fpng_amd_view_dest *dests = nullptr;
-    // fpng_amd_decode_batch(_device)_hwc_views: the views call with channels-last destinations (then dests is NULL).  The records of
-    // `resize` keep everything but the destination's layout -- dst: pixel (0, 0) of the top row, pitch: the rows' -- and go up as
-    // DecResizeHwc records with hwc_px (per view: pixel_elems, flags); the launch's prefix sums count tiles: hwc_pre
-    const fpng_amd_view_dest_hwc *hwc = nullptr;
-    std::vector<std::pair<uint32_t, uint32_t>> hwc_px;
-    std::vector<uint64_t> hwc_pre;
-    DecResizeHwc *d_resize_hwc = nullptr;
-    // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: either views call with a colour matrix per view (else
-    // NULL).  The records go up as DecResizeColor -- the record above (planar destinations: pixel_elems and flags 0) and the matrix
-    // of color_view (per record: its view's index in `color`) -- and the launch's prefix sums count tiles, as hwc_pre does
-    const fpng_amd_view_color *color = nullptr;
-    std::vector<uint32_t> color_view;
-    DecResizeColor *d_resize_color = nullptr;
-    bool per_tile() const { return hwc || color; } // a workgroup per (record, tile), all planes: dec_resize_hwc_kernel, dec_resize_color_kernel
-    size_t resize_rec_bytes() const { return color ? sizeof(DecResizeColor) : hwc ? sizeof(DecResizeHwc) : sizeof(DecResize); }
-    // fpng_amd_decode_batch(_device)_planar_views_post / _hwc_views_post: the colour call with a post-processing record per view
-    // (else NULL; only when at least one view has a flag, and then with `color`: the identity for a call without matrices).  A view
-    // with flags is a POST view: its record of `resize` writes the un-mirrored uint8 window into the scratch (dst: an offset until
-    // place_files(), as src) and its destination travels in post_recs[post_of[q]] to dec_view_post_kernel; a view without (post_of
-    // -1) is a DIRECT view, the colour call's.  The two kinds go up as two arrays, the direct records in front, and are launched
-    // one after the other with prefix sums of their own (dir_pre, post_pre: tiles); job k's post records are job_post[k] ..
-    // job_post[k + 1] - 1, its direct ones the rest of job_rec's
-    const fpng_amd_view_post *post = nullptr;
-    std::vector<int32_t> post_of;
-    std::vector<DecViewPost> post_recs;
-    std::vector<uint32_t> job_post;
-    std::vector<uint64_t> dir_pre, post_pre;
-    DecViewPost *d_post = nullptr;
-    // fpng_amd_decode_batch(_device)_planar_views_warp / _hwc_views_warp: the post call with a warp record per view (else NULL; only
-    // when at least one view has a warp flag and another matrix than the identity, and then with `post`: records without flags for a call without).  A view with a warp
-    // flag (and not the identity: warp_moves) is a post view whatever its post flags, and its record of post_recs carries the warp (DecViewPost::warp)
-    const fpng_amd_view_warp *warp = nullptr;
-    // fpng_amd_decode_batch(_device)_planar_views_tone / _hwc_views_tone: the warp call with a tone record per view (else NULL; only
-    // when at least one view has an op, and then with `post`).  A view with an op is a post view whatever its other flags; tone view t
-    // (tone_refs[t]: its post record and the chunks of dec_view_tone_hist_kernel in front of it) has kToneBytes of the scratch at
-    // d_tone + t * kToneBytes; job k's tone views are job_tone[k] .. job_tone[k + 1] - 1
-    const fpng_amd_view_tone *tone = nullptr;
-    // fpng_amd_decode_batch(_device)_planar_views_enhance / _hwc_views_enhance: the tone call with an enhance record per view (else NULL;
-    // only when at least one view has an op, and then with `post`).  A view with an op is a post view whatever its other flags, and
-    // the call's post stage is the kMode == 3 one
-    const fpng_amd_view_enhance *enhance = nullptr;
-    std::vector<DecToneRef> tone_refs;
-    std::vector<uint32_t> job_tone;
-    DecToneRef *d_tone_refs = nullptr;
-    uint8_t *d_tone = nullptr;
-    std::vector<uint32_t> view_ofs, job_rec;
-    std::vector<DecResize> resize; // per view (src: an offset into the intermediate planes until place_files())
-    std::vector<uint32_t> resize_tiles, resize_lds; // per view: its tiles per plane, the LDS bytes of one
-    std::vector<uint64_t> resize_pre; // (views call) per view and one more: the workgroups -- planes x tiles -- of the views in front
-    DecResize *d_resize = nullptr;
-    uint64_t *d_resize_pre = nullptr;
-    size_t mid_total = 0;
+    ViewPlan views; // the views of the resize, resize_view and views calls (view_plan.h); empty for every other call
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     std::vector<Parsed> ps;
     std::vector<DecJob> jobs;                // (their pointers into the scratch are offsets until place_files())
@@ -427,36 +367,8 @@ struct Batch {
     Worker *uploader = nullptr;
     ~Batch() { if (uploader) uploader->wait(); } // (every way out waits for the uploader first: it works on this struct)
     uint32_t nj() const { return (uint32_t)jobs.size(); }
-    uint32_t first_view(uint32_t file) const { return view_count ? view_ofs[file] : file; }
-    uint32_t views_of(uint32_t file) const { return view_count ? view_count[file] : 1u; }
     double since() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
-
-// the pixels of the file that the taps of view z of `crop` reach (fpng_amd_resize_view_source): per axis first(x) ..
-// first(x + w - 1) + count(x + w - 1) of the crop's samples.  z has passed check_view_records()
-DecCrop view_box(const DecCrop &crop, const fpng_amd_resize_view &z)
-{
-    uint32_t x0, x1, y0, y1;
-    resize_source_span(z.filter, crop.w, z.full_w, z.x, z.w, &x0, &x1);
-    resize_source_span(z.filter, crop.h, z.full_h, z.y, z.h, &y0, &y1);
-    return {crop.x + x0, crop.y + y0, x1 - x0, y1 - y0};
-}
-
-// the ONE box a file with these count >= 1 views decodes (fpng_amd_views_source): the bounding rectangle of their boxes.  The
-// records have passed check_view_records(); the crops may leave the image, so the far edges are taken in 64 bits and the answer's
-// w / h saturate (such a file is refused before its box is used).  each (or NULL): the views' own boxes, view_box() of each
-DecCrop views_box(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, DecCrop *each = nullptr)
-{
-    uint64_t x0 = UINT64_MAX, y0 = UINT64_MAX, x1 = 0, y1 = 0;
-    for (uint32_t k = 0; k < count; k++) {
-        const DecCrop c = {crops[k].x, crops[k].y, crops[k].w, crops[k].h};
-        const DecCrop v = view_box({0, 0, c.w, c.h}, views[k]); // (within the crop: no sum wraps)
-        if (each) each[k] = {c.x + v.x, c.y + v.y, v.w, v.h};
-        x0 = std::min<uint64_t>(x0, (uint64_t)c.x + v.x), x1 = std::max<uint64_t>(x1, (uint64_t)c.x + v.x + v.w);
-        y0 = std::min<uint64_t>(y0, (uint64_t)c.y + v.y), y1 = std::max<uint64_t>(y1, (uint64_t)c.y + v.y + v.h);
-    }
-    return {(uint32_t)x0, (uint32_t)y0, (uint32_t)std::min<uint64_t>(x1 - x0, UINT32_MAX), (uint32_t)std::min<uint64_t>(y1 - y0, UINT32_MAX)};
-}
 
 // ---- parse: every file's container and stream header (device-resident ones: from their heads and tails), job record, table key ----
 int parse_files(Batch &b)
@@ -478,10 +390,6 @@ int parse_files(Batch &b)
     }
     uint32_t *const table = nullptr; // (no host-side lookup table: the header reader only checks the code)
     HeaderMemo memo;
-    std::vector<DecResize> file_recs; // (the records of the file at hand's views, and their source boxes)
-    std::vector<DecCrop> file_boxes;
-    std::vector<std::pair<uint32_t, uint32_t>> file_px; // (channels-last destinations: the same views' pixel_elems and flags)
-    b.resize_pre.assign(1, 0), b.hwc_pre.assign(1, 0);
     b.ps.resize(b.n);
     for (uint32_t i = 0; i < b.n; i++) {
         const fpng_amd_png &f = b.files[i];
@@ -515,7 +423,7 @@ int parse_files(Batch &b)
         // (a crop that leaves the image: the file's own outcome -- it is not decoded and needs no room)
         DecCrop crop = {0, 0, p.w, p.h};
         uint32_t crop_nseg = 0, crop_cb0 = 0, crop_ncb = 0;
-        const uint32_t v0 = b.first_view(i), nv = b.views_of(i); // (the file's records of crops / sizes / dests)
+        const uint32_t v0 = b.views.first_view(i), nv = b.views.views_of(i); // (the file's records of the crops)
         if (b.crops) {
             bool inside = true; // (every one of the file's crops)
             for (uint32_t v = v0; v < v0 + nv && inside; v++) {
@@ -529,74 +437,19 @@ int parse_files(Batch &b)
         }
         // (views: judged on the caller's crops above; what the crop stage decodes, and the tiles that run, are those of the ONE box
         //  that holds the boxes of all of the file's views)
-        if (b.sizes) {
-            file_boxes.resize(nv);
-            crop = views_box(b.crops + v0, b.sizes + v0, nv, file_boxes.data());
+        if (b.views.active()) {
+            crop = b.views.file_box(i);
             dec_crop_tiles(p.w, p.h, crop, &crop_nseg, &crop_cb0, &crop_ncb); // (inside the caller's crops: never outside)
         }
         // (only files that will be written need room)
         int64_t pitch = 0, plane_pitch = 0;
-        if (b.planar) {
-            // a destination of dest_w x dest_h elements per plane (a crop: its own w and h; a view: its window's): its pitches, its room
-            auto judge = [&](uint8_t *d_pixels, int64_t row_pitch, int64_t plane_pitch_in, size_t pixels_cap, uint32_t dest_w, uint32_t dest_h) -> int {
-                const uint64_t roww = (uint64_t)dest_w * b.elem; // bytes of a plane's row (float planes: w elements)
-                if (roww >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * element bytes >= 2^31");
-                pitch = row_pitch ? row_pitch : (int64_t)roww;
-                const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
-                if (step < roww) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
-                const uint64_t span = (uint64_t)(dest_h - 1) * step + roww; // a plane, from its lowest row's first byte
-                plane_pitch = plane_pitch_in ? plane_pitch_in : (int64_t)((uint64_t)dest_h * step);
-                if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
-                const uint64_t pstep = (uint64_t)(plane_pitch < 0 ? -plane_pitch : plane_pitch);
-                if (pstep < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
-                if (pstep > (UINT64_MAX >> 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
-                if (!d_pixels || pixels_cap < (uint64_t)(desired - 1) * pstep + span)
-                    return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (num_chans - 1) * |plane_pitch| + (h - 1) * |row_pitch| + w (* element bytes)");
-                return FPNG_AMD_OK;
-            };
-            // the sibling for a channels-last destination of dest_w x dest_h pixels of pixel_elems elements, `desired` of them written:
-            // the rows' pitch and the room (fpng_amd_view_dest_hwc's rule; the record's own rules: decode_files_planar)
-            auto judge_hwc = [&](const fpng_amd_view_dest_hwc &d, uint32_t dest_w, uint32_t dest_h) -> int {
-                const uint32_t px = d.pixel_elems ? d.pixel_elems : desired;
-                const uint64_t span = ((uint64_t)(dest_w - 1) * px + desired) * b.elem; // a row, from its first byte to its last written one
-                if (span >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "((w - 1) * pixel_elems + num_chans) * element bytes >= 2^31");
-                pitch = d.row_pitch ? d.row_pitch : (int64_t)((uint64_t)dest_w * px * b.elem);
-                const uint64_t step = (uint64_t)(pitch < 0 ? -pitch : pitch);
-                if (step >= 0x80000000ull) return fail(FPNG_AMD_ERR_INVALID_ARG, "w * pixel_elems * element bytes >= 2^31");
-                if (step < span) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < ((w - 1) * pixel_elems + num_chans) * element bytes");
-                if (!d.d_pixels || d.pixels_cap < (uint64_t)(dest_h - 1) * step + span)
-                    return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_pixels / pixels_cap < (h - 1) * |row_pitch| + ((w - 1) * pixel_elems + num_chans) * element bytes");
-                plane_pitch = 0;
-                return FPNG_AMD_OK;
-            };
+        if (b.planar && !b.views.active()) { // a destination of the crop's w x h elements per plane: its pitches, its room
             const fpng_amd_png_planar &x = b.planar[i];
-            if (!b.sizes) {
-                if (int rc = judge((uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap, crop.w, crop.h)) return rc;
-            } else {
-                // a record per view for dec_resize_kernel, which reads the view's own box inside the planes of the job's box (src: an
-                // offset from those planes' first byte until the file is known to become a job)
-                if (crop.w >= 0x80000000u) return fail(FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31");
-                file_recs.clear(), file_px.clear();
-                for (uint32_t v = v0; v < v0 + nv; v++) {
-                    const fpng_amd_resize_view &z = b.sizes[v];
-                    const fpng_amd_view_dest dest = b.hwc     ? fpng_amd_view_dest{b.hwc[v].d_pixels, 0, 0, 0}
-                                                    : b.dests ? b.dests[v]
-                                                              : fpng_amd_view_dest{(uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap};
-                    if (int rc = b.hwc ? judge_hwc(b.hwc[v], z.w, z.h) : judge(dest.d_pixels, dest.row_pitch, dest.plane_pitch, dest.pixels_cap, z.w, z.h)) return rc;
-                    if (resize_tiles(z.w, z.h) * 4 * kResizeBlock >= (1ull << 32)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16");
-                    const DecCrop whole_crop = {b.crops[v].x, b.crops[v].y, b.crops[v].w, b.crops[v].h}, box = file_boxes[v - v0];
-                    DecResize rs = {};
-                    rs.src = (const uint8_t *)(uintptr_t)((size_t)(box.y - crop.y) * crop.w + (box.x - crop.x));
-                    rs.src_pitch = crop.w, rs.src_plane_pitch = (uint64_t)crop.w * crop.h;
-                    rs.dst = dest.d_pixels, rs.plane_pitch = plane_pitch, rs.pitch = (int32_t)pitch;
-                    rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags, rs.planes = desired, rs.filter = z.filter;
-                    rs.x = z.x, rs.y = z.y, rs.w = z.w, rs.h = z.h;
-                    rs.box_x = box.x - whole_crop.x, rs.box_y = box.y - whole_crop.y;
-                    rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
-                    file_recs.push_back(rs);
-                    if (b.hwc) file_px.push_back({b.hwc[v].pixel_elems ? b.hwc[v].pixel_elems : desired, b.hwc[v].flags});
-                }
-            }
+            const DestPitches d = judge_planar_dest((const uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap, crop.w, crop.h, desired, b.elem);
+            if (d.refused) return fail(d.refused.code, d.refused.why);
+            pitch = d.pitch, plane_pitch = d.plane_pitch;
+        } else if (b.planar) {
+            if (const Refusal no = b.views.file_records(i, f, b.planar[i], desired, crop)) return fail(no.code, no.why);
         } else if (b.ex) {
             const uint64_t row = (uint64_t)p.w * desired;
             pitch = b.ex[i].row_pitch ? b.ex[i].row_pitch : (int64_t)row;
@@ -613,52 +466,9 @@ int parse_files(Batch &b)
         DecJob j = make_job(p, desired);
         j.out = f.d_pixels, j.sub_base = b.sub_total;
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
-        if (b.sizes) {
-            // the crop kernels write tight uint8 planes of the box's size into the scratch; the resize reads them and writes the caller's
-            b.job_rec.push_back((uint32_t)b.resize.size());
-            b.job_tone.push_back((uint32_t)b.tone_refs.size());
-            for (DecResize &rs : file_recs) {
-                rs.src += b.mid_total; // (an offset until place_files())
-                const uint64_t tiles = resize_tiles(rs.w, rs.h);
-                const uint32_t view = v0 + (uint32_t)(&rs - file_recs.data());
-                const bool is_post = b.post && (b.post[view].flags || (b.warp && warp_moves(b.warp[view])) || (b.tone && b.tone[view].op) || (b.enhance && b.enhance[view].op));
-                if (is_post) { // (the destination goes to the post stage; the resize writes tight un-mirrored uint8 planes)
-                    const fpng_amd_view_post &vp = b.post[view];
-                    DecViewPost pr = {};
-                    pr.dst = rs.dst, pr.plane_pitch = rs.plane_pitch, pr.pitch = rs.pitch, pr.w = rs.w, pr.h = rs.h, pr.planes = rs.planes, pr.mirror = rs.flags & kResizeMirror;
-                    if (b.hwc) pr.pixel_elems = file_px[view - v0].first, pr.hwc_flags = file_px[view - v0].second;
-                    pr.flags = vp.flags, pr.radius = vp.blur_radius, pr.threshold = vp.solarize_threshold, pr.bits = vp.posterize_bits;
-                    if (vp.flags & kPostBlur) post_blur_weights(vp.blur_radius, vp.blur_sigma, pr.k);
-                    if (b.warp) pr.warp = warp_record(b.warp[view]);
-                    if (b.enhance) pr.enhance_op = b.enhance[view].op, pr.enhance_factor = b.enhance[view].factor;
-                    if (b.tone && b.tone[view].op) { // (tone: an offset until place_files())
-                        pr.tone_op = b.tone[view].op, pr.tone_factor = b.tone[view].factor;
-                        const uint64_t before = b.tone_refs.empty() ? 0 : b.tone_refs.back().pre + tone_chunks(b.post_recs[b.tone_refs.back().rec].w, b.post_recs[b.tone_refs.back().rec].h);
-                        b.tone_refs.push_back({before, (uint32_t)b.post_recs.size(), 0});
-                    }
-                    b.post_recs.push_back(pr);
-                    rs.dst = nullptr, rs.pitch = (int32_t)rs.w, rs.plane_pitch = (int64_t)((uint64_t)rs.w * rs.h), rs.flags &= ~kResizeMirror;
-                }
-                if (b.post) b.post_of.push_back(is_post ? (int32_t)b.post_recs.size() - 1 : -1);
-                b.resize.push_back(rs);
-                b.resize_tiles.push_back((uint32_t)tiles), b.resize_lds.push_back(resize_tile_lds(rs.taps_x, rs.taps_y, rs.rows));
-                b.resize_pre.push_back(b.resize_pre.back() + rs.planes * tiles);
-                if (b.per_tile()) { // (a workgroup per tile, all planes; channels-last: the tile's result bytes in its LDS)
-                    if (b.hwc && !is_post) b.resize_lds.back() = resize_hwc_tile_lds(rs.taps_x, rs.taps_y, rs.rows, rs.planes);
-                    b.hwc_pre.push_back(b.hwc_pre.back() + tiles);
-                    b.hwc_px.push_back(b.hwc && !is_post ? file_px[&rs - file_recs.data()] : std::pair<uint32_t, uint32_t>{0, 0});
-                    if (b.color) b.color_view.push_back(v0 + (uint32_t)(&rs - file_recs.data()));
-                }
-            }
-            j.out = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
+        if (b.views.active()) { // (the job writes its box's planes into the scratch: an offset until place_files())
+            j.out = (uint8_t *)(uintptr_t)b.views.add_job(i, desired, crop);
             pitch = (int64_t)crop.w, plane_pitch = (int64_t)((uint64_t)crop.w * crop.h);
-            b.mid_total += ((size_t)plane_pitch * desired + 15) & ~(size_t)15;
-            // (the post views' windows: next to the box's planes)
-            for (size_t q = b.job_rec.back(); b.post && q < b.resize.size(); q++)
-                if (b.post_of[q] >= 0) {
-                    b.resize[q].dst = (uint8_t *)(uintptr_t)b.mid_total; // (an offset until place_files())
-                    b.mid_total += ((size_t)b.resize[q].w * b.resize[q].h * desired + 15) & ~(size_t)15;
-                }
         }
         if (b.planar) j.pitch = (int32_t)pitch, b.plane_pitch.push_back(plane_pitch); // (|pitch| < 2^31: decode_files_planar)
         // (the tiles a crop needs: DecJob::nseg is read by the un-filter kernels, by the plan and by the granules' sizing only, so
@@ -693,12 +503,7 @@ int parse_files(Batch &b)
         b.jobs.push_back(j);
         b.job_file.push_back(i);
     }
-    b.job_rec.push_back((uint32_t)b.resize.size());
-    b.job_tone.push_back((uint32_t)b.tone_refs.size());
-    if (!b.tone_refs.empty()) { // (the entry that closes the sums)
-        const DecViewPost &last = b.post_recs[b.tone_refs.back().rec];
-        b.tone_refs.push_back({b.tone_refs.back().pre + tone_chunks(last.w, last.h), 0, 0});
-    }
+    b.views.close();
     if (tracing()) fprintf(stderr, "[decode] +%.0f us: %u files parsed, %u lookup tables wanted\n", b.since(), b.n, b.luts.count());
     return FPNG_AMD_OK;
 }
@@ -710,12 +515,13 @@ int place_files(Batch &b)
     const uint32_t nj = b.nj(), n_luts = b.luts.count();
     const size_t n_status = 2 * (size_t)nj + 1 + 2 * kMaxGroups; // status and eob index per file, changed and multi per group
     Scratch sc(b.z_total + 64, b.win_total, b.sub_total, b.seg_total);
-    const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288)),
-                 o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0), o_resize = sc.carve(b.resize.size() * b.resize_rec_bytes()), o_pre = sc.carve(b.view_count ? (b.resize_pre.size() + (b.post ? 1 : 0)) * sizeof(uint64_t) : 0), o_post = sc.carve(b.post_recs.size() * sizeof(DecViewPost)), o_tone_refs = sc.carve(b.tone_refs.size() * sizeof(DecToneRef)), o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
-    // (nothing more than without the check unless it is asked for)
-    const size_t o_mid = b.sizes ? sc.carve(b.mid_total) : 0; // (the crops' uint8 planes between the crop kernels and the resize)
-    // (the tone views' histograms and tables: behind the set-up block, which is uploaded; these are zeroed and written on the device)
-    const size_t n_tone = b.tone_refs.empty() ? 0 : b.tone_refs.size() - 1, o_tone = sc.carve(n_tone * kToneBytes);
+    const size_t o_luts = sc.carve(std::max<size_t>(n_luts, 1) * dec::kLutDwords * 4), o_keys = sc.carve(std::max<size_t>(b.luts.keys.size(), 288));
+    // the set-up block: job records, plane pitches, crops, the views' records, un-filter plans, status words
+    const size_t o_jobs = sc.carve(nj * sizeof(DecJob)), o_pp = sc.carve(b.planar ? nj * sizeof(int64_t) : 0), o_crop = sc.carve(b.crops ? nj * sizeof(DecCrop) : 0);
+    b.views.carve_records(sc);
+    const size_t o_plan = sc.carve(((size_t)nj + kMaxGroups) * (sizeof(DecUnfPiece) + 8)), o_status = sc.carve(n_status * 4);
+    // (behind the block, which is uploaded: what is only written on the device.  Nothing more than without the check unless it is asked for)
+    b.views.carve_scratch(sc);
     const size_t o_acc = b.verify & FPNG_AMD_VERIFY_ADLER32 ? sc.carve((size_t)nj * 16) : 0, o_part = b.verify & FPNG_AMD_VERIFY_CRC32 ? sc.carve((size_t)nj * b.max_ranges * 4) : 0;
     int rc;
     if ((rc = sc.place(e, b.d))) return rc;
@@ -725,13 +531,7 @@ int place_files(Batch &b)
     b.d_luts = (uint32_t *)(base + o_luts), b.d_keys = base + o_keys, b.d_jobs = (DecJob *)(base + o_jobs), b.d_plan = base + o_plan, b.d_status = (uint32_t *)(base + o_status);
     b.d_plane_pitch = b.planar ? (int64_t *)(base + o_pp) : nullptr;
     b.d_crops = b.crops ? (DecCrop *)(base + o_crop) : nullptr;
-    b.d_resize = b.sizes ? (DecResize *)(base + o_resize) : nullptr;
-    b.d_resize_hwc = b.hwc ? (DecResizeHwc *)(base + o_resize) : nullptr;
-    b.d_resize_color = b.color ? (DecResizeColor *)(base + o_resize) : nullptr;
-    b.d_resize_pre = b.view_count ? (uint64_t *)(base + o_pre) : nullptr;
-    b.d_post = b.post ? (DecViewPost *)(base + o_post) : nullptr;
-    b.d_tone_refs = n_tone ? (DecToneRef *)(base + o_tone_refs) : nullptr, b.d_tone = n_tone ? base + o_tone : nullptr;
-    for (size_t t = 0; t < n_tone; t++) b.post_recs[b.tone_refs[t].rec].tone = (uint32_t *)(b.d_tone + t * kToneBytes);
+    b.views.place(base);
     b.d_changed = b.d_status + nj, b.d_eob = b.d_changed + kMaxGroups, b.d_multi = b.d_eob + nj + 1; // (changed, multi: a word per group -- launch_dec_sync)
     b.setup_ofs = o_jobs, b.setup_plan = o_plan - o_jobs, b.setup_len = o_status + n_status * 4 - o_jobs;
     // the tables: from the encoder's cache when every one of this batch's is there; a batch of few distinct tables that are not
@@ -760,13 +560,7 @@ int place_files(Batch &b)
         DecJob &j = b.jobs[k];
         const Parsed &p = b.ps[b.job_file[k]];
         if (!b.device_data) j.z = b.d.z + (size_t)(uintptr_t)j.z;
-        if (b.sizes) {
-            j.out = base + o_mid + (size_t)(uintptr_t)j.out;
-            for (uint32_t q = b.job_rec[k]; q < b.job_rec[k + 1]; q++) {
-                b.resize[q].src = base + o_mid + (size_t)(uintptr_t)b.resize[q].src;
-                if (b.post && b.post_of[q] >= 0) b.post_recs[b.post_of[q]].src = b.resize[q].dst = base + o_mid + (size_t)(uintptr_t)b.resize[q].dst;
-            }
-        }
+        if (b.views.active()) j.out = b.views.d_mid + (size_t)(uintptr_t)j.out;
         // (parse_files sized the CRC partials of a host-resident file for a stream that starts on a 16-byte boundary; dec_verify_kernel
         //  counts the ranges from the real address, and one more range than sized would be the next file's slot)
         if (!b.device_data && (b.verify & FPNG_AMD_VERIFY_CRC32) && ((uintptr_t)j.z & 15)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "decode scratch: a file's stream is not 16-byte aligned");
@@ -841,43 +635,7 @@ int plan_groups(Batch &b)
     std::memcpy(h_setup, jobs.data(), nj * sizeof(DecJob));
     if (b.planar) std::memcpy(h_setup + ((uint8_t *)b.d_plane_pitch - (uint8_t *)b.d_jobs), b.plane_pitch.data(), nj * sizeof(int64_t));
     if (b.crops) std::memcpy(h_setup + ((uint8_t *)b.d_crops - (uint8_t *)b.d_jobs), b.crop.data(), nj * sizeof(DecCrop));
-    if (b.post) {
-        // (the direct views' records, then the post views', each kind in the views' order and with the tiles in front of it)
-        const size_t nd = b.resize.size() - b.post_recs.size();
-        size_t di = 0, pi = 0;
-        b.dir_pre.assign(1, 0), b.post_pre.assign(1, 0), b.job_post.clear();
-        for (uint32_t k = 0, q = 0; k <= nj; k++) {
-            for (; q < b.job_rec[k]; q++) {
-                DecResizeColor rec = {{b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second}, {}};
-                std::memcpy(rec.m, b.color[b.color_view[q]].m, sizeof rec.m);
-                const bool is_post = b.post_of[q] >= 0;
-                std::vector<uint64_t> &pre = is_post ? b.post_pre : b.dir_pre;
-                pre.push_back(pre.back() + b.resize_tiles[q]);
-                std::memcpy(h_setup + ((uint8_t *)(b.d_resize_color + (is_post ? nd + pi++ : di++)) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
-            }
-            b.job_post.push_back((uint32_t)pi);
-        }
-        std::memcpy(h_setup + ((uint8_t *)b.d_post - (uint8_t *)b.d_jobs), b.post_recs.data(), b.post_recs.size() * sizeof(DecViewPost));
-        if (b.d_tone_refs) std::memcpy(h_setup + ((uint8_t *)b.d_tone_refs - (uint8_t *)b.d_jobs), b.tone_refs.data(), b.tone_refs.size() * sizeof(DecToneRef));
-        std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), b.dir_pre.data(), b.dir_pre.size() * sizeof(uint64_t));
-        std::memcpy(h_setup + ((uint8_t *)(b.d_resize_pre + nd + 1) - (uint8_t *)b.d_jobs), b.post_pre.data(), b.post_pre.size() * sizeof(uint64_t));
-    } else if (b.color) {
-        for (size_t q = 0; q < b.resize.size(); q++) {
-            DecResizeColor rec = {{b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second}, {}};
-            std::memcpy(rec.m, b.color[b.color_view[q]].m, sizeof rec.m);
-            std::memcpy(h_setup + ((uint8_t *)(b.d_resize_color + q) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
-        }
-    } else if (b.hwc) {
-        for (size_t q = 0; q < b.resize.size(); q++) {
-            const DecResizeHwc rec = {b.resize[q], b.hwc_px[q].first, b.hwc_px[q].second};
-            std::memcpy(h_setup + ((uint8_t *)(b.d_resize_hwc + q) - (uint8_t *)b.d_jobs), &rec, sizeof rec);
-        }
-    } else if (b.sizes)
-        std::memcpy(h_setup + ((uint8_t *)b.d_resize - (uint8_t *)b.d_jobs), b.resize.data(), b.resize.size() * sizeof(DecResize));
-    if (b.view_count && !b.post) { // (the launch's prefix sums: planes x tiles, the channels-last and colour calls': tiles)
-        const std::vector<uint64_t> &pre = b.per_tile() ? b.hwc_pre : b.resize_pre;
-        std::memcpy(h_setup + ((uint8_t *)b.d_resize_pre - (uint8_t *)b.d_jobs), pre.data(), pre.size() * sizeof(uint64_t));
-    }
+    b.views.write_setup(h_setup, b.setup_ofs);
     return FPNG_AMD_OK;
 }
 
@@ -895,6 +653,53 @@ hipError_t upload_group(const Batch &b, const Group &g, hipStream_t st)
 
 // profiling (fpng_amd_encoder_set_profiling): events around the kernels of the first group of files
 hipError_t stamp(const Batch &b, uint32_t gi, int k) { return (b.prof && gi == 0) ? hipEventRecord(b.e->dec_prof_ev[k], b.s) : hipSuccess; }
+
+} // namespace
+
+// The resize of the records of jobs j0 .. j1 - 1: behind the group's pixel pass and stored copy on the same stream, on whatever the
+// scratch then holds -- it writes the spans of the destination and nothing else, whatever a file's status turns out to be
+int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const DecFloat *flt) const
+{
+    if (!active()) return FPNG_AMD_OK;
+    const uint32_t r0 = job_rec[j0], r1 = job_rec[j1]; // (the records of the group's jobs)
+    bool ok;
+    if (rq.posts) {
+        // the group's direct views as the colour call launches them; its post views' windows into the scratch -- uint8, planar,
+        // un-mirrored -- and the post stage out of those into the destinations
+        const DecResizeColor *recs = (const DecResizeColor *)d_recs;
+        const uint32_t p0 = job_post[j0], p1 = job_post[j1], d0 = r0 - p0, d1 = r1 - p1;
+        const uint32_t nd = (uint32_t)(resize.size() - post_recs.size());
+        uint32_t most_lds[2] = {0, 0};
+        bool any_filter[2] = {false, false};
+        for (uint32_t q = r0; q < r1; q++) {
+            const int kind = post_of[q] >= 0;
+            most_lds[kind] = std::max(most_lds[kind], lds[q]), any_filter[kind] |= resize[q].filter != kResizeBilinear;
+        }
+        ok = launch_dec_resize_color(s, recs + d0, d_pre + d0, dir_pre.data() + d0, d1 - d0, most_lds[0], flt, any_filter[0], hwc()) &&
+             launch_dec_resize_color(s, recs + nd + p0, d_pre + nd + 1 + p0, post_pre.data() + p0, p1 - p0, most_lds[1], nullptr, any_filter[1], false);
+        // (the group's tone views: their histograms zeroed every time -- a group that needed more rounds comes here again -- and
+        //  counted out of the windows just written, then their tables; the post stage looks them up)
+        const uint32_t t0 = d_tone ? job_tone[j0] : 0, t1 = d_tone ? job_tone[j1] : 0;
+        if (ok && t1 > t0) {
+            HIP_TRY(hipMemsetAsync(d_tone + (size_t)t0 * kToneBytes, 0, (size_t)(t1 - t0) * kToneBytes, s));
+            ok = launch_dec_view_tone(s, d_post, d_tone_refs + t0, tone_refs.data() + t0, t1 - t0);
+        }
+        ok = ok && launch_dec_view_post(s, d_post + p0, d_pre + nd + 1 + p0, post_pre.data() + p0, p1 - p0, flt, hwc(), rq.enhances ? 3 : rq.tones ? 2 : rq.warps ? 1 : 0);
+    } else {
+        const uint32_t most_tiles = *std::max_element(tiles.begin() + r0, tiles.begin() + r1), most_lds = *std::max_element(lds.begin() + r0, lds.begin() + r1);
+        // (a group of bilinear views -- the plain resize call's always are -- runs the instantiation without the second filter)
+        const bool any_filter = std::any_of(resize.begin() + r0, resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
+        // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
+        //  output per file keep the grid of the largest record)
+        ok = rq.colors ? launch_dec_resize_color(s, (const DecResizeColor *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, hwc())
+             : hwc()   ? launch_dec_resize_hwc(s, (const DecResizeHwc *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter)
+             : multi() ? launch_dec_resize_exact(s, (const DecResize *)d_recs + r0, d_pre + r0, plane_pre.data() + r0, r1 - r0, most_lds, flt, any_filter)
+                       : launch_dec_resize(s, (const DecResize *)d_recs + r0, r1 - r0, most_tiles, most_lds, flt, any_filter);
+    }
+    return ok ? FPNG_AMD_OK : fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
+}
+
+namespace {
 
 // everything behind group gi's synchronisation (every step of it is idempotent)
 int finish_group(Batch &b, uint32_t gi)
@@ -916,44 +721,8 @@ int finish_group(Batch &b, uint32_t gi)
     }
     if (b.verify & FPNG_AMD_VERIFY_CRC32) verify.crc_partials = b.d_crc_part + (size_t)g.j0 * b.max_ranges;
     launch_dec_finish(b.s, b.d_jobs + g.j0, g.j1 - g.j0, g.plan, placed, b.d_status + g.j0, next_epoch(b.e), any_stored, b.ex != nullptr,
-                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.sizes ? nullptr : b.flt, b.crops ? b.d_crops + g.j0 : nullptr);
-    // (the resize: behind the group's pixel pass and stored copy on the same stream, on whatever the scratch then holds -- it writes
-    //  the spans of the destination and nothing else, whatever a file's status turns out to be)
-    if (b.post) {
-        // the group's direct views as the colour call launches them; its post views' windows into the scratch -- uint8, planar,
-        // un-mirrored -- and the post stage out of those into the destinations
-        const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1], p0 = b.job_post[g.j0], p1 = b.job_post[g.j1], d0 = r0 - p0, d1 = r1 - p1;
-        const uint32_t nd = (uint32_t)(b.resize.size() - b.post_recs.size());
-        uint32_t lds[2] = {0, 0};
-        bool any_filter[2] = {false, false};
-        for (uint32_t q = r0; q < r1; q++) {
-            const int kind = b.post_of[q] >= 0;
-            lds[kind] = std::max(lds[kind], b.resize_lds[q]), any_filter[kind] |= b.resize[q].filter != kResizeBilinear;
-        }
-        bool ok = launch_dec_resize_color(b.s, b.d_resize_color + d0, b.d_resize_pre + d0, b.dir_pre.data() + d0, d1 - d0, lds[0], b.flt, any_filter[0], b.hwc != nullptr) &&
-                  launch_dec_resize_color(b.s, b.d_resize_color + nd + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, lds[1], nullptr, any_filter[1], false);
-        // (the group's tone views: their histograms zeroed every time -- a group that needed more rounds comes here again -- and
-        //  counted out of the windows just written, then their tables; the post stage looks them up)
-        const uint32_t t0 = b.d_tone ? b.job_tone[g.j0] : 0, t1 = b.d_tone ? b.job_tone[g.j1] : 0;
-        if (ok && t1 > t0) {
-            HIP_TRY(hipMemsetAsync(b.d_tone + (size_t)t0 * kToneBytes, 0, (size_t)(t1 - t0) * kToneBytes, b.s));
-            ok = launch_dec_view_tone(b.s, b.d_post, b.d_tone_refs + t0, b.tone_refs.data() + t0, t1 - t0);
-        }
-        ok = ok && launch_dec_view_post(b.s, b.d_post + p0, b.d_resize_pre + nd + 1 + p0, b.post_pre.data() + p0, p1 - p0, b.flt, b.hwc != nullptr, b.enhance ? 3 : b.tone ? 2 : b.warp ? 1 : 0);
-        if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
-    } else if (b.sizes) {
-        const uint32_t r0 = b.job_rec[g.j0], r1 = b.job_rec[g.j1]; // (the records of the group's jobs)
-        const uint32_t tiles = *std::max_element(b.resize_tiles.begin() + r0, b.resize_tiles.begin() + r1), lds = *std::max_element(b.resize_lds.begin() + r0, b.resize_lds.begin() + r1);
-        // (a group of bilinear views -- the plain resize call's always are -- runs the instantiation without the second filter)
-        const bool any_filter = std::any_of(b.resize.begin() + r0, b.resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
-        // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
-        //  output per file keep the grid of the largest record)
-        const bool ok = b.color      ? launch_dec_resize_color(b.s, b.d_resize_color + r0, b.d_resize_pre + r0, b.hwc_pre.data() + r0, r1 - r0, lds, b.flt, any_filter, b.hwc != nullptr)
-                        : b.hwc      ? launch_dec_resize_hwc(b.s, b.d_resize_hwc + r0, b.d_resize_pre + r0, b.hwc_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
-                        : b.view_count ? launch_dec_resize_exact(b.s, b.d_resize + r0, b.d_resize_pre + r0, b.resize_pre.data() + r0, r1 - r0, lds, b.flt, any_filter)
-                                       : launch_dec_resize(b.s, b.d_resize + r0, r1 - r0, tiles, lds, b.flt, any_filter);
-        if (!ok) return fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
-    }
+                      b.planar ? b.d_plane_pitch + g.j0 : nullptr, b.verify ? &verify : nullptr, b.views.active() ? nullptr : b.flt, b.crops ? b.d_crops + g.j0 : nullptr);
+    if (int rc = b.views.enqueue(b.s, g.j0, g.j1, b.flt)) return rc;
     HIP_TRY(stamp(b, gi, 4));
     if (b.prof && gi == 0) b.e->dec_prof_recorded = true;
     return FPNG_AMD_OK;
@@ -1109,15 +878,10 @@ int collect_results(Batch &b)
 }
 
 // ex / planar: fpng_amd_decode_batch(_device)_ex's / _planar's files (files = their data and size; desired is not used); flt: the
-// planar files are fpng_amd_decode_batch(_device)_planar_float's; crops: ... fpng_amd_decode_batch(_device)_planar_crop's; sizes (with
-// crops): ... fpng_amd_decode_batch(_device)_planar_resize_view's (the plain resize call's: as whole-window bilinear views); view_count
-// and dests (with sizes): ... fpng_amd_decode_batch(_device)_planar_views's, whose crops, sizes and dests hold a record per view; hwc
-// in the place of dests: fpng_amd_decode_batch(_device)_hwc_views's; color (with either): the _views_color calls' matrices, one per view
+// planar files are fpng_amd_decode_batch(_device)_planar_float's; rq: what else a planar-family call carries -- the crop call's
+// crops, the resize calls' views, the views calls' records, judged and normalised (decode_files_views)
 int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint32_t desired, fpng_amd_decode_result *results, bool device_data,
-                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const fpng_amd_crop *crops = nullptr,
-                 const fpng_amd_resize_view *sizes = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                 const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
-                 const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr, const fpng_amd_view_enhance *enhance = nullptr)
+                 const fpng_amd_png_ex *ex = nullptr, const fpng_amd_png_planar *planar = nullptr, const DecFloat *flt = nullptr, const ViewRequest &rq = ViewRequest())
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     if (!ex && !planar && desired != 3 && desired != 4) return fail(FPNG_AMD_ERR_INVALID_ARG, "desired_chans must be 3 or 4");
@@ -1126,14 +890,10 @@ int decode_files(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uin
     int rc = drain(e);
     if (rc) return rc;
     Batch b{e, files, ex, n, desired, results, device_data, e->stream};
-    b.planar = planar, b.crops = crops, b.sizes = sizes, b.verify = e->dec_verify;
-    if (view_count) { // (their sum fits 32 bits: decode_files_views)
-        b.view_count = view_count, b.dests = dests, b.hwc = hwc, b.color = color, b.post = color ? post : nullptr, b.warp = b.post ? warp : nullptr, b.tone = b.post ? tone : nullptr, b.enhance = b.post ? enhance : nullptr;
-        b.view_ofs.resize(n);
-        for (uint32_t i = 0, at = 0; i < n; at += view_count[i++]) b.view_ofs[i] = at;
-    }
+    b.planar = planar, b.crops = rq.crops, b.verify = e->dec_verify;
     if (flt) b.flt = flt, b.elem = dec_float_bytes(flt->dtype);
-    if ((rc = resident_workgroups(e, b.resident))) return rc;
+    b.views.begin(rq, n, b.elem);
+    if ((rc =resident_workgroups(e, b.resident))) return rc;
     if (const char *mr = getenv("FPNG_AMD_DECODE_MAX_ROUNDS")) b.max_rounds = (uint32_t)std::max(0, atoi(mr)); // (0: every dynamic file is left to the CPU decoder -- tests)
     if ((rc = parse_files(b)) || !b.nj()) return rc;
     if ((rc = place_files(b)) || (rc = plan_groups(b)) || (rc = enqueue_groups(b)) || (rc = settle_groups(b))) return rc;
@@ -1420,19 +1180,17 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
     }
     return FPNG_AMD_OK;
 }
-// view_count, dests: fpng_amd_decode_batch(_device)_planar_views's (decode_files_views has judged the counts and the records; crops and
-// views then hold a record per view, and the destinations, which `files` leave empty, are dests')
-int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const fpng_amd_float_format *fmt = nullptr,
-                        const fpng_amd_crop *crops = nullptr, const fpng_amd_resize_view *views = nullptr, const uint32_t *view_count = nullptr, const fpng_amd_view_dest *dests = nullptr,
-                        const fpng_amd_view_dest_hwc *hwc = nullptr, const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr,
-                        const fpng_amd_view_warp *warp = nullptr, const fpng_amd_view_tone *tone = nullptr, const fpng_amd_view_enhance *enhance = nullptr)
+// rq: what the call carries besides its files (ViewRequest: nothing, the float format, crops, one view per file, or the views calls'
+// records, which decode_files_views has judged and normalised: crops and views then hold a record per view, and the destinations,
+// which `files` leave empty, are dests' or hwc's)
+int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const ViewRequest &rq)
 {
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    for (uint32_t i = 0; crops && !view_count && i < n; i++)
-        if (!crops[i].w || !crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
+    for (uint32_t i = 0; rq.crops && !rq.view_count && i < n; i++)
+        if (!rq.crops[i].w || !rq.crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
     DecFloat flt = {}; // (views: their entry points have judged them -- check_resize_records / check_view_records)
     uint32_t elem = 1;
-    if (fmt) {
+    if (const fpng_amd_float_format *fmt = rq.fmt) {
         if (fmt->dtype >= kDecFloatTypes) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown element type (FPNG_AMD_F32, _F16, _BF16)");
         if (fmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_float_format::reserved must be 0");
         for (int c = 0; c < 4; c++)
@@ -1450,19 +1208,19 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
         plain[i].data = x.data, plain[i].size = x.size, plain[i].reserved = 0, plain[i].d_pixels = x.d_pixels, plain[i].pixels_cap = x.pixels_cap;
     }
     uint64_t n_views = 0;
-    for (uint32_t i = 0; view_count && i < n; i++) n_views += view_count[i];
-    for (uint64_t v = 0; hwc && v < n_views; v++) { // (a channels-last destination's twins of the two rules below)
-        const fpng_amd_view_dest_hwc &x = hwc[v];
+    for (uint32_t i = 0; rq.view_count && i < n; i++) n_views += rq.view_count[i];
+    for (uint64_t v = 0; rq.hwc && v < n_views; v++) { // (a channels-last destination's twins of the two rules below)
+        const fpng_amd_view_dest_hwc &x = rq.hwc[v];
         if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch) & (elem - 1)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels and row_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    for (uint64_t v = 0; dests && v < n_views; v++) { // (the same two rules for every view's destination)
-        const fpng_amd_view_dest &x = dests[v];
+    for (uint64_t v = 0; rq.dests && v < n_views; v++) { // (the same two rules for every view's destination)
+        const fpng_amd_view_dest &x = rq.dests[v];
         if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (elem - 1))
             return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
         if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
     }
-    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, fmt ? &flt : nullptr, crops, views, view_count, dests, hwc, color, post, warp, tone, enhance);
+    return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, rq.fmt ? &flt : nullptr, rq);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
 static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, row_pitch) == 8 && offsetof(fpng_amd_view_dest, pixels_cap) == 24, "fpng_amd_view_dest layout");
@@ -1470,38 +1228,12 @@ static_assert(sizeof(fpng_amd_view_dest) == 32 && offsetof(fpng_amd_view_dest, r
 static_assert(sizeof(fpng_amd_view_dest_hwc) == 32 && offsetof(fpng_amd_view_dest_hwc, row_pitch) == 8 && offsetof(fpng_amd_view_dest_hwc, pixel_elems) == 16 &&
                   offsetof(fpng_amd_view_dest_hwc, flags) == 20 && offsetof(fpng_amd_view_dest_hwc, pixels_cap) == 24 && FPNG_AMD_HWC_REVERSED == kHwcReversed,
               "fpng_amd_view_dest_hwc layout");
-int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
-                       const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_dest_hwc *hwc = nullptr,
-                       const fpng_amd_view_color *color = nullptr, const fpng_amd_view_post *post = nullptr, const fpng_amd_view_warp *warp = nullptr,
-                       const fpng_amd_view_tone *tone = nullptr, const fpng_amd_view_enhance *enhance = nullptr)
-{
-    if (!files || !view_count || !crops || !views || !(dests || hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (!view_count[i]) return fail(FPNG_AMD_ERR_INVALID_ARG, "a view_count of 0 (every file has at least one view)");
-        if ((total += view_count[i]) > UINT32_MAX) return fail(FPNG_AMD_ERR_INVALID_ARG, "the sum of view_count does not fit 32 bits");
-    }
-    if (int rc = check_view_records(crops, views, (uint32_t)total)) return rc;
-    for (uint32_t i = 0; i < n; i++)
-        if (files[i].d_pixels || files[i].row_pitch || files[i].plane_pitch || files[i].pixels_cap)
-            return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_png_planar::d_pixels, row_pitch, plane_pitch and pixels_cap must be NULL / 0: the destinations are the fpng_amd_view_dest records");
-    for (uint32_t i = 0, v = 0; hwc && i < n; i++)
-        for (const uint32_t end = v + view_count[i]; v < end; v++) {
-            const uint32_t px = hwc[v].pixel_elems, c = files[i].num_chans;
-            if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
-            if (hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
-        }
-    return decode_files_planar(e, files, n, results, device_data, fmt, crops, views, view_count, dests, hwc, color, post, warp, tone, enhance);
-}
 // fpng_amd_decode_batch(_device)_planar_views_color / _hwc_views_color: the matrices are judged first -- a record per view, the sum of
 // the counts (those the views call refuses: its own message, below) -- then everything the views call judges
 static_assert(sizeof(fpng_amd_view_color) == 64 && offsetof(fpng_amd_view_color, flags) == 48 && offsetof(fpng_amd_view_color, reserved) == 52, "fpng_amd_view_color layout");
-int check_color_records(const fpng_amd_view_color *colors, const uint32_t *view_count, uint32_t n)
+int check_color_records(const fpng_amd_view_color *colors, uint64_t total)
 {
-    uint64_t total = 0;
-    bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
-    for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
-    for (uint64_t v = 0; counts_ok && v < total; v++) {
+    for (uint64_t v = 0; v < total; v++) {
         const fpng_amd_view_color &c = colors[v];
         for (int k = 0; k < 12; k++)
             if (!std::isfinite(c.m[k / 4][k % 4]) || std::fabs(c.m[k / 4][k % 4]) > kColorMaxEntry)
@@ -1510,15 +1242,6 @@ int check_color_records(const fpng_amd_view_color *colors, const uint32_t *view_
         if (c.reserved[0] | c.reserved[1] | c.reserved[2]) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_color::reserved must be 0");
     }
     return FPNG_AMD_OK;
-}
-int decode_files_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
-                             const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_float_format *fmt,
-                             fpng_amd_decode_result *results, bool device_data)
-{
-    if (!colors) return fail(FPNG_AMD_ERR_INVALID_ARG, "null colors");
-    if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
-    if (int rc = check_color_records(colors, view_count, n)) return rc;
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
 }
 // fpng_amd_decode_batch(_device)_planar_views_post / _hwc_views_post: the post records are judged first, then the matrices (NULL: the
 // identity for every view), then everything the views call judges.  w, h: the view's window, where it is known (else 0: not judged)
@@ -1542,59 +1265,105 @@ static_assert(sizeof(fpng_amd_view_post) == 32 && offsetof(fpng_amd_view_post, b
                   offsetof(fpng_amd_view_post, reserved) == 24 && FPNG_AMD_POST_BLUR == kPostBlur && FPNG_AMD_POST_SOLARIZE == kPostSolarize &&
                   FPNG_AMD_POST_POSTERIZE == kPostPosterize && FPNG_AMD_BLUR_MAX_RADIUS == kPostMaxRadius,
               "fpng_amd_view_post layout");
-int decode_files_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
-                            const fpng_amd_view_dest *dests, const fpng_amd_view_dest_hwc *hwc, const fpng_amd_view_color *colors, const fpng_amd_view_post *posts,
-                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results, bool device_data, const fpng_amd_view_warp *warps = nullptr,
-                            bool with_warps = false, const fpng_amd_view_tone *tones = nullptr, bool with_tones = false, const fpng_amd_view_enhance *enhances = nullptr,
-                            bool with_enhances = false)
+// The views calls (fpng_amd_decode_batch(_device)_{planar,hwc}_views and their _color, _post, _warp, _tone, _enhance siblings): what
+// needs no file, no encoder and no device is judged first, in this order -- the record array that names the family (the arrays in
+// front of it may be NULL: the identity, no flags, no warp, no op), the destinations, every stage's records from the last stage to
+// the first, then what the plain views call judges: the arrays, the counts, the views, the files' empty destination fields and the
+// channels-last destinations' own rules.  used: which stages some view really uses (normalise_views)
+struct StagesUsed {
+    bool post = false, warp = false, tone = false, enhance = false;
+    uint64_t total = 0; // the views of the call, where the counts are good
+};
+int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const ViewRequest &rq, const fpng_amd_decode_result *results, StagesUsed &used)
 {
-    // with_warps: the _views_warp calls' -- the warp records are judged first, and posts may be NULL (no post flags).  with_tones: the
-    // _views_tone calls' -- the tone records are judged first, and posts and warps may each be NULL.  with_enhances: the _views_enhance
-    // calls' -- the enhance records are judged first, and tones may be NULL too
-    if (with_enhances && !enhances) return fail(FPNG_AMD_ERR_INVALID_ARG, "null enhances");
-    if (with_tones && !with_enhances && !tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones");
-    if (with_warps && !with_tones && !warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps");
-    if (!with_warps && !posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts");
-    if (!dests && !hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
+    const char *const null_array = "null files, view_count, crops, views, dests or results";
+    switch (rq.family) {
+    case ViewFamily::Enhance: if (!rq.enhances) return fail(FPNG_AMD_ERR_INVALID_ARG, "null enhances"); break;
+    case ViewFamily::Tone: if (!rq.tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones"); break;
+    case ViewFamily::Warp: if (!rq.warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps"); break;
+    case ViewFamily::Post: if (!rq.posts) return fail(FPNG_AMD_ERR_INVALID_ARG, "null posts"); break;
+    case ViewFamily::Color: if (!rq.colors) return fail(FPNG_AMD_ERR_INVALID_ARG, "null colors"); break;
+    case ViewFamily::Plain: break;
+    }
+    if (rq.family != ViewFamily::Plain && !rq.dests && !rq.hwc) return fail(FPNG_AMD_ERR_INVALID_ARG, null_array);
+    const uint32_t *const view_count = rq.view_count;
+    const fpng_amd_resize_view *const views = rq.views;
     uint64_t total = 0;
-    bool counts_ok = view_count != nullptr; // (else the views call refuses the counts, and no record is read)
+    bool counts_ok = view_count != nullptr; // (else the counts are refused below, and no stage's record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
-    bool any = false, any_warp = false, any_tone = false, any_enhance = false;
-    for (uint32_t i = 0, v = 0; enhances && counts_ok && i < n; i++) // (the planes of a view's destination: its file's num_chans)
+    used.total = counts_ok ? total : 0;
+    for (uint32_t i = 0, v = 0; rq.enhances && counts_ok && i < n; i++) // (the planes of a view's destination: its file's num_chans)
         for (const uint32_t end = v + view_count[i]; v < end; v++) {
-            if (const char *why = check_enhance_record(enhances[v], files ? files[i].num_chans : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
-            any_enhance |= enhances[v].op != 0;
+            if (const char *why = check_enhance_record(rq.enhances[v], files ? files[i].num_chans : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+            used.enhance |= rq.enhances[v].op != 0;
         }
-    for (uint64_t v = 0; tones && counts_ok && v < total; v++) {
-        if (const char *why = check_tone_record(tones[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
-        any_tone |= tones[v].op != 0;
+    for (uint64_t v = 0; rq.tones && v < used.total; v++) { // (w, h: the view's window, where it is known -- else 0: not judged)
+        if (const char *why = check_tone_record(rq.tones[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        used.tone |= rq.tones[v].op != 0;
     }
-    for (uint64_t v = 0; warps && counts_ok && v < total; v++) {
-        if (const char *why = check_warp_record(warps[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
-        any_warp |= warp_moves(warps[v]);
+    for (uint64_t v = 0; rq.warps && v < used.total; v++) {
+        if (const char *why = check_warp_record(rq.warps[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        used.warp |= warp_moves(rq.warps[v]);
     }
-    for (uint64_t v = 0; posts && counts_ok && v < total; v++) {
-        if (const char *why = check_post_record(posts[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
-        any |= posts[v].flags != 0;
+    for (uint64_t v = 0; rq.posts && v < used.total; v++) {
+        if (const char *why = check_post_record(rq.posts[v], views ? views[v].w : 0u, views ? views[v].h : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        used.post |= rq.posts[v].flags != 0;
     }
-    if (colors)
-        if (int rc = check_color_records(colors, view_count, n)) return rc;
-    // (no view with a flag: the colour call, or the plain one, enqueues what it always does; no warp flag: the post call does)
-    if (!any && !any_warp && !any_tone && !any_enhance) return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors);
-    std::vector<fpng_amd_view_post> no_posts;
-    if (!posts) no_posts.assign((size_t)total, fpng_amd_view_post{}), posts = no_posts.data();
-    if (!any_warp) warps = nullptr;
-    if (!any_tone) tones = nullptr;       // (no view with an op: what the warp call enqueues)
-    if (!any_enhance) enhances = nullptr; // (no view with an op: what the tone call enqueues)
-    std::vector<fpng_amd_view_color> identity;
-    if (!colors) {
+    if (rq.colors)
+        if (int rc = check_color_records(rq.colors, used.total)) return rc;
+    if (!files || !view_count || !rq.crops || !views || !(rq.dests || rq.hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, null_array);
+    total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!view_count[i]) return fail(FPNG_AMD_ERR_INVALID_ARG, "a view_count of 0 (every file has at least one view)");
+        if ((total += view_count[i]) > UINT32_MAX) return fail(FPNG_AMD_ERR_INVALID_ARG, "the sum of view_count does not fit 32 bits");
+    }
+    if (int rc = check_view_records(rq.crops, views, (uint32_t)total)) return rc;
+    for (uint32_t i = 0; i < n; i++)
+        if (files[i].d_pixels || files[i].row_pitch || files[i].plane_pitch || files[i].pixels_cap)
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_png_planar::d_pixels, row_pitch, plane_pitch and pixels_cap must be NULL / 0: the destinations are the fpng_amd_view_dest records");
+    for (uint32_t i = 0, v = 0; rq.hwc && i < n; i++)
+        for (const uint32_t end = v + view_count[i]; v < end; v++) {
+            const uint32_t px = rq.hwc[v].pixel_elems, c = files[i].num_chans;
+            if (px && px != c && !(px == 4 && c == 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_view_dest_hwc::pixel_elems must be 0, num_chans, or 4 with num_chans = 3");
+            if (rq.hwc[v].flags & ~(uint32_t)FPNG_AMD_HWC_REVERSED) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_view_dest_hwc::flags bits");
+        }
+    return FPNG_AMD_OK;
+}
+
+// THE normalisation rule of the views calls.  No view with a post flag, a warp that moves, a tone or an enhance op: the request is
+// the colour call's (with matrices) or the plain call's (without), which enqueue what they always do.  Otherwise the request is a
+// post call's: matrices for every view (the identity where none were given), post records for every view (without flags where none
+// were given), and of warps, tones and enhances only the stages that some view uses.  `made` keeps what is supplied here alive
+struct ViewDefaults {
+    std::vector<fpng_amd_view_post> posts;
+    std::vector<fpng_amd_view_color> colors;
+};
+ViewRequest normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults &made)
+{
+    if (!used.post && !used.warp && !used.tone && !used.enhance) {
+        rq.posts = nullptr, rq.warps = nullptr, rq.tones = nullptr, rq.enhances = nullptr;
+        return rq;
+    }
+    if (!rq.posts) made.posts.assign((size_t)used.total, fpng_amd_view_post{}), rq.posts = made.posts.data();
+    if (!rq.colors) {
         fpng_amd_view_color one = {};
         one.m[0][0] = one.m[1][1] = one.m[2][2] = 1.0f;
-        identity.assign((size_t)total, one);
-        colors = identity.data();
+        made.colors.assign((size_t)used.total, one), rq.colors = made.colors.data();
     }
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, device_data, hwc, colors, posts, warps, tones, enhances);
+    if (!used.warp) rq.warps = nullptr;
+    if (!used.tone) rq.tones = nullptr;
+    if (!used.enhance) rq.enhances = nullptr;
+    return rq;
 }
+
+int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const ViewRequest &asked)
+{
+    StagesUsed used;
+    if (int rc = check_views_request(files, n, asked, results, used)) return rc;
+    ViewDefaults made;
+    return decode_files_planar(e, files, n, results, device_data, normalise_views(asked, used, made));
+}
+
 // the plain resize call's records as views: the whole of the resized crop, bilinear
 std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint32_t n)
 {
@@ -1607,37 +1376,45 @@ std::vector<fpng_amd_resize_view> whole_views(const fpng_amd_resize *sizes, uint
 extern "C" int fpng_amd_decode_batch_planar_float(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
     if (!fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null format");
-    return decode_files_planar(e, files, n, results, false, fmt);
+    ViewRequest rq;
+    rq.fmt = fmt;
+    return decode_files_planar(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_float(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
     if (!fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null format");
-    return decode_files_planar(e, files, n, results, true, fmt);
+    ViewRequest rq;
+    rq.fmt = fmt;
+    return decode_files_planar(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results)
 {
-    return decode_files_planar(e, files, n, results, false);
+    return decode_files_planar(e, files, n, results, false, ViewRequest());
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results)
 {
-    return decode_files_planar(e, files, n, results, true);
+    return decode_files_planar(e, files, n, results, true, ViewRequest());
 }
 
 extern "C" int fpng_amd_decode_batch_planar_crop(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, uint32_t n, const fpng_amd_float_format *fmt,
                                                  fpng_amd_decode_result *results)
 {
     if (!crops) return fail(FPNG_AMD_ERR_INVALID_ARG, "null crops");
-    return decode_files_planar(e, files, n, results, false, fmt, crops);
+    ViewRequest rq;
+    rq.fmt = fmt, rq.crops = crops;
+    return decode_files_planar(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_crop(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, uint32_t n, const fpng_amd_float_format *fmt,
                                                         fpng_amd_decode_result *results)
 {
     if (!crops) return fail(FPNG_AMD_ERR_INVALID_ARG, "null crops");
-    return decode_files_planar(e, files, n, results, true, fmt, crops);
+    ViewRequest rq;
+    rq.fmt = fmt, rq.crops = crops;
+    return decode_files_planar(e, files, n, results, true, rq);
 }
 
 // (the records are judged first: their refusals need neither an encoder nor a device)
@@ -1646,7 +1423,10 @@ extern "C" int fpng_amd_decode_batch_planar_resize(fpng_amd_encoder *e, const fp
 {
     if (!crops || !sizes) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null sizes" : "null crops");
     if (int rc = check_resize_records(crops, sizes, n)) return rc;
-    return decode_files_planar(e, files, n, results, false, fmt, crops, whole_views(sizes, n).data());
+    const std::vector<fpng_amd_resize_view> views = whole_views(sizes, n);
+    ViewRequest rq;
+    rq.fmt = fmt, rq.crops = crops, rq.views = views.data();
+    return decode_files_planar(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize *sizes, uint32_t n,
@@ -1654,7 +1434,10 @@ extern "C" int fpng_amd_decode_batch_device_planar_resize(fpng_amd_encoder *e, c
 {
     if (!crops || !sizes) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null sizes" : "null crops");
     if (int rc = check_resize_records(crops, sizes, n)) return rc;
-    return decode_files_planar(e, files, n, results, true, fmt, crops, whole_views(sizes, n).data());
+    const std::vector<fpng_amd_resize_view> views = whole_views(sizes, n);
+    ViewRequest rq;
+    rq.fmt = fmt, rq.crops = crops, rq.views = views.data();
+    return decode_files_planar(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar_resize_view(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t n,
@@ -1662,7 +1445,9 @@ extern "C" int fpng_amd_decode_batch_planar_resize_view(fpng_amd_encoder *e, con
 {
     if (!crops || !views) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null views" : "null crops");
     if (int rc = check_view_records(crops, views, n)) return rc;
-    return decode_files_planar(e, files, n, results, false, fmt, crops, views);
+    ViewRequest rq;
+    rq.fmt = fmt, rq.crops = crops, rq.views = views;
+    return decode_files_planar(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_resize_view(fpng_amd_encoder *e, const fpng_amd_png_planar *files, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
@@ -1670,91 +1455,117 @@ extern "C" int fpng_amd_decode_batch_device_planar_resize_view(fpng_amd_encoder 
 {
     if (!crops || !views) return fail(FPNG_AMD_ERR_INVALID_ARG, crops ? "null views" : "null crops");
     if (int rc = check_view_records(crops, views, n)) return rc;
-    return decode_files_planar(e, files, n, results, true, fmt, crops, views);
+    ViewRequest rq;
+    rq.fmt = fmt, rq.crops = crops, rq.views = views;
+    return decode_files_planar(e, files, n, results, true, rq);
 }
 
+// ---- the views calls: each fills its request by name -- the family, the destinations' layout (dests: planar, hwc: channels-last)
+//      and the record arrays its signature takes -- and decode_files_views does the rest ----
 extern "C" int fpng_amd_decode_batch_planar_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                   const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, false);
+    ViewRequest rq;
+    rq.family = ViewFamily::Plain, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                          const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_float_format *fmt,
                                                          fpng_amd_decode_result *results)
 {
-    return decode_files_views(e, files, n, view_count, crops, views, dests, fmt, results, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Plain, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    if (!dests) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
-    return decode_files_views(e, files, n, view_count, crops, views, nullptr, fmt, results, false, dests);
+    ViewRequest rq;
+    rq.family = ViewFamily::Plain, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_hwc_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                       const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_float_format *fmt,
                                                       fpng_amd_decode_result *results)
 {
-    if (!dests) return fail(FPNG_AMD_ERR_INVALID_ARG, "null files, view_count, crops, views, dests or results");
-    return decode_files_views(e, files, n, view_count, crops, views, nullptr, fmt, results, true, dests);
+    ViewRequest rq;
+    rq.family = ViewFamily::Plain, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                         const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
                                                         const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_color(e, files, n, view_count, crops, views, dests, nullptr, colors, fmt, results, false);
+    ViewRequest rq;
+    rq.family = ViewFamily::Color, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                                const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
                                                                const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_color(e, files, n, view_count, crops, views, dests, nullptr, colors, fmt, results, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Color, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                      const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
                                                      const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_color(e, files, n, view_count, crops, views, nullptr, dests, colors, fmt, results, false);
+    ViewRequest rq;
+    rq.family = ViewFamily::Color, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_hwc_views_color(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                             const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
                                                             const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_color(e, files, n, view_count, crops, views, nullptr, dests, colors, fmt, results, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Color, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                        const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
                                                        const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false);
+    ViewRequest rq;
+    rq.family = ViewFamily::Post, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                               const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
                                                               const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Post, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                     const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
                                                     const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false);
+    ViewRequest rq;
+    rq.family = ViewFamily::Post, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_hwc_views_post(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
                                                            const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
                                                            const fpng_amd_view_post *posts, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Post, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1762,7 +1573,9 @@ extern "C" int fpng_amd_decode_batch_planar_views_warp(fpng_amd_encoder *e, cons
                                                        const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
                                                        fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false, warps, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Warp, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1770,7 +1583,9 @@ extern "C" int fpng_amd_decode_batch_device_planar_views_warp(fpng_amd_encoder *
                                                               const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
                                                               fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true, warps, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Warp, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1778,7 +1593,9 @@ extern "C" int fpng_amd_decode_batch_hwc_views_warp(fpng_amd_encoder *e, const f
                                                     const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
                                                     fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false, warps, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Warp, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_hwc_views_warp(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1786,7 +1603,9 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_warp(fpng_amd_encoder *e, 
                                                            const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_float_format *fmt,
                                                            fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Warp, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1794,7 +1613,9 @@ extern "C" int fpng_amd_decode_batch_planar_views_tone(fpng_amd_encoder *e, cons
                                                        const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
                                                        const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false, warps, true, tones, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Tone, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1802,7 +1623,9 @@ extern "C" int fpng_amd_decode_batch_device_planar_views_tone(fpng_amd_encoder *
                                                               const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
                                                               const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true, warps, true, tones, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Tone, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1810,7 +1633,9 @@ extern "C" int fpng_amd_decode_batch_hwc_views_tone(fpng_amd_encoder *e, const f
                                                     const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
                                                     const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false, warps, true, tones, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Tone, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_hwc_views_tone(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1818,7 +1643,9 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_tone(fpng_amd_encoder *e, 
                                                            const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
                                                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true, tones, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Tone, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_planar_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1826,7 +1653,9 @@ extern "C" int fpng_amd_decode_batch_planar_views_enhance(fpng_amd_encoder *e, c
                                                           const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
                                                           const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, false, warps, true, tones, true, enhances, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Enhance, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_planar_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
@@ -1835,7 +1664,9 @@ extern "C" int fpng_amd_decode_batch_device_planar_views_enhance(fpng_amd_encode
                                                                  const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt,
                                                                  fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, dests, nullptr, colors, posts, fmt, results, true, warps, true, tones, true, enhances, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Enhance, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
@@ -1843,7 +1674,9 @@ extern "C" int fpng_amd_decode_batch_hwc_views_enhance(fpng_amd_encoder *e, cons
                                                        const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
                                                        const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, false, warps, true, tones, true, enhances, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Enhance, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances;
+    return decode_files_views(e, files, n, results, false, rq);
 }
 
 extern "C" int fpng_amd_decode_batch_device_hwc_views_enhance(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
@@ -1852,7 +1685,9 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_enhance(fpng_amd_encoder *
                                                               const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_float_format *fmt,
                                                               fpng_amd_decode_result *results)
 {
-    return decode_files_views_post(e, files, n, view_count, crops, views, nullptr, dests, colors, posts, fmt, results, true, warps, true, tones, true, enhances, true);
+    ViewRequest rq;
+    rq.family = ViewFamily::Enhance, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances;
+    return decode_files_views(e, files, n, results, true, rq);
 }
 
 // the enhance rule on the host: the texts of view_enhance.h, which dec_view_post_kernel runs

@@ -36,4 +36,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   color_matrix, color_apply, view_post, blur_weights, view_post_apply,
                   view_warp, view_warp_apply, affine_matrix,
                   view_tone, view_tone_lut, view_tone_apply,
-                  view_enhance, view_enhance_apply, rotate_matrix, augment_op)
+                  view_enhance, view_enhance_apply, rotate_matrix, augment_op,
+                  view_alpha, view_alpha_source, view_alpha_result)

@@ -117,9 +117,14 @@ class ViewEnhance(C.Structure):  # fpng_amd_view_enhance: 16 bytes, the enhance 
     _fields_ = [("op", C.c_uint32), ("factor", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class ViewAlpha(C.Structure):  # fpng_amd_view_alpha: 16 bytes, the alpha record of ONE view of the _views_alpha calls
+    _fields_ = [("op", C.c_uint32), ("background", C.c_uint8 * 4), ("reserved", C.c_uint32 * 2)]
+
+
 POST_BLUR, POST_SOLARIZE, POST_POSTERIZE = 1, 2, 4  # FPNG_AMD_POST_*
 TONE_AUTOCONTRAST, TONE_EQUALIZE, TONE_CONTRAST = 1, 2, 3  # FPNG_AMD_TONE_*
 ENHANCE_BRIGHTNESS, ENHANCE_COLOR, ENHANCE_SHARPNESS = 1, 2, 3  # FPNG_AMD_ENHANCE_*
+ALPHA_COMPOSITE, ALPHA_PREMULTIPLIED = 1, 2  # FPNG_AMD_ALPHA_*
 WARP_AFFINE, WARP_BILINEAR = 1, 2  # FPNG_AMD_WARP_*
 BLUR_MAX_RADIUS = 16  # FPNG_AMD_BLUR_MAX_RADIUS
 HWC_REVERSED = 1  # FPNG_AMD_HWC_REVERSED
@@ -251,6 +256,8 @@ SIGNATURES = {
     "fpng_amd_view_tone_lut": (_int, [C.POINTER(ViewTone), C.c_void_p, C.c_void_p]),
     "fpng_amd_view_tone_apply": (_int, [C.POINTER(ViewTone), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_view_enhance_apply": (_int, [C.POINTER(ViewEnhance), _u32, _u32, C.c_void_p, C.c_void_p]),
+    "fpng_amd_view_alpha_source": (_int, [C.POINTER(ViewAlpha), _u32, _u32, C.c_void_p, C.c_void_p]),
+    "fpng_amd_view_alpha_result": (_int, [C.POINTER(ViewAlpha), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_blur_weights": (_int, [_u32, C.c_double, C.POINTER(C.c_int32 * 17)]),
     "fpng_amd_view_post_apply": (_int, [C.POINTER(ViewPost), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_color_apply": (None, [C.POINTER(ViewColor), C.POINTER(C.c_uint8 * 3), C.POINTER(C.c_float * 3)]),
@@ -274,7 +281,7 @@ SIGNATURES = {
 
 # The views calls: fpng_amd_decode_batch(_device)_{planar,hwc}_views<suffix>.  A stage's call takes the record arrays of every stage up
 # to and including its own, in this order, between the destinations and the float format.
-VIEW_STAGES = (("_color", ViewColor), ("_post", ViewPost), ("_warp", ViewWarp), ("_tone", ViewTone), ("_enhance", ViewEnhance))
+VIEW_STAGES = (("_color", ViewColor), ("_post", ViewPost), ("_warp", ViewWarp), ("_tone", ViewTone), ("_enhance", ViewEnhance), ("_alpha", ViewAlpha))
 VIEW_LAYOUTS = (("planar", ViewDest), ("hwc", ViewDestHwc))
 
 

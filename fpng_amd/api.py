@@ -746,6 +746,55 @@ def view_enhance_apply(enhance, planes):
     return out
 
 
+def view_alpha(op=None, background=(0, 0, 0)):
+    """The fpng_amd_view_alpha record of one view of the views calls' alpha= argument: what the view does with the fourth plane of a
+    4-channel file, inside the resize.  op="composite": every sample is put over the opaque `background` (R, G, B bytes) first, as
+    Image.alpha_composite(Image.new("RGBA", im.size, background + (255,)), im) does, then cropped and resized; a fourth destination
+    plane is 255.  op="premultiplied": Pillow's Image.resize of an RGBA image -- RGBA -> RGBa, resample, RGBa -> RGBA.  op=None: the
+    view is the enhance call's, untouched (alpha resized on its own, or dropped).  On a 3-channel file every op is op None."""
+    ops = {None: 0, "composite": _lib.ALPHA_COMPOSITE, "premultiplied": _lib.ALPHA_PREMULTIPLIED}
+    if not (op is None or isinstance(op, str)) or op not in ops:
+        raise ValueError(f"view_alpha: op is None, 'composite' or 'premultiplied', not {op!r}")
+    try:
+        bg = [int(b) for b in background]
+        if len(bg) != 3 or any(b != f for b, f in zip(bg, background)) or not all(0 <= b <= 255 for b in bg):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"view_alpha: background is three integers 0 .. 255 (R, G, B), not {background!r}") from None
+    if ops[op] != _lib.ALPHA_COMPOSITE and any(bg):
+        raise ValueError("view_alpha: a background goes with op='composite'")
+    rec = _lib.ViewAlpha()
+    rec.op = ops[op]
+    for k in range(3):
+        rec.background[k] = bg[k]
+    return rec
+
+
+def _view_alpha_twin(who, symbol, alpha, planes):
+    if not isinstance(alpha, _lib.ViewAlpha):
+        raise ValueError(f"{who}: alpha is what view_alpha() returns")
+    px = np.asarray(planes)
+    if px.dtype != np.uint8 or px.ndim != 3 or px.shape[0] != 4 or px.size == 0:
+        raise ValueError(f"{who}: planes is (4, h, w) uint8, not {px.shape} {px.dtype}")
+    px = np.ascontiguousarray(px)
+    out = np.empty_like(px)
+    check(getattr(_lib.load(), symbol)(C.byref(alpha), px.shape[2], px.shape[1], px.ctypes.data, out.ctypes.data))
+    return out
+
+
+def view_alpha_source(alpha, planes):
+    """fpng_amd_view_alpha_source, the host twin of the alpha stage's load (no GPU): planes (4, h, w) uint8 -- a crop's four planes --
+    -> (4, h, w) uint8, what the resize of a view with `alpha` (a view_alpha() record) reads: composited over the background with
+    255 in the fourth plane, premultiplied, or a copy."""
+    return _view_alpha_twin("view_alpha_source", "fpng_amd_view_alpha_source", alpha, planes)
+
+
+def view_alpha_result(alpha, planes):
+    """fpng_amd_view_alpha_result, the host twin of the alpha stage's store (no GPU): planes (4, h, w) uint8 -- the resize's four
+    result planes -- -> (4, h, w) uint8, what the later stages see: divided by the fourth plane for a premultiplied view, else a copy."""
+    return _view_alpha_twin("view_alpha_result", "fpng_amd_view_alpha_result", alpha, planes)
+
+
 def rotate_matrix(w, h, angle):
     """The six coefficients for view_warp() that Pillow's Image.rotate(angle) (no expand, the default centre, no translate) hands to
     transform() for a w x h image, computed as Pillow computes them: the cosine and sine of -radians(angle % 360) rounded to 15
@@ -1152,6 +1201,7 @@ class _DecodeBatchMultiViews(_DecodeBatchViews):
     warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
     tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
     enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
+    alphas = None  # the fpng_amd_view_alpha records of a descriptor made with alpha=, one per view: the call is then the _views_alpha one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
         super().__init__(pngs, outs, arr, res, device_data, keep)
@@ -1214,7 +1264,7 @@ _PLANAR_VIEWS = _ViewsLayout("planar", "", _lib.ViewDest, DecodeBatchMultiView, 
 _HWC_VIEWS = _ViewsLayout("hwc", "_hwc", _lib.ViewDestHwc, DecodeBatchMultiViewHwc, _hwc_view_dest, lambda s: (s[2], s[0], s[1]), lambda oh, ow: (oh, ow, 3))
 
 
-def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance):
+def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha=None):
     """the descriptor of a views call for either layout (Encoder.make_decode_batch_views / _hwc have the rules)"""
     who = layout.maker
     n = len(pngs)
@@ -1283,14 +1333,16 @@ def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, o
         batch.tones = _view_records(who, counts, tone, _lib.ViewTone, "tone")
     if enhance is not None:
         batch.enhances = _view_records(who, counts, enhance, _lib.ViewEnhance, "enhance")
+    if alpha is not None:
+        batch.alphas = _view_records(who, counts, alpha, _lib.ViewAlpha, "alpha")
     return batch
 
 
 def views_entry(layout, device_data, batch):
     """The C entry point of a views call and its arguments behind the encoder, as a pure function of the layout ("planar" / "hwc"),
-    where the files are and the descriptor: the last stage in the order colour < post < warp < tone < enhance whose records the
+    where the files are and the descriptor: the last stage in the order colour < post < warp < tone < enhance < alpha whose records the
     descriptor carries names the call, and the call takes the record arrays of all stages up to it (None for those not given)."""
-    arrays = [batch.colors, batch.posts, batch.warps, batch.tones, batch.enhances]
+    arrays = [batch.colors, batch.posts, batch.warps, batch.tones, batch.enhances, batch.alphas]
     stages = max((k + 1 for k, a in enumerate(arrays) if a is not None), default=0)
     fmt = C.byref(batch.fmt) if batch.fmt is not None else None
     return _lib.views_symbol(layout, device_data, stages), [batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, *arrays[:stages], fmt, batch.res]
@@ -2172,7 +2224,7 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None):
+                                scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
@@ -2189,18 +2241,21 @@ class Encoder:
         views' tone records (view_tone() makes them), nested as post's; the descriptor then goes through
         fpng_amd_decode_batch(_device)_planar_views_tone, with the others' records or without.  enhance: None, or the views' enhance
         records (view_enhance() makes them), nested as post's; the descriptor then goes through
-        fpng_amd_decode_batch(_device)_planar_views_enhance, with the others' records or without."""
-        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
+        fpng_amd_decode_batch(_device)_planar_views_enhance, with the others' records or without.  alpha: None, or the views' alpha
+        records (view_alpha() makes them), nested as post's; the descriptor then goes through
+        fpng_amd_decode_batch(_device)_planar_views_alpha, with the others' records or without."""
+        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha)
 
     def _decode_views(self, layout, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                      tone, enhance):
+                      tone, enhance, alpha):
         """a views call of either layout (_ViewsLayout), for files in device or host memory"""
         who = layout.device if device_data else layout.host
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, layout.batch_cls):
             raise ValueError(f"{who}: a descriptor of another call ({layout.maker}() makes this one's)")
         if isinstance(pngs, layout.batch_cls):
-            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone and enhance records ({layout.maker}(..., color=, post=, warp=, tone=, enhance=))")
+            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None or alpha is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone, enhance and alpha records "
+                                 f"({layout.maker}(..., color=, post=, warp=, tone=, enhance=, alpha=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2213,7 +2268,7 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty(layout.empty_shape(oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
+            batch = _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + (f"host memory ({layout.host})" if device_data else f"device memory ({layout.device})"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
@@ -2224,7 +2279,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -2252,30 +2307,36 @@ class Encoder:
         call's without.
         enhance: None, or an enhance record per view (view_enhance() makes them: brightness, color or sharpness as Pillow's
         ImageEnhance does them; nested as post's), applied to the bytes behind the tone operation and in front of the blur --
-        fpng_amd_decode_batch_device_planar_views_enhance; a record without an op leaves its view exactly the call's without."""
+        fpng_amd_decode_batch_device_planar_views_enhance; a record without an op leaves its view exactly the call's without.
+        alpha: None, or an alpha record per view (view_alpha() makes them; nested as post's): what the view does with the fourth
+        plane of a 4-channel file, inside the resize and in front of every other stage -- "composite" over an opaque background
+        colour as Image.alpha_composite does and then resize, or resize "premultiplied" as Image.resize of an RGBA image does --
+        fpng_amd_decode_batch_device_planar_views_alpha; a record without an op, and any record on a 3-channel file, leaves its
+        view exactly the call's without."""
         return self._decode_views(_PLANAR_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance)
+                                  tone, enhance, alpha)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views(_PLANAR_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance)
+                                  tone, enhance, alpha)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None):
+                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
         value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
         fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post), warp (then:
-        fpng_amd_decode_batch(_device)_hwc_views_warp), tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone) and enhance (then:
-        fpng_amd_decode_batch(_device)_hwc_views_enhance) -- is make_decode_batch_views()'s."""
-        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance)
+        fpng_amd_decode_batch(_device)_hwc_views_warp), tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone), enhance (then:
+        fpng_amd_decode_batch(_device)_hwc_views_enhance) and alpha (then: fpng_amd_decode_batch(_device)_hwc_views_alpha) -- is
+        make_decode_batch_views()'s."""
+        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha)
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -2289,13 +2350,13 @@ class Encoder:
         None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
         return self._decode_views(_HWC_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance)
+                                  tone, enhance, alpha)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views(_HWC_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance)
+                                  tone, enhance, alpha)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

@@ -420,6 +420,8 @@ int parse_files(Batch &b)
         const uint32_t desired = b.planar ? b.planar[i].num_chans : b.ex ? kDstFormats[b.ex[i].format].bytes : b.desired;
         const uint64_t need = (uint64_t)p.w * p.h * desired;
         if ((r.status = file_status(p, st, need))) continue;
+        // (what the job decodes: the destination's planes; with an alpha view of a 4-channel file all four of them)
+        const uint32_t job_planes = b.views.active() ? b.views.job_planes(i, p.c, desired) : desired;
         // (a crop that leaves the image: the file's own outcome -- it is not decoded and needs no room)
         DecCrop crop = {0, 0, p.w, p.h};
         uint32_t crop_nseg = 0, crop_cb0 = 0, crop_ncb = 0;
@@ -449,7 +451,7 @@ int parse_files(Batch &b)
             if (d.refused) return fail(d.refused.code, d.refused.why);
             pitch = d.pitch, plane_pitch = d.plane_pitch;
         } else if (b.planar) {
-            if (const Refusal no = b.views.file_records(i, f, b.planar[i], desired, crop)) return fail(no.code, no.why);
+            if (const Refusal no = b.views.file_records(i, f, b.planar[i], desired, crop, p.c)) return fail(no.code, no.why);
         } else if (b.ex) {
             const uint64_t row = (uint64_t)p.w * desired;
             pitch = b.ex[i].row_pitch ? b.ex[i].row_pitch : (int64_t)row;
@@ -463,11 +465,11 @@ int parse_files(Batch &b)
             continue;
         }
         if (!p.mode) p.lut = b.luts.find_or_add(sizes);
-        DecJob j = make_job(p, desired);
+        DecJob j = make_job(p, job_planes);
         j.out = f.d_pixels, j.sub_base = b.sub_total;
         if (b.ex) j.sel = kDstFormats[b.ex[i].format].sel, j.pitch = (int32_t)pitch; // (|pitch| < 2^31: decode_files)
         if (b.views.active()) { // (the job writes its box's planes into the scratch: an offset until place_files())
-            j.out = (uint8_t *)(uintptr_t)b.views.add_job(i, desired, crop);
+            j.out = (uint8_t *)(uintptr_t)b.views.add_job(i, desired, crop, job_planes);
             pitch = (int64_t)crop.w, plane_pitch = (int64_t)((uint64_t)crop.w * crop.h);
         }
         if (b.planar) j.pitch = (int32_t)pitch, b.plane_pitch.push_back(plane_pitch); // (|pitch| < 2^31: decode_files_planar)
@@ -670,13 +672,13 @@ int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const D
         const uint32_t p0 = job_post[j0], p1 = job_post[j1], d0 = r0 - p0, d1 = r1 - p1;
         const uint32_t nd = (uint32_t)(resize.size() - post_recs.size());
         uint32_t most_lds[2] = {0, 0};
-        bool any_filter[2] = {false, false};
+        bool any_filter[2] = {false, false}, any_alpha[2] = {false, false};
         for (uint32_t q = r0; q < r1; q++) {
             const int kind = post_of[q] >= 0;
-            most_lds[kind] = std::max(most_lds[kind], lds[q]), any_filter[kind] |= resize[q].filter != kResizeBilinear;
+            most_lds[kind] = std::max(most_lds[kind], lds[q]), any_filter[kind] |= resize[q].filter != kResizeBilinear, any_alpha[kind] |= resize_alpha_op(resize[q].flags) != 0;
         }
-        ok = launch_dec_resize_color(s, recs + d0, d_pre + d0, dir_pre.data() + d0, d1 - d0, most_lds[0], flt, any_filter[0], hwc()) &&
-             launch_dec_resize_color(s, recs + nd + p0, d_pre + nd + 1 + p0, post_pre.data() + p0, p1 - p0, most_lds[1], nullptr, any_filter[1], false);
+        ok = launch_dec_resize_color(s, recs + d0, d_pre + d0, dir_pre.data() + d0, d1 - d0, most_lds[0], flt, any_filter[0], hwc(), any_alpha[0]) &&
+             launch_dec_resize_color(s, recs + nd + p0, d_pre + nd + 1 + p0, post_pre.data() + p0, p1 - p0, most_lds[1], nullptr, any_filter[1], false, any_alpha[1]);
         // (the group's tone views: their histograms zeroed every time -- a group that needed more rounds comes here again -- and
         //  counted out of the windows just written, then their tables; the post stage looks them up)
         const uint32_t t0 = d_tone ? job_tone[j0] : 0, t1 = d_tone ? job_tone[j1] : 0;
@@ -691,9 +693,14 @@ int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const D
         const bool any_filter = std::any_of(resize.begin() + r0, resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
         // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
         //  output per file keep the grid of the largest record)
-        ok = rq.colors ? launch_dec_resize_color(s, (const DecResizeColor *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, hwc())
-             : hwc()   ? launch_dec_resize_hwc(s, (const DecResizeHwc *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter)
-             : multi() ? launch_dec_resize_exact(s, (const DecResize *)d_recs + r0, d_pre + r0, plane_pre.data() + r0, r1 - r0, most_lds, flt, any_filter)
+        // (and a group without an alpha op -- every call but the _alpha ones, and those without one -- the instantiations without the stage)
+        const bool any_alpha = std::any_of(resize.begin() + r0, resize.begin() + r1, [](const DecResize &r) { return resize_alpha_op(r.flags) != 0; });
+        // (the per-plane kernels have no PREMULTIPLIED store: normalise_views sends such a request to the colour kernel)
+        if (!per_tile() && std::any_of(resize.begin() + r0, resize.begin() + r1, [](const DecResize &r) { return resize_alpha_op(r.flags) == kAlphaPremultiplied; }))
+            return fail(FPNG_AMD_ERR_UNSUPPORTED, "a premultiplied view in a per-plane resize launch");
+        ok = rq.colors ? launch_dec_resize_color(s, (const DecResizeColor *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, hwc(), any_alpha)
+             : hwc()   ? launch_dec_resize_hwc(s, (const DecResizeHwc *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, any_alpha)
+             : multi() ? launch_dec_resize_exact(s, (const DecResize *)d_recs + r0, d_pre + r0, plane_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, any_alpha)
                        : launch_dec_resize(s, (const DecResize *)d_recs + r0, r1 - r0, most_tiles, most_lds, flt, any_filter);
     }
     return ok ? FPNG_AMD_OK : fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
@@ -1278,6 +1285,7 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
 {
     const char *const null_array = "null files, view_count, crops, views, dests or results";
     switch (rq.family) {
+    case ViewFamily::Alpha: if (!rq.alphas) return fail(FPNG_AMD_ERR_INVALID_ARG, "null alphas"); break;
     case ViewFamily::Enhance: if (!rq.enhances) return fail(FPNG_AMD_ERR_INVALID_ARG, "null enhances"); break;
     case ViewFamily::Tone: if (!rq.tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones"); break;
     case ViewFamily::Warp: if (!rq.warps) return fail(FPNG_AMD_ERR_INVALID_ARG, "null warps"); break;
@@ -1292,6 +1300,8 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
     bool counts_ok = view_count != nullptr; // (else the counts are refused below, and no stage's record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
     used.total = counts_ok ? total : 0;
+    for (uint64_t v = 0; rq.alphas && v < used.total; v++)
+        if (const char *why = check_alpha_record(rq.alphas[v])) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
     for (uint32_t i = 0, v = 0; rq.enhances && counts_ok && i < n; i++) // (the planes of a view's destination: its file's num_chans)
         for (const uint32_t end = v + view_count[i]; v < end; v++) {
             if (const char *why = check_enhance_record(rq.enhances[v], files ? files[i].num_chans : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
@@ -1333,23 +1343,32 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
 // THE normalisation rule of the views calls.  No view with a post flag, a warp that moves, a tone or an enhance op: the request is
 // the colour call's (with matrices) or the plain call's (without), which enqueue what they always do.  Otherwise the request is a
 // post call's: matrices for every view (the identity where none were given), post records for every view (without flags where none
-// were given), and of warps, tones and enhances only the stages that some view uses.  `made` keeps what is supplied here alive
+// were given), and of warps, tones and enhances only the stages that some view uses.  The alpha records are no post stage: they
+// travel inside the resize records of whichever call the request becomes, and a request in which no record has an op drops them.
+// One op chooses the kernel: a PREMULTIPLIED view divides its colour planes by its alpha plane's result at the store, which a
+// kernel with all of a sample's planes in one thread can do and the per-plane kernel of the plain planar call cannot, so a planar
+// request with such a view and without matrices becomes the colour call's under identity matrices -- bit for bit the plain call's
+// elements, at the plain call's speed (profiles/views_color_timing.txt).  `made` keeps what is supplied here alive
 struct ViewDefaults {
     std::vector<fpng_amd_view_post> posts;
     std::vector<fpng_amd_view_color> colors;
 };
 ViewRequest normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults &made)
 {
+    const auto identity_colors = [&] {
+        fpng_amd_view_color one = {};
+        one.m[0][0] = one.m[1][1] = one.m[2][2] = 1.0f;
+        made.colors.assign((size_t)used.total, one), rq.colors = made.colors.data();
+    };
+    if (rq.alphas && std::none_of(rq.alphas, rq.alphas + used.total, [](const fpng_amd_view_alpha &a) { return a.op != 0; })) rq.alphas = nullptr;
+    if (rq.alphas && !rq.colors && !rq.hwc && std::any_of(rq.alphas, rq.alphas + used.total, [](const fpng_amd_view_alpha &a) { return a.op == kAlphaPremultiplied; }))
+        identity_colors();
     if (!used.post && !used.warp && !used.tone && !used.enhance) {
         rq.posts = nullptr, rq.warps = nullptr, rq.tones = nullptr, rq.enhances = nullptr;
         return rq;
     }
     if (!rq.posts) made.posts.assign((size_t)used.total, fpng_amd_view_post{}), rq.posts = made.posts.data();
-    if (!rq.colors) {
-        fpng_amd_view_color one = {};
-        one.m[0][0] = one.m[1][1] = one.m[2][2] = 1.0f;
-        made.colors.assign((size_t)used.total, one), rq.colors = made.colors.data();
-    }
+    if (!rq.colors) identity_colors();
     if (!used.warp) rq.warps = nullptr;
     if (!used.tone) rq.tones = nullptr;
     if (!used.enhance) rq.enhances = nullptr;
@@ -1688,6 +1707,68 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_enhance(fpng_amd_encoder *
     ViewRequest rq;
     rq.family = ViewFamily::Enhance, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances;
     return decode_files_views(e, files, n, results, true, rq);
+}
+
+static_assert(sizeof(fpng_amd_view_alpha) == 16 && offsetof(fpng_amd_view_alpha, background) == 4 && offsetof(fpng_amd_view_alpha, reserved) == 8 &&
+                  FPNG_AMD_ALPHA_COMPOSITE == kAlphaComposite && FPNG_AMD_ALPHA_PREMULTIPLIED == kAlphaPremultiplied,
+              "fpng_amd_view_alpha layout");
+extern "C" int fpng_amd_decode_batch_planar_views_alpha(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                        const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                        const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                        const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas, const fpng_amd_float_format *fmt,
+                                                        fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Alpha, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas;
+    return decode_files_views(e, files, n, results, false, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_alpha(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                               const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                               const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                               const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas,
+                                                               const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Alpha, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas;
+    return decode_files_views(e, files, n, results, true, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_alpha(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                     const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                     const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                     const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas, const fpng_amd_float_format *fmt,
+                                                     fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Alpha, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas;
+    return decode_files_views(e, files, n, results, false, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_alpha(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                            const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                            const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                            const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas,
+                                                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Alpha, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas;
+    return decode_files_views(e, files, n, results, true, rq);
+}
+
+// the alpha rule on the host: the texts of view_alpha.h, which the resize kernels run in their load (source) and store (result)
+extern "C" int fpng_amd_view_alpha_source(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out)
+{
+    const char *why = nullptr;
+    const int rc = alpha_twin_checked(alpha, w, h, in, out, false, &why);
+    return rc ? fail(rc, why) : FPNG_AMD_OK;
+}
+
+extern "C" int fpng_amd_view_alpha_result(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out)
+{
+    const char *why = nullptr;
+    const int rc = alpha_twin_checked(alpha, w, h, in, out, true, &why);
+    return rc ? fail(rc, why) : FPNG_AMD_OK;
 }
 
 // the enhance rule on the host: the texts of view_enhance.h, which dec_view_post_kernel runs

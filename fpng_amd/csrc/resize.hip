@@ -22,6 +22,7 @@
 #include "float_store.h"
 #include "resize.h"
 #include "resize_hwc.h"
+#include "view_alpha.h"
 
 #include <hip/hip_runtime.h>
 
@@ -33,8 +34,13 @@ namespace {
 
 // One tile of one plane of one record: the kernels below find the three and hand them over.
 // kAnyFilter: the launch's records may ask for the bicubic filter; false: all of them are bilinear (the plain resize call's launches,
-// and a view call's whose files are), and the kernel holds the triangle's weight code alone
-template <int kDtype, bool kAnyFilter>
+// and a view call's whose files are), and the kernel holds the triangle's weight code alone.
+// kAlpha: the launch's records may carry the COMPOSITE alpha op (view_alpha.h; the _views_alpha calls' launches that hold such a
+// view): the load of the horizontal pass makes P' of the plane's and the alpha plane's bytes at the same offset.  A workgroup has
+// one plane, so the PREMULTIPLIED op, whose store divides a colour plane's result by the alpha plane's, never comes here: a planar
+// call with such a view runs dec_resize_color_kernel under identity matrices (decode_api.cpp: normalise_views).  false: the kernel
+// that was there before there was an alpha stage
+template <int kDtype, bool kAnyFilter, bool kAlpha = false>
 __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t plane, uint32_t tile, const DecFloat &flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
@@ -64,12 +70,17 @@ __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t pla
     const uint32_t nrows = std::min(fy[nq - 1] + cy[nq - 1] - row0, r.rows); // (the host's bound holds: T has r.rows rows)
     const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
     const uint8_t *const P = r.src + (uint64_t)plane * r.src_plane_pitch;
+    // (COMPOSITE, or no op: a PREMULTIPLIED view needs R'_3 next to its colour planes and goes to an all-planes kernel -- the host's rule)
+    [[maybe_unused]] const uint32_t a_mode = kAlpha ? alpha_load_mode(resize_alpha_op(r.flags), plane) : kAlphaLoadRaw;
     {
         const uint32_t first = fx[o], count = cx[o];
         for (uint32_t j = wave; j < nrows; j += kResizeBlock / kResizeTileW) {
             const uint8_t *s = P + (uint64_t)(row0 + j) * r.src_pitch + first;
             int32_t sum = 1 << (kResizeBits - 1);
-            for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
+            if constexpr (kAlpha) // (the sum over P'; the alpha plane's byte: the same offset, 3 - plane planes on)
+                sum = alpha_pass_sum(a_mode, s, s + (uint64_t)(3u - plane) * r.src_plane_pitch, resize_alpha_bg(r.flags, plane), count, Kx + o, kResizeTileW);
+            else
+                for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
             T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
         }
     }
@@ -113,7 +124,7 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
 // plane, tile) and none in surplus.  pre[k] (k = 0 .. n): the workgroups of the batch's records in front of this launch's record k
 // (planes x tiles each, never 0), so workgroup b of the launch is number pre[0] + b of the batch and belongs to the last record
 // whose pre is not above that; the launch has pre[n] - pre[0] workgroups.  The search is the same for all of a workgroup's threads.
-template <int kDtype, bool kAnyFilter>
+template <int kDtype, bool kAnyFilter, bool kAlpha = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_exact_kernel(const DecResize *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     const uint64_t g = pre[0] + blockIdx.x;
@@ -127,17 +138,20 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_exact_kernel(const De
     const uint32_t rel = (uint32_t)(g - pre[lo]), tiles = (uint32_t)resize_tiles(r.w, r.h); // (planes x tiles < 2^24: the host's rule)
     const uint32_t plane = rel / tiles;
     if (plane >= r.planes) return; // (never, with the host's pre)
-    dec_resize_tile<kDtype, kAnyFilter>(r, plane, rel - plane * tiles, flt);
+    dec_resize_tile<kDtype, kAnyFilter, kAlpha>(r, plane, rel - plane * tiles, flt);
 }
 
 } // namespace
 
-bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
+bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
+                             bool any_alpha)
 {
     using Kernel = void (*)(const DecResize *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][kDecFloatTypes + 1] = {
-        {dec_resize_exact_kernel<-1, false>, dec_resize_exact_kernel<0, false>, dec_resize_exact_kernel<1, false>, dec_resize_exact_kernel<2, false>},
-        {dec_resize_exact_kernel<-1, true>, dec_resize_exact_kernel<0, true>, dec_resize_exact_kernel<1, true>, dec_resize_exact_kernel<2, true>}};
+    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
+        {{dec_resize_exact_kernel<-1, false>, dec_resize_exact_kernel<0, false>, dec_resize_exact_kernel<1, false>, dec_resize_exact_kernel<2, false>},
+         {dec_resize_exact_kernel<-1, true>, dec_resize_exact_kernel<0, true>, dec_resize_exact_kernel<1, true>, dec_resize_exact_kernel<2, true>}},
+        {{dec_resize_exact_kernel<-1, false, true>, dec_resize_exact_kernel<0, false, true>, dec_resize_exact_kernel<1, false, true>, dec_resize_exact_kernel<2, false, true>},
+         {dec_resize_exact_kernel<-1, true, true>, dec_resize_exact_kernel<0, true, true>, dec_resize_exact_kernel<1, true, true>, dec_resize_exact_kernel<2, true, true>}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups, far below the 2^31 a grid's dimension allows)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     if (lds_bytes > 65536u) return false;
@@ -145,8 +159,8 @@ bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
-                           flt ? *flt : DecFloat{});
+        hipLaunchKernelGGL(kernels[any_alpha][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
+                           r1 - r0, flt ? *flt : DecFloat{});
         r0 = r1;
     }
     return true;
@@ -183,7 +197,10 @@ namespace {
 //      of the destination, back to front -- the reversed order an index into the pixel; the fmaf and the conversion are
 //      dec_resize_tile's.  Where every element of the run is written (pixel_elems == planes) and the elements are narrower than a
 //      dword, the run goes out as single elements up to the first 4-byte boundary, dwords, and single elements behind the last one.
-template <int kDtype, bool kAnyFilter>
+// kAlpha (view_alpha.h): the load of step 2 makes P' as dec_resize_tile's does; a PREMULTIPLIED view runs the passes for all FOUR planes,
+// whatever the destination's count -- R'_3 is then byte 3 of the same register -- and divides the three colour bytes by it before
+// they go to O.
+template <int kDtype, bool kAnyFilter, bool kAlpha = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecResizeHwc *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
@@ -226,7 +243,9 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
     const uint32_t o_stride = kResizeTileW * C; // bytes of a row of O
     constexpr uint32_t kWaves = kResizeBlock / kResizeTileW, kRowsPerWave = kResizeTileH / kWaves;
     uint32_t res[kRowsPerWave] = {};
-    for (uint32_t plane = 0; plane < C; plane++) {
+    [[maybe_unused]] const uint32_t a_op = kAlpha ? resize_alpha_op(r.flags) : 0u;
+    const uint32_t n_planes = kAlpha && a_op == kAlphaPremultiplied ? 4u : C;
+    for (uint32_t plane = 0; plane < n_planes; plane++) {
         if (plane) __syncthreads(); // (the plane before has been read out of T)
         const uint8_t *const S = r.src + (uint64_t)plane * r.src_plane_pitch;
         {
@@ -234,7 +253,10 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
             for (uint32_t j = wave; j < nrows; j += kResizeBlock / kResizeTileW) {
                 const uint8_t *s = S + (uint64_t)(row0 + j) * r.src_pitch + first;
                 int32_t sum = 1 << (kResizeBits - 1);
-                for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
+                if constexpr (kAlpha) // (the sum over P'; the alpha plane's byte: the same offset, 3 - plane planes on)
+                    sum = alpha_pass_sum(alpha_load_mode(a_op, plane), s, s + (uint64_t)(3u - plane) * r.src_plane_pitch, resize_alpha_bg(r.flags, plane), count, Kx + o, kResizeTileW);
+                else
+                    for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
                 T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
             }
         }
@@ -252,6 +274,14 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
             }
         }
     }
+    if constexpr (kAlpha)
+        if (a_op == kAlphaPremultiplied) { // (step 3 of the rule; a destination of three planes drops R_3 behind it)
+#pragma unroll
+            for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                const uint32_t a = res[k] >> 24;
+                res[k] = alpha_unmul(res[k] & 255u, a) | alpha_unmul(res[k] >> 8 & 255u, a) << 8 | alpha_unmul(res[k] >> 16 & 255u, a) << 16 | (C == 4 ? a << 24 : 0u);
+            }
+        }
     __syncthreads(); // (weights, taps and T have been read for the last time: O takes their place)
     if (o < nw) {
 #pragma unroll
@@ -316,12 +346,15 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
 
 } // namespace
 
-bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
+bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
+                           bool any_alpha)
 {
     using Kernel = void (*)(const DecResizeHwc *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][kDecFloatTypes + 1] = {
-        {dec_resize_hwc_kernel<-1, false>, dec_resize_hwc_kernel<0, false>, dec_resize_hwc_kernel<1, false>, dec_resize_hwc_kernel<2, false>},
-        {dec_resize_hwc_kernel<-1, true>, dec_resize_hwc_kernel<0, true>, dec_resize_hwc_kernel<1, true>, dec_resize_hwc_kernel<2, true>}};
+    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
+        {{dec_resize_hwc_kernel<-1, false>, dec_resize_hwc_kernel<0, false>, dec_resize_hwc_kernel<1, false>, dec_resize_hwc_kernel<2, false>},
+         {dec_resize_hwc_kernel<-1, true>, dec_resize_hwc_kernel<0, true>, dec_resize_hwc_kernel<1, true>, dec_resize_hwc_kernel<2, true>}},
+        {{dec_resize_hwc_kernel<-1, false, true>, dec_resize_hwc_kernel<0, false, true>, dec_resize_hwc_kernel<1, false, true>, dec_resize_hwc_kernel<2, false, true>},
+         {dec_resize_hwc_kernel<-1, true, true>, dec_resize_hwc_kernel<0, true, true>, dec_resize_hwc_kernel<1, true, true>, dec_resize_hwc_kernel<2, true, true>}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     if (lds_bytes > 65536u) return false;
@@ -329,8 +362,8 @@ bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
-                           flt ? *flt : DecFloat{});
+        hipLaunchKernelGGL(kernels[any_alpha][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
+                           r1 - r0, flt ? *flt : DecFloat{});
         r0 = r1;
     }
     return true;

@@ -17,11 +17,14 @@
 //      row chosen by the element's channel, needs the pixel's three bytes and twelve selects per element.)
 // A fourth channel (alpha, or the 255 of a 3-channel file) skips the matrix.  The kernels of resize.hip are not touched: the two
 // passes are repeated here.
+// kAlpha (view_alpha.h): the load of step 2 makes P'; a PREMULTIPLIED view runs the passes for all
+// FOUR planes, whatever the destination's count, and divides the three colour bytes by R'_3 in front of the matrix.
 #include "decode.h"
 #include "float_store.h"
 #include "resize.h"
 #include "resize_color.h"
 #include "resize_hwc.h"
+#include "view_alpha.h"
 
 #include <hip/hip_runtime.h>
 
@@ -49,7 +52,7 @@ template <int kDtype> __device__ __forceinline__ void color_store(uint8_t *p, ui
     else *(u16_a *)p = (uint16_t)b;
 }
 
-template <int kDtype, bool kAnyFilter, bool kHwc>
+template <int kDtype, bool kAnyFilter, bool kHwc, bool kAlpha = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const DecResizeColor *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
@@ -91,7 +94,9 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
     const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
     constexpr uint32_t kWaves = kResizeBlock / kResizeTileW, kRowsPerWave = kResizeTileH / kWaves;
     uint32_t res[kRowsPerWave] = {};
-    for (uint32_t plane = 0; plane < C; plane++) {
+    [[maybe_unused]] const uint32_t a_op = kAlpha ? resize_alpha_op(r.flags) : 0u;
+    const uint32_t n_planes = kAlpha && a_op == kAlphaPremultiplied ? 4u : C;
+    for (uint32_t plane = 0; plane < n_planes; plane++) {
         if (plane) __syncthreads(); // (the plane before has been read out of T)
         const uint8_t *const S = r.src + (uint64_t)plane * r.src_plane_pitch;
         {
@@ -99,7 +104,10 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
             for (uint32_t j = wave; j < nrows; j += kWaves) {
                 const uint8_t *s = S + (uint64_t)(row0 + j) * r.src_pitch + first;
                 int32_t sum = 1 << (kResizeBits - 1);
-                for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
+                if constexpr (kAlpha) // (the sum over P'; the alpha plane's byte: the same offset, 3 - plane planes on)
+                    sum = alpha_pass_sum(alpha_load_mode(a_op, plane), s, s + (uint64_t)(3u - plane) * r.src_plane_pitch, resize_alpha_bg(r.flags, plane), count, Kx + o, kResizeTileW);
+                else
+                    for (uint32_t t = 0; t < count; t++) sum += (int32_t)s[t] * Kx[t * kResizeTileW + o];
                 T[j * kResizeTileW + o] = (uint8_t)resize_clip8(sum);
             }
         }
@@ -117,6 +125,14 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
             }
         }
     }
+    if constexpr (kAlpha)
+        if (a_op == kAlphaPremultiplied) { // (step 3 of the alpha rule: in front of the matrix)
+#pragma unroll
+            for (uint32_t k = 0; k < kRowsPerWave; k++) {
+                const uint32_t a = res[k] >> 24;
+                res[k] = alpha_unmul(res[k] & 255u, a) | alpha_unmul(res[k] >> 8 & 255u, a) << 8 | alpha_unmul(res[k] >> 16 & 255u, a) << 16 | a << 24;
+            }
+        }
     // ---- 3. the store ----
     // (the view's matrix: the same for all of the workgroup's threads; every index below is a constant)
     const float m00 = recs[lo].m[0][0], m01 = recs[lo].m[0][1], m02 = recs[lo].m[0][2], m03 = recs[lo].m[0][3];
@@ -198,14 +214,18 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
 } // namespace
 
 bool launch_dec_resize_color(hipStream_t s, const DecResizeColor *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
-                             bool hwc)
+                             bool hwc, bool any_alpha)
 {
     using Kernel = void (*)(const DecResizeColor *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
-        {{dec_resize_color_kernel<-1, false, false>, dec_resize_color_kernel<0, false, false>, dec_resize_color_kernel<1, false, false>, dec_resize_color_kernel<2, false, false>},
-         {dec_resize_color_kernel<-1, true, false>, dec_resize_color_kernel<0, true, false>, dec_resize_color_kernel<1, true, false>, dec_resize_color_kernel<2, true, false>}},
-        {{dec_resize_color_kernel<-1, false, true>, dec_resize_color_kernel<0, false, true>, dec_resize_color_kernel<1, false, true>, dec_resize_color_kernel<2, false, true>},
-         {dec_resize_color_kernel<-1, true, true>, dec_resize_color_kernel<0, true, true>, dec_resize_color_kernel<1, true, true>, dec_resize_color_kernel<2, true, true>}}};
+    static const Kernel kernels[2][2][2][kDecFloatTypes + 1] = {
+        {{{dec_resize_color_kernel<-1, false, false>, dec_resize_color_kernel<0, false, false>, dec_resize_color_kernel<1, false, false>, dec_resize_color_kernel<2, false, false>},
+          {dec_resize_color_kernel<-1, true, false>, dec_resize_color_kernel<0, true, false>, dec_resize_color_kernel<1, true, false>, dec_resize_color_kernel<2, true, false>}},
+         {{dec_resize_color_kernel<-1, false, true>, dec_resize_color_kernel<0, false, true>, dec_resize_color_kernel<1, false, true>, dec_resize_color_kernel<2, false, true>},
+          {dec_resize_color_kernel<-1, true, true>, dec_resize_color_kernel<0, true, true>, dec_resize_color_kernel<1, true, true>, dec_resize_color_kernel<2, true, true>}}},
+        {{{dec_resize_color_kernel<-1, false, false, true>, dec_resize_color_kernel<0, false, false, true>, dec_resize_color_kernel<1, false, false, true>, dec_resize_color_kernel<2, false, false, true>},
+          {dec_resize_color_kernel<-1, true, false, true>, dec_resize_color_kernel<0, true, false, true>, dec_resize_color_kernel<1, true, false, true>, dec_resize_color_kernel<2, true, false, true>}},
+         {{dec_resize_color_kernel<-1, false, true, true>, dec_resize_color_kernel<0, false, true, true>, dec_resize_color_kernel<1, false, true, true>, dec_resize_color_kernel<2, false, true, true>},
+          {dec_resize_color_kernel<-1, true, true, true>, dec_resize_color_kernel<0, true, true, true>, dec_resize_color_kernel<1, true, true, true>, dec_resize_color_kernel<2, true, true, true>}}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     if (lds_bytes > 65536u) return false;
@@ -213,7 +233,7 @@ bool launch_dec_resize_color(hipStream_t s, const DecResizeColor *recs, const ui
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[hwc][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
+        hipLaunchKernelGGL(kernels[any_alpha][hwc][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
                            flt ? *flt : DecFloat{});
         r0 = r1;
     }

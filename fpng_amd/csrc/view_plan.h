@@ -1,5 +1,5 @@
 // view_plan.h -- the host side of the views stage of the planar-family decode calls (include/fpng_amd.h: _planar_resize,
-// _planar_resize_view, {planar,hwc}_views and their _color, _post, _warp, _tone and _enhance siblings): what a call asks for
+// _planar_resize_view, {planar,hwc}_views and their _color, _post, _warp, _tone, _enhance and _alpha siblings): what a call asks for
 // (ViewRequest) and everything the batch keeps about its views (ViewPlan).  decode_api.cpp's stages each make one call into the
 // plan: parse (per file: file_box, file_records, add_job; then close), place (carve_records, carve_scratch, place), plan
 // (write_setup) and finish (enqueue).  Everything up to and including write_setup builds records in host memory and calls nothing
@@ -10,6 +10,7 @@
 #include "resize.h"
 #include "resize_color.h"
 #include "resize_hwc.h"
+#include "view_alpha.h"
 #include "view_post.h"
 
 #include <algorithm>
@@ -20,7 +21,7 @@
 namespace fpng_amd {
 
 // which entry-point family was called: the last record array its signature takes
-enum class ViewFamily { Plain, Color, Post, Warp, Tone, Enhance };
+enum class ViewFamily { Plain, Color, Post, Warp, Tone, Enhance, Alpha };
 
 // Everything a planar-family call may carry (NULL: not given).  crops and views without view_count: one view per file, whose
 // destination is the planar file's own (the resize and resize_view calls); with view_count: file i has view_count[i] records of
@@ -37,6 +38,7 @@ struct ViewRequest {
     const fpng_amd_view_warp *warps = nullptr;
     const fpng_amd_view_tone *tones = nullptr;
     const fpng_amd_view_enhance *enhances = nullptr;
+    const fpng_amd_view_alpha *alphas = nullptr; // (the last array of the signatures; its stage sits inside the resize, in front of all others)
     ViewFamily family = ViewFamily::Plain;
 };
 
@@ -161,6 +163,19 @@ struct ViewPlan {
     uint32_t first_view(uint32_t file) const { return multi() ? view_ofs[file] : file; }
     uint32_t views_of(uint32_t file) const { return multi() ? rq.view_count[file] : 1u; }
 
+    // the alpha op and background of view `view` as they travel in DecResize::flags.  file_chans: the channels of the view's FILE --
+    // a file without an alpha plane has P_3 = 255, for which every op is the identity: its records normalise to op 0
+    uint32_t alpha_flags(uint32_t view, uint32_t file_chans) const { return rq.alphas && file_chans == 4 ? resize_alpha_flags(rq.alphas[view]) : 0u; }
+
+    // the planes that file i's job decodes into the scratch: the destination's `planes`, and all four of a 4-channel file of which
+    // some view has an alpha op -- its fourth plane is read even where the destination has three
+    uint32_t job_planes(uint32_t i, uint32_t file_chans, uint32_t planes) const
+    {
+        for (uint32_t v = first_view(i), end = v + views_of(i); v < end; v++)
+            if (alpha_flags(v, file_chans)) return 4;
+        return planes;
+    }
+
     // ---- parse ----
     void begin(const ViewRequest &request, uint32_t n_files, uint32_t elem_bytes)
     {
@@ -182,8 +197,9 @@ struct ViewPlan {
 
     // the destinations of file i's views judged, and a record per view for the resize kernels, which read the view's own box inside
     // the planes of the job's box `crop` (src: an offset from those planes' first byte until the file is known to become a job).
-    // f, x: the file, whose own destination is the view's in the calls with one view per file; planes: its num_chans
-    Refusal file_records(uint32_t i, const fpng_amd_png &f, const fpng_amd_png_planar &x, uint32_t planes, const DecCrop &crop)
+    // f, x: the file, whose own destination is the view's in the calls with one view per file; planes: its num_chans; file_chans:
+    // the channels in the file (alpha_flags)
+    Refusal file_records(uint32_t i, const fpng_amd_png &f, const fpng_amd_png_planar &x, uint32_t planes, const DecCrop &crop, uint32_t file_chans = 0)
     {
         if (crop.w >= 0x80000000u) return {FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31"};
         const uint32_t v0 = first_view(i), nv = views_of(i);
@@ -202,7 +218,7 @@ struct ViewPlan {
             rs.src = (const uint8_t *)(uintptr_t)((size_t)(box.y - crop.y) * crop.w + (box.x - crop.x));
             rs.src_pitch = crop.w, rs.src_plane_pitch = (uint64_t)crop.w * crop.h;
             rs.dst = dest.d_pixels, rs.plane_pitch = d.plane_pitch, rs.pitch = (int32_t)d.pitch;
-            rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags, rs.planes = planes, rs.filter = z.filter;
+            rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags | alpha_flags(v, file_chans), rs.planes = planes, rs.filter = z.filter;
             rs.x = z.x, rs.y = z.y, rs.w = z.w, rs.h = z.h;
             rs.box_x = box.x - whole_crop.x, rs.box_y = box.y - whole_crop.y;
             rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
@@ -219,8 +235,8 @@ struct ViewPlan {
 
     // file i becomes the next job: its records of file_records() join the plan.  The crop kernels write tight uint8 planes of the
     // box's size into the scratch; the resize reads them and writes the caller's.  Returns the planes' offset (the job's `out`
-    // until place()); their pitches are crop.w and crop.w * crop.h
-    size_t add_job(uint32_t i, uint32_t planes, const DecCrop &crop)
+    // until place()); their pitches are crop.w and crop.w * crop.h.  in_scratch: job_planes() of the file (0: `planes`)
+    size_t add_job(uint32_t i, uint32_t planes, const DecCrop &crop, uint32_t in_scratch = 0)
     {
         const uint32_t v0 = first_view(i);
         job_rec.push_back((uint32_t)resize.size());
@@ -258,7 +274,7 @@ struct ViewPlan {
             }
         }
         const size_t out = mid_total;
-        mid_total += ((size_t)crop.w * crop.h * planes + 15) & ~(size_t)15;
+        mid_total += ((size_t)crop.w * crop.h * (in_scratch ? in_scratch : planes) + 15) & ~(size_t)15;
         // (the post views' windows: next to the box's planes)
         for (size_t q = job_rec.back(); rq.posts && q < resize.size(); q++)
             if (post_of[q] >= 0) {

@@ -620,8 +620,8 @@ int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_
  *      most 65 taps; upscaling is unbounded).  A crop that leaves the image stays that file's own status 67; statuses,
  *      FPNG_AMD_DECODE_UNDECIDED, FPNG_AMD_DECODE_MAX_ROUNDS and the checksum flags behave as in the crop call.
  *      Not offered by THIS call: a window of the resized image and the bicubic filter (fpng_amd_decode_batch_planar_resize_view,
- *      below, has both).  Not offered at all: antialias off, nearest and Lanczos; premultiplied alpha (every plane is resized on
- *      its own, as an "L" image); a resize without a crop record (give the whole image as the crop); fpng_amd_decode_host and the
+ *      below, has both), and premultiplied alpha or a background (every plane is resized on its own, as an "L" image; the
+ *      _views_alpha calls, below, have both).  Not offered at all: antialias off, nearest and Lanczos; a resize without a crop record (give the whole image as the crop); fpng_amd_decode_host and the
  *      fpng:: drop-in.  Interleaved (channels-last) destinations: fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize with dlsym. ---- */
 typedef struct fpng_amd_resize {
@@ -663,7 +663,8 @@ int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint32_t *first
  *      views, an empty crop, full_w, full_h, w or h of 0, x + w > full_w or y + h > full_h (in 64 bits), unknown flag bits, an
  *      unknown filter, and a crop past the filter's scale limit against the FULL size: bilinear crop.w <= 32 * full_w, bicubic
  *      crop.w <= 16 * full_w (the same for h; at most 65 taps either way).  The bound of 2^22 tiles of 64 x 16 applies to the window.
- *      Not offered: antialias off, nearest, Lanczos; premultiplied alpha; fpng_amd_decode_host and the fpng:: drop-in.
+ *      Not offered: antialias off, nearest, Lanczos; fpng_amd_decode_host and the fpng:: drop-in; by THIS call, premultiplied
+ *      alpha (the _views_alpha calls, below).
  *      Interleaved (channels-last) destinations: fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize_view with dlsym. ---- */
 typedef struct fpng_amd_resize_view {
@@ -1126,6 +1127,77 @@ int fpng_amd_decode_batch_device_hwc_views_enhance(fpng_amd_encoder *enc, const 
 /* the whole stage for ONE view (no GPU): in is W', three planes of w x h bytes one behind the other; out is E.  The text that the
  * kernel runs.  The record is judged as the calls judge it (op 0: a copy) */
 int fpng_amd_view_enhance_apply(const fpng_amd_view_enhance *enhance, uint32_t w, uint32_t h, const uint8_t *in /* 3 planes */, uint8_t *out /* 3 planes */);
+/* ---- the enhance call with an ALPHA record per view: what a view does with the fourth plane of a 4-channel file.  Every call
+ *      above resizes that plane on its own, as an `L` image, or drops it; the loaders of RGBA files do one of two other things.
+ *      COMPOSITE: the sample is put over an opaque background colour first -- Image.alpha_composite(Image.new("RGBA", im.size,
+ *      bg + (255,)), im).convert("RGB"), or Image.paste(im, mask=alpha), which agree everywhere -- and then cropped and resized.
+ *      PREMULTIPLIED: Image.resize of the RGBA image, im.crop(box).resize(full, f).crop(window), which Pillow runs as RGBA -> RGBa,
+ *      resample, RGBa -> RGBA.  The argument lists are those of the _views_enhance calls with `alphas`, a record per view, behind
+ *      `enhances`; colors, posts, warps, tones and enhances may each be NULL; alphas may not.
+ *      THE RULE (every element is exact; all of it integer arithmetic on bytes, fpng_amd/csrc/view_alpha.h):
+ *          M(v, a)    = t = v * a + 128;  ((t >> 8) + t) >> 8                        RGBA -> RGBa
+ *          U(v, a)    = a == 0 || a == 255 ? v : min(255, (255 * v) / a)             RGBa -> RGBA; the division truncates
+ *          C(v, a, b) = t = v * a + b * (255 - a) + 128;  ((t >> 8) + t) >> 8        over an opaque background; a == 0 gives b
+ *        P_0 .. P_3 are the crop's planes as the crop call writes them for four planes (a 3-channel file: P_3 = 255).
+ *        1. at the LOAD of the resize.  COMPOSITE: P'_c = C(P_c, P_3, background[c]) for c < 3, P'_3 = 255.
+ *           PREMULTIPLIED: P'_c = M(P_c, P_3) for c < 3, P'_3 = P_3.
+ *        2. the resize of fpng_amd_decode_batch_planar_resize_view, unchanged, per plane on P', for either filter: R' = the window
+ *           of the full-size image.  (Where the full size is the crop's own, Image.resize returns a copy and never
+ *           premultiplies; the rule has no such case: steps 1 and 3 run around a resize that is the identity.)
+ *        3. at the STORE of the resize, PREMULTIPLIED only: R_c = U(R'_c, R'_3) for c < 3, R_3 = R'_3.  The clip in U is live
+ *           under the bicubic filter's overshoot, and where R'_3 is 0 the colour that is copied need not be 0.
+ *        Every later stage -- colour matrix, warp, tone, enhance, post, conversion, mirror, store -- sees R exactly as it sees the
+ *        resize's bytes in the calls above.  A destination of three planes drops R_3 behind step 3; a COMPOSITE view with four
+ *        planes gets 255 in the fourth.
+ *      GUARANTEES: a record with op == 0 leaves its view bit for bit the _views_enhance call's; a call in which no record has an
+ *      op enqueues exactly what that call enqueues, the same kernels in the same instantiations; any op on a 3-channel file equals
+ *      op 0 bit for bit (C(v, 255, b) = M(v, 255) = U(v, 255) = v); for a file with status 0 a view depends only on its own
+ *      records, whatever the file's other views are -- ops and backgrounds are per view over the ONE shared box of the file; source
+ *      boxes, the tiles that run, statuses, the scale limits and the spans that are written are the views call's.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null alphas; an unknown op; a
+ *      non-zero reserved word; background[3] != 0; a non-zero background without COMPOSITE; and everything the enhance call refuses.
+ *      The stage adds no launch, no pass over memory and no scratch: it runs inside the resize kernels' alpha instantiations,
+ *      which a launch takes only when one of its views has an op.  The job of a 4-channel file with such a view decodes its
+ *      fourth plane into the scratch even when the destination has three planes.
+ *      Not offered: backgrounds that are images; compositing after the resize; Pillow's premultiplied Image.transform (the warp
+ *      stage stays per band); the stage in the single-view _planar_resize(_view) calls, in fpng_amd_decode_host or in the fpng::
+ *      drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_alpha with dlsym. ---- */
+#define FPNG_AMD_ALPHA_COMPOSITE 1
+#define FPNG_AMD_ALPHA_PREMULTIPLIED 2
+typedef struct fpng_amd_view_alpha {
+    uint32_t op;            /* FPNG_AMD_ALPHA_*; 0 = none: this view is the enhance call's, untouched */
+    uint8_t background[4];  /* COMPOSITE: R, G, B of the opaque background, [3] = 0; else all 0 */
+    uint32_t reserved[2];   /* 0 */
+} fpng_amd_view_alpha;      /* 16 bytes */
+int fpng_amd_decode_batch_planar_views_alpha(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                             const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                             const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                             const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                             const fpng_amd_view_tone *tones /* the same, or NULL */, const fpng_amd_view_enhance *enhances /* the same, or NULL */,
+                                             const fpng_amd_view_alpha *alphas /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 planes */,
+                                             fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_alpha(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                    const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                    const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                    const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas,
+                                                    const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_alpha(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                          const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                          const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                          const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                          const fpng_amd_view_tone *tones /* the same, or NULL */, const fpng_amd_view_enhance *enhances /* the same, or NULL */,
+                                          const fpng_amd_view_alpha *alphas /* the same */, const fpng_amd_float_format *fmt /* NULL: uint8 */,
+                                          fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_alpha(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                 const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                 const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                 const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas,
+                                                 const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+/* steps 1 and 3 of the rule for ONE view (no GPU), over FOUR planes of w x h bytes one behind the other: _source makes P' of P,
+ * _result makes R of R'.  The texts that the kernels run.  The record is judged as the calls judge it (op 0: a copy) */
+int fpng_amd_view_alpha_source(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in /* 4 planes */, uint8_t *out /* 4 planes */);
+int fpng_amd_view_alpha_result(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in /* 4 planes */, uint8_t *out /* 4 planes */);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

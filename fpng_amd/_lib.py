@@ -121,10 +121,15 @@ class ViewAlpha(C.Structure):  # fpng_amd_view_alpha: 16 bytes, the alpha record
     _fields_ = [("op", C.c_uint32), ("background", C.c_uint8 * 4), ("reserved", C.c_uint32 * 2)]
 
 
+class ViewResample(C.Structure):  # fpng_amd_view_resample: 16 bytes, the RESAMPLE record of ONE view of the _views_resample calls
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 POST_BLUR, POST_SOLARIZE, POST_POSTERIZE = 1, 2, 4  # FPNG_AMD_POST_*
 TONE_AUTOCONTRAST, TONE_EQUALIZE, TONE_CONTRAST = 1, 2, 3  # FPNG_AMD_TONE_*
 ENHANCE_BRIGHTNESS, ENHANCE_COLOR, ENHANCE_SHARPNESS = 1, 2, 3  # FPNG_AMD_ENHANCE_*
 ALPHA_COMPOSITE, ALPHA_PREMULTIPLIED = 1, 2  # FPNG_AMD_ALPHA_*
+RESAMPLE_NEAREST, RESAMPLE_BOX, RESAMPLE_HAMMING, RESAMPLE_LANCZOS = 1, 2, 3, 4  # FPNG_AMD_RESAMPLE_*
 WARP_AFFINE, WARP_BILINEAR = 1, 2  # FPNG_AMD_WARP_*
 BLUR_MAX_RADIUS = 16  # FPNG_AMD_BLUR_MAX_RADIUS
 HWC_REVERSED = 1  # FPNG_AMD_HWC_REVERSED
@@ -256,6 +261,8 @@ SIGNATURES = {
     "fpng_amd_view_tone_lut": (_int, [C.POINTER(ViewTone), C.c_void_p, C.c_void_p]),
     "fpng_amd_view_tone_apply": (_int, [C.POINTER(ViewTone), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_view_enhance_apply": (_int, [C.POINTER(ViewEnhance), _u32, _u32, C.c_void_p, C.c_void_p]),
+    "fpng_amd_resample_weights": (_int, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_int32)]),
+    "fpng_amd_resample_view_source": (_int, [C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(ViewResample), C.POINTER(Crop)]),
     "fpng_amd_view_alpha_source": (_int, [C.POINTER(ViewAlpha), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_view_alpha_result": (_int, [C.POINTER(ViewAlpha), _u32, _u32, C.c_void_p, C.c_void_p]),
     "fpng_amd_blur_weights": (_int, [_u32, C.c_double, C.POINTER(C.c_int32 * 17)]),
@@ -281,7 +288,8 @@ SIGNATURES = {
 
 # The views calls: fpng_amd_decode_batch(_device)_{planar,hwc}_views<suffix>.  A stage's call takes the record arrays of every stage up
 # to and including its own, in this order, between the destinations and the float format.
-VIEW_STAGES = (("_color", ViewColor), ("_post", ViewPost), ("_warp", ViewWarp), ("_tone", ViewTone), ("_enhance", ViewEnhance), ("_alpha", ViewAlpha))
+VIEW_STAGES = (("_color", ViewColor), ("_post", ViewPost), ("_warp", ViewWarp), ("_tone", ViewTone), ("_enhance", ViewEnhance), ("_alpha", ViewAlpha),
+               ("_resample", ViewResample))
 VIEW_LAYOUTS = (("planar", ViewDest), ("hwc", ViewDestHwc))
 
 

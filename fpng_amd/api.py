@@ -746,6 +746,61 @@ def view_enhance_apply(enhance, planes):
     return out
 
 
+RESAMPLE_FILTERS = {None: 0, "nearest": _lib.RESAMPLE_NEAREST, "box": _lib.RESAMPLE_BOX, "hamming": _lib.RESAMPLE_HAMMING, "lanczos": _lib.RESAMPLE_LANCZOS}
+
+
+def view_resample(filter=None):
+    """The fpng_amd_view_resample record of one view of the views calls' resample= argument: the filter the view is resized with in
+    the place of its own filter= -- "nearest", "box", "hamming" or "lanczos", Pillow's Image.NEAREST, BOX, HAMMING and LANCZOS -- or
+    None: the view's own (the view is then the alpha call's, untouched).  An integer is taken as an FPNG_AMD_RESAMPLE_* value."""
+    rec = _lib.ViewResample()
+    if isinstance(filter, (int, np.integer)) and not isinstance(filter, bool) and 0 <= int(filter) <= 0xFFFFFFFF:
+        rec.filter = int(filter)  # (an unknown value: the library's refusal)
+    elif isinstance(filter, (str, type(None))) and filter in RESAMPLE_FILTERS:
+        rec.filter = RESAMPLE_FILTERS[filter]
+    else:
+        raise ValueError(f"view_resample: filter is None, 'nearest', 'box', 'hamming' or 'lanczos', not {filter!r}")
+    return rec
+
+
+def _resample_arg(arg):
+    """the resample= argument with its names (and None entries below the top) as view_resample() records"""
+    one = lambda v: v is None or isinstance(v, (str, int, np.integer))
+    if one(arg):
+        return view_resample(arg)
+    if isinstance(arg, _lib.ViewResample) or not hasattr(arg, "__len__"):
+        return arg
+    return [view_resample(f) if one(f) else f if isinstance(f, _lib.ViewResample) or not hasattr(f, "__len__") else [view_resample(v) if one(v) else v for v in f] for f in arg]
+
+
+def resample_weights(in_size, out_size, filter):
+    """fpng_amd_resample_weights: resize_weights() for the RESAMPLE filters "nearest", "box", "hamming" and "lanczos" -> (first, count,
+    weights).  "nearest": count 1, weight 2^22, first = Pillow's index.  The text the kernels run; no GPU needed.  A size of 0 or one
+    past the filter's limit (in_size <= 32 * out_size; lanczos: 3 * in_size <= 32 * out_size) raises FpngAmdError."""
+    in_size, out_size = int(in_size), int(out_size)
+    if not (0 <= in_size <= 0xFFFFFFFF and 0 <= out_size <= 0xFFFFFFFF):
+        raise ValueError(f"resample_weights: sizes {in_size} -> {out_size} (32 bits, not negative)")
+    fid = view_resample(filter).filter
+    first, count = np.zeros(max(out_size, 1), dtype=np.uint32), np.zeros(max(out_size, 1), dtype=np.uint32)
+    weights = np.zeros((max(out_size, 1), _lib.RESIZE_MAX_TAPS), dtype=np.int32)
+    check(_lib.load().fpng_amd_resample_weights(in_size, out_size, fid, first.ctypes.data_as(C.POINTER(C.c_uint32)), count.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                weights.ctypes.data_as(C.POINTER(C.c_int32))))
+    return first, count, weights
+
+
+def resample_view_source(crop, full, window=None, filter="bilinear", resample=None):
+    """fpng_amd_resample_view_source: resize_view_source() of a view whose RESAMPLE record is view_resample(resample) (a name, None or
+    a record).  No GPU needed."""
+    x, y, w, h = (int(v) for v in crop)
+    if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
+        raise ValueError(f"resample_view_source: crop {tuple(crop)} (four values of 32 bits, not negative)")
+    c, box = _lib.Crop(x, y, w, h), _lib.Crop()
+    v = _view_record("resample_view_source", full, window, filter, False)
+    r = resample if isinstance(resample, _lib.ViewResample) else view_resample(resample)
+    check(_lib.load().fpng_amd_resample_view_source(C.byref(c), C.byref(v), C.byref(r), C.byref(box)))
+    return box.x, box.y, box.w, box.h
+
+
 def view_alpha(op=None, background=(0, 0, 0)):
     """The fpng_amd_view_alpha record of one view of the views calls' alpha= argument: what the view does with the fourth plane of a
     4-channel file, inside the resize.  op="composite": every sample is put over the opaque `background` (R, G, B bytes) first, as
@@ -1201,6 +1256,7 @@ class _DecodeBatchMultiViews(_DecodeBatchViews):
     warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
     tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
     enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
+    resamples = None  # the fpng_amd_view_resample records of a descriptor made with resample=, one per view: the call is then the _views_resample one
     alphas = None  # the fpng_amd_view_alpha records of a descriptor made with alpha=, one per view: the call is then the _views_alpha one
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
@@ -1264,7 +1320,7 @@ _PLANAR_VIEWS = _ViewsLayout("planar", "", _lib.ViewDest, DecodeBatchMultiView, 
 _HWC_VIEWS = _ViewsLayout("hwc", "_hwc", _lib.ViewDestHwc, DecodeBatchMultiViewHwc, _hwc_view_dest, lambda s: (s[2], s[0], s[1]), lambda oh, ow: (oh, ow, 3))
 
 
-def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha=None):
+def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha=None, resample=None):
     """the descriptor of a views call for either layout (Encoder.make_decode_batch_views / _hwc have the rules)"""
     who = layout.maker
     n = len(pngs)
@@ -1335,14 +1391,16 @@ def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, o
         batch.enhances = _view_records(who, counts, enhance, _lib.ViewEnhance, "enhance")
     if alpha is not None:
         batch.alphas = _view_records(who, counts, alpha, _lib.ViewAlpha, "alpha")
+    if resample is not None:
+        batch.resamples = _view_records(who, counts, _resample_arg(resample), _lib.ViewResample, "resample")
     return batch
 
 
 def views_entry(layout, device_data, batch):
     """The C entry point of a views call and its arguments behind the encoder, as a pure function of the layout ("planar" / "hwc"),
-    where the files are and the descriptor: the last stage in the order colour < post < warp < tone < enhance < alpha whose records the
+    where the files are and the descriptor: the last stage in the order colour < post < warp < tone < enhance < alpha < resample whose records the
     descriptor carries names the call, and the call takes the record arrays of all stages up to it (None for those not given)."""
-    arrays = [batch.colors, batch.posts, batch.warps, batch.tones, batch.enhances, batch.alphas]
+    arrays = [batch.colors, batch.posts, batch.warps, batch.tones, batch.enhances, batch.alphas, batch.resamples]
     stages = max((k + 1 for k, a in enumerate(arrays) if a is not None), default=0)
     fmt = C.byref(batch.fmt) if batch.fmt is not None else None
     return _lib.views_symbol(layout, device_data, stages), [batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, *arrays[:stages], fmt, batch.res]
@@ -2224,7 +2282,7 @@ class Encoder:
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
+                                scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """Descriptor (fpng_amd_png_planar[n], the uint32[n] view counts, an fpng_amd_crop, fpng_amd_resize_view and fpng_amd_view_dest
         per view, the fpng_amd_float_format if any and the result records, one per file) for decode_device_views() /
         decode_batch_views(): make_decode_batch_resize_view() with one more level of nesting.  crops[i]: the list of file i's crops,
@@ -2243,19 +2301,21 @@ class Encoder:
         records (view_enhance() makes them), nested as post's; the descriptor then goes through
         fpng_amd_decode_batch(_device)_planar_views_enhance, with the others' records or without.  alpha: None, or the views' alpha
         records (view_alpha() makes them), nested as post's; the descriptor then goes through
-        fpng_amd_decode_batch(_device)_planar_views_alpha, with the others' records or without."""
-        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha)
+        fpng_amd_decode_batch(_device)_planar_views_alpha, with the others' records or without.  resample: None, or the views'
+        RESAMPLE filters -- "nearest", "box", "hamming", "lanczos", None (the view's own filter=) or what view_resample() returns --
+        nested as post's; the descriptor then goes through fpng_amd_decode_batch(_device)_planar_views_resample."""
+        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha, resample)
 
     def _decode_views(self, layout, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                      tone, enhance, alpha):
+                      tone, enhance, alpha, resample=None):
         """a views call of either layout (_ViewsLayout), for files in device or host memory"""
         who = layout.device if device_data else layout.host
         if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, layout.batch_cls):
             raise ValueError(f"{who}: a descriptor of another call ({layout.maker}() makes this one's)")
         if isinstance(pngs, layout.batch_cls):
-            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None or alpha is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone, enhance and alpha records "
-                                 f"({layout.maker}(..., color=, post=, warp=, tone=, enhance=, alpha=))")
+            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None or alpha is not None or resample is not None:
+                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone, enhance, alpha and resample records "
+                                 f"({layout.maker}(..., color=, post=, warp=, tone=, enhance=, alpha=, resample=))")
             batch = pngs
         else:
             if crops is None or full is None:
@@ -2268,7 +2328,7 @@ class Encoder:
                 sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
                 outs = [[torch.empty(layout.empty_shape(oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
                         for i in range(len(crops))]
-            batch = _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha)
+            batch = _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha, resample)
         if batch.device_data != device_data:
             raise ValueError(f"{who}: the files are in " + (f"host memory ({layout.host})" if device_data else f"device memory ({layout.device})"))
         if not all(t.is_cuda for ts in batch.outs for t in ts):
@@ -2279,7 +2339,7 @@ class Encoder:
         return batch.results() if results else batch
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
+                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """fpng_amd_decode_batch_device_planar_views: SEVERAL views of each file -- uint8 CUDA tensors holding whole files -- from one
         decode of it: two 224 x 224 RandomResizedCrop views for contrastive training, two global and six 96 x 96 local ones for
         multi-crop.  crops[i] lists file i's crops; each is resized to its full size by its filter and its window written to its
@@ -2312,31 +2372,36 @@ class Encoder:
         plane of a 4-channel file, inside the resize and in front of every other stage -- "composite" over an opaque background
         colour as Image.alpha_composite does and then resize, or resize "premultiplied" as Image.resize of an RGBA image does --
         fpng_amd_decode_batch_device_planar_views_alpha; a record without an op, and any record on a 3-channel file, leaves its
-        view exactly the call's without."""
+        view exactly the call's without.
+        resample: None, or a RESAMPLE filter per view -- "nearest", "box", "hamming" or "lanczos" (Pillow's Image.NEAREST, BOX,
+        HAMMING, LANCZOS), None for the view's own filter=, or what view_resample() returns; one for all views, one per file, or a
+        list per file of one per view -- which overrides the view's filter= in the resize:
+        fpng_amd_decode_batch_device_planar_views_resample.  "nearest" is what a label map is resized with: give the mask the
+        image's crops, windows, mirror flags and warp records.  A None leaves its view exactly the call's without."""
         return self._decode_views(_PLANAR_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha)
+                                  tone, enhance, alpha, resample)
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
+                           bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views(_PLANAR_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha)
+                                  tone, enhance, alpha, resample)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
-                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
+                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """Descriptor for decode_device_views_hwc() / decode_batch_views_hwc(): make_decode_batch_views() with CHANNELS-LAST
         destinations -- outs[i] lists file i's (window h, window w, c) views (dest_layout_hwc() has their rules), all of one c per
         file and one dtype per call; the records are fpng_amd_view_dest_hwc.  Everything else -- the nesting of crops and outs, one
         value / per file / per view for full, window, filter, mirror, order and bottom_up, the constants, color (then:
         fpng_amd_decode_batch(_device)_hwc_views_color), post (then: fpng_amd_decode_batch(_device)_hwc_views_post), warp (then:
         fpng_amd_decode_batch(_device)_hwc_views_warp), tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone), enhance (then:
-        fpng_amd_decode_batch(_device)_hwc_views_enhance) and alpha (then: fpng_amd_decode_batch(_device)_hwc_views_alpha) -- is
-        make_decode_batch_views()'s."""
-        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha)
+        fpng_amd_decode_batch(_device)_hwc_views_enhance) alpha (then: fpng_amd_decode_batch(_device)_hwc_views_alpha) and resample
+        (then: fpng_amd_decode_batch(_device)_hwc_views_resample) -- is make_decode_batch_views()'s."""
+        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha, resample)
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """fpng_amd_decode_batch_device_hwc_views: decode_device_views() into CHANNELS-LAST destinations -- each view's window is
         written to an (h, w, c) device tensor view, element (q, i, c) exactly what decode_device_views() writes at (c, q, i),
         without a permute copy.  For a batch that trains in torch.channels_last,
@@ -2350,13 +2415,13 @@ class Encoder:
         None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
         return self._decode_views(_HWC_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha)
+                                  tone, enhance, alpha, resample)
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
-                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None):
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views(_HWC_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha)
+                                  tone, enhance, alpha, resample)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

@@ -672,10 +672,11 @@ int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const D
         const uint32_t p0 = job_post[j0], p1 = job_post[j1], d0 = r0 - p0, d1 = r1 - p1;
         const uint32_t nd = (uint32_t)(resize.size() - post_recs.size());
         uint32_t most_lds[2] = {0, 0};
-        bool any_filter[2] = {false, false}, any_alpha[2] = {false, false};
+        uint32_t any_filter[2] = {0, 0}; // (resize_launch_kind: the most of the launch's records)
+        bool any_alpha[2] = {false, false};
         for (uint32_t q = r0; q < r1; q++) {
             const int kind = post_of[q] >= 0;
-            most_lds[kind] = std::max(most_lds[kind], lds[q]), any_filter[kind] |= resize[q].filter != kResizeBilinear, any_alpha[kind] |= resize_alpha_op(resize[q].flags) != 0;
+            most_lds[kind] = std::max(most_lds[kind], lds[q]), any_filter[kind] = std::max(any_filter[kind], resize_launch_kind(resize[q].filter)), any_alpha[kind] |= resize_alpha_op(resize[q].flags) != 0;
         }
         ok = launch_dec_resize_color(s, recs + d0, d_pre + d0, dir_pre.data() + d0, d1 - d0, most_lds[0], flt, any_filter[0], hwc(), any_alpha[0]) &&
              launch_dec_resize_color(s, recs + nd + p0, d_pre + nd + 1 + p0, post_pre.data() + p0, p1 - p0, most_lds[1], nullptr, any_filter[1], false, any_alpha[1]);
@@ -690,7 +691,9 @@ int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const D
     } else {
         const uint32_t most_tiles = *std::max_element(tiles.begin() + r0, tiles.begin() + r1), most_lds = *std::max_element(lds.begin() + r0, lds.begin() + r1);
         // (a group of bilinear views -- the plain resize call's always are -- runs the instantiation without the second filter)
-        const bool any_filter = std::any_of(resize.begin() + r0, resize.begin() + r1, [](const DecResize &r) { return r.filter != kResizeBilinear; });
+        // (and one with a RESAMPLE filter -- the _resample calls' alone -- the instantiation that takes every filter as a value)
+        uint32_t any_filter = 0;
+        for (uint32_t q = r0; q < r1; q++) any_filter = std::max(any_filter, resize_launch_kind(resize[q].filter));
         // (the views call mixes sizes and plane counts in one launch: a grid of exactly its records' workgroups; the calls with one
         //  output per file keep the grid of the largest record)
         // (and a group without an alpha op -- every call but the _alpha ones, and those without one -- the instantiations without the stage)
@@ -701,7 +704,7 @@ int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const D
         ok = rq.colors ? launch_dec_resize_color(s, (const DecResizeColor *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, hwc(), any_alpha)
              : hwc()   ? launch_dec_resize_hwc(s, (const DecResizeHwc *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, any_alpha)
              : multi() ? launch_dec_resize_exact(s, (const DecResize *)d_recs + r0, d_pre + r0, plane_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, any_alpha)
-                       : launch_dec_resize(s, (const DecResize *)d_recs + r0, r1 - r0, most_tiles, most_lds, flt, any_filter);
+                       : launch_dec_resize(s, (const DecResize *)d_recs + r0, r1 - r0, most_tiles, most_lds, flt, any_filter != 0);
     }
     return ok ? FPNG_AMD_OK : fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
 }
@@ -1171,7 +1174,8 @@ static_assert(sizeof(fpng_amd_resize_view) == 32 && offsetof(fpng_amd_resize_vie
 static_assert(FPNG_AMD_FILTER_BILINEAR == kResizeBilinear && FPNG_AMD_FILTER_BICUBIC == kResizeBicubic, "the kernel's filters");
 // views: fpng_amd_decode_batch(_device)_planar_resize_view's, a view per file (with crops; the destinations are then the views'
 // windows).  As check_resize_records: no file, no encoder, no device
-int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t n)
+// resamples (or NULL): the views' RESAMPLE records, which have been judged -- the scale limit is the effective filter's
+int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t n, const fpng_amd_view_resample *resamples = nullptr)
 {
     for (uint32_t i = 0; crops && views && i < n; i++) {
         const fpng_amd_resize_view &z = views[i];
@@ -1181,7 +1185,11 @@ int check_view_records(const fpng_amd_crop *crops, const fpng_amd_resize_view *v
         if ((uint64_t)z.x + z.w > z.full_w || (uint64_t)z.y + z.h > z.full_h) return fail(FPNG_AMD_ERR_INVALID_ARG, "a window that leaves the full size (x + w <= full_w and y + h <= full_h)");
         if (z.flags & ~(uint32_t)FPNG_AMD_RESIZE_MIRROR) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_resize_view::flags bits");
         if (z.filter >= kResizeFilters) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown filter (FPNG_AMD_FILTER_BILINEAR, _BICUBIC)");
-        if (!resize_scale_ok(crops[i].w, z.full_w, z.filter) || !resize_scale_ok(crops[i].h, z.full_h, z.filter))
+        const uint32_t filter = view_filter(z, resamples ? resamples + i : nullptr);
+        if (filter >= kResizeFilters && (!resize_scale_ok(crops[i].w, z.full_w, filter) || !resize_scale_ok(crops[i].h, z.full_h, filter)))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, filter == kResizeLanczos ? "a crop past the Lanczos limit (3 * w <= 32 * full_w and 3 * h <= 32 * full_h)"
+                                                                            : "a crop of more than 32 x its full size (nearest, box, Hamming: w <= 32 * full_w and h <= 32 * full_h)");
+        if (filter < kResizeFilters && (!resize_scale_ok(crops[i].w, z.full_w, z.filter) || !resize_scale_ok(crops[i].h, z.full_h, z.filter)))
             return fail(FPNG_AMD_ERR_INVALID_ARG, z.filter == kResizeBicubic ? "a crop of more than 16 x its full size (bicubic: w <= 16 * full_w and h <= 16 * full_h)"
                                                                               : "a crop of more than 32 x its full size (bilinear: w <= 32 * full_w and h <= 32 * full_h)");
     }
@@ -1277,6 +1285,15 @@ static_assert(sizeof(fpng_amd_view_post) == 32 && offsetof(fpng_amd_view_post, b
 // front of it may be NULL: the identity, no flags, no warp, no op), the destinations, every stage's records from the last stage to
 // the first, then what the plain views call judges: the arrays, the counts, the views, the files' empty destination fields and the
 // channels-last destinations' own rules.  used: which stages some view really uses (normalise_views)
+// the RESAMPLE record's own rules
+const char *check_resample_record(const fpng_amd_view_resample &r)
+{
+    if (r.filter > FPNG_AMD_RESAMPLE_LANCZOS) return "unknown fpng_amd_view_resample::filter (FPNG_AMD_RESAMPLE_NEAREST, _BOX, _HAMMING, _LANCZOS; 0: the view's own)";
+    if (r.flags) return "fpng_amd_view_resample::flags must be 0";
+    if (r.reserved[0] | r.reserved[1]) return "fpng_amd_view_resample::reserved must be 0";
+    return nullptr;
+}
+static_assert(sizeof(fpng_amd_view_resample) == 16 && offsetof(fpng_amd_view_resample, flags) == 4 && offsetof(fpng_amd_view_resample, reserved) == 8, "fpng_amd_view_resample layout");
 struct StagesUsed {
     bool post = false, warp = false, tone = false, enhance = false;
     uint64_t total = 0; // the views of the call, where the counts are good
@@ -1285,6 +1302,7 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
 {
     const char *const null_array = "null files, view_count, crops, views, dests or results";
     switch (rq.family) {
+    case ViewFamily::Resample: if (!rq.resamples) return fail(FPNG_AMD_ERR_INVALID_ARG, "null resamples"); break;
     case ViewFamily::Alpha: if (!rq.alphas) return fail(FPNG_AMD_ERR_INVALID_ARG, "null alphas"); break;
     case ViewFamily::Enhance: if (!rq.enhances) return fail(FPNG_AMD_ERR_INVALID_ARG, "null enhances"); break;
     case ViewFamily::Tone: if (!rq.tones) return fail(FPNG_AMD_ERR_INVALID_ARG, "null tones"); break;
@@ -1300,8 +1318,13 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
     bool counts_ok = view_count != nullptr; // (else the counts are refused below, and no stage's record is read)
     for (uint32_t i = 0; counts_ok && i < n; i++) counts_ok = view_count[i] && (total += view_count[i]) <= UINT32_MAX;
     used.total = counts_ok ? total : 0;
-    for (uint64_t v = 0; rq.alphas && v < used.total; v++)
+    for (uint64_t v = 0; rq.resamples && v < used.total; v++)
+        if (const char *why = check_resample_record(rq.resamples[v])) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+    for (uint64_t v = 0; rq.alphas && v < used.total; v++) {
         if (const char *why = check_alpha_record(rq.alphas[v])) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+        if (rq.resamples && rq.resamples[v].filter == FPNG_AMD_RESAMPLE_NEAREST && rq.alphas[v].op == kAlphaPremultiplied)
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "a PREMULTIPLIED alpha record on a view whose RESAMPLE filter is NEAREST (Pillow does not premultiply for nearest: the view without an alpha op is its result)");
+    }
     for (uint32_t i = 0, v = 0; rq.enhances && counts_ok && i < n; i++) // (the planes of a view's destination: its file's num_chans)
         for (const uint32_t end = v + view_count[i]; v < end; v++) {
             if (const char *why = check_enhance_record(rq.enhances[v], files ? files[i].num_chans : 0u)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
@@ -1327,7 +1350,7 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
         if (!view_count[i]) return fail(FPNG_AMD_ERR_INVALID_ARG, "a view_count of 0 (every file has at least one view)");
         if ((total += view_count[i]) > UINT32_MAX) return fail(FPNG_AMD_ERR_INVALID_ARG, "the sum of view_count does not fit 32 bits");
     }
-    if (int rc = check_view_records(rq.crops, views, (uint32_t)total)) return rc;
+    if (int rc = check_view_records(rq.crops, views, (uint32_t)total, rq.resamples)) return rc;
     for (uint32_t i = 0; i < n; i++)
         if (files[i].d_pixels || files[i].row_pitch || files[i].plane_pitch || files[i].pixels_cap)
             return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_png_planar::d_pixels, row_pitch, plane_pitch and pixels_cap must be NULL / 0: the destinations are the fpng_amd_view_dest records");
@@ -1360,6 +1383,8 @@ ViewRequest normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults
         one.m[0][0] = one.m[1][1] = one.m[2][2] = 1.0f;
         made.colors.assign((size_t)used.total, one), rq.colors = made.colors.data();
     };
+    // (RESAMPLE records without a filter: the request is the alpha call's)
+    if (rq.resamples && std::none_of(rq.resamples, rq.resamples + used.total, [](const fpng_amd_view_resample &r) { return r.filter != 0; })) rq.resamples = nullptr;
     if (rq.alphas && std::none_of(rq.alphas, rq.alphas + used.total, [](const fpng_amd_view_alpha &a) { return a.op != 0; })) rq.alphas = nullptr;
     if (rq.alphas && !rq.colors && !rq.hwc && std::any_of(rq.alphas, rq.alphas + used.total, [](const fpng_amd_view_alpha &a) { return a.op == kAlphaPremultiplied; }))
         identity_colors();
@@ -1756,6 +1781,51 @@ extern "C" int fpng_amd_decode_batch_device_hwc_views_alpha(fpng_amd_encoder *e,
     return decode_files_views(e, files, n, results, true, rq);
 }
 
+// the alpha calls with a RESAMPLE record per view (fpng_amd_view_resample): the resize's filter
+extern "C" int fpng_amd_decode_batch_planar_views_resample(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                        const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests, const fpng_amd_view_color *colors,
+                                                        const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                        const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas, const fpng_amd_view_resample *resamples, const fpng_amd_float_format *fmt,
+                                                        fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Resample, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas, rq.resamples = resamples;
+    return decode_files_views(e, files, n, results, false, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_device_planar_views_resample(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                               const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                               const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                               const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas, const fpng_amd_view_resample *resamples,
+                                                               const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Resample, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas, rq.resamples = resamples;
+    return decode_files_views(e, files, n, results, true, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_hwc_views_resample(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                     const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests, const fpng_amd_view_color *colors,
+                                                     const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps, const fpng_amd_view_tone *tones,
+                                                     const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas, const fpng_amd_view_resample *resamples, const fpng_amd_float_format *fmt,
+                                                     fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Resample, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas, rq.resamples = resamples;
+    return decode_files_views(e, files, n, results, false, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_device_hwc_views_resample(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                            const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                            const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                            const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas, const fpng_amd_view_resample *resamples,
+                                                            const fpng_amd_float_format *fmt, fpng_amd_decode_result *results)
+{
+    ViewRequest rq;
+    rq.family = ViewFamily::Resample, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.hwc = dests, rq.colors = colors, rq.posts = posts, rq.warps = warps, rq.tones = tones, rq.enhances = enhances, rq.alphas = alphas, rq.resamples = resamples;
+    return decode_files_views(e, files, n, results, true, rq);
+}
+
 // the alpha rule on the host: the texts of view_alpha.h, which the resize kernels run in their load (source) and store (result)
 extern "C" int fpng_amd_view_alpha_source(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in, uint8_t *out)
 {
@@ -1894,6 +1964,37 @@ extern "C" int fpng_amd_resize_weights_filter(uint32_t in_size, uint32_t out_siz
         std::fill(K, K + kResizeMaxTaps, 0);
         count[o] = resize_weights_of(filter, in_size, out_size, o, &first[o], K, 1);
     }
+    return FPNG_AMD_OK;
+}
+
+// fpng_amd_resize_weights_filter for the RESAMPLE filters: resample_weights_of, the text the kernels' resample instantiations run;
+// NEAREST: resize_nearest_indices, the text the host fills a view's indices with
+extern "C" int fpng_amd_resample_weights(uint32_t in_size, uint32_t out_size, uint32_t resample_filter, uint32_t *first, uint32_t *count, int32_t *weights)
+{
+    if (!first || !count || !weights) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (resample_filter < FPNG_AMD_RESAMPLE_NEAREST || resample_filter > FPNG_AMD_RESAMPLE_LANCZOS)
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown filter (FPNG_AMD_RESAMPLE_NEAREST, _BOX, _HAMMING, _LANCZOS)");
+    const uint32_t filter = resample_filter + (kResizeNearest - FPNG_AMD_RESAMPLE_NEAREST);
+    if (!resize_scale_ok(in_size, out_size, filter))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, filter == kResizeLanczos ? "in_size and out_size are at least 1, and 3 * in_size <= 32 * out_size (Lanczos)"
+                                                                       : "in_size and out_size are at least 1, and in_size <= 32 * out_size (nearest, box, Hamming)");
+    if (filter == kResizeNearest && !resize_nearest_indices(in_size, out_size, 0, out_size, first)) return fail(FPNG_AMD_ERR_UNSUPPORTED, "a NEAREST index outside the input");
+    for (uint32_t o = 0; o < out_size; o++) {
+        int32_t *K = weights + (size_t)o * kResizeMaxTaps;
+        std::fill(K, K + kResizeMaxTaps, 0);
+        if (filter == kResizeNearest) count[o] = 1, K[0] = 1 << kResizeBits;
+        else count[o] = resample_weights_of(filter, in_size, out_size, o, &first[o], K, 1);
+    }
+    return FPNG_AMD_OK;
+}
+
+extern "C" int fpng_amd_resample_view_source(const fpng_amd_crop *crop, const fpng_amd_resize_view *view, const fpng_amd_view_resample *resample, fpng_amd_crop *box)
+{
+    if (!crop || !view || !resample || !box) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    if (const char *why = check_resample_record(*resample)) return fail(FPNG_AMD_ERR_INVALID_ARG, why);
+    if (int rc = check_view_records(crop, view, 1, resample)) return rc;
+    const DecCrop b = view_box({crop->x, crop->y, crop->w, crop->h}, *view, resample);
+    box->x = b.x, box->y = b.y, box->w = b.w, box->h = b.h;
     return FPNG_AMD_OK;
 }
 

@@ -1,6 +1,7 @@
 // resize.hip -- the second stage of fpng_amd_decode_batch(_device)_planar_resize, _planar_resize_view and _planar_views: uint8
 // planes of the file, which the crop kernels of decode.hip (dec_unfilter_crop_kernel<-1, *>, dec_stored_crop_kernel<-1>) left in the
-// decode scratch, are resized by the rule of resize.h (bilinear or bicubic), mirrored where asked, and written once -- bytes, or
+// decode scratch, are resized by the rule of resize.h (bilinear or bicubic; in the _views_resample calls also Pillow's nearest, box,
+// Hamming and Lanczos), mirrored where asked, and written once -- bytes, or
 // the float call's elements.  What is written is a WINDOW (x, y, w, h) of the crop resized to full_w x full_h (the plain resize
 // call: the whole of it); the scratch holds the box of the crop that the window's taps reach, so a tap at crop column f is byte
 // f - box_x of its row -- as a sub-rectangle of the planes of ONE box per file that holds the boxes of all of the file's views (the
@@ -40,7 +41,9 @@ namespace {
 // one plane, so the PREMULTIPLIED op, whose store divides a colour plane's result by the alpha plane's, never comes here: a planar
 // call with such a view runs dec_resize_color_kernel under identity matrices (decode_api.cpp: normalise_views).  false: the kernel
 // that was there before there was an alpha stage
-template <int kDtype, bool kAnyFilter, bool kAlpha = false>
+// kResample: the launch's records may carry a RESAMPLE filter (resize.h: NEAREST, BOX, HAMMING, LANCZOS): step 1 takes every record's
+// weights from resample_tile_weights, the filter a value (kAnyFilter is then not looked at); false: the kernel as it was
+template <int kDtype, bool kAnyFilter, bool kAlpha = false, bool kResample = false>
 __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t plane, uint32_t tile, const DecFloat &flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
@@ -51,17 +54,21 @@ __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t pla
     uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
     uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
     const uint32_t tid = threadIdx.x;
-    const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
+    [[maybe_unused]] const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
     // ---- 1. the tile's weights (first: relative to the view's box, which the host made of these samples' own first and count --
     //      resize_taps -- so first >= box_x and first >= box_y, whatever the file's other views are) ----
     if (tid < kResizeTileW) {
         uint32_t first = r.box_x, count = 0;
-        if (ox0 + tid < r.w) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        if constexpr (kResample) {
+            if (ox0 + tid < r.w) count = resample_tile_weights(r.filter, r.in_w, r.full_w, r.x + ox0 + tid, r.nearest, ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        } else if (ox0 + tid < r.w) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
         fx[tid] = first - r.box_x, cx[tid] = count;
     } else if (tid < kResizeTileW + kResizeTileH) {
         const uint32_t q = tid - kResizeTileW;
         uint32_t first = r.box_y, count = 0;
-        if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        if constexpr (kResample) {
+            if (q < nq) count = resample_tile_weights(r.filter, r.in_h, r.full_h, r.y + oq0 + q, r.nearest + r.w, oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        } else if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
         fy[q] = first - r.box_y, cy[q] = count;
     }
     __syncthreads();
@@ -124,7 +131,7 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
 // plane, tile) and none in surplus.  pre[k] (k = 0 .. n): the workgroups of the batch's records in front of this launch's record k
 // (planes x tiles each, never 0), so workgroup b of the launch is number pre[0] + b of the batch and belongs to the last record
 // whose pre is not above that; the launch has pre[n] - pre[0] workgroups.  The search is the same for all of a workgroup's threads.
-template <int kDtype, bool kAnyFilter, bool kAlpha = false>
+template <int kDtype, bool kAnyFilter, bool kAlpha = false, bool kResample = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_exact_kernel(const DecResize *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     const uint64_t g = pre[0] + blockIdx.x;
@@ -138,28 +145,30 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_exact_kernel(const De
     const uint32_t rel = (uint32_t)(g - pre[lo]), tiles = (uint32_t)resize_tiles(r.w, r.h); // (planes x tiles < 2^24: the host's rule)
     const uint32_t plane = rel / tiles;
     if (plane >= r.planes) return; // (never, with the host's pre)
-    dec_resize_tile<kDtype, kAnyFilter, kAlpha>(r, plane, rel - plane * tiles, flt);
+    dec_resize_tile<kDtype, kAnyFilter, kAlpha, kResample>(r, plane, rel - plane * tiles, flt);
 }
 
 } // namespace
 
-bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
+bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                              bool any_alpha)
 {
     using Kernel = void (*)(const DecResize *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
+    static const Kernel kernels[2][kResizeLaunchKinds][kDecFloatTypes + 1] = {
         {{dec_resize_exact_kernel<-1, false>, dec_resize_exact_kernel<0, false>, dec_resize_exact_kernel<1, false>, dec_resize_exact_kernel<2, false>},
-         {dec_resize_exact_kernel<-1, true>, dec_resize_exact_kernel<0, true>, dec_resize_exact_kernel<1, true>, dec_resize_exact_kernel<2, true>}},
+         {dec_resize_exact_kernel<-1, true>, dec_resize_exact_kernel<0, true>, dec_resize_exact_kernel<1, true>, dec_resize_exact_kernel<2, true>},
+         {dec_resize_exact_kernel<-1, true, false, true>, dec_resize_exact_kernel<0, true, false, true>, dec_resize_exact_kernel<1, true, false, true>, dec_resize_exact_kernel<2, true, false, true>}},
         {{dec_resize_exact_kernel<-1, false, true>, dec_resize_exact_kernel<0, false, true>, dec_resize_exact_kernel<1, false, true>, dec_resize_exact_kernel<2, false, true>},
-         {dec_resize_exact_kernel<-1, true, true>, dec_resize_exact_kernel<0, true, true>, dec_resize_exact_kernel<1, true, true>, dec_resize_exact_kernel<2, true, true>}}};
+         {dec_resize_exact_kernel<-1, true, true>, dec_resize_exact_kernel<0, true, true>, dec_resize_exact_kernel<1, true, true>, dec_resize_exact_kernel<2, true, true>},
+         {dec_resize_exact_kernel<-1, true, true, true>, dec_resize_exact_kernel<0, true, true, true>, dec_resize_exact_kernel<1, true, true, true>, dec_resize_exact_kernel<2, true, true, true>}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups, far below the 2^31 a grid's dimension allows)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
-    if (lds_bytes > 65536u) return false;
+    if (lds_bytes > 65536u || filters >= kResizeLaunchKinds) return false;
     for (uint32_t r0 = 0; r0 < n;) {
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_alpha][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
+        hipLaunchKernelGGL(kernels[any_alpha][filters][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
                            r1 - r0, flt ? *flt : DecFloat{});
         r0 = r1;
     }
@@ -200,7 +209,8 @@ namespace {
 // kAlpha (view_alpha.h): the load of step 2 makes P' as dec_resize_tile's does; a PREMULTIPLIED view runs the passes for all FOUR planes,
 // whatever the destination's count -- R'_3 is then byte 3 of the same register -- and divides the three colour bytes by it before
 // they go to O.
-template <int kDtype, bool kAnyFilter, bool kAlpha = false>
+// kResample: as dec_resize_tile's
+template <int kDtype, bool kAnyFilter, bool kAlpha = false, bool kResample = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecResizeHwc *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
@@ -222,16 +232,20 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
     uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
     uint8_t *const T = (uint8_t *)(cy + kResizeTileH), *const O = resize_lds; // (O: once the passes are done, in the place of everything else)
     const uint32_t tid = threadIdx.x;
-    const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
+    [[maybe_unused]] const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
     // ---- 1. the tile's weights ----
     if (tid < kResizeTileW) {
         uint32_t first = r.box_x, count = 0;
-        if (tid < nw) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        if constexpr (kResample) {
+            if (tid < nw) count = resample_tile_weights(r.filter, r.in_w, r.full_w, r.x + ox0 + tid, r.nearest, ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        } else if (tid < nw) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
         fx[tid] = first - r.box_x, cx[tid] = count;
     } else if (tid < kResizeTileW + kResizeTileH) {
         const uint32_t q = tid - kResizeTileW;
         uint32_t first = r.box_y, count = 0;
-        if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        if constexpr (kResample) {
+            if (q < nq) count = resample_tile_weights(r.filter, r.in_h, r.full_h, r.y + oq0 + q, r.nearest + r.w, oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        } else if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
         fy[q] = first - r.box_y, cy[q] = count;
     }
     __syncthreads();
@@ -346,23 +360,25 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
 
 } // namespace
 
-bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
+bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                            bool any_alpha)
 {
     using Kernel = void (*)(const DecResizeHwc *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][2][kDecFloatTypes + 1] = {
+    static const Kernel kernels[2][kResizeLaunchKinds][kDecFloatTypes + 1] = {
         {{dec_resize_hwc_kernel<-1, false>, dec_resize_hwc_kernel<0, false>, dec_resize_hwc_kernel<1, false>, dec_resize_hwc_kernel<2, false>},
-         {dec_resize_hwc_kernel<-1, true>, dec_resize_hwc_kernel<0, true>, dec_resize_hwc_kernel<1, true>, dec_resize_hwc_kernel<2, true>}},
+         {dec_resize_hwc_kernel<-1, true>, dec_resize_hwc_kernel<0, true>, dec_resize_hwc_kernel<1, true>, dec_resize_hwc_kernel<2, true>},
+         {dec_resize_hwc_kernel<-1, true, false, true>, dec_resize_hwc_kernel<0, true, false, true>, dec_resize_hwc_kernel<1, true, false, true>, dec_resize_hwc_kernel<2, true, false, true>}},
         {{dec_resize_hwc_kernel<-1, false, true>, dec_resize_hwc_kernel<0, false, true>, dec_resize_hwc_kernel<1, false, true>, dec_resize_hwc_kernel<2, false, true>},
-         {dec_resize_hwc_kernel<-1, true, true>, dec_resize_hwc_kernel<0, true, true>, dec_resize_hwc_kernel<1, true, true>, dec_resize_hwc_kernel<2, true, true>}}};
+         {dec_resize_hwc_kernel<-1, true, true>, dec_resize_hwc_kernel<0, true, true>, dec_resize_hwc_kernel<1, true, true>, dec_resize_hwc_kernel<2, true, true>},
+         {dec_resize_hwc_kernel<-1, true, true, true>, dec_resize_hwc_kernel<0, true, true, true>, dec_resize_hwc_kernel<1, true, true, true>, dec_resize_hwc_kernel<2, true, true, true>}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
-    if (lds_bytes > 65536u) return false;
+    if (lds_bytes > 65536u || filters >= kResizeLaunchKinds) return false;
     for (uint32_t r0 = 0; r0 < n;) {
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_alpha][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
+        hipLaunchKernelGGL(kernels[any_alpha][filters][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
                            r1 - r0, flt ? *flt : DecFloat{});
         r0 = r1;
     }

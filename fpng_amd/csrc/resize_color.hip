@@ -52,7 +52,8 @@ template <int kDtype> __device__ __forceinline__ void color_store(uint8_t *p, ui
     else *(u16_a *)p = (uint16_t)b;
 }
 
-template <int kDtype, bool kAnyFilter, bool kHwc, bool kAlpha = false>
+// kResample: as dec_resize_tile's (resize.hip)
+template <int kDtype, bool kAnyFilter, bool kHwc, bool kAlpha = false, bool kResample = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const DecResizeColor *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
@@ -74,16 +75,20 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
     uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
     uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
     const uint32_t tid = threadIdx.x;
-    const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
+    [[maybe_unused]] const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
     // ---- 1. the tile's weights ----
     if (tid < kResizeTileW) {
         uint32_t first = r.box_x, count = 0;
-        if (tid < nw) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        if constexpr (kResample) {
+            if (tid < nw) count = resample_tile_weights(r.filter, r.in_w, r.full_w, r.x + ox0 + tid, r.nearest, ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
+        } else if (tid < nw) count = resize_weights_of(filter, r.in_w, r.full_w, r.x + ox0 + tid, &first, Kx + tid, kResizeTileW, r.taps_x);
         fx[tid] = first - r.box_x, cx[tid] = count;
     } else if (tid < kResizeTileW + kResizeTileH) {
         const uint32_t q = tid - kResizeTileW;
         uint32_t first = r.box_y, count = 0;
-        if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        if constexpr (kResample) {
+            if (q < nq) count = resample_tile_weights(r.filter, r.in_h, r.full_h, r.y + oq0 + q, r.nearest + r.w, oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
+        } else if (q < nq) count = resize_weights_of(filter, r.in_h, r.full_h, r.y + oq0 + q, &first, Ky + q, kResizeTileH, r.taps_y);
         fy[q] = first - r.box_y, cy[q] = count;
     }
     __syncthreads();
@@ -213,27 +218,31 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
 
 } // namespace
 
-bool launch_dec_resize_color(hipStream_t s, const DecResizeColor *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
+bool launch_dec_resize_color(hipStream_t s, const DecResizeColor *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                              bool hwc, bool any_alpha)
 {
     using Kernel = void (*)(const DecResizeColor *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][2][2][kDecFloatTypes + 1] = {
+    static const Kernel kernels[2][2][kResizeLaunchKinds][kDecFloatTypes + 1] = {
         {{{dec_resize_color_kernel<-1, false, false>, dec_resize_color_kernel<0, false, false>, dec_resize_color_kernel<1, false, false>, dec_resize_color_kernel<2, false, false>},
-          {dec_resize_color_kernel<-1, true, false>, dec_resize_color_kernel<0, true, false>, dec_resize_color_kernel<1, true, false>, dec_resize_color_kernel<2, true, false>}},
+          {dec_resize_color_kernel<-1, true, false>, dec_resize_color_kernel<0, true, false>, dec_resize_color_kernel<1, true, false>, dec_resize_color_kernel<2, true, false>},
+          {dec_resize_color_kernel<-1, true, false, false, true>, dec_resize_color_kernel<0, true, false, false, true>, dec_resize_color_kernel<1, true, false, false, true>, dec_resize_color_kernel<2, true, false, false, true>}},
          {{dec_resize_color_kernel<-1, false, true>, dec_resize_color_kernel<0, false, true>, dec_resize_color_kernel<1, false, true>, dec_resize_color_kernel<2, false, true>},
-          {dec_resize_color_kernel<-1, true, true>, dec_resize_color_kernel<0, true, true>, dec_resize_color_kernel<1, true, true>, dec_resize_color_kernel<2, true, true>}}},
+          {dec_resize_color_kernel<-1, true, true>, dec_resize_color_kernel<0, true, true>, dec_resize_color_kernel<1, true, true>, dec_resize_color_kernel<2, true, true>},
+          {dec_resize_color_kernel<-1, true, true, false, true>, dec_resize_color_kernel<0, true, true, false, true>, dec_resize_color_kernel<1, true, true, false, true>, dec_resize_color_kernel<2, true, true, false, true>}}},
         {{{dec_resize_color_kernel<-1, false, false, true>, dec_resize_color_kernel<0, false, false, true>, dec_resize_color_kernel<1, false, false, true>, dec_resize_color_kernel<2, false, false, true>},
-          {dec_resize_color_kernel<-1, true, false, true>, dec_resize_color_kernel<0, true, false, true>, dec_resize_color_kernel<1, true, false, true>, dec_resize_color_kernel<2, true, false, true>}},
+          {dec_resize_color_kernel<-1, true, false, true>, dec_resize_color_kernel<0, true, false, true>, dec_resize_color_kernel<1, true, false, true>, dec_resize_color_kernel<2, true, false, true>},
+          {dec_resize_color_kernel<-1, true, false, true, true>, dec_resize_color_kernel<0, true, false, true, true>, dec_resize_color_kernel<1, true, false, true, true>, dec_resize_color_kernel<2, true, false, true, true>}},
          {{dec_resize_color_kernel<-1, false, true, true>, dec_resize_color_kernel<0, false, true, true>, dec_resize_color_kernel<1, false, true, true>, dec_resize_color_kernel<2, false, true, true>},
-          {dec_resize_color_kernel<-1, true, true, true>, dec_resize_color_kernel<0, true, true, true>, dec_resize_color_kernel<1, true, true, true>, dec_resize_color_kernel<2, true, true, true>}}}};
+          {dec_resize_color_kernel<-1, true, true, true>, dec_resize_color_kernel<0, true, true, true>, dec_resize_color_kernel<1, true, true, true>, dec_resize_color_kernel<2, true, true, true>},
+          {dec_resize_color_kernel<-1, true, true, true, true>, dec_resize_color_kernel<0, true, true, true, true>, dec_resize_color_kernel<1, true, true, true, true>, dec_resize_color_kernel<2, true, true, true, true>}}}};
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
-    if (lds_bytes > 65536u) return false;
+    if (lds_bytes > 65536u || filters >= kResizeLaunchKinds) return false;
     for (uint32_t r0 = 0; r0 < n;) {
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_alpha][hwc][any_filter][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
+        hipLaunchKernelGGL(kernels[any_alpha][hwc][filters][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
                            flt ? *flt : DecFloat{});
         r0 = r1;
     }

@@ -18,7 +18,7 @@ struct DecResizeHwc {
     DecResize r;
     uint32_t pixel_elems, hwc_flags;
 };
-static_assert(sizeof(DecResizeHwc) == 112 && offsetof(DecResizeHwc, r) == 0 && offsetof(DecResizeHwc, pixel_elems) == 104 && offsetof(DecResizeHwc, hwc_flags) == 108, "DecResizeHwc layout");
+static_assert(sizeof(DecResizeHwc) == 120 && offsetof(DecResizeHwc, r) == 0 && offsetof(DecResizeHwc, pixel_elems) == 112 && offsetof(DecResizeHwc, hwc_flags) == 116, "DecResizeHwc layout");
 
 // the LDS bytes of one tile: resize_tile_lds(), whose bytes the tile's result bytes O[row][column * planes + plane] take over once
 // the passes are done (a tile of few taps and rows needs less than O does)
@@ -32,7 +32,7 @@ FPNG_RESIZE_FN uint32_t resize_hwc_tile_lds(uint32_t taps_x, uint32_t taps_y, ui
 // entries, the TILES of the batch's records in front of each of recs[0 .. n].  lds_bytes: the most resize_hwc_tile_lds() of the
 // launch's records.  false: a record without or with too many tiles, or lds_bytes out of range; nothing more is launched.
 // any_alpha: some record of the launch carries an alpha op (view_alpha.h): the kernel's alpha instantiation.
-bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, bool any_filter,
+bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                            bool any_alpha = false);
 
 } // namespace fpng_amd

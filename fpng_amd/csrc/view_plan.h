@@ -1,5 +1,5 @@
 // view_plan.h -- the host side of the views stage of the planar-family decode calls (include/fpng_amd.h: _planar_resize,
-// _planar_resize_view, {planar,hwc}_views and their _color, _post, _warp, _tone, _enhance and _alpha siblings): what a call asks for
+// _planar_resize_view, {planar,hwc}_views and their _color, _post, _warp, _tone, _enhance, _alpha and _resample siblings): what a call asks for
 // (ViewRequest) and everything the batch keeps about its views (ViewPlan).  decode_api.cpp's stages each make one call into the
 // plan: parse (per file: file_box, file_records, add_job; then close), place (carve_records, carve_scratch, place), plan
 // (write_setup) and finish (enqueue).  Everything up to and including write_setup builds records in host memory and calls nothing
@@ -21,7 +21,7 @@
 namespace fpng_amd {
 
 // which entry-point family was called: the last record array its signature takes
-enum class ViewFamily { Plain, Color, Post, Warp, Tone, Enhance, Alpha };
+enum class ViewFamily { Plain, Color, Post, Warp, Tone, Enhance, Alpha, Resample };
 
 // Everything a planar-family call may carry (NULL: not given).  crops and views without view_count: one view per file, whose
 // destination is the planar file's own (the resize and resize_view calls); with view_count: file i has view_count[i] records of
@@ -38,7 +38,8 @@ struct ViewRequest {
     const fpng_amd_view_warp *warps = nullptr;
     const fpng_amd_view_tone *tones = nullptr;
     const fpng_amd_view_enhance *enhances = nullptr;
-    const fpng_amd_view_alpha *alphas = nullptr; // (the last array of the signatures; its stage sits inside the resize, in front of all others)
+    const fpng_amd_view_alpha *alphas = nullptr; // (its stage sits inside the resize, in front of all others)
+    const fpng_amd_view_resample *resamples = nullptr; // (the last array of the signatures: the resize's own filter)
     ViewFamily family = ViewFamily::Plain;
 };
 
@@ -48,25 +49,38 @@ struct Refusal { // code 0: none
     explicit operator bool() const { return code != 0; }
 };
 
+// the filter a view is resized with, as it travels in DecResize::filter: its RESAMPLE record's (kResizeNearest ..), where there is one
+// with a filter, else the view's own
+inline uint32_t view_filter(const fpng_amd_resize_view &z, const fpng_amd_view_resample *resample)
+{
+    return resample && resample->filter ? resample->filter + (kResizeNearest - FPNG_AMD_RESAMPLE_NEAREST) : z.filter;
+}
+static_assert(FPNG_AMD_RESAMPLE_NEAREST + 1 == kResizeNearest && FPNG_AMD_RESAMPLE_BOX + 1 == kResizeBox && FPNG_AMD_RESAMPLE_HAMMING + 1 == kResizeHamming &&
+                  FPNG_AMD_RESAMPLE_LANCZOS + 1 == kResizeLanczos,
+              "the kernels' RESAMPLE filters");
+
 // the pixels of the file that the taps of view z of `crop` reach (fpng_amd_resize_view_source): per axis first(x) ..
-// first(x + w - 1) + count(x + w - 1) of the crop's samples.  z has passed check_view_records()
-inline DecCrop view_box(const DecCrop &crop, const fpng_amd_resize_view &z)
+// first(x + w - 1) + count(x + w - 1) of the crop's samples.  z has passed check_view_records() under its RESAMPLE record, if any (NEAREST:
+// idx(x) .. idx(x + w - 1) + 1)
+inline DecCrop view_box(const DecCrop &crop, const fpng_amd_resize_view &z, const fpng_amd_view_resample *resample = nullptr)
 {
     uint32_t x0, x1, y0, y1;
-    resize_source_span(z.filter, crop.w, z.full_w, z.x, z.w, &x0, &x1);
-    resize_source_span(z.filter, crop.h, z.full_h, z.y, z.h, &y0, &y1);
+    const uint32_t filter = view_filter(z, resample);
+    resize_source_span(filter, crop.w, z.full_w, z.x, z.w, &x0, &x1);
+    resize_source_span(filter, crop.h, z.full_h, z.y, z.h, &y0, &y1);
     return {crop.x + x0, crop.y + y0, x1 - x0, y1 - y0};
 }
 
 // the ONE box a file with these count >= 1 views decodes (fpng_amd_views_source): the bounding rectangle of their boxes.  The
 // records have passed check_view_records(); the crops may leave the image, so the far edges are taken in 64 bits and the answer's
-// w / h saturate (such a file is refused before its box is used).  each (or NULL): the views' own boxes, view_box() of each
-inline DecCrop views_box(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, DecCrop *each = nullptr)
+// w / h saturate (such a file is refused before its box is used).  each (or NULL): the views' own boxes, view_box() of each;
+// resamples (or NULL): the views' RESAMPLE records
+inline DecCrop views_box(const fpng_amd_crop *crops, const fpng_amd_resize_view *views, uint32_t count, DecCrop *each = nullptr, const fpng_amd_view_resample *resamples = nullptr)
 {
     uint64_t x0 = UINT64_MAX, y0 = UINT64_MAX, x1 = 0, y1 = 0;
     for (uint32_t k = 0; k < count; k++) {
         const DecCrop c = {crops[k].x, crops[k].y, crops[k].w, crops[k].h};
-        const DecCrop v = view_box({0, 0, c.w, c.h}, views[k]); // (within the crop: no sum wraps)
+        const DecCrop v = view_box({0, 0, c.w, c.h}, views[k], resamples ? resamples + k : nullptr); // (within the crop: no sum wraps)
         if (each) each[k] = {c.x + v.x, c.y + v.y, v.w, v.h};
         x0 = std::min<uint64_t>(x0, (uint64_t)c.x + v.x), x1 = std::max<uint64_t>(x1, (uint64_t)c.x + v.x + v.w);
         y0 = std::min<uint64_t>(y0, (uint64_t)c.y + v.y), y1 = std::max<uint64_t>(y1, (uint64_t)c.y + v.y + v.h);
@@ -136,6 +150,9 @@ struct ViewPlan {
     std::vector<DecViewPost> post_recs;                // per post view
     std::vector<DecToneRef> tone_refs;                 // per tone view -- a post view with a tone op -- and the entry that closes the sums
     std::vector<uint32_t> job_rec, job_post, job_tone; // per job and one more: its first record, post record and tone view
+    // the NEAREST views' indices (resize.h: DecResize::nearest), w + h words per such record, in the records' order; until place()
+    // a record's `nearest` is 1 + the index of its first word here (NULL: not a NEAREST view)
+    std::vector<uint32_t> nearest;
     // the launches' prefix sums, an entry per record and one more: workgroups (planes x tiles) of the records in front, their tiles
     // (the per-tile launches), and in a post call the tiles of the direct and of the post records, each kind counted on its own
     std::vector<uint64_t> plane_pre, tile_pre, dir_pre, post_pre;
@@ -144,13 +161,15 @@ struct ViewPlan {
     std::vector<DecResize> file_recs; // (the file at hand: its views' records, their source boxes, pixel_elems and flags)
     std::vector<DecCrop> file_boxes;
     std::vector<std::pair<uint32_t, uint32_t>> file_px;
+    std::vector<uint32_t> file_nearest; // (its NEAREST views' indices; a record's `nearest`: 1 + its first word's index here)
 
     // the scratch: offsets from carve_*(), pointers from place().  recs, pre, post, tone_refs lie inside the set-up block
     struct Carves {
-        size_t recs = 0, pre = 0, post = 0, tone_refs = 0, mid = 0, tone = 0;
+        size_t recs = 0, pre = 0, post = 0, tone_refs = 0, nearest = 0, mid = 0, tone = 0;
     } at;
     uint8_t *d_recs = nullptr, *d_mid = nullptr, *d_tone = nullptr;
     uint64_t *d_pre = nullptr;
+    uint32_t *d_nearest = nullptr;
     DecViewPost *d_post = nullptr;
     DecToneRef *d_tone_refs = nullptr;
 
@@ -165,6 +184,8 @@ struct ViewPlan {
 
     // the alpha op and background of view `view` as they travel in DecResize::flags.  file_chans: the channels of the view's FILE --
     // a file without an alpha plane has P_3 = 255, for which every op is the identity: its records normalise to op 0
+    uint32_t filter_of(uint32_t view) const { return view_filter(rq.views[view], rq.resamples ? rq.resamples + view : nullptr); }
+
     uint32_t alpha_flags(uint32_t view, uint32_t file_chans) const { return rq.alphas && file_chans == 4 ? resize_alpha_flags(rq.alphas[view]) : 0u; }
 
     // the planes that file i's job decodes into the scratch: the destination's `planes`, and all four of a 4-channel file of which
@@ -192,7 +213,7 @@ struct ViewPlan {
     {
         const uint32_t v0 = first_view(i), nv = views_of(i);
         file_boxes.resize(nv);
-        return views_box(rq.crops + v0, rq.views + v0, nv, file_boxes.data());
+        return views_box(rq.crops + v0, rq.views + v0, nv, file_boxes.data(), rq.resamples ? rq.resamples + v0 : nullptr);
     }
 
     // the destinations of file i's views judged, and a record per view for the resize kernels, which read the view's own box inside
@@ -203,7 +224,7 @@ struct ViewPlan {
     {
         if (crop.w >= 0x80000000u) return {FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31"};
         const uint32_t v0 = first_view(i), nv = views_of(i);
-        file_recs.clear(), file_px.clear();
+        file_recs.clear(), file_px.clear(), file_nearest.clear();
         for (uint32_t v = v0; v < v0 + nv; v++) {
             const fpng_amd_resize_view &z = rq.views[v];
             const fpng_amd_view_dest dest = rq.hwc     ? fpng_amd_view_dest{rq.hwc[v].d_pixels, 0, 0, 0}
@@ -218,10 +239,17 @@ struct ViewPlan {
             rs.src = (const uint8_t *)(uintptr_t)((size_t)(box.y - crop.y) * crop.w + (box.x - crop.x));
             rs.src_pitch = crop.w, rs.src_plane_pitch = (uint64_t)crop.w * crop.h;
             rs.dst = dest.d_pixels, rs.plane_pitch = d.plane_pitch, rs.pitch = (int32_t)d.pitch;
-            rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags | alpha_flags(v, file_chans), rs.planes = planes, rs.filter = z.filter;
+            rs.in_w = whole_crop.w, rs.in_h = whole_crop.h, rs.full_w = z.full_w, rs.full_h = z.full_h, rs.flags = z.flags | alpha_flags(v, file_chans), rs.planes = planes, rs.filter = filter_of(v);
             rs.x = z.x, rs.y = z.y, rs.w = z.w, rs.h = z.h;
             rs.box_x = box.x - whole_crop.x, rs.box_y = box.y - whole_crop.y;
-            rs.taps_x = resize_max_taps(rs.in_w, z.full_w, z.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, z.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, z.filter);
+            rs.taps_x = resize_max_taps(rs.in_w, z.full_w, rs.filter), rs.taps_y = resize_max_taps(rs.in_h, z.full_h, rs.filter), rs.rows = resize_tile_rows(rs.in_h, z.full_h, rs.filter);
+            if (rs.filter == kResizeNearest) { // (the window's columns, then its rows, as samples of the crop)
+                const size_t at = file_nearest.size();
+                file_nearest.resize(at + (size_t)z.w + z.h);
+                if (!resize_nearest_indices(rs.in_w, z.full_w, z.x, z.w, file_nearest.data() + at) || !resize_nearest_indices(rs.in_h, z.full_h, z.y, z.h, file_nearest.data() + at + z.w))
+                    return {FPNG_AMD_ERR_UNSUPPORTED, "a NEAREST index outside the crop"};
+                rs.nearest = (const uint32_t *)(uintptr_t)(at + 1);
+            }
             file_recs.push_back(rs);
             if (rq.hwc) file_px.push_back({rq.hwc[v].pixel_elems ? rq.hwc[v].pixel_elems : planes, rq.hwc[v].flags});
         }
@@ -243,6 +271,7 @@ struct ViewPlan {
         job_tone.push_back((uint32_t)tone_refs.size());
         for (DecResize &rs : file_recs) {
             rs.src += mid_total; // (an offset until place())
+            if (rs.nearest) rs.nearest = (const uint32_t *)((uintptr_t)rs.nearest + nearest.size()); // (1 + an index until place())
             const uint64_t n_tiles = resize_tiles(rs.w, rs.h);
             const uint32_t k = (uint32_t)(&rs - file_recs.data()), view = v0 + k;
             const bool is_post = is_post_view(view);
@@ -273,6 +302,7 @@ struct ViewPlan {
                 if (rq.colors) color_view.push_back(view);
             }
         }
+        nearest.insert(nearest.end(), file_nearest.begin(), file_nearest.end());
         const size_t out = mid_total;
         mid_total += ((size_t)crop.w * crop.h * (in_scratch ? in_scratch : planes) + 15) & ~(size_t)15;
         // (the post views' windows: next to the box's planes)
@@ -310,6 +340,7 @@ struct ViewPlan {
         at.pre = sc.carve(multi() ? (plane_pre.size() + (rq.posts ? 1 : 0)) * sizeof(uint64_t) : 0);
         at.post = sc.carve(post_recs.size() * sizeof(DecViewPost));
         at.tone_refs = sc.carve(tone_refs.size() * sizeof(DecToneRef));
+        at.nearest = sc.carve(nearest.size() * sizeof(uint32_t));
     }
     template <class S> void carve_scratch(S &sc)
     {
@@ -322,11 +353,13 @@ struct ViewPlan {
         if (!active()) return;
         d_recs = base + at.recs, d_mid = base + at.mid;
         d_pre = multi() ? (uint64_t *)(base + at.pre) : nullptr;
+        d_nearest = (uint32_t *)(base + at.nearest);
         d_post = rq.posts ? (DecViewPost *)(base + at.post) : nullptr;
         d_tone_refs = n_tone() ? (DecToneRef *)(base + at.tone_refs) : nullptr, d_tone = n_tone() ? base + at.tone : nullptr;
         for (size_t t = 0; t < n_tone(); t++) post_recs[tone_refs[t].rec].tone = (uint32_t *)(d_tone + t * kToneBytes);
         for (size_t q = 0; q < resize.size(); q++) {
             resize[q].src = d_mid + (size_t)(uintptr_t)resize[q].src;
+            if (resize[q].nearest) resize[q].nearest = d_nearest + ((size_t)(uintptr_t)resize[q].nearest - 1);
             if (rq.posts && post_of[q] >= 0) post_recs[post_of[q]].src = resize[q].dst = d_mid + (size_t)(uintptr_t)resize[q].dst;
         }
     }
@@ -355,6 +388,7 @@ struct ViewPlan {
         if (!active()) return;
         uint8_t *const h_recs = h_setup + (at.recs - setup_ofs), *const h_pre = h_setup + (at.pre - setup_ofs);
         const size_t nd = resize.size() - post_recs.size(), step = rec_bytes();
+        if (!nearest.empty()) std::memcpy(h_setup + (at.nearest - setup_ofs), nearest.data(), nearest.size() * sizeof(uint32_t));
         size_t di = 0, pi = 0;
         if (rq.posts) dir_pre.assign(1, 0), post_pre.assign(1, 0), job_post.clear();
         for (size_t k = 0, q = 0; k < job_rec.size(); k++) {

@@ -621,7 +621,7 @@ int fpng_amd_decode_crop_tiles(uint32_t file_w, uint32_t file_h, const fpng_amd_
  *      FPNG_AMD_DECODE_UNDECIDED, FPNG_AMD_DECODE_MAX_ROUNDS and the checksum flags behave as in the crop call.
  *      Not offered by THIS call: a window of the resized image and the bicubic filter (fpng_amd_decode_batch_planar_resize_view,
  *      below, has both), and premultiplied alpha or a background (every plane is resized on its own, as an "L" image; the
- *      _views_alpha calls, below, have both).  Not offered at all: antialias off, nearest and Lanczos; a resize without a crop record (give the whole image as the crop); fpng_amd_decode_host and the
+ *      _views_alpha calls, below, have both).  Nearest, box, Hamming and Lanczos: the _views_resample calls, below.  Not offered at all: antialias off; a resize without a crop record (give the whole image as the crop); fpng_amd_decode_host and the
  *      fpng:: drop-in.  Interleaved (channels-last) destinations: fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize with dlsym. ---- */
 typedef struct fpng_amd_resize {
@@ -663,7 +663,8 @@ int fpng_amd_resize_weights(uint32_t in_size, uint32_t out_size, uint32_t *first
  *      views, an empty crop, full_w, full_h, w or h of 0, x + w > full_w or y + h > full_h (in 64 bits), unknown flag bits, an
  *      unknown filter, and a crop past the filter's scale limit against the FULL size: bilinear crop.w <= 32 * full_w, bicubic
  *      crop.w <= 16 * full_w (the same for h; at most 65 taps either way).  The bound of 2^22 tiles of 64 x 16 applies to the window.
- *      Not offered: antialias off, nearest, Lanczos; fpng_amd_decode_host and the fpng:: drop-in; by THIS call, premultiplied
+ *      Pillow's other four filters (nearest, box, Hamming, Lanczos): the RESAMPLE record of the _views_resample calls, below.
+ *      Not offered: antialias off; fpng_amd_decode_host and the fpng:: drop-in; by THIS call, premultiplied
  *      alpha (the _views_alpha calls, below).
  *      Interleaved (channels-last) destinations: fpng_amd_decode_batch_hwc_views, below.
  *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_resize_view with dlsym. ---- */
@@ -1198,6 +1199,86 @@ int fpng_amd_decode_batch_device_hwc_views_alpha(fpng_amd_encoder *enc, const fp
  * _result makes R of R'.  The texts that the kernels run.  The record is judged as the calls judge it (op 0: a copy) */
 int fpng_amd_view_alpha_source(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in /* 4 planes */, uint8_t *out /* 4 planes */);
 int fpng_amd_view_alpha_result(const fpng_amd_view_alpha *alpha, uint32_t w, uint32_t h, const uint8_t *in /* 4 planes */, uint8_t *out /* 4 planes */);
+/* ---- the alpha call with a RESAMPLE record per view: Pillow's other four filters.  fpng_amd_resize_view::filter knows
+ *      bilinear and bicubic; the record overrides it with Image.NEAREST (what a label map -- a segmentation mask, an instance
+ *      or depth render -- must be resized with, next to its image's crop, mirror and warp), Image.BOX, Image.HAMMING or
+ *      Image.LANCZOS.  The argument lists are those of the _views_alpha calls with `resamples`, a record per view, behind `alphas`;
+ *      colors, posts, warps, tones, enhances and alphas may each be NULL; resamples may not.
+ *      THE RULE.  BOX, HAMMING and LANCZOS are the resize of fpng_amd_decode_batch_planar_resize_view, unchanged -- centre,
+ *      first, count, the two walks over the taps, the division by ww, 2^22 fixed point, both clamps, double arithmetic in the
+ *      order written, nothing contracted -- with a kernel function of the SIGNED argument a and a base support each:
+ *          BOX:      s_f = 0.5;  k_f(a) = a > -0.5 && a <= 0.5 ? 1 : 0
+ *          HAMMING:  s_f = 1;    x = |a|;  x == 0 ? 1 : x >= 1 ? 0 : (x = x * pi;  sin(x) / x * (c0 + c1 * cos(x))) with
+ *                                c0 = (double)0.54f, c1 = (double)0.46f, as Pillow writes them
+ *          LANCZOS:  s_f = 3;    -3 <= a && a < 3 ? sinc(a) * sinc(a / 3) : 0;  sinc(x) = x == 0 ? 1 : (x = x * pi;  sin(x) / x)
+ *        NEAREST is no convolution: Pillow's resize runs it as an affine scale.  Per axis a = (double)in / out, xo = a * 0.5, and
+ *        for o = 0 .. out - 1: idx[o] = (int)xo, then xo += a -- the running sum is part of the rule ((int)((o + 0.5) * a) is
+ *        another table for a fifth of the size pairs below 400; 2 -> 7 is the first).  Output sample o is input sample idx[o]:
+ *        one tap of weight 2^22, so every stage around the resize -- mirror, channels-last, the colour matrix, COMPOSITE alpha,
+ *        float stores, warp, tone, enhance, post -- is what it is for the other filters.  A view's source box is idx[x] ..
+ *        idx[x + w - 1] + 1 per axis.
+ *      EXACTNESS.  NEAREST and BOX: every element exact, as for bilinear and bicubic.  HAMMING and LANCZOS: the kernels and the
+ *      host twin below compute sin and cos with ONE text (fpng_amd/csrc/resize.h: an argument reduction and a polynomial in
+ *      double, errors below 1 ulp) and agree bit for bit, always.  Pillow calls its C library's sin and cos, which is another
+ *      program and may differ in a value's last bit; the weights are rounded to 2^-22, so such a difference changes a weight, by
+ *      one unit, only where k * 2^22 lies within about 1e-9 of a half-integer.  The CPU tests hold the twin against Pillow on some
+ *      13 000 size pairs per filter without meeting a case.
+ *      LIMITS, per axis, the crop against the FULL size: in * max(s_f, 1) <= 32 * out -- 32 x for NEAREST, BOX and HAMMING,
+ *      3 * in <= 32 * out for LANCZOS; at most 65 taps; upscaling is unbounded.
+ *      ALPHA.  COMPOSITE goes with every filter.  Pillow does not premultiply for NEAREST (Image.resize of an RGBA image with
+ *      NEAREST is the four planes resized on their own: the view without an alpha op), so a PREMULTIPLIED alpha record on a view
+ *      whose filter is NEAREST is refused.
+ *      GUARANTEES: a record with filter == 0 leaves its view bit for bit the _views_alpha call's; a call in which every record
+ *      has filter 0 enqueues exactly what that call enqueues, the same kernels in the same instantiations; a record's filter
+ *      overrides its view's fpng_amd_resize_view::filter, which must still be a valid one.  A launch that holds a view with a
+ *      RESAMPLE filter runs the resize kernels' resample instantiations, which take every filter as a value; BOX, HAMMING and
+ *      LANCZOS weights are computed per tile in the kernel, NEAREST indices -- w + h words per view -- on the host.
+ *      FPNG_AMD_ERR_INVALID_ARG, with nothing launched and before the encoder is looked at: a null resamples; an unknown filter;
+ *      non-zero flags or reserved words; a crop past the filter's limit; NEAREST with a PREMULTIPLIED alpha record; and everything
+ *      the alpha call refuses.
+ *      Not offered: antialias off (reducing_gap, Image.reduce); the record in the single-view _planar_resize(_view) calls, in
+ *      fpng_amd_decode_host or in the fpng:: drop-in.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_planar_views_resample with dlsym. ---- */
+#define FPNG_AMD_RESAMPLE_NEAREST 1u
+#define FPNG_AMD_RESAMPLE_BOX 2u
+#define FPNG_AMD_RESAMPLE_HAMMING 3u
+#define FPNG_AMD_RESAMPLE_LANCZOS 4u
+typedef struct fpng_amd_view_resample {
+    uint32_t filter;        /* FPNG_AMD_RESAMPLE_*; 0 = the view's own fpng_amd_resize_view::filter: this view is the alpha call's, untouched */
+    uint32_t flags;         /* 0 */
+    uint32_t reserved[2];   /* 0 */
+} fpng_amd_view_resample;   /* 16 bytes */
+int fpng_amd_decode_batch_planar_views_resample(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                                const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                                const fpng_amd_view_dest *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                                const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                                const fpng_amd_view_tone *tones /* the same, or NULL */, const fpng_amd_view_enhance *enhances /* the same, or NULL */,
+                                                const fpng_amd_view_alpha *alphas /* the same, or NULL */, const fpng_amd_view_resample *resamples /* the same */,
+                                                const fpng_amd_float_format *fmt /* NULL: uint8 planes */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_planar_views_resample(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                       const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest *dests,
+                                                       const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                       const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas,
+                                                       const fpng_amd_view_resample *resamples, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_hwc_views_resample(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count /* n, each >= 1 */,
+                                             const fpng_amd_crop *crops /* sum(view_count) */, const fpng_amd_resize_view *views /* the same */,
+                                             const fpng_amd_view_dest_hwc *dests /* the same */, const fpng_amd_view_color *colors /* the same, or NULL */,
+                                             const fpng_amd_view_post *posts /* the same, or NULL */, const fpng_amd_view_warp *warps /* the same, or NULL */,
+                                             const fpng_amd_view_tone *tones /* the same, or NULL */, const fpng_amd_view_enhance *enhances /* the same, or NULL */,
+                                             const fpng_amd_view_alpha *alphas /* the same, or NULL */, const fpng_amd_view_resample *resamples /* the same */,
+                                             const fpng_amd_float_format *fmt /* NULL: uint8 */, fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_hwc_views_resample(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                                    const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_view_dest_hwc *dests,
+                                                    const fpng_amd_view_color *colors, const fpng_amd_view_post *posts, const fpng_amd_view_warp *warps,
+                                                    const fpng_amd_view_tone *tones, const fpng_amd_view_enhance *enhances, const fpng_amd_view_alpha *alphas,
+                                                    const fpng_amd_view_resample *resamples, const fpng_amd_float_format *fmt, fpng_amd_decode_result *results);
+/* fpng_amd_resize_weights_filter for the RESAMPLE filters (no GPU; the text that the kernels run): out_size rows of 65 weights
+ * (those behind a row's count: 0), first and count per output sample.  NEAREST: count 1, weight 2^22, first = idx.
+ * FPNG_AMD_ERR_INVALID_ARG for null pointers, a filter that is not one of FPNG_AMD_RESAMPLE_*, and sizes past the filter's limit */
+int fpng_amd_resample_weights(uint32_t in_size, uint32_t out_size, uint32_t resample_filter, uint32_t *first, uint32_t *count, int32_t *weights /* out_size * 65 */);
+/* fpng_amd_resize_view_source under a RESAMPLE record (filter 0: that function's answer): the box of the file that the view's
+ * taps reach.  The records are judged as the calls judge them */
+int fpng_amd_resample_view_source(const fpng_amd_crop *crop, const fpng_amd_resize_view *view, const fpng_amd_view_resample *resample, fpng_amd_crop *box);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

@@ -371,10 +371,7 @@ def resize_view_source(crop, full, window=None, filter="bilinear"):
     h) (None: the whole) of the crop (x, y, w, h) resized to full = (full_w, full_h) by `filter` -- which is what the crop stage of
     decode_device_resize_view() decodes: crop_tiles(file_w, file_h, box) names the tiles that run.  No GPU needed.  Whatever the
     call refuses in a record raises FpngAmdError (FPNG_AMD_ERR_INVALID_ARG)."""
-    x, y, w, h = (int(v) for v in crop)
-    if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
-        raise ValueError(f"resize_view_source: crop {tuple(crop)} (four values of 32 bits, not negative)")
-    c, box = _lib.Crop(x, y, w, h), _lib.Crop()
+    c, box = _crop_record("resize_view_source", crop), _lib.Crop()
     v = _view_record("resize_view_source", full, window, filter, False)
     check(_lib.load().fpng_amd_resize_view_source(C.byref(c), C.byref(v), C.byref(box)))
     return box.x, box.y, box.w, box.h
@@ -791,10 +788,7 @@ def resample_weights(in_size, out_size, filter):
 def resample_view_source(crop, full, window=None, filter="bilinear", resample=None):
     """fpng_amd_resample_view_source: resize_view_source() of a view whose RESAMPLE record is view_resample(resample) (a name, None or
     a record).  No GPU needed."""
-    x, y, w, h = (int(v) for v in crop)
-    if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
-        raise ValueError(f"resample_view_source: crop {tuple(crop)} (four values of 32 bits, not negative)")
-    c, box = _lib.Crop(x, y, w, h), _lib.Crop()
+    c, box = _crop_record("resample_view_source", crop), _lib.Crop()
     v = _view_record("resample_view_source", full, window, filter, False)
     r = resample if isinstance(resample, _lib.ViewResample) else view_resample(resample)
     check(_lib.load().fpng_amd_resample_view_source(C.byref(c), C.byref(v), C.byref(r), C.byref(box)))
@@ -1165,8 +1159,22 @@ def synth_image(kind, w, h, num_chans, seed=12345):
     return out.reshape(h, w, num_chans)
 
 
+# The views calls' stages in the order the C calls take their record arrays: (keyword, the descriptor's attribute, the record's
+# class, what to say of an entry that is no such record where the keyword has a wording of its own).  The last stage whose records a
+# descriptor carries names the call.  color and resample take more than records: _color_records / _resample_arg convert them.
+_VIEW_STAGES = (("color", "colors", _lib.ViewColor, None),
+                ("post", "posts", _lib.ViewPost, "a post record is what view_post() returns"),
+                ("warp", "warps", _lib.ViewWarp, "a warp record is what view_warp() returns"),
+                ("tone", "tones", _lib.ViewTone, None),
+                ("enhance", "enhances", _lib.ViewEnhance, None),
+                ("alpha", "alphas", _lib.ViewAlpha, None),
+                ("resample", "resamples", _lib.ViewResample, None))
+
+
 class DecodeBatch:
     """What Encoder.make_decode_batch() returns: the files, the output tensors and the C arrays of one fpng_amd_decode_batch_device() call."""
+
+    maker = "make_decode_batch"
 
     def __init__(self, pngs, outs, arr, res, desired_chans):
         self.pngs, self.outs, self.arr, self.res, self.desired_chans = pngs, outs, arr, res, desired_chans
@@ -1184,10 +1192,24 @@ class DecodeBatch:
 
 
 class _DecodeBatchViews:
-    """The files, the caller's destination views and the C arrays of one decode call into views (DecodeBatchEx, DecodeBatchPlanar)"""
+    """The files, the caller's destination views and the C arrays of one decode call into views (DecodeBatchEx, DecodeBatchPlanar,
+    DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView, DecodeBatchMultiViewHwc).
+    maker: the Encoder method that makes the class's descriptors; extras: the call's further arrays, stored under their names."""
 
-    def __init__(self, pngs, outs, arr, res, device_data, keep):
+    maker = None
+
+    def __init__(self, pngs, outs, arr, res, device_data, keep, **extras):
         self.pngs, self.outs, self.arr, self.res, self.device_data, self._keep = pngs, outs, arr, res, device_data, keep
+        self.__dict__.update(extras)
+
+    @classmethod
+    def call(cls, device_data):
+        """the name of the Encoder method that runs the class's descriptors of files in device / host memory"""
+        return ("decode_device" if device_data else "decode_batch") + cls.maker[len("make_decode_batch"):]
+
+    def tensors(self):
+        """every destination view"""
+        return self.outs
 
     def statuses(self):
         """status of every file after the last call"""
@@ -1202,10 +1224,14 @@ class DecodeBatchEx(_DecodeBatchViews):
     """What Encoder.make_decode_batch_ex() returns: the files, the caller's destination views and the C arrays of one
     fpng_amd_decode_batch(_device)_ex() call."""
 
+    maker = "make_decode_batch_ex"
+
 
 class DecodeBatchPlanar(_DecodeBatchViews):
     """What Encoder.make_decode_batch_planar() returns: the same for one fpng_amd_decode_batch(_device)_planar() call (outs: the
     caller's (c, h, w) views).  Not a DecodeBatchEx: neither call takes the other's descriptor."""
+
+    maker = "make_decode_batch_planar"
 
 
 class DecodeBatchFloat(_DecodeBatchViews):
@@ -1213,9 +1239,7 @@ class DecodeBatchFloat(_DecodeBatchViews):
     caller's float (c, h, w) views, all of one dtype; fmt: the call's fpng_amd_float_format).  Neither a DecodeBatchPlanar nor a
     DecodeBatchEx: no call takes another's descriptor."""
 
-    def __init__(self, pngs, outs, arr, res, device_data, keep, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.fmt = fmt
+    maker = "make_decode_batch_float"
 
 
 class DecodeBatchCrop(_DecodeBatchViews):
@@ -1223,9 +1247,7 @@ class DecodeBatchCrop(_DecodeBatchViews):
     fpng_amd_crop[n]; outs: the caller's (c, crop h, crop w) views, uint8 or all of one float dtype; fmt: the call's
     fpng_amd_float_format, None for uint8 planes).  No other call takes this descriptor."""
 
-    def __init__(self, pngs, outs, arr, res, device_data, keep, crops, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.crops, self.fmt = crops, fmt
+    maker = "make_decode_batch_crop"
 
 
 class DecodeBatchResize(_DecodeBatchViews):
@@ -1233,9 +1255,7 @@ class DecodeBatchResize(_DecodeBatchViews):
     the fpng_amd_crop[n]; sizes: the fpng_amd_resize[n]; outs: the caller's (c, out_h, out_w) views, uint8 or all of one float
     dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No other call takes this descriptor."""
 
-    def __init__(self, pngs, outs, arr, res, device_data, keep, crops, sizes, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.crops, self.sizes, self.fmt = crops, sizes, fmt
+    maker = "make_decode_batch_resize"
 
 
 class DecodeBatchResizeView(_DecodeBatchViews):
@@ -1243,25 +1263,21 @@ class DecodeBatchResizeView(_DecodeBatchViews):
     (crops: the fpng_amd_crop[n]; views: the fpng_amd_resize_view[n]; outs: the caller's (c, window h, window w) views, uint8 or all
     of one float dtype; fmt: the call's fpng_amd_float_format, None for uint8 planes).  No other call takes this descriptor."""
 
-    def __init__(self, pngs, outs, arr, res, device_data, keep, crops, views, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.crops, self.views, self.fmt = crops, views, fmt
+    maker = "make_decode_batch_resize_view"
 
 
 class _DecodeBatchMultiViews(_DecodeBatchViews):
-    """what the descriptors of the views calls share, whatever the destinations' layout"""
-
-    colors = None
-    posts = None  # the fpng_amd_view_post records of a descriptor made with post=, one per view: the call is then the _views_post one
-    warps = None  # the fpng_amd_view_warp records of a descriptor made with warp=, one per view: the call is then the _views_warp one
-    tones = None  # the fpng_amd_view_tone records of a descriptor made with tone=, one per view: the call is then the _views_tone one
-    enhances = None  # the fpng_amd_view_enhance records of a descriptor made with enhance=, one per view: the call is then the _views_enhance one
-    resamples = None  # the fpng_amd_view_resample records of a descriptor made with resample=, one per view: the call is then the _views_resample one
-    alphas = None  # the fpng_amd_view_alpha records of a descriptor made with alpha=, one per view: the call is then the _views_alpha one
+    """What the descriptors of the views calls share, whatever the destinations' layout.  colors, posts, warps, tones, enhances,
+    alphas, resamples (_VIEW_STAGES): the records, one per view, of a descriptor made with color=, post=, ..., else None; the call is
+    then the _views_color, _views_post, ... one."""
 
     def __init__(self, pngs, outs, arr, res, device_data, keep, counts, crops, views, dests, fmt):
-        super().__init__(pngs, outs, arr, res, device_data, keep)
-        self.counts, self.crops, self.views, self.dests, self.fmt = counts, crops, views, dests, fmt
+        super().__init__(pngs, outs, arr, res, device_data, keep, counts=counts, crops=crops, views=views, dests=dests, fmt=fmt)
+        for _, attr, _, _ in _VIEW_STAGES:
+            setattr(self, attr, None)
+
+    def tensors(self):
+        return [t for ts in self.outs for t in ts]
 
     def results(self):
         """list, per file, of (status, the list of the caller's own destination views (filled in place) or None, channels_in_file)"""
@@ -1276,6 +1292,7 @@ class DecodeBatchMultiView(_DecodeBatchMultiViews):
     other call takes this descriptor.  colors: the fpng_amd_view_color records of a descriptor made with color=, one per view (the
     call is then fpng_amd_decode_batch(_device)_planar_views_color), else None."""
 
+    maker = "make_decode_batch_views"
 
 
 class DecodeBatchMultiViewHwc(_DecodeBatchMultiViews):
@@ -1283,6 +1300,8 @@ class DecodeBatchMultiViewHwc(_DecodeBatchMultiViews):
     fpng_amd_decode_batch(_device)_hwc_views() call (dests: the fpng_amd_view_dest_hwc records; outs: per file the list of the
     caller's (window h, window w, c) views; colors: as DecodeBatchMultiView's, for fpng_amd_decode_batch(_device)_hwc_views_color).
     No other call takes this descriptor."""
+
+    maker = "make_decode_batch_views_hwc"
 
 
 def _planar_view_dest(rec, t, order, bottom_up, is_u8):
@@ -1307,21 +1326,98 @@ def _hwc_view_dest(rec, t, order, bottom_up, is_u8):
 
 
 class _ViewsLayout:
-    """What the views calls' two destination layouts differ in.  name: the layout's part of the C symbols; suffix: of the Python
-    methods; dest_cls, batch_cls: the destination record and the descriptor; put_dest: writes a tensor view's destination record
+    """What the views calls' two destination layouts differ in.  name: the layout's part of the C symbols; dest_cls, batch_cls: the
+    destination record and the descriptor, whose maker names the Python methods; put_dest: writes a tensor view's destination record
     (its layout function and pixels_cap formula); chw: a view's shape as (c, h, w); empty_shape: of an allocated (oh, ow) output."""
 
-    def __init__(self, name, suffix, dest_cls, batch_cls, put_dest, chw, empty_shape):
-        self.name, self.suffix, self.dest_cls, self.batch_cls, self.put_dest, self.chw, self.empty_shape = name, suffix, dest_cls, batch_cls, put_dest, chw, empty_shape
-        self.maker, self.host, self.device = f"make_decode_batch_views{suffix}", f"decode_batch_views{suffix}", f"decode_device_views{suffix}"
+    def __init__(self, name, dest_cls, batch_cls, put_dest, chw, empty_shape):
+        self.name, self.dest_cls, self.batch_cls, self.put_dest, self.chw, self.empty_shape = name, dest_cls, batch_cls, put_dest, chw, empty_shape
+        self.maker, self.host, self.device = batch_cls.maker, batch_cls.call(False), batch_cls.call(True)
 
 
-_PLANAR_VIEWS = _ViewsLayout("planar", "", _lib.ViewDest, DecodeBatchMultiView, _planar_view_dest, lambda s: (s[0], s[1], s[2]), lambda oh, ow: (3, oh, ow))
-_HWC_VIEWS = _ViewsLayout("hwc", "_hwc", _lib.ViewDestHwc, DecodeBatchMultiViewHwc, _hwc_view_dest, lambda s: (s[2], s[0], s[1]), lambda oh, ow: (oh, ow, 3))
+_PLANAR_VIEWS = _ViewsLayout("planar", _lib.ViewDest, DecodeBatchMultiView, _planar_view_dest, lambda s: (s[0], s[1], s[2]), lambda oh, ow: (3, oh, ow))
+_HWC_VIEWS = _ViewsLayout("hwc", _lib.ViewDestHwc, DecodeBatchMultiViewHwc, _hwc_view_dest, lambda s: (s[2], s[0], s[1]), lambda oh, ow: (oh, ow, 3))
 
 
-def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha=None, resample=None):
-    """the descriptor of a views call for either layout (Encoder.make_decode_batch_views / _hwc have the rules)"""
+def _per_file(who, n, v, what):
+    """an argument of a per-file call -> a list with a value per file.  v: one value (_VIEW_ARG has what one looks like) for all
+    files, or a sequence with one per file"""
+    vs = [v] * n if _VIEW_ARG[what](v) else list(v)
+    if len(vs) != n:
+        raise ValueError(f"{who}: {n} files, {len(vs)} {what}")
+    return vs
+
+
+def _file_records(who, pngs, arr):
+    """data and size of the file records arr[len(pngs)] of any decode call into views: uint8 CUDA tensors holding whole files, or
+    bytes-like objects in host memory, one kind per call.  -> (device_data, keep: the host copies the records point into)"""
+    device_data = len(pngs) > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+    keep = []
+    for i, p in enumerate(pngs):
+        if device_data:
+            if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
+                raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
+            arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
+        else:
+            b = np.frombuffer(bytes(p), dtype=np.uint8)
+            keep.append(b)
+            arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+    return device_data, keep
+
+
+def _dest_format(who, outs, mean, std, scale, bias, always=False):
+    """The destinations of one call (outs: all of them, in one list) share one dtype: -> (is_u8, the call's fpng_amd_float_format
+    from its constants -- None for uint8 destinations, which take no constants).  always: the call has a format whatever the dtype
+    (make_decode_batch_float, whose layout function refuses the uint8 views).  The format's dtype is the views' to fill in."""
+    dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
+    if len(dtypes) > 1:
+        raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
+    is_u8 = dtypes == {torch.uint8}
+    if is_u8 and not always:
+        if any(v is not None for v in (mean, std, scale, bias)):
+            raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
+        return True, None
+    sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
+    fmt = _lib.FloatFormat()
+    for k in range(4):
+        fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+    return is_u8, fmt
+
+
+def _planar_dests(arr, outs, orders, ups, is_u8, fmt):
+    """the destination part of a per-file call's fpng_amd_png_planar records: file i's is its (c, h, w) view outs[i], as the views
+    calls describe one (_planar_view_dest); float views put their dtype into fmt"""
+    for rec, t, order, up in zip(arr, outs, orders, ups):
+        code = _planar_view_dest(rec, t, order, up, is_u8)
+        rec.num_chans = t.shape[0]
+        if code is not None:
+            fmt.dtype = code
+
+
+def _window_hw(full, window):
+    """(h, w) of the window (x, y, w, h) -- None: the whole -- of an image resized to full = (full_w, full_h)"""
+    return (int(window[3]), int(window[2])) if window is not None else (int(full[1]), int(full[0]))
+
+
+def _alloc_dtype(who, dtype):
+    """the dtype= of a call that allocates its destinations"""
+    if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
+        raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+    return dtype
+
+
+def _fmt_ref(batch):
+    return C.byref(batch.fmt) if batch.fmt is not None else None
+
+
+def _file_symbol(stem, device_data):
+    """the C entry point of a per-file decode call into views: fpng_amd_decode_batch(_device)_<stem>"""
+    return f"fpng_amd_decode_batch{'_device' if device_data else ''}_{stem}"
+
+
+def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, stages):
+    """the descriptor of a views call for either layout (Encoder.make_decode_batch_views / _hwc have the rules).  stages: the stage
+    keywords' values by keyword (_VIEW_STAGES)"""
     who = layout.maker
     n = len(pngs)
     if len(crops) != n or len(outs) != n:
@@ -1333,37 +1429,16 @@ def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, o
             raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
     fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
     filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
-    dtypes = {t.dtype for ts in outs for t in ts if isinstance(t, torch.Tensor)}
-    if len(dtypes) > 1:
-        raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-    is_u8 = dtypes == {torch.uint8}
-    fmt = None
-    if is_u8:
-        if any(v is not None for v in (mean, std, scale, bias)):
-            raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
-    else:
-        sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
-        fmt = _lib.FloatFormat()
-        for k in range(4):
-            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+    is_u8, fmt = _dest_format(who, [t for ts in outs for t in ts], mean, std, scale, bias)
     orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
-    device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
     total = sum(counts)
     arr = (_lib.PngPlanarIn * n)()
     narr = (C.c_uint32 * n)(*counts)
     carr, varr, darr = (_lib.Crop * total)(), (_lib.ResizeView * total)(), (layout.dest_cls * total)()
     res = (_lib.DecodeResult * n)()
-    keep = []
+    device_data, keep = _file_records(who, pngs, arr)
     at = 0
-    for i, p in enumerate(pngs):
-        if device_data:
-            if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
-            arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-        else:
-            b = np.frombuffer(bytes(p), dtype=np.uint8)
-            keep.append(b)
-            arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
+    for i in range(n):
         codes = [layout.put_dest(darr[at + k], t, orders[i][k], bool(ups[i][k]), is_u8) for k, t in enumerate(outs[i])]
         chans = {layout.chw(t.shape)[0] for t in outs[i]}
         if len(chans) != 1:
@@ -1379,20 +1454,14 @@ def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, o
                 raise ValueError(f"{who}: destination {k} of file {i} is {ow} x {oh}, its window {v.w} x {v.h}")
             at += 1
     batch = layout.batch_cls(list(pngs), outs, arr, res, device_data, keep, narr, carr, varr, darr, fmt)
-    if color is not None:
-        batch.colors = _color_records(who, counts, color)
-    if post is not None:
-        batch.posts = _view_records(who, counts, post, _lib.ViewPost, "post", "a post record is what view_post() returns")
-    if warp is not None:
-        batch.warps = _view_records(who, counts, warp, _lib.ViewWarp, "warp", "a warp record is what view_warp() returns")
-    if tone is not None:
-        batch.tones = _view_records(who, counts, tone, _lib.ViewTone, "tone")
-    if enhance is not None:
-        batch.enhances = _view_records(who, counts, enhance, _lib.ViewEnhance, "enhance")
-    if alpha is not None:
-        batch.alphas = _view_records(who, counts, alpha, _lib.ViewAlpha, "alpha")
-    if resample is not None:
-        batch.resamples = _view_records(who, counts, _resample_arg(resample), _lib.ViewResample, "resample")
+    for key, attr, cls, wrong in _VIEW_STAGES:
+        arg = stages.get(key)
+        if arg is None:
+            continue
+        if key == "color":
+            setattr(batch, attr, _color_records(who, counts, arg))
+        else:
+            setattr(batch, attr, _view_records(who, counts, _resample_arg(arg) if key == "resample" else arg, cls, key, wrong))
     return batch
 
 
@@ -1400,10 +1469,9 @@ def views_entry(layout, device_data, batch):
     """The C entry point of a views call and its arguments behind the encoder, as a pure function of the layout ("planar" / "hwc"),
     where the files are and the descriptor: the last stage in the order colour < post < warp < tone < enhance < alpha < resample whose records the
     descriptor carries names the call, and the call takes the record arrays of all stages up to it (None for those not given)."""
-    arrays = [batch.colors, batch.posts, batch.warps, batch.tones, batch.enhances, batch.alphas, batch.resamples]
+    arrays = [getattr(batch, attr) for _, attr, _, _ in _VIEW_STAGES]
     stages = max((k + 1 for k, a in enumerate(arrays) if a is not None), default=0)
-    fmt = C.byref(batch.fmt) if batch.fmt is not None else None
-    return _lib.views_symbol(layout, device_data, stages), [batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, *arrays[:stages], fmt, batch.res]
+    return _lib.views_symbol(layout, device_data, stages), [batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, *arrays[:stages], _fmt_ref(batch), batch.res]
 
 
 class Encoder:
@@ -1737,16 +1805,15 @@ class Encoder:
         n = len(pngs)
         arr = (_lib.PngIn * n)()
         res = (_lib.DecodeResult * n)()
-        keep, outs = [], []
+        device_data, keep = _file_records("decode_batch", pngs, arr)  # (keep: alive until the call has returned)
+        if device_data:
+            raise ValueError("decode_batch: the files are in device memory (decode_device)")
+        outs = []
         for i, p in enumerate(pngs):
-            b = np.frombuffer(bytes(p), dtype=np.uint8)
-            keep.append(b)
             w, h = dims[i] if dims else ((struct.unpack(">II", bytes(p[16:24]))) if len(p) >= 24 else (0, 0))
             cap = w * h * desired_chans if 0 < w <= (1 << 24) and 0 < h <= (1 << 24) and w * h <= (1 << 30) else 0
             t = torch.empty(max(cap, 16), dtype=torch.uint8, device=f"cuda:{self.device}")
             outs.append(t)
-            arr[i].data = b.ctypes.data if b.size else None
-            arr[i].size = b.size
             arr[i].d_pixels = t.data_ptr()
             arr[i].pixels_cap = t.numel()
         self._sync_stream()
@@ -1796,54 +1863,53 @@ class Encoder:
         call's room check (pixels_cap) is the span from the view's first byte to its last, so a file with more rows or more bytes
         than that is refused (FPNG_AMD_ERR_BUFFER_TOO_SMALL), but a shorter, wider one would write between the view's rows.
         Build it once when the same buffers are decoded repeatedly."""
+        who = "make_decode_batch_ex"
         n = len(pngs)
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        if len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(outs)} destinations")
+        orders, ups = _per_file(who, n, order, "plane orders"), _per_file(who, n, bottom_up, "bottom_up flags")
         arr = (_lib.PngExIn * n)()
         res = (_lib.DecodeResult * n)()
-        keep = []
-        for i, (p, t) in enumerate(zip(pngs, outs)):
+        device_data, keep = _file_records(who, pngs, arr)
+        for i, t in enumerate(outs):
             if not (isinstance(t, torch.Tensor) and t.is_cuda):
-                raise ValueError("make_decode_batch_ex: the destinations are CUDA tensors")
+                raise ValueError(f"{who}: the destinations are CUDA tensors")
             ptr, rp, fmt = dest_layout(t, orders[i], ups[i])
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError("make_decode_batch_ex: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
             h, w, _ = t.shape
             arr[i].format, arr[i].d_pixels, arr[i].row_pitch = fmt, ptr, rp
             arr[i].pixels_cap = (h - 1) * abs(rp) + w * dest_bytes(fmt)  # (the view's own rows: nothing around them)
         return DecodeBatchEx(list(pngs), list(outs), arr, res, device_data, keep)
 
+    def _run_decode(self, cls, device_data, pngs, make, entry, results):
+        """What every decode call into views does.  cls: the call's descriptor class; pngs: such a descriptor, or the files, of which
+        make(who) then builds one; entry(batch): the C entry point's name and its arguments behind the encoder."""
+        who = cls.call(device_data)
+        if isinstance(pngs, (DecodeBatch, _DecodeBatchViews)) and not isinstance(pngs, cls):
+            raise ValueError(f"{who}: a {type(pngs).maker}() descriptor is another call's ({cls.maker}() makes this one's)")
+        batch = pngs if isinstance(pngs, cls) else make(who)
+        if batch.device_data != device_data:
+            raise ValueError(f"{who}: the files are in " + (f"host memory ({cls.call(False)})" if device_data else f"device memory ({cls.call(True)})"))
+        if not all(t.is_cuda for t in batch.tensors()):
+            raise ValueError(f"{who}: the destinations are CUDA tensors")
+        self._sync_stream()
+        symbol, args = entry(batch)
+        check(getattr(self.lib, symbol)(self.h, *args))
+        return batch.results() if results else batch
+
+    def _decode_ex(self, device_data, pngs, outs, order, bottom_up, results):
+        return self._run_decode(DecodeBatchEx, device_data, pngs, lambda who: self.make_decode_batch_ex(pngs, outs, order, bottom_up),
+                                lambda b: (_file_symbol("ex", device_data), [b.arr, len(b.arr), b.res]), results)
+
     def decode_device_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_device_ex: uint8 CUDA tensors holding whole files, decoded into the caller's device tensor views
         `outs` in place (make_decode_batch_ex() has the rules) -> list of (status, the caller's view or None, channels_in_file).
         pngs may be a make_decode_batch_ex() descriptor of device files (outs = None); results=False returns the descriptor."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
-            raise ValueError("decode_device_ex: a planar, float or crop descriptor (decode_device_planar, decode_device_float, decode_device_crop)")
-        batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
-        if not batch.device_data:
-            raise ValueError("decode_device_ex: the files are in host memory (decode_batch_ex)")
-        self._sync_stream()
-        check(self.lib.fpng_amd_decode_batch_device_ex(self.h, batch.arr, len(batch.arr), batch.res))
-        return batch.results() if results else batch
+        return self._decode_ex(True, pngs, outs, order, bottom_up, results)
 
     def decode_batch_ex(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_ex: files in host memory (bytes) decoded into the caller's device tensor views -- decode_device_ex()
         for host-resident files.  pngs may be a make_decode_batch_ex() descriptor of host files (outs = None)."""
-        if isinstance(pngs, (DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
-            raise ValueError("decode_batch_ex: a planar, float or crop descriptor (decode_batch_planar, decode_batch_float, decode_batch_crop)")
-        batch = pngs if isinstance(pngs, DecodeBatchEx) else self.make_decode_batch_ex(pngs, outs, order, bottom_up)
-        if batch.device_data:
-            raise ValueError("decode_batch_ex: the files are in device memory (decode_device_ex)")
-        self._sync_stream()
-        check(self.lib.fpng_amd_decode_batch_ex(self.h, batch.arr, len(batch.arr), batch.res))
-        return batch.results() if results else batch
+        return self._decode_ex(False, pngs, outs, order, bottom_up, results)
 
     @staticmethod
     def make_decode_batch_planar(pngs, outs, order="rgb", bottom_up=False):
@@ -1853,56 +1919,31 @@ class Encoder:
         dest_layout_planar(view, order, bottom_up) (order / bottom_up: one value, or one per file).  c = the planes written, 3 or 4.
         Size every view to its file, as for make_decode_batch_ex(): pixels_cap is the view's own span.  Build it once when the same
         buffers are decoded repeatedly."""
+        who = "make_decode_batch_planar"
         n = len(pngs)
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        if len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(outs)} destinations")
+        orders, ups = _per_file(who, n, order, "plane orders"), _per_file(who, n, bottom_up, "bottom_up flags")
         arr = (_lib.PngPlanarIn * n)()
         res = (_lib.DecodeResult * n)()
-        keep = []
-        for i, (p, t) in enumerate(zip(pngs, outs)):
-            ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError("make_decode_batch_planar: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            c, h, w = t.shape
-            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
-            arr[i].pixels_cap = (c - 1) * abs(pp) + (h - 1) * abs(rp) + w  # (the view's own spans: nothing around them)
+        device_data, keep = _file_records(who, pngs, arr)
+        _planar_dests(arr, outs, orders, ups, True, None)
         return DecodeBatchPlanar(list(pngs), list(outs), arr, res, device_data, keep)
 
-    def _decode_planar(self, who, fn, device_data, pngs, outs, order, bottom_up, results):
-        if isinstance(pngs, DecodeBatchEx):
-            raise ValueError(f"{who}: a make_decode_batch_ex() descriptor (decode_device_ex / decode_batch_ex)")
-        if isinstance(pngs, DecodeBatchFloat):
-            raise ValueError(f"{who}: a make_decode_batch_float() descriptor (decode_device_float / decode_batch_float)")
-        if isinstance(pngs, DecodeBatchCrop):
-            raise ValueError(f"{who}: a make_decode_batch_crop() descriptor (decode_device_crop / decode_batch_crop)")
-        if isinstance(pngs, DecodeBatchResize):
-            raise ValueError(f"{who}: a make_decode_batch_resize() descriptor (decode_device_resize / decode_batch_resize)")
-        batch = pngs if isinstance(pngs, DecodeBatchPlanar) else self.make_decode_batch_planar(pngs, outs, order, bottom_up)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_planar)" if device_data else "device memory (decode_device_planar)"))
-        if not all(t.is_cuda for t in batch.outs):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        check(fn(self.h, batch.arr, len(batch.arr), batch.res))
-        return batch.results() if results else batch
+    def _decode_planar(self, device_data, pngs, outs, order, bottom_up, results):
+        return self._run_decode(DecodeBatchPlanar, device_data, pngs, lambda who: self.make_decode_batch_planar(pngs, outs, order, bottom_up),
+                                lambda b: (_file_symbol("planar", device_data), [b.arr, len(b.arr), b.res]), results)
 
     def decode_device_planar(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_device_planar: uint8 CUDA tensors holding whole files, decoded into the caller's (c, h, w) device
         tensor views `outs` in place (make_decode_batch_planar() has the rules) -> list of (status, the caller's view or None,
         channels_in_file) -- without the permute(2, 0, 1).contiguous() copy behind a packed decode.  pngs may be a
         make_decode_batch_planar() descriptor of device files (outs = None); results=False returns the descriptor."""
-        return self._decode_planar("decode_device_planar", self.lib.fpng_amd_decode_batch_device_planar, True, pngs, outs, order, bottom_up, results)
+        return self._decode_planar(True, pngs, outs, order, bottom_up, results)
 
     def decode_batch_planar(self, pngs, outs=None, order="rgb", bottom_up=False, results=True):
         """fpng_amd_decode_batch_planar: decode_device_planar() for files in host memory (bytes)."""
-        return self._decode_planar("decode_batch_planar", self.lib.fpng_amd_decode_batch_planar, False, pngs, outs, order, bottom_up, results)
+        return self._decode_planar(False, pngs, outs, order, bottom_up, results)
 
     @staticmethod
     def make_decode_batch_float(pngs, outs, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
@@ -1912,57 +1953,32 @@ class Encoder:
         fmaf(byte, scale[c], bias[c]) of the FILE's channel c (R, G, B, A, whatever the planes' order in memory), rounded to the
         dtype: give mean and std (normalize_constants(): (byte / 255 - mean) / std), or scale and bias (up to four values each,
         padded with 1 / 255 and 0), or neither for plain [0, 1] values.  pixels_cap is the view's own span in bytes."""
-        sc, bi = _float_constants("make_decode_batch_float", normalize_constants, mean, std, scale, bias)
+        who = "make_decode_batch_float"
         n = len(pngs)
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"make_decode_batch_float: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        if len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(outs)} destinations")
+        _, fmt = _dest_format(who, outs, mean, std, scale, bias, always=True)
+        orders, ups = _per_file(who, n, order, "plane orders"), _per_file(who, n, bottom_up, "bottom_up flags")
         arr = (_lib.PngPlanarIn * n)()
         res = (_lib.DecodeResult * n)()
-        fmt = _lib.FloatFormat()
-        keep = []
-        for i, (p, t) in enumerate(zip(pngs, outs)):
-            ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError("make_decode_batch_float: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            c, h, w = t.shape
-            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
-            arr[i].pixels_cap = (c - 1) * abs(pp) + (h - 1) * abs(rp) + w * t.element_size()  # (the view's own spans, in bytes)
-        for k in range(4):
-            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt)
+        device_data, keep = _file_records(who, pngs, arr)
+        _planar_dests(arr, outs, orders, ups, False, fmt)
+        return DecodeBatchFloat(list(pngs), list(outs), arr, res, device_data, keep, fmt=fmt)
 
-    def _decode_float(self, who, fn, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
-            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_float() makes this one's)")
-        batch = pngs if isinstance(pngs, DecodeBatchFloat) else self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_float)" if device_data else "device memory (decode_device_float)"))
-        if not all(t.is_cuda for t in batch.outs):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        check(fn(self.h, batch.arr, len(batch.arr), C.byref(batch.fmt), batch.res))
-        return batch.results() if results else batch
+    def _decode_float(self, device_data, pngs, outs, order, bottom_up, mean, std, scale, bias, results):
+        return self._run_decode(DecodeBatchFloat, device_data, pngs, lambda who: self.make_decode_batch_float(pngs, outs, order, bottom_up, mean, std, scale, bias),
+                                lambda b: (_file_symbol("planar_float", device_data), [b.arr, len(b.arr), _fmt_ref(b), b.res]), results)
 
     def decode_device_float(self, pngs, outs=None, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
         """fpng_amd_decode_batch_device_planar_float: uint8 CUDA tensors holding whole files, decoded into the caller's float (c, h, w)
         device tensor views `outs` in place as normalised values (make_decode_batch_float() has the rules) -> list of (status, the
         caller's view or None, channels_in_file) -- without the x.to(dtype).sub(mean).div(std) pass behind decode_device_planar().
         pngs may be a make_decode_batch_float() descriptor of device files (outs = None); results=False returns the descriptor."""
-        return self._decode_float("decode_device_float", self.lib.fpng_amd_decode_batch_device_planar_float, True, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
+        return self._decode_float(True, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
 
     def decode_batch_float(self, pngs, outs=None, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
         """fpng_amd_decode_batch_planar_float: decode_device_float() for files in host memory (bytes)."""
-        return self._decode_float("decode_batch_float", self.lib.fpng_amd_decode_batch_planar_float, False, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
+        return self._decode_float(False, pngs, outs, order, bottom_up, mean, std, scale, bias, results)
 
     @staticmethod
     def make_decode_batch_crop(pngs, crops, outs, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
@@ -1973,71 +1989,32 @@ class Encoder:
         views of ONE dtype, described by dest_layout_float() with the constants of make_decode_batch_float().  Element (c, j, i) is
         what the full call writes at (c, y + j, x + i).  A crop that leaves its file's image is that file's status
         (DECODE_CROP_OUTSIDE), found by the call; pixels_cap is the view's own span in bytes."""
+        who = "make_decode_batch_crop"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
-            raise ValueError(f"make_decode_batch_crop: {n} files, {len(crops)} crops, {len(outs)} destinations")
-        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"make_decode_batch_crop: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        is_u8 = dtypes == {torch.uint8}
-        fmt = None
-        if is_u8:
-            if any(v is not None for v in (mean, std, scale, bias)):
-                raise ValueError("make_decode_batch_crop: mean / std / scale / bias go with float destinations, not uint8 ones")
-        else:
-            sc, bi = _float_constants("make_decode_batch_crop", normalize_constants, mean, std, scale, bias)
-            fmt = _lib.FloatFormat()
-            for k in range(4):
-                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+            raise ValueError(f"{who}: {n} files, {len(crops)} crops, {len(outs)} destinations")
+        is_u8, fmt = _dest_format(who, outs, mean, std, scale, bias)
+        orders, ups = _per_file(who, n, order, "plane orders"), _per_file(who, n, bottom_up, "bottom_up flags")
         arr = (_lib.PngPlanarIn * n)()
         carr = (_lib.Crop * n)()
         res = (_lib.DecodeResult * n)()
-        keep = []
-        for i, (p, t) in enumerate(zip(pngs, outs)):
-            if is_u8:
-                ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
-            else:
-                ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
-            x, y, w, h = (int(v) for v in crops[i])
-            if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
-                raise ValueError(f"make_decode_batch_crop: crop {tuple(crops[i])} of file {i} (four values of 32 bits, not negative)")
-            c, th, tw = t.shape
-            if (th, tw) != (h, w):
-                raise ValueError(f"make_decode_batch_crop: destination {i} is {tw} x {th}, its crop {w} x {h}")
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError("make_decode_batch_crop: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            carr[i].x, carr[i].y, carr[i].w, carr[i].h = x, y, w, h
-            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
-            arr[i].pixels_cap = (c - 1) * abs(pp) + (h - 1) * abs(rp) + w * t.element_size()  # (the view's own spans, in bytes)
-        return DecodeBatchCrop(list(pngs), list(outs), arr, res, device_data, keep, carr, fmt)
+        device_data, keep = _file_records(who, pngs, arr)
+        _planar_dests(arr, outs, orders, ups, is_u8, fmt)
+        for i, t in enumerate(outs):
+            c = _crop_record(f"{who}: file {i}", crops[i], carr[i])
+            if (t.shape[1], t.shape[2]) != (c.h, c.w):
+                raise ValueError(f"{who}: destination {i} is {t.shape[2]} x {t.shape[1]}, its crop {c.w} x {c.h}")
+        return DecodeBatchCrop(list(pngs), list(outs), arr, res, device_data, keep, crops=carr, fmt=fmt)
 
-    def _decode_crop(self, who, fn, device_data, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView)):
-            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_crop() makes this one's)")
-        if isinstance(pngs, DecodeBatchCrop):
-            batch = pngs
-        else:
-            if outs is None:  # (c = 3 planes of the crop's size each; files with alpha lose it)
-                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
-                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
-                outs = [torch.empty((3, int(c[3]), int(c[2])), dtype=dtype, device=f"cuda:{self.device}") for c in crops]
-            batch = self.make_decode_batch_crop(pngs, crops, outs, order, bottom_up, mean, std, scale, bias)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_crop)" if device_data else "device memory (decode_device_crop)"))
-        if not all(t.is_cuda for t in batch.outs):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        check(fn(self.h, batch.arr, batch.crops, len(batch.arr), C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
-        return batch.results() if results else batch
+    def _decode_crop(self, device_data, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results):
+        def make(who):
+            dests = outs
+            if dests is None:  # (c = 3 planes of the crop's size each; files with alpha lose it)
+                dests = [torch.empty((3, int(c[3]), int(c[2])), dtype=_alloc_dtype(who, dtype), device=f"cuda:{self.device}") for c in crops]
+            return self.make_decode_batch_crop(pngs, crops, dests, order, bottom_up, mean, std, scale, bias)
+
+        return self._run_decode(DecodeBatchCrop, device_data, pngs, make,
+                                lambda b: (_file_symbol("planar_crop", device_data), [b.arr, b.crops, len(b.arr), _fmt_ref(b), b.res]), results)
 
     def decode_device_crop(self, pngs, crops=None, outs=None, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None,
                            results=True):
@@ -2046,14 +2023,12 @@ class Encoder:
         (status, the caller's view or None, channels_in_file) -- without the full decode and the t[:, y:y+h, x:x+w].contiguous()
         copy behind it.  outs=None allocates (3, h, w) tensors of `dtype` (default torch.uint8).  pngs may be a
         make_decode_batch_crop() descriptor of device files (crops = outs = None); results=False returns the descriptor."""
-        return self._decode_crop("decode_device_crop", self.lib.fpng_amd_decode_batch_device_planar_crop, True, pngs, crops, outs, dtype, order, bottom_up,
-                                 mean, std, scale, bias, results)
+        return self._decode_crop(True, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     def decode_batch_crop(self, pngs, crops=None, outs=None, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None,
                           results=True):
         """fpng_amd_decode_batch_planar_crop: decode_device_crop() for files in host memory (bytes)."""
-        return self._decode_crop("decode_batch_crop", self.lib.fpng_amd_decode_batch_planar_crop, False, pngs, crops, outs, dtype, order, bottom_up,
-                                 mean, std, scale, bias, results)
+        return self._decode_crop(False, pngs, crops, outs, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     @staticmethod
     def make_decode_batch_resize(pngs, crops, outs, mirror=False, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
@@ -2063,81 +2038,39 @@ class Encoder:
         float16 / bfloat16 of ONE dtype with the constants of make_decode_batch_float(); mirror: one bool, or one per file.  Each
         crop is resized to its view's size by Pillow's 8-bit antialiased bilinear rule, mirrored where
         asked, and written once.  The call refuses (FpngAmdError) an empty crop and one of more than 32 x its output size in w or h."""
+        who = "make_decode_batch_resize"
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
-            raise ValueError(f"make_decode_batch_resize: {n} files, {len(crops)} crops, {len(outs)} destinations")
-        mirrors = [bool(mirror)] * n if isinstance(mirror, (bool, int, np.bool_)) else [bool(m) for m in mirror]
-        if len(mirrors) != n:
-            raise ValueError(f"make_decode_batch_resize: {n} files, {len(mirrors)} mirror flags")
-        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"make_decode_batch_resize: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        is_u8 = dtypes == {torch.uint8}
-        fmt = None
-        if is_u8:
-            if any(v is not None for v in (mean, std, scale, bias)):
-                raise ValueError("make_decode_batch_resize: mean / std / scale / bias go with float destinations, not uint8 ones")
-        else:
-            sc, bi = _float_constants("make_decode_batch_resize", normalize_constants, mean, std, scale, bias)
-            fmt = _lib.FloatFormat()
-            for k in range(4):
-                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+            raise ValueError(f"{who}: {n} files, {len(crops)} crops, {len(outs)} destinations")
+        mirrors = _per_file(who, n, mirror, "mirror flags")
+        is_u8, fmt = _dest_format(who, outs, mean, std, scale, bias)
+        orders, ups = _per_file(who, n, order, "plane orders"), _per_file(who, n, bottom_up, "bottom_up flags")
         arr = (_lib.PngPlanarIn * n)()
         carr = (_lib.Crop * n)()
         sarr = (_lib.Resize * n)()
         res = (_lib.DecodeResult * n)()
-        keep = []
-        for i, (p, t) in enumerate(zip(pngs, outs)):
-            if is_u8:
-                ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
-            else:
-                ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
-            x, y, w, h = (int(v) for v in crops[i])
-            if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
-                raise ValueError(f"make_decode_batch_resize: crop {tuple(crops[i])} of file {i} (four values of 32 bits, not negative)")
-            c, oh, ow = t.shape
-            if oh < 1 or ow < 1:
-                raise ValueError(f"make_decode_batch_resize: destination {i} is {ow} x {oh}")
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError("make_decode_batch_resize: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            carr[i].x, carr[i].y, carr[i].w, carr[i].h = x, y, w, h
+        device_data, keep = _file_records(who, pngs, arr)
+        _planar_dests(arr, outs, orders, ups, is_u8, fmt)
+        for i, t in enumerate(outs):
+            _crop_record(f"{who}: file {i}", crops[i], carr[i])
+            _, oh, ow = t.shape
             sarr[i].out_w, sarr[i].out_h, sarr[i].flags, sarr[i].reserved = ow, oh, (RESIZE_MIRROR if mirrors[i] else 0), 0
-            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
-            arr[i].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
-        return DecodeBatchResize(list(pngs), list(outs), arr, res, device_data, keep, carr, sarr, fmt)
+        return DecodeBatchResize(list(pngs), list(outs), arr, res, device_data, keep, crops=carr, sizes=sarr, fmt=fmt)
 
-    def _decode_resize(self, who, fn, device_data, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResizeView, DecodeBatchMultiView)):
-            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize() makes this one's)")
-        if isinstance(pngs, DecodeBatchResize):
-            batch = pngs
-        else:
+    def _decode_resize(self, device_data, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+        def make(who):
+            dests = outs
             if crops is None:
                 raise ValueError(f"{who}: crops, an (x, y, w, h) per file")
-            if outs is None:  # (c = 3 planes of the output size each; files with alpha lose it)
+            if dests is None:  # (c = 3 planes of the output size each; files with alpha lose it)
                 if size is None:
                     raise ValueError(f"{who}: outs, or size=(out_h, out_w) to allocate them")
-                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
-                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
                 oh, ow = (int(v) for v in size)
-                outs = list(torch.empty((len(pngs), 3, oh, ow), dtype=dtype, device=f"cuda:{self.device}"))
-            batch = self.make_decode_batch_resize(pngs, crops, outs, mirror, order, bottom_up, mean, std, scale, bias)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_resize)" if device_data else "device memory (decode_device_resize)"))
-        if not all(t.is_cuda for t in batch.outs):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        check(fn(self.h, batch.arr, batch.crops, batch.sizes, len(batch.arr), C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
-        return batch.results() if results else batch
+                dests = list(torch.empty((len(pngs), 3, oh, ow), dtype=_alloc_dtype(who, dtype), device=f"cuda:{self.device}"))
+            return self.make_decode_batch_resize(pngs, crops, dests, mirror, order, bottom_up, mean, std, scale, bias)
+
+        return self._run_decode(DecodeBatchResize, device_data, pngs, make,
+                                lambda b: (_file_symbol("planar_resize", device_data), [b.arr, b.crops, b.sizes, len(b.arr), _fmt_ref(b), b.res]), results)
 
     def decode_device_resize(self, pngs, crops=None, outs=None, size=None, mirror=False, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None,
                              scale=None, bias=None, results=True):
@@ -2147,14 +2080,12 @@ class Encoder:
         channels_in_file) -- RandomResizedCrop + RandomHorizontalFlip + Normalize without the F.interpolate, flip and normalise
         passes behind decode_device_crop().  outs=None with size=(out_h, out_w) allocates one (n, 3, out_h, out_w) tensor of `dtype`
         and returns its slices.  pngs may be a make_decode_batch_resize() descriptor of device files; results=False returns it."""
-        return self._decode_resize("decode_device_resize", self.lib.fpng_amd_decode_batch_device_planar_resize, True, pngs, crops, outs, size, mirror, dtype, order,
-                                   bottom_up, mean, std, scale, bias, results)
+        return self._decode_resize(True, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     def decode_batch_resize(self, pngs, crops=None, outs=None, size=None, mirror=False, dtype=torch.uint8, order="rgb", bottom_up=False, mean=None, std=None,
                             scale=None, bias=None, results=True):
         """fpng_amd_decode_batch_planar_resize: decode_device_resize() for files in host memory (bytes)."""
-        return self._decode_resize("decode_batch_resize", self.lib.fpng_amd_decode_batch_planar_resize, False, pngs, crops, outs, size, mirror, dtype, order,
-                                   bottom_up, mean, std, scale, bias, results)
+        return self._decode_resize(False, pngs, crops, outs, size, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     @staticmethod
     def make_decode_batch_resize_view(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
@@ -2171,95 +2102,39 @@ class Encoder:
         n = len(pngs)
         if len(crops) != n or len(outs) != n:
             raise ValueError(f"{who}: {n} files, {len(crops)} crops, {len(outs)} destinations")
-
-        def per_file(v, one, what):
-            vs = [v] * n if one(v) else list(v)
-            if len(vs) != n:
-                raise ValueError(f"{who}: {n} files, {len(vs)} {what}")
-            return vs
-
-        def is_ints(v):
-            return all(isinstance(a, (int, np.integer)) for a in v)
-
-        fulls = per_file(full, lambda v: len(v) == 2 and is_ints(v), "full sizes")
-        windows = per_file(window, lambda v: v is None or (len(v) == 4 and is_ints(v)), "windows")
-        filters = per_file(filter, lambda v: isinstance(v, (str, int, np.integer)), "filters")
-        mirrors = [bool(m) for m in per_file(mirror, lambda v: isinstance(v, (bool, int, np.bool_)), "mirror flags")]
-        dtypes = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"{who}: the destinations of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        is_u8 = dtypes == {torch.uint8}
-        fmt = None
-        if is_u8:
-            if any(v is not None for v in (mean, std, scale, bias)):
-                raise ValueError(f"{who}: mean / std / scale / bias go with float destinations, not uint8 ones")
-        else:
-            sc, bi = _float_constants(who, normalize_constants, mean, std, scale, bias)
-            fmt = _lib.FloatFormat()
-            for k in range(4):
-                fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        device_data = n > 0 and isinstance(pngs[0], torch.Tensor) and pngs[0].is_cuda
+        fulls, windows = _per_file(who, n, full, "full sizes"), _per_file(who, n, window, "windows")
+        filters, mirrors = _per_file(who, n, filter, "filters"), _per_file(who, n, mirror, "mirror flags")
+        is_u8, fmt = _dest_format(who, outs, mean, std, scale, bias)
+        orders, ups = _per_file(who, n, order, "plane orders"), _per_file(who, n, bottom_up, "bottom_up flags")
         arr = (_lib.PngPlanarIn * n)()
         carr = (_lib.Crop * n)()
         varr = (_lib.ResizeView * n)()
         res = (_lib.DecodeResult * n)()
-        keep = []
-        for i, (p, t) in enumerate(zip(pngs, outs)):
-            if is_u8:
-                ptr, rp, pp = dest_layout_planar(t, orders[i], ups[i])
-            else:
-                ptr, rp, pp, fmt.dtype = dest_layout_float(t, orders[i], ups[i])
-            x, y, w, h = (int(v) for v in crops[i])
-            if min(x, y, w, h) < 0 or max(x, y, w, h) > 0xFFFFFFFF:
-                raise ValueError(f"{who}: crop {tuple(crops[i])} of file {i} (four values of 32 bits, not negative)")
-            v = _view_record(who, fulls[i], windows[i], filters[i], mirrors[i], varr[i])
-            c, oh, ow = t.shape
-            if (oh, ow) != (v.h, v.w) or oh < 1 or ow < 1:
+        device_data, keep = _file_records(who, pngs, arr)
+        _planar_dests(arr, outs, orders, ups, is_u8, fmt)
+        for i, t in enumerate(outs):
+            _crop_record(f"{who}: file {i}", crops[i], carr[i])
+            v = _view_record(who, fulls[i], windows[i], filters[i], bool(mirrors[i]), varr[i])
+            _, oh, ow = t.shape
+            if (oh, ow) != (v.h, v.w):
                 raise ValueError(f"{who}: destination {i} is {ow} x {oh}, its window {v.w} x {v.h}")
-            if device_data:
-                if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.is_contiguous()):
-                    raise ValueError(f"{who}: device files are contiguous uint8 CUDA tensors, all of them")
-                arr[i].data, arr[i].size = (p.data_ptr() if p.numel() else None), p.numel()
-            else:
-                b = np.frombuffer(bytes(p), dtype=np.uint8)
-                keep.append(b)
-                arr[i].data, arr[i].size = (b.ctypes.data if b.size else None), b.size
-            carr[i].x, carr[i].y, carr[i].w, carr[i].h = x, y, w, h
-            arr[i].num_chans, arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = c, ptr, rp, pp
-            arr[i].pixels_cap = (c - 1) * abs(pp) + (oh - 1) * abs(rp) + ow * t.element_size()  # (the view's own spans, in bytes)
-        return DecodeBatchResizeView(list(pngs), list(outs), arr, res, device_data, keep, carr, varr, fmt)
+        return DecodeBatchResizeView(list(pngs), list(outs), arr, res, device_data, keep, crops=carr, views=varr, fmt=fmt)
 
-    def _decode_resize_view(self, who, fn, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
-        if isinstance(pngs, (DecodeBatchEx, DecodeBatchPlanar, DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchMultiView)):
-            raise ValueError(f"{who}: a descriptor of another call (make_decode_batch_resize_view() makes this one's)")
-        if isinstance(pngs, DecodeBatchResizeView):
-            batch = pngs
-        else:
+    def _decode_resize_view(self, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results):
+        def make(who):
+            dests = outs
             if crops is None or full is None:
                 raise ValueError(f"{who}: crops, an (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
-            if outs is None:  # (c = 3 planes of the window's size each; files with alpha lose it)
-                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
-                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
-                one_full = len(full) == 2 and all(isinstance(a, (int, np.integer)) for a in full)
-                one_win = window is None or (len(window) == 4 and all(isinstance(a, (int, np.integer)) for a in window))
-                if one_full and one_win:  # one size: one (n, 3, h, w) tensor and its slices
-                    ow, oh = (int(window[2]), int(window[3])) if window is not None else (int(full[0]), int(full[1]))
-                    outs = list(torch.empty((len(pngs), 3, oh, ow), dtype=dtype, device=f"cuda:{self.device}"))
+            if dests is None:  # (c = 3 planes of the window's size each; files with alpha lose it)
+                n, where = len(pngs), dict(dtype=_alloc_dtype(who, dtype), device=f"cuda:{self.device}")
+                if _VIEW_ARG["full sizes"](full) and _VIEW_ARG["windows"](window):  # one size: one (n, 3, h, w) tensor and its slices
+                    dests = list(torch.empty((n, 3, *_window_hw(full, window)), **where))
                 else:
-                    fulls = [full] * len(pngs) if one_full else list(full)
-                    wins = [window] * len(pngs) if one_win else list(window)
-                    sizes = [(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fulls, wins)]
-                    outs = [torch.empty((3, oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes]
-            batch = self.make_decode_batch_resize_view(pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + ("host memory (decode_batch_resize_view)" if device_data else "device memory (decode_device_resize_view)"))
-        if not all(t.is_cuda for t in batch.outs):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        check(fn(self.h, batch.arr, batch.crops, batch.views, len(batch.arr), C.byref(batch.fmt) if batch.fmt is not None else None, batch.res))
-        return batch.results() if results else batch
+                    dests = [torch.empty((3, *_window_hw(f_, w_)), **where) for f_, w_ in zip(_per_file(who, n, full, "full sizes"), _per_file(who, n, window, "windows"))]
+            return self.make_decode_batch_resize_view(pngs, crops, dests, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias)
+
+        return self._run_decode(DecodeBatchResizeView, device_data, pngs, make,
+                                lambda b: (_file_symbol("planar_resize_view", device_data), [b.arr, b.crops, b.views, len(b.arr), _fmt_ref(b), b.res]), results)
 
     def decode_device_resize_view(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                                   bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
@@ -2271,14 +2146,12 @@ class Encoder:
         center_crop_view().  Only the source pixels the window's taps reach are decoded (resize_view_source()).  outs=None
         allocates (3, h, w) tensors of `dtype`, one (n, 3, h, w) tensor's slices where all files share one size.  pngs may be a
         make_decode_batch_resize_view() descriptor of device files; results=False returns it."""
-        return self._decode_resize_view("decode_device_resize_view", self.lib.fpng_amd_decode_batch_device_planar_resize_view, True, pngs, crops, outs, full, window,
-                                        filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
+        return self._decode_resize_view(True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     def decode_batch_resize_view(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                                  bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True):
         """fpng_amd_decode_batch_planar_resize_view: decode_device_resize_view() for files in host memory (bytes)."""
-        return self._decode_resize_view("decode_batch_resize_view", self.lib.fpng_amd_decode_batch_planar_resize_view, False, pngs, crops, outs, full, window,
-                                        filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
+        return self._decode_resize_view(False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results)
 
     @staticmethod
     def make_decode_batch_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
@@ -2304,39 +2177,28 @@ class Encoder:
         fpng_amd_decode_batch(_device)_planar_views_alpha, with the others' records or without.  resample: None, or the views'
         RESAMPLE filters -- "nearest", "box", "hamming", "lanczos", None (the view's own filter=) or what view_resample() returns --
         nested as post's; the descriptor then goes through fpng_amd_decode_batch(_device)_planar_views_resample."""
-        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha, resample)
+        return _make_views_batch(_PLANAR_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias,
+                                 dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
 
-    def _decode_views(self, layout, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                      tone, enhance, alpha, resample=None):
-        """a views call of either layout (_ViewsLayout), for files in device or host memory"""
-        who = layout.device if device_data else layout.host
-        if isinstance(pngs, _DecodeBatchViews) and not isinstance(pngs, layout.batch_cls):
-            raise ValueError(f"{who}: a descriptor of another call ({layout.maker}() makes this one's)")
-        if isinstance(pngs, layout.batch_cls):
-            if color is not None or post is not None or warp is not None or tone is not None or enhance is not None or alpha is not None or resample is not None:
-                raise ValueError(f"{who}: a descriptor carries its own colour matrices, post, warp, tone, enhance, alpha and resample records "
-                                 f"({layout.maker}(..., color=, post=, warp=, tone=, enhance=, alpha=, resample=))")
-            batch = pngs
-        else:
+    def _decode_views(self, layout, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, stages):
+        """a views call of either layout (_ViewsLayout), for files in device or host memory; stages: as _make_views_batch's"""
+        if isinstance(pngs, layout.batch_cls) and any(v is not None for v in stages.values()):
+            raise ValueError(f"{layout.batch_cls.call(device_data)}: a descriptor carries its own records of the stages {', '.join(k for k, _, _, _ in _VIEW_STAGES)} "
+                             f"({layout.maker}(..., {', '.join(k + '=' for k, _, _, _ in _VIEW_STAGES)}))")
+
+        def make(who):
+            dests = outs
             if crops is None or full is None:
                 raise ValueError(f"{who}: crops, a list of (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
             if outs is None or any(o is None for o in outs):  # (each window's size with c = 3; files with alpha lose it)
-                if dtype is not torch.uint8 and dtype not in FLOAT_DTYPES:
-                    raise ValueError(f"{who}: dtype {dtype} (torch.uint8, float32, float16 or bfloat16)")
+                where = dict(dtype=_alloc_dtype(who, dtype), device=f"cuda:{self.device}")
                 counts = [len(c) for c in crops]
                 fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
-                sizes = [[(int(w_[3]), int(w_[2])) if w_ is not None else (int(f_[1]), int(f_[0])) for f_, w_ in zip(fs, ws)] for fs, ws in zip(fulls, windows)]
-                outs = [[torch.empty(layout.empty_shape(oh, ow), dtype=dtype, device=f"cuda:{self.device}") for oh, ow in sizes[i]] if outs is None or outs[i] is None else outs[i]
-                        for i in range(len(crops))]
-            batch = _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha, resample)
-        if batch.device_data != device_data:
-            raise ValueError(f"{who}: the files are in " + (f"host memory ({layout.host})" if device_data else f"device memory ({layout.device})"))
-        if not all(t.is_cuda for ts in batch.outs for t in ts):
-            raise ValueError(f"{who}: the destinations are CUDA tensors")
-        self._sync_stream()
-        symbol, args = views_entry(layout.name, device_data, batch)
-        check(getattr(self.lib, symbol)(self.h, *args))
-        return batch.results() if results else batch
+                dests = [[torch.empty(layout.empty_shape(*_window_hw(f_, w_)), **where) for f_, w_ in zip(fulls[i], windows[i])] if outs is None or outs[i] is None else outs[i]
+                         for i in range(len(crops))]
+            return _make_views_batch(layout, pngs, crops, dests, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, stages)
+
+        return self._run_decode(layout.batch_cls, device_data, pngs, make, lambda b: views_entry(layout.name, device_data, b), results)
 
     def decode_device_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                             bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
@@ -2378,14 +2240,14 @@ class Encoder:
         list per file of one per view -- which overrides the view's filter= in the resize:
         fpng_amd_decode_batch_device_planar_views_resample.  "nearest" is what a label map is resized with: give the mask the
         image's crops, windows, mirror flags and warp records.  A None leaves its view exactly the call's without."""
-        return self._decode_views(_PLANAR_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha, resample)
+        return self._decode_views(_PLANAR_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                                  dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
 
     def decode_batch_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                            bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
-        return self._decode_views(_PLANAR_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha, resample)
+        return self._decode_views(_PLANAR_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                                  dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
@@ -2398,7 +2260,8 @@ class Encoder:
         fpng_amd_decode_batch(_device)_hwc_views_warp), tone (then: fpng_amd_decode_batch(_device)_hwc_views_tone), enhance (then:
         fpng_amd_decode_batch(_device)_hwc_views_enhance) alpha (then: fpng_amd_decode_batch(_device)_hwc_views_alpha) and resample
         (then: fpng_amd_decode_batch(_device)_hwc_views_resample) -- is make_decode_batch_views()'s."""
-        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, color, post, warp, tone, enhance, alpha, resample)
+        return _make_views_batch(_HWC_VIEWS, pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias,
+                                 dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
 
     def decode_device_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                                 bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
@@ -2414,14 +2277,14 @@ class Encoder:
         uint8 or float.  -> list, per file, of (status, the list of the caller's views or None, channels_in_file).  outs=None (or
         None for a file) allocates contiguous (h, w, 3) tensors of `dtype`.  pngs may be a make_decode_batch_views_hwc() descriptor
         of device files; results=False returns it.  color: as decode_device_views()'s (fpng_amd_decode_batch_device_hwc_views_color)."""
-        return self._decode_views(_HWC_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha, resample)
+        return self._decode_views(_HWC_VIEWS, True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                                  dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
 
     def decode_batch_views_hwc(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None):
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
-        return self._decode_views(_HWC_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, color, post, warp,
-                                  tone, enhance, alpha, resample)
+        return self._decode_views(_HWC_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                                  dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

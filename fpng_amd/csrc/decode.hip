@@ -835,7 +835,7 @@ constexpr uint32_t kTileData = 16;    // where a row's data bytes begin in its L
 constexpr uint32_t kTilePitch = kTileData + 1024 + 8; // bytes of LDS per row: slack of eight bytes on either side of the window (decode_core.h: Out::put64)
 constexpr uint32_t kUnfBlock = 512;   // threads of dec_unfilter_kernel: all of them walk and fill matches, kDecBlock of them own a dword column
 constexpr uint32_t kRowMaskWords = 8; // a row's bitmap of marked pixels: 256 pixels
-constexpr uint32_t kMaxWalksPerRow = 64; // (a subsequence puts out 39 bytes at the very least: a window of 1024 has 28 walks at most)
+constexpr uint32_t kMaxWalksPerRow = 64; // (a subsequence puts out 42 bytes at the very least -- literals of 12 bits behind a match that reaches 17 bits in: a window of 1025 has 26 walks at most)
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef uint32_t __attribute__((aligned(1))) u32_any_t;

@@ -22,6 +22,8 @@ TESTS = [
     "tests/test_dropin_decode.py::test_flat_rows_with_a_run_at_the_first_pixel",
     "tests/test_decode_model.py::test_edited_token_streams_get_the_references_answer",
     "tests/test_decode_model.py::test_edited_token_streams_of_megapixel_images",
+    "tests/test_sync_cases_cpu.py::test_case_is_valid_and_shows_its_property",
+    "tests/test_sync_cases_cpu.py::test_batch_is_valid_and_shows_its_property",
 ]
 
 

@@ -59,12 +59,48 @@ struct HostOut {
     }
 };
 
+// what a decode did, for fpng_emul_decode_trace: records of 32-bit words, each one a tag and then its fields (tests/sync_cases.py
+// reads them).  Positions are those of the file (no z_shift), bits counted from the zlib stream's first byte.
+enum : uint32_t {
+    kTrFile = 1,  // first_bit lo, hi, end_limit lo, hi, n_sub, code bits of the end-of-block symbol
+    kTrStep = 2,  // round, block, valid threads, step, n_need, kind (kTrRedo..), n, then the n threads decoded again (numbers within the block)
+    kTrBlock = 3, // round, block, valid threads, steps, DecBlockRec::left, 1 if its phase maps were used
+    kTrEnd = 4,   // the subsequence the end-of-block symbol begins in, where the symbol ends (bits behind that subsequence's nominal first bit)
+    kTrWalks = 5, // most walks of any window (fill_tile's count, not clamped), fewest bytes of a subsequence that is neither first nor last
+};
+enum : uint32_t { kTrRedo = 0, kTrMaps = 1, kTrLeft = 2 }; // a step: decoded again (in place or gathered), phase maps, given up by round 0
+struct Trace {
+    std::vector<uint32_t> v;
+    void put(std::initializer_list<uint32_t> w) { v.insert(v.end(), w); }
+};
+
 } // namespace
+
+static int decode_impl(const uint8_t *png, uint32_t size, uint32_t desired, uint8_t *out, size_t out_cap, uint32_t *w_, uint32_t *h_, uint32_t *c_, uint32_t sub_block, uint32_t lead_in,
+                       uint32_t max_border_rounds, uint32_t *stats, Trace *tr);
 
 // status: the decoder's (0, FPNG_DECODE_* or FPNG_AMD_DECODE_UNDECIDED); stats[0] = correction rounds inside workgroups (max),
 // stats[1] = border rounds, stats[2] = subsequences, stats[3] = subsequences corrected at least once
 extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desired, uint8_t *out, size_t out_cap, uint32_t *w_, uint32_t *h_, uint32_t *c_, uint32_t sub_block,
                                 uint32_t lead_in, uint32_t /*unused*/, uint32_t max_border_rounds, uint32_t *stats)
+{
+    return decode_impl(png, size, desired, out, out_cap, w_, h_, c_, sub_block, lead_in, max_border_rounds, stats, nullptr);
+}
+// The same decode, and what it did (the records above) in trace[0 .. *trace_len): which branch of the synchronisation every block
+// took.  Returns -1010 if `trace_cap` words are too few (*trace_len: the words needed).
+extern "C" int fpng_emul_decode_trace(const uint8_t *png, uint32_t size, uint32_t desired, uint8_t *out, size_t out_cap, uint32_t *w_, uint32_t *h_, uint32_t *c_, uint32_t sub_block,
+                                      uint32_t lead_in, uint32_t max_border_rounds, uint32_t *stats, uint32_t *trace, uint32_t trace_cap, uint32_t *trace_len)
+{
+    Trace tr;
+    const int st = decode_impl(png, size, desired, out, out_cap, w_, h_, c_, sub_block, lead_in, max_border_rounds, stats, &tr);
+    *trace_len = (uint32_t)tr.v.size();
+    if (tr.v.size() > trace_cap) return -1010;
+    std::copy(tr.v.begin(), tr.v.end(), trace);
+    return st;
+}
+// (tr: where the records go; nullptr: none are kept)
+static int decode_impl(const uint8_t *png, uint32_t size, uint32_t desired, uint8_t *out, size_t out_cap, uint32_t *w_, uint32_t *h_, uint32_t *c_, uint32_t sub_block, uint32_t lead_in,
+                       uint32_t max_border_rounds, uint32_t *stats, Trace *tr)
 {
     fpng_amd_decode_result res;
     uint32_t mode = 0, idat_ofs = 0, idat_len = 0;
@@ -92,9 +128,15 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
         std::vector<uint32_t> zdw((idat_len + z_shift + 16) / 4 + 64, 0);
         memcpy((uint8_t *)zdw.data() + z_shift, zsrc, idat_len);
         const uint64_t z_bytes = (uint64_t)idat_len + z_shift;
-        first_bit += 8 * z_shift, end_limit += 8 * z_shift;
         const uint8_t *lenof = (const uint8_t *)(lut.data() + kLutEntries);
         const uint32_t n_sub = (uint32_t)((end_limit - first_bit + kSubBits - 1) / kSubBits), nb = (n_sub + sub_block - 1) / sub_block;
+        if (tr) {
+            uint32_t eob_bits = 0; // (the table's one entry kind that is neither literals nor a match: fpng_emul_tokenize)
+            for (uint32_t k = 0; k < kLutEntries && !eob_bits; k++)
+                if (lut[k] && !((lut[k] >> 26) & 3u) && !(lut[k] & kEntMatch)) eob_bits = (lut[k] >> 12) & 15u;
+            tr->put({kTrFile, (uint32_t)first_bit, (uint32_t)(first_bit >> 32), (uint32_t)end_limit, (uint32_t)(end_limit >> 32), n_sub, eob_bits});
+        }
+        first_bit += 8 * z_shift, end_limit += 8 * z_shift;
         std::vector<uint32_t> info(n_sub), bytes(n_sub), eob_rel(n_sub, 0);
         std::vector<std::vector<uint64_t>> tok(n_sub, std::vector<uint64_t>(kRecCap, 0)); // the entries the settling decode of every subsequence leaves
         struct Rec {
@@ -161,16 +203,25 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
                 inner++;
                 uint32_t n_need = 0;
                 for (uint32_t t = 0; t < nthreads; t++) n_need += want[t] != st[t].start;
+                size_t tr_n = 0; // (where the step's record counts the threads decoded again)
+                auto tr_step = [&](uint32_t kind) {
+                    if (tr) tr->put({kTrStep, round, blk, nthreads, it, n_need, kind, 0u}), tr_n = tr->v.size() - 1;
+                };
+                auto tr_thread = [&](uint32_t t) {
+                    if (tr) tr->v.push_back(t), tr->v[tr_n]++;
+                };
                 if (!round && it >= kRefixRounds) { // round 0's kernel is kept lean: the block is left to round 1
                     unsettled = 2;
+                    tr_step(kTrLeft);
                     break;
                 }
                 const bool cand_now = round && !cand_done && (it >= kRefixRounds || (cand_first && it >= 1)); // (thread 0 takes its wanted start in step 0)
+                tr_step(cand_now ? kTrMaps : kTrRedo);
                 if (!cand_now) {
                     // (the kernel gathers them into one wave from four on, else decodes them again where they are)
-                    (void)n_need;
                     for (uint32_t t = 0; t < nthreads; t++)
                         if (want[t] != st[t].start) {
+                            tr_thread(t);
                             HostRec rec = {&tok[local0 + t]};
                             sub_redo<VoteAlone>(in, lut.data(), lenof, want[t], nominal_of(t) + kSubBits, data_limit, st[t], rec, (t ^ it) & 1);
                             s_end[t] = st[t].end;
@@ -204,6 +255,7 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
                     if (srel == kPhaseUnknown) continue;
                     const uint32_t ws = nominal_of(t) + srel;
                     if (ws == st[t].start) continue;
+                    tr_thread(t);
                     HostRec rec = {&tok[local0 + t]};
                     sub_redo<VoteAlone>(in, lut.data(), lenof, ws, nominal_of(t) + kSubBits, data_limit, st[t], rec, true);
                     dirty[t] = true;
@@ -212,6 +264,7 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
                 for (uint32_t t = 0; t < nthreads; t++) s_end[t] = st[t].end;
             }
             max_inner = std::max(max_inner, inner);
+            if (tr) tr->put({kTrBlock, round, blk, nthreads, inner, unsettled, cand_done ? 1u : 0u});
             bool any_dirty = false;
             for (uint32_t t = 0; t < nthreads; t++)
                 if (dirty[t]) {
@@ -324,6 +377,7 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
             status |= 2;
         if (acc != total) status |= 2;
         const uint32_t eob_index = last_blk * sub_block + last_local;
+        if (tr && last_blk < nb) tr->put({kTrEnd, eob_index, eob_rel[eob_index]});
         // the stream must end 4 bytes (the Adler-32) before the IDAT does (eob_status() of decode.hip)
         if (last_blk < nb && ((first_bit + (uint64_t)eob_index * kSubBits + eob_rel[eob_index] + 7) >> 3) + 4 != z_bytes) status |= 2;
         if (status & (1 | 16)) return FPNG_AMD_DECODE_UNDECIDED; // (decode_api.cpp: not converged / left to the CPU decoder go first)
@@ -370,7 +424,7 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
         }
         // ---- dec_unfilter_kernel's tiles, first half: every window filled from the records of the subsequences that reach into it -- from
         //      the one it begins in to the one the next window begins in, a walk each (decode_core.h) -- then the pixels of the long matches ----
-        uint32_t err = 0;
+        uint32_t err = 0, max_walks = 0;
         bool fault = false;
         std::vector<uint8_t> tile(8 + cbw + 1 + 8);
         for (uint32_t y = 0; y < h; y++)
@@ -381,6 +435,7 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
                 if (i0 == 0xFFFFFFFFu) return -1005; // (the stream covers the image: every window begins somewhere)
                 uint32_t i1 = wi + 1 < (size_t)h * ncb ? win[wi + 1] : 0xFFFFFFFFu;
                 i1 = std::min(i1, eob_index);
+                if (i1 >= i0) max_walks = std::max(max_walks, i1 - i0 + 1u); // (decode.hip, fill_tile: cnt, before it is clamped)
                 std::fill(tile.begin(), tile.end(), (uint8_t)0xCD);
                 const uint32_t fb = cb ? 0u : 1u, npx = (wd.wlen - fb) / c;
                 std::vector<bool> marked(npx, false);
@@ -439,6 +494,11 @@ extern "C" int fpng_emul_decode(const uint8_t *png, uint32_t size, uint32_t desi
                 }
                 memcpy(filt.data() + wd.ws, tile.data() + 8, wd.wlen);
             }
+        if (tr) {
+            uint32_t min_bytes = 0xFFFFFFFFu; // (none: the file has no subsequence between its first and its last)
+            for (uint32_t i = 1; i < eob_index; i++) min_bytes = std::min(min_bytes, bytes[i]);
+            tr->put({kTrWalks, max_walks, min_bytes});
+        }
         if (fault) return -1004;
         if (err & kEmitLeaveToCpu) return FPNG_AMD_DECODE_UNDECIDED; // (decode_api.cpp: kDecStalled goes first -- a match at a row's first pixel is the CPU decoder's)
         if (err & 2) return 1;

@@ -37,4 +37,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   view_warp, view_warp_apply, affine_matrix,
                   view_tone, view_tone_lut, view_tone_apply,
                   view_enhance, view_enhance_apply, rotate_matrix, augment_op,
-                  view_alpha, view_alpha_source, view_alpha_result, view_resample, resample_weights, resample_view_source)
+                  view_alpha, view_alpha_source, view_alpha_result, view_resample, resample_weights, resample_view_source,
+                  RENDITION_FILTERS, rendition, renditions_plan, rendition_pixels)

@@ -150,6 +150,15 @@ class PackedResult(C.Structure):  # fpng_amd_packed_result: 24 bytes
 DESC_IMAGE, DESC_EX, DESC_PLANAR, DESC_PLANAR_FLOAT = 0, 1, 2, 3  # FPNG_AMD_DESC_*
 
 
+class Rendition(C.Structure):  # fpng_amd_rendition: 56 bytes, no padding
+    _fields_ = [("image", C.c_uint32), ("filter", C.c_uint32), ("box_x", C.c_uint32), ("box_y", C.c_uint32), ("box_w", C.c_uint32), ("box_h", C.c_uint32),
+                ("w", C.c_uint32), ("h", C.c_uint32), ("alpha_op", C.c_uint32), ("reserved", C.c_uint32), ("d_out", C.c_void_p), ("out_cap", C.c_size_t)]
+
+
+# FPNG_AMD_RENDITION_*: one numbering for the six filters
+RENDITION_FILTERS = {"bilinear": 0, "bicubic": 1, "nearest": 2, "box": 3, "hamming": 4, "lanczos": 5}
+
+
 class DecodeResult(C.Structure):
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels_in_file", C.c_uint32), ("status", C.c_int32)]
 
@@ -209,6 +218,9 @@ SIGNATURES = {
     "fpng_amd_encode_wait_packed": (_int, [_vp, _u64, C.POINTER(PackedResult), _u32, C.POINTER(_u64)]),
     "fpng_amd_pack_place": (_int, [C.POINTER(_u64), C.POINTER(_u32), _u32, _u32, _u32, _u64, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u64)]),
     "fpng_amd_pack_capacity": (_sz, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _u32, _u32, _u32]),
+    "fpng_amd_encode_submit_renditions": (_int, [_vp, _u32, _vp, _u32, C.POINTER(FloatFormat), C.POINTER(Rendition), _u32, _u32, C.POINTER(Pack), C.POINTER(_u64)]),
+    "fpng_amd_renditions_plan": (_int, [_u32, _vp, _u32, C.POINTER(FloatFormat), C.POINTER(Rendition), _u32, _int, C.POINTER(_u64), C.POINTER(_u64)]),
+    "fpng_amd_rendition_pixels": (_int, [_u32, _vp, _u32, C.POINTER(FloatFormat), C.POINTER(Rendition), _vp, _sz]),
     "fpng_amd_encode_wait": (_int, [_vp, _u64, C.POINTER(Result), _u32]),
     "fpng_amd_encode_query": (_int, [_vp, _u64]),
     "fpng_amd_encode_host": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(_sz)]),

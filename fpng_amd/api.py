@@ -1003,6 +1003,131 @@ def pack_place(sizes, align, lead, cap, statuses=None):
     return list(zip(off, st_out)), total.value
 
 
+# ---- renditions: resized copies of device images, encoded in one submission (fpng_amd_encode_submit_renditions) ----
+RENDITION_FILTERS = _lib.RENDITION_FILTERS  # name -> FPNG_AMD_RENDITION_*
+_RENDITION_ALPHA = {None: 0, "straight": 0, "premultiplied": _lib.ALPHA_PREMULTIPLIED}
+_DESC_KINDS = {"image": _lib.DESC_IMAGE, "ex": _lib.DESC_EX, "planar": _lib.DESC_PLANAR, "float": _lib.DESC_PLANAR_FLOAT}
+
+
+def _u32(who, what, v):
+    v = int(v)
+    if not 0 <= v <= 0xFFFFFFFF:
+        raise ValueError(f"{who}: {what} {v}")
+    return v
+
+
+def rendition(image, size, box=None, filter="bilinear", alpha=None):
+    """An fpng_amd_rendition record: image `image` (an index into the call's images) cropped to box = (x, y, w, h) (None: the whole
+    image) and resized to size = (w, h) as Pillow's img.crop(box).resize(size, filter) does -- filter: "bilinear", "bicubic",
+    "nearest", "box", "hamming" or "lanczos" (or a FPNG_AMD_RENDITION_* value).  alpha (4-channel images): None, the planes resized
+    independently, or "premultiplied", Pillow's Image.resize of an RGBA image.  What the library refuses (a box outside the image, a
+    scale beyond the filter's limit, ...) is refused by the call the record goes to."""
+    r = _lib.Rendition()
+    r.image = _u32("rendition", "image", image)
+    if isinstance(filter, str):
+        if filter not in RENDITION_FILTERS:
+            raise ValueError(f"rendition: filter {filter!r} ({', '.join(sorted(RENDITION_FILTERS))})")
+        r.filter = RENDITION_FILTERS[filter]
+    else:
+        r.filter = _u32("rendition", "filter", filter)
+    if box is not None:
+        r.box_x, r.box_y, r.box_w, r.box_h = (_u32("rendition", "box", v) for v in box)
+    r.w, r.h = (_u32("rendition", "size", v) for v in size)
+    if isinstance(alpha, str) or alpha is None:
+        if alpha not in _RENDITION_ALPHA:
+            raise ValueError(f"rendition: alpha {alpha!r} (None or 'premultiplied')")
+        r.alpha_op = _RENDITION_ALPHA[alpha]
+    else:
+        r.alpha_op = _u32("rendition", "alpha", alpha)
+    return r
+
+
+def _source_records(who, images, kind, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+    """(record array of `kind` without outputs, fpng_amd_float_format or None, [channels]) for tensors as Encoder.submit / submit_ex /
+    submit_planar / submit_float take them, from their strides and data_ptr() alone: CPU tensors work too (the host twin's)"""
+    if kind not in _DESC_KINDS:
+        raise ValueError(f"{who}: kind is one of {sorted(_DESC_KINDS)}, not {kind!r}")
+    n = len(images)
+    orders = [order] * n if isinstance(order, str) else list(order)
+    ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+    fmt = None
+    if kind == "float":
+        sc, bi = _float_constants(who, denormalize_constants, mean, std, scale, bias)
+        if len({t.dtype for t in images}) > 1:
+            raise ValueError(f"{who}: the images of one call share one dtype")
+        fmt = _lib.FloatFormat()
+        for k in range(4):
+            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
+    elif any(v is not None for v in (mean, std, scale, bias)):
+        raise ValueError(f"{who}: mean / std / scale / bias go with kind 'float'")
+    if kind == "image":
+        arr = (Image * n)()
+        for a, im in zip(arr, images):
+            if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or not im.is_contiguous():
+                raise ValueError(f"{who}: kind 'image' takes contiguous uint8 tensors shaped (h, w, c)")
+            a.d_pixels, (a.h, a.w, a.num_chans) = im.data_ptr(), im.shape
+        chans = [a.num_chans for a in arr]
+    elif kind == "ex":
+        arr = (ImageEx * n)()
+        for a, im, o, up in zip(arr, images, orders, ups):
+            a.d_pixels, a.row_pitch, a.format = source_layout(im, o, up)
+            a.w, a.h = im.shape[1], im.shape[0]
+        chans = [format_channels(a.format) for a in arr]
+    else:
+        arr = (ImagePlanar * n)()
+        for a, im, o, up in zip(arr, images, orders, ups):
+            if kind == "float":
+                a.d_pixels, a.row_pitch, a.plane_pitch, fmt.dtype = source_layout_float(im, o, up)
+            else:
+                a.d_pixels, a.row_pitch, a.plane_pitch = source_layout_planar(im, o, up)
+            a.num_chans, a.h, a.w = im.shape
+        chans = [a.num_chans for a in arr]
+    return arr, fmt, chans
+
+
+def _rendition_records(renditions):
+    arr = (_lib.Rendition * len(renditions))()
+    for i, r in enumerate(renditions):
+        if not isinstance(r, _lib.Rendition):
+            raise ValueError("renditions: a list of fpng_amd.rendition() records")
+        C.memmove(C.byref(arr, i * C.sizeof(_lib.Rendition)), C.byref(r), C.sizeof(_lib.Rendition))
+    return arr
+
+
+def _as_tensors(images):
+    images = [images] if isinstance(images, (torch.Tensor, np.ndarray)) else list(images)
+    return [torch.from_numpy(im) if isinstance(im, np.ndarray) else im for im in images]
+
+
+def renditions_plan(images, renditions, kind="image", packed=False, **layout):
+    """fpng_amd_renditions_plan: the validation of Encoder.submit_renditions() without a GPU -- raises FpngAmdError as that call would --
+    and (scratch bytes, [offset of every rendition's tight rows in the scratch]).  images: tensors as for submit_renditions (CPU
+    tensors work: only their addresses and strides are looked at); a rendition's d_out / out_cap are judged as they stand in the
+    record (packed=True: they must be unset)."""
+    images = _as_tensors(images)
+    arr, fmt, _ = _source_records("renditions_plan", images, kind, **layout)
+    rarr = _rendition_records(renditions)
+    total, offs = C.c_uint64(0), (C.c_uint64 * len(rarr))()
+    check(_lib.load().fpng_amd_renditions_plan(_DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), C.byref(fmt) if fmt is not None else None, rarr, len(rarr),
+                                               1 if packed else 0, C.byref(total), offs))
+    return total.value, list(offs)
+
+
+def rendition_pixels(images, rendition, kind="image", **layout):
+    """fpng_amd_rendition_pixels, the resize stage's host twin (no GPU; the text the kernel compiles): the (h, w, c) uint8 array of
+    R,G,B[,A] pixels whose file Encoder.submit_renditions() writes for this record.  images: CPU tensors or numpy arrays in the
+    layout of `kind` (one, or a list that the record's `image` indexes), with that kind's layout arguments."""
+    images = _as_tensors(images)
+    if any(im.is_cuda for im in images):
+        raise ValueError("rendition_pixels: host tensors (the twin runs on the CPU)")
+    arr, fmt, chans = _source_records("rendition_pixels", images, kind, **layout)
+    c = chans[rendition.image] if rendition.image < len(chans) else 4
+    out = np.empty((max(rendition.h, 1), max(rendition.w, 1), c), dtype=np.uint8)
+    check(_lib.load().fpng_amd_rendition_pixels(_DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), C.byref(fmt) if fmt is not None else None, C.byref(rendition),
+                                                out.ctypes.data, out.size))
+    return out
+
+
 class _NoOut:
     """stands where a make_batch_*() call expects an output tensor: a packed submission's descriptors carry none"""
     is_cuda = True
@@ -1742,6 +1867,63 @@ class Encoder:
         n = self.submit_packed(batch, arena, align=align, lead=lead, flags=flags)
         records, total = self.wait_packed(self.last_ticket, n)
         return arena[:total], records
+
+    def submit_renditions(self, images, renditions, kind="image", outs=None, arena=None, flags=0, align=16, lead=0, table=None, **layout):
+        """fpng_amd_encode_submit_renditions: resized copies of device images, one file per fpng_amd.rendition() record, in ONE
+        submission -- img.crop(box).resize(size, filter) as Pillow computes it, encoded as submit() encodes those pixels.  images:
+        CUDA tensors as for submit / submit_ex / submit_planar / submit_float (kind "image" | "ex" | "planar" | "float", **layout:
+        that call's order / bottom_up / mean / std / scale / bias), read where they lie.  Either outs -- one uint8 CUDA tensor of
+        >= max_encoded_size(w, h, c) bytes per rendition -- or arena (with align, lead, table as for submit_packed): the files
+        back to back in it, in rendition order.  Asynchronous; wait(last_ticket, n) for the (png_size, mode, status) records, with
+        an arena wait_packed(last_ticket, n).  Returns the number of renditions."""
+        if (outs is None) == (arena is None):
+            raise ValueError("submit_renditions: outs (one per rendition) or arena, one of the two")
+        images = list(images)
+        if not all(isinstance(im, torch.Tensor) and im.is_cuda for im in images):
+            raise ValueError("submit_renditions: images are CUDA tensors")
+        arr, fmt, _ = _source_records("submit_renditions", images, kind, **layout)
+        rarr = _rendition_records(renditions)
+        n = len(rarr)
+        pack = None
+        if outs is not None:
+            if len(outs) != n or not all(o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() for o in outs):
+                raise ValueError("submit_renditions: outs are contiguous uint8 CUDA tensors, one per rendition")
+            for r, o in zip(rarr, outs):
+                r.d_out, r.out_cap = o.data_ptr(), o.numel()
+        else:
+            if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()):
+                raise ValueError("submit_renditions: arena is a contiguous uint8 CUDA tensor")
+            pack = _lib.Pack(arena.data_ptr(), arena.numel(), align, lead, None, 0)
+            if table is not None:
+                if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= 2 * (n + 1)):
+                    raise ValueError("submit_renditions: table is a contiguous int64 CUDA tensor of 2 * (n + 1) elements")
+                pack.d_table = table.data_ptr()
+        self._sync_stream()
+        t = C.c_uint64(0)
+        check(self.lib.fpng_amd_encode_submit_renditions(self.h, _DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), C.byref(fmt) if fmt is not None else None,
+                                                         rarr, n, flags, C.byref(pack) if pack is not None else None, C.byref(t)))
+        self.last_ticket = t.value
+        self._keep[t.value] = (images, outs, arena, table)  # sources and destinations stay alive while the submission runs
+        for old in [k for k in self._keep if k + 8 <= t.value]:
+            del self._keep[old]
+        return n
+
+    def encode_renditions(self, images, renditions, kind="image", flags=0, **layout):
+        """Convenience: outputs of max_encoded_size() each, one submit_renditions(), the wait: the files as a list of bytes, in
+        rendition order."""
+        images = list(images)
+        _, _, chans = _source_records("encode_renditions", images, kind, **layout)
+        for r in renditions:
+            if r.image >= len(images):
+                raise ValueError(f"encode_renditions: rendition of image {r.image} of {len(images)}")
+        outs = [torch.empty(max_encoded_size(r.w, r.h, chans[r.image]) + 64, dtype=torch.uint8, device=images[r.image].device) for r in renditions]
+        n = self.submit_renditions(images, renditions, kind=kind, outs=outs, flags=flags, **layout)
+        pngs = []
+        for out, (size, _, status) in zip(outs, self.wait(self.last_ticket, n)):
+            if status:
+                raise FpngAmdError(status, "device reported an encode failure")
+            pngs.append(bytes(out[:size].cpu().numpy()))
+        return pngs
 
     def wait(self, ticket, n):
         """Waits for the submission `ticket` (see last_ticket) only; returns its (png_size, mode, status) records."""

@@ -4,6 +4,7 @@
 // (reference src/fpng.cpp:1662-1680), job descriptors, scratch management, kernel launches on one
 // stream.  There is no CPU implementation of the encode path in this library.
 #include "encoder.h"
+#include "encode_resize.h"
 #include "lanes.h"
 #include "quantize.h"
 
@@ -393,6 +394,7 @@ void fpng_amd_encoder_destroy(fpng_amd_encoder *e)
         sl.jobs2.release();
         sl.results.release();
         sl.offsets.release();
+        sl.rend.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.in) (void)hipEventDestroy(sl.in);
         if (sl.walked) (void)hipEventDestroy(sl.walked);
@@ -512,6 +514,76 @@ constexpr SrcFormat kSrcFormats[FPNG_AMD_SRC_COUNT] = {
 
 static_assert(sizeof(fpng_amd_image_planar) == 56 && offsetof(fpng_amd_image_planar, w) == 24 && offsetof(fpng_amd_image_planar, d_out) == 40, "fpng_amd_image_planar layout");
 
+// ---- one image record judged by its kind's own rules: what prepare_jobs() and the renditions' rendition_sources() both call, so
+// that "every rule of the kind's own submit holds" for the renditions by construction ----
+// fmt of the float kind: scale and bias into fq, the element's bytes into *elem
+int check_float_format(const fpng_amd_float_format *ffmt, FloatQuant &fq, int64_t *elem)
+{
+    if (ffmt->dtype > FPNG_AMD_BF16) return fail(FPNG_AMD_ERR_INVALID_ARG, "dtype is FPNG_AMD_F32, _F16 or _BF16");
+    if (ffmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt->reserved must be 0");
+    for (int k = 0; k < 4; k++) {
+        if (!std::isfinite(ffmt->scale[k]) || !std::isfinite(ffmt->bias[k])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
+        fq.scale[k] = ffmt->scale[k], fq.bias[k] = ffmt->bias[k];
+    }
+    *elem = ffmt->dtype == FPNG_AMD_F32 ? 4 : 2;
+    return FPNG_AMD_OK;
+}
+
+// fpng_amd_image_planar (elem: bytes of an element, 1 for uint8 planes): the record as a fpng_amd_image plus its two pitches
+int check_planar_source(const fpng_amd_image_planar &x, int64_t elem, fpng_amd_image &im, int64_t &pitch, int64_t &plane_pitch)
+{
+    int rc;
+    if (x.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "reserved must be 0");
+    if ((rc = check_dims(x.w, x.h, x.num_chans))) return rc;
+    const int64_t row_bytes = (int64_t)x.w * elem;
+    if (elem > 1 && (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (uint64_t)(elem - 1)))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
+    pitch = x.row_pitch ? x.row_pitch : row_bytes;
+    const int64_t apitch = pitch < 0 ? -pitch : pitch;
+    if (apitch < row_bytes) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
+    // (h, w < 2^24 and |row_pitch| < 2^63 / 2^24 keep the span in 64 bits)
+    if (apitch > (INT64_MAX >> 26)) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| too large");
+    const int64_t span = (int64_t)(x.h - 1) * apitch + row_bytes; // bytes from a plane's lowest row to the end of its highest
+    plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)x.h * apitch;
+    if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
+    if ((plane_pitch < 0 ? -plane_pitch : plane_pitch) < span)
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
+    im.d_pixels = x.d_pixels;
+    im.w = x.w, im.h = x.h, im.num_chans = x.num_chans;
+    im.d_out = x.d_out;
+    im.out_cap = x.out_cap;
+    return FPNG_AMD_OK;
+}
+
+// fpng_amd_image_ex: the record as a fpng_amd_image plus its format and pitch
+int check_ex_source(const fpng_amd_image_ex &x, fpng_amd_image &im, const SrcFormat *&fmt, int64_t &pitch)
+{
+    int rc;
+    if (x.format >= FPNG_AMD_SRC_COUNT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown source format");
+    fmt = &kSrcFormats[x.format];
+    if ((rc = check_dims(x.w, x.h, fmt->chans))) return rc;
+    const int64_t packed = (int64_t)x.w * fmt->bytes;
+    pitch = x.row_pitch ? x.row_pitch : packed;
+    if ((pitch < 0 ? -pitch : pitch) < packed) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w * source bytes per pixel");
+    if (fmt->bytes == 4 && (((uintptr_t)x.d_pixels & 3) || (pitch & 3)))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "4-byte source pixels need d_pixels and row_pitch to be multiples of 4");
+    im.d_pixels = x.d_pixels;
+    im.w = x.w, im.h = x.h, im.num_chans = fmt->chans;
+    im.d_out = x.d_out;
+    im.out_cap = x.out_cap;
+    return FPNG_AMD_OK;
+}
+
+// The pixels of a record of any kind, once it is a fpng_amd_image (the outputs are the caller's to judge)
+int check_source_pixels(const fpng_amd_image &im, bool planar)
+{
+    int rc;
+    if ((rc = check_dims(im.w, im.h, im.num_chans))) return rc;
+    if (!im.d_pixels) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
+    if (!planar && im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
+    return FPNG_AMD_OK;
+}
+
 // Fills slot.jobs[0..n) for whole-image jobs and sizes the scratch buffers.  Only `slot` (which is free) and
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
 // ex_images (fpng_amd_encode_submit_ex) or pl_images (fpng_amd_encode_submit_planar) replaces `images` when it is given.
@@ -535,63 +607,21 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     sub.planar = pl_images != nullptr;
     int64_t elem = 1; // bytes of a planar source's element
     if (ffmt) {
-        if (ffmt->dtype > FPNG_AMD_BF16) return fail(FPNG_AMD_ERR_INVALID_ARG, "dtype is FPNG_AMD_F32, _F16 or _BF16");
-        if (ffmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt->reserved must be 0");
-        for (int k = 0; k < 4; k++) {
-            if (!std::isfinite(ffmt->scale[k]) || !std::isfinite(ffmt->bias[k])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
-            sub.fq.scale[k] = ffmt->scale[k], sub.fq.bias[k] = ffmt->bias[k];
-        }
+        if ((rc = check_float_format(ffmt, sub.fq, &elem))) return rc;
         sub.planar_float = true;
         sub.float_dtype = ffmt->dtype;
-        elem = ffmt->dtype == FPNG_AMD_F32 ? 4 : 2;
     }
     for (uint32_t i = 0; i < n; i++) {
         fpng_amd_image im_of_ex;
         const SrcFormat *fmt = nullptr;
         int64_t pitch = 0, plane_pitch = 0;
-        if (pl_images) {
-            const fpng_amd_image_planar &x = pl_images[i];
-            if (x.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "reserved must be 0");
-            if ((rc = check_dims(x.w, x.h, x.num_chans))) return rc;
-            const int64_t row_bytes = (int64_t)x.w * elem;
-            if (elem > 1 && (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (uint64_t)(elem - 1)))
-                return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
-            pitch = x.row_pitch ? x.row_pitch : row_bytes;
-            const int64_t apitch = pitch < 0 ? -pitch : pitch;
-            if (apitch < row_bytes) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
-            // (h, w < 2^24 and |row_pitch| < 2^63 / 2^24 keep the span in 64 bits)
-            if (apitch > (INT64_MAX >> 26)) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| too large");
-            const int64_t span = (int64_t)(x.h - 1) * apitch + row_bytes; // bytes from a plane's lowest row to the end of its highest
-            plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)x.h * apitch;
-            if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
-            if ((plane_pitch < 0 ? -plane_pitch : plane_pitch) < span)
-                return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
-            im_of_ex.d_pixels = x.d_pixels;
-            im_of_ex.w = x.w, im_of_ex.h = x.h, im_of_ex.num_chans = x.num_chans;
-            im_of_ex.d_out = x.d_out;
-            im_of_ex.out_cap = x.out_cap;
-        }
-        if (ex_images) {
-            const fpng_amd_image_ex &x = ex_images[i];
-            if (x.format >= FPNG_AMD_SRC_COUNT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown source format");
-            fmt = &kSrcFormats[x.format];
-            if ((rc = check_dims(x.w, x.h, fmt->chans))) return rc;
-            const int64_t packed = (int64_t)x.w * fmt->bytes;
-            pitch = x.row_pitch ? x.row_pitch : packed;
-            if ((pitch < 0 ? -pitch : pitch) < packed) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w * source bytes per pixel");
-            if (fmt->bytes == 4 && (((uintptr_t)x.d_pixels & 3) || (pitch & 3)))
-                return fail(FPNG_AMD_ERR_INVALID_ARG, "4-byte source pixels need d_pixels and row_pitch to be multiples of 4");
-            im_of_ex.d_pixels = x.d_pixels;
-            im_of_ex.w = x.w, im_of_ex.h = x.h, im_of_ex.num_chans = fmt->chans;
-            im_of_ex.d_out = x.d_out;
-            im_of_ex.out_cap = x.out_cap;
-        }
+        if (pl_images && (rc = check_planar_source(pl_images[i], elem, im_of_ex, pitch, plane_pitch))) return rc;
+        if (ex_images && (rc = check_ex_source(ex_images[i], im_of_ex, fmt, pitch))) return rc;
         const fpng_amd_image &im = (ex_images || pl_images) ? im_of_ex : images[i];
-        if ((rc = check_dims(im.w, im.h, im.num_chans))) return rc;
+        if ((rc = check_source_pixels(im, pl_images != nullptr))) return rc;
         if (packed && (im.d_out || im.out_cap)) return fail(FPNG_AMD_ERR_INVALID_ARG, "packed submission: d_out must be NULL and out_cap 0");
-        if (!im.d_pixels || (!packed && !im.d_out)) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
-        if (((uintptr_t)im.d_out & 15) || (!pl_images && im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)))
-            return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
+        if (!packed && !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
+        if ((uintptr_t)im.d_out & 15) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
         if (!packed && im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.num_chans))
             return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
         Job &j = slot.jobs.p[i];
@@ -653,8 +683,171 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     return FPNG_AMD_OK;
 }
 
+// ---- renditions (fpng_amd_encode_submit_renditions, include/fpng_amd.h; the resize stage: encode_resize.h) ----
+// An image record of any of the four kinds, judged by its kind's own rules, as the resize stage reads it
+struct RenditionSource {
+    uintptr_t base; // channel data of pixel (0, 0): EncResize::src of the whole image
+    int64_t pitch, plane_pitch;
+    uint32_t layout, sel, chans, w, h;
+    uint32_t px_bytes; // from a pixel to the next one of its row (planar: the element)
+};
+
+// What fpng_amd_renditions_plan answers and what the submit call stages: the records with their pointers still open (dst_off:
+// where a rendition's rows begin in the scratch; nearest_at: where its indices begin in `nearest`, -1 without)
+struct RenditionPlan {
+    std::vector<EncResize> recs;
+    std::vector<uint64_t> dst_off, pre;
+    std::vector<int64_t> nearest_at;
+    std::vector<uint32_t> nearest;
+    FloatQuant fq = {};
+    uint64_t scratch_bytes = 0;
+    uint32_t lds = 0;
+};
+
+static_assert(sizeof(fpng_amd_rendition) == 56 && offsetof(fpng_amd_rendition, box_x) == 8 && offsetof(fpng_amd_rendition, w) == 24 && offsetof(fpng_amd_rendition, alpha_op) == 32 &&
+                  offsetof(fpng_amd_rendition, d_out) == 40 && offsetof(fpng_amd_rendition, out_cap) == 48, "fpng_amd_rendition layout");
+static_assert(FPNG_AMD_RENDITION_BILINEAR == kResizeBilinear && FPNG_AMD_RENDITION_BICUBIC == kResizeBicubic && FPNG_AMD_RENDITION_NEAREST == kResizeNearest &&
+                  FPNG_AMD_RENDITION_BOX == kResizeBox && FPNG_AMD_RENDITION_HAMMING == kResizeHamming && FPNG_AMD_RENDITION_LANCZOS == kResizeLanczos &&
+                  FPNG_AMD_RENDITION_FILTERS == kResizeAllFilters, "the kernel's filters (resize.h)");
+
+enum { kRenditionOuts = 0, kRenditionPacked = 1, kRenditionNoOuts = 2 }; // how plan_renditions judges d_out and out_cap
+
+int rendition_sources(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *ffmt, std::vector<RenditionSource> &out, FloatQuant &fq)
+{
+    if (desc_kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
+    if ((desc_kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (ffmt != nullptr)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
+    if (!images || !n_images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    int64_t elem = 1; // bytes of a planar source's element
+    int rc;
+    if (ffmt && (rc = check_float_format(ffmt, fq, &elem))) return rc;
+    out.resize(n_images);
+    for (uint32_t i = 0; i < n_images; i++) {
+        RenditionSource &s = out[i];
+        fpng_amd_image im_of;
+        const SrcFormat *f = nullptr;
+        s.pitch = s.plane_pitch = 0;
+        const bool planar = desc_kind >= FPNG_AMD_DESC_PLANAR;
+        if (planar && (rc = check_planar_source(((const fpng_amd_image_planar *)images)[i], elem, im_of, s.pitch, s.plane_pitch))) return rc;
+        if (desc_kind == FPNG_AMD_DESC_EX && (rc = check_ex_source(((const fpng_amd_image_ex *)images)[i], im_of, f, s.pitch))) return rc;
+        const fpng_amd_image &im = desc_kind == FPNG_AMD_DESC_IMAGE ? ((const fpng_amd_image *)images)[i] : im_of;
+        if ((rc = check_source_pixels(im, planar))) return rc;
+        if (im.d_out || im.out_cap) return fail(FPNG_AMD_ERR_INVALID_ARG, "renditions: an image record's d_out must be NULL and its out_cap 0 (the files belong to the renditions)");
+        if (desc_kind == FPNG_AMD_DESC_IMAGE) f = &kSrcFormats[im.num_chans == 3 ? FPNG_AMD_SRC_RGB : FPNG_AMD_SRC_RGBA], s.pitch = (int64_t)im.w * im.num_chans;
+        s.w = im.w, s.h = im.h, s.chans = im.num_chans;
+        s.sel = f ? f->sel : 0, s.px_bytes = f ? f->bytes : (uint32_t)elem;
+        s.layout = f ? (f->bytes == 3 ? kEncSrcBytes3 : kEncSrcBytes4) : ffmt ? kEncSrcFloat + ffmt->dtype : kEncSrcPlanar;
+        s.base = (uintptr_t)im.d_pixels;
+    }
+    return FPNG_AMD_OK;
+}
+
+int plan_renditions(const std::vector<RenditionSource> &src, const fpng_amd_rendition *renditions, uint32_t n, int outs, RenditionPlan &plan)
+{
+    if (!renditions || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty renditions");
+    if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "more than 65535 renditions");
+    plan.recs.resize(n), plan.dst_off.resize(n), plan.nearest_at.assign(n, -1), plan.pre.assign((size_t)n + 1, 0);
+    uint64_t cursor = 0;
+    int rc;
+    for (uint32_t k = 0; k < n; k++) {
+        const fpng_amd_rendition &r = renditions[k];
+        if (r.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_rendition::reserved must be 0");
+        if (r.image >= src.size()) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_rendition::image >= n_images");
+        if (r.filter >= kResizeAllFilters) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_rendition::filter (FPNG_AMD_RENDITION_*)");
+        if (r.alpha_op != 0 && r.alpha_op != FPNG_AMD_ALPHA_PREMULTIPLIED) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_rendition::alpha_op is 0 or FPNG_AMD_ALPHA_PREMULTIPLIED");
+        const RenditionSource &s = src[r.image];
+        uint32_t bw = r.box_w, bh = r.box_h;
+        if (!(r.box_x | r.box_y | r.box_w | r.box_h)) bw = s.w, bh = s.h; // the whole image
+        else if (!bw || !bh) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty box (all four fields 0 mean the whole image)");
+        if ((uint64_t)r.box_x + bw > s.w || (uint64_t)r.box_y + bh > s.h) return fail(FPNG_AMD_ERR_INVALID_ARG, "the box reaches outside the image");
+        if ((rc = check_dims(r.w, r.h, s.chans))) return rc;
+        if (!resize_scale_ok(bw, r.w, r.filter) || !resize_scale_ok(bh, r.h, r.filter))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "the scale is beyond the filter's limit: box * max(support, 1) <= 32 * size per axis");
+        if (outs == kRenditionPacked && (r.d_out || r.out_cap)) return fail(FPNG_AMD_ERR_INVALID_ARG, "packed submission: d_out must be NULL and out_cap 0");
+        if (outs == kRenditionOuts) {
+            if (!r.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
+            if ((uintptr_t)r.d_out & 15) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned");
+            if (r.out_cap < fpng_amd_max_encoded_size(r.w, r.h, s.chans)) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
+        }
+        EncResize &e = plan.recs[k];
+        std::memset(&e, 0, sizeof e);
+        e.src = (const uint8_t *)(uintptr_t)((int64_t)s.base + (int64_t)r.box_y * s.pitch + (int64_t)r.box_x * s.px_bytes);
+        e.pitch = s.pitch, e.plane_pitch = s.plane_pitch;
+        e.layout = s.layout, e.sel = s.sel, e.chans = s.chans, e.filter = r.filter;
+        e.in_w = bw, e.in_h = bh, e.w = r.w, e.h = r.h;
+        // Pillow's Image.resize: NEAREST does not premultiply, and size == box is self.copy() before any conversion
+        e.premul = s.chans == 4 && r.alpha_op == FPNG_AMD_ALPHA_PREMULTIPLIED && r.filter != kResizeNearest && !(r.w == bw && r.h == bh);
+        e.taps_x = resize_max_taps(bw, r.w, r.filter), e.taps_y = resize_max_taps(bh, r.h, r.filter), e.rows = resize_tile_rows(bh, r.h, r.filter);
+        e.fused = enc_resize_fused(e.layout, e.taps_x, e.taps_y, e.rows, e.chans);
+        plan.lds = std::max(plan.lds, enc_resize_tile_lds(e.taps_x, e.taps_y, e.rows, e.chans, e.fused != 0));
+        if (r.filter == kResizeNearest) {
+            const size_t at = plan.nearest.size();
+            plan.nearest_at[k] = (int64_t)at;
+            plan.nearest.resize(at + r.w + r.h);
+            if (!resize_nearest_indices(bw, r.w, 0, r.w, plan.nearest.data() + at) || !resize_nearest_indices(bh, r.h, 0, r.h, plan.nearest.data() + at + r.w))
+                return fail(FPNG_AMD_ERR_UNSUPPORTED, "a NEAREST index outside the box");
+        }
+        plan.dst_off[k] = enc_resize_place(&cursor, r.w, r.h, s.chans);
+        plan.pre[k + 1] = plan.pre[k] + resize_tiles(r.w, r.h);
+    }
+    if (plan.lds > kEncResizeMaxLds) return fail(FPNG_AMD_ERR_UNSUPPORTED, "a rendition's tile needs more than 64 KiB of LDS");
+    plan.scratch_bytes = enc_resize_scratch_bytes(cursor);
+    return FPNG_AMD_OK;
+}
+
+// What submit() runs in front of the chain for fpng_amd_encode_submit_renditions: the plan, and the fpng_amd_image records of the
+// renditions' rows in the lane's scratch that the chain then encodes
+struct RenditionStage {
+    RenditionPlan plan;
+    const fpng_amd_rendition *renditions = nullptr;
+    uint32_t n = 0;
+    std::vector<fpng_amd_image> images;
+    size_t at_pre = 0, at_fq = 0, at_nearest = 0, rec_bytes = 0; // d_rend: EncResize[n], pre[n + 1], FloatQuant, the NEAREST indices
+};
+
+// Sizes the lane's scratch (growing it while the lane's previous submission runs is safe, as for every DeviceBuf: giving a block
+// up waits for the device), closes the records' pointers and leaves them in the slot's pinned memory
+int stage_renditions(fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, RenditionStage &st)
+{
+    const uint32_t n = st.n;
+    st.at_pre = (size_t)n * sizeof(EncResize);
+    st.at_fq = st.at_pre + ((size_t)n + 1) * sizeof(uint64_t);
+    st.at_nearest = st.at_fq + sizeof(FloatQuant);
+    st.rec_bytes = st.at_nearest + st.plan.nearest.size() * sizeof(uint32_t);
+    int rc;
+    if ((rc = sc.d_resized.ensure(st.plan.scratch_bytes)) || (rc = sc.d_rend.ensure(st.rec_bytes)) || (rc = slot.rend.ensure(st.rec_bytes))) return rc;
+    st.images.resize(n);
+    for (uint32_t k = 0; k < n; k++) {
+        EncResize &e = st.plan.recs[k];
+        e.dst = sc.d_resized.p + st.plan.dst_off[k];
+        e.nearest = st.plan.nearest_at[k] < 0 ? nullptr : (const uint32_t *)(sc.d_rend.p + st.at_nearest) + st.plan.nearest_at[k];
+        fpng_amd_image &im = st.images[k];
+        im.d_pixels = e.dst;
+        im.w = e.w, im.h = e.h, im.num_chans = e.chans;
+        im.d_out = st.renditions[k].d_out;
+        im.out_cap = st.renditions[k].out_cap;
+    }
+    std::memcpy(slot.rend.p, st.plan.recs.data(), st.at_pre);
+    std::memcpy(slot.rend.p + st.at_pre, st.plan.pre.data(), st.at_fq - st.at_pre);
+    std::memcpy(slot.rend.p + st.at_fq, &st.plan.fq, sizeof(FloatQuant));
+    if (!st.plan.nearest.empty()) std::memcpy(slot.rend.p + st.at_nearest, st.plan.nearest.data(), st.rec_bytes - st.at_nearest);
+    return FPNG_AMD_OK;
+}
+
+int launch_renditions(hipStream_t s, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const RenditionStage &st)
+{
+    HIP_TRY(hipMemcpyAsync(sc.d_rend.p, slot.rend.p, st.rec_bytes, hipMemcpyHostToDevice, s));
+    if (!launch_enc_resize(s, (const EncResize *)sc.d_rend.p, (const uint64_t *)(sc.d_rend.p + st.at_pre), st.plan.pre.data(), st.n, st.plan.lds,
+                           (const FloatQuant *)(sc.d_rend.p + st.at_fq)))
+        return fail(FPNG_AMD_ERR_UNSUPPORTED, "the renditions' resize could not be launched");
+    HIP_TRY(hipGetLastError());
+    return FPNG_AMD_OK;
+}
+
+// stage (fpng_amd_encode_submit_renditions): the renditions' resize runs on the lane's stream in front of the chain, and the chain's
+// images are the stage's -- the plain path over rows in the lane's scratch
 int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out,
-           const fpng_amd_image_planar *pl_images = nullptr, const fpng_amd_float_format *ffmt = nullptr, const fpng_amd_pack *pack = nullptr)
+           const fpng_amd_image_planar *pl_images = nullptr, const fpng_amd_float_format *ffmt = nullptr, const fpng_amd_pack *pack = nullptr,
+           RenditionStage *stage = nullptr)
 {
     if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
     HIP_TRY(hipSetDevice(e->device));
@@ -679,8 +872,12 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     hipStream_t s = e->lane_stream[lane];
     fpng_amd_encoder::Scratch &sc = e->sc[lane];
     Submission sub;
-    int rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub, ffmt, pack != nullptr);
-    if (rc) return rc;
+    int rc;
+    if (stage) {
+        if ((rc = stage_renditions(slot, sc, *stage))) return rc;
+        images = stage->images.data(), n = stage->n;
+    }
+    if ((rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub, ffmt, pack != nullptr))) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
     const bool two_pass = (flags & FPNG_AMD_ENCODE_SLOWER) && !force_stored;
@@ -722,6 +919,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
         (void)hipGetLastError();
         HIP_TRY(hipStreamWaitEvent(s, sc.last_done, 0)); // the scratch set's previous user
     }
+    // (in front of the first phase mark: the resize is no phase of fpng_amd_encoder_last_phase_ms)
+    if (stage && (rc = launch_renditions(s, slot, sc, *stage))) return rc;
     // (Measured and dropped, profiles/r03_latency.txt: letting one- and two-frame submissions read their job records straight from
     // the slot's pinned host memory instead of uploading them -- the upload is a blit kernel + a dispatch gap, ~7 us -- costs
     // 7 us MORE per chain: every kernel's first touch of the record goes over PCIe.)
@@ -872,11 +1071,9 @@ int fpng_amd_encode_submit_planar_float(fpng_amd_encoder *e, const fpng_amd_imag
     return submit(e, nullptr, nullptr, n, flags, ticket, images, fmt);
 }
 
-int fpng_amd_encode_submit_packed(fpng_amd_encoder *e, uint32_t desc_kind, const void *images, uint32_t n, const fpng_amd_float_format *fmt,
-                                  uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket)
+// what a packed submission asks of its fpng_amd_pack (fpng_amd_encode_submit_packed, fpng_amd_encode_submit_renditions)
+static int check_pack(const fpng_amd_pack *pack)
 {
-    // everything about the arena is checked here, before the encoder is looked at: nothing is launched, no ticket handed out
-    if (desc_kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
     if (!pack || !pack->d_arena) return fail(FPNG_AMD_ERR_INVALID_ARG, "null pack or d_arena");
     const uint32_t align = pack_align_of(pack->align);
     if (!align) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->align must be 0 or a power of two in 16 .. 65536");
@@ -884,6 +1081,90 @@ int fpng_amd_encode_submit_packed(fpng_amd_encoder *e, uint32_t desc_kind, const
     if ((uintptr_t)pack->d_arena & (align - 1)) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->d_arena must be a multiple of pack->align");
     if ((uintptr_t)pack->d_table & 7) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->d_table must be 8-byte aligned");
     if (pack->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "pack->reserved must be 0");
+    return FPNG_AMD_OK;
+}
+
+int fpng_amd_encode_submit_renditions(fpng_amd_encoder *e, uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt,
+                                      const fpng_amd_rendition *renditions, uint32_t n_renditions, uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket)
+{
+    // everything is judged here, before the encoder is looked at: nothing is launched, no ticket handed out
+    int rc;
+    if (pack && (rc = check_pack(pack))) return rc;
+    std::vector<RenditionSource> src;
+    RenditionStage st;
+    if ((rc = rendition_sources(desc_kind, images, n_images, fmt, src, st.plan.fq)) ||
+        (rc = plan_renditions(src, renditions, n_renditions, pack ? kRenditionPacked : kRenditionOuts, st.plan)))
+        return rc;
+    st.renditions = renditions, st.n = n_renditions;
+    return submit(e, nullptr, nullptr, 0, flags, ticket, nullptr, nullptr, pack, &st);
+}
+
+int fpng_amd_renditions_plan(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt, const fpng_amd_rendition *renditions,
+                             uint32_t n_renditions, int packed, uint64_t *scratch_bytes, uint64_t *offsets)
+{
+    std::vector<RenditionSource> src;
+    RenditionPlan plan;
+    int rc;
+    if ((rc = rendition_sources(desc_kind, images, n_images, fmt, src, plan.fq)) ||
+        (rc = plan_renditions(src, renditions, n_renditions, packed ? kRenditionPacked : kRenditionOuts, plan)))
+        return rc;
+    if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+    if (offsets) std::copy(plan.dst_off.begin(), plan.dst_off.end(), offsets);
+    return FPNG_AMD_OK;
+}
+
+// The resize stage on the host: what enc_resize_kernel computes, tile by tile, here for the whole rendition at once -- the same
+// weights (resample_tile_weights), the same sums through the same accessor (enc_row_sum), the same clamps and the same U
+int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt, const fpng_amd_rendition *rendition,
+                              uint8_t *out, size_t out_cap)
+{
+    std::vector<RenditionSource> src;
+    RenditionPlan plan;
+    int rc;
+    if (!out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null out");
+    if ((rc = rendition_sources(desc_kind, images, n_images, fmt, src, plan.fq)) || (rc = plan_renditions(src, rendition, rendition ? 1u : 0u, kRenditionNoOuts, plan))) return rc;
+    EncResize r = plan.recs[0];
+    r.nearest = plan.nearest.empty() ? nullptr : plan.nearest.data();
+    const size_t w = r.w, h = r.h, C = r.chans;
+    if (out_cap < w * h * C) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < w * h * channels");
+    std::vector<uint32_t> fx(w), cx(w), fy(h), cy(h);
+    std::vector<int32_t> Kx(w * r.taps_x), Ky(h * r.taps_y);
+    for (uint32_t o = 0; o < w; o++) cx[o] = resample_tile_weights(r.filter, r.in_w, r.w, o, r.nearest, o, &fx[o], Kx.data() + (size_t)o * r.taps_x, 1, r.taps_x);
+    for (uint32_t q = 0; q < h; q++) cy[q] = resample_tile_weights(r.filter, r.in_h, r.h, q, r.nearest ? r.nearest + r.w : nullptr, q, &fy[q], Ky.data() + (size_t)q * r.taps_y, 1, r.taps_y);
+    const size_t plane = (size_t)r.in_h * w; // the horizontal pass's bytes of one channel
+    std::vector<uint8_t> T(plane * C);
+    std::vector<uint32_t> px(w * h, 0u);
+    for (uint32_t y = 0; y < r.in_h; y++)
+        for (uint32_t o = 0; o < w; o++) {
+            uint8_t *const t = T.data() + (size_t)y * w + o;
+            const int32_t *const K = Kx.data() + (size_t)o * r.taps_x;
+            if (r.fused) { // (the kernel's choice, so that the twin runs the text the kernel runs for this record)
+                const EncSums4 s = enc_row_sums4(r, y, fx[o], cx[o], K, 1);
+                t[0] = (uint8_t)resize_clip8(s.c0), t[plane] = (uint8_t)resize_clip8(s.c1), t[2 * plane] = (uint8_t)resize_clip8(s.c2);
+                if (C == 4) t[3 * plane] = (uint8_t)resize_clip8(s.c3);
+            } else
+                for (uint32_t c = 0; c < C; c++) t[c * plane] = (uint8_t)resize_clip8(enc_row_sum(r, plan.fq, c, y, fx[o], cx[o], K, 1));
+        }
+    for (uint32_t c = 0; c < C; c++)
+        for (uint32_t q = 0; q < h; q++)
+            for (uint32_t o = 0; o < w; o++) {
+                int32_t sum = 1 << (kResizeBits - 1);
+                for (uint32_t t = 0; t < cy[q]; t++) sum += (int32_t)T[c * plane + (size_t)(fy[q] + t) * w + o] * Ky[(size_t)q * r.taps_y + t];
+                px[(size_t)q * w + o] |= resize_clip8(sum) << (8 * c);
+            }
+    for (size_t i = 0; i < w * h; i++) {
+        const uint32_t v = r.premul ? enc_unmul_pixel(px[i]) : px[i];
+        for (uint32_t c = 0; c < C; c++) out[i * C + c] = (uint8_t)(v >> (8 * c));
+    }
+    return FPNG_AMD_OK;
+}
+
+int fpng_amd_encode_submit_packed(fpng_amd_encoder *e, uint32_t desc_kind, const void *images, uint32_t n, const fpng_amd_float_format *fmt,
+                                  uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket)
+{
+    // everything about the arena is checked here, before the encoder is looked at: nothing is launched, no ticket handed out
+    if (desc_kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
+    if (int rc = check_pack(pack)) return rc;
     if ((desc_kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (fmt != nullptr))
         return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
     if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");

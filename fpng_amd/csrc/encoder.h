@@ -137,11 +137,14 @@ struct fpng_amd_encoder {
         size_t hist_zero = 0; // leading counters of d_hist that are zero when the lane's stream gets there (the table builder re-zeroes what it read)
         DeviceBuf<TokenTable> d_dyn;
         DeviceBuf<uint32_t> d_local; // rows pipeline: the rows' local streams (Job::local_base / local_stride)
+        // fpng_amd_encode_submit_renditions: the renditions' tight rows, which the chain reads as its images, and the resize
+        // stage's records (EncResize, tile prefix sums, float constants, NEAREST indices).  Guarded by last_done like d_local
+        DeviceBuf<uint8_t> d_resized, d_rend;
         hipEvent_t last_done = nullptr; // `done` event (owned by a slot) of the last submission that used this set
         void release()
         {
             d_jobs.release(), d_rows.release(), d_row_off.release(), d_states.release(), d_results.release();
-            d_partials.release(), d_hist.release(), d_dyn.release(), d_local.release();
+            d_partials.release(), d_hist.release(), d_dyn.release(), d_local.release(), d_resized.release(), d_rend.release();
         }
     };
     static constexpr int kLanes = 8; // most lanes an encoder can have; n_lanes of them exist and take submissions in turn
@@ -165,6 +168,7 @@ struct fpng_amd_encoder {
         PinnedBuf<Job> jobs, jobs2; // jobs2: the second upload of 2-pass (tables patched)
         PinnedBuf<Result> results;
         PinnedBuf<uint64_t> offsets; // packed submissions: n offsets, total, files placed -- written by pack_place_kernel
+        PinnedBuf<uint8_t> rend;     // rendition submissions: the resize stage's records on their way to Scratch::d_rend
         bool packed = false;
         hipEvent_t in = nullptr;     // recorded on the caller's stream: the inputs are ready
         hipEvent_t walked = nullptr; // recorded after the row walk

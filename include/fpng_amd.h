@@ -1361,6 +1361,78 @@ int fpng_amd_pack_place(const uint64_t *png_sizes, const uint32_t *statuses, uin
 /* The arena size with which nothing can be refused: the cursor after placing n files of fpng_amd_max_encoded_size() each
  * (0 for an invalid align or lead). */
 size_t fpng_amd_pack_capacity(const uint32_t *w, const uint32_t *h, const uint32_t *num_chans, uint32_t n, uint32_t align, uint32_t lead);
+/* ---- RENDITIONS: resized copies of device images, encoded in one submission -- a thumbnail next to a frame, Resize(256) copies
+ *      into a packed shard, a float CHW output as a full file plus a preview -- without a Pillow pass on the host.
+ *      THE RULE.  A rendition of an image is img.crop(box).resize((w, h), filter) as Pillow computes it (reducing_gap unset;
+ *      torchvision's resized_crop), and its file is byte for byte the one fpng_encode_image_to_memory() writes for those pixels, in
+ *      compressed, 2-pass and stored modes alike.
+ *      - Weights: per axis the rule of csrc/resize.h (section "decode ... resize" above) with `in` = the BOX's size, so taps never
+ *        leave the box.  (This is not Pillow's box= argument of resize(), whose taps may leave the box.)
+ *      - Filters, ONE numbering for the six (FPNG_AMD_RENDITION_*; it is neither FPNG_AMD_FILTER_* nor FPNG_AMD_RESAMPLE_*, which
+ *        split them over two records): bilinear, bicubic, nearest, box, Hamming, Lanczos.  Limits per axis: in * max(s_f, 1) <=
+ *        32 * out (s_f: 1, 2, 1, 0.5, 1, 3).  Nearest uses an index table that the host builds (the running sum of Pillow's affine path).
+ *      - 4-channel files, alpha_op 0: the four planes are resized independently.  FPNG_AMD_ALPHA_PREMULTIPLIED: Pillow's
+ *        Image.resize of an RGBA image -- colour bytes M(v, a) on load, U(R'_c, R'_3) on store (fpng_amd_view_alpha above) -- except
+ *        with the nearest filter, where Pillow does not premultiply and the planes stay straight, and for a rendition whose size
+ *        equals its box, which is a plain copy (Pillow returns self.copy() before any conversion, and U(M(v, a), a) is not v).
+ *        FPNG_AMD_ALPHA_COMPOSITE is not offered here.
+ *      - 3-channel files (RGB, BGR, *X / X* sources, 3 planes): alpha_op is checked and then ignored.
+ *      - Float planar sources are quantised per element (fpng_amd_encode_submit_planar_float's rule) first; the rendition is the
+ *        resize of those bytes.
+ *      THE CALL.  desc_kind, images (n_images records) and fmt are those of fpng_amd_encode_submit_packed, and every rule of the
+ *      kind's own submit call holds for the records -- except that their d_out must be NULL and their out_cap 0: the files belong to
+ *      the renditions.  pack: NULL (every rendition has d_out, 16-byte aligned, and out_cap >= fpng_amd_max_encoded_size(w, h,
+ *      the image's channels)) or an fpng_amd_pack under fpng_amd_encode_submit_packed's rules (every rendition's d_out NULL, out_cap 0;
+ *      the files are placed in rendition order).  One call may mix images, channel counts, filters and sizes, and an image may have
+ *      several renditions or none.  The ticket carries n_renditions result records in rendition order and works with
+ *      fpng_amd_encode_wait / _query / _finish / _join and, with a pack, fpng_amd_encode_wait_packed.
+ *      The source is only read, and only bytes of the box's own pixels (4-byte interleaved sources: the aligned dword that is the
+ *      pixel): pitch padding, X bytes, a fourth plane behind a 3-channel planar image and pixels outside the box influence nothing.
+ *      REFUSALS, each FPNG_AMD_ERR_INVALID_ARG (out_cap too small: FPNG_AMD_ERR_BUFFER_TOO_SMALL) with nothing launched, no ticket
+ *      handed out and the encoder as it was: an unknown desc_kind, filter or alpha_op (anything but 0 and
+ *      FPNG_AMD_ALPHA_PREMULTIPLIED); image >= n_images; a box that is partly zero (box_w or box_h 0 while another field is not),
+ *      or reaches outside the image; w or h that fpng_amd_encode_submit refuses; a scale beyond the filter's limit; reserved != 0;
+ *      n_renditions 0 or above 65535; d_out set together with a pack, or missing without one; and whatever the kind's own submit
+ *      or fpng_amd_encode_submit_packed refuses about the images, fmt and pack.
+ *      HOW.  A kernel of its own (csrc/encode_resize.hip) resamples every rendition from the source as it lies into tight
+ *      R,G,B[,A] rows in the lane's scratch, on the lane's stream in front of the chain, and the unchanged chain of
+ *      fpng_amd_encode_submit encodes those rows.  The resize is not a phase of fpng_amd_encoder_last_phase_ms: it runs in front of
+ *      the first phase mark and is left unmarked (FPNG_AMD_NUM_PHASES stays what it is).
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encode_submit_renditions with dlsym. ---- */
+#define FPNG_AMD_RENDITION_BILINEAR 0u
+#define FPNG_AMD_RENDITION_BICUBIC 1u
+#define FPNG_AMD_RENDITION_NEAREST 2u
+#define FPNG_AMD_RENDITION_BOX 3u
+#define FPNG_AMD_RENDITION_HAMMING 4u
+#define FPNG_AMD_RENDITION_LANCZOS 5u
+#define FPNG_AMD_RENDITION_FILTERS 6u
+typedef struct fpng_amd_rendition {
+    uint32_t image;                      /* index into the call's images */
+    uint32_t filter;                     /* FPNG_AMD_RENDITION_* */
+    uint32_t box_x, box_y, box_w, box_h; /* in pixels of the image, top-down; all 0 = the whole image */
+    uint32_t w, h;                       /* the file's size */
+    uint32_t alpha_op, reserved;         /* 0 or FPNG_AMD_ALPHA_PREMULTIPLIED; 0 */
+    uint8_t *d_out;                      /* DEVICE, 16-byte aligned, receives the whole .png file; NULL with a pack */
+    size_t out_cap;                      /* >= fpng_amd_max_encoded_size(w, h, the image's channels); 0 with a pack */
+} fpng_amd_rendition; /* 56 bytes, no padding */
+int fpng_amd_encode_submit_renditions(fpng_amd_encoder *enc, uint32_t desc_kind, const void *images, uint32_t n_images,
+                                      const fpng_amd_float_format *fmt, const fpng_amd_rendition *renditions, uint32_t n_renditions,
+                                      uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket);
+/* The validation of fpng_amd_encode_submit_renditions on the HOST, without a GPU (the submit call runs this text): the same
+ * return codes for the same records (packed: nonzero = judge the renditions as under a pack, d_out NULL and out_cap 0; the pack
+ * itself is not looked at here).  On success scratch_bytes (may be NULL) is what the resize stage needs of the lane's scratch and
+ * offsets[k] (may be NULL; n_renditions words) where rendition k's tight rows (w * channels bytes each) begin in it: every offset a
+ * multiple of 16, no two renditions overlapping, room behind the last one for the row walk's aligned reads. */
+int fpng_amd_renditions_plan(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt,
+                             const fpng_amd_rendition *renditions, uint32_t n_renditions, int packed, uint64_t *scratch_bytes,
+                             uint64_t *offsets);
+/* The resize stage's HOST twin, over the text the kernel compiles (csrc/encode_resize.h: source accessor, passes, alpha rule):
+ * `images` are records as above whose d_pixels are HOST pointers to a copy of the source in its own layout (pitches, formats and
+ * float constants as they are); out receives rendition->w * rendition->h * channels tight R,G,B[,A] bytes (out_cap: its room, else
+ * FPNG_AMD_ERR_BUFFER_TOO_SMALL).  The rendition's d_out and out_cap are not looked at; everything else is validated as by the
+ * submit call.  For tests and for callers that want to predict a file's bytes. */
+int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt,
+                              const fpng_amd_rendition *rendition, uint8_t *out, size_t out_cap);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

@@ -1042,19 +1042,30 @@ def rendition(image, size, box=None, filter="bilinear", alpha=None):
     return r
 
 
-def _source_records(who, images, kind, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
-    """(record array of `kind` without outputs, fpng_amd_float_format or None, [channels]) for tensors as Encoder.submit / submit_ex /
-    submit_planar / submit_float take them, from their strides and data_ptr() alone: CPU tensors work too (the host twin's)"""
+def _per_image(who, n, v, one, what):
+    """order / bottom_up of an encode call: one value for all images, or a sequence with one per image"""
+    vs = [v] * n if isinstance(v, one) else list(v)
+    if len(vs) != n:
+        raise ValueError(f"{who}: {n} images, {len(vs)} {what}")
+    return vs
+
+
+def _source_records(who, images, kind, outs=None, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
+    """The image records of every encode call: (record array of `kind`, fpng_amd_float_format or None) for tensors as
+    Encoder.submit / submit_ex / submit_planar / submit_float take them, from their strides and data_ptr() alone -- CPU tensors work
+    too (the host twin's).  outs: an output tensor per image, or None for records without outputs (packed calls, renditions)."""
     if kind not in _DESC_KINDS:
         raise ValueError(f"{who}: kind is one of {sorted(_DESC_KINDS)}, not {kind!r}")
     n = len(images)
-    orders = [order] * n if isinstance(order, str) else list(order)
-    ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
+    orders, ups = _per_image(who, n, order, str, "orders"), _per_image(who, n, bottom_up, bool, "bottom_up flags")
+    if outs is not None and len(outs) != n:
+        raise ValueError(f"{who}: {n} images, {len(outs)} outs")
     fmt = None
     if kind == "float":
         sc, bi = _float_constants(who, denormalize_constants, mean, std, scale, bias)
-        if len({t.dtype for t in images}) > 1:
-            raise ValueError(f"{who}: the images of one call share one dtype")
+        dtypes = {t.dtype for t in images if isinstance(t, torch.Tensor)}
+        if len(dtypes) > 1:
+            raise ValueError(f"{who}: the images of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
         fmt = _lib.FloatFormat()
         for k in range(4):
             fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
@@ -1066,13 +1077,11 @@ def _source_records(who, images, kind, order="rgb", bottom_up=False, mean=None, 
             if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or not im.is_contiguous():
                 raise ValueError(f"{who}: kind 'image' takes contiguous uint8 tensors shaped (h, w, c)")
             a.d_pixels, (a.h, a.w, a.num_chans) = im.data_ptr(), im.shape
-        chans = [a.num_chans for a in arr]
     elif kind == "ex":
         arr = (ImageEx * n)()
         for a, im, o, up in zip(arr, images, orders, ups):
             a.d_pixels, a.row_pitch, a.format = source_layout(im, o, up)
             a.w, a.h = im.shape[1], im.shape[0]
-        chans = [format_channels(a.format) for a in arr]
     else:
         arr = (ImagePlanar * n)()
         for a, im, o, up in zip(arr, images, orders, ups):
@@ -1081,8 +1090,14 @@ def _source_records(who, images, kind, order="rgb", bottom_up=False, mean=None, 
             else:
                 a.d_pixels, a.row_pitch, a.plane_pitch = source_layout_planar(im, o, up)
             a.num_chans, a.h, a.w = im.shape
-        chans = [a.num_chans for a in arr]
-    return arr, fmt, chans
+    for a, out in zip(arr, outs or ()):
+        a.d_out, a.out_cap = out.data_ptr(), out.numel()
+    return arr, fmt
+
+
+def _record_channels(kind, arr):
+    """PNG channels of every record of _source_records(.., kind, ..)"""
+    return [format_channels(a.format) if kind == "ex" else a.num_chans for a in arr]
 
 
 def _rendition_records(renditions):
@@ -1105,7 +1120,7 @@ def renditions_plan(images, renditions, kind="image", packed=False, **layout):
     tensors work: only their addresses and strides are looked at); a rendition's d_out / out_cap are judged as they stand in the
     record (packed=True: they must be unset)."""
     images = _as_tensors(images)
-    arr, fmt, _ = _source_records("renditions_plan", images, kind, **layout)
+    arr, fmt = _source_records("renditions_plan", images, kind, **layout)
     rarr = _rendition_records(renditions)
     total, offs = C.c_uint64(0), (C.c_uint64 * len(rarr))()
     check(_lib.load().fpng_amd_renditions_plan(_DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), C.byref(fmt) if fmt is not None else None, rarr, len(rarr),
@@ -1120,8 +1135,8 @@ def rendition_pixels(images, rendition, kind="image", **layout):
     images = _as_tensors(images)
     if any(im.is_cuda for im in images):
         raise ValueError("rendition_pixels: host tensors (the twin runs on the CPU)")
-    arr, fmt, chans = _source_records("rendition_pixels", images, kind, **layout)
-    c = chans[rendition.image] if rendition.image < len(chans) else 4
+    arr, fmt = _source_records("rendition_pixels", images, kind, **layout)
+    c = _record_channels(kind, arr)[rendition.image] if rendition.image < len(arr) else 4
     out = np.empty((max(rendition.h, 1), max(rendition.w, 1), c), dtype=np.uint8)
     check(_lib.load().fpng_amd_rendition_pixels(_DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), C.byref(fmt) if fmt is not None else None, C.byref(rendition),
                                                 out.ctypes.data, out.size))
@@ -1129,16 +1144,42 @@ def rendition_pixels(images, rendition, kind="image", **layout):
 
 
 class _NoOut:
-    """stands where a make_batch_*() call expects an output tensor: a packed submission's descriptors carry none"""
+    """stands in a make_batch_packed() descriptor where the other makers' hold an output tensor: a packed submission has none"""
     is_cuda = True
 
-    @staticmethod
-    def data_ptr():
-        return None
 
-    @staticmethod
-    def numel():
-        return 0
+def _need_cuda(who, tensors, what):
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+        raise ValueError(f"{who}: {what} are CUDA tensors")
+
+
+def _own_batch(who, maker, batch, record, size=3):
+    """the prebuilt descriptor of a submit call is its own maker's: anything else is refused before the library is touched"""
+    if not (isinstance(batch, tuple) and len(batch) == size and isinstance(batch[2], C.Array) and batch[2]._type_ is record):
+        raise ValueError(f"{who}: without outs, images is a {maker}() descriptor")
+    return batch
+
+
+def _pack_record(who, arena, align, lead, table, n):
+    """the fpng_amd_pack of a packed call of n files: its arena and, if given, its table, checked"""
+    if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()):
+        raise ValueError(f"{who}: arena is a contiguous uint8 CUDA tensor")
+    pack = _lib.Pack(arena.data_ptr(), arena.numel(), align, lead, None, 0)
+    if table is not None:
+        if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= 2 * (n + 1)):
+            raise ValueError(f"{who}: table is a contiguous int64 CUDA tensor of 2 * (n + 1) elements")
+        pack.d_table = table.data_ptr()
+    return pack
+
+
+def _files(outs, records):
+    """the files of a finished submission as bytes: outs[i][:png_size], or FpngAmdError for the first record with a status"""
+    pngs = []
+    for out, (size, _, status) in zip(outs, records):
+        if status:
+            raise FpngAmdError(status, "device reported an encode failure")
+        pngs.append(bytes(out[:size].cpu().numpy()))
+    return pngs
 
 
 def layout_1pass(num_chans):
@@ -1649,101 +1690,63 @@ class Encoder:
     def make_batch(images, outs):
         """Descriptor array (fpng_amd_image[n]) for a list of image / output tensors.  Build it once when the
         same buffers are encoded repeatedly (a capture pipeline): submit() then costs one C call."""
-        n = len(images)
-        arr = (Image * n)()
-        for i, (im, out) in enumerate(zip(images, outs)):
-            assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous() and im.dim() == 3
-            h, w, c = im.shape
-            arr[i].d_pixels = im.data_ptr()
-            arr[i].w, arr[i].h, arr[i].num_chans = w, h, c
-            arr[i].d_out = out.data_ptr()
-            arr[i].out_cap = out.numel()
-        return (images, outs, arr)
+        _need_cuda("make_batch", images, "images")
+        return (images, outs, _source_records("make_batch", images, "image", outs)[0])
+
+    def _submit(self, call, n, keep):
+        """What every submit method ends in: call(ticket) is its one C call; `keep` -- the descriptor, and whatever else the GPU
+        reads or writes -- stays alive while the submission can be in flight.  Returns n."""
+        self._sync_stream()
+        t = C.c_uint64(0)
+        check(call(C.byref(t)))
+        self.last_ticket = t.value
+        # a submission 8 tickets back has finished (its slot was reused)
+        self._keep[t.value] = keep
+        for old in [k for k in self._keep if k + 8 <= t.value]:
+            del self._keep[old]
+        return n
 
     def submit(self, images, outs=None, flags=0):
         """images: list of uint8 CUDA tensors shaped (h, w, c), contiguous, and outs: list of uint8 CUDA
         tensors with >= max_encoded_size bytes -- or images = a make_batch() descriptor and outs = None.
         Asynchronous; call finish() for the sizes."""
-        batch = images if outs is None else self.make_batch(images, outs)
+        batch = _own_batch("submit", "make_batch", images, Image) if outs is None else self.make_batch(images, outs)
         n = len(batch[2])
-        self._sync_stream()
-        t = C.c_uint64(0)
-        check(self.lib.fpng_amd_encode_submit(self.h, batch[2], n, flags, C.byref(t)))
-        self.last_ticket = t.value
-        # buffers of submissions in flight stay alive; a submission 8 tickets back has finished (its slot was reused)
-        self._keep[t.value] = batch
-        for old in [k for k in self._keep if k + 8 <= t.value]:
-            del self._keep[old]
-        return n
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit(self.h, batch[2], n, flags, t), n, batch)
 
     @staticmethod
     def make_batch_ex(images, outs, order="rgb", bottom_up=False):
         """Descriptor array (fpng_amd_image_ex[n]) for submit_ex(): uint8 CUDA tensor VIEWS (h, w, c) in place -- crops, BGR(A),
         [..., :3] of RGBA, bottom-up buffers -- described by source_layout(view, order, bottom_up) (order / bottom_up: one value, or
         one per image).  outs: uint8 CUDA tensors of >= max_encoded_size(w, h, c) bytes."""
-        n = len(images)
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        arr = (ImageEx * n)()
-        for i, (im, out) in enumerate(zip(images, outs)):
-            assert im.is_cuda and out.is_cuda
-            ptr, rp, fmt = source_layout(im, orders[i], ups[i])
-            arr[i].d_pixels, arr[i].row_pitch, arr[i].format = ptr, rp, fmt
-            arr[i].w, arr[i].h = im.shape[1], im.shape[0]
-            arr[i].d_out = out.data_ptr()
-            arr[i].out_cap = out.numel()
-        return (images, outs, arr)
+        _need_cuda("make_batch_ex", images, "images")
+        _need_cuda("make_batch_ex", outs, "outs")
+        return (images, outs, _source_records("make_batch_ex", images, "ex", outs, order, bottom_up)[0])
 
     def submit_ex(self, images, outs=None, flags=0, order="rgb", bottom_up=False):
         """submit() for images in other layouts (fpng_amd_encode_submit_ex): images = tensor views as for make_batch_ex() with outs,
         or a make_batch_ex() descriptor and outs = None.  The files are the ones submit() writes for the same pixels repacked as
         R,G,B[,A].  Asynchronous; wait(last_ticket, n) / finish() for the sizes."""
-        batch = images if outs is None else self.make_batch_ex(images, outs, order, bottom_up)
+        batch = _own_batch("submit_ex", "make_batch_ex", images, ImageEx) if outs is None else self.make_batch_ex(images, outs, order, bottom_up)
         n = len(batch[2])
-        self._sync_stream()
-        t = C.c_uint64(0)
-        check(self.lib.fpng_amd_encode_submit_ex(self.h, batch[2], n, flags, C.byref(t)))
-        self.last_ticket = t.value
-        self._keep[t.value] = batch
-        for old in [k for k in self._keep if k + 8 <= t.value]:
-            del self._keep[old]
-        return n
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit_ex(self.h, batch[2], n, flags, t), n, batch)
 
     @staticmethod
     def make_batch_planar(images, outs, order="rgb", bottom_up=False):
         """Descriptor array (fpng_amd_image_planar[n]) for submit_planar(): uint8 tensor VIEWS shaped (c, h, w) -- channels first, as
         torch holds images -- encoded where they lie, described by source_layout_planar(view, order, bottom_up) (order / bottom_up: one
         value, or one per image).  list(nchw_batch) is a valid `images`.  outs: uint8 tensors of >= max_encoded_size(w, h, c) bytes."""
-        n = len(images)
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        arr = (ImagePlanar * n)()
-        for i, (im, out) in enumerate(zip(images, outs)):
-            ptr, rp, pp = source_layout_planar(im, orders[i], ups[i])
-            arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = ptr, rp, pp
-            arr[i].num_chans, arr[i].h, arr[i].w = im.shape
-            arr[i].reserved = 0
-            arr[i].d_out = out.data_ptr()
-            arr[i].out_cap = out.numel()
-        return (images, outs, arr)
+        return (images, outs, _source_records("make_batch_planar", images, "planar", outs, order, bottom_up)[0])
 
     def submit_planar(self, images, outs=None, flags=0, order="rgb", bottom_up=False):
         """submit() for planar (c, h, w) images (fpng_amd_encode_submit_planar): images = CUDA tensor views as for make_batch_planar()
         with outs, or a make_batch_planar() descriptor and outs = None.  The files are the ones submit() writes for the same pixels
         interleaved as R,G,B[,A] -- without the permute(1, 2, 0).contiguous() copy.  Asynchronous; wait(last_ticket, n) / finish()
         for the sizes."""
-        batch = images if outs is None else self.make_batch_planar(images, outs, order, bottom_up)
-        if not all(im.is_cuda and out.is_cuda for im, out in zip(batch[0], batch[1])):
-            raise ValueError("submit_planar: images and outs are CUDA tensors")
+        batch = _own_batch("submit_planar", "make_batch_planar", images, ImagePlanar) if outs is None else self.make_batch_planar(images, outs, order, bottom_up)
+        _need_cuda("submit_planar", [*batch[0], *batch[1]], "images and outs")
         n = len(batch[2])
-        self._sync_stream()
-        t = C.c_uint64(0)
-        check(self.lib.fpng_amd_encode_submit_planar(self.h, batch[2], n, flags, C.byref(t)))
-        self.last_ticket = t.value
-        self._keep[t.value] = batch
-        for old in [k for k in self._keep if k + 8 <= t.value]:
-            del self._keep[old]
-        return n
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit_planar(self.h, batch[2], n, flags, t), n, batch)
 
     @staticmethod
     def make_batch_float(images, outs, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
@@ -1753,66 +1756,33 @@ class Encoder:
         (R, G, B, A, whatever the planes' order in memory) is rint(fmaf(x, scale[c], bias[c])) clamped to [0, 255], NaN giving 0: give
         mean and std (denormalize_constants(): (x * std + mean) * 255), or scale and bias (up to four values each, padded with 255
         and 0), or neither for plain [0, 1] values.  list(nchw_batch) is a valid `images`."""
-        sc, bi = _float_constants("make_batch_float", denormalize_constants, mean, std, scale, bias)
-        n = len(images)
-        orders = [order] * n if isinstance(order, str) else list(order)
-        ups = [bottom_up] * n if isinstance(bottom_up, bool) else list(bottom_up)
-        dtypes = {t.dtype for t in images if isinstance(t, torch.Tensor)}
-        if len(dtypes) > 1:
-            raise ValueError(f"make_batch_float: the images of one call share one dtype, not {sorted(str(d) for d in dtypes)}")
-        arr = (ImagePlanar * n)()
-        fmt = _lib.FloatFormat()
-        for i, (im, out) in enumerate(zip(images, outs)):
-            ptr, rp, pp, fmt.dtype = source_layout_float(im, orders[i], ups[i])
-            arr[i].d_pixels, arr[i].row_pitch, arr[i].plane_pitch = ptr, rp, pp
-            arr[i].num_chans, arr[i].h, arr[i].w = im.shape
-            arr[i].reserved = 0
-            arr[i].d_out = out.data_ptr()
-            arr[i].out_cap = out.numel()
-        for k in range(4):
-            fmt.scale[k], fmt.bias[k] = float(sc[k]), float(bi[k])
-        return (images, outs, arr, fmt)
+        return (images, outs) + _source_records("make_batch_float", images, "float", outs, order, bottom_up, mean, std, scale, bias)
 
     def submit_float(self, images, outs=None, flags=0, order="rgb", bottom_up=False, mean=None, std=None, scale=None, bias=None):
         """submit_planar() for float (c, h, w) images (fpng_amd_encode_submit_planar_float): images = CUDA tensor views as for
         make_batch_float() with outs, or a make_batch_float() descriptor and outs = None.  The files are the ones submit_planar()
         writes for x.mul(scale).add(bias).round().clamp(0, 255).to(torch.uint8) -- without those passes and the uint8 image between
         them.  Asynchronous; wait(last_ticket, n) / finish() for the sizes."""
-        batch = images if outs is None else self.make_batch_float(images, outs, order, bottom_up, mean, std, scale, bias)
-        if not all(im.is_cuda and out.is_cuda for im, out in zip(batch[0], batch[1])):
-            raise ValueError("submit_float: images and outs are CUDA tensors")
+        if outs is None:
+            batch = _own_batch("submit_float", "make_batch_float", images, ImagePlanar, size=4)
+        else:
+            batch = self.make_batch_float(images, outs, order, bottom_up, mean, std, scale, bias)
+        _need_cuda("submit_float", [*batch[0], *batch[1]], "images and outs")
         n = len(batch[2])
-        self._sync_stream()
-        t = C.c_uint64(0)
-        check(self.lib.fpng_amd_encode_submit_planar_float(self.h, batch[2], n, C.byref(batch[3]), flags, C.byref(t)))
-        self.last_ticket = t.value
-        self._keep[t.value] = batch
-        for old in [k for k in self._keep if k + 8 <= t.value]:
-            del self._keep[old]
-        return n
-
-    _PACK_KINDS = {"image": _lib.DESC_IMAGE, "ex": _lib.DESC_EX, "planar": _lib.DESC_PLANAR, "float": _lib.DESC_PLANAR_FLOAT}
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit_planar_float(self.h, batch[2], n, C.byref(batch[3]), flags, t), n, batch)
 
     @staticmethod
     def make_batch_packed(images, kind="image", **layout):
         """Descriptor for submit_packed(): the make_batch*() descriptor of `kind` ("image" | "ex" | "planar" | "float", with that
         kind's layout arguments: order, bottom_up, and for "float" mean / std / scale / bias) without outputs."""
-        if kind not in Encoder._PACK_KINDS:
-            raise ValueError(f"make_batch_packed: kind is one of {sorted(Encoder._PACK_KINDS)}, not {kind!r}")
-        outs = [_NoOut] * len(images)
-        if kind == "image":
-            if layout:
-                raise ValueError(f"make_batch_packed: kind 'image' takes no layout arguments, got {sorted(layout)}")
-            arr = (Image * len(images))()
-            for a, im in zip(arr, images):
-                if im.dtype != torch.uint8 or im.dim() != 3 or not im.is_contiguous():
-                    raise ValueError("make_batch_packed: kind 'image' takes contiguous uint8 tensors shaped (h, w, c)")
-                a.d_pixels, (a.h, a.w, a.num_chans) = im.data_ptr(), im.shape
-            batch = (images, outs, arr)
-        else:
-            make = {"ex": Encoder.make_batch_ex, "planar": Encoder.make_batch_planar, "float": Encoder.make_batch_float}[kind]
-            batch = make(images, outs, **layout)
-        return ("packed", kind) + tuple(batch)
+        if kind == "image" and layout:
+            raise ValueError(f"make_batch_packed: kind 'image' takes no layout arguments, got {sorted(layout)}")
+        if kind in ("ex", "planar") and set(layout) - {"order", "bottom_up"}:  # (what that kind's own maker has no argument for)
+            raise TypeError(f"make_batch_packed: kind {kind!r} takes order and bottom_up, got {sorted(layout)}")
+        if kind == "ex":
+            _need_cuda("make_batch_packed", images, "images")  # (as make_batch_ex asks)
+        arr, fmt = _source_records("make_batch_packed", images, kind, **layout)
+        return ("packed", kind, images, [_NoOut] * len(images), arr) + ((fmt,) if kind == "float" else ())
 
     def submit_packed(self, images, arena, kind="image", align=16, lead=0, table=None, flags=0, **layout):
         """fpng_amd_encode_submit_packed: the files of ONE submission back to back in `arena` (a uint8 CUDA tensor whose address is a
@@ -1822,27 +1792,20 @@ class Encoder:
         submit_planar / submit_float (kind, **layout: that call's order / bottom_up / mean / std / scale / bias), or a
         make_batch_packed() descriptor.  table: optional int64 CUDA tensor of 2 * (n + 1) elements, filled with {offset, png_size} per
         file and {total, files placed}.  Asynchronous; wait_packed(last_ticket, n) for the records."""
-        batch = images if isinstance(images, tuple) and images[:1] == ("packed",) else self.make_batch_packed(images, kind, **layout)
+        if isinstance(images, tuple) and images[:1] == ("packed",):
+            batch = images
+        elif isinstance(images, tuple) and any(isinstance(v, C.Array) for v in images):
+            raise ValueError("submit_packed: a descriptor comes from make_batch_packed(), not from another call's maker")
+        else:
+            batch = self.make_batch_packed(images, kind, **layout)
         kind, arr = batch[1], batch[4]
         n = len(arr)
-        if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()):
-            raise ValueError("submit_packed: arena is a contiguous uint8 CUDA tensor")
-        if not all(im.is_cuda for im in batch[2]):
-            raise ValueError("submit_packed: images are CUDA tensors")
-        pack = _lib.Pack(arena.data_ptr(), arena.numel(), align, lead, None, 0)
-        if table is not None:
-            if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= 2 * (n + 1)):
-                raise ValueError("submit_packed: table is a contiguous int64 CUDA tensor of 2 * (n + 1) elements")
-            pack.d_table = table.data_ptr()
-        self._sync_stream()
-        t = C.c_uint64(0)
-        check(self.lib.fpng_amd_encode_submit_packed(self.h, self._PACK_KINDS[kind], C.cast(arr, C.c_void_p), n,
-                                                     C.byref(batch[5]) if kind == "float" else None, flags, C.byref(pack), C.byref(t)))
-        self.last_ticket = t.value
-        self._keep[t.value] = (batch, arena, table)  # the arena and the table stay alive with the sources
-        for old in [k for k in self._keep if k + 8 <= t.value]:
-            del self._keep[old]
-        return n
+        pack = _pack_record("submit_packed", arena, align, lead, table, n)
+        _need_cuda("submit_packed", batch[2], "images")
+        fmt = C.byref(batch[5]) if kind == "float" else None
+        # (the arena and the table stay alive with the sources)
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit_packed(self.h, _DESC_KINDS[kind], C.cast(arr, C.c_void_p), n, fmt, flags, C.byref(pack), t),
+                            n, (batch, arena, table))
 
     def wait_packed(self, ticket, n):
         """Waits for the packed submission `ticket`; returns ([(offset, png_size, mode, status)], total): file i is
@@ -1858,7 +1821,7 @@ class Encoder:
         records as wait_packed() gives them; one .cpu() of the first and one write() make a shard body."""
         batch = self.make_batch_packed(images, kind, **layout)
         arr = batch[4]
-        dims = [(a.w, a.h, format_channels(a.format) if kind == "ex" else a.num_chans) for a in arr]
+        dims = [(a.w, a.h, c) for a, c in zip(arr, _record_channels(kind, arr))]
         cap = pack_capacity(dims, align, lead)
         a = max(int(align), 16)
         raw = torch.empty(cap + a, dtype=torch.uint8, device=batch[2][0].device)
@@ -1879,9 +1842,8 @@ class Encoder:
         if (outs is None) == (arena is None):
             raise ValueError("submit_renditions: outs (one per rendition) or arena, one of the two")
         images = list(images)
-        if not all(isinstance(im, torch.Tensor) and im.is_cuda for im in images):
-            raise ValueError("submit_renditions: images are CUDA tensors")
-        arr, fmt, _ = _source_records("submit_renditions", images, kind, **layout)
+        _need_cuda("submit_renditions", images, "images")
+        arr, fmt = _source_records("submit_renditions", images, kind, **layout)
         rarr = _rendition_records(renditions)
         n = len(rarr)
         pack = None
@@ -1891,39 +1853,23 @@ class Encoder:
             for r, o in zip(rarr, outs):
                 r.d_out, r.out_cap = o.data_ptr(), o.numel()
         else:
-            if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()):
-                raise ValueError("submit_renditions: arena is a contiguous uint8 CUDA tensor")
-            pack = _lib.Pack(arena.data_ptr(), arena.numel(), align, lead, None, 0)
-            if table is not None:
-                if not (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= 2 * (n + 1)):
-                    raise ValueError("submit_renditions: table is a contiguous int64 CUDA tensor of 2 * (n + 1) elements")
-                pack.d_table = table.data_ptr()
-        self._sync_stream()
-        t = C.c_uint64(0)
-        check(self.lib.fpng_amd_encode_submit_renditions(self.h, _DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), C.byref(fmt) if fmt is not None else None,
-                                                         rarr, n, flags, C.byref(pack) if pack is not None else None, C.byref(t)))
-        self.last_ticket = t.value
-        self._keep[t.value] = (images, outs, arena, table)  # sources and destinations stay alive while the submission runs
-        for old in [k for k in self._keep if k + 8 <= t.value]:
-            del self._keep[old]
-        return n
+            pack = C.byref(_pack_record("submit_renditions", arena, align, lead, table, n))
+        fmt = C.byref(fmt) if fmt is not None else None
+        # (sources and destinations stay alive while the submission runs)
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit_renditions(self.h, _DESC_KINDS[kind], C.cast(arr, C.c_void_p), len(arr), fmt, rarr, n, flags, pack, t),
+                            n, (images, outs, arena, table))
 
     def encode_renditions(self, images, renditions, kind="image", flags=0, **layout):
         """Convenience: outputs of max_encoded_size() each, one submit_renditions(), the wait: the files as a list of bytes, in
         rendition order."""
         images = list(images)
-        _, _, chans = _source_records("encode_renditions", images, kind, **layout)
+        chans = _record_channels(kind, _source_records("encode_renditions", images, kind, **layout)[0])
         for r in renditions:
             if r.image >= len(images):
                 raise ValueError(f"encode_renditions: rendition of image {r.image} of {len(images)}")
         outs = [torch.empty(max_encoded_size(r.w, r.h, chans[r.image]) + 64, dtype=torch.uint8, device=images[r.image].device) for r in renditions]
         n = self.submit_renditions(images, renditions, kind=kind, outs=outs, flags=flags, **layout)
-        pngs = []
-        for out, (size, _, status) in zip(outs, self.wait(self.last_ticket, n)):
-            if status:
-                raise FpngAmdError(status, "device reported an encode failure")
-            pngs.append(bytes(out[:size].cpu().numpy()))
-        return pngs
+        return _files(outs, self.wait(self.last_ticket, n))
 
     def wait(self, ticket, n):
         """Waits for the submission `ticket` (see last_ticket) only; returns its (png_size, mode, status) records."""
@@ -1973,12 +1919,7 @@ class Encoder:
         res = []
         for ticket, m in parts:
             res += self.wait(ticket, m)
-        pngs = []
-        for out, (size, mode, status) in zip(outs, res):
-            if status:
-                raise FpngAmdError(status, "device reported an encode failure")
-            pngs.append(bytes(out[:size].cpu().numpy()))
-        return pngs, [m for _, m, _ in res]
+        return _files(outs, res), [m for _, m, _ in res]
 
     def decode_batch(self, pngs, desired_chans, dims=None):
         """fpng_amd_decode_batch: list of fpng-written files (bytes) -> list of (status, uint8 CUDA tensor (h, w, desired_chans)

@@ -469,12 +469,12 @@ struct Submission {
     uint64_t total_rows = 0;
     uint64_t local_dwords = kLocalFrontPad; // scratch for the rows' local streams (assemble_kernel may read up to four dwords in front of a stream)
     uint32_t chan_mask = 0;    // bit 0: 3-channel jobs present, bit 1: 4-channel jobs
-    bool ex = false;           // fpng_amd_encode_submit_ex: the jobs carry a source layout, the *_ex kernels read their pixels
-    bool planar = false;       // fpng_amd_encode_submit_planar: planar jobs, the *_planar kernels read their pixels (chan_mask says which)
-    bool planar_float = false; // fpng_amd_encode_submit_planar_float: planar jobs of floats (`planar` is set too), the *_planar_float kernels of float_dtype
+    // FPNG_AMD_DESC_* of the batch, which names the kernel family that reads its pixels: _IMAGE the plain kernels, _EX the *_ex ones
+    // (the jobs carry a source layout), _PLANAR the *_planar ones (chan_mask says which), _PLANAR_FLOAT the *_planar_float ones of float_dtype
+    uint32_t kind = FPNG_AMD_DESC_IMAGE;
     uint32_t float_dtype = 0;
     FloatQuant fq = {};
-    uint32_t layout_mask = 0;  // (ex) bit 0: 3-byte sources, bit 1: 4-byte sources with 4 channels, bit 2: 4-byte sources with 3
+    uint32_t layout_mask = 0;  // (_EX) bit 0: 3-byte sources, bit 1: 4-byte sources with 4 channels, bit 2: 4-byte sources with 3
     uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
 };
 
@@ -514,10 +514,43 @@ constexpr SrcFormat kSrcFormats[FPNG_AMD_SRC_COUNT] = {
 
 static_assert(sizeof(fpng_amd_image_planar) == 56 && offsetof(fpng_amd_image_planar, w) == 24 && offsetof(fpng_amd_image_planar, d_out) == 40, "fpng_amd_image_planar layout");
 
-// ---- one image record judged by its kind's own rules: what prepare_jobs() and the renditions' rendition_sources() both call, so
-// that "every rule of the kind's own submit holds" for the renditions by construction ----
-// fmt of the float kind: scale and bias into fq, the element's bytes into *elem
-int check_float_format(const fpng_amd_float_format *ffmt, FloatQuant &fq, int64_t *elem)
+// ---- the image records of one call: what every encode entry point makes of its arguments, so that the four kinds travel as one
+// value and are told apart in one place, read_source() ----
+struct SourceBatch {
+    uint32_t kind; // FPNG_AMD_DESC_*: what `records` points at
+    const void *records;
+    uint32_t n;
+    const fpng_amd_float_format *fmt = nullptr; // with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it
+};
+
+// what holds for a batch of any kind, whoever submits it
+int check_batch(const SourceBatch &b)
+{
+    if (b.kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
+    if ((b.kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (b.fmt != nullptr)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
+    if (!b.records || !b.n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    return FPNG_AMD_OK;
+}
+
+// One record of any kind, judged by its kind's own rules (read_source): what prepare_jobs() makes a Job of and the renditions'
+// resize stage reads, so that "every rule of the kind's own submit holds" for the renditions by construction
+struct Source {
+    uintptr_t base; // channel data of pixel (0, 0): Job::rows, EncResize::src of the whole image
+    int64_t pitch, plane_pitch;
+    uint32_t layout, sel, chans, w, h; // layout: kEncSrc*
+    uint32_t px_bytes; // from a pixel to the next one of its row (planar: the element)
+    uint8_t *d_out;    // the record's output, the caller's to judge
+    size_t out_cap;
+    // the fields that a record of every kind has under the same names
+    template <typename Record> void take(const Record &x, uint32_t num_chans, int64_t row_pitch, int64_t planes_pitch)
+    {
+        base = (uintptr_t)x.d_pixels, pitch = row_pitch, plane_pitch = planes_pitch;
+        w = x.w, h = x.h, chans = num_chans, d_out = x.d_out, out_cap = x.out_cap;
+    }
+};
+
+// fmt of the float kind: scale and bias into fq
+int check_float_format(const fpng_amd_float_format *ffmt, FloatQuant &fq)
 {
     if (ffmt->dtype > FPNG_AMD_BF16) return fail(FPNG_AMD_ERR_INVALID_ARG, "dtype is FPNG_AMD_F32, _F16 or _BF16");
     if (ffmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt->reserved must be 0");
@@ -525,12 +558,11 @@ int check_float_format(const fpng_amd_float_format *ffmt, FloatQuant &fq, int64_
         if (!std::isfinite(ffmt->scale[k]) || !std::isfinite(ffmt->bias[k])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
         fq.scale[k] = ffmt->scale[k], fq.bias[k] = ffmt->bias[k];
     }
-    *elem = ffmt->dtype == FPNG_AMD_F32 ? 4 : 2;
     return FPNG_AMD_OK;
 }
 
-// fpng_amd_image_planar (elem: bytes of an element, 1 for uint8 planes): the record as a fpng_amd_image plus its two pitches
-int check_planar_source(const fpng_amd_image_planar &x, int64_t elem, fpng_amd_image &im, int64_t &pitch, int64_t &plane_pitch)
+// fpng_amd_image_planar (elem: bytes of an element, 1 for uint8 planes): its size, pointers and two pitches into s
+int check_planar_source(const fpng_amd_image_planar &x, int64_t elem, Source &s)
 {
     int rc;
     if (x.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "reserved must be 0");
@@ -538,62 +570,85 @@ int check_planar_source(const fpng_amd_image_planar &x, int64_t elem, fpng_amd_i
     const int64_t row_bytes = (int64_t)x.w * elem;
     if (elem > 1 && (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (uint64_t)(elem - 1)))
         return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
-    pitch = x.row_pitch ? x.row_pitch : row_bytes;
+    const int64_t pitch = x.row_pitch ? x.row_pitch : row_bytes;
     const int64_t apitch = pitch < 0 ? -pitch : pitch;
     if (apitch < row_bytes) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w (* element bytes)");
     // (h, w < 2^24 and |row_pitch| < 2^63 / 2^24 keep the span in 64 bits)
     if (apitch > (INT64_MAX >> 26)) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| too large");
     const int64_t span = (int64_t)(x.h - 1) * apitch + row_bytes; // bytes from a plane's lowest row to the end of its highest
-    plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)x.h * apitch;
+    const int64_t plane_pitch = x.plane_pitch ? x.plane_pitch : (int64_t)x.h * apitch;
     if (plane_pitch == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "plane_pitch out of range");
     if ((plane_pitch < 0 ? -plane_pitch : plane_pitch) < span)
         return fail(FPNG_AMD_ERR_INVALID_ARG, "|plane_pitch| < (h - 1) * |row_pitch| + w (* element bytes): the planes overlap");
-    im.d_pixels = x.d_pixels;
-    im.w = x.w, im.h = x.h, im.num_chans = x.num_chans;
-    im.d_out = x.d_out;
-    im.out_cap = x.out_cap;
+    s.take(x, x.num_chans, pitch, plane_pitch);
     return FPNG_AMD_OK;
 }
 
-// fpng_amd_image_ex: the record as a fpng_amd_image plus its format and pitch
-int check_ex_source(const fpng_amd_image_ex &x, fpng_amd_image &im, const SrcFormat *&fmt, int64_t &pitch)
+// fpng_amd_image_ex: its size, pointers and pitch into s, and its format
+int check_ex_source(const fpng_amd_image_ex &x, Source &s, const SrcFormat *&fmt)
 {
     int rc;
     if (x.format >= FPNG_AMD_SRC_COUNT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown source format");
     fmt = &kSrcFormats[x.format];
     if ((rc = check_dims(x.w, x.h, fmt->chans))) return rc;
     const int64_t packed = (int64_t)x.w * fmt->bytes;
-    pitch = x.row_pitch ? x.row_pitch : packed;
+    const int64_t pitch = x.row_pitch ? x.row_pitch : packed;
     if ((pitch < 0 ? -pitch : pitch) < packed) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| < w * source bytes per pixel");
     if (fmt->bytes == 4 && (((uintptr_t)x.d_pixels & 3) || (pitch & 3)))
         return fail(FPNG_AMD_ERR_INVALID_ARG, "4-byte source pixels need d_pixels and row_pitch to be multiples of 4");
-    im.d_pixels = x.d_pixels;
-    im.w = x.w, im.h = x.h, im.num_chans = fmt->chans;
-    im.d_out = x.d_out;
-    im.out_cap = x.out_cap;
+    s.take(x, fmt->chans, pitch, 0);
     return FPNG_AMD_OK;
 }
 
-// The pixels of a record of any kind, once it is a fpng_amd_image (the outputs are the caller's to judge)
-int check_source_pixels(const fpng_amd_image &im, bool planar)
+// The pixels of a record of any kind, once its size and pointers are in s (the outputs are the caller's to judge)
+int check_source_pixels(const Source &s, bool planar)
 {
     int rc;
-    if ((rc = check_dims(im.w, im.h, im.num_chans))) return rc;
-    if (!im.d_pixels) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
-    if (!planar && im.num_chans == 4 && ((uintptr_t)im.d_pixels & 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
+    if ((rc = check_dims(s.w, s.h, s.chans))) return rc;
+    if (!s.base) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
+    if (!planar && s.chans == 4 && (s.base & 3)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
     return FPNG_AMD_OK;
+}
+
+// Record i of a batch that check_batch(), and check_float_format() its fmt, have passed, as a Source: the one place that knows what
+// `records` points at and applies each kind's rules
+int read_source(const SourceBatch &b, uint32_t i, Source &s)
+{
+    const SrcFormat *f = nullptr;
+    const bool planar = b.kind >= FPNG_AMD_DESC_PLANAR;
+    const int64_t elem = !b.fmt ? 1 : b.fmt->dtype == FPNG_AMD_F32 ? 4 : 2; // bytes of a planar source's element
+    int rc;
+    if (planar) {
+        if ((rc = check_planar_source(((const fpng_amd_image_planar *)b.records)[i], elem, s))) return rc;
+    } else if (b.kind == FPNG_AMD_DESC_EX) {
+        if ((rc = check_ex_source(((const fpng_amd_image_ex *)b.records)[i], s, f))) return rc;
+    } else {
+        const fpng_amd_image &im = ((const fpng_amd_image *)b.records)[i];
+        s.take(im, im.num_chans, (int64_t)im.w * im.num_chans, 0); // tight rows of R,G,B[,A]
+    }
+    if ((rc = check_source_pixels(s, planar))) return rc;
+    if (b.kind == FPNG_AMD_DESC_IMAGE) f = &kSrcFormats[s.chans == 3 ? FPNG_AMD_SRC_RGB : FPNG_AMD_SRC_RGBA];
+    s.sel = f ? f->sel : 0, s.px_bytes = f ? f->bytes : (uint32_t)elem;
+    s.layout = f ? (f->bytes == 3 ? kEncSrcBytes3 : kEncSrcBytes4) : b.fmt ? kEncSrcFloat + b.fmt->dtype : kEncSrcPlanar;
+    return FPNG_AMD_OK;
+}
+
+// a row's local stream in dwords: at most L bits per filtered byte, L = the longest literal code of the table in use (12 for the
+// per-image tables of 2-pass, reference fpng.cpp:1111; run tokens need less per byte they cover), + end-of-block; rows start
+// 16-byte aligned and the 16-byte flush / assemble_kernel may touch up to four dwords past the stream.  Whole 128-byte lines
+uint32_t local_stride(uint32_t bpl, uint32_t chans, bool two_pass)
+{
+    const uint64_t bits_per_byte = two_pass ? 12u : g_1pass_bits_per_byte[chans];
+    return (uint32_t)(((((uint64_t)bpl + 1) * bits_per_byte + 64 + 31) / 32 + 4 + 31) & ~31ull);
 }
 
 // Fills slot.jobs[0..n) for whole-image jobs and sizes the scratch buffers.  Only `slot` (which is free) and
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
-// ex_images (fpng_amd_encode_submit_ex) or pl_images (fpng_amd_encode_submit_planar) replaces `images` when it is given.
-// ffmt (fpng_amd_encode_submit_planar_float, with pl_images): the planes hold floats of that type; pitches stay bytes.
+// b: a batch that check_batch() has passed (the float kind: the planes hold floats of b.fmt's type; pitches stay bytes).
 // packed (fpng_amd_encode_submit_packed): the records carry no outputs -- pack_place_kernel fills Job::out / out_cap on the device.
-int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const fpng_amd_image *images,
-                 const fpng_amd_image_ex *ex_images, const fpng_amd_image_planar *pl_images, uint32_t n, uint32_t flags, Submission &sub,
-                 const fpng_amd_float_format *ffmt = nullptr, bool packed = false)
+int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const SourceBatch &b, uint32_t flags, Submission &sub, bool packed)
 {
-    if (!e || !(images || ex_images || pl_images) || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
+    const uint32_t n = b.n;
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "batch larger than 65535 images");
     int rc;
     if ((rc = slot.jobs.ensure(n)) || (rc = slot.results.ensure(n))) return rc;
@@ -603,66 +658,45 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     const bool two_pass = (flags & FPNG_AMD_ENCODE_SLOWER) && !force_stored;
     sub = Submission();
     sub.n = n;
-    sub.ex = ex_images != nullptr;
-    sub.planar = pl_images != nullptr;
-    int64_t elem = 1; // bytes of a planar source's element
-    if (ffmt) {
-        if ((rc = check_float_format(ffmt, sub.fq, &elem))) return rc;
-        sub.planar_float = true;
-        sub.float_dtype = ffmt->dtype;
-    }
+    sub.kind = b.kind;
+    if (b.fmt && (rc = check_float_format(b.fmt, sub.fq))) return rc;
+    sub.float_dtype = b.fmt ? b.fmt->dtype : 0;
     for (uint32_t i = 0; i < n; i++) {
-        fpng_amd_image im_of_ex;
-        const SrcFormat *fmt = nullptr;
-        int64_t pitch = 0, plane_pitch = 0;
-        if (pl_images && (rc = check_planar_source(pl_images[i], elem, im_of_ex, pitch, plane_pitch))) return rc;
-        if (ex_images && (rc = check_ex_source(ex_images[i], im_of_ex, fmt, pitch))) return rc;
-        const fpng_amd_image &im = (ex_images || pl_images) ? im_of_ex : images[i];
-        if ((rc = check_source_pixels(im, pl_images != nullptr))) return rc;
+        Source im;
+        if ((rc = read_source(b, i, im))) return rc;
         if (packed && (im.d_out || im.out_cap)) return fail(FPNG_AMD_ERR_INVALID_ARG, "packed submission: d_out must be NULL and out_cap 0");
         if (!packed && !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
         if ((uintptr_t)im.d_out & 15) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
-        if (!packed && im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.num_chans))
+        if (!packed && im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.chans))
             return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
         Job &j = slot.jobs.p[i];
         std::memset(&j, 0, sizeof j);
-        j.rows = (const uint8_t *)im.d_pixels;
-        j.row_above = nullptr;
+        j.rows = (const uint8_t *)im.base;
         j.out = im.d_out;
         j.out_cap = im.out_cap;
         j.w = im.w;
-        j.c = im.num_chans;
-        j.bpl = im.w * im.num_chans;
-        j.nrows = j.h_total = im.h;
-        j.y0 = 0;
+        j.c = im.chans;
+        j.bpl = im.w * im.chans;
+        j.nrows = j.h_total = im.h; // (row_above and y0 stay 0: whole images)
         j.flags = flags & (FPNG_AMD_ENCODE_SLOWER | FPNG_AMD_FORCE_UNCOMPRESSED); // (the reference looks at these two bits only; the bits above are the kernels' own)
         j.row_base = (uint32_t)sub.total_rows;
         j.one_pass = two_pass ? 0 : 1;
         j.whole_png = j.is_first = j.is_last = 1;
         j.bit_bias = (int64_t)kPngHeaderBytes * 8;
-        j.table = two_pass ? nullptr /* patched below */ : dt.one_pass[im.num_chans];
-        j.crc_blocks = (uint32_t)((fpng_amd_max_encoded_size(im.w, im.h, im.num_chans) + kCrcRangeBytes - 1) / kCrcRangeBytes) + 1;
-        make_png_header(j.png_header, im.w, im.h, im.num_chans);
-        // a row's local stream: at most L bits per filtered byte, L = the longest literal code of the table in use
-        // (12 for the per-image tables of 2-pass, reference fpng.cpp:1111; run tokens need less per byte they
-        // cover), + end-of-block; rows start 16-byte aligned and the 16-byte flush / assemble_kernel may touch up
-        // to four dwords past the stream
-        const uint64_t bits_per_byte = two_pass ? 12u : g_1pass_bits_per_byte[im.num_chans];
-        j.local_stride = (uint32_t)(((((uint64_t)j.bpl + 1) * bits_per_byte + 64 + 31) / 32 + 4 + 31) & ~31ull); // whole 128-byte lines
+        j.table = two_pass ? nullptr /* patched below */ : dt.one_pass[im.chans];
+        j.crc_blocks = (uint32_t)((fpng_amd_max_encoded_size(im.w, im.h, im.chans) + kCrcRangeBytes - 1) / kCrcRangeBytes) + 1;
+        make_png_header(j.png_header, im.w, im.h, im.chans);
+        j.local_stride = local_stride(j.bpl, im.chans, two_pass);
         j.local_base = sub.local_dwords;
-        sub.chan_mask |= (im.num_chans == 3) ? 1u : 2u;
-        if (fmt) {
-            j.pitch = pitch;
-            j.src_bytes = fmt->bytes;
-            j.sel = fmt->sel;
-            sub.layout_mask |= fmt->bytes == 3 ? 1u : (fmt->chans == 4 ? 2u : 4u);
+        sub.chan_mask |= (im.chans == 3) ? 1u : 2u;
+        if (b.kind != FPNG_AMD_DESC_IMAGE) { // the source layout the kind's kernels read (the plain kernels know theirs: the fields stay 0)
+            j.pitch = im.pitch;
+            j.plane_pitch = im.plane_pitch;
+            j.sel = im.sel;
+            j.src_bytes = b.fmt ? kFloatLayout + b.fmt->dtype : im.px_bytes;
         }
-        if (pl_images) {
-            j.pitch = pitch;
-            j.plane_pitch = plane_pitch;
-            j.src_bytes = ffmt ? kFloatLayout + ffmt->dtype : 1;
-        }
-        if (im.num_chans == 4) sub.px4 += (uint64_t)im.w * im.h, sub.px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
+        if (b.kind == FPNG_AMD_DESC_EX) sub.layout_mask |= im.px_bytes == 3 ? 1u : (im.chans == 4 ? 2u : 4u);
+        if (im.chans == 4) sub.px4 += (uint64_t)im.w * im.h, sub.px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
         const uint64_t units = im.h; // records of the job: one per row
         sub.local_dwords += (uint64_t)j.local_stride * units;
         if (sub.total_rows + units > 0xFFFFFFFFull) return fail(FPNG_AMD_ERR_UNSUPPORTED, "too many rows in one batch");
@@ -684,14 +718,6 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
 }
 
 // ---- renditions (fpng_amd_encode_submit_renditions, include/fpng_amd.h; the resize stage: encode_resize.h) ----
-// An image record of any of the four kinds, judged by its kind's own rules, as the resize stage reads it
-struct RenditionSource {
-    uintptr_t base; // channel data of pixel (0, 0): EncResize::src of the whole image
-    int64_t pitch, plane_pitch;
-    uint32_t layout, sel, chans, w, h;
-    uint32_t px_bytes; // from a pixel to the next one of its row (planar: the element)
-};
-
 // What fpng_amd_renditions_plan answers and what the submit call stages: the records with their pointers still open (dst_off:
 // where a rendition's rows begin in the scratch; nearest_at: where its indices begin in `nearest`, -1 without)
 struct RenditionPlan {
@@ -712,49 +738,36 @@ static_assert(FPNG_AMD_RENDITION_BILINEAR == kResizeBilinear && FPNG_AMD_RENDITI
 
 enum { kRenditionOuts = 0, kRenditionPacked = 1, kRenditionNoOuts = 2 }; // how plan_renditions judges d_out and out_cap
 
-int rendition_sources(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *ffmt, std::vector<RenditionSource> &out, FloatQuant &fq)
+// the images of a renditions call, each judged as its kind's own submit judges it -- but for the outputs, which they have none of
+int rendition_sources(const SourceBatch &b, std::vector<Source> &out, FloatQuant &fq)
 {
-    if (desc_kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
-    if ((desc_kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (ffmt != nullptr)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
-    if (!images || !n_images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    int64_t elem = 1; // bytes of a planar source's element
     int rc;
-    if (ffmt && (rc = check_float_format(ffmt, fq, &elem))) return rc;
-    out.resize(n_images);
-    for (uint32_t i = 0; i < n_images; i++) {
-        RenditionSource &s = out[i];
-        fpng_amd_image im_of;
-        const SrcFormat *f = nullptr;
-        s.pitch = s.plane_pitch = 0;
-        const bool planar = desc_kind >= FPNG_AMD_DESC_PLANAR;
-        if (planar && (rc = check_planar_source(((const fpng_amd_image_planar *)images)[i], elem, im_of, s.pitch, s.plane_pitch))) return rc;
-        if (desc_kind == FPNG_AMD_DESC_EX && (rc = check_ex_source(((const fpng_amd_image_ex *)images)[i], im_of, f, s.pitch))) return rc;
-        const fpng_amd_image &im = desc_kind == FPNG_AMD_DESC_IMAGE ? ((const fpng_amd_image *)images)[i] : im_of;
-        if ((rc = check_source_pixels(im, planar))) return rc;
-        if (im.d_out || im.out_cap) return fail(FPNG_AMD_ERR_INVALID_ARG, "renditions: an image record's d_out must be NULL and its out_cap 0 (the files belong to the renditions)");
-        if (desc_kind == FPNG_AMD_DESC_IMAGE) f = &kSrcFormats[im.num_chans == 3 ? FPNG_AMD_SRC_RGB : FPNG_AMD_SRC_RGBA], s.pitch = (int64_t)im.w * im.num_chans;
-        s.w = im.w, s.h = im.h, s.chans = im.num_chans;
-        s.sel = f ? f->sel : 0, s.px_bytes = f ? f->bytes : (uint32_t)elem;
-        s.layout = f ? (f->bytes == 3 ? kEncSrcBytes3 : kEncSrcBytes4) : ffmt ? kEncSrcFloat + ffmt->dtype : kEncSrcPlanar;
-        s.base = (uintptr_t)im.d_pixels;
+    if ((rc = check_batch(b)) || (b.fmt && (rc = check_float_format(b.fmt, fq)))) return rc;
+    out.resize(b.n);
+    for (uint32_t i = 0; i < b.n; i++) {
+        if ((rc = read_source(b, i, out[i]))) return rc;
+        if (out[i].d_out || out[i].out_cap) return fail(FPNG_AMD_ERR_INVALID_ARG, "renditions: an image record's d_out must be NULL and its out_cap 0 (the files belong to the renditions)");
     }
     return FPNG_AMD_OK;
 }
 
-int plan_renditions(const std::vector<RenditionSource> &src, const fpng_amd_rendition *renditions, uint32_t n, int outs, RenditionPlan &plan)
+// the images first, then the renditions of them: everything a renditions call can be refused for short of the encoder
+int plan_renditions(const SourceBatch &images, const fpng_amd_rendition *renditions, uint32_t n, int outs, RenditionPlan &plan)
 {
+    std::vector<Source> src;
+    int rc;
+    if ((rc = rendition_sources(images, src, plan.fq))) return rc;
     if (!renditions || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty renditions");
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "more than 65535 renditions");
     plan.recs.resize(n), plan.dst_off.resize(n), plan.nearest_at.assign(n, -1), plan.pre.assign((size_t)n + 1, 0);
     uint64_t cursor = 0;
-    int rc;
     for (uint32_t k = 0; k < n; k++) {
         const fpng_amd_rendition &r = renditions[k];
         if (r.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_rendition::reserved must be 0");
         if (r.image >= src.size()) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_rendition::image >= n_images");
         if (r.filter >= kResizeAllFilters) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown fpng_amd_rendition::filter (FPNG_AMD_RENDITION_*)");
         if (r.alpha_op != 0 && r.alpha_op != FPNG_AMD_ALPHA_PREMULTIPLIED) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_rendition::alpha_op is 0 or FPNG_AMD_ALPHA_PREMULTIPLIED");
-        const RenditionSource &s = src[r.image];
+        const Source &s = src[r.image];
         uint32_t bw = r.box_w, bh = r.box_h;
         if (!(r.box_x | r.box_y | r.box_w | r.box_h)) bw = s.w, bh = s.h; // the whole image
         else if (!bw || !bh) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty box (all four fields 0 mean the whole image)");
@@ -800,7 +813,7 @@ struct RenditionStage {
     RenditionPlan plan;
     const fpng_amd_rendition *renditions = nullptr;
     uint32_t n = 0;
-    std::vector<fpng_amd_image> images;
+    std::vector<fpng_amd_image> images; // n of them: the batch the call submits, filled in by stage_renditions()
     size_t at_pre = 0, at_fq = 0, at_nearest = 0, rec_bytes = 0; // d_rend: EncResize[n], pre[n + 1], FloatQuant, the NEAREST indices
 };
 
@@ -815,7 +828,6 @@ int stage_renditions(fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc
     st.rec_bytes = st.at_nearest + st.plan.nearest.size() * sizeof(uint32_t);
     int rc;
     if ((rc = sc.d_resized.ensure(st.plan.scratch_bytes)) || (rc = sc.d_rend.ensure(st.rec_bytes)) || (rc = slot.rend.ensure(st.rec_bytes))) return rc;
-    st.images.resize(n);
     for (uint32_t k = 0; k < n; k++) {
         EncResize &e = st.plan.recs[k];
         e.dst = sc.d_resized.p + st.plan.dst_off[k];
@@ -843,13 +855,15 @@ int launch_renditions(hipStream_t s, fpng_amd_encoder::Slot &slot, fpng_amd_enco
     return FPNG_AMD_OK;
 }
 
-// stage (fpng_amd_encode_submit_renditions): the renditions' resize runs on the lane's stream in front of the chain, and the chain's
-// images are the stage's -- the plain path over rows in the lane's scratch
-int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_image_ex *ex_images, uint32_t n, uint32_t flags, uint64_t *ticket_out,
-           const fpng_amd_image_planar *pl_images = nullptr, const fpng_amd_float_format *ffmt = nullptr, const fpng_amd_pack *pack = nullptr,
-           RenditionStage *stage = nullptr)
+// The one way onto the GPU for a batch of any kind.  pack (fpng_amd_encode_submit_packed, checked by check_pack): the files go into
+// its arena.  stage (fpng_amd_encode_submit_renditions): the renditions' resize runs on the lane's stream in front of the chain, and
+// the batch is the stage's images -- the plain path over rows in the lane's scratch
+int submit(fpng_amd_encoder *e, const SourceBatch &batch, uint32_t flags, uint64_t *ticket_out, const fpng_amd_pack *pack = nullptr, RenditionStage *stage = nullptr)
 {
     if (!e) return fail(FPNG_AMD_ERR_INVALID_ARG, "null encoder");
+    int rc;
+    if ((rc = check_batch(batch))) return rc;
+    const uint32_t n = batch.n;
     HIP_TRY(hipSetDevice(e->device));
     // next slot of the ring; wait only if the submission that used it is still running.  Nothing of the encoder's
     // state changes before the batch has been validated.
@@ -872,12 +886,8 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     hipStream_t s = e->lane_stream[lane];
     fpng_amd_encoder::Scratch &sc = e->sc[lane];
     Submission sub;
-    int rc;
-    if (stage) {
-        if ((rc = stage_renditions(slot, sc, *stage))) return rc;
-        images = stage->images.data(), n = stage->n;
-    }
-    if ((rc = prepare_jobs(e, slot, sc, images, ex_images, pl_images, n, flags, sub, ffmt, pack != nullptr))) return rc;
+    if (stage && (rc = stage_renditions(slot, sc, *stage))) return rc;
+    if ((rc = prepare_jobs(e, slot, sc, batch, flags, sub, pack != nullptr))) return rc;
     const DeviceTables &dt = g_dev[e->device];
     const bool force_stored = (flags & FPNG_AMD_FORCE_UNCOMPRESSED) != 0;
     const bool two_pass = (flags & FPNG_AMD_ENCODE_SLOWER) && !force_stored;
@@ -926,7 +936,7 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     // 7 us MORE per chain: every kernel's first touch of the record goes over PCIe.)
     // One image: its record travels in the arguments of the chain's first kernel, which leaves it in d_jobs for the others
     // (encode_rows_first_kernel): no blit kernel + dispatch gap in front of the chain.
-    const bool job_in_args = n == 1 && !force_stored && !sub.ex && !sub.planar; // (the *_first kernels have no layout forms)
+    const bool job_in_args = n == 1 && !force_stored && sub.kind == FPNG_AMD_DESC_IMAGE; // (the *_first kernels have no layout forms)
     const Job *d_jobs = sc.d_jobs.p;
     if (!job_in_args) HIP_TRY(hipMemcpyAsync(sc.d_jobs.p, slot.jobs.p, n * sizeof(Job), hipMemcpyHostToDevice, s));
     if ((rc = mark(e, s, 0))) return rc;
@@ -945,14 +955,13 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
         sc.hist_zero = 0;
         if (job_in_args)
             launch_hist_first(s, slot.jobs.p[0], sc.d_jobs.p, sc.d_hist.p);
-        else if (sub.planar_float)
-            launch_hist_planar_float(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p, sub.float_dtype, sub.fq);
-        else if (sub.planar)
-            launch_hist_planar(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
-        else if (sub.ex)
-            launch_hist_ex(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
         else
-            launch_hist(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
+            switch (sub.kind) {
+            case FPNG_AMD_DESC_PLANAR_FLOAT: launch_hist_planar_float(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p, sub.float_dtype, sub.fq); break;
+            case FPNG_AMD_DESC_PLANAR: launch_hist_planar(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p); break;
+            case FPNG_AMD_DESC_EX: launch_hist_ex(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p); break;
+            default: launch_hist(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
+            }
         if ((rc = mark(e, s, ++ph))) return rc;
         launch_build_dynamic(s, sc.d_jobs.p, n, sc.d_hist.p, sc.d_dyn.p, rezero);
         if (rezero) sc.hist_zero = n_counters;
@@ -976,14 +985,17 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
     // (both kernels get slower by more than the two small launches cost) and 5-19 % MORE single-frame latency.
     if (job_in_args)
         launch_encode_rows_first(s, two_pass ? slot.jobs2.p[0] : slot.jobs.p[0], sc.d_jobs.p, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
-    else if (!force_stored && sub.planar_float)
-        launch_encode_rows_planar_float(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, sub.float_dtype, sub.fq);
-    else if (!force_stored && sub.planar)
-        launch_encode_rows_planar(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
-    else if (!force_stored && sub.ex)
-        launch_encode_rows_ex(s, d_jobs, n, sub.max_rows, sub.layout_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
     else if (!force_stored)
-        launch_encode_rows(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
+        switch (sub.kind) {
+        case FPNG_AMD_DESC_PLANAR_FLOAT:
+            launch_encode_rows_planar_float(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, sub.float_dtype, sub.fq);
+            break;
+        case FPNG_AMD_DESC_PLANAR: launch_encode_rows_planar(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p); break;
+        case FPNG_AMD_DESC_EX:
+            launch_encode_rows_ex(s, d_jobs, n, sub.max_rows, sub.layout_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
+            break;
+        default: launch_encode_rows(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
+        }
     if ((rc = mark(e, s, ++ph))) return rc;
     if (stagger) { // (only staggered walks wait for it)
         // ... and only a submission that follows while this one runs: with every other lane idle (one frame at a time) the marker
@@ -1010,15 +1022,15 @@ int submit(fpng_amd_encoder *e, const fpng_amd_image *images, const fpng_amd_ima
         launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
     if ((rc = mark(e, s, ++ph))) return rc;
     uint32_t *adler_parts = sc.d_partials.p + (size_t)n * sub.max_crc_blocks;
-    if (sub.planar_float)
+    switch (sub.kind) {
+    case FPNG_AMD_DESC_PLANAR_FLOAT:
         launch_assemble_planar_float(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts,
                                      sub.float_dtype, sub.fq);
-    else if (sub.planar)
-        launch_assemble_planar(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
-    else if (sub.ex)
-        launch_assemble_ex(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
-    else
-        launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
+        break;
+    case FPNG_AMD_DESC_PLANAR: launch_assemble_planar(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts); break;
+    case FPNG_AMD_DESC_EX: launch_assemble_ex(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts); break;
+    default: launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
+    }
     if ((rc = mark(e, s, ++ph))) return rc;
     launch_finalize(s, d_jobs, n, sub.max_crc_blocks, sc.d_rows.p, sc.d_states.p, dt.crc, sc.d_partials.p, adler_parts, slot.results.p);
     if ((rc = mark(e, s, ++ph))) return rc;
@@ -1049,26 +1061,24 @@ extern "C" {
 
 int fpng_amd_encode_submit(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags, uint64_t *ticket)
 {
-    return submit(e, images, nullptr, n, flags, ticket);
+    return submit(e, {FPNG_AMD_DESC_IMAGE, images, n}, flags, ticket);
 }
 
 int fpng_amd_encode_submit_ex(fpng_amd_encoder *e, const fpng_amd_image_ex *images, uint32_t n, uint32_t flags, uint64_t *ticket)
 {
-    if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    return submit(e, nullptr, images, n, flags, ticket);
+    return submit(e, {FPNG_AMD_DESC_EX, images, n}, flags, ticket);
 }
 
 int fpng_amd_encode_submit_planar(fpng_amd_encoder *e, const fpng_amd_image_planar *images, uint32_t n, uint32_t flags, uint64_t *ticket)
 {
-    if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    return submit(e, nullptr, nullptr, n, flags, ticket, images);
+    return submit(e, {FPNG_AMD_DESC_PLANAR, images, n}, flags, ticket);
 }
 
 int fpng_amd_encode_submit_planar_float(fpng_amd_encoder *e, const fpng_amd_image_planar *images, uint32_t n, const fpng_amd_float_format *fmt, uint32_t flags,
                                         uint64_t *ticket)
 {
-    if (!images || !fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch or format");
-    return submit(e, nullptr, nullptr, n, flags, ticket, images, fmt);
+    if (!images || !fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch or format"); // (this call's own words for the two)
+    return submit(e, {FPNG_AMD_DESC_PLANAR_FLOAT, images, n, fmt}, flags, ticket);
 }
 
 // what a packed submission asks of its fpng_amd_pack (fpng_amd_encode_submit_packed, fpng_amd_encode_submit_renditions)
@@ -1090,24 +1100,18 @@ int fpng_amd_encode_submit_renditions(fpng_amd_encoder *e, uint32_t desc_kind, c
     // everything is judged here, before the encoder is looked at: nothing is launched, no ticket handed out
     int rc;
     if (pack && (rc = check_pack(pack))) return rc;
-    std::vector<RenditionSource> src;
     RenditionStage st;
-    if ((rc = rendition_sources(desc_kind, images, n_images, fmt, src, st.plan.fq)) ||
-        (rc = plan_renditions(src, renditions, n_renditions, pack ? kRenditionPacked : kRenditionOuts, st.plan)))
-        return rc;
+    if ((rc = plan_renditions({desc_kind, images, n_images, fmt}, renditions, n_renditions, pack ? kRenditionPacked : kRenditionOuts, st.plan))) return rc;
     st.renditions = renditions, st.n = n_renditions;
-    return submit(e, nullptr, nullptr, 0, flags, ticket, nullptr, nullptr, pack, &st);
+    st.images.resize(n_renditions);
+    return submit(e, {FPNG_AMD_DESC_IMAGE, st.images.data(), n_renditions}, flags, ticket, pack, &st);
 }
 
 int fpng_amd_renditions_plan(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt, const fpng_amd_rendition *renditions,
                              uint32_t n_renditions, int packed, uint64_t *scratch_bytes, uint64_t *offsets)
 {
-    std::vector<RenditionSource> src;
     RenditionPlan plan;
-    int rc;
-    if ((rc = rendition_sources(desc_kind, images, n_images, fmt, src, plan.fq)) ||
-        (rc = plan_renditions(src, renditions, n_renditions, packed ? kRenditionPacked : kRenditionOuts, plan)))
-        return rc;
+    if (int rc = plan_renditions({desc_kind, images, n_images, fmt}, renditions, n_renditions, packed ? kRenditionPacked : kRenditionOuts, plan)) return rc;
     if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
     if (offsets) std::copy(plan.dst_off.begin(), plan.dst_off.end(), offsets);
     return FPNG_AMD_OK;
@@ -1118,11 +1122,9 @@ int fpng_amd_renditions_plan(uint32_t desc_kind, const void *images, uint32_t n_
 int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt, const fpng_amd_rendition *rendition,
                               uint8_t *out, size_t out_cap)
 {
-    std::vector<RenditionSource> src;
     RenditionPlan plan;
-    int rc;
     if (!out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null out");
-    if ((rc = rendition_sources(desc_kind, images, n_images, fmt, src, plan.fq)) || (rc = plan_renditions(src, rendition, rendition ? 1u : 0u, kRenditionNoOuts, plan))) return rc;
+    if (int rc = plan_renditions({desc_kind, images, n_images, fmt}, rendition, rendition ? 1u : 0u, kRenditionNoOuts, plan)) return rc;
     EncResize r = plan.recs[0];
     r.nearest = plan.nearest.empty() ? nullptr : plan.nearest.data();
     const size_t w = r.w, h = r.h, C = r.chans;
@@ -1162,15 +1164,11 @@ int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n
 int fpng_amd_encode_submit_packed(fpng_amd_encoder *e, uint32_t desc_kind, const void *images, uint32_t n, const fpng_amd_float_format *fmt,
                                   uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket)
 {
-    // everything about the arena is checked here, before the encoder is looked at: nothing is launched, no ticket handed out
-    if (desc_kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
-    if (int rc = check_pack(pack)) return rc;
-    if ((desc_kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (fmt != nullptr))
-        return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
-    if (!images) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
-    if (desc_kind == FPNG_AMD_DESC_IMAGE) return submit(e, (const fpng_amd_image *)images, nullptr, n, flags, ticket, nullptr, nullptr, pack);
-    if (desc_kind == FPNG_AMD_DESC_EX) return submit(e, nullptr, (const fpng_amd_image_ex *)images, n, flags, ticket, nullptr, nullptr, pack);
-    return submit(e, nullptr, nullptr, n, flags, ticket, (const fpng_amd_image_planar *)images, fmt, pack);
+    // the batch and the arena are judged here, before the encoder is looked at: nothing is launched, no ticket handed out
+    const SourceBatch batch = {desc_kind, images, n, fmt};
+    int rc;
+    if ((rc = check_batch(batch)) || (rc = check_pack(pack))) return rc;
+    return submit(e, batch, flags, ticket, pack);
 }
 
 int fpng_amd_encode_wait_packed(fpng_amd_encoder *e, uint64_t ticket, fpng_amd_packed_result *results, uint32_t n, uint64_t *total)
@@ -1246,7 +1244,7 @@ int fpng_amd_quantize_float(const void *src, uint32_t dtype, float scale, float 
 
 int fpng_amd_encode_batch_async(fpng_amd_encoder *e, const fpng_amd_image *images, uint32_t n, uint32_t flags)
 {
-    return submit(e, images, nullptr, n, flags, nullptr);
+    return submit(e, {FPNG_AMD_DESC_IMAGE, images, n}, flags, /*ticket_out=*/nullptr);
 }
 
 int fpng_amd_encode_query(fpng_amd_encoder *e, uint64_t ticket)
@@ -1489,7 +1487,7 @@ static int host_batch_ring(fpng_amd_encoder *e, const fpng_amd_host_image *imgs,
         uint64_t t = 0;
         {
             std::lock_guard<std::mutex> lk(emu);
-            if ((rc = submit(e, &im, nullptr, 1, flags, &t))) failed = rc;
+            if ((rc = submit(e, {FPNG_AMD_DESC_IMAGE, &im, 1}, flags, &t))) failed = rc;
         }
         {
             std::lock_guard<std::mutex> lk(mu);
@@ -1561,8 +1559,7 @@ static void band_job(fpng_amd_encoder *e, const fpng_amd_band *b, bool two_pass,
     j.is_first = b->y0 == 0;
     j.is_last = b->y1 == b->h_total;
     j.bit_bias = (int64_t)kPngHeaderBytes * 8;
-    const uint64_t bits_per_byte = two_pass ? 12u : g_1pass_bits_per_byte[b->num_chans];
-    j.local_stride = (uint32_t)(((((uint64_t)j.bpl + 1) * bits_per_byte + 64 + 31) / 32 + 4 + 31) & ~31ull); // whole 128-byte lines
+    j.local_stride = local_stride(j.bpl, b->num_chans, two_pass);
     j.local_base = kLocalFrontPad;
     j.table = two_pass ? e->sc[0].d_dyn.p : g_dev[e->device].one_pass[b->num_chans];
 }

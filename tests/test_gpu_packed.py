@@ -248,6 +248,42 @@ def test_all_four_descriptor_kinds(enc, contents, expected, flags):
         _check(arena, pat, recs, total, files, sizes, 64, 16, cap, f"kind {kind} flags {flags}")
 
 
+@pytest.mark.parametrize("flags", [0, 1, 2])
+def test_single_job_submissions_of_every_kind(enc, contents, expected, flags):
+    """n = 1 through every submit method, one after the other: the plain kind's record travels in the kernel arguments, every other
+    kind's is uploaded, and each kind has kernels of its own -- every file is the reference's for the pixels, and the tickets are
+    consecutive.  The rendition is the whole image at its own size, so its pixels are the source's."""
+    import torch
+    import fpng_amd
+    tickets = []
+    for img in (contents[(63, 5, 3)], _content(7, 16, 3, 4)):
+        h, w, c = img.shape
+        want = expected(img, flags)
+        dev = torch.from_numpy(img).cuda()
+        swapped = dev[..., [2, 1, 0, 3][:c]].contiguous()  # B,G,R[,A]
+        chw = dev.permute(2, 0, 1).contiguous()
+        as_float = chw.to(torch.float32) / 255.0  # (rint(fl(b / 255) * 255) is b)
+        arena, _ = _arena(fpng_amd.pack_capacity([(w, h, c)]), 16)
+        doors = [("submit", lambda o: enc.submit([dev], [o], flags)),
+                 ("submit_ex", lambda o: enc.submit_ex([swapped], [o], flags, order="bgr")),
+                 ("submit_planar", lambda o: enc.submit_planar([chw], [o], flags)),
+                 ("submit_float", lambda o: enc.submit_float([as_float], [o], flags)),
+                 ("submit_packed", lambda o: enc.submit_packed([dev], arena[:arena.numel() - 4096], flags=flags)),
+                 ("submit_renditions", lambda o: enc.submit_renditions([dev], [fpng_amd.rendition(0, (w, h))], outs=[o], flags=flags))]
+        for name, door in doors:
+            out = torch.zeros(fpng_amd.max_encoded_size(w, h, c) + 64, dtype=torch.uint8, device="cuda")
+            assert door(out) == 1
+            tickets.append(enc.last_ticket)
+            if name == "submit_packed":
+                ((off, size, mode, status),), _ = enc.wait_packed(enc.last_ticket, 1)
+                out = arena[off:]
+            else:
+                ((size, mode, status),) = enc.wait(enc.last_ticket, 1)
+            assert status == 0 and mode == (1 if flags == 2 else mode), (name, status, mode)
+            _same(bytes(out[:size].cpu().numpy()), want, f"{name}, n = 1, {w} x {h} x {c}, flags {flags}")
+    assert tickets == list(range(tickets[0], tickets[0] + len(tickets))), tickets
+
+
 def test_ordering(enc, contents, expected):
     import torch
     import fpng_amd

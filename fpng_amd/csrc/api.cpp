@@ -468,14 +468,7 @@ struct Submission {
     uint32_t n = 0, max_rows = 0, max_crc_blocks = 0;
     uint64_t total_rows = 0;
     uint64_t local_dwords = kLocalFrontPad; // scratch for the rows' local streams (assemble_kernel may read up to four dwords in front of a stream)
-    uint32_t chan_mask = 0;    // bit 0: 3-channel jobs present, bit 1: 4-channel jobs
-    // FPNG_AMD_DESC_* of the batch, which names the kernel family that reads its pixels: _IMAGE the plain kernels, _EX the *_ex ones
-    // (the jobs carry a source layout), _PLANAR the *_planar ones (chan_mask says which), _PLANAR_FLOAT the *_planar_float ones of float_dtype
-    uint32_t kind = FPNG_AMD_DESC_IMAGE;
-    uint32_t float_dtype = 0;
-    FloatQuant fq = {};
-    uint32_t layout_mask = 0;  // (_EX) bit 0: 3-byte sources, bit 1: 4-byte sources with 4 channels, bit 2: 4-byte sources with 3
-    uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
+    SourceForms src; // what names the kernels that read the batch's pixels (kernels.h)
 };
 
 int mark(fpng_amd_encoder *e, hipStream_t s, uint32_t idx)
@@ -658,9 +651,10 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     const bool two_pass = (flags & FPNG_AMD_ENCODE_SLOWER) && !force_stored;
     sub = Submission();
     sub.n = n;
-    sub.kind = b.kind;
-    if (b.fmt && (rc = check_float_format(b.fmt, sub.fq))) return rc;
-    sub.float_dtype = b.fmt ? b.fmt->dtype : 0;
+    sub.src.kind = b.kind;
+    if (b.fmt && (rc = check_float_format(b.fmt, sub.src.fq))) return rc;
+    sub.src.dtype = b.fmt ? b.fmt->dtype : 0;
+    uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
     for (uint32_t i = 0; i < n; i++) {
         Source im;
         if ((rc = read_source(b, i, im))) return rc;
@@ -688,15 +682,14 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
         make_png_header(j.png_header, im.w, im.h, im.chans);
         j.local_stride = local_stride(j.bpl, im.chans, two_pass);
         j.local_base = sub.local_dwords;
-        sub.chan_mask |= (im.chans == 3) ? 1u : 2u;
         if (b.kind != FPNG_AMD_DESC_IMAGE) { // the source layout the kind's kernels read (the plain kernels know theirs: the fields stay 0)
             j.pitch = im.pitch;
             j.plane_pitch = im.plane_pitch;
             j.sel = im.sel;
             j.src_bytes = b.fmt ? kFloatLayout + b.fmt->dtype : im.px_bytes;
         }
-        if (b.kind == FPNG_AMD_DESC_EX) sub.layout_mask |= im.px_bytes == 3 ? 1u : (im.chans == 4 ? 2u : 4u);
-        if (im.chans == 4) sub.px4 += (uint64_t)im.w * im.h, sub.px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
+        sub.src.mask |= im.chans == 4 ? 2u : (b.kind == FPNG_AMD_DESC_EX && im.px_bytes == 4 ? 4u : 1u);
+        if (im.chans == 4) px4 += (uint64_t)im.w * im.h, px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
         const uint64_t units = im.h; // records of the job: one per row
         sub.local_dwords += (uint64_t)j.local_stride * units;
         if (sub.total_rows + units > 0xFFFFFFFFull) return fail(FPNG_AMD_ERR_UNSUPPORTED, "too many rows in one batch");
@@ -704,6 +697,7 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
         sub.max_rows = std::max(sub.max_rows, im.h);
         sub.max_crc_blocks = std::max(sub.max_crc_blocks, j.crc_blocks);
     }
+    sub.src.wide4 = 2 * px4_wide >= px4;
     if ((rc = sc.d_jobs.ensure(n))) return rc;
     if ((rc = sc.d_rows.ensure(sub.total_rows))) return rc;
     if ((rc = sc.d_row_off.ensure(sub.total_rows))) return rc;
@@ -936,7 +930,7 @@ int submit(fpng_amd_encoder *e, const SourceBatch &batch, uint32_t flags, uint64
     // 7 us MORE per chain: every kernel's first touch of the record goes over PCIe.)
     // One image: its record travels in the arguments of the chain's first kernel, which leaves it in d_jobs for the others
     // (encode_rows_first_kernel): no blit kernel + dispatch gap in front of the chain.
-    const bool job_in_args = n == 1 && !force_stored && sub.kind == FPNG_AMD_DESC_IMAGE; // (the *_first kernels have no layout forms)
+    const bool job_in_args = n == 1 && !force_stored && sub.src.kind == FPNG_AMD_DESC_IMAGE; // (the *_first kernels read packed pixels only)
     const Job *d_jobs = sc.d_jobs.p;
     if (!job_in_args) HIP_TRY(hipMemcpyAsync(sc.d_jobs.p, slot.jobs.p, n * sizeof(Job), hipMemcpyHostToDevice, s));
     if ((rc = mark(e, s, 0))) return rc;
@@ -956,12 +950,7 @@ int submit(fpng_amd_encoder *e, const SourceBatch &batch, uint32_t flags, uint64
         if (job_in_args)
             launch_hist_first(s, slot.jobs.p[0], sc.d_jobs.p, sc.d_hist.p);
         else
-            switch (sub.kind) {
-            case FPNG_AMD_DESC_PLANAR_FLOAT: launch_hist_planar_float(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p, sub.float_dtype, sub.fq); break;
-            case FPNG_AMD_DESC_PLANAR: launch_hist_planar(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p); break;
-            case FPNG_AMD_DESC_EX: launch_hist_ex(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p); break;
-            default: launch_hist(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p);
-            }
+            launch_hist(s, sc.d_jobs.p, n, sub.max_rows, sc.d_hist.p, sub.src);
         if ((rc = mark(e, s, ++ph))) return rc;
         launch_build_dynamic(s, sc.d_jobs.p, n, sc.d_hist.p, sc.d_dyn.p, rezero);
         if (rezero) sc.hist_zero = n_counters;
@@ -986,16 +975,7 @@ int submit(fpng_amd_encoder *e, const SourceBatch &batch, uint32_t flags, uint64
     if (job_in_args)
         launch_encode_rows_first(s, two_pass ? slot.jobs2.p[0] : slot.jobs.p[0], sc.d_jobs.p, sc.d_rows.p, sc.d_states.p, sc.d_local.p);
     else if (!force_stored)
-        switch (sub.kind) {
-        case FPNG_AMD_DESC_PLANAR_FLOAT:
-            launch_encode_rows_planar_float(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, sub.float_dtype, sub.fq);
-            break;
-        case FPNG_AMD_DESC_PLANAR: launch_encode_rows_planar(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p); break;
-        case FPNG_AMD_DESC_EX:
-            launch_encode_rows_ex(s, d_jobs, n, sub.max_rows, sub.layout_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
-            break;
-        default: launch_encode_rows(s, d_jobs, n, sub.max_rows, sub.chan_mask, sc.d_rows.p, sc.d_states.p, sc.d_local.p, 2 * sub.px4_wide >= sub.px4);
-        }
+        launch_encode_rows(s, d_jobs, n, sub.max_rows, sc.d_rows.p, sc.d_states.p, sc.d_local.p, sub.src);
     if ((rc = mark(e, s, ++ph))) return rc;
     if (stagger) { // (only staggered walks wait for it)
         // ... and only a submission that follows while this one runs: with every other lane idle (one frame at a time) the marker
@@ -1022,15 +1002,7 @@ int submit(fpng_amd_encoder *e, const SourceBatch &batch, uint32_t flags, uint64
         launch_scan(s, d_jobs, n, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p);
     if ((rc = mark(e, s, ++ph))) return rc;
     uint32_t *adler_parts = sc.d_partials.p + (size_t)n * sub.max_crc_blocks;
-    switch (sub.kind) {
-    case FPNG_AMD_DESC_PLANAR_FLOAT:
-        launch_assemble_planar_float(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts,
-                                     sub.float_dtype, sub.fq);
-        break;
-    case FPNG_AMD_DESC_PLANAR: launch_assemble_planar(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts); break;
-    case FPNG_AMD_DESC_EX: launch_assemble_ex(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts); break;
-    default: launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts);
-    }
+    launch_assemble(s, d_jobs, n, sub.max_crc_blocks, sc.d_states.p, sc.d_row_off.p, sc.d_local.p, dt.crc, sc.d_partials.p, adler_parts, sub.src);
     if ((rc = mark(e, s, ++ph))) return rc;
     launch_finalize(s, d_jobs, n, sub.max_crc_blocks, sc.d_rows.p, sc.d_states.p, dt.crc, sc.d_partials.p, adler_parts, slot.results.p);
     if ((rc = mark(e, s, ++ph))) return rc;
@@ -1611,7 +1583,7 @@ int fpng_amd_band_encode(fpng_amd_encoder *e, const fpng_amd_band *b, uint32_t f
         launch_build_dynamic(s, sc.d_jobs.p + 1, 1, d_hist288, sc.d_dyn.p, 0);
     }
     HIP_TRY(hipMemcpyAsync(sc.d_jobs.p, &j, sizeof(Job), hipMemcpyHostToDevice, s));
-    launch_encode_rows(s, sc.d_jobs.p, 1, j.nrows, b->num_chans == 3 ? 1u : 2u, sc.d_rows.p, sc.d_states.p, sc.d_local.p, b->w >= kWideRowPixels);
+    launch_encode_rows(s, sc.d_jobs.p, 1, j.nrows, sc.d_rows.p, sc.d_states.p, sc.d_local.p, plain_source(b->num_chans, b->w));
     launch_scan(s, sc.d_jobs.p, 1, sc.d_rows.p, sc.d_row_off.p, sc.d_states.p); // band count: sums only
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(e->h_states.p, sc.d_states.p, sizeof(JobState), hipMemcpyDeviceToHost, s));

@@ -1,5 +1,6 @@
 // kernels.h -- host/device shared structures and kernel launchers (internal).
 #pragma once
+#include "fpng_amd.h"
 #include "format.h"
 #include "pack.h"
 #include "crc_geometry.h"
@@ -13,6 +14,16 @@ namespace fpng_amd {
 constexpr uint32_t kCrcRangeBytes = 1u << 16;
 constexpr uint32_t kCrcRowBytes = 4096;
 static_assert(kCrcRangeBytes == 1u << kCrcRangeLog2Max && kCrcRowBytes == 1u << kCrcRangeLog2Min, "crc_geometry.h: range sizes from one block row to kCrcRangeBytes");
+
+// The form of a job's source pixels: ONE numbering for Job::src_bytes and for the template argument of everything that reads pixels
+// (hist_kernel, encode_rows_kernel, stored_kernel and what they call).  kFormEx3 / kFormEx4 are the bytes of an _ex source pixel.
+constexpr int kFormPacked = 0; // fpng_amd_encode_submit: R,G,B[,A] bytes, rows bpl apart (the jobs' layout fields stay 0)
+constexpr int kFormPlanar = 1; // fpng_amd_encode_submit_planar
+constexpr int kFormEx = 2;     // an _ex job of either pixel size, read from the job at run time (never in Job::src_bytes; the row walk has none)
+constexpr int kFormEx3 = 3, kFormEx4 = 4; // fpng_amd_encode_submit_ex
+constexpr int kFloatLayout = 16; // + dtype (FPNG_AMD_F32 / _F16 / _BF16): fpng_amd_encode_submit_planar_float
+constexpr bool is_float_layout(int form) { return form >= kFloatLayout; }
+constexpr bool is_planar_layout(int form) { return form == kFormPlanar || is_float_layout(form); }
 
 // One unit of work: a whole image, or a band of rows of one image (multi-GPU).
 struct Job {
@@ -33,13 +44,13 @@ struct Job {
     uint64_t local_base;      // dwords
     uint32_t local_stride;    // dwords per row (worst-case token bits of a row + slack)
     uint32_t local_pad;
-    // source layout of fpng_amd_encode_submit_ex jobs (zero elsewhere; read only by the *_ex kernels): row r of the job starts at
+    // source layout of fpng_amd_encode_submit_ex jobs (zero elsewhere; read only by the kernels of their form): row r of the job starts at
     // rows + r * pitch, a pixel is src_bytes bytes, and v_perm_b32 with selector `sel` turns a source pixel's dword into the PNG's
     // R,G,B[,A] bytes (0x0c = a zero byte).  These words were reserved before: the record stays 224 bytes and png_header where it
     // was, so the other kernels' code is, instruction for instruction, the same (tools/isa_diff.py)
     int64_t pitch;            // signed bytes from one row to the next
-    uint32_t src_bytes;       // 3 or 4; 1 = a planar job (fpng_amd_encode_submit_planar): a byte per pixel and plane;
-                              // kFloatLayout + dtype = a planar job of floats (fpng_amd_encode_submit_planar_float): pitches in bytes of the float source
+    uint32_t src_bytes;       // the job's source form (kForm*, above):kFormEx3 / kFormEx4 = the bytes of a source pixel; kFormPlanar: a byte per pixel
+                              // and plane; kFloatLayout + dtype: planes of floats, pitches in bytes of the float source
     uint32_t sel;
     int64_t plane_pitch;      // planar jobs: signed bytes from one channel's plane to the next (R -> G -> B [-> A]); `rows` is the R plane's top row
     uint8_t png_header[60];   // 58 bytes used (reference fpng.cpp:1767-1791), IDAT length patched on device
@@ -66,7 +77,7 @@ struct JobState {
 };
 
 // JobState::status: a stored outcome whose 58 + zlib_size exceeds UINT32_MAX (FPNG_AMD_STATUS_STORED_TOO_LARGE): scan_kernel decides
-// it, and assemble / stored_ex / finalize then write nothing of that file.  (kStatusArenaFull = 2, packed submissions: pack.h)
+// it, and assemble / stored_kernel / finalize then write nothing of that file.  (kStatusArenaFull = 2, packed submissions: pack.h)
 constexpr uint32_t kStatusStoredTooLarge = 1;
 // JobState::zlib_size of a file of a packed submission that is refused (by pack_place_kernel, or by the scan before it).  assemble_kernel has no look at the status on its way to a compressed file's
 // rows (before packed submissions only stored files could be refused), but it leaves -- as the stored forms and crc_kernel do -- when
@@ -94,12 +105,34 @@ struct CrcDeviceTables {
 };
 void build_crc_device_tables(CrcDeviceTables *t);
 
-void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist);
+// The sources of one submission, as far as the launchers of the three stages that read pixels (hist, encode_rows, assemble's stored
+// files) need them to pick their kernels.  Only those kernels have a form per kind; the rest of the chain is shared as it is.
+struct FloatQuant {
+    float scale[4], bias[4]; // per file channel R, G, B, A
+};
+struct SourceForms {
+    // FPNG_AMD_DESC_* of the batch.  _IMAGE: kFormPacked jobs; _EX: jobs with a source layout (Job::pitch / src_bytes / sel);
+    // _PLANAR: planar jobs (Job::plane_pitch); _PLANAR_FLOAT: planar jobs whose planes hold elements of `dtype`, which the kernels turn
+    // into bytes as they load them (quantize.h) -- fq's constants are the submission's and travel in the kernel arguments: the Job record is full
+    uint32_t kind = FPNG_AMD_DESC_IMAGE;
+    uint32_t dtype = 0; // FPNG_AMD_F32 / _F16 / _BF16
+    // one row kernel instantiation per bit.  _EX: bit 0 = 3-byte sources, bit 1 = 4-byte sources with 4 channels, bit 2 = 4-byte sources
+    // with 3; every other kind: bit 0 = the batch has 3-channel jobs, bit 1 = 4-channel jobs
+    uint32_t mask = 0;
+    // _IMAGE, _EX: the 4-channel jobs' pixels lie mostly in rows of kWideRowPixels and more (their walk then runs with seven waves per SIMD instead of eight: kernels.hip)
+    bool wide4 = false;
+    FloatQuant fq = {};
+};
+constexpr uint32_t kWideRowPixels = 3584; // (same-box A/B: 3840-pixel rows gain with six waves, 3072-pixel rows lose 1 % in 1-pass)
+// one plain image or row band of `chans` channels and rows of w pixels
+inline SourceForms plain_source(uint32_t chans, uint32_t w) { return {FPNG_AMD_DESC_IMAGE, 0, chans == 3 ? 1u : 2u, w >= kWideRowPixels, {}}; }
+// (src defaults to plain images: what the stages that look at no mask need to know of row bands and training sets)
+void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, SourceForms src = {});
 void launch_scan(hipStream_t s, const Job *jobs, uint32_t n_jobs, const RowInfo *rows, uint64_t *row_off, JobState *states);
 // fpng_amd_encode_submit_packed: the scan without the heads (the jobs have no `out` yet), then pack_place_kernel -- one workgroup:
 // the rule of pack.h over the sizes the scan decided; it patches jobs[i].out / out_cap and refuses (JobState::status =
 // kStatusArenaFull, JobState::zlib_size = kZlibSizeNoFile) what finds no room -- and pack_heads_kernel, which writes the heads of
-// the placed files.  Three launches.  assemble / stored_* / finalize behind them are the ones every submission runs.
+// the placed files.  Three launches.  assemble / stored_kernel / finalize behind them are the ones every submission runs.
 struct PackArgs {
     uint8_t *arena;
     uint64_t cap;
@@ -108,49 +141,19 @@ struct PackArgs {
     uint64_t *h_offsets;  // pinned host memory (device-visible), n + 2 words: the files' offsets, total, files placed
 };
 void launch_scan_packed(hipStream_t s, Job *jobs, uint32_t n_jobs, const RowInfo *rows, uint64_t *row_off, JobState *states, const PackArgs &pa);
-// chan_mask: bit 0 = the batch has 3-channel jobs, bit 1 = 4-channel jobs (one kernel instantiation each)
-// wide4: the 4-channel jobs' pixels lie mostly in rows of kWideRowPixels and more (their walk then runs with seven waves per SIMD instead of eight: kernels.hip)
-constexpr uint32_t kWideRowPixels = 3584; // (same-box A/B: 3840-pixel rows gain with six waves, 3072-pixel rows lose 1 % in 1-pass)
-void launch_encode_rows(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                        JobState *states, uint32_t *local, bool wide4 = false);
+void launch_encode_rows(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, RowInfo *rows, JobState *states, uint32_t *local, SourceForms src);
 // one job per submission: the record travels in the kernel arguments and is left at d_job for the kernels that follow
 void launch_encode_rows_first(hipStream_t s, const Job &job, Job *d_job, RowInfo *rows, JobState *states, uint32_t *local);
 void launch_hist_first(hipStream_t s, const Job &job, Job *d_job, uint32_t *hist);
 // adler_parts (whole images; two words per CRC range and job, or NULL for row bands): where the workgroups of an image that
-// fell back to stored blocks leave their range's share of the Adler-32
+// fell back to stored blocks leave their range's share of the Adler-32.  Every kind but _IMAGE: stored_kernel of the kind's form writes
+// the stored files first, and assemble_kernel then takes their CRC in place
 void launch_assemble(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                     const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
+                     const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts, SourceForms src = {});
 void launch_crc(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, const JobState *states,
                 const CrcDeviceTables *tabs, uint32_t *partials);
 void launch_finalize(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, const RowInfo *rows,
                      JobState *states, const CrcDeviceTables *tabs, const uint32_t *partials, const uint32_t *adler_parts, Result *results);
-// fpng_amd_encode_submit_ex: the same chain for jobs with a source layout (Job::pitch / src_bytes / sel).  Only the kernels that read
-// pixels have layout forms.  layout_mask: bit 0 = 3-byte sources, bit 1 = 4-byte sources with 4 channels, bit 2 = 4-byte sources with 3
-void launch_hist_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist);
-void launch_encode_rows_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t layout_mask, RowInfo *rows,
-                           JobState *states, uint32_t *local, bool wide4);
-void launch_assemble_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                        const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
-// fpng_amd_encode_submit_planar: the same chain again for planar jobs (Job::plane_pitch, src_bytes = 1), kernels of their own.
-// chan_mask as launch_encode_rows
-void launch_hist_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist);
-void launch_encode_rows_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                               JobState *states, uint32_t *local);
-void launch_assemble_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                            const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts);
-// fpng_amd_encode_submit_planar_float: planar jobs whose planes hold f32 / f16 / bf16 elements (dtype: FPNG_AMD_F32 / _F16 / _BF16).
-// The kernels that read pixels turn every element into its byte as they load it (quantize.h); the constants are the submission's
-// and travel in the kernel arguments -- the Job record is full.  Job::src_bytes = kFloatLayout + dtype.
-constexpr uint32_t kFloatLayout = 16;
-struct FloatQuant {
-    float scale[4], bias[4]; // per file channel R, G, B, A
-};
-void launch_hist_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, uint32_t dtype, const FloatQuant &fq);
-void launch_encode_rows_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                                     JobState *states, uint32_t *local, uint32_t dtype, const FloatQuant &fq);
-void launch_assemble_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                                  const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts,
-                                  uint32_t dtype, const FloatQuant &fq);
 // table training: sums[0..288) += the 16-bit adjusted histogram of every image (hist_all: 288 counters per image)
 void launch_train_accumulate(hipStream_t s, const uint32_t *hist_all, uint32_t n_images, uint64_t *sums);
 // dst[0..16) |= src[0..16): the 16-byte piece two neighbouring band windows share (each holds zeros where the other's bits are)

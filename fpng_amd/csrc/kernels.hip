@@ -23,7 +23,7 @@
 // fpng_amd_wrap_png() for callers that do not hand over the bands' CRC partials.
 //
 // fpng_amd_encode_submit_ex jobs (strided / bottom-up / BGR(A) / padded-alpha sources) take the same chain; the kernels that read
-// pixels have layout forms for them (hist_ex_kernel, encode_rows_ex_kernel, stored_ex_kernel), the others are shared as they are.
+// pixels are templates over the source form (kernels.h: hist_kernel, encode_rows_kernel, stored_kernel), the others are shared as they are.
 //
 // Integer / byte work throughout, bounded by VALU issue and HBM traffic: no MFMA.
 #include "kernels.h"
@@ -56,7 +56,7 @@ constexpr int kScanBlock = kWave * kScanWaves;
 constexpr int kHistWaves = 8;              // hist_kernel: one LDS histogram (36 KiB) and one round of global atomics per block
 constexpr int kHistBlock = kWave * kHistWaves;
 constexpr int kRowBlock = kWave * kRowWaves;
-constexpr uint32_t kStoredExBlocks = 64; // stored_ex_kernel: workgroups per image
+constexpr uint32_t kStoredExBlocks = 64; // stored_kernel: workgroups per image
 #ifndef FPNG_STAGE_DWORDS
 #define FPNG_STAGE_DWORDS 1024
 #endif
@@ -72,7 +72,7 @@ constexpr uint32_t kStoredExBlocks = 64; // stored_ex_kernel: workgroups per ima
 #ifndef FPNG_ROWS_WPE4
 #define FPNG_ROWS_WPE4 7
 #endif
-// the planar walks (encode_rows_planar_kernel): a super-window's source dwords are two per plane and row instead of the packed
+// the planar walks (encode_rows_kernel<C, WPE, kFormPlanar>): a super-window's source dwords are two per plane and row instead of the packed
 // walk's four per row: 65 / 77 vector registers (3 / 4 channels) and no scratch at six / five waves per SIMD, the setting the timings
 // of profiles/planar_timing.txt were taken with.  Seven / six compile to the same register counts, also without scratch, and have
 // not been timed; eight / seven spill in the super-window loop (profiles/planar_kernel_resources.txt)
@@ -82,7 +82,7 @@ constexpr uint32_t kStoredExBlocks = 64; // stored_ex_kernel: workgroups per ima
 #ifndef FPNG_ROWS_WPE_PLANAR4
 #define FPNG_ROWS_WPE_PLANAR4 5
 #endif
-// the float walks (encode_rows_planar_float_kernel): the planar walk with twice (f32) or one and a half times (f16 / bf16) the source
+// the float walks (encode_rows_kernel<C, WPE, kFloatLayout + dtype, FloatQuant>): the planar walk with twice (f32) or one and a half times (f16 / bf16) the source
 // dwords of a super-window in flight, converted to the planar walk's bytes as they arrive.  Per instantiation the most waves per
 // SIMD without scratch (profiles/float_encode_kernel_resources.txt): 3 channels 79 (f32) / 73 (f16, bf16) vector registers at six,
 // 4 channels 89 (f16, bf16) at five and 98 (f32) at four -- f32 at five spills one register in the super-window loop.  Not timed
@@ -324,11 +324,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, ui
     return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)p, 0, (int)uniform(bytes), 0x00020000);
 }
 
-// L: source layout.  0 = packed R,G,B[,A] (fpng_amd_encode_submit), else the bytes per source pixel of an _ex job (3 or 4): the loads
+// L: source form (kernels.h).  kFormPacked = packed R,G,B[,A] (fpng_amd_encode_submit), kFormEx3 / kFormEx4 = the bytes per source pixel of an _ex job: the loads
 // follow the source pixel, and one v_perm_b32 with the job's wave-uniform selector turns the FILTERED pixel into the PNG's byte order
 // (the filter is bytewise, so permuting before or after it is the same; a selector byte 0x0c zeroes an ignored X byte).  Everything
 // downstream -- literal tokens, the RLE compare, the histogram, the Adler sums -- sees only permuted values.
-template <int C, int L = 0> struct RowWindows {
+template <int C, int L = kFormPacked> struct RowWindows {
     static constexpr int SB = L ? L : C; // source bytes per pixel
     __amdgpu_buffer_rsrc_t cur, up;
     uint32_t voff; // per-lane byte offset of its pixel inside window 0 of the row (RGB: aligned down)
@@ -399,13 +399,13 @@ template <int C, int L = 0> struct RowWindows {
     __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
 };
 
-// L = 1: a PLANAR source (fpng_amd_encode_submit_planar) -- one plane of w-byte rows per channel, Job::plane_pitch bytes apart, a
+// L = kFormPlanar: a PLANAR source (fpng_amd_encode_submit_planar) -- one plane of w-byte rows per channel, Job::plane_pitch bytes apart, a
 // byte per pixel and plane.  One buffer resource per plane and row (all wave-uniform), each with its base aligned down to a dword
 // and its own byte phase, as the 3-byte path does: rows and planes start at any byte.  64-pixel windows load a byte per plane and
 // lane and pack the pixel; the super-windows load the dwords that hold the lane's four bytes of every plane (walk_row).  The
 // resources end with the dword the row's last byte lies in, so lanes past the row end may see up to three bytes that are not the
 // row's: the walk masks them, as it does for packed 3-byte pixels.
-template <int C> struct RowWindows<C, 1> {
+template <int C> struct RowWindows<C, kFormPlanar> {
     static constexpr int SB = 1;
     __amdgpu_buffer_rsrc_t cur[C], up[C];
     uint32_t phase[C], up_phase[C];
@@ -454,14 +454,12 @@ template <int C> struct RowWindows<C, 1> {
 template <int C> struct PlaneDwords {
     uint32_t lo[C], hi[C];
 };
-// L = kFloatLayout + dtype: a planar source of FLOATS (fpng_amd_encode_submit_planar_float) -- RowWindows<C, 1> with elements of four
+// L = kFloatLayout + dtype: a planar source of FLOATS (fpng_amd_encode_submit_planar_float) -- RowWindows<C, kFormPlanar> with elements of four
 // (f32) or two (f16 / bf16) bytes in the place of its bytes.  Every element is turned into its byte (quantize.h) as soon as it is
 // loaded, the row above too (Up subtracts the QUANTISED row), so that filter() and the super-windows' filt hand the walk what the
 // planar layout does.  Elements are aligned to their size only: the resources' bases are aligned down to a dword and a 16-bit row
 // may start two bytes into it (phase 0 or 2; always 0 for f32).  A missing Up row is a zero-sized resource whose loads return 0.0,
 // which does not quantise to 0 with a bias: up_mask clears those bytes.
-constexpr bool is_float_layout(int L) { return L >= (int)kFloatLayout; }
-constexpr bool is_planar_layout(int L) { return L == 1 || is_float_layout(L); }
 template <int C, uint32_t DT> struct FloatRowWindows {
     static constexpr int SB = DT == kF32 ? 4 : 2; // bytes per element
     __amdgpu_buffer_rsrc_t cur[C], up[C];
@@ -514,7 +512,7 @@ template <int C, uint32_t DT> struct FloatRowWindows {
         uint32_t cb[C], ub[C];
 #pragma unroll
         for (int ch = 0; ch < C; ch++) cb[ch] = byte_of(q.c[ch], ch), ub[ch] = byte_of(q.u[ch], ch);
-        return sub_bytes(RowWindows<C, 1>::pack(cb), RowWindows<C, 1>::pack(ub) & up_mask);
+        return sub_bytes(RowWindows<C, kFormPlanar>::pack(cb), RowWindows<C, kFormPlanar>::pack(ub) & up_mask);
     }
     __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
 
@@ -564,7 +562,7 @@ template <int C> __device__ __forceinline__ uint32_t planar_first_pixel(const ui
 
 // what a lane holds of one super-window of a row before it is filtered (walk_row, phase A)
 template <int C, int L, bool = is_float_layout(L)> struct SuperWindowSource {
-    using type = std::conditional_t<L == 1, PlaneDwords<C>, u32x4>;
+    using type = std::conditional_t<L == kFormPlanar, PlaneDwords<C>, u32x4>;
 };
 template <int C, int L> struct SuperWindowSource<C, L, true> {
     using type = typename RowWindows<C, L>::Dwords;
@@ -722,7 +720,7 @@ struct RowResult {
 
 // Walks row r of the job.  L: source layout (RowWindows); rows of an L != 0 job lie job.pitch bytes apart.
 // FQ: nothing, or (float layouts) the submission's FloatQuant
-template <int C, Pass PASS, int L = 0, typename... FQ>
+template <int C, Pass PASS, int L = kFormPacked, typename... FQ>
 __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables &T, uint32_t *hist, uint32_t r, uint32_t lane, EmitSink *sink, const FQ &...fq)
 {
     constexpr bool kFloat = is_float_layout(L), kPlanar = is_planar_layout(L); // (float sources are planar ones: fq has their constants)
@@ -747,7 +745,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
     if (L) px.sel = uniform(job.sel);
     if constexpr (kFloat)
         px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane, fq...);
-    else if constexpr (L == 1)
+    else if constexpr (L == kFormPlanar)
         px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane);
     else
         px.init(row, up_row, L ? w * (uint32_t)SB : bpl, lane);
@@ -941,7 +939,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
                 if constexpr (kFloat) {
                     px.load_dwords(px.cur, voff4, S * kSrcSuperBytes, c4);
                     px.load_dwords(px.up, voff4, S * kSrcSuperBytes, u4);
-                } else if constexpr (L == 1) {
+                } else if constexpr (L == kFormPlanar) {
 #pragma unroll
                     for (int ch = 0; ch < C; ch++) {
                         const u32x2 c2 = __builtin_amdgcn_raw_buffer_load_b64(px.cur[ch], voff4, S * kSrcSuperBytes, 0);
@@ -962,7 +960,7 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
 #pragma unroll
                     for (int ch = 0; ch < C; ch++) fd[ch] = sub_bytes(px.bytes_of(c4, ch, px.phase[ch]), px.bytes_of(u4, ch, px.up_phase[ch]) & px.up_mask);
                     if (C == 3) fd[3] = 0;
-                } else if constexpr (L == 1) {
+                } else if constexpr (L == kFormPlanar) {
 #pragma unroll
                     for (int ch = 0; ch < C; ch++)
                         fd[ch] = sub_bytes(__builtin_amdgcn_alignbyte(c4.hi[ch], c4.lo[ch], px.phase[ch]),
@@ -1219,9 +1217,8 @@ __device__ __forceinline__ const Job &job_of_block(const Job *jobs) { return job
 // hist_kernel (2-pass, pass 1): literal / length-symbol histogram of the whole image
 // (reference fpng.cpp:1021-1084 / :1299-1363).  job.table here is the "symbol" table whose
 // chunk[q] holds (length symbol - 256).
-// EX: 1 = the jobs of fpng_amd_encode_submit_ex (hist_ex_kernel), walked with their source layout; 2 = planar jobs (hist_planar_kernel);
-// kFloatLayout + dtype = planar jobs of floats (hist_planar_float_kernel), fq their constants
-template <int EX = 0, typename... FQ>
+// FORM: the jobs' source form (kernels.h), which the rows are walked with; kFormEx: the _ex jobs of either pixel size.  fq: the constants of float forms
+template <int FORM = kFormPacked, typename... FQ>
 __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const FQ &...fq)
 {
     __shared__ PackedTables T;
@@ -1232,27 +1229,17 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const 
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, r = blockIdx.x * kHistWaves + uniform(threadIdx.x >> 6);
     if (r < job.nrows) {
-        if constexpr (is_float_layout(EX)) {
+        if constexpr (FORM == kFormEx) {
             if (job.c == 4)
-                walk_row<4, Pass::Hist, EX>(job, T, hist, r, lane, nullptr, fq...);
+                walk_row<4, Pass::Hist, kFormEx4>(job, T, hist, r, lane, nullptr);
+            else if (job.src_bytes == kFormEx4)
+                walk_row<3, Pass::Hist, kFormEx4>(job, T, hist, r, lane, nullptr);
             else
-                walk_row<3, Pass::Hist, EX>(job, T, hist, r, lane, nullptr, fq...);
-        } else if (EX == 2) {
-            if (job.c == 4)
-                walk_row<4, Pass::Hist, 1>(job, T, hist, r, lane, nullptr);
-            else
-                walk_row<3, Pass::Hist, 1>(job, T, hist, r, lane, nullptr);
-        } else if (EX) {
-            if (job.c == 4)
-                walk_row<4, Pass::Hist, 4>(job, T, hist, r, lane, nullptr);
-            else if (job.src_bytes == 4)
-                walk_row<3, Pass::Hist, 4>(job, T, hist, r, lane, nullptr);
-            else
-                walk_row<3, Pass::Hist, 3>(job, T, hist, r, lane, nullptr);
+                walk_row<3, Pass::Hist, kFormEx3>(job, T, hist, r, lane, nullptr);
         } else if (job.c == 4)
-            walk_row<4, Pass::Hist>(job, T, hist, r, lane, nullptr);
+            walk_row<4, Pass::Hist, FORM>(job, T, hist, r, lane, nullptr, fq...);
         else
-            walk_row<3, Pass::Hist>(job, T, hist, r, lane, nullptr);
+            walk_row<3, Pass::Hist, FORM>(job, T, hist, r, lane, nullptr, fq...);
         if (lane == 0) hist_add(hist, (job.y0 + r) ? 2 : 0, r); // the row's filter-type literal
     }
     __syncthreads();
@@ -1262,24 +1249,11 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const 
         if (s) atomicAdd(&dst[i], s);
     }
 }
-__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_kernel(const Job *jobs, uint32_t *hist_out)
+// one instantiation per form that is launched; FQ: nothing, or (float forms) FloatQuant, the submission's constants
+template <int FORM, typename... FQ>
+__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_kernel(const Job *jobs, uint32_t *hist_out, const FQ... fq)
 {
-    hist_block(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
-}
-__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_ex_kernel(const Job *jobs, uint32_t *hist_out)
-{
-    hist_block<true>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
-}
-// the jobs of fpng_amd_encode_submit_planar
-__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_planar_kernel(const Job *jobs, uint32_t *hist_out)
-{
-    hist_block<2>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288);
-}
-// the jobs of fpng_amd_encode_submit_planar_float with elements of type DT
-template <uint32_t DT>
-__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_planar_float_kernel(const Job *jobs, uint32_t *hist_out, const FloatQuant fq)
-{
-    hist_block<(int)(kFloatLayout + DT)>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288, fq);
+    hist_block<FORM>(job_of_block(jobs), hist_out + (size_t)blockIdx.y * 288, fq...);
 }
 // (JobArg / the *_first_kernel forms: one image per submission, its job record in the kernel arguments -- see encode_rows_first_kernel)
 struct JobArg {
@@ -1576,8 +1550,9 @@ __global__ __launch_bounds__(kWave) void pack_heads_kernel(const Job *jobs, cons
 // ---------------------------------------------------------------------------------------------
 // One instantiation per channel count (jobs of the other kind leave at once): the 3-channel walk needs far
 // fewer registers than the 4-pixels-per-lane RGBA one and keeps 8 waves per SIMD.
-// L: source layout (RowWindows); an L != 0 instantiation takes the _ex jobs of its channel count and source pixel size.
-template <int C, int L = 0, typename... FQ>
+// L: source form (kernels.h); an instantiation of another form than kFormPacked takes the jobs of its channel count and form (_ex jobs: of
+// its source pixel size -- 3-byte sources give 3 channels; 4-byte ones 4, or 3 with an ignored X byte).
+template <int C, int L = kFormPacked, typename... FQ>
 __device__ __forceinline__ void encode_rows_block(const Job &job, uint32_t by, uint32_t bx, RowInfo *rows_out, JobState *states, uint32_t *local, const FQ &...fq)
 {
     __shared__ PackedTables T;
@@ -1634,43 +1609,15 @@ __device__ __forceinline__ void xcd_block_order(uint32_t &bx, uint32_t &by)
     bx = logical - by * gridDim.x;
 }
 
-template <int C, int WPE>
+// FORM: the jobs' source form; FQ: nothing, or (float forms) FloatQuant -- the submission's constants in the arguments
+template <int C, int WPE, int FORM, typename... FQ>
 __global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_kernel(const Job *jobs, RowInfo *rows_out,
-                                                                                                      JobState *states, uint32_t *local)
+                                                                                                      JobState *states, uint32_t *local,
+                                                                                                      const FQ... fq)
 {
     uint32_t bx, by;
     xcd_block_order(bx, by);
-    encode_rows_block<C>(jobs[by], by, bx, rows_out, states, local);
-}
-// the _ex jobs: source pixels of L bytes (3-byte sources give 3 channels; 4-byte ones 4, or 3 with an ignored X byte)
-template <int C, int WPE, int L>
-__global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_ex_kernel(const Job *jobs, RowInfo *rows_out,
-                                                                                                         JobState *states, uint32_t *local)
-{
-    uint32_t bx, by;
-    xcd_block_order(bx, by);
-    encode_rows_block<C, L>(jobs[by], by, bx, rows_out, states, local);
-}
-
-// the planar jobs (fpng_amd_encode_submit_planar) of C channels: RowWindows<C, 1>
-template <int C, int WPE>
-__global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_planar_kernel(const Job *jobs, RowInfo *rows_out,
-                                                                                                             JobState *states, uint32_t *local)
-{
-    uint32_t bx, by;
-    xcd_block_order(bx, by);
-    encode_rows_block<C, 1>(jobs[by], by, bx, rows_out, states, local);
-}
-
-// the planar jobs of floats (fpng_amd_encode_submit_planar_float) of C channels and element type DT: the constants in the arguments
-template <int C, int WPE, uint32_t DT>
-__global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_planar_float_kernel(const Job *jobs, RowInfo *rows_out,
-                                                                                                                   JobState *states, uint32_t *local,
-                                                                                                                   const FloatQuant fq)
-{
-    uint32_t bx, by;
-    xcd_block_order(bx, by);
-    encode_rows_block<C, (int)(kFloatLayout + DT)>(jobs[by], by, bx, rows_out, states, local, fq);
+    encode_rows_block<C, FORM>(jobs[by], by, bx, rows_out, states, local, fq...);
 }
 
 // One image per submission, first kernel of its chain: the job record comes IN THE KERNEL ARGUMENTS instead of through an
@@ -1824,31 +1771,32 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(const Job *jobs, const
 // -- together with its CRC partial and its share of the Adler-32 (byte sum, position-weighted sum: finalize_kernel adds the
 // ranges up).  A piece of 16 file bytes that lies inside one stored block and one row is 16 consecutive pixel bytes (5 aligned
 // loads + v_alignbyte); pieces with a block header, a filter byte or the ends of the stream are built byte by byte.
-// EX: jobs of fpng_amd_encode_submit_ex -- PNG byte b of a row is channel b % c of pixel b / c, found in the source through the
-// job's pitch, pixel size and selector; those images take the byte-by-byte path for every piece (stored blocks are their fallback
-// and FPNG_FORCE_UNCOMPRESSED's form, not a hot path)
-// EX == 2: planar jobs (stored_planar_kernel) -- channel ch of pixel p of a row lies at ch * plane_pitch + row * pitch + p
+// FORM (kernels.h; stored_kernel): every form but kFormPacked takes the byte-by-byte path for every piece (stored blocks are those images'
+// fallback and FPNG_FORCE_UNCOMPRESSED's form, not a hot path)
+// kFormEx: jobs of fpng_amd_encode_submit_ex -- PNG byte b of a row is channel b % c of pixel b / c, found in the source through the
+// job's pitch, pixel size and selector
+// kFormPlanar: planar jobs -- channel ch of pixel p of a row lies at ch * plane_pitch + row * pitch + p
 __device__ __forceinline__ float channel_of(const float (&v)[4], uint32_t ch) { return ch == 0 ? v[0] : ch == 1 ? v[1] : ch == 2 ? v[2] : v[3]; }
-// EX == kFloatLayout + dtype: planar jobs of floats (stored_planar_float_kernel) -- the element there, quantised with fq's constants
-template <int EX = 0, typename... FQ>
+// kFloatLayout + dtype: planar jobs of floats -- the element there, quantised with fq's constants
+template <int FORM = kFormPacked, typename... FQ>
 __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 px, uint32_t s, const FQ &...fq)
 {
     const uint32_t stride = job.bpl + 1, row = s / stride, col = s - row * stride;
-    if constexpr (is_float_layout(EX)) {
+    if constexpr (is_float_layout(FORM)) {
         if (!col) return 0u;
-        constexpr uint32_t DT = (uint32_t)EX - kFloatLayout;
+        constexpr uint32_t DT = (uint32_t)(FORM - kFloatLayout);
         const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
         gptr_cu8 e = px + ((int64_t)ch * job.plane_pitch + (int64_t)row * job.pitch + (int64_t)p * (DT == kF32 ? 4 : 2));
         const uint32_t bits = DT == kF32 ? *(gptr_cu32)(uintptr_t)e : (uint32_t) * (const FPNG_GLOBAL uint16_t *)(uintptr_t)e;
         // (selected, not indexed: indexing the kernel argument by a lane's value would put a copy of it into scratch)
         return quantize(widen<DT>(bits), channel_of(fq.scale, ch)..., channel_of(fq.bias, ch)...);
     }
-    if (EX == 2) {
+    if (FORM == kFormPlanar) {
         if (!col) return 0u;
         const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
         return (uint32_t)px[(int64_t)ch * job.plane_pitch + (int64_t)row * job.pitch + (int64_t)p];
     }
-    if (EX) {
+    if (FORM == kFormEx) {
         if (!col) return 0u;
         const uint32_t b = col - 1, p = b / job.c, ch = b - p * job.c;
         return (uint32_t)px[(int64_t)row * job.pitch + (int64_t)p * job.src_bytes + ((job.sel >> (8 * ch)) & 3u)];
@@ -1856,7 +1804,7 @@ __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 
     return col ? (uint32_t)px[(size_t)row * job.bpl + col - 1] : 0u;
 }
 
-template <int EX = 0, typename... FQ>
+template <int FORM = kFormPacked, typename... FQ>
 __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &st, int64_t range_begin, uint32_t range_bytes, int32_t db, int32_t de,
                                                 uint32_t (*tab)[256], uint32_t *red, const CrcDeviceTables *tabs, uint32_t *crc_out, uint32_t *adler_out,
                                                 const FQ &...fq)
@@ -1878,7 +1826,7 @@ __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &
         if (o + 16 > db && o < de) {
             const int64_t fo = range_begin + o;
             bool fast = false;
-            if (!EX && z >= 7 && w >= 5 && w <= 65540u - 16u) {
+            if (FORM == kFormPacked && z >= 7 && w >= 5 && w <= 65540u - 16u) {
                 const uint64_t s0 = k * 65535u + (w - 5);
                 if (s0 + 16 <= n_filtered) {
                     const uint32_t s32 = (uint32_t)s0, r = s32 / stride, col = s32 - r * stride;
@@ -1920,7 +1868,7 @@ __device__ __forceinline__ void assemble_stored(const Job &job, const JobState &
                         } else {
                             const uint64_t sj = kk * 65535u + (ww - 5);
                             if (sj < n_filtered) {
-                                b = stored_stream_byte<EX>(job, px, (uint32_t)sj, fq...);
+                                b = stored_stream_byte<FORM>(job, px, (uint32_t)sj, fq...);
                                 a_sum += b;
                                 w_sum += (uint64_t)(n_filtered - (uint32_t)sj) * b;
                             }
@@ -2179,13 +2127,15 @@ __global__ __launch_bounds__(kBlock) void assemble_kernel(const Job *jobs, JobSt
     if (tid == 0) partials[(size_t)blockIdx.y * max_crc_blocks + blockIdx.x] = red[0] ^ red[1] ^ red[2] ^ red[3];
 }
 
-// stored_ex_kernel: the stored blocks of the _ex images that fell back (or were asked for with FPNG_FORCE_UNCOMPRESSED), straight
-// from their source layout, with their ranges' Adler shares.  grid (<= max_crc_blocks, n_jobs), each workgroup takes every
-// gridDim.x-th range; compressed images leave at once.  assemble_kernel runs behind it with adler_parts = NULL: for a stored image it
+// stored_kernel: the stored blocks of the images of every form but kFormPacked that fell back (or were asked for with
+// FPNG_FORCE_UNCOMPRESSED), straight from their source form (FORM; FQ: nothing, or FloatQuant for the float forms), with their ranges'
+// Adler shares.  grid (<= max_crc_blocks, n_jobs), each workgroup takes every gridDim.x-th range; compressed images leave at once.
+// assemble_kernel runs behind it with adler_parts = NULL: for a stored image it
 // then takes the CRC of the bytes in place, as for a stored row band, and writes nothing.  (A layout form of assemble_kernel itself
 // does not leave the packed form's code as it is: the compiler allocates registers differently once both exist.)
-__global__ __launch_bounds__(kBlock) void stored_ex_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
-                                                          uint32_t *adler_parts, uint32_t max_crc_blocks)
+template <int FORM, typename... FQ>
+__global__ __launch_bounds__(kBlock) void stored_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
+                                                       uint32_t *adler_parts, uint32_t max_crc_blocks, const FQ... fq)
 {
     __shared__ uint32_t tab[16][256];
     __shared__ uint32_t red[3 * kWavesPerBlock];
@@ -2205,62 +2155,7 @@ __global__ __launch_bounds__(kBlock) void stored_ex_kernel(const Job *jobs, cons
         const int64_t range_begin = range_end - range_bytes;
         const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
         const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
-        assemble_stored<true>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
-        __syncthreads(); // (`red` is read by thread 0 at the end of the range)
-    }
-}
-
-// stored_planar_kernel: the same for the planar jobs of fpng_amd_encode_submit_planar
-__global__ __launch_bounds__(kBlock) void stored_planar_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
-                                                          uint32_t *adler_parts, uint32_t max_crc_blocks)
-{
-    __shared__ uint32_t tab[16][256];
-    __shared__ uint32_t red[3 * kWavesPerBlock];
-    const Job &job = job_of_block(jobs);
-    const JobState &st = states[blockIdx.y];
-    if (uniform(st.mode) == 0u || uniform(st.status)) return;
-    const int64_t data_begin = kPngHeaderBytes, data_end = (int64_t)(kPngHeaderBytes + st.zlib_size - 4);
-    const int64_t end_aligned = (data_end + 15) & ~15ll;
-    const uint32_t range_bytes = 1u << uniform(crc_range_log2(st));
-    auto sat = [](int64_t v) { return (int32_t)(v > 0x7FFFFFFFll ? 0x7FFFFFFFll : (v < -0x7FFFFFFFll ? -0x7FFFFFFFll : v)); };
-    if (end_aligned - (int64_t)blockIdx.x * range_bytes <= (data_begin & ~15ll)) return;
-    for (int i = threadIdx.x; i < 16 * 256; i += kBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
-    __syncthreads();
-    for (uint32_t b = blockIdx.x; b < max_crc_blocks; b += gridDim.x) {
-        const int64_t range_end = end_aligned - (int64_t)b * range_bytes;
-        if (range_end <= (data_begin & ~15ll)) break; // nothing of the data in this range or the ones behind it
-        const int64_t range_begin = range_end - range_bytes;
-        const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
-        const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
-        assemble_stored<2>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot]);
-        __syncthreads(); // (`red` is read by thread 0 at the end of the range)
-    }
-}
-
-// stored_planar_float_kernel: the same for the planar jobs of floats of fpng_amd_encode_submit_planar_float, element type DT
-template <uint32_t DT>
-__global__ __launch_bounds__(kBlock) void stored_planar_float_kernel(const Job *jobs, const JobState *states, const CrcDeviceTables *tabs, uint32_t *partials,
-                                                                uint32_t *adler_parts, uint32_t max_crc_blocks, const FloatQuant fq)
-{
-    __shared__ uint32_t tab[16][256];
-    __shared__ uint32_t red[3 * kWavesPerBlock];
-    const Job &job = job_of_block(jobs);
-    const JobState &st = states[blockIdx.y];
-    if (uniform(st.mode) == 0u || uniform(st.status)) return;
-    const int64_t data_begin = kPngHeaderBytes, data_end = (int64_t)(kPngHeaderBytes + st.zlib_size - 4);
-    const int64_t end_aligned = (data_end + 15) & ~15ll;
-    const uint32_t range_bytes = 1u << uniform(crc_range_log2(st));
-    auto sat = [](int64_t v) { return (int32_t)(v > 0x7FFFFFFFll ? 0x7FFFFFFFll : (v < -0x7FFFFFFFll ? -0x7FFFFFFFll : v)); };
-    if (end_aligned - (int64_t)blockIdx.x * range_bytes <= (data_begin & ~15ll)) return;
-    for (int i = threadIdx.x; i < 16 * 256; i += kBlock) (&tab[0][0])[i] = (&tabs->striped[0][0])[i];
-    __syncthreads();
-    for (uint32_t b = blockIdx.x; b < max_crc_blocks; b += gridDim.x) {
-        const int64_t range_end = end_aligned - (int64_t)b * range_bytes;
-        if (range_end <= (data_begin & ~15ll)) break; // nothing of the data in this range or the ones behind it
-        const int64_t range_begin = range_end - range_bytes;
-        const int32_t db = sat(data_begin - range_begin), de = sat(data_end - range_begin);
-        const size_t slot = (size_t)blockIdx.y * max_crc_blocks + b;
-        assemble_stored<(int)(kFloatLayout + DT)>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot], fq);
+        assemble_stored<FORM>(job, st, range_begin, range_bytes, db, de, tab, red, tabs, &partials[slot], &adler_parts[2 * slot], fq...);
         __syncthreads(); // (`red` is read by thread 0 at the end of the range)
     }
 }
@@ -2743,9 +2638,22 @@ static dim3 row_grid(uint32_t max_rows, uint32_t n_jobs)
     return dim3((max_rows + kRowWaves - 1) / kRowWaves, n_jobs, 1);
 }
 
-void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist)
+// The kernels of the stages that read pixels, by SourceForms: tables indexed with the kind (the forms without constants) and with the
+// element type (the float forms, whose kernels take the FloatQuant behind their other arguments)
+static_assert(FPNG_AMD_DESC_IMAGE == 0 && FPNG_AMD_DESC_EX == 1 && FPNG_AMD_DESC_PLANAR == 2 && kF32 == 0 && kF16 == 1 && kBF16 == 2, "the launchers' tables");
+constexpr int kFormF32 = kFloatLayout + (int)kF32, kFormF16 = kFloatLayout + (int)kF16, kFormBF16 = kFloatLayout + (int)kBF16;
+
+void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, SourceForms src)
 {
-    hipLaunchKernelGGL(hist_kernel, dim3((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1), dim3(kHistBlock), 0, s, jobs, hist);
+    using Kernel = void (*)(const Job *, uint32_t *);
+    using FloatKernel = void (*)(const Job *, uint32_t *, FloatQuant);
+    static const Kernel kernels[3] = {hist_kernel<kFormPacked>, hist_kernel<kFormEx>, hist_kernel<kFormPlanar>};
+    static const FloatKernel float_kernels[3] = {hist_kernel<kFormF32, FloatQuant>, hist_kernel<kFormF16, FloatQuant>, hist_kernel<kFormBF16, FloatQuant>};
+    const dim3 grid((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1);
+    if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
+        hipLaunchKernelGGL(float_kernels[src.dtype], grid, dim3(kHistBlock), 0, s, jobs, hist, src.fq);
+    else
+        hipLaunchKernelGGL(kernels[src.kind], grid, dim3(kHistBlock), 0, s, jobs, hist);
 }
 void launch_hist_first(hipStream_t s, const Job &job, Job *d_job, uint32_t *hist)
 {
@@ -2767,72 +2675,28 @@ void launch_build_dynamic(hipStream_t s, const Job *jobs, uint32_t n_jobs, const
 {
     hipLaunchKernelGGL(build_dynamic_kernel, dim3(n_jobs), dim3(kWave), 0, s, jobs, (uint32_t *)hist, tables, rezero);
 }
-void launch_encode_rows(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                        JobState *states, uint32_t *local, bool wide4)
+void launch_encode_rows(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, RowInfo *rows, JobState *states, uint32_t *local, SourceForms src)
 {
-    if (chan_mask & 1u)
-        hipLaunchKernelGGL((encode_rows_kernel<3, FPNG_ROWS_WPE>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-    if ((chan_mask & 2u) && wide4)
-        hipLaunchKernelGGL((encode_rows_kernel<4, FPNG_ROWS_WPE4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-    else if (chan_mask & 2u)
-        hipLaunchKernelGGL((encode_rows_kernel<4, FPNG_ROWS_WPE>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-}
-void launch_hist_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist)
-{
-    hipLaunchKernelGGL(hist_ex_kernel, dim3((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1), dim3(kHistBlock), 0, s, jobs, hist);
-}
-void launch_encode_rows_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t layout_mask, RowInfo *rows,
-                           JobState *states, uint32_t *local, bool wide4)
-{
-    if (layout_mask & 1u)
-        hipLaunchKernelGGL((encode_rows_ex_kernel<3, FPNG_ROWS_WPE, 3>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-    if (layout_mask & 4u)
-        hipLaunchKernelGGL((encode_rows_ex_kernel<3, FPNG_ROWS_WPE, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-    if ((layout_mask & 2u) && wide4)
-        hipLaunchKernelGGL((encode_rows_ex_kernel<4, FPNG_ROWS_WPE4, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-    else if (layout_mask & 2u)
-        hipLaunchKernelGGL((encode_rows_ex_kernel<4, FPNG_ROWS_WPE, 4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-}
-void launch_hist_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist)
-{
-    hipLaunchKernelGGL(hist_planar_kernel, dim3((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1), dim3(kHistBlock), 0, s, jobs, hist);
-}
-void launch_encode_rows_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                               JobState *states, uint32_t *local)
-{
-    if (chan_mask & 1u)
-        hipLaunchKernelGGL((encode_rows_planar_kernel<3, FPNG_ROWS_WPE_PLANAR3>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-    if (chan_mask & 2u)
-        hipLaunchKernelGGL((encode_rows_planar_kernel<4, FPNG_ROWS_WPE_PLANAR4>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
-}
-void launch_hist_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, uint32_t dtype, const FloatQuant &fq)
-{
-    const dim3 grid((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1);
-    if (dtype == kF32)
-        hipLaunchKernelGGL(hist_planar_float_kernel<kF32>, grid, dim3(kHistBlock), 0, s, jobs, hist, fq);
-    else if (dtype == kF16)
-        hipLaunchKernelGGL(hist_planar_float_kernel<kF16>, grid, dim3(kHistBlock), 0, s, jobs, hist, fq);
-    else
-        hipLaunchKernelGGL(hist_planar_float_kernel<kBF16>, grid, dim3(kHistBlock), 0, s, jobs, hist, fq);
-}
-template <uint32_t DT>
-static void launch_encode_rows_planar_float_of(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                                               JobState *states, uint32_t *local, const FloatQuant &fq)
-{
-    if (chan_mask & 1u)
-        hipLaunchKernelGGL((encode_rows_planar_float_kernel<3, FPNG_ROWS_WPE_FLOAT3, DT>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local, fq);
-    if (chan_mask & 2u)
-        hipLaunchKernelGGL((encode_rows_planar_float_kernel<4, DT == kF32 ? FPNG_ROWS_WPE_FLOAT4_F32 : FPNG_ROWS_WPE_FLOAT4, DT>), row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local, fq);
-}
-void launch_encode_rows_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t chan_mask, RowInfo *rows,
-                                     JobState *states, uint32_t *local, uint32_t dtype, const FloatQuant &fq)
-{
-    if (dtype == kF32)
-        launch_encode_rows_planar_float_of<kF32>(s, jobs, n_jobs, max_rows, chan_mask, rows, states, local, fq);
-    else if (dtype == kF16)
-        launch_encode_rows_planar_float_of<kF16>(s, jobs, n_jobs, max_rows, chan_mask, rows, states, local, fq);
-    else
-        launch_encode_rows_planar_float_of<kBF16>(s, jobs, n_jobs, max_rows, chan_mask, rows, states, local, fq);
+    using Kernel = void (*)(const Job *, RowInfo *, JobState *, uint32_t *);
+    using FloatKernel = void (*)(const Job *, RowInfo *, JobState *, uint32_t *, FloatQuant);
+    // per kind the instantiation of every bit of the mask (kernels.h), and as [3] the one that bit 1, the 4-channel jobs, launches with wide4
+    static const Kernel kernels[3][4] = {
+        {encode_rows_kernel<3, FPNG_ROWS_WPE, kFormPacked>, encode_rows_kernel<4, FPNG_ROWS_WPE, kFormPacked>, nullptr, encode_rows_kernel<4, FPNG_ROWS_WPE4, kFormPacked>},
+        {encode_rows_kernel<3, FPNG_ROWS_WPE, kFormEx3>, encode_rows_kernel<4, FPNG_ROWS_WPE, kFormEx4>, encode_rows_kernel<3, FPNG_ROWS_WPE, kFormEx4>,
+         encode_rows_kernel<4, FPNG_ROWS_WPE4, kFormEx4>},
+        {encode_rows_kernel<3, FPNG_ROWS_WPE_PLANAR3, kFormPlanar>, encode_rows_kernel<4, FPNG_ROWS_WPE_PLANAR4, kFormPlanar>, nullptr,
+         encode_rows_kernel<4, FPNG_ROWS_WPE_PLANAR4, kFormPlanar>}}; // (the planar walks, uint8 and float, have no form for wide rows)
+    static const FloatKernel float_kernels[3][2] = {
+        {encode_rows_kernel<3, FPNG_ROWS_WPE_FLOAT3, kFormF32, FloatQuant>, encode_rows_kernel<4, FPNG_ROWS_WPE_FLOAT4_F32, kFormF32, FloatQuant>},
+        {encode_rows_kernel<3, FPNG_ROWS_WPE_FLOAT3, kFormF16, FloatQuant>, encode_rows_kernel<4, FPNG_ROWS_WPE_FLOAT4, kFormF16, FloatQuant>},
+        {encode_rows_kernel<3, FPNG_ROWS_WPE_FLOAT3, kFormBF16, FloatQuant>, encode_rows_kernel<4, FPNG_ROWS_WPE_FLOAT4, kFormBF16, FloatQuant>}};
+    for (const uint32_t bit : {0u, 2u, 1u}) { // (the 3-channel jobs' walks first)
+        if (!(src.mask >> bit & 1u)) continue;
+        if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
+            hipLaunchKernelGGL(float_kernels[src.dtype][bit], row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local, src.fq);
+        else
+            hipLaunchKernelGGL(kernels[src.kind][bit == 1 && src.wide4 ? 3 : bit], row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local);
+    }
 }
 void launch_encode_rows_first(hipStream_t s, const Job &job, Job *d_job, RowInfo *rows, JobState *states, uint32_t *local)
 {
@@ -2846,41 +2710,23 @@ void launch_encode_rows_first(hipStream_t s, const Job &job, Job *d_job, RowInfo
         hipLaunchKernelGGL((encode_rows_first_kernel<4, FPNG_ROWS_WPE>), row_grid(job.nrows, 1), dim3(kRowBlock), 0, s, arg, d_job, rows, states, local);
 }
 void launch_assemble(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                     const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts)
+                     const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts, SourceForms src)
 {
+    if (src.kind != FPNG_AMD_DESC_IMAGE) { // assemble_kernel writes stored files of packed pixels only: stored_kernel in front of it
+        using Kernel = void (*)(const Job *, const JobState *, const CrcDeviceTables *, uint32_t *, uint32_t *, uint32_t);
+        using FloatKernel = void (*)(const Job *, const JobState *, const CrcDeviceTables *, uint32_t *, uint32_t *, uint32_t, FloatQuant);
+        static const Kernel kernels[3] = {nullptr, stored_kernel<kFormEx>, stored_kernel<kFormPlanar>};
+        static const FloatKernel float_kernels[3] = {stored_kernel<kFormF32, FloatQuant>, stored_kernel<kFormF16, FloatQuant>, stored_kernel<kFormBF16, FloatQuant>};
+        // (a small grid: for compressed images -- the usual case -- its workgroups only look at the mode)
+        const dim3 grid(std::min(max_crc_blocks, kStoredExBlocks), n_jobs);
+        if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
+            hipLaunchKernelGGL(float_kernels[src.dtype], grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, src.fq);
+        else
+            hipLaunchKernelGGL(kernels[src.kind], grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
+        adler_parts = nullptr;
+    }
     hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
                        partials, adler_parts, max_crc_blocks);
-}
-void launch_assemble_ex(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                        const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts)
-{
-    // (a small grid: for compressed images -- the usual case -- its workgroups only look at the mode)
-    const uint32_t gx = std::min(max_crc_blocks, kStoredExBlocks);
-    hipLaunchKernelGGL(stored_ex_kernel, dim3(gx, n_jobs), dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
-    hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
-                       partials, (uint32_t *)nullptr, max_crc_blocks);
-}
-void launch_assemble_planar(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                            const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts)
-{
-    const uint32_t gx = std::min(max_crc_blocks, kStoredExBlocks);
-    hipLaunchKernelGGL(stored_planar_kernel, dim3(gx, n_jobs), dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);
-    hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
-                       partials, (uint32_t *)nullptr, max_crc_blocks);
-}
-void launch_assemble_planar_float(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, JobState *states,
-                                  const uint64_t *row_off, const uint32_t *local, const CrcDeviceTables *tabs, uint32_t *partials, uint32_t *adler_parts,
-                                  uint32_t dtype, const FloatQuant &fq)
-{
-    const dim3 grid(std::min(max_crc_blocks, kStoredExBlocks), n_jobs);
-    if (dtype == kF32)
-        hipLaunchKernelGGL(stored_planar_float_kernel<kF32>, grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, fq);
-    else if (dtype == kF16)
-        hipLaunchKernelGGL(stored_planar_float_kernel<kF16>, grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, fq);
-    else
-        hipLaunchKernelGGL(stored_planar_float_kernel<kBF16>, grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, fq);
-    hipLaunchKernelGGL(assemble_kernel, dim3(max_crc_blocks, n_jobs), dim3(kBlock), 0, s, jobs, states, row_off, local, tabs,
-                       partials, (uint32_t *)nullptr, max_crc_blocks);
 }
 void launch_crc(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_crc_blocks, const JobState *states,
                 const CrcDeviceTables *tabs, uint32_t *partials)

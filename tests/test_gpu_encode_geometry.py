@@ -257,7 +257,7 @@ def test_group_c_fold_depth(enc, part):
 
 
 def test_group_s_stored_walk_through_every_stored_kernel(enc):
-    """assemble_kernel's stored branch, stored_ex_kernel, stored_planar_kernel and stored_planar_float_kernel write the same files"""
+    """assemble_kernel's stored branch and stored_kernel's _ex, planar and planar float (f32) instantiations write the same files"""
     cases = _cases("S")
     assert all(k["flags"] == 2 for k in cases)
     assert {AG.n_filtered(k["w"], k["h"], k["c"]) for k in cases} >= {65534, 65535, 65536, 131070, 131071}

@@ -65,4 +65,4 @@ lines.append(f"total HBM-side traffic per launch: {tot/1e6:.1f} MB" + (f"  ({tot
 open(f"profiles/{tag}_pmc_traffic.txt", "w").write("\n".join(lines) + "\n")
 print("\n".join(lines))
 for r in csv.DictReader(open(f"profiles/{tag}_kernel_stats.csv")):
-    print(r["Name"].replace("fpng_amd::(anonymous namespace)::", "").split("(")[0][:28], r["Calls"], round(float(r["AverageNs"]) / 1e3, 1), "us")
+    print(r["Name"].replace("fpng_amd::(anonymous namespace)::", "").split("(")[0][:48], r["Calls"], round(float(r["AverageNs"]) / 1e3, 1), "us")

@@ -38,4 +38,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   view_tone, view_tone_lut, view_tone_apply,
                   view_enhance, view_enhance_apply, rotate_matrix, augment_op,
                   view_alpha, view_alpha_source, view_alpha_result, view_resample, resample_weights, resample_view_source,
-                  RENDITION_FILTERS, rendition, renditions_plan, rendition_pixels)
+                  RENDITION_FILTERS, rendition, renditions_plan, rendition_pixels,
+                  YUV_SURFACES, YUV_STANDARDS, yuv_matrix, yuv_frame_layout, yuv_pixels)

@@ -159,6 +159,19 @@ class Rendition(C.Structure):  # fpng_amd_rendition: 56 bytes, no padding
 RENDITION_FILTERS = {"bilinear": 0, "bicubic": 1, "nearest": 2, "box": 3, "hamming": 4, "lanczos": 5}
 
 
+class YuvFrame(C.Structure):  # fpng_amd_yuv_frame: 56 bytes, no padding
+    _fields_ = [("d_luma", C.c_void_p), ("row_pitch", C.c_int64), ("chroma_offset", C.c_int64), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("reserved", C.c_uint64), ("d_out", C.c_void_p), ("out_cap", C.c_size_t)]
+
+
+class YuvFormat(C.Structure):  # fpng_amd_yuv_format: 56 bytes
+    _fields_ = [("surface", C.c_uint32), ("reserved", C.c_uint32), ("m", (C.c_float * 4) * 3)]
+
+
+YUV_SURFACES = {"nv12": 0, "p016": 1, "yuv444": 2, "yuv444_16": 3}  # FPNG_AMD_YUV_* (p016 serves P010 / P012)
+YUV_STANDARDS = {"bt601": 0, "bt709": 1, "bt2020": 2}  # FPNG_AMD_YUV_BT*
+
+
 class DecodeResult(C.Structure):
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels_in_file", C.c_uint32), ("status", C.c_int32)]
 
@@ -221,6 +234,9 @@ SIGNATURES = {
     "fpng_amd_encode_submit_renditions": (_int, [_vp, _u32, _vp, _u32, C.POINTER(FloatFormat), C.POINTER(Rendition), _u32, _u32, C.POINTER(Pack), C.POINTER(_u64)]),
     "fpng_amd_renditions_plan": (_int, [_u32, _vp, _u32, C.POINTER(FloatFormat), C.POINTER(Rendition), _u32, _int, C.POINTER(_u64), C.POINTER(_u64)]),
     "fpng_amd_rendition_pixels": (_int, [_u32, _vp, _u32, C.POINTER(FloatFormat), C.POINTER(Rendition), _vp, _sz]),
+    "fpng_amd_encode_submit_yuv": (_int, [_vp, C.POINTER(YuvFrame), _u32, C.POINTER(YuvFormat), C.POINTER(Rendition), _u32, _u32, C.POINTER(Pack), C.POINTER(_u64)]),
+    "fpng_amd_yuv_matrix": (_int, [_u32, _int, C.POINTER(C.c_float)]),
+    "fpng_amd_yuv_pixels": (_int, [C.POINTER(YuvFrame), _u32, C.POINTER(YuvFormat), _u32, C.POINTER(Rendition), _vp, _sz]),
     "fpng_amd_encode_wait": (_int, [_vp, _u64, C.POINTER(Result), _u32]),
     "fpng_amd_encode_query": (_int, [_vp, _u64]),
     "fpng_amd_encode_host": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(_sz)]),

@@ -1143,6 +1143,106 @@ def rendition_pixels(images, rendition, kind="image", **layout):
     return out
 
 
+# ---- YUV video frames: encoding straight from a decoder's surfaces (fpng_amd_encode_submit_yuv) ----
+YUV_SURFACES = _lib.YUV_SURFACES    # name -> FPNG_AMD_YUV_*: "nv12", "p016" (also P010 / P012), "yuv444", "yuv444_16"
+YUV_STANDARDS = _lib.YUV_STANDARDS  # name -> FPNG_AMD_YUV_BT*: "bt601", "bt709", "bt2020"
+
+
+def yuv_matrix(standard="bt709", full_range=False):
+    """fpng_amd_yuv_matrix: the (3, 4) float32 matrix [R, G, B] = m[:, :3] @ [Y, Cb, Cr] + m[:, 3] of "bt601", "bt709" or "bt2020",
+    limited (Y 16..235, C 16..240) or full range, for 8-bit values -- 16-bit elements count as word / 256, so the same matrix
+    serves P010 / P012 / P016.  Swap columns 1 and 2 for NV21 / YVU orders."""
+    if standard not in YUV_STANDARDS:
+        raise ValueError(f"yuv_matrix: standard {standard!r} ({', '.join(sorted(YUV_STANDARDS))})")
+    m = np.empty((3, 4), dtype=np.float32)
+    check(_lib.load().fpng_amd_yuv_matrix(YUV_STANDARDS[standard], 1 if full_range else 0, m.ctypes.data_as(C.POINTER(C.c_float))))
+    return m
+
+
+def _yuv_format(who, surface, matrix, standard, full_range):
+    if surface not in YUV_SURFACES:
+        raise ValueError(f"{who}: surface {surface!r} ({', '.join(sorted(YUV_SURFACES))})")
+    m = yuv_matrix(standard, full_range) if matrix is None else np.asarray(matrix, dtype=np.float32)
+    if m.shape != (3, 4):
+        raise ValueError(f"{who}: matrix is 3 x 4, not {m.shape}")
+    fmt = _lib.YuvFormat()
+    fmt.surface = YUV_SURFACES[surface]
+    for c in range(3):
+        for k in range(4):
+            fmt.m[c][k] = float(m[c, k])
+    return fmt
+
+
+def yuv_frame_layout(frame, surface="nv12"):
+    """(d_luma, row_pitch, chroma_offset, w, h) of an fpng_amd_yuv_frame for a tuple of tensor views of ONE surface, from data_ptr()
+    and strides alone: (Y (h, w), CbCr (ceil(h / 2), ceil(w / 2), 2)) for "nv12" / "p016", (Y, Cb, Cr), each (h, w), for "yuv444" /
+    "yuv444_16"; uint8, or uint16 / int16 for the 16-bit surfaces.  ValueError when the planes' row strides differ, when elements
+    are not tight, or when (4:4:4) Cr - Cb is not Cb - Y.  row_pitch 0 stands for tight rows where no plane has a second row."""
+    who = "yuv_frame_layout"
+    if surface not in YUV_SURFACES:
+        raise ValueError(f"{who}: surface {surface!r} ({', '.join(sorted(YUV_SURFACES))})")
+    s = YUV_SURFACES[surface]
+    is420, elem = s < 2, 2 if s & 1 else 1
+    planes = [torch.from_numpy(p) if isinstance(p, np.ndarray) else p for p in frame]
+    if len(planes) != (2 if is420 else 3) or not all(isinstance(p, torch.Tensor) for p in planes):
+        raise ValueError(f"{who}: a {surface} frame is a tuple of {'(Y, CbCr)' if is420 else '(Y, Cb, Cr)'} tensors")
+    dtypes = (torch.uint8,) if elem == 1 else tuple(d for d in (getattr(torch, "uint16", None), torch.int16) if d is not None)
+    if not all(p.dtype in dtypes for p in planes):
+        raise ValueError(f"{who}: {surface} planes are {' or '.join(str(d) for d in dtypes)} tensors")
+    y = planes[0]
+    if y.dim() != 2 or not y.shape[0] or not y.shape[1]:
+        raise ValueError(f"{who}: Y is shaped (h, w)")
+    h, w = y.shape
+    for p in planes[1:]:
+        want = ((h + 1) // 2, (w + 1) // 2, 2) if is420 else (h, w)
+        if tuple(p.shape) != want:
+            raise ValueError(f"{who}: a chroma plane of a {w} x {h} {surface} frame is shaped {want}, not {tuple(p.shape)}")
+    pitches = set()
+    for p in planes:
+        # (the stride of a dimension of one element says nothing)
+        inner = [(p.shape[1], p.stride(1), p.shape[2] if p.dim() == 3 else 1)] + ([(2, p.stride(2), 1)] if p.dim() == 3 else [])
+        if any(n > 1 and st != step for n, st, step in inner):
+            raise ValueError(f"{who}: the elements of a row are not tight (strides {tuple(p.stride())})")
+        if p.shape[0] > 1:
+            pitches.add(p.stride(0) * elem)
+    if len(pitches) > 1:
+        raise ValueError(f"{who}: the planes' row strides differ ({sorted(pitches)} bytes): a surface has one pitch")
+    offs = [p.data_ptr() - q.data_ptr() for p, q in zip(planes[1:], planes[:-1])]
+    if len(set(offs)) > 1:
+        raise ValueError(f"{who}: Cr - Cb ({offs[1]} bytes) is not Cb - Y ({offs[0]} bytes)")
+    return y.data_ptr(), (pitches.pop() if pitches else 0), offs[0], w, h
+
+
+def _yuv_records(who, frames, surface, outs=None):
+    frames = [tuple(f) for f in frames]
+    if outs is not None and len(outs) != len(frames):
+        raise ValueError(f"{who}: {len(frames)} frames, {len(outs)} outs")
+    arr = (_lib.YuvFrame * len(frames))()
+    for a, f in zip(arr, frames):
+        a.d_luma, a.row_pitch, a.chroma_offset, a.w, a.h = yuv_frame_layout(f, surface)
+    for a, out in zip(arr, outs or ()):
+        a.d_out, a.out_cap = out.data_ptr(), out.numel()
+    return frames, arr
+
+
+def yuv_pixels(frames, surface="nv12", matrix=None, standard="bt709", full_range=False, frame=0, rendition=None):
+    """fpng_amd_yuv_pixels, the conversion's host twin (no GPU; the text the kernels compile): the (h, w, 3) uint8 array of R,G,B
+    pixels whose file Encoder.submit_yuv() writes for frame `frame` of `frames` (CPU tensors or numpy arrays, each a tuple as for
+    yuv_frame_layout) -- or, with an fpng_amd.rendition() record, for that rendition of it (the record's `image` is not looked at)."""
+    frames, arr = _yuv_records("yuv_pixels", frames, surface)
+    if any(p.is_cuda for f in frames for p in f if isinstance(p, torch.Tensor)):
+        raise ValueError("yuv_pixels: host tensors (the twin runs on the CPU)")
+    fmt = _yuv_format("yuv_pixels", surface, matrix, standard, full_range)
+    if rendition is not None:
+        shape = (max(rendition.h, 1), max(rendition.w, 1), 3)
+    else:
+        shape = (arr[frame].h, arr[frame].w, 3) if 0 <= frame < len(arr) else (1, 1, 3)
+    out = np.empty(shape, dtype=np.uint8)
+    check(_lib.load().fpng_amd_yuv_pixels(arr, len(arr), C.byref(fmt), _u32("yuv_pixels", "frame", frame), C.byref(rendition) if rendition is not None else None,
+                                          out.ctypes.data, out.size))
+    return out
+
+
 class _NoOut:
     """stands in a make_batch_packed() descriptor where the other makers' hold an output tensor: a packed submission has none"""
     is_cuda = True
@@ -1869,6 +1969,65 @@ class Encoder:
                 raise ValueError(f"encode_renditions: rendition of image {r.image} of {len(images)}")
         outs = [torch.empty(max_encoded_size(r.w, r.h, chans[r.image]) + 64, dtype=torch.uint8, device=images[r.image].device) for r in renditions]
         n = self.submit_renditions(images, renditions, kind=kind, outs=outs, flags=flags, **layout)
+        return _files(outs, self.wait(self.last_ticket, n))
+
+    @staticmethod
+    def make_batch_yuv(frames, outs=None, surface="nv12", matrix=None, standard="bt709", full_range=False):
+        """Descriptor ("yuv", frames, outs, fpng_amd_yuv_frame[n], fpng_amd_yuv_format) for submit_yuv(): build it once when the same
+        surfaces are encoded repeatedly (a decoder's ring of frames); submit_yuv(descriptor) then costs one C call.  outs: one
+        uint8 CUDA tensor of >= max_encoded_size(w, h, 3) bytes per frame, or None for a call with an arena or with renditions."""
+        frames, arr = _yuv_records("make_batch_yuv", frames, surface, outs)
+        return ("yuv", frames, outs, arr, _yuv_format("make_batch_yuv", surface, matrix, standard, full_range))
+
+    def submit_yuv(self, frames, outs=None, arena=None, renditions=None, surface="nv12", matrix=None, standard="bt709", full_range=False, flags=0, align=16,
+                   lead=0, table=None):
+        """fpng_amd_encode_submit_yuv: video frames as the decoder left them -- "nv12", "p016" (P010 / P012 too), "yuv444",
+        "yuv444_16" -- encoded as 3-channel files in ONE submission, the conversion inside the row walk: no RGB image exists in
+        memory.  frames: a tuple of CUDA tensor views per frame, as yuv_frame_layout() takes them.  matrix: a (3, 4) array, or None
+        for yuv_matrix(standard, full_range).  4:2:0 chroma is replicated, not interpolated.  Without renditions every frame is a
+        file: outs -- one uint8 CUDA tensor of >= max_encoded_size(w, h, 3) bytes per frame -- or arena (with align, lead, table as
+        for submit_packed).  With renditions (fpng_amd.rendition() records whose `image` indexes the frames) the files are the
+        renditions', as submit_renditions() writes them for the converted frames: outs, one per rendition, or arena.
+        frames may also be a make_batch_yuv() descriptor (its outs, surface and matrix then hold, and outs here stays None unless
+        the files are renditions').  Asynchronous; wait(last_ticket, n) for the (png_size, mode, status) records, with an arena
+        wait_packed(last_ticket, n).  Returns the number of files."""
+        if isinstance(frames, tuple) and frames[:1] == ("yuv",):
+            _, frames, own_outs, arr, fmt = frames
+            if own_outs is not None:
+                if outs is not None or arena is not None or renditions is not None:
+                    raise ValueError("submit_yuv: a descriptor with outs is a whole call: no outs, arena or renditions beside it")
+                outs = own_outs
+        else:
+            frames, arr = _yuv_records("submit_yuv", frames, surface, outs if renditions is None else None)
+            fmt = _yuv_format("submit_yuv", surface, matrix, standard, full_range)
+        if (outs is None) == (arena is None):
+            raise ValueError("submit_yuv: outs (one per file) or arena, one of the two")
+        _need_cuda("submit_yuv", [p for f in frames for p in f], "the frames' planes")
+        rarr = _rendition_records(renditions) if renditions is not None else None
+        n = len(arr) if rarr is None else len(rarr)
+        pack = None
+        if outs is not None:
+            if len(outs) != n or not all(o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() for o in outs):
+                raise ValueError("submit_yuv: outs are contiguous uint8 CUDA tensors, one per file")
+            for r, o in zip(rarr if rarr is not None else (), outs):
+                r.d_out, r.out_cap = o.data_ptr(), o.numel()
+        else:
+            pack = C.byref(_pack_record("submit_yuv", arena, align, lead, table, n))
+        # (sources and destinations stay alive while the submission runs)
+        return self._submit(lambda t: self.lib.fpng_amd_encode_submit_yuv(self.h, arr, len(arr), C.byref(fmt), rarr, 0 if rarr is None else len(rarr), flags, pack, t),
+                            n, (frames, outs, arena, table))
+
+    def encode_yuv(self, frames, renditions=None, surface="nv12", matrix=None, standard="bt709", full_range=False, flags=0):
+        """Convenience: outputs of max_encoded_size() each, one submit_yuv(), the wait: the files as a list of bytes -- one per frame,
+        or one per rendition, in their order."""
+        frames = [tuple(f) for f in frames]
+        if renditions is None:
+            dims = [tuple(yuv_frame_layout(f, surface)[3:]) for f in frames]
+        else:
+            dims = [(r.w, r.h) for r in renditions]
+        dev = frames[0][0].device
+        outs = [torch.empty(max_encoded_size(w, h, 3) + 64, dtype=torch.uint8, device=dev) for w, h in dims]
+        n = self.submit_yuv(frames, outs=outs, renditions=renditions, surface=surface, matrix=matrix, standard=standard, full_range=full_range, flags=flags)
         return _files(outs, self.wait(self.last_ticket, n))
 
     def wait(self, ticket, n):

@@ -7,6 +7,7 @@
 #include "encode_resize.h"
 #include "lanes.h"
 #include "quantize.h"
+#include "yuv.h"
 
 #include <algorithm>
 #include <cmath>
@@ -514,12 +515,15 @@ struct SourceBatch {
     const void *records;
     uint32_t n;
     const fpng_amd_float_format *fmt = nullptr; // with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it
+    // kind kDescYuv (kernels.h), fpng_amd_yuv_frame records: only fpng_amd_encode_submit_yuv and fpng_amd_yuv_pixels set it, so the
+    // generic entry points, whose fmt is the float one, keep refusing the kind as unknown
+    const fpng_amd_yuv_format *yuv = nullptr;
 };
 
 // what holds for a batch of any kind, whoever submits it
 int check_batch(const SourceBatch &b)
 {
-    if (b.kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
+    if (b.kind == kDescYuv ? !b.yuv : b.kind > FPNG_AMD_DESC_PLANAR_FLOAT) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown desc_kind");
     if ((b.kind == FPNG_AMD_DESC_PLANAR_FLOAT) != (b.fmt != nullptr)) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt goes with FPNG_AMD_DESC_PLANAR_FLOAT, and only with it");
     if (!b.records || !b.n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     return FPNG_AMD_OK;
@@ -551,6 +555,49 @@ int check_float_format(const fpng_amd_float_format *ffmt, FloatQuant &fq)
         if (!std::isfinite(ffmt->scale[k]) || !std::isfinite(ffmt->bias[k])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
         fq.scale[k] = ffmt->scale[k], fq.bias[k] = ffmt->bias[k];
     }
+    return FPNG_AMD_OK;
+}
+
+// fmt of the YUV kind: its matrix into ym
+int check_yuv_format(const fpng_amd_yuv_format *yfmt, YuvMatrix &ym)
+{
+    if (yfmt->surface >= FPNG_AMD_YUV_SURFACES) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown surface (FPNG_AMD_YUV_*)");
+    if (yfmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fmt->reserved must be 0");
+    for (int c = 0; c < 3; c++)
+        for (int k = 0; k < 4; k++) {
+            if (!std::isfinite(yfmt->m[c][k]) || std::fabs(yfmt->m[c][k]) > kColorMaxEntry)
+                return fail(FPNG_AMD_ERR_INVALID_ARG, "the matrix's entries must be finite and at most 65536 in magnitude");
+            ym.m[c][k] = yfmt->m[c][k];
+        }
+    return FPNG_AMD_OK;
+}
+
+static_assert(sizeof(fpng_amd_yuv_frame) == 56 && offsetof(fpng_amd_yuv_frame, w) == 24 && offsetof(fpng_amd_yuv_frame, d_out) == 40 && sizeof(fpng_amd_yuv_format) == 56,
+              "fpng_amd_yuv_frame / fpng_amd_yuv_format layout");
+
+// fpng_amd_yuv_frame of a surface that check_yuv_format() has passed: its size, pointers, pitch and chroma offset into s
+int check_yuv_source(const fpng_amd_yuv_frame &x, uint32_t surface, Source &s)
+{
+    int rc;
+    if (x.reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "reserved must be 0");
+    if ((rc = check_dims(x.w, x.h, 3))) return rc;
+    const int64_t elem = yuv_elem_bytes(surface), row_bytes = (int64_t)x.w * elem, chroma_bytes = (int64_t)yuv_chroma_row_bytes(surface, x.w);
+    if (x.row_pitch < 0) return fail(FPNG_AMD_ERR_INVALID_ARG, "row_pitch must not be negative");
+    if (elem > 1 && (((uintptr_t)x.d_luma | (uint64_t)x.row_pitch | (uint64_t)x.chroma_offset) & 1u))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "d_luma, row_pitch and chroma_offset must be multiples of 2 on 16-bit surfaces");
+    const int64_t pitch = x.row_pitch ? x.row_pitch : std::max(row_bytes, chroma_bytes);
+    if (pitch < row_bytes) return fail(FPNG_AMD_ERR_INVALID_ARG, "row_pitch < w (* element bytes)");
+    if (pitch < chroma_bytes) return fail(FPNG_AMD_ERR_INVALID_ARG, "row_pitch < 2 * ceil(w / 2) (* element bytes): an odd width's last pixel has a full chroma pair");
+    if (pitch > (INT64_MAX >> 26)) return fail(FPNG_AMD_ERR_INVALID_ARG, "row_pitch too large");
+    if (x.chroma_offset == INT64_MIN) return fail(FPNG_AMD_ERR_INVALID_ARG, "chroma_offset out of range");
+    const int64_t span = (int64_t)(x.h - 1) * pitch + row_bytes; // bytes from the luma plane's first row to the end of its last
+    // (a 4:2:0 chroma plane in FRONT of the luma plane ends (h + 1) / 2 - 1 rows and a chroma row behind its start)
+    const int64_t chroma_span = yuv_is_420(surface) ? (int64_t)((x.h + 1) / 2 - 1) * pitch + chroma_bytes : span;
+    if ((x.chroma_offset < 0 ? -x.chroma_offset : x.chroma_offset) < span || (x.chroma_offset < 0 && -x.chroma_offset < chroma_span))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "|chroma_offset| < (h - 1) * row_pitch + w (* element bytes): the planes overlap");
+    s.base = (uintptr_t)x.d_luma, s.pitch = pitch, s.plane_pitch = x.chroma_offset;
+    s.w = x.w, s.h = x.h, s.chans = 3, s.d_out = x.d_out, s.out_cap = x.out_cap;
+    s.layout = kEncSrcYuv + surface, s.sel = 0, s.px_bytes = (uint32_t)elem;
     return FPNG_AMD_OK;
 }
 
@@ -603,7 +650,7 @@ int check_source_pixels(const Source &s, bool planar)
     return FPNG_AMD_OK;
 }
 
-// Record i of a batch that check_batch(), and check_float_format() its fmt, have passed, as a Source: the one place that knows what
+// Record i of a batch that check_batch(), and check_float_format() / check_yuv_format() its fmt, have passed, as a Source: the one place that knows what
 // `records` points at and applies each kind's rules
 int read_source(const SourceBatch &b, uint32_t i, Source &s)
 {
@@ -611,6 +658,10 @@ int read_source(const SourceBatch &b, uint32_t i, Source &s)
     const bool planar = b.kind >= FPNG_AMD_DESC_PLANAR;
     const int64_t elem = !b.fmt ? 1 : b.fmt->dtype == FPNG_AMD_F32 ? 4 : 2; // bytes of a planar source's element
     int rc;
+    if (b.kind == kDescYuv) {
+        if ((rc = check_yuv_source(((const fpng_amd_yuv_frame *)b.records)[i], b.yuv->surface, s))) return rc;
+        return check_source_pixels(s, true);
+    }
     if (planar) {
         if ((rc = check_planar_source(((const fpng_amd_image_planar *)b.records)[i], elem, s))) return rc;
     } else if (b.kind == FPNG_AMD_DESC_EX) {
@@ -626,6 +677,16 @@ int read_source(const SourceBatch &b, uint32_t i, Source &s)
     return FPNG_AMD_OK;
 }
 
+// where a record's file goes, judged as every submit judges it (packed: the arena's the place, the record names none)
+int check_output(const Source &im, bool packed)
+{
+    if (packed && (im.d_out || im.out_cap)) return fail(FPNG_AMD_ERR_INVALID_ARG, "packed submission: d_out must be NULL and out_cap 0");
+    if (!packed && !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
+    if ((uintptr_t)im.d_out & 15) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
+    if (!packed && im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.chans)) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
+    return FPNG_AMD_OK;
+}
+
 // a row's local stream in dwords: at most L bits per filtered byte, L = the longest literal code of the table in use (12 for the
 // per-image tables of 2-pass, reference fpng.cpp:1111; run tokens need less per byte they cover), + end-of-block; rows start
 // 16-byte aligned and the 16-byte flush / assemble_kernel may touch up to four dwords past the stream.  Whole 128-byte lines
@@ -637,7 +698,8 @@ uint32_t local_stride(uint32_t bpl, uint32_t chans, bool two_pass)
 
 // Fills slot.jobs[0..n) for whole-image jobs and sizes the scratch buffers.  Only `slot` (which is free) and
 // the lane's device scratch are touched: the records of submissions in flight stay where they are.
-// b: a batch that check_batch() has passed (the float kind: the planes hold floats of b.fmt's type; pitches stay bytes).
+// b: a batch that check_batch() has passed (the float kind: the planes hold floats of b.fmt's type; pitches stay bytes; the YUV
+// kind: frames of b.yuv's surface).
 // packed (fpng_amd_encode_submit_packed): the records carry no outputs -- pack_place_kernel fills Job::out / out_cap on the device.
 int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc, const SourceBatch &b, uint32_t flags, Submission &sub, bool packed)
 {
@@ -653,16 +715,13 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
     sub.n = n;
     sub.src.kind = b.kind;
     if (b.fmt && (rc = check_float_format(b.fmt, sub.src.fq))) return rc;
-    sub.src.dtype = b.fmt ? b.fmt->dtype : 0;
+    if (b.yuv && (rc = check_yuv_format(b.yuv, sub.src.ym))) return rc;
+    sub.src.dtype = b.fmt ? b.fmt->dtype : b.yuv ? b.yuv->surface : 0;
     uint64_t px4 = 0, px4_wide = 0; // pixels of the 4-channel jobs, and of those with rows of kWideRowPixels and more
     for (uint32_t i = 0; i < n; i++) {
         Source im;
         if ((rc = read_source(b, i, im))) return rc;
-        if (packed && (im.d_out || im.out_cap)) return fail(FPNG_AMD_ERR_INVALID_ARG, "packed submission: d_out must be NULL and out_cap 0");
-        if (!packed && !im.d_out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null device pointer");
-        if ((uintptr_t)im.d_out & 15) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_out must be 16-byte aligned, RGBA d_pixels 4-byte aligned");
-        if (!packed && im.out_cap < fpng_amd_max_encoded_size(im.w, im.h, im.chans))
-            return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < fpng_amd_max_encoded_size()");
+        if ((rc = check_output(im, packed))) return rc;
         Job &j = slot.jobs.p[i];
         std::memset(&j, 0, sizeof j);
         j.rows = (const uint8_t *)im.base;
@@ -686,7 +745,7 @@ int prepare_jobs(fpng_amd_encoder *e, fpng_amd_encoder::Slot &slot, fpng_amd_enc
             j.pitch = im.pitch;
             j.plane_pitch = im.plane_pitch;
             j.sel = im.sel;
-            j.src_bytes = b.fmt ? kFloatLayout + b.fmt->dtype : im.px_bytes;
+            j.src_bytes = b.fmt ? kFloatLayout + b.fmt->dtype : b.yuv ? kYuvLayout + b.yuv->surface : im.px_bytes;
         }
         sub.src.mask |= im.chans == 4 ? 2u : (b.kind == FPNG_AMD_DESC_EX && im.px_bytes == 4 ? 4u : 1u);
         if (im.chans == 4) px4 += (uint64_t)im.w * im.h, px4_wide += im.w >= kWideRowPixels ? (uint64_t)im.w * im.h : 0u;
@@ -719,7 +778,7 @@ struct RenditionPlan {
     std::vector<uint64_t> dst_off, pre;
     std::vector<int64_t> nearest_at;
     std::vector<uint32_t> nearest;
-    FloatQuant fq = {};
+    EncConsts k = {};
     uint64_t scratch_bytes = 0;
     uint32_t lds = 0;
 };
@@ -733,10 +792,10 @@ static_assert(FPNG_AMD_RENDITION_BILINEAR == kResizeBilinear && FPNG_AMD_RENDITI
 enum { kRenditionOuts = 0, kRenditionPacked = 1, kRenditionNoOuts = 2 }; // how plan_renditions judges d_out and out_cap
 
 // the images of a renditions call, each judged as its kind's own submit judges it -- but for the outputs, which they have none of
-int rendition_sources(const SourceBatch &b, std::vector<Source> &out, FloatQuant &fq)
+int rendition_sources(const SourceBatch &b, std::vector<Source> &out, EncConsts &k)
 {
     int rc;
-    if ((rc = check_batch(b)) || (b.fmt && (rc = check_float_format(b.fmt, fq)))) return rc;
+    if ((rc = check_batch(b)) || (b.fmt && (rc = check_float_format(b.fmt, k.fq))) || (b.yuv && (rc = check_yuv_format(b.yuv, k.ym)))) return rc;
     out.resize(b.n);
     for (uint32_t i = 0; i < b.n; i++) {
         if ((rc = read_source(b, i, out[i]))) return rc;
@@ -750,7 +809,7 @@ int plan_renditions(const SourceBatch &images, const fpng_amd_rendition *renditi
 {
     std::vector<Source> src;
     int rc;
-    if ((rc = rendition_sources(images, src, plan.fq))) return rc;
+    if ((rc = rendition_sources(images, src, plan.k))) return rc;
     if (!renditions || !n) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty renditions");
     if (n > 65535) return fail(FPNG_AMD_ERR_INVALID_ARG, "more than 65535 renditions");
     plan.recs.resize(n), plan.dst_off.resize(n), plan.nearest_at.assign(n, -1), plan.pre.assign((size_t)n + 1, 0);
@@ -777,9 +836,12 @@ int plan_renditions(const SourceBatch &images, const fpng_amd_rendition *renditi
         }
         EncResize &e = plan.recs[k];
         std::memset(&e, 0, sizeof e);
-        e.src = (const uint8_t *)(uintptr_t)((int64_t)s.base + (int64_t)r.box_y * s.pitch + (int64_t)r.box_x * s.px_bytes);
         e.pitch = s.pitch, e.plane_pitch = s.plane_pitch;
         e.layout = s.layout, e.sel = s.sel, e.chans = s.chans, e.filter = r.filter;
+        if (s.layout >= kEncSrcYuv) // (the chroma of a 4:2:0 pixel follows its coordinates in the FRAME: the box's origin travels beside the frame's base)
+            e.src = (const uint8_t *)s.base, e.sel = r.box_x, e.reserved = r.box_y;
+        else
+            e.src = (const uint8_t *)(uintptr_t)((int64_t)s.base + (int64_t)r.box_y * s.pitch + (int64_t)r.box_x * s.px_bytes);
         e.in_w = bw, e.in_h = bh, e.w = r.w, e.h = r.h;
         // Pillow's Image.resize: NEAREST does not premultiply, and size == box is self.copy() before any conversion
         e.premul = s.chans == 4 && r.alpha_op == FPNG_AMD_ALPHA_PREMULTIPLIED && r.filter != kResizeNearest && !(r.w == bw && r.h == bh);
@@ -808,7 +870,7 @@ struct RenditionStage {
     const fpng_amd_rendition *renditions = nullptr;
     uint32_t n = 0;
     std::vector<fpng_amd_image> images; // n of them: the batch the call submits, filled in by stage_renditions()
-    size_t at_pre = 0, at_fq = 0, at_nearest = 0, rec_bytes = 0; // d_rend: EncResize[n], pre[n + 1], FloatQuant, the NEAREST indices
+    size_t at_pre = 0, at_fq = 0, at_nearest = 0, rec_bytes = 0; // d_rend: EncResize[n], pre[n + 1], EncConsts, the NEAREST indices
 };
 
 // Sizes the lane's scratch (growing it while the lane's previous submission runs is safe, as for every DeviceBuf: giving a block
@@ -818,7 +880,7 @@ int stage_renditions(fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc
     const uint32_t n = st.n;
     st.at_pre = (size_t)n * sizeof(EncResize);
     st.at_fq = st.at_pre + ((size_t)n + 1) * sizeof(uint64_t);
-    st.at_nearest = st.at_fq + sizeof(FloatQuant);
+    st.at_nearest = st.at_fq + sizeof(EncConsts);
     st.rec_bytes = st.at_nearest + st.plan.nearest.size() * sizeof(uint32_t);
     int rc;
     if ((rc = sc.d_resized.ensure(st.plan.scratch_bytes)) || (rc = sc.d_rend.ensure(st.rec_bytes)) || (rc = slot.rend.ensure(st.rec_bytes))) return rc;
@@ -834,7 +896,7 @@ int stage_renditions(fpng_amd_encoder::Slot &slot, fpng_amd_encoder::Scratch &sc
     }
     std::memcpy(slot.rend.p, st.plan.recs.data(), st.at_pre);
     std::memcpy(slot.rend.p + st.at_pre, st.plan.pre.data(), st.at_fq - st.at_pre);
-    std::memcpy(slot.rend.p + st.at_fq, &st.plan.fq, sizeof(FloatQuant));
+    std::memcpy(slot.rend.p + st.at_fq, &st.plan.k, sizeof(EncConsts));
     if (!st.plan.nearest.empty()) std::memcpy(slot.rend.p + st.at_nearest, st.plan.nearest.data(), st.rec_bytes - st.at_nearest);
     return FPNG_AMD_OK;
 }
@@ -843,7 +905,7 @@ int launch_renditions(hipStream_t s, fpng_amd_encoder::Slot &slot, fpng_amd_enco
 {
     HIP_TRY(hipMemcpyAsync(sc.d_rend.p, slot.rend.p, st.rec_bytes, hipMemcpyHostToDevice, s));
     if (!launch_enc_resize(s, (const EncResize *)sc.d_rend.p, (const uint64_t *)(sc.d_rend.p + st.at_pre), st.plan.pre.data(), st.n, st.plan.lds,
-                           (const FloatQuant *)(sc.d_rend.p + st.at_fq)))
+                           (const EncConsts *)(sc.d_rend.p + st.at_fq), st.plan.recs[0].layout >= kEncSrcYuv))
         return fail(FPNG_AMD_ERR_UNSUPPORTED, "the renditions' resize could not be launched");
     HIP_TRY(hipGetLastError());
     return FPNG_AMD_OK;
@@ -1020,6 +1082,14 @@ int submit(fpng_amd_encoder *e, const SourceBatch &batch, uint32_t flags, uint64
     return FPNG_AMD_OK;
 }
 
+// the tight R,G,B bytes of a whole frame of surface S whose planes lie in HOST memory: yuv.h's accessor, pixel by pixel
+template <uint32_t S> void yuv_frame_pixels(const Source &s, const YuvMatrix &ym, uint8_t *out)
+{
+    for (uint32_t y = 0; y < s.h; y++)
+        for (uint32_t x = 0; x < s.w; x++)
+            for (uint32_t c = 0; c < 3; c++) *out++ = (uint8_t)yuv_channel<S>((const uint8_t *)s.base, s.pitch, s.plane_pitch, ym, c, x, y);
+}
+
 fpng_amd_encoder::Slot *slot_of(fpng_amd_encoder *e, uint64_t ticket)
 {
     if (!ticket || ticket > e->submitted || ticket + fpng_amd_encoder::kSlots <= e->submitted) return nullptr;
@@ -1091,12 +1161,11 @@ int fpng_amd_renditions_plan(uint32_t desc_kind, const void *images, uint32_t n_
 
 // The resize stage on the host: what enc_resize_kernel computes, tile by tile, here for the whole rendition at once -- the same
 // weights (resample_tile_weights), the same sums through the same accessor (enc_row_sum), the same clamps and the same U
-int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt, const fpng_amd_rendition *rendition,
-                              uint8_t *out, size_t out_cap)
+static int rendition_pixels(const SourceBatch &images, const fpng_amd_rendition *rendition, uint8_t *out, size_t out_cap)
 {
     RenditionPlan plan;
     if (!out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null out");
-    if (int rc = plan_renditions({desc_kind, images, n_images, fmt}, rendition, rendition ? 1u : 0u, kRenditionNoOuts, plan)) return rc;
+    if (int rc = plan_renditions(images, rendition, rendition ? 1u : 0u, kRenditionNoOuts, plan)) return rc;
     EncResize r = plan.recs[0];
     r.nearest = plan.nearest.empty() ? nullptr : plan.nearest.data();
     const size_t w = r.w, h = r.h, C = r.chans;
@@ -1117,7 +1186,7 @@ int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n
                 t[0] = (uint8_t)resize_clip8(s.c0), t[plane] = (uint8_t)resize_clip8(s.c1), t[2 * plane] = (uint8_t)resize_clip8(s.c2);
                 if (C == 4) t[3 * plane] = (uint8_t)resize_clip8(s.c3);
             } else
-                for (uint32_t c = 0; c < C; c++) t[c * plane] = (uint8_t)resize_clip8(enc_row_sum(r, plan.fq, c, y, fx[o], cx[o], K, 1));
+                for (uint32_t c = 0; c < C; c++) t[c * plane] = (uint8_t)resize_clip8(r.layout >= kEncSrcYuv ? enc_row_sum<true>(r, plan.k, c, y, fx[o], cx[o], K, 1) : enc_row_sum<false>(r, plan.k, c, y, fx[o], cx[o], K, 1));
         }
     for (uint32_t c = 0; c < C; c++)
         for (uint32_t q = 0; q < h; q++)
@@ -1129,6 +1198,85 @@ int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n
     for (size_t i = 0; i < w * h; i++) {
         const uint32_t v = r.premul ? enc_unmul_pixel(px[i]) : px[i];
         for (uint32_t c = 0; c < C; c++) out[i * C + c] = (uint8_t)(v >> (8 * c));
+    }
+    return FPNG_AMD_OK;
+}
+int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt, const fpng_amd_rendition *rendition,
+                              uint8_t *out, size_t out_cap)
+{
+    return rendition_pixels({desc_kind, images, n_images, fmt}, rendition, out, out_cap);
+}
+
+// ---- YUV video frames (include/fpng_amd.h; the rule: yuv.h) ----
+// Everything is judged here, before the encoder is looked at: nothing is launched, no ticket handed out
+int fpng_amd_encode_submit_yuv(fpng_amd_encoder *e, const fpng_amd_yuv_frame *frames, uint32_t n_frames, const fpng_amd_yuv_format *fmt,
+                               const fpng_amd_rendition *renditions, uint32_t n_renditions, uint32_t flags, const fpng_amd_pack *pack, uint64_t *ticket)
+{
+    if (!fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null fmt");
+    const SourceBatch batch = {kDescYuv, frames, n_frames, nullptr, fmt};
+    int rc;
+    if (pack && (rc = check_pack(pack))) return rc;
+    if (renditions || n_renditions) { // the files are the renditions': fpng_amd_encode_submit_renditions over these frames
+        RenditionStage st;
+        if ((rc = plan_renditions(batch, renditions, n_renditions, pack ? kRenditionPacked : kRenditionOuts, st.plan))) return rc;
+        st.renditions = renditions, st.n = n_renditions;
+        st.images.resize(n_renditions);
+        return submit(e, {FPNG_AMD_DESC_IMAGE, st.images.data(), n_renditions}, flags, ticket, pack, &st);
+    }
+    YuvMatrix ym;
+    if ((rc = check_batch(batch)) || (rc = check_yuv_format(fmt, ym))) return rc;
+    for (uint32_t i = 0; i < n_frames; i++) {
+        Source s;
+        if ((rc = read_source(batch, i, s)) || (rc = check_output(s, pack != nullptr))) return rc;
+    }
+    return submit(e, batch, flags, ticket, pack);
+}
+
+int fpng_amd_yuv_matrix(uint32_t standard, int full_range, float m[12])
+{
+    static const double kKr[3] = {0.299, 0.2126, 0.2627}, kKb[3] = {0.114, 0.0722, 0.0593}; // BT.601, BT.709, BT.2020
+    if (standard > FPNG_AMD_YUV_BT2020) return fail(FPNG_AMD_ERR_INVALID_ARG, "standard is FPNG_AMD_YUV_BT601, _BT709 or _BT2020");
+    if (!m) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    const double kr = kKr[standard], kb = kKb[standard], kg = 1.0 - kr - kb;
+    const double sy = full_range ? 1.0 : 255.0 / 219.0, sc = full_range ? 1.0 : 255.0 / 224.0, y0 = full_range ? 0.0 : 16.0;
+    const double coef[3][3] = {{sy, 0.0, 2.0 * (1.0 - kr) * sc},
+                               {sy, -(2.0 * kb * (1.0 - kb) / kg) * sc, -(2.0 * kr * (1.0 - kr) / kg) * sc},
+                               {sy, 2.0 * (1.0 - kb) * sc, 0.0}};
+    for (int c = 0; c < 3; c++) {
+        float *const row = m + 4 * c;
+        for (int k = 0; k < 3; k++) row[k] = (float)coef[c][k];
+        // from the ROUNDED coefficients: every grey (k, 128, 128) then comes out as a grey
+        row[3] = (float)(-((double)row[0] * y0 + 128.0 * (double)row[1] + 128.0 * (double)row[2]));
+    }
+    return FPNG_AMD_OK;
+}
+
+int fpng_amd_yuv_pixels(const fpng_amd_yuv_frame *frames, uint32_t n_frames, const fpng_amd_yuv_format *fmt, uint32_t frame_index,
+                        const fpng_amd_rendition *rendition, uint8_t *out, size_t out_cap)
+{
+    if (!fmt) return fail(FPNG_AMD_ERR_INVALID_ARG, "null fmt");
+    if (!out) return fail(FPNG_AMD_ERR_INVALID_ARG, "null out");
+    const SourceBatch batch = {kDescYuv, frames, n_frames, nullptr, fmt};
+    if (rendition) { // the renditions' twin over the frames, the rendition taken of frame frame_index
+        fpng_amd_rendition r = *rendition;
+        r.image = frame_index;
+        return rendition_pixels(batch, &r, out, out_cap);
+    }
+    YuvMatrix ym;
+    int rc;
+    if ((rc = check_batch(batch)) || (rc = check_yuv_format(fmt, ym))) return rc;
+    if (frame_index >= n_frames) return fail(FPNG_AMD_ERR_INVALID_ARG, "frame_index >= n_frames");
+    Source s, chosen = {};
+    for (uint32_t i = 0; i < n_frames; i++) {
+        if ((rc = read_source(batch, i, s))) return rc;
+        if (i == frame_index) chosen = s;
+    }
+    if (out_cap < (size_t)chosen.w * chosen.h * 3) return fail(FPNG_AMD_ERR_BUFFER_TOO_SMALL, "out_cap < w * h * 3");
+    switch (fmt->surface) {
+    case FPNG_AMD_YUV_NV12: yuv_frame_pixels<kYuvNV12>(chosen, ym, out); break;
+    case FPNG_AMD_YUV_P016: yuv_frame_pixels<kYuvP016>(chosen, ym, out); break;
+    case FPNG_AMD_YUV_444: yuv_frame_pixels<kYuv444>(chosen, ym, out); break;
+    default: yuv_frame_pixels<kYuv444_16>(chosen, ym, out); break;
     }
     return FPNG_AMD_OK;
 }

@@ -1,7 +1,7 @@
 // encode_resize.h -- the front stage of fpng_amd_encode_submit_renditions (include/fpng_amd.h): a RENDITION of a device image --
 // img.crop(box).resize((w, h), filter) as Pillow computes it -- resampled from the source AS IT LIES (any of the four descriptor
 // kinds: interleaved in every FPNG_AMD_SRC_* format with a signed pitch, planar uint8 with signed row and plane pitches, planar
-// floats through quantize.h) into tight R,G,B[,A] rows that the unchanged encode chain then reads like any fpng_amd_image.
+// floats through quantize.h; and the YUV surfaces of fpng_amd_encode_submit_yuv through yuv.h) into tight R,G,B[,A] rows that the unchanged encode chain then reads like any fpng_amd_image.
 //
 // The rule of the resize is resize.h's, untouched, with `in` = the BOX's size: taps never leave the box.  The alpha rule is
 // view_alpha.h's PREMULTIPLIED op (M on load, U on store).  What is new is the source accessor below and the tight interleaved
@@ -19,6 +19,7 @@
 #include "quantize.h"
 #include "resize.h"
 #include "view_alpha.h"
+#include "yuv.h"
 
 namespace fpng_amd {
 
@@ -27,11 +28,21 @@ constexpr uint32_t kEncSrcBytes3 = 0;  // interleaved, 3 source bytes per pixel,
 constexpr uint32_t kEncSrcBytes4 = 1;  // interleaved, 4 source bytes per pixel, base and pitch multiples of 4: one aligned dword per pixel
 constexpr uint32_t kEncSrcPlanar = 2;  // planar uint8
 constexpr uint32_t kEncSrcFloat = 3;   // + kF32 / kF16 / kBF16: planar floats, quantised per element (quantize.h)
-constexpr uint32_t kEncSrcLayouts = 6;
+constexpr uint32_t kEncSrcYuv = 6;     // + FPNG_AMD_YUV_*: a YUV surface, converted per pixel (yuv.h)
+constexpr uint32_t kEncSrcLayouts = 10;
+
+// the constants of a submission's sources, behind the records in the kernel's memory: the float kind's, the YUV kind's
+struct EncConsts {
+    FloatQuant fq;
+    YuvMatrix ym;
+};
 
 // a rendition's work for enc_resize_kernel.  src: channel data of pixel (0, 0) of the BOX -- the first byte of its source pixel
 // (interleaved), or its element in the R plane (planar); pitch: signed bytes between rows; plane_pitch: signed bytes from one
 // channel's plane to the next (planar); sel: kSrcFormats' selector, byte k = the source byte of channel k (interleaved).
+// YUV surfaces: src = the luma plane's top row of the FRAME, plane_pitch = the chroma offset, and the box's origin travels in
+// sel (x) and reserved (y) -- a 4:2:0 pixel's chroma index depends on its ABSOLUTE coordinates, so a box with an odd origin cannot
+// be folded into src as the other layouts fold theirs.
 // dst: the tight rows, w * chans bytes each.  premul: view_alpha.h's PREMULTIPLIED op is in force (4 channels, not NEAREST, not
 // the identity: the host's rule).  nearest: a NEAREST rendition's indices, the w columns' and then the h rows', as samples of the
 // box (the host's resize_nearest_indices), else NULL
@@ -45,7 +56,7 @@ struct EncResize {
     uint32_t premul;
     uint32_t taps_x, taps_y, rows; // what the tile's LDS is laid out with (resize_max_taps, resize_tile_rows)
     uint32_t fused;                // enc_resize_fused(): the horizontal pass makes all channels at once, T has a plane of `rows` rows per channel
-    uint32_t reserved;
+    uint32_t reserved;             // YUV surfaces: the box's first row in the frame
 };
 static_assert(sizeof(EncResize) == 96 && offsetof(EncResize, nearest) == 32 && offsetof(EncResize, layout) == 40 && offsetof(EncResize, rows) == 84 && offsetof(EncResize, fused) == 88,
               "EncResize layout");
@@ -56,9 +67,11 @@ typedef uint16_t __attribute__((may_alias, aligned(2))) enc_u16_any;
 // THE ACCESSOR: channel c (the file's: R, G, B, A = 0 .. 3) of pixel (x, y) of the box, as the byte the file's pixel is made of.
 // Only bytes of that pixel are read (kEncSrcBytes4: the aligned dword that is the pixel); L: the record's layout, known where
 // this is compiled
-template <uint32_t L> FPNG_RESIZE_FN uint32_t enc_src_channel(const EncResize &r, const FloatQuant &fq, uint32_t c, uint32_t x, uint32_t y)
+template <uint32_t L> FPNG_RESIZE_FN uint32_t enc_src_channel(const EncResize &r, const EncConsts &k, uint32_t c, uint32_t x, uint32_t y)
 {
-    if constexpr (L == kEncSrcBytes3) {
+    if constexpr (L >= kEncSrcYuv) {
+        return yuv_channel<L - kEncSrcYuv>(r.src, r.pitch, r.plane_pitch, k.ym, c, r.sel + x, r.reserved + y);
+    } else if constexpr (L == kEncSrcBytes3) {
         return (r.src + (int64_t)y * r.pitch + (uint64_t)x * 3u)[r.sel >> (8u * c) & 0xFFu];
     } else if constexpr (L == kEncSrcBytes4) {
         return *(const enc_u32_any *)(r.src + (int64_t)y * r.pitch + (uint64_t)x * 4u) >> (8u * (r.sel >> (8u * c) & 3u)) & 0xFFu;
@@ -67,9 +80,9 @@ template <uint32_t L> FPNG_RESIZE_FN uint32_t enc_src_channel(const EncResize &r
         if constexpr (L == kEncSrcPlanar) return row[x];
         else {
             constexpr uint32_t DT = L - kEncSrcFloat;
-            // (fq lies in memory -- the kernel's in global memory behind its records: an index into a kernel ARGUMENT would put
+            // (k lies in memory -- the kernel's in global memory behind its records: an index into a kernel ARGUMENT would put
             //  the argument into private memory)
-            const float sc = fq.scale[c], bi = fq.bias[c];
+            const float sc = k.fq.scale[c], bi = k.fq.bias[c];
             const uint32_t bits = DT == kF32 ? *(const enc_u32_any *)(row + (uint64_t)x * 4u) : (uint32_t) * (const enc_u16_any *)(row + (uint64_t)x * 2u);
             return quantize(widen<DT>(bits), sc, bi);
         }
@@ -78,30 +91,41 @@ template <uint32_t L> FPNG_RESIZE_FN uint32_t enc_src_channel(const EncResize &r
 
 // one output sample of the horizontal pass: 2^21 + the sum over its `count` taps, columns first .. first + count - 1 of row y of
 // the box, of P'_c * K[t * stride] -- P' = M(P_c, P_3) for a colour channel of a premultiplied rendition, else the channel's byte
-template <uint32_t L, bool kMul> FPNG_RESIZE_FN int32_t enc_row_sum_of(const EncResize &r, const FloatQuant &fq, uint32_t c, uint32_t y, uint32_t first, uint32_t count, const int32_t *K, uint32_t stride)
+template <uint32_t L, bool kMul> FPNG_RESIZE_FN int32_t enc_row_sum_of(const EncResize &r, const EncConsts &k, uint32_t c, uint32_t y, uint32_t first, uint32_t count, const int32_t *K, uint32_t stride)
 {
     int32_t sum = 1 << (kResizeBits - 1);
     for (uint32_t t = 0; t < count; t++) {
-        uint32_t v = enc_src_channel<L>(r, fq, c, first + t, y);
-        if constexpr (kMul) v = alpha_mul(v, enc_src_channel<L>(r, fq, 3u, first + t, y));
+        uint32_t v = enc_src_channel<L>(r, k, c, first + t, y);
+        if constexpr (kMul) v = alpha_mul(v, enc_src_channel<L>(r, k, 3u, first + t, y));
         sum += (int32_t)v * K[t * stride];
     }
     return sum;
 }
-template <uint32_t L> FPNG_RESIZE_FN int32_t enc_row_sum_layout(const EncResize &r, const FloatQuant &fq, uint32_t c, uint32_t y, uint32_t first, uint32_t count, const int32_t *K, uint32_t stride)
+template <uint32_t L> FPNG_RESIZE_FN int32_t enc_row_sum_layout(const EncResize &r, const EncConsts &k, uint32_t c, uint32_t y, uint32_t first, uint32_t count, const int32_t *K, uint32_t stride)
 {
-    return r.premul && c < 3u ? enc_row_sum_of<L, true>(r, fq, c, y, first, count, K, stride) : enc_row_sum_of<L, false>(r, fq, c, y, first, count, K, stride);
+    if constexpr (L >= kEncSrcYuv) return enc_row_sum_of<L, false>(r, k, c, y, first, count, K, stride); // (three channels: never premultiplied)
+    else return r.premul && c < 3u ? enc_row_sum_of<L, true>(r, k, c, y, first, count, K, stride) : enc_row_sum_of<L, false>(r, k, c, y, first, count, K, stride);
 }
-// the same with the layout as a value (the same for all of a workgroup's threads)
-FPNG_RESIZE_FN int32_t enc_row_sum(const EncResize &r, const FloatQuant &fq, uint32_t c, uint32_t y, uint32_t first, uint32_t count, const int32_t *K, uint32_t stride)
+// the same with the layout as a value (the same for all of a workgroup's threads).  kYuv: the record's layout is one of the YUV
+// surfaces' (all records of a submission are, or none is).  They have a text of their own so that the kernel of the other
+// layouts stays the one it was: with the four surfaces in ONE switch enc_resize_kernel needs 177 vector registers instead of 136
+template <bool kYuv> FPNG_RESIZE_FN int32_t enc_row_sum(const EncResize &r, const EncConsts &k, uint32_t c, uint32_t y, uint32_t first, uint32_t count, const int32_t *K, uint32_t stride)
 {
+    if constexpr (kYuv) {
+        switch (r.layout) {
+        case kEncSrcYuv + kYuvNV12: return enc_row_sum_layout<kEncSrcYuv + kYuvNV12>(r, k, c, y, first, count, K, stride);
+        case kEncSrcYuv + kYuvP016: return enc_row_sum_layout<kEncSrcYuv + kYuvP016>(r, k, c, y, first, count, K, stride);
+        case kEncSrcYuv + kYuv444: return enc_row_sum_layout<kEncSrcYuv + kYuv444>(r, k, c, y, first, count, K, stride);
+        default: return enc_row_sum_layout<kEncSrcYuv + kYuv444_16>(r, k, c, y, first, count, K, stride);
+        }
+    }
     switch (r.layout) {
-    case kEncSrcBytes3: return enc_row_sum_layout<kEncSrcBytes3>(r, fq, c, y, first, count, K, stride);
-    case kEncSrcBytes4: return enc_row_sum_layout<kEncSrcBytes4>(r, fq, c, y, first, count, K, stride);
-    case kEncSrcPlanar: return enc_row_sum_layout<kEncSrcPlanar>(r, fq, c, y, first, count, K, stride);
-    case kEncSrcFloat + kF32: return enc_row_sum_layout<kEncSrcFloat + kF32>(r, fq, c, y, first, count, K, stride);
-    case kEncSrcFloat + kF16: return enc_row_sum_layout<kEncSrcFloat + kF16>(r, fq, c, y, first, count, K, stride);
-    default: return enc_row_sum_layout<kEncSrcFloat + kBF16>(r, fq, c, y, first, count, K, stride);
+    case kEncSrcBytes3: return enc_row_sum_layout<kEncSrcBytes3>(r, k, c, y, first, count, K, stride);
+    case kEncSrcBytes4: return enc_row_sum_layout<kEncSrcBytes4>(r, k, c, y, first, count, K, stride);
+    case kEncSrcPlanar: return enc_row_sum_layout<kEncSrcPlanar>(r, k, c, y, first, count, K, stride);
+    case kEncSrcFloat + kF32: return enc_row_sum_layout<kEncSrcFloat + kF32>(r, k, c, y, first, count, K, stride);
+    case kEncSrcFloat + kF16: return enc_row_sum_layout<kEncSrcFloat + kF16>(r, k, c, y, first, count, K, stride);
+    default: return enc_row_sum_layout<kEncSrcFloat + kBF16>(r, k, c, y, first, count, K, stride);
     }
 }
 
@@ -146,7 +170,7 @@ constexpr uint32_t kEncResizeMaxLds = 65536u; // what a launch may ask for (laun
 // How the channels share the LDS: a 4-byte interleaved source whose tile, with T once per channel, stays within 32 KB (reductions up
 // to about 8 x; so that as many workgroups fit a compute unit as before) runs the FUSED horizontal pass -- one load per tap for all
 // channels (enc_row_sums4).  Every other rendition's channels take turns in one T (enc_row_sum), whatever its scale: the limits'
-// 55 KB tiles among them
+// 55 KB tiles among them, and every YUV surface (no fused pass for those layouts)
 constexpr uint32_t kEncResizeFusedLds = 32768u;
 FPNG_RESIZE_FN bool enc_resize_fused(uint32_t layout, uint32_t taps_x, uint32_t taps_y, uint32_t rows, uint32_t chans)
 {
@@ -166,8 +190,9 @@ FPNG_RESIZE_FN uint64_t enc_resize_scratch_bytes(uint64_t cursor) { return ((cur
 
 // An exact grid as launch_dec_resize_hwc's, a workgroup per (record, tile): pre (device) and h_pre (host, the same words) hold n + 1
 // entries, the TILES of the submission's records in front of each of recs[0 .. n].  lds_bytes: the most enc_resize_tile_lds() of the
-// records.  fq (device): the submission's float constants (read for float sources only).  false: a record without or with too
+// records.  consts (device): the submission's constants (read for float sources and YUV surfaces only).  yuv: the records are
+// those of YUV frames (enc_resize_kernel<true>).  false: a record without or with too
 // many tiles, or lds_bytes above kEncResizeMaxLds; nothing more is launched.
-bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const FloatQuant *fq);
+bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const EncConsts *consts, bool yuv = false);
 
 } // namespace fpng_amd

@@ -28,7 +28,8 @@ namespace fpng_amd {
 
 namespace {
 
-__global__ __launch_bounds__(kResizeBlock) void enc_resize_kernel(const EncResize *recs, const uint64_t *pre, uint32_t n, const FloatQuant *__restrict__ fq_in)
+// kYuv: the submission's sources are YUV surfaces (enc_row_sum<true>)
+template <bool kYuv> __global__ __launch_bounds__(kResizeBlock) void enc_resize_kernel(const EncResize *recs, const uint64_t *pre, uint32_t n, const EncConsts *__restrict__ consts_in)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t enc_resize_lds[];
     const uint64_t g = pre[0] + blockIdx.x;
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(kResizeBlock) void enc_resize_kernel(const EncResiz
         else hi = mid;
     }
     const EncResize r = recs[lo];
-    const FloatQuant &fq = *fq_in;
+    const EncConsts &consts = *consts_in;
     const uint32_t C = r.chans;
     const uint32_t tile = (uint32_t)(g - pre[lo]);
     if ((uint64_t)tile >= resize_tiles(r.w, r.h)) return; // (never, with the host's pre)
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(kResizeBlock) void enc_resize_kernel(const EncResiz
     } else
         for (uint32_t c = 0; c < C; c++) {
             if (c) __syncthreads(); // (the channel before has been read out of T)
-            for (uint32_t j = wave; j < nrows; j += kWaves) T[j * kResizeTileW + o] = (uint8_t)resize_clip8(enc_row_sum(r, fq, c, row0 + j, first_x, count_x, Kx + o, kResizeTileW));
+            for (uint32_t j = wave; j < nrows; j += kWaves) T[j * kResizeTileW + o] = (uint8_t)resize_clip8(enc_row_sum<kYuv>(r, consts, c, row0 + j, first_x, count_x, Kx + o, kResizeTileW));
             __syncthreads();
             vertical(T, c);
         }
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(kResizeBlock) void enc_resize_kernel(const EncResiz
 
 } // namespace
 
-bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const FloatQuant *fq)
+bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const EncConsts *consts, bool yuv)
 {
     // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
     constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
@@ -145,7 +146,7 @@ bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre
         uint32_t r1 = r0 + 1;
         if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
         while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(enc_resize_kernel, dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, fq);
+        hipLaunchKernelGGL(yuv ? enc_resize_kernel<true> : enc_resize_kernel<false>, dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, consts);
         r0 = r1;
     }
     return true;

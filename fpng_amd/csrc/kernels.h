@@ -22,8 +22,15 @@ constexpr int kFormPlanar = 1; // fpng_amd_encode_submit_planar
 constexpr int kFormEx = 2;     // an _ex job of either pixel size, read from the job at run time (never in Job::src_bytes; the row walk has none)
 constexpr int kFormEx3 = 3, kFormEx4 = 4; // fpng_amd_encode_submit_ex
 constexpr int kFloatLayout = 16; // + dtype (FPNG_AMD_F32 / _F16 / _BF16): fpng_amd_encode_submit_planar_float
-constexpr bool is_float_layout(int form) { return form >= kFloatLayout; }
-constexpr bool is_planar_layout(int form) { return form == kFormPlanar || is_float_layout(form); }
+constexpr int kYuvLayout = 32;   // + surface (FPNG_AMD_YUV_*): fpng_amd_encode_submit_yuv -- always 3 channels in the file
+constexpr int kYuvSurfaces = 4;
+constexpr bool is_float_layout(int form) { return form >= kFloatLayout && form < kYuvLayout; }
+constexpr bool is_yuv_layout(int form) { return form >= kYuvLayout && form < kYuvLayout + kYuvSurfaces; }
+// (YUV surfaces are walked as planar ones: their loads hand the walk a lane's bytes per FILE channel, yuv.h's rule applied)
+constexpr bool is_planar_layout(int form) { return form == kFormPlanar || is_float_layout(form) || is_yuv_layout(form); }
+// SourceForms::kind of a YUV batch: an internal kind, reached through fpng_amd_encode_submit_yuv only -- the generic entry points
+// keep refusing it as an unknown desc_kind, and there is no public FPNG_AMD_DESC_* name for it
+constexpr uint32_t kDescYuv = 4;
 
 // One unit of work: a whole image, or a band of rows of one image (multi-GPU).
 struct Job {
@@ -50,7 +57,9 @@ struct Job {
     // was, so the other kernels' code is, instruction for instruction, the same (tools/isa_diff.py)
     int64_t pitch;            // signed bytes from one row to the next
     uint32_t src_bytes;       // the job's source form (kForm*, above):kFormEx3 / kFormEx4 = the bytes of a source pixel; kFormPlanar: a byte per pixel
-                              // and plane; kFloatLayout + dtype: planes of floats, pitches in bytes of the float source
+                              // and plane; kFloatLayout + dtype: planes of floats, pitches in bytes of the float source;
+                              // kYuvLayout + surface: `rows` = the luma plane's top row, `pitch` = the row pitch of all planes,
+                              // `plane_pitch` = the chroma offset (yuv.h)
     uint32_t sel;
     int64_t plane_pitch;      // planar jobs: signed bytes from one channel's plane to the next (R -> G -> B [-> A]); `rows` is the R plane's top row
     uint8_t png_header[60];   // 58 bytes used (reference fpng.cpp:1767-1791), IDAT length patched on device
@@ -110,18 +119,24 @@ void build_crc_device_tables(CrcDeviceTables *t);
 struct FloatQuant {
     float scale[4], bias[4]; // per file channel R, G, B, A
 };
+// the 3 x 4 matrix of a YUV submission (yuv.h): file channel c = m[c][0] Y + m[c][1] Cb + m[c][2] Cr + m[c][3]
+struct YuvMatrix {
+    float m[3][4];
+};
 struct SourceForms {
-    // FPNG_AMD_DESC_* of the batch.  _IMAGE: kFormPacked jobs; _EX: jobs with a source layout (Job::pitch / src_bytes / sel);
+    // FPNG_AMD_DESC_* of the batch, or kDescYuv.  _IMAGE: kFormPacked jobs; _EX: jobs with a source layout (Job::pitch / src_bytes / sel);
     // _PLANAR: planar jobs (Job::plane_pitch); _PLANAR_FLOAT: planar jobs whose planes hold elements of `dtype`, which the kernels turn
     // into bytes as they load them (quantize.h) -- fq's constants are the submission's and travel in the kernel arguments: the Job record is full
     uint32_t kind = FPNG_AMD_DESC_IMAGE;
-    uint32_t dtype = 0; // FPNG_AMD_F32 / _F16 / _BF16
+    // kDescYuv: jobs of kYuvLayout + dtype, dtype = the surface; ym's matrix travels as fq does
+    uint32_t dtype = 0; // FPNG_AMD_F32 / _F16 / _BF16; kDescYuv: FPNG_AMD_YUV_*
     // one row kernel instantiation per bit.  _EX: bit 0 = 3-byte sources, bit 1 = 4-byte sources with 4 channels, bit 2 = 4-byte sources
     // with 3; every other kind: bit 0 = the batch has 3-channel jobs, bit 1 = 4-channel jobs
     uint32_t mask = 0;
     // _IMAGE, _EX: the 4-channel jobs' pixels lie mostly in rows of kWideRowPixels and more (their walk then runs with seven waves per SIMD instead of eight: kernels.hip)
     bool wide4 = false;
     FloatQuant fq = {};
+    YuvMatrix ym = {};
 };
 constexpr uint32_t kWideRowPixels = 3584; // (same-box A/B: 3840-pixel rows gain with six waves, 3072-pixel rows lose 1 % in 1-pass)
 // one plain image or row band of `chans` channels and rows of w pixels

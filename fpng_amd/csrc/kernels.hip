@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "crc_device.h"
 #include "quantize.h"
+#include "yuv.h"
 
 #include <hip/hip_runtime.h>
 
@@ -95,6 +96,12 @@ constexpr uint32_t kStoredExBlocks = 64; // stored_kernel: workgroups per image
 #endif
 #ifndef FPNG_ROWS_WPE_FLOAT4_F32
 #define FPNG_ROWS_WPE_FLOAT4_F32 4
+#endif
+// the YUV walks (encode_rows_kernel<3, WPE, kYuvLayout + surface, YuvMatrix>): the planar walk over two (4:2:0) or three (4:4:4) source
+// planes of bytes or 16-bit words, converted to the file's three bytes per pixel as they arrive (yuv.h).  Six waves per SIMD as the other
+// 3-channel planar walks; registers and scratch: profiles/yuv_encode_kernel_resources.txt
+#ifndef FPNG_ROWS_WPE_YUV
+#define FPNG_ROWS_WPE_YUV 6
 #endif
 constexpr int kStageDwords = FPNG_STAGE_DWORDS; // per-wave LDS staging window of the output bit stream
 // Local-stream stores carry the non-temporal hint (build with -DFPNG_LOCAL_NT=0 to A/B it: the hint decides whether the
@@ -552,6 +559,138 @@ template <int C> struct RowWindows<C, (int)(kFloatLayout + kF32)> : FloatRowWind
 template <int C> struct RowWindows<C, (int)(kFloatLayout + kF16)> : FloatRowWindows<C, kF16> {};
 template <int C> struct RowWindows<C, (int)(kFloatLayout + kBF16)> : FloatRowWindows<C, kBF16> {};
 
+// L = kYuvLayout + surface: a YUV video surface (fpng_amd_encode_submit_yuv) -- FloatRowWindows with the surface's two (4:2:0: luma,
+// interleaved Cb,Cr) or three (4:4:4: Y, Cb, Cr) planes in the place of the file's channels, elements of one or two bytes, and
+// yuv.h's rule in the place of quantize(): every pixel is turned into its three FILE bytes as soon as its elements are loaded, the
+// row above too (Up subtracts the CONVERTED row; for an even row that one has another chroma row), so that filter() and the
+// super-windows' filt hand the walk what the planar layout does.  8-bit planes start at any byte, 16-bit ones at a multiple of two:
+// the resources' bases are aligned down to a dword, with a phase per plane.  A 4:2:0 lane's four pixels are two chroma pairs: their
+// bytes lie at the byte offsets in the chroma row at which its four luma elements lie in the luma row, so both are the same loads.
+// A missing Up row is a zero-sized resource whose elements read 0, which the matrix does not turn into 0: up_mask clears those bytes.
+template <uint32_t S> struct YuvRowWindows {
+    static constexpr int SB = (int)yuv_elem_bytes(S); // bytes per element
+    static constexpr int NP = yuv_planes(S);
+    static constexpr bool k420 = yuv_is_420(S);
+    __amdgpu_buffer_rsrc_t cur[NP], up[NP];
+    uint32_t phase[NP], up_phase[NP];
+    uint32_t up_mask = 0;
+    float m[3][4];
+    uint32_t sel = 0;
+    uint32_t lane_ = 0;
+
+    // luma: the luma plane's top row (Job::rows); pitch: of every plane; r: the row of the frame (whole images: y0 == 0); has_up: the
+    // file's row r has a row above it; w: pixels of a row
+    __device__ __forceinline__ void init_planes(const uint8_t *luma, int64_t pitch, int64_t chroma_offset, uint32_t r, bool has_up, uint32_t w, uint32_t lane, const YuvMatrix &ym)
+    {
+        lane_ = lane;
+        up_mask = has_up ? ~0u : 0u;
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) m[c][k] = ym.m[c][k];
+        const uint32_t ru = has_up ? r - 1u : r;
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            const bool half = k420 && p; // the chroma plane of a 4:2:0 surface: a row per two rows of the frame
+            const uint32_t bytes = half ? (uint32_t)yuv_chroma_row_bytes(S, w) : w * (uint32_t)SB;
+            const uint8_t *plane = luma + (int64_t)p * chroma_offset;
+            const uint8_t *rp = plane + (int64_t)(half ? r >> 1 : r) * pitch;
+            const uint32_t a = uniform((uint32_t)((uintptr_t)rp & 3));
+            phase[p] = a;
+            cur[p] = make_rsrc(rp - a, (a + bytes + 3) & ~3u);
+            // (branch-free, as in the primary template: no Up row -> a zero-sized resource, reads return 0)
+            const uint8_t *ub = plane + (int64_t)(half ? ru >> 1 : ru) * pitch;
+            const uint32_t b = uniform((uint32_t)((uintptr_t)ub & 3));
+            up_phase[p] = b;
+            up[p] = make_rsrc(ub - b, has_up ? ((b + bytes + 3) & ~3u) : 0u);
+        }
+    }
+    // the pixel whose elements Y, Cb, Cr are e: its file bytes, packed
+    __device__ __forceinline__ uint32_t pixel_of(const uint32_t (&e)[3]) const
+    {
+        const float y = yuv_elem<S>(e[0]), cb = yuv_elem<S>(e[1]), cr = yuv_elem<S>(e[2]);
+        return yuv_byte(m[0][0], m[0][1], m[0][2], m[0][3], y, cb, cr) | (yuv_byte(m[1][0], m[1][1], m[1][2], m[1][3], y, cb, cr) << 8) |
+               (yuv_byte(m[2][0], m[2][1], m[2][2], m[2][3], y, cb, cr) << 16);
+    }
+    struct Raw {
+        uint32_t c[3], u[3]; // Y, Cb, Cr of the lane's pixel
+    };
+    // element i + x0 of the row behind res (x0: a multiple of 64)
+    static __device__ __forceinline__ uint32_t load_elem(__amdgpu_buffer_rsrc_t res, uint32_t i, uint32_t x0, uint32_t ph)
+    {
+        if constexpr (SB == 2) return __builtin_amdgcn_raw_buffer_load_b16(res, i * 2, x0 * 2 + ph, 0);
+        else return __builtin_amdgcn_raw_buffer_load_b8(res, i, x0 + ph, 0);
+    }
+    __device__ __forceinline__ Raw load_raw(uint32_t x0) const
+    {
+        Raw q;
+        q.c[0] = load_elem(cur[0], lane_, x0, phase[0]);
+        q.u[0] = load_elem(up[0], lane_, x0, up_phase[0]);
+        if constexpr (k420) {
+            const uint32_t ci = lane_ & ~1u; // the pair of pixel x0 + lane: elements 2 ((x0 + lane) >> 1) and the next one
+            q.c[1] = load_elem(cur[1], ci, x0, phase[1]), q.c[2] = load_elem(cur[1], ci + 1, x0, phase[1]);
+            q.u[1] = load_elem(up[1], ci, x0, up_phase[1]), q.u[2] = load_elem(up[1], ci + 1, x0, up_phase[1]);
+        } else {
+            q.c[1] = load_elem(cur[1], lane_, x0, phase[1]), q.c[2] = load_elem(cur[2], lane_, x0, phase[2]);
+            q.u[1] = load_elem(up[1], lane_, x0, up_phase[1]), q.u[2] = load_elem(up[2], lane_, x0, up_phase[2]);
+        }
+        return q;
+    }
+    __device__ __forceinline__ uint32_t filter(const Raw &q) const { return sub_bytes(pixel_of(q.c), pixel_of(q.u) & up_mask); }
+    __device__ __forceinline__ uint32_t filtered_at(uint32_t x0) const { return filter(load_raw(x0)); }
+
+    // a super-window: per plane the dwords that hold the lane's four elements -- two for bytes, three for 16-bit words (a row may
+    // start two bytes into a dword)
+    static constexpr int ND = SB == 2 ? 3 : 2;
+    struct Dwords {
+        uint32_t d[NP][ND];
+    };
+    __device__ __forceinline__ void load_dwords(const __amdgpu_buffer_rsrc_t (&res)[NP], uint32_t voff, uint32_t soff, Dwords &o) const
+    {
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            if constexpr (SB == 2) {
+                const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(res[p], voff, soff, 0);
+                o.d[p][0] = v.x, o.d[p][1] = v.y, o.d[p][2] = v.z;
+            } else {
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(res[p], voff, soff, 0);
+                o.d[p][0] = v.x, o.d[p][1] = v.y;
+            }
+        }
+    }
+    // the four elements of a plane that a lane's dwords hold
+    static __device__ __forceinline__ void elems4(const uint32_t (&d)[ND], uint32_t ph, uint32_t (&e)[4])
+    {
+        if constexpr (SB == 2) {
+            const uint32_t lo = __builtin_amdgcn_alignbyte(d[1], d[0], ph), hi = __builtin_amdgcn_alignbyte(d[2], d[1], ph);
+            e[0] = lo & 0xFFFFu, e[1] = lo >> 16, e[2] = hi & 0xFFFFu, e[3] = hi >> 16;
+        } else {
+            const uint32_t v = __builtin_amdgcn_alignbyte(d[1], d[0], ph);
+            e[0] = v & 0xFFu, e[1] = (v >> 8) & 0xFFu, e[2] = (v >> 16) & 0xFFu, e[3] = v >> 24;
+        }
+    }
+    // the lane's four pixels: out[c] = their four bytes of file channel c, packed (what the planar walk's plane dwords are)
+    __device__ __forceinline__ void bytes_of(const Dwords &q, const uint32_t (&ph)[NP], uint32_t (&out)[3]) const
+    {
+        uint32_t ye[4], ce[4], re[4] = {};
+        elems4(q.d[0], ph[0], ye);
+        elems4(q.d[1], ph[1], ce);
+        if constexpr (!k420) elems4(q.d[2], ph[2], re);
+        out[0] = out[1] = out[2] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            // (4:2:0: ce = Cb, Cr of pixels 0 and 1, then of pixels 2 and 3)
+            const float y = yuv_elem<S>(ye[j]), cb = yuv_elem<S>(k420 ? ce[2 * (j >> 1)] : ce[j]), cr = yuv_elem<S>(k420 ? ce[2 * (j >> 1) + 1] : re[j]);
+#pragma unroll
+            for (int c = 0; c < 3; c++) out[c] |= yuv_byte(m[c][0], m[c][1], m[c][2], m[c][3], y, cb, cr) << (8 * j);
+        }
+    }
+};
+template <> struct RowWindows<3, (int)(kYuvLayout + kYuvNV12)> : YuvRowWindows<kYuvNV12> {};
+template <> struct RowWindows<3, (int)(kYuvLayout + kYuvP016)> : YuvRowWindows<kYuvP016> {};
+template <> struct RowWindows<3, (int)(kYuvLayout + kYuv444)> : YuvRowWindows<kYuv444> {};
+template <> struct RowWindows<3, (int)(kYuvLayout + kYuv444_16)> : YuvRowWindows<kYuv444_16> {};
+
 // pixel 0 of the four that a lane's plane dwords hold (byte 0 of each plane's dword)
 template <int C> __device__ __forceinline__ uint32_t planar_first_pixel(const uint32_t (&fd)[4])
 {
@@ -561,7 +700,7 @@ template <int C> __device__ __forceinline__ uint32_t planar_first_pixel(const ui
 }
 
 // what a lane holds of one super-window of a row before it is filtered (walk_row, phase A)
-template <int C, int L, bool = is_float_layout(L)> struct SuperWindowSource {
+template <int C, int L, bool = is_float_layout(L) || is_yuv_layout(L)> struct SuperWindowSource {
     using type = std::conditional_t<L == kFormPlanar, PlaneDwords<C>, u32x4>;
 };
 template <int C, int L> struct SuperWindowSource<C, L, true> {
@@ -719,11 +858,12 @@ struct RowResult {
 };
 
 // Walks row r of the job.  L: source layout (RowWindows); rows of an L != 0 job lie job.pitch bytes apart.
-// FQ: nothing, or (float layouts) the submission's FloatQuant
+// FQ: nothing, or (float layouts) the submission's FloatQuant, or (YUV layouts) its YuvMatrix
 template <int C, Pass PASS, int L = kFormPacked, typename... FQ>
 __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables &T, uint32_t *hist, uint32_t r, uint32_t lane, EmitSink *sink, const FQ &...fq)
 {
     constexpr bool kFloat = is_float_layout(L), kPlanar = is_planar_layout(L); // (float sources are planar ones: fq has their constants)
+    constexpr bool kYuv = is_yuv_layout(L);                                    // (YUV surfaces too: fq has their matrix)
     using Raw = typename RowWindows<C, L>::Raw;
     constexpr int SB = RowWindows<C, L>::SB;
     constexpr int PF = 4; // windows in flight ahead of the one being processed
@@ -743,7 +883,9 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
 
     RowWindows<C, L> px;
     if (L) px.sel = uniform(job.sel);
-    if constexpr (kFloat)
+    if constexpr (kYuv)
+        px.init_planes(job.rows, pitch, (int64_t)uniform64((uint64_t)job.plane_pitch), r, filter_up, w, lane, fq...);
+    else if constexpr (kFloat)
         px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane, fq...);
     else if constexpr (L == kFormPlanar)
         px.init_planes(row, up_row, (int64_t)uniform64((uint64_t)job.plane_pitch), w, lane);
@@ -933,10 +1075,10 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
         if (NSX > S0) {
             const uint32_t voff4 = lane * kSrcLaneBytes;
             // (planar sources: per plane, the two aligned dwords that hold the lane's four bytes of the row and of the row above)
-            // (float sources: per plane, the dwords that hold the lane's four elements)
+            // (float sources and YUV surfaces: per plane, the dwords that hold the lane's four elements)
             using W4 = typename SuperWindowSource<C, L>::type;
             auto load4 = [&](uint32_t S, W4 &c4, W4 &u4) {
-                if constexpr (kFloat) {
+                if constexpr (kFloat || kYuv) {
                     px.load_dwords(px.cur, voff4, S * kSrcSuperBytes, c4);
                     px.load_dwords(px.up, voff4, S * kSrcSuperBytes, u4);
                 } else if constexpr (L == kFormPlanar) {
@@ -956,7 +1098,14 @@ __device__ __forceinline__ RowResult walk_row(const Job &job, const PackedTables
             // filtered bytes of the lane's four pixels, packed: fd[0..ND) (L != 0: in source order, four dwords for 4-byte sources)
             // (planar: fd[ch] = the lane's four filtered bytes of plane ch)
             auto filt = [&](const W4 &c4, const W4 &u4, uint32_t (&fd)[4]) {
-                if constexpr (kFloat) {
+                if constexpr (kYuv) {
+                    uint32_t cb[3], ub[3];
+                    px.bytes_of(c4, px.phase, cb);
+                    px.bytes_of(u4, px.up_phase, ub);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) fd[ch] = sub_bytes(cb[ch], ub[ch] & px.up_mask);
+                    fd[3] = 0;
+                } else if constexpr (kFloat) {
 #pragma unroll
                     for (int ch = 0; ch < C; ch++) fd[ch] = sub_bytes(px.bytes_of(c4, ch, px.phase[ch]), px.bytes_of(u4, ch, px.up_phase[ch]) & px.up_mask);
                     if (C == 3) fd[3] = 0;
@@ -1217,7 +1366,7 @@ __device__ __forceinline__ const Job &job_of_block(const Job *jobs) { return job
 // hist_kernel (2-pass, pass 1): literal / length-symbol histogram of the whole image
 // (reference fpng.cpp:1021-1084 / :1299-1363).  job.table here is the "symbol" table whose
 // chunk[q] holds (length symbol - 256).
-// FORM: the jobs' source form (kernels.h), which the rows are walked with; kFormEx: the _ex jobs of either pixel size.  fq: the constants of float forms
+// FORM: the jobs' source form (kernels.h), which the rows are walked with; kFormEx: the _ex jobs of either pixel size.  fq: the constants of float and YUV forms
 template <int FORM = kFormPacked, typename... FQ>
 __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const FQ &...fq)
 {
@@ -1236,6 +1385,8 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const 
                 walk_row<3, Pass::Hist, kFormEx4>(job, T, hist, r, lane, nullptr);
             else
                 walk_row<3, Pass::Hist, kFormEx3>(job, T, hist, r, lane, nullptr);
+        } else if constexpr (is_yuv_layout(FORM)) {
+            walk_row<3, Pass::Hist, FORM>(job, T, hist, r, lane, nullptr, fq...); // (a YUV surface's file has three channels)
         } else if (job.c == 4)
             walk_row<4, Pass::Hist, FORM>(job, T, hist, r, lane, nullptr, fq...);
         else
@@ -1249,7 +1400,7 @@ __device__ __forceinline__ void hist_block(const Job &job, uint32_t *dst, const 
         if (s) atomicAdd(&dst[i], s);
     }
 }
-// one instantiation per form that is launched; FQ: nothing, or (float forms) FloatQuant, the submission's constants
+// one instantiation per form that is launched; FQ: nothing, or (float forms) FloatQuant / (YUV forms) YuvMatrix, the submission's constants
 template <int FORM, typename... FQ>
 __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_num_sgpr(80))) void hist_kernel(const Job *jobs, uint32_t *hist_out, const FQ... fq)
 {
@@ -1609,7 +1760,7 @@ __device__ __forceinline__ void xcd_block_order(uint32_t &bx, uint32_t &by)
     bx = logical - by * gridDim.x;
 }
 
-// FORM: the jobs' source form; FQ: nothing, or (float forms) FloatQuant -- the submission's constants in the arguments
+// FORM: the jobs' source form; FQ: nothing, or (float forms) FloatQuant / (YUV forms) YuvMatrix -- the submission's constants in the arguments
 template <int C, int WPE, int FORM, typename... FQ>
 __global__ __launch_bounds__(kRowBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(WPE, WPE))) void encode_rows_kernel(const Job *jobs, RowInfo *rows_out,
                                                                                                       JobState *states, uint32_t *local,
@@ -1782,6 +1933,12 @@ template <int FORM = kFormPacked, typename... FQ>
 __device__ __forceinline__ uint32_t stored_stream_byte(const Job &job, gptr_cu8 px, uint32_t s, const FQ &...fq)
 {
     const uint32_t stride = job.bpl + 1, row = s / stride, col = s - row * stride;
+    if constexpr (is_yuv_layout(FORM)) {
+        // kYuvLayout + surface: yuv.h's accessor on the frame's planes with fq's matrix
+        if (!col) return 0u;
+        const uint32_t b = col - 1, p = b / 3u;
+        return yuv_channel<(uint32_t)(FORM - kYuvLayout)>((const uint8_t *)(uintptr_t)px, job.pitch, job.plane_pitch, fq..., b - p * 3u, p, row);
+    }
     if constexpr (is_float_layout(FORM)) {
         if (!col) return 0u;
         constexpr uint32_t DT = (uint32_t)(FORM - kFloatLayout);
@@ -2129,7 +2286,7 @@ __global__ __launch_bounds__(kBlock) void assemble_kernel(const Job *jobs, JobSt
 
 // stored_kernel: the stored blocks of the images of every form but kFormPacked that fell back (or were asked for with
 // FPNG_FORCE_UNCOMPRESSED), straight from their source form (FORM; FQ: nothing, or FloatQuant for the float forms), with their ranges'
-// Adler shares.  grid (<= max_crc_blocks, n_jobs), each workgroup takes every gridDim.x-th range; compressed images leave at once.
+// Adler shares (YUV forms: their YuvMatrix).  grid (<= max_crc_blocks, n_jobs), each workgroup takes every gridDim.x-th range; compressed images leave at once.
 // assemble_kernel runs behind it with adler_parts = NULL: for a stored image it
 // then takes the CRC of the bytes in place, as for a stored row band, and writes nothing.  (A layout form of assemble_kernel itself
 // does not leave the packed form's code as it is: the compiler allocates registers differently once both exist.)
@@ -2642,6 +2799,8 @@ static dim3 row_grid(uint32_t max_rows, uint32_t n_jobs)
 // element type (the float forms, whose kernels take the FloatQuant behind their other arguments)
 static_assert(FPNG_AMD_DESC_IMAGE == 0 && FPNG_AMD_DESC_EX == 1 && FPNG_AMD_DESC_PLANAR == 2 && kF32 == 0 && kF16 == 1 && kBF16 == 2, "the launchers' tables");
 constexpr int kFormF32 = kFloatLayout + (int)kF32, kFormF16 = kFloatLayout + (int)kF16, kFormBF16 = kFloatLayout + (int)kBF16;
+// ... and with the surface (the YUV forms, kDescYuv, whose kernels take the YuvMatrix there)
+constexpr int kFormNV12 = kYuvLayout + (int)kYuvNV12, kFormP016 = kYuvLayout + (int)kYuvP016, kFormYuv444 = kYuvLayout + (int)kYuv444, kFormYuv444_16 = kYuvLayout + (int)kYuv444_16;
 
 void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_rows, uint32_t *hist, SourceForms src)
 {
@@ -2649,8 +2808,13 @@ void launch_hist(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t max_r
     using FloatKernel = void (*)(const Job *, uint32_t *, FloatQuant);
     static const Kernel kernels[3] = {hist_kernel<kFormPacked>, hist_kernel<kFormEx>, hist_kernel<kFormPlanar>};
     static const FloatKernel float_kernels[3] = {hist_kernel<kFormF32, FloatQuant>, hist_kernel<kFormF16, FloatQuant>, hist_kernel<kFormBF16, FloatQuant>};
+    using YuvKernel = void (*)(const Job *, uint32_t *, YuvMatrix);
+    static const YuvKernel yuv_kernels[kYuvSurfaces] = {hist_kernel<kFormNV12, YuvMatrix>, hist_kernel<kFormP016, YuvMatrix>, hist_kernel<kFormYuv444, YuvMatrix>,
+                                                        hist_kernel<kFormYuv444_16, YuvMatrix>};
     const dim3 grid((max_rows + kHistWaves - 1) / kHistWaves, n_jobs, 1);
-    if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
+    if (src.kind == kDescYuv)
+        hipLaunchKernelGGL(yuv_kernels[src.dtype], grid, dim3(kHistBlock), 0, s, jobs, hist, src.ym);
+    else if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
         hipLaunchKernelGGL(float_kernels[src.dtype], grid, dim3(kHistBlock), 0, s, jobs, hist, src.fq);
     else
         hipLaunchKernelGGL(kernels[src.kind], grid, dim3(kHistBlock), 0, s, jobs, hist);
@@ -2690,6 +2854,14 @@ void launch_encode_rows(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_
         {encode_rows_kernel<3, FPNG_ROWS_WPE_FLOAT3, kFormF32, FloatQuant>, encode_rows_kernel<4, FPNG_ROWS_WPE_FLOAT4_F32, kFormF32, FloatQuant>},
         {encode_rows_kernel<3, FPNG_ROWS_WPE_FLOAT3, kFormF16, FloatQuant>, encode_rows_kernel<4, FPNG_ROWS_WPE_FLOAT4, kFormF16, FloatQuant>},
         {encode_rows_kernel<3, FPNG_ROWS_WPE_FLOAT3, kFormBF16, FloatQuant>, encode_rows_kernel<4, FPNG_ROWS_WPE_FLOAT4, kFormBF16, FloatQuant>}};
+    using YuvKernel = void (*)(const Job *, RowInfo *, JobState *, uint32_t *, YuvMatrix);
+    static const YuvKernel yuv_kernels[kYuvSurfaces] = {
+        encode_rows_kernel<3, FPNG_ROWS_WPE_YUV, kFormNV12, YuvMatrix>, encode_rows_kernel<3, FPNG_ROWS_WPE_YUV, kFormP016, YuvMatrix>,
+        encode_rows_kernel<3, FPNG_ROWS_WPE_YUV, kFormYuv444, YuvMatrix>, encode_rows_kernel<3, FPNG_ROWS_WPE_YUV, kFormYuv444_16, YuvMatrix>};
+    if (src.kind == kDescYuv) { // (three channels, one walk)
+        hipLaunchKernelGGL(yuv_kernels[src.dtype], row_grid(max_rows, n_jobs), dim3(kRowBlock), 0, s, jobs, rows, states, local, src.ym);
+        return;
+    }
     for (const uint32_t bit : {0u, 2u, 1u}) { // (the 3-channel jobs' walks first)
         if (!(src.mask >> bit & 1u)) continue;
         if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
@@ -2718,8 +2890,13 @@ void launch_assemble(hipStream_t s, const Job *jobs, uint32_t n_jobs, uint32_t m
         static const Kernel kernels[3] = {nullptr, stored_kernel<kFormEx>, stored_kernel<kFormPlanar>};
         static const FloatKernel float_kernels[3] = {stored_kernel<kFormF32, FloatQuant>, stored_kernel<kFormF16, FloatQuant>, stored_kernel<kFormBF16, FloatQuant>};
         // (a small grid: for compressed images -- the usual case -- its workgroups only look at the mode)
+        using YuvKernel = void (*)(const Job *, const JobState *, const CrcDeviceTables *, uint32_t *, uint32_t *, uint32_t, YuvMatrix);
+        static const YuvKernel yuv_kernels[kYuvSurfaces] = {stored_kernel<kFormNV12, YuvMatrix>, stored_kernel<kFormP016, YuvMatrix>, stored_kernel<kFormYuv444, YuvMatrix>,
+                                                            stored_kernel<kFormYuv444_16, YuvMatrix>};
         const dim3 grid(std::min(max_crc_blocks, kStoredExBlocks), n_jobs);
-        if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
+        if (src.kind == kDescYuv)
+            hipLaunchKernelGGL(yuv_kernels[src.dtype], grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, src.ym);
+        else if (src.kind == FPNG_AMD_DESC_PLANAR_FLOAT)
             hipLaunchKernelGGL(float_kernels[src.dtype], grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks, src.fq);
         else
             hipLaunchKernelGGL(kernels[src.kind], grid, dim3(kBlock), 0, s, jobs, states, tabs, partials, adler_parts, max_crc_blocks);

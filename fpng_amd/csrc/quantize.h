@@ -55,11 +55,13 @@ template <uint32_t DT> FPNG_QUANT_FN float widen(uint32_t bits)
     return DT == kF32 ? bits_to_float(bits) : DT == kF16 ? widen_f16(bits & 0xFFFFu) : widen_bf16(bits & 0xFFFFu);
 }
 
-FPNG_QUANT_FN uint32_t quantize(float x, float scale, float bias)
+// the second line of the rule on its own: what yuv.h rounds a colour matrix's sums with
+FPNG_QUANT_FN uint32_t round_to_byte(float y)
 {
-    float y = fmaf(x, scale, bias);
     y = fminf(fmaxf(y, 0.0f), 255.0f); // (NaN -> 0)
     return (uint32_t)(int32_t)rintf(y);
 }
+
+FPNG_QUANT_FN uint32_t quantize(float x, float scale, float bias) { return round_to_byte(fmaf(x, scale, bias)); }
 
 } // namespace fpng_amd

@@ -21,15 +21,20 @@ namespace fpng_amd {
 
 constexpr float kColorMaxEntry = 65536.0f; // |m[c][k]| <= this
 
+// t_c of the rule for row (m0, m1, m2, m3) of a matrix, alone (yuv.h rounds it with quantize.h's clamp and rint)
+FPNG_RESIZE_FN float color_mix(float m0, float m1, float m2, float m3, float r, float g, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fmaf(m2, b, __builtin_fmaf(m1, g, __builtin_fmaf(m0, r, m3)));
+#else
+    return std::fmaf(m2, b, std::fmaf(m1, g, std::fmaf(m0, r, m3)));
+#endif
+}
 // u_c of the rule for row (m0, m1, m2, m3) of a view's matrix.  (The clamp as two selects: which zero fmaxf returns for a t_c of
 // -0.0f is left open by C; this returns +0.0f, on the host and on the device.)
 FPNG_RESIZE_FN float color_apply(float m0, float m1, float m2, float m3, float r, float g, float b)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const float t = __builtin_fmaf(m2, b, __builtin_fmaf(m1, g, __builtin_fmaf(m0, r, m3)));
-#else
-    const float t = std::fmaf(m2, b, std::fmaf(m1, g, std::fmaf(m0, r, m3)));
-#endif
+    const float t = color_mix(m0, m1, m2, m3, r, g, b);
     const float lo = t > 0.0f ? t : 0.0f;
     return lo < 255.0f ? lo : 255.0f;
 }

@@ -1433,6 +1433,84 @@ int fpng_amd_renditions_plan(uint32_t desc_kind, const void *images, uint32_t n_
  * submit call.  For tests and for callers that want to predict a file's bytes. */
 int fpng_amd_rendition_pixels(uint32_t desc_kind, const void *images, uint32_t n_images, const fpng_amd_float_format *fmt,
                               const fpng_amd_rendition *rendition, uint8_t *out, size_t out_cap);
+/* ---- YUV VIDEO FRAMES: encoding straight from the surfaces a video decoder returns (rocDecode, VA-API, an ffmpeg hardware
+ *      frame) -- "every n-th frame of these videos as lossless PNGs, plus a thumbnail" -- without the conversion pass that leaves
+ *      an RGB image of twice an NV12 frame's bytes in memory for the encoder to read back.  The conversion runs inside the row
+ *      walk: no RGB image exists in memory.
+ *      SURFACES (rocDecode's four output formats).  One base pointer, ONE row pitch for all planes, one signed chroma offset:
+ *        FPNG_AMD_YUV_NV12    8-bit luma plane, then one plane of interleaved Cb,Cr at half resolution in both directions
+ *        FPNG_AMD_YUV_P016    the same with 16-bit little-endian elements; serves P010 / P012, whose bits are MSB-aligned
+ *        FPNG_AMD_YUV_444     three 8-bit planes Y, Cb, Cr
+ *        FPNG_AMD_YUV_444_16  three 16-bit planes Y, Cb, Cr
+ *      THE RULE (csrc/yuv.h, the one text the kernels, the renditions' accessor and fpng_amd_yuv_pixels compile).  Pixel (x, y) of
+ *      a w x h frame:
+ *        Y = e(luma, x, y);   4:2:0: Cb = e(chroma, 2 (x >> 1), y >> 1), Cr = e(chroma, 2 (x >> 1) + 1, y >> 1);
+ *        4:4:4: Cb = e(plane 1, x, y), Cr = e(plane 2, x, y)
+ *        e of an 8-bit element = (float)byte; of a 16-bit element = (float)word * 2^-8 (exact, so one matrix serves 8-, 10-, 12- and
+ *        16-bit content)
+ *        t_c = fmaf(m[c][2], Cr, fmaf(m[c][1], Cb, fmaf(m[c][0], Y, m[c][3])))    c = R, G, B: the colour rule of the views calls
+ *        byte_c = (uint8) rint(fminf(fmaxf(t_c, 0), 255)), ties to even            the rounding of the float sources
+ *      The chroma of a 4:2:0 surface is REPLICATED over its 2 x 2 pixels: no interpolation, no chroma siting option.
+ *      The file always has 3 channels and is byte for byte what fpng_encode_image_to_memory() writes for those R,G,B bytes, in
+ *      compressed, 2-pass and stored modes.  (The Up filter subtracts the CONVERTED row above.)
+ *      THE MATRIX.  m: one 3 x 4 fp32 matrix per submission; NV21 and YVU orders are a swap of its columns 1 and 2.  A non-finite
+ *      entry, or one above 65536 in magnitude, is refused.  fpng_amd_yuv_matrix(standard, full_range, m) fills it for BT.601,
+ *      BT.709 and BT.2020, limited (Y 16..235, C 16..240) or full range: the nine coefficients in double from Kr and Kb -- with the
+ *      limited-range scales 255/219 (luma) and 255/224 (chroma) -- rounded to fp32, then m[c][3] = (float)(-(m[c][0] y0 +
+ *      128 m[c][1] + 128 m[c][2])) in double FROM THE ROUNDED coefficients, y0 = 16 (limited) or 0 (full): every grey (k, 128, 128)
+ *      comes out as (k', k', k').  FPNG_AMD_ERR_INVALID_ARG for an unknown standard or a null m.
+ *      THE RECORDS.  fpng_amd_yuv_frame: d_luma = the luma plane's top row; row_pitch in bytes, shared by all planes, 0 = tight
+ *      (w elements; 4:2:0: 2 ceil(w / 2)); chroma_offset = the signed bytes from the luma plane's top row to the chroma plane's top
+ *      row, and for the 4:4:4 surfaces again from Cb's to Cr's (negative: the chroma lies in front of the luma).  8-bit planes may
+ *      start at any byte.  These are the three layout words a decoder hands out with a surface: one base, one pitch, plane offsets.
+ *      THE CALL.  Without renditions every frame is a file: to its d_out (16-byte aligned, out_cap >= fpng_amd_max_encoded_size(w,
+ *      h, 3)), or, with a pack, into the arena under fpng_amd_encode_submit_packed's rules (d_out NULL, out_cap 0).  With
+ *      renditions the frames' d_out is NULL and their out_cap 0, and every rule of fpng_amd_encode_submit_renditions holds with
+ *      channels = 3 (alpha_op is checked and ignored; a box's chroma is the frame's: a box with an odd origin keeps the pairs of the
+ *      frame's even columns and rows).  Tickets work with fpng_amd_encode_wait / _query / _finish / _join and _wait_packed, and may
+ *      be in flight next to those of the other kinds.  The source is only read.
+ *      REFUSALS, each FPNG_AMD_ERR_INVALID_ARG (out_cap too small: FPNG_AMD_ERR_BUFFER_TOO_SMALL) with nothing launched, no ticket
+ *      handed out and the encoder as it was: a null fmt; an unknown surface; reserved != 0 (format or frame); a bad matrix entry;
+ *      a negative row_pitch; row_pitch below w elements or, on the 4:2:0 surfaces, below 2 ceil(w / 2) elements (an odd width's last
+ *      pixel has a full chroma pair); on the 16-bit surfaces d_luma, row_pitch or chroma_offset not a multiple of 2;
+ *      |chroma_offset| < (h - 1) row_pitch + w elements (the planes overlap); and everything the plain, packed and renditions calls
+ *      refuse about sizes, outputs, pack and renditions.  The four generic entry points (desc_kind) do not take YUV frames.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_encode_submit_yuv with dlsym. ---- */
+#define FPNG_AMD_YUV_NV12 0u
+#define FPNG_AMD_YUV_P016 1u
+#define FPNG_AMD_YUV_444 2u
+#define FPNG_AMD_YUV_444_16 3u
+#define FPNG_AMD_YUV_SURFACES 4u
+#define FPNG_AMD_YUV_BT601 0u
+#define FPNG_AMD_YUV_BT709 1u
+#define FPNG_AMD_YUV_BT2020 2u
+typedef struct fpng_amd_yuv_frame {
+    const void *d_luma;    /* DEVICE: the luma plane's top row */
+    int64_t row_pitch;     /* bytes, of every plane; 0 = tight */
+    int64_t chroma_offset; /* signed bytes, luma top row -> chroma top row (4:4:4: and Cb -> Cr) */
+    uint32_t w, h;
+    uint64_t reserved;     /* 0 */
+    uint8_t *d_out;        /* DEVICE, 16-byte aligned, receives the whole .png file; NULL with a pack or with renditions */
+    size_t out_cap;        /* >= fpng_amd_max_encoded_size(w, h, 3); 0 with a pack or with renditions */
+} fpng_amd_yuv_frame; /* 56 bytes, no padding */
+typedef struct fpng_amd_yuv_format {
+    uint32_t surface;  /* FPNG_AMD_YUV_* */
+    uint32_t reserved; /* 0 */
+    float m[3][4];     /* file channel c = m[c][0] Y + m[c][1] Cb + m[c][2] Cr + m[c][3] */
+} fpng_amd_yuv_format; /* 56 bytes */
+int fpng_amd_encode_submit_yuv(fpng_amd_encoder *enc, const fpng_amd_yuv_frame *frames, uint32_t n_frames, const fpng_amd_yuv_format *fmt,
+                               const fpng_amd_rendition *renditions, uint32_t n_renditions, uint32_t flags, const fpng_amd_pack *pack,
+                               uint64_t *ticket);
+/* standard: FPNG_AMD_YUV_BT601 / _BT709 / _BT2020; full_range: 0 = limited (studio) range */
+int fpng_amd_yuv_matrix(uint32_t standard, int full_range, float m[12]);
+/* The conversion's (and, with a rendition, the resize stage's) HOST twin over the text the kernels compile: `frames` are records
+ * as above whose d_luma are HOST pointers to a copy of the surface in its own layout; out receives the tight R,G,B bytes of frame
+ * frame_index (rendition NULL: w * h * 3) or of that rendition of it (rendition->image is not looked at; w * h * 3 of the
+ * rendition's size; out_cap: out's room, else FPNG_AMD_ERR_BUFFER_TOO_SMALL).  The rendition's d_out and out_cap are not looked
+ * at, nor are the frames' without a rendition (with one they are NULL and 0, as in the submit call); everything else is validated
+ * as by the submit call. */
+int fpng_amd_yuv_pixels(const fpng_amd_yuv_frame *frames, uint32_t n_frames, const fpng_amd_yuv_format *fmt, uint32_t frame_index,
+                        const fpng_amd_rendition *rendition, uint8_t *out, size_t out_cap);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

@@ -39,4 +39,5 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   view_enhance, view_enhance_apply, rotate_matrix, augment_op,
                   view_alpha, view_alpha_source, view_alpha_result, view_resample, resample_weights, resample_view_source,
                   RENDITION_FILTERS, rendition, renditions_plan, rendition_pixels,
-                  YUV_SURFACES, YUV_STANDARDS, yuv_matrix, yuv_frame_layout, yuv_pixels)
+                  YUV_SURFACES, YUV_STANDARDS, yuv_matrix, yuv_frame_layout, yuv_pixels,
+                  DecodeBatchYuv, YuvSurface, yuv_matrix_from_rgb, yuv_surface, yuv_surface_planes, yuv_surface_bytes)

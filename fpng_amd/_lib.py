@@ -168,6 +168,14 @@ class YuvFormat(C.Structure):  # fpng_amd_yuv_format: 56 bytes
     _fields_ = [("surface", C.c_uint32), ("reserved", C.c_uint32), ("m", (C.c_float * 4) * 3)]
 
 
+class YuvDest(C.Structure):  # fpng_amd_yuv_dest: 40 bytes
+    _fields_ = [("d_luma", C.c_void_p), ("row_pitch", C.c_int64), ("chroma_offset", C.c_int64), ("surface_cap", C.c_size_t), ("reserved", C.c_uint64)]
+
+
+class YuvStoreFormat(C.Structure):  # fpng_amd_yuv_store_format: 56 bytes
+    _fields_ = [("surface", C.c_uint32), ("depth", C.c_uint32), ("m", (C.c_float * 4) * 3)]
+
+
 YUV_SURFACES = {"nv12": 0, "p016": 1, "yuv444": 2, "yuv444_16": 3}  # FPNG_AMD_YUV_* (p016 serves P010 / P012)
 YUV_STANDARDS = {"bt601": 0, "bt709": 1, "bt2020": 2}  # FPNG_AMD_YUV_BT*
 
@@ -332,6 +340,13 @@ for _layout, _dest in VIEW_LAYOUTS:
         for _device in (False, True):
             SIGNATURES[views_symbol(_layout, _device, _stages)] = (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(_dest)] +
                                                                   [C.POINTER(rec) for _, rec in VIEW_STAGES[:_stages]] + [C.POINTER(FloatFormat), C.POINTER(DecodeResult)])
+
+# the YUV views call takes the plain views call's arrays with fpng_amd_yuv_dest records and its own format
+for _device in (False, True):
+    SIGNATURES[views_symbol("yuv", _device, 0)] = (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(YuvDest),
+                                                          C.POINTER(YuvStoreFormat), C.POINTER(DecodeResult)])
+SIGNATURES["fpng_amd_yuv_matrix_from_rgb"] = (_int, [_u32, _int, C.POINTER(C.c_float)])
+SIGNATURES["fpng_amd_yuv_surface"] = (_int, [_vp, _u32, _u32, C.POINTER(YuvStoreFormat), C.POINTER(YuvDest)])
 
 _lib = None
 

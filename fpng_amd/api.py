@@ -1459,7 +1459,8 @@ class DecodeBatch:
 
 class _DecodeBatchViews:
     """The files, the caller's destination views and the C arrays of one decode call into views (DecodeBatchEx, DecodeBatchPlanar,
-    DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView, DecodeBatchMultiViewHwc).
+    DecodeBatchFloat, DecodeBatchCrop, DecodeBatchResize, DecodeBatchResizeView, DecodeBatchMultiView, DecodeBatchMultiViewHwc,
+    DecodeBatchYuv).
     maker: the Encoder method that makes the class's descriptors; extras: the call's further arrays, stored under their names."""
 
     maker = None
@@ -1596,9 +1597,120 @@ class _ViewsLayout:
     destination record and the descriptor, whose maker names the Python methods; put_dest: writes a tensor view's destination record
     (its layout function and pixels_cap formula); chw: a view's shape as (c, h, w); empty_shape: of an allocated (oh, ow) output."""
 
-    def __init__(self, name, dest_cls, batch_cls, put_dest, chw, empty_shape):
+    def __init__(self, name, dest_cls, batch_cls, put_dest, chw, empty_shape, fmt=None):
         self.name, self.dest_cls, self.batch_cls, self.put_dest, self.chw, self.empty_shape = name, dest_cls, batch_cls, put_dest, chw, empty_shape
+        self.fmt = fmt  # the call's own format record in the place of the float format (the YUV layout's), else None
         self.maker, self.host, self.device = batch_cls.maker, batch_cls.call(False), batch_cls.call(True)
+
+
+class DecodeBatchYuv(_DecodeBatchMultiViews):
+    """What Encoder.make_decode_batch_yuv() returns: DecodeBatchMultiView's twin for one fpng_amd_decode_batch(_device)_yuv_views()
+    call (dests: the fpng_amd_yuv_dest records; outs: per file the list of the caller's surfaces, each a YuvSurface -- the tuple of
+    plane tensors yuv_frame_layout() takes; fmt: the call's fpng_amd_yuv_store_format).  No other call takes this descriptor."""
+
+    maker = "make_decode_batch_yuv"
+
+
+class YuvSurface(tuple):
+    """a YUV surface as a destination of the views machinery: the tuple of its plane tensors (yuv_frame_layout() has the shapes),
+    which answers the questions that machinery asks a destination tensor"""
+
+    @property
+    def shape(self):
+        return (3,) + tuple(self[0].shape)
+
+    @property
+    def is_cuda(self):
+        return all(p.is_cuda for p in self)
+
+
+def yuv_surface_bytes(surface, w, h, row_pitch, chroma_offset):
+    """fpng_amd_yuv_dest::surface_cap of a w x h surface with these layout words: the bytes from the top row of its lowest-addressed
+    plane to the last element of its highest one"""
+    s = YUV_SURFACES[surface]
+    elem = 2 if s & 1 else 1
+    chroma_row = (2 * ((w + 1) // 2) if s < 2 else w) * elem
+    pitch = row_pitch or max(w * elem, chroma_row)
+    span = (h - 1) * pitch + w * elem
+    if s >= 2:
+        return 2 * abs(chroma_offset) + span
+    return abs(chroma_offset) + (span if chroma_offset < 0 else ((h + 1) // 2 - 1) * pitch + chroma_row)
+
+
+def _yuv_views(surface, fmt):
+    """the views calls' layout (_ViewsLayout) whose destinations are surfaces of `surface` under the call's format `fmt`"""
+
+    def put_dest(rec, t, order, bottom_up, is_u8):
+        rec.d_luma, rec.row_pitch, rec.chroma_offset, w, h = yuv_frame_layout(t, surface)
+        rec.surface_cap = yuv_surface_bytes(surface, w, h, rec.row_pitch, rec.chroma_offset)
+        return None
+
+    return _ViewsLayout("yuv", _lib.YuvDest, DecodeBatchYuv, put_dest, lambda s: (s[0], s[1], s[2]), None, fmt)
+
+
+def _yuv_store_format(who, surface, depth, matrix, standard, full_range):
+    if surface not in YUV_SURFACES:
+        raise ValueError(f"{who}: surface {surface!r} ({', '.join(sorted(YUV_SURFACES))})")
+    m = yuv_matrix_from_rgb(standard, full_range) if matrix is None else np.asarray(matrix, dtype=np.float32)
+    if m.shape != (3, 4):
+        raise ValueError(f"{who}: matrix is 3 x 4, not {m.shape}")
+    fmt = _lib.YuvStoreFormat()
+    fmt.surface, fmt.depth = YUV_SURFACES[surface], _u32(who, "depth", depth or 0)
+    for c in range(3):
+        for k in range(4):
+            fmt.m[c][k] = float(m[c, k])
+    return fmt
+
+
+def yuv_matrix_from_rgb(standard="bt709", full_range=False):
+    """fpng_amd_yuv_matrix_from_rgb: the (3, 4) float32 matrix [Y, Cb, Cr] = m[:, :3] @ [R, G, B] + m[:, 3] of "bt601", "bt709" or
+    "bt2020", limited (Y 16..235, C 16..240) or full range, in 8-bit units -- the decode side's direction, the other way round from
+    yuv_matrix().  Swap rows 1 and 2 for NV21 / YVU orders."""
+    if standard not in YUV_STANDARDS:
+        raise ValueError(f"yuv_matrix_from_rgb: standard {standard!r} ({', '.join(sorted(YUV_STANDARDS))})")
+    m = np.empty((3, 4), dtype=np.float32)
+    check(_lib.load().fpng_amd_yuv_matrix_from_rgb(YUV_STANDARDS[standard], 1 if full_range else 0, m.ctypes.data_as(C.POINTER(C.c_float))))
+    return m
+
+
+def yuv_surface_planes(surface, w, h, make):
+    """the planes of a tight w x h surface as views of ONE buffer: make(n, elem_bytes) returns a flat array or tensor of n elements of
+    that size, which has reshape and basic slicing -> the tuple yuv_frame_layout() takes"""
+    s = YUV_SURFACES[surface]
+    elem = 2 if s & 1 else 1
+    if s >= 2:
+        buf = make(3 * h * w, elem).reshape(3, h, w)
+        return (buf[0], buf[1], buf[2])
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    rows = make((h + ch) * 2 * cw, elem).reshape(h + ch, 2 * cw)
+    return (rows[:h, :w], rows[h:].reshape(ch, cw, 2))
+
+
+def yuv_surface(rgb, surface="nv12", depth=None, matrix=None, standard="bt709", full_range=False):
+    """fpng_amd_yuv_surface, the host twin of Encoder.decode_device_yuv()'s last stage (no GPU; the text the kernel compiles): the
+    planes of the tight surface -- numpy arrays, as yuv_frame_layout() takes them -- for the (h, w, 3) uint8 array of R,G,B pixels
+    `rgb`.  depth: None (the surface's own: 8 / 16), or 10, 12 or 16 on the 16-bit surfaces; matrix: a (3, 4) matrix of the
+    caller's, else yuv_matrix_from_rgb(standard, full_range)."""
+    who = "yuv_surface"
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or not rgb.shape[0] or not rgb.shape[1]:
+        raise ValueError(f"{who}: rgb is an (h, w, 3) uint8 array")
+    fmt = _yuv_store_format(who, surface, depth, matrix, standard, full_range)
+    h, w = rgb.shape[:2]
+    planes = yuv_surface_planes(surface, w, h, lambda n, elem: np.zeros(n, dtype=np.uint8 if elem == 1 else np.uint16))
+    rec = _lib.YuvDest()
+    rec.d_luma, rec.row_pitch, rec.chroma_offset, _, _ = yuv_frame_layout(planes, surface)
+    rec.surface_cap = yuv_surface_bytes(surface, w, h, rec.row_pitch, rec.chroma_offset)
+    check(_lib.load().fpng_amd_yuv_surface(rgb.ctypes.data, w, h, C.byref(fmt), C.byref(rec)))
+    return planes
+
+
+def _png_size(png):
+    """(w, h) of a file from its IHDR, for the calls that take the whole file at its own size by default (a device file: 8 bytes come back)"""
+    head = bytes(png[16:24].cpu().numpy()) if isinstance(png, torch.Tensor) else bytes(png)[16:24]
+    if len(head) != 8:
+        raise ValueError("a file of fewer than 24 bytes has no size")
+    return int.from_bytes(head[:4], "big"), int.from_bytes(head[4:], "big")
 
 
 _PLANAR_VIEWS = _ViewsLayout("planar", _lib.ViewDest, DecodeBatchMultiView, _planar_view_dest, lambda s: (s[0], s[1], s[2]), lambda oh, ow: (3, oh, ow))
@@ -1695,7 +1807,7 @@ def _make_views_batch(layout, pngs, crops, outs, full, window, filter, mirror, o
             raise ValueError(f"{who}: file {i} has {counts[i]} crops (at least one) and {len(outs[i])} destinations")
     fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
     filters, mirrors = _per_view(who, counts, filter, "filters"), _per_view(who, counts, mirror, "mirror flags")
-    is_u8, fmt = _dest_format(who, [t for ts in outs for t in ts], mean, std, scale, bias)
+    is_u8, fmt = (True, layout.fmt) if layout.fmt is not None else _dest_format(who, [t for ts in outs for t in ts], mean, std, scale, bias)
     orders, ups = _per_view(who, counts, order, "plane orders"), _per_view(who, counts, bottom_up, "bottom_up flags")
     total = sum(counts)
     arr = (_lib.PngPlanarIn * n)()
@@ -2530,6 +2642,55 @@ class Encoder:
         """fpng_amd_decode_batch_planar_views: decode_device_views() for files in host memory (bytes)."""
         return self._decode_views(_PLANAR_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
                                   dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
+
+    @staticmethod
+    def make_decode_batch_yuv(pngs, crops, outs, full, surface="nv12", depth=None, window=None, filter="bilinear", mirror=False, matrix=None, standard="bt709",
+                              full_range=False):
+        """Descriptor for decode_device_yuv() / decode_batch_yuv(): make_decode_batch_views() with surfaces in the place of the (c, h,
+        w) views -- outs[i]: the list of file i's surfaces, each the tuple of plane tensors yuv_frame_layout() takes for `surface`,
+        its Y plane (window h, window w).  crops, full, window, filter and mirror nest as there; surface, depth and the matrix (a (3, 4)
+        one of the caller's, else yuv_matrix_from_rgb(standard, full_range)) are the call's."""
+        fmt = _yuv_store_format("make_decode_batch_yuv", surface, depth, matrix, standard, full_range)
+        outs = [[YuvSurface(t) for t in ts] for ts in outs]
+        return _make_views_batch(_yuv_views(surface, fmt), pngs, crops, outs, full, window, filter, mirror, "rgb", False, None, None, None, None, {})
+
+    def _decode_yuv(self, device_data, pngs, outs, surface, depth, crops, full, window, filter, mirror, matrix, standard, full_range, results):
+        def make(who):
+            cs, fs, dests = crops, full, outs
+            if cs is None:  # (the whole of every file)
+                cs = [[(0, 0) + _png_size(p)] for p in pngs]
+            cs = [list(c) for c in cs]
+            counts = [len(c) for c in cs]
+            if fs is None:  # (every crop at its own size: the identity)
+                fs = [[(int(c[2]), int(c[3])) for c in file] for file in cs]
+            if dests is None or any(o is None for o in dests):  # (tight surfaces of each window's size)
+                elems = {1: torch.uint8, 2: getattr(torch, "uint16", torch.int16)}
+                fulls, windows = _per_view(who, counts, fs, "full sizes"), _per_view(who, counts, window, "windows")
+                alloc = lambda hw: yuv_surface_planes(surface, hw[1], hw[0], lambda n, elem: torch.empty(n, dtype=elems[elem], device=f"cuda:{self.device}"))
+                dests = [[alloc(_window_hw(f_, w_)) for f_, w_ in zip(fulls[i], windows[i])] if dests is None or dests[i] is None else dests[i] for i in range(len(cs))]
+            return self.make_decode_batch_yuv(pngs, cs, dests, fs, surface, depth, window, filter, mirror, matrix, standard, full_range)
+
+        return self._run_decode(DecodeBatchYuv, device_data, pngs, make, lambda b: views_entry("yuv", device_data, b), results)
+
+    def decode_device_yuv(self, pngs, outs=None, surface="nv12", depth=None, crops=None, full=None, window=None, filter="bilinear", mirror=False, matrix=None,
+                          standard="bt709", full_range=False, results=True):
+        """fpng_amd_decode_batch_device_yuv_views: views of each file -- uint8 CUDA tensors holding whole files -- written as the YUV
+        surfaces a hardware video encoder takes: "nv12", "p016" (depth 10 / 12 / 16: P010 / P012 / P016), "yuv444", "yuv444_16".
+        Everything in front of the surface is decode_device_views(): crops[i] lists file i's crops (None: the whole file, one view),
+        each resized to its full size (None: its own, the identity) by its filter, its window mirrored where asked; nested lists
+        give several views per file from one decode of it -- one 4K file into 2160p, 1080p and 720p NV12 for an adaptive-bitrate
+        ladder.  outs[i][k]: the surface of view k of file i, the tuple of plane tensors yuv_frame_layout() takes (any pitch, chroma
+        anywhere); outs=None (or None for a file) allocates tight surfaces.  The rule (include/fpng_amd.h; yuv_surface() is its
+        host twin): Y, Cb, Cr = the matrix's rows over R, G, B in fp32 fused multiply-adds, scaled to the depth, clamped and rounded
+        to nearest even; 4:2:0 chroma from the MEAN of each 2 x 2 block (centre siting, no siting option).  matrix: a (3, 4) matrix of
+        the caller's, else yuv_matrix_from_rgb(standard, full_range).  -> list, per file, of (status, the list of its surfaces or
+        None, channels_in_file); results=False returns the descriptor.  pngs may be a make_decode_batch_yuv() descriptor."""
+        return self._decode_yuv(True, pngs, outs, surface, depth, crops, full, window, filter, mirror, matrix, standard, full_range, results)
+
+    def decode_batch_yuv(self, pngs, outs=None, surface="nv12", depth=None, crops=None, full=None, window=None, filter="bilinear", mirror=False, matrix=None,
+                         standard="bt709", full_range=False, results=True):
+        """fpng_amd_decode_batch_yuv_views: decode_device_yuv() for files in host memory (bytes)."""
+        return self._decode_yuv(False, pngs, outs, surface, depth, crops, full, window, filter, mirror, matrix, standard, full_range, results)
 
     @staticmethod
     def make_decode_batch_views_hwc(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,

@@ -1232,9 +1232,24 @@ int fpng_amd_encode_submit_yuv(fpng_amd_encoder *e, const fpng_amd_yuv_frame *fr
     return submit(e, batch, flags, ticket, pack);
 }
 
+static const double kKr[3] = {0.299, 0.2126, 0.2627}, kKb[3] = {0.114, 0.0722, 0.0593}; // BT.601, BT.709, BT.2020
+
+// the other direction (yuv_store.h's rule): rows Y, Cb, Cr over R, G, B, each coefficient in double, rounded to fp32
+int fpng_amd_yuv_matrix_from_rgb(uint32_t standard, int full_range, float m[12])
+{
+    if (standard > FPNG_AMD_YUV_BT2020) return fail(FPNG_AMD_ERR_INVALID_ARG, "standard is FPNG_AMD_YUV_BT601, _BT709 or _BT2020");
+    if (!m) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
+    const double kr = kKr[standard], kb = kKb[standard], kg = 1.0 - kr - kb;
+    const double sy = full_range ? 1.0 : 219.0 / 255.0, sc = full_range ? 1.0 : 224.0 / 255.0;
+    const double coef[3][4] = {{kr * sy, kg * sy, kb * sy, full_range ? 0.0 : 16.0},
+                               {-kr / (2.0 * (1.0 - kb)) * sc, -kg / (2.0 * (1.0 - kb)) * sc, 0.5 * sc, 128.0},
+                               {0.5 * sc, -kg / (2.0 * (1.0 - kr)) * sc, -kb / (2.0 * (1.0 - kr)) * sc, 128.0}};
+    for (int k = 0; k < 12; k++) m[k] = (float)coef[k / 4][k % 4];
+    return FPNG_AMD_OK;
+}
+
 int fpng_amd_yuv_matrix(uint32_t standard, int full_range, float m[12])
 {
-    static const double kKr[3] = {0.299, 0.2126, 0.2627}, kKb[3] = {0.114, 0.0722, 0.0593}; // BT.601, BT.709, BT.2020
     if (standard > FPNG_AMD_YUV_BT2020) return fail(FPNG_AMD_ERR_INVALID_ARG, "standard is FPNG_AMD_YUV_BT601, _BT709 or _BT2020");
     if (!m) return fail(FPNG_AMD_ERR_INVALID_ARG, "null argument");
     const double kr = kKr[standard], kb = kKb[standard], kg = 1.0 - kr - kb;

@@ -705,6 +705,12 @@ int fpng_amd::ViewPlan::enqueue(hipStream_t s, uint32_t j0, uint32_t j1, const D
              : hwc()   ? launch_dec_resize_hwc(s, (const DecResizeHwc *)d_recs + r0, d_pre + r0, tile_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, any_alpha)
              : multi() ? launch_dec_resize_exact(s, (const DecResize *)d_recs + r0, d_pre + r0, plane_pre.data() + r0, r1 - r0, most_lds, flt, any_filter, any_alpha)
                        : launch_dec_resize(s, (const DecResize *)d_recs + r0, r1 - r0, most_tiles, most_lds, flt, any_filter != 0);
+        // (a YUV call: the planes just written into the scratch become the caller's surfaces)
+        if (ok && rq.yuv) {
+            YuvMatrix f;
+            std::memcpy(f.m, rq.yuv_fmt->m, sizeof f.m);
+            ok = launch_dec_yuv_store(s, d_yuv + r0, d_yuv_pre + r0, yuv_pre.data() + r0, r1 - r0, rq.yuv_fmt->surface, f, yuv_depth(rq.yuv_fmt->surface, rq.yuv_depth));
+        }
     }
     return ok ? FPNG_AMD_OK : fail(FPNG_AMD_ERR_UNSUPPORTED, "resize launch: tiles or LDS out of range");
 }
@@ -1344,7 +1350,7 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
     }
     if (rq.colors)
         if (int rc = check_color_records(rq.colors, used.total)) return rc;
-    if (!files || !view_count || !rq.crops || !views || !(rq.dests || rq.hwc) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, null_array);
+    if (!files || !view_count || !rq.crops || !views || !(rq.dests || rq.hwc || rq.yuv) || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, null_array);
     total = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (!view_count[i]) return fail(FPNG_AMD_ERR_INVALID_ARG, "a view_count of 0 (every file has at least one view)");
@@ -1406,6 +1412,39 @@ int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, ui
     if (int rc = check_views_request(files, n, asked, results, used)) return rc;
     ViewDefaults made;
     return decode_files_planar(e, files, n, results, device_data, normalise_views(asked, used, made));
+}
+
+// ---- fpng_amd_decode_batch(_device)_yuv_views (the rule: yuv_store.h) ----
+static_assert(sizeof(fpng_amd_yuv_dest) == 40 && offsetof(fpng_amd_yuv_dest, chroma_offset) == 16 && offsetof(fpng_amd_yuv_dest, reserved) == 32 &&
+                  sizeof(fpng_amd_yuv_store_format) == 56 && offsetof(fpng_amd_yuv_store_format, m) == 8,
+              "fpng_amd_yuv_dest / fpng_amd_yuv_store_format layout");
+// fmt of the YUV views call and of its host twin: its depth (the surface's own for 0) into *depth
+int check_yuv_store_format(const fpng_amd_yuv_store_format *fmt, uint32_t *depth)
+{
+    if (fmt->surface >= FPNG_AMD_YUV_SURFACES) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown surface (FPNG_AMD_YUV_*)");
+    if (!(*depth = yuv_store_depth(fmt->surface, fmt->depth)))
+        return fail(FPNG_AMD_ERR_INVALID_ARG, "a depth the surface does not have (8-bit surfaces: 0 or 8; 16-bit surfaces: 0, 10, 12 or 16)");
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(fmt->m[k / 4][k % 4]) || std::fabs(fmt->m[k / 4][k % 4]) > kColorMaxEntry)
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_yuv_store_format::m: every entry must be finite and at most 65536 in magnitude");
+    return FPNG_AMD_OK;
+}
+// What needs no file, no encoder and no device is judged first: the format, then what the views call judges, then every surface's
+// own words against its view's size; the room (d_luma, surface_cap) is judged per file whose header is accepted (ViewPlan::file_records)
+int decode_files_yuv(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops, const fpng_amd_resize_view *views,
+                     const fpng_amd_yuv_dest *dests, const fpng_amd_yuv_store_format *fmt, fpng_amd_decode_result *results, bool device_data)
+{
+    if (!fmt || !dests) return fail(FPNG_AMD_ERR_INVALID_ARG, fmt ? "null dests" : "null fmt");
+    ViewRequest rq;
+    rq.family = ViewFamily::Plain, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.yuv = dests, rq.yuv_fmt = fmt;
+    if (int rc = check_yuv_store_format(fmt, &rq.yuv_depth)) return rc;
+    StagesUsed used;
+    if (int rc = check_views_request(files, n, rq, results, used)) return rc;
+    for (uint32_t i = 0; i < n; i++)
+        if (files[i].num_chans != 3) return fail(FPNG_AMD_ERR_INVALID_ARG, "num_chans must be 3 (a 4-channel file's alpha is dropped)");
+    for (uint64_t v = 0; v < used.total; v++)
+        if (const Refusal no = judge_yuv_dest(dests[v], fmt->surface, views[v].w, views[v].h, false)) return fail(no.code, no.why);
+    return decode_files_planar(e, files, n, results, device_data, rq);
 }
 
 // the plain resize call's records as views: the whole of the resized crop, bilinear
@@ -1521,6 +1560,41 @@ extern "C" int fpng_amd_decode_batch_device_planar_views(fpng_amd_encoder *e, co
     ViewRequest rq;
     rq.family = ViewFamily::Plain, rq.fmt = fmt, rq.view_count = view_count, rq.crops = crops, rq.views = views, rq.dests = dests;
     return decode_files_views(e, files, n, results, true, rq);
+}
+
+extern "C" int fpng_amd_decode_batch_yuv_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                               const fpng_amd_resize_view *views, const fpng_amd_yuv_dest *dests, const fpng_amd_yuv_store_format *fmt, fpng_amd_decode_result *results)
+{
+    return decode_files_yuv(e, files, n, view_count, crops, views, dests, fmt, results, false);
+}
+
+extern "C" int fpng_amd_decode_batch_device_yuv_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,
+                                                      const fpng_amd_resize_view *views, const fpng_amd_yuv_dest *dests, const fpng_amd_yuv_store_format *fmt,
+                                                      fpng_amd_decode_result *results)
+{
+    return decode_files_yuv(e, files, n, view_count, crops, views, dests, fmt, results, true);
+}
+
+// the host twin: yuv_store.h's walk over tight R,G,B bytes into a surface in HOST memory, the format and the record judged as by the call
+extern "C" int fpng_amd_yuv_surface(const uint8_t *rgb, uint32_t w, uint32_t h, const fpng_amd_yuv_store_format *fmt, const fpng_amd_yuv_dest *host_dest)
+{
+    if (!fmt || !host_dest) return fail(FPNG_AMD_ERR_INVALID_ARG, fmt ? "null host_dest" : "null fmt");
+    if (!rgb || !w || !h) return fail(FPNG_AMD_ERR_INVALID_ARG, "null rgb or an empty size (w or h is 0)");
+    uint32_t depth = 0;
+    if (int rc = check_yuv_store_format(fmt, &depth)) return rc;
+    int64_t pitch = 0;
+    if (const Refusal no = judge_yuv_dest(*host_dest, fmt->surface, w, h, true, &pitch)) return fail(no.code, no.why);
+    YuvMatrix f;
+    std::memcpy(f.m, fmt->m, sizeof f.m);
+    const YuvDepth dp = yuv_depth(fmt->surface, depth);
+    uint8_t *const luma = (uint8_t *)host_dest->d_luma;
+    switch (fmt->surface) {
+    case FPNG_AMD_YUV_NV12: yuv_store_surface<kYuvNV12>(rgb, w, h, f, dp, luma, pitch, host_dest->chroma_offset); break;
+    case FPNG_AMD_YUV_P016: yuv_store_surface<kYuvP016>(rgb, w, h, f, dp, luma, pitch, host_dest->chroma_offset); break;
+    case FPNG_AMD_YUV_444: yuv_store_surface<kYuv444>(rgb, w, h, f, dp, luma, pitch, host_dest->chroma_offset); break;
+    default: yuv_store_surface<kYuv444_16>(rgb, w, h, f, dp, luma, pitch, host_dest->chroma_offset); break;
+    }
+    return FPNG_AMD_OK;
 }
 
 extern "C" int fpng_amd_decode_batch_hwc_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count, const fpng_amd_crop *crops,

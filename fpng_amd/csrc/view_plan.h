@@ -12,6 +12,7 @@
 #include "resize_hwc.h"
 #include "view_alpha.h"
 #include "view_post.h"
+#include "yuv_store.h"
 
 #include <algorithm>
 #include <cstring>
@@ -40,6 +41,10 @@ struct ViewRequest {
     const fpng_amd_view_enhance *enhances = nullptr;
     const fpng_amd_view_alpha *alphas = nullptr; // (its stage sits inside the resize, in front of all others)
     const fpng_amd_view_resample *resamples = nullptr; // (the last array of the signatures: the resize's own filter)
+    // fpng_amd_decode_batch(_device)_yuv_views: the views' surfaces in the place of dests, and the call's format (judged: yuv_depth is its depth)
+    const fpng_amd_yuv_dest *yuv = nullptr;
+    const fpng_amd_yuv_store_format *yuv_fmt = nullptr;
+    uint32_t yuv_depth = 0;
     ViewFamily family = ViewFamily::Plain;
 };
 
@@ -132,10 +137,42 @@ inline DestPitches judge_hwc_dest(const fpng_amd_view_dest_hwc &d, uint32_t dest
     return {pitch, 0, {}};
 }
 
+// a YUV surface of `surface` for a view of w x h pixels (fpng_amd_yuv_dest's rules).  room: d_luma and surface_cap are judged too
+// (a file whose header is accepted); pitch: the rows' pitch in bytes
+inline Refusal judge_yuv_dest(const fpng_amd_yuv_dest &d, uint32_t surface, uint32_t w, uint32_t h, bool room, int64_t *pitch_out = nullptr)
+{
+    const int kBad = FPNG_AMD_ERR_INVALID_ARG;
+    if (d.reserved) return {kBad, "fpng_amd_yuv_dest::reserved must be 0"};
+    const uint64_t elem = yuv_elem_bytes(surface);
+    if ((uint64_t)w * elem >= 0x80000000ull - 16) return {kBad, "w * element bytes >= 2^31 - 16"}; // (a chroma row and the scratch planes' pitch stay below 2^31)
+    const int64_t row_bytes = (int64_t)((uint64_t)w * elem), chroma_bytes = (int64_t)yuv_chroma_row_bytes(surface, w);
+    if (d.row_pitch < 0) return {kBad, "row_pitch must not be negative"};
+    if (elem > 1 && (((uintptr_t)d.d_luma | (uint64_t)d.row_pitch | (uint64_t)d.chroma_offset) & 1u))
+        return {kBad, "d_luma, row_pitch and chroma_offset must be multiples of 2 on 16-bit surfaces"};
+    const int64_t pitch = d.row_pitch ? d.row_pitch : std::max(row_bytes, chroma_bytes);
+    if (pitch < row_bytes) return {kBad, "row_pitch < w (* element bytes)"};
+    if (pitch < chroma_bytes) return {kBad, "row_pitch < 2 * ceil(w / 2) (* element bytes): an odd width's last pixel has a full chroma pair"};
+    if (pitch >= (int64_t)0x80000000ll) return {kBad, "row_pitch >= 2^31"};
+    const int64_t limit = INT64_MAX >> 2; // (two offsets and a plane's span stay inside 64 bits)
+    if (d.chroma_offset < -limit || d.chroma_offset > limit) return {kBad, "chroma_offset out of range"};
+    const int64_t span = (int64_t)(h - 1) * pitch + row_bytes; // bytes from the luma plane's first row to the end of its last
+    // (a 4:2:0 chroma plane in FRONT of the luma plane ends (h + 1) / 2 - 1 rows and a chroma row behind its start)
+    const int64_t chroma_span = yuv_is_420(surface) ? (int64_t)(((uint64_t)h + 1) / 2 - 1) * pitch + chroma_bytes : span;
+    const int64_t aco = d.chroma_offset < 0 ? -d.chroma_offset : d.chroma_offset;
+    if (aco < span || (d.chroma_offset < 0 && aco < chroma_span)) return {kBad, "|chroma_offset| < (h - 1) * row_pitch + w (* element bytes): the planes overlap"};
+    // from the lowest plane's top row to the last element of the highest one
+    const uint64_t need = yuv_is_420(surface) ? (uint64_t)aco + (uint64_t)(d.chroma_offset < 0 ? span : chroma_span) : 2 * (uint64_t)aco + (uint64_t)span;
+    if (room && (!d.d_luma || d.surface_cap < need)) return {FPNG_AMD_ERR_BUFFER_TOO_SMALL, "d_luma / surface_cap < the surface's bytes, from the lowest plane's top row to the last element of the highest"};
+    if (pitch_out) *pitch_out = pitch;
+    return {};
+}
+
 // One call's views.  A RECORD is a view of a file that became a job, numbered in the views' order over the jobs; job k's records
 // are job_rec[k] .. job_rec[k + 1] - 1.  A view with a post flag, a warp that moves, a tone or an enhance op is a POST view: its
 // resize record writes the un-mirrored uint8 window into the scratch and its destination travels in a DecViewPost record to
-// dec_view_post_kernel; every other view is a DIRECT view, whose resize record writes the destination.  An empty plan (a call
+// dec_view_post_kernel; every other view is a DIRECT view, whose resize record writes the destination.  The views of a YUV call
+// (rq.yuv) are direct views whose destinations the plan itself places in the scratch -- three uint8 planes, rows yuv_stage_pitch()
+// apart -- and whose surfaces travel in DecYuvStore records to dec_yuv_store_kernel (yuv_store.h).  An empty plan (a call
 // without views) holds nothing and every method returns at once.
 struct ViewPlan {
     ViewRequest rq;      // as normalised by decode_api.cpp (normalise_views): posts only when some view is a post view, and then with colors
@@ -148,6 +185,8 @@ struct ViewPlan {
     std::vector<uint32_t> color_view;                  // per record of a colour launch: its view's index in rq.colors
     std::vector<int32_t> post_of;                      // per record of a post call: its index in post_recs, or -1 for a direct view
     std::vector<DecViewPost> post_recs;                // per post view
+    std::vector<DecYuvStore> yuv_recs;                 // per record of a YUV call: its surface (src: an offset into the intermediate planes until place())
+    std::vector<uint64_t> yuv_pre;                     // ... and one more: the workgroups of dec_yuv_store_kernel of the records in front
     std::vector<DecToneRef> tone_refs;                 // per tone view -- a post view with a tone op -- and the entry that closes the sums
     std::vector<uint32_t> job_rec, job_post, job_tone; // per job and one more: its first record, post record and tone view
     // the NEAREST views' indices (resize.h: DecResize::nearest), w + h words per such record, in the records' order; until place()
@@ -161,17 +200,20 @@ struct ViewPlan {
     std::vector<DecResize> file_recs; // (the file at hand: its views' records, their source boxes, pixel_elems and flags)
     std::vector<DecCrop> file_boxes;
     std::vector<std::pair<uint32_t, uint32_t>> file_px;
+    std::vector<DecYuvStore> file_yuv;  // (a YUV call: its views' surfaces)
     std::vector<uint32_t> file_nearest; // (its NEAREST views' indices; a record's `nearest`: 1 + its first word's index here)
 
     // the scratch: offsets from carve_*(), pointers from place().  recs, pre, post, tone_refs lie inside the set-up block
     struct Carves {
-        size_t recs = 0, pre = 0, post = 0, tone_refs = 0, nearest = 0, mid = 0, tone = 0;
+        size_t recs = 0, pre = 0, post = 0, tone_refs = 0, nearest = 0, yuv = 0, yuv_pre = 0, mid = 0, tone = 0;
     } at;
     uint8_t *d_recs = nullptr, *d_mid = nullptr, *d_tone = nullptr;
     uint64_t *d_pre = nullptr;
     uint32_t *d_nearest = nullptr;
     DecViewPost *d_post = nullptr;
     DecToneRef *d_tone_refs = nullptr;
+    DecYuvStore *d_yuv = nullptr;
+    uint64_t *d_yuv_pre = nullptr;
 
     bool active() const { return rq.views != nullptr; }
     bool multi() const { return rq.view_count != nullptr; }
@@ -206,6 +248,7 @@ struct ViewPlan {
             for (uint32_t i = 0, at_view = 0; i < n_files; at_view += rq.view_count[i++]) view_ofs[i] = at_view;
         }
         if (active()) plane_pre.assign(1, 0), tile_pre.assign(1, 0);
+        if (rq.yuv) yuv_pre.assign(1, 0);
     }
 
     // what the crop stage decodes of file i: the ONE box that holds the boxes of all of its views (which file_records() uses)
@@ -224,14 +267,21 @@ struct ViewPlan {
     {
         if (crop.w >= 0x80000000u) return {FPNG_AMD_ERR_INVALID_ARG, "crop.w >= 2^31"};
         const uint32_t v0 = first_view(i), nv = views_of(i);
-        file_recs.clear(), file_px.clear(), file_nearest.clear();
+        file_recs.clear(), file_px.clear(), file_nearest.clear(), file_yuv.clear();
         for (uint32_t v = v0; v < v0 + nv; v++) {
             const fpng_amd_resize_view &z = rq.views[v];
-            const fpng_amd_view_dest dest = rq.hwc     ? fpng_amd_view_dest{rq.hwc[v].d_pixels, 0, 0, 0}
-                                            : rq.dests ? rq.dests[v]
-                                                       : fpng_amd_view_dest{(uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap};
-            const DestPitches d = rq.hwc ? judge_hwc_dest(rq.hwc[v], z.w, z.h, planes, elem)
-                                         : judge_planar_dest(dest.d_pixels, dest.row_pitch, dest.plane_pitch, dest.pixels_cap, z.w, z.h, planes, elem);
+            fpng_amd_view_dest dest = rq.hwc     ? fpng_amd_view_dest{rq.hwc[v].d_pixels, 0, 0, 0}
+                                      : rq.dests ? rq.dests[v]
+                                                 : fpng_amd_view_dest{(uint8_t *)f.d_pixels, x.row_pitch, x.plane_pitch, f.pixels_cap};
+            DestPitches d;
+            if (rq.yuv) { // (the resize writes three uint8 planes into the scratch, as a post view's; the surface travels to dec_yuv_store_kernel)
+                int64_t pitch = 0;
+                if (const Refusal no = judge_yuv_dest(rq.yuv[v], rq.yuv_fmt->surface, z.w, z.h, true, &pitch)) return no;
+                const uint32_t stage = yuv_stage_pitch(z.w);
+                file_yuv.push_back({nullptr, (uint8_t *)rq.yuv[v].d_luma, pitch, rq.yuv[v].chroma_offset, (uint64_t)stage * z.h, stage, z.w, z.h, 0});
+                dest.d_pixels = nullptr, d.pitch = (int64_t)stage, d.plane_pitch = (int64_t)((uint64_t)stage * z.h);
+            } else
+                d = rq.hwc ? judge_hwc_dest(rq.hwc[v], z.w, z.h, planes, elem) : judge_planar_dest(dest.d_pixels, dest.row_pitch, dest.plane_pitch, dest.pixels_cap, z.w, z.h, planes, elem);
             if (d.refused) return d.refused;
             if (resize_tiles(z.w, z.h) * 4 * kResizeBlock >= (1ull << 32)) return {FPNG_AMD_ERR_UNSUPPORTED, "an output size of more than 2^22 tiles of 64 x 16"};
             const DecCrop whole_crop = {rq.crops[v].x, rq.crops[v].y, rq.crops[v].w, rq.crops[v].h}, box = file_boxes[v - v0];
@@ -305,6 +355,13 @@ struct ViewPlan {
         nearest.insert(nearest.end(), file_nearest.begin(), file_nearest.end());
         const size_t out = mid_total;
         mid_total += ((size_t)crop.w * crop.h * (in_scratch ? in_scratch : planes) + 15) & ~(size_t)15;
+        // (a YUV call's views: their three planes next to the box's, rows and planes a multiple of 16 bytes)
+        for (size_t q = job_rec.back(), k = 0; rq.yuv && q < resize.size(); q++, k++) {
+            resize[q].dst = (uint8_t *)(uintptr_t)mid_total; // (an offset until place())
+            yuv_recs.push_back(file_yuv[k]);
+            yuv_pre.push_back(yuv_pre.back() + yuv_store_blocks(rq.yuv_fmt->surface, resize[q].w, resize[q].h));
+            mid_total += (size_t)yuv_recs.back().src_plane_pitch * 3;
+        }
         // (the post views' windows: next to the box's planes)
         for (size_t q = job_rec.back(); rq.posts && q < resize.size(); q++)
             if (post_of[q] >= 0) {
@@ -341,6 +398,8 @@ struct ViewPlan {
         at.post = sc.carve(post_recs.size() * sizeof(DecViewPost));
         at.tone_refs = sc.carve(tone_refs.size() * sizeof(DecToneRef));
         at.nearest = sc.carve(nearest.size() * sizeof(uint32_t));
+        at.yuv = sc.carve(yuv_recs.size() * sizeof(DecYuvStore));
+        at.yuv_pre = sc.carve(yuv_pre.size() * sizeof(uint64_t));
     }
     template <class S> void carve_scratch(S &sc)
     {
@@ -354,6 +413,7 @@ struct ViewPlan {
         d_recs = base + at.recs, d_mid = base + at.mid;
         d_pre = multi() ? (uint64_t *)(base + at.pre) : nullptr;
         d_nearest = (uint32_t *)(base + at.nearest);
+        d_yuv = rq.yuv ? (DecYuvStore *)(base + at.yuv) : nullptr, d_yuv_pre = rq.yuv ? (uint64_t *)(base + at.yuv_pre) : nullptr;
         d_post = rq.posts ? (DecViewPost *)(base + at.post) : nullptr;
         d_tone_refs = n_tone() ? (DecToneRef *)(base + at.tone_refs) : nullptr, d_tone = n_tone() ? base + at.tone : nullptr;
         for (size_t t = 0; t < n_tone(); t++) post_recs[tone_refs[t].rec].tone = (uint32_t *)(d_tone + t * kToneBytes);
@@ -361,6 +421,7 @@ struct ViewPlan {
             resize[q].src = d_mid + (size_t)(uintptr_t)resize[q].src;
             if (resize[q].nearest) resize[q].nearest = d_nearest + ((size_t)(uintptr_t)resize[q].nearest - 1);
             if (rq.posts && post_of[q] >= 0) post_recs[post_of[q]].src = resize[q].dst = d_mid + (size_t)(uintptr_t)resize[q].dst;
+            if (rq.yuv) yuv_recs[q].src = resize[q].dst = d_mid + (size_t)(uintptr_t)resize[q].dst;
         }
     }
 
@@ -389,6 +450,10 @@ struct ViewPlan {
         uint8_t *const h_recs = h_setup + (at.recs - setup_ofs), *const h_pre = h_setup + (at.pre - setup_ofs);
         const size_t nd = resize.size() - post_recs.size(), step = rec_bytes();
         if (!nearest.empty()) std::memcpy(h_setup + (at.nearest - setup_ofs), nearest.data(), nearest.size() * sizeof(uint32_t));
+        if (!yuv_recs.empty()) {
+            std::memcpy(h_setup + (at.yuv - setup_ofs), yuv_recs.data(), yuv_recs.size() * sizeof(DecYuvStore));
+            std::memcpy(h_setup + (at.yuv_pre - setup_ofs), yuv_pre.data(), yuv_pre.size() * sizeof(uint64_t));
+        }
         size_t di = 0, pi = 0;
         if (rq.posts) dir_pre.assign(1, 0), post_pre.assign(1, 0), job_post.clear();
         for (size_t k = 0, q = 0; k < job_rec.size(); k++) {

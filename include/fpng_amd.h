@@ -1511,6 +1511,82 @@ int fpng_amd_yuv_matrix(uint32_t standard, int full_range, float m[12]);
  * as by the submit call. */
 int fpng_amd_yuv_pixels(const fpng_amd_yuv_frame *frames, uint32_t n_frames, const fpng_amd_yuv_format *fmt, uint32_t frame_index,
                         const fpng_amd_rendition *rendition, uint8_t *out, size_t out_cap);
+/* ---- DECODING INTO YUV VIDEO SURFACES: the views of fpng_amd_decode_batch(_device)_planar_views written as the surfaces a
+ *      hardware video encoder takes -- frame sequences kept as fpng files, fed to an encoder at a fixed size or as the sizes of an
+ *      adaptive-bitrate ladder, one decode of a file for all of its sizes -- without a colour-conversion kernel of the caller's.
+ *      SURFACES: the four of the encode side above (FPNG_AMD_YUV_NV12, _P016, _444, _444_16), one base pointer, ONE row pitch for
+ *      all planes, one signed chroma offset.
+ *      THE RULE (csrc/yuv_store.h, the one text that dec_yuv_store_kernel and fpng_amd_yuv_surface compile).  P: the view's three
+ *      uint8 planes R, G, B (w x h) -- exactly what fpng_amd_decode_batch(_device)_planar_views writes for that file, crop and view
+ *      with num_chans = 3 and fmt == NULL (a 4-channel file's alpha is dropped).  f: the call's 3 x 4 fp32 matrix, rows Y, Cb, Cr,
+ *      columns R, G, B, offset.  d: the depth, 8 on the 8-bit surfaces, 10, 12 or 16 on the 16-bit ones.
+ *        t_c(r, g, b) = fmaf(f[c][2], b, fmaf(f[c][1], g, fmaf(f[c][0], r, f[c][3])))       the colour rule of the views calls
+ *        elem_d(t)    = rint(fminf(fmaxf(t * 2^(d-8), 0), 2^d - 1)), ties to even            (t * 2^(d-8) is exact)
+ *        Y(x, y)      = elem_d(t_0(P_R[y][x], P_G[y][x], P_B[y][x]))
+ *        4:4:4:  Cb(x, y) = elem_d(t_1(the same pixel)),  Cr(x, y) = elem_d(t_2(the same pixel))
+ *        4:2:0:  chroma sample (i, j), i < ceil(w / 2), j < ceil(h / 2):
+ *                S_k = P_k[min(2j, h-1)][min(2i, w-1)] + P_k[min(2j, h-1)][min(2i+1, w-1)]
+ *                    + P_k[min(2j+1, h-1)][min(2i, w-1)] + P_k[min(2j+1, h-1)][min(2i+1, w-1)]      (integer, 0 .. 1020)
+ *                m_k = (float)S_k * 0.25f                                                           (exact)
+ *                Cb = elem_d(t_1(m_R, m_G, m_B)),  Cr = elem_d(t_2(m_R, m_G, m_B))
+ *      A 16-bit element is stored as elem_d << (16 - d), little-endian, MSB-aligned: the P010 / P012 / P016 form that the encode
+ *      side reads back as word * 2^-8.  The chroma of a 4:2:0 surface is the MEAN of its 2 x 2 block (centre siting); at an odd
+ *      edge the existing pixels count twice.  There is no chroma siting option.  Nothing is clamped to 16..235 beyond the clamp
+ *      to the element range.
+ *      THE MATRIX.  fpng_amd_yuv_matrix_from_rgb(standard, full_range, m) fills it for BT.601, BT.709 and BT.2020 (Kr, Kb: those
+ *      of fpng_amd_yuv_matrix).  With kg = 1 - kr - kb, each coefficient in double, rounded to fp32:
+ *        Y:  kr sy, kg sy, kb sy;   Cb: -kr / (2 (1 - kb)) sc, -kg / (2 (1 - kb)) sc, 0.5 sc;
+ *        Cr: 0.5 sc, -kg / (2 (1 - kr)) sc, -kb / (2 (1 - kr)) sc
+ *      full range: sy = sc = 1, offsets 0, 128, 128; limited range: sy = 219 / 255, sc = 224 / 255, offsets 16, 128, 128.
+ *      FPNG_AMD_ERR_INVALID_ARG for an unknown standard or a null m.  A caller's own matrix: finite entries of magnitude <= 65536;
+ *      NV21 / YVU orders are a swap of its rows 1 and 2.  Every grey (k, k, k) gives chroma exactly 128 << (d - 8), and in full
+ *      range luma exactly k << (d - 8).  A 4:4:4 surface of depth 10, 12 or 16 converted back by the encode side under
+ *      fpng_amd_yuv_matrix's matrix of the same standard and range returns the R, G, B bytes; depth 8 does not (most pixels differ by
+ *      1 or 2).
+ *      THE CALL.  files, view_count, crops, views and results are those of fpng_amd_decode_batch(_device)_planar_views, with every
+ *      rule of that call: the files' destination fields are NULL / 0, one box is decoded per file, statuses 64 and 67,
+ *      FPNG_AMD_DECODE_MAX_ROUNDS and the checksum flags behave as there, bilinear and bicubic filters, the mirror flag and a window
+ *      of the resized crop are available, and a view with full == crop size is the identity (the whole file at its own size is such
+ *      a view).  files[i].num_chans must be 3.  dests: one fpng_amd_yuv_dest per view.  row_pitch 0 = tight: w elements, on the
+ *      4:2:0 surfaces 2 ceil(w / 2).  surface_cap counts from the top row of the LOWEST-addressed plane to the last element of the
+ *      highest one.  8-bit planes may start at any byte.  Only the surfaces' elements are written, whatever a file's status: not a
+ *      byte of pitch padding, between the planes, in front of or behind them.  Destinations of one call must not overlap.
+ *      REFUSALS, each FPNG_AMD_ERR_INVALID_ARG (too little room: FPNG_AMD_ERR_BUFFER_TOO_SMALL) with nothing launched: a null fmt or
+ *      dests; an unknown surface; a depth the surface does not have; a bad matrix entry; reserved != 0; a negative row_pitch; a
+ *      row_pitch below the view's w elements or, on the 4:2:0 surfaces, below 2 ceil(w / 2) elements; on the 16-bit surfaces d_luma,
+ *      row_pitch or chroma_offset not a multiple of 2; |chroma_offset| < (h - 1) row_pitch + w elements (the planes overlap); a null
+ *      d_luma or too little surface_cap for a file whose header is accepted.
+ *      NOT OFFERED by this call: the colour, post, warp, tone, enhance, alpha and resample records, fpng_amd_decode_host and the
+ *      fpng:: drop-in.
+ *      HOW.  The views go through the planar views path into three uint8 planes in the decode scratch (rows padded to 16 bytes);
+ *      dec_yuv_store_kernel, enqueued behind the resize on the same stream, converts them: one more write and one more read of 3
+ *      bytes per output pixel in front of the 1.5 - 6 bytes of the surface.  Measured once (profiles/yuv_store_timing.txt, one
+ *      MI355X, 8 x 4K RGB files -> NV12): at 1080p 0.87 ms a step against 0.83 ms for the planar views call into uint8 planes
+ *      alone and 2.26 ms for that call followed by a torch expression of the conversion; at the files' own size 1.28 / 1.18 /
+ *      3.75 ms.
+ *      fpng_amd_yuv_surface is the HOST twin, no GPU: rgb = tight h x w x 3 bytes in host memory, host_dest->d_luma a HOST pointer;
+ *      the record and the format are validated as by the call.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_yuv_views with dlsym. ---- */
+typedef struct fpng_amd_yuv_dest {
+    void *d_luma;          /* DEVICE: the luma plane's top row */
+    int64_t row_pitch;     /* bytes, of every plane; 0 = tight (w elements; 4:2:0: 2 ceil(w/2)) */
+    int64_t chroma_offset; /* signed bytes luma top row -> chroma top row (4:4:4: and Cb -> Cr) */
+    size_t surface_cap;    /* bytes writable from the LOWEST-addressed plane's top row: up to the last element of the highest plane */
+    uint64_t reserved;     /* 0 */
+} fpng_amd_yuv_dest;       /* 40 bytes */
+typedef struct fpng_amd_yuv_store_format {
+    uint32_t surface;      /* FPNG_AMD_YUV_NV12 / _P016 / _444 / _444_16 */
+    uint32_t depth;        /* 0 = the surface's own (8 / 16); 8-bit surfaces: 0 or 8; 16-bit: 0, 10, 12, 16 */
+    float m[3][4];         /* row c = Y, Cb, Cr: m[c][0] R + m[c][1] G + m[c][2] B + m[c][3] */
+} fpng_amd_yuv_store_format; /* 56 bytes */
+int fpng_amd_decode_batch_yuv_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                    const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_yuv_dest *dests,
+                                    const fpng_amd_yuv_store_format *fmt, fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_yuv_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const uint32_t *view_count,
+                                           const fpng_amd_crop *crops, const fpng_amd_resize_view *views, const fpng_amd_yuv_dest *dests,
+                                           const fpng_amd_yuv_store_format *fmt, fpng_amd_decode_result *results);
+int fpng_amd_yuv_matrix_from_rgb(uint32_t standard, int full_range, float m[12]);
+int fpng_amd_yuv_surface(const uint8_t *rgb, uint32_t w, uint32_t h, const fpng_amd_yuv_store_format *fmt, const fpng_amd_yuv_dest *host_dest);
 /* One HOST-resident file to HOST pixels (reference src/fpng.h:108 fpng_decode_memory; the fpng:: drop-in routes images of
  * 256K pixels and more through it): container checks, upload, GPU decode, download into memory obtained from `reserve`.
  * `reserve` is called with w * h * desired_chans once the container and the block header are accepted -- BEFORE the stream is known

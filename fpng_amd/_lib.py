@@ -184,6 +184,11 @@ class DecodeResult(C.Structure):
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels_in_file", C.c_uint32), ("status", C.c_int32)]
 
 
+# fpng_amd_decode_batch(_device)_png: the general decode tier for ordinary PNG files
+DECODE_UNSUPPORTED_PNG = 67  # FPNG_AMD_DECODE_UNSUPPORTED_PNG: a valid PNG the tier does not decode (other bit depths, interlace, unknown critical chunks)
+PNG_GENERAL_ONLY = 1  # FPNG_AMD_PNG_GENERAL_ONLY: flags -- every file through the general tier, fpng-written ones too
+
+
 class BandPlan(C.Structure):
     _fields_ = [("end_bit", C.c_uint64), ("zlib_size", C.c_uint64), ("adler", C.c_uint32), ("stored", C.c_uint32)]
 
@@ -278,6 +283,9 @@ SIGNATURES = {
     "fpng_amd_node_encode_host_image": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, RESERVE_FN, _vp, C.POINTER(_sz)]),
     "fpng_amd_decode_batch": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_png": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_batch_device_png": (_int, [_vp, C.POINTER(PngIn), _u32, _u32, _u32, C.POINTER(DecodeResult)]),
+    "fpng_amd_decode_png_last_kernel_ms": (_int, [_vp, C.POINTER(C.c_float * 2)]),
     "fpng_amd_decode_batch_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_device_ex": (_int, [_vp, C.POINTER(PngExIn), _u32, C.POINTER(DecodeResult)]),
     "fpng_amd_decode_batch_planar": (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(DecodeResult)]),

@@ -35,6 +35,8 @@ VERIFY_CRC32, VERIFY_ADLER32 = 1, 2
 DECODE_BAD_CRC32, DECODE_BAD_ADLER32 = 65, 66
 # a file's status when its crop leaves the image (Encoder.decode_device_crop; FPNG_AMD_DECODE_CROP_OUTSIDE)
 DECODE_CROP_OUTSIDE = _lib.DECODE_CROP_OUTSIDE
+FPNG_AMD_DECODE_UNSUPPORTED_PNG = _lib.DECODE_UNSUPPORTED_PNG  # decode_device_png / decode_batch_png: a valid PNG the general tier does not decode
+FPNG_AMD_PNG_GENERAL_ONLY = _lib.PNG_GENERAL_ONLY  # ... flags: every file through the general tier, fpng-written ones too
 # fpng_amd_resize.flags (Encoder.decode_device_resize: mirror=True sets it): the output's columns in reverse order
 RESIZE_MIRROR = _lib.RESIZE_MIRROR
 # fpng_amd_resize_view.filter (Encoder.decode_device_resize_view: filter="bilinear" / "bicubic")
@@ -1494,6 +1496,20 @@ class DecodeBatchEx(_DecodeBatchViews):
     maker = "make_decode_batch_ex"
 
 
+class DecodeBatchPng(_DecodeBatchViews):
+    """What Encoder.make_decode_batch_png() returns: the files (ordinary PNGs), the output tensors and the C arrays of one
+    fpng_amd_decode_batch(_device)_png() call."""
+
+    maker = "make_decode_batch_png"
+
+    def results(self):
+        """list of (status, uint8 CUDA tensor (h, w, desired_chans) or None, channels_in_file)"""
+        out, d = [], self.desired_chans
+        for r, t in zip(self.res, self.outs):
+            out.append((r.status, t.view(-1)[: r.w * r.h * d].view(r.h, r.w, d) if r.status == 0 else None, r.channels_in_file))
+        return out
+
+
 class DecodeBatchPlanar(_DecodeBatchViews):
     """What Encoder.make_decode_batch_planar() returns: the same for one fpng_amd_decode_batch(_device)_planar() call (outs: the
     caller's (c, h, w) views).  Not a DecodeBatchEx: neither call takes the other's descriptor."""
@@ -2247,6 +2263,64 @@ class Encoder:
         self._sync_stream()
         check(self.lib.fpng_amd_decode_batch_device(self.h, batch.arr, len(batch.arr), batch.desired_chans, batch.res))
         return batch.results() if results else batch
+
+    def make_decode_batch_png(self, pngs, desired_chans=4, dims=None, outs=None, flags=0):
+        """Descriptor (fpng_amd_png[n] + the result records) for decode_device_png() / decode_batch_png(): ordinary PNG files --
+        uint8 CUDA tensors holding whole files, or bytes-like objects in host memory, one kind per batch.  dims: list of (w, h)
+        that sizes the output tensors (default: read from the files' headers); outs: preallocated contiguous uint8 CUDA tensors
+        of at least w * h * desired_chans elements to decode into instead."""
+        import struct
+        who = "make_decode_batch_png"
+        n = len(pngs)
+        if desired_chans not in (3, 4):
+            raise ValueError(f"{who}: desired_chans is 3 or 4")
+        if outs is not None and len(outs) != n:
+            raise ValueError(f"{who}: {n} files, {len(outs)} destinations")
+        arr = (_lib.PngIn * n)()
+        res = (_lib.DecodeResult * n)()
+        device_data, keep = _file_records(who, pngs, arr)
+        if outs is None and dims is None:
+            if device_data:  # (the headers' 24 bytes, one copy for the batch)
+                heads = torch.stack([torch.nn.functional.pad(p[:24], (0, max(0, 24 - p.numel()))) for p in pngs]).cpu().numpy() if n else np.zeros((0, 24), np.uint8)
+                dims = [struct.unpack(">II", heads[i, 16:24].tobytes()) for i in range(n)]
+            else:
+                dims = [struct.unpack(">II", bytes(p[16:24])) if len(p) >= 24 else (0, 0) for p in pngs]
+        made = []
+        for i in range(n):
+            if outs is not None:
+                t = outs[i]
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+                    raise ValueError(f"{who}: the destinations are contiguous uint8 CUDA tensors")
+            else:
+                w, h = dims[i]
+                cap = w * h * desired_chans if 0 < w <= (1 << 24) and 0 < h <= (1 << 24) and w * h <= (1 << 30) else 0
+                t = torch.empty(max(cap, 16), dtype=torch.uint8, device=f"cuda:{self.device}")
+            made.append(t)
+            arr[i].d_pixels, arr[i].pixels_cap = t.data_ptr(), t.numel()
+        return DecodeBatchPng(list(pngs), made, arr, res, device_data, keep, desired_chans=desired_chans, flags=flags)
+
+    def _decode_png(self, device_data, pngs, desired_chans, dims, outs, flags, results):
+        return self._run_decode(DecodeBatchPng, device_data, pngs, lambda who: self.make_decode_batch_png(pngs, desired_chans, dims, outs, flags),
+                                lambda b: ("fpng_amd_decode_batch_device_png" if device_data else "fpng_amd_decode_batch_png", [b.arr, len(b.arr), b.desired_chans, b.flags, b.res]),
+                                results)
+
+    def decode_device_png(self, pngs, desired_chans=4, dims=None, outs=None, flags=0, results=True):
+        """fpng_amd_decode_batch_device_png: ordinary PNG files (8-bit grey, grey + alpha, RGB, palette, RGBA; any zlib stream, all
+        five filters, any number of IDAT chunks) in uint8 CUDA tensors -> list of (status, uint8 CUDA tensor (h, w, desired_chans)
+        or None, channels_in_file).  fpng-written files of the batch take the fpng path unless flags has FPNG_AMD_PNG_GENERAL_ONLY;
+        FPNG_AMD_DECODE_UNSUPPORTED_PNG: a valid PNG outside this tier (other bit depths, interlace, unknown critical chunks).
+        pngs may be a make_decode_batch_png() descriptor; results=False returns the descriptor."""
+        return self._decode_png(True, pngs, desired_chans, dims, outs, flags, results)
+
+    def decode_batch_png(self, pngs, desired_chans=4, dims=None, outs=None, flags=0, results=True):
+        """fpng_amd_decode_batch_png: decode_device_png() for files in host memory (bytes-like objects), uploaded in groups."""
+        return self._decode_png(False, pngs, desired_chans, dims, outs, flags, results)
+
+    def last_decode_png_kernel_ms(self):
+        """with profiling on: (inflate ms, un-filter ms) of the last decode_*_png call's first group of general-tier files"""
+        ms = (C.c_float * 2)()
+        check(self.lib.fpng_amd_decode_png_last_kernel_ms(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     @staticmethod
     def make_decode_batch_ex(pngs, outs, order="rgb", bottom_up=False):

@@ -413,6 +413,8 @@ void fpng_amd_encoder_destroy(fpng_amd_encoder *e)
     e->d_lut_cache.release();
     for (hipEvent_t ev : e->dec_prof_ev)
         if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->png_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->dec_ev2)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->dec_ev3)

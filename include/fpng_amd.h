@@ -478,6 +478,46 @@ int fpng_amd_decode_batch(fpng_amd_encoder *enc, const fpng_amd_png *files, uint
                           fpng_amd_decode_result *results);
 int fpng_amd_decode_batch_device(fpng_amd_encoder *enc, const fpng_amd_png *files, uint32_t n, uint32_t desired_chans,
                                  fpng_amd_decode_result *results);
+/* ---- decoding ORDINARY PNG files -- what libpng, Pillow or zlib write -- with a second, general tier on the GPU (png_inflate.hip):
+ *      RFC 1950 / 1951 inflate, PNG filters 0-4, 8-bit grey, grey + alpha, RGB, palette and RGBA, any number of IDAT chunks.  One
+ *      file is decoded by one wavefront: throughput comes from the number of files in the batch.
+ *      The calls follow fpng_amd_decode_batch(_device): the same records, desired_chans 3 or 4, tight w * h * desired_chans bytes in
+ *      device memory, the call returns when they are there, the same argument and room rules (FPNG_AMD_ERR_BUFFER_TOO_SMALL for a
+ *      file whose header is accepted and whose d_pixels / pixels_cap does not hold it); nothing is written for a file whose header
+ *      is refused.  channels_in_file is 1, 2, 3 or 4 by colour type (palette: 3, or 4 with a tRNS chunk).
+ *      Routing: a file that carries fpng's marker chunk behind its IHDR goes through fpng_amd_decode_batch(_device), bit for bit
+ *      as there; every other file goes through the general tier, and so does a marked file that the fpng path answers with
+ *      FPNG_DECODE_NOT_FPNG or FPNG_AMD_DECODE_UNDECIDED -- these calls never return UNDECIDED.  FPNG_AMD_PNG_GENERAL_ONLY in
+ *      `flags` sends every file through the general tier.  fpng_amd_encoder_set_decode_verify applies to the fpng path's files only.
+ *      Pixels: grey is replicated to R, G, B; alpha is kept at 4 channels and dropped at 3; palette indices are looked up in PLTE,
+ *      alpha from tRNS (255 behind its end); a tRNS colour key on grey or RGB files gives alpha 0 at 4 channels to the pixels whose
+ *      bytes equal the LOW bytes of the key's 16-bit samples -- what Pillow's convert("RGBA") does -- and changes nothing at 3.
+ *      Status per file: FPNG_DECODE_FAILED_NOT_PNG / _HEADER_CRC32 / _INVALID_DIMENSIONS / _DIMENSIONS_TOO_LARGE for signature, IHDR
+ *      and dimensions as in the fpng path (w, h <= 2^24, w * h <= 2^30, 32-bit file size);
+ *      FPNG_AMD_DECODE_UNSUPPORTED_PNG for a valid PNG outside this tier: bit depth 1, 2, 4 or 16, Adam7 interlace, an unknown
+ *      critical chunk (APNG's included), and for an IHDR with an unknown colour type, compression or filter method;
+ *      FPNG_DECODE_FAILED_CHUNK_PARSING for a chunk that leaves the file or has a type that is not four letters, IDAT chunks that are
+ *      not consecutive, no IDAT, a palette file without PLTE or whose PLTE length is no multiple of 3 or above 768;
+ *      FPNG_DECODE_FAILED_INVALID_IDAT for everything wrong with the stream: a bad zlib header (CM, window, FDICT, FCHECK), block
+ *      type 3, a stored block whose LEN != ~NLEN, over-subscribed or incomplete codes (the distance code may have one code, or
+ *      none), no end-of-block code, a repeat with nothing in front of it, more than 286 / 30 code lengths, symbols 286 / 287 or
+ *      30 / 31, a distance in front of the first output byte, input that ends before the final block's end-of-block symbol, fewer
+ *      than h * (1 + bytes per row) bytes of output, a filter byte above 4, a palette index at or behind PLTE's entry count.
+ *      The whole stream is inflated and checked; output beyond the image is never stored and does not make a file fail (Pillow
+ *      accepts such files too).  Chunk CRCs behind IHDR, the Adler-32 and the presence of IEND are not checked.
+ *      (67 is also FPNG_AMD_DECODE_CROP_OUTSIDE: the crop calls never return the one, these calls never the other.)
+ *      Device scratch: the batch's filtered scanlines, h * (1 + bytes per row) per general-tier file, and for host-resident
+ *      files their own bytes; above FPNG_AMD_PNG_SCRATCH_LIMIT bytes (environment, default 2^30) the files run in groups that reuse it.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_png with dlsym. ---- */
+#define FPNG_AMD_DECODE_UNSUPPORTED_PNG 67 /* a valid PNG this tier does not decode */
+#define FPNG_AMD_PNG_GENERAL_ONLY 1u       /* flags: send every file through the general tier, fpng-written ones too */
+int fpng_amd_decode_batch_png(fpng_amd_encoder *enc, const fpng_amd_png *files, uint32_t n, uint32_t desired_chans, uint32_t flags,
+                              fpng_amd_decode_result *results);
+int fpng_amd_decode_batch_device_png(fpng_amd_encoder *enc, const fpng_amd_png *files, uint32_t n, uint32_t desired_chans, uint32_t flags,
+                                     fpng_amd_decode_result *results);
+/* with fpng_amd_encoder_set_profiling on: the milliseconds the last such call's first group of general-tier files spent in the
+ * inflate kernel and in the un-filter kernel (zeros when there was none) */
+int fpng_amd_decode_png_last_kernel_ms(fpng_amd_encoder *enc, float ms[2]);
 /* ---- decoding into other pixel layouts: strided, bottom-up, BGR(A), padded alpha -- the twin of fpng_amd_encode_submit_ex.  A
  *      FPNG_AMD_SRC_* format names the DESTINATION pixel here and fixes its bytes; the values are those fpng_decode_memory() gives
  *      for desired_channels = 3 (RGB, BGR) or 4 (the others), reordered into the format:

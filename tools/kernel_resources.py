@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fpng_amd", "csrc")
 defs = [a for a in sys.argv[1:] if a.startswith("-D")]
 with tempfile.TemporaryDirectory() as t:
-    for src in ("kernels.hip", "decode.hip", "resize.hip", "resize_color.hip", "view_post.hip", "view_tone.hip", "yuv_store.hip"):
+    for src in ("kernels.hip", "decode.hip", "resize.hip", "resize_color.hip", "view_post.hip", "view_tone.hip", "yuv_store.hip", "png_inflate.hip"):
         co = os.path.join(t, src + ".s")
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-gpu-rdc", "--cuda-device-only", "-S", "-I", os.path.join(ROOT, "include"),
                                "-I", CSRC, "-o", co, "-x", "hip", os.path.join(CSRC, src)] + defs, stderr=subprocess.DEVNULL)

@@ -1,7 +1,8 @@
 // png_loader.h -- a small, self-contained PNG reader for the fpng_amd_test harness: ANY PNG, interlaced (Adam7) or not (grey, RGB,
 // palette, grey+alpha, RGBA; 1/2/4/8/16 bits per sample; tRNS) to 8-bit RGBA, the role lodepng_decode_memory(..., LCT_RGBA, 8)
 // plays in the reference's harness (reference src/fpng_test.cpp:1116-1122).  Plain RFC 1950/1951 inflate + PNG filters 0-4
-// (RFC 2083), no dependencies.  Test-tool code: the product never reads PNGs other than its own (fpng_decode.cpp).
+// (RFC 2083), no dependencies.  Test-tool code: the product's own reader of foreign PNGs is the GPU's general decode
+// tier (fpng_amd/csrc/png_inflate_core.h: 8-bit, no interlace); fpng::fpng_decode_memory reads fpng's files only (fpng_decode.cpp).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>

@@ -11,8 +11,10 @@
 //     h * (1 + bytes per row) bytes is inflated, checked and never stored; such a file is ACCEPTED, as Pillow 12 accepts it (its
 //     decoder stops at the image's last row and never looks at what follows; a damaged stream behind the image, which Pillow
 //     therefore lets pass, is refused here).
-//   * Literal/length codes must be complete; the distance code may be complete, have one single code (RFC 1951; fpng writes it)
-//     or no code at all (a block of literals).
+//   * The code length code must be complete.  The literal/length and the distance code may each be complete or consist of one
+//     single 1-bit code, as zlib allows (RFC 1951 for distances; fpng writes it): for literal/length that is the end-of-block
+//     symbol alone, a block without output.  The distance code may also have no code at all (a block of literals).  The unused
+//     code of a single-code table is no code: meeting it is INVALID_IDAT.
 //   * Chunk CRCs behind IHDR, the stream's Adler-32 and the presence of IEND are not checked.  The zlib window size is checked in
 //     the header only: distances are held against the output so far and 32768.
 //   * Every loop ends because it consumes input bits or file bytes, or produces output bytes: the file has at most 2^32 bytes, a
@@ -203,7 +205,8 @@ PNGI_FN bool pngi_overrun(const Reader &r) { return r.cnt < r.pad; }
 
 // ---- Huffman tables ----
 // lens[0 .. n) -> count / sym / fast (in LDS).  Lane 0 counts, checks and numbers the codes, all lanes fill the fast table.
-// may_be_short: the distance code's exceptions (one code, or none).  Returns false for an over-subscribed or incomplete code.
+// may_be_short: the exceptions of the literal/length and the distance code (one 1-bit code, or none; the caller refuses a
+// literal/length code without the end-of-block symbol).  Returns false for an over-subscribed or incomplete code.
 PNGI_FN bool pngi_build(InflateShared &sh, const uint8_t *lens, uint32_t n, uint16_t *count, uint16_t *sym, uint16_t *fast, uint32_t fast_bits, bool may_be_short)
 {
     PNGI_SYNC();
@@ -489,7 +492,8 @@ PNGI_FN uint32_t pngi_stream(InflateShared &sh, const File &f, Reader &r)
             }
         }
         PNGI_SYNC();
-        if (!pngi_build(sh, sh.lens, n_lit, sh.lit_count, sh.lit_sym, sh.lit_fast, kLitFastBits, false)) return kBadIdat;
+        // (a code of one 1-bit code passes here as it does for distances: with the check above it is the end-of-block symbol alone)
+        if (!pngi_build(sh, sh.lens, n_lit, sh.lit_count, sh.lit_sym, sh.lit_fast, kLitFastBits, true)) return kBadIdat;
         if (!pngi_build(sh, sh.lens + 288, n_dist, sh.dist_count, sh.dist_sym, sh.dist_fast, kDistFastBits, true)) return kBadIdat;
         for (bool eob = false; !eob;) { // a batch of up to 64 tokens.  Ends: every token takes at least one bit of a bounded input
             uint32_t n = 0, bytes = 0, bad = 0;

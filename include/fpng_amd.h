@@ -499,10 +499,12 @@ int fpng_amd_decode_batch_device(fpng_amd_encoder *enc, const fpng_amd_png *file
  *      FPNG_DECODE_FAILED_CHUNK_PARSING for a chunk that leaves the file or has a type that is not four letters, IDAT chunks that are
  *      not consecutive, no IDAT, a palette file without PLTE or whose PLTE length is no multiple of 3 or above 768;
  *      FPNG_DECODE_FAILED_INVALID_IDAT for everything wrong with the stream: a bad zlib header (CM, window, FDICT, FCHECK), block
- *      type 3, a stored block whose LEN != ~NLEN, over-subscribed or incomplete codes (the distance code may have one code, or
- *      none), no end-of-block code, a repeat with nothing in front of it, more than 286 / 30 code lengths, symbols 286 / 287 or
- *      30 / 31, a distance in front of the first output byte, input that ends before the final block's end-of-block symbol, fewer
- *      than h * (1 + bytes per row) bytes of output, a filter byte above 4, a palette index at or behind PLTE's entry count.
+ *      type 3, a stored block whose LEN != ~NLEN, over-subscribed or incomplete codes (as in zlib the literal/length and the
+ *      distance code may each consist of one 1-bit code -- for literal/length the end-of-block symbol alone -- whose unused code
+ *      is refused where it is met; the distance code may have none), no end-of-block code, a repeat with nothing in front of
+ *      it, more than 286 / 30 code lengths, symbols 286 / 287 or 30 / 31, a distance in front of the first output byte, input
+ *      that ends before the final block's end-of-block symbol, fewer than h * (1 + bytes per row) bytes of output, a filter
+ *      byte above 4, a palette index at or behind PLTE's entry count.
  *      The whole stream is inflated and checked; output beyond the image is never stored and does not make a file fail (Pillow
  *      accepts such files too).  Chunk CRCs behind IHDR, the Adler-32 and the presence of IEND are not checked.
  *      (67 is also FPNG_AMD_DECODE_CROP_OUTSIDE: the crop calls never return the one, these calls never the other.)

@@ -8,6 +8,8 @@ import zlib
 
 import numpy as np
 
+from deflate_writer import DIST_BASE, DIST_EXTRA, LENGTH_BASE, LENGTH_EXTRA, _bits, _msb
+
 OK, NOT_FPNG, NOT_PNG, HEADER_CRC32, BAD_DIMS, CHUNK_PARSING, INVALID_IDAT, UNDECIDED, UNSUPPORTED = 0, 1, 3, 4, 5, 7, 8, 64, 67
 BPP = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
 SIG = b"\x89PNG\r\n\x1a\n"
@@ -326,26 +328,6 @@ def idat_cases():
 
 def designed_cases():
     return format_cases() + shape_cases() + stream_cases() + idat_cases() + hand_cases()
-
-
-def _bits(*fields):
-    """(value, width) fields, LSB first -> bytes"""
-    v = at = 0
-    for val, n in fields:
-        v |= val << at
-        at += n
-    return v.to_bytes((at + 7) // 8, "little")
-
-
-LENGTH_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
-LENGTH_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
-DIST_BASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577)
-DIST_EXTRA = (0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13)
-
-
-def _msb(code, n):
-    """a Huffman code of n bits as a field of _bits (codes go out most significant bit first)"""
-    return (int(format(code, f"0{n}b")[::-1], 2), n)
 
 
 def fixed_symbol(s):

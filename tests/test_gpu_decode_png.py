@@ -43,10 +43,11 @@ def _to_device(files):
     return out
 
 
-def decode(enc, files, desired, flags=0, host=False):
-    """-> [(status, pixels as numpy (h, w, desired) or None, channels_in_file)]; asserts that the guard bands are untouched"""
+def decode(enc, files, desired, flags=0, host=False, dims=None):
+    """-> [(status, pixels as numpy (h, w, desired) or None, channels_in_file)]; asserts that the guard bands are untouched.
+    dims: the files' known (w, h), where they are no damaged files whose headers need the cap of _dims"""
     import torch
-    sizes = [max(w * h * desired, 1) for w, h in map(_dims, files)]
+    sizes = [max(w * h * desired, 1) for w, h in (map(_dims, files) if dims is None else dims)]
     arena = torch.full((sum(sizes) + GUARD * (len(files) + 1),), 0xA5, dtype=torch.uint8, device="cuda")
     outs, at = [], GUARD
     for n in sizes:

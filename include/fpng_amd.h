@@ -492,6 +492,11 @@ int fpng_amd_decode_batch_device(fpng_amd_encoder *enc, const fpng_amd_png *file
  *      Pixels: grey is replicated to R, G, B; alpha is kept at 4 channels and dropped at 3; palette indices are looked up in PLTE,
  *      alpha from tRNS (255 behind its end); a tRNS colour key on grey or RGB files gives alpha 0 at 4 channels to the pixels whose
  *      bytes equal the LOW bytes of the key's 16-bit samples -- what Pillow's convert("RGBA") does -- and changes nothing at 3.
+ *      A tRNS chunk of another length than its colour type asks for is taken leniently, not refused: a grey tRNS of fewer than 2
+ *      bytes and an RGB tRNS of fewer than 6 are ignored (no key), a palette tRNS is read up to 256 bytes and an empty one leaves
+ *      channels_in_file at 3 (Pillow refuses a 1-byte grey, a 4-byte RGB and, at 4 channels, a 257-byte palette tRNS; the tests
+ *      hold these three against the host twin of the kernels alone).  The file's last PLTE counts; a tRNS in front of it counts
+ *      as one behind it; a tRNS in a grey + alpha or RGBA file and a PLTE, of any length, in a file without palette are ignored.
  *      Status per file: FPNG_DECODE_FAILED_NOT_PNG / _HEADER_CRC32 / _INVALID_DIMENSIONS / _DIMENSIONS_TOO_LARGE for signature, IHDR
  *      and dimensions as in the fpng path (w, h <= 2^24, w * h <= 2^30, 32-bit file size);
  *      FPNG_AMD_DECODE_UNSUPPORTED_PNG for a valid PNG outside this tier: bit depth 1, 2, 4 or 16, Adam7 interlace, an unknown

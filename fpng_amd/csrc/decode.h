@@ -235,7 +235,7 @@ bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_
 // The same for fpng_amd_decode_batch(_device)_planar_views, whose records -- several per file -- mix sizes and plane counts: a grid
 // of exactly the records' workgroups.  pre (device) and h_pre (host, the same words): n + 1 entries, the workgroups (planes x tiles)
 // of the batch's records in front of each of recs[0 .. n]; split into launches of fewer than 2^24 workgroups.  false: a record
-// without or with too many workgroups, or lds_bytes out of range; nothing more is launched.  any_alpha: some record of the launch
+// without or with too many workgroups, or lds_bytes out of range; nothing is launched.  any_alpha: some record of the launch
 // carries an alpha op (view_alpha.h) -- the kernel's alpha instantiation, as filters (resize_launch_kind: 0 all bilinear, 1 some bicubic, 2 some RESAMPLE
 // filter) chooses among the one with the triangle alone, the one with both filters and the resample instantiation.
 bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,

@@ -192,7 +192,7 @@ FPNG_RESIZE_FN uint64_t enc_resize_scratch_bytes(uint64_t cursor) { return ((cur
 // entries, the TILES of the submission's records in front of each of recs[0 .. n].  lds_bytes: the most enc_resize_tile_lds() of the
 // records.  consts (device): the submission's constants (read for float sources and YUV surfaces only).  yuv: the records are
 // those of YUV frames (enc_resize_kernel<true>).  false: a record without or with too
-// many tiles, or lds_bytes above kEncResizeMaxLds; nothing more is launched.
+// many tiles, or lds_bytes above kEncResizeMaxLds; nothing is launched.
 bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const EncConsts *consts, bool yuv = false);
 
 } // namespace fpng_amd

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 
 #include "encode_resize.h"
+#include "exact_grid.h"
+#include "resize_tile.h"
 
 #include <algorithm>
 
@@ -32,24 +34,17 @@ namespace {
 template <bool kYuv> __global__ __launch_bounds__(kResizeBlock) void enc_resize_kernel(const EncResize *recs, const uint64_t *pre, uint32_t n, const EncConsts *__restrict__ consts_in)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t enc_resize_lds[];
-    const uint64_t g = pre[0] + blockIdx.x;
-    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(pre, n, blockIdx.x, g);
     const EncResize r = recs[lo];
     const EncConsts &consts = *consts_in;
     const uint32_t C = r.chans;
-    const uint32_t tile = (uint32_t)(g - pre[lo]);
+    const uint32_t tile = (uint32_t)exact_grid_within(pre, lo, g);
     if ((uint64_t)tile >= resize_tiles(r.w, r.h)) return; // (never, with the host's pre)
-    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW;
-    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
-    const uint32_t nq = std::min(kResizeTileH, r.h - oq0), nw = std::min(kResizeTileW, r.w - ox0);
-    int32_t *const Kx = (int32_t *)enc_resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
-    uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
-    uint8_t *const T = (uint8_t *)(cy + kResizeTileH), *const O = enc_resize_lds; // (O: once the passes are done, in the place of everything else)
+    uint32_t ox0, oq0, nw, nq;
+    resize_tile_at(tile, r.w, r.h, ox0, oq0, nw, nq);
+    FPNG_RESIZE_TILE_LDS(enc_resize_lds, r.taps_x, r.taps_y);
+    uint8_t *const O = enc_resize_lds; // (once the passes are done, in the place of everything else)
     const uint32_t tid = threadIdx.x;
     // ---- 1. the tile's weights: samples of the box (in_w x in_h) resized to w x h ----
     if (tid < kResizeTileW) {
@@ -124,14 +119,8 @@ template <bool kYuv> __global__ __launch_bounds__(kResizeBlock) void enc_resize_
     for (uint32_t q = wave; q < nq; q += kWaves) {
         const uint8_t *const Oq = O + q * o_stride;
         uint8_t *const D = r.dst + (uint64_t)(oq0 + q) * ((uint64_t)r.w * C) + (uint64_t)ox0 * C;
-        const uint32_t head = std::min(n_el, (0u - (uint32_t)(uintptr_t)D) & 3u);
-        const uint32_t nd = (n_el - head) / 4u, tail0 = head + nd * 4u;
-        if (o < head) D[o] = Oq[o];
-        for (uint32_t d = o; d < nd; d += kResizeTileW) {
-            const uint32_t e = head + d * 4u;
-            *(uint32_t *)(D + e) = Oq[e] | (uint32_t)Oq[e + 1] << 8 | (uint32_t)Oq[e + 2] << 16 | (uint32_t)Oq[e + 3] << 24;
-        }
-        if (tail0 + o < n_el) D[tail0 + o] = Oq[tail0 + o];
+        resize_tile_run<1>(D, n_el, o, [&](uint32_t e) { D[e] = Oq[e]; },
+                           [&](uint32_t e) { *(uint32_t *)(D + e) = Oq[e] | (uint32_t)Oq[e + 1] << 8 | (uint32_t)Oq[e + 2] << 16 | (uint32_t)Oq[e + 3] << 24; });
     }
 }
 
@@ -139,17 +128,10 @@ template <bool kYuv> __global__ __launch_bounds__(kResizeBlock) void enc_resize_
 
 bool launch_enc_resize(hipStream_t s, const EncResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const EncConsts *consts, bool yuv)
 {
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
     if (lds_bytes > kEncResizeMaxLds) return false;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
-        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(yuv ? enc_resize_kernel<true> : enc_resize_kernel<false>, dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, consts);
-        r0 = r1;
-    }
-    return true;
+    return exact_grid_walk(h_pre, n, kResizeBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) {
+        hipLaunchKernelGGL(yuv ? enc_resize_kernel<true> : enc_resize_kernel<false>, dim3(groups), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, consts);
+    });
 }
 
 } // namespace fpng_amd

@@ -20,9 +20,11 @@
 // largest tile of its files (resize_tile_lds): ~8 KB for a 1080p crop -> 224 x 224, 55 KB at the bilinear 32 x limit, 41 KB at the
 // bicubic 16 x limit.
 #include "decode.h"
+#include "exact_grid.h"
 #include "float_store.h"
 #include "resize.h"
 #include "resize_hwc.h"
+#include "resize_tile.h"
 #include "view_alpha.h"
 
 #include <hip/hip_runtime.h>
@@ -47,12 +49,9 @@ template <int kDtype, bool kAnyFilter, bool kAlpha = false, bool kResample = fal
 __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t plane, uint32_t tile, const DecFloat &flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
-    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW;
-    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
-    const uint32_t nq = std::min(kResizeTileH, r.h - oq0);
-    int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
-    uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
-    uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
+    uint32_t ox0, oq0, nw, nq;
+    resize_tile_at(tile, r.w, r.h, ox0, oq0, nw, nq);
+    FPNG_RESIZE_TILE_LDS(resize_lds, r.taps_x, r.taps_y);
     const uint32_t tid = threadIdx.x;
     [[maybe_unused]] const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
     // ---- 1. the tile's weights (first: relative to the view's box, which the host made of these samples' own first and count --
@@ -72,7 +71,7 @@ __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t pla
         fy[q] = first - r.box_y, cy[q] = count;
     }
     __syncthreads();
-    // ---- 2. the horizontal pass: source rows row0 .. row0 + nrows - 1 (first and first + count do not decrease with the sample) ----
+    // ---- 2. the horizontal pass ----
     const uint32_t row0 = fy[0];
     const uint32_t nrows = std::min(fy[nq - 1] + cy[nq - 1] - row0, r.rows); // (the host's bound holds: T has r.rows rows)
     const uint32_t o = tid % kResizeTileW, wave = tid / kResizeTileW;
@@ -93,27 +92,18 @@ __device__ __forceinline__ void dec_resize_tile(const DecResize &r, uint32_t pla
     }
     __syncthreads();
     // ---- 3. the vertical pass, the mirror, the element ----
-    if (ox0 + o >= r.w) return;
+    if (ox0 + o >= r.w) return; // (o >= nw, in the spelling this kernel was compiled with: the other one moves its instructions)
     const uint32_t col = r.flags & kResizeMirror ? r.w - 1 - (ox0 + o) : ox0 + o;
     constexpr uint32_t kElem = kDtype < 0 ? 1u : dec_float_bytes((uint32_t)kDtype);
-    // (c is the FILE's channel: plane b of the record is channel b, whatever the planes' order in memory -- a select, not an index
-    //  into the argument, which would put it into private memory)
-    const float sc = plane == 0 ? flt.scale[0] : plane == 1 ? flt.scale[1] : plane == 2 ? flt.scale[2] : flt.scale[3];
-    const float bi = plane == 0 ? flt.bias[0] : plane == 1 ? flt.bias[1] : plane == 2 ? flt.bias[2] : flt.bias[3];
+    float sc, bi; // (plane b of the record is the FILE's channel b, whatever the planes' order in memory)
+    float_scale_bias(flt, plane, sc, bi);
     uint8_t *const D = r.dst + (int64_t)plane * r.plane_pitch + (int64_t)col * kElem;
     for (uint32_t q = wave; q < nq; q += kResizeBlock / kResizeTileW) {
         const uint32_t first = fy[q] - row0;
         const uint32_t count = first < nrows ? std::min(cy[q], nrows - first) : 0u;
         int32_t sum = 1 << (kResizeBits - 1);
         for (uint32_t t = 0; t < count; t++) sum += (int32_t)T[(first + t) * kResizeTileW + o] * Ky[t * kResizeTileH + q];
-        const uint32_t v = resize_clip8(sum);
-        uint8_t *p = D + (int64_t)(oq0 + q) * r.pitch;
-        if constexpr (kDtype < 0) *p = (uint8_t)v;
-        else {
-            const float f = __builtin_fmaf((float)v, sc, bi);
-            if constexpr (kDtype == 0) *(f32_a *)p = f;
-            else *(u16_a *)p = half_bits<kDtype>(f);
-        }
+        elem_store<kDtype>(D + (int64_t)(oq0 + q) * r.pitch, byte_elem_bits<kDtype>(resize_clip8(sum), sc, bi));
     }
 }
 
@@ -134,45 +124,33 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_kernel(const DecResiz
 template <int kDtype, bool kAnyFilter, bool kAlpha = false, bool kResample = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_exact_kernel(const DecResize *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
-    const uint64_t g = pre[0] + blockIdx.x;
-    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(pre, n, blockIdx.x, g);
     const DecResize r = recs[lo];
-    const uint32_t rel = (uint32_t)(g - pre[lo]), tiles = (uint32_t)resize_tiles(r.w, r.h); // (planes x tiles < 2^24: the host's rule)
+    const uint32_t rel = (uint32_t)exact_grid_within(pre, lo, g), tiles = (uint32_t)resize_tiles(r.w, r.h); // (planes x tiles < 2^24: the host's rule)
     const uint32_t plane = rel / tiles;
     if (plane >= r.planes) return; // (never, with the host's pre)
     dec_resize_tile<kDtype, kAnyFilter, kAlpha, kResample>(r, plane, rel - plane * tiles, flt);
 }
+
+// The exact-grid launchers' instantiations by index: alpha (0 / 1), the launch's kind of filters (resize.h: triangle alone, both
+// filters, resample), element (0: bytes, 1 + dtype).  kAnyFilter is the kind >= 1, kResample the kind == 2.
+constexpr uint32_t exact_index(uint32_t alpha, uint32_t kind, uint32_t elem) { return (alpha * kResizeLaunchKinds + kind) * (kDecFloatTypes + 1) + elem; }
+template <uint32_t I> struct ExactAt {
+    static constexpr uint32_t kKind = I / (kDecFloatTypes + 1) % kResizeLaunchKinds;
+    static constexpr auto value = dec_resize_exact_kernel<(int)(I % (kDecFloatTypes + 1)) - 1, kKind >= 1, I / (kDecFloatTypes + 1) / kResizeLaunchKinds != 0, kKind == 2>;
+};
 
 } // namespace
 
 bool launch_dec_resize_exact(hipStream_t s, const DecResize *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                              bool any_alpha)
 {
-    using Kernel = void (*)(const DecResize *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][kResizeLaunchKinds][kDecFloatTypes + 1] = {
-        {{dec_resize_exact_kernel<-1, false>, dec_resize_exact_kernel<0, false>, dec_resize_exact_kernel<1, false>, dec_resize_exact_kernel<2, false>},
-         {dec_resize_exact_kernel<-1, true>, dec_resize_exact_kernel<0, true>, dec_resize_exact_kernel<1, true>, dec_resize_exact_kernel<2, true>},
-         {dec_resize_exact_kernel<-1, true, false, true>, dec_resize_exact_kernel<0, true, false, true>, dec_resize_exact_kernel<1, true, false, true>, dec_resize_exact_kernel<2, true, false, true>}},
-        {{dec_resize_exact_kernel<-1, false, true>, dec_resize_exact_kernel<0, false, true>, dec_resize_exact_kernel<1, false, true>, dec_resize_exact_kernel<2, false, true>},
-         {dec_resize_exact_kernel<-1, true, true>, dec_resize_exact_kernel<0, true, true>, dec_resize_exact_kernel<1, true, true>, dec_resize_exact_kernel<2, true, true>},
-         {dec_resize_exact_kernel<-1, true, true, true>, dec_resize_exact_kernel<0, true, true, true>, dec_resize_exact_kernel<1, true, true, true>, dec_resize_exact_kernel<2, true, true, true>}}};
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups, far below the 2^31 a grid's dimension allows)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
+    static constexpr auto kernels = exact_grid_table<ExactAt, exact_index(1, kResizeLaunchKinds - 1, kDecFloatTypes) + 1>();
     if (lds_bytes > 65536u || filters >= kResizeLaunchKinds) return false;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
-        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_alpha][filters][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
-                           r1 - r0, flt ? *flt : DecFloat{});
-        r0 = r1;
-    }
-    return true;
+    return exact_grid_walk(h_pre, n, kResizeBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) {
+        hipLaunchKernelGGL(kernels[exact_index(any_alpha, filters, flt ? flt->dtype + 1 : 0)], dim3(groups), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+    });
 }
 
 bool launch_dec_resize(hipStream_t s, const DecResize *recs, uint32_t n, uint32_t max_tiles, uint32_t lds_bytes, const DecFloat *flt, bool any_filter)
@@ -214,23 +192,16 @@ template <int kDtype, bool kAnyFilter, bool kAlpha = false, bool kResample = fal
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecResizeHwc *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
-    const uint64_t g = pre[0] + blockIdx.x;
-    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(pre, n, blockIdx.x, g);
     const DecResize r = recs[lo].r;
     const uint32_t P = recs[lo].pixel_elems, reversed = recs[lo].hwc_flags & kHwcReversed, C = r.planes;
-    const uint32_t tile = (uint32_t)(g - pre[lo]);
+    const uint32_t tile = (uint32_t)exact_grid_within(pre, lo, g);
     if ((uint64_t)tile >= resize_tiles(r.w, r.h)) return; // (never, with the host's pre)
-    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW;
-    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
-    const uint32_t nq = std::min(kResizeTileH, r.h - oq0), nw = std::min(kResizeTileW, r.w - ox0);
-    int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
-    uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
-    uint8_t *const T = (uint8_t *)(cy + kResizeTileH), *const O = resize_lds; // (O: once the passes are done, in the place of everything else)
+    uint32_t ox0, oq0, nw, nq;
+    resize_tile_at(tile, r.w, r.h, ox0, oq0, nw, nq);
+    FPNG_RESIZE_TILE_LDS(resize_lds, r.taps_x, r.taps_y);
+    uint8_t *const O = resize_lds; // (once the passes are done, in the place of everything else)
     const uint32_t tid = threadIdx.x;
     [[maybe_unused]] const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
     // ---- 1. the tile's weights ----
@@ -320,24 +291,11 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
         auto bits = [&](uint32_t e) -> uint32_t {
             const uint32_t i = P == 4 ? e >> 2 : e / 3u, k = e - i * P; // (P is 3 or 4)
             const uint32_t c = reversed ? C - 1 - k : k;              // the FILE's channel
-            const uint32_t v = Oq[(mirror ? nw - 1 - i : i) * C + c];
-            if constexpr (kDtype < 0) return v;
-            else {
-                // (a select, not an index into the argument, which would put it into private memory)
-                const float sc = c == 0 ? flt.scale[0] : c == 1 ? flt.scale[1] : c == 2 ? flt.scale[2] : flt.scale[3];
-                const float bi = c == 0 ? flt.bias[0] : c == 1 ? flt.bias[1] : c == 2 ? flt.bias[2] : flt.bias[3];
-                const float f = __builtin_fmaf((float)v, sc, bi);
-                if constexpr (kDtype == 0) return __builtin_bit_cast(uint32_t, f);
-                else return half_bits<kDtype>(f);
-            }
+            float sc, bi;
+            float_scale_bias(flt, c, sc, bi);
+            return byte_elem_bits<kDtype>(Oq[(mirror ? nw - 1 - i : i) * C + c], sc, bi);
         };
-        auto store1 = [&](uint32_t e) {
-            uint8_t *p = D + (size_t)e * kElem;
-            const uint32_t b = bits(e);
-            if constexpr (kDtype < 0) *p = (uint8_t)b;
-            else if constexpr (kDtype == 0) *(f32_a *)p = __builtin_bit_cast(float, b);
-            else *(u16_a *)p = (uint16_t)b;
-        };
+        auto store1 = [&](uint32_t e) { elem_store<kDtype>(D + (size_t)e * kElem, bits(e)); };
         if (kElem == 4 || P != C) {
             for (uint32_t e = o; e < n_el; e += kResizeTileW)
                 if (P == C || (e & 3u) < C) store1(e); // (P == 4: position e % 4; 3 is the caller's)
@@ -358,31 +316,21 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_hwc_kernel(const DecR
     }
 }
 
+template <uint32_t I> struct HwcAt { // (exact_index)
+    static constexpr uint32_t kKind = I / (kDecFloatTypes + 1) % kResizeLaunchKinds;
+    static constexpr auto value = dec_resize_hwc_kernel<(int)(I % (kDecFloatTypes + 1)) - 1, kKind >= 1, I / (kDecFloatTypes + 1) / kResizeLaunchKinds != 0, kKind == 2>;
+};
+
 } // namespace
 
 bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                            bool any_alpha)
 {
-    using Kernel = void (*)(const DecResizeHwc *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][kResizeLaunchKinds][kDecFloatTypes + 1] = {
-        {{dec_resize_hwc_kernel<-1, false>, dec_resize_hwc_kernel<0, false>, dec_resize_hwc_kernel<1, false>, dec_resize_hwc_kernel<2, false>},
-         {dec_resize_hwc_kernel<-1, true>, dec_resize_hwc_kernel<0, true>, dec_resize_hwc_kernel<1, true>, dec_resize_hwc_kernel<2, true>},
-         {dec_resize_hwc_kernel<-1, true, false, true>, dec_resize_hwc_kernel<0, true, false, true>, dec_resize_hwc_kernel<1, true, false, true>, dec_resize_hwc_kernel<2, true, false, true>}},
-        {{dec_resize_hwc_kernel<-1, false, true>, dec_resize_hwc_kernel<0, false, true>, dec_resize_hwc_kernel<1, false, true>, dec_resize_hwc_kernel<2, false, true>},
-         {dec_resize_hwc_kernel<-1, true, true>, dec_resize_hwc_kernel<0, true, true>, dec_resize_hwc_kernel<1, true, true>, dec_resize_hwc_kernel<2, true, true>},
-         {dec_resize_hwc_kernel<-1, true, true, true>, dec_resize_hwc_kernel<0, true, true, true>, dec_resize_hwc_kernel<1, true, true, true>, dec_resize_hwc_kernel<2, true, true, true>}}};
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
+    static constexpr auto kernels = exact_grid_table<HwcAt, exact_index(1, kResizeLaunchKinds - 1, kDecFloatTypes) + 1>();
     if (lds_bytes > 65536u || filters >= kResizeLaunchKinds) return false;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
-        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_alpha][filters][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0,
-                           r1 - r0, flt ? *flt : DecFloat{});
-        r0 = r1;
-    }
-    return true;
+    return exact_grid_walk(h_pre, n, kResizeBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) {
+        hipLaunchKernelGGL(kernels[exact_index(any_alpha, filters, flt ? flt->dtype + 1 : 0)], dim3(groups), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+    });
 }
 
 } // namespace fpng_amd

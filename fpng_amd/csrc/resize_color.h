@@ -49,7 +49,7 @@ static_assert(sizeof(DecResizeColor) == 168 && offsetof(DecResizeColor, d) == 0 
 
 // An exact grid as launch_dec_resize_hwc's, a workgroup per (record, tile): pre / h_pre count TILES.  hwc: channels-last
 // destinations (lds_bytes: the most resize_hwc_tile_lds() of the launch's records), else planar ones (the most resize_tile_lds()).
-// false: a record without or with too many tiles, or lds_bytes out of range; nothing more is launched.  any_alpha: some record of
+// false: a record without or with too many tiles, or lds_bytes out of range; nothing is launched.  any_alpha: some record of
 // the launch carries an alpha op (view_alpha.h): the kernel's alpha instantiation.
 bool launch_dec_resize_color(hipStream_t s, const DecResizeColor *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                              bool hwc, bool any_alpha = false);

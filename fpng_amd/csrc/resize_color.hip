@@ -20,10 +20,12 @@
 // kAlpha (view_alpha.h): the load of step 2 makes P'; a PREMULTIPLIED view runs the passes for all
 // FOUR planes, whatever the destination's count, and divides the three colour bytes by R'_3 in front of the matrix.
 #include "decode.h"
+#include "exact_grid.h"
 #include "float_store.h"
 #include "resize.h"
 #include "resize_color.h"
 #include "resize_hwc.h"
+#include "resize_tile.h"
 #include "view_alpha.h"
 
 #include <hip/hip_runtime.h>
@@ -34,46 +36,20 @@ namespace fpng_amd {
 
 namespace {
 
-// u (0 .. 255, or the alpha byte as a float) of FILE channel c -> the bits of the destination's element
-template <int kDtype> __device__ __forceinline__ uint32_t color_elem_bits(float u, float sc, float bi)
-{
-    if constexpr (kDtype < 0) return (uint32_t)__builtin_rintf(u); // (0 .. 255: ties to even)
-    else {
-        const float f = __builtin_fmaf(u, sc, bi);
-        if constexpr (kDtype == 0) return __builtin_bit_cast(uint32_t, f);
-        else return half_bits<kDtype>(f);
-    }
-}
-
-template <int kDtype> __device__ __forceinline__ void color_store(uint8_t *p, uint32_t b)
-{
-    if constexpr (kDtype < 0) *p = (uint8_t)b;
-    else if constexpr (kDtype == 0) *(f32_a *)p = __builtin_bit_cast(float, b);
-    else *(u16_a *)p = (uint16_t)b;
-}
-
 // kResample: as dec_resize_tile's (resize.hip)
 template <int kDtype, bool kAnyFilter, bool kHwc, bool kAlpha = false, bool kResample = false>
 __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const DecResizeColor *recs, const uint64_t *pre, uint32_t n, DecFloat flt)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t resize_lds[];
-    const uint64_t g = pre[0] + blockIdx.x;
-    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(pre, n, blockIdx.x, g);
     const DecResize r = recs[lo].d.r;
     const uint32_t C = r.planes;
-    const uint32_t tile = (uint32_t)(g - pre[lo]);
+    const uint32_t tile = (uint32_t)exact_grid_within(pre, lo, g);
     if ((uint64_t)tile >= resize_tiles(r.w, r.h)) return; // (never, with the host's pre)
-    const uint32_t tiles_x = (r.w + kResizeTileW - 1) / kResizeTileW;
-    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
-    const uint32_t nq = std::min(kResizeTileH, r.h - oq0), nw = std::min(kResizeTileW, r.w - ox0);
-    int32_t *const Kx = (int32_t *)resize_lds, *const Ky = Kx + r.taps_x * kResizeTileW;
-    uint32_t *const fx = (uint32_t *)(Ky + r.taps_y * kResizeTileH), *const cx = fx + kResizeTileW, *const fy = cx + kResizeTileW, *const cy = fy + kResizeTileH;
-    uint8_t *const T = (uint8_t *)(cy + kResizeTileH);
+    uint32_t ox0, oq0, nw, nq;
+    resize_tile_at(tile, r.w, r.h, ox0, oq0, nw, nq);
+    FPNG_RESIZE_TILE_LDS(resize_lds, r.taps_x, r.taps_y);
     const uint32_t tid = threadIdx.x;
     [[maybe_unused]] const uint32_t filter = kAnyFilter ? r.filter : kResizeBilinear;
     // ---- 1. the tile's weights ----
@@ -155,10 +131,10 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
             if (q >= nq) break;
             const float rr = (float)(res[k] & 255u), gg = (float)(res[k] >> 8 & 255u), bb = (float)(res[k] >> 16 & 255u), aa = (float)(res[k] >> 24);
             uint8_t *const p = D + (int64_t)(oq0 + q) * r.pitch;
-            color_store<kDtype>(p, color_elem_bits<kDtype>(color_apply(m00, m01, m02, m03, rr, gg, bb), flt.scale[0], flt.bias[0]));
-            color_store<kDtype>(p + r.plane_pitch, color_elem_bits<kDtype>(color_apply(m10, m11, m12, m13, rr, gg, bb), flt.scale[1], flt.bias[1]));
-            color_store<kDtype>(p + 2 * r.plane_pitch, color_elem_bits<kDtype>(color_apply(m20, m21, m22, m23, rr, gg, bb), flt.scale[2], flt.bias[2]));
-            if (C == 4) color_store<kDtype>(p + 3 * r.plane_pitch, color_elem_bits<kDtype>(aa, flt.scale[3], flt.bias[3]));
+            elem_store<kDtype>(p, float_elem_bits<kDtype>(color_apply(m00, m01, m02, m03, rr, gg, bb), flt.scale[0], flt.bias[0]));
+            elem_store<kDtype>(p + r.plane_pitch, float_elem_bits<kDtype>(color_apply(m10, m11, m12, m13, rr, gg, bb), flt.scale[1], flt.bias[1]));
+            elem_store<kDtype>(p + 2 * r.plane_pitch, float_elem_bits<kDtype>(color_apply(m20, m21, m22, m23, rr, gg, bb), flt.scale[2], flt.bias[2]));
+            if (C == 4) elem_store<kDtype>(p + 3 * r.plane_pitch, float_elem_bits<kDtype>(aa, flt.scale[3], flt.bias[3]));
         }
     } else {
         const uint32_t P = recs[lo].d.pixel_elems, reversed = recs[lo].d.hwc_flags & kHwcReversed;
@@ -184,10 +160,10 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
                 const float rr = (float)(res[k] & 255u), gg = (float)(res[k] >> 8 & 255u), bb = (float)(res[k] >> 16 & 255u), aa = (float)(res[k] >> 24);
                 uint8_t *const px = B + (size_t)i * C * kElem;
                 const uint32_t last = (C - 1) * kElem; // (reversed: file channel c is element C - 1 - c of its pixel)
-                color_store<kDtype>(px + (reversed ? last : 0u), color_elem_bits<kDtype>(color_apply(m00, m01, m02, m03, rr, gg, bb), flt.scale[0], flt.bias[0]));
-                color_store<kDtype>(px + (reversed ? last - kElem : kElem), color_elem_bits<kDtype>(color_apply(m10, m11, m12, m13, rr, gg, bb), flt.scale[1], flt.bias[1]));
-                color_store<kDtype>(px + (reversed ? last - 2 * kElem : 2 * kElem), color_elem_bits<kDtype>(color_apply(m20, m21, m22, m23, rr, gg, bb), flt.scale[2], flt.bias[2]));
-                if (C == 4) color_store<kDtype>(px + (reversed ? 0u : 3 * kElem), color_elem_bits<kDtype>(aa, flt.scale[3], flt.bias[3]));
+                elem_store<kDtype>(px + (reversed ? last : 0u), float_elem_bits<kDtype>(color_apply(m00, m01, m02, m03, rr, gg, bb), flt.scale[0], flt.bias[0]));
+                elem_store<kDtype>(px + (reversed ? last - kElem : kElem), float_elem_bits<kDtype>(color_apply(m10, m11, m12, m13, rr, gg, bb), flt.scale[1], flt.bias[1]));
+                elem_store<kDtype>(px + (reversed ? last - 2 * kElem : 2 * kElem), float_elem_bits<kDtype>(color_apply(m20, m21, m22, m23, rr, gg, bb), flt.scale[2], flt.bias[2]));
+                if (C == 4) elem_store<kDtype>(px + (reversed ? 0u : 3 * kElem), float_elem_bits<kDtype>(aa, flt.scale[3], flt.bias[3]));
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             auto copy1 = [&](uint32_t e, uint32_t at) __attribute__((always_inline)) { // element e of the run: element `at` of the buffer
@@ -201,52 +177,34 @@ __global__ __launch_bounds__(kResizeBlock) void dec_resize_color_kernel(const De
                     else if ((e & 3u) < C) copy1(e, (e >> 2) * C + (e & 3u)); // (P == 4: position e % 4; 3 is the caller's)
                 }
             } else {
-                constexpr uint32_t kPer = 4u / kElem; // elements per dword
-                const uint32_t head = std::min(n_el, (uint32_t)((0u - (uint32_t)(uintptr_t)D) & 3u) / kElem); // (D is a multiple of kElem)
-                const uint32_t nd = (n_el - head) / kPer, tail0 = head + nd * kPer;
-                if (o < head) copy1(o, o);
-                for (uint32_t d = o; d < nd; d += kResizeTileW) {
-                    const size_t at = (size_t)(head + d * kPer) * kElem;
+                resize_tile_run<kElem < 4 ? kElem : 1u>(D, n_el, o, [&](uint32_t e) { copy1(e, e); }, [&](uint32_t e) {
+                    const size_t at = (size_t)e * kElem;
                     *(uint32_t *)(D + at) = *(const uint32_t *)(B + at);
-                }
-                if (tail0 + o < n_el) copy1(tail0 + o, tail0 + o);
+                });
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // (the next row's elements go into the same buffer)
         }
     }
 }
 
+// The instantiations by index: alpha (0 / 1), channels-last (0 / 1), the launch's kind of filters (resize.h: triangle alone, both
+// filters, resample), element (0: bytes, 1 + dtype).  kAnyFilter is the kind >= 1, kResample the kind == 2.
+constexpr uint32_t color_index(uint32_t alpha, uint32_t hwc, uint32_t kind, uint32_t elem) { return ((alpha * 2 + hwc) * kResizeLaunchKinds + kind) * (kDecFloatTypes + 1) + elem; }
+template <uint32_t I> struct ColorAt {
+    static constexpr uint32_t kKind = I / (kDecFloatTypes + 1) % kResizeLaunchKinds, kForm = I / (kDecFloatTypes + 1) / kResizeLaunchKinds;
+    static constexpr auto value = dec_resize_color_kernel<(int)(I % (kDecFloatTypes + 1)) - 1, kKind >= 1, kForm % 2 != 0, kForm / 2 != 0, kKind == 2>;
+};
+
 } // namespace
 
 bool launch_dec_resize_color(hipStream_t s, const DecResizeColor *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                              bool hwc, bool any_alpha)
 {
-    using Kernel = void (*)(const DecResizeColor *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[2][2][kResizeLaunchKinds][kDecFloatTypes + 1] = {
-        {{{dec_resize_color_kernel<-1, false, false>, dec_resize_color_kernel<0, false, false>, dec_resize_color_kernel<1, false, false>, dec_resize_color_kernel<2, false, false>},
-          {dec_resize_color_kernel<-1, true, false>, dec_resize_color_kernel<0, true, false>, dec_resize_color_kernel<1, true, false>, dec_resize_color_kernel<2, true, false>},
-          {dec_resize_color_kernel<-1, true, false, false, true>, dec_resize_color_kernel<0, true, false, false, true>, dec_resize_color_kernel<1, true, false, false, true>, dec_resize_color_kernel<2, true, false, false, true>}},
-         {{dec_resize_color_kernel<-1, false, true>, dec_resize_color_kernel<0, false, true>, dec_resize_color_kernel<1, false, true>, dec_resize_color_kernel<2, false, true>},
-          {dec_resize_color_kernel<-1, true, true>, dec_resize_color_kernel<0, true, true>, dec_resize_color_kernel<1, true, true>, dec_resize_color_kernel<2, true, true>},
-          {dec_resize_color_kernel<-1, true, true, false, true>, dec_resize_color_kernel<0, true, true, false, true>, dec_resize_color_kernel<1, true, true, false, true>, dec_resize_color_kernel<2, true, true, false, true>}}},
-        {{{dec_resize_color_kernel<-1, false, false, true>, dec_resize_color_kernel<0, false, false, true>, dec_resize_color_kernel<1, false, false, true>, dec_resize_color_kernel<2, false, false, true>},
-          {dec_resize_color_kernel<-1, true, false, true>, dec_resize_color_kernel<0, true, false, true>, dec_resize_color_kernel<1, true, false, true>, dec_resize_color_kernel<2, true, false, true>},
-          {dec_resize_color_kernel<-1, true, false, true, true>, dec_resize_color_kernel<0, true, false, true, true>, dec_resize_color_kernel<1, true, false, true, true>, dec_resize_color_kernel<2, true, false, true, true>}},
-         {{dec_resize_color_kernel<-1, false, true, true>, dec_resize_color_kernel<0, false, true, true>, dec_resize_color_kernel<1, false, true, true>, dec_resize_color_kernel<2, false, true, true>},
-          {dec_resize_color_kernel<-1, true, true, true>, dec_resize_color_kernel<0, true, true, true>, dec_resize_color_kernel<1, true, true, true>, dec_resize_color_kernel<2, true, true, true>},
-          {dec_resize_color_kernel<-1, true, true, true, true>, dec_resize_color_kernel<0, true, true, true, true>, dec_resize_color_kernel<1, true, true, true, true>, dec_resize_color_kernel<2, true, true, true, true>}}}};
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
+    static constexpr auto kernels = exact_grid_table<ColorAt, color_index(1, 1, kResizeLaunchKinds - 1, kDecFloatTypes) + 1>();
     if (lds_bytes > 65536u || filters >= kResizeLaunchKinds) return false;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
-        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[any_alpha][hwc][filters][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0,
-                           flt ? *flt : DecFloat{});
-        r0 = r1;
-    }
-    return true;
+    return exact_grid_walk(h_pre, n, kResizeBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) {
+        hipLaunchKernelGGL(kernels[color_index(any_alpha, hwc, filters, flt ? flt->dtype + 1 : 0)], dim3(groups), dim3(kResizeBlock), lds_bytes, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+    });
 }
 
 } // namespace fpng_amd

@@ -30,7 +30,7 @@ FPNG_RESIZE_FN uint32_t resize_hwc_tile_lds(uint32_t taps_x, uint32_t taps_y, ui
 
 // An exact grid as launch_dec_resize_exact's, a workgroup per (record, tile): pre (device) and h_pre (host, the same words) hold n + 1
 // entries, the TILES of the batch's records in front of each of recs[0 .. n].  lds_bytes: the most resize_hwc_tile_lds() of the
-// launch's records.  false: a record without or with too many tiles, or lds_bytes out of range; nothing more is launched.
+// launch's records.  false: a record without or with too many tiles, or lds_bytes out of range; nothing is launched.
 // any_alpha: some record of the launch carries an alpha op (view_alpha.h): the kernel's alpha instantiation.
 bool launch_dec_resize_hwc(hipStream_t s, const DecResizeHwc *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t lds_bytes, const DecFloat *flt, uint32_t filters,
                            bool any_alpha = false);

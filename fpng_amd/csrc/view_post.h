@@ -16,6 +16,7 @@
 //   posterize: Z = S & (0xFF00 >> bits) & 0xFF            8 is the identity, 0 gives 0
 #pragma once
 #include "decode.h"
+#include "exact_grid.h"
 #include "resize.h"
 #include "view_enhance.h"
 #include "view_tone.h"
@@ -79,7 +80,7 @@ static_assert(sizeof(DecViewPost) == 264 && offsetof(DecViewPost, enhance_op) ==
 // An exact grid as launch_dec_resize_color's, a workgroup per (record, tile of kResizeTileW x kResizeTileH): pre / h_pre count TILES.
 // hwc: channels-last destinations.  mode 1: some record of the call has a warp (the instantiations that gather; 0: the post call's
 // own); mode 2: some record has a tone op (the instantiations that gather and apply a table); mode 3: some record has an enhance op
-// (those that also blend against a degenerate image).  false: a record without or with too many tiles; nothing more is launched.
+// (those that also blend against a degenerate image).  false: a record without or with too many tiles; nothing is launched.
 bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, int mode = 0);
 
 // The tone views of a call, in the order of their post records: refs[t].rec is tone view t's record of `recs`, refs[t].pre the chunks
@@ -89,12 +90,13 @@ struct DecToneRef {
     uint32_t rec, pad_;
 };
 static_assert(sizeof(DecToneRef) == 16, "DecToneRef layout");
+FPNG_GRID_FN uint64_t exact_grid_pre(const DecToneRef &e) { return e.pre; } // (exact_grid.h: the refs are their own pre[])
 // what one workgroup of dec_view_tone_hist_kernel counts: eight 64 x 16 tiles' worth of samples in all three planes -- 24576 (contrast:
 // 8192) LDS atomics against the at most 768 (256) global ones of its flush; a 224 x 224 view is seven workgroups
 constexpr uint32_t kToneChunk = 8 * kResizeTileW * kResizeTileH;
 inline uint64_t tone_chunks(uint32_t w, uint32_t h) { return ((uint64_t)w * h + kToneChunk - 1) / kToneChunk; }
 // refs .. refs + n (device; h_refs: the host's copy, n + 1 entries): the histograms -- zeroed on the stream by the caller -- and then
-// the tables of those tone views.  false: a view without or with too many chunks; nothing more is launched.
+// the tables of those tone views.  false: a view without or with too many chunks; nothing is launched.
 bool launch_dec_view_tone(hipStream_t s, const DecViewPost *recs, const DecToneRef *refs, const DecToneRef *h_refs, uint32_t n);
 
 } // namespace fpng_amd

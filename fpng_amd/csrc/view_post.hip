@@ -36,9 +36,11 @@
 // LDS reads of the passes are bytes at consecutive addresses along a wave's lanes: four lanes a bank, one address each -- no conflict.
 // The kernel is symmetric, so taps -d and d share one product: sum = 2^21 + s[0] k[0] + sum_d (s[-d] + s[d]) k[d] -- the same integer.
 #include "decode.h"
+#include "exact_grid.h"
 #include "float_store.h"
 #include "resize.h"
 #include "resize_hwc.h"
+#include "resize_tile.h"
 #include "view_post.h"
 
 #include <hip/hip_runtime.h>
@@ -50,17 +52,6 @@ namespace fpng_amd {
 namespace {
 
 constexpr uint32_t kPostHaloW = kResizeTileW + 2 * kPostMaxRadius, kPostHaloH = kResizeTileH + 2 * kPostMaxRadius; // 96 x 48
-
-// byte z of FILE channel c -> the destination's element, stored
-template <int kDtype> __device__ __forceinline__ void post_store(uint8_t *p, uint32_t z, float sc, float bi)
-{
-    if constexpr (kDtype < 0) *p = (uint8_t)z;
-    else {
-        const float f = __builtin_fmaf((float)z, sc, bi);
-        if constexpr (kDtype == 0) *(f32_a *)p = f;
-        else *(u16_a *)p = half_bits<kDtype>(f);
-    }
-}
 
 // kMode: 0 the post calls', 1 the warp calls' (gathers), 2 the tone calls' (gathers and applies a table), 3 the enhance calls' (gathers,
 // applies a table and blends against a degenerate image)
@@ -74,20 +65,14 @@ template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResize
     __shared__ __attribute__((aligned(16))) uint8_t S[(kWarp ? 3 : 1) * kHalo + (kTone ? kToneLutBytes : 0) + (kEnh ? kEHalo : 0)];
     __shared__ __attribute__((aligned(16))) uint8_t Hb[kPostHaloH * kResizeTileW]; // the horizontal pass: rows of kResizeTileW bytes
     __shared__ int32_t K[kPostMaxRadius + 1];                                   // k[d]: taps -d and d share it
-    const uint64_t g = pre[0] + blockIdx.x;
-    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(pre, n, blockIdx.x, g);
     const DecViewPost &r = recs[lo];
     const uint32_t w = r.w, h = r.h, C = r.planes, flags = r.flags;
-    const uint32_t tile = (uint32_t)(g - pre[lo]);
+    const uint32_t tile = (uint32_t)exact_grid_within(pre, lo, g);
     if ((uint64_t)tile >= resize_tiles(w, h)) return; // (never, with the host's pre)
-    const uint32_t tiles_x = (w + kResizeTileW - 1) / kResizeTileW;
-    const uint32_t ox0 = tile % tiles_x * kResizeTileW, oq0 = tile / tiles_x * kResizeTileH;
-    const uint32_t nq = std::min(kResizeTileH, h - oq0), nw = std::min(kResizeTileW, w - ox0);
+    uint32_t ox0, oq0, nw, nq;
+    resize_tile_at(tile, w, h, ox0, oq0, nw, nq);
     // (the host's records: 1 .. 16 with blur, and below w and h -- the bounds of S and of one reflection, held here too)
     const uint32_t R = (flags & kPostBlur) ? std::min(std::min(r.radius, kPostMaxRadius), std::min(w, h) - 1u) : 0u;
     const uint32_t tid = threadIdx.x, o = tid % kResizeTileW, wave = tid / kResizeTileW;
@@ -321,38 +306,28 @@ template <int kDtype, bool kHwc, int kMode> __global__ __launch_bounds__(kResize
         const uint32_t q = wave + k * kWaves;
         if (q >= nq) break;
         uint8_t *const p = r.dst + (int64_t)(oq0 + q) * r.pitch + first;
-        post_store<kDtype>(p + at[0], res[k] & 255u, flt.scale[0], flt.bias[0]);
-        post_store<kDtype>(p + at[1], res[k] >> 8 & 255u, flt.scale[1], flt.bias[1]);
-        post_store<kDtype>(p + at[2], res[k] >> 16 & 255u, flt.scale[2], flt.bias[2]);
-        if (C == 4) post_store<kDtype>(p + at[3], res[k] >> 24, flt.scale[3], flt.bias[3]);
+        elem_store<kDtype>(p + at[0], byte_elem_bits<kDtype>(res[k] & 255u, flt.scale[0], flt.bias[0]));
+        elem_store<kDtype>(p + at[1], byte_elem_bits<kDtype>(res[k] >> 8 & 255u, flt.scale[1], flt.bias[1]));
+        elem_store<kDtype>(p + at[2], byte_elem_bits<kDtype>(res[k] >> 16 & 255u, flt.scale[2], flt.bias[2]));
+        if (C == 4) elem_store<kDtype>(p + at[3], byte_elem_bits<kDtype>(res[k] >> 24, flt.scale[3], flt.bias[3]));
     }
 }
+
+// The instantiations by index: kMode (0 .. 3), channels-last (0 / 1), element (0: bytes, 1 + dtype)
+constexpr uint32_t post_index(uint32_t mode, uint32_t hwc, uint32_t elem) { return (mode * 2 + hwc) * (kDecFloatTypes + 1) + elem; }
+template <uint32_t I> struct PostAt {
+    static constexpr auto value = dec_view_post_kernel<(int)(I % (kDecFloatTypes + 1)) - 1, I / (kDecFloatTypes + 1) % 2 != 0, (int)(I / (kDecFloatTypes + 1) / 2)>;
+};
 
 } // namespace
 
 bool launch_dec_view_post(hipStream_t s, const DecViewPost *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, const DecFloat *flt, bool hwc, int mode)
 {
-    using Kernel = void (*)(const DecViewPost *, const uint64_t *, uint32_t, DecFloat);
-    static const Kernel kernels[4][2][kDecFloatTypes + 1] = {
-        {{dec_view_post_kernel<-1, false, 0>, dec_view_post_kernel<0, false, 0>, dec_view_post_kernel<1, false, 0>, dec_view_post_kernel<2, false, 0>},
-         {dec_view_post_kernel<-1, true, 0>, dec_view_post_kernel<0, true, 0>, dec_view_post_kernel<1, true, 0>, dec_view_post_kernel<2, true, 0>}},
-        {{dec_view_post_kernel<-1, false, 1>, dec_view_post_kernel<0, false, 1>, dec_view_post_kernel<1, false, 1>, dec_view_post_kernel<2, false, 1>},
-         {dec_view_post_kernel<-1, true, 1>, dec_view_post_kernel<0, true, 1>, dec_view_post_kernel<1, true, 1>, dec_view_post_kernel<2, true, 1>}},
-        {{dec_view_post_kernel<-1, false, 2>, dec_view_post_kernel<0, false, 2>, dec_view_post_kernel<1, false, 2>, dec_view_post_kernel<2, false, 2>},
-         {dec_view_post_kernel<-1, true, 2>, dec_view_post_kernel<0, true, 2>, dec_view_post_kernel<1, true, 2>, dec_view_post_kernel<2, true, 2>}},
-        {{dec_view_post_kernel<-1, false, 3>, dec_view_post_kernel<0, false, 3>, dec_view_post_kernel<1, false, 3>, dec_view_post_kernel<2, false, 3>},
-         {dec_view_post_kernel<-1, true, 3>, dec_view_post_kernel<0, true, 3>, dec_view_post_kernel<1, true, 3>, dec_view_post_kernel<2, true, 3>}}};
+    static constexpr auto kernels = exact_grid_table<PostAt, post_index(3, 1, kDecFloatTypes) + 1>();
     if (mode < 0 || mode > 3) return false;
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
-        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[mode][hwc][flt ? flt->dtype + 1 : 0], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
-        r0 = r1;
-    }
-    return true;
+    return exact_grid_walk(h_pre, n, kResizeBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) {
+        hipLaunchKernelGGL(kernels[post_index(mode, hwc, flt ? flt->dtype + 1 : 0)], dim3(groups), dim3(kResizeBlock), 0, s, recs + r0, pre + r0, r1 - r0, flt ? *flt : DecFloat{});
+    });
 }
 
 } // namespace fpng_amd

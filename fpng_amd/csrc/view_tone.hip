@@ -27,16 +27,11 @@ constexpr uint32_t kToneLutBlock = 256;
 __global__ __launch_bounds__(kResizeBlock) void dec_view_tone_hist_kernel(const DecViewPost *recs, const DecToneRef *refs, uint32_t n)
 {
     __shared__ uint32_t H[kToneHistWords];
-    const uint64_t g = refs[0].pre + blockIdx.x;
-    uint32_t lo = 0, hi = n; // refs[lo].pre <= g < refs[hi].pre
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (refs[mid].pre <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(refs, n, blockIdx.x, g); // (refs[].pre: exact_grid_pre of view_post.h)
     const DecViewPost &r = recs[refs[lo].rec];
     const uint32_t w = r.w, h = r.h, op = r.tone_op;
-    const uint64_t total = (uint64_t)w * h, first = (g - refs[lo].pre) * kToneChunk; // (total < 2^32: the host)
+    const uint64_t total = (uint64_t)w * h, first = exact_grid_within(refs, lo, g) * kToneChunk; // (total < 2^32: the host)
     if (!op || !r.tone || first >= total) return;                                    // (never, with the host's refs)
     const uint32_t tid = threadIdx.x;
     for (uint32_t k = tid; k < kToneHistWords; k += kResizeBlock) H[k] = 0;
@@ -119,15 +114,8 @@ __global__ __launch_bounds__(kToneLutBlock) void dec_view_tone_lut_kernel(const 
 
 bool launch_dec_view_tone(hipStream_t s, const DecViewPost *recs, const DecToneRef *refs, const DecToneRef *h_refs, uint32_t n)
 {
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kResizeBlock - 1;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_refs[r1].pre <= h_refs[r0].pre || h_refs[r1].pre - h_refs[r0].pre > kMaxGrid) return false;
-        while (r1 < n && h_refs[r1 + 1].pre > h_refs[r1].pre && h_refs[r1 + 1].pre - h_refs[r0].pre <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(dec_view_tone_hist_kernel, dim3((uint32_t)(h_refs[r1].pre - h_refs[r0].pre)), dim3(kResizeBlock), 0, s, recs, refs + r0, r1 - r0);
-        r0 = r1;
-    }
+    if (!exact_grid_walk(h_refs, n, kResizeBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) { hipLaunchKernelGGL(dec_view_tone_hist_kernel, dim3(groups), dim3(kResizeBlock), 0, s, recs, refs + r0, r1 - r0); }))
+        return false;
     if (n) hipLaunchKernelGGL(dec_view_tone_lut_kernel, dim3(n), dim3(kToneLutBlock), 0, s, recs, refs);
     return true;
 }

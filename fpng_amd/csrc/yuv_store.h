@@ -116,7 +116,7 @@ FPNG_QUANT_FN uint64_t yuv_store_blocks(uint32_t surface, uint32_t w, uint32_t h
 }
 
 // An exact grid over the launch's records: pre[k] (k = 0 .. n), h_pre its host copy: the workgroups of the batch's records in front
-// of record k.  false: a record without or with too many workgroups; nothing more is launched
+// of record k.  false: a record without or with too many workgroups; nothing is launched
 bool launch_dec_yuv_store(hipStream_t s, const DecYuvStore *recs, const uint64_t *pre, const uint64_t *h_pre, uint32_t n, uint32_t surface, const YuvMatrix &f, const YuvDepth &dp);
 
 } // namespace fpng_amd

@@ -21,6 +21,7 @@
 // 16-bit surfaces' lanes for the same pieces there.
 #include <hip/hip_runtime.h>
 
+#include "exact_grid.h"
 #include "yuv_store.h"
 
 namespace fpng_amd {
@@ -75,18 +76,13 @@ template <uint32_t S> __global__ __launch_bounds__(kYuvBlock) void dec_yuv_store
 {
     constexpr bool k420 = yuv_is_420(S);
     constexpr uint32_t kElem = yuv_elem_bytes(S);
-    const uint64_t g = pre[0] + blockIdx.x;
-    uint32_t lo = 0, hi = n; // pre[lo] <= g < pre[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    uint64_t g;
+    const uint32_t lo = exact_grid_find(pre, n, blockIdx.x, g);
     const DecYuvStore &r = recs[lo];
     const uint32_t w = r.w, h = r.h;
     const uint32_t strips = (w + kYuvStrip - 1) / kYuvStrip, rows = k420 ? (h + 1) / 2 : h;
     const uint32_t blocks_x = (strips + kYuvBlockX - 1) / kYuvBlockX;
-    const uint64_t rel = g - pre[lo];
+    const uint64_t rel = exact_grid_within(pre, lo, g);
     if (rel >= yuv_store_blocks(S, w, h)) return; // (never, with the host's pre)
     const uint32_t i = (uint32_t)(rel % blocks_x) * kYuvBlockX + threadIdx.x % kYuvBlockX;
     const uint32_t j = (uint32_t)(rel / blocks_x) * kYuvBlockY + threadIdx.x / kYuvBlockX;
@@ -158,16 +154,9 @@ bool launch_dec_yuv_store(hipStream_t s, const DecYuvStore *recs, const uint64_t
     using Kernel = void (*)(const DecYuvStore *, const uint64_t *, uint32_t, YuvMatrix, YuvDepth);
     static const Kernel kernels[kYuvSurfaces] = {dec_yuv_store_kernel<kYuvNV12>, dec_yuv_store_kernel<kYuvP016>, dec_yuv_store_kernel<kYuv444>, dec_yuv_store_kernel<kYuv444_16>};
     if (surface >= (uint32_t)kYuvSurfaces) return false;
-    // (a launch holds fewer than 2^32 threads: fewer than 2^24 workgroups)
-    constexpr uint64_t kMaxGrid = (1ull << 32) / kYuvBlock - 1;
-    for (uint32_t r0 = 0; r0 < n;) {
-        uint32_t r1 = r0 + 1;
-        if (h_pre[r1] <= h_pre[r0] || h_pre[r1] - h_pre[r0] > kMaxGrid) return false;
-        while (r1 < n && h_pre[r1 + 1] > h_pre[r1] && h_pre[r1 + 1] - h_pre[r0] <= kMaxGrid) r1++;
-        hipLaunchKernelGGL(kernels[surface], dim3((uint32_t)(h_pre[r1] - h_pre[r0])), dim3(kYuvBlock), 0, s, recs + r0, pre + r0, r1 - r0, f, dp);
-        r0 = r1;
-    }
-    return true;
+    return exact_grid_walk(h_pre, n, kYuvBlock, [&](uint32_t r0, uint32_t r1, uint32_t groups) {
+        hipLaunchKernelGGL(kernels[surface], dim3(groups), dim3(kYuvBlock), 0, s, recs + r0, pre + r0, r1 - r0, f, dp);
+    });
 }
 
 } // namespace fpng_amd

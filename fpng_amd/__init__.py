@@ -31,6 +31,7 @@ from .api import (FPNG_ADLER32_INIT, FPNG_CRC32_INIT, FPNG_ENCODE_SLOWER, FPNG_F
                   VERIFY_CRC32, VERIFY_ADLER32, DECODE_BAD_CRC32, DECODE_BAD_ADLER32,
                   DECODE_CROP_OUTSIDE, DecodeBatchCrop, crop_tiles,
                   FPNG_AMD_DECODE_UNSUPPORTED_PNG, FPNG_AMD_PNG_GENERAL_ONLY, DecodeBatchPng,
+                  FPNG_AMD_DECODE_PNG_CROP_OUTSIDE, DecodeBatchPngViews, DecodeBatchPngViewsHwc, png_views_entry,
                   RESIZE_MIRROR, DecodeBatchResize, resize_weights,
                   FILTER_BILINEAR, FILTER_BICUBIC, DecodeBatchResizeView, resize_view_source, center_crop_view,
                   DecodeBatchMultiView, views_source, dest_layout_hwc, DecodeBatchMultiViewHwc,

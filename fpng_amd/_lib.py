@@ -353,7 +353,23 @@ for _layout, _dest in VIEW_LAYOUTS:
 for _device in (False, True):
     SIGNATURES[views_symbol("yuv", _device, 0)] = (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(_u32), C.POINTER(Crop), C.POINTER(ResizeView), C.POINTER(YuvDest),
                                                           C.POINTER(YuvStoreFormat), C.POINTER(DecodeResult)])
-SIGNATURES["fpng_amd_yuv_matrix_from_rgb"] = (_int, [_u32, _int, C.POINTER(C.c_float)])
+
+# fpng_amd_decode_batch(_device)_png_views: views of ordinary PNG files, every family through one request record
+DECODE_PNG_CROP_OUTSIDE = 68  # FPNG_AMD_DECODE_PNG_CROP_OUTSIDE: a file's status when a crop of it leaves the image (67 there: UNSUPPORTED_PNG)
+
+
+class PngViews(C.Structure):  # fpng_amd_png_views: 112 bytes
+    _fields_ = [("view_count", C.POINTER(_u32)), ("crops", C.POINTER(Crop)), ("views", C.POINTER(ResizeView)), ("dests", C.POINTER(ViewDest)), ("hwc", C.POINTER(ViewDestHwc)),
+                ("fmt", C.POINTER(FloatFormat))] + [(name[1:] + "s", C.POINTER(rec)) for name, rec in VIEW_STAGES] + [("flags", _u32), ("reserved", _u32)]
+
+
+def png_views_symbol(device_data):
+    return f"fpng_amd_decode_batch{'_device' if device_data else ''}_png_views"
+
+
+for _device in (False, True):
+    SIGNATURES[png_views_symbol(_device)] = (_int, [_vp, C.POINTER(PngPlanarIn), _u32, C.POINTER(PngViews), C.POINTER(DecodeResult)])
+SIGNATURES["fpng_amd_yuv_matrix_from_rgb"] =(_int, [_u32, _int, C.POINTER(C.c_float)])
 SIGNATURES["fpng_amd_yuv_surface"] = (_int, [_vp, _u32, _u32, C.POINTER(YuvStoreFormat), C.POINTER(YuvDest)])
 
 _lib = None

@@ -37,6 +37,7 @@ DECODE_BAD_CRC32, DECODE_BAD_ADLER32 = 65, 66
 DECODE_CROP_OUTSIDE = _lib.DECODE_CROP_OUTSIDE
 FPNG_AMD_DECODE_UNSUPPORTED_PNG = _lib.DECODE_UNSUPPORTED_PNG  # decode_device_png / decode_batch_png: a valid PNG the general tier does not decode
 FPNG_AMD_PNG_GENERAL_ONLY = _lib.PNG_GENERAL_ONLY  # ... flags: every file through the general tier, fpng-written ones too
+FPNG_AMD_DECODE_PNG_CROP_OUTSIDE = _lib.DECODE_PNG_CROP_OUTSIDE  # decode_device_png_views / decode_batch_png_views: a crop of the file leaves the image
 # fpng_amd_resize.flags (Encoder.decode_device_resize: mirror=True sets it): the output's columns in reverse order
 RESIZE_MIRROR = _lib.RESIZE_MIRROR
 # fpng_amd_resize_view.filter (Encoder.decode_device_resize_view: filter="bilinear" / "bicubic")
@@ -1587,6 +1588,19 @@ class DecodeBatchMultiViewHwc(_DecodeBatchMultiViews):
     maker = "make_decode_batch_views_hwc"
 
 
+class DecodeBatchPngViews(_DecodeBatchMultiViews):
+    """What Encoder.make_decode_batch_png_views() returns for layout="planar": DecodeBatchMultiView's descriptor for ORDINARY PNG
+    files and one fpng_amd_decode_batch(_device)_png_views() call (flags: the call's, FPNG_AMD_PNG_GENERAL_ONLY).  No other call
+    takes this descriptor."""
+
+    maker = "make_decode_batch_png_views"
+    flags = 0
+
+
+class DecodeBatchPngViewsHwc(DecodeBatchPngViews):
+    """... and for layout="hwc": DecodeBatchMultiViewHwc's twin (dests: the fpng_amd_view_dest_hwc records)."""
+
+
 def _planar_view_dest(rec, t, order, bottom_up, is_u8):
     """the fpng_amd_view_dest of a (c, h, w) view; -> the float format's dtype code, or None"""
     if is_u8:
@@ -1733,6 +1747,10 @@ _PLANAR_VIEWS = _ViewsLayout("planar", _lib.ViewDest, DecodeBatchMultiView, _pla
 _HWC_VIEWS = _ViewsLayout("hwc", _lib.ViewDestHwc, DecodeBatchMultiViewHwc, _hwc_view_dest, lambda s: (s[2], s[0], s[1]), lambda oh, ow: (oh, ow, 3))
 
 
+_PNG_VIEWS = {"planar": _ViewsLayout("planar", _lib.ViewDest, DecodeBatchPngViews, _planar_view_dest, _PLANAR_VIEWS.chw, _PLANAR_VIEWS.empty_shape),
+              "hwc": _ViewsLayout("hwc", _lib.ViewDestHwc, DecodeBatchPngViewsHwc, _hwc_view_dest, _HWC_VIEWS.chw, _HWC_VIEWS.empty_shape)}
+
+
 def _per_file(who, n, v, what):
     """an argument of a per-file call -> a list with a value per file.  v: one value (_VIEW_ARG has what one looks like) for all
     files, or a sequence with one per file"""
@@ -1866,6 +1884,23 @@ def views_entry(layout, device_data, batch):
     arrays = [getattr(batch, attr) for _, attr, _, _ in _VIEW_STAGES]
     stages = max((k + 1 for k, a in enumerate(arrays) if a is not None), default=0)
     return _lib.views_symbol(layout, device_data, stages), [batch.arr, len(batch.arr), batch.counts, batch.crops, batch.views, batch.dests, *arrays[:stages], _fmt_ref(batch), batch.res]
+
+
+def png_views_entry(layout, device_data, batch, flags):
+    """The C entry point of a PNG views call and its arguments behind the encoder, as a pure function of the layout ("planar" /
+    "hwc"), where the files are, the descriptor and the call's flags: fpng_amd_decode_batch(_device)_png_views takes every family
+    through one fpng_amd_png_views record -- the destinations in `dests` or in `hwc`, the stage arrays the descriptor carries (NULL
+    for those not given; the last one given names the family the request is judged as)."""
+    rq = _lib.PngViews()
+    rq.view_count, rq.crops, rq.views = batch.counts, batch.crops, batch.views
+    setattr(rq, "hwc" if layout == "hwc" else "dests", batch.dests)
+    if batch.fmt is not None:
+        rq.fmt = C.pointer(batch.fmt)
+    for _, attr, _, _ in _VIEW_STAGES:
+        if getattr(batch, attr) is not None:
+            setattr(rq, attr, getattr(batch, attr))
+    rq.flags, rq.reserved = int(flags), 0
+    return _lib.png_views_symbol(device_data), [batch.arr, len(batch.arr), C.byref(rq), batch.res]
 
 
 class Encoder:
@@ -2802,6 +2837,68 @@ class Encoder:
         """fpng_amd_decode_batch_hwc_views: decode_device_views_hwc() for files in host memory (bytes)."""
         return self._decode_views(_HWC_VIEWS, False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
                                   dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
+
+    @staticmethod
+    def make_decode_batch_png_views(pngs, crops, outs, full, window=None, filter="bilinear", mirror=False, order="rgb", bottom_up=False, mean=None, std=None,
+                                    scale=None, bias=None, color=None, post=None, warp=None, tone=None, enhance=None, alpha=None, resample=None, layout="planar", flags=0):
+        """Descriptor for decode_device_png_views() / decode_batch_png_views(): make_decode_batch_views() (layout="planar": (c, h, w)
+        destinations) or make_decode_batch_views_hwc() (layout="hwc": (h, w, c) ones) for ORDINARY PNG files -- the same nesting of
+        crops and outs, the same constants and the same stage keywords; flags: the call's (FPNG_AMD_PNG_GENERAL_ONLY)."""
+        if layout not in _PNG_VIEWS:
+            raise ValueError(f"make_decode_batch_png_views: layout {layout!r} (\"planar\" or \"hwc\")")
+        batch = _make_views_batch(_PNG_VIEWS[layout], pngs, crops, outs, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias,
+                                  dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample))
+        batch.flags = int(flags)
+        return batch
+
+    def _decode_png_views(self, device_data, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results, stages, layout, flags):
+        if isinstance(pngs, DecodeBatchPngViews):  # (a descriptor knows its layout and carries its flags)
+            layout, flags = ("hwc" if isinstance(pngs, DecodeBatchPngViewsHwc) else "planar"), pngs.flags
+        if layout not in _PNG_VIEWS:
+            raise ValueError(f"{DecodeBatchPngViews.call(device_data)}: layout {layout!r} (\"planar\" or \"hwc\")")
+        lay = _PNG_VIEWS[layout]
+        if isinstance(pngs, lay.batch_cls) and any(v is not None for v in stages.values()):
+            raise ValueError(f"{lay.batch_cls.call(device_data)}: a descriptor carries its own records of the stages {', '.join(k for k, _, _, _ in _VIEW_STAGES)}")
+
+        def make(who):
+            dests = outs
+            if crops is None or full is None:
+                raise ValueError(f"{who}: crops, a list of (x, y, w, h) per file, and full, the (full_w, full_h) they are resized to")
+            if outs is None or any(o is None for o in outs):  # (each window's size with c = 3; files with alpha lose it)
+                where = dict(dtype=_alloc_dtype(who, dtype), device=f"cuda:{self.device}")
+                counts = [len(c) for c in crops]
+                fulls, windows = _per_view(who, counts, full, "full sizes"), _per_view(who, counts, window, "windows")
+                dests = [[torch.empty(lay.empty_shape(*_window_hw(f_, w_)), **where) for f_, w_ in zip(fulls[i], windows[i])] if outs is None or outs[i] is None else outs[i]
+                         for i in range(len(crops))]
+            batch = _make_views_batch(lay, pngs, crops, dests, full, window, filter, mirror, order, bottom_up, mean, std, scale, bias, stages)
+            batch.flags = int(flags)
+            return batch
+
+        return self._run_decode(lay.batch_cls, device_data, pngs, make, lambda b: png_views_entry(layout, device_data, b, b.flags), results)
+
+    def decode_device_png_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                                bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None,
+                                alpha=None, resample=None, layout="planar", flags=0):
+        """fpng_amd_decode_batch_device_png_views: decode_device_views() (layout="planar") or decode_device_views_hwc()
+        (layout="hwc") for ORDINARY PNG files -- what libpng, Pillow or zlib write: 8-bit grey, grey + alpha, RGB, palette, RGBA, not
+        interlaced -- in uint8 CUDA tensors.  Every argument is the views call's, every stage keyword included; a view holds exactly
+        what that call writes for an fpng-written file with the same pixels.  A file has an alpha plane, which the alpha records act
+        on and a 4-channel destination gets, when decode_device_png() at 4 channels can give it an alpha below 255 (grey + alpha,
+        RGBA, palette with tRNS, grey or RGB with a colour key); another file's fourth plane is 255.  Files with fpng's marker go
+        through the fpng tier's views path unless flags has FPNG_AMD_PNG_GENERAL_ONLY.  -> list, per file, of (status, the list of
+        the caller's views or None, channels_in_file): the statuses of decode_device_png(), a bad filter byte or palette index
+        counting only where the file's one source box (views_source()) makes the decoder look, and
+        FPNG_AMD_DECODE_PNG_CROP_OUTSIDE (68) for a crop that leaves the image -- 67 is FPNG_AMD_DECODE_UNSUPPORTED_PNG here.
+        pngs may be a make_decode_batch_png_views() descriptor of device files; results=False returns it."""
+        return self._decode_png_views(True, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                                      dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample), layout, flags)
+
+    def decode_batch_png_views(self, pngs, crops=None, outs=None, full=None, window=None, filter="bilinear", mirror=False, dtype=torch.uint8, order="rgb",
+                               bottom_up=False, mean=None, std=None, scale=None, bias=None, results=True, color=None, post=None, warp=None, tone=None, enhance=None,
+                               alpha=None, resample=None, layout="planar", flags=0):
+        """fpng_amd_decode_batch_png_views: decode_device_png_views() for files in host memory (bytes)."""
+        return self._decode_png_views(False, pngs, crops, outs, full, window, filter, mirror, dtype, order, bottom_up, mean, std, scale, bias, results,
+                                      dict(color=color, post=post, warp=warp, tone=tone, enhance=enhance, alpha=alpha, resample=resample), layout, flags)
 
     def set_decode_verify(self, flags):
         """fpng_amd_encoder_set_decode_verify: every later decode call of this encoder also checks the files' IDAT CRC-32

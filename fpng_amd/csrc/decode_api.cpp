@@ -12,6 +12,7 @@
 #include "resize_hwc.h"
 #include "view_plan.h"
 #include "view_post.h"
+#include "view_request.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -1300,11 +1301,9 @@ const char *check_resample_record(const fpng_amd_view_resample &r)
     return nullptr;
 }
 static_assert(sizeof(fpng_amd_view_resample) == 16 && offsetof(fpng_amd_view_resample, flags) == 4 && offsetof(fpng_amd_view_resample, reserved) == 8, "fpng_amd_view_resample layout");
-struct StagesUsed {
-    bool post = false, warp = false, tone = false, enhance = false;
-    uint64_t total = 0; // the views of the call, where the counts are good
-};
-int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const ViewRequest &rq, const fpng_amd_decode_result *results, StagesUsed &used)
+// (StagesUsed, ViewDefaults and the three functions below: declared in view_request.h, which png_views_api.cpp judges its request through)
+} // namespace
+int fpng_amd::check_views_request(const fpng_amd_png_planar *files, uint32_t n, const ViewRequest &rq, const fpng_amd_decode_result *results, StagesUsed &used)
 {
     const char *const null_array = "null files, view_count, crops, views, dests or results";
     switch (rq.family) {
@@ -1378,11 +1377,7 @@ int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const View
 // kernel with all of a sample's planes in one thread can do and the per-plane kernel of the plain planar call cannot, so a planar
 // request with such a view and without matrices becomes the colour call's under identity matrices -- bit for bit the plain call's
 // elements, at the plain call's speed (profiles/views_color_timing.txt).  `made` keeps what is supplied here alive
-struct ViewDefaults {
-    std::vector<fpng_amd_view_post> posts;
-    std::vector<fpng_amd_view_color> colors;
-};
-ViewRequest normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults &made)
+ViewRequest fpng_amd::normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults &made)
 {
     const auto identity_colors = [&] {
         fpng_amd_view_color one = {};
@@ -1406,13 +1401,14 @@ ViewRequest normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults
     return rq;
 }
 
-int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const ViewRequest &asked)
+int fpng_amd::decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const ViewRequest &asked)
 {
     StagesUsed used;
     if (int rc = check_views_request(files, n, asked, results, used)) return rc;
     ViewDefaults made;
     return decode_files_planar(e, files, n, results, device_data, normalise_views(asked, used, made));
 }
+namespace {
 
 // ---- fpng_amd_decode_batch(_device)_yuv_views (the rule: yuv_store.h) ----
 static_assert(sizeof(fpng_amd_yuv_dest) == 40 && offsetof(fpng_amd_yuv_dest, chroma_offset) == 16 && offsetof(fpng_amd_yuv_dest, reserved) == 32 &&

@@ -200,8 +200,9 @@ struct fpng_amd_encoder {
     uint32_t lut_cache_n = 0;
     hipEvent_t dec_prof_ev[5] = {}; // profiling: around the decode kernels of the last call's first group of files
     bool dec_prof_recorded = false;
-    hipEvent_t png_ev[3] = {}; // fpng_amd_decode_batch(_device)_png with profiling on: around the two kernels of the call's first group
+    hipEvent_t png_ev[4] = {}; // fpng_amd_decode_batch(_device)_png with profiling on: around the two kernels of the call's first group
     bool png_ev_recorded = false;
+    bool png_ev_split = false; // (the png_views calls: the host works between the two kernels, and [3] is in front of the second)
     hipStream_t dec_up = nullptr; // ... the stream the files' bytes are uploaded on, one event per group of files
     hipEvent_t dec_ev[16] = {};
     hipEvent_t dec_ev2[16] = {}, dec_ev3[16] = {}; // the streamed fpng_amd_decode_host: a piece's byte count is known / its finished rows are pixels

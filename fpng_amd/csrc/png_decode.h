@@ -12,4 +12,11 @@ namespace fpng_amd {
 // and behind the two launches.
 void launch_png_decode(hipStream_t s, const pngi::File *files, pngi::State *states, uint32_t n, hipEvent_t *ev = nullptr);
 
+// The views call's two launches (png_views_api.cpp), between which the host reads the states: png_inflate_kernel alone, then
+// png_unfilter_box_kernel, which stores box i of file i -- inside the image, files[i].scan holding rows 0 .. y + h - 1 -- as planes
+// for the files whose status is 0 and sets the status of those whose visited scanlines are at fault.  boxes: a device array of n
+// records; those of files whose status is not 0 are not read.
+void launch_png_inflate(hipStream_t s, const pngi::File *files, pngi::State *states, uint32_t n);
+void launch_png_unfilter_box(hipStream_t s, const pngi::File *files, pngi::State *states, const pngi::Box *boxes, uint32_t n);
+
 } // namespace fpng_amd

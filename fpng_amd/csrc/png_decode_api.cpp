@@ -22,7 +22,7 @@ static_assert(pngi::kNotPng == fpng::FPNG_DECODE_FAILED_NOT_PNG && pngi::kHeader
                   pngi::kBadChunk == fpng::FPNG_DECODE_FAILED_CHUNK_PARSING && pngi::kBadIdat == fpng::FPNG_DECODE_FAILED_INVALID_IDAT &&
                   pngi::kUnsupported == FPNG_AMD_DECODE_UNSUPPORTED_PNG,
               "the tier's statuses are the public ones");
-static_assert(sizeof(pngi::File) == 56 && sizeof(pngi::State) == 32, "the kernels' records");
+static_assert(sizeof(pngi::File) == 64 && sizeof(pngi::State) == 32, "the kernels' records");
 
 constexpr uint32_t kPngHead = 64; // bytes of a device-resident file that come back: signature, IHDR, the next chunk's length and type
 constexpr size_t kDefaultScratchLimit = (size_t)1 << 30;
@@ -153,7 +153,7 @@ int decode_png(fpng_amd_encoder *e, const fpng_amd_png *files, uint32_t n, uint3
     }
     if ((rc = e->d_decode.ensure(need))) return rc;
     const bool prof = e->profiling;
-    e->png_ev_recorded = false;
+    e->png_ev_recorded = false, e->png_ev_split = false;
     if (prof)
         for (hipEvent_t &ev : e->png_ev)
             if (!ev) HIP_TRY(hipEventCreate(&ev));
@@ -220,6 +220,6 @@ extern "C" int fpng_amd_decode_png_last_kernel_ms(fpng_amd_encoder *e, float ms[
     if (!e->png_ev_recorded) return FPNG_AMD_OK;
     HIP_TRY(hipEventSynchronize(e->png_ev[2]));
     HIP_TRY(hipEventElapsedTime(&ms[0], e->png_ev[0], e->png_ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms[1], e->png_ev[1], e->png_ev[2]));
+    HIP_TRY(hipEventElapsedTime(&ms[1], e->png_ev[e->png_ev_split ? 3 : 1], e->png_ev[2]));
     return FPNG_AMD_OK;
 }

@@ -1,9 +1,11 @@
 // png_inflate_core.h -- the general decode tier's per-wave logic (png_inflate.hip, png_decode_api.cpp): ordinary PNG files, as
 // libpng, Pillow or zlib write them.  One 64-lane wave works on one file: pngi_inflate walks the chunks, inflates the zlib stream
 // that the IDAT chunks carry (RFC 1950 / 1951) into the file's filtered scanlines, pngi_unfilter undoes PNG filters 0-4 and
-// expands the pixels.  The same text compiles for the GPU (hipcc) and, with plain g++, for the host: there the wave's lanes run one
+// expands the pixels; pngi_unfilter_box does the same for the rows and pixels that a box of the image needs and stores the box as
+// tight uint8 planes, the layout the views stage reads (view_plan.h).  The same text compiles for the GPU (hipcc) and, with plain g++, for the host: there the wave's lanes run one
 // after the other inside PNGI_LANES, a value every lane holds (PngiLane<T>) is an array of 64, the wave operation (pngi_shift_up)
-// is a loop and the LDS arrays are plain arrays.  tests/cpp/png_inflate_host.cpp runs that form, under the sanitizers too.
+// is a loop and the LDS arrays are plain arrays.  tests/cpp/png_inflate_host.cpp and png_unfilter_box_host.cpp run that form, under
+// the sanitizers too.
 //
 // Rules of this tier (include/fpng_amd.h has the caller's view):
 //   * 8-bit grey, grey + alpha, RGB, palette, RGBA; no interlace; any number of consecutive IDAT chunks, empty ones included.
@@ -17,6 +19,11 @@
 //     code of a single-code table is no code: meeting it is INVALID_IDAT.
 //   * Chunk CRCs behind IHDR, the stream's Adler-32 and the presence of IEND are not checked.  The zlib window size is checked in
 //     the header only: distances are held against the output so far and 32768.
+//   * The box entry visits rows 0 .. y1 - 1 and of each row pixels 0 .. x1 - 1 (x1 = box.x + box.w, y1 = box.y + box.h): no predictor
+//     reads to the right of or below a pixel.  INVALID_IDAT is a filter byte above 4 in one of those rows, or a palette index at or
+//     behind PLTE's count at a pixel INSIDE the box; rows and pixels that are never visited cannot fail a file (the fpng tier's crop
+//     calls have the same property), nor can a palette index outside the box.  The stream is inflated and checked to its end all
+//     the same, and refused if it yields fewer than h * (1 + bytes per row) bytes: File::need_bytes.
 //   * Every loop ends because it consumes input bits or file bytes, or produces output bytes: the file has at most 2^32 bytes, a
 //     token at least one bit and at most 258 output bytes.  No workgroup waits for another one.
 #pragma once
@@ -74,14 +81,21 @@ PNGI_FN void pngi_shift_up(PngiLane<uint32_t> &dst, PngiLane<uint32_t> &src, uin
 
 struct File {             // one file of a launch
     const uint8_t *data;  // the whole .png
-    uint8_t *scan;        // scratch: scan_bytes, the filtered scanlines
-    uint8_t *out;         // w * h * dst_c bytes
-    uint64_t scan_bytes;  // h * (1 + w * bpp)
+    uint8_t *scan;        // scratch: scan_bytes, the filtered scanlines that are kept
+    uint8_t *out;         // w * h * dst_c bytes (pngi_unfilter)
+    uint64_t scan_bytes;  // rows * (1 + w * bpp): the image's h rows, or the y1 rows a box needs
     uint32_t size;
     uint32_t w, h;
     uint32_t color;       // IHDR colour type: 0, 2, 3, 4, 6
     uint32_t bpp;         // bytes per pixel in the file: 1, 3, 1, 2, 4
     uint32_t dst_c;       // 3 or 4
+    uint64_t need_bytes;  // what the stream must yield at least, h * (1 + w * bpp); 0: scan_bytes (every row is kept)
+};
+struct Box {              // pngi_unfilter_box: what is stored of a file
+    uint8_t *planes;      // n_planes tight planes of w x h bytes: pitch w, plane pitch w * h
+    uint32_t x, y, w, h;  // inside the image, not empty
+    uint32_t n_planes;    // 3 or 4 (R, G, B[, A])
+    uint32_t pad_;
 };
 struct State {            // what pngi_inflate leaves for pngi_unfilter and the host
     uint32_t status;
@@ -538,7 +552,7 @@ PNGI_FN uint32_t pngi_stream(InflateShared &sh, const File &f, Reader &r)
         }
     } while (!final_block);
     if (pngi_overrun(r)) return kBadIdat;
-    if (out < f.scan_bytes) return kBadIdat;
+    if (out < (f.need_bytes ? f.need_bytes : f.scan_bytes)) return kBadIdat;
     return kOk;
 }
 
@@ -582,14 +596,30 @@ PNGI_FN void pngi_store_pixel(uint8_t *out, uint64_t index, uint32_t dst_c, uint
     if (dst_c == 4) p[3] = (uint8_t)(rgba >> 24);
 }
 
+// the box's store step: the pixel at p of the first plane gets R, G, B[, A] of rgba, a byte per plane (plane: box.w * box.h, at
+// most 2^30 -- check_ihdr)
+PNGI_FN void pngi_store_box(uint8_t *p, uint32_t plane, uint32_t n_planes, uint32_t rgba)
+{
+    p[0] = (uint8_t)rgba, p[plane] = (uint8_t)(rgba >> 8), p[2 * (uint64_t)plane] = (uint8_t)(rgba >> 16);
+    if (n_planes == 4) p[3 * (uint64_t)plane] = (uint8_t)(rgba >> 24);
+}
+
 // Bands of 64 rows: lane k works on row y0 + k and, at step t, on its pixel t - k.  Its left neighbour is its own last value, the
 // pixel above is the last value of lane k - 1 and the one above to the left that lane's value a step earlier: pngi_shift_up hands
 // them down, no reconstructed byte goes through memory inside a band.  The band's last row is written back over its filtered
 // bytes in the scanlines (all of them staged by then), where the next band's lane 0 finds it.
-PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &st)
+// The ONE walk of both entries.  kBox = false: the whole image, w x h, into f.out (box is not read).  kBox = true: rows 0 .. h - 1
+// and pixels 0 .. w - 1 with w = box.x + box.w and h = box.y + box.h -- bands, tiles, staging and the write-back of lane 63's row
+// end there -- and the pixels inside the box into its planes.  The scanlines' stride is the file's in both.
+// (The box's place is read once per band, into what each lane keeps of its row -- where the row starts in the first plane and its
+//  first pixel inside the box, none for a row above the box -- so the kernel, which hands `box` in as the record in device memory,
+//  holds none of it in scalar registers across the steps: that is what keeps it free of spills.  A row's bytes, x1 * bpp and
+//  w * bpp + 1 <= 2^26 + 1, are 32-bit products in the box entry for the same reason.)
+template <bool kBox> PNGI_FN uint32_t pngi_unfilter_walk(UnfilterShared &sh, const File &f, const State &st, const Box &box)
 {
-    const uint32_t bpp = f.bpp, w = f.w, h = f.h, row_bytes = kTileSteps * bpp, pitch = row_bytes + 4;
-    const uint64_t stride = (uint64_t)w * bpp + 1;
+    const uint32_t bpp = f.bpp, w = kBox ? box.x + box.w : f.w, h = kBox ? box.y + box.h : f.h, row_bytes = kTileSteps * bpp, pitch = row_bytes + 4;
+    const uint64_t stride = kBox ? (uint64_t)(f.w * bpp + 1u) : (uint64_t)f.w * bpp + 1, row_end = kBox ? (uint64_t)(w * bpp) : stride - 1; // (row_end: the bytes of a row that are visited)
+    const uint32_t plane = kBox ? box.w * box.h : 0u, n_planes = kBox ? box.n_planes : 0u;
     // palette, colour key
     // (the key's samples are 16-bit numbers; of an 8-bit file Pillow compares their low bytes, and so does this)
     uint32_t key = 0; // (alpha 0: no opaque pixel equals it)
@@ -611,7 +641,8 @@ PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &s
                 sh.pal[i] = v;
             }
     }
-    PngiLane<uint32_t> last, up, ft, bad;
+    PngiLane<uint32_t> last, up, ft, bad, x_min; // (x_min: the row's first pixel inside the box, UINT32_MAX: none)
+    PngiLane<uint8_t *> box_row;                 // (... and where that pixel lies in the first plane)
     PNGI_LANES(lane) bad[lane] = 0;
     for (uint32_t y0 = 0; y0 < h; y0 += kBandRows) { // ends: h / 64 bands
         PNGI_SYNC(); // (the band above has stored its last row)
@@ -621,6 +652,11 @@ PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &s
             uint32_t t = y < h ? f.scan[y * stride] : 0;
             if (t > 4) bad[lane] = 1, t = 0;
             ft[lane] = t, last[lane] = 0, up[lane] = 0;
+            if (kBox) {
+                const bool in = y >= box.y && y < h;
+                x_min[lane] = in ? box.x : UINT32_MAX;
+                box_row[lane] = in ? box.planes + (uint64_t)(y - box.y) * box.w : nullptr;
+            }
         }
         const uint32_t rows = h - y0 < kBandRows ? h - y0 : kBandRows, steps = w + rows - 1;
         for (uint32_t t0 = 0; t0 < steps; t0 += kTileSteps) { // ends: (w + 63) / 64 tiles
@@ -631,7 +667,7 @@ PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &s
                 {
                     for (uint32_t i = lane; i < row_bytes; i += kWave) {
                         const int64_t at = ((int64_t)t0 - r) * bpp + i; // byte of the row
-                        sh.tile[r * pitch + i] = at >= 0 && at < (int64_t)stride - 1 ? row[at] : 0;
+                        sh.tile[r * pitch + i] = at >= 0 && at < (int64_t)row_end ? row[at] : 0;
                     }
                 }
             }
@@ -639,7 +675,7 @@ PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &s
             {
                 for (uint32_t i = lane; i < row_bytes; i += kWave) {
                     const uint64_t at = (uint64_t)t0 * bpp + i;
-                    sh.above[i] = y0 && at < stride - 1 ? f.scan[(y0 - 1) * stride + 1 + at] : 0;
+                    sh.above[i] = y0 && at < row_end ? f.scan[(y0 - 1) * stride + 1 + at] : 0;
                 }
             }
             PNGI_SYNC();
@@ -673,9 +709,11 @@ PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &s
                     else if (f.color == 4) rgba = (cur & 255) * 0x010101u | ((cur >> 8) << 24);
                     else {
                         rgba = sh.pal[cur & 255];
-                        if ((cur & 255) >= st.plte_n) bad[lane] = 1;
+                        // (the box entry: a palette index outside the box fails no file)
+                        if ((cur & 255) >= st.plte_n && (!kBox || x >= x_min[lane])) bad[lane] = 1;
                     }
-                    pngi_store_pixel(f.out, (uint64_t)y * w + x, f.dst_c, rgba);
+                    if (!kBox) pngi_store_pixel(f.out, (uint64_t)y * w + x, f.dst_c, rgba);
+                    else if (x >= x_min[lane]) pngi_store_box(box_row[lane] + (x - x_min[lane]), plane, n_planes, rgba);
                 }
             }
         }
@@ -687,6 +725,19 @@ PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &s
     }
     PNGI_SYNC();
     return sh.bad ? (uint32_t)kBadIdat : (uint32_t)kOk;
+}
+
+// the whole image, interleaved: w * h * dst_c bytes at f.out
+PNGI_FN uint32_t pngi_unfilter(UnfilterShared &sh, const File &f, const State &st)
+{
+    const Box none = {};
+    return pngi_unfilter_walk<false>(sh, f, st, none);
+}
+
+// a box of the image as planes (the rules: this file's header).  f.scan holds rows 0 .. box.y + box.h - 1 and no more
+PNGI_FN uint32_t pngi_unfilter_box(UnfilterShared &sh, const File &f, const State &st, const Box &box)
+{
+    return pngi_unfilter_walk<true>(sh, f, st, box);
 }
 
 } // namespace pngi

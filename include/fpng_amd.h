@@ -1326,6 +1326,64 @@ int fpng_amd_resample_weights(uint32_t in_size, uint32_t out_size, uint32_t resa
 /* fpng_amd_resize_view_source under a RESAMPLE record (filter 0: that function's answer): the box of the file that the view's
  * taps reach.  The records are judged as the calls judge them */
 int fpng_amd_resample_view_source(const fpng_amd_crop *crop, const fpng_amd_resize_view *view, const fpng_amd_view_resample *resample, fpng_amd_crop *box);
+/* ---- views of ORDINARY PNG files: the general tier (fpng_amd_decode_batch_png above) feeds the views stage.  One call for every
+ *      views family: the request record carries what the {planar,hwc}_views calls and their _color .. _resample siblings take as
+ *      arguments, and is judged as the call would judge it whose last array is the last stage array given here (colors < posts <
+ *      warps < tones < enhances < alphas < resamples; none: the plain views call) -- same rules, same order, same messages.
+ *      In front of them: a NULL request, reserved != 0, flags other than FPNG_AMD_PNG_GENERAL_ONLY, and dests and hwc both given
+ *      or both NULL are FPNG_AMD_ERR_INVALID_ARG.  `files` are used as the views calls use them: data, size and num_chans 3 or 4,
+ *      the destination fields empty.
+ *      Routing as in the png calls: one fetch of the heads; a file with fpng's marker goes through the existing views call of the
+ *      request's family, its views bit for bit that call's; what that path answers with FPNG_DECODE_NOT_FPNG or
+ *      FPNG_AMD_DECODE_UNDECIDED, every unmarked file, and under FPNG_AMD_PNG_GENERAL_ONLY every file goes through the general
+ *      tier.  There the stream is inflated and checked to its end, but only the rows that the file's ONE box needs (that of
+ *      fpng_amd_views_source; rows 0 .. box.y + box.h - 1) are kept, and png_unfilter_box_kernel reconstructs of them pixels
+ *      0 .. box.x + box.w - 1 and stores the box as tight uint8 planes in the scratch, which the views stage reads exactly as it
+ *      reads an fpng file's.  The views are therefore those of the existing calls on an fpng file with the same pixels.
+ *      Which files have an alpha plane (a 4-channel file to the views stage: the alpha records act on it, num_chans = 4 gives its
+ *      alpha as fourth plane): colour types 4 and 6, palette with a non-empty tRNS, grey with a tRNS of at least 2 bytes, RGB with
+ *      one of at least 6 -- the files fpng_amd_decode_batch_png at 4 channels can give an alpha below 255.  Every other file is a
+ *      3-channel file; num_chans = 4 gives it a fourth plane of 255.  channels_in_file in the results is what the png calls report.
+ *      Status per file: the png calls', with two differences.  A filter byte above 4 counts in rows 0 .. box.y + box.h - 1 and a
+ *      palette index at or behind PLTE's count at a pixel inside the box: rows and pixels the kernel never visits cannot fail a
+ *      file (the fpng tier's crop calls have the same property).  And the crop rule of the views calls -- the crop of ANY of
+ *      the file's views leaves the image, judged on the caller's crops -- is reported as FPNG_AMD_DECODE_PNG_CROP_OUTSIDE (68),
+ *      also for the files of the fpng path, whose 67 is translated: 67 from these calls always means UNSUPPORTED_PNG.  They never
+ *      return UNDECIDED.  A file whose status is not 0 gets no job: none of its views is written.
+ *      A refused call launches nothing: the IHDRs, the boxes, the crops and every destination's pitches and room
+ *      (FPNG_AMD_ERR_BUFFER_TOO_SMALL) are judged for every file from the heads and the request, before the first kernel of the
+ *      general tier runs.
+ *      Device scratch, per general-tier file: its kept scanlines, for host-resident files their bytes, and its share of the views
+ *      stage's scratch (the box's planes, the post views' windows, the tone views' histograms and tables); above
+ *      FPNG_AMD_PNG_SCRATCH_LIMIT the files run in groups (a file that alone exceeds it is a group of its own), each with one more
+ *      stream synchronisation between the inflate kernel and the box kernel, where the host learns of tRNS.
+ *      fpng_amd_decode_png_last_kernel_ms reports the first group's inflate and box kernels for these calls too.
+ *      Out of scope: YUV destinations; the calls with one view per file (_planar, _planar_float, _planar_crop, _planar_resize,
+ *      _planar_resize_view) for ordinary files; 16-bit, 1/2/4-bit and interlaced files, which stay UNSUPPORTED_PNG; the speed of
+ *      png_inflate_kernel, which these calls use as it is.
+ *      Added after ABI version 5 without changing it: look for fpng_amd_decode_batch_png_views with dlsym. ---- */
+#define FPNG_AMD_DECODE_PNG_CROP_OUTSIDE 68 /* per-file status of the png_views calls: a crop of the file leaves the image */
+typedef struct fpng_amd_png_views {      /* every array: one record per view, sum(view_count) of them, in the files' order */
+    const uint32_t *view_count;                /* n, each >= 1 */
+    const fpng_amd_crop *crops;
+    const fpng_amd_resize_view *views;
+    const fpng_amd_view_dest *dests;           /* planar destinations, or ...            */
+    const fpng_amd_view_dest_hwc *hwc;         /* ... channels-last ones: exactly one set */
+    const fpng_amd_float_format *fmt;          /* NULL: uint8 */
+    const fpng_amd_view_color *colors;         /* the stage arrays: each NULL or given */
+    const fpng_amd_view_post *posts;
+    const fpng_amd_view_warp *warps;
+    const fpng_amd_view_tone *tones;
+    const fpng_amd_view_enhance *enhances;
+    const fpng_amd_view_alpha *alphas;
+    const fpng_amd_view_resample *resamples;
+    uint32_t flags;                            /* FPNG_AMD_PNG_GENERAL_ONLY */
+    uint32_t reserved;                         /* 0 */
+} fpng_amd_png_views;                    /* 112 bytes */
+int fpng_amd_decode_batch_png_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_png_views *rq,
+                                    fpng_amd_decode_result *results /* n: one per FILE */);
+int fpng_amd_decode_batch_device_png_views(fpng_amd_encoder *enc, const fpng_amd_png_planar *files, uint32_t n, const fpng_amd_png_views *rq,
+                                           fpng_amd_decode_result *results);
 /* ---- encoding FROM planar images of floats (f32, f16 or bf16) -- the twin of the float decode: what a caller otherwise does with
  *      x.mul(std).add(mean).mul(255).round().clamp(0, 255).to(uint8) and fpng_amd_encode_submit_planar, inside the row walk that
  *      reads the pixels; no uint8 image is written in between.  For plane c (the file's channel c: R, G, B, A = 0 .. 3, wherever

@@ -17,9 +17,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libfpng_amd.so")
 DROPIN_LIB = os.path.join(LIB_DIR, "libfpng.so")
-SOURCES = ["kernels.hip", "decode.hip", "resize.hip", "resize_color.hip", "view_post.hip", "view_tone.hip", "yuv_store.hip", "encode_resize.hip", "png_inflate.hip", "api.cpp", "pipeline.cpp", "sharded.cpp", "decode_api.cpp", "png_decode_api.cpp", "png_views_api.cpp", "format.cpp", "synth.cpp"]
+SOURCES = ["kernels.hip", "decode.hip", "resize.hip", "resize_color.hip", "view_post.hip", "view_tone.hip", "yuv_store.hip", "encode_resize.hip", "png_inflate.hip", "api.cpp", "pipeline.cpp", "sharded.cpp", "decode_api.cpp", "png_tier.cpp", "png_decode_api.cpp", "png_views_api.cpp", "format.cpp", "synth.cpp"]
 HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "format.h"), os.path.join(CSRC, "encoder.h"), os.path.join(CSRC, "decode.h"), os.path.join(CSRC, "decode_core.h"), os.path.join(CSRC, "dec_unfilter_body.inc"), os.path.join(CSRC, "crc_device.h"), os.path.join(CSRC, "host_workers.h"), os.path.join(CSRC, "png_parse.h"),
-           os.path.join(CSRC, "lanes.h"), os.path.join(CSRC, "quantize.h"), os.path.join(CSRC, "pack.h"), os.path.join(CSRC, "crc_geometry.h"), os.path.join(CSRC, "resize.h"), os.path.join(CSRC, "resize_hwc.h"), os.path.join(CSRC, "resize_color.h"), os.path.join(CSRC, "view_post.h"), os.path.join(CSRC, "view_plan.h"), os.path.join(CSRC, "view_warp.h"), os.path.join(CSRC, "view_tone.h"), os.path.join(CSRC, "view_enhance.h"), os.path.join(CSRC, "view_alpha.h"), os.path.join(CSRC, "float_store.h"), os.path.join(CSRC, "exact_grid.h"), os.path.join(CSRC, "resize_tile.h"), os.path.join(CSRC, "encode_resize.h"), os.path.join(CSRC, "yuv.h"), os.path.join(CSRC, "yuv_store.h"), os.path.join(CSRC, "png_inflate_core.h"), os.path.join(CSRC, "png_decode.h"), os.path.join(CSRC, "view_request.h"), os.path.join(CSRC, "png_views_gather.h"), os.path.join(ROOT, "include", "fpng_amd.h")]
+           os.path.join(CSRC, "lanes.h"), os.path.join(CSRC, "quantize.h"), os.path.join(CSRC, "pack.h"), os.path.join(CSRC, "crc_geometry.h"), os.path.join(CSRC, "resize.h"), os.path.join(CSRC, "resize_hwc.h"), os.path.join(CSRC, "resize_color.h"), os.path.join(CSRC, "view_post.h"), os.path.join(CSRC, "view_plan.h"), os.path.join(CSRC, "view_warp.h"), os.path.join(CSRC, "view_tone.h"), os.path.join(CSRC, "view_enhance.h"), os.path.join(CSRC, "view_alpha.h"), os.path.join(CSRC, "float_store.h"), os.path.join(CSRC, "exact_grid.h"), os.path.join(CSRC, "resize_tile.h"), os.path.join(CSRC, "encode_resize.h"), os.path.join(CSRC, "yuv.h"), os.path.join(CSRC, "yuv_store.h"), os.path.join(CSRC, "png_inflate_core.h"), os.path.join(CSRC, "png_decode.h"), os.path.join(CSRC, "view_request.h"), os.path.join(CSRC, "png_views_gather.h"), os.path.join(CSRC, "png_tier_plan.h"), os.path.join(CSRC, "png_tier.h"), os.path.join(ROOT, "include", "fpng_amd.h")]
 ARCH = "gfx950"
 
 

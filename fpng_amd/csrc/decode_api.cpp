@@ -7,6 +7,7 @@
 #include "encoder.h"
 #include "host_workers.h"
 #include "png_parse.h"
+#include "png_tier_plan.h"
 #include "resize.h"
 #include "resize_color.h"
 #include "resize_hwc.h"
@@ -256,7 +257,7 @@ struct DecArrays { // the device arrays both decode paths work on (seg: dec_unfi
 // subsequences in whole workgroups); each path carves its own tail behind them, then calls place().
 struct Scratch {
     size_t need = 0, z, win, info, bytes, rel, last, eob, tok, recs, boff, win_words, gran_words;
-    size_t carve(size_t n) { const size_t o = need; need += (n + 255) & ~(size_t)255; return o; }
+    size_t carve(size_t n) { const size_t o = need; need += align256(n); return o; }
     Scratch(size_t z_bytes, size_t win_words_, size_t subs, size_t gran_words_)
     {
         subs = std::max<size_t>(subs, 1), win_words = std::max<size_t>(win_words_, 1), gran_words = std::max<size_t>(gran_words_, 1);
@@ -377,7 +378,7 @@ int parse_files(Batch &b)
     using namespace fpng::parse;
     fpng_amd_encoder *e = b.e;
     if (b.device_data) { // their first and last bytes come back first (one round trip for the batch)
-        const size_t per = kHeadBytes + kTailBytes, refs = ((size_t)b.n * sizeof(DecFileRef) + 255) & ~(size_t)255;
+        const size_t per = kHeadBytes + kTailBytes, refs = align256((size_t)b.n * sizeof(DecFileRef));
         int rc;
         if ((rc = e->h_dec_fetch.ensure((size_t)b.n * per + refs)) || (rc = e->d_decode.ensure((size_t)b.n * per + refs))) return rc;
         DecFileRef *h_refs = (DecFileRef *)(e->h_dec_fetch.p + (size_t)b.n * per);
@@ -1210,16 +1211,9 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
     if (!e || !files || !n || !results) return fail(FPNG_AMD_ERR_INVALID_ARG, "null/empty batch");
     for (uint32_t i = 0; rq.crops && !rq.view_count && i < n; i++)
         if (!rq.crops[i].w || !rq.crops[i].h) return fail(FPNG_AMD_ERR_INVALID_ARG, "an empty crop (w or h is 0)");
-    DecFloat flt = {}; // (views: their entry points have judged them -- check_resize_records / check_view_records)
-    uint32_t elem = 1;
-    if (const fpng_amd_float_format *fmt = rq.fmt) {
-        if (fmt->dtype >= kDecFloatTypes) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown element type (FPNG_AMD_F32, _F16, _BF16)");
-        if (fmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_float_format::reserved must be 0");
-        for (int c = 0; c < 4; c++)
-            if (!std::isfinite(fmt->scale[c]) || !std::isfinite(fmt->bias[c])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
-        flt.dtype = fmt->dtype, elem = dec_float_bytes(fmt->dtype);
-        std::memcpy(flt.scale, fmt->scale, sizeof flt.scale), std::memcpy(flt.bias, fmt->bias, sizeof flt.bias);
-    }
+    DecFloat flt; // (views: their entry points have judged them -- check_resize_records / check_view_records)
+    uint32_t elem;
+    if (int rc = check_float_format(rq.fmt, flt, elem)) return rc;
     std::vector<fpng_amd_png> plain(n);
     for (uint32_t i = 0; i < n; i++) {
         const fpng_amd_png_planar &x = files[i];
@@ -1231,17 +1225,7 @@ int decode_files_planar(fpng_amd_encoder *e, const fpng_amd_png_planar *files, u
     }
     uint64_t n_views = 0;
     for (uint32_t i = 0; rq.view_count && i < n; i++) n_views += rq.view_count[i];
-    for (uint64_t v = 0; rq.hwc && v < n_views; v++) { // (a channels-last destination's twins of the two rules below)
-        const fpng_amd_view_dest_hwc &x = rq.hwc[v];
-        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch) & (elem - 1)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels and row_pitch must be multiples of the element size");
-        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
-    }
-    for (uint64_t v = 0; rq.dests && v < n_views; v++) { // (the same two rules for every view's destination)
-        const fpng_amd_view_dest &x = rq.dests[v];
-        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (elem - 1))
-            return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
-        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
-    }
+    if (int rc = check_view_dests(rq, n_views, elem)) return rc;
     return decode_files(e, plain.data(), n, 0, results, device_data, nullptr, files, rq.fmt ? &flt : nullptr, rq);
 }
 // fpng_amd_decode_batch(_device)_planar_views: what needs no file, no encoder and no device is judged first, as in the view call
@@ -1301,8 +1285,36 @@ const char *check_resample_record(const fpng_amd_view_resample &r)
     return nullptr;
 }
 static_assert(sizeof(fpng_amd_view_resample) == 16 && offsetof(fpng_amd_view_resample, flags) == 4 && offsetof(fpng_amd_view_resample, reserved) == 8, "fpng_amd_view_resample layout");
-// (StagesUsed, ViewDefaults and the three functions below: declared in view_request.h, which png_views_api.cpp judges its request through)
+// (StagesUsed, ViewDefaults and the functions below: declared in view_request.h, which png_views_api.cpp judges its request through)
 } // namespace
+
+int fpng_amd::check_float_format(const fpng_amd_float_format *fmt, DecFloat &flt, uint32_t &elem)
+{
+    flt = {}, elem = 1;
+    if (!fmt) return FPNG_AMD_OK;
+    if (fmt->dtype >= kDecFloatTypes) return fail(FPNG_AMD_ERR_INVALID_ARG, "unknown element type (FPNG_AMD_F32, _F16, _BF16)");
+    if (fmt->reserved) return fail(FPNG_AMD_ERR_INVALID_ARG, "fpng_amd_float_format::reserved must be 0");
+    for (int c = 0; c < 4; c++)
+        if (!std::isfinite(fmt->scale[c]) || !std::isfinite(fmt->bias[c])) return fail(FPNG_AMD_ERR_INVALID_ARG, "scale and bias must be finite");
+    flt.dtype = fmt->dtype, elem = dec_float_bytes(fmt->dtype);
+    std::memcpy(flt.scale, fmt->scale, sizeof flt.scale), std::memcpy(flt.bias, fmt->bias, sizeof flt.bias);
+    return FPNG_AMD_OK;
+}
+int fpng_amd::check_view_dests(const ViewRequest &rq, uint64_t n_views, uint32_t elem)
+{
+    for (uint64_t v = 0; rq.hwc && v < n_views; v++) { // (a channels-last destination's twins of the two rules below)
+        const fpng_amd_view_dest_hwc &x = rq.hwc[v];
+        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch) & (elem - 1)) return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels and row_pitch must be multiples of the element size");
+        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
+    }
+    for (uint64_t v = 0; rq.dests && v < n_views; v++) { // (a file's own destination words, for every view's destination: decode_files_planar)
+        const fpng_amd_view_dest &x = rq.dests[v];
+        if (((uintptr_t)x.d_pixels | (uint64_t)x.row_pitch | (uint64_t)x.plane_pitch) & (elem - 1))
+            return fail(FPNG_AMD_ERR_INVALID_ARG, "d_pixels, row_pitch and plane_pitch must be multiples of the element size");
+        if (x.row_pitch <= -(int64_t)0x80000000ll || x.row_pitch >= (int64_t)0x80000000ll) return fail(FPNG_AMD_ERR_INVALID_ARG, "|row_pitch| >= 2^31");
+    }
+    return FPNG_AMD_OK;
+}
 int fpng_amd::check_views_request(const fpng_amd_png_planar *files, uint32_t n, const ViewRequest &rq, const fpng_amd_decode_result *results, StagesUsed &used)
 {
     const char *const null_array = "null files, view_count, crops, views, dests or results";

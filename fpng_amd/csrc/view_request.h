@@ -24,6 +24,11 @@ struct ViewDefaults {
 int check_views_request(const fpng_amd_png_planar *files, uint32_t n, const ViewRequest &rq, const fpng_amd_decode_result *results, StagesUsed &used);
 // THE normalisation rule of the views calls
 ViewRequest normalise_views(ViewRequest rq, const StagesUsed &used, ViewDefaults &made);
+// The words that the planar family judges behind the encoder (decode_files_planar), for it and for the views of ordinary PNG files.
+// fmt (or NULL: uint8, elem 1) -> flt, and elem, the bytes of an element
+int check_float_format(const fpng_amd_float_format *fmt, DecFloat &flt, uint32_t &elem);
+// every view's destination, hwc's then dests': whole elements, |row_pitch| < 2^31
+int check_view_dests(const ViewRequest &rq, uint64_t n_views, uint32_t elem);
 // fpng-written files through the views call of asked.family
 int decode_files_views(fpng_amd_encoder *e, const fpng_amd_png_planar *files, uint32_t n, fpng_amd_decode_result *results, bool device_data, const ViewRequest &asked);
 

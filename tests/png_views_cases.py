@@ -1,7 +1,8 @@
 """What the GPU tests of the PNG views call share (test_gpu_decode_png_views.py): ordinary files written by Pillow, the views of a
 file, the oracle -- decode_device_png of the file, those pixels through the fpng encoder, that file through the existing views calls
--- and one runner for both.  Run as a program it is the groups test's child: the routing batch in one group, then with
-FPNG_AMD_PNG_SCRATCH_LIMIT set in this fresh process to a file per group, and the two compared."""
+-- and one runner for both.  Run as a program it is the groups tests' child: the routing batch in one group, then with
+FPNG_AMD_PNG_SCRATCH_LIMIT set in this fresh process to a file per group, and the two compared; with the argument "two" a small
+mixed batch in one group and in exactly two, the file that the fpng path leaves UNDECIDED in the second."""
 import functools
 import io
 import os
@@ -209,6 +210,96 @@ def _child():
     print("OK", ok)
 
 
+BPP = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+UNDECIDED = 64
+
+
+def small_views(w, h):
+    """three_views for files from 80 x 48 up"""
+    return [((5, 7, w - 10, h - 12), (56, 28), None, "bilinear", False),
+            ((64, 32, 16, 16), (40, 40), None, "bilinear", False),
+            ((0, 0, w, h), (w // 2, h // 2), (10, 8, 32, 24), "bicubic", True)]
+
+
+def two_groups_batch(enc):
+    """(names, files, views): files of 129 x 65 -- written by the fpng encoder, by Pillow, a marked file that the fpng path answers
+    NOT_FPNG -- and tests/golden/first_pixel_match.png (65 x 16, RGBA), which it leaves UNDECIDED"""
+    import torch
+    import fpng_amd
+    w, h = 129, 65
+    fpng_files = []
+    for k, c in enumerate((3, 4)):
+        (png,), _ = enc.encode_tensors([torch.from_numpy(fpng_amd.synth_image(("grad", "blocks")[k], w, h, c)).cuda()], 0)
+        fpng_files.append(bytes(png))
+    marked = bytearray(fpng_files[0])  # (routing_batch's)
+    assert marked[37:41] == b"fdEC" and marked[45] == 0
+    marked[45] = 1
+    marked[46:50] = struct.pack(">I", zlib.crc32(bytes(marked[37:46])))
+    golden = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "first_pixel_match.png"), "rb").read()
+    assert dims(golden) == (65, 16)
+    batch = [("fpng_rgb", fpng_files[0], small_views(w, h)),
+             ("pillow_rgb", pillow_file("rgb", w, h, 21), small_views(w, h)),
+             ("marked_not_fpng", bytes(marked), small_views(w, h)[:1]),
+             ("fpng_rgba", fpng_files[1], small_views(w, h)[:2]),
+             ("pillow_palette_trns", pillow_file("palette_trns", w, h, 22), small_views(w, h)),
+             ("first_pixel_match", golden, [((0, 0, 65, 16), (32, 8), None, "bilinear", False), ((40, 4, 16, 8), (24, 12), None, "bicubic", True)]),
+             ("pillow_grey_alpha", pillow_file("grey_alpha", w, h, 23), small_views(w, h))]
+    return [b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch]
+
+
+def tier_need(file, views):
+    """what a device-resident file of the general tier counts against FPNG_AMD_PNG_SCRATCH_LIMIT in the png_views calls, when no view
+    has a post stage (the environment table; fpng_amd/csrc/png_tier_plan.h: png_groups): the scanlines it keeps, down
+    to the last row of its box, rounded up to 256, and its share of the plan's scratch, the box's planes at 4 channels plus 256"""
+    import fpng_amd
+    w, _ = dims(file)
+    _, by, bw, bh = fpng_amd.views_source([v[0] for v in views], [v[1] for v in views], [v[2] for v in views], [v[3] for v in views])
+    up = lambda n, a: (n + a - 1) // a * a  # noqa: E731
+    return up((by + bh) * (1 + w * BPP[file[25]]), 256) + up(up(bw * bh * 4, 16) + 256, 256)
+
+
+def groups_of(needs, limit):
+    """[g0, g1) of every group: a file joins while the sum stays at or under the limit; a file that alone exceeds it is a group of its own"""
+    out, start, room = [], 0, 0
+    for i, need in enumerate(needs):
+        if i != start and room + need > limit:
+            out.append((start, i))
+            start, room = i, 0
+        room += need
+    return out + ([(start, len(needs))] if needs else [])
+
+
+def _child_two_groups():
+    """the small mixed batch, routed (flags 0): one group against exactly two with the UNDECIDED file in the second; prints OK or fails"""
+    import torch
+    import fpng_amd
+    enc = fpng_amd.Encoder(device=0)
+    names, files, views = two_groups_batch(enc)
+    chans = [3] * len(files)
+    fast = {"fpng_rgb", "fpng_rgba", "marked_not_fpng", "first_pixel_match"}
+    for name, f in zip(names, files):
+        assert (f[37:41] == b"fdEC") == (name in fast), name
+    # the tier takes the files routed to it at once, in the call's order, then what the fpng path left, in the call's order
+    order = [n for n in names if n not in fast] + ["marked_not_fpng", "first_pixel_match"]
+    needs = [tier_need(files[names.index(n)], views[names.index(n)]) for n in order]
+    limit = sum(needs[:3])  # (the three files routed at once fill the first group exactly: a sum equal to the limit joins)
+    assert groups_of(needs, limit) == [(0, 3), (3, 5)] and groups_of(needs, 1 << 30) == [(0, 5)], (needs, limit)
+    assert groups_of(needs, limit - 1)[0] == (0, 2)
+    k = names.index("first_pixel_match")
+    (st, _, _), = run(enc, [files[k]], [views[k]], [3], torch.uint8, "planar", png=False)[0]
+    assert st == UNDECIDED, st
+    one = snapshot(*run(enc, files, views, chans, torch.uint8, "planar"))
+    os.environ["FPNG_AMD_PNG_SCRATCH_LIMIT"] = str(limit)
+    two = snapshot(*run(enc, files, views, chans, torch.uint8, "planar"))
+    assert [a[0] for a in one] == [0] * len(files), [a[0] for a in one]
+    for name, a, b in zip(names, one, two):
+        assert a[0] == b[0] and a[1] == b[1], (name, a[0], b[0])
+        for x, y in zip(a[2], b[2]):
+            assert np.array_equal(x, y) and not (x == PATTERN).all(), name
+    enc.close()
+    print("OK", limit)
+
+
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    _child()
+    _child_two_groups() if sys.argv[1:] == ["two"] else _child()

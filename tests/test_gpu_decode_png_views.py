@@ -164,6 +164,16 @@ def test_groups_give_the_same_elements():
     assert r.returncode == 0 and r.stdout.strip().startswith("OK"), (r.stdout[-500:], r.stderr[-3000:])
 
 
+def test_two_groups_with_the_undecided_file_in_the_second():
+    """a mixed batch of files of at most 129 x 65, routed, with FPNG_AMD_PNG_SCRATCH_LIMIT computed from the per-file terms so that
+    exactly two groups form and the fpng-written file that the fpng path leaves UNDECIDED (tests/golden/first_pixel_match.png) comes
+    to the tier behind the files routed at once, in the second group: the statuses and elements of the one-group run"""
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.path.join(ROOT, "tests"))
+    env.pop("FPNG_AMD_PNG_SCRATCH_LIMIT", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "png_views_cases.py"), "two"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().startswith("OK"), (r.stdout[-500:], r.stderr[-3000:])
+
+
 def test_host_resident_files_equal_the_device_form(enc):
     import torch
     names, files, views, want = V.routing_batch(enc)
